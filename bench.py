@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- decode tokens/s of Llama-3-8B int4 g=64, batch 1, on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one decode step (one token) through InferenceEngine.generate_step: hipGraph replay of the fused
@@ -22,6 +22,9 @@ Prints ONE JSON line on rank 0 with the driver's contract plus:
   tp70b        -- only with --gpus N > 1 on the default workload: after the replicas' timing the same ranks decode ONE Llama-3-70B int4
                   sequence tensor-parallel (BASELINE.json configs[4]), once per communicator backend (IPC one-shot, RCCL); `value` stays
                   the replicas figure.
+  dump_outputs -- with --dump-outputs DIR: what the last timed step returned to its caller (rank 0's token id and logprobs[V]),
+                  written as DIR/token.npy (float64) and DIR/logprobs.npy (float32).  Weights and prompt are seeded, so the same
+                  arguments give the same inputs on every run and two builds can be compared output for output.
   repetitions  -- 5 repetitions of the K timed steps (the first is `value`): median and min ms per step.
   cpu_baseline -- the CPU oracle (oracle/pie_oracle.c, OpenMP) timed on this box's host cores on a bounded sample, at the GPU run's
                   context (the same 128-token prompt).
@@ -67,7 +70,24 @@ def parse():
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE", help="developer: one of the library's test / tuning switches (_ffi.KNOBS) for this run")
     ap.add_argument("--bits", type=int, choices=[2, 4, 6, 8], default=4, help="8 / 6 / 2: MLX int8 / int6 / int2 g=64 weights (W8S / W6S / W2S units; a different workload than the metric's)")
     ap.add_argument("--dense", action="store_true", help="BASELINE.json configs[2]: unquantised bf16 weights (a different workload than the metric's)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "(token id, logprobs) as DIR/<name>.npy in float64 / float32")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, last):
+    """Writes the (token id, logprobs) pair the caller of generate_step received in the last timed step; returns the file names."""
+    tok, logprobs = last
+    arrays = {"token": tok.detach().reshape(-1).to(torch.float64).cpu().numpy(),
+              "logprobs": logprobs.detach().reshape(-1).to(torch.float32).cpu().numpy()}
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "files": {f"{name}.npy": list(a.shape) for name, a in arrays.items()}}
 
 
 def _err_eps(got, ref):
@@ -294,9 +314,12 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        next(gen)
+        last = next(gen)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    # copied to the host before anything else runs on the device: the step's output buffers are reused by later steps
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
+    del last
     launches_per_step = model.graph_launches(True)  # kernel nodes of the captured step graph (hipGraphGetNodes), not a formula
     # 5 repetitions, median and min.  `value` stays the driver's contract (the K steps just timed); four more repetitions of
     # the same K steps from the same prompt (the prefix cache makes the re-prefill one token) are reported beside it.
@@ -409,6 +432,7 @@ def main():
                      "stream_peak": stream_gbps, "frac_of_stream": k_gbps / stream_gbps,  # measured in this run: pie_stream_read over 1 GiB
                      "step": {"achieved": step_gbps, "frac": step_gbps / HBM_PEAK_GBPS, "frac_of_stream": step_gbps / stream_gbps, "bytes_per_step": step_bytes,
                               "floor": floor}},
+        "dump_outputs": dumped,
         "repetitions": {"ms_per_step": rep_ms, "median_ms_per_step": float(np.median(rep_ms)), "min_ms_per_step": float(np.min(rep_ms))},
     }
     if world > 1 and not tp and args.model == "8b" and args.bits == 4 and not args.dense and not args.layers and not args.paged \

@@ -2,6 +2,8 @@
 // with -fsanitize=thread).  The three scenarios are the reference's concurrency cases
 // (tests/cpp/test_page_allocator.cpp:206-330), restated against the C ABI; rounds are repeated so the tagged free-list
 // head sees many recycles of the same indices (the ABA pattern).
+#include <sched.h>
+
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -143,12 +145,19 @@ static void push_pop_stress(size_t n_threads, size_t ops) {
     pie_page_pool_destroy(p);
 }
 
+// CPUs this process may run on (hardware_concurrency counts the whole host)
+static size_t usable_cpus() {
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof(set), &set) == 0) return static_cast<size_t>(CPU_COUNT(&set));
+    return std::thread::hardware_concurrency();
+}
+
 int main() {
-    const size_t hw = std::max(4u, std::thread::hardware_concurrency());
+    const size_t hw = std::max<size_t>(4, usable_cpus());
     for (int round = 0; round < 5; ++round) {
         producers_consumer(hw);
         free_shared_page();
-        push_pop_stress(hw, 20000);
+        push_pop_stress(std::min<size_t>(hw, 128 / 4), 20000);  // every thread starts with 4 of the 128 pages
     }
     std::puts("ok");
     return 0;

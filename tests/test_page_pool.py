@@ -17,6 +17,11 @@ DEFAULT_NUM_HEADS, DEFAULT_HEAD_DIM = 4, 16                                   # 
 LARGE_POOL_SIZE, SMALL_POOL_SIZE, TINY_POOL_SIZE, SINGLE_PAGE_POOL = 1024, 10, 4, 1   # :22-25
 
 
+def usable_cpus():
+    """CPUs this process may run on (the reference uses hardware_concurrency, which counts the whole host)."""
+    return len(os.sched_getaffinity(0))
+
+
 def make_allocator(pages):
     return PageAllocator(pages, DEFAULT_NUM_HEADS, DEFAULT_HEAD_DIM)
 
@@ -185,7 +190,7 @@ def _run(threads):
 
 
 def test_concurrent_alloc_free_producers_consumer():                         # :206-254
-    num_threads = max(2, os.cpu_count() or 2)
+    num_threads = max(2, usable_cpus())
     num_producers = num_threads - 1
     pages_per_p = LARGE_POOL_SIZE // num_producers
     total = pages_per_p * num_producers
@@ -230,7 +235,7 @@ def test_concurrent_free_shared_page():                                      # :
 
 def test_high_contention_push_pop_stress():                                  # :282-330
     num_pages, ops_per_thr, pages_per_thread = 128, 2000, 4
-    num_threads = max(4, os.cpu_count() or 4)
+    num_threads = min(max(4, usable_cpus()), num_pages // pages_per_thread)  # every thread starts with its own pages
     alloc = make_allocator(num_pages)
     local = [allocate_pages(alloc, pages_per_thread) for _ in range(num_threads)]
 
