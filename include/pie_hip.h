@@ -493,6 +493,29 @@ int pie_paged_attn_decode_i8(const void *q, const void *slab, size_t n_pages, co
                              const int32_t *context_lens, int B, int n_heads, int n_kv_heads, int head_dim, float scale, int dtype,
                              void *out, void *workspace, void *stream);
 
+/* ---------------------------------------------------------------- quantized KV cache (QuantizedKVCache, cache/kv_cache/quantized.py)
+ * The reference's format: every cached row stored as mx.quantize output -- codes uint32 [n_kv_heads, capacity, head_dim*bits/32],
+ * scales / biases T [n_kv_heads, capacity, head_dim/group_size] (B = 1).  bits 4 / 8, group_size 32 / 64 / 128 dividing head_dim,
+ * head_dim 64 / 128, T bf16 / f16; anything else is PIE_E_ARG / PIE_E_SHAPE before a launch.
+ * pie_kv_quantize: rows [0, n) of every head of x T [H, src_cap, head_dim] -> the same rows of codes / scales / biases [H, dst_cap, ...];
+ *   bit-identical with mx.quantize (cache/kv_cache/cache.py:144-147, quantized.py:91-96).
+ * pie_attn_decode_quant: quantized_scaled_dot_product_attention (models/base.py:56-89) for one query row: q, out T [n_heads, head_dim],
+ *   the first T positions of the cache attended; queries *= scale and the scores rounded to T as there, softmax and the value
+ *   product in fp32, one rounding of the output.  workspace: pie_sdpa_decode_workspace_bytes(n_heads, head_dim) bytes.
+ * pie_decoder_set_kv_quant: the quantized alternative to pie_decoder_set_kv -- HOST arrays [n_layers] of the layers' six device buffers.
+ *   Steps append the new K / V rows quantized (the attention launch quantizes the row its q|k|v launch staged) and attend the cache
+ *   as pie_attn_decode_quant does.  Prompts (pie_decoder_prefill / _prefill_embeds) take the batched pass over a T scratch of one layer's
+ *   K / V, dequantized from the codes, with the chunk's rows quantized into the cache before its attention.  Refused (PIE_E_STATE) on
+ *   tensor-parallel decoders. */
+int pie_kv_quantize(const void *x, int H, int n, int src_cap, int head_dim, int group_size, int bits, int dtype, void *codes, void *scales,
+                    void *biases, int dst_cap, void *stream);
+int pie_attn_decode_quant(const void *q, const void *k_codes, const void *k_scales, const void *k_biases, const void *v_codes,
+                          const void *v_scales, const void *v_biases, int n_heads, int n_kv_heads, int T, int cap, int head_dim,
+                          int group_size, int bits, float scale, int dtype, void *out, void *workspace, void *stream);
+int pie_decoder_set_kv_quant(pie_decoder *d, const void *const *k_codes, const void *const *k_scales, const void *const *k_biases,
+                             const void *const *v_codes, const void *const *v_scales, const void *const *v_biases, int capacity,
+                             int group_size, int bits, void *stream);
+
 /* ---------------------------------------------------------------- vision tower ops
  * Call sites: models/intern/vision.py (Qwen2.5-VL vision tower: PatchEmbed :87-121, Attention :143-186, MLP :189-197,
  * PatchMerger :124-140).  RMSNorm, SiLU * up and the residual adds are pie_rms_norm / pie_silu_mul / pie_add.

@@ -39,6 +39,7 @@ EXPORTS = [
     "pie_w16m_bytes", "pie_repack_w16m", "pie_linear_w16m_workspace", "pie_linear_w16m", "pie_gelu", "pie_vision_qkv_rope", "pie_sdpa_segments", "pie_bias_silu_mul", "pie_add_bias", "pie_add_bias_rms_norm",
     "pie_w4m_bytes", "pie_repack_w4s_to_w4m", "pie_qgemm_w4m",
     "pie_comm_create", "pie_comm_rccl_unique_id", "pie_comm_create_rccl", "pie_comm_export", "pie_comm_connect", "pie_allreduce_f32", "pie_comm_status", "pie_comm_destroy", "pie_decoder_set_comm", "pie_sample", "pie_sample_workspace_bytes",
+    "pie_kv_quantize", "pie_attn_decode_quant", "pie_decoder_set_kv_quant",
 ]
 
 
@@ -94,6 +95,9 @@ def load() -> C.CDLL:
     for name in ("pie_w4s_bytes", "pie_w16s_bytes", "pie_w8s_bytes", "pie_w4s32_bytes", "pie_w8s32_bytes", "pie_w2s_bytes", "pie_w6s_bytes", "pie_sdpa_decode_workspace_bytes", "pie_decoder_step_bytes", "pie_decoder_kernel_bytes"):
         getattr(lib, name).restype = C.c_size_t
     lib.pie_sdpa_decode.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pie_kv_quantize.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+    lib.pie_attn_decode_quant.argtypes = [C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pie_decoder_set_kv_quant.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6 + [C.c_int] * 3 + [C.c_void_p]
     lib.pie_sdpa_prefill.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_rms_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_silu_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]

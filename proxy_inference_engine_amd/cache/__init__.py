@@ -1,4 +1,4 @@
-from .kv_cache import BaseCache, ReusableKVCache
+from .kv_cache import BaseCache, QuantizedKVCache, ReusableKVCache
 from .prompt_cache import PromptCache
 
-__all__ = ["BaseCache", "ReusableKVCache", "PromptCache"]
+__all__ = ["BaseCache", "ReusableKVCache", "QuantizedKVCache", "PromptCache"]

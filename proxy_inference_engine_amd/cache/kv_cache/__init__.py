@@ -24,12 +24,22 @@ class BaseCache(ABC):
     # -- persistence (cache/kv_cache/__init__.py:163-210): one .safetensors file, arrays named by their position in the
     # nested [layer][keys|values] list ("3.0" = layer 3 keys), metadata flattened the same way:
     # "0.<i>" = meta_state of layer i, "1.<key>" = the caller's metadata, "2.<i>" = cache class name of layer i.
+    # A QuantizedKVCache layer's state and meta_state are nested one level deeper, as tree_flatten names them: arrays
+    # "<i>.<0 keys | 1 values>.<0 codes | 1 scales | 2 biases>", meta "0.<i>.<0 step | 1 offset | 2 group_size | 3 bits>".
     @staticmethod
     def save_cache(file_name: str, cache: list["BaseCache"], metadata: dict[str, str] | None = None) -> None:
         from safetensors.torch import save_file
         arrays: dict[str, torch.Tensor] = {}
         meta: dict[str, str] = {}
         for i, c in enumerate(cache):
+            if isinstance(c, QuantizedKVCache):
+                for j, triple in enumerate(c.state):
+                    for k, t in enumerate(triple or ()):
+                        arrays[f"{i}.{j}.{k}"] = t.detach().to("cpu").contiguous()
+                for k, v in enumerate(c.meta_state):
+                    meta[f"0.{i}.{k}"] = v
+                meta[f"2.{i}"] = type(c).__name__
+                continue
             for j, t in enumerate(c.state):
                 if t is not None:
                     arrays[f"{i}.{j}"] = t.detach().to("cpu").contiguous()
@@ -45,7 +55,7 @@ class BaseCache(ABC):
         from safetensors import safe_open
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        classes = {"ReusableKVCache": ReusableKVCache}
+        classes = {"ReusableKVCache": ReusableKVCache, "QuantizedKVCache": QuantizedKVCache}
         with safe_open(file_name, framework="pt", device="cpu") as f:
             meta = f.metadata() or {}
             n = sum(1 for k in meta if k.startswith("2."))
@@ -55,6 +65,13 @@ class BaseCache(ABC):
                 if name not in classes:
                     raise ValueError(f"{file_name}: cache class {name} is not on the MI355X path")
                 c = classes[name]()
+                if isinstance(c, QuantizedKVCache):
+                    keys = f.keys()
+                    if f"{i}.0.0" in keys:
+                        c.state = tuple(tuple(f.get_tensor(f"{i}.{j}.{k}").to(device) for k in range(3)) for j in range(2))
+                    c.meta_state = tuple(meta[f"0.{i}.{k}"] for k in range(4))
+                    cache.append(c)
+                    continue
                 state = tuple(f.get_tensor(f"{i}.{j}").to(device) if f"{i}.{j}" in f.keys() else None for j in range(2))
                 c.state = state
                 c.meta_state = meta.get(f"0.{i}", "")
@@ -94,5 +111,6 @@ class BaseCache(ABC):
 
 from .reusable import ReusableKVCache  # noqa: E402
 from .paged import PageAllocator, PagedKVCache, PagedSequence  # noqa: E402
+from .quantized import QuantizedKVCache  # noqa: E402
 
-__all__ = ["BaseCache", "ReusableKVCache", "PagedKVCache", "PagedSequence", "PageAllocator"]
+__all__ = ["BaseCache", "ReusableKVCache", "QuantizedKVCache", "PagedKVCache", "PagedSequence", "PageAllocator"]

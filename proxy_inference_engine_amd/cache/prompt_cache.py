@@ -20,7 +20,7 @@ import torch
 
 logger = logging.getLogger(__name__)
 
-from .kv_cache import BaseCache, PagedKVCache, ReusableKVCache
+from .kv_cache import BaseCache, PagedKVCache, QuantizedKVCache, ReusableKVCache
 
 
 def _as_list(ids) -> list[int]:
@@ -80,7 +80,7 @@ class PromptCache:
         if common == 0:
             return prompt_ids
         for layer_cache in self.cache:
-            assert isinstance(layer_cache, (ReusableKVCache, PagedKVCache))
+            assert isinstance(layer_cache, (ReusableKVCache, QuantizedKVCache, PagedKVCache))
             layer_cache.reuse(len(ids), common)
         # DEVIATION from prompt_cache.py:52-76, which leaves computed_ids untouched here: after a diverging request B the
         # reference's history reads A + B[k:] while the KV rows beyond k belong to B, so a later request that matches A beyond k

@@ -118,7 +118,7 @@ static bool fuse_attn(const pie_decoder *d, int li) {
     const pie_decoder_config &c = d->cfg;
     if (pie_knob(PIE_KNOB_FUSE_ATTN) == 0 || !d->xcd_ok || !d->seam || g_live_decoders.load() > 4) return false;
     (void)li;  // (any weight format of the q|k|v matrix)
-    return !d->tp() && !d->combine && !(d->kv_i8 && d->block_table) && c.n_heads == 32 && c.n_kv_heads == 8 && c.head_dim == 128 && c.hidden <= 4096 &&
+    return !d->tp() && !d->combine && !(d->kv_i8 && d->block_table) && !d->kv_quant && c.n_heads == 32 && c.n_kv_heads == 8 && c.head_dim == 128 && c.hidden <= 4096 &&
            d->splits >= 1 && d->splits <= 4;
 }
 
@@ -175,7 +175,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
             a.lin_bias = (const u16 *)w.bqkv, a.rope_traditional = c.rope_traditional;
             a.block_table = d->block_table, a.n_pages = d->n_pages;
             const bool i8 = d->kv_i8 && d->block_table;  // int8 pages: the T rows go to the staging page, then get quantised into the sequence's page
-            if (i8) a.kv_table = d->kv_table_stage, a.block_table = d->zero_table, a.n_pages = 1;
+            if (i8 || d->kv_quant) a.kv_table = d->kv_table_stage, a.block_table = d->zero_table, a.n_pages = 1;
             a.prof = reinterpret_cast<unsigned long long *>(d->pf_sink) + PROF_QKV;
             if (embed_here) {  // the step's embedding launch folded into this one (embed_in_qkv): x = the token's row, dequantised by every workgroup
                 a.x = nullptr, a.rope_cs = nullptr, a.rope_cs_out = d->rope_cs, a.h_out = d->h, a.token = token_ptr;
@@ -198,6 +198,15 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
                 a.splits = splits < 1 ? 1 : (splits > ATTN_MAX_SPLITS ? ATTN_MAX_SPLITS : splits);
                 a.part_acc = d->part_acc, a.part_ml = d->part_ml, a.out = d->attn;
                 return paged_attn_i8_launch(c.dtype, D, a, st);  // merges its splits itself (k_attn_combine): o_proj reads d->attn
+            }
+            if (d->kv_quant) {  // quantized KV: the launch first quantises the staged rows into the cache, then scores the codes
+                const void *const *p = &d->kvq_host[(size_t)6 * li];
+                QAttnArgs a = {};
+                a.q = d->qbuf, a.kc = (const u32 *)p[0], a.ks = (const u16 *)p[1], a.kb = (const u16 *)p[2];
+                a.vc = (const u32 *)p[3], a.vs = (const u16 *)p[4], a.vb = (const u16 *)p[5];
+                a.state = d->state, a.gs = d->kvq_gs, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.splits = d->splits, a.scale = 1.0f / sqrtf((float)D);
+                a.part_acc = d->part_acc, a.part_ml = d->part_ml, a.stage = d->kv_stage;
+                return attn_decode_quant_launch(c.dtype, D, d->kvq_bits, a, d->combine, d->attn, st);  // short caches: merged by the o_proj prologue
             }
             if (fuse_attn(d, li)) return PIE_OK;  // ran behind the q|k|v launch's seam
             AttnArgs a = attn_args(d, li);
@@ -349,7 +358,7 @@ int pie_decoder_destroy(pie_decoder *d) {
     drop_graphs(d);
     prefill_free(d);
     void *ptrs[] = {d->state, d->kv_table, d->qbuf, d->attn, d->act, d->part_acc, d->part_ml, d->stats, d->rope_cs, d->pf_sink, d->seam, d->tp_part, d->kv_stage, d->kv_table_stage,
-                    d->zero_table};
+                    d->zero_table, d->kvq_scratch, d->kvq_table};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete d;
@@ -420,9 +429,66 @@ int pie_decoder_set_kv(pie_decoder *d, const void *const *k_ptrs, const void *co
     PIE_LAUNCH_CHECK();
     d->kv_set = true;
     d->kv_cap = capacity;
-    const bool was_paged = d->block_table != nullptr;
+    const bool was_paged = d->block_table != nullptr, was_quant = d->kv_quant;
+    d->block_table = nullptr, d->n_pages = 0, d->kv_quant = false;
+    if (plan_attention(d) || was_paged || was_quant) drop_graphs(d);  // the launch sequence changed: captured graphs are stale
+    return PIE_OK;
+}
+
+// The staging page of the q|k|v epilogue (int8 pages, quantized KV): K block then V block [n_kv_heads, 64, head_dim] T, the table that points
+// every layer at it, and a block table of `blocks` zeros (position p -> page 0, row p % 64).
+static int ensure_staging(pie_decoder *d, int blocks) {
+    const int L = d->cfg.n_layers;
+    const size_t v_off = (size_t)d->cfg.n_kv_heads * PIE_PAGE_TOKENS * d->cfg.head_dim * 2;
+    if (!d->kv_stage) {
+        PIE_HIP_TRY(hipMalloc((void **)&d->kv_stage, 2 * v_off));
+        PIE_HIP_TRY(hipMemset(d->kv_stage, 0, 2 * v_off));
+        PIE_HIP_TRY(hipMalloc((void **)&d->kv_table_stage, sizeof(unsigned long long) * 2 * L));
+        std::vector<unsigned long long> stab(2 * (size_t)L);
+        for (int i = 0; i < L; ++i) stab[i] = (unsigned long long)(uintptr_t)d->kv_stage, stab[L + i] = stab[i] + v_off;
+        PIE_HIP_TRY(hipMemcpy(d->kv_table_stage, stab.data(), stab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    }
+    if (d->zero_blocks < blocks) {
+        if (d->zero_table) (void)hipFree(d->zero_table);
+        d->zero_table = nullptr, d->zero_blocks = 0;
+        PIE_HIP_TRY(hipMalloc((void **)&d->zero_table, sizeof(int) * (size_t)blocks));
+        PIE_HIP_TRY(hipMemset(d->zero_table, 0, sizeof(int) * (size_t)blocks));
+        d->zero_blocks = blocks;
+        drop_graphs(d);  // the table's address is a launch argument
+    }
+    return PIE_OK;
+}
+
+int pie_decoder_set_kv_quant(pie_decoder *d, const void *const *k_codes, const void *const *k_scales, const void *const *k_biases,
+                             const void *const *v_codes, const void *const *v_scales, const void *const *v_biases, int capacity, int group_size,
+                             int bits, void *stream) {
+    PIE_REQUIRE(d && k_codes && k_scales && k_biases && v_codes && v_scales && v_biases, PIE_E_ARG, "pie_decoder_set_kv_quant: null pointer");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_kv_quant: a quantized KV cache is not available on a tensor-parallel decoder");
+    if (int rc = kv_quant_check("pie_decoder_set_kv_quant", d->cfg.dtype, d->cfg.head_dim, group_size, bits)) return rc;
+    const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
+    PIE_REQUIRE(rep == 1 || rep == 2 || rep == 4 || rep == 8, PIE_E_SHAPE, "pie_decoder_set_kv_quant: n_heads / n_kv_heads must be 1, 2, 4 or 8");
+    PIE_REQUIRE(capacity > 0 && capacity <= (1 << 30), PIE_E_SHAPE, "pie_decoder_set_kv_quant: capacity must be positive");
+    const int L = d->cfg.n_layers;
+    std::vector<const void *> host((size_t)6 * L);
+    for (int i = 0; i < L; ++i) {
+        const void *p[6] = {k_codes[i], k_scales[i], k_biases[i], v_codes[i], v_scales[i], v_biases[i]};
+        for (int j = 0; j < 6; ++j) {
+            PIE_REQUIRE(p[j] && pie_aligned(p[j], j % 3 == 0 ? 8 : 2), PIE_E_ALIGN, "pie_decoder_set_kv_quant: null or misaligned cache buffer");
+            host[(size_t)6 * i + j] = p[j];
+        }
+    }
+    int rc = ensure_staging(d, (capacity + PIE_PAGE_TOKENS - 1) / PIE_PAGE_TOKENS);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, st, d->state, -1, -1, capacity);
+    PIE_LAUNCH_CHECK();
+    // the buffers, group and width are arguments of the attention launches: a captured graph is stale when any of them changes
+    const bool changed = !d->kv_quant || d->kvq_host != host || d->kvq_gs != group_size || d->kvq_bits != bits || d->block_table != nullptr;
+    d->kvq_host = std::move(host), d->kvq_gs = group_size, d->kvq_bits = bits, d->kv_quant = true;
     d->block_table = nullptr, d->n_pages = 0;
-    if (plan_attention(d) || was_paged) drop_graphs(d);  // the launch sequence changed: captured graphs are stale
+    d->kv_set = true;
+    d->kv_cap = capacity;
+    if (plan_attention(d) || changed) drop_graphs(d);
     return PIE_OK;
 }
 
@@ -446,22 +512,8 @@ int pie_decoder_set_paged_kv(pie_decoder *d, const void *const *slabs, size_t n_
     d->slab_host.assign(slabs, slabs + L);
     hipStream_t st = (hipStream_t)stream;
     if (d->kv_i8) {  // int8 pages (PIE_OPT_KV_I8): the staging page, the table that points every layer at it, and a block table of zeros
-        if (!d->kv_stage) {
-            PIE_HIP_TRY(hipMalloc((void **)&d->kv_stage, 2 * v_off));
-            PIE_HIP_TRY(hipMemset(d->kv_stage, 0, 2 * v_off));
-            PIE_HIP_TRY(hipMalloc((void **)&d->kv_table_stage, sizeof(unsigned long long) * 2 * L));
-            std::vector<unsigned long long> stab(2 * (size_t)L);
-            for (int i = 0; i < L; ++i) stab[i] = (unsigned long long)(uintptr_t)d->kv_stage, stab[L + i] = stab[i] + v_off;
-            PIE_HIP_TRY(hipMemcpy(d->kv_table_stage, stab.data(), stab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        }
-        if (d->zero_blocks < max_blocks) {
-            if (d->zero_table) (void)hipFree(d->zero_table);
-            d->zero_table = nullptr, d->zero_blocks = 0;
-            PIE_HIP_TRY(hipMalloc((void **)&d->zero_table, sizeof(int) * (size_t)max_blocks));
-            PIE_HIP_TRY(hipMemset(d->zero_table, 0, sizeof(int) * (size_t)max_blocks));
-            d->zero_blocks = max_blocks;
-            drop_graphs(d);  // the table's address is a launch argument
-        }
+        const int rc = ensure_staging(d, max_blocks);
+        if (rc) return rc;
     }
     const bool blocks_changed = d->max_blocks != max_blocks;
     d->max_blocks = max_blocks;
@@ -472,8 +524,8 @@ int pie_decoder_set_paged_kv(pie_decoder *d, const void *const *slabs, size_t n_
     d->kv_set = true;
     d->kv_cap = capacity;
     // kernel arguments are baked into captured graphs: a new table pointer or pool size invalidates them
-    const bool changed = d->block_table != block_table || d->n_pages != (int)n_pages || blocks_changed || (d->kv_i8 && slabs_changed);
-    d->block_table = block_table, d->n_pages = (int)n_pages;
+    const bool changed = d->block_table != block_table || d->n_pages != (int)n_pages || blocks_changed || (d->kv_i8 && slabs_changed) || d->kv_quant;
+    d->block_table = block_table, d->n_pages = (int)n_pages, d->kv_quant = false;
     if (plan_attention(d) || changed) drop_graphs(d);
     return PIE_OK;
 }

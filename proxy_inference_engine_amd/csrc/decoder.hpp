@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "attention.hpp"
+#include "kv_quant.hpp"
 #include "tail.hpp"
 #include "w4_gemv.hpp"
 
@@ -47,6 +48,16 @@ struct pie_decoder {
     int *zero_table = nullptr;                     // [zero_blocks] zeros
     int zero_blocks = 0, max_blocks = 0;
     std::vector<const void *> slab_host;           // the layers' slab bases (host copy of kv_table's first half)
+    // quantized KV (pie_decoder_set_kv_quant): the layers' K codes / scales / biases, V codes / scales / biases ([6 * n_layers], launch arguments of
+    // the attention launch); the q|k|v epilogue stages the new T rows as for int8 pages and the attention launch quantizes them into the cache
+    bool kv_quant = false;
+    int kvq_gs = 0, kvq_bits = 0;
+    std::vector<const void *> kvq_host;
+    // the prompt pass on a quantized cache (prefill.hip): one layer's K and V as T [n_kv, kvq_scratch_cap, D] each, and a pointer table
+    // [2 * n_layers] that points every layer at them
+    u16 *kvq_scratch = nullptr;
+    unsigned long long *kvq_table = nullptr;
+    int kvq_scratch_cap = 0;
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     bool graph_fused[2] = {false, false};           // the captured graph holds the fused q|k|v + attention launch (re-captured when fusion is withdrawn)

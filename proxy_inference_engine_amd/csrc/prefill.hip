@@ -729,6 +729,24 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
     return rc;
 }
 
+// Quantized KV (pie_decoder_set_kv_quant): the T scratch of one layer's K and V at the cache's capacity and the table that points every layer at it.
+static int kvq_scratch_reserve(pie_decoder *d) {
+    const pie_decoder_config &c = d->cfg;
+    if (!d->kvq_table) {
+        PIE_HIP_TRY(hipMalloc((void **)&d->kvq_table, sizeof(unsigned long long) * 2 * c.n_layers));
+    }
+    if (d->kvq_scratch_cap == d->kv_cap && d->kvq_scratch) return PIE_OK;  // (rows are kv_cap apart: the layout follows the cache's capacity)
+    if (d->kvq_scratch) (void)hipFree(d->kvq_scratch);
+    d->kvq_scratch = nullptr, d->kvq_scratch_cap = 0;
+    const size_t half = (size_t)c.n_kv_heads * d->kv_cap * c.head_dim;
+    PIE_HIP_TRY(hipMalloc((void **)&d->kvq_scratch, 2 * half * 2));
+    d->kvq_scratch_cap = d->kv_cap;
+    std::vector<unsigned long long> tab(2 * (size_t)c.n_layers);
+    for (int i = 0; i < c.n_layers; ++i) tab[i] = (unsigned long long)(uintptr_t)d->kvq_scratch, tab[c.n_layers + i] = tab[i] + half * 2;
+    PIE_HIP_TRY(hipMemcpy(d->kvq_table, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    return PIE_OK;
+}
+
 template <class T>
 static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int L, void *logits_all, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
@@ -741,6 +759,17 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
     int rc = scratch_reserve(d, chunk, w_elems, d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
+    // quantized KV: the pass runs on the T scratch (kv_table below), the layer's codes are expanded into it and the chunk's rows quantized back
+    unsigned long long *kv_table = d->kv_table;
+    if (d->kv_quant) {
+        if ((rc = kvq_scratch_reserve(d))) return rc;
+        kv_table = d->kvq_table;
+    }
+    u16 *const sk = d->kvq_scratch, *const sv = d->kvq_scratch ? d->kvq_scratch + (size_t)c.n_kv_heads * d->kvq_scratch_cap * D : nullptr;
+    auto kvq_layer = [d](int li) {
+        const void *const *p = &d->kvq_host[(size_t)6 * li];
+        return QKvLayer{(const u32 *)p[0], (const u16 *)p[1], (const u16 *)p[2], (const u32 *)p[3], (const u16 *)p[4], (const u16 *)p[5]};
+    };
     const bool mfma_attn = pie_knob(PIE_KNOB_PREFILL_ATTN_VALU) != 1;  // 1 forces the row-per-launch-slice VALU kernel (tests compare the two)
     for (int c0 = 0; c0 < L; c0 += chunk) {
         const int M = L - c0 < chunk ? L - c0 : chunk;
@@ -761,7 +790,9 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             // Attention.__call__ (language.py:75-108) on input_layernorm(x)
             // input_layernorm: layer 0 here; for the later layers it was fused with the previous block's residual add
             if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
-            W4mRope re = {s->rope_cs, d->state, nullptr, d->kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
+            if (d->kv_quant && (rc = kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, true, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st)))
+                return rc;
+            W4mRope re = {s->rope_cs, d->state, nullptr, kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
                           c.rope_traditional, s->q, nullptr, 0};
             bool roped = false;
             W4lSlabs sq, so, sd;  // K-split products handed over as fp32 slabs (q|k|v only without a bias: RoPE takes T(x W^T + b))
@@ -771,20 +802,22 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
                 const unsigned row_wgs = sq.S > 1 ? (M < 512 ? 4u : 1u) : 1u;  // few rows of slabs: four workgroups per row (256 tokens: 6.03 vs 6.20 ms; from 512 rows no difference)
                 decltype(&k_rope_append_rows<T, false, false>) rope_k = &k_rope_append_rows<T, false, false>;
                 if (sq.S > 1) rope_k = &k_rope_append_rows<T, true, false>;
-                hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, d->state, d->kv_table, li,
+                hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, d->state, kv_table, li,
                                    c.n_layers, c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, d->block_table, d->n_pages, s->rope_cs, (const int *)nullptr, 0,
                                    (u16 *)nullptr, (const int *)nullptr, (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, (size_t)0);
                 PIE_LAUNCH_CHECK();
             }
+            if (d->kv_quant && (rc = kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, false, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st)))
+                return rc;
             if (mfma_attn) {  // causal flash attention on the MFMA units (prefill_attn.hpp)
                 PrefillAttnArgs pa = {};
-                pa.q = s->q, pa.kv_table = d->kv_table, pa.layer = li, pa.n_layers = c.n_layers, pa.state = d->state;
+                pa.q = s->q, pa.kv_table = kv_table, pa.layer = li, pa.n_layers = c.n_layers, pa.state = d->state;
                 pa.block_table = d->block_table, pa.n_pages = d->n_pages;
                 pa.M = M, pa.Hq = c.n_heads, pa.Hkv = c.n_kv_heads, pa.scale = 1.0f / sqrtf((float)D), pa.out = s->attn;
                 if ((rc = prefill_attn_launch_t<T>(pa, D, st))) return rc;
             } else {  // PIE_KNOB_PREFILL_ATTN_VALU = 1: the VALU decode kernel, one query row per blockIdx.z (cross-check for the tests)
                 AttnArgs a = {};
-                a.q = s->q, a.kv_table = d->kv_table, a.layer = li, a.n_layers = c.n_layers, a.state = d->state;
+                a.q = s->q, a.kv_table = kv_table, a.layer = li, a.n_layers = c.n_layers, a.state = d->state;
                 a.block_table = d->block_table, a.n_pages = d->n_pages, a.bt_stride = 0;  // every row reads the one sequence's table
                 a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.splits = d->splits, a.rows = M, a.scale = 1.0f / sqrtf((float)D);
                 a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;

@@ -15,7 +15,9 @@ from collections.abc import Callable, Generator, Iterator
 import torch
 
 from .. import hip_ops
-from ..cache import PromptCache
+from ..cache import PromptCache, QuantizedKVCache, ReusableKVCache
+from ..cache.kv_cache import PagedKVCache
+from ..cache.kv_cache.quantized import check_format as check_kv_format
 from ..logits_processors import repetition_penalty_logits_processor
 from ..models import load
 from ..samplers import make_sampler
@@ -96,10 +98,16 @@ class InferenceEngine:
         return prompt_ids
 
     # ------------------------------------------------------------------ the hot loop
-    def generate_step(self, prompt_ids, pixel_values=None, mask=None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
+    def generate_step(self, prompt_ids, pixel_values=None, mask=None, kv_bits: int | None = None, kv_group_size: int = 64,
+                      quantized_kv_start: int = 0) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
         """Yields (next_token_id[1] int32, logprobs[V] fp32) per step, forever (inference_engine.py:228-297).
         Prefill of the non-cached prompt suffix, then one forward per token; all device work is queued
-        asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202)."""
+        asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202).
+        kv_bits (4 / 8; None = 16-bit KV), kv_group_size, quantized_kv_start: mlx_lm's KV quantization -- before a model call the
+        prompt cache's layers become QuantizedKVCache once they hold more than quantized_kv_start positions (BaseCache.maybe_quantize,
+        cache/kv_cache/__init__.py:240-266)."""
+        if kv_bits is not None:
+            check_kv_format(kv_group_size, kv_bits)
         if mask is not None and not (isinstance(mask, str) and mask == "causal"):
             check_generate_mask(mask, getattr(getattr(self.model, "args", None), "num_attention_heads", None))
         if pixel_values is not None and not hasattr(self.model, "get_input_embeddings"):
@@ -118,6 +126,8 @@ class InferenceEngine:
                     state = "root"
             sampler = self.samplers[state]
             procs = self.logits_processors.get(state) or []
+            if kv_bits is not None:
+                self._maybe_quantize(quantized_kv_start, kv_group_size, kv_bits)
             if pixel_values is not None and not fed_back:
                 # the prompt of a VLM request (:246-252): text embeddings with the image features scattered in, through the
                 # text tower.  The reference passes pixel_values on every later step too, where a single new token holds
@@ -169,6 +179,15 @@ class InferenceEngine:
             yield next_token, logprobs
             step_count += 1
 
+    def _maybe_quantize(self, quantized_start: int, group_size: int, bits: int) -> None:
+        """BaseCache.maybe_quantize (cache/kv_cache/__init__.py:240-266) on the prompt cache's layers."""
+        cache = self.prompt_cache.cache
+        if cache and isinstance(cache[0], PagedKVCache):
+            raise ValueError("kv_bits: the quantized KV cache runs on contiguous caches, not on KV pages")
+        if cache and isinstance(cache[0], ReusableKVCache) and cache[0].offset > quantized_start:
+            for i in range(len(cache)):
+                cache[i] = QuantizedKVCache.from_cache(cache[i], group_size=group_size, bits=bits)
+
     def generate(self, prompt_ids, **inference_kwargs) -> Generator[ModelOutput, None, str]:
         """Stop-token / max_completion_tokens loop (inference_engine.py:175-226).  Yields (token_id, logprobs_map);
         the generator's return value is the stop reason ("stop" | "length" | "tool_calls")."""
@@ -178,7 +197,8 @@ class InferenceEngine:
         logprobs_map: dict[int, float] = {}
         stop_reason = "stop"
         token_count = 0
-        for new_tokens, new_logprobs in self.generate_step(prompt_ids):
+        kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start") if inference_kwargs.get(k) is not None}
+        for new_tokens, new_logprobs in self.generate_step(prompt_ids, **kv):
             token_count += new_tokens.numel()
             if collect_logprobs:
                 logprobs_map = get_top_logprobs(new_logprobs, top_logprobs)

@@ -384,6 +384,70 @@ def scaled_dot_product_attention(q, k, v, scale: float, mask=None, T: int | None
     return out
 
 
+def kv_quantize_rows(x: torch.Tensor, n: int, codes: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor, group_size: int = 64,
+                     bits: int = 8) -> None:
+    """mx.quantize of the first n rows of every head of x [B, H, cap, D] (T) into the same rows of a quantized KV cache's
+    codes [B, H, cap', D*bits/32] (uint32), scales / biases [B, H, cap', D/group_size] (T), bit-identical with mx.quantize."""
+    for t in (x, codes, scales, biases):
+        _dev(t)
+    B, H, cap, D = x.shape
+    dcap = codes.shape[2]
+    if codes.shape != (B, H, dcap, D * bits // 32) or scales.shape != (B, H, dcap, D // group_size) or biases.shape != scales.shape:
+        raise ValueError("kv_quantize_rows: codes / scales / biases do not match x, group_size and bits")
+    if codes.element_size() != 4 or scales.dtype != x.dtype or biases.dtype != x.dtype:
+        raise ValueError("kv_quantize_rows: codes must be 32-bit words, scales / biases of x's dtype")
+    _ffi.check(_ffi.load().pie_kv_quantize(_ffi.p(x), B * H, int(n), cap, D, group_size, bits, _ffi.dtype_code(x.dtype), _ffi.p(codes),
+                                           _ffi.p(scales), _ffi.p(biases), dcap, _ffi.stream()))
+
+
+def kv_quantize(x: torch.Tensor, group_size: int = 64, bits: int = 8):
+    """mx.quantize(x, group_size, bits) of K / V rows x [..., L, D] -> (codes uint32 [..., L, D*bits/32], scales, biases [..., L, D/group_size])."""
+    _dev(x)
+    *lead, L, D = x.shape
+    if bits not in (4, 8) or group_size not in (32, 64, 128) or D % group_size:
+        raise ValueError(f"kv_quantize: bits 4 / 8 and group_size 32 / 64 / 128 dividing the row ({D}) only; got bits={bits}, group_size={group_size}")
+    x4 = x.reshape(1, -1, L, D)
+    codes = torch.empty((*lead, L, D * bits // 32), dtype=torch.uint32, device=x.device)
+    scales = torch.empty((*lead, L, D // group_size), dtype=x.dtype, device=x.device)
+    biases = torch.empty_like(scales)
+    kv_quantize_rows(x4, L, codes.reshape(1, -1, L, D * bits // 32), scales.reshape(1, -1, L, D // group_size),
+                     biases.reshape(1, -1, L, D // group_size), group_size, bits)
+    return codes, scales, biases
+
+
+def attn_decode_quant(q: torch.Tensor, k: tuple, v: tuple, scale: float, group_size: int = 64, bits: int = 8, T: int | None = None) -> torch.Tensor:
+    """quantized_scaled_dot_product_attention (models/base.py:56-89) for one query row: q [Hq, D] (or [1, Hq, 1, D]) T, k / v the
+    (codes, scales, biases) triples of a QuantizedKVCache layer ([1, Hkv, cap, ...] or [Hkv, cap, ...]); the first T positions
+    (default: all) are attended.  Returns the shape of q."""
+    shape = q.shape
+    q2 = q.reshape(-1, shape[-1])
+    kk = [t.reshape(-1, t.shape[-2], t.shape[-1]) for t in k]
+    vv = [t.reshape(-1, t.shape[-2], t.shape[-1]) for t in v]
+    for t in (q2, *kk, *vv):
+        _dev(t)
+    Hq, D = q2.shape
+    Hkv, cap = kk[0].shape[0], kk[0].shape[1]
+    if bits not in (4, 8) or group_size not in (32, 64, 128) or D % group_size:
+        raise ValueError(f"attn_decode_quant: bits 4 / 8 and group_size 32 / 64 / 128 dividing head_dim ({D}) only; got bits={bits}, group_size={group_size}")
+    for trip, what in ((kk, "k"), (vv, "v")):
+        c, sc, bi = trip
+        if c.shape != (Hkv, cap, D * bits // 32) or sc.shape != (Hkv, cap, D // group_size) or bi.shape != sc.shape:
+            raise ValueError(f"attn_decode_quant: {what} triple {[tuple(t.shape) for t in trip]} does not match {Hkv} kv-heads x {cap} positions, "
+                             f"head_dim {D}, bits {bits}, group_size {group_size}")
+        if c.element_size() != 4 or sc.dtype != q.dtype or bi.dtype != q.dtype:
+            raise ValueError(f"attn_decode_quant: {what} codes must be 32-bit words, scales / biases of q's dtype")
+    T = cap if T is None else int(T)
+    key = (q.device, Hq, D)
+    ws = _sdpa_ws.get(key)
+    if ws is None:
+        ws = torch.empty(_ffi.load().pie_sdpa_decode_workspace_bytes(Hq, D), dtype=torch.uint8, device=q.device)
+        _sdpa_ws[key] = ws
+    out = torch.empty_like(q2)
+    _ffi.check(_ffi.load().pie_attn_decode_quant(_ffi.p(q2), *(_ffi.p(t) for t in kk), *(_ffi.p(t) for t in vv), Hq, Hkv, T, cap, D,
+                                                 group_size, bits, float(scale), _ffi.dtype_code(q.dtype), _ffi.p(out), _ffi.p(ws), _ffi.stream()))
+    return out.reshape(shape)
+
+
 def paged_kv_append(k: torch.Tensor, v: torch.Tensor, slab: torch.Tensor, n_pages: int, block_table: torch.Tensor,
                     positions: torch.Tensor) -> None:
     """Stores the new K / V rows [B, Hkv, D] of B sequences in their pages (sequence s at positions[s]; < 0 = idle).

@@ -19,7 +19,7 @@ import torch
 
 from .. import base
 from ... import _ffi, hip_ops
-from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, ReusableKVCache
+from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, QuantizedKVCache, ReusableKVCache
 from .utils import Llama3RoPE
 
 
@@ -385,6 +385,8 @@ class Model:
             raise ValueError(f"expected {len(self.layers)} layer caches, got {len(cache)}")
         if isinstance(cache[0], PagedKVCache):
             return self._sync_paged(cache, n_new)
+        if isinstance(cache[0], QuantizedKVCache):
+            return self._sync_quant(cache, n_new)
         off = cache[0].offset
         for c in cache:
             if not isinstance(c, ReusableKVCache):
@@ -400,6 +402,30 @@ class Model:
             kp = (C.c_void_p * n)(*key[0])
             vp = (C.c_void_p * n)(*key[1])
             _ffi.check(lib.pie_decoder_set_kv(self._dec, kp, vp, cap, _ffi.stream()))
+            self._kv_key = key
+        if self._dev_offset != off:
+            _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
+            self._dev_offset = off
+
+    def _sync_quant(self, cache: list[QuantizedKVCache], n_new: int) -> None:
+        """_sync_cache for QuantizedKVCache layers (quantized.py:53-80 for the capacity): the decoder appends quantised rows and
+        attends the codes.  The binding key carries the format, so a captured step graph is re-captured when it changes."""
+        c0 = cache[0]
+        off = c0.offset
+        for c in cache:
+            if not isinstance(c, QuantizedKVCache):
+                raise TypeError("all layers of a quantized cache must be QuantizedKVCache")
+            if c.offset != off or c.group_size != c0.group_size or c.bits != c0.bits:
+                raise ValueError("layer caches disagree on offset or format")
+            c.reserve(n_new, self.n_kv_heads, self.head_dim, self.dtype, self.device)
+        cap = min(c.capacity for c in cache)
+        ptrs = tuple(tuple(t.data_ptr() for t in (*c.keys, *c.values)) for c in cache)
+        key = ("quant", ptrs, cap, c0.group_size, c0.bits)
+        lib = _ffi.load()
+        if key != self._kv_key:
+            n = len(cache)
+            cols = [(C.c_void_p * n)(*[p[j] for p in ptrs]) for j in range(6)]
+            _ffi.check(lib.pie_decoder_set_kv_quant(self._dec, *cols, cap, c0.group_size, c0.bits, _ffi.stream()))
             self._kv_key = key
         if self._dev_offset != off:
             _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
