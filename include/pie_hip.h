@@ -516,6 +516,29 @@ int pie_decoder_set_kv_quant(pie_decoder *d, const void *const *k_codes, const v
                              const void *const *v_codes, const void *const *v_scales, const void *const *v_biases, int capacity,
                              int group_size, int bits, void *stream);
 
+/* ---------------------------------------------------------------- rotating KV cache (RotatingKVCache, cache/kv_cache/rotating.py)
+ * A ring of `window` rows over the contiguous buffers of pie_decoder_set_kv, in the reference's row order: rows [0, keep) are the first
+ * positions (never evicted), the rest rotate.  Position p >= rot0 lives in row keep + (p - rot0) % (window - keep), earlier positions in row p.
+ * pie_decoder_set_kv_ring: binds the ring to the decoder's buffers (call after pie_decoder_set_kv; window 0 = unbounded again).  Steps
+ *   (graph replay included) write the new K / V rows to their ring row and attend min(offset + 1, window) rows -- the q|k|v launch stages
+ *   the rows, the attention launch moves them.  Prompts of 2+ rows (pie_decoder_prefill / _prefill_embeds) append at buffer rows
+ *   row0 .. row0 + L - 1 with RoPE at the absolute positions offset .. offset + L - 1, and row r attends rows row0 + r - window .. row0 + r.
+ *   `positions`: the steps' positions stay below it (the staging page's table covers them).  Refused (PIE_E_STATE) on tensor-parallel
+ *   decoders and on paged or quantized caches.
+ * pie_kv_ring_order: rows keep + j <- rows keep + (j + shift) % n, j < n_dst, of every head of k and v (T [H, cap, head_dim]), through
+ *   `scratch` (2 * H * n_dst * head_dim elements of T): a full ring into temporal order, or a long store cut to the window.
+ * pie_sdpa_prefill_window: pie_sdpa_prefill where row r also ignores keys below offset + r - window (create_causal_mask(L, offset,
+ *   window_size=window), models/base.py:18-34); key blocks below a query tile's window are skipped.
+ * pie_sdpa_decode_ring: the decoder's step attention on a ring, op level: the new rows wait in `stage` ([2, Hkv, 64, D] T, row pos % 64),
+ *   are moved into ring row slot(pos) of k / v [Hkv, cap, D] and min(pos + 1, window) rows are attended -> out [Hq, D].  workspace:
+ *   pie_sdpa_decode_workspace_bytes(Hq, D) + 32 bytes. */
+int pie_decoder_set_kv_ring(pie_decoder *d, int window, int keep, int rot0, int row0, int positions, void *stream);
+int pie_kv_ring_order(void *k, void *v, int H, int cap, int head_dim, int keep, int n, int shift, int n_dst, void *scratch, void *stream);
+int pie_sdpa_prefill_window(const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D, int window,
+                            float scale, int dtype, void *out, void *stream);
+int pie_sdpa_decode_ring(const void *q, void *k, void *v, const void *stage, int Hq, int Hkv, int cap, int D, int pos, int window, int keep,
+                         int rot0, float scale, int dtype, void *out, void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- vision tower ops
  * Call sites: models/intern/vision.py (Qwen2.5-VL vision tower: PatchEmbed :87-121, Attention :143-186, MLP :189-197,
  * PatchMerger :124-140).  RMSNorm, SiLU * up and the residual adds are pie_rms_norm / pie_silu_mul / pie_add.

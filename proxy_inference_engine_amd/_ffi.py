@@ -40,6 +40,7 @@ EXPORTS = [
     "pie_w4m_bytes", "pie_repack_w4s_to_w4m", "pie_qgemm_w4m",
     "pie_comm_create", "pie_comm_rccl_unique_id", "pie_comm_create_rccl", "pie_comm_export", "pie_comm_connect", "pie_allreduce_f32", "pie_comm_status", "pie_comm_destroy", "pie_decoder_set_comm", "pie_sample", "pie_sample_workspace_bytes",
     "pie_kv_quantize", "pie_attn_decode_quant", "pie_decoder_set_kv_quant",
+    "pie_decoder_set_kv_ring", "pie_kv_ring_order", "pie_sdpa_prefill_window", "pie_sdpa_decode_ring",
 ]
 
 
@@ -99,6 +100,10 @@ def load() -> C.CDLL:
     lib.pie_attn_decode_quant.argtypes = [C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_decoder_set_kv_quant.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6 + [C.c_int] * 3 + [C.c_void_p]
     lib.pie_sdpa_prefill.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_sdpa_prefill_window.argtypes = [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_decoder_set_kv_ring.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+    lib.pie_kv_ring_order.argtypes = [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p] * 2
+    lib.pie_sdpa_decode_ring.argtypes = [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_rms_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_silu_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_add.argtypes = lib.pie_silu_mul.argtypes

@@ -1,4 +1,4 @@
-from .kv_cache import BaseCache, QuantizedKVCache, ReusableKVCache
+from .kv_cache import BaseCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from .prompt_cache import PromptCache
 
-__all__ = ["BaseCache", "ReusableKVCache", "QuantizedKVCache", "PromptCache"]
+__all__ = ["BaseCache", "ReusableKVCache", "QuantizedKVCache", "RotatingKVCache", "PromptCache"]

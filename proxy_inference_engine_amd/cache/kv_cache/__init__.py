@@ -15,6 +15,12 @@ class BaseCache(ABC):
 
     @staticmethod
     def make_kv_cache(model, max_kv_size: int | None = None, reusable: bool = True) -> list["BaseCache"]:
+        # max_kv_size: a RotatingKVCache(max_kv_size, keep=4) per layer.  The reference gets there through a model without make_cache, which
+        # its Llama is; this project's Llama has a make_cache, so the ring is chosen here first to keep that behaviour.
+        if max_kv_size is not None:
+            if getattr(model, "_page_pool", None) is not None:
+                raise ValueError("max_kv_size: a rotating KV cache runs on contiguous buffers, not on the model's KV pages")
+            return [RotatingKVCache(max_size=max_kv_size, keep=4) for _ in range(len(model.layers))]
         if hasattr(model, "make_cache") and model.make_cache is not None:
             return model.make_cache()
         if max_kv_size is not None or not reusable:
@@ -26,12 +32,21 @@ class BaseCache(ABC):
     # "0.<i>" = meta_state of layer i, "1.<key>" = the caller's metadata, "2.<i>" = cache class name of layer i.
     # A QuantizedKVCache layer's state and meta_state are nested one level deeper, as tree_flatten names them: arrays
     # "<i>.<0 keys | 1 values>.<0 codes | 1 scales | 2 biases>", meta "0.<i>.<0 step | 1 offset | 2 group_size | 3 bits>".
+    # A RotatingKVCache layer: arrays "<i>.0" / "<i>.1" (its state), meta "0.<i>.<k>" = keep, max_size, step, offset, _idx.
     @staticmethod
     def save_cache(file_name: str, cache: list["BaseCache"], metadata: dict[str, str] | None = None) -> None:
         from safetensors.torch import save_file
         arrays: dict[str, torch.Tensor] = {}
         meta: dict[str, str] = {}
         for i, c in enumerate(cache):
+            if isinstance(c, RotatingKVCache):
+                for j, t in enumerate(c.state):
+                    if t is not None:
+                        arrays[f"{i}.{j}"] = t.detach().to("cpu").contiguous()
+                for k, v in enumerate(c.meta_state):
+                    meta[f"0.{i}.{k}"] = v
+                meta[f"2.{i}"] = type(c).__name__
+                continue
             if isinstance(c, QuantizedKVCache):
                 for j, triple in enumerate(c.state):
                     for k, t in enumerate(triple or ()):
@@ -55,7 +70,7 @@ class BaseCache(ABC):
         from safetensors import safe_open
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        classes = {"ReusableKVCache": ReusableKVCache, "QuantizedKVCache": QuantizedKVCache}
+        classes = {"ReusableKVCache": ReusableKVCache, "QuantizedKVCache": QuantizedKVCache, "RotatingKVCache": RotatingKVCache}
         with safe_open(file_name, framework="pt", device="cpu") as f:
             meta = f.metadata() or {}
             n = sum(1 for k in meta if k.startswith("2."))
@@ -64,6 +79,16 @@ class BaseCache(ABC):
                 name = meta[f"2.{i}"]
                 if name not in classes:
                     raise ValueError(f"{file_name}: cache class {name} is not on the MI355X path")
+                if name == "RotatingKVCache":
+                    # the reference's loader calls the class without arguments, which RotatingKVCache(max_size) does not accept: the size
+                    # comes from the meta strings here
+                    ms = tuple(meta[f"0.{i}.{k}"] for k in range(5))
+                    c = RotatingKVCache(max_size=int(ms[1]), keep=int(ms[0]), step=int(ms[2]))
+                    if f"{i}.0" in f.keys():
+                        c.state = (f.get_tensor(f"{i}.0").to(device), f.get_tensor(f"{i}.1").to(device))
+                    c.meta_state = ms
+                    cache.append(c)
+                    continue
                 c = classes[name]()
                 if isinstance(c, QuantizedKVCache):
                     keys = f.keys()
@@ -112,5 +137,6 @@ class BaseCache(ABC):
 from .reusable import ReusableKVCache  # noqa: E402
 from .paged import PageAllocator, PagedKVCache, PagedSequence  # noqa: E402
 from .quantized import QuantizedKVCache  # noqa: E402
+from .rotating import RotatingKVCache  # noqa: E402
 
-__all__ = ["BaseCache", "ReusableKVCache", "QuantizedKVCache", "PagedKVCache", "PagedSequence", "PageAllocator"]
+__all__ = ["BaseCache", "ReusableKVCache", "QuantizedKVCache", "RotatingKVCache", "PagedKVCache", "PagedSequence", "PageAllocator"]

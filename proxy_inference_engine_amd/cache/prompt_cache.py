@@ -20,7 +20,7 @@ import torch
 
 logger = logging.getLogger(__name__)
 
-from .kv_cache import BaseCache, PagedKVCache, QuantizedKVCache, ReusableKVCache
+from .kv_cache import BaseCache, PagedKVCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 
 
 def _as_list(ids) -> list[int]:
@@ -79,8 +79,14 @@ class PromptCache:
             common += 1
         if common == 0:
             return prompt_ids
+        if any(isinstance(c, RotatingKVCache) for c in self.cache) and not all(c.is_trimmable() for c in self.cache):
+            # DEVIATION: the reference asserts here (rotating caches are not reusable).  A ring that has evicted nothing yet is trimmed to the
+            # prefix like any other cache; one that has evicted rows no longer holds the prefix, so the request starts on fresh rings.
+            self.cache = [RotatingKVCache(c.max_size, keep=c.keep, step=c.step) for c in self.cache]
+            del history[:]
+            return prompt_ids
         for layer_cache in self.cache:
-            assert isinstance(layer_cache, (ReusableKVCache, QuantizedKVCache, PagedKVCache))
+            assert isinstance(layer_cache, (ReusableKVCache, QuantizedKVCache, PagedKVCache, RotatingKVCache))
             layer_cache.reuse(len(ids), common)
         # DEVIATION from prompt_cache.py:52-76, which leaves computed_ids untouched here: after a diverging request B the
         # reference's history reads A + B[k:] while the KV rows beyond k belong to B, so a later request that matches A beyond k

@@ -28,7 +28,13 @@ struct DecState {
     int token;  // input token of the step / greedy output after it
     int cap;    // capacity of the per-layer KV buffers (tokens)
     int pad;
+    // RotatingKVCache (pie_decoder_set_kv_ring): window = max_size (0 = unbounded: every other cache), keep = sink rows, rot0 = the
+    // position written at row `keep` when the ring last started rotating.  Position p >= rot0 lives in row keep + (p - rot0) % (window - keep),
+    // earlier ones in row p; a step attends min(pos + 1, window) rows.  All from pos: the ring fills up inside replayed graphs.
+    int window, keep, rot0, pad2;
 };
+__host__ __device__ __forceinline__ int ring_slot(const DecState &s, int p) { return p < s.rot0 ? p : s.keep + (p - s.rot0) % (s.window - s.keep); }
+__host__ __device__ __forceinline__ int ring_len(const DecState &s) { return s.window > 0 && s.pos + 1 > s.window ? s.window : s.pos + 1; }
 
 // How T cached positions are cut into splits: fixed launch geometry (graph-replayable), data-dependent activity.
 struct AttnSplit {
@@ -75,6 +81,9 @@ struct AttnArgs {
     unsigned long long pf_bytes;
     int pf_rows;      // extra blockIdx.y rows doing this (0 = none)
     unsigned *pf_sink;
+    // RotatingKVCache (RING instantiation, decoder only): the q|k|v launch staged the step's K / V rows in this page (K block then V block,
+    // each [Hkv, 64, D], row pos % 64); the split that holds the row's ring slot moves them there and scores them from the page
+    const u16 *ring_stage;
 };
 
 constexpr int ATTN_WAVES = 8;  // waves per workgroup (2 per SIMD: one wave's VALU scoring overlaps the other's loads)
@@ -115,7 +124,7 @@ struct AttnNoSeam {
 };
 // q0: the first of the REP query heads scored here (the kernel: g * REP, all heads of the kv group; the fused caller: ONE head of group g per
 // workgroup -- a head's online softmax never looks at another head, so the grouping does not change a bit).
-template <class T, int D, int REP, bool PAGED, bool NTKV, int WAVES, class SEAM = AttnNoSeam>
+template <class T, int D, int REP, bool PAGED, bool NTKV, int WAVES, class SEAM = AttnNoSeam, bool RING = false>
 __device__ __forceinline__ void attn_decode_body(const AttnArgs &a, const int g, const int split, const int row, const int q0, const SEAM seam = SEAM()) {
     constexpr int LPT = D / 8;     // lanes per token row (16 B each)
     constexpr int TPW = 64 / LPT;  // token rows per wave-load
@@ -137,9 +146,10 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs &a, const int g,
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ts = lane / LPT, dc = lane % LPT;
     const float sl2 = a.scale * ATTN_LOG2E;
-    const int Ttot = PAGED && a.ctx_len ? a.ctx_len[row] : (a.state ? a.state->pos + 1 : a.T) + row;
+    const int Ttot = RING ? ring_len(*a.state) : PAGED && a.ctx_len ? a.ctx_len[row] : (a.state ? a.state->pos + 1 : a.T) + row;
     const int cap = PAGED ? 64 : a.state ? a.state->cap : a.cap;
     const AttnSplit sp = attn_split(Ttot, a.splits);
+    const int rslot = RING ? ring_slot(*a.state, a.state->pos) : -1;  // RING: the row the step's K / V go to (every other row is read as cached)
     ATTN_STAMP(1);  // the position has arrived
     if constexpr (PAGED) {
         if (a.splits == 1 && a.ctx_len && sp.active == 0) {  // idle slot of a one-split batch: zeros, as k_attn_combine leaves it
@@ -167,6 +177,16 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs &a, const int g,
     const u16 *vbase = PAGED && a.slab ? a.slab + (size_t)a.Hkv * 64 * D : a.k ? a.v : reinterpret_cast<const u16 *>(a.kv_table[a.n_layers + a.layer]);
     kbase += (size_t)g * cap * D + dc * 8;
     vbase += (size_t)g * cap * D + dc * 8;
+    const u16 *kst = nullptr, *vst = nullptr;  // RING: the staged rows of this kv-head
+    if constexpr (RING) {
+        kst = a.ring_stage + ((size_t)g * 64 + (a.state->pos & 63)) * D + dc * 8;
+        vst = kst + (size_t)a.Hkv * 64 * D;
+        if (rslot >= t_begin && rslot < t_end && threadIdx.x < (unsigned)LPT) {  // the slot's one reader moves the rows; it scores them from the page
+            const size_t o = (size_t)rslot * D;
+            *reinterpret_cast<uint4 *>(const_cast<u16 *>(kbase) + o) = *reinterpret_cast<const uint4 *>(kst);
+            *reinterpret_cast<uint4 *>(const_cast<u16 *>(vbase) + o) = *reinterpret_cast<const uint4 *>(vst);
+        }
+    }
     const int *bt = PAGED ? a.block_table + (size_t)row * a.bt_stride : nullptr;
     const size_t page_elems = (size_t)2 * 64 * a.Hkv * D;
     const unsigned last_page = (unsigned)a.n_pages - 1u;
@@ -196,6 +216,10 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs &a, const int g,
             kq[d] = attn_load_row<NTKV>(kbase + off);
             vq[d] = attn_load_row<NTKV>(vbase + off);
             pgq[d] = page_of(b + DA);
+        } else if constexpr (RING) {
+            const bool st = t == rslot;
+            kq[d] = attn_load_row<NTKV>(st ? kst : kbase + (size_t)t * D);
+            vq[d] = attn_load_row<NTKV>(st ? vst : vbase + (size_t)t * D);
         } else {
             kq[d] = attn_load_row<NTKV>(kbase + (size_t)t * D);
             vq[d] = attn_load_row<NTKV>(vbase + (size_t)t * D);
@@ -387,7 +411,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs &a, const int g,
     ATTN_STAMP(6);
 }
 
-template <class T, int D, int REP, bool PAGED = false, bool NTKV = false, int WAVES = ATTN_WAVES>
+template <class T, int D, int REP, bool PAGED = false, bool NTKV = false, int WAVES = ATTN_WAVES, bool RING = false>
 __global__ void __launch_bounds__(WAVES * 64) k_attn_decode(const AttnArgs a) {
     constexpr int NT = WAVES * 64;
     const int g = blockIdx.x, split = blockIdx.y;
@@ -403,7 +427,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_attn_decode(const AttnArgs a) {
         if (acc == 0x9e3779b9u) a.pf_sink[0] = acc;  // keeps the loads alive; practically never taken
         return;
     }
-    attn_decode_body<T, D, REP, PAGED, NTKV, WAVES>(a, g, split, (int)blockIdx.z, g * REP);
+    attn_decode_body<T, D, REP, PAGED, NTKV, WAVES, AttnNoSeam, RING>(a, g, split, (int)blockIdx.z, g * REP);
 }
 
 // Merge of the active splits for 8 consecutive dims [d0, d0+8) of q-head h (fp32):
@@ -461,7 +485,7 @@ __global__ void __launch_bounds__(256) k_attn_combine(const AttnArgs a, int D) {
     const int row = blockIdx.y, PPH = D >> 3, NG = 256 / PPH;
     const size_t h = (size_t)row * a.Hq + blockIdx.x;
     const int pc = threadIdx.x % PPH, grp = threadIdx.x / PPH, d0 = pc * 8, lane = threadIdx.x & 63;
-    const int Ttot = a.ctx_len ? a.ctx_len[row] : (a.state ? a.state->pos + 1 : a.T) + row;
+    const int Ttot = a.ctx_len ? a.ctx_len[row] : a.ring_stage ? ring_len(*a.state) : (a.state ? a.state->pos + 1 : a.T) + row;
     const int active = attn_split(Ttot, a.splits).active;  // <= ATTN_MAX_SPLITS <= 64; 0 for an idle paged slot
     const float *ml = a.part_ml + h * a.splits * 2;
     const float *pa = a.part_acc + h * a.splits * D + d0;

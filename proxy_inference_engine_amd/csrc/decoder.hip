@@ -46,15 +46,21 @@ __global__ void k_set_state(DecState *s, int pos, int token, int cap) {
     if (token >= 0) s->token = token;
     if (cap >= 0) s->cap = cap;
 }
+__global__ void k_set_ring(DecState *s, DecState *rows, int window, int keep, int rot0, int row0) {
+    s->window = window, s->keep = keep, s->rot0 = rot0;
+    if (rows) rows->pos = row0, rows->cap = s->cap, rows->window = window, rows->keep = keep, rows->rot0 = rot0;
+}
 
 // Picks the split count / merge path for the current cache capacity; returns true when the launch sequence changed.
 static bool plan_attention(pie_decoder *d) {
     const pie_decoder_config &c = d->cfg;
     int splits;
+    // a ring attends at most its window, whatever the buffers hold after a long prompt
+    const int cap = d->ring && d->ring_w < d->kv_cap ? d->ring_w : d->kv_cap;
     if (c.kv_splits > 0) splits = c.kv_splits > ATTN_MAX_SPLITS ? ATTN_MAX_SPLITS : c.kv_splits;
-    else if (d->kv_cap <= d->merge_max_cap) splits = GEMV_ATTN_SPLITS;
+    else if (cap <= d->merge_max_cap) splits = GEMV_ATTN_SPLITS;
     else {
-        splits = d->kv_cap / 64;  // >= 64 positions per workgroup, 16 per wave
+        splits = cap / 64;  // >= 64 positions per workgroup, 16 per wave
         const int fill = 256 / c.n_kv_heads > 0 ? 256 / c.n_kv_heads : 1;
         if (splits > fill) splits = fill;
         if (splits > ATTN_MAX_SPLITS) splits = ATTN_MAX_SPLITS;
@@ -118,7 +124,7 @@ static bool fuse_attn(const pie_decoder *d, int li) {
     const pie_decoder_config &c = d->cfg;
     if (pie_knob(PIE_KNOB_FUSE_ATTN) == 0 || !d->xcd_ok || !d->seam || g_live_decoders.load() > 4) return false;
     (void)li;  // (any weight format of the q|k|v matrix)
-    return !d->tp() && !d->combine && !(d->kv_i8 && d->block_table) && !d->kv_quant && c.n_heads == 32 && c.n_kv_heads == 8 && c.head_dim == 128 && c.hidden <= 4096 &&
+    return !d->tp() && !d->combine && !(d->kv_i8 && d->block_table) && !d->kv_quant && !d->ring && c.n_heads == 32 && c.n_kv_heads == 8 && c.head_dim == 128 && c.hidden <= 4096 &&
            d->splits >= 1 && d->splits <= 4;
 }
 
@@ -175,7 +181,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
             a.lin_bias = (const u16 *)w.bqkv, a.rope_traditional = c.rope_traditional;
             a.block_table = d->block_table, a.n_pages = d->n_pages;
             const bool i8 = d->kv_i8 && d->block_table;  // int8 pages: the T rows go to the staging page, then get quantised into the sequence's page
-            if (i8 || d->kv_quant) a.kv_table = d->kv_table_stage, a.block_table = d->zero_table, a.n_pages = 1;
+            if (i8 || d->kv_quant || d->ring) a.kv_table = d->kv_table_stage, a.block_table = d->zero_table, a.n_pages = 1;
             a.prof = reinterpret_cast<unsigned long long *>(d->pf_sink) + PROF_QKV;
             if (embed_here) {  // the step's embedding launch folded into this one (embed_in_qkv): x = the token's row, dequantised by every workgroup
                 a.x = nullptr, a.rope_cs = nullptr, a.rope_cs_out = d->rope_cs, a.h_out = d->h, a.token = token_ptr;
@@ -210,6 +216,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
             }
             if (fuse_attn(d, li)) return PIE_OK;  // ran behind the q|k|v launch's seam
             AttnArgs a = attn_args(d, li);
+            if (d->ring) a.ring_stage = d->kv_stage;  // rotating cache: the staged rows go to their ring slot inside this launch
             return attn_decode_launch(c.dtype, D, a, d->combine, st);  // short caches: partials are merged by the o_proj prologue
         }
         case PIE_K_OPROJ: {  // h = x + o_proj(attn)  (language.py:108,151)
@@ -358,7 +365,7 @@ int pie_decoder_destroy(pie_decoder *d) {
     drop_graphs(d);
     prefill_free(d);
     void *ptrs[] = {d->state, d->kv_table, d->qbuf, d->attn, d->act, d->part_acc, d->part_ml, d->stats, d->rope_cs, d->pf_sink, d->seam, d->tp_part, d->kv_stage, d->kv_table_stage,
-                    d->zero_table, d->kvq_scratch, d->kvq_table};
+                    d->zero_table, d->kvq_scratch, d->kvq_table, d->ring_rows};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete d;
@@ -411,6 +418,14 @@ int pie_decoder_set_globals(pie_decoder *d, const pie_global_weights *w) {
     return PIE_OK;
 }
 
+// Any binding other than pie_decoder_set_kv_ring makes the cache unbounded again (window 0 in the device-side state); true if it was a ring.
+static bool leave_ring(pie_decoder *d, hipStream_t st) {
+    if (!d->ring) return false;
+    hipLaunchKernelGGL(k_set_ring, dim3(1), dim3(1), 0, st, d->state, (DecState *)nullptr, 0, 0, 0, 0);
+    d->ring = false, d->ring_w = 0;
+    return true;
+}
+
 int pie_decoder_set_kv(pie_decoder *d, const void *const *k_ptrs, const void *const *v_ptrs, int capacity, void *stream) {
     PIE_REQUIRE(d && k_ptrs && v_ptrs, PIE_E_ARG, "pie_decoder_set_kv: null pointer");
     PIE_REQUIRE(capacity > 0, PIE_E_SHAPE, "pie_decoder_set_kv: capacity must be positive");
@@ -429,9 +444,9 @@ int pie_decoder_set_kv(pie_decoder *d, const void *const *k_ptrs, const void *co
     PIE_LAUNCH_CHECK();
     d->kv_set = true;
     d->kv_cap = capacity;
-    const bool was_paged = d->block_table != nullptr, was_quant = d->kv_quant;
+    const bool was_paged = d->block_table != nullptr, was_quant = d->kv_quant, was_ring = leave_ring(d, st);
     d->block_table = nullptr, d->n_pages = 0, d->kv_quant = false;
-    if (plan_attention(d) || was_paged || was_quant) drop_graphs(d);  // the launch sequence changed: captured graphs are stale
+    if (plan_attention(d) || was_paged || was_quant || was_ring) drop_graphs(d);  // the launch sequence changed: captured graphs are stale
     return PIE_OK;
 }
 
@@ -459,6 +474,37 @@ static int ensure_staging(pie_decoder *d, int blocks) {
     return PIE_OK;
 }
 
+int pie_decoder_set_kv_ring(pie_decoder *d, int window, int keep, int rot0, int row0, int positions, void *stream) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_kv_ring: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_kv_ring: a rotating KV cache is not available on a tensor-parallel decoder");
+    PIE_REQUIRE(d->kv_set && !d->block_table && !d->kv_quant, PIE_E_STATE, "pie_decoder_set_kv_ring: bind the ring's buffers with pie_decoder_set_kv first");
+    hipStream_t st = (hipStream_t)stream;
+    if (window == 0) {
+        if (leave_ring(d, st)) {
+            PIE_LAUNCH_CHECK();
+            plan_attention(d);
+            drop_graphs(d);
+        }
+        return PIE_OK;
+    }
+    PIE_REQUIRE(window >= 1 && keep >= 0 && keep < window, PIE_E_ARG, "pie_decoder_set_kv_ring: need 0 <= keep < window");
+    // (the buffers grow with the ring until it is full: a step's row and length stay below the rows the host has allocated)
+    PIE_REQUIRE(row0 >= 0 && row0 <= d->kv_cap && rot0 >= 0 && positions >= 1, PIE_E_SHAPE, "pie_decoder_set_kv_ring: the prompt row base lies outside the buffers");
+    if (!d->ring_rows) {
+        PIE_HIP_TRY(hipMalloc((void **)&d->ring_rows, sizeof(DecState)));
+        PIE_HIP_TRY(hipMemset(d->ring_rows, 0, sizeof(DecState)));
+    }
+    // the staging page's block table is indexed by the position: it must cover every position a step (graph replay included) writes
+    const int rc = ensure_staging(d, (positions + PIE_PAGE_TOKENS - 1) / PIE_PAGE_TOKENS);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_set_ring, dim3(1), dim3(1), 0, st, d->state, d->ring_rows, window, keep, rot0, row0);
+    PIE_LAUNCH_CHECK();
+    const bool changed = !d->ring || d->ring_w != window;  // (keep, rot0, row0 are device-side values, not launch arguments)
+    d->ring = true, d->ring_w = window, d->ring_row0 = row0;
+    if (plan_attention(d) || changed) drop_graphs(d);
+    return PIE_OK;
+}
+
 int pie_decoder_set_kv_quant(pie_decoder *d, const void *const *k_codes, const void *const *k_scales, const void *const *k_biases,
                              const void *const *v_codes, const void *const *v_scales, const void *const *v_biases, int capacity, int group_size,
                              int bits, void *stream) {
@@ -483,7 +529,7 @@ int pie_decoder_set_kv_quant(pie_decoder *d, const void *const *k_codes, const v
     hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, st, d->state, -1, -1, capacity);
     PIE_LAUNCH_CHECK();
     // the buffers, group and width are arguments of the attention launches: a captured graph is stale when any of them changes
-    const bool changed = !d->kv_quant || d->kvq_host != host || d->kvq_gs != group_size || d->kvq_bits != bits || d->block_table != nullptr;
+    const bool changed = leave_ring(d, st) || !d->kv_quant || d->kvq_host != host || d->kvq_gs != group_size || d->kvq_bits != bits || d->block_table != nullptr;
     d->kvq_host = std::move(host), d->kvq_gs = group_size, d->kvq_bits = bits, d->kv_quant = true;
     d->block_table = nullptr, d->n_pages = 0;
     d->kv_set = true;
@@ -524,7 +570,7 @@ int pie_decoder_set_paged_kv(pie_decoder *d, const void *const *slabs, size_t n_
     d->kv_set = true;
     d->kv_cap = capacity;
     // kernel arguments are baked into captured graphs: a new table pointer or pool size invalidates them
-    const bool changed = d->block_table != block_table || d->n_pages != (int)n_pages || blocks_changed || (d->kv_i8 && slabs_changed) || d->kv_quant;
+    const bool changed = leave_ring(d, st) | (d->block_table != block_table || d->n_pages != (int)n_pages || blocks_changed || (d->kv_i8 && slabs_changed) || d->kv_quant);
     d->block_table = block_table, d->n_pages = (int)n_pages, d->kv_quant = false;
     if (plan_attention(d) || changed) drop_graphs(d);
     return PIE_OK;
@@ -617,7 +663,9 @@ int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_
     // path has no collective yet
     // int8 pages: the batched prompt path of ONE sequence reads and writes T pages; such prompts run as decode steps here (fresh prompts go
     // through pie_decoder_prefill_batch, which the Python host does)
-    if (L >= prefill_min_rows() && !d->tp() && !(d->kv_i8 && d->block_table)) return prefill_batched(d, ids, nullptr, L, logits_all, st);  // MLX's qmm regime
+    // a rotating cache takes every multi-row update through the windowed pass: a chunk is not a run of single-row updates there
+    // (rotating.py: the chunk sees the retained window plus itself, a step only the newest rows)
+    if ((L >= prefill_min_rows() || (d->ring && L >= 2)) && !d->tp() && !(d->kv_i8 && d->block_table)) return prefill_batched(d, ids, nullptr, L, logits_all, st);  // MLX's qmm regime
     for (int l = 0; l < L; ++l) {
         const bool last = l == L - 1;
         u16 *dst = logits_all ? (u16 *)logits_all + (size_t)l * d->cfg.vocab : d->logits;
@@ -636,7 +684,8 @@ int pie_decoder_prefill_embeds(pie_decoder *d, const void *embeds, int L, void *
     PIE_REQUIRE(pie_aligned(embeds, 16), PIE_E_ALIGN, "pie_decoder_prefill_embeds: 16-byte alignment required");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_prefill_embeds: not available on a tensor-parallel shard");
     hipStream_t st = (hipStream_t)stream;
-    if (!(d->kv_i8 && d->block_table)) return prefill_batched(d, nullptr, embeds, L, logits_all, st);
+    // (one row on a rotating cache is a single-row update: the decode step below, as in rotating.py)
+    if (!(d->kv_i8 && d->block_table) && !(d->ring && L == 1)) return prefill_batched(d, nullptr, embeds, L, logits_all, st);
     // int8 pages: the batched prompt path of one sequence reads and writes T pages, so -- like a prompt of tokens (pie_decoder_prefill) -- the rows
     // run as decode steps, each with its row copied into the residual stream instead of an embedding launch (no RoPE table either: the
     // q|k|v epilogue computes its own angles).  The greedy token the tail leaves in the device-side state is that of the last row.

@@ -58,6 +58,13 @@ struct pie_decoder {
     u16 *kvq_scratch = nullptr;
     unsigned long long *kvq_table = nullptr;
     int kvq_scratch_cap = 0;
+    // RotatingKVCache (pie_decoder_set_kv_ring) over the contiguous buffers of pie_decoder_set_kv: the window / sink rows live in the
+    // device-side state (the step finds its row and length from pos); the q|k|v epilogue stages the new rows as for quantized KV and the
+    // attention launch (RING) moves them into their ring slot.  ring_rows: a second DecState whose pos is the buffer row of the prompt
+    // pass's first row (the retained window's length) and whose cap is the buffers' -- what the prompt pass's append and attention read.
+    bool ring = false;
+    int ring_w = 0, ring_row0 = 0;  // window; buffer row of the next prompt pass's first row (host copy of ring_rows->pos at bind time)
+    DecState *ring_rows = nullptr;
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     bool graph_fused[2] = {false, false};           // the captured graph holds the fused q|k|v + attention launch (re-captured when fusion is withdrawn)

@@ -5,14 +5,14 @@
 #include "tail.hpp"
 
 // ---------------------------------------------------------------- attention launch
-template <class T, int D, bool PAGED, bool NT, bool SHORT = false>
+template <class T, int D, bool PAGED, bool NT, bool SHORT = false, bool RING = false>
 static int attn_launch_rep(int rep, const AttnArgs &a, bool combine, hipStream_t st) {
     const int rows = a.rows > 0 ? a.rows : 1;
     const dim3 grid(a.Hkv, a.splits + a.pf_rows, rows);
 #define ATTN_GO(R)                                                                                                                      \
     {                                                                                                                                   \
         constexpr int W_ = SHORT ? attn_short_waves(R) : ATTN_WAVES;                                                                    \
-        hipLaunchKernelGGL((k_attn_decode<T, D, R, PAGED, NT, W_>), grid, dim3(W_ * 64), 0, st, a);                                      \
+        hipLaunchKernelGGL((k_attn_decode<T, D, R, PAGED, NT, W_, RING>), grid, dim3(W_ * 64), 0, st, a);                                      \
     }                                                                                                                                   \
     break
     switch (rep) {  // q-heads per kv-head: Llama-3-8B/70B 4/8, Llama-3.2-3B 3, Qwen2.5-7B 7, MHA 1
@@ -37,6 +37,12 @@ static int attn_launch_rep(int rep, const AttnArgs &a, bool combine, hipStream_t
 
 template <class T, int D>
 static int attn_launch_d(int rep, const AttnArgs &a, bool combine, hipStream_t st) {
+    if (a.ring_stage) {  // RotatingKVCache (decoder step, contiguous buffers): the same three plans, rows found by the ring rule
+        if (a.block_table) return pie::fail(PIE_E_STATE, "sdpa_decode: a rotating cache is contiguous");
+        if (a.nt_kv) return attn_launch_rep<T, D, false, true, false, true>(rep, a, combine, st);
+        if (!combine) return attn_launch_rep<T, D, false, false, true, true>(rep, a, combine, st);
+        return attn_launch_rep<T, D, false, false, false, true>(rep, a, combine, st);
+    }
     if (a.nt_kv) return a.block_table ? attn_launch_rep<T, D, true, true>(rep, a, combine, st) : attn_launch_rep<T, D, false, true>(rep, a, combine, st);
     if (!combine)  // the merged-split plan of short caches (capacity <= 1024): 4-wave workgroups
         return a.block_table ? attn_launch_rep<T, D, true, false, true>(rep, a, combine, st)
@@ -166,6 +172,33 @@ int pie_sdpa_decode(const void *q, const void *k, const void *v, int Hq, int Hkv
     a.part_ml = a.part_acc + (size_t)Hq * ATTN_MAX_SPLITS * D;
     a.out = (u16 *)out;
     return attn_decode_launch(dtype, D, a, true, (hipStream_t)stream);
+}
+
+// The decoder's rotating-cache step attention (RING) at op level: the new K / V rows wait in `stage` ([2, Hkv, 64, D], row pos % 64) as the
+// q|k|v epilogue leaves them; the launch moves them into ring row slot(pos) of k / v [Hkv, cap, D] and attends min(pos + 1, window) rows.
+// The ring state (DecState) goes into the workspace behind the split partials.
+int pie_sdpa_decode_ring(const void *q, void *k, void *v, const void *stage, int Hq, int Hkv, int cap, int D, int pos, int window, int keep,
+                         int rot0, float scale, int dtype, void *out, void *workspace, void *stream) {
+    PIE_REQUIRE(q && k && v && stage && out && workspace, PIE_E_ARG, "pie_sdpa_decode_ring: null pointer");
+    PIE_REQUIRE(window >= 1 && keep >= 0 && keep < window && pos >= 0 && rot0 >= 0, PIE_E_ARG, "pie_sdpa_decode_ring: need 0 <= keep < window, pos >= 0");
+    DecState s = {};
+    s.pos = pos, s.cap = cap, s.window = window, s.keep = keep, s.rot0 = rot0;
+    const int T = ring_len(s), slot = ring_slot(s, pos);
+    PIE_REQUIRE(Hkv > 0 && cap >= 1 && T <= cap && slot < cap, PIE_E_SHAPE, "pie_sdpa_decode_ring: the ring's rows and the new row's slot must lie in the buffers");
+    PIE_REQUIRE(pie_aligned(q, 16) && pie_aligned(k, 16) && pie_aligned(v, 16) && pie_aligned(stage, 16) && pie_aligned(workspace, 16), PIE_E_ALIGN,
+                "pie_sdpa_decode_ring: 16-byte alignment required");
+    hipStream_t st = (hipStream_t)stream;
+    DecState *ds = reinterpret_cast<DecState *>((char *)workspace + pie_sdpa_decode_workspace_bytes(Hq, D));
+    PIE_HIP_TRY(hipMemcpyAsync(ds, &s, sizeof(s), hipMemcpyHostToDevice, st));  // (pageable source: staged before the call returns)
+    AttnArgs a = {};
+    a.q = (const u16 *)q, a.k = (const u16 *)k, a.v = (const u16 *)v, a.state = ds, a.ring_stage = (const u16 *)stage;
+    a.Hq = Hq, a.Hkv = Hkv, a.scale = scale;
+    a.splits = T >= 2048 ? ATTN_MAX_SPLITS : (T >= 512 ? 16 : (T >= 128 ? 4 : 1));
+    a.nt_kv = T >= 2048;
+    a.part_acc = (float *)workspace;
+    a.part_ml = a.part_acc + (size_t)Hq * ATTN_MAX_SPLITS * D;
+    a.out = (u16 *)out;
+    return attn_decode_launch(dtype, D, a, true, st);
 }
 
 // ---------------------------------------------------------------- paged KV

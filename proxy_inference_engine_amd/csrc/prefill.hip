@@ -357,6 +357,7 @@ static int add_rms_norm_rows(u16 *x, const u16 *r, const void *w, float eps, int
 }
 
 __global__ void k_add_pos(DecState *s, int delta) { s->pos += delta; }
+__global__ void k_set_pos(DecState *s, int pos) { s->pos = pos; }
 
 // ---------------------------------------------------------------- scratch
 struct PrefillScratch {
@@ -770,7 +771,15 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
         const void *const *p = &d->kvq_host[(size_t)6 * li];
         return QKvLayer{(const u32 *)p[0], (const u16 *)p[1], (const u16 *)p[2], (const u32 *)p[3], (const u16 *)p[4], (const u16 *)p[5]};
     };
-    const bool mfma_attn = pie_knob(PIE_KNOB_PREFILL_ATTN_VALU) != 1;  // 1 forces the row-per-launch-slice VALU kernel (tests compare the two)
+    // RotatingKVCache: the chunk's K / V rows go to rows ring_rows->pos + m of the buffers (the retained window in temporal order, then the
+    // update: cache/kv_cache/rotating.py), RoPE stays at the absolute position state->pos + m; the attention is windowed
+    DecState *const kvs = d->ring ? d->ring_rows : d->state;
+    if (d->ring) {  // every pass starts at the row the host bound (pie_decoder_set_kv_ring): the chunk loop below advances it
+        PIE_REQUIRE((long long)d->ring_row0 + L <= d->kv_cap, PIE_E_SHAPE, "pie_decoder_prefill: the rotating cache's buffers do not hold the update");
+        hipLaunchKernelGGL(k_set_pos, dim3(1), dim3(1), 0, st, d->ring_rows, d->ring_row0);
+        PIE_LAUNCH_CHECK();
+    }
+    const bool mfma_attn = d->ring || pie_knob(PIE_KNOB_PREFILL_ATTN_VALU) != 1;  // 1 forces the row-per-launch-slice VALU kernel (tests compare the two)
     for (int c0 = 0; c0 < L; c0 += chunk) {
         const int M = L - c0 < chunk ? L - c0 : chunk;
         // h = embed_tokens(inputs)  (language.py:176)
@@ -792,7 +801,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
             if (d->kv_quant && (rc = kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, true, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st)))
                 return rc;
-            W4mRope re = {s->rope_cs, d->state, nullptr, kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
+            W4mRope re = {s->rope_cs, kvs, nullptr, kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
                           c.rope_traditional, s->q, nullptr, 0};
             bool roped = false;
             W4lSlabs sq, so, sd;  // K-split products handed over as fp32 slabs (q|k|v only without a bias: RoPE takes T(x W^T + b))
@@ -802,7 +811,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
                 const unsigned row_wgs = sq.S > 1 ? (M < 512 ? 4u : 1u) : 1u;  // few rows of slabs: four workgroups per row (256 tokens: 6.03 vs 6.20 ms; from 512 rows no difference)
                 decltype(&k_rope_append_rows<T, false, false>) rope_k = &k_rope_append_rows<T, false, false>;
                 if (sq.S > 1) rope_k = &k_rope_append_rows<T, true, false>;
-                hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, d->state, kv_table, li,
+                hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, kvs, kv_table, li,
                                    c.n_layers, c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, d->block_table, d->n_pages, s->rope_cs, (const int *)nullptr, 0,
                                    (u16 *)nullptr, (const int *)nullptr, (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, (size_t)0);
                 PIE_LAUNCH_CHECK();
@@ -811,7 +820,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
                 return rc;
             if (mfma_attn) {  // causal flash attention on the MFMA units (prefill_attn.hpp)
                 PrefillAttnArgs pa = {};
-                pa.q = s->q, pa.kv_table = kv_table, pa.layer = li, pa.n_layers = c.n_layers, pa.state = d->state;
+                pa.q = s->q, pa.kv_table = kv_table, pa.layer = li, pa.n_layers = c.n_layers, pa.state = kvs, pa.window = d->ring ? d->ring_w : 0;
                 pa.block_table = d->block_table, pa.n_pages = d->n_pages;
                 pa.M = M, pa.Hq = c.n_heads, pa.Hkv = c.n_kv_heads, pa.scale = 1.0f / sqrtf((float)D), pa.out = s->attn;
                 if ((rc = prefill_attn_launch_t<T>(pa, D, st))) return rc;
@@ -855,6 +864,10 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             PIE_HIP_TRY(hipMemcpyAsync(d->h, s->x + (size_t)(M - 1) * H, 2 * (size_t)H, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_add_pos, dim3(1), dim3(1), 0, st, d->state, last ? M - 1 : M);
         PIE_LAUNCH_CHECK();
+        if (d->ring && !last) {
+            hipLaunchKernelGGL(k_add_pos, dim3(1), dim3(1), 0, st, d->ring_rows, M);
+            PIE_LAUNCH_CHECK();
+        }
     }
     // logits[:, -1, :] -> logprobs -> greedy token; the tail advances the device-side offset past the last prompt token
     if ((rc = enqueue_kernel(d, PIE_K_LMHEAD, 0, nullptr, d->logits, st))) return rc;
@@ -862,6 +875,23 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
 }
 
 // mx.fast.scaled_dot_product_attention(q, k, v, scale, mask=causal) for L > 1 (models/base.py:37-53,111-113), op level.
+// The windowed form (RotatingKVCache prompts): query row r sees keys offset + r - window .. offset + r -- create_causal_mask(L, offset,
+// window_size=window) in index space (models/base.py:18-34).  Key blocks wholly below a tile's first row's bound are skipped.
+extern "C" int pie_sdpa_prefill_window(const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D, int window,
+                                       float scale, int dtype, void *out, void *stream) {
+    PIE_REQUIRE(q && k && v && out, PIE_E_ARG, "pie_sdpa_prefill_window: null pointer");
+    PIE_REQUIRE(L >= 1 && offset >= 0 && offset + L <= cap && window >= 1, PIE_E_SHAPE, "pie_sdpa_prefill_window: need offset + L <= cap, window >= 1");
+    PIE_REQUIRE(D == 64 || D == 128, PIE_E_SHAPE, "pie_sdpa_prefill_window: head_dim must be 64 or 128");
+    PIE_REQUIRE(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, PIE_E_SHAPE, "pie_sdpa_prefill_window: n_heads / n_kv_heads must be between 1 and 8");
+    PIE_REQUIRE(pie_aligned(q, 16) && pie_aligned(k, 16) && pie_aligned(v, 16) && pie_aligned(out, 8), PIE_E_ALIGN, "pie_sdpa_prefill_window: misaligned pointer");
+    PrefillAttnArgs a = {};
+    a.q = (const u16 *)q, a.k = (const u16 *)k, a.v = (const u16 *)v, a.offset = offset, a.cap = cap, a.window = window;
+    a.M = L, a.Hq = Hq, a.Hkv = Hkv, a.scale = scale, a.out = (u16 *)out;
+    if (dtype == PIE_BF16) return prefill_attn_launch_t<BF16>(a, D, (hipStream_t)stream);
+    if (dtype == PIE_F16) return prefill_attn_launch_t<F16>(a, D, (hipStream_t)stream);
+    return pie::fail(PIE_E_ARG, "pie_sdpa_prefill_window: dtype must be PIE_BF16 or PIE_F16");
+}
+
 extern "C" int pie_sdpa_prefill(const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D, float scale,
                                 int dtype, void *out, void *stream) {
     PIE_REQUIRE(q && k && v && out, PIE_E_ARG, "pie_sdpa_prefill: null pointer");

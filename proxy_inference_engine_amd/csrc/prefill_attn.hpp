@@ -42,6 +42,7 @@ struct PrefillAttnArgs {
     const int *seg_lo, *seg_hi;
     const int *block_table;              // paged KV (nullable, decoder only): kv_table holds the layers' slab K / V bases; key t
     int n_pages;                         //   lives in page block_table[t / 64] (each [Hkv, 64, D]) at row t % 64
+    int window;                          // > 0 (WIN instantiation, RotatingKVCache): row r also needs key >= offset + r - window
 };
 
 template <class T> struct MfmaT;
@@ -75,7 +76,7 @@ __device__ __forceinline__ int pa_off(int row, int ch) {
 // QT: 32-row query tiles per workgroup (1 or 2).  With QT = 2 the workgroup has 2*REP waves -- waves [0, REP) own the first
 // tile, [REP, 2 REP) the second -- and one staged K/V block serves 64 query rows: half the L2 -> LDS traffic and barriers per
 // unit of work, at the same number of waves per CU (one 8-wave workgroup instead of two 4-wave ones for REP = 4).
-template <class T, int D, int REP, int QT, bool SEG = false>
+template <class T, int D, int REP, int QT, bool SEG = false, bool WIN = false>
 __global__ void __launch_bounds__(REP * QT * 64) k_prefill_attn(const PrefillAttnArgs a) {
     constexpr int BK = 32, NT = REP * QT * 64, CH = D / 8, KS = D / 16, DT = D / 32;  // chunks per row, k-steps of Q.K^T, 32-dim output tiles
     constexpr int BM = 32 * QT;
@@ -99,7 +100,7 @@ __global__ void __launch_bounds__(REP * QT * 64) k_prefill_attn(const PrefillAtt
     // last / first key any row of this tile attends (segment bounds are non-decreasing in the row index)
     // (bounds clamped to the buffer: a bad segment table must not become a wild address)
     const int t_last = SEG ? max(min(a.seg_hi[r_last], a.cap), 1) - 1 : pos0 + r_last;
-    const int b_first = SEG ? min(max(a.seg_lo[wg_r0], 0), t_last) / BK : 0;
+    const int b_first = SEG ? min(max(a.seg_lo[wg_r0], 0), t_last) / BK : WIN ? max(pos0 + wg_r0 - a.window, 0) / BK : 0;
     const int n_blocks = t_last / BK + 1;
     const u16 *kbase = (a.state ? reinterpret_cast<const u16 *>(a.kv_table[a.layer]) : a.k) + (size_t)g * cap * D;
     const u16 *vbase = (a.state ? reinterpret_cast<const u16 *>(a.kv_table[a.n_layers + a.layer]) : a.v) + (size_t)g * cap * D;
@@ -146,7 +147,7 @@ __global__ void __launch_bounds__(REP * QT * 64) k_prefill_attn(const PrefillAtt
     for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const uint4 *>(a.q + ((size_t)qrow * a.Hq + hq) * D + 16 * s + 8 * h);
     // last (and, SEG, first) key this lane's query row attends (rows past M are padding: never stored)
     const int t_row = SEG ? a.seg_hi[qrow] - 1 : pos0 + r0 + c;
-    const int t_lo = SEG ? a.seg_lo[qrow] : 0;
+    const int t_lo = SEG ? a.seg_lo[qrow] : WIN ? pos0 + qrow - a.window : 0;
     const float sl2 = a.scale * ATTN_LOG2E;
 
     f32x16_t oacc[DT];
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(REP * QT * 64) k_prefill_attn(const PrefillAtt
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int t = t0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            sc[i] = (t <= t_row && (!SEG || t >= t_lo)) ? sacc[i] * sl2 : ATTN_NEG;
+            sc[i] = (t <= t_row && (!(SEG || WIN) || t >= t_lo)) ? sacc[i] * sl2 : ATTN_NEG;
             mloc = fmaxf(mloc, sc[i]);
         }
         mloc = xor32_max(mloc);  // the other 16 keys of the block live in the partner lane
@@ -199,8 +200,8 @@ __global__ void __launch_bounds__(REP * QT * 64) k_prefill_attn(const PrefillAtt
 #pragma unroll
         for (int i = 0; i < 16; i += 2) {
             const int ta = t0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            const float pa = (ta <= t_row && (!SEG || ta >= t_lo)) ? attn_exp2(sc[i] - m_run) : 0.0f;
-            const float pb = (ta + 1 <= t_row && (!SEG || ta + 1 >= t_lo)) ? attn_exp2(sc[i + 1] - m_run) : 0.0f;
+            const float pa = (ta <= t_row && (!(SEG || WIN) || ta >= t_lo)) ? attn_exp2(sc[i] - m_run) : 0.0f;
+            const float pb = (ta + 1 <= t_row && (!(SEG || WIN) || ta + 1 >= t_lo)) ? attn_exp2(sc[i + 1] - m_run) : 0.0f;
             l_run += pa + pb;
             const float ha = round_T<T>(pa), hb = round_T<T>(pb);
             phi[i >> 1] = pack2<T>(ha, hb);
@@ -249,7 +250,9 @@ static int prefill_attn_launch_d(const PrefillAttnArgs &a, hipStream_t st) {
     const bool two = rep <= 4 && a.M > 32 && (qt > 0 ? qt == 2 : ((a.M + 63) / 64) * a.Hkv >= 256);
     const dim3 grid(((a.M + (two ? 63 : 31)) / (two ? 64 : 32)) * a.Hkv);
 #define PA_LAUNCH(R)                                                                                         \
-    if (two && R <= 4) hipLaunchKernelGGL((k_prefill_attn<T, D, R, (R <= 4 ? 2 : 1)>), grid, dim3(R * 128), 0, st, a); \
+    if (a.window > 0 && two && R <= 4) hipLaunchKernelGGL((k_prefill_attn<T, D, R, (R <= 4 ? 2 : 1), false, true>), grid, dim3(R * 128), 0, st, a); \
+    else if (a.window > 0) hipLaunchKernelGGL((k_prefill_attn<T, D, R, 1, false, true>), grid, dim3(R * 64), 0, st, a); \
+    else if (two && R <= 4) hipLaunchKernelGGL((k_prefill_attn<T, D, R, (R <= 4 ? 2 : 1)>), grid, dim3(R * 128), 0, st, a); \
     else hipLaunchKernelGGL((k_prefill_attn<T, D, R, 1>), grid, dim3(R * 64), 0, st, a);                     \
     break
     switch (rep) {

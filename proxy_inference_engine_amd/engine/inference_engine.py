@@ -15,7 +15,7 @@ from collections.abc import Callable, Generator, Iterator
 import torch
 
 from .. import hip_ops
-from ..cache import PromptCache, QuantizedKVCache, ReusableKVCache
+from ..cache import BaseCache, PromptCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from ..cache.kv_cache import PagedKVCache
 from ..cache.kv_cache.quantized import check_format as check_kv_format
 from ..logits_processors import repetition_penalty_logits_processor
@@ -99,15 +99,24 @@ class InferenceEngine:
 
     # ------------------------------------------------------------------ the hot loop
     def generate_step(self, prompt_ids, pixel_values=None, mask=None, kv_bits: int | None = None, kv_group_size: int = 64,
-                      quantized_kv_start: int = 0) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
+                      quantized_kv_start: int = 0, max_kv_size: int | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
         """Yields (next_token_id[1] int32, logprobs[V] fp32) per step, forever (inference_engine.py:228-297).
         Prefill of the non-cached prompt suffix, then one forward per token; all device work is queued
         asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202).
         kv_bits (4 / 8; None = 16-bit KV), kv_group_size, quantized_kv_start: mlx_lm's KV quantization -- before a model call the
         prompt cache's layers become QuantizedKVCache once they hold more than quantized_kv_start positions (BaseCache.maybe_quantize,
-        cache/kv_cache/__init__.py:240-266)."""
+        cache/kv_cache/__init__.py:240-266).
+        max_kv_size (mlx_lm's name): the prompt cache becomes RotatingKVCache(max_kv_size, keep=4) per layer -- memory and step cost
+        bounded by the window; kv_bits then has no effect (a rotating cache stays 16-bit, as in the reference).  A prompt cache of
+        another kind or size is replaced by fresh rings (and back to the model's own caches when max_kv_size is None)."""
         if kv_bits is not None:
             check_kv_format(kv_group_size, kv_bits)
+        if max_kv_size is not None:
+            RotatingKVCache(max_kv_size, keep=4)  # ValueError for a window that cannot hold the 4 sink rows plus one
+            if getattr(self.model, "_page_pool", None) is not None:
+                raise ValueError("max_kv_size: a rotating KV cache runs on contiguous buffers, not on the model's KV pages")
+            if getattr(self.model, "tp", None) is not None:
+                raise ValueError("max_kv_size: a rotating KV cache is not available on a tensor-parallel model")
         if mask is not None and not (isinstance(mask, str) and mask == "causal"):
             check_generate_mask(mask, getattr(getattr(self.model, "args", None), "num_attention_heads", None))
         if pixel_values is not None and not hasattr(self.model, "get_input_embeddings"):
@@ -167,8 +176,15 @@ class InferenceEngine:
                 return tok, logprobs
             return sampler(logprobs[None]), logprobs                           # :271
 
+        cur = self.prompt_cache.cache
+        ring = bool(cur) and isinstance(cur[0], RotatingKVCache)
+        if cur and (ring != (max_kv_size is not None) or (ring and cur[0].max_size != max_kv_size)):
+            self.prompt_cache.cache, self.prompt_cache.computed_ids = [], []  # another cache kind: nothing of it is reusable
         if len(self.prompt_cache.cache) == 0:
-            self.prompt_cache.create_kv_cache(self.model)                      # :274-275
+            if max_kv_size is not None:
+                self.prompt_cache.cache = BaseCache.make_kv_cache(self.model, max_kv_size=max_kv_size)
+            else:
+                self.prompt_cache.create_kv_cache(self.model)                  # :274-275
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
         next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))   # :278 (host ids: no read-back)
@@ -197,7 +213,7 @@ class InferenceEngine:
         logprobs_map: dict[int, float] = {}
         stop_reason = "stop"
         token_count = 0
-        kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start") if inference_kwargs.get(k) is not None}
+        kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start", "max_kv_size") if inference_kwargs.get(k) is not None}
         for new_tokens, new_logprobs in self.generate_step(prompt_ids, **kv):
             token_count += new_tokens.numel()
             if collect_logprobs:

@@ -821,3 +821,48 @@ def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: in
 
 
 _sample_ws: dict = {}
+
+
+# ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)
+def kv_ring_order(keys: torch.Tensor, values: torch.Tensor, keep: int, n: int, shift: int, n_dst: int) -> None:
+    """In place on RotatingKVCache buffers [1, H, cap, D]: rows keep + j <- rows keep + (j + shift) % n for j < n_dst."""
+    for t in (keys, values):
+        _dev(t)
+        if t.dim() != 4 or t.shape[0] != 1 or not t.is_contiguous():
+            raise ValueError("kv_ring_order: contiguous [1, H, cap, D] buffers")
+    _, H, cap, D = keys.shape
+    scratch = torch.empty((2, H, max(n_dst, 1), D), dtype=keys.dtype, device=keys.device)
+    _ffi.check(_ffi.load().pie_kv_ring_order(_ffi.p(keys), _ffi.p(values), H, cap, D, keep, n, shift, n_dst, _ffi.p(scratch), _ffi.stream()))
+
+
+def sdpa_prefill_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, offset: int, window: int) -> torch.Tensor:
+    """Windowed causal prompt attention: q [1, Hq, L, D], k / v [1, Hkv, cap, D] with the L new rows at offset .. offset + L - 1;
+    query i sees rows offset + i - window .. offset + i (create_causal_mask(L, offset, window_size=window))."""
+    for t in (q, k, v):
+        _dev(t)
+    _, Hq, L, D = q.shape
+    Hkv, cap = k.shape[1], k.shape[2]
+    qt = q[0].transpose(0, 1).contiguous()
+    out = torch.empty_like(qt)
+    _ffi.check(_ffi.load().pie_sdpa_prefill_window(_ffi.p(qt), _ffi.p(k.contiguous()), _ffi.p(v.contiguous()), Hq, Hkv, L, offset, cap, D, window,
+                                                   float(scale), _ffi.dtype_code(q.dtype), _ffi.p(out), _ffi.stream()))
+    return out.transpose(0, 1).unsqueeze(0).contiguous()
+
+
+def sdpa_decode_ring(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, scale: float,
+                     pos: int, window: int, keep: int, rot0: int) -> torch.Tensor:
+    """The decoder's step attention on a ring: q [Hq, D]; k / v [Hkv, cap, D] ring buffers (updated in place: the new rows k_new / v_new
+    [Hkv, D] go to ring row slot(pos)); attends min(pos + 1, window) rows -> [Hq, D]."""
+    for t in (q, k, v, k_new, v_new):
+        _dev(t)
+    Hq, D = q.shape
+    Hkv, cap = k.shape[0], k.shape[1]
+    stage = torch.zeros((2, Hkv, 64, D), dtype=k.dtype, device=k.device)
+    stage[0, :, pos % 64] = k_new
+    stage[1, :, pos % 64] = v_new
+    lib = _ffi.load()
+    ws = torch.empty(lib.pie_sdpa_decode_workspace_bytes(Hq, D) + 32, dtype=torch.uint8, device=q.device)
+    out = torch.empty_like(q)
+    _ffi.check(lib.pie_sdpa_decode_ring(_ffi.p(q.contiguous()), _ffi.p(k), _ffi.p(v), _ffi.p(stage), Hq, Hkv, cap, D, pos, window, keep, rot0,
+                                        float(scale), _ffi.dtype_code(q.dtype), _ffi.p(out), _ffi.p(ws), _ffi.stream()))
+    return out

@@ -30,8 +30,14 @@ def create_attention_mask(h: torch.Tensor, cache=None):
     T = h.shape[1]
     if T <= 1:
         return None
-    offset = cache[0].offset if cache is not None and len(cache) > 0 else 0
-    return create_causal_mask(T, offset, device=h.device).to(h.dtype)
+    window_size, offset = None, 0
+    if cache is not None and len(cache) > 0:
+        c = cache[0]
+        if hasattr(c, "max_size"):  # a rotating cache: its retained window, then the chunk (base.py:37-53)
+            offset, window_size = min(c.max_size, c.offset), c.max_size
+        else:
+            offset = c.offset
+    return create_causal_mask(T, offset, window_size=window_size, device=h.device).to(h.dtype)
 
 
 def sanitize(weights: dict, tie_word_embeddings: bool) -> dict:

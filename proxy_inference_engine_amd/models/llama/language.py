@@ -19,7 +19,7 @@ import torch
 
 from .. import base
 from ... import _ffi, hip_ops
-from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, QuantizedKVCache, ReusableKVCache
+from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from .utils import Llama3RoPE
 
 
@@ -290,6 +290,7 @@ class Model:
         _ffi.check(lib.pie_decoder_bind_outputs(self._dec, _ffi.p(self.logits), _ffi.p(self.logprobs), _ffi.p(self.token), _ffi.p(self.hidden),
                                                 _ffi.p(self.history), self.history.numel()))
         self._kv_key = None      # (pointers, capacity) currently in the decoder's device table
+        self._ring_key = None    # (window, keep, rot0, row0, positions) of the bound rotating cache
         self._kv_hold = None
         self._page_pool, self._page_blocks = None, 16
         self._batch_bufs: dict = {}
@@ -387,6 +388,8 @@ class Model:
             return self._sync_paged(cache, n_new)
         if isinstance(cache[0], QuantizedKVCache):
             return self._sync_quant(cache, n_new)
+        if isinstance(cache[0], RotatingKVCache):
+            return self._sync_ring(cache, n_new)
         off = cache[0].offset
         for c in cache:
             if not isinstance(c, ReusableKVCache):
@@ -427,6 +430,43 @@ class Model:
             cols = [(C.c_void_p * n)(*[p[j] for p in ptrs]) for j in range(6)]
             _ffi.check(lib.pie_decoder_set_kv_quant(self._dec, *cols, cap, c0.group_size, c0.bits, _ffi.stream()))
             self._kv_key = key
+        if self._dev_offset != off:
+            _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
+            self._dev_offset = off
+
+    def _sync_ring(self, cache: list[RotatingKVCache], n_new: int) -> None:
+        """_sync_cache for RotatingKVCache layers (rotating.py): every layer's rows are rearranged for the update first (HIP row moves,
+        outside any captured graph), then the decoder is pointed at the ring -- its window and sink rows, the row rule of the steps and
+        the buffer row a prompt pass appends at.  Everything is checked before the first launch."""
+        c0 = cache[0]
+        for c in cache:
+            if not isinstance(c, RotatingKVCache):
+                raise TypeError("all layers of a rotating cache must be RotatingKVCache")
+            if (c.offset, c.max_size, c.keep, c._idx, c._len) != (c0.offset, c0.max_size, c0.keep, c0._idx, c0._len):
+                raise ValueError("layer caches disagree on offset or ring geometry")
+        if self.tp is not None:
+            raise ValueError("a rotating KV cache is not available on a tensor-parallel model")
+        if c0.keys is not None and (c0.keys.dtype != self.dtype or c0.keys.device != self.device):
+            raise ValueError("the rotating cache's buffers are not in the model's dtype / device")
+        rows = [c.prepare(n_new, self.n_kv_heads, self.head_dim, self.dtype, self.device) for c in cache]
+        cap = min(c.capacity for c in cache)
+        key = (tuple(c.keys.data_ptr() for c in cache), tuple(c.values.data_ptr() for c in cache), cap)
+        lib = _ffi.load()
+        if key != self._kv_key:
+            n = len(cache)
+            kp = (C.c_void_p * n)(*key[0])
+            vp = (C.c_void_p * n)(*key[1])
+            _ffi.check(lib.pie_decoder_set_kv(self._dec, kp, vp, cap, _ffi.stream()))
+            self._kv_key = key
+            self._ring_key = None
+        # the steps' positions stay below `positions` (the staging table covers them): grown in 64k steps
+        off = c0.offset
+        positions = ((off + n_new) // 65536 + 1) * 65536
+        row0 = rows[0] if n_new > 1 else 0
+        ring = (c0.max_size, c0.keep, c0._rot0, row0, positions)
+        if ring != getattr(self, "_ring_key", None):
+            _ffi.check(lib.pie_decoder_set_kv_ring(self._dec, c0.max_size, c0.keep, c0._rot0, row0, positions, _ffi.stream()))
+            self._ring_key = ring
         if self._dev_offset != off:
             _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
             self._dev_offset = off
@@ -481,10 +521,13 @@ class Model:
             return
         c0 = cache[0]
         offset = int(c0.page_manager.offset if isinstance(c0, PagedKVCache) else c0.offset)
+        window = None
+        if isinstance(c0, RotatingKVCache):  # the windowed mask create_attention_mask builds for a ring (models/base.py)
+            offset, window = min(c0.max_size, offset), c0.max_size
         m = torch.as_tensor(mask)
         blocked = (~m) if m.dtype == torch.bool else (m < 0)
         blocked = blocked.reshape(-1, blocked.shape[-1]) if blocked.dim() > 2 else blocked
-        want = base.create_causal_mask(L, offset, device=blocked.device) < 0
+        want = base.create_causal_mask(L, offset, window_size=window, device=blocked.device) < 0
         if blocked.shape != want.shape or not torch.equal(blocked, want):
             raise NotImplementedError(f"an explicit mask of shape {tuple(m.shape)} that is not the causal mask for {L} new positions at offset {offset} "
                                       "is not supported: the attention kernels apply the causal mask of models/base.py:37-53 implicitly")
