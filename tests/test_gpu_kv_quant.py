@@ -338,8 +338,10 @@ class RefQuantLlama:
         for li in range(self.nl):
             self.kq[li], self.vq[li] = self.quantize_rows(self.k[li]), self.quantize_rows(self.v[li])
 
-    def forward(self, ids, quantized=True):
-        """ids [L] at offset self.T -> logits of the last row (T-rounded fp32)."""
+    def forward(self, ids, quantized=True, extra=None):
+        """ids [L] at offset self.T -> logits of the last row (T-rounded fp32).  extra[li]: rows attended after the new ones (a kernel's
+        read past the end, for the long-context tests' sensitivity checks): quantized triples [Hkv, n, ...] on a step, fp32 (K, V)
+        [Hkv, n, D] on a 16-bit prompt, where only its last row sees them.  Not stored."""
         w, dt, D, L = self.w, self.dt, self.D, len(ids)
         e = "model.embed_tokens"
         h = po.dequantize(w[e + ".weight"][ids], w[e + ".scales"][ids], w[e + ".biases"][ids], 64, 4, dt)
@@ -357,13 +359,24 @@ class RefQuantLlama:
             if not quantized:  # 16-bit prompt
                 self.k[li] = np.concatenate([self.k[li], k], axis=1)
                 self.v[li] = np.concatenate([self.v[li], v], axis=1)
-                o = po.sdpa(q, self.k[li], self.v[li], scale, po.causal_mask(L, off, dt), dt, fused=True)
+                ks, vs, mask = self.k[li], self.v[li], po.causal_mask(L, off, dt)
+                if extra is not None:
+                    n = extra[li][0].shape[1]
+                    ks, vs = np.concatenate([ks, extra[li][0]], axis=1), np.concatenate([vs, extra[li][1]], axis=1)
+                    tail = np.full((L, n), mask.min(), np.float32)
+                    tail[-1] = 0.0
+                    mask = np.ascontiguousarray(np.concatenate([mask, tail], axis=1))
+                o = po.sdpa(q, ks, vs, scale, mask, dt, fused=True)
             else:
                 self.append(li, self.quantize_rows(k), self.quantize_rows(v))
                 T = off + L
                 if L == 1:
-                    flat = lambda t: tuple(a.reshape(self.Hkv * T, -1) for a in t)  # noqa: E731
-                    o = ref_attention(q[:, 0], flat(self.kq[li]), flat(self.vq[li]), self.Hkv, T, scale, self.gs, self.bits, dt)[:, None]
+                    kq, vq, Ta = self.kq[li], self.vq[li], T
+                    if extra is not None:
+                        kq, vq = (tuple(np.concatenate([a, b], axis=1) for a, b in zip(t, e)) for t, e in ((kq, extra[li][0]), (vq, extra[li][1])))
+                        Ta += extra[li][0][0].shape[1]
+                    flat = lambda t: tuple(a.reshape(self.Hkv * Ta, -1) for a in t)  # noqa: E731
+                    o = ref_attention(q[:, 0], flat(kq), flat(vq), self.Hkv, Ta, scale, self.gs, self.bits, dt)[:, None]
                 else:
                     deq = lambda t: po.dequantize(*(a.reshape(self.Hkv * T, -1) for a in t), self.gs, self.bits, dt).reshape(self.Hkv, T, D)  # noqa: E731
                     o = po.sdpa(q, deq(self.kq[li]), deq(self.vq[li]), scale, po.causal_mask(L, off, dt), dt, fused=True)

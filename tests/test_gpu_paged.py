@@ -57,6 +57,7 @@ def _fill(ops, alloc, rng, lens, Hkv, D, dt, max_blocks):
     (6, 2, 64, [129, 0, 64, 31]),          # an idle slot (context 0) in the batch
     (4, 4, 64, [200]),
     (16, 8, 128, [(7 * i) % 90 for i in range(64)]),   # 64 short sequences x 8 kv-heads: ONE split each, the kernel writes the result itself (no combine launch); idle slots among them
+    (32, 8, 128, [20000, 1, 8193]),        # long context: 313 pages in one sequence (22 splits: 512 workgroups over 3 x 8 kv-heads)
 ])
 def test_paged_attention_vs_oracle(ops, dt, Hq, Hkv, D, lens):
     from proxy_inference_engine_amd.cache.kv_cache.paged import PageAllocator
@@ -706,6 +707,7 @@ def test_prompt_pass_then_few_sequence_step_with_a_large_vocabulary():
     (16, 2, 128, [200, 70]),               # 8 q-heads per kv-head: the 2-wave form
     (4, 4, 64, [200]),
     (16, 8, 128, [(11 * i) % 70 for i in range(128)]),   # 128 short sequences x 8 kv-heads: one split each, written directly; idle slots among them
+    (32, 8, 128, [20000, 1, 8193]),        # long context: 313 pages in one sequence (22 splits: 512 workgroups over 3 x 8 kv-heads)
 ])
 def test_int8_pages_append_and_attention_vs_oracle(ops, dt, Hq, Hkv, D, lens):
     """The reference page's own storage: int8 K / V blocks + float16 per-head scales.  Appended rows equal the oracle's quantiser bit for

@@ -138,7 +138,9 @@ class RefRotatingLlama:
         self.idx += 1
         return None
 
-    def forward(self, ids):
+    def forward(self, ids, extra=None):
+        """extra[li]: (K, V) [Hkv, n, D] attended after the stored rows by a single-row update (a kernel's read of a row too many, for the
+        long-context tests' sensitivity checks)."""
         w, dt, D, L = self.w, self.dt, self.D, len(ids)
         e = "model.embed_tokens"
         h = po.dequantize(w[e + ".weight"][ids], w[e + ".scales"][ids], w[e + ".biases"][ids], 64, 4, dt)
@@ -158,6 +160,9 @@ class RefRotatingLlama:
             ks = np.stack([self.kv[li][r][0] for r in self.rows], 1)
             vs = np.stack([self.kv[li][r][1] for r in self.rows], 1)
             rows_seen = len(self.rows) if L >= 2 or self.offset >= self.W else self.offset
+            if extra is not None:
+                ks, vs = np.concatenate([ks[:, :rows_seen], extra[li][0]], 1), np.concatenate([vs[:, :rows_seen], extra[li][1]], 1)
+                rows_seen += extra[li][0].shape[1]
             o = po.sdpa(q, ks, vs, 1.0 / np.sqrt(D), mask, dt, fused=True, T=rows_seen)
             o = np.ascontiguousarray(po.round_T(o, dt).transpose(1, 0, 2)).reshape(L, self.Hq * D)
             h = po.add(h, self.lin(o, p + ".self_attn.o_proj", L), dt)
