@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- decode tokens/s of Llama-3-8B int4 g=64, batch 1, on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" = one decode step (one token) through InferenceEngine.generate_step: hipGraph replay of the fused
 HIP launch sequence, synthetic random-weight checkpoint (no network), weights and KV cache resident in HBM.
@@ -10,25 +10,29 @@ Workload (config.workload): Llama-3-8B-shaped, int4 group 64, bf16 activations, 
 N > 1: batch-1 decode has no independent units inside one sequence and the 8B model fits one card, so ranks are
 independent REPLICAS (one sequence each, no data-path collective): value = sum of tokens over ranks / max time.
 
+A plain run does only what the headline figure needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs, the line.
+Everything that takes runs of its own after the timed steps (the repetitions, the per-kernel and streaming-read roofline, the CPU
+oracle and its parity gate, the 70B tensor-parallel leg) runs only with --full.
+
 Prints ONE JSON line on rank 0 with the driver's contract plus:
-  roofline     -- the dominant kernel (gate/up W4S GEMV): algorithmic bytes per launch / mean launch duration,
-                  measured here with HIP events on the launch stream, against the 8 TB/s HBM3E peak;
-                  `step` = the same fraction for the whole decode step (the north-star figure).
+  roofline     -- `step`: the decode step's algorithmic HBM bytes / measured ms per step (the north-star figure; "achieved HBM GB/s"
+                  of `metric`) against the 8 TB/s HBM3E peak.  With --full also the dominant kernel (gate/up W4S GEMV):
+                  algorithmic bytes per launch / mean launch duration, measured here with HIP events on the launch stream;
                   `stream_peak` / `frac_of_stream`: the same against a bare streaming read measured in this run (pie_stream_read).
-                  `step.floor`: what the launch structure itself costs -- per dependent launch 1.59 us of command-processor time, 0.56 us of
+                  `step.floor` (--full): what the launch structure itself costs -- per dependent launch 1.59 us of command-processor time, 0.56 us of
                   workgroup start-up, 0.63 us to publish its output, 1.15 us until the consumer has touched it (the barrier-bit chain of
                   tools/pipeline_probe, profiles/r04_pipeline_probe.txt) -- plus the step's bytes at the stream rate measured in this run;
                   `ms_per_step / floor` says how far the step is from ITS floor, `frac` how far from 8 TB/s.
-  tp70b        -- only with --gpus N > 1 on the default workload: after the replicas' timing the same ranks decode ONE Llama-3-70B int4
+  tp70b        -- only with --full and --gpus N > 1 on the default workload: after the replicas' timing the same ranks decode ONE Llama-3-70B int4
                   sequence tensor-parallel (BASELINE.json configs[4]), once per communicator backend (IPC one-shot, RCCL); `value` stays
                   the replicas figure.
   dump_outputs -- with --dump-outputs DIR: what the last timed step returned to its caller (rank 0's token id and logprobs[V]),
                   written as DIR/token.npy (float64) and DIR/logprobs.npy (float32).  Weights and prompt are seeded, so the same
                   arguments give the same inputs on every run and two builds can be compared output for output.
-  repetitions  -- 5 repetitions of the K timed steps (the first is `value`): median and min ms per step.
-  cpu_baseline -- the CPU oracle (oracle/pie_oracle.c, OpenMP) timed on this box's host cores on a bounded sample, at the GPU run's
-                  context (the same 128-token prompt).
-  parity       -- the same oracle steps teacher-forced through the HIP model (full 32 layers, V = 128256), outside the timed
+  repetitions  -- --full: 5 repetitions of the K timed steps (the first is `value`): median and min ms per step.
+  cpu_baseline -- --full: the CPU oracle (oracle/pie_oracle.c, OpenMP) timed on this box's host cores on a bounded sample, at the GPU
+                  run's context (the same 128-token prompt); a plain run reports it as not measured (`value` null).
+  parity       -- --full: the same oracle steps teacher-forced through the HIP model (full 32 layers, V = 128256), outside the timed
                   region: greedy ids where the oracle's top-2 margin exceeds the bound, max / rms logit error in bf16 ulps of
                   the largest logit; the process exits non-zero when it fails.
 """
@@ -57,8 +61,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--layers", type=int, default=0, help="debug: override num_hidden_layers (invalidates the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-tokens", type=int, default=48)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need, each in runs of its own after the "
+                    "timed steps: repetitions, the gate/up kernel and streaming-read roofline, the CPU oracle and its parity gate, the 70B TP leg (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle and its parity gate")
+    ap.add_argument("--cpu-tokens", type=int, default=48, help="--full: decode steps of the CPU oracle and its parity gate")
     ap.add_argument("--kv-splits", type=int, default=0)
     ap.add_argument("--paged", action="store_true", help="KV cache in 64-token pages of one slab (PagedKVCache) instead of contiguous per-layer buffers")
     ap.add_argument("--model", choices=["8b", "70b", "qv", "3b"], default="8b",
@@ -238,120 +244,14 @@ def tp70b_leg(args, rank, world, dist):
     return out
 
 
-def main():
-    args = parse()
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    n_dev = torch.cuda.device_count()
-    torch.cuda.set_device(local_rank % max(n_dev, 1))  # one rank per GPU; PIE_BENCH_BACKEND=gloo lets ranks share a card (rehearsal)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = os.environ.get("PIE_BENCH_BACKEND", "nccl")  # "nccl" is RCCL on ROCm
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-        else:
-            dist.init_process_group(backend)
-
-    from proxy_inference_engine_amd import InferenceEngine
-    from proxy_inference_engine_amd.models.llama import Model, ModelArgs
-    from proxy_inference_engine_amd.models.utils import LLAMA3_8B, LLAMA3_70B, LLAMA32_3B, QWEN2VL_7B_TEXT, synthetic_checkpoint
-
-    for kv in args.knob:
-        from proxy_inference_engine_amd import _ffi as _knob_ffi
-        name, _, value = kv.partition("=")
-        _knob_ffi.set_knob(name, int(value))
-    cfg = dict({"70b": LLAMA3_70B, "qv": QWEN2VL_7B_TEXT, "3b": LLAMA32_3B}.get(args.model, LLAMA3_8B))
-    if args.layers:
-        cfg["num_hidden_layers"] = args.layers
-    if args.dense:
-        cfg["quantization"] = None
-    elif args.bits != 4:
-        cfg["quantization"] = {"group_size": 64, "bits": args.bits}
-    tp = args.tp if args.tp > 1 else 0
-    if tp and (tp != world or args.dense or args.bits != 4 or args.paged):
-        raise SystemExit("--tp N needs N ranks (--gpus N under torch.distributed.run), int4 weights and contiguous caches")
-    comm = None
-    if tp:
-        full_cfg = cfg
-        cfg, weights, comm = tp_shard(full_cfg, tp, rank, dist, args.tp_backend)
-    else:
-        # heavy-tailed lm_head rows: the parity gate's id comparison needs steps whose greedy token is decided by more than rounding noise
-        # (models/utils.py: synthetic_checkpoint); same shapes and bytes, so the timing is that of any Llama-3-8B int4 checkpoint
-        weights = synthetic_checkpoint(cfg, seed=0, dtype=torch.bfloat16, lm_head_tail=1.5)
-    # the CPU oracle + the teacher-forced parity gate run for every one-card configuration except the 70B model (its oracle step takes 3 s and
-    # 120 GB of host memory twice over); dense weights: 8 oracle steps (15 GB per step at 16 bits + 30 GB in float32)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.model in ("8b", "qv", "3b")
-    cpu_tokens = min(args.cpu_tokens, 8) if args.dense else args.cpu_tokens
-    weights_host = None
-    if want_cpu:  # the oracle reads the same checkpoint, in the reference's on-disk layout, from host memory
-        weights_host = {k: (v.cpu().numpy().view(np.uint32) if v.dtype == torch.int32 else v.view(torch.int16).cpu().numpy().view(np.uint16))
-                        for k, v in weights.items()}
-    model = Model(ModelArgs(**cfg), weights, kv_splits=args.kv_splits, tp=comm)
-    del weights
-    torch.cuda.empty_cache()
-
-    if args.paged:
-        model.enable_paged_kv(num_pages=(args.prompt + args.warmup + args.steps + 2) // 64 + 2)
-    eng = InferenceEngine(model=model)
-    prompt = torch.randint(0, cfg["vocab_size"], (args.prompt,), generator=torch.Generator().manual_seed(1 if tp else 1 + rank))
-    eng.prepare_engine(prompt, temp=0)
-    gen = eng.generate_step(prompt)
-    next(gen)  # prefill + first token
-    for _ in range(args.warmup):
-        next(gen)
-
-    def barrier():
-        torch.cuda.synchronize()
-        if dist is not None:
-            dist.barrier()
-            torch.cuda.synchronize()
-
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last = next(gen)
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    # copied to the host before anything else runs on the device: the step's output buffers are reused by later steps
-    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
-    del last
-    launches_per_step = model.graph_launches(True)  # kernel nodes of the captured step graph (hipGraphGetNodes), not a formula
-    # SURVEY 8(d): 5 repetitions, median and min.  `value` stays the driver's contract (the K steps just timed); four more repetitions of
-    # the same K steps from the same prompt (the prefix cache makes the re-prefill one token) are reported beside it.
-    rep_ms = [1e3 * elapsed / args.steps]
-    if world == 1 and not args.layers:
-        for _ in range(4):
-            gen = eng.generate_step(prompt)
-            next(gen)
-            for _ in range(args.warmup):
-                next(gen)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                next(gen)
-            torch.cuda.synchronize()
-            rep_ms.append(1e3 * (time.perf_counter() - t1) / args.steps)
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-        dist.barrier()
-    tokens_per_s = (1 if tp else world) * args.steps / elapsed  # TP: all ranks decode ONE sequence together
-    T_mid = args.prompt + 1 + args.warmup + args.steps // 2  # context length in the middle of the timed region
-    step_bytes = model.step_bytes(T_mid, True)
-    step_gbps = step_bytes * (args.steps / elapsed) / 1e9  # per GPU
-
+def roofline_full(args, model, n_l, elapsed, T_mid, step_bytes, step_gbps, launches_per_step):
+    """--full: the `roofline` object with the figures that take runs of their own after the timed steps -- the dominant kernel timed
+    alone, a bare streaming read -- and the launch floor measured against them."""
     # dominant kernel (gate/up GEMV: 38 % of the step's bytes), timed alone with HIP events on the launch stream,
     # cycling through the layers so every launch streams weights that are not in the 256 MiB Infinity Cache.
     # Events bracket a whole sweep over the layers (back-to-back launches on the launch stream), so the figure is the
     # kernel's steady-state duration -- what rocprofv3 --kernel-trace reports per dispatch -- not launch gaps.
     reps = 8
-    n_l = cfg["num_hidden_layers"]
     for li in range(n_l):
         model.launch_kernel("gate_up", li)
     torch.cuda.synchronize()
@@ -412,6 +312,123 @@ def main():
     if args.model == "8b" and args.bits == 4 and not args.dense and not args.layers:
         floor["ms_per_step_over_probe_chain"] = (1e3 * elapsed / args.steps) / 1.150
 
+    return {"bound": "hbm", "kernel": "k_w4s_gemv<bf16, rmsnorm, swiglu> (gate/up)", "achieved": k_gbps, "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s", "frac": k_gbps / HBM_PEAK_GBPS, "traffic": traffic, "bytes_per_launch": k_bytes,
+            "ms_per_launch": k_ms,
+            "stream_peak": stream_gbps, "frac_of_stream": k_gbps / stream_gbps,  # measured in this run: pie_stream_read over 1 GiB
+            "step": {"achieved": step_gbps, "frac": step_gbps / HBM_PEAK_GBPS, "frac_of_stream": step_gbps / stream_gbps, "bytes_per_step": step_bytes,
+                     "floor": floor}}
+
+
+def main():
+    args = parse()
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
+    n_dev = torch.cuda.device_count()
+    torch.cuda.set_device(local_rank % max(n_dev, 1))  # one rank per GPU; PIE_BENCH_BACKEND=gloo lets ranks share a card (rehearsal)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        backend = os.environ.get("PIE_BENCH_BACKEND", "nccl")  # "nccl" is RCCL on ROCm
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group(backend)
+
+    from proxy_inference_engine_amd import InferenceEngine
+    from proxy_inference_engine_amd.models.llama import Model, ModelArgs
+    from proxy_inference_engine_amd.models.utils import LLAMA3_8B, LLAMA3_70B, LLAMA32_3B, QWEN2VL_7B_TEXT, synthetic_checkpoint
+
+    for kv in args.knob:
+        from proxy_inference_engine_amd import _ffi as _knob_ffi
+        name, _, value = kv.partition("=")
+        _knob_ffi.set_knob(name, int(value))
+    cfg = dict({"70b": LLAMA3_70B, "qv": QWEN2VL_7B_TEXT, "3b": LLAMA32_3B}.get(args.model, LLAMA3_8B))
+    if args.layers:
+        cfg["num_hidden_layers"] = args.layers
+    if args.dense:
+        cfg["quantization"] = None
+    elif args.bits != 4:
+        cfg["quantization"] = {"group_size": 64, "bits": args.bits}
+    tp = args.tp if args.tp > 1 else 0
+    if tp and (tp != world or args.dense or args.bits != 4 or args.paged):
+        raise SystemExit("--tp N needs N ranks (--gpus N under torch.distributed.run), int4 weights and contiguous caches")
+    comm = None
+    if tp:
+        full_cfg = cfg
+        cfg, weights, comm = tp_shard(full_cfg, tp, rank, dist, args.tp_backend)
+    else:
+        # heavy-tailed lm_head rows: the parity gate's id comparison needs steps whose greedy token is decided by more than rounding noise
+        # (models/utils.py: synthetic_checkpoint); same shapes and bytes, so the timing is that of any Llama-3-8B int4 checkpoint
+        weights = synthetic_checkpoint(cfg, seed=0, dtype=torch.bfloat16, lm_head_tail=1.5)
+    # the CPU oracle + the teacher-forced parity gate run for every one-card configuration except the 70B model (its oracle step takes 3 s and
+    # 120 GB of host memory twice over); dense weights: 8 oracle steps (15 GB per step at 16 bits + 30 GB in float32)
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model in ("8b", "qv", "3b")
+    cpu_tokens = min(args.cpu_tokens, 8) if args.dense else args.cpu_tokens
+    weights_host = None
+    if want_cpu:  # the oracle reads the same checkpoint, in the reference's on-disk layout, from host memory
+        weights_host = {k: (v.cpu().numpy().view(np.uint32) if v.dtype == torch.int32 else v.view(torch.int16).cpu().numpy().view(np.uint16))
+                        for k, v in weights.items()}
+    model = Model(ModelArgs(**cfg), weights, kv_splits=args.kv_splits, tp=comm)
+    del weights
+    torch.cuda.empty_cache()
+
+    if args.paged:
+        model.enable_paged_kv(num_pages=(args.prompt + args.warmup + args.steps + 2) // 64 + 2)
+    eng = InferenceEngine(model=model)
+    prompt = torch.randint(0, cfg["vocab_size"], (args.prompt,), generator=torch.Generator().manual_seed(1 if tp else 1 + rank))
+    eng.prepare_engine(prompt, temp=0)
+    gen = eng.generate_step(prompt)
+    next(gen)  # prefill + first token
+    for _ in range(args.warmup):
+        next(gen)
+
+    def barrier():
+        torch.cuda.synchronize()
+        if dist is not None:
+            dist.barrier()
+            torch.cuda.synchronize()
+
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        last = next(gen)
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    # copied to the host before anything else runs on the device: the step's output buffers are reused by later steps
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
+    del last
+    launches_per_step = model.graph_launches(True)  # kernel nodes of the captured step graph (hipGraphGetNodes), not a formula
+    # SURVEY 8(d): 5 repetitions, median and min.  `value` stays the driver's contract (the K steps just timed); four more repetitions of
+    # the same K steps from the same prompt (the prefix cache makes the re-prefill one token) are reported beside it.
+    rep_ms = [1e3 * elapsed / args.steps]
+    if args.full and world == 1 and not args.layers:
+        for _ in range(4):
+            gen = eng.generate_step(prompt)
+            next(gen)
+            for _ in range(args.warmup):
+                next(gen)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                next(gen)
+            torch.cuda.synchronize()
+            rep_ms.append(1e3 * (time.perf_counter() - t1) / args.steps)
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+        dist.barrier()
+    tokens_per_s = (1 if tp else world) * args.steps / elapsed  # TP: all ranks decode ONE sequence together
+    T_mid = args.prompt + 1 + args.warmup + args.steps // 2  # context length in the middle of the timed region
+    step_bytes = model.step_bytes(T_mid, True)
+    step_gbps = step_bytes * (args.steps / elapsed) / 1e9  # per GPU
+    n_l = cfg["num_hidden_layers"]
+
     shape_cfg = full_cfg if tp else cfg
     out = {
         "metric": (f"decode tokens/sec, Llama-3-{args.model.upper()} int4 g=64 batch=1, TP={tp}; achieved HBM GB/s per GPU" if tp else
@@ -426,16 +443,14 @@ def main():
                    "parallelism": f"TP={tp} ({args.tp_backend} collectives)" if tp else ("replicas" if world > 1 else "single GPU"),
                    "launches_per_step": launches_per_step,  # kernel nodes of the captured hipGraph
                    "hipgraph": True, "kv": "paged (64-token pages)" if args.paged else "contiguous"},
-        "roofline": {"bound": "hbm", "kernel": "k_w4s_gemv<bf16, rmsnorm, swiglu> (gate/up)", "achieved": k_gbps, "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": k_gbps / HBM_PEAK_GBPS, "traffic": traffic, "bytes_per_launch": k_bytes,
-                     "ms_per_launch": k_ms,
-                     "stream_peak": stream_gbps, "frac_of_stream": k_gbps / stream_gbps,  # measured in this run: pie_stream_read over 1 GiB
-                     "step": {"achieved": step_gbps, "frac": step_gbps / HBM_PEAK_GBPS, "frac_of_stream": step_gbps / stream_gbps, "bytes_per_step": step_bytes,
-                              "floor": floor}},
+        "roofline": (roofline_full(args, model, n_l, elapsed, T_mid, step_bytes, step_gbps, launches_per_step) if args.full else
+                     {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                      "step": {"achieved": step_gbps, "frac": step_gbps / HBM_PEAK_GBPS, "bytes_per_step": step_bytes}}),
         "dump_outputs": dumped,
-        "repetitions": {"ms_per_step": rep_ms, "median_ms_per_step": float(np.median(rep_ms)), "min_ms_per_step": float(np.min(rep_ms))},
     }
-    if world > 1 and not tp and args.model == "8b" and args.bits == 4 and not args.dense and not args.layers and not args.paged \
+    if args.full:
+        out["repetitions"] = {"ms_per_step": rep_ms, "median_ms_per_step": float(np.median(rep_ms)), "min_ms_per_step": float(np.min(rep_ms))}
+    if args.full and world > 1 and not tp and args.model == "8b" and args.bits == 4 and not args.dense and not args.layers and not args.paged \
             and os.environ.get("PIE_BENCH_TP70B", "1") != "0":
         del eng, gen, model
         eng = gen = model = None
@@ -452,7 +467,7 @@ def main():
                 out["parity"] = {"ok": False, "error": str(e)}
         else:
             out["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": 0, "kind": "port",
-                                   "sample": "skipped (timed on rank 0 at N=1 only)"}
+                                   "sample": "skipped (timed on rank 0 at N=1 only)" if args.full else "not measured (bench.py --full)"}
         print(json.dumps(out), flush=True)
     if comm is not None:
         err = comm.status()

@@ -16,6 +16,6 @@ try A_nomega_graph rocprofv3 --kernel-trace --stats --output-format csv -d $O/A 
 try B_nomega_eager rocprofv3 --kernel-trace --stats --output-format csv -d $O/B -- $B --model 8b --mode launch --steps 32 --warmup 4 --no-mega --graph 0
 try C_tiny rocprofv3 --kernel-trace --stats --output-format csv -d $O/C -- $B --model tiny --mode launch --steps 8 --warmup 2 --no-mega --graph 0
 cd $R
-try D_python rocprofv3 --kernel-trace --stats --output-format csv -d $O/D -- python3 bench.py --no-cpu-baseline --steps 16 --warmup 4
+try D_python rocprofv3 --kernel-trace --stats --output-format csv -d $O/D -- python3 bench.py --full --no-cpu-baseline --steps 16 --warmup 4
 find $O -name "*.csv" -size +20M -delete
 tail -4 $O/*.log

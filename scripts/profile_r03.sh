@@ -20,7 +20,7 @@ run step_fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/step_fetch -
 run step_write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/step_write -- $B --model 8b --mode launch --no-mega --graph 0 --steps 8 --warmup 2 --sync-every 1
 run engine_fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/engine_fetch -- $B --model 8b --mode mega --graph 0 --steps 8 --warmup 2 --sync-every 1
 run engine_write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/engine_write -- $B --model 8b --mode mega --graph 0 --steps 8 --warmup 2 --sync-every 1
-(cd $R && run bench_stats rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- /usr/bin/python3.10 bench.py --no-cpu-baseline --steps 64 --warmup 8)
+(cd $R && run bench_stats rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- "$(readlink -f "$(command -v python3)")" bench.py --full --no-cpu-baseline --steps 64 --warmup 8)
 $B --model 8b --steps 200 --warmup 20 > $O/plain.log 2>&1 || true
 $R/tools/step_bench --model 8b --check 1 --steps 1 --warmup 1 | grep -i "library\|device" > $O/version.log 2>&1 || true
 /usr/bin/python3.10 -c "import sys; sys.path.insert(0, '$R'); from proxy_inference_engine_amd import _ffi; print(_ffi.load().pie_version().decode())" > $O/pie_version.txt 2>/dev/null || true

@@ -6,6 +6,6 @@ O=$R/gpurun_out/r5/bench2
 mkdir -p $O
 cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0 PIE_BENCH_BACKEND=gloo
-timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps ${STEPS:-32} --warmup 8 > $O/bench_2rank.log 2>&1
+timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps ${STEPS:-32} --warmup 8 > $O/bench_2rank.log 2>&1
 echo "rc=$?"; grep -E '^\{' $O/bench_2rank.log | python -c "import sys, json; d = json.loads(sys.stdin.read()); print(json.dumps({k: d[k] for k in ('value', 'n_gpus', 'ms_per_step', 'tp70b')}, indent=1)); print(json.dumps(d['roofline']['step']['floor'], indent=1))"
 tail -n 5 $O/bench_2rank.log | cut -c1-300

@@ -10,4 +10,4 @@ cd /tmp && export TMPDIR=/tmp
 B=$R/tools/step_bench
 timeout -k 10 200 $B --model 8b --steps 256 --warmup 32 > $O/step_bits4.log 2>&1; tail -n 3 $O/step_bits4.log
 timeout -k 10 200 $B --model 8b --bits 2 --steps 256 --warmup 32 > $O/step_bits2.log 2>&1; tail -n 3 $O/step_bits2.log
-cd $R && timeout -k 10 500 python bench.py --bits 2 > $O/r05_bench_line_bits2.json 2> $O/bits2.err; tail -c 1500 $O/r05_bench_line_bits2.json; tail -n 3 $O/bits2.err
+cd $R && timeout -k 10 500 python bench.py --full --bits 2 > $O/r05_bench_line_bits2.json 2> $O/bits2.err; tail -c 1500 $O/r05_bench_line_bits2.json; tail -n 3 $O/bits2.err
