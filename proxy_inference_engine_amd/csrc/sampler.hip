@@ -5,14 +5,15 @@
 // mx.random.categorical = argmax(x + Gumbel noise).  The reference's default request has temp = 1.0, so this runs once per token right
 // behind the decode step.  Restated with library ops it is a sort of 128 k floats plus ~10 small launches (150-200 us, 10-15 % of a
 // step); a first single-workgroup version of this file took 120-480 us because one CU did all the arithmetic.  This form spreads a
-// row over up to 256 workgroups and needs no sort:
+// row over up to 1024 workgroups of 512 ids (V <= 524288) and needs no sort:
 //   * the filter is "every id whose value is at least T": T comes from a 3-digit radix select (11 + 11 + 10 bits) over the
 //     order-preserving 32-bit keys of x = logprob / temp.  Each digit is one launch: workgroups histogram their slice in LDS and add
 //     the bins to a global histogram with 64-bit INTEGER atomics (order-independent); the next launch's workgroups all walk that
 //     histogram to the same digit.  top-k counts ids; top-p weighs them with exp(x - max) as 2^-40 fixed-point integers and looks
 //     for the ascending cumulative mass (1 - top_p) x total -- exact arithmetic where the reference's fp32 cumsum over the sorted row
 //     rounds as it goes, so the kept set can differ from the reference's only for ids whose cumulative mass lies within that rounding
-//     of 1 - top_p; min-p is a plain threshold, max + log(min_p), joined with the top min_tokens_to_keep;
+//     of 1 - top_p; every id tied at the threshold value is kept (the reference's argsort order keeps only the tied ids it happens
+//     to sort last); min-p is a plain threshold, max + log(min_p), joined with the top min_tokens_to_keep;
 //   * equal values at the top-k boundary are common (log-probabilities of bf16 logits repeat): exactly k ids are kept, the ties with
 //     the lowest vocabulary index first (mx.argpartition leaves the choice open);
 //   * the draw is argmax(x + G) over the kept ids, G = -log(-log(u)), u from Philox-4x32-10 keyed by (seed, call counter, row,

@@ -19,7 +19,8 @@ __global__ void __launch_bounds__(256) k_logits_stats(const u16 *logits, int V, 
     const int tile_len = (V + gridDim.x - 1) / gridDim.x;
     const int begin = blockIdx.x * tile_len, end = min(V, begin + tile_len);
     float mx = -INFINITY;
-    int arg = 0x7fffffff;
+    // a thread's first index is its argmax until a larger value comes: a tile (or row) of -inf answers its first index, like mx.argmax
+    int arg = begin + (int)threadIdx.x < end ? begin + (int)threadIdx.x : 0x7fffffff;
     for (int i = begin + threadIdx.x; i < end; i += 256) {
         const float v = T::to_f32(logits[i]);
         if (v > mx) mx = v, arg = i;  // ascending i per thread: first maximal index wins
@@ -43,7 +44,7 @@ __global__ void __launch_bounds__(256) k_logits_stats(const u16 *logits, int V, 
     if (threadIdx.x == 0) {
         LogitStat st;
         st.max = tmax, st.sumexp = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3], st.argmax = targ, st.pad = 0;
-        stats[blockIdx.x] = st;  // empty tile: max = -inf, sumexp = 0, argmax = INT_MAX
+        stats[blockIdx.x] = st;  // empty tile: max = -inf, sumexp = 0, argmax = INT_MAX (loses every tie with a real -inf tile)
     }
 }
 

@@ -804,8 +804,10 @@ def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: in
         x = x.float()
     x = x.contiguous()
     rows, V = x.shape
-    seed, counter = _rng.hip_state(x.device)
     lib = _ffi.load()
+    if int(lib.pie_sample_workspace_bytes(rows, V)) == 0:  # V > 524288 (1024 workgroups of 512 ids) or an empty block: refused, nothing launched
+        raise ValueError(f"sample: a [rows, V] block with rows >= 1 and 1 <= V <= 524288, got [{rows}, {V}]")
+    seed, counter = _rng.hip_state(x.device)
     key = (str(x.device), rows, V)
     ws = _sample_ws.get(key)
     if ws is None:  # zeroed once; the kernels leave it ready for the next call

@@ -126,6 +126,86 @@ def _ref_sets(logprobs, temp, top_p=0.0, min_p=0.0, keep=1, top_k=-1):
     return set(range(len(x)))
 
 
+def _ref_kept32(logprobs, temp, top_p=0.0, min_p=0.0, keep=1, top_k=-1):
+    """The reference's filters in the reference's own precision, as a bool mask [V] (top-p: the kernel's exact rule, _topp_sets).
+    x = fp32(lp) * fp32(1 / temp); min-p keeps x >= fp32(max + fp32(log(min_p))) together with the first `keep` ids of the stable
+    descending order; top-k keeps the first k ids of a stable sort on (-x, index) -- ties go to the lowest vocabulary index, the
+    product's documented rule where mx.argpartition leaves the choice open."""
+    x = np.asarray(logprobs, np.float32) * np.float32(1.0 / temp)
+    V = x.shape[0]
+    if 0 < top_p < 1.0:
+        return _topp_sets(x, top_p)[0]
+    kept = np.zeros(V, bool)
+    if min_p != 0.0:
+        kept = x >= np.float32(x.max() + np.float32(np.log(min_p)))
+        kept[np.argsort(-x, kind="stable")[:keep]] = True
+        return kept
+    if top_k > 0:
+        kept[np.argsort(-x, kind="stable")[:top_k]] = True
+        return kept
+    return np.ones(V, bool)
+
+
+def _topp_sets(x, top_p):
+    """Top-p over x = the already scaled fp32 values -> (exact, ref, margin, v).
+    exact: the kernel's rule.  Tie classes merged, masses exp(x - max) in float64: v is the smallest value with
+      mass{x < v} <= fp32(1 - top_p) * total < mass{x <= v};  kept = {x >= v}  (empty when no value qualifies).
+    margin: the distance of the target from the nearer end of v's interval, as a fraction of the total mass.
+    ref: the reference's set -- fp32 softmax, stable ascending sort, sequential fp32 cumsum, keep cum > fp32(1 - top_p) (as _ref_sets)."""
+    x = np.asarray(x, np.float32)
+    xd = x.astype(np.float64)
+    fin = np.isfinite(xd)
+    m = xd[fin].max() if fin.any() else 0.0
+    w = np.where(fin, np.exp(xd - m), 0.0)
+    total = w.sum()
+    target = float(np.float32(1.0 - top_p)) * total
+    vals, inv = np.unique(x, return_inverse=True)                 # ascending classes (-inf first)
+    mass = np.bincount(inv.reshape(-1), weights=w, minlength=len(vals))
+    hi = np.cumsum(mass)
+    lo = hi - mass
+    c = np.nonzero((lo <= target) & (target < hi))[0]
+    if len(c):
+        v = vals[c[0]]
+        exact = x >= v
+        margin = min(target - lo[c[0]], hi[c[0]] - target) / total
+    else:
+        v, exact, margin = np.float32(np.inf), np.zeros(x.shape[0], bool), 0.0
+    p = (w / total).astype(np.float32) if total > 0 else np.zeros(x.shape[0], np.float32)
+    order = np.argsort(p, kind="stable")
+    cum = np.cumsum(p[order], dtype=np.float32)
+    ref = np.zeros(x.shape[0], bool)
+    ref[order[cum > np.float32(1 - top_p)]] = True
+    return exact, ref, margin, v
+
+
+def _topp_relations(x, top_p, exact, ref):
+    """The two top-p sets of _topp_sets differ only by (a) ids of the tie class at v -- the kernel keeps the whole class, the sorted
+    cumulative sum splits it -- and (b) ids whose exact ascending cumulative mass lies within the fp32 cumsum's rounding of
+    1 - top_p: |fp32 cumsum_i - cum_i| <= (i + 4) * 2^-23 * cum_i for the i-th partial sum (i roundings of the running sum, a few of
+    the fp32 softmax).  Returns the ids that break both."""
+    x = np.asarray(x, np.float32)
+    v = _topp_sets(x, top_p)[3]
+    xd = x.astype(np.float64)
+    fin = np.isfinite(xd)
+    w = np.where(fin, np.exp(xd - (xd[fin].max() if fin.any() else 0.0)), 0.0)
+    if w.sum() == 0:                                                  # all -inf: both sets are empty
+        return np.nonzero(exact ^ ref)[0].tolist()
+    p = w / w.sum()
+    order = np.argsort(p.astype(np.float32), kind="stable")
+    cum = np.cumsum(p[order])
+    pos = np.empty_like(order)
+    pos[order] = np.arange(len(order))
+    bad = []
+    for i in np.nonzero(exact ^ ref)[0]:
+        if x[i] == v:
+            continue
+        j = pos[i]
+        if abs(cum[j] - float(np.float32(1 - top_p))) <= (j + 5) * 2.0 ** -23 * cum[j] + 2.0 ** -24:
+            continue
+        bad.append(int(i))
+    return bad
+
+
 @pytest.mark.parametrize("kw", [dict(top_p=0.6), dict(top_p=0.95), dict(min_p=0.1), dict(min_p=0.3, min_tokens_to_keep=4),
                                 dict(top_k=5), dict()])
 def test_sampler_reference_keep_sets_and_distribution(kw):
@@ -238,3 +318,109 @@ def test_generate_step_mask_arrays_that_the_reference_loop_can_carry():
                      (torch.full((1, 1), float("-inf")), "hides every key")):
         with pytest.raises(ValueError, match=why):
             check_generate_mask(bad, 4)
+
+
+# ------------------------------------------------------------------ the fp32 restatement of the sampler filters on designed rows
+def _modes(row):
+    """(mode name, keyword arguments of _ref_kept32 / make_sampler) for every branch of make_sampler on a designed row."""
+    return [("top_k", dict(top_k=row.top_k)), ("top_p", dict(top_p=row.top_p)), ("min_p", dict(min_p=row.min_p)),
+            ("min_p_keep", dict(min_p=row.min_p, keep=row.keep)), ("categorical", dict())]
+
+
+def _unique_answer(x, mode, kw):
+    """True when the reference's own definition leaves no choice to its sort order (no tie across the boundary, a top-p crossing
+    far from every step of the cumulative sum)."""
+    xs = np.sort(x)[::-1]
+    if mode == "top_k":
+        k = kw["top_k"]
+        return xs[k - 1] > xs[k] or xs[k] == -np.inf
+    if mode.startswith("min_p"):
+        keep = kw.get("keep", 1)
+        thr = np.float32(xs[0] + np.float32(np.log(kw["min_p"])))
+        return keep >= len(xs) or xs[keep - 1] > xs[keep] or xs[keep] >= thr or xs[keep] == -np.inf
+    if mode == "top_p":
+        exact, ref, margin, _ = _topp_sets(x, kw["top_p"])
+        if not np.array_equal(exact, ref) or margin < 1e-4:
+            return False
+        p = np.exp(x.astype(np.float64) - x.max())
+        cum = np.cumsum(np.sort(p / p.sum()))
+        return np.min(np.abs(cum - (1 - kw["top_p"]))) > 1e-4 and len(np.unique(x[exact])) == int(exact.sum())
+    return True
+
+
+def test_fp32_restatement_agrees_with_the_torch_reference_on_designed_rows():
+    """_ref_kept32 (the filters in fp32, ties by index) against tests/sampler_reference.py's op-for-op torch restatement, on every designed
+    row and branch where the reference's answer is unique; compared on the finite ids (the torch filters mark the drawable ids)."""
+    from tests import sampler_reference as sr
+    from tests.sampler_rows import families
+    compared = 0
+    for V in (64, 513, 4099, 32000):
+        for row in families(V, seed=V):
+            if not np.isfinite(row.lp).any():
+                continue
+            x = row.lp * np.float32(1.0 / row.temp)
+            for mode, kw in _modes(row):
+                if not _unique_answer(x, mode, kw):
+                    continue
+                mine = _ref_kept32(row.lp, row.temp, **kw) & np.isfinite(x)
+                tkw = dict(kw)
+                if "keep" in tkw:
+                    tkw["min_tokens_to_keep"] = tkw.pop("keep")
+                theirs = sr.kept_mask(torch.from_numpy(row.lp)[None], row.temp, **tkw)[0].numpy()
+                assert np.array_equal(mine, theirs), (V, row.name, mode, np.nonzero(mine ^ theirs)[0][:8])
+                compared += 1
+    assert compared >= 120, compared
+
+
+def test_top_p_exact_rule_and_reference_set_differ_only_at_the_threshold():
+    """The kernel's top-p rule keeps the whole tie class at the threshold value v; the reference's sorted fp32 cumsum keeps part of it
+    (a deliberate difference, csrc/sampler.hip's header) and rounds as it goes.  On every designed row the two sets differ only by
+    that tie class and by ids within the cumsum's rounding of 1 - top_p; on the designed top-p tie they differ by exactly half the class."""
+    from tests.sampler_rows import families, topp_tie
+    for V in (64, 513, 4099, 32000, 128256):
+        for row in families(V, seed=V + 1):
+            for top_p in (row.top_p, 0.3, 0.95):
+                x = row.lp * np.float32(1.0 / row.temp)
+                exact, ref, _, _ = _topp_sets(x, top_p)
+                assert _topp_relations(x, top_p, exact, ref) == [], (V, row.name, top_p)
+    for V in (64, 4099, 152064):
+        row = topp_tie(V, seed=3)
+        exact, ref, margin, v = _topp_sets(row.lp, row.top_p)
+        tie = row.notes["tie"]
+        assert margin > 0.1 and v == row.lp[tie[0]]
+        assert set(np.nonzero(exact)[0]) == set(tie) | set(row.notes["big"])
+        assert set(np.nonzero(exact & ~ref)[0]) == set(tie[:3]) and not (ref & ~exact).any()   # stable ascending: the last 3 stay
+
+
+def test_fp32_scaling_merges_what_float64_keeps_apart():
+    """At temp 3.0 fp32(x * fp32(1/3)) maps two adjacent log-probs to one value: in the reference's precision they tie at the top-k
+    boundary (the lower index is kept), while the float64 comparator _ref_sets still orders them (it keeps the larger, higher index)."""
+    from tests.sampler_rows import merged_by_temp
+    for V in (64, 4099, 128256):
+        row = merged_by_temp(V, seed=V)
+        lo, hi = row.notes["lo"], row.notes["hi"]
+        assert row.lp[hi] > row.lp[lo] and np.float32(row.lp[hi] * np.float32(1 / 3.0)) == np.float32(row.lp[lo] * np.float32(1 / 3.0))
+        k32 = _ref_kept32(row.lp, row.temp, top_k=row.top_k)
+        k64 = _ref_sets(row.lp, row.temp, top_k=row.top_k)
+        assert k32[lo] and not k32[hi] and hi in k64 and lo not in k64 and int(k32.sum()) == row.top_k
+
+
+def test_designed_rows_are_what_they_claim():
+    """The generator's rows (tests/sampler_rows.py) have the structure the kernel tests rely on."""
+    from tests import sampler_rows as R
+    for V in (4099, 128256, R.V_MAX):
+        w = R.wide_tie(V, seed=1)
+        tie, x = w.notes["tie"], w.lp
+        assert len(tie) >= 36 and len(np.unique(tie // R.SLICE)) >= 8 and (x[tie] == x[tie[0]]).all()
+        assert int((x > x[tie[0]]).sum()) == 20 and 20 < w.top_k < 20 + len(tie)
+        assert any(t % 2 == 0 and t + 1 in set(tie.tolist()) for t in tie)          # ids one kernel thread owns together
+        last = R.wide_tie(V, seed=1, last_slice=True)
+        assert (last.notes["tie"] // R.SLICE == (V - 1) // R.SLICE).all() or V - (V - 1) // R.SLICE * R.SLICE < 40
+        for n in (1, 3, 600):
+            sp = R.sparse(V, n, seed=2)
+            fin = np.isfinite(sp.lp)
+            assert int(fin.sum()) == n and sp.top_k > n and not fin[R.SLICE:2 * R.SLICE].any()
+        q = R.quantized(V, seed=3)
+        assert len(np.unique(q.lp)) < 4096                                          # bf16: a few thousand values at most
+        assert np.sort(q.lp)[::-1][q.top_k - 1] == np.sort(q.lp)[::-1][q.top_k]     # k inside a tie class
+    assert R.VOCABS[-1] == R.V_MAX == 524288
