@@ -48,7 +48,7 @@ enum {
     PIE_KNOB_PREFILL_MIN = 0,        /* prompts shorter than this run as iterated decode steps (MLX's qmv regime); default 6, min 2 */
     PIE_KNOB_PREFILL_CHUNK = 1,      /* rows per prompt chunk; default 4096 (16..8192) */
     PIE_KNOB_PREFILL_RESIDENT = 2,   /* GiB budget for resident dequantised layer matrices; default: half of the free HBM; 0 = none */
-    PIE_KNOB_SMALL_M = 3,            /* rows up to which int4 Linears that k_w4r_gemm does not take use the few-row kernel; default 32; 0 = the T copy + library GEMM */
+    PIE_KNOB_SMALL_M = 3,            /* rows up to which int4 Linears that k_w4r_gemm does not take use the few-row kernel; default 32; 0 = the many-row tile kernel takes them */
     PIE_KNOB_W4L_SLABS = 4,          /* 0: K-split products of the int4 GEMMs reduced by their own launch instead of by their consumers (bit-equal) */
     PIE_KNOB_PREFILL_ATTN_VALU = 5,  /* 1: the VALU prompt attention instead of the MFMA flash kernel (the tests' cross-check) */
     PIE_KNOB_PREFILL_QT = 6,         /* 1 / 2: one / two 32-row query tiles per prompt-attention workgroup */
@@ -129,7 +129,7 @@ int pie_qgemv_w6g64(const void *x, int M, const void *packed, int N, int K, cons
  * "bits": 4 | 8}; nn.quantize takes any group_size in {32, 64, 128}, models/utils.py:96-111): weight uint32 [N, K*bits/32], scales / biases
  * T [N, K/32].  Same call sites and streaming kernel as the group-64 paths on "W4S32" units of 2560 B / "W8S32" units of 4608 B: the W4S / W8S
  * unit with TWO {scale | bias << 16} words per lane (its code pieces are two consecutive 32-wide groups).  Decode steps and prompts below 6
- * rows multiply in the exact-fp32 regime (one pass over the weights per row); longer prompts dequantise to T and call the library GEMM. */
+ * rows multiply in the exact-fp32 regime (one pass over the weights per row); longer prompts dequantise to a W16M copy for k_w16l_gemm. */
 size_t pie_w4s32_bytes(int N_out, int K);
 int pie_repack_w4g32(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out,
                      void *packed, void *stream);

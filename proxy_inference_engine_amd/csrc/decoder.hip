@@ -285,6 +285,21 @@ static int enqueue_step(pie_decoder *d, const int *token_ptr, bool with_logits, 
     return enqueue_kernel(d, PIE_K_TAIL, 0, token_ptr, logits_dst, st);
 }
 
+int capture_graph(const std::function<int(hipStream_t)> &enqueue, int *enqueue_rc, hipGraph_t *graph, hipError_t *end_err) {
+    *enqueue_rc = PIE_OK, *graph = nullptr, *end_err = hipSuccess;
+    hipStream_t cs = nullptr;
+    PIE_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    const hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) {
+        (void)hipStreamDestroy(cs);
+        return pie::fail(PIE_E_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
+    }
+    *enqueue_rc = enqueue(cs);
+    *end_err = hipStreamEndCapture(cs, graph);
+    (void)hipStreamDestroy(cs);
+    return PIE_OK;
+}
+
 extern "C" {
 
 const char *pie_hello(void) { return "pie_core \xe2\x9c\x93"; }
@@ -600,29 +615,18 @@ int pie_decoder_step(pie_decoder *d, int flags, void *stream) {
     const bool with_logits = (flags & PIE_STEP_LOGITS) != 0;
     if (!(flags & PIE_STEP_GRAPH)) return enqueue_step(d, &d->state->token, with_logits, d->logits, st);
     const int gi = with_logits ? 1 : 0;
-    if (d->graph[gi] && d->graph_fused[gi] && !fuse_attn(d, 0)) drop_graphs(d);  // fusion was withdrawn (knob, a third live decoder): capture the two-launch form
+    if (d->graph[gi] && d->graph_fused[gi] && !fuse_attn(d, 0)) drop_graphs(d);  // fusion was withdrawn (knob, more than four live decoders): capture the two-launch form
     if (!d->graph[gi]) {
         d->graph_fused[gi] = fuse_attn(d, 0);
-        if (d->graph[gi]) {
-            (void)hipGraphExecDestroy(d->graph[gi]);
-            d->graph[gi] = nullptr;
-        }
-        // Capture on a private stream (the caller's may be the legacy default stream, which cannot be captured);
-        // the instantiated graph is then launched on the caller's stream.
+        // captured on a private stream, launched on the caller's
         hipGraph_t g = nullptr;
-        hipStream_t cs = nullptr;
-        PIE_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-        if (e != hipSuccess) {
-            (void)hipStreamDestroy(cs);
-            return pie::fail(PIE_E_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
-        }
-        rc = enqueue_step(d, &d->state->token, with_logits, d->logits, cs);
-        e = hipStreamEndCapture(cs, &g);
-        (void)hipStreamDestroy(cs);
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
+        hipError_t e = hipSuccess;
+        int erc = PIE_OK;
+        if ((rc = capture_graph([&](hipStream_t cs) { return enqueue_step(d, &d->state->token, with_logits, d->logits, cs); }, &erc, &g, &e)))
             return rc;
+        if (erc) {
+            if (g) (void)hipGraphDestroy(g);
+            return erc;
         }
         if (e != hipSuccess) return pie::fail(PIE_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
         {  // what the graph really holds, for the benchmark's launches_per_step (not a formula)

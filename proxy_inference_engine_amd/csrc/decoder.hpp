@@ -1,5 +1,6 @@
 // decoder.hpp -- the decoder object shared by decoder.hip (single-token step) and prefill.hip (batched prompt).
 #pragma once
+#include <functional>
 #include <unordered_map>
 #include <vector>
 
@@ -105,8 +106,13 @@ int paged_kv_append_i8_staged_launch(int dtype, const void *stage_k, const void 
 // paged_i8.hip: split-KV decode attention over int8 pages (a.slab = the layer's int8 slab, a.ctx_len / a.block_table as for T pages)
 int paged_attn_i8_launch(int dtype, int D, const AttnArgs &a, hipStream_t st);
 
-// prefill.hip: batched prompt processing (L >= prefill_min_rows() tokens): per layer the W4S weights are dequantised to T
-// and multiplied by hipBLASLt, with hand-written HIP kernels for RoPE + cache append, causal attention and SwiGLU.
+// decoder.hip: captures the launches enqueue(stream) queues into a graph, on a private non-blocking stream (the caller's may be the legacy default
+// stream, which cannot be captured) in thread-local mode.  Returns the failure to begin the capture (enqueue did not run), else PIE_OK with
+// enqueue's result in *enqueue_rc and the graph (the caller's to destroy) in *graph, or hipStreamEndCapture's error in *end_err.
+int capture_graph(const std::function<int(hipStream_t)> &enqueue, int *enqueue_rc, hipGraph_t *graph, hipError_t *end_err);
+
+// prefill.hip: batched prompt processing (L >= prefill_min_rows() tokens): per layer many-row GEMMs on the weights' W4M tiles (int4) or
+// W16M copies (the other formats), with hand-written HIP kernels for RoPE + cache append, causal attention and SwiGLU.
 int prefill_min_rows();
 int prefill_batched(pie_decoder *d, const int32_t *ids, const void *embeds, int L, void *logits_all, hipStream_t st);
 void prefill_free(pie_decoder *d);

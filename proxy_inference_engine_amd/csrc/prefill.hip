@@ -568,11 +568,11 @@ int w4r_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int
                     const W4mRope *rope, int *slabs, bool *bias_done, bool wide_scales);
 
 // int4 checkpoints: prompts beyond small_rows() rows run the hand-written many-row W4 MFMA GEMM on the same W4M tiles -- no 16-bit
-// copy of the weights, no hipBLASLt (which remains the path of shapes the tile kernels do not take: N not a multiple of 32).
-static bool w4l_enabled() { return true; }
-// Dense (16-bit) modules keep the library GEMM: for 16-bit weights hipBLASLt is a plain GEMM done well.  The hand-written 16-bit kernel of
-// rounds 2-3 (k_w16l_gemm: 0-20 % slower on prompts, 15-38 % on the vision tower's small shapes) was deleted in round 4 (EXPERIMENTS.md).
-// Rows up to which an int4 Linear runs on the W4M kernel instead of the T copy + hipBLASLt (PIE_KNOB_SMALL_M: 0 disables, max 32).
+// copy of the weights, except for shapes the tile kernels do not take (N not a multiple of 32), which multiply a W16M copy on k_w16l_gemm.
+// Dense (16-bit), int8 and group-32 modules multiply their W16M copy on k_w16l_gemm (w16_gemm.hpp): the hand-written 16-bit MFMA GEMM of
+// round 5, which replaced the library GEMM (EXPERIMENTS.md).
+// Rows up to which an int4 Linear that k_w4r_gemm does not take runs on the few-row W4M kernel instead of the many-row tile kernel
+// (PIE_KNOB_SMALL_M: 0 disables, max 32).
 static int small_rows() {
     const int k = pie_knob(PIE_KNOB_SMALL_M);
     const int v = k >= 0 ? k : 32;
@@ -689,7 +689,7 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
             return bias_rows<T>(y, bias, M, N, st);
         }
     }
-    if (is_int4 && N % 32 == 0 && K % 64 == 0 && w4l_enabled()) {  // beyond 256 rows: the many-row tile kernels
+    if (is_int4 && N % 32 == 0 && K % 64 == 0) {  // beyond 256 rows: the many-row tile kernels
         void *wm = nullptr;
         int rc = w4m_tiles(&wm);
         if (rc) return rc;
@@ -730,6 +730,62 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
     return rc;
 }
 
+// ---------------------------------------------------------------- what the many-row passes share
+// Elements of the 16-bit weight scratch: the largest W16M copy a pass may build (with_lm_head: the lm_head goes through linear_rows too)
+static size_t w16_copy_elems(const pie_decoder_config &c, bool with_lm_head) {
+    const int H = c.hidden, NQKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, I = c.inter;
+    size_t w_elems = w16m_size(2 * I, H) / 2;  // the 16-bit copies are W16M tiles (rows padded to 32, columns to 64)
+    if (w16m_size(NQKV, H) / 2 > w_elems) w_elems = w16m_size(NQKV, H) / 2;
+    if (w16m_size(H, I) / 2 > w_elems) w_elems = w16m_size(H, I) / 2;
+    if (with_lm_head && w16m_size(c.vocab, H) / 2 > w_elems) w_elems = w16m_size(c.vocab, H) / 2;
+    return w_elems;
+}
+
+// h = embed_tokens(ids) (language.py:176) for M rows into x
+static int embed_rows(const pie_decoder *d, const int32_t *ids, int M, u16 *x, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    if (d->mat_fmt(d->glob.embed_codes) == PIE_W_DENSE) return pie_embedding_dense(ids, M, d->glob.embed_codes, c.vocab, c.hidden, c.dtype, x, st);
+    return embedding_launch(ids, M, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, c.vocab, c.hidden, c.dtype, x, nullptr, nullptr,
+                            nullptr, 0, st, embed_bits(d));
+}
+
+// The k_rope_append_rows form for a q|k|v projection handed over as fp32 slabs or not, appended to int8 pages or not
+template <class T>
+static decltype(&k_rope_append_rows<T>) rope_append_kernel(bool slabs, bool i8) {
+    if (slabs) return i8 ? &k_rope_append_rows<T, true, true> : &k_rope_append_rows<T, true, false>;
+    return i8 ? &k_rope_append_rows<T, false, true> : &k_rope_append_rows<T, false, false>;
+}
+
+// The rest of a decoder layer after its attention, on M rows: o_proj of s->attn, the residual adds on s->x, the MLP in between, and
+// the norm that follows the layer into s->xn -- next_norm: the next block's input_layernorm or the final norm (language.py:187);
+// nullptr: the layer ends in the plain add and s->xn is left as it is.
+template <class T>
+static int mlp_rows(pie_decoder *d, const pie_layer_weights &w, int M, const void *next_norm, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    const int H = c.hidden, QD = c.n_heads * c.head_dim, I = c.inter;
+    PrefillScratch *s = d->prefill;
+    W4lSlabs so, sd;  // o_proj / down handed to their consumers as K-split fp32 slabs where the shape qualifies
+    int rc;
+    if ((rc = linear_rows<T>(d, w.wo, H, QD, s->attn, M, s->r, st, true, w.bo, false, nullptr, nullptr, nullptr, H <= 8192 ? &so : nullptr)))
+        return rc;
+    // h = x + r (language.py:151) + post_attention_layernorm(h) for MLP.__call__ (language.py:126-127)
+    if ((rc = add_rms_norm_rows<T>(s->x, s->r, w.mlp_norm, c.rms_eps, M, H, c.dtype, s->xn, st, so.S > 1 ? w.bo : nullptr, &so)))
+        return rc;
+    bool fused_act = false;
+    if ((rc = linear_rows<T>(d, w.wgateup, 2 * I, H, s->xn, M, s->gu, st, true, w.bgateup, false, s->act, &fused_act))) return rc;
+    if (!fused_act) {
+        const size_t n_act = (size_t)M * I;
+        hipLaunchKernelGGL(k_swiglu_rows<T>, dim3((unsigned)((n_act / 4 + 255) / 256)), dim3(256), 0, st, s->gu, n_act, s->act);
+        PIE_LAUNCH_CHECK();
+    }
+    if ((rc = linear_rows<T>(d, w.wdown, H, I, s->act, M, s->r, st, true, w.bdown, false, nullptr, nullptr, nullptr,
+                             next_norm && H <= 8192 ? &sd : nullptr)))
+        return rc;
+    // out = h + r (language.py:153), fused with the norm that follows when there is one
+    if (!next_norm) return pie_add(s->x, s->r, (size_t)M * H, c.dtype, s->x, st);
+    return add_rms_norm_rows<T>(s->x, s->r, next_norm, c.rms_eps, M, H, c.dtype, s->xn, st, sd.S > 1 ? w.bdown : nullptr, &sd);
+}
+
 // Quantized KV (pie_decoder_set_kv_quant): the T scratch of one layer's K and V at the cache's capacity and the table that points every layer at it.
 static int kvq_scratch_reserve(pie_decoder *d) {
     const pie_decoder_config &c = d->cfg;
@@ -751,13 +807,9 @@ static int kvq_scratch_reserve(pie_decoder *d) {
 template <class T>
 static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int L, void *logits_all, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
-    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD, I = c.inter;
+    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
     const int chunk = prefill_chunk_rows() < L ? prefill_chunk_rows() : L;
-    size_t w_elems = w16m_size(2 * I, H) / 2;  // the 16-bit copies are W16M tiles (rows padded to 32, columns to 64)
-    if (w16m_size(NQKV, H) / 2 > w_elems) w_elems = w16m_size(NQKV, H) / 2;
-    if (w16m_size(H, I) / 2 > w_elems) w_elems = w16m_size(H, I) / 2;
-    if (logits_all && w16m_size(c.vocab, H) / 2 > w_elems) w_elems = w16m_size(c.vocab, H) / 2;
-    int rc = scratch_reserve(d, chunk, w_elems, d->splits);
+    int rc = scratch_reserve(d, chunk, w16_copy_elems(c, logits_all != nullptr), d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     // quantized KV: the pass runs on the T scratch (kv_table below), the layer's codes are expanded into it and the chunk's rows quantized back
@@ -783,15 +835,10 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
     for (int c0 = 0; c0 < L; c0 += chunk) {
         const int M = L - c0 < chunk ? L - c0 : chunk;
         // h = embed_tokens(inputs)  (language.py:176)
-        if (embeds) {  // h = inputs_embeds (models/intern/language.py:155-158)
+        if (embeds)  // h = inputs_embeds (models/intern/language.py:155-158)
             PIE_HIP_TRY(hipMemcpyAsync(s->x, (const u16 *)embeds + (size_t)c0 * H, (size_t)M * H * 2, hipMemcpyDeviceToDevice, st));
-            rc = PIE_OK;
-        } else
-            rc = d->mat_fmt(d->glob.embed_codes) == PIE_W_DENSE
-                 ? pie_embedding_dense(ids + c0, M, d->glob.embed_codes, c.vocab, H, c.dtype, s->x, st)
-                 : embedding_launch(ids + c0, M, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, c.vocab, H, c.dtype, s->x, nullptr,
-                                    nullptr, nullptr, 0, st, embed_bits(d));
-        if (rc) return rc;
+        else if ((rc = embed_rows(d, ids + c0, M, s->x, st)))
+            return rc;
         hipLaunchKernelGGL(k_rope_cs_rows, dim3(M), dim3(64), 0, st, d->glob.rope_freqs, d->state, nullptr, D / 2, s->rope_cs);
         PIE_LAUNCH_CHECK();
         for (int li = 0; li < c.n_layers; ++li) {
@@ -804,13 +851,12 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             W4mRope re = {s->rope_cs, kvs, nullptr, kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
                           c.rope_traditional, s->q, nullptr, 0};
             bool roped = false;
-            W4lSlabs sq, so, sd;  // K-split products handed over as fp32 slabs (q|k|v only without a bias: RoPE takes T(x W^T + b))
+            W4lSlabs sq;  // q|k|v as the fp32 slabs of a K-split product (no Linear bias: RoPE takes T(x W^T + b))
             if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, M, s->qkv, st, true, w.bqkv, false, nullptr, &roped, &re, w.bqkv ? nullptr : &sq)))
                 return rc;
             if (!roped) {
                 const unsigned row_wgs = sq.S > 1 ? (M < 512 ? 4u : 1u) : 1u;  // few rows of slabs: four workgroups per row (256 tokens: 6.03 vs 6.20 ms; from 512 rows no difference)
-                decltype(&k_rope_append_rows<T, false, false>) rope_k = &k_rope_append_rows<T, false, false>;
-                if (sq.S > 1) rope_k = &k_rope_append_rows<T, true, false>;
+                const auto rope_k = rope_append_kernel<T>(sq.S > 1, false);
                 hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, kvs, kv_table, li,
                                    c.n_layers, c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, d->block_table, d->n_pages, s->rope_cs, (const int *)nullptr, 0,
                                    (u16 *)nullptr, (const int *)nullptr, (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, (size_t)0);
@@ -832,28 +878,8 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
                 a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
                 if ((rc = attn_decode_launch(c.dtype, D, a, true, st))) return rc;
             }
-            if ((rc = linear_rows<T>(d, w.wo, H, QD, s->attn, M, s->r, st, true, w.bo, false, nullptr, nullptr, nullptr,
-                                     H <= 8192 ? &so : nullptr)))
-                return rc;
-            // h = x + r (language.py:151) + post_attention_layernorm(h) for MLP.__call__ (language.py:126-127)
-            if ((rc = add_rms_norm_rows<T>(s->x, s->r, w.mlp_norm, c.rms_eps, M, H, c.dtype, s->xn, st, so.S > 1 ? w.bo : nullptr, &so)))
-                return rc;
-            bool fused_act = false;
-            if ((rc = linear_rows<T>(d, w.wgateup, 2 * I, H, s->xn, M, s->gu, st, true, w.bgateup, false, s->act, &fused_act))) return rc;
-            if (!fused_act) {
-                const size_t n_act = (size_t)M * I;
-                hipLaunchKernelGGL(k_swiglu_rows<T>, dim3((unsigned)((n_act / 4 + 255) / 256)), dim3(256), 0, st, s->gu, n_act, s->act);
-                PIE_LAUNCH_CHECK();
-            }
-            const bool fused_next = li + 1 < c.n_layers;
-            if ((rc = linear_rows<T>(d, w.wdown, H, I, s->act, M, s->r, st, true, w.bdown, false, nullptr, nullptr, nullptr,
-                                     fused_next && H <= 8192 ? &sd : nullptr)))
-                return rc;
-            // out = h + r (language.py:153), fused with the next block's input_layernorm when there is one
-            if (fused_next)
-                rc = add_rms_norm_rows<T>(s->x, s->r, d->layers[li + 1].attn_norm, c.rms_eps, M, H, c.dtype, s->xn, st, sd.S > 1 ? w.bdown : nullptr, &sd);
-            else rc = pie_add(s->x, s->r, (size_t)M * H, c.dtype, s->x, st);
-            if (rc) return rc;
+            // the last layer ends in the plain add: the final norm runs below, and only for logits on every position
+            if ((rc = mlp_rows<T>(d, w, M, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : nullptr, st))) return rc;
         }
         if (logits_all) {  // lm_head on every position, like the reference (language.py:205-209)
             if ((rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
@@ -926,21 +952,18 @@ static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
 }
 
 // ---------------------------------------------------------------- one decode step for B sequences (continuous batching)
-// The weights stream once for all B rows (few-row int4 GEMM for B <= 32, the T copy + hipBLASLt beyond); each row is its own
-// sequence: RoPE at its own position, K/V appended to its own page, attention over its own block table (k_attn_decode PAGED,
-// one sequence per blockIdx.z), lm_head + tail on every row.  What the reference's Scheduler / BatchDetails / PagedAttention
-// skeleton (src/pie_core/include/engine/batch_details.hpp:10-88, scheduler.hpp) describes for decode-state sequences.
+// The weights stream once for all B rows (linear_rows: up to 5 rows the streaming GEMV where the format has one, beyond that int4 matrices
+// on their W4M tiles and the others on the W16M copy + k_w16l_gemm); each row is its own sequence: RoPE at its own position, K/V appended
+// to its own page, attention over its own block table (k_attn_decode PAGED, one sequence per blockIdx.z), lm_head + tail on every row.
+// What the reference's Scheduler / BatchDetails / PagedAttention skeleton (src/pie_core/include/engine/batch_details.hpp:10-88,
+// scheduler.hpp) describes for decode-state sequences.
 template <class T>
 static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *ctx_len, const void *const *slabs, int n_pages,
                           const int32_t *block_tables, int max_blocks, int B, u16 *logits, float *logprobs, int32_t *next_tokens, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD, I = c.inter;
-    size_t w_elems = w16m_size(2 * I, H) / 2;  // the 16-bit copies are W16M tiles (rows padded to 32, columns to 64)
-    if (w16m_size(NQKV, H) / 2 > w_elems) w_elems = w16m_size(NQKV, H) / 2;
-    if (w16m_size(H, I) / 2 > w_elems) w_elems = w16m_size(H, I) / 2;
-    if (w16m_size(c.vocab, H) / 2 > w_elems) w_elems = w16m_size(c.vocab, H) / 2;
     const int splits = batch_attn_splits(d, B, max_blocks);
-    int rc = scratch_reserve(d, B, w_elems, splits > d->splits ? splits : d->splits);
+    int rc = scratch_reserve(d, B, w16_copy_elems(c, true), splits > d->splits ? splits : d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     const int lm_waves = w4s_gemv_waves(c.vocab, H);  // the fused few-sequence form: one log-softmax partial per GEMV wave and row
@@ -954,8 +977,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
     for (const pie_layer_weights &w : d->layers)
         if (w.bqkv || w.bo || w.bgateup || w.bdown) fused_rows = false;
     if (fused_rows) {
-        rc = embedding_launch(tokens, B, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, c.vocab, H, c.dtype, s->x, nullptr, nullptr, nullptr, 0, st, 4);
-        if (rc) return rc;
+        if ((rc = embed_rows(d, tokens, B, s->x, st))) return rc;
         hipLaunchKernelGGL(k_rope_cs_rows, dim3(B), dim3(64), 0, st, d->glob.rope_freqs, nullptr, ctx_len, D / 2, s->rope_cs);
         PIE_LAUNCH_CHECK();
         for (int li = 0; li < c.n_layers; ++li) {
@@ -993,11 +1015,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         PIE_LAUNCH_CHECK();
         return PIE_OK;
     }
-    rc = d->mat_fmt(d->glob.embed_codes) == PIE_W_DENSE
-             ? pie_embedding_dense(tokens, B, d->glob.embed_codes, c.vocab, H, c.dtype, s->x, st)
-             : embedding_launch(tokens, B, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, c.vocab, H, c.dtype, s->x, nullptr, nullptr,
-                                nullptr, 0, st, embed_bits(d));
-    if (rc) return rc;
+    if ((rc = embed_rows(d, tokens, B, s->x, st))) return rc;
     hipLaunchKernelGGL(k_rope_cs_rows, dim3(B), dim3(64), 0, st, d->glob.rope_freqs, nullptr, ctx_len, D / 2, s->rope_cs);
     PIE_LAUNCH_CHECK();
     for (int li = 0; li < c.n_layers; ++li) {
@@ -1011,9 +1029,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, B, s->qkv, st, true, w.bqkv, false, nullptr, &roped, &re, w.bqkv ? nullptr : &sq)))
             return rc;
         if (!roped) {
-            decltype(&k_rope_append_rows<T, false, false>) rope_k = &k_rope_append_rows<T, false, false>;
-            if (sq.S > 1) rope_k = d->kv_i8 ? &k_rope_append_rows<T, true, true> : &k_rope_append_rows<T, true, false>;
-            else if (d->kv_i8) rope_k = &k_rope_append_rows<T, false, true>;
+            const auto rope_k = rope_append_kernel<T>(sq.S > 1, d->kv_i8);
             hipLaunchKernelGGL(rope_k, dim3(B, sq.S > 1 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers,
                                c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, ctx_len, max_blocks, (u16 *)slabs[li],
                                (const int *)nullptr, (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, i8pb);
@@ -1025,25 +1041,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         a.nt_kv = (size_t)B * max_blocks * 64 >= 2048;
         a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
         if ((rc = d->kv_i8 ? paged_attn_i8_launch(c.dtype, D, a, st) : attn_decode_launch(c.dtype, D, a, true, st))) return rc;
-        W4lSlabs so, sd;  // o_proj / down handed over as K-split fp32 slabs where the shape qualifies
-        if ((rc = linear_rows<T>(d, w.wo, H, QD, s->attn, B, s->r, st, true, w.bo, false, nullptr, nullptr, nullptr,
-                                 H <= 8192 ? &so : nullptr)))
-            return rc;
-        if ((rc = add_rms_norm_rows<T>(s->x, s->r, w.mlp_norm, c.rms_eps, B, H, c.dtype, s->xn, st, so.S > 1 ? w.bo : nullptr, &so)))
-            return rc;
-        bool fused_act = false;
-        if ((rc = linear_rows<T>(d, w.wgateup, 2 * I, H, s->xn, B, s->gu, st, true, w.bgateup, false, s->act, &fused_act))) return rc;
-        if (!fused_act) {
-            const size_t n_act = (size_t)B * I;
-            hipLaunchKernelGGL(k_swiglu_rows<T>, dim3((unsigned)((n_act / 4 + 255) / 256)), dim3(256), 0, st, s->gu, n_act, s->act);
-            PIE_LAUNCH_CHECK();
-        }
-        if ((rc = linear_rows<T>(d, w.wdown, H, I, s->act, B, s->r, st, true, w.bdown, false, nullptr, nullptr, nullptr,
-                                 H <= 8192 ? &sd : nullptr)))
-            return rc;
-        const void *next_norm = li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm;  // final norm: language.py:187
-        if ((rc = add_rms_norm_rows<T>(s->x, s->r, next_norm, c.rms_eps, B, H, c.dtype, s->xn, st, sd.S > 1 ? w.bdown : nullptr, &sd)))
-            return rc;
+        if ((rc = mlp_rows<T>(d, w, B, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
     }
     if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, B, logits, st, false, nullptr, true))) return rc;
     return logits_tail_rows_launch(c.dtype, logits, c.vocab, B, s->tail_stats, logprobs, next_tokens, st);
@@ -1069,21 +1067,13 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
                             const int32_t *block_tables, int max_blocks, u16 *logits, float *logprobs, int32_t *next_tokens, hipStream_t st,
                             int n_chunks = 0, const int32_t *chunks = nullptr) {
     const pie_decoder_config &c = d->cfg;
-    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD, I = c.inter;
-    size_t w_elems = w16m_size(2 * I, H) / 2;  // the 16-bit copies are W16M tiles (rows padded to 32, columns to 64)
-    if (w16m_size(NQKV, H) / 2 > w_elems) w_elems = w16m_size(NQKV, H) / 2;
-    if (w16m_size(H, I) / 2 > w_elems) w_elems = w16m_size(H, I) / 2;
-    if (w16m_size(c.vocab, H) / 2 > w_elems) w_elems = w16m_size(c.vocab, H) / 2;
+    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
     const int dsplits = n_decode > 0 ? batch_attn_splits(d, n_decode, max_blocks) : 1;
-    int rc = scratch_reserve(d, N > S ? N : S, w_elems, dsplits > d->splits ? dsplits : d->splits);
+    int rc = scratch_reserve(d, N > S ? N : S, w16_copy_elems(c, true), dsplits > d->splits ? dsplits : d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     if ((rc = tail_stats_reserve(s, (size_t)TAIL_STAT_TILES * (size_t)S))) return rc;
-    rc = d->mat_fmt(d->glob.embed_codes) == PIE_W_DENSE
-             ? pie_embedding_dense(ids, N, d->glob.embed_codes, c.vocab, H, c.dtype, s->x, st)
-             : embedding_launch(ids, N, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, c.vocab, H, c.dtype, s->x, nullptr, nullptr,
-                                nullptr, 0, st, embed_bits(d));
-    if (rc) return rc;
+    if ((rc = embed_rows(d, ids, N, s->x, st))) return rc;
     hipLaunchKernelGGL(k_rope_cs_rows, dim3(N), dim3(64), 0, st, d->glob.rope_freqs, nullptr, row_ctx, D / 2, s->rope_cs);
     PIE_LAUNCH_CHECK();
     for (int li = 0; li < c.n_layers; ++li) {
@@ -1092,9 +1082,7 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
         W4lSlabs sq;  // q|k|v as the fp32 slabs of a K-split product (no Linear bias: RoPE takes T(x W^T + b))
         if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, N, s->qkv, st, true, w.bqkv, false, nullptr, nullptr, nullptr, w.bqkv ? nullptr : &sq)))
             return rc;
-        decltype(&k_rope_append_rows<T, false, false>) rope_k = &k_rope_append_rows<T, false, false>;
-        if (sq.S > 1) rope_k = d->kv_i8 ? &k_rope_append_rows<T, true, true> : &k_rope_append_rows<T, true, false>;
-        else if (d->kv_i8) rope_k = &k_rope_append_rows<T, false, true>;
+        const auto rope_k = rope_append_kernel<T>(sq.S > 1, d->kv_i8);
         hipLaunchKernelGGL(rope_k, dim3(N, sq.S > 1 && N < 512 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers,
                            c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, row_ctx, max_blocks, (u16 *)slabs[li],
                            row_seq, s->kc, s->vc, sq.part, sq.S, sq.MN,
@@ -1121,25 +1109,7 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
             ca.M = ch[1], ca.Hq = c.n_heads, ca.Hkv = c.n_kv_heads, ca.scale = pa.scale;
             if ((rc = prefill_attn_launch_t<T>(ca, D, st))) return rc;
         }
-        W4lSlabs so, sd;  // K-split products handed to their consumers as fp32 slabs (as in the single-prompt path)
-        if ((rc = linear_rows<T>(d, w.wo, H, QD, s->attn, N, s->r, st, true, w.bo, false, nullptr, nullptr, nullptr,
-                                 H <= 8192 ? &so : nullptr)))
-            return rc;
-        if ((rc = add_rms_norm_rows<T>(s->x, s->r, w.mlp_norm, c.rms_eps, N, H, c.dtype, s->xn, st, so.S > 1 ? w.bo : nullptr, &so)))
-            return rc;
-        bool fused_act = false;
-        if ((rc = linear_rows<T>(d, w.wgateup, 2 * I, H, s->xn, N, s->gu, st, true, w.bgateup, false, s->act, &fused_act))) return rc;
-        if (!fused_act) {
-            const size_t n_act = (size_t)N * I;
-            hipLaunchKernelGGL(k_swiglu_rows<T>, dim3((unsigned)((n_act / 4 + 255) / 256)), dim3(256), 0, st, s->gu, n_act, s->act);
-            PIE_LAUNCH_CHECK();
-        }
-        if ((rc = linear_rows<T>(d, w.wdown, H, I, s->act, N, s->r, st, true, w.bdown, false, nullptr, nullptr, nullptr,
-                                 H <= 8192 ? &sd : nullptr)))
-            return rc;
-        const void *next_norm = li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm;
-        if ((rc = add_rms_norm_rows<T>(s->x, s->r, next_norm, c.rms_eps, N, H, c.dtype, s->xn, st, sd.S > 1 ? w.bdown : nullptr, &sd)))
-            return rc;
+        if ((rc = mlp_rows<T>(d, w, N, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
     }
     // the normalised last row of every prompt -> lm_head -> tail
     hipLaunchKernelGGL(k_gather_rows, dim3(S), dim3(256), 0, st, (const uint4 *)s->xn, last_rows, H / 8, (uint4 *)s->r);
@@ -1238,18 +1208,14 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     }
     if (s->warm_key == key && s->warm_gen == s->alloc_gen) {
         if (s->batch_graph) (void)hipGraphExecDestroy(s->batch_graph), s->batch_graph = nullptr;
-        hipGraph_t g = nullptr;
-        hipStream_t cs = nullptr;
-        PIE_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-        if (e != hipSuccess) {
-            (void)hipStreamDestroy(cs);
-            return pie::fail(PIE_E_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
-        }
         const unsigned gen = s->alloc_gen;
-        const int rc = decode_batch(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, logits, logprobs, next_tokens, cs);
-        e = hipStreamEndCapture(cs, &g);
-        (void)hipStreamDestroy(cs);
+        hipGraph_t g = nullptr;
+        hipError_t e = hipSuccess;
+        int rc = PIE_OK;
+        const int crc = capture_graph(
+            [&](hipStream_t cs) { return decode_batch(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, logits, logprobs, next_tokens, cs); },
+            &rc, &g, &e);
+        if (crc) return crc;
         if (rc || e != hipSuccess || d->prefill->alloc_gen != gen) {  // something allocated or failed under capture: run this call eagerly instead
             if (g) (void)hipGraphDestroy(g);
             (void)hipGetLastError();

@@ -413,15 +413,15 @@ def test_batched_prefill_chunks_and_regimes(tiny, knobs):
 @pytest.mark.parametrize("L", [6, 9, 16, 24, 32, 33])
 def test_short_prompt_int4_gemm_paths(tiny, knobs, L):
     """Prompts of 6..33 tokens on the three int4 GEMM paths: the weight-streaming k_w4r_gemm (default), round 2's kernels (knob w4r = 0: the
-    one-strip few-row kernel up to 32 rows, the many-row tile kernel at 33) and, with small_m = 0 as well, the T copy + hipBLASLt below 33
-    rows: same qmm contract, every position against the oracle, and the paths within one rounding of each other."""
+    one-strip few-row kernel up to 32 rows, the many-row tile kernel at 33) and, with small_m = 0 as well, the many-row tile kernel below 33
+    rows too: same qmm contract, every position against the oracle, and the paths within one rounding of each other."""
     g, cfg, w, _ = tiny
     rng = np.random.default_rng(L)
     prompt = rng.integers(0, cfg["vocab_size"], L)
     orc = po.OracleLlama(cfg, w, DT)
     want = orc.forward(prompt, [po.OracleKVCache() for _ in orc.layers])
     outs = {}
-    for name, w4r, small in (("w4r", None, None), ("round-2 kernels", 0, 32), ("library GEMM", 0, 0)):
+    for name, w4r, small in (("w4r", None, None), ("round-2 kernels", 0, 32), ("many-row kernel", 0, 0)):
         knobs("w4r", w4r)
         knobs("small_m", small)
         m = build(cfg, w)
@@ -431,7 +431,7 @@ def test_short_prompt_int4_gemm_paths(tiny, knobs, L):
             assert_vec_close(got[l], want[l], DT, what=f"{name} L={L} position {l}")
         tok, _, logits = m.step(None, cache)                           # decode continues on the cache the short prompt filled
         outs[name] = (got, logits.float().cpu().numpy())
-    for name in ("round-2 kernels", "library GEMM"):
+    for name in ("round-2 kernels", "many-row kernel"):
         assert_vec_close(outs["w4r"][0][-1], outs[name][0][-1], DT, what=f"w4r vs {name}")
         assert_vec_close(outs["w4r"][1], outs[name][1], DT, what=f"decode after w4r vs {name} prompt")
 
