@@ -19,6 +19,8 @@ PIE_OPT_KV_I8 = 2
 KNOBS = {"prefill_min": 0, "prefill_chunk": 1, "prefill_resident": 2, "small_m": 3, "w4l_slabs": 4, "prefill_attn_valu": 5,
          "prefill_qt": 6, "attn_merge_max_cap": 7, "attn_warm_max_mb": 8, "w4r": 9, "fuse_attn": 10}
 PIE_I8 = 3  # KV page storage: int8 rows + per-head fp16 scales
+# weight formats (pie_decoder_config.weight_format; pie_layer_weights / pie_global_weights fmt_* take PIE_W_* + 1, 0 = the decoder's)
+PIE_W_INT4_G64, PIE_W_DENSE, PIE_W_INT8_G64, PIE_W_INT4_G32, PIE_W_INT8_G32, PIE_W_INT2_G64, PIE_W_INT6_G64 = range(7)
 KERNELS = {"embed": 0, "qkv": 1, "attn": 2, "o_proj": 3, "gate_up": 4, "down": 5, "lm_head": 6, "tail": 7}
 
 EXPORTS = [

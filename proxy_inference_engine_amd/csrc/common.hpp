@@ -189,7 +189,9 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// W4S geometry (see include/pie_hip.h): one unit = row pair x 2048-wide K slice.
+// ---------------------------------------------------------------- weight formats (PIE_W_*, include/pie_hip.h)
+// Every streaming format has the same unit shape: one ROW PAIR x one K slice, unit index = pair * n_slices + slice.
+// W4S (MLX int4 group-64 triplets): [2 x 64 lanes x 16 B] nibble-reordered codes + [64 x 4 B] {scale | bias << 16} per 2048-wide slice.
 constexpr int W4S_UNIT_BYTES = 2304;
 constexpr int W4S_SLICE_K = 2048;
 static inline __host__ __device__ int w4s_slices(int K) { return (K + W4S_SLICE_K - 1) / W4S_SLICE_K; }
@@ -209,12 +211,6 @@ constexpr int W8S_UNIT_BYTES = 4352;
 constexpr int W4S32_UNIT_BYTES = 2560;
 // W8S32 (MLX int8 group-32 triplets): likewise the W8S unit with two {scale | bias << 16} words per lane (code pieces 0-1 / 2-3) = 4608 B.
 constexpr int W8S32_UNIT_BYTES = 4608;
-enum { FMT_W4S = 0, FMT_W16S = 1, FMT_W8S = 2, FMT_W4S32 = 3, FMT_W8S32 = 4, FMT_W2S = 5, FMT_W6S = 6 };
-static inline __host__ __device__ constexpr int fmt_unit_bytes(int fmt) {
-    if (fmt == FMT_W2S) return 1280;
-    if (fmt == FMT_W6S) return 3328;
-    return fmt == FMT_W16S ? W16S_UNIT_BYTES : (fmt == FMT_W8S ? W8S_UNIT_BYTES : (fmt == FMT_W4S32 ? W4S32_UNIT_BYTES : (fmt == FMT_W8S32 ? W8S32_UNIT_BYTES : W4S_UNIT_BYTES)));
-}
 // W2S (MLX int2 group-64 triplets, round 5): the same unit shape with ONE 16-byte code piece per lane (its group's 64 two-bit codes) --
 // [64 lanes x 16 B] codes + [64 x 4 B] {scale | bias << 16} = 1280 B per row pair x 2048-wide K slice: 0.3125 B per weight, the checkpoint's own figure.
 // Word t of a lane's piece holds codes 16 t .. 16 t + 15 of the group: the even ones in the low 16-bit half, the odd ones in the high half, pair j
@@ -225,4 +221,33 @@ constexpr int W2S_UNIT_BYTES = 1280;
 // 0.8125 B per weight, the checkpoint's own figure (MLX stores the codes as a byte-straddling bit stream, four to three bytes).  q = lo + 16 hi, so a
 // group's dot product is the W4S dot of the low plane plus 16 times the W2S dot of the high plane: both loops unchanged, no straddling read in the stream.
 constexpr int W6S_UNIT_BYTES = 3328;
-constexpr int PIE_EMBED_W4G32 = 36, PIE_EMBED_W8G32 = 40;  // embedding_launch's `bits` for 4- / 8-bit codes in 32-wide groups (4 and 8 = the 64-wide group forms)
+// The kernels' names for the formats: the PIE_W_* numbers themselves.
+enum { FMT_W4S = PIE_W_INT4_G64, FMT_W16S = PIE_W_DENSE, FMT_W8S = PIE_W_INT8_G64, FMT_W4S32 = PIE_W_INT4_G32, FMT_W8S32 = PIE_W_INT8_G32,
+       FMT_W2S = PIE_W_INT2_G64, FMT_W6S = PIE_W_INT6_G64 };
+// What each format is: unit bytes, K-slice width, code bits (16: dense), group size (0: none), and whether the decoder's embedding table
+// may be held in it (W2S / W6S are Linear formats: such a checkpoint hands its table over as 4- / 8-bit codes).  unit_bytes 0: no such format.
+struct WeightFormat {
+    int unit_bytes, slice_k, bits, group;
+    bool embed;
+};
+static inline __host__ __device__ constexpr WeightFormat weight_format(int fmt) {
+    switch (fmt) {
+        case FMT_W4S: return {W4S_UNIT_BYTES, W4S_SLICE_K, 4, 64, true};
+        case FMT_W16S: return {W16S_UNIT_BYTES, W16S_SLICE_K, 16, 0, true};
+        case FMT_W8S: return {W8S_UNIT_BYTES, W4S_SLICE_K, 8, 64, true};
+        case FMT_W4S32: return {W4S32_UNIT_BYTES, W4S_SLICE_K, 4, 32, true};
+        case FMT_W8S32: return {W8S32_UNIT_BYTES, W4S_SLICE_K, 8, 32, true};
+        case FMT_W2S: return {W2S_UNIT_BYTES, W4S_SLICE_K, 2, 64, false};
+        case FMT_W6S: return {W6S_UNIT_BYTES, W4S_SLICE_K, 6, 64, false};
+        default: return {0, 1, 0, 0, false};
+    }
+}
+static inline __host__ __device__ constexpr int fmt_unit_bytes(int fmt) { return weight_format(fmt).unit_bytes; }
+static inline bool fmt_valid(int fmt) { return weight_format(fmt).unit_bytes != 0; }
+static inline bool fmt_may_embed(int fmt) { return weight_format(fmt).embed; }
+static inline int fmt_slices(int fmt, int K) { return (K + weight_format(fmt).slice_k - 1) / weight_format(fmt).slice_k; }
+// Bytes of one packed [N, K] matrix; 0 for odd N, K % 64 != 0, non-positive sizes or an unknown format.
+static inline size_t packed_bytes(int fmt, int N, int K) {
+    if (N <= 0 || K <= 0 || (N & 1) || (K & 63)) return 0;
+    return (size_t)(N / 2) * fmt_slices(fmt, K) * fmt_unit_bytes(fmt);
+}

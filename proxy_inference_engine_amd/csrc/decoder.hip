@@ -17,9 +17,6 @@
 #include "w4_gemv.hpp"
 #include "decoder.hpp"
 
-int embedding_launch(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype,
-                     void *out, const float *freqs, const DecState *state, float *rope_cs, int half, hipStream_t st, int bits);
-
 namespace {
 thread_local std::string g_last_error;
 #if defined(PIE_GEMV_PROF) && PIE_GEMV_PROF == 3
@@ -142,11 +139,10 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
     a.prof = d->pf_sink;
     // the CUs this launch leaves idle warm the Infinity Cache with o_proj's weights (attention.hpp: +1.3 % on the step)
     if (!d->combine) {
-        const int f = d->mat_fmt(w.wo);
         a.pf_rows = (256 - c.n_kv_heads * d->splits) / c.n_kv_heads;
         if (a.pf_rows < 0) a.pf_rows = 0;
         a.pf_ptr = (const char *)w.wo, a.pf_sink = d->pf_sink;
-        a.pf_bytes = f == PIE_W_INT2_G64 ? pie_w2s_bytes(H, QD) : f == PIE_W_INT6_G64 ? pie_w6s_bytes(H, QD) : f == PIE_W_DENSE ? pie_w16s_bytes(H, QD) : (f == PIE_W_INT8_G64 ? pie_w8s_bytes(H, QD) : (f == PIE_W_INT4_G32 ? pie_w4s32_bytes(H, QD) : (f == PIE_W_INT8_G32 ? pie_w8s32_bytes(H, QD) : pie_w4s_bytes(H, QD))));
+        a.pf_bytes = packed_bytes(d->mat_fmt(w.wo), H, QD);
         const int cap_mb = pie_knob(PIE_KNOB_ATTN_WARM_MAX_MB) >= 0 ? pie_knob(PIE_KNOB_ATTN_WARM_MAX_MB) : ATTN_WARM_DEFAULT_MB;
         if (a.pf_bytes > (unsigned long long)cap_mb << 20) a.pf_bytes = (unsigned long long)cap_mb << 20;
         if (!a.pf_bytes) a.pf_rows = 0;
@@ -159,22 +155,16 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
     const pie_decoder_config &c = d->cfg;
     const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D;
     const pie_layer_weights &w = d->layers[li];
-    auto gfmt = [d](const void *m) {  // streaming format of one matrix (per-module quantisation: models/utils.py:99-109)
-        const int f = d->mat_fmt(m);
-        if (f == PIE_W_INT2_G64) return (int)FMT_W2S;
-        if (f == PIE_W_INT6_G64) return (int)FMT_W6S;
-        return f == PIE_W_DENSE ? (int)FMT_W16S : (f == PIE_W_INT8_G64 ? FMT_W8S : (f == PIE_W_INT4_G32 ? FMT_W4S32 : (f == PIE_W_INT8_G32 ? FMT_W8S32 : FMT_W4S)));
-    };
     const int efmt = d->mat_fmt(d->glob.embed_codes);
     const bool dense_embed = efmt == PIE_W_DENSE;
     switch (which) {
         case PIE_K_EMBED:  // h = embed_tokens(inputs)  (language.py:176)
             if (dense_embed) return pie_embedding_dense(token_ptr, 1, d->glob.embed_codes, d->embed_vocab(), H, c.dtype, d->h, st);
             return embedding_launch(token_ptr, 1, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, d->embed_vocab(), H, c.dtype, d->h,
-                                    d->glob.rope_freqs, d->state, d->rope_cs, D / 2, st, embed_bits(d));
+                                    d->glob.rope_freqs, d->state, d->rope_cs, D / 2, st, efmt);
         case PIE_K_QKV: {  // q,k,v = proj(input_layernorm(x)); rope(offset=cache.offset); cache.update_and_fetch  (language.py:83-95)
             GemvArgs a = {};
-            a.fmt = gfmt(w.wqkv), a.w = (const char *)w.wqkv, a.K = H, a.N = QD + 2 * KVD;
+            a.fmt = d->mat_fmt(w.wqkv), a.w = (const char *)w.wqkv, a.K = H, a.N = QD + 2 * KVD;
             a.x = d->h, a.norm_w = (const u16 *)w.attn_norm, a.eps = c.rms_eps;
             a.freqs = d->glob.rope_freqs, a.rope_cs = dense_embed || d->row_is_h ? nullptr : d->rope_cs /* filled by the quantised embedding kernel */, a.state = d->state, a.q_out = d->qbuf, a.kv_table = d->kv_table;
             a.layer = li, a.n_layers = c.n_layers, a.n_heads = c.n_heads, a.n_kv_heads = c.n_kv_heads, a.head_dim = D;
@@ -221,7 +211,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
         }
         case PIE_K_OPROJ: {  // h = x + o_proj(attn)  (language.py:108,151)
             GemvArgs a = {};
-            a.fmt = gfmt(w.wo), a.w = (const char *)w.wo, a.K = QD, a.N = H, a.resid = d->h, a.lin_bias = (const u16 *)w.bo;
+            a.fmt = d->mat_fmt(w.wo), a.w = (const char *)w.wo, a.K = QD, a.N = H, a.resid = d->h, a.lin_bias = (const u16 *)w.bo;
             // tensor-parallel shard (row-parallel Linear over the local heads): un-rounded fp32 partial, summed over the ranks,
             // THEN the Linear's one rounding and the residual add
             // the one-shot communicator: the push half of the all-reduce rides in this epilogue (EPI_TP_PUSH); RCCL: fp32 partial in memory
@@ -237,14 +227,14 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
         }
         case PIE_K_GATEUP: {  // silu(gate(post_attention_layernorm(h))) * up(...)  (language.py:127,152)
             GemvArgs a = {};
-            a.fmt = gfmt(w.wgateup), a.w = (const char *)w.wgateup, a.K = H, a.N = 2 * c.inter, a.x = d->h, a.norm_w = (const u16 *)w.mlp_norm, a.eps = c.rms_eps;
+            a.fmt = d->mat_fmt(w.wgateup), a.w = (const char *)w.wgateup, a.K = H, a.N = 2 * c.inter, a.x = d->h, a.norm_w = (const u16 *)w.mlp_norm, a.eps = c.rms_eps;
             a.y = d->act, a.lin_bias = (const u16 *)w.bgateup;
             a.prof = reinterpret_cast<unsigned long long *>(d->pf_sink) + PROF_GU;
             return w4s_gemv_launch(c.dtype, PRO_RMSNORM, EPI_SWIGLU, a, 1, st);
         }
         case PIE_K_DOWN: {  // out = h + down_proj(...)  (language.py:127,153)
             GemvArgs a = {};
-            a.fmt = gfmt(w.wdown), a.w = (const char *)w.wdown, a.K = c.inter, a.N = H, a.x = d->act, a.resid = d->h, a.lin_bias = (const u16 *)w.bdown;
+            a.fmt = d->mat_fmt(w.wdown), a.w = (const char *)w.wdown, a.K = c.inter, a.N = H, a.x = d->act, a.resid = d->h, a.lin_bias = (const u16 *)w.bdown;
             const bool push = d->tp() && tp_comm_push_args(d->comm, &a.tp_peers, &a.tp_epoch, &a.tp_stride);
             a.y32 = d->tp_part, a.tp_rank = c.tp_rank, a.tp_world = c.tp_world;
             a.prof = reinterpret_cast<unsigned long long *>(d->pf_sink) + PROF_DOWN;
@@ -253,7 +243,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
         }
         case PIE_K_LMHEAD: {  // lm_head(norm(h)) (language.py:187,206-209) with per-tile log-softmax partials
             GemvArgs a = {};
-            a.fmt = gfmt(d->glob.lm_head), a.w = (const char *)d->glob.lm_head, a.K = H, a.N = c.vocab, a.x = d->h, a.norm_w = (const u16 *)d->glob.final_norm, a.eps = c.rms_eps;
+            a.fmt = d->mat_fmt(d->glob.lm_head), a.w = (const char *)d->glob.lm_head, a.K = H, a.N = c.vocab, a.x = d->h, a.norm_w = (const u16 *)d->glob.final_norm, a.eps = c.rms_eps;
             a.y = logits_dst, a.stats = d->stats;
             return w4s_gemv_launch(c.dtype, PRO_RMSNORM, EPI_LOGITS, a, 1, st);
         }
@@ -340,8 +330,7 @@ int pie_decoder_create(const pie_decoder_config *cfg, pie_decoder **out) {
     PIE_REQUIRE(c.n_layers > 0 && c.n_heads > 0 && c.n_kv_heads > 0 && c.n_heads % c.n_kv_heads == 0, PIE_E_SHAPE, "pie_decoder_create: bad head counts");
     PIE_REQUIRE(c.vocab > 0 && c.vocab % 2 == 0, PIE_E_SHAPE, "pie_decoder_create: vocab must be even");
     PIE_REQUIRE(c.hidden <= 32768 && c.inter <= 32768 && c.n_heads * c.head_dim <= 32768, PIE_E_SHAPE, "pie_decoder_create: K > 32768 not supported");
-    PIE_REQUIRE(c.weight_format == PIE_W_INT4_G64 || c.weight_format == PIE_W_DENSE || c.weight_format == PIE_W_INT8_G64 || c.weight_format == PIE_W_INT4_G32 || c.weight_format == PIE_W_INT8_G32 || c.weight_format == PIE_W_INT2_G64 || c.weight_format == PIE_W_INT6_G64, PIE_E_ARG,
-                "pie_decoder_create: unknown weight_format");
+    PIE_REQUIRE(fmt_valid(c.weight_format), PIE_E_ARG, "pie_decoder_create: unknown weight_format");
     PIE_REQUIRE(c.tp_world >= 0 && c.tp_world <= 8 && c.tp_rank >= 0 && c.tp_rank < (c.tp_world > 0 ? c.tp_world : 1), PIE_E_ARG,
                 "pie_decoder_create: 0 <= tp_rank < tp_world <= 8");
     pie_decoder *d = new (std::nothrow) pie_decoder();
@@ -400,7 +389,7 @@ int pie_decoder_set_layer(pie_decoder *d, int layer, const pie_layer_weights *w)
         const int f[4] = {w->fmt_qkv, w->fmt_o, w->fmt_gateup, w->fmt_down};
         const void *m[4] = {w->wqkv, w->wo, w->wgateup, w->wdown};
         for (int i = 0; i < 4; ++i) {
-            PIE_REQUIRE(f[i] >= 0 && f[i] <= PIE_W_INT6_G64 + 1, PIE_E_ARG, "pie_decoder_set_layer: unknown per-matrix weight format");
+            PIE_REQUIRE(f[i] == 0 || fmt_valid(f[i] - 1), PIE_E_ARG, "pie_decoder_set_layer: unknown per-matrix weight format");
             if (f[i]) d->fmt_map[m[i]] = f[i] - 1;
             else d->fmt_map.erase(m[i]);
         }
@@ -415,11 +404,11 @@ int pie_decoder_set_layer(pie_decoder *d, int layer, const pie_layer_weights *w)
 int pie_decoder_set_globals(pie_decoder *d, const pie_global_weights *w) {
     PIE_REQUIRE(d && w, PIE_E_ARG, "pie_decoder_set_globals: null pointer");
     PIE_REQUIRE(w->embed_codes && w->final_norm && w->lm_head && w->rope_freqs, PIE_E_ARG, "pie_decoder_set_globals: null weight");
-    PIE_REQUIRE(w->fmt_embed >= 0 && w->fmt_embed <= PIE_W_INT8_G32 + 1 && w->fmt_lm_head >= 0 && w->fmt_lm_head <= PIE_W_INT6_G64 + 1, PIE_E_ARG,
+    PIE_REQUIRE((w->fmt_embed == 0 || fmt_may_embed(w->fmt_embed - 1)) && (w->fmt_lm_head == 0 || fmt_valid(w->fmt_lm_head - 1)), PIE_E_ARG,
                 "pie_decoder_set_globals: unknown per-matrix weight format");
-    PIE_REQUIRE((w->fmt_embed ? w->fmt_embed - 1 : d->cfg.weight_format) == PIE_W_DENSE || (w->embed_scales && w->embed_biases), PIE_E_ARG,
-                "pie_decoder_set_globals: a quantised embedding needs scales and biases");
-    PIE_REQUIRE((w->fmt_embed ? w->fmt_embed - 1 : d->cfg.weight_format) != PIE_W_INT2_G64 && (w->fmt_embed ? w->fmt_embed - 1 : d->cfg.weight_format) != PIE_W_INT6_G64, PIE_E_ARG,
+    const int efmt = w->fmt_embed ? w->fmt_embed - 1 : d->cfg.weight_format;
+    PIE_REQUIRE(efmt == PIE_W_DENSE || (w->embed_scales && w->embed_biases), PIE_E_ARG, "pie_decoder_set_globals: a quantised embedding needs scales and biases");
+    PIE_REQUIRE(fmt_may_embed(efmt), PIE_E_ARG,
                 "pie_decoder_set_globals: the embedding table of a 2- / 6-bit checkpoint is handed over as 4- / 8-bit codes (fmt_embed = PIE_W_INT4_G64 + 1 / PIE_W_INT8_G64 + 1); W2S and W6S are Linear formats");
     if (w->fmt_embed) d->fmt_map[w->embed_codes] = w->fmt_embed - 1;
     else d->fmt_map.erase(w->embed_codes);
@@ -778,11 +767,8 @@ int pie_decoder_status(pie_decoder *d, unsigned *error) {
 }
 
 static size_t lin_bytes(const pie_decoder *d, const void *m, size_t n, size_t k) {  // algorithmic bytes of one Linear's weights
-    const int f = d->mat_fmt(m);
-    if (f == PIE_W_DENSE) return n * k * 2;
-    if (f == PIE_W_INT2_G64) return n * k / 4 + 2 * (n * k / 64) * 2;  // two-bit codes + the group's 16-bit scale and bias
-    if (f == PIE_W_INT6_G64) return n * k * 3 / 4 + 2 * (n * k / 64) * 2;  // six-bit codes likewise
-    return n * k / (f == PIE_W_INT8_G64 || f == PIE_W_INT8_G32 ? 1 : 2) + 2 * (n * k / (f == PIE_W_INT4_G32 || f == PIE_W_INT8_G32 ? 32 : 64)) * 2;  // codes + 16-bit scale and bias per group of 64 (32)
+    const WeightFormat f = weight_format(d->mat_fmt(m));
+    return n * k * f.bits / 8 + (f.group ? 2 * (n * k / f.group) * 2 : 0);  // codes + the group's 16-bit scale and bias (dense: the 16-bit weights)
 }
 
 size_t pie_decoder_kernel_bytes(const pie_decoder *d, int which, int T) {

@@ -20,9 +20,6 @@
 #include "decoder.hpp"
 #include "prefill_attn.hpp"
 
-int embedding_launch(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype,
-                     void *out, const float *freqs, const DecState *state, float *rope_cs, int half, hipStream_t st, int bits);
-
 // ---------------------------------------------------------------- kernels
 // W4S -> T row-major [N, K]; one thread per code word (8 weights, 16 B out).  Same arithmetic as k_dequantize_w4g64.
 template <class T, bool G32 = false>  // G32: W4S32 units (two {scale | bias} words per lane: code piece j is its own 32-wide group)
@@ -512,28 +509,12 @@ template <class T>
 static int expand_weights(pie_decoder *d, const void *packed, int N, int K, void *w16m, u16 *staging, hipStream_t st) {
     const int wf = d->mat_fmt(packed);  // per-module quantisation: a checkpoint may mix formats (models/utils.py:99-109)
     if (wf == PIE_W_DENSE) return w16m_from_w16s_launch(packed, N, K, w16m, st);
-    if (wf == PIE_W_INT8_G64 || wf == PIE_W_INT8_G32) {
-        const size_t w8 = (size_t)N * (K >> 2);
-        if (wf == PIE_W_INT8_G32) hipLaunchKernelGGL((k_dequant_w8s<T, true>), dim3((unsigned)((w8 + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
-        else hipLaunchKernelGGL((k_dequant_w8s<T, false>), dim3((unsigned)((w8 + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
-        PIE_LAUNCH_CHECK();
-        return w16m_from_rows_launch(staging, N, K, w16m, st);
-    }
-    if (wf == PIE_W_INT2_G64) {
-        const size_t w2 = (size_t)N * (K >> 4);
-        hipLaunchKernelGGL((k_dequant_w2s<T>), dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
-        PIE_LAUNCH_CHECK();
-        return w16m_from_rows_launch(staging, N, K, w16m, st);
-    }
-    if (wf == PIE_W_INT6_G64) {
-        const size_t w6 = (size_t)N * (K >> 3);
-        hipLaunchKernelGGL((k_dequant_w6s<T>), dim3((unsigned)((w6 + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
-        PIE_LAUNCH_CHECK();
-        return w16m_from_rows_launch(staging, N, K, w16m, st);
-    }
-    const size_t words = (size_t)N * (K >> 3);
-    if (wf == PIE_W_INT4_G32) hipLaunchKernelGGL((k_dequant_w4s<T, true>), dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
-    else hipLaunchKernelGGL((k_dequant_w4s<T, false>), dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
+    // one thread per code word: 4 weights (8-bit codes), 16 (2-bit), else 8 (4-bit codes and W6S's low plane)
+    const auto k = wf == PIE_W_INT8_G64 ? k_dequant_w8s<T, false> : wf == PIE_W_INT8_G32 ? k_dequant_w8s<T, true> : wf == PIE_W_INT2_G64 ? k_dequant_w2s<T>
+                 : wf == PIE_W_INT6_G64 ? k_dequant_w6s<T> : wf == PIE_W_INT4_G32 ? k_dequant_w4s<T, true> : k_dequant_w4s<T, false>;
+    const int bits = weight_format(wf).bits;
+    const size_t words = (size_t)N * (K >> (bits == 8 ? 2 : bits == 2 ? 4 : 3));
+    hipLaunchKernelGGL(k, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, (const u32 *)packed, N, K, w4s_slices(K), staging);
     PIE_LAUNCH_CHECK();
     return w16m_from_rows_launch(staging, N, K, w16m, st);
 }
@@ -602,10 +583,11 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
     // vs 3.96 / 4.82 / 6.20 / 9.75 / 14.38.  (With ONE workgroup per row the RoPE consumer could not keep enough slab loads in flight
     // below ~200 rows -- 4.21 ms at 64 tokens -- so few rows get four workgroups each there; that split applies to the RoPE consumer, not to the
     // add + RMSNorm consumers, whose row-wide reduction keeps them at one workgroup per row.)
-    const bool is_int4 = d->mat_fmt(packed) == PIE_W_INT4_G64;
-    if ((d->mat_fmt(packed) == PIE_W_INT4_G32 || d->mat_fmt(packed) == PIE_W_INT8_G32 || d->mat_fmt(packed) == PIE_W_INT2_G64 || d->mat_fmt(packed) == PIE_W_INT6_G64) && M <= GEMV_ROWS_MAX && K <= 32768 && N % 2 == 0) {  // group-32 / two-bit codes, qmv regime: the streaming GEMV, one pass per row
+    const int wf = d->mat_fmt(packed);
+    const bool is_int4 = wf == PIE_W_INT4_G64;
+    if ((wf == PIE_W_INT4_G32 || wf == PIE_W_INT8_G32 || wf == PIE_W_INT2_G64 || wf == PIE_W_INT6_G64) && M <= GEMV_ROWS_MAX && K <= 32768 && N % 2 == 0) {  // group-32 / 2- / 6-bit codes, qmv regime: the streaming GEMV, one pass per row
         GemvArgs a = {};
-        a.fmt = d->mat_fmt(packed) == PIE_W_INT2_G64 ? FMT_W2S : d->mat_fmt(packed) == PIE_W_INT6_G64 ? FMT_W6S : d->mat_fmt(packed) == PIE_W_INT8_G32 ? FMT_W8S32 : FMT_W4S32, a.w = (const char *)packed, a.K = K, a.N = N, a.x = x, a.y = y, a.lin_bias = (const u16 *)bias;
+        a.fmt = wf, a.w = (const char *)packed, a.K = K, a.N = N, a.x = x, a.y = y, a.lin_bias = (const u16 *)bias;
         return w4s_gemv_launch(d->cfg.dtype, PRO_NONE, EPI_STORE, a, M, st);
     }
     // Below 6 rows MLX multiplies row by row (qmv: exact fp32 per row, mx.quantized_matmul as reached from nn.QuantizedLinear): the
@@ -746,7 +728,7 @@ static int embed_rows(const pie_decoder *d, const int32_t *ids, int M, u16 *x, h
     const pie_decoder_config &c = d->cfg;
     if (d->mat_fmt(d->glob.embed_codes) == PIE_W_DENSE) return pie_embedding_dense(ids, M, d->glob.embed_codes, c.vocab, c.hidden, c.dtype, x, st);
     return embedding_launch(ids, M, d->glob.embed_codes, d->glob.embed_scales, d->glob.embed_biases, c.vocab, c.hidden, c.dtype, x, nullptr, nullptr,
-                            nullptr, 0, st, embed_bits(d));
+                            nullptr, 0, st, d->mat_fmt(d->glob.embed_codes));
 }
 
 // The k_rope_append_rows form for a q|k|v projection handed over as fp32 slabs or not, appended to int8 pages or not

@@ -412,7 +412,7 @@ int w4s_gemv_launch(int dtype, int pro, int epi, GemvArgs &a, int M, hipStream_t
     PIE_REQUIRE(a.K % 64 == 0 && a.K > 0, PIE_E_SHAPE, "w4s_gemv: K must be a positive multiple of 64");
     PIE_REQUIRE(a.N % 2 == 0 && a.N > 0, PIE_E_SHAPE, "w4s_gemv: N must be even");
     PIE_REQUIRE(a.K <= 32768, PIE_E_SHAPE, "w4s_gemv: K > 32768 not supported");
-    PIE_REQUIRE(a.fmt >= FMT_W4S && a.fmt <= FMT_W6S, PIE_E_ARG, "w4s_gemv: unknown weight format");
+    PIE_REQUIRE(fmt_valid(a.fmt), PIE_E_ARG, "w4s_gemv: unknown weight format");
     PIE_REQUIRE(pro != PRO_ATTN || (a.splits >= 1 && a.splits <= GEMV_ATTN_SPLITS && a.K <= 2 * 8 * GEMV_WAVES * 64 && a.head_dim % 8 == 0), PIE_E_SHAPE,
                 "w4s_gemv: attention-merge prologue supports <= 4 splits and n_heads*head_dim <= 8192");
     // Every pointer the chosen prologue / epilogue dereferences, checked HERE so that a null can never reach a kernel (a dense
@@ -432,13 +432,11 @@ int w4s_gemv_launch(int dtype, int pro, int epi, GemvArgs &a, int M, hipStream_t
     PIE_REQUIRE(epi != EPI_RESIDUAL || a.resid, PIE_E_ARG, "w4s_gemv: EPI_RESIDUAL without a residual stream");
     PIE_REQUIRE(epi != EPI_ROPE_KV || (a.state && a.q_out && a.kv_table && (a.rope_cs || a.freqs)), PIE_E_ARG,
                 "w4s_gemv: EPI_ROPE_KV needs state, q_out, kv_table and rope_cs or freqs");
-    a.n_slices = a.fmt == FMT_W16S ? w16s_slices(a.K) : w4s_slices(a.K);
+    a.n_slices = fmt_slices(a.fmt, a.K);
     a.n_pairs = a.N / 2;
     a.n_waves = w4s_gemv_waves(a.N, a.K);
-    const size_t unit_bytes = fmt_unit_bytes(a.fmt);
-    PIE_REQUIRE((size_t)a.n_pairs * a.n_slices * unit_bytes < ((size_t)1 << 32) - 8192, PIE_E_SHAPE,
-                "w4s_gemv: one matrix must stay below 4 GiB (32-bit buffer offsets)");
-    const unsigned lds = (unsigned)gemv_lds(a.K, a.fmt == FMT_W4S32 || a.fmt == FMT_W8S32).total;
+    PIE_REQUIRE(packed_bytes(a.fmt, a.N, a.K) < ((size_t)1 << 32) - 8192, PIE_E_SHAPE, "w4s_gemv: one matrix must stay below 4 GiB (32-bit buffer offsets)");
+    const unsigned lds = (unsigned)gemv_lds(a.K, weight_format(a.fmt).group == 32).total;
     PIE_REQUIRE(lds <= 65536u, PIE_E_SHAPE, "w4s_gemv: activation vector does not fit the 64 KB LDS image");
     dim3 grid((a.n_waves + GEMV_WAVES - 1) / GEMV_WAVES, M);
     a.full_rounds = a.n_pairs / a.n_waves, a.rem_pairs = a.n_pairs - a.full_rounds * a.n_waves;
@@ -514,7 +512,7 @@ int w4s_gemv_rows_fused_launch(int dtype, int pro, int epi, GemvRowsArgs &a, hip
     PIE_REQUIRE(epi != EPI_ROPE_KV || (a.rope_cs && a.ctx_len && a.block_table && a.slab && a.q_out && a.n_pages > 0 && a.bt_stride > 0 && a.head_dim > 0), PIE_E_ARG,
                 "w4s_gemv_rows: EPI_ROPE_KV needs the rows' RoPE table, context lengths, block tables, the slab and q_out");
     a.n_slices = w4s_slices(a.K), a.n_pairs = a.N / 2, a.n_waves = w4s_gemv_waves(a.N, a.K);
-    PIE_REQUIRE((size_t)a.n_pairs * a.n_slices * W4S_UNIT_BYTES < ((size_t)1 << 32) - 8192, PIE_E_SHAPE, "w4s_gemv_rows: one matrix must stay below 4 GiB");
+    PIE_REQUIRE(packed_bytes(FMT_W4S, a.N, a.K) < ((size_t)1 << 32) - 8192, PIE_E_SHAPE, "w4s_gemv_rows: one matrix must stay below 4 GiB");
     // rows per workgroup: all of them where their LDS images fit, else the fewest equal chunks (K = 14336: 5 rows -> 3 + 2)
     int mr_fit = GEMV_ROWS_MAX;
     while (mr_fit > 1 && gemv_rows_lds_bytes(a.K, mr_fit) > 160u * 1024u) --mr_fit;
@@ -541,16 +539,73 @@ int w4s_gemv_rows_launch(int dtype, const void *packed, int N, int K, const u16 
     return w4s_gemv_rows_fused_launch(dtype, PRO_NONE, EPI_STORE, a, stream);
 }
 
-// ---------------------------------------------------------------- C ABI
-int embedding_launch(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype,
-                     void *out, const float *freqs, const DecState *state, float *rope_cs, int half, hipStream_t st, int bits);
-
-extern "C" {
-
-size_t pie_w4s_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w4s_slices(K) * W4S_UNIT_BYTES;
+// ---------------------------------------------------------------- shared bodies of the per-format entry points
+// Calls f(BF16()) or f(F16()) for the activation dtype; false for any other dtype.
+template <class F> static bool with_dtype(int dtype, F &&f) {
+    if (dtype == PIE_BF16) return f(BF16()), true;
+    if (dtype == PIE_F16) return f(F16()), true;
+    return false;
 }
+
+// MLX triplet -> streaming units: one thread per output dword, blocks of 256.
+typedef void (*RepackKernel)(const u32 *, const u16 *, const u16 *, int, int, const int *, int, int, u32 *);
+static RepackKernel repack_kernel(int fmt) {
+    switch (fmt) {
+        case FMT_W4S: return k_repack_w4s;
+        case FMT_W8S: return k_repack_w8s;
+        case FMT_W4S32: return k_repack_w4s32;
+        case FMT_W8S32: return k_repack_w8s32;
+        case FMT_W2S: return k_repack_w2s;
+        case FMT_W6S: return k_repack_w6s;
+        default: return nullptr;
+    }
+}
+static int repack_launch(const std::string &fn, int fmt, const uint32_t *codes, const void *scales, const void *biases, int N_src, int K,
+                         const int32_t *row_map, int N_out, void *packed, void *stream) {
+    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, fn + ": null pointer");
+    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, fn + ": N_out must be even");
+    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, fn + ": K must be a multiple of 64, at most 32768");
+    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, fn + ": packed must be 256-byte aligned");
+    const int n_pairs = N_out / 2, ns = fmt_slices(fmt, K);
+    const size_t total = (size_t)n_pairs * ns * (fmt_unit_bytes(fmt) / 4);
+    hipLaunchKernelGGL(repack_kernel(fmt), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales,
+                       (const u16 *)biases, N_src, K, row_map, n_pairs, ns, (u32 *)packed);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// y[M, N] = T(x[M, K] . W^T) (+ bias), row by row on the streaming GEMV
+static int gemv_store(const std::string &fn, int fmt, const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype,
+                      void *stream) {
+    PIE_REQUIRE(x && packed && y, PIE_E_ARG, fn + ": null pointer");
+    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, fn + ": M out of range");
+    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, fn + ": misaligned pointer");
+    GemvArgs a = {};
+    a.fmt = fmt, a.w = (const char *)packed, a.K = K, a.N = N, a.x = (const u16 *)x, a.y = (u16 *)y, a.lin_bias = (const u16 *)lin_bias;
+    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
+}
+
+int embedding_launch(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype,
+                     void *out, const float *freqs, const DecState *state, float *rope_cs, int half, hipStream_t st, int fmt) {
+    PIE_REQUIRE(ids && codes && scales && biases && out, PIE_E_ARG, "pie_embedding_w4g64: null pointer");
+    PIE_REQUIRE(L > 0 && V > 0 && H > 0 && H % 64 == 0, PIE_E_SHAPE, "pie_embedding_w4g64: H must be a multiple of 64");
+    PIE_REQUIRE(pie_aligned(out, 16), PIE_E_ALIGN, "pie_embedding_w4g64: out must be 16-byte aligned");
+    PIE_REQUIRE(half <= 256, PIE_E_SHAPE, "embedding: head_dim too large for the RoPE table");
+    const WeightFormat f = weight_format(fmt);
+    PIE_REQUIRE(f.embed && (f.bits == 4 || f.bits == 8), PIE_E_ARG, "embedding: the table must hold 4- or 8-bit codes");
+    const bool ok = with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const auto k = f.group == 32 ? (f.bits == 8 ? k_embedding_w4g64<T, 8, 32> : k_embedding_w4g64<T, 4, 32>)
+                                     : (f.bits == 8 ? k_embedding_w4g64<T, 8> : k_embedding_w4g64<T, 4>);
+        hipLaunchKernelGGL(k, dim3(L), dim3(256), 0, st, ids, codes, (const u16 *)scales, (const u16 *)biases, V, H, (u16 *)out, freqs, state, rope_cs, half);
+    });
+    PIE_REQUIRE(ok, PIE_E_ARG, "pie_embedding_w4g64: bad dtype");
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// ---------------------------------------------------------------- C ABI
+extern "C" {
 
 int pie_quantize_w4g64(const void *w, int N, int K, int dtype, uint32_t *codes, void *scales, void *biases, void *stream) {
     return pie_quantize_g64(w, N, K, 4, dtype, codes, scales, biases, stream);
@@ -562,26 +617,12 @@ int pie_quantize_g64(const void *w, int N, int K, int bits, int dtype, uint32_t 
     PIE_REQUIRE(N > 0 && K > 0 && K % 64 == 0, PIE_E_SHAPE, "pie_quantize_w4g64: K must be a multiple of 64");
     PIE_REQUIRE(pie_aligned(w, 16) && pie_aligned(codes, 16), PIE_E_ALIGN, "pie_quantize_w4g64: 16-byte alignment required");
     const size_t groups = (size_t)N * (K / 64);
-    dim3 grid((unsigned)((groups + 127) / 128)), block(128);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PIE_BF16 && bits == 6)
-        hipLaunchKernelGGL((k_quantize_w4g64<BF16, 6>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_F16 && bits == 6)
-        hipLaunchKernelGGL((k_quantize_w4g64<F16, 6>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_BF16 && bits == 2)
-        hipLaunchKernelGGL((k_quantize_w4g64<BF16, 2>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_F16 && bits == 2)
-        hipLaunchKernelGGL((k_quantize_w4g64<F16, 2>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_BF16 && bits == 4)
-        hipLaunchKernelGGL((k_quantize_w4g64<BF16, 4>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_F16 && bits == 4)
-        hipLaunchKernelGGL((k_quantize_w4g64<F16, 4>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_BF16)
-        hipLaunchKernelGGL((k_quantize_w4g64<BF16, 8>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else if (dtype == PIE_F16)
-        hipLaunchKernelGGL((k_quantize_w4g64<F16, 8>), grid, block, 0, st, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
-    else
-        return pie::fail(PIE_E_ARG, "pie_quantize_w4g64: bad dtype");
+    const bool ok = with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const auto k = bits == 2 ? k_quantize_w4g64<T, 2> : bits == 4 ? k_quantize_w4g64<T, 4> : bits == 6 ? k_quantize_w4g64<T, 6> : k_quantize_w4g64<T, 8>;
+        hipLaunchKernelGGL(k, dim3((unsigned)((groups + 127) / 128)), dim3(128), 0, (hipStream_t)stream, (const u16 *)w, N, K, codes, (u16 *)scales, (u16 *)biases);
+    });
+    PIE_REQUIRE(ok, PIE_E_ARG, "pie_quantize_w4g64: bad dtype");
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
@@ -598,36 +639,87 @@ int pie_dequantize_g64(const uint32_t *codes, const void *scales, const void *bi
     PIE_REQUIRE(N > 0 && K > 0 && K % 64 == 0, PIE_E_SHAPE, "pie_dequantize_w4g64: K must be a multiple of 64");
     PIE_REQUIRE(pie_aligned(w_out, 16), PIE_E_ALIGN, "pie_dequantize_w4g64: output must be 16-byte aligned");
     const size_t n_words = (size_t)N * (K / (32 / bits));
-    dim3 grid((unsigned)((n_words + 255) / 256)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PIE_BF16 && bits == 4)
-        hipLaunchKernelGGL((k_dequantize_w4g64<BF16, 4>), grid, block, 0, st, codes, (const u16 *)scales, (const u16 *)biases, n_words, (u16 *)w_out);
-    else if (dtype == PIE_F16 && bits == 4)
-        hipLaunchKernelGGL((k_dequantize_w4g64<F16, 4>), grid, block, 0, st, codes, (const u16 *)scales, (const u16 *)biases, n_words, (u16 *)w_out);
-    else if (dtype == PIE_BF16)
-        hipLaunchKernelGGL((k_dequantize_w4g64<BF16, 8>), grid, block, 0, st, codes, (const u16 *)scales, (const u16 *)biases, n_words, (u16 *)w_out);
-    else if (dtype == PIE_F16)
-        hipLaunchKernelGGL((k_dequantize_w4g64<F16, 8>), grid, block, 0, st, codes, (const u16 *)scales, (const u16 *)biases, n_words, (u16 *)w_out);
-    else
-        return pie::fail(PIE_E_ARG, "pie_dequantize_w4g64: bad dtype");
+    const bool ok = with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const auto k = bits == 4 ? k_dequantize_w4g64<T, 4> : k_dequantize_w4g64<T, 8>;
+        hipLaunchKernelGGL(k, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales, (const u16 *)biases,
+                           n_words, (u16 *)w_out);
+    });
+    PIE_REQUIRE(ok, PIE_E_ARG, "pie_dequantize_w4g64: bad dtype");
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
 
-int pie_repack_w4g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map,
-                     int N_out, void *packed, void *stream) {
-    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, "pie_repack_w4g64: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_w4g64: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0, PIE_E_SHAPE, "pie_repack_w4g64: K must be a multiple of 64");
-    PIE_REQUIRE(w4s_slices(K) <= 16, PIE_E_SHAPE, "pie_repack_w4g64: K > 32768 not supported");
-    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, "pie_repack_w4g64: packed must be 256-byte aligned");
-    const int n_pairs = N_out / 2, ns = w4s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 576;
-    dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    hipLaunchKernelGGL(k_repack_w4s, grid, block, 0, (hipStream_t)stream, codes, (const u16 *)scales, (const u16 *)biases, N_src, K,
-                       row_map, n_pairs, ns, (u32 *)packed);
+size_t pie_w4s_bytes(int N_out, int K) { return packed_bytes(FMT_W4S, N_out, K); }
+size_t pie_w8s_bytes(int N_out, int K) { return packed_bytes(FMT_W8S, N_out, K); }
+size_t pie_w2s_bytes(int N_out, int K) { return packed_bytes(FMT_W2S, N_out, K); }
+size_t pie_w6s_bytes(int N_out, int K) { return packed_bytes(FMT_W6S, N_out, K); }
+size_t pie_w4s32_bytes(int N_out, int K) { return packed_bytes(FMT_W4S32, N_out, K); }
+size_t pie_w8s32_bytes(int N_out, int K) { return packed_bytes(FMT_W8S32, N_out, K); }
+size_t pie_w16s_bytes(int N_out, int K) { return packed_bytes(FMT_W16S, N_out, K); }
+
+int pie_repack_w4g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out, void *packed,
+                     void *stream) {
+    return repack_launch("pie_repack_w4g64", FMT_W4S, codes, scales, biases, N_src, K, row_map, N_out, packed, stream);
+}
+int pie_repack_w8g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out, void *packed,
+                     void *stream) {
+    return repack_launch("pie_repack_w8g64", FMT_W8S, codes, scales, biases, N_src, K, row_map, N_out, packed, stream);
+}
+int pie_repack_w2g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out, void *packed,
+                     void *stream) {
+    return repack_launch("pie_repack_w2g64", FMT_W2S, codes, scales, biases, N_src, K, row_map, N_out, packed, stream);
+}
+int pie_repack_w6g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out, void *packed,
+                     void *stream) {
+    return repack_launch("pie_repack_w6g64", FMT_W6S, codes, scales, biases, N_src, K, row_map, N_out, packed, stream);
+}
+int pie_repack_w4g32(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out, void *packed,
+                     void *stream) {
+    return repack_launch("pie_repack_w4g32", FMT_W4S32, codes, scales, biases, N_src, K, row_map, N_out, packed, stream);
+}
+int pie_repack_w8g32(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out, void *packed,
+                     void *stream) {
+    return repack_launch("pie_repack_w8g32", FMT_W8S32, codes, scales, biases, N_src, K, row_map, N_out, packed, stream);
+}
+
+int pie_repack_dense(const void *w, int N_src, int K, const int32_t *row_map, int N_out, void *packed, void *stream) {
+    PIE_REQUIRE(w && packed, PIE_E_ARG, "pie_repack_dense: null pointer");
+    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_dense: N_out must be even");
+    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_dense: K must be a multiple of 64, at most 32768");
+    PIE_REQUIRE(pie_aligned(packed, 256) && pie_aligned(w, 16), PIE_E_ALIGN, "pie_repack_dense: packed needs 256-byte, w 16-byte alignment");
+    const int n_pairs = N_out / 2, ns = w16s_slices(K);
+    const size_t total = (size_t)n_pairs * ns * (W16S_UNIT_BYTES / 16);  // one thread per 16-byte piece
+    hipLaunchKernelGGL(k_repack_w16s, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16 *)w, N_src, K, row_map,
+                       n_pairs, ns, (uint4 *)packed);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
+}
+
+int pie_qgemv_w4g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w4g64: null pointer");
+    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w4g64: M out of range");
+    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w4g64: misaligned pointer");
+    // one pass over the weights per up to GEMV_ROWS_MAX rows (k_w4s_gemv_rows); every row with the batch-1 arithmetic
+    return w4s_gemv_rows_launch(dtype, packed, N, K, (const u16 *)x, M, (u16 *)y, (const u16 *)lin_bias, (hipStream_t)stream);
+}
+int pie_qgemv_w8g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    return gemv_store("pie_qgemv_w8g64", FMT_W8S, x, M, packed, N, K, lin_bias, y, dtype, stream);
+}
+int pie_qgemv_w2g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    return gemv_store("pie_qgemv_w2g64", FMT_W2S, x, M, packed, N, K, lin_bias, y, dtype, stream);
+}
+int pie_qgemv_w6g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    return gemv_store("pie_qgemv_w6g64", FMT_W6S, x, M, packed, N, K, lin_bias, y, dtype, stream);
+}
+int pie_qgemv_w4g32(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    return gemv_store("pie_qgemv_w4g32", FMT_W4S32, x, M, packed, N, K, lin_bias, y, dtype, stream);
+}
+int pie_qgemv_w8g32(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    return gemv_store("pie_qgemv_w8g32", FMT_W8S32, x, M, packed, N, K, lin_bias, y, dtype, stream);
+}
+int pie_gemv_dense(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
+    return gemv_store("pie_gemv_dense", FMT_W16S, x, M, packed, N, K, lin_bias, y, dtype, stream);
 }
 
 int pie_qgemv_w4g64_f32(const void *x, int M, const void *packed, int N, int K, float *y, int dtype, void *stream) {
@@ -642,207 +734,19 @@ int pie_qgemv_w4g64_f32(const void *x, int M, const void *packed, int N, int K, 
     return w4s_gemv_launch(dtype, PRO_NONE, EPI_PARTIAL_F32, a, M, (hipStream_t)stream);
 }
 
-size_t pie_w8s_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w4s_slices(K) * W8S_UNIT_BYTES;
+int pie_embedding_w4g64(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype, void *out,
+                        void *stream) {
+    return embedding_launch(ids, L, codes, scales, biases, V, H, dtype, out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, FMT_W4S);
 }
-
-int pie_repack_w8g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out,
-                     void *packed, void *stream) {
-    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, "pie_repack_w8g64: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_w8g64: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_w8g64: K must be a multiple of 64, at most 32768");
-    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, "pie_repack_w8g64: packed must be 256-byte aligned");
-    const int n_pairs = N_out / 2, ns = w4s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 1088;
-    hipLaunchKernelGGL(k_repack_w8s, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales,
-                       (const u16 *)biases, N_src, K, row_map, n_pairs, ns, (u32 *)packed);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+int pie_embedding_g64(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int bits, int dtype, void *out,
+                      void *stream) {
+    PIE_REQUIRE(bits == 4 || bits == 8, PIE_E_ARG, "pie_embedding_g64: bits must be 4 or 8");
+    return embedding_launch(ids, L, codes, scales, biases, V, H, dtype, out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, bits == 8 ? FMT_W8S : FMT_W4S);
 }
-
-int pie_qgemv_w8g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w8g64: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w8g64: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w8g64: misaligned pointer");
-    GemvArgs a = {};
-    a.fmt = FMT_W8S;
-    a.w = (const char *)packed;
-    a.K = K, a.N = N;
-    a.x = (const u16 *)x;
-    a.y = (u16 *)y;
-    a.lin_bias = (const u16 *)lin_bias;
-    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
-}
-
-size_t pie_w2s_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w4s_slices(K) * W2S_UNIT_BYTES;
-}
-
-int pie_repack_w2g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out,
-                     void *packed, void *stream) {
-    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, "pie_repack_w2g64: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_w2g64: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_w2g64: K must be a multiple of 64, at most 32768");
-    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, "pie_repack_w2g64: packed must be 256-byte aligned");
-    const int n_pairs = N_out / 2, ns = w4s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 320;
-    hipLaunchKernelGGL(k_repack_w2s, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales,
-                       (const u16 *)biases, N_src, K, row_map, n_pairs, ns, (u32 *)packed);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-int pie_qgemv_w2g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w2g64: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w2g64: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w2g64: misaligned pointer");
-    GemvArgs a = {};
-    a.fmt = FMT_W2S;
-    a.w = (const char *)packed;
-    a.K = K, a.N = N;
-    a.x = (const u16 *)x;
-    a.y = (u16 *)y;
-    a.lin_bias = (const u16 *)lin_bias;
-    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
-}
-
-size_t pie_w6s_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w4s_slices(K) * W6S_UNIT_BYTES;
-}
-
-int pie_repack_w6g64(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out,
-                     void *packed, void *stream) {
-    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, "pie_repack_w6g64: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_w6g64: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_w6g64: K must be a multiple of 64, at most 32768");
-    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, "pie_repack_w6g64: packed must be 256-byte aligned");
-    const int n_pairs = N_out / 2, ns = w4s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 832;
-    hipLaunchKernelGGL(k_repack_w6s, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales,
-                       (const u16 *)biases, N_src, K, row_map, n_pairs, ns, (u32 *)packed);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-int pie_qgemv_w6g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w6g64: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w6g64: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w6g64: misaligned pointer");
-    GemvArgs a = {};
-    a.fmt = FMT_W6S;
-    a.w = (const char *)packed;
-    a.K = K, a.N = N;
-    a.x = (const u16 *)x;
-    a.y = (u16 *)y;
-    a.lin_bias = (const u16 *)lin_bias;
-    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
-}
-
-size_t pie_w4s32_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w4s_slices(K) * W4S32_UNIT_BYTES;
-}
-
-int pie_repack_w4g32(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out,
-                     void *packed, void *stream) {
-    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, "pie_repack_w4g32: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_w4g32: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_w4g32: K must be a multiple of 64, at most 32768");
-    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, "pie_repack_w4g32: packed must be 256-byte aligned");
-    const int n_pairs = N_out / 2, ns = w4s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 640;
-    hipLaunchKernelGGL(k_repack_w4s32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales,
-                       (const u16 *)biases, N_src, K, row_map, n_pairs, ns, (u32 *)packed);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-int pie_qgemv_w4g32(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w4g32: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w4g32: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w4g32: misaligned pointer");
-    GemvArgs a = {};
-    a.fmt = FMT_W4S32;
-    a.w = (const char *)packed;
-    a.K = K, a.N = N;
-    a.x = (const u16 *)x;
-    a.y = (u16 *)y;
-    a.lin_bias = (const u16 *)lin_bias;
-    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
-}
-
 int pie_embedding_g32(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int bits, int dtype, void *out,
                       void *stream) {
     PIE_REQUIRE(bits == 4 || bits == 8, PIE_E_ARG, "pie_embedding_g32: bits must be 4 or 8");
-    return embedding_launch(ids, L, codes, scales, biases, V, H, dtype, out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, bits == 8 ? PIE_EMBED_W8G32 : PIE_EMBED_W4G32);
-}
-
-size_t pie_w8s32_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w4s_slices(K) * W8S32_UNIT_BYTES;
-}
-
-int pie_repack_w8g32(const uint32_t *codes, const void *scales, const void *biases, int N_src, int K, const int32_t *row_map, int N_out,
-                     void *packed, void *stream) {
-    PIE_REQUIRE(codes && scales && biases && packed, PIE_E_ARG, "pie_repack_w8g32: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_w8g32: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_w8g32: K must be a multiple of 64, at most 32768");
-    PIE_REQUIRE(pie_aligned(packed, 256), PIE_E_ALIGN, "pie_repack_w8g32: packed must be 256-byte aligned");
-    const int n_pairs = N_out / 2, ns = w4s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 1152;
-    hipLaunchKernelGGL(k_repack_w8s32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, (const u16 *)scales,
-                       (const u16 *)biases, N_src, K, row_map, n_pairs, ns, (u32 *)packed);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-int pie_qgemv_w8g32(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w8g32: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w8g32: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w8g32: misaligned pointer");
-    GemvArgs a = {};
-    a.fmt = FMT_W8S32;
-    a.w = (const char *)packed;
-    a.K = K, a.N = N;
-    a.x = (const u16 *)x;
-    a.y = (u16 *)y;
-    a.lin_bias = (const u16 *)lin_bias;
-    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
-}
-
-size_t pie_w16s_bytes(int N_out, int K) {
-    if (N_out <= 0 || K <= 0 || (N_out & 1) || (K & 63)) return 0;
-    return (size_t)(N_out / 2) * w16s_slices(K) * W16S_UNIT_BYTES;
-}
-
-int pie_repack_dense(const void *w, int N_src, int K, const int32_t *row_map, int N_out, void *packed, void *stream) {
-    PIE_REQUIRE(w && packed, PIE_E_ARG, "pie_repack_dense: null pointer");
-    PIE_REQUIRE(N_src > 0 && N_out > 0 && (N_out % 2) == 0, PIE_E_SHAPE, "pie_repack_dense: N_out must be even");
-    PIE_REQUIRE(K > 0 && K % 64 == 0 && K <= 32768, PIE_E_SHAPE, "pie_repack_dense: K must be a multiple of 64, at most 32768");
-    PIE_REQUIRE(pie_aligned(packed, 256) && pie_aligned(w, 16), PIE_E_ALIGN, "pie_repack_dense: packed needs 256-byte, w 16-byte alignment");
-    const int n_pairs = N_out / 2, ns = w16s_slices(K);
-    const size_t total = (size_t)n_pairs * ns * 128;
-    hipLaunchKernelGGL(k_repack_w16s, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16 *)w, N_src, K, row_map,
-                       n_pairs, ns, (uint4 *)packed);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-int pie_gemv_dense(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype, void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_gemv_dense: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_gemv_dense: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_gemv_dense: misaligned pointer");
-    GemvArgs a = {};
-    a.fmt = FMT_W16S;
-    a.w = (const char *)packed;
-    a.K = K, a.N = N;
-    a.x = (const u16 *)x;
-    a.y = (u16 *)y;
-    a.lin_bias = (const u16 *)lin_bias;
-    return w4s_gemv_launch(dtype, PRO_NONE, EPI_STORE, a, M, (hipStream_t)stream);
+    return embedding_launch(ids, L, codes, scales, biases, V, H, dtype, out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, bits == 8 ? FMT_W8S32 : FMT_W4S32);
 }
 
 int pie_embedding_dense(const int32_t *ids, int L, const void *table, int V, int H, int dtype, void *out, void *stream) {
@@ -854,60 +758,6 @@ int pie_embedding_dense(const int32_t *ids, int L, const void *table, int V, int
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
-
-int pie_qgemv_w4g64(const void *x, int M, const void *packed, int N, int K, const void *lin_bias, void *y, int dtype,
-                    void *stream) {
-    PIE_REQUIRE(x && packed && y, PIE_E_ARG, "pie_qgemv_w4g64: null pointer");
-    PIE_REQUIRE(M > 0 && M <= 65535, PIE_E_SHAPE, "pie_qgemv_w4g64: M out of range");
-    PIE_REQUIRE(pie_aligned(x, 16) && pie_aligned(packed, 16) && pie_aligned(y, 4), PIE_E_ALIGN, "pie_qgemv_w4g64: misaligned pointer");
-    // one pass over the weights per up to GEMV_ROWS_MAX rows (k_w4s_gemv_rows); every row with the batch-1 arithmetic
-    return w4s_gemv_rows_launch(dtype, packed, N, K, (const u16 *)x, M, (u16 *)y, (const u16 *)lin_bias, (hipStream_t)stream);
-}
-
-int pie_embedding_w4g64(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H,
-                        int dtype, void *out, void *stream) {
-    return embedding_launch(ids, L, codes, scales, biases, V, H, dtype, out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, 4);
-}
-int pie_embedding_g64(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int bits,
-                      int dtype, void *out, void *stream) {
-    PIE_REQUIRE(bits == 4 || bits == 8, PIE_E_ARG, "pie_embedding_g64: bits must be 4 or 8");
-    return embedding_launch(ids, L, codes, scales, biases, V, H, dtype, out, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, bits);
-}
-}  // extern "C"
-
-int embedding_launch(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype,
-                     void *out, const float *freqs, const DecState *state, float *rope_cs, int half, hipStream_t st, int bits) {
-    PIE_REQUIRE(ids && codes && scales && biases && out, PIE_E_ARG, "pie_embedding_w4g64: null pointer");
-    PIE_REQUIRE(L > 0 && V > 0 && H > 0 && H % 64 == 0, PIE_E_SHAPE, "pie_embedding_w4g64: H must be a multiple of 64");
-    PIE_REQUIRE(pie_aligned(out, 16), PIE_E_ALIGN, "pie_embedding_w4g64: out must be 16-byte aligned");
-    PIE_REQUIRE(half <= 256, PIE_E_SHAPE, "embedding: head_dim too large for the RoPE table");
-#define PIE_EMB(TT, BB)                                                                                                            \
-    hipLaunchKernelGGL((k_embedding_w4g64<TT, BB>), dim3(L), dim3(256), 0, st, ids, codes, (const u16 *)scales, (const u16 *)biases, V, H, \
-                       (u16 *)out, freqs, state, rope_cs, half)
-    if (dtype == PIE_BF16 && bits == PIE_EMBED_W4G32)
-        hipLaunchKernelGGL((k_embedding_w4g64<BF16, 4, 32>), dim3(L), dim3(256), 0, st, ids, codes, (const u16 *)scales, (const u16 *)biases, V, H, (u16 *)out, freqs, state,
-                           rope_cs, half);
-    else if (dtype == PIE_F16 && bits == PIE_EMBED_W4G32)
-        hipLaunchKernelGGL((k_embedding_w4g64<F16, 4, 32>), dim3(L), dim3(256), 0, st, ids, codes, (const u16 *)scales, (const u16 *)biases, V, H, (u16 *)out, freqs, state,
-                           rope_cs, half);
-    else if (dtype == PIE_BF16 && bits == PIE_EMBED_W8G32)
-        hipLaunchKernelGGL((k_embedding_w4g64<BF16, 8, 32>), dim3(L), dim3(256), 0, st, ids, codes, (const u16 *)scales, (const u16 *)biases, V, H, (u16 *)out, freqs, state,
-                           rope_cs, half);
-    else if (dtype == PIE_F16 && bits == PIE_EMBED_W8G32)
-        hipLaunchKernelGGL((k_embedding_w4g64<F16, 8, 32>), dim3(L), dim3(256), 0, st, ids, codes, (const u16 *)scales, (const u16 *)biases, V, H, (u16 *)out, freqs, state,
-                           rope_cs, half);
-    else if (dtype == PIE_BF16 && bits == 8) PIE_EMB(BF16, 8);
-    else if (dtype == PIE_F16 && bits == 8) PIE_EMB(F16, 8);
-    else if (dtype == PIE_BF16) PIE_EMB(BF16, 4);
-    else if (dtype == PIE_F16) PIE_EMB(F16, 4);
-#undef PIE_EMB
-    else
-        return pie::fail(PIE_E_ARG, "pie_embedding_w4g64: bad dtype");
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-extern "C" {
 
 int pie_qkv_row_map(int n_heads, int n_kv_heads, int head_dim, int32_t *map) {
     if (!map || n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || (head_dim & 1)) return pie::fail(PIE_E_ARG, "pie_qkv_row_map: bad argument");

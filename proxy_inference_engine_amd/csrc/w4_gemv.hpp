@@ -57,7 +57,7 @@ struct LogitStat {  // per-wave partial of the log-softmax / argmax tail
 };
 
 struct GemvArgs {
-    int fmt;        // FMT_W4S (int4 g=64 units) or FMT_W16S (dense 16-bit units)
+    int fmt;        // weight format of the stream: PIE_W_* = FMT_* (common.hpp)
     const char *w;  // W4S / W16S
     int n_pairs, n_slices, n_waves, K, N;
     int full_rounds, rem_pairs, n_blocks;  // launcher: n_pairs = full_rounds * n_waves + rem_pairs; workgroups the leftover pairs are dealt over (0: the first waves); see k_w4s_gemv
@@ -1123,3 +1123,7 @@ int w4s_gemv_rows_launch(int dtype, const void *packed, int N, int K, const u16 
 // the fused forms (pro: PRO_NONE / PRO_RMSNORM; epi: EPI_STORE / EPI_RESIDUAL / EPI_SWIGLU / EPI_ROPE_KV / EPI_LOGITS): w, K, N, M and the operands of the
 // chosen prologue / epilogue set by the caller
 int w4s_gemv_rows_fused_launch(int dtype, int pro, int epi, GemvRowsArgs &a, hipStream_t stream);
+// nn.QuantizedEmbedding: out[l, :] = the dequantised row ids[l] of an MLX-layout table in format fmt (PIE_W_INT4_G64 / INT8_G64 / INT4_G32 /
+// INT8_G32).  The decoder's step also passes freqs / state / rope_cs / half: block 0 then writes the step's RoPE table (else nullptr / 0).
+int embedding_launch(const int32_t *ids, int L, const uint32_t *codes, const void *scales, const void *biases, int V, int H, int dtype,
+                     void *out, const float *freqs, const DecState *state, float *rope_cs, int half, hipStream_t st, int fmt);

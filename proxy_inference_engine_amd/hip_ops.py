@@ -11,7 +11,9 @@ there is no torch-op or CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -55,213 +57,113 @@ def dequantize(codes: torch.Tensor, scales: torch.Tensor, biases: torch.Tensor, 
     return out
 
 
+class _Format(NamedTuple):
+    bits: int                # code bits (16: dense 16-bit weights)
+    group_size: int | None   # weights per scale / bias pair (None: dense)
+    size: str                # the C ABI's packed size, repack and streaming-GEMV entry points
+    repack: str
+    gemv: str
+
+
+# The streaming formats (include/pie_hip.h PIE_W_*), keyed by their PIE_W_* code
+FORMATS = {
+    _ffi.PIE_W_INT4_G64: _Format(4, 64, "pie_w4s_bytes", "pie_repack_w4g64", "pie_qgemv_w4g64"),
+    _ffi.PIE_W_DENSE: _Format(16, None, "pie_w16s_bytes", "pie_repack_dense", "pie_gemv_dense"),
+    _ffi.PIE_W_INT8_G64: _Format(8, 64, "pie_w8s_bytes", "pie_repack_w8g64", "pie_qgemv_w8g64"),
+    _ffi.PIE_W_INT4_G32: _Format(4, 32, "pie_w4s32_bytes", "pie_repack_w4g32", "pie_qgemv_w4g32"),
+    _ffi.PIE_W_INT8_G32: _Format(8, 32, "pie_w8s32_bytes", "pie_repack_w8g32", "pie_qgemv_w8g32"),
+    _ffi.PIE_W_INT2_G64: _Format(2, 64, "pie_w2s_bytes", "pie_repack_w2g64", "pie_qgemv_w2g64"),
+    _ffi.PIE_W_INT6_G64: _Format(6, 64, "pie_w6s_bytes", "pie_repack_w6g64", "pie_qgemv_w6g64"),
+}
+
+
+def weight_format(bits: int, group_size: int) -> int:
+    """The PIE_W_* code of MLX triplets with these bits and group size (ValueError if no streaming format holds them)."""
+    for fmt, f in FORMATS.items():
+        if (f.bits, f.group_size) == (bits, group_size):
+            return fmt
+    raise ValueError(f"no streaming format for bits={bits}, group_size={group_size}")
+
+
 @dataclass
-class W4SWeight:
-    """One quantised Linear in the W4S streaming layout (include/pie_hip.h)."""
-    packed: torch.Tensor          # uint8 [pie_w4s_bytes(N, K)]
+class PackedWeight:
+    """One Linear in its streaming layout (include/pie_hip.h): fmt is the PIE_W_* format of `packed`."""
+    packed: torch.Tensor          # uint8 [pie_w*s_bytes(N, K)]
     N: int
     K: int
     dtype: torch.dtype
+    fmt: int
     lin_bias: torch.Tensor | None = None
+
+    @property
+    def bits(self) -> int:
+        return FORMATS[self.fmt].bits
+
+    @property
+    def group_size(self) -> int | None:
+        return FORMATS[self.fmt].group_size
 
     @property
     def nbytes(self) -> int:
         return self.packed.numel()
 
 
-@dataclass
-class W8SWeight:
-    """One MLX int8 g=64 Linear in the W8S streaming layout (include/pie_hip.h)."""
-    packed: torch.Tensor          # uint8 [pie_w8s_bytes(N, K)]
-    N: int
-    K: int
-    dtype: torch.dtype
-    lin_bias: torch.Tensor | None = None
-
-    @property
-    def nbytes(self) -> int:
-        return self.packed.numel()
+def _packed_buffer(fmt: int, N_out: int, K: int, device) -> torch.Tensor:
+    nbytes = getattr(_ffi.load(), FORMATS[fmt].size)(N_out, K)
+    if nbytes == 0:
+        raise ValueError(f"unsupported shape for {FORMATS[fmt].repack}: N={N_out} (must be even), K={K} (multiple of 64)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-@dataclass
-class W2SWeight:
-    """One MLX int2 g=64 Linear in the W2S streaming layout (include/pie_hip.h)."""
-    packed: torch.Tensor          # uint8 [pie_w2s_bytes(N, K)]
-    N: int
-    K: int
-    dtype: torch.dtype
-    lin_bias: torch.Tensor | None = None
-
-    @property
-    def nbytes(self) -> int:
-        return self.packed.numel()
+def _row_map(row_map: torch.Tensor | None, device) -> torch.Tensor | None:
+    return None if row_map is None else row_map.to(device=device, dtype=torch.int32).contiguous()
 
 
-@dataclass
-class W6SWeight(W2SWeight):
-    """One MLX int6 g=64 Linear in the W6S streaming layout (low-nibble plane + high-two-bit plane; include/pie_hip.h)."""
-
-
-@dataclass
-class W4S32Weight:
-    """One MLX int4 group-32 Linear in the W4S32 streaming layout (include/pie_hip.h)."""
-    packed: torch.Tensor          # uint8 [pie_w4s32_bytes(N, K)]
-    N: int
-    K: int
-    dtype: torch.dtype
-    lin_bias: torch.Tensor | None = None
-
-    @property
-    def nbytes(self) -> int:
-        return self.packed.numel()
-
-
-@dataclass
-class W8S32Weight(W4S32Weight):
-    """One MLX int8 group-32 Linear in the W8S32 streaming layout (include/pie_hip.h)."""
-
-
-def repack_w4s32(codes, scales, biases, row_map: torch.Tensor | None = None, lin_bias=None, bits: int = 4) -> W4S32Weight:
-    """Load-time repack of an MLX 4-bit (bits=8: 8-bit) group-32 triplet (weight [N_src, K*bits/32], scales / biases [N_src, K/32]) into W4S32
-    (W8S32); row_map as for repack_w4s."""
+def repack(codes, scales, biases, *, bits: int, group_size: int = 64, row_map: torch.Tensor | None = None, lin_bias=None) -> PackedWeight:
+    """Load-time repack of an MLX-quantised Linear -- mx.quantize's triplet: weight uint32 [N_src, K*bits/32] (6 bits: MLX's bit stream),
+    scales / biases [N_src, K/group_size] -- into its streaming layout.  row_map (int32 [N_out]) selects / reorders source rows (q|k|v
+    concatenation, gate/up interleave)."""
+    fmt = weight_format(bits, group_size)
     for t in (codes, scales, biases):
         _dev(t)
     N_src, K = codes.shape[0], codes.shape[1] * 32 // bits
-    if tuple(scales.shape) != (N_src, K // 32) or tuple(biases.shape) != (N_src, K // 32):
-        raise ValueError(f"group-32 scales / biases must be [{N_src}, {K // 32}], got {tuple(scales.shape)} / {tuple(biases.shape)}")
+    if K * bits != codes.shape[1] * 32 or tuple(scales.shape) != (N_src, K // group_size) or tuple(biases.shape) != (N_src, K // group_size):
+        raise ValueError(f"{bits}-bit rows must hold whole codes and scales / biases must be [{N_src}, {K // group_size}]; got "
+                         f"{tuple(codes.shape)} / {tuple(scales.shape)} / {tuple(biases.shape)}")
     N_out = N_src if row_map is None else int(row_map.numel())
-    lib = _ffi.load()
-    nbytes = (lib.pie_w8s32_bytes if bits == 8 else lib.pie_w4s32_bytes)(N_out, K)
-    if nbytes == 0:
-        raise ValueError(f"unsupported shape for W4S32 / W8S32: N={N_out} (must be even), K={K} (multiple of 64)")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-    if row_map is not None:
-        row_map = row_map.to(device=codes.device, dtype=torch.int32).contiguous()
-    _ffi.check((lib.pie_repack_w8g32 if bits == 8 else lib.pie_repack_w4g32)(_ffi.p(codes.contiguous()), _ffi.p(scales.contiguous()), _ffi.p(biases.contiguous()), N_src, K,
-                                                                            _ffi.p(row_map), N_out, _ffi.p(packed), _ffi.stream()))
-    return (W8S32Weight if bits == 8 else W4S32Weight)(packed, N_out, K, scales.dtype, lin_bias)
+    packed, row_map = _packed_buffer(fmt, N_out, K, codes.device), _row_map(row_map, codes.device)
+    _ffi.check(getattr(_ffi.load(), FORMATS[fmt].repack)(_ffi.p(codes), _ffi.p(scales), _ffi.p(biases), N_src, K, _ffi.p(row_map), N_out,
+                                                         _ffi.p(packed), _ffi.stream()))
+    return PackedWeight(packed, N_out, K, scales.dtype, fmt, lin_bias)
 
 
-def repack_w8s32(codes, scales, biases, row_map: torch.Tensor | None = None, lin_bias=None) -> W8S32Weight:
-    return repack_w4s32(codes, scales, biases, row_map=row_map, lin_bias=lin_bias, bits=8)
+# repack for one format each, like the C ABI's pie_repack_w4g64 .. pie_repack_w8g32 (repack_w4s32(bits=8) is repack_w8s32)
+repack_w4s, repack_w8s, repack_w2s, repack_w6s = (functools.partial(repack, bits=b) for b in (4, 8, 2, 6))
+repack_w4s32, repack_w8s32 = functools.partial(repack, bits=4, group_size=32), functools.partial(repack, bits=8, group_size=32)
 
 
-def repack_w2s(codes, scales, biases, row_map: torch.Tensor | None = None, lin_bias=None) -> W2SWeight:
-    """Load-time repack of an MLX 2-bit group-64 triplet (weight [N_src, K/16], scales / biases [N_src, K/64]) into W2S; row_map as for repack_w4s."""
-    for t in (codes, scales, biases):
-        _dev(t)
-    N_src, K = codes.shape[0], codes.shape[1] * 16
-    if tuple(scales.shape) != (N_src, K // 64) or tuple(biases.shape) != (N_src, K // 64):
-        raise ValueError(f"group-64 scales / biases must be [{N_src}, {K // 64}], got {tuple(scales.shape)} / {tuple(biases.shape)}")
-    N_out = N_src if row_map is None else int(row_map.numel())
-    nbytes = _ffi.load().pie_w2s_bytes(N_out, K)
-    if nbytes == 0:
-        raise ValueError(f"unsupported shape for W2S: N={N_out} (must be even), K={K} (multiple of 64)")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-    if row_map is not None:
-        row_map = row_map.to(device=codes.device, dtype=torch.int32).contiguous()
-    _ffi.check(_ffi.load().pie_repack_w2g64(_ffi.p(codes.contiguous()), _ffi.p(scales.contiguous()), _ffi.p(biases.contiguous()), N_src, K, _ffi.p(row_map), N_out,
-                                            _ffi.p(packed), _ffi.stream()))
-    return W2SWeight(packed, N_out, K, scales.dtype, lin_bias)
-
-
-def repack_w6s(codes, scales, biases, row_map: torch.Tensor | None = None, lin_bias=None) -> W6SWeight:
-    """Load-time repack of an MLX 6-bit group-64 triplet (weight [N_src, 3K/16]: MLX's bit stream; scales / biases [N_src, K/64]) into W6S."""
-    for t in (codes, scales, biases):
-        _dev(t)
-    N_src, K = codes.shape[0], codes.shape[1] * 16 // 3
-    if codes.shape[1] % 12 or tuple(scales.shape) != (N_src, K // 64) or tuple(biases.shape) != (N_src, K // 64):
-        raise ValueError(f"6-bit rows hold 12 words per group of 64; scales / biases must be [{N_src}, {K // 64}], got {tuple(codes.shape)} / {tuple(scales.shape)} / {tuple(biases.shape)}")
-    N_out = N_src if row_map is None else int(row_map.numel())
-    nbytes = _ffi.load().pie_w6s_bytes(N_out, K)
-    if nbytes == 0:
-        raise ValueError(f"unsupported shape for W6S: N={N_out} (must be even), K={K} (multiple of 64)")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-    if row_map is not None:
-        row_map = row_map.to(device=codes.device, dtype=torch.int32).contiguous()
-    _ffi.check(_ffi.load().pie_repack_w6g64(_ffi.p(codes.contiguous()), _ffi.p(scales.contiguous()), _ffi.p(biases.contiguous()), N_src, K, _ffi.p(row_map), N_out,
-                                            _ffi.p(packed), _ffi.stream()))
-    return W6SWeight(packed, N_out, K, scales.dtype, lin_bias)
-
-
-def repack_w8s(codes, scales, biases, row_map: torch.Tensor | None = None, lin_bias=None) -> W8SWeight:
-    """Load-time repack of an MLX 8-bit triplet (weight [N_src, K/4], scales, biases) into W8S; row_map as for repack_w4s."""
-    for t in (codes, scales, biases):
-        _dev(t)
-    N_src, K = codes.shape[0], codes.shape[1] * 4
-    N_out = N_src if row_map is None else int(row_map.numel())
-    nbytes = _ffi.load().pie_w8s_bytes(N_out, K)
-    if nbytes == 0:
-        raise ValueError(f"unsupported shape for W8S: N={N_out} (must be even), K={K} (multiple of 64)")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-    if row_map is not None:
-        row_map = row_map.to(device=codes.device, dtype=torch.int32).contiguous()
-    _ffi.check(_ffi.load().pie_repack_w8g64(_ffi.p(codes), _ffi.p(scales), _ffi.p(biases), N_src, K, _ffi.p(row_map), N_out,
-                                            _ffi.p(packed), _ffi.stream()))
-    return W8SWeight(packed, N_out, K, scales.dtype, lin_bias)
-
-
-def repack_w4s(codes, scales, biases, row_map: torch.Tensor | None = None, lin_bias=None) -> W4SWeight:
-    """Load-time repack of an MLX triplet (weight, scales, biases) [N_src,K] into W4S.
-    row_map (int32 [N_out]) selects / reorders source rows (q|k|v concatenation, gate/up interleave)."""
-    for t in (codes, scales, biases):
-        _dev(t)
-    N_src, K = codes.shape[0], codes.shape[1] * 8
-    N_out = N_src if row_map is None else int(row_map.numel())
-    if N_out % 2:
-        raise ValueError("W4S needs an even number of rows")
-    nbytes = _ffi.load().pie_w4s_bytes(N_out, K)
-    if nbytes == 0:
-        raise ValueError(f"unsupported shape for W4S: N={N_out}, K={K}")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-    if row_map is not None:
-        row_map = row_map.to(device=codes.device, dtype=torch.int32).contiguous()
-    _ffi.check(_ffi.load().pie_repack_w4g64(_ffi.p(codes), _ffi.p(scales), _ffi.p(biases), N_src, K, _ffi.p(row_map), N_out,
-                                            _ffi.p(packed), _ffi.stream()))
-    return W4SWeight(packed, N_out, K, scales.dtype, lin_bias)
-
-
-@dataclass
-class W16SWeight:
-    """One dense 16-bit Linear in the W16S streaming layout (include/pie_hip.h)."""
-    packed: torch.Tensor          # uint8 [pie_w16s_bytes(N, K)]
-    N: int
-    K: int
-    dtype: torch.dtype
-    lin_bias: torch.Tensor | None = None
-
-    @property
-    def nbytes(self) -> int:
-        return self.packed.numel()
-
-
-def repack_dense(w: torch.Tensor, row_map: torch.Tensor | None = None, lin_bias=None) -> W16SWeight:
-    """Load-time repack of an nn.Linear weight [N_src, K] (bf16 / f16) into W16S; row_map as for repack_w4s."""
+def repack_dense(w: torch.Tensor, row_map: torch.Tensor | None = None, lin_bias=None) -> PackedWeight:
+    """Load-time repack of an nn.Linear weight [N_src, K] (bf16 / f16) into W16S; row_map as for repack."""
     _dev(w)
     if w.dtype not in (torch.bfloat16, torch.float16) or w.dim() != 2:
         raise ValueError("dense weights must be 2-D bfloat16 / float16")
-    w = w.contiguous()
     N_src, K = w.shape
     N_out = N_src if row_map is None else int(row_map.numel())
-    nbytes = _ffi.load().pie_w16s_bytes(N_out, K)
-    if nbytes == 0:
-        raise ValueError(f"unsupported shape for W16S: N={N_out} (must be even), K={K} (multiple of 64)")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    if row_map is not None:
-        row_map = row_map.to(device=w.device, dtype=torch.int32).contiguous()
+    packed, row_map = _packed_buffer(_ffi.PIE_W_DENSE, N_out, K, w.device), _row_map(row_map, w.device)
     _ffi.check(_ffi.load().pie_repack_dense(_ffi.p(w), N_src, K, _ffi.p(row_map), N_out, _ffi.p(packed), _ffi.stream()))
-    return W16SWeight(packed, N_out, K, w.dtype, lin_bias)
+    return PackedWeight(packed, N_out, K, w.dtype, _ffi.PIE_W_DENSE, lin_bias)
 
 
-def linear(x: torch.Tensor, w: W16SWeight) -> torch.Tensor:
-    """nn.Linear.__call__ on a W16S weight: x [..., K] -> [..., N]; fp32 accumulate, one rounding (+ bias in T)."""
+def linear(x: torch.Tensor, w: PackedWeight) -> torch.Tensor:
+    """nn.Linear.__call__ / nn.QuantizedLinear.__call__ on a packed weight: x [..., K] -> [..., N]; fp32 accumulate, one rounding
+    (+ bias in T), on the format's streaming-GEMV entry point."""
     _dev(x)
     if x.shape[-1] != w.K or x.dtype != w.dtype:
         raise ValueError(f"x [..., {x.shape[-1]}] {x.dtype} does not match weight K={w.K} {w.dtype}")
     M = x.numel() // w.K
     y = torch.empty((*x.shape[:-1], w.N), dtype=x.dtype, device=x.device)
-    _ffi.check(_ffi.load().pie_gemv_dense(_ffi.p(x), M, _ffi.p(w.packed), w.N, w.K, _ffi.p(w.lin_bias), _ffi.p(y),
-                                          _ffi.dtype_code(x.dtype), _ffi.stream()))
+    _ffi.check(getattr(_ffi.load(), FORMATS[w.fmt].gemv)(_ffi.p(x), M, _ffi.p(w.packed), w.N, w.K, _ffi.p(w.lin_bias), _ffi.p(y),
+                                                        _ffi.dtype_code(x.dtype), _ffi.stream()))
     return y
 
 
@@ -277,30 +179,20 @@ def embedding_dense(ids: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def quantized_matmul(x: torch.Tensor, w: "W4SWeight | W8SWeight | W4S32Weight", transpose: bool = True, group_size: int | None = None, bits: int | None = None):
-    """mx.quantized_matmul(x, w, scales, biases, transpose=True, group_size=64|32, bits=4|8) on a W4S / W8S / W4S32 weight:
-    x [..., K] -> [..., N]; fp32 accumulate, result in x.dtype (+ nn.QuantizedLinear's bias when present)."""
-    w_bits = 8 if isinstance(w, (W8SWeight, W8S32Weight)) else (6 if isinstance(w, W6SWeight) else (2 if isinstance(w, W2SWeight) else 4))
-    w_group = 32 if isinstance(w, W4S32Weight) else 64
-    if not transpose or (group_size is not None and group_size != w_group) or (bits is not None and bits != w_bits):
+def quantized_matmul(x: torch.Tensor, w: PackedWeight, transpose: bool = True, group_size: int | None = None, bits: int | None = None):
+    """mx.quantized_matmul(x, w, scales, biases, transpose=True, group_size, bits) on a packed weight: x [..., K] -> [..., N]; fp32
+    accumulate, result in x.dtype (+ nn.QuantizedLinear's bias when present)."""
+    if not transpose or (group_size is not None and group_size != w.group_size) or (bits is not None and bits != w.bits):
         raise ValueError("only transpose=True with the weight's own group size and bit width is implemented (the nn.QuantizedLinear form)")
-    _dev(x)
-    if x.shape[-1] != w.K or x.dtype != w.dtype:
-        raise ValueError(f"x [..., {x.shape[-1]}] {x.dtype} does not match weight K={w.K} {w.dtype}")
-    M = x.numel() // w.K
-    y = torch.empty((*x.shape[:-1], w.N), dtype=x.dtype, device=x.device)
-    lib = _ffi.load()
-    fn = lib.pie_qgemv_w2g64 if w_bits == 2 else lib.pie_qgemv_w6g64 if w_bits == 6 else (lib.pie_qgemv_w8g32 if w_bits == 8 else lib.pie_qgemv_w4g32) if w_group == 32 else (lib.pie_qgemv_w8g64 if w_bits == 8 else lib.pie_qgemv_w4g64)
-    _ffi.check(fn(_ffi.p(x), M, _ffi.p(w.packed), w.N, w.K, _ffi.p(w.lin_bias), _ffi.p(y), _ffi.dtype_code(x.dtype), _ffi.stream()))
-    return y
+    return linear(x, w)
 
 
-def quantized_matmul_partial(x: torch.Tensor, w: W4SWeight) -> torch.Tensor:
+def quantized_matmul_partial(x: torch.Tensor, w: PackedWeight) -> torch.Tensor:
     """The fp32 row sums of quantized_matmul before their rounding to T: x [..., K] -> fp32 [..., N].  Row-parallel shards of a
     tensor-parallel Linear are summed over the ranks in this form (tp.py)."""
     _dev(x)
-    if not isinstance(w, W4SWeight) or x.shape[-1] != w.K or x.dtype != w.dtype:
-        raise ValueError("quantized_matmul_partial takes a W4S weight matching x's last dimension and dtype")
+    if w.fmt != _ffi.PIE_W_INT4_G64 or x.shape[-1] != w.K or x.dtype != w.dtype:
+        raise ValueError("quantized_matmul_partial takes an int4 group-64 weight matching x's last dimension and dtype")
     M = x.numel() // w.K
     y = torch.empty((*x.shape[:-1], w.N), dtype=torch.float32, device=x.device)
     _ffi.check(_ffi.load().pie_qgemv_w4g64_f32(_ffi.p(x), M, _ffi.p(w.packed), w.N, w.K, _ffi.p(y), _ffi.dtype_code(x.dtype), _ffi.stream()))
@@ -757,13 +649,13 @@ def add_bias_rms_norm(x: torch.Tensor, r: torch.Tensor, bias: torch.Tensor, norm
     return y, xn
 
 
-def quantized_matmul_rows(x: torch.Tensor, w: "W4SWeight", w4m: torch.Tensor | None = None) -> torch.Tensor:
+def quantized_matmul_rows(x: torch.Tensor, w: PackedWeight, w4m: torch.Tensor | None = None) -> torch.Tensor:
     """mx.quantized_matmul in its many-row regime -- weights dequantised to T, T x T products on the MFMA units, fp32
     accumulation -- reading the int4 weights in 4-bit form (pie_qgemm_w4m: the few-row kernels up to 32 rows, the 256 x 256-tile
     prompt GEMM beyond).  x [M, K]; w: the W4S matrix (N % 32 == 0); w4m: its W4M tile copy from `repack_w4m` (built here when absent)."""
     _dev(x)
-    if not isinstance(w, W4SWeight):
-        raise TypeError("quantized_matmul_rows takes a W4SWeight (int4 g=64)")
+    if w.fmt != _ffi.PIE_W_INT4_G64:
+        raise TypeError("quantized_matmul_rows takes an int4 group-64 weight")
     M, K = x.shape
     if K != w.K or M < 1 or w.N % 32:
         raise ValueError("quantized_matmul_rows: x [M, K], N % 32 == 0")
@@ -776,7 +668,7 @@ def quantized_matmul_rows(x: torch.Tensor, w: "W4SWeight", w4m: torch.Tensor | N
     return y
 
 
-def repack_w4m(w: "W4SWeight") -> torch.Tensor:
+def repack_w4m(w: PackedWeight) -> torch.Tensor:
     """W4S stream -> W4M tiles (32 rows x 64 columns, MFMA operand order; include/pie_hip.h), same bytes per weight."""
     lib = _ffi.load()
     n = lib.pie_w4m_bytes(w.N, w.K)

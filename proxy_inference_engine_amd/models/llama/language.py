@@ -194,10 +194,10 @@ class Model:
         qkv_map = None if args.rope_traditional else hip_ops.qkv_row_map(self.n_heads, self.n_kv_heads, self.head_dim).to(device)
         gu_map = hip_ops.gateup_row_map(I).to(device)
 
-        g32 = self.group_size == 32
-        wfmt = (4 if self.bits == 8 else 3) if g32 else (2 if self.bits == 8 else 0)  # PIE_W_INT8_G32 / INT4_G32 / INT8_G64 / INT4_G64
-        fmt_code = {False: 2, True: wfmt + 1}  # pie_layer_weights.fmt_*: PIE_W_* + 1 (0 = the decoder's default format)
-        PIE_W_INT2_G64, PIE_W_INT6_G64 = 5, 6  # W2S / W6S units: every Linear of a native 2- / 6-bit checkpoint (the embedding table stays wfmt = 4- / 8-bit codes)
+        # 64-wide units also serve 128-wide groups (scales written twice, above); every Linear of a native 2- / 6-bit checkpoint streams W2S / W6S
+        # units, its embedding table stays 4- / 8-bit codes (the decoder's default format: the table's)
+        group = 32 if self.group_size == 32 else 64
+        wfmt = _ffi.PIE_W_DENSE if self.dense else hip_ops.weight_format(self.bits, group)
         self.mixed = False  # some module is dense although config["quantization"] is set (per-module predicate, models/utils.py:99-109)
 
         def quantized(names: list[str]) -> bool:
@@ -208,20 +208,16 @@ class Model:
             return qf
 
         def pack(names: list[str], row_map=None):
-            """One streaming-layout matrix from the (concatenated) Linear weights `names`; returns (matrix, format code)."""
+            """One streaming-layout matrix from the (concatenated) Linear weights `names`; returns (matrix, its pie_layer_weights.fmt_* code)."""
             if not quantized(names):
                 ws = [_dense(weights, n, self.dtype) for n in names]
-                return hip_ops.repack_dense(torch.cat(ws, dim=0) if len(ws) > 1 else ws[0], row_map=row_map), fmt_code[False]
-            trip = [torch.cat(t, dim=0) for t in zip(*(_triplet(weights, n) for n in names))]
-            if self.native_narrow:
-                if names == ["model.embed_tokens"]:  # tied lm_head: the table's own narrow codes, not the gather's 4- / 8-bit copy
+                m = hip_ops.repack_dense(torch.cat(ws, dim=0) if len(ws) > 1 else ws[0], row_map=row_map)
+            else:
+                trip = [torch.cat(t, dim=0) for t in zip(*(_triplet(weights, n) for n in names))]
+                if self.native_narrow and names == ["model.embed_tokens"]:  # tied lm_head: the table's own narrow codes, not the gather's 4- / 8-bit copy
                     trip[0] = embed_codes_narrow
-                if self.native_narrow == 6:
-                    return hip_ops.repack_w6s(*trip, row_map=row_map), PIE_W_INT6_G64 + 1
-                return hip_ops.repack_w2s(*trip, row_map=row_map), PIE_W_INT2_G64 + 1
-            if g32:
-                return hip_ops.repack_w4s32(*trip, row_map=row_map, bits=self.bits), fmt_code[True]
-            return (hip_ops.repack_w8s if self.bits == 8 else hip_ops.repack_w4s)(*trip, row_map=row_map), fmt_code[True]
+                m = hip_ops.repack(*trip, bits=self.native_narrow or self.bits, group_size=group, row_map=row_map)
+            return m, m.fmt + 1  # PIE_W_* + 1 (0 = the decoder's default format)
 
         def bias(names: list[str], row_map=None):
             """The (concatenated) Linear biases of `names` in the packed row order of the matching matrix; a Linear without a
@@ -258,7 +254,7 @@ class Model:
         self.norm = weights["model.norm.weight"].contiguous()
         head = "model.embed_tokens" if args.tie_word_embeddings else "lm_head"  # language.py:206-209
         self.lm_head, f_head = pack([head])
-        f_embed = fmt_code[self.embed_quantized]
+        f_embed = (wfmt if self.embed_quantized else _ffi.PIE_W_DENSE) + 1
 
         # decoder-owned outputs live in torch tensors so callers can read them without copies
         self.logits = torch.zeros(V, dtype=self.dtype, device=device)
@@ -269,7 +265,7 @@ class Model:
         lib = _ffi.load()
         cfg = _ffi.pie_decoder_config(_ffi.dtype_code(self.dtype), H, args.num_hidden_layers, self.n_heads, self.n_kv_heads,
                                       self.head_dim, I, V, float(args.rms_norm_eps), int(args.tie_word_embeddings), int(kv_splits),
-                                      1 if self.dense else wfmt, int(bool(args.rope_traditional)),
+                                      wfmt, int(bool(args.rope_traditional)),
                                       tp.rank if tp is not None else 0, tp.world if tp is not None else 0)
         self._dec = C.c_void_p()
         _ffi.check(lib.pie_decoder_create(C.byref(cfg), C.byref(self._dec)))

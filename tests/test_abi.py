@@ -79,3 +79,90 @@ def test_no_library_gemm_behind_the_c_abi():
     assert lib.pie_w16m_bytes(1280, 3420) == 40 * 54 * 4096 and lib.pie_w16m_bytes(0, 64) == 0   # 32-row x 64-column tiles, zero-padded
     assert lib.pie_linear_w16m_workspace(4096, 6144, 4096) == 0                                    # no K split where the tiles fill the chip
     assert lib.pie_linear_w16m_workspace(64, 4096, 14336) % (64 * 4096 * 4) == 0 and lib.pie_linear_w16m_workspace(64, 4096, 14336) > 0
+
+
+def test_weight_format_entry_points_refuse_before_any_launch_without_gpu():
+    """The per-format entry points: every packed size at several (N, K) (0 for odd N, K % 64 != 0 and non-positive sizes), and every
+    refusal the repack, streaming-GEMV, quantise / dequantise and embedding functions make before a launch -- its code and the function
+    pie_last_error() names.  None of these calls reaches HIP, so they run without a device."""
+    from proxy_inference_engine_amd import _ffi
+    lib = _ffi.load()
+    units = {"pie_w4s_bytes": (2304, 2048), "pie_w8s_bytes": (4352, 2048), "pie_w2s_bytes": (1280, 2048), "pie_w6s_bytes": (3328, 2048),
+             "pie_w4s32_bytes": (2560, 2048), "pie_w8s32_bytes": (4608, 2048), "pie_w16s_bytes": (2048, 512)}
+    for name, (unit, slice_k) in units.items():
+        fn = getattr(lib, name)
+        for N, K in ((2, 64), (6, 576), (4096, 4096), (4096, 14336), (1024, 3072), (128256, 4096), (2, 32768), (2, 40960)):
+            assert fn(N, K) == (N // 2) * -(-K // slice_k) * unit, (name, N, K)
+        for N, K in ((3, 4096), (4, 100), (4, 32), (0, 64), (-2, 64), (2, 0), (2, -64)):
+            assert fn(N, K) == 0, (name, N, K)
+
+    buf = ctypes.create_string_buffer(8192)
+    base = (ctypes.addressof(buf) + 255) & ~255
+    p, odd = ctypes.c_void_p(base), ctypes.c_void_p(base + 2)   # 256-byte aligned / misaligned stand-ins, never dereferenced
+    ARG, SHAPE, ALIGN = -1, -2, -3
+    BF16, BAD = _ffi.PIE_BF16, 7
+
+    def refused(fn, args, code, who):
+        rc = getattr(lib, fn)(*args)
+        err = lib.pie_last_error()
+        assert rc == code and err.split(b":")[0] == who.encode(), (fn, args, rc, err)
+
+    for fn in ("pie_repack_w4g64", "pie_repack_w8g64", "pie_repack_w2g64", "pie_repack_w6g64", "pie_repack_w4g32", "pie_repack_w8g32"):
+        ok = [p, p, p, 8, 256, None, 8, p, None]   # codes, scales, biases, N_src, K, row_map, N_out, packed, stream
+        for i, v, code in ((0, None, ARG), (1, None, ARG), (2, None, ARG), (7, None, ARG), (6, 7, SHAPE), (6, 0, SHAPE), (3, 0, SHAPE),
+                           (4, 100, SHAPE), (4, 0, SHAPE), (4, 32768 + 64, SHAPE), (7, odd, ALIGN)):
+            refused(fn, ok[:i] + [v] + ok[i + 1:], code, fn)
+    ok = [p, 8, 256, None, 8, p, None]   # w, N_src, K, row_map, N_out, packed, stream
+    for i, v, code in ((0, None, ARG), (5, None, ARG), (4, 7, SHAPE), (1, 0, SHAPE), (2, 100, SHAPE), (2, 32768 + 64, SHAPE), (5, odd, ALIGN),
+                       (0, odd, ALIGN)):
+        refused("pie_repack_dense", ok[:i] + [v] + ok[i + 1:], code, "pie_repack_dense")
+
+    for fn in ("pie_qgemv_w4g64", "pie_qgemv_w8g64", "pie_qgemv_w2g64", "pie_qgemv_w6g64", "pie_qgemv_w4g32", "pie_qgemv_w8g32", "pie_gemv_dense"):
+        for M in (1, 2):   # pie_qgemv_w4g64 takes several rows through the many-row streaming launch
+            who = "w4s_gemv_rows" if fn == "pie_qgemv_w4g64" and M > 1 else "w4s_gemv"
+            ok = [p, M, p, 64, 256, None, p, BF16, None]   # x, M, packed, N, K, lin_bias, y, dtype, stream
+            for i, v, code, by in ((0, None, ARG, fn), (2, None, ARG, fn), (6, None, ARG, fn), (1, 0, SHAPE, fn), (1, 65536, SHAPE, fn),
+                                   (0, odd, ALIGN, fn), (2, odd, ALIGN, fn), (4, 100, SHAPE, who), (4, 0, SHAPE, who), (3, 63, SHAPE, who),
+                                   (3, 0, SHAPE, who), (4, 32768 + 64, SHAPE, who), (7, BAD, ARG, who)):
+                refused(fn, ok[:i] + [v] + ok[i + 1:], code, by)
+    ok = [p, 1, p, 64, 256, p, BF16, None]   # x, M, packed, N, K, y (fp32), dtype, stream
+    for i, v, code, by in ((0, None, ARG, "pie_qgemv_w4g64_f32"), (5, None, ARG, "pie_qgemv_w4g64_f32"), (1, 0, SHAPE, "pie_qgemv_w4g64_f32"),
+                           (4, 100, SHAPE, "w4s_gemv"), (3, 63, SHAPE, "w4s_gemv"), (4, 32768 + 64, SHAPE, "w4s_gemv"), (6, BAD, ARG, "w4s_gemv")):
+        refused("pie_qgemv_w4g64_f32", ok[:i] + [v] + ok[i + 1:], code, by)
+
+    ok = [p, 8, 256, 4, BF16, p, p, p, None]   # w, N, K, bits, dtype, codes, scales, biases, stream
+    for i, v, code, by in ((0, None, ARG, "pie_quantize_w4g64"), (5, None, ARG, "pie_quantize_w4g64"), (7, None, ARG, "pie_quantize_w4g64"),
+                           (3, 3, ARG, "pie_quantize_g64"), (3, 16, ARG, "pie_quantize_g64"), (1, 0, SHAPE, "pie_quantize_w4g64"),
+                           (2, 100, SHAPE, "pie_quantize_w4g64"), (0, odd, ALIGN, "pie_quantize_w4g64"), (5, odd, ALIGN, "pie_quantize_w4g64")):
+        refused("pie_quantize_g64", ok[:i] + [v] + ok[i + 1:], code, by)
+    for bits in (2, 4, 6, 8):
+        refused("pie_quantize_g64", ok[:3] + [bits, BAD] + ok[5:], ARG, "pie_quantize_w4g64")
+    refused("pie_quantize_w4g64", [None, 8, 256, BF16, p, p, p, None], ARG, "pie_quantize_w4g64")
+    refused("pie_quantize_w4g64", [p, 8, 100, BF16, p, p, p, None], SHAPE, "pie_quantize_w4g64")
+    refused("pie_quantize_w4g64", [p, 8, 256, BAD, p, p, p, None], ARG, "pie_quantize_w4g64")
+
+    ok = [p, p, p, 8, 256, 4, BF16, p, None]   # codes, scales, biases, N, K, bits, dtype, w_out, stream
+    for i, v, code, by in ((0, None, ARG, "pie_dequantize_w4g64"), (7, None, ARG, "pie_dequantize_w4g64"), (5, 2, ARG, "pie_dequantize_g64"),
+                           (5, 6, ARG, "pie_dequantize_g64"), (3, 0, SHAPE, "pie_dequantize_w4g64"), (4, 100, SHAPE, "pie_dequantize_w4g64"),
+                           (7, odd, ALIGN, "pie_dequantize_w4g64")):
+        refused("pie_dequantize_g64", ok[:i] + [v] + ok[i + 1:], code, by)
+    for bits in (4, 8):
+        refused("pie_dequantize_g64", ok[:5] + [bits, BAD] + ok[7:], ARG, "pie_dequantize_w4g64")
+    refused("pie_dequantize_w4g64", [p, p, p, 8, 100, BF16, p, None], SHAPE, "pie_dequantize_w4g64")
+    refused("pie_dequantize_w4g64", [p, p, p, 8, 256, BAD, p, None], ARG, "pie_dequantize_w4g64")
+
+    for fn in ("pie_embedding_g64", "pie_embedding_g32"):
+        ok = [p, 2, p, p, p, 16, 256, 4, BF16, p, None]   # ids, L, codes, scales, biases, V, H, bits, dtype, out, stream
+        for i, v, code, by in ((7, 2, ARG, fn), (7, 6, ARG, fn), (0, None, ARG, "pie_embedding_w4g64"), (2, None, ARG, "pie_embedding_w4g64"),
+                               (9, None, ARG, "pie_embedding_w4g64"), (1, 0, SHAPE, "pie_embedding_w4g64"), (5, 0, SHAPE, "pie_embedding_w4g64"),
+                               (6, 100, SHAPE, "pie_embedding_w4g64"), (9, odd, ALIGN, "pie_embedding_w4g64")):
+            refused(fn, ok[:i] + [v] + ok[i + 1:], code, by)
+        for bits in (4, 8):
+            refused(fn, ok[:7] + [bits, BAD] + ok[9:], ARG, "pie_embedding_w4g64")
+    ok = [p, 2, p, p, p, 16, 256, BF16, p, None]   # ids, L, codes, scales, biases, V, H, dtype, out, stream
+    for i, v, code in ((0, None, ARG), (4, None, ARG), (1, 0, SHAPE), (6, 100, SHAPE), (8, odd, ALIGN), (7, BAD, ARG)):
+        refused("pie_embedding_w4g64", ok[:i] + [v] + ok[i + 1:], code, "pie_embedding_w4g64")
+    ok = [p, 2, p, 16, 256, BF16, p, None]   # ids, L, table, V, H, dtype, out, stream
+    for i, v, code in ((0, None, ARG), (2, None, ARG), (6, None, ARG), (1, 0, SHAPE), (4, 100, SHAPE), (5, BAD, ARG), (2, odd, ALIGN),
+                       (6, odd, ALIGN)):
+        refused("pie_embedding_dense", ok[:i] + [v] + ok[i + 1:], code, "pie_embedding_dense")

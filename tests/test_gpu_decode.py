@@ -1083,8 +1083,9 @@ def test_narrow_checkpoints_stream_native_units(bits, group, tied, dtype):
     H, I, V, QKV = 256, 768, 512, 256 + 2 * 128
     n_lin = 2 * (QKV * H + H * H + 2 * I * H + H * I) + V * H          # weights of every Linear the step streams
     unit = 1280 if bits == 2 else 3328
+    from proxy_inference_engine_amd import _ffi
     for m in (model.layers[0].wqkv, model.layers[0].wdown, model.lm_head):
-        assert type(m).__name__ == ("W2SWeight" if bits == 2 else "W6SWeight") and m.nbytes == (m.N // 2) * ((m.K + 2047) // 2048) * unit
+        assert m.fmt == (_ffi.PIE_W_INT2_G64 if bits == 2 else _ffi.PIE_W_INT6_G64) and m.nbytes == (m.N // 2) * ((m.K + 2047) // 2048) * unit
     want_bytes = n_lin * (4 * bits + 2) // 32                              # `bits` per weight + a 16-bit (scale, bias) pair per 64 weights
     got_bytes = model.step_bytes(64)
     assert want_bytes <= got_bytes <= want_bytes + 200_000, (got_bytes, want_bytes)   # + norms, 64 positions of K / V, the tail
