@@ -27,80 +27,47 @@ class BaseCache(ABC):
             raise NotImplementedError("only ReusableKVCache is on the engine path (prompt_cache.py:34-41, :73)")
         return [ReusableKVCache() for _ in range(len(model.layers))]
 
-    # -- persistence (cache/kv_cache/__init__.py:163-210): one .safetensors file, arrays named by their position in the
-    # nested [layer][keys|values] list ("3.0" = layer 3 keys), metadata flattened the same way:
-    # "0.<i>" = meta_state of layer i, "1.<key>" = the caller's metadata, "2.<i>" = cache class name of layer i.
-    # A QuantizedKVCache layer's state and meta_state are nested one level deeper, as tree_flatten names them: arrays
-    # "<i>.<0 keys | 1 values>.<0 codes | 1 scales | 2 biases>", meta "0.<i>.<0 step | 1 offset | 2 group_size | 3 bits>".
-    # A RotatingKVCache layer: arrays "<i>.0" / "<i>.1" (its state), meta "0.<i>.<k>" = keep, max_size, step, offset, _idx.
+    # -- persistence (cache/kv_cache/__init__.py:163-210): one .safetensors file.  The per-layer `state` list and the metadata list
+    # [per-layer meta_state, the caller's metadata, per-layer class names] are flattened by position, as tree_flatten names them:
+    # arrays "3.0" = layer 3 keys (a QuantizedKVCache: "3.0.<0 codes | 1 scales | 2 biases>"), metadata "0.<i>" = meta_state of
+    # layer i (a tuple: "0.<i>.<k>"), "1.<key>" = the caller's, "2.<i>" = the class layer i is restored as.
+    saved_as: str | None = None      # the class name a layer is stored under, if not its own
+    meta_args: dict[str, int] = {}   # constructor arguments load_cache takes from the stored meta_state: name -> position (the reference
+                                     # calls every class without arguments, which RotatingKVCache(max_size) does not accept)
+
     @staticmethod
     def save_cache(file_name: str, cache: list["BaseCache"], metadata: dict[str, str] | None = None) -> None:
         from safetensors.torch import save_file
         arrays: dict[str, torch.Tensor] = {}
         meta: dict[str, str] = {}
         for i, c in enumerate(cache):
-            if isinstance(c, RotatingKVCache):
-                for j, t in enumerate(c.state):
-                    if t is not None:
-                        arrays[f"{i}.{j}"] = t.detach().to("cpu").contiguous()
-                for k, v in enumerate(c.meta_state):
-                    meta[f"0.{i}.{k}"] = v
-                meta[f"2.{i}"] = type(c).__name__
-                continue
-            if isinstance(c, QuantizedKVCache):
-                for j, triple in enumerate(c.state):
-                    for k, t in enumerate(triple or ()):
-                        arrays[f"{i}.{j}.{k}"] = t.detach().to("cpu").contiguous()
-                for k, v in enumerate(c.meta_state):
-                    meta[f"0.{i}.{k}"] = v
-                meta[f"2.{i}"] = type(c).__name__
-                continue
-            for j, t in enumerate(c.state):
-                if t is not None:
-                    arrays[f"{i}.{j}"] = t.detach().to("cpu").contiguous()
-            meta[f"0.{i}"] = str(c.meta_state)
-            # a paged cache is stored as its gathered rows, the layout a ReusableKVCache restores from
-            meta[f"2.{i}"] = "ReusableKVCache" if type(c).__name__ == "PagedKVCache" else type(c).__name__
+            _flatten(c.state, str(i), arrays)
+            _flatten(c.meta_state, f"0.{i}", meta)
+            meta[f"2.{i}"] = c.saved_as or type(c).__name__
         for k, v in (metadata or {}).items():
             meta[f"1.{k}"] = str(v)
-        save_file(arrays, file_name, metadata=meta)
+        save_file({k: t.detach().to("cpu").contiguous() for k, t in arrays.items()}, file_name, metadata=meta)
 
     @staticmethod
     def load_cache(file_name: str, device=None) -> tuple[list["BaseCache"], dict[str, str]]:
         from safetensors import safe_open
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        classes = {"ReusableKVCache": ReusableKVCache, "QuantizedKVCache": QuantizedKVCache, "RotatingKVCache": RotatingKVCache}
+        classes = {cls.__name__: cls for cls in (ReusableKVCache, QuantizedKVCache, RotatingKVCache)}
         with safe_open(file_name, framework="pt", device="cpu") as f:
             meta = f.metadata() or {}
-            n = sum(1 for k in meta if k.startswith("2."))
-            cache: list[BaseCache] = []
-            for i in range(n):
-                name = meta[f"2.{i}"]
-                if name not in classes:
-                    raise ValueError(f"{file_name}: cache class {name} is not on the MI355X path")
-                if name == "RotatingKVCache":
-                    # the reference's loader calls the class without arguments, which RotatingKVCache(max_size) does not accept: the size
-                    # comes from the meta strings here
-                    ms = tuple(meta[f"0.{i}.{k}"] for k in range(5))
-                    c = RotatingKVCache(max_size=int(ms[1]), keep=int(ms[0]), step=int(ms[2]))
-                    if f"{i}.0" in f.keys():
-                        c.state = (f.get_tensor(f"{i}.0").to(device), f.get_tensor(f"{i}.1").to(device))
-                    c.meta_state = ms
-                    cache.append(c)
-                    continue
-                c = classes[name]()
-                if isinstance(c, QuantizedKVCache):
-                    keys = f.keys()
-                    if f"{i}.0.0" in keys:
-                        c.state = tuple(tuple(f.get_tensor(f"{i}.{j}.{k}").to(device) for k in range(3)) for j in range(2))
-                    c.meta_state = tuple(meta[f"0.{i}.{k}"] for k in range(4))
-                    cache.append(c)
-                    continue
-                state = tuple(f.get_tensor(f"{i}.{j}").to(device) if f"{i}.{j}" in f.keys() else None for j in range(2))
+            arrays = {k: f.get_tensor(k).to(device) for k in f.keys()}
+        cache: list[BaseCache] = []
+        for i in range(sum(1 for k in meta if k.startswith("2."))):
+            name = meta[f"2.{i}"]
+            if name not in classes:
+                raise ValueError(f"{file_name}: cache class {name} is not on the MI355X path")
+            state, meta_state = _unflatten(arrays, str(i)), _unflatten(meta, f"0.{i}")
+            c = classes[name](**{k: int(meta_state[j]) for k, j in classes[name].meta_args.items()})
+            if state is not None:
                 c.state = state
-                c.meta_state = meta.get(f"0.{i}", "")
-                cache.append(c)
+            c.meta_state = meta_state
+            cache.append(c)
         return cache, {k[2:]: v for k, v in meta.items() if k.startswith("1.")}
 
     @property
@@ -124,6 +91,12 @@ class BaseCache(ABC):
     def is_trimmable(self) -> bool:
         return False
 
+    # The decode kernels append the new rows themselves, so every cache on the decode path also offers update_and_fetch as its two
+    # halves, which the decoder's binding (models/llama/kv_binding.py) calls on every layer around a model call:
+    #   reserve(needed, n_kv_heads, head_dim, dtype, device)   room for `needed` more positions behind `offset`: allocates or grows the
+    #                                                          [1, n_kv_heads, capacity, head_dim] buffers where the cache owns them
+    #   advance(n)                                             books the `n` rows the decoder has written: offset += n
+
     @abstractmethod
     def trim(self, n: int) -> int: ...
 
@@ -132,6 +105,27 @@ class BaseCache(ABC):
 
     @abstractmethod
     def to_quantized(self, group_size: int = 64, bits: int = 4) -> "BaseCache": ...
+
+
+def _flatten(tree, name: str, out: dict) -> None:
+    """tree_flatten: the leaves of nested tuples / lists under dotted position names; None holds nothing."""
+    if isinstance(tree, (tuple, list)):
+        for i, t in enumerate(tree):
+            _flatten(t, f"{name}.{i}", out)
+    elif tree is not None:
+        out[name] = tree
+
+
+def _unflatten(flat: dict, name: str):
+    """tree_unflatten of what _flatten stored under `name`: the leaf, a tuple of what lies below it, or None."""
+    if name in flat:
+        return flat[name]
+    if not any(k.startswith(name + ".") for k in flat):
+        return None
+    below = []
+    while (t := _unflatten(flat, f"{name}.{len(below)}")) is not None:
+        below.append(t)
+    return tuple(below) or None
 
 
 from .reusable import ReusableKVCache  # noqa: E402

@@ -259,6 +259,17 @@ class PagedKVCache(BaseCache):
     def capacity(self) -> int:
         return self.page_manager.capacity
 
+    saved_as = "ReusableKVCache"  # save_cache stores the gathered rows, the layout a ReusableKVCache restores from
+
+    def reserve(self, needed: int, *geometry) -> None:
+        """Pages for `needed` more positions (the pool has the geometry); like reuse and trim, layer 0 acts for the sequence."""
+        if self.layer == 0:
+            self.page_manager.reserve(needed)
+
+    def advance(self, n: int) -> None:
+        if self.layer == 0:
+            self.page_manager.advance(n)
+
     def reuse(self, new_prompt_length: int, common_prefix_length: int) -> None:
         """Trim to the common prefix (reusable.py:44-94); room for the new prompt is taken page by page later."""
         if self.layer == 0:

@@ -37,6 +37,8 @@ class RotatingKVCache(BaseCache):
         self._len = 0          # the reference's keys.shape[2] (rows in use; 0 = no keys yet)
         self._rot0 = self.max_size  # position written at row `keep` when the ring last started rotating (device-side ring rule)
 
+    meta_args = {"max_size": 1, "keep": 0, "step": 2}
+
     # ------------------------------------------------------------------ buffers
     @property
     def capacity(self) -> int:

@@ -8,6 +8,9 @@ into the streaming layouts at load, and (2) keeps the reference's calling conven
 
     logits[1, L, V] = model(inputs[1, L], mask=None, cache=[ReusableKVCache, ...])
 
+The cache may be of any of the four kinds (reusable, quantized, rotating, paged); what the decoder is pointed at is kept by one
+`KVBinding` (kv_binding.py), which every entry point syncs before its launch and advances after it.
+
 Checkpoints: config["quantization"] = {"group_size": 64 | 128, "bits": 2 | 3 | 4 | 6 | 8} (2 / 3-bit codes ride the 4-bit units, 6-bit
 codes the 8-bit units), no entry = dense 16-bit weights, or a per-module mix of both; 32-wide groups are refused by name.
 """
@@ -19,7 +22,8 @@ import torch
 
 from .. import base
 from ... import _ffi, hip_ops
-from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, QuantizedKVCache, ReusableKVCache, RotatingKVCache
+from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, ReusableKVCache
+from .kv_binding import KVBinding, on_int8_pages
 from .utils import Llama3RoPE
 
 
@@ -285,12 +289,9 @@ class Model:
         self.history = torch.zeros(1 << 20, dtype=torch.int32, device=device)
         _ffi.check(lib.pie_decoder_bind_outputs(self._dec, _ffi.p(self.logits), _ffi.p(self.logprobs), _ffi.p(self.token), _ffi.p(self.hidden),
                                                 _ffi.p(self.history), self.history.numel()))
-        self._kv_key = None      # (pointers, capacity) currently in the decoder's device table
-        self._ring_key = None    # (window, keep, rot0, row0, positions) of the bound rotating cache
-        self._kv_hold = None
+        self._kv = KVBinding(lib, self._dec, len(self.layers), self.n_kv_heads, self.head_dim, self.dtype, device, tensor_parallel=tp is not None)
         self._page_pool, self._page_blocks = None, 16
         self._batch_bufs: dict = {}
-        self._dev_offset = None  # device-side cache offset the decoder believes in
         torch.cuda.synchronize(device)
 
     def __del__(self):
@@ -302,7 +303,8 @@ class Model:
                 pass
             self._dec = None
 
-    # ------------------------------------------------------------------ cache plumbing
+    # ------------------------------------------------------------------ cache plumbing: the caches are made here; `self._kv` (kv_binding.py)
+    # points the decoder at whichever kind a call is given
     def make_cache(self) -> list[BaseCache]:
         if self._page_pool is not None:
             return self.make_paged_cache(self._page_pool, max_blocks=self._page_blocks)
@@ -329,9 +331,8 @@ class Model:
                 raise ValueError("kv_scales: two float16 tensors [n_layers, n_kv_heads]")
             for li in range(len(self.layers)):
                 hip_ops.page_i8_set_scales(self._page_pool.slab[li], num_pages, self.n_kv_heads, self.head_dim, ks[li], vs[li])
-        _ffi.check(_ffi.load().pie_decoder_configure(self._dec, _ffi.PIE_OPT_KV_I8, int(kv_dtype == torch.int8)))
-        self._kv_i8 = kv_dtype == torch.int8
-        self._kv_key = None
+        self._kv.match_page_format(self._page_pool, always=True)
+        self._kv.invalidate()
         self._page_blocks = max_blocks
         return self._page_pool
 
@@ -347,133 +348,6 @@ class Model:
             raise ValueError("the allocator's geometry does not match this model")
         seq = PagedSequence(allocator, max_blocks)
         return [PagedKVCache(seq, i) for i in range(len(self.layers))]
-
-    def _match_page_format(self, allocator: PageAllocator) -> None:
-        """The decoder indexes the slabs with the page stride of ITS page format (PIE_OPT_KV_I8); a pool handed to make_cache(allocator=...)
-        may be of the other one.  The batch entry points therefore follow the pool they are given (and the C ABI checks the slab size)."""
-        want = allocator.dtype == torch.int8
-        if getattr(self, "_kv_i8", None) != want:
-            _ffi.check(_ffi.load().pie_decoder_configure(self._dec, _ffi.PIE_OPT_KV_I8, int(want)))
-            self._kv_i8 = want
-
-    def _sync_paged(self, cache: list[PagedKVCache], n_new: int) -> None:
-        seq = cache[0].page_manager
-        if any(not isinstance(c, PagedKVCache) or c.page_manager is not seq for c in cache):
-            raise TypeError("the layers of a paged cache must share one PagedSequence")
-        seq.reserve(n_new)
-        a = seq.allocator
-        self._match_page_format(a)  # int8 pages (round 4): the step's new K / V row is quantised into the sequence's page, attention reads the codes back
-        key = ("paged", a.slab.data_ptr(), a.size(), seq.table.data_ptr(), seq.max_blocks, a.dtype == torch.int8)
-        lib = _ffi.load()
-        if key != self._kv_key:
-            n = len(cache)
-            slabs = (C.c_void_p * n)(*[a.slab[i].data_ptr() for i in range(n)])
-            _ffi.check(lib.pie_decoder_set_paged_kv(self._dec, slabs, a.size(), _ffi.p(seq.table), seq.max_blocks, _ffi.stream()))
-            self._kv_key = key
-            self._kv_hold = (a, seq.table)  # keeps the slab and the table alive while the decoder points at them
-        if self._dev_offset != seq.offset:
-            _ffi.check(lib.pie_decoder_set_state(self._dec, seq.offset, -1, _ffi.stream()))
-            self._dev_offset = seq.offset
-
-    def _sync_cache(self, cache: list[ReusableKVCache], n_new: int) -> None:
-        """The host half of cache.update_and_fetch for every layer (reusable.py:113-131), then make the decoder's
-        device-side view (buffer addresses, capacity, offset) match the Python objects."""
-        if len(cache) != len(self.layers):
-            raise ValueError(f"expected {len(self.layers)} layer caches, got {len(cache)}")
-        if isinstance(cache[0], PagedKVCache):
-            return self._sync_paged(cache, n_new)
-        if isinstance(cache[0], QuantizedKVCache):
-            return self._sync_quant(cache, n_new)
-        if isinstance(cache[0], RotatingKVCache):
-            return self._sync_ring(cache, n_new)
-        off = cache[0].offset
-        for c in cache:
-            if not isinstance(c, ReusableKVCache):
-                raise TypeError("the decode path runs on ReusableKVCache (prompt_cache.py:73)")
-            if c.offset != off:
-                raise ValueError("layer caches disagree on offset")
-            c.reserve(n_new, self.n_kv_heads, self.head_dim, self.dtype, self.device)
-        cap = min(c.capacity for c in cache)
-        key = (tuple(c.keys.data_ptr() for c in cache), tuple(c.values.data_ptr() for c in cache), cap)
-        lib = _ffi.load()
-        if key != self._kv_key:
-            n = len(cache)
-            kp = (C.c_void_p * n)(*key[0])
-            vp = (C.c_void_p * n)(*key[1])
-            _ffi.check(lib.pie_decoder_set_kv(self._dec, kp, vp, cap, _ffi.stream()))
-            self._kv_key = key
-        if self._dev_offset != off:
-            _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
-            self._dev_offset = off
-
-    def _sync_quant(self, cache: list[QuantizedKVCache], n_new: int) -> None:
-        """_sync_cache for QuantizedKVCache layers (quantized.py:53-80 for the capacity): the decoder appends quantised rows and
-        attends the codes.  The binding key carries the format, so a captured step graph is re-captured when it changes."""
-        c0 = cache[0]
-        off = c0.offset
-        for c in cache:
-            if not isinstance(c, QuantizedKVCache):
-                raise TypeError("all layers of a quantized cache must be QuantizedKVCache")
-            if c.offset != off or c.group_size != c0.group_size or c.bits != c0.bits:
-                raise ValueError("layer caches disagree on offset or format")
-            c.reserve(n_new, self.n_kv_heads, self.head_dim, self.dtype, self.device)
-        cap = min(c.capacity for c in cache)
-        ptrs = tuple(tuple(t.data_ptr() for t in (*c.keys, *c.values)) for c in cache)
-        key = ("quant", ptrs, cap, c0.group_size, c0.bits)
-        lib = _ffi.load()
-        if key != self._kv_key:
-            n = len(cache)
-            cols = [(C.c_void_p * n)(*[p[j] for p in ptrs]) for j in range(6)]
-            _ffi.check(lib.pie_decoder_set_kv_quant(self._dec, *cols, cap, c0.group_size, c0.bits, _ffi.stream()))
-            self._kv_key = key
-        if self._dev_offset != off:
-            _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
-            self._dev_offset = off
-
-    def _sync_ring(self, cache: list[RotatingKVCache], n_new: int) -> None:
-        """_sync_cache for RotatingKVCache layers (rotating.py): every layer's rows are rearranged for the update first (HIP row moves,
-        outside any captured graph), then the decoder is pointed at the ring -- its window and sink rows, the row rule of the steps and
-        the buffer row a prompt pass appends at.  Everything is checked before the first launch."""
-        c0 = cache[0]
-        for c in cache:
-            if not isinstance(c, RotatingKVCache):
-                raise TypeError("all layers of a rotating cache must be RotatingKVCache")
-            if (c.offset, c.max_size, c.keep, c._idx, c._len) != (c0.offset, c0.max_size, c0.keep, c0._idx, c0._len):
-                raise ValueError("layer caches disagree on offset or ring geometry")
-        if self.tp is not None:
-            raise ValueError("a rotating KV cache is not available on a tensor-parallel model")
-        if c0.keys is not None and (c0.keys.dtype != self.dtype or c0.keys.device != self.device):
-            raise ValueError("the rotating cache's buffers are not in the model's dtype / device")
-        rows = [c.prepare(n_new, self.n_kv_heads, self.head_dim, self.dtype, self.device) for c in cache]
-        cap = min(c.capacity for c in cache)
-        key = (tuple(c.keys.data_ptr() for c in cache), tuple(c.values.data_ptr() for c in cache), cap)
-        lib = _ffi.load()
-        if key != self._kv_key:
-            n = len(cache)
-            kp = (C.c_void_p * n)(*key[0])
-            vp = (C.c_void_p * n)(*key[1])
-            _ffi.check(lib.pie_decoder_set_kv(self._dec, kp, vp, cap, _ffi.stream()))
-            self._kv_key = key
-            self._ring_key = None
-        # the steps' positions stay below `positions` (the staging table covers them): grown in 64k steps
-        off = c0.offset
-        positions = ((off + n_new) // 65536 + 1) * 65536
-        row0 = rows[0] if n_new > 1 else 0
-        ring = (c0.max_size, c0.keep, c0._rot0, row0, positions)
-        if ring != getattr(self, "_ring_key", None):
-            _ffi.check(lib.pie_decoder_set_kv_ring(self._dec, c0.max_size, c0.keep, c0._rot0, row0, positions, _ffi.stream()))
-            self._ring_key = ring
-        if self._dev_offset != off:
-            _ffi.check(lib.pie_decoder_set_state(self._dec, off, -1, _ffi.stream()))
-            self._dev_offset = off
-
-    def _advance(self, cache, n: int) -> None:
-        if isinstance(cache[0], PagedKVCache):
-            cache[0].page_manager.advance(n)
-        else:
-            for c in cache:
-                c.advance(n)  # reusable.py:139
-        self._dev_offset += n
 
     # ------------------------------------------------------------------ reference calling convention
     def __call__(self, inputs: torch.Tensor | None = None, mask=None, cache: list[BaseCache] | None = None,
@@ -492,7 +366,7 @@ class Model:
         if inputs_embeds is not None:
             emb = self._check_embeds(inputs_embeds)
             L = emb.shape[0]
-            self._sync_cache(cache, L)
+            self._kv.sync(cache, L)
             out = torch.empty((L, self.vocab_out), dtype=self.dtype, device=self.device)
             _ffi.check(lib.pie_decoder_prefill_embeds(self._dec, _ffi.p(emb), L, _ffi.p(out), _ffi.stream()))
         else:
@@ -500,10 +374,10 @@ class Model:
                 raise ValueError("batch-1 path: inputs must be [1, L]")
             ids = inputs.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            self._sync_cache(cache, L)
+            self._kv.sync(cache, L)
             out = torch.empty((L, self.vocab_out), dtype=self.dtype, device=self.device)
             _ffi.check(lib.pie_decoder_prefill(self._dec, _ffi.p(ids), L, _ffi.p(out), _ffi.stream()))
-        self._advance(cache, L)
+        self._kv.advance(cache, L)
         return out.unsqueeze(0)
 
     def _check_mask(self, mask, L: int, cache) -> None:
@@ -515,11 +389,9 @@ class Model:
             if mask != "causal":
                 raise NotImplementedError(f"mask={mask!r}: only the causal mask is supported")
             return
-        c0 = cache[0]
-        offset = int(c0.page_manager.offset if isinstance(c0, PagedKVCache) else c0.offset)
-        window = None
-        if isinstance(c0, RotatingKVCache):  # the windowed mask create_attention_mask builds for a ring (models/base.py)
-            offset, window = min(c0.max_size, offset), c0.max_size
+        offset, window = int(cache[0].offset), getattr(cache[0], "max_size", None)
+        if window is not None:  # a ring: the windowed mask create_attention_mask builds for it (models/base.py)
+            offset = min(window, offset)
         m = torch.as_tensor(mask)
         blocked = (~m) if m.dtype == torch.bool else (m < 0)
         blocked = blocked.reshape(-1, blocked.shape[-1]) if blocked.dim() > 2 else blocked
@@ -551,15 +423,15 @@ class Model:
         On an int8 page pool such a prompt runs as L decode steps (~1.2 ms per row on the 8B model: the batched single-sequence pass reads
         T pages and the several-prompts pass takes token ids only); warned about once."""
         emb = self._check_embeds(inputs_embeds)
-        if emb.shape[0] >= 6 and isinstance(cache[0], PagedKVCache) and cache[0].page_manager.allocator.dtype == torch.int8 and not getattr(self, "_warned_i8_embeds", False):
+        if emb.shape[0] >= 6 and on_int8_pages(cache) and not getattr(self, "_warned_i8_embeds", False):
             import warnings
             warnings.warn("a prompt of embeddings on int8 KV pages is processed one row per decode step; use T pages for VLM prompts, or token prompts", stacklevel=2)
             self._warned_i8_embeds = True
         L = emb.shape[0]
-        self._sync_cache(cache, L)
+        self._kv.sync(cache, L)
         _ffi.check(_ffi.load().pie_decoder_prefill_embeds(self._dec, _ffi.p(emb), L, None, _ffi.stream()))
-        self._advance(cache, L)
-        pos = self._dev_offset
+        self._kv.advance(cache, L)
+        pos = self._kv.offset
         token = self.history[pos:pos + 1] if pos < self.history.numel() else self.token.clone()
         return token, self.logprobs, self.logits
 
@@ -573,23 +445,22 @@ class Model:
         lib = _ffi.load()
         if ids is None:
             L = 1
-            self._sync_cache(cache, L)
+            self._kv.sync(cache, L)
         else:
             ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            if L >= 6 and isinstance(cache[0], PagedKVCache) and cache[0].page_manager.allocator.dtype == torch.int8 and cache[0].offset == 0:
+            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0:
                 # A fresh prompt on int8 pages: the single-sequence prompt pass reads T pages (it would run the prompt as L decode steps,
                 # ~1.2 ms per token), the several-prompts pass quantises into int8 pages -- one prompt is a batch of one.
                 nxt, logprobs, logits = self.prefill_batch([ids.cpu().numpy()], [cache])  # (a prompt arrives once: the host copy is the pass's own row bookkeeping)
                 pos = cache[0].offset  # position the chosen token will occupy
-                self._kv_key = None     # the pass bound its own table: the next step re-binds the sequence and sets the device-side offset
-                self._dev_offset = None
+                self._kv.invalidate()   # the pass bound its own table: the next step re-binds the sequence and sets the device-side offset
                 _ffi.check(lib.pie_decoder_set_token_from(self._dec, _ffi.p(nxt), _ffi.stream()))  # device to device: step(None) feeds it back
                 if pos < self.history.numel():
                     self.history[pos:pos + 1].copy_(nxt[:1])
                     return self.history[pos:pos + 1], logprobs[0], logits[0]
                 return nxt[:1].clone(), logprobs[0], logits[0]
-            self._sync_cache(cache, L)
+            self._kv.sync(cache, L)
             if L == 1:
                 _ffi.check(lib.pie_decoder_set_token_from(self._dec, _ffi.p(ids), _ffi.stream()))
         if L == 1:
@@ -597,8 +468,8 @@ class Model:
             _ffi.check(lib.pie_decoder_step(self._dec, flags, _ffi.stream()))
         else:
             _ffi.check(lib.pie_decoder_prefill(self._dec, _ffi.p(ids), L, None, _ffi.stream()))
-        self._advance(cache, L)
-        pos = self._dev_offset  # position the chosen token will occupy
+        self._kv.advance(cache, L)
+        pos = self._kv.offset  # position the chosen token will occupy
         token = self.history[pos:pos + 1] if pos < self.history.numel() else self.token.clone()
         return token, self.logprobs, self.logits
 
@@ -610,14 +481,7 @@ class Model:
         valid until the next step_batch of that size; every cache advances by one position.  graph: replay a captured hipGraph
         of the step while the batch size and table width stay the same (captured on the second such step).
         The weights stream once for the whole batch: int4 models run the few-row MFMA GEMM up to 32 sequences."""
-        seqs = []
-        for c in caches:
-            if len(c) != len(self.layers) or not isinstance(c[0], PagedKVCache):
-                raise TypeError("step_batch runs on paged caches (enable_paged_kv(), then make_cache())")
-            seqs.append(c[0].page_manager)
-        a = seqs[0].allocator
-        if any(s.allocator is not a for s in seqs) or len({id(s) for s in seqs}) != len(seqs):
-            raise ValueError("step_batch: distinct sequences of one page pool")
+        seqs = self._kv.sequences("step_batch", caches)
         B = len(seqs)
         tokens = tokens.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
         if tokens.numel() != B:
@@ -651,10 +515,7 @@ class Model:
             buf["key"] = key
         buf["tokens"].copy_(tokens)
         buf["ctx"].copy_(torch.tensor([s.offset + 1 for s in seqs], dtype=torch.int32))
-        n = len(self.layers)
-        slabs = (C.c_void_p * n)(*[a.slab[i].data_ptr() for i in range(n)])
-        self._match_page_format(a)
-        _ffi.check(_ffi.load().pie_decoder_step_batch(self._dec, _ffi.p(buf["tokens"]), _ffi.p(buf["ctx"]), slabs, a.size(), a.slab[0].numel() * a.slab.element_size(), _ffi.p(buf["table"]),
+        _ffi.check(_ffi.load().pie_decoder_step_batch(self._dec, _ffi.p(buf["tokens"]), _ffi.p(buf["ctx"]), *self._kv.pool_args(seqs[0].allocator), _ffi.p(buf["table"]),
                                                       buf["table"].shape[1], B, _ffi.p(buf["logits"]), _ffi.p(buf["logprobs"]), _ffi.p(buf["next"]),
                                                       _ffi.PIE_STEP_GRAPH if graph else 0, _ffi.stream()))
         nxt, logprobs, logits = buf["next"], buf["logprobs"], buf["logits"]
@@ -680,22 +541,14 @@ class Model:
 
     def _varlen_pass(self, who: str, tokens, decode_caches, prompts, caches):
         import numpy as np
-        seqs, dseqs = [], []
-        for c in list(decode_caches) + list(caches):
-            if len(c) != len(self.layers) or not isinstance(c[0], PagedKVCache):
-                raise TypeError(f"{who} runs on paged caches (enable_paged_kv(), then make_cache())")
-        for c in caches:
-            if c[0].offset != 0 and who == "prefill_batch":
-                raise ValueError(f"{who} takes fresh caches for the prompts (nothing cached before the prompt)")
-            seqs.append(c[0].page_manager)
-        dseqs = [c[0].page_manager for c in decode_caches]
-        every = dseqs + seqs
-        if not every:
-            raise ValueError(f"{who}: an empty batch")
+        every = self._kv.sequences(who, list(decode_caches) + list(caches))
+        B = len(decode_caches)
+        dseqs, seqs = every[:B], every[B:]
+        if who == "prefill_batch" and any(s.offset for s in seqs):
+            raise ValueError(f"{who} takes fresh caches for the prompts (nothing cached before the prompt)")
+        if len(prompts) != len(seqs):
+            raise ValueError(f"{who}: one prompt per prompt cache")
         a = every[0].allocator
-        if len(prompts) != len(seqs) or any(s.allocator is not a for s in every) or len({id(s) for s in every}) != len(every):
-            raise ValueError(f"{who}: one distinct sequence of one page pool per prompt and per decoding row")
-        B = len(dseqs)
         if B:
             tokens = torch.as_tensor(tokens).reshape(-1).to(device=self.device, dtype=torch.int32)   # stays on the device: no host sync per pass
             if tokens.numel() != B:
@@ -737,12 +590,9 @@ class Model:
         logits = torch.empty((B + S, V), dtype=self.dtype, device=self.device)
         logprobs = torch.empty((B + S, V), dtype=torch.float32, device=self.device)
         nxt = torch.empty(B + S, dtype=torch.int32, device=self.device)
-        n = len(self.layers)
-        slabs = (C.c_void_p * n)(*[a.slab[i].data_ptr() for i in range(n)])
-        self._match_page_format(a)
         lib = _ffi.load()
         head = (self._dec, _ffi.p(t_ids), _ffi.p(t_ctx), _ffi.p(t_seq), _ffi.p(t_lo), _ffi.p(t_hi), _ffi.p(t_last), B + N, B + S)
-        tail = (slabs, a.size(), a.slab[0].numel() * a.slab.element_size(), _ffi.p(t_table), mb, _ffi.p(logits), _ffi.p(logprobs), _ffi.p(nxt))
+        tail = (*self._kv.pool_args(a), _ffi.p(t_table), mb, _ffi.p(logits), _ffi.p(logprobs), _ffi.p(nxt))
         if B or len(chunks):
             _ffi.check(lib.pie_decoder_step_mixed(*head, B, *tail, len(chunks), chunks.ctypes.data if len(chunks) else None, _ffi.stream()))
         else:

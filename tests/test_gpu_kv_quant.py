@@ -293,7 +293,7 @@ def test_refused_configurations_raise(tiny):
         rc = lib.pie_decoder_set_kv_quant(model._dec, arr, arr, arr, arr, arr, arr, 256, gs, bits, _ffi.stream())
         assert rc < 0 and b"pie_decoder_set_kv_quant" in lib.pie_last_error()
     # the decoder still runs on a 16-bit cache afterwards
-    model._kv_key = None
+    model._kv.invalidate()
     _, toks = run(model, model.make_cache(), [int(t) for t in g["prompt"]], 2)
     assert len(toks) == 3
 

@@ -350,7 +350,7 @@ def test_refused_configurations_raise_without_launch(tiny):
     with pytest.raises(TypeError):
         model.step_batch(torch.tensor([1], dtype=torch.int32, device="cuda"), [ring(model, 16)])
     lib = _ffi.load()
-    model._kv_key = None
+    model._kv.invalidate()
     for W, keep in ((8, 8), (-1, 0)):
         rc = lib.pie_decoder_set_kv_ring(model._dec, W, keep, W, 0, 65536, _ffi.stream())
         assert rc < 0 and b"pie_decoder_set_kv_ring" in lib.pie_last_error()
