@@ -56,7 +56,8 @@ enum {
     PIE_KNOB_ATTN_WARM_MAX_MB = 8,   /* the attention launch's idle CUs warm the Infinity Cache with at most this many MB of o_proj's weights; 0 = off (read per step enqueue / graph capture) */
     PIE_KNOB_W4R = 9,                /* 0: int4 Linears of 6..256 rows on the round-2 kernels (k_w4m_gemm, k_w4l2_gemm) instead of the weight-streaming k_w4r_gemm (the tests' cross-check) */
     PIE_KNOB_FUSE_ATTN = 10,         /* 0: the step's attention as its own launch instead of behind the q|k|v launch's XCD-local seam (32 / 8 / 128 heads; bit-identical; read per step enqueue / graph capture) */
-    PIE_KNOB_COUNT = 11
+    PIE_KNOB_ATTN_MERGE_IN_LAUNCH = 11, /* 0: the fused launch leaves the split-KV partials to o_proj's merging prologue instead of finishing every query head itself (bit-identical; read where the q|k|v launch is enqueued / captured) */
+    PIE_KNOB_COUNT = 12
 };
 #define PIE_KNOB_DEFAULT (-1)
 int pie_set_knob(int knob, int value);
@@ -226,7 +227,8 @@ int pie_sample(const float *logprobs, int rows, int V, int mode, double temp, do
  *   rmsnorm+qkv GEMV+RoPE+cache append | split-KV attention | [combine] | split merge+o_proj+residual |
  *   rmsnorm+gate/up GEMV+SwiGLU | down_proj+residual ; then rmsnorm+lm_head ; log-softmax+argmax.
  * 4 per layer for models with 32 query / 8 kv heads of 128 and hidden <= 4096 (Llama-3-8B, Mistral-7B; any weight format) on a contiguous or T-page cache up to 1024 positions: the
- * attention then runs inside the q|k|v launch, behind an XCD-local seam (PIE_KNOB_FUSE_ATTN; bit-identical).
+ * attention then runs inside the q|k|v launch, behind an XCD-local seam (PIE_KNOB_FUSE_ATTN; bit-identical), which also merges its splits, so
+ * o_proj takes one attention vector (PIE_KNOB_ATTN_MERGE_IN_LAUNCH; bit-identical).
  * Position and token live in device memory so the captured hipGraph is replayable. */
 typedef struct pie_decoder pie_decoder;
 

@@ -439,16 +439,37 @@ struct AttnMergeRegs {
     float mj[MAXS], lj[MAXS];
     float4 a0[MAXS], a1[MAXS];
 };
-template <int MAXS>
+// PAST_L1: the partials were written by other workgroups of THIS launch (the fused q|k|v + attention launch merges a head once its last split
+// has arrived, w4_gemv.hpp): every read is an sc1 load served by the XCD's L2, never by a line parked in the CU's L1 (four heads share one
+// 128-byte line of part_ml, and a CU can host the mergers of several of them).
+template <bool PAST_L1>
+__device__ __forceinline__ float2 attn_part_load2(const float *p) {
+    if constexpr (PAST_L1) {
+        const unsigned long long v = __hip_atomic_load(reinterpret_cast<unsigned long long *>(const_cast<float *>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return make_float2(__builtin_bit_cast(float, (unsigned)v), __builtin_bit_cast(float, (unsigned)(v >> 32)));
+    } else {
+        return *reinterpret_cast<const float2 *>(p);
+    }
+}
+template <bool PAST_L1>
+__device__ __forceinline__ float4 attn_part_load4(const float *p) {
+    if constexpr (PAST_L1) {
+        const float2 lo = attn_part_load2<true>(p), hi = attn_part_load2<true>(p + 2);
+        return make_float4(lo.x, lo.y, hi.x, hi.y);
+    } else {
+        return *reinterpret_cast<const float4 *>(p);
+    }
+}
+template <int MAXS, bool PAST_L1 = false>
 __device__ __forceinline__ void attn_merge_load(const float *part_acc, const float *part_ml, int splits, int active, int h, int D, int d0,
                                                 AttnMergeRegs<MAXS> &r) {
 #pragma unroll
     for (int j = 0; j < MAXS; ++j) {
         const int jc = j < active ? j : active - 1;
-        const float2 ml = *reinterpret_cast<const float2 *>(part_ml + ((size_t)h * splits + jc) * 2);
+        const float2 ml = attn_part_load2<PAST_L1>(part_ml + ((size_t)h * splits + jc) * 2);
         r.mj[j] = ml.x, r.lj[j] = ml.y;
         const float *pa = part_acc + ((size_t)h * splits + jc) * D + d0;
-        r.a0[j] = *reinterpret_cast<const float4 *>(pa), r.a1[j] = *reinterpret_cast<const float4 *>(pa + 4);
+        r.a0[j] = attn_part_load4<PAST_L1>(pa), r.a1[j] = attn_part_load4<PAST_L1>(pa + 4);
     }
 }
 template <int MAXS>

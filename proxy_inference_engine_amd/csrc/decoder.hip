@@ -6,7 +6,7 @@
 // Launches per step: embed | per layer { rmsnorm+qkv+rope+append, split-KV attention, [combine: caches beyond 1024
 // positions only], merge+o_proj+residual, rmsnorm+gate/up+swiglu, down+residual } | rmsnorm+lm_head(+wave stats) | finish.
 // (The embedding rides in layer 0's q|k|v launch for int4 models; for the 32 / 8 / 128 head geometry the attention rides in every q|k|v launch,
-// behind an XCD-local seam: fuse_attn() below.)
+// behind an XCD-local seam: attn_form() below.)
 #include <atomic>
 #include <cstring>
 #include <new>
@@ -26,7 +26,8 @@ constexpr int PROF_QKV = 16, PROF_O = 20, PROF_GU = 24, PROF_DOWN = 28;
 #endif
 }
 namespace {
-int g_knobs[PIE_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+int g_knobs[PIE_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(PIE_KNOB_COUNT == 12, "one PIE_KNOB_DEFAULT per knob");
 }
 int pie_knob(int knob) { return knob >= 0 && knob < PIE_KNOB_COUNT ? g_knobs[knob] : PIE_KNOB_DEFAULT; }
 namespace pie {
@@ -117,12 +118,16 @@ static bool xcd_classes_hold() {
 // after arriving, so a launch holds at most 128 workgroup slots while it waits and the chip has 768 for this kernel: up to five such launches in flight
 // cannot starve each other's producers.  A process that holds more than four live decoders gets the two-launch form (captured graphs follow at their next step).
 static std::atomic<int> g_live_decoders{0};
-static bool fuse_attn(const pie_decoder *d, int li) {
+// Knob PIE_KNOB_ATTN_MERGE_IN_LAUNCH = 0 leaves the fused launch's partials to o_proj's merging prologue (bit-identical; the tests' cross-check and the A/B).
+// This reads process-global state (knobs, the live-decoder count), so it is asked ONCE per q|k|v launch: enqueue_kernel records the answer in
+// d->attn_form and the ATTN / OPROJ launches follow the record.
+static int attn_form(const pie_decoder *d) {
     const pie_decoder_config &c = d->cfg;
-    if (pie_knob(PIE_KNOB_FUSE_ATTN) == 0 || !d->xcd_ok || !d->seam || g_live_decoders.load() > 4) return false;
-    (void)li;  // (any weight format of the q|k|v matrix)
-    return !d->tp() && !d->combine && !(d->kv_i8 && d->block_table) && !d->kv_quant && !d->ring && c.n_heads == 32 && c.n_kv_heads == 8 && c.head_dim == 128 && c.hidden <= 4096 &&
-           d->splits >= 1 && d->splits <= 4;
+    if (pie_knob(PIE_KNOB_FUSE_ATTN) == 0 || !d->xcd_ok || !d->seam || g_live_decoders.load() > 4) return ATTN_TWO_LAUNCHES;
+    const bool fits = !d->tp() && !d->combine && !(d->kv_i8 && d->block_table) && !d->kv_quant && !d->ring && c.n_heads == 32 && c.n_kv_heads == 8 && c.head_dim == 128 && c.hidden <= 4096 &&
+                      d->splits >= 1 && d->splits <= 4;  // (any weight format of the q|k|v matrix)
+    if (!fits) return ATTN_TWO_LAUNCHES;
+    return pie_knob(PIE_KNOB_ATTN_MERGE_IN_LAUNCH) == 0 ? ATTN_FUSED : ATTN_FUSED_MERGED;
 }
 
 // What the step's attention launch is given (contiguous or T-page cache, not the int8 pages)
@@ -178,7 +183,8 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
                 a.emb_codes = (const u32 *)d->glob.embed_codes, a.emb_scales = (const u16 *)d->glob.embed_scales, a.emb_biases = (const u16 *)d->glob.embed_biases;
                 a.emb_vocab = d->embed_vocab();
             }
-            if (fuse_attn(d, li)) a.fuse = 1, a.attn = attn_args(d, li), a.seam = d->seam;  // the step's attention behind an XCD-local seam of this launch
+            d->attn_form = attn_form(d);  // the one decision of this layer's attention; PIE_K_ATTN and PIE_K_OPROJ follow it
+            if (d->attn_form != ATTN_TWO_LAUNCHES) a.fuse = 1, a.attn = attn_args(d, li), a.seam = d->seam, a.merge = d->attn_form == ATTN_FUSED_MERGED;  // the step's attention behind an XCD-local seam of this launch
             const int rc = w4s_gemv_launch(c.dtype, embed_here ? PRO_EMBED : PRO_RMSNORM, EPI_ROPE_KV, a, 1, st);
             if (rc || !i8) return rc;
             const size_t blk = (size_t)c.n_kv_heads * PIE_PAGE_TOKENS * D;
@@ -204,7 +210,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
                 a.part_acc = d->part_acc, a.part_ml = d->part_ml, a.stage = d->kv_stage;
                 return attn_decode_quant_launch(c.dtype, D, d->kvq_bits, a, d->combine, d->attn, st);  // short caches: merged by the o_proj prologue
             }
-            if (fuse_attn(d, li)) return PIE_OK;  // ran behind the q|k|v launch's seam
+            if (d->attn_form != ATTN_TWO_LAUNCHES) return PIE_OK;  // ran behind the q|k|v launch's seam
             AttnArgs a = attn_args(d, li);
             if (d->ring) a.ring_stage = d->kv_stage;  // rotating cache: the staged rows go to their ring slot inside this launch
             return attn_decode_launch(c.dtype, D, a, d->combine, st);  // short caches: partials are merged by the o_proj prologue
@@ -218,7 +224,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
             const bool push = d->tp() && tp_comm_push_args(d->comm, &a.tp_peers, &a.tp_epoch, &a.tp_stride);
             const int epi = d->tp() ? (push ? EPI_TP_PUSH : EPI_PARTIAL_F32) : EPI_RESIDUAL;
             a.y32 = d->tp_part, a.tp_rank = c.tp_rank, a.tp_world = c.tp_world;
-            const bool merged_attn = d->combine || (d->kv_i8 && d->block_table);  // the attention output is already one T vector
+            const bool merged_attn = d->combine || (d->kv_i8 && d->block_table) || d->attn_form == ATTN_FUSED_MERGED;  // the attention output is already one T vector
             if (merged_attn) a.x = d->attn;
             else a.part_acc = d->part_acc, a.part_ml = d->part_ml, a.splits = d->splits, a.state = d->state, a.head_dim = D;
             a.prof = reinterpret_cast<unsigned long long *>(d->pf_sink) + PROF_O;
@@ -353,9 +359,9 @@ int pie_decoder_create(const pie_decoder_config *cfg, pie_decoder **out) {
     PIE_ALLOC(d->stats, sizeof(LogitStat) * (size_t)d->n_stats);
     PIE_ALLOC(d->rope_cs, sizeof(float) * (size_t)c.head_dim);
     PIE_ALLOC(d->pf_sink, 8192);  // the developer builds' stamps (-DPIE_ATTN_PROF: words 2..9; -DPIE_GEMV_PROF: 16 + 4 kind ..)
-    PIE_ALLOC(d->seam, 2048);     // 8 x {counter, generation} 64 bytes apart, [256] the give-up flag
+    PIE_ALLOC(d->seam, sizeof(unsigned) * GEMV_SEAM_WORDS);  // 8 XCD counters 128 bytes apart, [256] the give-up flag, then 32 per-head counters 128 bytes apart (w4_gemv.hpp)
     d->xcd_ok = xcd_classes_hold();
-    ++g_live_decoders;
+    ++g_live_decoders, d->counted_live = true;
     if (d->tp()) PIE_ALLOC(d->tp_part, sizeof(float) * ((size_t)c.hidden + 4));  // RCCL backend: the fp32 partial; [hidden]: the step's log-sum-exp
 #undef PIE_ALLOC
     plan_attention(d);
@@ -365,7 +371,7 @@ int pie_decoder_create(const pie_decoder_config *cfg, pie_decoder **out) {
 
 int pie_decoder_destroy(pie_decoder *d) {
     if (!d) return PIE_OK;
-    if (d->seam) --g_live_decoders;  // (counted once the seam buffer exists: a create that failed earlier never was)
+    if (d->counted_live) --g_live_decoders, d->counted_live = false;  // (a create that failed before it was counted never was)
     drop_graphs(d);
     prefill_free(d);
     void *ptrs[] = {d->state, d->kv_table, d->qbuf, d->attn, d->act, d->part_acc, d->part_ml, d->stats, d->rope_cs, d->pf_sink, d->seam, d->tp_part, d->kv_stage, d->kv_table_stage,
@@ -604,9 +610,8 @@ int pie_decoder_step(pie_decoder *d, int flags, void *stream) {
     const bool with_logits = (flags & PIE_STEP_LOGITS) != 0;
     if (!(flags & PIE_STEP_GRAPH)) return enqueue_step(d, &d->state->token, with_logits, d->logits, st);
     const int gi = with_logits ? 1 : 0;
-    if (d->graph[gi] && d->graph_fused[gi] && !fuse_attn(d, 0)) drop_graphs(d);  // fusion was withdrawn (knob, more than four live decoders): capture the two-launch form
+    if (d->graph[gi] && d->graph_form[gi] > attn_form(d)) drop_graphs(d);  // the captured form was withdrawn (a knob, more than four live decoders): capture what is allowed now
     if (!d->graph[gi]) {
-        d->graph_fused[gi] = fuse_attn(d, 0);
         // captured on a private stream, launched on the caller's
         hipGraph_t g = nullptr;
         hipError_t e = hipSuccess;
@@ -618,6 +623,7 @@ int pie_decoder_step(pie_decoder *d, int flags, void *stream) {
             return erc;
         }
         if (e != hipSuccess) return pie::fail(PIE_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+        d->graph_form[gi] = d->attn_form;  // what the capture's q|k|v launches decided, not a second look at the knobs
         {  // what the graph really holds, for the benchmark's launches_per_step (not a formula)
             size_t n_nodes = 0;
             d->graph_kernels[gi] = -1;

@@ -9,6 +9,9 @@
 #include "tail.hpp"
 #include "w4_gemv.hpp"
 
+// The step's attention: its own launch | behind the q|k|v launch's seam, merged by o_proj's prologue | behind the seam and merged there
+enum { ATTN_TWO_LAUNCHES = 0, ATTN_FUSED = 1, ATTN_FUSED_MERGED = 2 };
+
 struct pie_decoder {
     pie_decoder_config cfg;
     std::vector<pie_layer_weights> layers;
@@ -27,6 +30,10 @@ struct pie_decoder {
     unsigned *pf_sink = nullptr;  // scratch for the developer builds' in-kernel stamps
     unsigned *seam = nullptr;     // the fused q|k|v + attention launch's per-XCD arrival counters / generations (w4_gemv.hpp, FUSE); zeroed once
     bool xcd_ok = false;          // the dispatcher places workgroups with equal blockIdx.x % 8 on one XCD (checked at creation)
+    bool counted_live = false;    // this decoder is in g_live_decoders (decoder.hip)
+    // How the step's attention runs (decoder.hip: attn_form).  Decided ONCE, where the q|k|v launch is enqueued; the ATTN and OPROJ launches that
+    // follow it -- in a step, a capture or by name -- read this record, never the knobs: o_proj must take the input that was really written.
+    int attn_form = ATTN_TWO_LAUNCHES;
     // caller-owned outputs (pie_decoder_bind_outputs)
     u16 *h = nullptr, *logits = nullptr;
     float *logprobs = nullptr;
@@ -68,7 +75,7 @@ struct pie_decoder {
     DecState *ring_rows = nullptr;
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
-    bool graph_fused[2] = {false, false};           // the captured graph holds the fused q|k|v + attention launch (re-captured when fusion is withdrawn)
+    int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)
     struct PrefillScratch *prefill = nullptr;       // batched prompt processing (prefill.hip), allocated on first use
     // tensor parallelism (cfg.tp_world > 1): this decoder is one rank's shard; comm is caller-owned (pie_decoder_set_comm)
     pie_comm *comm = nullptr;

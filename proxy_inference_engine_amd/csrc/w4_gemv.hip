@@ -448,6 +448,7 @@ int w4s_gemv_launch(int dtype, int pro, int epi, GemvArgs &a, int M, hipStream_t
                         a.attn.splits >= 1 && a.attn.splits <= 4 && a.attn.Hq == 32 && a.attn.Hkv == 8 && a.attn.part_acc && a.attn.part_ml && a.attn.q,
                     PIE_E_SHAPE, "w4s_gemv: the fused attention is built for 32 query heads and 8 kv heads of 128 (kv-group = XCD)");
         PIE_REQUIRE(a.K <= 8 * GEMV_WAVES * 64, PIE_E_SHAPE, "w4s_gemv: the fused attention takes hidden sizes up to 4096");
+        PIE_REQUIRE(!a.merge || a.attn.out, PIE_E_ARG, "w4s_gemv: the fused attention merges its heads into a null vector");
 #define PIE_FUSE_GO(TT, PRO_, FMT_) hipLaunchKernelGGL((k_w4s_gemv<TT, PRO_, EPI_ROPE_KV, 1, 0, FMT_, 1>), grid, dim3(GEMV_WAVES * 64), lds, stream, a)
 #define PIE_FUSE_FMT(TT)                                                  \
     if (pro == PRO_EMBED) PIE_FUSE_GO(TT, PRO_EMBED, FMT_W4S);            \

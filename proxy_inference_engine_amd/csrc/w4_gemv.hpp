@@ -99,8 +99,12 @@ struct GemvArgs {
     // FUSE (EPI_ROPE_KV, the 32 / 8 / 128 head geometry): the step's attention runs behind an XCD-local seam of this launch
     int fuse;             // launcher: take the FUSE instantiation
     AttnArgs attn;        // what k_attn_decode would be launched with
-    unsigned *seam;       // per XCD class c: a monotonic arrival counter at [32 c] (+32 per launch); [256]: a spin gave up (never, unless CUs are masked)
+    unsigned *seam;       // per XCD class c: a monotonic arrival counter at [32 c] (+32 per launch); [256]: a spin gave up (never, unless CUs are masked);
+                          // per query head h: a monotonic arrival counter of its splits at [GEMV_SEAM_HEADS + 32 h] (+4 per launch), a cache line each
+    int merge;            // FUSE: the last split of a query head to arrive merges the head's partials into attn.out (o_proj then takes it as PRO_NONE)
 };
+constexpr int GEMV_SEAM_HEADS = 512;                               // word offset of the per-head counters in GemvArgs::seam
+constexpr int GEMV_SEAM_WORDS = GEMV_SEAM_HEADS + 32 * 32;         // 32 query heads (the FUSE geometry)
 
 // out[0..8) = T(scale * q + bias) of one code word: separate multiply and add roundings, like the oracle (mx.dequantize)
 template <class T>
@@ -768,6 +772,33 @@ __global__ void __launch_bounds__(GEMV_WAVES * 64, 4) k_w4s_gemv(const GemvArgs 
             // (The K / V prefetch goes out before the wait; issued ahead of the weight stream it delayed the GEMV: 1.174 -> 1.195 ms.)
             if (a.attn.block_table) attn_decode_body<T, 128, 1, true, false, 4>(a.attn, c, ja >> 2, 0, 4 * c + (ja & 3), seam_wait);  // T pages (uniform)
             else attn_decode_body<T, 128, 1, false, false, 4>(a.attn, c, ja >> 2, 0, 4 * c + (ja & 3), seam_wait);
+            if (a.merge) {
+                // The second hand-off, per query head: its splits' workgroups sit on this XCD too, so the head is finished HERE, once, instead of by
+                // each of o_proj's 256 workgroups (PRO_ATTN: 80 KB of partials through the fabric per workgroup to stage 8 KB).  Same rules as the
+                // seam above: the partial (or an idle split's neutral one) is acknowledged by the L2 before the arrival, the arrival is an atomic
+                // performed at that L2, and the merger reads the partials with sc1 loads.  Nobody waits: the arrival returns the count, and the
+                // workgroup that completes the head merges it.  The counter only grows, by 4 per launch whatever the split count (split 0 adds
+                // 5 - splits, the others 1), so it needs no re-arming between graph replays and wraps cleanly.
+                const int h = 4 * c + (ja & 3), split = ja >> 2;
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+                __syncthreads();
+                if (wave == 0) {
+                    unsigned arrived = 0;
+                    if (lane == 0) {
+                        const unsigned inc = split == 0 ? 5u - (unsigned)a.attn.splits : 1u;
+                        arrived = __hip_atomic_fetch_add(a.seam + GEMV_SEAM_HEADS + 32 * h, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + inc;
+                    }
+                    arrived = __builtin_amdgcn_readfirstlane(arrived);
+                    if ((arrived & 3u) == 0 && lane < 16) {  // the head's last arrival: the prologue's merge (all slots, split order, pack2 rounding), 8 dims per lane
+                        AttnMergeRegs<GEMV_ATTN_SPLITS> mr;
+                        float o[8];
+                        attn_merge_load<GEMV_ATTN_SPLITS, true>(a.attn.part_acc, a.attn.part_ml, a.attn.splits, a.attn.splits, h, 128, lane * 8, mr);
+                        attn_merge_finish<GEMV_ATTN_SPLITS>(mr, a.attn.splits, o);
+                        *reinterpret_cast<uint4 *>(a.attn.out + (size_t)h * 128 + lane * 8) =
+                            make_uint4(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]), pack2<T>(o[4], o[5]), pack2<T>(o[6], o[7]));
+                    }
+                }
+            }
         } else if (a.attn.pf_rows > 0) {  // Infinity-Cache warm-up of o_proj (attention.hpp: AttnArgs::pf_ptr)
             const unsigned nblk = 8u * (32u - (unsigned)n_attn), bid = (unsigned)c * (32u - (unsigned)n_attn) + (unsigned)j;
             unsigned acc = 0;
