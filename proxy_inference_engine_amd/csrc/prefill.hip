@@ -18,7 +18,7 @@
 #include <mutex>
 
 #include "decoder.hpp"
-#include "prefill_attn.hpp"
+#include "gemm_rows.hpp"  // the many-row GEMM family of w4m_gemm.hip: W4mRope, W4lSlabs, the int4 entry (prefill_attn.hpp comes with it)
 
 // ---------------------------------------------------------------- kernels
 // W4S -> T row-major [N, K]; one thread per code word (8 weights, 16 B out).  Same arithmetic as k_dequantize_w4g64.
@@ -115,14 +115,6 @@ __global__ void k_rope_cs_rows(const float *freqs, const DecState *state, const 
     }
 }
 
-// A K-split many-row GEMM (w4m_gemm.hip) leaves S fp32 partial slabs [S][M][N]; its consumer can form the Linear's output itself --
-// the slabs summed in slab order, then the one rounding to T: exactly k_w4l_reduce's arithmetic -- which saves that launch and the
-// round trip of y through memory (prompts of 33..~700 rows split K; a launch is ~5 us of a 150-300 us layer there).
-struct W4lSlabs {
-    const float *part = nullptr;
-    int S = 0;
-    size_t MN = 0;
-};
 #ifndef SLAB_BATCH
 #define SLAB_BATCH 4
 #endif
@@ -338,7 +330,7 @@ __global__ void __launch_bounds__(256) k_add_rms_norm_rows(u16 *x, const u16 *r,
 template <class T>
 static int add_rms_norm_rows(u16 *x, const u16 *r, const void *w, float eps, int M, int H, int dtype, u16 *xn, hipStream_t st,
                              const void *bias = nullptr, const W4lSlabs *sl = nullptr) {
-    if (sl && sl->S > 1) {  // (linear_rows only hands out slabs for H <= 8192)
+    if (sl && sl->S > 1) {  // (mlp_rows only offers to take slabs for H <= 8192)
         hipLaunchKernelGGL(k_add_rms_norm_rows<T>, dim3(M), dim3(256), 0, st, x, r, (const u16 *)w, eps, H, xn, (const u16 *)bias, sl->part, sl->S,
                            sl->MN);
         PIE_LAUNCH_CHECK();
@@ -368,7 +360,7 @@ struct PrefillScratch {
     // 4.6 B per parameter (7 ms of a 10.8 ms 128-token prefill on the 8B model) for 2 B per parameter of HBM; kept when
     // that is a small share of the free memory (PIE_KNOB_PREFILL_RESIDENT overrides), built on first use.
     std::map<const void *, u16 *> resident;
-    // W4M tile copies (w4m_gemm.hip) of int4 layer matrices for prompts of at most small_rows() rows: 0.5625 B per weight each
+    // W4M tile copies (w4m_gemm.hip) of int4 matrices, the operand of every many-row int4 GEMM: 0.5625 B per weight each
     std::map<const void *, void *> resident_w4m;
     LogitStat *tail_stats = nullptr;  // multi-sequence step / several prompts per pass: per-row tail partials
     size_t tail_entries = 0;           // its capacity in ENTRIES (rows x partials per row: the two users need 256 and max(lm_head waves, 256) per row)
@@ -495,14 +487,6 @@ static size_t resident_budget(pie_decoder *d) {
     return s->resident_left;
 }
 
-// w16_gemm.hpp / w4m_gemm.hip: the 16-bit many-row MFMA GEMM on W16M tiles (weights in MFMA A-fragment order)
-size_t w16m_size(int N, int K);
-int w16m_from_rows_launch(const void *w, int N, int K, void *w16m, hipStream_t st);
-int w16m_from_w16s_launch(const void *w16s, int N, int K, void *w16m, hipStream_t st);
-size_t w16l_workspace_bytes(int M, int N, int K);
-int w16l_gemm_launch(int dtype, const void *w16m, const void *x, int ldx, int M, int N, int K, void *y, void *workspace, hipStream_t st, const void *bias,
-                     void *swiglu_act, bool *fused, int ldy);
-
 // The 16-bit operand of a many-row product, as W16M tiles: dense modules straight from their W16S units, int8 / group-32 modules
 // dequantised (mx.dequantize's arithmetic: the qmm regime multiplies T copies) into the row-major staging buffer and tiled from there.
 template <class T>
@@ -519,47 +503,6 @@ static int expand_weights(pie_decoder *d, const void *packed, int N, int K, void
     return w16m_from_rows_launch(staging, N, K, w16m, st);
 }
 
-// y[M, N] = x[M, K] . W^T for one streaming-layout matrix.  keep: a layer matrix (eligible for the resident copy); the
-// lm_head of a logits-on-every-position call always goes through the scratch.
-// w4m_gemm.hip: the few-row int4 GEMM on W4M tiles
-size_t w4m_bytes(int N, int K);
-int w4m_repack_launch(const void *w4s, int N, int K, void *w4m, hipStream_t st);
-struct W4mRope {  // q|k|v epilogue arguments (defined identically in w4m_gemm.hip)
-    const float *rope_cs;
-    const DecState *state;
-    const int *ctx_len;
-    const unsigned long long *kv_table;
-    u16 *slab;
-    const int *block_table;
-    int bt_stride, n_pages, layer, n_layers, n_heads, n_kv_heads, HD, traditional;
-    u16 *q_out;
-    const u16 *bias;
-    size_t i8_page_bytes;  // != 0 (with slab): int8 pages with per-head scales (paged_i8.hip)
-};
-int w4m_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, hipStream_t st, int swiglu, const void *bias, const W4mRope *rope);
-int w4l_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, void *workspace, hipStream_t st, void *swiglu_act, bool *fused,
-                    int *slabs);  // many rows (MFMA-bound)
-size_t w4l_workspace_bytes(int M, int N, int K);
-// 6 .. 256 rows: the weight-streaming form (w4r_gemm.hpp); epi 0 store (+ bias), 1 SwiGLU (+ bias), 2 RoPE + append
-bool w4r_serves(int M, int N, int K);
-int w4r_splits(int M, int N, int K);
-size_t w4r_workspace_bytes(int M, int N, int K);
-bool w4m_wide_scales(const void *w4m);
-int w4r_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, void *workspace, hipStream_t st, int epi, const void *bias,
-                    const W4mRope *rope, int *slabs, bool *bias_done, bool wide_scales);
-
-// int4 checkpoints: prompts beyond small_rows() rows run the hand-written many-row W4 MFMA GEMM on the same W4M tiles -- no 16-bit
-// copy of the weights, except for shapes the tile kernels do not take (N not a multiple of 32), which multiply a W16M copy on k_w16l_gemm.
-// Dense (16-bit), int8 and group-32 modules multiply their W16M copy on k_w16l_gemm (w16_gemm.hpp): the hand-written 16-bit MFMA GEMM of
-// round 5, which replaced the library GEMM (EXPERIMENTS.md).
-// Rows up to which an int4 Linear that k_w4r_gemm does not take runs on the few-row W4M kernel instead of the many-row tile kernel
-// (PIE_KNOB_SMALL_M: 0 disables, max 32).
-static int small_rows() {
-    const int k = pie_knob(PIE_KNOB_SMALL_M);
-    const int v = k >= 0 ? k : 32;
-    return v < 0 ? 0 : (v > 32 ? 32 : v);
-}
-
 template <class T>
 static int bias_rows(u16 *y, const void *bias, int M, int N, hipStream_t st) {
     const size_t n8 = (size_t)M * N / 8;
@@ -568,21 +511,34 @@ static int bias_rows(u16 *y, const void *bias, int M, int N, hipStream_t st) {
     return PIE_OK;
 }
 
+// What a many-row Linear is asked for beyond y = x . W^T, and what it did about it
+struct RowsOpts {
+    const void *bias = nullptr;  // the Linear's
+    bool keep = true;            // a layer matrix (eligible for a resident copy); the lm_head of a logits-on-every-position call goes through the scratch
+    bool keep_w4m = false;       // ... unless this says that its int4 tiles may stay (the lm_head of the multi-sequence passes)
+    u16 *act = nullptr;          // the packed gate|up matrix: the GEMM may apply the SwiGLU itself and write act [M, N / 2] instead of y (RowsDone::fused_swiglu)
+    W4mRope *rope = nullptr;     // the packed q|k|v matrix: the GEMM may rotate q / k and append k / v itself instead of writing y (RowsDone::roped)
+    bool slabs = false;          // the caller's consumer takes the fp32 slabs of a K-split GEMM (and the bias) instead of y (RowsDone::slabs.S > 1 tells whether it must)
+};
+struct RowsDone {
+    bool fused_swiglu = false, roped = false;
+    W4lSlabs slabs;
+};
+
+// y[M, N] = x[M, K] . W^T (+ bias) for one streaming-layout matrix, by weight format and row count:
+//   * up to GEMV_ROWS_MAX rows (MLX's qmv regime) the streaming GEMVs, where the format and shape have one;
+//   * int4 g=64 matrices on their resident W4M tiles through the one int4 entry (w4_rows_launch, w4m_gemm.hip: k_w4r_gemm up to 256 rows, the tile kernels
+//     beyond) -- no 16-bit copy of the weights;
+//   * everything else -- dense, int8 and group-32 modules, int4 shapes the tiles do not take (N not a multiple of 32) or that the residency budget has no
+//     room for -- multiplies a W16M copy on k_w16l_gemm (w16_gemm.hpp).
 template <class T>
-static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u16 *x, int M, u16 *y, hipStream_t st, bool keep = true,
-                       const void *bias = nullptr, bool keep_w4m = false, u16 *act = nullptr, bool *used_act = nullptr, W4mRope *rope = nullptr,
-                       W4lSlabs *slabs = nullptr) {
-    // slabs: the caller's consumer takes the fp32 slabs of a K-split many-row GEMM (and the bias) instead of y; slabs->S > 1 tells whether it must
-    // rope / used_act: for the packed q|k|v matrix the few-row kernel can rotate q / k and append k / v itself
-    // act / used_act: for the packed gate|up matrix the few-row kernel can apply the SwiGLU itself and write act [M, N / 2]
+static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u16 *x, int M, u16 *y, hipStream_t st, const RowsOpts &o = RowsOpts(),
+                       RowsDone *done = nullptr) {
     PrefillScratch *s = d->prefill;
-    if (used_act) *used_act = false;
-    if (slabs) *slabs = W4lSlabs();
-    if (pie_knob(PIE_KNOB_W4L_SLABS) == 0) slabs = nullptr;  // always reduce in the GEMM's own launch (the bit-equality test)
-    // 8B prompt of 64 / 128 / 256 / 512 / 700 tokens, slabs summed by the consumers vs reduce launches: 3.70 / 4.56 / 6.13 / 9.56 / 14.26 ms
-    // vs 3.96 / 4.82 / 6.20 / 9.75 / 14.38.  (With ONE workgroup per row the RoPE consumer could not keep enough slab loads in flight
-    // below ~200 rows -- 4.21 ms at 64 tokens -- so few rows get four workgroups each there; that split applies to the RoPE consumer, not to the
-    // add + RMSNorm consumers, whose row-wide reduction keeps them at one workgroup per row.)
+    RowsDone none;
+    if (!done) done = &none;
+    *done = RowsDone();
+    const void *bias = o.bias;
     const int wf = d->mat_fmt(packed);
     const bool is_int4 = wf == PIE_W_INT4_G64;
     if ((wf == PIE_W_INT4_G32 || wf == PIE_W_INT8_G32 || wf == PIE_W_INT2_G64 || wf == PIE_W_INT6_G64) && M <= GEMV_ROWS_MAX && K <= 32768 && N % 2 == 0) {  // group-32 / 2- / 6-bit codes, qmv regime: the streaming GEMV, one pass per row
@@ -594,23 +550,6 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
     // streaming GEMV with the rows' images side by side -- one pass over the weights, each row with the batch-1 arithmetic.
     if (is_int4 && M <= GEMV_ROWS_MAX && K % 64 == 0 && N % 2 == 0 && gemv_rows_lds_bytes(K, 1) <= 160u * 1024u)
         return w4s_gemv_rows_launch(d->cfg.dtype, packed, N, K, x, M, y, (const u16 *)bias, st);
-    // resident W4M tile copy of an int4 matrix (0.5625 B per weight, built on first use within the residency budget); nullptr: no room
-    auto w4m_tiles = [&](void **out) -> int {
-        *out = nullptr;
-        auto it = s->resident_w4m.find(packed);
-        if (it != s->resident_w4m.end()) {
-            *out = it->second;
-            return PIE_OK;
-        }
-        void *wm = nullptr;
-        if (resident_budget(d) >= w4m_bytes(N, K) && hipMalloc(&wm, w4m_bytes(N, K)) == hipSuccess) {
-            s->resident_w4m[packed] = wm, s->resident_left -= w4m_bytes(N, K), ++s->alloc_gen;
-            *out = wm;
-            return w4m_repack_launch(packed, N, K, wm, st);
-        }
-        (void)hipGetLastError();
-        return PIE_OK;
-    };
     auto w4l_reserve = [&](size_t wb) -> int {  // fp32 slabs of a K-split product
         if (wb > s->w4l_ws_bytes) {
             if (s->w4l_ws) (void)hipFree(s->w4l_ws);
@@ -620,73 +559,31 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
         }
         return PIE_OK;
     };
-    // 6 .. 256 rows (a chat turn behind a cached prefix, a prompt chunk, a multi-sequence step): the weight-streaming MFMA GEMM, every CU
-    // streaming its slab of W4M tiles once (w4r_gemm.hpp).  q|k|v, o_proj and down split K over workgroups and hand fp32 slabs to their
-    // consumers (RoPE + append, add + RMSNorm); gate|up carries the SwiGLU in its epilogue.
-    if (is_int4 && w4r_serves(M, N, K)) {
+    int rc = PIE_OK;
+    if (is_int4 && N % 32 == 0 && K % 64 == 0) {  // every shape the W4M tiles take: get tiles, reserve, enter, add the bias if it is still ours
+        // resident W4M tile copy (0.5625 B per weight, built on first use within the residency budget); none: no room, the W16M path below
         void *wm = nullptr;
-        int rc = w4m_tiles(&wm);
-        if (rc) return rc;
+        auto it = s->resident_w4m.find(packed);
+        if (it != s->resident_w4m.end()) wm = it->second;
+        else if (resident_budget(d) >= w4m_bytes(N, K) && hipMalloc(&wm, w4m_bytes(N, K)) == hipSuccess) {
+            s->resident_w4m[packed] = wm, s->resident_left -= w4m_bytes(N, K), ++s->alloc_gen;
+            if ((rc = w4m_repack_launch(packed, N, K, wm, st))) return rc;
+        } else (void)hipGetLastError(), wm = nullptr;
         if (wm) {
-            const bool wide = w4m_wide_scales(wm);
-            if (act && used_act) {  // gate|up: SwiGLU (and the Linear's bias) in the epilogue
-                *used_act = true;
-                return w4r_gemm_launch(d->cfg.dtype, wm, x, M, N, K, act, nullptr, st, 1, bias, nullptr, nullptr, nullptr, wide);
-            }
-            if (rope && used_act && w4r_splits(M, N, K) == 1) {  // q|k|v wide enough to fill the chip without a K split: RoPE + append in the epilogue
-                *used_act = true;
-                rope->bias = (const u16 *)bias;
-                return w4r_gemm_launch(d->cfg.dtype, wm, x, M, N, K, nullptr, nullptr, st, 2, nullptr, rope, nullptr, nullptr, wide);
-            }
-            if ((rc = w4l_reserve(w4r_workspace_bytes(M, N, K)))) return rc;
-            int n_slabs = 0;
-            bool bias_done = false;
-            rc = w4r_gemm_launch(d->cfg.dtype, wm, x, M, N, K, y, s->w4l_ws, st, 0, bias, nullptr, slabs ? &n_slabs : nullptr, &bias_done, wide);
-            if (!rc && n_slabs > 1) {  // y was NOT written: the consumer sums the slabs, rounds and adds the bias
-                slabs->part = (const float *)s->w4l_ws, slabs->S = n_slabs, slabs->MN = (size_t)M * N;
-                return PIE_OK;
-            }
-            if (rc || !bias || bias_done) return rc;
-            return bias_rows<T>(y, bias, M, N, st);
-        }
-    }
-    // Up to 32 rows of a shape k_w4r_gemm does not take (K < 256) -- or all of them with knob PIE_KNOB_W4R = 0, the tests' comparator: round 2's
-    // first few-row kernel, one workgroup per 32-column strip
-    if ((keep || keep_w4m) && is_int4 && M <= small_rows() && N % 32 == 0 && K % 64 == 0) {
-        void *wm = nullptr;
-        int rc = w4m_tiles(&wm);
-        if (rc) return rc;
-        if (wm) {
-            if (rope && used_act) {
-                *used_act = true;
-                rope->bias = (const u16 *)bias;
-                return w4m_gemm_launch(d->cfg.dtype, wm, x, M, N, K, nullptr, st, 2, nullptr, rope);
-            }
-            if (act && used_act) {
-                *used_act = true;
-                return w4m_gemm_launch(d->cfg.dtype, wm, x, M, N, K, act, st, 1, bias, nullptr);
-            }
-            rc = w4m_gemm_launch(d->cfg.dtype, wm, x, M, N, K, y, st, 0, nullptr, nullptr);
-            if (rc || !bias) return rc;
-            return bias_rows<T>(y, bias, M, N, st);
-        }
-    }
-    if (is_int4 && N % 32 == 0 && K % 64 == 0) {  // beyond 256 rows: the many-row tile kernels
-        void *wm = nullptr;
-        int rc = w4m_tiles(&wm);
-        if (rc) return rc;
-        if (wm) {
-            if ((rc = w4l_reserve(w4l_workspace_bytes(M, N, K)))) return rc;  // fp32 partial tiles of a K-split shape (medium prompts)
-            bool fused = false;  // gate|up without a Linear bias: the SwiGLU rides in the GEMM's epilogue where the shape allows
-            int n_slabs = 0;
-            rc = w4l_gemm_launch(d->cfg.dtype, wm, x, M, N, K, y, s->w4l_ws, st, (act && used_act && !bias) ? act : nullptr, &fused, slabs ? &n_slabs : nullptr);
-            if (fused) *used_act = true;
-            if (!rc && n_slabs > 1) {  // y was NOT written: the consumer sums the slabs, rounds and adds the bias
-                slabs->part = (const float *)s->w4l_ws, slabs->S = n_slabs, slabs->MN = (size_t)M * N;
-                return PIE_OK;
-            }
-            if (rc || !bias) return rc;
-            return bias_rows<T>(y, bias, M, N, st);
+            W4Rows q = {d->cfg.dtype, wm, x, M, N, K, y};
+            q.bias = bias, q.wish = o.act ? W4R_SWIGLU : o.rope ? W4R_ROPE : W4R_STORE, q.act = o.act, q.rope = o.rope;
+            // 8B prompt of 64 / 128 / 256 / 512 / 700 tokens, slabs summed by the consumers vs reduce launches: 3.70 / 4.56 / 6.13 / 9.56 / 14.26 ms
+            // vs 3.96 / 4.82 / 6.20 / 9.75 / 14.38.  (With ONE workgroup per row the RoPE consumer could not keep enough slab loads in flight
+            // below ~200 rows -- 4.21 ms at 64 tokens -- so few rows get four workgroups each there; that split applies to the RoPE consumer, not to the
+            // add + RMSNorm consumers, whose row-wide reduction keeps them at one workgroup per row.)
+            q.take_slabs = o.slabs, q.few_rows = o.keep || o.keep_w4m;
+            if ((rc = w4l_reserve(w4_rows_workspace_bytes(q)))) return rc;
+            W4Outcome out;
+            if ((rc = w4_rows_launch(q, s->w4l_ws, st, &out))) return rc;
+            done->fused_swiglu = out.epi == W4R_SWIGLU, done->roped = out.epi == W4R_ROPE;
+            if (out.slabs > 1) done->slabs.part = (const float *)s->w4l_ws, done->slabs.S = out.slabs, done->slabs.MN = (size_t)M * N;
+            else if (bias && !out.bias_done) return bias_rows<T>(y, bias, M, N, st);
+            return PIE_OK;
         }
     }
     // Everything else -- dense modules, int8 and group-32 modules beyond the GEMV's rows -- multiplies a 16-bit copy of the matrix in W16M
@@ -694,7 +591,7 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
     PIE_REQUIRE(K % 64 == 0, PIE_E_SHAPE, "prefill: a many-row Linear needs in_features % 64 == 0 (pie_set_knob(PIE_KNOB_PREFILL_MIN, 1000000) processes prompts as iterated decode steps)");
     u16 *wM = s->wM;
     bool ready = false;
-    if (keep) {
+    if (o.keep) {
         const size_t bytes = w16m_size(N, K);
         auto it = s->resident.find(packed);
         if (it != s->resident.end()) wM = it->second, ready = true;
@@ -703,13 +600,10 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
             else (void)hipGetLastError(), wM = s->wM, s->resident_left = 0;  // out of memory: scratch from here on
         }
     }
-    int rc = PIE_OK;
     if (!ready && (rc = expand_weights<T>(d, packed, N, K, wM, s->wT, st))) return rc;
     if ((rc = w4l_reserve(w16l_workspace_bytes(M, N, K)))) return rc;  // fp32 slabs of a K-split shape (few rows, narrow matrices)
-    bool fused = false;  // gate|up: bias and SwiGLU in the GEMM's epilogue where the shape does not split K
-    rc = w16l_gemm_launch(d->cfg.dtype, wM, x, 0, M, N, K, y, s->w4l_ws, st, bias, (act && used_act) ? act : nullptr, &fused, 0);
-    if (fused) *used_act = true;
-    return rc;
+    // gate|up: bias and SwiGLU in the GEMM's epilogue where the shape does not split K
+    return w16l_gemm_launch(d->cfg.dtype, wM, x, 0, M, N, K, y, s->w4l_ws, st, bias, o.act, &done->fused_swiglu, 0);
 }
 
 // ---------------------------------------------------------------- what the many-row passes share
@@ -746,26 +640,28 @@ static int mlp_rows(pie_decoder *d, const pie_layer_weights &w, int M, const voi
     const pie_decoder_config &c = d->cfg;
     const int H = c.hidden, QD = c.n_heads * c.head_dim, I = c.inter;
     PrefillScratch *s = d->prefill;
-    W4lSlabs so, sd;  // o_proj / down handed to their consumers as K-split fp32 slabs where the shape qualifies
+    RowsDone o_done, gu_done, down_done;
     int rc;
-    if ((rc = linear_rows<T>(d, w.wo, H, QD, s->attn, M, s->r, st, true, w.bo, false, nullptr, nullptr, nullptr, H <= 8192 ? &so : nullptr)))
-        return rc;
+    RowsOpts o_opts;  // o_proj / down handed to their consumers as K-split fp32 slabs where the shape qualifies
+    o_opts.bias = w.bo, o_opts.slabs = H <= 8192;
+    if ((rc = linear_rows<T>(d, w.wo, H, QD, s->attn, M, s->r, st, o_opts, &o_done))) return rc;
     // h = x + r (language.py:151) + post_attention_layernorm(h) for MLP.__call__ (language.py:126-127)
-    if ((rc = add_rms_norm_rows<T>(s->x, s->r, w.mlp_norm, c.rms_eps, M, H, c.dtype, s->xn, st, so.S > 1 ? w.bo : nullptr, &so)))
+    if ((rc = add_rms_norm_rows<T>(s->x, s->r, w.mlp_norm, c.rms_eps, M, H, c.dtype, s->xn, st, o_done.slabs.S > 1 ? w.bo : nullptr, &o_done.slabs)))
         return rc;
-    bool fused_act = false;
-    if ((rc = linear_rows<T>(d, w.wgateup, 2 * I, H, s->xn, M, s->gu, st, true, w.bgateup, false, s->act, &fused_act))) return rc;
-    if (!fused_act) {
+    RowsOpts gu_opts;
+    gu_opts.bias = w.bgateup, gu_opts.act = s->act;
+    if ((rc = linear_rows<T>(d, w.wgateup, 2 * I, H, s->xn, M, s->gu, st, gu_opts, &gu_done))) return rc;
+    if (!gu_done.fused_swiglu) {
         const size_t n_act = (size_t)M * I;
         hipLaunchKernelGGL(k_swiglu_rows<T>, dim3((unsigned)((n_act / 4 + 255) / 256)), dim3(256), 0, st, s->gu, n_act, s->act);
         PIE_LAUNCH_CHECK();
     }
-    if ((rc = linear_rows<T>(d, w.wdown, H, I, s->act, M, s->r, st, true, w.bdown, false, nullptr, nullptr, nullptr,
-                             next_norm && H <= 8192 ? &sd : nullptr)))
-        return rc;
+    RowsOpts down_opts;
+    down_opts.bias = w.bdown, down_opts.slabs = next_norm && H <= 8192;
+    if ((rc = linear_rows<T>(d, w.wdown, H, I, s->act, M, s->r, st, down_opts, &down_done))) return rc;
     // out = h + r (language.py:153), fused with the norm that follows when there is one
     if (!next_norm) return pie_add(s->x, s->r, (size_t)M * H, c.dtype, s->x, st);
-    return add_rms_norm_rows<T>(s->x, s->r, next_norm, c.rms_eps, M, H, c.dtype, s->xn, st, sd.S > 1 ? w.bdown : nullptr, &sd);
+    return add_rms_norm_rows<T>(s->x, s->r, next_norm, c.rms_eps, M, H, c.dtype, s->xn, st, down_done.slabs.S > 1 ? w.bdown : nullptr, &down_done.slabs);
 }
 
 // Quantized KV (pie_decoder_set_kv_quant): the T scratch of one layer's K and V at the cache's capacity and the table that points every layer at it.
@@ -832,11 +728,12 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
                 return rc;
             W4mRope re = {s->rope_cs, kvs, nullptr, kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
                           c.rope_traditional, s->q, nullptr, 0};
-            bool roped = false;
-            W4lSlabs sq;  // q|k|v as the fp32 slabs of a K-split product (no Linear bias: RoPE takes T(x W^T + b))
-            if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, M, s->qkv, st, true, w.bqkv, false, nullptr, &roped, &re, w.bqkv ? nullptr : &sq)))
-                return rc;
-            if (!roped) {
+            RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
+            qkv_opts.bias = w.bqkv, qkv_opts.rope = &re, qkv_opts.slabs = !w.bqkv;
+            RowsDone qkv_done;
+            if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, M, s->qkv, st, qkv_opts, &qkv_done))) return rc;
+            const W4lSlabs &sq = qkv_done.slabs;
+            if (!qkv_done.roped) {
                 const unsigned row_wgs = sq.S > 1 ? (M < 512 ? 4u : 1u) : 1u;  // few rows of slabs: four workgroups per row (256 tokens: 6.03 vs 6.20 ms; from 512 rows no difference)
                 const auto rope_k = rope_append_kernel<T>(sq.S > 1, false);
                 hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, kvs, kv_table, li,
@@ -865,7 +762,9 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
         }
         if (logits_all) {  // lm_head on every position, like the reference (language.py:205-209)
             if ((rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
-            if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, false))) return rc;
+            RowsOpts head_opts;
+            head_opts.keep = false;  // the lm_head on every position: through the scratch
+            if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, head_opts))) return rc;
         }
         const bool last = c0 + M >= L;
         if (last)  // the last position continues through the decode step's lm_head + tail below
@@ -1006,11 +905,12 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         const size_t i8pb = d->kv_i8 ? pie_page_i8_bytes(c.n_kv_heads, D) : 0;  // int8 pages: the append (epilogue or row kernel) quantises
         W4mRope re = {s->rope_cs, nullptr, ctx_len, nullptr, (u16 *)slabs[li], block_tables, max_blocks, n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads,
                       D, c.rope_traditional, s->q, nullptr, i8pb};
-        bool roped = false;
-        W4lSlabs sq;  // q|k|v as the fp32 slabs of a K-split product (no Linear bias: RoPE takes T(x W^T + b))
-        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, B, s->qkv, st, true, w.bqkv, false, nullptr, &roped, &re, w.bqkv ? nullptr : &sq)))
-            return rc;
-        if (!roped) {
+        RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
+        qkv_opts.bias = w.bqkv, qkv_opts.rope = &re, qkv_opts.slabs = !w.bqkv;
+        RowsDone qkv_done;
+        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, B, s->qkv, st, qkv_opts, &qkv_done))) return rc;
+        const W4lSlabs &sq = qkv_done.slabs;
+        if (!qkv_done.roped) {
             const auto rope_k = rope_append_kernel<T>(sq.S > 1, d->kv_i8);
             hipLaunchKernelGGL(rope_k, dim3(B, sq.S > 1 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers,
                                c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, ctx_len, max_blocks, (u16 *)slabs[li],
@@ -1025,7 +925,9 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         if ((rc = d->kv_i8 ? paged_attn_i8_launch(c.dtype, D, a, st) : attn_decode_launch(c.dtype, D, a, true, st))) return rc;
         if ((rc = mlp_rows<T>(d, w, B, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
     }
-    if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, B, logits, st, false, nullptr, true))) return rc;
+    RowsOpts head_opts;
+    head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
+    if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, B, logits, st, head_opts))) return rc;
     return logits_tail_rows_launch(c.dtype, logits, c.vocab, B, s->tail_stats, logprobs, next_tokens, st);
 }
 
@@ -1061,9 +963,11 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
     for (int li = 0; li < c.n_layers; ++li) {
         const pie_layer_weights &w = d->layers[li];
         if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, N, H, c.dtype, s->xn, st))) return rc;
-        W4lSlabs sq;  // q|k|v as the fp32 slabs of a K-split product (no Linear bias: RoPE takes T(x W^T + b))
-        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, N, s->qkv, st, true, w.bqkv, false, nullptr, nullptr, nullptr, w.bqkv ? nullptr : &sq)))
-            return rc;
+        RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
+        qkv_opts.bias = w.bqkv, qkv_opts.slabs = !w.bqkv;
+        RowsDone qkv_done;
+        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, N, s->qkv, st, qkv_opts, &qkv_done))) return rc;
+        const W4lSlabs &sq = qkv_done.slabs;
         const auto rope_k = rope_append_kernel<T>(sq.S > 1, d->kv_i8);
         hipLaunchKernelGGL(rope_k, dim3(N, sq.S > 1 && N < 512 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers,
                            c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, row_ctx, max_blocks, (u16 *)slabs[li],
@@ -1096,7 +1000,9 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
     // the normalised last row of every prompt -> lm_head -> tail
     hipLaunchKernelGGL(k_gather_rows, dim3(S), dim3(256), 0, st, (const uint4 *)s->xn, last_rows, H / 8, (uint4 *)s->r);
     PIE_LAUNCH_CHECK();
-    if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->r, S, logits, st, false, nullptr, true))) return rc;
+    RowsOpts head_opts;
+    head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
+    if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->r, S, logits, st, head_opts))) return rc;
     return logits_tail_rows_launch(c.dtype, logits, c.vocab, S, s->tail_stats, logprobs, next_tokens, st);
 }
 

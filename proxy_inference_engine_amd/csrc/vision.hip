@@ -5,14 +5,7 @@
 // kernel wants, block-diagonal non-causal attention on the MFMA units (prefill_attn.hpp, SEG instantiation: full-image and
 // 64-patch-window layers are the same kernel with different segment tables), bias add for any column count, and erf-GELU.
 // RMSNorm, SiLU*up and residual adds are the ops the text tower already has (ops.hip).
-#include "prefill_attn.hpp"
-
-// w4m_gemm.hip / w16_gemm.hpp
-size_t w16m_size(int N, int K);
-int w16m_from_rows_launch(const void *w, int N, int K, void *w16m, hipStream_t st);
-size_t w16l_workspace_bytes(int M, int N, int K);
-int w16l_gemm_launch(int dtype, const void *w16m, const void *x, int ldx, int M, int N, int K, void *y, void *workspace, hipStream_t st, const void *bias,
-                     void *swiglu_act, bool *fused, int ldy);
+#include "gemm_rows.hpp"  // the W16M GEMM of w4m_gemm.hip / w16_gemm.hpp (prefill_attn.hpp comes with it)
 
 // y[m, n] = T(y[m, n] + b[n]), any N (two columns per thread; rows of odd length end in a single column)
 template <class T>

@@ -7,7 +7,11 @@
 //   <= 32 rows      k_w4m_gemm  (round 2's first form: one workgroup per 32-column strip, x fragments straight from L2): what remains for
 //                   K < 256 columns and as the tests' comparator (knob PIE_KNOB_W4R = 0); its persistent, LDS-staged and multi-strip
 //                   siblings were replaced by k_w4r_gemm (19 us against 26 us on gate|up at 32 rows: EXPERIMENTS.md)
-// Epilogues: store, SwiGLU on the interleaved gate|up rows, RoPE + cache append on the packed q|k|v rows, fp32 slabs of a K split.
+// Epilogues (W4Epi, gemm_rows.hpp): store, SwiGLU on the interleaved gate|up rows, RoPE + cache append on the packed q|k|v rows, fp32 slabs of a K split.
+// One entry serves every caller -- w4_rows_launch (below, with the route order, the epilogue each route takes and who adds the Linear's bias): linear_rows
+// of prefill.hip and the C ABI's pie_qgemm_w4m describe the product they want (W4Rows), ask w4_rows_workspace_bytes for the scratch, and read what was
+// done from one W4Outcome.  The per-family launchers (w4r_ / w4l_ / w4m_gemm_launch) stay callable for the bench tools; every K split that is not handed
+// to a consumer as slabs is reduced by the one reduce_slabs.
 //
 // W4M layout (derived on the device from the W4S stream, cached next to it; same 0.5625 B/weight): tiles of 32 output rows x
 // 64 columns (one quantisation group per row), 1152 B each, tile (nt, g) at ((nt * K/64) + g) * 1152:
@@ -19,7 +23,7 @@
 #include <map>
 #include <mutex>
 
-#include "prefill_attn.hpp"  // MfmaT, f32x16_t, DecState
+#include "gemm_rows.hpp"  // W4mRope, W4Epi, the request / outcome types and the prototypes (prefill_attn.hpp: MfmaT, f32x16_t, DecState)
 
 #ifndef W4M_ABL
 #define W4M_ABL 0  // developer ablation mask (tools/w4m_bench): 1 no dequantisation, 2 no x loads, 4 no MFMA; 0 in the product
@@ -107,20 +111,6 @@ __device__ __forceinline__ uint4 w4m_dequant_pk(u32 word, w4m_f32x2 s2, w4m_f32x
 }
 
 // Sum of the 8 waves' partial tiles (fixed order), rounded once, stored for the live rows.
-// Arguments of the q|k|v epilogue (rope = 2): RoPE on the q and k pairs and the cache append, exactly k_rope_append_rows (prefill.hip).
-struct W4mRope {
-    const float *rope_cs;               // [M, HD / 2, 2] (cos, sin) of every row's position (k_rope_cs_rows)
-    const DecState *state;              // single sequence: row m sits at state->pos + m, cache capacity state->cap ...
-    const int *ctx_len;                 // ... or a batch of sequences: row m at ctx_len[m] - 1 (< 0: idle slot)
-    const unsigned long long *kv_table; // per-layer K / V buffer (or slab) bases ...
-    u16 *slab;                          // ... or this layer's slab directly (batch)
-    const int *block_table;             // paged KV (nullable): table row m * bt_stride
-    int bt_stride, n_pages, layer, n_layers, n_heads, n_kv_heads, HD, traditional;
-    u16 *q_out;                         // [M, n_heads, HD]
-    const u16 *bias;                    // the Linear's bias (packed order), nullable
-    size_t i8_page_bytes;               // != 0 (with slab): the pages are int8 with per-head fp16 scales (paged_i8.hip): K / V are quantised on the way in
-};
-
 // one packed column pair (R, R + 1) of x-row m: the fp32 sums a, b -> T, (+ bias), then RoPE + store / cache append
 template <class T>
 __device__ __forceinline__ void w4m_rope_pair(float a, float b, int m, int R, const W4mRope &r) {
@@ -615,7 +605,14 @@ __global__ void __launch_bounds__(256) k_w4l_reduce(const float *part, int S, si
     }
     *reinterpret_cast<uint2 *>(y + i) = make_uint2(w4m_pack<T>(a.x, a.y), w4m_pack<T>(a.z, a.w));
 }
-
+// the reduce launch of every K-split GEMM of this file whose caller does not sum the slabs itself
+static int reduce_slabs(int dtype, const float *part, int S, int M, int N, void *y, hipStream_t st) {
+    const size_t MN = (size_t)M * N;
+    const dim3 rg((unsigned)((MN / 4 + 255) / 256));
+    hipLaunchKernelGGL(dtype == PIE_BF16 ? k_w4l_reduce<BF16> : k_w4l_reduce<F16>, rg, dim3(256), 0, st, part, S, MN, (u16 *)y);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
 
 // K-split factor the launcher will use for [M, N, K]: enough workgroups for the chip, at least 8 groups (512 columns) per split.
 // Decomposition: row tile (64 / 128 / 256 rows) x K split, and which kernel.  The one-wave-per-SIMD form (k_w4l2_gemm) needs a multiple
@@ -661,84 +658,62 @@ size_t w4l_workspace_bytes(int M, int N, int K) {
 }
 
 // workspace: w4l_workspace_bytes() of device scratch (may be null when that is 0)
-// swiglu_act (nullable): gate|up matrix and the caller wants the MLP activation [M, N / 2] there instead of y; *fused says whether it got it
-// slabs (nullable): the caller's consumer can sum the fp32 partial slabs of a K-split shape itself (in z order, then the Linear's one rounding:
-//   what k_w4l_reduce does) -- *slabs = S and NO reduce launch then, workspace holds [S][M][N]; *slabs = 0 when y was written
-int w4l_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, void *workspace, hipStream_t st, void *swiglu_act, bool *fused,
-                    int *slabs) {
-    if (fused) *fused = false;
-    if (slabs) *slabs = 0;
+// act (nullable): the packed gate|up matrix and the caller wishes the MLP activation [M, N / 2] there instead of y; done->epi says whether it got it
+//   (a shape that splits K, or that only the 8-wave form takes, writes y).  These kernels never apply a Linear bias.
+// take_slabs: the caller's consumer sums the fp32 partial slabs of a K-split shape itself -- done->slabs = S and NO reduce launch then
+int w4l_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, void *workspace, hipStream_t st, void *act, bool take_slabs,
+                    W4Outcome *done) {
+    *done = W4Outcome();
     PIE_REQUIRE(M >= 1 && N > 0 && K > 0 && N % 32 == 0 && K % 64 == 0, PIE_E_SHAPE, "W4 GEMM: N must be a multiple of 32 and K of 64");
     PIE_REQUIRE(pie_aligned(w4m, 16) && pie_aligned(x, 16) && pie_aligned(y, 8), PIE_E_ALIGN, "W4 GEMM: 16-byte alignment required");
     PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "W4 GEMM: dtype must be PIE_BF16 or PIE_F16");
     const W4lPlan plan = w4l_plan(M, N, K);
     const int S = plan.S, mt = plan.mt;
     PIE_REQUIRE(S == 1 || workspace, PIE_E_ARG, "W4 GEMM: this shape splits K and needs its workspace");
+    float *part = S > 1 ? (float *)workspace : nullptr;
     if (plan.v2) {
-        float *part2 = S > 1 ? (float *)workspace : nullptr;
         const dim3 grid((unsigned)((N / 32 + 7) / 8), (unsigned)((M + mt - 1) / mt), (unsigned)S);
 #define W4L2_GO(TT, MB_, SW_, Y_, P_) hipLaunchKernelGGL((k_w4l2_gemm<TT, MB_, SW_>), grid, dim3(256), 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)(Y_), P_)
 #define W4L2_MB(TT, SW_, Y_, P_) \
     if (mt == 64) W4L2_GO(TT, 2, SW_, Y_, P_); \
     else if (mt == 128) W4L2_GO(TT, 4, SW_, Y_, P_); \
     else W4L2_GO(TT, 8, SW_, Y_, P_)
-        if (S == 1 && swiglu_act && fused) {
-            if (dtype == PIE_BF16) { W4L2_MB(BF16, true, swiglu_act, nullptr); }
-            else { W4L2_MB(F16, true, swiglu_act, nullptr); }
+        if (S == 1 && act) {
+            if (dtype == PIE_BF16) { W4L2_MB(BF16, true, act, nullptr); }
+            else { W4L2_MB(F16, true, act, nullptr); }
             PIE_LAUNCH_CHECK();
-            *fused = true;
+            done->epi = W4R_SWIGLU;
             return PIE_OK;
         }
-        if (dtype == PIE_BF16) { W4L2_MB(BF16, false, y, part2); }
-        else { W4L2_MB(F16, false, y, part2); }
+        if (dtype == PIE_BF16) { W4L2_MB(BF16, false, y, part); }
+        else { W4L2_MB(F16, false, y, part); }
 #undef W4L2_MB
 #undef W4L2_GO
-        PIE_LAUNCH_CHECK();
-        if (S > 1 && slabs) {
-            *slabs = S;
-            return PIE_OK;
-        }
-        if (S > 1) {
-            const size_t MN = (size_t)M * N;
-            const dim3 rg((unsigned)((MN / 4 + 255) / 256));
-            if (dtype == PIE_BF16) hipLaunchKernelGGL(k_w4l_reduce<BF16>, rg, dim3(256), 0, st, part2, S, MN, (u16 *)y);
-            else hipLaunchKernelGGL(k_w4l_reduce<F16>, rg, dim3(256), 0, st, part2, S, MN, (u16 *)y);
-            PIE_LAUNCH_CHECK();
-        }
-        return PIE_OK;
-    }
-    // blockIdx.x = column block (fastest): the workgroups that share an x tile are dispatched together and read it through every XCD's L2
-    const dim3 grid((unsigned)((N / 32 + W4M_WAVES - 1) / W4M_WAVES), (unsigned)((M + mt - 1) / mt), (unsigned)S), block(W4M_WAVES * 64);
-    float *part = S > 1 ? (float *)workspace : nullptr;
-#define W4L_GO(TT, MB_) hipLaunchKernelGGL((k_w4l_gemm<TT, MB_>), grid, block, 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)y, part)
-    if (dtype == PIE_BF16) {
-        if (mt == 64) W4L_GO(BF16, 2);
-        else if (mt == 128) W4L_GO(BF16, 4);
-        else W4L_GO(BF16, 8);
     } else {
-        if (mt == 64) W4L_GO(F16, 2);
-        else if (mt == 128) W4L_GO(F16, 4);
-        else W4L_GO(F16, 8);
-    }
+        // blockIdx.x = column block (fastest): the workgroups that share an x tile are dispatched together and read it through every XCD's L2
+        const dim3 grid((unsigned)((N / 32 + W4M_WAVES - 1) / W4M_WAVES), (unsigned)((M + mt - 1) / mt), (unsigned)S), block(W4M_WAVES * 64);
+#define W4L_GO(TT, MB_) hipLaunchKernelGGL((k_w4l_gemm<TT, MB_>), grid, block, 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)y, part)
+        if (dtype == PIE_BF16) {
+            if (mt == 64) W4L_GO(BF16, 2);
+            else if (mt == 128) W4L_GO(BF16, 4);
+            else W4L_GO(BF16, 8);
+        } else {
+            if (mt == 64) W4L_GO(F16, 2);
+            else if (mt == 128) W4L_GO(F16, 4);
+            else W4L_GO(F16, 8);
+        }
 #undef W4L_GO
+    }
     PIE_LAUNCH_CHECK();
-    if (S > 1 && slabs) {
-        *slabs = S;
+    if (S > 1 && take_slabs) {
+        done->slabs = S;
         return PIE_OK;
     }
-    if (S > 1) {
-        const size_t MN = (size_t)M * N;
-        const dim3 rg((unsigned)((MN / 4 + 255) / 256));
-        if (dtype == PIE_BF16) hipLaunchKernelGGL(k_w4l_reduce<BF16>, rg, dim3(256), 0, st, part, S, MN, (u16 *)y);
-        else hipLaunchKernelGGL(k_w4l_reduce<F16>, rg, dim3(256), 0, st, part, S, MN, (u16 *)y);
-        PIE_LAUNCH_CHECK();
-    }
-    return PIE_OK;
+    return S > 1 ? reduce_slabs(dtype, part, S, M, N, y, st) : PIE_OK;
 }
 
 // ---------------------------------------------------------------- 16-bit weights, many rows (w16_gemm.hpp)
 #include "w16_gemm.hpp"
-int bias_any_launch(int dtype, void *y, const void *bias, int M, int N, hipStream_t st);  // vision.hip
 
 static char *g_w16_zero = nullptr;  // 4 KiB of zeros: the weight tile of the ring's dummy steps
 static std::mutex g_w16_mutex;
@@ -882,11 +857,7 @@ int w16l_gemm_launch(int dtype, const void *w16m, const void *x, int ldx, int M,
     PIE_LAUNCH_CHECK();
     if (sg && fused) *fused = true;
     if (plan.S > 1) {
-        const size_t MN = (size_t)M * N;
-        const dim3 rg((unsigned)((MN / 4 + 255) / 256));
-        if (dtype == PIE_BF16) hipLaunchKernelGGL(k_w4l_reduce<BF16>, rg, dim3(256), 0, st, a.part, plan.S, MN, (u16 *)y);
-        else hipLaunchKernelGGL(k_w4l_reduce<F16>, rg, dim3(256), 0, st, a.part, plan.S, MN, (u16 *)y);
-        PIE_LAUNCH_CHECK();
+        if ((rc = reduce_slabs(dtype, a.part, plan.S, M, N, y, st))) return rc;
         if (bias) return bias_any_launch(dtype, y, bias, M, N, st);
     }
     return PIE_OK;
@@ -949,14 +920,14 @@ static void w4r_go(const W4rPlan &pl, int N, hipStream_t st, const W4rArgs &a, c
     }
 }
 
-// epi: W4R_STORE (y [M, N], + bias), W4R_SWIGLU (y = activation [M, N / 2], + bias), W4R_ROPE (rope != nullptr; q -> rope->q_out, k / v -> cache).
-// slabs (nullable, STORE only): the caller's consumer sums the fp32 slabs of a K-split shape itself -> *slabs = S and workspace holds
-// [S][M][N]; otherwise a K-split shape is reduced here (k_w4l_reduce) and the bias, if any, is left to the caller (returns *slabs = 0).
+// epi: W4R_STORE (y [M, N], + bias), W4R_SWIGLU (y = activation [M, N / 2], + bias), W4R_ROPE (rope != nullptr, its bias field; q -> rope->q_out, k / v -> cache).
+// workspace (STORE only; nullptr: no K split): w4r_workspace_bytes() of device scratch.
+// take_slabs (STORE only): the caller's consumer sums the fp32 slabs of a K-split shape itself -> done->slabs = S and workspace holds [S][M][N];
+// otherwise a K-split shape is reduced here and the bias, if any, is left to the caller (done->bias_done = false).
 // wide_scales: some |scale| of the matrix is >= 2^100 (w4m_repack_launch reports it): outside w4r_dequant's domain, the plain conversion everywhere.
 int w4r_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, void *workspace, hipStream_t st, int epi, const void *bias,
-                    const W4mRope *rope, int *slabs, bool *bias_done, bool wide_scales) {
-    if (slabs) *slabs = 0;
-    if (bias_done) *bias_done = false;
+                    const W4mRope *rope, bool take_slabs, W4Outcome *done, bool wide_scales) {
+    *done = W4Outcome();
     PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "W4R GEMM: dtype must be PIE_BF16 or PIE_F16");
     PIE_REQUIRE((epi == W4R_ROPE) == (rope != nullptr), PIE_E_ARG, "W4R GEMM: the q|k|v epilogue needs its arguments");
     const bool may_split = epi == W4R_STORE && workspace != nullptr;
@@ -970,26 +941,20 @@ int w4r_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int
     a.prof = g_w4r_prof;
 #endif
     const W4mRope r = rope ? *rope : W4mRope{};
-    const int e = pl.S > 1 ? W4R_SLAB : epi;
-    if (pl.S > 1) a.part = (float *)workspace, a.bias = nullptr;
-    a.epi = e;
+    if (pl.S > 1) a.part = (float *)workspace, a.bias = nullptr, a.epi = W4R_SLAB;
     if (dtype == PIE_F16) w4r_go<F16, false>(pl, N, st, a, r);  // f16 scales cannot leave w4r_dequant's domain
     else if (wide_scales) w4r_go<BF16, true>(pl, N, st, a, r);
     else w4r_go<BF16, false>(pl, N, st, a, r);
     PIE_LAUNCH_CHECK();
+    done->epi = epi;
     if (pl.S > 1) {
-        if (slabs) {
-            *slabs = pl.S;
+        if (take_slabs) {
+            done->slabs = pl.S;
             return PIE_OK;
         }
-        const size_t MN = (size_t)M * N;
-        const dim3 rg((unsigned)((MN / 4 + 255) / 256));
-        if (dtype == PIE_BF16) hipLaunchKernelGGL(k_w4l_reduce<BF16>, rg, dim3(256), 0, st, (const float *)workspace, pl.S, MN, (u16 *)y);
-        else hipLaunchKernelGGL(k_w4l_reduce<F16>, rg, dim3(256), 0, st, (const float *)workspace, pl.S, MN, (u16 *)y);
-        PIE_LAUNCH_CHECK();
-        return PIE_OK;
+        return reduce_slabs(dtype, (const float *)workspace, pl.S, M, N, y, st);
     }
-    if (bias_done) *bias_done = true;
+    done->bias_done = true;  // (STORE / SWIGLU: a.bias; ROPE: rope->bias)
     return PIE_OK;
 }
 
@@ -1026,22 +991,79 @@ int w4m_repack_launch(const void *w4s, int N, int K, void *w4m, hipStream_t st) 
     return PIE_OK;
 }
 
-// swiglu: N = 2 * inter interleaved gate|up rows -> y is the activation [M, N / 2] (bias: the Linear's, applied before it).
-// swiglu == 2 (rope != nullptr): N = packed q|k|v rows; the epilogue rotates q / k and appends k / v to the cache (y unused).
-int w4m_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, hipStream_t st, int swiglu, const void *bias, const W4mRope *rope) {
+// The few-row kernel.  epi W4R_SWIGLU: N = 2 * inter interleaved gate|up rows -> y is the activation [M, N / 2] (bias: the Linear's, applied before it);
+// W4R_ROPE (rope != nullptr): N = packed q|k|v rows; the epilogue adds rope->bias, rotates q / k and appends k / v to the cache (y unused);
+// W4R_STORE: y [M, N] without a bias (the kernel has none on that epilogue).
+int w4m_gemm_launch(int dtype, const void *w4m, const void *x, int M, int N, int K, void *y, hipStream_t st, int epi, const void *bias, const W4mRope *rope) {
     const W4mRope rope_args = rope ? *rope : W4mRope{};
-    PIE_REQUIRE((swiglu == 2) == (rope != nullptr), PIE_E_ARG, "W4M GEMM: the q|k|v epilogue needs its arguments");
+    PIE_REQUIRE(epi == W4R_STORE || epi == W4R_SWIGLU || epi == W4R_ROPE, PIE_E_ARG, "W4M GEMM: store, SwiGLU or q|k|v epilogue");
+    PIE_REQUIRE((epi == W4R_ROPE) == (rope != nullptr), PIE_E_ARG, "W4M GEMM: the q|k|v epilogue needs its arguments");
     PIE_REQUIRE(M >= 1 && M <= 32, PIE_E_SHAPE, "W4M GEMM: 1 to 32 rows");
     PIE_REQUIRE(N > 0 && K > 0 && N % 32 == 0 && K % 64 == 0, PIE_E_SHAPE, "W4M GEMM: N must be a multiple of 32 and K of 64");
     PIE_REQUIRE(pie_aligned(w4m, 16) && pie_aligned(x, 16), PIE_E_ALIGN, "W4M GEMM: 16-byte alignment required");
     PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "W4M GEMM: dtype must be PIE_BF16 or PIE_F16");
     const dim3 grid(N >> 5), block(W4M_WAVES * 64);
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_w4m_gemm<BF16>, grid, block, 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)y, swiglu, (const u16 *)bias, rope_args);
-    else hipLaunchKernelGGL(k_w4m_gemm<F16>, grid, block, 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)y, swiglu, (const u16 *)bias, rope_args);
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_w4m_gemm<BF16>, grid, block, 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)y, epi, (const u16 *)bias, rope_args);
+    else hipLaunchKernelGGL(k_w4m_gemm<F16>, grid, block, 0, st, (const char *)w4m, (const u16 *)x, M, N, K, (u16 *)y, epi, (const u16 *)bias, rope_args);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
 
+// ---------------------------------------------------------------- the one entry: every many-row int4 Linear
+// Routes, in this order (linear_rows of prefill.hip has taken the rows of the GEMV regime, up to GEMV_ROWS_MAX, before it comes here):
+//   1. k_w4r_gemm wherever it serves (w4r_serves: up to 256 rows, K of at least one step; never with PIE_KNOB_W4R = 0).  It takes the SwiGLU wish always
+//      and the RoPE wish only where the shape fills the chip without a K split (w4r_splits == 1); otherwise it stores -- as slabs if the caller takes them.
+//   2. the few-row k_w4m_gemm for the rows that are left (K < 256, or the knob), if the caller allows it, with every wish;
+//   3. the tile kernels for everything else: the SwiGLU wish only without a Linear bias and where the shape allows, never RoPE.
+// Who adds the Linear's bias: k_w4r_gemm in its epilogue when it does not split K; k_w4m_gemm in its SwiGLU and (via rope->bias) RoPE epilogues, not on
+// store; the tile kernels never.  A K split reduced in here leaves it to the caller (done->bias_done = false), slabs handed out leave it to their consumer.
+enum { W4_ROUTE_STREAM, W4_ROUTE_FEW, W4_ROUTE_TILE };
+// Rows up to which an int4 Linear that k_w4r_gemm does not take runs on the few-row kernel instead of the tile kernels (PIE_KNOB_SMALL_M: 0 disables, max 32)
+static int small_rows() {
+    const int k = pie_knob(PIE_KNOB_SMALL_M);
+    const int v = k >= 0 ? k : 32;
+    return v < 0 ? 0 : (v > 32 ? 32 : v);
+}
+static int w4_rows_route(const W4Rows &q) {
+    if (w4r_serves(q.M, q.N, q.K)) return W4_ROUTE_STREAM;
+    // pie_qgemm_w4m is how the tests and developer tools reach one kernel by its row count, as the comparator of another: its rule is fixed, 32 rows, where
+    // linear_rows follows the decoder's knob and keeps the few-row kernel to matrices with resident tiles (few_rows)
+    if (q.abi_rows ? q.M <= 32 : (q.few_rows && q.M <= small_rows())) return W4_ROUTE_FEW;
+    return W4_ROUTE_TILE;
+}
+// k_w4r_gemm's epilogue for a request
+static int w4r_epi(const W4Rows &q) {
+    if (q.wish == W4R_ROPE && w4r_splits(q.M, q.N, q.K) != 1) return W4R_STORE;  // a K split cannot rotate: its consumer does (k_rope_append_rows)
+    return q.wish;
+}
+size_t w4_rows_workspace_bytes(const W4Rows &q) {
+    switch (w4_rows_route(q)) {
+    case W4_ROUTE_STREAM: return w4r_epi(q) == W4R_STORE ? w4r_workspace_bytes(q.M, q.N, q.K) : 0;
+    case W4_ROUTE_FEW: return 0;
+    default: return w4l_workspace_bytes(q.M, q.N, q.K);
+    }
+}
+int w4_rows_launch(const W4Rows &q, void *workspace, hipStream_t st, W4Outcome *done) {
+    *done = W4Outcome();
+    PIE_REQUIRE((q.wish == W4R_STORE || (q.wish == W4R_SWIGLU && q.act) || (q.wish == W4R_ROPE && q.rope)), PIE_E_ARG, "W4 rows: an epilogue wish needs its arguments");
+    const bool take_slabs = q.take_slabs && pie_knob(PIE_KNOB_W4L_SLABS) != 0;  // knob 0: always reduce in the GEMM's own launch (the bit-equality test)
+    switch (w4_rows_route(q)) {
+    case W4_ROUTE_STREAM: {
+        const int epi = w4r_epi(q);
+        if (epi == W4R_ROPE) q.rope->bias = (const u16 *)q.bias;
+        return w4r_gemm_launch(q.dtype, q.w4m, q.x, q.M, q.N, q.K, epi == W4R_SWIGLU ? q.act : epi == W4R_ROPE ? nullptr : q.y, epi == W4R_STORE ? workspace : nullptr,
+                               st, epi, epi == W4R_ROPE ? nullptr : q.bias, epi == W4R_ROPE ? q.rope : nullptr, take_slabs && epi == W4R_STORE, done,
+                               w4m_wide_scales(q.w4m));
+    }
+    case W4_ROUTE_FEW:
+        done->epi = q.wish, done->bias_done = q.wish != W4R_STORE;
+        if (q.wish == W4R_ROPE) q.rope->bias = (const u16 *)q.bias;
+        return w4m_gemm_launch(q.dtype, q.w4m, q.x, q.M, q.N, q.K, q.wish == W4R_SWIGLU ? q.act : q.wish == W4R_ROPE ? nullptr : q.y, st, q.wish,
+                               q.wish == W4R_SWIGLU ? q.bias : nullptr, q.wish == W4R_ROPE ? q.rope : nullptr);
+    default:  // gate|up without a Linear bias: the SwiGLU rides in the GEMM's epilogue where the shape allows
+        return w4l_gemm_launch(q.dtype, q.w4m, q.x, q.M, q.N, q.K, q.y, workspace, st, q.wish == W4R_SWIGLU && !q.bias ? q.act : nullptr, take_slabs, done);
+    }
+}
 
 extern "C" {
 
@@ -1056,25 +1078,17 @@ int pie_qgemm_w4m(const void *x, const void *w4m, int M, int N, int K, int dtype
     PIE_REQUIRE(x && w4m && y, PIE_E_ARG, "pie_qgemm_w4m: null pointer");
     // before any plan or workspace arithmetic: with N < 32 a plan has no column tiles and divides by zero on the host
     PIE_REQUIRE(M > 0 && N >= 32 && N % 32 == 0 && K >= 64 && K % 64 == 0, PIE_E_SHAPE, "pie_qgemm_w4m: M > 0, N a multiple of 32, K a multiple of 64");
-    if (w4r_serves(M, N, K)) {  // 6 .. 256 rows (and fewer, when asked at this level): the weight-streaming form
-        hipStream_t st = (hipStream_t)stream;
-        void *ws = nullptr;
-        const size_t wb = w4r_workspace_bytes(M, N, K);
-        if (wb && hipMallocAsync(&ws, wb, st) != hipSuccess) return pie::fail(PIE_E_HIP, "pie_qgemm_w4m: hipMallocAsync failed");
-        const int rc = w4r_gemm_launch(dtype, w4m, x, M, N, K, y, ws, st, W4R_STORE, nullptr, nullptr, nullptr, nullptr, w4m_wide_scales(w4m));
-        if (ws) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    if (M > 32) {  // the prompt GEMM; a K-split shape takes stream-ordered scratch for its fp32 partial tiles
-        hipStream_t st = (hipStream_t)stream;
-        void *ws = nullptr;
-        const size_t wb = w4l_workspace_bytes(M, N, K);
-        if (wb && hipMallocAsync(&ws, wb, st) != hipSuccess) return pie::fail(PIE_E_HIP, "pie_qgemm_w4m: hipMallocAsync failed");
-        const int rc = w4l_gemm_launch(dtype, w4m, x, M, N, K, y, ws, st, nullptr, nullptr, nullptr);
-        if (ws) (void)hipFreeAsync(ws, st);
-        return rc;
-    }
-    return w4m_gemm_launch(dtype, w4m, x, M, N, K, y, (hipStream_t)stream, 0, nullptr, nullptr);
+    // the op-level call: no Linear bias, no epilogue wish, no consumer for slabs -- a K-split shape is reduced in here, on stream-ordered scratch
+    hipStream_t st = (hipStream_t)stream;
+    W4Rows q = {dtype, w4m, x, M, N, K, y};
+    q.abi_rows = true;
+    void *ws = nullptr;
+    const size_t wb = w4_rows_workspace_bytes(q);
+    if (wb && hipMallocAsync(&ws, wb, st) != hipSuccess) return pie::fail(PIE_E_HIP, "pie_qgemm_w4m: hipMallocAsync failed");
+    W4Outcome done;
+    const int rc = w4_rows_launch(q, ws, st, &done);
+    if (ws) (void)hipFreeAsync(ws, st);
+    return rc;
 }
 
 }  // extern "C"

@@ -22,10 +22,9 @@
 //     one barrier per step; the closing wait is a COUNTED vmcnt that leaves the younger DMAs and weight tiles in flight;
 //   * the K-phases' partial tiles are summed through LDS in phase order (deterministic) by all 512 threads, 8 consecutive output columns
 //     per thread, which is also the shape the epilogues want: store (+ bias), SwiGLU on the interleaved gate|up columns, RoPE + cache
-//     append on the packed q|k|v columns, or un-rounded fp32 slabs of a K split that the consumer kernel sums (W4lSlabs, prefill.hip).
+//     append on the packed q|k|v columns, or un-rounded fp32 slabs of a K split that the consumer kernel sums (W4lSlabs, gemm_rows.hpp).
 #pragma once
 
-enum { W4R_STORE = 0, W4R_SWIGLU = 1, W4R_ROPE = 2, W4R_SLAB = 3 };
 #ifndef W4R_ABL
 #define W4R_ABL 0  // developer ablation mask (tools/w4r_bench): 1 no conversion, 2 no MFMA, 4 no x DMA, 8 no LDS fragment reads, 16 no weight loads; 0 in the product
 #endif
@@ -38,7 +37,7 @@ struct W4rArgs {
     u16 *y;            // STORE: [M, N]; SWIGLU: the activation [M, N / 2]
     float *part;       // SLAB: [gridDim.y][M][N] un-rounded fp32 sums
     const u16 *bias;   // the Linear's bias (nullable; STORE / SWIGLU; ROPE takes W4mRope::bias)
-    int epi;           // W4R_STORE / W4R_SWIGLU / W4R_ROPE / W4R_SLAB (run-time: the epilogues are outside the loop, one kernel per geometry)
+    int epi;           // W4Epi of gemm_rows.hpp: W4R_STORE / W4R_SWIGLU / W4R_ROPE / W4R_SLAB (run-time: the epilogues are outside the loop, one kernel per geometry)
 #ifdef W4R_PROF
     unsigned long long *prof;  // developer build: [workgroup][wave][step][4] s_memtime stamps (tools/w4r_bench)
 #endif

@@ -651,8 +651,10 @@ def add_bias_rms_norm(x: torch.Tensor, r: torch.Tensor, bias: torch.Tensor, norm
 
 def quantized_matmul_rows(x: torch.Tensor, w: PackedWeight, w4m: torch.Tensor | None = None) -> torch.Tensor:
     """mx.quantized_matmul in its many-row regime -- weights dequantised to T, T x T products on the MFMA units, fp32
-    accumulation -- reading the int4 weights in 4-bit form (pie_qgemm_w4m: the few-row kernels up to 32 rows, the 256 x 256-tile
-    prompt GEMM beyond).  x [M, K]; w: the W4S matrix (N % 32 == 0); w4m: its W4M tile copy from `repack_w4m` (built here when absent)."""
+    accumulation -- reading the int4 weights in 4-bit form.  pie_qgemm_w4m goes through the library's one many-row int4 entry (w4_rows_launch,
+    w4m_gemm.hip), as a plain store without bias: the weight-streaming k_w4r_gemm wherever it serves (up to 256 rows, K of at least 256, 128 beyond
+    64 rows), else the few-row kernel up to 32 rows and the tile kernels beyond; a K-split shape is reduced inside the call.  Unlike the decoder, this call
+    does not follow knob small_m (the w4r knob does apply), so that tests can reach each kernel by its row count.  x [M, K]; w: the W4S matrix (N % 32 == 0); w4m: its W4M tile copy from `repack_w4m` (built here when absent)."""
     _dev(x)
     if w.fmt != _ffi.PIE_W_INT4_G64:
         raise TypeError("quantized_matmul_rows takes an int4 group-64 weight")

@@ -5,6 +5,7 @@ top-1/top-2 margin exceeds the 16-bit error bound; logits / logprobs / hidden st
 4 eps_T * max|ref| (max) and 4 eps_T * rms(ref) (rms), eps = 2^-8 (bf16) / 2^-11 (f16): tests/_util.py
 assert_vec_close.  (BASELINE.md's absolute 2e-2 presumed O(1) logits; one bf16 ulp of a logit of 20 is 0.125.)
 """
+import copy
 import json
 
 import numpy as np
@@ -434,6 +435,35 @@ def test_short_prompt_int4_gemm_paths(tiny, knobs, L):
     for name in ("round-2 kernels", "many-row kernel"):
         assert_vec_close(outs["w4r"][0][-1], outs[name][0][-1], DT, what=f"w4r vs {name}")
         assert_vec_close(outs["w4r"][1], outs[name][1], DT, what=f"decode after w4r vs {name} prompt")
+
+
+@pytest.mark.parametrize("L", [30, 40])
+def test_short_prompt_int4_gemm_paths_with_linear_biases(knobs, L):
+    """The Linear biases (attention_bias / mlp_bias) on each int4 many-row route of the tiny model: k_w4r_gemm (default); with knob w4r = 0 the
+    few-row kernel's store / SwiGLU / RoPE epilogues at 30 rows and the tile kernels at 40 (gate|up declined for fusion because of its bias; down,
+    K = 704 = 11 groups, on the 8-wave k_w4l_gemm, the K = 256 matrices on k_w4l2_gemm); with small_m = 0 as well the tile kernels at 30 rows too.
+    Every position against the oracle, then one decode step on the cache the prompt filled."""
+    cfg = dict(po.TINY_CONFIG, attention_bias=True, mlp_bias=True, tie_word_embeddings=False)
+    w = po.synth_checkpoint(cfg, seed=33, dtype=DT, lm_head_gain=4.0)
+    assert "model.layers.0.self_attn.k_proj.bias" in w and "model.layers.1.mlp.down_proj.bias" in w
+    prompt = np.random.default_rng(L).integers(0, cfg["vocab_size"], L)
+    orc = po.OracleLlama(cfg, w, DT)
+    ocache = [po.OracleKVCache() for _ in orc.layers]
+    want = orc.forward(prompt, ocache)
+    want_next = {}                                                     # the oracle's decode step per token a route sampled (one, bar a near-tie)
+    for name, w4r, small in (("w4r", None, None), ("round-2 kernels", 0, 32), ("many-row kernel", 0, 0)):
+        knobs("w4r", w4r)
+        knobs("small_m", small)
+        m = build(cfg, w)
+        cache = m.make_cache()
+        got = m(torch.from_numpy(prompt)[None].cuda(), cache=cache)[0].float().cpu().numpy()
+        for l in range(L):
+            assert_vec_close(got[l], want[l], DT, what=f"bias, {name} L={L} position {l}")
+        t = int(m.token.item())
+        if t not in want_next:
+            want_next[t] = orc.forward(np.array([t]), copy.deepcopy(ocache))[0]
+        tok, _, logits = m.step(None, cache)
+        assert_vec_close(logits.float().cpu().numpy(), want_next[t], DT, what=f"bias, decode after {name} L={L}")
 
 
 def test_batched_prefill_llama8b_shapes(knobs):

@@ -98,10 +98,11 @@ static int check_shape(int M, int N, int K, int epi, bool with_bias, bool no_sla
     const size_t wsb = w4r_workspace_bytes(M, N, K);
     if (wsb) hipMalloc(&d.ws, wsb), hipMemset(d.ws, 0xFF, wsb);
     hipLaunchKernelGGL(k_ref, dim3((N + 127) / 128, M), dim3(128), 0, 0, d.w, d.x, M, N, K, d.ref);
-    int slabs = 0;
-    bool bias_done = false;
-    const int rc = w4r_gemm_launch(PIE_BF16, d.w, d.x, M, N, K, d.y, d.ws, 0, epi, with_bias ? d.bias : nullptr, nullptr, no_slab_consumer ? nullptr : &slabs, &bias_done, g_plain);
+    W4Outcome done;
+    const int rc = w4r_gemm_launch(PIE_BF16, d.w, d.x, M, N, K, d.y, d.ws, 0, epi, with_bias ? d.bias : nullptr, nullptr, !no_slab_consumer, &done, g_plain);
     if (rc) return 1;
+    const int slabs = done.slabs;
+    const bool bias_done = done.bias_done;
     if (hipDeviceSynchronize() != hipSuccess) {
         printf("M=%d N=%d K=%d epi=%d: kernel FAULT: %s\n", M, N, K, epi, hipGetErrorString(hipGetLastError()));
         exit(2);
@@ -216,7 +217,8 @@ int main(int argc, char **argv) {
         extern unsigned long long *g_w4r_prof;
         for (int i = 0; i < 5; ++i) {
             g_w4r_prof = i == 4 ? prof : nullptr;
-            w4r_gemm_launch(PIE_BF16, w + bytes * i, x, M, N, K, y, nullptr, 0, W4R_SWIGLU, nullptr, nullptr, nullptr, nullptr, g_plain);
+            W4Outcome done;
+            w4r_gemm_launch(PIE_BF16, w + bytes * i, x, M, N, K, y, nullptr, 0, W4R_SWIGLU, nullptr, nullptr, false, &done, g_plain);
         }
         hipDeviceSynchronize();
         std::vector<unsigned long long> h(8 * 8 * 32 * 4);
@@ -258,15 +260,13 @@ int main(int argc, char **argv) {
         const auto hw = make_tiles(s.N, s.K, 5);
         for (int i = 0; i < copies; ++i) hipMemcpy(w + bytes * i, hw.data(), bytes, hipMemcpyHostToDevice);
         for (int M : Ms) {
-            int slabs = 0;
-            const double us_new = time_it(2 * copies, [&](int i) { w4r_gemm_launch(PIE_BF16, w + bytes * (i % copies), x, M, s.N, s.K, y, ws, 0, s.epi, nullptr, nullptr, &slabs, nullptr, g_plain); });
+            W4Outcome done;
+            const double us_new = time_it(2 * copies, [&](int i) { w4r_gemm_launch(PIE_BF16, w + bytes * (i % copies), x, M, s.N, s.K, y, ws, 0, s.epi, nullptr, nullptr, true, &done, g_plain); });
             double us_old;
             if (M <= 32) {
-                us_old = time_it(2 * copies, [&](int i) { w4m_gemm_launch(PIE_BF16, w + bytes * (i % copies), x, M, s.N, s.K, y, 0, s.epi == W4R_SWIGLU ? 1 : 0, nullptr, nullptr); });
+                us_old = time_it(2 * copies, [&](int i) { w4m_gemm_launch(PIE_BF16, w + bytes * (i % copies), x, M, s.N, s.K, y, 0, s.epi, nullptr, nullptr); });
             } else {
-                bool fused = false;
-                int sl = 0;
-                us_old = time_it(2 * copies, [&](int i) { w4l_gemm_launch(PIE_BF16, w + bytes * (i % copies), x, M, s.N, s.K, y, ws, 0, s.epi == W4R_SWIGLU ? (void *)y : nullptr, &fused, &sl); });
+                us_old = time_it(2 * copies, [&](int i) { w4l_gemm_launch(PIE_BF16, w + bytes * (i % copies), x, M, s.N, s.K, y, ws, 0, s.epi == W4R_SWIGLU ? (void *)y : nullptr, true, &done); });
             }
             const W4rPlan pl = w4r_plan(M, s.N, s.K, s.epi == W4R_STORE);
             const double flop = 2.0 * M * s.N * s.K;
