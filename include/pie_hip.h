@@ -198,6 +198,12 @@ int pie_add(const void *a, const void *b, size_t n, int dtype, void *y, void *st
  * engine/inference_engine.py:268-271 + samplers/__init__.py:37-38: logprobs = f32(logits) - logsumexp,
  * token = first argmax.  logits [V] T, logprobs fp32 [V], token device int32 [1]. */
 int pie_logprobs_argmax(const void *logits, int V, int dtype, float *logprobs, int32_t *token, void *stream);
+/* The repetition penalty (logits_processors/repetition.py:11-22) on logits [V] T, in place: for every DISTINCT id among ids[0..n) (device
+ * int32), x = f32(logits[id]), logits[id] = T(x < 0 ? x * (float)penalty : x / (float)penalty) -- one IEEE fp32 multiplication or division,
+ * then one round-to-nearest-even to T.  An id that occurs several times is penalised once (the reference gathers, computes and scatters);
+ * ids outside [0, V) are skipped and never indexed; -0.0 is not < 0 and is divided.  One launch of one workgroup.
+ * penalty < 0 or not finite, n outside 1..1024: PIE_E_ARG; V < 1: PIE_E_SHAPE -- each before any launch. */
+int pie_logits_penalty(void *logits, int V, int dtype, const int32_t *ids, int n, double penalty, void *stream);
 /* Measurement aid (no reference counterpart; SURVEY.md 8d "fraction of a measured device-copy bandwidth"): a bare streaming read of `bytes`
  * shaped like the weight GEMV's stream (one 8-wave workgroup per CU, non-temporal 16-byte loads, nothing computed).  bench.py times it for
  * roofline.stream_peak. */
@@ -369,6 +375,29 @@ int pie_decoder_bind_outputs(pie_decoder *d, void *logits, float *logprobs, int3
 /* Copies a device-resident token id into the decoder's device-side state (the input of the next
  * pie_decoder_step) without a host round trip; a no-op when `token_dev` is the bound token output. */
 int pie_decoder_set_token_from(pie_decoder *d, const int32_t *token_dev, void *stream);
+/* The step's configurable tail: the engine's two generation knobs inside the launch sequence, so that a request with a
+ * repetition penalty or a stochastic sampler still costs one graph replay per token and no host synchronisation.  The configuration applies
+ * wherever the tail writes the BOUND outputs: pie_decoder_step with PIE_STEP_LOGITS (eager or PIE_STEP_GRAPH) and the last row of
+ * pie_decoder_prefill / _prefill_embeds with logits_all == NULL; with logits_all != NULL the logits stay raw and the tail greedy.  Order:
+ * lm_head | penalty on the bound logits (which then hold the processed logits) | per-tile partials recomputed from them (pie_logprobs_argmax's
+ * own partition, so logprobs and the greedy token are bit-identical with pie_logprobs_argmax of the bound logits) | finish | pie_sample's
+ * launches over the bound logprobs; the drawn id becomes *token, the fed-back token and history[new position].  Any cache kind; refused
+ * (PIE_E_STATE) on tensor-parallel decoders, whose tail is vocabulary-parallel.  pie_decoder_step_batch / _prefill_batch / _step_mixed ignore
+ * it.  A change of either setting (the seed included: it is a launch argument) drops the captured graphs; with neither set the step is
+ * exactly the unconfigured one.
+ * pie_decoder_set_logits_penalty: pie_logits_penalty over the ids the model was fed at positions max(0, p + 1 - context_size) .. p, p = the
+ *   position the tail processes (the row's own input id included, the token about to be chosen not: prompt_cache.update runs before the
+ *   processors, inference_engine.py:255-266).  ids_by_pos: caller-owned DEVICE int32 [ids_cap], ids_by_pos[q] = the id fed at position q.  The
+ *   caller writes every id it passes explicitly (a prompt's rows, an explicit single token); a step records its input token -- the
+ *   device-side state's -- at ids_by_pos[p] itself before it penalises, so fed-back tokens need no host.  Every index is checked against
+ *   ids_cap on the device.  penalty == 1.0 or context_size == 0 switches it off; otherwise penalty finite and >= 0, context_size 1..1024.
+ * pie_decoder_set_sampler: mode PIE_SAMPLE_GREEDY restores the greedy tail; otherwise pie_sample's modes, argument checks, random stream
+ *   (seed, DEVICE counter) and workspace (pie_sample_workspace_bytes(1, vocab) bytes, zeroed once by the caller), all caller-owned and
+ *   alive while set. */
+enum { PIE_SAMPLE_GREEDY = -1 };
+int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_size, int32_t *ids_by_pos, int ids_cap);
+int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
+                            void *workspace, size_t workspace_bytes);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -15,6 +15,7 @@ _PKG = Path(__file__).resolve().parent
 PIE_BF16, PIE_F16 = 1, 2
 PIE_STEP_LOGITS, PIE_STEP_GRAPH = 1, 2
 PIE_OPT_KV_I8 = 2
+PIE_SAMPLE_GREEDY = -1  # pie_decoder_set_sampler: the greedy tail
 # test / tuning switches (include/pie_hip.h: pie_set_knob); -1 restores a default
 KNOBS = {"prefill_min": 0, "prefill_chunk": 1, "prefill_resident": 2, "small_m": 3, "w4l_slabs": 4, "prefill_attn_valu": 5,
          "prefill_qt": 6, "attn_merge_max_cap": 7, "attn_warm_max_mb": 8, "w4r": 9, "fuse_attn": 10, "attn_merge_in_launch": 11}
@@ -43,6 +44,7 @@ EXPORTS = [
     "pie_comm_create", "pie_comm_rccl_unique_id", "pie_comm_create_rccl", "pie_comm_export", "pie_comm_connect", "pie_allreduce_f32", "pie_comm_status", "pie_comm_destroy", "pie_decoder_set_comm", "pie_sample", "pie_sample_workspace_bytes",
     "pie_kv_quantize", "pie_attn_decode_quant", "pie_decoder_set_kv_quant",
     "pie_decoder_set_kv_ring", "pie_kv_ring_order", "pie_sdpa_prefill_window", "pie_sdpa_decode_ring",
+    "pie_logits_penalty", "pie_decoder_set_logits_penalty", "pie_decoder_set_sampler",
 ]
 
 
@@ -118,6 +120,9 @@ def load() -> C.CDLL:
     lib.pie_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_sample_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pie_logits_penalty.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+    lib.pie_decoder_set_logits_penalty.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int]
+    lib.pie_decoder_set_sampler.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.pie_sample_workspace_bytes.restype = C.c_size_t
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]

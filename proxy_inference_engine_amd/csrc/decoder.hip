@@ -8,6 +8,7 @@
 // (The embedding rides in layer 0's q|k|v launch for int4 models; for the 32 / 8 / 128 head geometry the attention rides in every q|k|v launch,
 // behind an XCD-local seam: attn_form() below.)
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -155,6 +156,26 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
     return a;
 }
 
+// The configured tail over the bound outputs (include/pie_hip.h): penalty + fresh partials | finish | the sampler's launches.
+// from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
+static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    const LogitStat *stats = d->stats;
+    int n_stats = d->n_stats, rc;
+    if (d->pen != 1.0) {
+        PenArgs a = {};
+        a.logits = d->logits, a.V = c.vocab, a.penalty = (float)d->pen, a.ids_by_pos = d->ids_by_pos, a.ids_cap = d->ids_cap, a.context = d->pen_ctx;
+        a.state = d->state, a.record = from_state;
+        if ((rc = logits_penalty_launch(c.dtype, a, st))) return rc;
+        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st))) return rc;  // the lm_head epilogue's partials are stale
+        stats = d->tail_stats, n_stats = TAIL_STAT_TILES;
+    }
+    if ((rc = logits_tail_launch(c.dtype, d->logits, c.vocab, stats, n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st))) return rc;
+    if (d->smp_mode == PIE_SAMPLE_GREEDY) return PIE_OK;
+    const SampleFeed feed = {&d->state->token, &d->state->pos, d->history, d->hist_cap};
+    return sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st);
+}
+
 // One launch of the step's sequence (PIE_K_* of include/pie_hip.h); `li` is the layer for per-layer kernels.
 int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 *logits_dst, hipStream_t st, bool embed_here) {
     const pie_decoder_config &c = d->cfg;
@@ -257,6 +278,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
             if (d->tp())  // vocabulary-parallel: (max, sum exp, argmax) of every shard -> global log-sum-exp and token
                 return tp_tail_launch(d->comm, c.dtype, logits_dst, c.vocab, c.tp_rank * c.vocab, d->stats, d->n_stats, d->tp_part + H, d->logprobs, d->token_out,
                                       d->state, d->history, d->hist_cap, st);
+            if (d->tail_configured() && logits_dst == d->logits && !d->tail_raw) return configured_tail(d, token_ptr == &d->state->token && !d->row_is_h, st);
             return logits_tail_launch(c.dtype, logits_dst, c.vocab, d->stats, d->n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st);
         default: return pie::fail(PIE_E_ARG, "pie_decoder: unknown kernel id");
     }
@@ -375,7 +397,7 @@ int pie_decoder_destroy(pie_decoder *d) {
     drop_graphs(d);
     prefill_free(d);
     void *ptrs[] = {d->state, d->kv_table, d->qbuf, d->attn, d->act, d->part_acc, d->part_ml, d->stats, d->rope_cs, d->pf_sink, d->seam, d->tp_part, d->kv_stage, d->kv_table_stage,
-                    d->zero_table, d->kvq_scratch, d->kvq_table, d->ring_rows};
+                    d->zero_table, d->kvq_scratch, d->kvq_table, d->ring_rows, d->tail_stats};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete d;
@@ -653,11 +675,22 @@ int pie_decoder_graph_launches(const pie_decoder *d, int flags) {
     return d->graph[gi] ? d->graph_kernels[gi] : -1;
 }
 
+}  // extern "C"
+namespace {
+struct RawTail {  // pie_decoder::tail_raw for the duration of one prompt pass
+    pie_decoder *d;
+    RawTail(pie_decoder *dec, bool raw) : d(dec) { d->tail_raw = raw; }
+    ~RawTail() { d->tail_raw = false; }
+};
+}  // namespace
+extern "C" {
+
 int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_all, void *stream) {
     int rc = ready(d);
     if (rc) return rc;
     PIE_REQUIRE(ids && L > 0, PIE_E_ARG, "pie_decoder_prefill: need at least one token");
     hipStream_t st = (hipStream_t)stream;
+    const RawTail raw(d, logits_all != nullptr);  // logits on every position: raw, whatever tail is configured
     // a tensor-parallel shard feeds its prompt through the step kernels (2 all-reduces per layer and token); the many-row GEMM
     // path has no collective yet
     // int8 pages: the batched prompt path of ONE sequence reads and writes T pages; such prompts run as decode steps here (fresh prompts go
@@ -683,6 +716,7 @@ int pie_decoder_prefill_embeds(pie_decoder *d, const void *embeds, int L, void *
     PIE_REQUIRE(pie_aligned(embeds, 16), PIE_E_ALIGN, "pie_decoder_prefill_embeds: 16-byte alignment required");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_prefill_embeds: not available on a tensor-parallel shard");
     hipStream_t st = (hipStream_t)stream;
+    const RawTail raw(d, logits_all != nullptr);
     // (one row on a rotating cache is a single-row update: the decode step below, as in rotating.py)
     if (!(d->kv_i8 && d->block_table) && !(d->ring && L == 1)) return prefill_batched(d, nullptr, embeds, L, logits_all, st);
     // int8 pages: the batched prompt path of one sequence reads and writes T pages, so -- like a prompt of tokens (pie_decoder_prefill) -- the rows
@@ -743,6 +777,41 @@ int pie_decoder_configure(pie_decoder *d, int option, int value) {
     d->kv_i8 = value != 0;
     plan_attention(d);
     drop_graphs(d);
+    return PIE_OK;
+}
+
+int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_size, int32_t *ids_by_pos, int ids_cap) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logits_penalty: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logits_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    PIE_REQUIRE(penalty >= 0.0 && std::isfinite(penalty), PIE_E_ARG, "pie_decoder_set_logits_penalty: the penalty must be finite and non-negative");
+    PIE_REQUIRE(context_size >= 0 && context_size <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_logits_penalty: context_size must be 1..1024 (0: off)");
+    if (penalty == 1.0 || context_size == 0) penalty = 1.0, context_size = 0, ids_by_pos = nullptr, ids_cap = 0;
+    else PIE_REQUIRE(ids_by_pos && ids_cap >= 1 && pie_aligned(ids_by_pos, 4), PIE_E_ARG, "pie_decoder_set_logits_penalty: ids_by_pos must hold at least one id");
+    if (penalty != 1.0 && !d->tail_stats) {
+        const int rc = dev_alloc((void **)&d->tail_stats, sizeof(LogitStat) * TAIL_STAT_TILES);
+        if (rc) return rc;
+    }
+    const bool changed = d->pen != penalty || d->pen_ctx != context_size || d->ids_by_pos != ids_by_pos || d->ids_cap != ids_cap;
+    d->pen = penalty, d->pen_ctx = context_size, d->ids_by_pos = ids_by_pos, d->ids_cap = ids_cap;
+    if (changed) drop_graphs(d);  // every one of them is a launch argument
+    return PIE_OK;
+}
+
+int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
+                            void *workspace, size_t workspace_bytes) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_sampler: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_sampler: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (mode == PIE_SAMPLE_GREEDY) {
+        if (d->smp_mode != PIE_SAMPLE_GREEDY) drop_graphs(d);
+        d->smp_mode = PIE_SAMPLE_GREEDY, d->smp_counter = nullptr, d->smp_ws = nullptr;
+        return PIE_OK;
+    }
+    PIE_REQUIRE(counter && workspace, PIE_E_ARG, "pie_decoder_set_sampler: null pointer");
+    if (int rc = sample_check("pie_decoder_set_sampler", d->cfg.vocab, mode, temp, p, k, workspace)) return rc;
+    PIE_REQUIRE(workspace_bytes >= pie_sample_workspace_bytes(1, d->cfg.vocab), PIE_E_SHAPE, "pie_decoder_set_sampler: the workspace is smaller than pie_sample_workspace_bytes(1, vocab)");
+    const bool changed = d->smp_mode != mode || d->smp_temp != temp || d->smp_p != p || d->smp_k != k || d->smp_seed != seed || d->smp_counter != counter || d->smp_ws != workspace;
+    d->smp_mode = mode, d->smp_temp = temp, d->smp_p = p, d->smp_k = k, d->smp_seed = seed, d->smp_counter = counter, d->smp_ws = workspace;
+    if (changed) drop_graphs(d);
     return PIE_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include "attention.hpp"
 #include "kv_quant.hpp"
+#include "sampler.hpp"
 #include "tail.hpp"
 #include "w4_gemv.hpp"
 
@@ -73,6 +74,18 @@ struct pie_decoder {
     bool ring = false;
     int ring_w = 0, ring_row0 = 0;  // window; buffer row of the next prompt pass's first row (host copy of ring_rows->pos at bind time)
     DecState *ring_rows = nullptr;
+    // The configured tail (pie_decoder_set_logits_penalty / _set_sampler): applied where the tail writes the bound outputs and
+    // tail_raw is false (a prompt pass asked for logits on every position keeps raw logits and the greedy tail).  All launch arguments.
+    double pen = 1.0;  // 1.0: off
+    int pen_ctx = 0, ids_cap = 0;
+    int *ids_by_pos = nullptr;        // caller-owned
+    LogitStat *tail_stats = nullptr;  // [TAIL_STAT_TILES] partials of the penalised logits (owned, allocated when a penalty is first set)
+    int smp_mode = PIE_SAMPLE_GREEDY, smp_k = 0;
+    double smp_temp = 1.0, smp_p = 0.0;
+    unsigned long long smp_seed = 0, *smp_counter = nullptr;
+    void *smp_ws = nullptr;
+    bool tail_raw = false;
+    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)

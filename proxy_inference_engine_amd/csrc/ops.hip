@@ -1,6 +1,8 @@
 // ops.hip -- op-level entry points that are not the W4S GEMV: attention (decode), RMSNorm, RoPE,
 // SiLU*mul, residual add, and the log-softmax / argmax tail.  One C-ABI function per MLX op the reference
 // calls on the decode path (see include/pie_hip.h for the call sites).
+#include <cmath>
+
 #include "attention.hpp"
 #include "tail.hpp"
 
@@ -336,6 +338,16 @@ int pie_logprobs_argmax(const void *logits, int V, int dtype, float *logprobs, i
     PIE_REQUIRE(logits && logprobs && token, PIE_E_ARG, "pie_logprobs_argmax: null pointer");
     PIE_REQUIRE(V > 0, PIE_E_SHAPE, "pie_logprobs_argmax: empty vocabulary");
     return logits_tail_launch(dtype, (const u16 *)logits, V, nullptr, 0, logprobs, token, nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+int pie_logits_penalty(void *logits, int V, int dtype, const int32_t *ids, int n, double penalty, void *stream) {
+    PIE_REQUIRE(logits && ids, PIE_E_ARG, "pie_logits_penalty: null pointer");
+    PIE_REQUIRE(penalty >= 0.0 && std::isfinite(penalty), PIE_E_ARG, "pie_logits_penalty: the penalty must be finite and non-negative");
+    PIE_REQUIRE(n >= 1 && n <= PEN_MAX_IDS, PIE_E_ARG, "pie_logits_penalty: 1 <= n <= 1024 ids");
+    PIE_REQUIRE(V >= 1, PIE_E_SHAPE, "pie_logits_penalty: empty vocabulary");
+    PenArgs a = {};
+    a.logits = (u16 *)logits, a.V = V, a.penalty = (float)penalty, a.ids = ids, a.n = n;
+    return logits_penalty_launch(dtype, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 //     by the last workgroup, so a captured graph keeps drawing fresh numbers.  The random stream is this library's own, not MLX's:
 //     parity is the kept-token set and the distribution.
 #include "common.hpp"
+#include "sampler.hpp"
 
 namespace {
 
@@ -73,6 +74,10 @@ struct SmpArgs {
     unsigned long long *ws;       // rows x smp_row_words(gridDim.x)
     int *token_out, *kept_count;
     unsigned char *kept_mask;
+    // the decode step's tail (rows = 1): the drawn id also becomes the step's fed-back token and history[*feed_pos]; null elsewhere
+    int *feed_token, *history;
+    const int *feed_pos;
+    int hist_cap;
 };
 
 // The selection runs in ASCENDING key order with an integer target: the answer is the smallest key T with
@@ -313,7 +318,13 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a) {
         const unsigned long long arr = atomicAdd(ws + H_ARRIVE, 1ull | ((unsigned long long)kept << 32)) + (1ull | ((unsigned long long)kept << 32));
         if ((unsigned)arr == G) {  // last workgroup of the row
             const unsigned long long win = __hip_atomic_load(ws + H_BEST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.token_out[row] = (int)~(unsigned)win;
+            const int tok = (int)~(unsigned)win;
+            a.token_out[row] = tok;
+            if (a.feed_token) {
+                *a.feed_token = tok;
+                const int pos = *a.feed_pos;  // already advanced by the tail: the position the drawn token will occupy
+                if (a.history && pos >= 0 && pos < a.hist_cap) a.history[pos] = tok;
+            }
             if (a.kept_count) a.kept_count[row] = (int)(arr >> 32);
             ws[H_MAXKEY] = 0;  // ready for the next call's atomic max
             const unsigned long long rows_done = atomicAdd(a.counter + 1, 1ull) + 1;
@@ -323,6 +334,43 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a) {
 }
 
 }  // namespace
+
+int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace) {
+    const std::string w(who);
+    PIE_REQUIRE(V >= 1 && V <= SMP_MAX_WGS * SMP_SLICE, PIE_E_SHAPE, w + ": rows >= 1 and 1 <= V <= 524288");
+    PIE_REQUIRE(pie_aligned(workspace, 8), PIE_E_ALIGN, w + ": workspace needs 8-byte alignment");
+    PIE_REQUIRE(mode >= SMP_CATEGORICAL && mode <= SMP_MIN_P, PIE_E_ARG, w + ": unknown mode");
+    PIE_REQUIRE(temp > 0.0, PIE_E_ARG, w + ": temperature must be positive (temp = 0 is the greedy tail, pie_logprobs_argmax)");
+    // the reference's own argument checks (top_k.py:20-24, min_p.py:30-40)
+    PIE_REQUIRE(mode != SMP_TOP_K || (k > 0 && k < V), PIE_E_ARG, w + ": `top_k` has to be an integer in the (0, V) interval");
+    PIE_REQUIRE(mode != SMP_MIN_P || (p > 0.0 && p <= 1.0), PIE_E_ARG, w + ": `min_p` has to be a float in the (0, 1] interval");
+    PIE_REQUIRE(mode != SMP_MIN_P || (k >= 1 && k <= V), PIE_E_ARG, w + ": `min_tokens_to_keep` has to be a positive integer");
+    PIE_REQUIRE(mode != SMP_TOP_P || (p > 0.0 && p < 1.0), PIE_E_ARG, w + ": `top_p` has to be in (0, 1) (samplers/__init__.py:39)");
+    return PIE_OK;
+}
+
+// pie_sample's launches (arguments already checked: sample_check): 2 (categorical, min-p that keeps one) or 5
+int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
+                  void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st) {
+    SmpArgs a = {};
+    a.logprobs = logprobs, a.V = V, a.mode = mode, a.seed = seed, a.counter = counter, a.ws = (unsigned long long *)workspace;
+    a.token_out = tokens, a.kept_count = kept_count, a.kept_mask = kept_mask;
+    a.feed_token = feed.token, a.feed_pos = feed.pos, a.history = feed.history, a.hist_cap = feed.hist_cap;
+    // Python scalars enter the reference's fp32 arithmetic as the fp32 value of the double expression: 1 / temperature, 1 - top_p, log(min_p)
+    a.inv_temp = (float)(1.0 / temp);
+    a.thr = mode == SMP_TOP_P ? (float)(1.0 - p) : (mode == SMP_MIN_P ? (float)log(p) : 0.0f);
+    a.k = mode == SMP_TOP_K || mode == SMP_MIN_P ? k : 0;
+    const dim3 grid((unsigned)((V + SMP_SLICE - 1) / SMP_SLICE), (unsigned)rows), block(SMP_T);
+    hipLaunchKernelGGL(k_smp_init, grid, block, 0, st, a);
+    if (mode == SMP_TOP_P || mode == SMP_TOP_K || (mode == SMP_MIN_P && k > 1)) {
+        hipLaunchKernelGGL(k_smp_digit<0>, grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_smp_digit<1>, grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_smp_digit<2>, grid, block, 0, st, a);
+    }
+    hipLaunchKernelGGL(k_smp_draw, grid, block, 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
 
 extern "C" {
 
@@ -335,33 +383,10 @@ size_t pie_sample_workspace_bytes(int rows, int V) {
 int pie_sample(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                void *workspace, int32_t *tokens, int32_t *kept_count, unsigned char *kept_mask, void *stream) {
     PIE_REQUIRE(logprobs && counter && tokens && workspace, PIE_E_ARG, "pie_sample: null pointer");
-    PIE_REQUIRE(rows >= 1 && V >= 1 && V <= SMP_MAX_WGS * SMP_SLICE, PIE_E_SHAPE, "pie_sample: rows >= 1 and 1 <= V <= 524288");
-    PIE_REQUIRE(pie_aligned(workspace, 8), PIE_E_ALIGN, "pie_sample: workspace needs 8-byte alignment");
-    PIE_REQUIRE(mode >= SMP_CATEGORICAL && mode <= SMP_MIN_P, PIE_E_ARG, "pie_sample: unknown mode");
-    PIE_REQUIRE(temp > 0.0, PIE_E_ARG, "pie_sample: temperature must be positive (temp = 0 is the greedy tail, pie_logprobs_argmax)");
-    // the reference's own argument checks (top_k.py:20-24, min_p.py:30-40)
-    PIE_REQUIRE(mode != SMP_TOP_K || (k > 0 && k < V), PIE_E_ARG, "pie_sample: `top_k` has to be an integer in the (0, V) interval");
-    PIE_REQUIRE(mode != SMP_MIN_P || (p > 0.0 && p <= 1.0), PIE_E_ARG, "pie_sample: `min_p` has to be a float in the (0, 1] interval");
-    PIE_REQUIRE(mode != SMP_MIN_P || (k >= 1 && k <= V), PIE_E_ARG, "pie_sample: `min_tokens_to_keep` has to be a positive integer");
-    PIE_REQUIRE(mode != SMP_TOP_P || (p > 0.0 && p < 1.0), PIE_E_ARG, "pie_sample: `top_p` has to be in (0, 1) (samplers/__init__.py:39)");
-    SmpArgs a = {};
-    a.logprobs = logprobs, a.V = V, a.mode = mode, a.seed = seed, a.counter = counter, a.ws = (unsigned long long *)workspace;
-    a.token_out = tokens, a.kept_count = kept_count, a.kept_mask = kept_mask;
-    // Python scalars enter the reference's fp32 arithmetic as the fp32 value of the double expression: 1 / temperature, 1 - top_p, log(min_p)
-    a.inv_temp = (float)(1.0 / temp);
-    a.thr = mode == SMP_TOP_P ? (float)(1.0 - p) : (mode == SMP_MIN_P ? (float)log(p) : 0.0f);
-    a.k = mode == SMP_TOP_K || mode == SMP_MIN_P ? k : 0;
-    const dim3 grid((unsigned)((V + SMP_SLICE - 1) / SMP_SLICE), (unsigned)rows), block(SMP_T);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_smp_init, grid, block, 0, st, a);
-    if (mode == SMP_TOP_P || mode == SMP_TOP_K || (mode == SMP_MIN_P && k > 1)) {
-        hipLaunchKernelGGL(k_smp_digit<0>, grid, block, 0, st, a);
-        hipLaunchKernelGGL(k_smp_digit<1>, grid, block, 0, st, a);
-        hipLaunchKernelGGL(k_smp_digit<2>, grid, block, 0, st, a);
-    }
-    hipLaunchKernelGGL(k_smp_draw, grid, block, 0, st, a);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+    PIE_REQUIRE(rows >= 1, PIE_E_SHAPE, "pie_sample: rows >= 1 and 1 <= V <= 524288");
+    if (int rc = sample_check("pie_sample", V, mode, temp, p, k, workspace)) return rc;
+    SampleFeed none = {};
+    return sample_launch(logprobs, rows, V, mode, temp, p, k, seed, counter, workspace, tokens, kept_count, kept_mask, none, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,17 @@
+// sampler.hpp -- pie_sample's launch sequence for callers inside the library (sampler.hip): the decode step's tail draws with it.
+#pragma once
+#include "common.hpp"
+
+// Where the decode step's tail wants the drawn id besides `tokens` (rows = 1): the device-side state's fed-back token and the token history
+// at the (already advanced) position *pos.  All null: a plain pie_sample.
+struct SampleFeed {
+    int *token;
+    const int *pos;
+    int *history;
+    int hist_cap;
+};
+
+// pie_sample's argument checks, reported under `who`; nothing is launched
+int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace);
+int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
+                  void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st);

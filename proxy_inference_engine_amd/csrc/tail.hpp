@@ -154,3 +154,68 @@ static inline int logits_tail_launch(int dtype, const u16 *logits, int V, const 
     if (tmp) PIE_HIP_TRY(hipFreeAsync(tmp, st));
     return PIE_OK;
 }
+
+// ---------------------------------------------------------------- repetition penalty (logits_processors/repetition.py:11-22)
+// logits[id] = T(x < 0 ? x * penalty : x / penalty), x = f32(logits[id]), once for every distinct id of a window of at most PEN_MAX_IDS token
+// ids: the reference gathers, computes and scatters, so an id that occurs several times is penalised once.  One workgroup, a thread per
+// window entry; an entry owns its id when no earlier entry holds it.  Ids outside [0, V) are skipped, never indexed.
+// The window is either ids[0..n) (the op, pie_logits_penalty) or -- state != nullptr, the decode step's tail -- the positions
+// max(0, pos + 1 - context) .. pos of ids_by_pos, pos = state->pos: the ids the model was fed, the row's own input included
+// (prompt_cache.update(ids) runs before the processors, inference_engine.py:255-266).  record: the step's input token is state->token
+// (fed back by the previous tail, or set by the caller): it is written to ids_by_pos[pos] first, so fed-back tokens never visit the host.
+// Every index into ids_by_pos is checked against ids_cap here.
+constexpr int PEN_MAX_IDS = 1024;
+
+struct PenArgs {
+    u16 *logits;
+    int V;
+    float penalty;
+    const int *ids;  // the op's window
+    int n;
+    int *ids_by_pos;  // the step's window
+    int ids_cap, context;
+    const DecState *state;
+    int record;
+};
+
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty(const PenArgs a) {
+    __shared__ int s_ids[PEN_MAX_IDS];
+    const int t = threadIdx.x;
+    int n = a.n, id = -1;
+    if (a.state) {
+        const int pos = a.state->pos, lo = pos + 1 - a.context > 0 ? pos + 1 - a.context : 0;
+        n = pos + 1 - lo;  // <= context <= PEN_MAX_IDS
+        const int p = lo + t;
+        if (t < n && p >= 0 && p < a.ids_cap) {
+            if (a.record && p == pos) id = a.state->token, a.ids_by_pos[p] = id;
+            else id = a.ids_by_pos[p];
+        }
+    } else if (t < n) {
+        id = a.ids[t];
+    }
+    s_ids[t] = id;
+    __syncthreads();
+    if (t >= n || id < 0 || id >= a.V) return;
+    for (int j = 0; j < t; ++j)
+        if (s_ids[j] == id) return;  // an earlier entry owns this id
+    const float x = T::to_f32(a.logits[id]);
+    a.logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, a.penalty) : __fdiv_rn(x, a.penalty));  // -0.0 is not < 0: divided
+}
+
+static inline int logits_penalty_launch(int dtype, const PenArgs &a, hipStream_t st) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits penalty: dtype must be PIE_BF16 or PIE_F16");
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_penalty<BF16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a);
+    else hipLaunchKernelGGL(k_logits_penalty<F16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// The per-tile partials of `logits` as pie_logprobs_argmax computes them (k_logits_stats over TAIL_STAT_TILES tiles), into caller-owned
+// scratch: the step's tail after a penalty, whose lm_head epilogue partials are stale.
+static inline int logits_stats_launch(int dtype, const u16 *logits, int V, LogitStat *stats, hipStream_t st) {
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_stats<BF16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats);
+    else hipLaunchKernelGGL(k_logits_stats<F16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}

@@ -49,6 +49,28 @@ def check_generate_mask(mask, n_heads: int | None = None) -> None:
         raise ValueError("generate_step(mask=additive array): a non-finite entry hides every key of its rows (softmax of an empty row)")
 
 
+def fused_tail_spec(processors, sampler, structuring_engine=None, tensor_parallel: bool = False):
+    """Whether one _inference call can end inside the decode step's configured tail (Model.set_step_tail), and with what:
+    returns (sampler spec or None, repetition_penalty, context_size) -- set_step_tail's arguments -- or None for the host-orchestrated
+    branches.  Fused: no structuring engine (its hooks are host callables), processors empty or exactly the one repetition-penalty
+    processor with 1 <= context_size <= 1024 (context_size 0 means the whole history upstream, tokens[-0:]), a sampler that is greedy or
+    carries a `hip_spec` (make_sampler's own closures), and a model that is not tensor-parallel (vocabulary-parallel tail)."""
+    if structuring_engine is not None or tensor_parallel:
+        return None
+    procs = list(processors or [])
+    penalty, context_size = 1.0, 60
+    if procs:
+        if len(procs) != 1 or not hasattr(procs[0], "penalty") or not hasattr(procs[0], "context_size"):
+            return None
+        penalty, context_size = float(procs[0].penalty), int(procs[0].context_size)
+        if not 1 <= context_size <= 1024:
+            return None
+    if getattr(sampler, "is_greedy", False):
+        return None, penalty, context_size
+    spec = getattr(sampler, "hip_spec", None)
+    return None if spec is None else (tuple(spec), penalty, context_size)
+
+
 class InferenceEngine:
     """One model, one PromptCache, not re-entrant -- like the reference (server/app.py:23,35)."""
 
@@ -137,6 +159,26 @@ class InferenceEngine:
             procs = self.logits_processors.get(state) or []
             if kv_bits is not None:
                 self._maybe_quantize(quantized_kv_start, kv_group_size, kv_bits)
+            set_tail = getattr(self.model, "set_step_tail", None)
+            spec = fused_tail_spec(procs, sampler, self.structuring_engine, getattr(self.model, "tp", None) is not None) if set_tail is not None else None
+            offset = int(self.prompt_cache.cache[0].offset) if self.prompt_cache.cache else 0
+            if spec is not None and offset + int(ids.numel()) <= self.model.fed_ids.numel():
+                # The whole tail inside the step: penalty, log-softmax and the draw ride the replayed graph; the drawn token
+                # is fed back on the device, so a fed-back step passes nothing, whatever the sampler
+                penalised = spec[1] != 1.0
+                if penalised and not fed_back and offset > 0:  # a reused prefix: its ids may predate this configuration (fed back unrecorded, loaded from disk)
+                    seen = self.prompt_cache.computed_ids[-min(offset, spec[2]):]
+                    self.model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
+                set_tail(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2])
+                if pixel_values is not None and not fed_back:
+                    embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
+                    tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)
+                else:
+                    tok, logprobs, _ = self.model.step(None if fed_back else ids, self.prompt_cache.cache)
+                self.prompt_cache.update(ids)                                  # :255 (device ids resolve lazily)
+                return tok, logprobs
+            if set_tail is not None:
+                set_tail()  # the host-orchestrated branches below run on Model.step's documented greedy tail
             if pixel_values is not None and not fed_back:
                 # the prompt of a VLM request (:246-252): text embeddings with the image features scattered in, through the
                 # text tower.  The reference passes pixel_values on every later step too, where a single new token holds

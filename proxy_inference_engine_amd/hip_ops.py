@@ -470,6 +470,17 @@ def logprobs_argmax(logits: torch.Tensor):
     return tok, lp
 
 
+def logits_penalty(logits: torch.Tensor, ids: torch.Tensor, penalty: float) -> torch.Tensor:
+    """The repetition penalty (logits_processors/repetition.py:11-22) on 16-bit logits [V], IN PLACE: every distinct id of `ids` (device
+    int32, 1..1024 of them) once, x < 0 ? x * penalty : x / penalty in fp32, one rounding; ids outside [0, V) are skipped.  Returns logits."""
+    _dev(logits), _dev(ids)
+    if not logits.is_contiguous() or ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError("logits_penalty: contiguous logits and contiguous int32 ids")
+    _ffi.check(_ffi.load().pie_logits_penalty(_ffi.p(logits), logits.numel(), _ffi.dtype_code(logits.dtype), _ffi.p(ids), ids.numel(), float(penalty),
+                                              _ffi.stream()))
+    return logits
+
+
 def qkv_row_map(n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
     n = (n_heads + 2 * n_kv_heads) * head_dim
     arr = (C.c_int32 * n)()
@@ -702,12 +713,7 @@ def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: in
     if int(lib.pie_sample_workspace_bytes(rows, V)) == 0:  # V > 524288 (1024 workgroups of 512 ids) or an empty block: refused, nothing launched
         raise ValueError(f"sample: a [rows, V] block with rows >= 1 and 1 <= V <= 524288, got [{rows}, {V}]")
     seed, counter = _rng.hip_state(x.device)
-    key = (str(x.device), rows, V)
-    ws = _sample_ws.get(key)
-    if ws is None:  # zeroed once; the kernels leave it ready for the next call
-        if len(_sample_ws) > 8:
-            _sample_ws.clear()
-        ws = _sample_ws[key] = torch.zeros(int(lib.pie_sample_workspace_bytes(rows, V)) // 8, dtype=torch.int64, device=x.device)
+    ws = sample_workspace(x.device, rows, V)
     tokens = torch.empty(rows, dtype=torch.int32, device=x.device)
     kept = torch.empty(rows, dtype=torch.int32, device=x.device) if want_mask else None
     mask = torch.empty((rows, V), dtype=torch.uint8, device=x.device) if want_mask else None
@@ -717,6 +723,18 @@ def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: in
 
 
 _sample_ws: dict = {}
+
+
+def sample_workspace(device, rows: int, V: int) -> torch.Tensor:
+    """pie_sample's workspace for a [rows, V] block on `device`: zeroed once, the kernels leave it ready for the next call.  The decode
+    step's tail (Model.set_step_tail) draws through the same one, in stream order with sample()."""
+    key = (str(device), rows, V)
+    ws = _sample_ws.get(key)
+    if ws is None:
+        if len(_sample_ws) > 8:
+            _sample_ws.clear()
+        ws = _sample_ws[key] = torch.zeros(int(_ffi.load().pie_sample_workspace_bytes(rows, V)) // 8, dtype=torch.int64, device=device)
+    return ws
 
 
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)

@@ -1,7 +1,8 @@
 """Repetition penalty (mirror of logits_processors/repetition.py:6-24 of the reference).
 
-Only installed when repetition_penalty != 1.0 (engine/inference_engine.py:328-333), i.e. off the measured
-greedy path; it edits <= context_size logits in place, host-orchestrated on device tensors."""
+Only installed when repetition_penalty != 1.0 (engine/inference_engine.py:328-333); it edits <= context_size logits in place,
+host-orchestrated on device tensors.  The processor carries `.penalty` and `.context_size`: where it is a request's only processor the
+engine runs the same edit inside the decode step's tail (hip_ops.logits_penalty's kernel, Model.set_step_tail) and never calls it."""
 from __future__ import annotations
 
 from collections.abc import Callable
@@ -21,4 +22,5 @@ def make_repetition_penalty(penalty: float = 1.0, context_size: int = 60) -> Cal
             logits[:, idx] = sel
         return logits
 
+    repetition_penalty_processor.penalty, repetition_penalty_processor.context_size = float(penalty), int(context_size)
     return repetition_penalty_processor

@@ -109,5 +109,21 @@ class Model:
     def step(self, ids, cache, graph: bool = True):
         return self.language_model.step(ids, cache, graph)
 
-    def step_embeds(self, inputs_embeds, cache):
-        return self.language_model.step_embeds(inputs_embeds, cache)
+    def step_embeds(self, inputs_embeds, cache, ids=None):
+        return self.language_model.step_embeds(inputs_embeds, cache, ids)
+
+    # the step's configurable tail is the text tower's (llama/language.py: set_step_tail)
+    def set_step_tail(self, sampler=None, repetition_penalty: float = 1.0, context_size: int = 60) -> None:
+        self.language_model.set_step_tail(sampler, repetition_penalty, context_size)
+
+    @property
+    def step_tail(self):
+        return self.language_model.step_tail
+
+    @property
+    def fed_ids(self):
+        return self.language_model.fed_ids
+
+    @property
+    def tp(self):
+        return getattr(self.language_model, "tp", None)

@@ -118,6 +118,9 @@ def _dense(weights: dict, prefix: str, dtype: torch.dtype) -> torch.Tensor:
     return w
 
 
+_GREEDY_TAIL = (None, None, None)  # Model._tail: (sampler spec, (penalty, context_size), seed)
+
+
 class Model:
     def __init__(self, args: ModelArgs, weights: dict[str, torch.Tensor], kv_splits: int = 0, tp=None):
         """weights: the checkpoint in the layout models/utils.py:51-125 of the reference consumes (HF names,
@@ -289,6 +292,10 @@ class Model:
         self.history = torch.zeros(1 << 20, dtype=torch.int32, device=device)
         _ffi.check(lib.pie_decoder_bind_outputs(self._dec, _ffi.p(self.logits), _ffi.p(self.logprobs), _ffi.p(self.token), _ffi.p(self.hidden),
                                                 _ffi.p(self.history), self.history.numel()))
+        # the ids the model was fed, by position: the window of the step tail's repetition penalty (set_step_tail).  step / step_embeds /
+        # __call__ copy explicit ids in, device to device; the decode step records a fed-back token itself
+        self.fed_ids = torch.zeros(self.history.numel(), dtype=torch.int32, device=device)
+        self._tail = _GREEDY_TAIL
         self._kv = KVBinding(lib, self._dec, len(self.layers), self.n_kv_heads, self.head_dim, self.dtype, device, tensor_parallel=tp is not None)
         self._page_pool, self._page_blocks = None, 16
         self._batch_bufs: dict = {}
@@ -349,6 +356,46 @@ class Model:
         seq = PagedSequence(allocator, max_blocks)
         return [PagedKVCache(seq, i) for i in range(len(self.layers))]
 
+    # ------------------------------------------------------------------ the step's tail
+    def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60) -> None:
+        """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler), inside the replayed graph:
+        sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
+        samplers' random stream (samplers.seed) -- the returned token is then the drawn one; repetition_penalty != 1.0 with context_size
+        1..1024: the penalty over the last context_size fed ids (`fed_ids`), applied to the returned logits before the log-softmax.
+        The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
+        returning raw logits."""
+        pen = (float(repetition_penalty), int(context_size)) if repetition_penalty != 1.0 and context_size != 0 else None
+        seed = counter = None
+        if sampler is not None:
+            from ...samplers import _rng
+            seed, counter = _rng.hip_state(self.device)
+            sampler = (str(sampler[0]), float(sampler[1]), float(sampler[2]), int(sampler[3]))
+        tail = (sampler, pen, seed)
+        if tail == self._tail:
+            return
+        lib = _ffi.load()
+        if pen != self._tail[1]:
+            _ffi.check(lib.pie_decoder_set_logits_penalty(self._dec, pen[0] if pen else 1.0, pen[1] if pen else 0, _ffi.p(self.fed_ids), self.fed_ids.numel()))
+            self._tail = (self._tail[0], pen, self._tail[2])
+        if sampler is None:
+            _ffi.check(lib.pie_decoder_set_sampler(self._dec, _ffi.PIE_SAMPLE_GREEDY, 1.0, 0.0, 0, 0, None, None, 0))
+        else:
+            self._tail_ws = ws = hip_ops.sample_workspace(self.device, 1, self.logprobs.numel())  # (kept alive while the decoder points at it)
+            _ffi.check(lib.pie_decoder_set_sampler(self._dec, hip_ops.SAMPLE_MODES[sampler[0]], sampler[1], sampler[2], sampler[3], seed, _ffi.p(counter),
+                                                   _ffi.p(ws), ws.numel() * 8))
+        self._tail = tail
+
+    @property
+    def step_tail(self) -> tuple:
+        """(sampler or None, (penalty, context_size) or None): what set_step_tail last configured."""
+        return self._tail[:2]
+
+    def _feed(self, ids: torch.Tensor, offset: int) -> None:
+        """fed_ids[offset : offset + L] = ids (device int32 [L]); positions beyond the buffer are not recorded (the penalty's window skips them)."""
+        n = min(ids.numel(), self.fed_ids.numel() - offset)
+        if n > 0:
+            self.fed_ids[offset:offset + n].copy_(ids[:n])
+
     # ------------------------------------------------------------------ reference calling convention
     def __call__(self, inputs: torch.Tensor | None = None, mask=None, cache: list[BaseCache] | None = None,
                  inputs_embeds: torch.Tensor | None = None) -> torch.Tensor:
@@ -375,6 +422,7 @@ class Model:
             ids = inputs.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
             self._kv.sync(cache, L)
+            self._feed(ids, self._kv.offset)
             out = torch.empty((L, self.vocab_out), dtype=self.dtype, device=self.device)
             _ffi.check(lib.pie_decoder_prefill(self._dec, _ffi.p(ids), L, _ffi.p(out), _ffi.stream()))
         self._kv.advance(cache, L)
@@ -418,8 +466,9 @@ class Model:
             return hip_ops.embedding_dense(ids, self.embed_tokens[0])
         return hip_ops.embedding(ids, *self.embed_tokens, bits=self.bits, group_size=32 if self.group_size == 32 else 64)
 
-    def step_embeds(self, inputs_embeds: torch.Tensor, cache: list[BaseCache]):
+    def step_embeds(self, inputs_embeds: torch.Tensor, cache: list[BaseCache], ids: torch.Tensor | None = None):
         """`step` for a prompt given as embeddings: forwards the rows, lm_head + tail on the last one only.
+        ids: the token ids the rows were embedded from, recorded in `fed_ids` for the tail's repetition penalty.
         On an int8 page pool such a prompt runs as L decode steps (~1.2 ms per row on the 8B model: the batched single-sequence pass reads
         T pages and the several-prompts pass takes token ids only); warned about once."""
         emb = self._check_embeds(inputs_embeds)
@@ -429,6 +478,8 @@ class Model:
             self._warned_i8_embeds = True
         L = emb.shape[0]
         self._kv.sync(cache, L)
+        if ids is not None:
+            self._feed(ids.reshape(-1).to(device=self.device, dtype=torch.int32), self._kv.offset)
         _ffi.check(_ffi.load().pie_decoder_prefill_embeds(self._dec, _ffi.p(emb), L, None, _ffi.stream()))
         self._kv.advance(cache, L)
         pos = self._kv.offset
@@ -440,6 +491,7 @@ class Model:
         processors: forwards `ids` [L] (device int32) and returns (token[1], logprobs[V], logits[V]).
         `ids=None` feeds back the previous step's greedy token, which already sits in the decoder's device-side
         state (no copy, no host sync).  L == 1 replays the captured hipGraph.
+        After set_step_tail(...) the same call applies the repetition penalty and / or draws the token (and feeds THAT back).
         token is a view of the device-side history at the new position (stable); logprobs / logits are the
         decoder's output buffers, valid until the next call."""
         lib = _ffi.load()
@@ -449,7 +501,7 @@ class Model:
         else:
             ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0:
+            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None):  # (the several-prompts pass ends in the greedy tail only)
                 # A fresh prompt on int8 pages: the single-sequence prompt pass reads T pages (it would run the prompt as L decode steps,
                 # ~1.2 ms per token), the several-prompts pass quantises into int8 pages -- one prompt is a batch of one.
                 nxt, logprobs, logits = self.prefill_batch([ids.cpu().numpy()], [cache])  # (a prompt arrives once: the host copy is the pass's own row bookkeeping)
@@ -461,6 +513,7 @@ class Model:
                     return self.history[pos:pos + 1], logprobs[0], logits[0]
                 return nxt[:1].clone(), logprobs[0], logits[0]
             self._kv.sync(cache, L)
+            self._feed(ids, self._kv.offset)
             if L == 1:
                 _ffi.check(lib.pie_decoder_set_token_from(self._dec, _ffi.p(ids), _ffi.stream()))
         if L == 1:

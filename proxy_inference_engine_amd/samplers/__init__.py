@@ -42,16 +42,20 @@ def _argmax_f32(x: torch.Tensor) -> torch.Tensor:
 
 def make_sampler(temp: float = 0.0, top_p: float = 0.0, min_p: float = 0.0, min_tokens_to_keep: int = 1,
                  top_k: int = -1) -> Callable[[torch.Tensor], torch.Tensor]:
+    """The stochastic closures carry `hip_spec = (mode, temp, p, k)` -- hip_ops.sample's arguments -- so the engine can run the same
+    draw inside the decode step's tail (Model.set_step_tail) instead of calling the closure."""
     if temp == 0:
         return greedy
     elif top_p > 0 and top_p < 1.0:
-        return lambda x: top_p_sampling(x, top_p, temp)
+        sampler, spec = (lambda x: top_p_sampling(x, top_p, temp)), ("top_p", temp, top_p, 0)
     elif min_p != 0.0:
-        return lambda x: min_p_sampling(x, min_p, min_tokens_to_keep, temp)
+        sampler, spec = (lambda x: min_p_sampling(x, min_p, min_tokens_to_keep, temp)), ("min_p", temp, min_p, min_tokens_to_keep)
     elif top_k > 0:
-        return lambda x: top_k_sampling(x, top_k, temp)
+        sampler, spec = (lambda x: top_k_sampling(x, top_k, temp)), ("top_k", temp, 0.0, top_k)
     else:
-        return lambda x: categorical_sampling(x, temp)
+        sampler, spec = (lambda x: categorical_sampling(x, temp)), ("categorical", temp, 0.0, 0)
+    sampler.hip_spec = spec
+    return sampler
 
 
 greedy.is_greedy = True  # lets the engine pick the fused tail
