@@ -226,6 +226,49 @@ size_t pie_sample_workspace_bytes(int rows, int V);
 int pie_sample(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                void *workspace, int32_t *tokens, int32_t *kept_count, unsigned char *kept_mask, void *stream);
 
+/* ---------------------------------------------------------------- per-row tails
+ * One record per output row of a multi-sequence pass, in DEVICE memory: everything about a row's penalty and sampler that pie_sample and
+ * pie_logits_penalty take as arguments.  Nothing of it is a launch argument, so a captured graph keeps replaying while requests with
+ * different parameters come and go in its rows.
+ *   mode          PIE_SAMPLE_GREEDY (the row keeps the argmax already in tokens[r]) or one of the four PIE_SAMPLE_*
+ *   inv_temp, thr pie_sample's derived fp32 values: (float)(1 / temp); (float)(1 - top_p) or (float)log(min_p)
+ *   k             top_k, or min_tokens_to_keep
+ *   seed, calls   the row's own random stream: draw number `calls` of `seed`; the row's last draw workgroup advances `calls`
+ *   penalty       the repetition penalty as fp32; exactly 1.0: none
+ *   context_size  its window, 1..1024 positions
+ * pie_row_tail_pack fills a record in HOST memory from the arguments of pie_sample (mode, temp, p, k, seed) and pie_logits_penalty
+ * (penalty) with their argument rules (no vocabulary is known here: top_k > 0, min_tokens_to_keep >= 1; mode PIE_SAMPLE_GREEDY ignores
+ * temp, p and k), context_size 1..1024: PIE_E_ARG otherwise, nothing touches a device.  The kernels do not trust the bytes they read: an
+ * unknown mode acts as greedy, k is clamped to [1, V], context_size to [1, 1024], and every index is checked. */
+enum { PIE_SAMPLE_GREEDY = -1 };
+typedef struct pie_row_tail {
+    int32_t mode;
+    float inv_temp, thr;
+    int32_t k;
+    unsigned long long seed, calls;
+    float penalty;
+    int32_t context_size;
+} pie_row_tail;
+size_t pie_row_tail_bytes(void); /* sizeof(pie_row_tail), for bindings */
+int pie_row_tail_pack(int mode, double temp, double p, int k, unsigned long long seed, unsigned long long calls, double penalty, int context_size,
+                      pie_row_tail *out);
+/* pie_sample with per-row parameters: row r of logprobs [rows, V] is filtered and drawn exactly as pie_sample(logprobs + r * V, rows = 1, ...)
+ * with table[r]'s mode, temperature, p, k and seed and a counter of {table[r].calls, 0} -- the same token and kept mask, bit for bit; a
+ * request's stream depends on neither its row nor its neighbours.  table: DEVICE pie_row_tail [rows], 8-byte aligned; a drawn row's `calls`
+ * is advanced by one.  A greedy (or unknown-mode) row is left alone: its workspace, tokens[r], kept_count[r] and kept_mask row are not
+ * written.  Always 5 launches over a (V / 512, rows) grid; a workgroup whose row does not need a launch returns at once.  workspace:
+ * pie_sample_workspace_bytes(rows, V) bytes, zeroed once, reusable from call to call whatever the rows' modes become. */
+int pie_sample_rows(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int32_t *tokens, int32_t *kept_count,
+                    unsigned char *kept_mask, void *stream);
+/* pie_logits_penalty with per-row windows, one launch, one workgroup per row of logits [rows, V] T.  recent_ids: caller-owned DEVICE int32
+ * [rows, 1024], a ring per row: the id fed at position q lives at recent_ids[r][q & 1023].  ids / ctx: the pass's input ids and context
+ * lengths [n_src]; out_rows (nullable) [rows]: output row s reads source row i = out_rows ? out_rows[s] : s.  With pos = ctx[i] - 1 the
+ * kernel records ids[i] at recent_ids[s][pos & 1023], then penalises the distinct ids of positions max(0, pos + 1 - context_size) .. pos
+ * with pie_logits_penalty's arithmetic (the row's own input is inside the window, the token about to be chosen is not).  A row with
+ * pos < 0 (an idle slot) or i outside [0, n_src) is skipped; a row whose penalty is exactly 1.0 is recorded and not penalised. */
+int pie_logits_penalty_rows(void *logits, int rows, int V, int dtype, const pie_row_tail *table, int32_t *recent_ids, const int32_t *ids,
+                            const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream);
+
 /* ---------------------------------------------------------------- fused decode step
  * One forward of Model.__call__ (models/llama/language.py:199-210) for inputs[1,1] over per-layer
  * ReusableKVCache buffers (cache/kv_cache/reusable.py:96-142) followed by the tail of _inference
@@ -383,7 +426,7 @@ int pie_decoder_set_token_from(pie_decoder *d, const int32_t *token_dev, void *s
  * own partition, so logprobs and the greedy token are bit-identical with pie_logprobs_argmax of the bound logits) | finish | pie_sample's
  * launches over the bound logprobs; the drawn id becomes *token, the fed-back token and history[new position].  Any cache kind; refused
  * (PIE_E_STATE) on tensor-parallel decoders, whose tail is vocabulary-parallel.  pie_decoder_step_batch / _prefill_batch / _step_mixed ignore
- * it.  A change of either setting (the seed included: it is a launch argument) drops the captured graphs; with neither set the step is
+ * it (their own tail: pie_decoder_set_batch_tail).  A change of either setting (the seed included: it is a launch argument) drops the captured graphs; with neither set the step is
  * exactly the unconfigured one.
  * pie_decoder_set_logits_penalty: pie_logits_penalty over the ids the model was fed at positions max(0, p + 1 - context_size) .. p, p = the
  *   position the tail processes (the row's own input id included, the token about to be chosen not: prompt_cache.update runs before the
@@ -394,10 +437,26 @@ int pie_decoder_set_token_from(pie_decoder *d, const int32_t *token_dev, void *s
  * pie_decoder_set_sampler: mode PIE_SAMPLE_GREEDY restores the greedy tail; otherwise pie_sample's modes, argument checks, random stream
  *   (seed, DEVICE counter) and workspace (pie_sample_workspace_bytes(1, vocab) bytes, zeroed once by the caller), all caller-owned and
  *   alive while set. */
-enum { PIE_SAMPLE_GREEDY = -1 };
 int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_size, int32_t *ids_by_pos, int ids_cap);
 int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                             void *workspace, size_t workspace_bytes);
+/* The multi-sequence passes' tail: per-row penalties and samplers inside pie_decoder_step_batch (eager or PIE_STEP_GRAPH),
+ * pie_decoder_prefill_batch and pie_decoder_step_mixed.  table: DEVICE pie_row_tail [rows_cap], record s belongs to output row s (in the
+ * two prompt passes the decoding rows first, then prompt j at n_decode + j: a request's first token is drawn by its own sampler);
+ * recent_ids: DEVICE int32 [rows_cap, 1024]; workspace: pie_sample_workspace_bytes(rows_cap, vocab) bytes, zeroed once; all caller-owned
+ * and alive while set.  With a table set the passes end in: lm_head | pie_logits_penalty_rows on the output logits (input ids and context
+ * lengths: tokens / context_lens, or ids / row_context_lens / out_rows) | the unchanged log-softmax + argmax over every row |
+ * pie_sample_rows into next_tokens.  logits then hold the processed logits and logprobs their log-softmax, each row bit-identical with
+ * pie_logits_penalty + pie_logprobs_argmax + a one-row pie_sample of that row.  The records' CONTENTS may change between calls (the host
+ * writes them in stream order) and a captured step keeps replaying; the three addresses and rows_cap are part of the captured graph's key.
+ * table == NULL switches the tail off: the passes then launch exactly what they launch without it.  A pass with more output rows than
+ * rows_cap is PIE_E_SHAPE before any launch; a misaligned table or workspace (8 bytes) or ring (4) PIE_E_ALIGN; tensor-parallel decoders
+ * refuse the setter (PIE_E_STATE).  pie_decoder_batch_graph_replays: how many pie_decoder_step_batch calls so far were served by
+ * replaying the captured graph (tests assert the replay branch with it); pie_decoder_batch_graph_launches: the kernel nodes of the
+ * graph captured last (-1: none yet), what one replayed step launches. */
+int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap, int32_t *recent_ids, void *workspace);
+unsigned long long pie_decoder_batch_graph_replays(const pie_decoder *d);
+int pie_decoder_batch_graph_launches(const pie_decoder *d);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -45,6 +45,7 @@ EXPORTS = [
     "pie_kv_quantize", "pie_attn_decode_quant", "pie_decoder_set_kv_quant",
     "pie_decoder_set_kv_ring", "pie_kv_ring_order", "pie_sdpa_prefill_window", "pie_sdpa_decode_ring",
     "pie_logits_penalty", "pie_decoder_set_logits_penalty", "pie_decoder_set_sampler",
+    "pie_row_tail_bytes", "pie_row_tail_pack", "pie_sample_rows", "pie_logits_penalty_rows", "pie_decoder_set_batch_tail", "pie_decoder_batch_graph_replays", "pie_decoder_batch_graph_launches",
 ]
 
 
@@ -66,6 +67,12 @@ class pie_global_weights(C.Structure):
     _fields_ = [("embed_codes", C.c_void_p), ("embed_scales", C.c_void_p), ("embed_biases", C.c_void_p),
                 ("final_norm", C.c_void_p), ("lm_head", C.c_void_p), ("rope_freqs", C.c_void_p),
                 ("fmt_embed", C.c_int), ("fmt_lm_head", C.c_int)]
+
+
+class pie_row_tail(C.Structure):
+    """One output row's penalty and sampler in device memory (include/pie_hip.h)."""
+    _fields_ = [("mode", C.c_int32), ("inv_temp", C.c_float), ("thr", C.c_float), ("k", C.c_int32), ("seed", C.c_uint64), ("calls", C.c_uint64),
+                ("penalty", C.c_float), ("context_size", C.c_int32)]
 
 
 def set_knob(name: str, value: int | None) -> None:
@@ -124,6 +131,15 @@ def load() -> C.CDLL:
     lib.pie_decoder_set_logits_penalty.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int]
     lib.pie_decoder_set_sampler.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.pie_sample_workspace_bytes.restype = C.c_size_t
+    lib.pie_row_tail_bytes.restype = C.c_size_t
+    lib.pie_row_tail_bytes.argtypes = []
+    lib.pie_row_tail_pack.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.c_double, C.c_int, C.POINTER(pie_row_tail)]
+    lib.pie_sample_rows.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    lib.pie_logits_penalty_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    lib.pie_decoder_set_batch_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_decoder_batch_graph_replays.argtypes = [C.c_void_p]
+    lib.pie_decoder_batch_graph_replays.restype = C.c_uint64
+    lib.pie_decoder_batch_graph_launches.argtypes = [C.c_void_p]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

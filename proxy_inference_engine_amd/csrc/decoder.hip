@@ -815,6 +815,23 @@ int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int
     return PIE_OK;
 }
 
+int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap, int32_t *recent_ids, void *workspace) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_tail: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_tail: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (!table) {
+        d->bt_table = nullptr, d->bt_rows_cap = 0, d->bt_recent = nullptr, d->bt_ws = nullptr;
+        return PIE_OK;
+    }
+    PIE_REQUIRE(recent_ids && workspace, PIE_E_ARG, "pie_decoder_set_batch_tail: null pointer");
+    PIE_REQUIRE(pie_aligned(recent_ids, 4), PIE_E_ALIGN, "pie_decoder_set_batch_tail: the ring needs 4-byte alignment");
+    if (int rc = sample_rows_check("pie_decoder_set_batch_tail", rows_cap, d->cfg.vocab, table, workspace)) return rc;
+    d->bt_table = table, d->bt_rows_cap = rows_cap, d->bt_recent = recent_ids, d->bt_ws = workspace;  // (the batch graph's key holds them: no graph to drop)
+    return PIE_OK;
+}
+
+unsigned long long pie_decoder_batch_graph_replays(const pie_decoder *d) { return d ? d->batch_replays : 0; }
+int pie_decoder_batch_graph_launches(const pie_decoder *d) { return d ? d->batch_graph_kernels : -1; }
+
 int pie_decoder_set_comm(pie_decoder *d, pie_comm *c) {
     PIE_REQUIRE(d && c, PIE_E_ARG, "pie_decoder_set_comm: null pointer");
     int rank = 0, world = 0;

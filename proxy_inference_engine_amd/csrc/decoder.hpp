@@ -85,6 +85,14 @@ struct pie_decoder {
     unsigned long long smp_seed = 0, *smp_counter = nullptr;
     void *smp_ws = nullptr;
     bool tail_raw = false;
+    // The multi-sequence passes' tail (pie_decoder_set_batch_tail): per-row records, rings and sampler workspace, caller-owned.
+    // bt_table == nullptr: off.  The passes read the records on the device only; the addresses are in the captured batch graph's key.
+    pie_row_tail *bt_table = nullptr;
+    int bt_rows_cap = 0;
+    int *bt_recent = nullptr;
+    void *bt_ws = nullptr;
+    unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
+    int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
     bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)

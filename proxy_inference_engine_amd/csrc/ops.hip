@@ -350,4 +350,15 @@ int pie_logits_penalty(void *logits, int V, int dtype, const int32_t *ids, int n
     return logits_penalty_launch(dtype, a, (hipStream_t)stream);
 }
 
+int pie_logits_penalty_rows(void *logits, int rows, int V, int dtype, const pie_row_tail *table, int32_t *recent_ids, const int32_t *ids,
+                            const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream) {
+    PIE_REQUIRE(logits && table && recent_ids && ids && ctx, PIE_E_ARG, "pie_logits_penalty_rows: null pointer");
+    PIE_REQUIRE(rows >= 1 && rows <= 65535 && n_src >= 1 && V >= 1, PIE_E_SHAPE, "pie_logits_penalty_rows: 1 <= rows <= 65535, n_src >= 1, V >= 1");
+    PIE_REQUIRE(out_rows || n_src >= rows, PIE_E_SHAPE, "pie_logits_penalty_rows: without out_rows every output row needs its source row");
+    PIE_REQUIRE(pie_aligned(table, 8) && pie_aligned(recent_ids, 4), PIE_E_ALIGN, "pie_logits_penalty_rows: misaligned table or ring");
+    PenRowsArgs a = {};
+    a.logits = (u16 *)logits, a.V = V, a.n_src = n_src, a.table = table, a.recent = recent_ids, a.ids = ids, a.ctx = ctx, a.out_rows = out_rows;
+    return logits_penalty_rows_launch(dtype, a, rows, (hipStream_t)stream);
+}
+
 }  // extern "C"

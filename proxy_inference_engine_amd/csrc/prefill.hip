@@ -832,6 +832,23 @@ static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
     return splits;
 }
 
+// ---------------------------------------------------------------- the multi-sequence passes' tail
+// What follows the lm_head of `rows` output rows.  No table set: the greedy tail, as ever.  A table (pie_decoder_set_batch_tail):
+// every row's own penalty over its own window first (ids / ctx / out_rows: the pass's input ids, context lengths and, where output row s
+// is not source row s, its source rows), then the same log-softmax + argmax, then every row's own sampler over the fp32 log-probabilities.
+static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *ctx, const int32_t *out_rows, int n_src, int rows, u16 *logits,
+                             float *logprobs, int32_t *next_tokens, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    PrefillScratch *s = d->prefill;
+    if (!d->bt_table) return logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st);
+    PenRowsArgs p = {};
+    p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = d->bt_table, p.recent = d->bt_recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
+    int rc = logits_penalty_rows_launch(c.dtype, p, rows, st);
+    if (rc) return rc;
+    if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
+    return sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st);
+}
+
 // ---------------------------------------------------------------- one decode step for B sequences (continuous batching)
 // The weights stream once for all B rows (linear_rows: up to 5 rows the streaming GEMV where the format has one, beyond that int4 matrices
 // on their W4M tiles and the others on the W16M copy + k_w16l_gemm); each row is its own sequence: RoPE at its own position, K/V appended
@@ -888,6 +905,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         g.w = (const char *)d->glob.lm_head, g.K = H, g.N = c.vocab, g.M = B, g.x = s->x, g.norm_w = (const u16 *)d->glob.final_norm, g.eps = c.rms_eps;
         g.y = logits, g.stats = s->tail_stats;
         if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_RMSNORM, EPI_LOGITS, g, st))) return rc;
+        if (d->bt_table) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty)
         const dim3 fg(TAIL_FINISH_BLOCKS, B);
         if (c.dtype == PIE_BF16)
             hipLaunchKernelGGL(k_logits_finish<BF16>, fg, dim3(256), 0, st, logits, c.vocab, s->tail_stats, lm_waves, logprobs, next_tokens, (DecState *)nullptr, (int *)nullptr, 0, (const unsigned *)nullptr);
@@ -928,7 +946,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
     RowsOpts head_opts;
     head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
     if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, B, logits, st, head_opts))) return rc;
-    return logits_tail_rows_launch(c.dtype, logits, c.vocab, B, s->tail_stats, logprobs, next_tokens, st);
+    return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);
 }
 
 
@@ -1003,7 +1021,7 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
     RowsOpts head_opts;
     head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
     if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->r, S, logits, st, head_opts))) return rc;
-    return logits_tail_rows_launch(c.dtype, logits, c.vocab, S, s->tail_stats, logprobs, next_tokens, st);
+    return batch_tail_launch(d, ids, row_ctx, last_rows, N, S, logits, logprobs, next_tokens, st);
 }
 
 static size_t active_page_bytes(const pie_decoder *d);
@@ -1023,6 +1041,7 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     }
     PIE_REQUIRE(d->glob_set, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: set_globals must be called first");
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: a layer has no weights (pie_decoder_set_layer)");
+    PIE_REQUIRE(!d->bt_table || S <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch tail's rows_cap");
     PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_prefill_batch / _step_mixed: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
@@ -1075,6 +1094,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_step_batch: not available on a tensor-parallel shard");
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_step_batch: a layer has no weights (pie_decoder_set_layer)");
     PIE_REQUIRE(B >= 1 && B <= 4096 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_step_batch: bad batch shape");
+    PIE_REQUIRE(!d->bt_table || B <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch tail's rows_cap");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_step_batch: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
     const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
@@ -1088,10 +1108,12 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     std::vector<uintptr_t> key = {(uintptr_t)tokens, (uintptr_t)context_lens, (uintptr_t)block_tables, (uintptr_t)logits, (uintptr_t)logprobs,
                                   (uintptr_t)next_tokens, (uintptr_t)n_pages, (uintptr_t)max_blocks, (uintptr_t)B, (uintptr_t)d->kv_i8 /* the page format is baked into the launches too */};
     for (int i = 0; i < d->cfg.n_layers; ++i) key.push_back((uintptr_t)slabs[i]);
+    for (uintptr_t v : {(uintptr_t)d->bt_table, (uintptr_t)d->bt_recent, (uintptr_t)d->bt_ws, (uintptr_t)d->bt_rows_cap}) key.push_back(v);  // the tail's launches bake them in
     if (!d->prefill) d->prefill = new PrefillScratch();
     PrefillScratch *s = d->prefill;
     if (s->batch_graph && s->batch_key == key && s->batch_gen == s->alloc_gen) {
         PIE_HIP_TRY(hipGraphLaunch(s->batch_graph, st));
+        ++d->batch_replays;
         return PIE_OK;
     }
     if (s->warm_key == key && s->warm_gen == s->alloc_gen) {
@@ -1112,6 +1134,21 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
         }
         s = d->prefill;
         e = hipGraphInstantiate(&s->batch_graph, g, nullptr, nullptr, 0);
+        {  // the kernel nodes the graph really holds (pie_decoder_batch_graph_launches), not a formula
+            size_t n_nodes = 0;
+            d->batch_graph_kernels = -1;
+            if (hipGraphGetNodes(g, nullptr, &n_nodes) == hipSuccess && n_nodes) {
+                std::vector<hipGraphNode_t> nodes(n_nodes);
+                if (hipGraphGetNodes(g, nodes.data(), &n_nodes) == hipSuccess) {
+                    int k = 0;
+                    for (size_t i = 0; i < n_nodes; ++i) {
+                        hipGraphNodeType t;
+                        if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++k;
+                    }
+                    d->batch_graph_kernels = k;
+                }
+            }
+        }
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) return pie::fail(PIE_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
         s->batch_key = key, s->batch_gen = s->alloc_gen;

@@ -71,6 +71,9 @@ struct SmpArgs {
     int k;                // top_k, or min_tokens_to_keep
     unsigned long long seed;
     unsigned long long *counter;  // [0] calls so far, [1] rows finished in this call
+    // pie_sample_rows: row r's mode, inv_temp, thr, k, seed and call counter come from table[r] (device memory, untrusted) instead of the
+    // fields above, which are the one-record case shared by every row; null: pie_sample
+    pie_row_tail *table;
     unsigned long long *ws;       // rows x smp_row_words(gridDim.x)
     int *token_out, *kept_count;
     unsigned char *kept_mask;
@@ -85,6 +88,19 @@ struct SmpArgs {
 // top-p: key = okey(x), weight = exp(x - max) in fixed point, target = (1 - top_p) x total: T = smallest kept value.
 // top-k / min_tokens_to_keep: key = ~okey(x) (descending values), weight = 1, target = k - 1: T = complement of the k-th largest value.
 __device__ __forceinline__ bool smp_select_on_probs(int mode) { return mode == SMP_TOP_P; }
+// The launch's arguments as row `row` sees them.  With a table the row's own record replaces the shared one: an unknown mode acts as greedy
+// (PIE_SAMPLE_GREEDY), k is clamped to [1, V]; inv_temp, thr and seed only enter arithmetic.  Block-uniform.
+__device__ __forceinline__ SmpArgs smp_row_args(const SmpArgs &in, unsigned row) {
+    SmpArgs a = in;
+    if (in.table) {
+        const pie_row_tail &t = in.table[row];
+        const int mode = t.mode;
+        a.mode = mode >= SMP_CATEGORICAL && mode <= SMP_MIN_P ? mode : PIE_SAMPLE_GREEDY;
+        a.inv_temp = t.inv_temp, a.thr = t.thr, a.seed = t.seed;
+        a.k = a.mode == SMP_TOP_K || a.mode == SMP_MIN_P ? min(max(t.k, 1), in.V) : 0;
+    }
+    return a;
+}
 __device__ __forceinline__ bool smp_has_select(const SmpArgs &a) { return a.mode == SMP_TOP_P || a.mode == SMP_TOP_K || (a.mode == SMP_MIN_P && a.k > 1); }
 
 // Walks one global histogram (n bins) from bin 0 up: first bin b with cum + h[b] > target.  Every thread returns the same (b, cum below b).
@@ -142,9 +158,11 @@ __device__ __forceinline__ unsigned long long smp_weight(const SmpArgs &a, float
 __device__ __forceinline__ unsigned smp_key(const SmpArgs &a, float xs) { return a.mode == SMP_TOP_P ? okey(xs) : ~okey(xs); }
 
 // launch 0: clears the row's workspace and finds max(x) (needed by top-p's weights and min-p's threshold)
-__global__ void __launch_bounds__(SMP_T) k_smp_init(const SmpArgs a) {
+__global__ void __launch_bounds__(SMP_T) k_smp_init(const SmpArgs a_in) {
     __shared__ unsigned s_m[SMP_T / 64];
     const unsigned row = blockIdx.y, G = gridDim.x;
+    const SmpArgs a = smp_row_args(a_in, row);
+    if (a.mode == PIE_SAMPLE_GREEDY) return;  // (a table row only) nothing of a greedy row is touched
     unsigned long long *ws = a.ws + (size_t)row * smp_row_words(G);
     const size_t words = SMP_HDR + 3 * (size_t)SMP_BINS;  // the per-workgroup count table is fully rewritten by digit 2's launch
     for (size_t i = (size_t)blockIdx.x * SMP_T + threadIdx.x; i < words; i += (size_t)G * SMP_T)
@@ -165,10 +183,12 @@ __global__ void __launch_bounds__(SMP_T) k_smp_init(const SmpArgs a) {
 
 // launches 1..3: one radix digit each (DIGIT 0: bits 31..21, 1: bits 20..10, 2: bits 9..0)
 template <int DIGIT>
-__global__ void __launch_bounds__(SMP_T) k_smp_digit(const SmpArgs a) {
+__global__ void __launch_bounds__(SMP_T) k_smp_digit(const SmpArgs a_in) {
     __shared__ unsigned long long s_h[SMP_BINS];
     __shared__ unsigned long long s_scan[SMP_T + 2];
     const unsigned row = blockIdx.y, G = gridDim.x;
+    const SmpArgs a = smp_row_args(a_in, row);
+    if (!smp_has_select(a)) return;  // (a table row only: pie_sample does not launch the digits then) greedy, categorical, min-p that keeps one
     unsigned long long *ws = a.ws + (size_t)row * smp_row_words(G);
     unsigned long long *h0 = ws + SMP_HDR, *h1 = h0 + SMP_BINS, *h2 = h1 + SMP_BINS;
     const float xmax = okey_inv((unsigned)__hip_atomic_load(ws + H_MAXKEY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -213,12 +233,14 @@ __global__ void __launch_bounds__(SMP_T) k_smp_digit(const SmpArgs a) {
 }
 
 // last launch: the filter threshold from the three histograms, then the Gumbel-max draw over the kept ids
-__global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a) {
+__global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a_in) {
     __shared__ unsigned long long s_scan[SMP_T + 2];
     __shared__ unsigned s_cnt[SMP_T];
     __shared__ unsigned long long s_best[SMP_T / 64];
     __shared__ unsigned s_kept[SMP_T / 64];
     const unsigned row = blockIdx.y, G = gridDim.x;
+    const SmpArgs a = smp_row_args(a_in, row);
+    if (a.mode == PIE_SAMPLE_GREEDY) return;
     unsigned long long *ws = a.ws + (size_t)row * smp_row_words(G);
     unsigned long long *h0 = ws + SMP_HDR, *h1 = h0 + SMP_BINS, *h2 = h1 + SMP_BINS;
     const float xmax = okey_inv((unsigned)__hip_atomic_load(ws + H_MAXKEY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -282,9 +304,10 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a) {
         for (int t = 0; t < (int)threadIdx.x; ++t) tie_rank += s_cnt[t];
         __syncthreads();
     }
-    const unsigned long long call = a.counter[0];
+    // a table row draws as row 0 of its own one-row call number `calls`: its stream depends on neither its slot nor its neighbours
+    const unsigned long long call = a.table ? a.table[row].calls : a.counter[0];
     unsigned r4[4];
-    philox(a.seed, call, row, (unsigned)base >> 2, r4);  // ids base, base + 1 share one 4-word block (base is even)
+    philox(a.seed, call, a.table ? 0u : row, (unsigned)base >> 2, r4);  // ids base, base + 1 share one 4-word block (base is even)
     unsigned long long best = 0;  // packed: okey(x + G) << 32 | ~index  (max = larger value, then lower index)
     unsigned n_kept = 0;
 #pragma unroll
@@ -319,6 +342,13 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a) {
         if ((unsigned)arr == G) {  // last workgroup of the row
             const unsigned long long win = __hip_atomic_load(ws + H_BEST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int tok = (int)~(unsigned)win;
+            if (a.table) {
+                ws[H_MAXKEY] = 0;  // ready for the row's next k_smp_init, whatever its mode is then
+                a.table[row].calls = call + 1;  // every workgroup of the row has read it: they arrived
+                if (tok >= 0 && tok < a.V) a.token_out[row] = tok;  // (no id was drawable only under a record of NaNs: the argmax stays)
+                if (a.kept_count) a.kept_count[row] = (int)(arr >> 32);
+                return;
+            }
             a.token_out[row] = tok;
             if (a.feed_token) {
                 *a.feed_token = tok;
@@ -335,10 +365,8 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a) {
 
 }  // namespace
 
-int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace) {
-    const std::string w(who);
-    PIE_REQUIRE(V >= 1 && V <= SMP_MAX_WGS * SMP_SLICE, PIE_E_SHAPE, w + ": rows >= 1 and 1 <= V <= 524288");
-    PIE_REQUIRE(pie_aligned(workspace, 8), PIE_E_ALIGN, w + ": workspace needs 8-byte alignment");
+// the rules of the parameters alone (V: the vocabulary, INT_MAX where none is known)
+static int sample_params_check(const std::string &w, int V, int mode, double temp, double p, int k) {
     PIE_REQUIRE(mode >= SMP_CATEGORICAL && mode <= SMP_MIN_P, PIE_E_ARG, w + ": unknown mode");
     PIE_REQUIRE(temp > 0.0, PIE_E_ARG, w + ": temperature must be positive (temp = 0 is the greedy tail, pie_logprobs_argmax)");
     // the reference's own argument checks (top_k.py:20-24, min_p.py:30-40)
@@ -349,6 +377,20 @@ int sample_check(const char *who, int V, int mode, double temp, double p, int k,
     return PIE_OK;
 }
 
+int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace) {
+    const std::string w(who);
+    PIE_REQUIRE(V >= 1 && V <= SMP_MAX_WGS * SMP_SLICE, PIE_E_SHAPE, w + ": rows >= 1 and 1 <= V <= 524288");
+    PIE_REQUIRE(pie_aligned(workspace, 8), PIE_E_ALIGN, w + ": workspace needs 8-byte alignment");
+    return sample_params_check(w, V, mode, temp, p, k);
+}
+
+// Python scalars enter the reference's fp32 arithmetic as the fp32 value of the double expression: 1 / temperature, 1 - top_p, log(min_p)
+static void sample_derive(int mode, double temp, double p, int k, float *inv_temp, float *thr, int *k_out) {
+    *inv_temp = (float)(1.0 / temp);
+    *thr = mode == SMP_TOP_P ? (float)(1.0 - p) : (mode == SMP_MIN_P ? (float)log(p) : 0.0f);
+    *k_out = mode == SMP_TOP_K || mode == SMP_MIN_P ? k : 0;
+}
+
 // pie_sample's launches (arguments already checked: sample_check): 2 (categorical, min-p that keeps one) or 5
 int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                   void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st) {
@@ -356,10 +398,7 @@ int sample_launch(const float *logprobs, int rows, int V, int mode, double temp,
     a.logprobs = logprobs, a.V = V, a.mode = mode, a.seed = seed, a.counter = counter, a.ws = (unsigned long long *)workspace;
     a.token_out = tokens, a.kept_count = kept_count, a.kept_mask = kept_mask;
     a.feed_token = feed.token, a.feed_pos = feed.pos, a.history = feed.history, a.hist_cap = feed.hist_cap;
-    // Python scalars enter the reference's fp32 arithmetic as the fp32 value of the double expression: 1 / temperature, 1 - top_p, log(min_p)
-    a.inv_temp = (float)(1.0 / temp);
-    a.thr = mode == SMP_TOP_P ? (float)(1.0 - p) : (mode == SMP_MIN_P ? (float)log(p) : 0.0f);
-    a.k = mode == SMP_TOP_K || mode == SMP_MIN_P ? k : 0;
+    sample_derive(mode, temp, p, k, &a.inv_temp, &a.thr, &a.k);
     const dim3 grid((unsigned)((V + SMP_SLICE - 1) / SMP_SLICE), (unsigned)rows), block(SMP_T);
     hipLaunchKernelGGL(k_smp_init, grid, block, 0, st, a);
     if (mode == SMP_TOP_P || mode == SMP_TOP_K || (mode == SMP_MIN_P && k > 1)) {
@@ -372,7 +411,59 @@ int sample_launch(const float *logprobs, int rows, int V, int mode, double temp,
     return PIE_OK;
 }
 
+// pie_sample_rows' launches (arguments already checked): always the five, every workgroup deciding by its row's record
+int sample_rows_launch(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask,
+                       hipStream_t st) {
+    SmpArgs a = {};
+    a.logprobs = logprobs, a.V = V, a.mode = PIE_SAMPLE_GREEDY, a.table = table, a.ws = (unsigned long long *)workspace;
+    a.token_out = tokens, a.kept_count = kept_count, a.kept_mask = kept_mask;
+    const dim3 grid((unsigned)((V + SMP_SLICE - 1) / SMP_SLICE), (unsigned)rows), block(SMP_T);
+    hipLaunchKernelGGL(k_smp_init, grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_smp_digit<0>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_smp_digit<1>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_smp_digit<2>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_smp_draw, grid, block, 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+int sample_rows_check(const char *who, int rows, int V, const void *table, const void *workspace) {
+    const std::string w(who);
+    PIE_REQUIRE(rows >= 1 && rows <= 65535 && V >= 1 && V <= SMP_MAX_WGS * SMP_SLICE, PIE_E_SHAPE, w + ": 1 <= rows <= 65535 and 1 <= V <= 524288");
+    PIE_REQUIRE(pie_aligned(workspace, 8), PIE_E_ALIGN, w + ": workspace needs 8-byte alignment");
+    PIE_REQUIRE(pie_aligned(table, 8), PIE_E_ALIGN, w + ": the record table needs 8-byte alignment");
+    return PIE_OK;
+}
+
 extern "C" {
+
+size_t pie_row_tail_bytes(void) { return sizeof(pie_row_tail); }
+
+int pie_row_tail_pack(int mode, double temp, double p, int k, unsigned long long seed, unsigned long long calls, double penalty, int context_size,
+                      pie_row_tail *out) {
+    PIE_REQUIRE(out, PIE_E_ARG, "pie_row_tail_pack: null pointer");
+    PIE_REQUIRE(penalty >= 0.0 && std::isfinite(penalty), PIE_E_ARG, "pie_row_tail_pack: the penalty must be finite and non-negative");
+    PIE_REQUIRE(context_size >= 1 && context_size <= 1024, PIE_E_ARG, "pie_row_tail_pack: context_size must be 1..1024");
+    pie_row_tail r = {};
+    r.mode = PIE_SAMPLE_GREEDY, r.inv_temp = 1.0f;
+    if (mode != PIE_SAMPLE_GREEDY) {
+        if (int rc = sample_params_check("pie_row_tail_pack", 0x7FFFFFFF, mode, temp, p, k)) return rc;
+        r.mode = mode;
+        int kk = 0;
+        sample_derive(mode, temp, p, k, &r.inv_temp, &r.thr, &kk);
+        r.k = kk;
+    }
+    r.seed = seed, r.calls = calls, r.penalty = (float)penalty, r.context_size = context_size;
+    *out = r;
+    return PIE_OK;
+}
+
+int pie_sample_rows(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int32_t *tokens, int32_t *kept_count,
+                    unsigned char *kept_mask, void *stream) {
+    PIE_REQUIRE(logprobs && table && tokens && workspace, PIE_E_ARG, "pie_sample_rows: null pointer");
+    if (int rc = sample_rows_check("pie_sample_rows", rows, V, table, workspace)) return rc;
+    return sample_rows_launch(logprobs, rows, V, table, workspace, tokens, kept_count, kept_mask, (hipStream_t)stream);
+}
 
 size_t pie_sample_workspace_bytes(int rows, int V) {
     if (rows < 1 || V < 1) return 0;

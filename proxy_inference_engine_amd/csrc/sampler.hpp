@@ -15,3 +15,7 @@ struct SampleFeed {
 int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace);
 int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                   void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st);
+// pie_sample_rows' checks and launches (per-row records in device memory): the multi-sequence passes' tail draws with them
+int sample_rows_check(const char *who, int rows, int V, const void *table, const void *workspace);
+int sample_rows_launch(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask,
+                       hipStream_t st);

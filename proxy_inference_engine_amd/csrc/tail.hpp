@@ -211,6 +211,59 @@ static inline int logits_penalty_launch(int dtype, const PenArgs &a, hipStream_t
     return PIE_OK;
 }
 
+// The same penalty for every row of a multi-sequence pass at once (pie_logits_penalty_rows): one workgroup per output row s, the penalty and
+// the window size from the row's record (device memory, untrusted: the context is clamped to [1, PEN_MAX_IDS]), the window from the row's
+// ring recent[s][q & 1023] = the id fed at position q.  Source row i = out_rows ? out_rows[s] : s of the pass's ids / ctx (checked against
+// n_src); pos = ctx[i] - 1 < 0: an idle slot, skipped.  The row's own input id is recorded at pos first; a penalty of exactly 1.0 stops there.
+struct PenRowsArgs {
+    u16 *logits;
+    int V, n_src;
+    const pie_row_tail *table;
+    int *recent;
+    const int *ids, *ctx, *out_rows;
+};
+
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty_rows(const PenRowsArgs a) {
+    __shared__ int s_ids[PEN_MAX_IDS];
+    const int t = threadIdx.x, s = blockIdx.x;
+    const int i = a.out_rows ? a.out_rows[s] : s;
+    if (i < 0 || i >= a.n_src) return;  // block-uniform, like every return before the barrier
+    const int pos = a.ctx[i] - 1;
+    if (pos < 0) return;
+    int *ring = a.recent + (size_t)s * PEN_MAX_IDS;
+    const float penalty = a.table[s].penalty;
+    if (penalty == 1.0f) {
+        if (t == 0) ring[pos & (PEN_MAX_IDS - 1)] = a.ids[i];
+        return;
+    }
+    int context = a.table[s].context_size;
+    context = context < 1 ? 1 : (context > PEN_MAX_IDS ? PEN_MAX_IDS : context);
+    const int lo = pos + 1 - context > 0 ? pos + 1 - context : 0, n = pos + 1 - lo;  // 1 <= n <= context
+    int id = -1;
+    if (t < n) {
+        const int p = lo + t;
+        if (p == pos) id = a.ids[i], ring[p & (PEN_MAX_IDS - 1)] = id;
+        else id = ring[p & (PEN_MAX_IDS - 1)];
+    }
+    s_ids[t] = id;
+    __syncthreads();
+    if (t >= n || id < 0 || id >= a.V) return;
+    for (int j = 0; j < t; ++j)
+        if (s_ids[j] == id) return;  // an earlier entry owns this id
+    u16 *logits = a.logits + (size_t)s * a.V;
+    const float x = T::to_f32(logits[id]);
+    logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, penalty) : __fdiv_rn(x, penalty));  // k_logits_penalty's arithmetic
+}
+
+static inline int logits_penalty_rows_launch(int dtype, const PenRowsArgs &a, int rows, hipStream_t st) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits penalty: dtype must be PIE_BF16 or PIE_F16");
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_penalty_rows<BF16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a);
+    else hipLaunchKernelGGL(k_logits_penalty_rows<F16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
 // The per-tile partials of `logits` as pie_logprobs_argmax computes them (k_logits_stats over TAIL_STAT_TILES tiles), into caller-owned
 // scratch: the step's tail after a penalty, whose lm_head epilogue partials are stale.
 static inline int logits_stats_launch(int dtype, const u16 *logits, int V, LogitStat *stats, hipStream_t st) {

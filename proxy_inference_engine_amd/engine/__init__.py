@@ -1,4 +1,4 @@
-from .batch_engine import BatchedEngine
+from .batch_engine import BatchedEngine, SamplingParams
 from .inference_engine import InferenceEngine
 
-__all__ = ["InferenceEngine", "BatchedEngine"]
+__all__ = ["InferenceEngine", "BatchedEngine", "SamplingParams"]

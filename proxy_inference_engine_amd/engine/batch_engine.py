@@ -6,7 +6,8 @@ empty, the Python engine serves one sequence).  This is the smallest complete lo
 wait in a queue, join the batch when a slot and enough pages are free -- their prompt rows ride the decode step of the sequences
 in flight (`Model.step_mixed`: both kinds of sequence in one pass over the weights, as BatchDetails holds both), or run as a
 prompt pass of their own when nothing is decoding -- every step decodes all active sequences with one pass over the weights
-(`Model.step_batch`), finished sequences leave and return their pages.  Greedy by default; `sampler` maps a [B, V] log-probability block to B token ids."""
+(`Model.step_batch`), finished sequences leave and return their pages.  Greedy by default; `generate(sampling=...)` gives every request
+its own `SamplingParams`, run per row inside the passes; `sampler` maps a [B, V] log-probability block to B token ids."""
 from __future__ import annotations
 
 from collections import deque
@@ -16,6 +17,46 @@ from typing import Callable, Iterable
 import torch
 
 from ..cache.kv_cache.paged import TOKEN_CAPACITY_PER_PAGE
+
+
+@dataclass
+class SamplingParams:
+    """One request's sampler and repetition penalty: the reference's per-Sequence SamplingParams (temperature, top_p, top_k, min_p, rng_seed;
+    include/sequence/sampling_params.hpp) and LogitsParams (repetition_penalty, repetition_context_size; logits_params.hpp).  The branch
+    is make_sampler's: temp == 0 greedy, else top_p inside (0, 1), else min_p != 0, else top_k > 0, else plain categorical.
+    seed None: a fresh random seed per request."""
+    temp: float = 0.0
+    top_p: float = 1.0
+    top_k: int = -1
+    min_p: float = 0.0
+    min_tokens_to_keep: int = 1
+    seed: int | None = None
+    repetition_penalty: float = 1.0
+    repetition_context_size: int = 60
+
+    def hip_spec(self) -> tuple | None:
+        """None (greedy) or (mode, temp, p, k) as hip_ops.sample / row_tail_pack take them."""
+        if self.temp == 0:
+            return None
+        if 0 < self.top_p < 1.0:
+            return ("top_p", float(self.temp), float(self.top_p), 0)
+        if self.min_p != 0.0:
+            return ("min_p", float(self.temp), float(self.min_p), int(self.min_tokens_to_keep))
+        if self.top_k > 0:
+            return ("top_k", float(self.temp), 0.0, int(self.top_k))
+        return ("categorical", float(self.temp), 0.0, 0)
+
+    @property
+    def plain(self) -> bool:
+        """Greedy without a penalty: today's tail."""
+        return self.temp == 0 and self.repetition_penalty == 1.0
+
+    def record(self, calls: int = 0, seed: int | None = None):
+        """The request's device record (hip_ops.row_tail_pack) after `calls` drawn tokens; ValueError for arguments the samplers refuse."""
+        from .. import hip_ops
+        spec = self.hip_spec() or (None, 1.0, 0.0, 0)
+        return hip_ops.row_tail_pack(*spec, seed=(self.seed or 0) if seed is None else seed, calls=calls, penalty=self.repetition_penalty,
+                                     context_size=self.repetition_context_size)
 
 
 @dataclass
@@ -55,10 +96,35 @@ class BatchedEngine:
     def _pages_for(self, n_tokens: int) -> int:
         return (n_tokens + TOKEN_CAPACITY_PER_PAGE - 1) // TOKEN_CAPACITY_PER_PAGE
 
-    def generate(self, prompts: list, max_new_tokens: int) -> list[list[int]]:
-        """Token ids generated for every prompt (in order), at most max_new_tokens each, ending early at a stop token."""
+    def generate(self, prompts: list, max_new_tokens: int, sampling: SamplingParams | list | None = None) -> list[list[int]]:
+        """Token ids generated for every prompt (in order), at most max_new_tokens each, ending early at a stop token.
+        sampling: None (greedy, or the constructor's `sampler`), one SamplingParams for every request, or one per prompt: each request's
+        own sampler, seed and repetition penalty, applied to its row inside every pass (Model.set_batch_tail) -- a request's tokens depend
+        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters."""
+        if sampling is not None:
+            if self.sampler is not None:
+                raise ValueError("generate: `sampling` and the constructor's `sampler` callable exclude each other")
+            params = [sampling] * len(prompts) if isinstance(sampling, SamplingParams) else list(sampling)
+            if len(params) != len(prompts) or not all(isinstance(sp, SamplingParams) for sp in params):
+                raise ValueError("generate: `sampling` is one SamplingParams or one per prompt")
+            import os
+            seeds = [int.from_bytes(os.urandom(8), "little") if sp.seed is None else int(sp.seed) for sp in params]
+            for sp, sd in zip(params, seeds):
+                sp.record(0, sd)              # every request's arguments are checked before anything runs
+            if all(sp.plain for sp in params):
+                sampling = None               # nothing to configure: today's passes
         if max_new_tokens < 1:
             return [[] for _ in prompts]
+        if sampling is None:
+            return self._generate(prompts, max_new_tokens, None)
+        self.model.set_batch_tail(self.max_batch)
+        self.model.write_batch_tail(list(range(self.max_batch)), [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
+        try:
+            return self._generate(prompts, max_new_tokens, (params, seeds))
+        finally:
+            self.model.clear_batch_tail()
+
+    def _generate(self, prompts: list, max_new_tokens: int, tails) -> list[list[int]]:
         for p in prompts:
             if self._pages_for(len(p) + max_new_tokens) > self.pool.size():
                 raise ValueError("a prompt does not fit the page pool")
@@ -91,6 +157,40 @@ class BatchedEngine:
             seq = root[0].page_manager.fork()                               # whole pages: add_ref only, nothing is copied
             return [type(root[0])(seq, i) for i in range(len(root))]
         filling: list = []            # chunked prefill: [request, prompt, cache, rows done] of admitted prompts not yet fully in their pages
+        slots: list = []              # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
+
+        def seat(rows: list) -> None:
+            """The coming pass's output rows, in order: a request index (its own record; its ring rows from the ids it has been fed) or
+            None (a prompt still filling: greedy, its token is discarded).  Rewrites the rows whose occupant changed -- the moment at which
+            step_batch rewrites the block table; a row a request keeps is left alone (its `calls` advances on the device)."""
+            if tails is None:
+                return
+            params, seeds = tails
+            drawn = {a.request: len(a.generated) for a in active}
+            want = [None if r is None else (r, drawn.get(r, 0)) for r in rows]
+            slots.extend([None] * (len(want) - len(slots)))
+            idx, recs, fed = [], [], []
+            for s_, w in enumerate(want):
+                have = slots[s_]
+                # the same request one token further on is the row's own progress, not a new occupant
+                if w == have or (w is not None and have is not None and w[0] == have[0] and w[1] == have[1] + 1):
+                    slots[s_] = w
+                    continue
+                idx.append(s_)
+                if w is None:
+                    recs.append(SamplingParams().record())
+                    fed.append(None)
+                else:
+                    sp = params[w[0]]
+                    recs.append(sp.record(w[1], seeds[w[0]]))
+                    gen = next((a.generated for a in active if a.request == w[0]), [])
+                    fed.append(None if sp.repetition_penalty == 1.0 else list(prompts[w[0]]) + list(gen[:-1]))
+                slots[s_] = w
+            self.model.write_batch_tail(idx, recs, fed)
+
+        def lone_step(idx) -> bool:
+            """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record of its own."""
+            return tails is None or tails[0][idx].plain
         while pending or active or filling:
             # every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
             if active:
@@ -133,6 +233,7 @@ class BatchedEngine:
                     if n > 0:
                         take.append((f, n))
                         budget -= n
+                seat([a.request for a in active] + [f[0] if f[3] + n == len(f[1]) else None for f, n in take])
                 nxt, logprobs, _ = self.model.step_mixed(torch.cat([a.token for a in active]) if active else None, [a.cache for a in active],
                                                          [f[1][f[3]:f[3] + n] for f, n in take], [f[2] for f, _ in take])
                 self.steps += 1
@@ -161,6 +262,7 @@ class BatchedEngine:
             n_mix = len(active) + rows
             if active and batch and self.mixed and (n_mix <= 512 or (n_mix + 255) // 256 == (rows + 255) // 256):
                 # the admitted prompts ride the decode step of the sequences in flight: one pass over the weights for both
+                seat([a.request for a in active] + [idx for idx, _, _ in batch])
                 nxt, logprobs, _ = self.model.step_mixed(torch.cat([a.token for a in active]), [a.cache for a in active],
                                                          [p for _, p, _ in batch], [c for _, _, c in batch])
                 self.steps += 1
@@ -176,11 +278,13 @@ class BatchedEngine:
             joined = []
             if self._i8 and batch and (len(batch) == 1 or not self.batch_prefill):
                 for idx, prompt, cache in batch:
+                    seat([idx])
                     toks, logprobs, _ = self.model.prefill_batch([prompt], [cache])
                     if self.sampler is not None:
                         toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
                     joined.append(_Active(idx, cache, toks[:1].clone()))
             elif P and batch:                                            # suffixes behind the shared prefix: prompts continuing a cached prefix
+                seat([idx for idx, _, _ in batch])
                 toks, logprobs, _ = self.model.step_mixed(None, [], [p for _, p, _ in batch], [c for _, _, c in batch])
                 if self.sampler is not None:
                     toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
@@ -188,18 +292,25 @@ class BatchedEngine:
                     joined.append(_Active(idx, cache, toks[i:i + 1].clone()))
             elif len(batch) == 1 or (batch and not self.batch_prefill):
                 for idx, prompt, cache in batch:
+                    if not lone_step(idx):                                # its first token is drawn by its own sampler: a batch of one
+                        seat([idx])
+                        toks, _, _ = self.model.prefill_batch([prompt], [cache])
+                        joined.append(_Active(idx, cache, toks[:1].clone()))
+                        continue
                     ids = torch.as_tensor(prompt, dtype=torch.int32).reshape(-1)
                     tok, logprobs, _ = self.model.step(ids.to(self.model.device), cache)
                     if self.sampler is not None:
                         tok = self.sampler(logprobs[None]).reshape(1).to(torch.int32)
                     joined.append(_Active(idx, cache, tok.reshape(1).clone()))
             elif batch:
+                seat([idx for idx, _, _ in batch])
                 toks, logprobs, _ = self.model.prefill_batch([p for _, p, _ in batch], [c for _, _, c in batch])
                 if self.sampler is not None:
                     toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
                 for i, (idx, _, cache) in enumerate(batch):
                     joined.append(_Active(idx, cache, toks[i:i + 1].clone()))
             if active:
+                seat([a.request for a in active])
                 nxt, logprobs, _ = self.model.step_batch(torch.cat([a.token for a in active]), [a.cache for a in active])
                 self.steps += 1
                 if self.sampler is not None:

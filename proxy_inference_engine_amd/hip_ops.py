@@ -737,6 +737,82 @@ def sample_workspace(device, rows: int, V: int) -> torch.Tensor:
     return ws
 
 
+# ---------------------------------------------------------------- per-row tails (include/pie_hip.h: pie_row_tail)
+ROW_TAIL_WORDS = C.sizeof(_ffi.pie_row_tail) // 8   # a record as int64 words: a device table is an int64 [rows, ROW_TAIL_WORDS] tensor
+RECENT_IDS = 1024                                    # ring positions per row
+
+
+def row_tail_pack(mode: str | None = None, temp: float = 1.0, p: float = 0.0, k: int = 0, seed: int = 0, calls: int = 0, penalty: float = 1.0,
+                  context_size: int = 60) -> _ffi.pie_row_tail:
+    """One row's record (pie_row_tail_pack) in host memory: mode None = greedy, else one of SAMPLE_MODES with hip_ops.sample's arguments;
+    seed / calls: the row's own random stream and how many tokens it has drawn; penalty (1.0: none) over the last context_size fed ids.
+    ValueError for whatever pie_sample / pie_logits_penalty refuse.  Needs no device."""
+    rec = _ffi.pie_row_tail()
+    code = _ffi.PIE_SAMPLE_GREEDY if mode is None else SAMPLE_MODES[mode]
+    _ffi.check(_ffi.load().pie_row_tail_pack(code, float(temp), float(p), int(k), int(seed) & (2 ** 64 - 1), int(calls), float(penalty), int(context_size),
+                                             C.byref(rec)))
+    return rec
+
+
+def row_tail_table(records, device=None) -> torch.Tensor:
+    """Records (row_tail_pack) as an int64 [rows, ROW_TAIL_WORDS] tensor, on `device` when given."""
+    import numpy as np
+    host = np.frombuffer(b"".join(bytes(r) for r in records), dtype=np.int64).reshape(len(records), ROW_TAIL_WORDS).copy()
+    t = torch.from_numpy(host)
+    return t if device is None else t.to(device)
+
+
+def _table(table: torch.Tensor, rows: int, who: str) -> None:
+    _dev(table)
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != ROW_TAIL_WORDS or table.shape[0] < rows:
+        raise ValueError(f"{who}: the table is a contiguous int64 [>= rows, {ROW_TAIL_WORDS}] device tensor (row_tail_table)")
+
+
+def sample_rows(logprobs: torch.Tensor, table: torch.Tensor, tokens: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                want_mask: bool = False):
+    """pie_sample_rows: row r of logprobs fp32 [rows, V] drawn with table[r]'s own sampler, seed and call counter (advanced on the device);
+    greedy rows keep tokens[r] as given (zeros when tokens is None).  Returns tokens int32 [rows], with want_mask also (kept_count, kept
+    uint8 [rows, V]) -- rows of greedy records are left unwritten."""
+    x = logprobs
+    _dev(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("sample_rows: contiguous fp32 [rows, V] log-probabilities")
+    rows, V = x.shape
+    _table(table, rows, "sample_rows")
+    lib = _ffi.load()
+    if int(lib.pie_sample_workspace_bytes(rows, V)) == 0:
+        raise ValueError(f"sample_rows: a [rows, V] block with rows >= 1 and 1 <= V <= 524288, got [{rows}, {V}]")
+    ws = sample_workspace(x.device, rows, V) if workspace is None else workspace
+    if tokens is None:
+        tokens = torch.zeros(rows, dtype=torch.int32, device=x.device)
+    kept = torch.zeros(rows, dtype=torch.int32, device=x.device) if want_mask else None
+    mask = torch.zeros((rows, V), dtype=torch.uint8, device=x.device) if want_mask else None
+    _ffi.check(lib.pie_sample_rows(_ffi.p(x), rows, V, _ffi.p(table), _ffi.p(ws), _ffi.p(tokens), _ffi.p(kept), _ffi.p(mask), _ffi.stream()))
+    return (tokens, kept, mask) if want_mask else tokens
+
+
+def logits_penalty_rows(logits: torch.Tensor, table: torch.Tensor, recent_ids: torch.Tensor, ids: torch.Tensor, ctx: torch.Tensor,
+                        out_rows: torch.Tensor | None = None) -> torch.Tensor:
+    """pie_logits_penalty_rows on 16-bit logits [rows, V], IN PLACE: row s with source row i = out_rows[s] (or s) records ids[i] at
+    recent_ids[s][(ctx[i] - 1) & 1023] and is penalised over its last table[s].context_size fed ids.  recent_ids int32 [rows, 1024];
+    ids / ctx (/ out_rows) int32 device tensors.  Returns logits."""
+    _dev(logits), _dev(recent_ids)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logits_penalty_rows: contiguous [rows, V] logits")
+    rows, V = logits.shape
+    _table(table, rows, "logits_penalty_rows")
+    for t in (recent_ids, ids, ctx) + ((out_rows,) if out_rows is not None else ()):
+        _dev(t)
+        if t.dtype != torch.int32:
+            raise ValueError("logits_penalty_rows: contiguous int32 index tensors")
+    if recent_ids.shape != (recent_ids.shape[0], RECENT_IDS) or recent_ids.shape[0] < rows or ids.numel() != ctx.numel() or \
+            (out_rows is not None and out_rows.numel() != rows):
+        raise ValueError("logits_penalty_rows: recent_ids [>= rows, 1024], ids and ctx of one length, out_rows [rows]")
+    _ffi.check(_ffi.load().pie_logits_penalty_rows(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(table), _ffi.p(recent_ids), _ffi.p(ids),
+                                                   _ffi.p(ctx), _ffi.p(out_rows), ids.numel(), _ffi.stream()))
+    return logits
+
+
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)
 def kv_ring_order(keys: torch.Tensor, values: torch.Tensor, keep: int, n: int, shift: int, n_dst: int) -> None:
     """In place on RotatingKVCache buffers [1, H, cap, D]: rows keep + j <- rows keep + (j + shift) % n for j < n_dst."""

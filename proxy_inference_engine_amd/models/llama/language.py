@@ -299,6 +299,8 @@ class Model:
         self._kv = KVBinding(lib, self._dec, len(self.layers), self.n_kv_heads, self.head_dim, self.dtype, device, tensor_parallel=tp is not None)
         self._page_pool, self._page_blocks = None, 16
         self._batch_bufs: dict = {}
+        self._batch_tails: dict = {}   # rows_cap -> the batch tail's device buffers (set_batch_tail)
+        self._batch_tail = None
         torch.cuda.synchronize(device)
 
     def __del__(self):
@@ -575,6 +577,65 @@ class Model:
         for s in seqs:
             s.advance(1)
         return nxt, logprobs, logits
+
+    # ------------------------------------------------------------------ the multi-sequence passes' tail
+    def set_batch_tail(self, rows_cap: int) -> dict:
+        """From now on step_batch / prefill_batch / step_mixed end every output row in its own repetition penalty and sampler
+        (pie_decoder_set_batch_tail): row s follows record s of a device table this model owns -- {"table": int64 [rows_cap, ROW_TAIL_WORDS],
+        "recent": int32 [rows_cap, 1024] rings of fed ids, "ws": the sampler's workspace}, returned, and kept per rows_cap (the 4 most
+        recent, like the step's buffers).  A new table holds greedy records without a penalty: the passes' results are the untailed ones
+        until write_batch_tail changes a row.  The returned tokens are then the drawn ones, logits the processed ones."""
+        rows_cap = int(rows_cap)
+        if rows_cap < 1:
+            raise ValueError("set_batch_tail: rows_cap >= 1")
+        bt = self._batch_tails.pop(rows_cap, None)
+        if bt is None:
+            while len(self._batch_tails) >= 4:
+                self._batch_tails.pop(next(iter(self._batch_tails)))
+            bt = {"table": hip_ops.row_tail_table([hip_ops.row_tail_pack()] * rows_cap, self.device),
+                  "recent": torch.zeros((rows_cap, hip_ops.RECENT_IDS), dtype=torch.int32, device=self.device),
+                  "ws": torch.zeros(int(_ffi.load().pie_sample_workspace_bytes(rows_cap, self.args.vocab_size)) // 8, dtype=torch.int64, device=self.device)}
+        self._batch_tails[rows_cap] = bt  # most recently used last
+        _ffi.check(_ffi.load().pie_decoder_set_batch_tail(self._dec, _ffi.p(bt["table"]), rows_cap, _ffi.p(bt["recent"]), _ffi.p(bt["ws"])))
+        self._batch_tail = bt
+        return bt
+
+    def write_batch_tail(self, rows: list[int], records: list, fed: list | None = None) -> None:
+        """Rewrites the records of `rows` of the armed table (hip_ops.row_tail_pack), in stream order, one copy for all of them -- when a
+        row's occupant changes; `calls` of a record = the tokens that request has drawn so far.  fed[i] (None: leave the ring): the ids the
+        occupant of rows[i] has been fed so far, by position, of which the ring keeps the last 1024."""
+        import numpy as np
+        bt = self._batch_tail
+        if bt is None:
+            raise RuntimeError("write_batch_tail: no batch tail is set (set_batch_tail)")
+        if not rows:
+            return
+        idx = torch.tensor(rows, dtype=torch.long, device=self.device)
+        bt["table"].index_copy_(0, idx, hip_ops.row_tail_table(records, self.device))
+        ring_rows, rings = [], []
+        for r, ids in zip(rows, fed or []):
+            if ids is None:
+                continue
+            ids = np.asarray(ids, dtype=np.int32).reshape(-1)
+            q = np.arange(max(0, ids.size - hip_ops.RECENT_IDS), ids.size)
+            ring = np.zeros(hip_ops.RECENT_IDS, np.int32)
+            ring[q & (hip_ops.RECENT_IDS - 1)] = ids[q]
+            ring_rows.append(r), rings.append(ring)
+        if rings:
+            bt["recent"].index_copy_(0, torch.tensor(ring_rows, dtype=torch.long, device=self.device), torch.from_numpy(np.stack(rings)).to(self.device))
+
+    def clear_batch_tail(self) -> None:
+        """Back to the greedy tail of the multi-sequence passes; the buffers stay cached for the next set_batch_tail."""
+        _ffi.check(_ffi.load().pie_decoder_set_batch_tail(self._dec, None, 0, None, None))
+        self._batch_tail = None
+
+    def batch_graph_launches(self) -> int:
+        """Kernel nodes of the step_batch graph captured last (-1 before the first capture)."""
+        return int(_ffi.load().pie_decoder_batch_graph_launches(self._dec))
+
+    def batch_graph_replays(self) -> int:
+        """step_batch calls so far that replayed the captured graph."""
+        return int(_ffi.load().pie_decoder_batch_graph_replays(self._dec))
 
     def prefill_batch(self, prompts: list, caches: list[list[BaseCache]]):
         """Several fresh prompts in ONE pass (pie_decoder_prefill_batch): their rows are concatenated for the GEMMs, every row keeps
