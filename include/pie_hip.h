@@ -204,6 +204,21 @@ int pie_logprobs_argmax(const void *logits, int V, int dtype, float *logprobs, i
  * ids outside [0, V) are skipped and never indexed; -0.0 is not < 0 and is divided.  One launch of one workgroup.
  * penalty < 0 or not finite, n outside 1..1024: PIE_E_ARG; V < 1: PIE_E_SHAPE -- each before any launch. */
 int pie_logits_penalty(void *logits, int V, int dtype, const int32_t *ids, int n, double penalty, void *stream);
+/* The token mask of structured decoding (the reference's first processor, structuring_engine.process_logits, inference_engine.py:319-335,
+ * leaves only the allowed ids finite) fused into the log-softmax: mask is DEVICE uint32 [mask_words >= ceil(V / 32)], token i is allowed
+ * iff bit i & 31 of word i >> 5 is set (LSB first, the layout grammar engines export); bits at or beyond V are ignored.  logits [V] T are
+ * masked IN PLACE -- a disallowed id becomes -inf, an allowed id keeps its bits -- then logprobs and token are written exactly as
+ * pie_logprobs_argmax of the masked logits writes them (same 256-tile partition, same first-argmax rule).  Two launches: the masked
+ * partials pass, then the finish.  An all-zero mask is the caller's error: token 0 and NaN logprobs, like pie_logprobs_argmax of an
+ * all -inf row.  mask_words < ceil(V / 32): PIE_E_SHAPE; a mask not 4-byte aligned: PIE_E_ALIGN -- each before any launch. */
+int pie_logprobs_argmax_masked(void *logits, int V, int dtype, const uint32_t *mask, int mask_words, float *logprobs, int32_t *token,
+                               void *stream);
+/* logit_bias (logits_params.hpp; logit_processor_factory.cpp) on logits [V] T, in place: ids DEVICE int32 [n], bias DEVICE float [n]; for
+ * every entry t whose id is in [0, V) and not held by an earlier entry, logits[id] = T(f32(logits[id]) + bias[t]) -- one IEEE fp32
+ * addition, one round-to-nearest-even to T.  The first of duplicate ids owns the id (pie_logits_penalty's rule); ids out of range are
+ * skipped and never indexed.  One launch of one workgroup.  n outside 1..1024: PIE_E_ARG; V < 1: PIE_E_SHAPE; ids or bias not
+ * 4-byte aligned: PIE_E_ALIGN -- each before any launch. */
+int pie_logits_bias(void *logits, int V, int dtype, const int32_t *ids, const float *bias, int n, void *stream);
 /* Measurement aid (no reference counterpart; SURVEY.md 8d "fraction of a measured device-copy bandwidth"): a bare streaming read of `bytes`
  * shaped like the weight GEMV's stream (one 8-wave workgroup per CU, non-temporal 16-byte loads, nothing computed).  bench.py times it for
  * roofline.stream_peak. */
@@ -440,6 +455,24 @@ int pie_decoder_set_token_from(pie_decoder *d, const int32_t *token_dev, void *s
 int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_size, int32_t *ids_by_pos, int ids_cap);
 int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                             void *workspace, size_t workspace_bytes);
+/* Token mask and logit bias in the step's configured tail, applied wherever that tail applies (above).  The processed
+ * logits are what this sequence gives on T: (1) mask: pie_logprobs_argmax_masked's rule; (2) the repetition penalty, exactly as above;
+ * (3) bias: pie_logits_bias; then the unchanged log-softmax, finish and draw.  The bound logits hold the processed logits afterwards, and
+ * the bound logprobs and the greedy token are bit-identical with pie_logprobs_argmax of them.  RULE: a masked id is -inf in the processed
+ * logits, whatever else is configured.  (The mask is applied physically last, inside the partials pass: -inf stays -inf under any
+ * penalty > 0 and any finite bias.  The one deviation from the reference's order: with penalty == 0.0 a masked id inside the window is
+ * -inf here, where -inf * 0 gives the reference a NaN and a NaN row.)  Launches beyond the unconfigured step's: mask alone 1 (the masked
+ * partials); bias and / or penalty 2 (one edit launch, the partials), a mask on top of them none.
+ * pie_decoder_set_logits_mask: mask DEVICE uint32 [mask_words >= ceil(vocab / 32)]; NULL switches it off.  mask_words too small:
+ *   PIE_E_SHAPE; not 4-byte aligned: PIE_E_ALIGN.
+ * pie_decoder_set_logit_bias: ids DEVICE int32 [n], bias DEVICE float [n], n 1..1024; n == 0 switches it off; n outside 0..1024: PIE_E_ARG; ids or bias not
+ *   4-byte aligned: PIE_E_ALIGN.  With only a bias set the
+ *   edit launch runs with its penalty phase off and records nothing in ids_by_pos.
+ * Both keep caller-owned device memory that stays alive while set; its CONTENTS may change between steps (the host writes in stream
+ * order and a captured graph keeps replaying).  Switching either on or off, a new address or a new n drops the captured graphs.
+ * Tensor-parallel decoders refuse (PIE_E_STATE).  pie_decoder_step_batch / _prefill_batch / _step_mixed ignore both. */
+int pie_decoder_set_logits_mask(pie_decoder *d, const uint32_t *mask, int mask_words);
+int pie_decoder_set_logit_bias(pie_decoder *d, const int32_t *ids, const float *bias, int n);
 /* The multi-sequence passes' tail: per-row penalties and samplers inside pie_decoder_step_batch (eager or PIE_STEP_GRAPH),
  * pie_decoder_prefill_batch and pie_decoder_step_mixed.  table: DEVICE pie_row_tail [rows_cap], record s belongs to output row s (in the
  * two prompt passes the decoding rows first, then prompt j at n_decode + j: a request's first token is drawn by its own sampler);

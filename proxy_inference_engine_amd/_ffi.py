@@ -45,6 +45,7 @@ EXPORTS = [
     "pie_kv_quantize", "pie_attn_decode_quant", "pie_decoder_set_kv_quant",
     "pie_decoder_set_kv_ring", "pie_kv_ring_order", "pie_sdpa_prefill_window", "pie_sdpa_decode_ring",
     "pie_logits_penalty", "pie_decoder_set_logits_penalty", "pie_decoder_set_sampler",
+    "pie_logprobs_argmax_masked", "pie_logits_bias", "pie_decoder_set_logits_mask", "pie_decoder_set_logit_bias",
     "pie_row_tail_bytes", "pie_row_tail_pack", "pie_sample_rows", "pie_logits_penalty_rows", "pie_decoder_set_batch_tail", "pie_decoder_batch_graph_replays", "pie_decoder_batch_graph_launches",
 ]
 
@@ -130,6 +131,10 @@ def load() -> C.CDLL:
     lib.pie_logits_penalty.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
     lib.pie_decoder_set_logits_penalty.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int]
     lib.pie_decoder_set_sampler.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.pie_logprobs_argmax_masked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pie_logits_bias.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.pie_decoder_set_logits_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.pie_decoder_set_logit_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.pie_sample_workspace_bytes.restype = C.c_size_t
     lib.pie_row_tail_bytes.restype = C.c_size_t
     lib.pie_row_tail_bytes.argtypes = []

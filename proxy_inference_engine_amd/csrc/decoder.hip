@@ -156,18 +156,24 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
     return a;
 }
 
-// The configured tail over the bound outputs (include/pie_hip.h): penalty + fresh partials | finish | the sampler's launches.
+// The configured tail over the bound outputs (include/pie_hip.h): penalty and / or bias (one launch) + fresh partials, which apply the token
+// mask on their way | finish | the sampler's launches.
 // from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
 static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     const LogitStat *stats = d->stats;
     int n_stats = d->n_stats, rc;
-    if (d->pen != 1.0) {
+    if (d->pen != 1.0 || d->bias_n) {
         PenArgs a = {};
         a.logits = d->logits, a.V = c.vocab, a.penalty = (float)d->pen, a.ids_by_pos = d->ids_by_pos, a.ids_cap = d->ids_cap, a.context = d->pen_ctx;
         a.state = d->state, a.record = from_state;
-        if ((rc = logits_penalty_launch(c.dtype, a, st))) return rc;
-        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st))) return rc;  // the lm_head epilogue's partials are stale
+        const BiasArgs b = {d->bias_ids, d->bias_vals, d->bias_n, d->pen != 1.0};
+        if ((rc = d->bias_n ? logits_edit_launch(c.dtype, a, b, st) : logits_penalty_launch(c.dtype, a, st))) return rc;
+    }
+    if (d->pen != 1.0 || d->bias_n || d->tok_mask) {  // the lm_head epilogue's partials are stale
+        if ((rc = d->tok_mask ? logits_stats_masked_launch(c.dtype, d->logits, c.vocab, d->tok_mask, d->tail_stats, st)
+                              : logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st)))
+            return rc;
         stats = d->tail_stats, n_stats = TAIL_STAT_TILES;
     }
     if ((rc = logits_tail_launch(c.dtype, d->logits, c.vocab, stats, n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st))) return rc;
@@ -780,6 +786,10 @@ int pie_decoder_configure(pie_decoder *d, int option, int value) {
     return PIE_OK;
 }
 
+static int tail_stats_alloc(pie_decoder *d) {
+    return d->tail_stats ? PIE_OK : dev_alloc((void **)&d->tail_stats, sizeof(LogitStat) * TAIL_STAT_TILES);
+}
+
 int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_size, int32_t *ids_by_pos, int ids_cap) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logits_penalty: null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logits_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
@@ -787,13 +797,39 @@ int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_s
     PIE_REQUIRE(context_size >= 0 && context_size <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_logits_penalty: context_size must be 1..1024 (0: off)");
     if (penalty == 1.0 || context_size == 0) penalty = 1.0, context_size = 0, ids_by_pos = nullptr, ids_cap = 0;
     else PIE_REQUIRE(ids_by_pos && ids_cap >= 1 && pie_aligned(ids_by_pos, 4), PIE_E_ARG, "pie_decoder_set_logits_penalty: ids_by_pos must hold at least one id");
-    if (penalty != 1.0 && !d->tail_stats) {
-        const int rc = dev_alloc((void **)&d->tail_stats, sizeof(LogitStat) * TAIL_STAT_TILES);
-        if (rc) return rc;
-    }
+    if (penalty != 1.0)
+        if (int rc = tail_stats_alloc(d)) return rc;
     const bool changed = d->pen != penalty || d->pen_ctx != context_size || d->ids_by_pos != ids_by_pos || d->ids_cap != ids_cap;
     d->pen = penalty, d->pen_ctx = context_size, d->ids_by_pos = ids_by_pos, d->ids_cap = ids_cap;
     if (changed) drop_graphs(d);  // every one of them is a launch argument
+    return PIE_OK;
+}
+
+int pie_decoder_set_logits_mask(pie_decoder *d, const uint32_t *mask, int mask_words) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logits_mask: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logits_mask: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (mask) {
+        PIE_REQUIRE(mask_words >= (d->cfg.vocab + 31) / 32, PIE_E_SHAPE, "pie_decoder_set_logits_mask: the mask needs ceil(vocab / 32) words");
+        PIE_REQUIRE(pie_aligned(mask, 4), PIE_E_ALIGN, "pie_decoder_set_logits_mask: the mask needs 4-byte alignment");
+        if (int rc = tail_stats_alloc(d)) return rc;
+    }
+    if (d->tok_mask != mask) drop_graphs(d);  // the address is a launch argument (the words behind it are read by every launch)
+    d->tok_mask = mask;
+    return PIE_OK;
+}
+
+int pie_decoder_set_logit_bias(pie_decoder *d, const int32_t *ids, const float *bias, int n) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logit_bias: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logit_bias: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    PIE_REQUIRE(n >= 0 && n <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_logit_bias: 1 <= n <= 1024 entries (0: off)");
+    if (n == 0) ids = nullptr, bias = nullptr;
+    else {
+        PIE_REQUIRE(ids && bias, PIE_E_ARG, "pie_decoder_set_logit_bias: null pointer");
+        PIE_REQUIRE(pie_aligned(ids, 4) && pie_aligned(bias, 4), PIE_E_ALIGN, "pie_decoder_set_logit_bias: ids and bias need 4-byte alignment");
+        if (int rc = tail_stats_alloc(d)) return rc;
+    }
+    if (d->bias_ids != ids || d->bias_vals != bias || d->bias_n != n) drop_graphs(d);  // every one of them is a launch argument
+    d->bias_ids = ids, d->bias_vals = bias, d->bias_n = n;
     return PIE_OK;
 }
 

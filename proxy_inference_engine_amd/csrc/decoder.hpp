@@ -79,12 +79,18 @@ struct pie_decoder {
     double pen = 1.0;  // 1.0: off
     int pen_ctx = 0, ids_cap = 0;
     int *ids_by_pos = nullptr;        // caller-owned
-    LogitStat *tail_stats = nullptr;  // [TAIL_STAT_TILES] partials of the penalised logits (owned, allocated when a penalty is first set)
+    LogitStat *tail_stats = nullptr;  // [TAIL_STAT_TILES] partials of the processed logits (owned, allocated when a penalty, a mask or a bias is first set)
     int smp_mode = PIE_SAMPLE_GREEDY, smp_k = 0;
     double smp_temp = 1.0, smp_p = 0.0;
     unsigned long long smp_seed = 0, *smp_counter = nullptr;
     void *smp_ws = nullptr;
     bool tail_raw = false;
+    // The tail's token mask and logit bias (pie_decoder_set_logits_mask / _set_logit_bias): caller-owned device memory whose
+    // CONTENTS may change between steps; the addresses and bias_n are launch arguments.
+    const unsigned *tok_mask = nullptr;  // [>= ceil(vocab / 32)] words, nullptr: off
+    const int *bias_ids = nullptr;
+    const float *bias_vals = nullptr;
+    int bias_n = 0;  // 0: off
     // The multi-sequence passes' tail (pie_decoder_set_batch_tail): per-row records, rings and sampler workspace, caller-owned.
     // bt_table == nullptr: off.  The passes read the records on the device only; the addresses are in the captured batch graph's key.
     pie_row_tail *bt_table = nullptr;
@@ -93,7 +99,7 @@ struct pie_decoder {
     void *bt_ws = nullptr;
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
-    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY; }
+    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)

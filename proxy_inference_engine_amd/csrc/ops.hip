@@ -350,6 +350,32 @@ int pie_logits_penalty(void *logits, int V, int dtype, const int32_t *ids, int n
     return logits_penalty_launch(dtype, a, (hipStream_t)stream);
 }
 
+int pie_logprobs_argmax_masked(void *logits, int V, int dtype, const uint32_t *mask, int mask_words, float *logprobs, int32_t *token, void *stream) {
+    PIE_REQUIRE(logits && mask && logprobs && token, PIE_E_ARG, "pie_logprobs_argmax_masked: null pointer");
+    PIE_REQUIRE(V > 0, PIE_E_SHAPE, "pie_logprobs_argmax_masked: empty vocabulary");
+    PIE_REQUIRE(mask_words >= (V + 31) / 32, PIE_E_SHAPE, "pie_logprobs_argmax_masked: the mask needs ceil(V / 32) words");
+    PIE_REQUIRE(pie_aligned(mask, 4), PIE_E_ALIGN, "pie_logprobs_argmax_masked: the mask needs 4-byte alignment");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_logprobs_argmax_masked: dtype must be PIE_BF16 or PIE_F16");
+    hipStream_t st = (hipStream_t)stream;
+    LogitStat *stats = nullptr;  // stream-ordered scratch, like pie_logprobs_argmax's
+    if (hipMallocAsync((void **)&stats, sizeof(LogitStat) * TAIL_STAT_TILES, st) != hipSuccess) return pie::fail(PIE_E_HIP, "pie_logprobs_argmax_masked: hipMallocAsync failed");
+    int rc = logits_stats_masked_launch(dtype, (u16 *)logits, V, mask, stats, st);
+    if (!rc) rc = logits_tail_launch(dtype, (const u16 *)logits, V, stats, TAIL_STAT_TILES, logprobs, token, nullptr, nullptr, 0, st);
+    (void)hipFreeAsync(stats, st);
+    return rc;
+}
+
+int pie_logits_bias(void *logits, int V, int dtype, const int32_t *ids, const float *bias, int n, void *stream) {
+    PIE_REQUIRE(logits && ids && bias, PIE_E_ARG, "pie_logits_bias: null pointer");
+    PIE_REQUIRE(n >= 1 && n <= PEN_MAX_IDS, PIE_E_ARG, "pie_logits_bias: 1 <= n <= 1024 entries");
+    PIE_REQUIRE(V >= 1, PIE_E_SHAPE, "pie_logits_bias: empty vocabulary");
+    PIE_REQUIRE(pie_aligned(ids, 4) && pie_aligned(bias, 4), PIE_E_ALIGN, "pie_logits_bias: ids and bias need 4-byte alignment");
+    PenArgs a = {};
+    a.logits = (u16 *)logits, a.V = V, a.penalty = 1.0f;
+    const BiasArgs b = {ids, bias, n, 0};  // the penalty phase off
+    return logits_edit_launch(dtype, a, b, (hipStream_t)stream);
+}
+
 int pie_logits_penalty_rows(void *logits, int rows, int V, int dtype, const pie_row_tail *table, int32_t *recent_ids, const int32_t *ids,
                             const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream) {
     PIE_REQUIRE(logits && table && recent_ids && ids && ctx, PIE_E_ARG, "pie_logits_penalty_rows: null pointer");

@@ -11,8 +11,11 @@
 constexpr int TAIL_STAT_TILES = 256;
 constexpr int TAIL_FINISH_BLOCKS = 64;
 
-template <class T>
-__global__ void __launch_bounds__(256) k_logits_stats(const u16 *logits, int V, LogitStat *stats) {
+// MASKED: the token mask of the step's tail (include/pie_hip.h, "token mask and logit bias") rides this pass: token i is allowed iff bit
+// i & 31 of mask[i >> 5] is set (mask holds at least ceil(V / 32) words: checked by every caller before the launch); a disallowed id is
+// written back as -inf and counted as -inf, an allowed one keeps its bits.  The second loop re-reads what the same thread wrote.
+template <class T, bool MASKED>
+__device__ __forceinline__ void logits_stats_tile(u16 *logits, int V, LogitStat *stats, const unsigned *mask) {
     __shared__ float s_max[4], s_sum[4];
     __shared__ int s_arg[4];
     logits += (size_t)blockIdx.y * V, stats += (size_t)blockIdx.y * gridDim.x;  // blockIdx.y: row of a batch of logit vectors
@@ -22,7 +25,13 @@ __global__ void __launch_bounds__(256) k_logits_stats(const u16 *logits, int V, 
     // a thread's first index is its argmax until a larger value comes: a tile (or row) of -inf answers its first index, like mx.argmax
     int arg = begin + (int)threadIdx.x < end ? begin + (int)threadIdx.x : 0x7fffffff;
     for (int i = begin + threadIdx.x; i < end; i += 256) {
-        const float v = T::to_f32(logits[i]);
+        float v;
+        if constexpr (MASKED) {
+            if ((mask[i >> 5] >> (i & 31)) & 1u) v = T::to_f32(logits[i]);
+            else logits[i] = T::from_f32(-INFINITY), v = -INFINITY;
+        } else {
+            v = T::to_f32(logits[i]);
+        }
         if (v > mx) mx = v, arg = i;  // ascending i per thread: first maximal index wins
     }
     const float wmax = wave_max(mx);
@@ -46,6 +55,16 @@ __global__ void __launch_bounds__(256) k_logits_stats(const u16 *logits, int V, 
         st.max = tmax, st.sumexp = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3], st.argmax = targ, st.pad = 0;
         stats[blockIdx.x] = st;  // empty tile: max = -inf, sumexp = 0, argmax = INT_MAX (loses every tie with a real -inf tile)
     }
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_logits_stats(const u16 *logits, int V, LogitStat *stats) {
+    logits_stats_tile<T, false>(const_cast<u16 *>(logits), V, stats, nullptr);
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_logits_stats_masked(u16 *logits, int V, LogitStat *stats, const unsigned *mask) {
+    logits_stats_tile<T, true>(logits, V, stats, mask);
 }
 
 constexpr int TAIL_MAX_STATS = 4096;  // 256 threads x 16 register-resident partials
@@ -179,8 +198,7 @@ struct PenArgs {
 };
 
 template <class T>
-__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty(const PenArgs a) {
-    __shared__ int s_ids[PEN_MAX_IDS];
+__device__ __forceinline__ void logits_penalty_phase(const PenArgs &a, int *s_ids) {
     const int t = threadIdx.x;
     int n = a.n, id = -1;
     if (a.state) {
@@ -201,6 +219,50 @@ __global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty(const PenArgs a)
         if (s_ids[j] == id) return;  // an earlier entry owns this id
     const float x = T::to_f32(a.logits[id]);
     a.logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, a.penalty) : __fdiv_rn(x, a.penalty));  // -0.0 is not < 0: divided
+}
+
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty(const PenArgs a) {
+    __shared__ int s_ids[PEN_MAX_IDS];
+    logits_penalty_phase<T>(a, s_ids);
+}
+
+// The logit bias (logits_params.hpp: logit_bias; logit_processor_factory.cpp builds it after the repetition penalty), in the penalty's launch:
+// phase 1 is logits_penalty_phase (skipped when b.penalise == 0: then nothing is recorded in ids_by_pos either), phase 2 one thread per
+// entry t < n: logits[ids[t]] = T(f32(logits[ids[t]]) + bias[t]), one fp32 addition and one rounding, for every entry whose id is in [0, V) and
+// not held by an earlier entry (k_logits_penalty's rule, decided through the same LDS array).  ids / bias are read on the device each launch.
+// Phase 2 reads what phase 1 stored to the same id from another wave.  The rule this rests on: __syncthreads() is a workgroup-scope release /
+// acquire fence around the barrier, and at workgroup scope that needs no cache maintenance here -- the waves of one workgroup run on one CU
+// (the library is not built with -mtgsplit) and their global accesses go through that CU's one in-order vector L1, so a plain store issued
+// before the barrier is what a plain load issued after it returns.  Nothing here crosses a workgroup.
+struct BiasArgs {
+    const int *ids;
+    const float *bias;
+    int n;  // 1..PEN_MAX_IDS
+    int penalise;  // run phase 1 (the caller's own decision: no float sentinel)
+};
+
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_edit(const PenArgs a, const BiasArgs b) {
+    __shared__ int s_ids[PEN_MAX_IDS];
+    if (b.penalise) logits_penalty_phase<T>(a, s_ids);  // block-uniform
+    __syncthreads();  // phase 1's stores are visible, and its readers of s_ids are done
+    const int t = threadIdx.x;
+    const int id = t < b.n ? b.ids[t] : -1;
+    s_ids[t] = id;
+    __syncthreads();
+    if (id < 0 || id >= a.V) return;
+    for (int j = 0; j < t; ++j)
+        if (s_ids[j] == id) return;  // an earlier entry owns this id
+    a.logits[id] = T::from_f32(__fadd_rn(T::to_f32(a.logits[id]), b.bias[t]));
+}
+
+static inline int logits_edit_launch(int dtype, const PenArgs &a, const BiasArgs &b, hipStream_t st) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits bias: dtype must be PIE_BF16 or PIE_F16");
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_edit<BF16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a, b);
+    else hipLaunchKernelGGL(k_logits_edit<F16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a, b);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
 }
 
 static inline int logits_penalty_launch(int dtype, const PenArgs &a, hipStream_t st) {
@@ -269,6 +331,15 @@ static inline int logits_penalty_rows_launch(int dtype, const PenRowsArgs &a, in
 static inline int logits_stats_launch(int dtype, const u16 *logits, int V, LogitStat *stats, hipStream_t st) {
     if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_stats<BF16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats);
     else hipLaunchKernelGGL(k_logits_stats<F16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// The same partials with the token mask applied on the way (k_logits_stats_masked): `logits` then hold -inf at every disallowed id.
+static inline int logits_stats_masked_launch(int dtype, u16 *logits, int V, const unsigned *mask, LogitStat *stats, hipStream_t st) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits mask: dtype must be PIE_BF16 or PIE_F16");
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_stats_masked<BF16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats, mask);
+    else hipLaunchKernelGGL(k_logits_stats_masked<F16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats, mask);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }

@@ -18,7 +18,7 @@ from .. import hip_ops
 from ..cache import BaseCache, PromptCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from ..cache.kv_cache import PagedKVCache
 from ..cache.kv_cache.quantized import check_format as check_kv_format
-from ..logits_processors import repetition_penalty_logits_processor
+from ..logits_processors import check_vocab, make_logit_bias, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
 from ..models import load
 from ..samplers import make_sampler
 
@@ -71,6 +71,33 @@ def fused_tail_spec(processors, sampler, structuring_engine=None, tensor_paralle
     return None if spec is None else (tuple(spec), penalty, context_size)
 
 
+def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_parallel: bool = False):
+    """fused_tail_spec with the tail's token mask and logit bias: whether one _inference call can end inside the decode
+    step's configured tail, and with what -- a dict(sampler=spec or None, repetition_penalty, context_size, mask=the token-mask processor
+    or None, bias=the logit-bias processor or None), or None for the host-orchestrated branches.  Fused: the processor list is a
+    sub-sequence of (one token mask, one repetition penalty, one logit bias) in that order -- the order the kernels define -- and
+    fused_tail_spec's other conditions hold: no structuring engine, a repetition context of 1..1024, a greedy or `hip_spec` sampler,
+    no tensor parallelism."""
+    kinds = []
+    for proc in list(processors or []):
+        if hasattr(proc, "mask_fn") and hasattr(proc, "mask"):
+            kinds.append("mask")
+        elif hasattr(proc, "penalty") and hasattr(proc, "context_size"):
+            kinds.append("penalty")
+        elif hasattr(proc, "ids") and hasattr(proc, "values"):
+            kinds.append("bias")
+        else:
+            return None
+    order = [("mask", "penalty", "bias").index(k) for k in kinds]
+    if any(b <= a for a, b in zip(order, order[1:])):  # out of order, or one kind twice
+        return None
+    by_kind = dict(zip(kinds, list(processors or [])))
+    spec = fused_tail_spec([by_kind["penalty"]] if "penalty" in by_kind else [], sampler, structuring_engine, tensor_parallel)
+    if spec is None:
+        return None
+    return dict(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2], mask=by_kind.get("mask"), bias=by_kind.get("bias"))
+
+
 class InferenceEngine:
     """One model, one PromptCache, not re-entrant -- like the reference (server/app.py:23,35)."""
 
@@ -102,13 +129,19 @@ class InferenceEngine:
         return wrapped
 
     def make_processors(self, **kwargs) -> list[LogitsProcessor]:
-        """inference_engine.py:319-335: [PSE process_logits] + optional repetition penalty."""
+        """inference_engine.py:319-335: [PSE process_logits] + optional repetition penalty; around it the two processors DESIGN.md 12
+        defines -- [token mask] in front (where the PSE's masking stands), [logit bias] behind (logit_processor_factory.cpp's order).
+        token_mask: packed words, a bool mask or a callable tokens -> mask (make_token_mask); logit_bias: {token id: bias}."""
         procs: list[LogitsProcessor] = []
         if self.structuring_engine is not None:
             procs.append(self.structuring_engine.process_logits)
+        if kwargs.get("token_mask") is not None:
+            procs.append(make_token_mask(kwargs["token_mask"]))
         if kwargs.get("repetition_penalty", 1.0) != 1.0:
             procs.append(repetition_penalty_logits_processor(float(kwargs.get("repetition_penalty", 1.0)),
                                                              int(kwargs.get("context_size", 60))))
+        if kwargs.get("logit_bias"):
+            procs.append(make_logit_bias(kwargs["logit_bias"]))
         return procs
 
     def prepare_engine(self, prompt_ids, **inference_kwargs):
@@ -160,22 +193,36 @@ class InferenceEngine:
             if kv_bits is not None:
                 self._maybe_quantize(quantized_kv_start, kv_group_size, kv_bits)
             set_tail = getattr(self.model, "set_step_tail", None)
-            spec = fused_tail_spec(procs, sampler, self.structuring_engine, getattr(self.model, "tp", None) is not None) if set_tail is not None else None
+            plan = fused_tail_plan(procs, sampler, self.structuring_engine, getattr(self.model, "tp", None) is not None) if set_tail is not None else None
             offset = int(self.prompt_cache.cache[0].offset) if self.prompt_cache.cache else 0
-            if spec is not None and offset + int(ids.numel()) <= self.model.fed_ids.numel():
-                # The whole tail inside the step: penalty, log-softmax and the draw ride the replayed graph; the drawn token
-                # is fed back on the device, so a fed-back step passes nothing, whatever the sampler
-                penalised = spec[1] != 1.0
+            if plan is not None and offset + int(ids.numel()) <= self.model.fed_ids.numel():
+                # The whole tail inside the step: mask, penalty, bias, log-softmax and the draw ride the replayed graph; the
+                # drawn token is fed back on the device, so a fed-back step passes nothing, whatever the sampler
+                penalised = plan["repetition_penalty"] != 1.0
                 if penalised and not fed_back and offset > 0:  # a reused prefix: its ids may predate this configuration (fed back unrecorded, loaded from disk)
-                    seen = self.prompt_cache.computed_ids[-min(offset, spec[2]):]
+                    seen = self.prompt_cache.computed_ids[-min(offset, plan["context_size"]):]
                     self.model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
-                set_tail(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2])
+                mask, bias, recorded = plan["mask"], plan["bias"], False
+                vocab = getattr(self.model, "language_model", self.model).logprobs.numel()
+                words = None
+                if mask is not None:
+                    check_vocab(mask, vocab)
+                    words = mask.mask  # (static host words: set_step_tail refuses a mask that allows no token when it uploads them)
+                if mask is not None and mask.mask_fn is not None:
+                    # a grammar's mask depends on the tokens so far, this row's input included (the processors run after :255): the one
+                    # read-back of the fed-back token such a request pays per step, then a 16 KB upload into the replayed graph's buffer
+                    self.prompt_cache.update(ids)
+                    recorded = True
+                    words = packed_token_mask(mask.mask_fn(self.prompt_cache.computed_ids), vocab)
+                set_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
+                         token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values))
                 if pixel_values is not None and not fed_back:
                     embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
                     tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)
                 else:
                     tok, logprobs, _ = self.model.step(None if fed_back else ids, self.prompt_cache.cache)
-                self.prompt_cache.update(ids)                                  # :255 (device ids resolve lazily)
+                if not recorded:
+                    self.prompt_cache.update(ids)                              # :255 (device ids resolve lazily)
                 return tok, logprobs
             if set_tail is not None:
                 set_tail()  # the host-orchestrated branches below run on Model.step's documented greedy tail

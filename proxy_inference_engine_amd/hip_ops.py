@@ -481,6 +481,57 @@ def logits_penalty(logits: torch.Tensor, ids: torch.Tensor, penalty: float) -> t
     return logits
 
 
+def pack_token_mask(allowed, vocab_size: int) -> torch.Tensor:
+    """The token mask of structured decoding as the kernels read it: HOST int32 [ceil(V / 32)], token i is allowed iff bit i & 31 of
+    word i >> 5 is set (LSB first; bit 31 is the int32's sign).  allowed: a bool [V] tensor, or an iterable of token ids.  Host
+    arithmetic; ValueError for ids outside [0, V), a bool tensor of another length and an empty set (an all-zero mask leaves no token)."""
+    import numpy as np
+    V = int(vocab_size)
+    if V < 1:
+        raise ValueError("pack_token_mask: vocab_size must be positive")
+    if isinstance(allowed, torch.Tensor) and allowed.dtype == torch.bool:
+        if allowed.numel() != V:
+            raise ValueError(f"pack_token_mask: a bool mask needs {V} entries, got {allowed.numel()}")
+        bits = allowed.detach().reshape(-1).cpu().numpy()
+    else:
+        ids = np.asarray(allowed.detach().cpu().numpy() if isinstance(allowed, torch.Tensor) else list(allowed), dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= V):
+            raise ValueError(f"pack_token_mask: token ids must be in [0, {V})")
+        bits = np.zeros(V, dtype=bool)
+        bits[ids] = True
+    if not bits.any():
+        raise ValueError("pack_token_mask: no token is allowed")
+    words = np.packbits(np.pad(bits, (0, -V % 32)), bitorder="little").view("<u4")
+    return torch.from_numpy(words.astype(np.uint32).view(np.int32).copy())
+
+
+def logprobs_argmax_masked(logits: torch.Tensor, mask_words: torch.Tensor):
+    """logprobs_argmax with a token mask (pack_token_mask's layout, device int32 [>= ceil(V / 32)]): `logits` [V] are masked IN PLACE
+    (-inf at every disallowed id, the others keep their bits), then (token int32 [1], logprobs fp32 [V]) are logprobs_argmax of them."""
+    _dev(logits), _dev(mask_words)
+    if not logits.is_contiguous() or mask_words.dtype != torch.int32 or mask_words.dim() != 1 or mask_words.stride(0) != 1:
+        raise ValueError("logprobs_argmax_masked: contiguous logits and contiguous int32 mask words")
+    V = logits.numel()
+    lp = torch.empty(V, dtype=torch.float32, device=logits.device)
+    tok = torch.empty(1, dtype=torch.int32, device=logits.device)
+    _ffi.check(_ffi.load().pie_logprobs_argmax_masked(_ffi.p(logits), V, _ffi.dtype_code(logits.dtype), _ffi.p(mask_words), mask_words.numel(),
+                                                      _ffi.p(lp), _ffi.p(tok), _ffi.stream()))
+    return tok, lp
+
+
+def logits_bias(logits: torch.Tensor, ids: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """logit_bias on 16-bit logits [V], IN PLACE: logits[ids[t]] = T(f32(logits[ids[t]]) + bias[t]) (one fp32 addition, one rounding) for
+    every entry whose id is in [0, V) and not held by an earlier entry; ids device int32 [n], bias device float32 [n], 1 <= n <= 1024.
+    Returns logits."""
+    _dev(logits), _dev(ids), _dev(bias)
+    if not logits.is_contiguous() or ids.dtype != torch.int32 or bias.dtype != torch.float32 or not ids.is_contiguous() or not bias.is_contiguous() or \
+            ids.numel() != bias.numel():
+        raise ValueError("logits_bias: contiguous logits, contiguous int32 ids and as many contiguous float32 biases")
+    _ffi.check(_ffi.load().pie_logits_bias(_ffi.p(logits), logits.numel(), _ffi.dtype_code(logits.dtype), _ffi.p(ids), _ffi.p(bias), ids.numel(),
+                                           _ffi.stream()))
+    return logits
+
+
 def qkv_row_map(n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
     n = (n_heads + 2 * n_kv_heads) * head_dim
     arr = (C.c_int32 * n)()

@@ -296,6 +296,8 @@ class Model:
         # __call__ copy explicit ids in, device to device; the decode step records a fed-back token itself
         self.fed_ids = torch.zeros(self.history.numel(), dtype=torch.int32, device=device)
         self._tail = _GREEDY_TAIL
+        # the tail's token mask and logit bias (set_step_tail): buffers at stable addresses, made when first used; (mask on, bias entries)
+        self._mask_words, self._bias_table, self._edits, self._edit_src = None, None, (False, 0), (None, None)
         self._kv = KVBinding(lib, self._dec, len(self.layers), self.n_kv_heads, self.head_dim, self.dtype, device, tensor_parallel=tp is not None)
         self._page_pool, self._page_blocks = None, 16
         self._batch_bufs: dict = {}
@@ -359,13 +361,21 @@ class Model:
         return [PagedKVCache(seq, i) for i in range(len(self.layers))]
 
     # ------------------------------------------------------------------ the step's tail
-    def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60) -> None:
-        """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler), inside the replayed graph:
+    def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
+                      token_mask=None, logit_bias=None) -> None:
+        """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
+        DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
         samplers' random stream (samplers.seed) -- the returned token is then the drawn one; repetition_penalty != 1.0 with context_size
         1..1024: the penalty over the last context_size fed ids (`fed_ids`), applied to the returned logits before the log-softmax.
+        token_mask: packed int32 words (hip_ops.pack_token_mask; host or device) -- a disallowed id is -inf in the returned logits,
+        whatever else is configured; logit_bias: (ids, values), 1..1024 entries added after the penalty.  The model owns one mask buffer
+        and one bias table at stable addresses and copies the contents in, in stream order: new words every token are a copy and a
+        replay, not a re-capture (a new number of bias entries is one).  A mask tensor, or a pair of bias sequences, already uploaded is not copied
+        again: pass new objects for new contents.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
+        self._set_tail_edits(token_mask, logit_bias)
         pen = (float(repetition_penalty), int(context_size)) if repetition_penalty != 1.0 and context_size != 0 else None
         seed = counter = None
         if sampler is not None:
@@ -387,10 +397,53 @@ class Model:
                                                    _ffi.p(ws), ws.numel() * 8))
         self._tail = tail
 
+    def _set_tail_edits(self, token_mask, logit_bias) -> None:
+        """The mask words and the bias table into the model's own buffers; the library is asked only when an edit is switched on or
+        off or the number of bias entries changes (the addresses never do)."""
+        lib = _ffi.load()
+        V = self.logprobs.numel()
+        if token_mask is not None and token_mask is not self._edit_src[0]:
+            words = token_mask.reshape(-1)
+            if words.dtype != torch.int32 or words.numel() < (V + 31) // 32:
+                raise ValueError(f"set_step_tail: token_mask is {(V + 31) // 32} packed int32 words (hip_ops.pack_token_mask)")
+            if not words.is_cuda:  # seen on the host: a mask that allows no token below V is refused here, not decoded as token 0
+                from ...logits_processors import packed_token_mask
+                words = packed_token_mask(words, V)
+            if self._mask_words is None:
+                self._mask_words = torch.zeros((V + 31) // 32, dtype=torch.int32, device=self.device)
+            self._mask_words.copy_(words[:self._mask_words.numel()])
+        n = 0
+        if logit_bias is not None:
+            ids, values = logit_bias
+            n = len(ids)
+            if not 1 <= n <= 1024 or len(values) != n:
+                raise ValueError("set_step_tail: logit_bias is (ids, values) with 1..1024 entries each")
+            prev = self._edit_src[1]
+            if prev is None or ids is not prev[0] or values is not prev[1]:  # (the same two objects: uploaded already)
+                if self._bias_table is None:
+                    self._bias_table = (torch.zeros(1024, dtype=torch.int32, device=self.device), torch.zeros(1024, dtype=torch.float32, device=self.device))
+                self._bias_table[0][:n].copy_(torch.as_tensor(ids, dtype=torch.int32))
+                self._bias_table[1][:n].copy_(torch.as_tensor(values, dtype=torch.float32))
+        self._edit_src = (token_mask, logit_bias)
+        if (token_mask is not None) != self._edits[0]:
+            _ffi.check(lib.pie_decoder_set_logits_mask(self._dec, _ffi.p(self._mask_words) if token_mask is not None else None,
+                                                       self._mask_words.numel() if token_mask is not None else 0))
+            self._edits = (token_mask is not None, self._edits[1])
+        if n != self._edits[1]:
+            _ffi.check(lib.pie_decoder_set_logit_bias(self._dec, _ffi.p(self._bias_table[0]) if n else None, _ffi.p(self._bias_table[1]) if n else None, n))
+            self._edits = (self._edits[0], n)
+
     @property
     def step_tail(self) -> tuple:
         """(sampler or None, (penalty, context_size) or None): what set_step_tail last configured."""
         return self._tail[:2]
+
+    @property
+    def step_tail_edits(self) -> tuple:
+        """(token mask or None, logit bias or None) as set_step_tail last configured them: the model's device buffers -- the packed
+        int32 words, and (ids int32 [n], values float32 [n])."""
+        on, n = self._edits
+        return (self._mask_words if on else None, (self._bias_table[0][:n], self._bias_table[1][:n]) if n else None)
 
     def _feed(self, ids: torch.Tensor, offset: int) -> None:
         """fed_ids[offset : offset + L] = ids (device int32 [L]); positions beyond the buffer are not recorded (the penalty's window skips them)."""
@@ -503,7 +556,7 @@ class Model:
         else:
             ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None):  # (the several-prompts pass ends in the greedy tail only)
+            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0):  # (the several-prompts pass ends in the greedy tail only)
                 # A fresh prompt on int8 pages: the single-sequence prompt pass reads T pages (it would run the prompt as L decode steps,
                 # ~1.2 ms per token), the several-prompts pass quantises into int8 pages -- one prompt is a batch of one.
                 nxt, logprobs, logits = self.prefill_batch([ids.cpu().numpy()], [cache])  # (a prompt arrives once: the host copy is the pass's own row bookkeeping)
