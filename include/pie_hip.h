@@ -284,6 +284,26 @@ int pie_sample_rows(const float *logprobs, int rows, int V, pie_row_tail *table,
 int pie_logits_penalty_rows(void *logits, int rows, int V, int dtype, const pie_row_tail *table, int32_t *recent_ids, const int32_t *ids,
                             const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream);
 
+/* ---------------------------------------------------------------- top-n log-probabilities
+ * get_top_logprobs (engine/utils.py:4-48) on the device, sort-free: for every row of fp32 log-probabilities [rows, V] the n best
+ * (id, value) pairs and the chosen token's own, n 1..PIE_TOP_LOGPROBS_MAX.  tokens (nullable) DEVICE int32 [rows]; count (nullable)
+ * DEVICE int32 [rows].
+ *   rank    ids are ranked by (key(lp[id]) descending, id ascending), key = the samplers' order-preserving 32-bit key: float order, with
+ *           +0.0 above -0.0 and NaNs placed by their bits; ties go to the lowest id, the samplers' rule at the top-k boundary
+ *   output  out_ids int32 [rows, n + 1], out_vals fp32 [rows, n + 1].  Slot 0: (tokens[r], lp[r][tokens[r]]), or (-1, -inf) when tokens is
+ *           NULL or the id lies outside [0, V) (never indexed).  Slots 1..m, m = min(c, V): the first m ids in rank order with bit copies
+ *           of their values.  Slots m + 1..n: (-1, -inf)
+ *   count   c = count ? count[r] : n, read on the device and not trusted: c > n acts as n; c == 0 writes slot 0 and the fill; c < 0 leaves
+ *           the row's record untouched (its workgroups return at once)
+ * Two launches (slices of 512 ids, then one workgroup per row), deterministic: no atomics, nothing depends on arrival order.  workspace:
+ * pie_top_logprobs_workspace_bytes(rows, V, n) bytes of device memory, 8-byte aligned; needs no initialisation and carries nothing from call
+ * to call (0 is returned for sizes the op refuses).  n outside 1..20: PIE_E_ARG; rows < 1, V < 1 or V > 524288: PIE_E_SHAPE; logprobs,
+ * tokens, count or an output not 4-byte aligned, or the workspace not 8-byte aligned: PIE_E_ALIGN -- each before any launch. */
+enum { PIE_TOP_LOGPROBS_MAX = 20 };
+size_t pie_top_logprobs_workspace_bytes(int rows, int V, int n);
+int pie_top_logprobs(const float *logprobs, int rows, int V, int n, const int32_t *tokens, const int32_t *count, int32_t *out_ids, float *out_vals,
+                     void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- fused decode step
  * One forward of Model.__call__ (models/llama/language.py:199-210) for inputs[1,1] over per-layer
  * ReusableKVCache buffers (cache/kv_cache/reusable.py:96-142) followed by the tail of _inference
@@ -490,6 +510,22 @@ int pie_decoder_set_logit_bias(pie_decoder *d, const int32_t *ids, const float *
 int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap, int32_t *recent_ids, void *workspace);
 unsigned long long pie_decoder_batch_graph_replays(const pie_decoder *d);
 int pie_decoder_batch_graph_launches(const pie_decoder *d);
+/* Top-n log-probabilities inside the passes: pie_top_logprobs as the last launches of a tail, after the token is final.
+ * pie_decoder_set_top_logprobs: the single-sequence step.  Applies wherever the configured tail applies (above: eager and PIE_STEP_GRAPH
+ *   steps, the last row of pie_decoder_prefill / _prefill_embeds with logits_all == NULL), after the draw: slot 0 is the token that is fed
+ *   back, on every KV binding.  out_ids int32 [n + 1], out_vals fp32 [n + 1], workspace of at least pie_top_logprobs_workspace_bytes(1, vocab, n)
+ *   bytes (workspace_bytes; smaller: PIE_E_SHAPE), all caller-owned DEVICE memory, alive while set.  n == 0 switches it off; a decoder that does
+ *   not set it launches exactly what it launches without; setting it, a new n or a new address drops the captured graphs;
+ *   pie_decoder_graph_launches counts its 2 launches.
+ * pie_decoder_set_batch_top_logprobs: pie_decoder_step_batch (eager or PIE_STEP_GRAPH), _prefill_batch and _step_mixed, after next_tokens
+ *   are final (after pie_sample_rows with a batch tail, after the argmax without: the two settings are independent).  Record s = output
+ *   row s (pie_decoder_set_batch_tail's row order): out_ids int32 [rows_cap, n + 1], out_vals fp32 [rows_cap, n + 1], count DEVICE int32
+ *   [rows_cap] (NULL: n in every row) whose CONTENTS may change between calls while a captured step keeps replaying; workspace
+ *   pie_top_logprobs_workspace_bytes(rows_cap, vocab, n) bytes.  The addresses, n and rows_cap are part of the captured graph's key.
+ *   n == 0 switches it off.  A pass with more output rows than rows_cap is PIE_E_SHAPE before any launch.
+ * Both: the op's argument rules; tensor-parallel decoders refuse (PIE_E_STATE). */
+int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float *out_vals, void *workspace, size_t workspace_bytes);
+int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int32_t *out_ids, float *out_vals, const int32_t *count, void *workspace);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -16,6 +16,7 @@ PIE_BF16, PIE_F16 = 1, 2
 PIE_STEP_LOGITS, PIE_STEP_GRAPH = 1, 2
 PIE_OPT_KV_I8 = 2
 PIE_SAMPLE_GREEDY = -1  # pie_decoder_set_sampler: the greedy tail
+PIE_TOP_LOGPROBS_MAX = 20  # pie_top_logprobs: the largest n
 # test / tuning switches (include/pie_hip.h: pie_set_knob); -1 restores a default
 KNOBS = {"prefill_min": 0, "prefill_chunk": 1, "prefill_resident": 2, "small_m": 3, "w4l_slabs": 4, "prefill_attn_valu": 5,
          "prefill_qt": 6, "attn_merge_max_cap": 7, "attn_warm_max_mb": 8, "w4r": 9, "fuse_attn": 10, "attn_merge_in_launch": 11}
@@ -47,6 +48,7 @@ EXPORTS = [
     "pie_logits_penalty", "pie_decoder_set_logits_penalty", "pie_decoder_set_sampler",
     "pie_logprobs_argmax_masked", "pie_logits_bias", "pie_decoder_set_logits_mask", "pie_decoder_set_logit_bias",
     "pie_row_tail_bytes", "pie_row_tail_pack", "pie_sample_rows", "pie_logits_penalty_rows", "pie_decoder_set_batch_tail", "pie_decoder_batch_graph_replays", "pie_decoder_batch_graph_launches",
+    "pie_top_logprobs_workspace_bytes", "pie_top_logprobs", "pie_decoder_set_top_logprobs", "pie_decoder_set_batch_top_logprobs",
 ]
 
 
@@ -145,6 +147,11 @@ def load() -> C.CDLL:
     lib.pie_decoder_batch_graph_replays.argtypes = [C.c_void_p]
     lib.pie_decoder_batch_graph_replays.restype = C.c_uint64
     lib.pie_decoder_batch_graph_launches.argtypes = [C.c_void_p]
+    lib.pie_top_logprobs_workspace_bytes.restype = C.c_size_t
+    lib.pie_top_logprobs_workspace_bytes.argtypes = [C.c_int] * 3
+    lib.pie_top_logprobs.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 6
+    lib.pie_decoder_set_top_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.pie_decoder_set_batch_top_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

@@ -157,7 +157,7 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
 }
 
 // The configured tail over the bound outputs (include/pie_hip.h): penalty and / or bias (one launch) + fresh partials, which apply the token
-// mask on their way | finish | the sampler's launches.
+// mask on their way | finish | the sampler's launches | the top-n log-probabilities' two.
 // from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
 static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
@@ -177,9 +177,14 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
         stats = d->tail_stats, n_stats = TAIL_STAT_TILES;
     }
     if ((rc = logits_tail_launch(c.dtype, d->logits, c.vocab, stats, n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st))) return rc;
-    if (d->smp_mode == PIE_SAMPLE_GREEDY) return PIE_OK;
-    const SampleFeed feed = {&d->state->token, &d->state->pos, d->history, d->hist_cap};
-    return sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st);
+    if (d->smp_mode != PIE_SAMPLE_GREEDY) {
+        const SampleFeed feed = {&d->state->token, &d->state->pos, d->history, d->hist_cap};
+        if ((rc = sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st)))
+            return rc;
+    }
+    if (!d->tlp_n) return PIE_OK;
+    // last, after the draw: slot 0 is the token that is fed back
+    return top_logprobs_launch(d->logprobs, 1, c.vocab, d->tlp_n, d->token_out, nullptr, d->tlp_ids, d->tlp_vals, d->tlp_ws, st);
 }
 
 // One launch of the step's sequence (PIE_K_* of include/pie_hip.h); `li` is the layer for per-layer kernels.
@@ -848,6 +853,34 @@ int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int
     const bool changed = d->smp_mode != mode || d->smp_temp != temp || d->smp_p != p || d->smp_k != k || d->smp_seed != seed || d->smp_counter != counter || d->smp_ws != workspace;
     d->smp_mode = mode, d->smp_temp = temp, d->smp_p = p, d->smp_k = k, d->smp_seed = seed, d->smp_counter = counter, d->smp_ws = workspace;
     if (changed) drop_graphs(d);
+    return PIE_OK;
+}
+
+int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float *out_vals, void *workspace, size_t workspace_bytes) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_top_logprobs: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_top_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (n == 0) out_ids = nullptr, out_vals = nullptr, workspace = nullptr;
+    else {
+        PIE_REQUIRE(d->out_set, PIE_E_STATE, "pie_decoder_set_top_logprobs: bind_outputs must be called first");
+        if (int rc = top_logprobs_check("pie_decoder_set_top_logprobs", 1, d->cfg.vocab, n, true, d->logprobs, d->token_out, nullptr, out_ids, out_vals, workspace)) return rc;
+        PIE_REQUIRE(workspace_bytes >= pie_top_logprobs_workspace_bytes(1, d->cfg.vocab, n), PIE_E_SHAPE,
+                    "pie_decoder_set_top_logprobs: the workspace is smaller than pie_top_logprobs_workspace_bytes(1, vocab, n)");
+    }
+    if (d->tlp_n != n || d->tlp_ids != out_ids || d->tlp_vals != out_vals || d->tlp_ws != workspace) drop_graphs(d);  // every one of them is a launch argument
+    d->tlp_n = n, d->tlp_ids = out_ids, d->tlp_vals = out_vals, d->tlp_ws = workspace;
+    return PIE_OK;
+}
+
+int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int32_t *out_ids, float *out_vals, const int32_t *count, void *workspace) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_top_logprobs: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_top_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (n == 0) {
+        d->btl_n = 0, d->btl_rows_cap = 0, d->btl_ids = nullptr, d->btl_vals = nullptr, d->btl_count = nullptr, d->btl_ws = nullptr;
+        return PIE_OK;
+    }
+    // (a pass is handed its logprobs per call: their alignment is checked there, with rows <= rows_cap)
+    if (int rc = top_logprobs_check("pie_decoder_set_batch_top_logprobs", rows_cap, d->cfg.vocab, n, false, nullptr, nullptr, count, out_ids, out_vals, workspace)) return rc;
+    d->btl_n = n, d->btl_rows_cap = rows_cap, d->btl_ids = out_ids, d->btl_vals = out_vals, d->btl_count = count, d->btl_ws = workspace;  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "kv_quant.hpp"
 #include "sampler.hpp"
 #include "tail.hpp"
+#include "top_logprobs.hpp"
 #include "w4_gemv.hpp"
 
 // The step's attention: its own launch | behind the q|k|v launch's seam, merged by o_proj's prologue | behind the seam and merged there
@@ -97,9 +98,20 @@ struct pie_decoder {
     int bt_rows_cap = 0;
     int *bt_recent = nullptr;
     void *bt_ws = nullptr;
+    // Top-n log-probabilities (pie_decoder_set_top_logprobs / _set_batch_top_logprobs): pie_top_logprobs' launches behind the
+    // step's configured tail (tlp_n > 0) and behind the multi-sequence passes' tail (btl_n > 0).  Caller-owned; all launch arguments.
+    int tlp_n = 0;
+    int *tlp_ids = nullptr;
+    float *tlp_vals = nullptr;
+    void *tlp_ws = nullptr;
+    int btl_n = 0, btl_rows_cap = 0;
+    int *btl_ids = nullptr;
+    float *btl_vals = nullptr;
+    const int *btl_count = nullptr;
+    void *btl_ws = nullptr;
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
-    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n; }
+    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)

@@ -836,17 +836,27 @@ static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
 // What follows the lm_head of `rows` output rows.  No table set: the greedy tail, as ever.  A table (pie_decoder_set_batch_tail):
 // every row's own penalty over its own window first (ids / ctx / out_rows: the pass's input ids, context lengths and, where output row s
 // is not source row s, its source rows), then the same log-softmax + argmax, then every row's own sampler over the fp32 log-probabilities.
+// The rows' top-n log-probability records (pie_decoder_set_batch_top_logprobs), once next_tokens are final.  Off: nothing is launched.
+static int batch_top_logprobs_launch(pie_decoder *d, int rows, const float *logprobs, const int32_t *next_tokens, hipStream_t st) {
+    if (!d->btl_n) return PIE_OK;
+    return top_logprobs_launch(logprobs, rows, d->cfg.vocab, d->btl_n, next_tokens, d->btl_count, d->btl_ids, d->btl_vals, d->btl_ws, st);
+}
+
 static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *ctx, const int32_t *out_rows, int n_src, int rows, u16 *logits,
                              float *logprobs, int32_t *next_tokens, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     PrefillScratch *s = d->prefill;
-    if (!d->bt_table) return logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st);
+    int rc;
+    if (!d->bt_table) {
+        if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
+        return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
+    }
     PenRowsArgs p = {};
     p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = d->bt_table, p.recent = d->bt_recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
-    int rc = logits_penalty_rows_launch(c.dtype, p, rows, st);
-    if (rc) return rc;
+    if ((rc = logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
     if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
-    return sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st);
+    if ((rc = sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st))) return rc;
+    return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
 }
 
 // ---------------------------------------------------------------- one decode step for B sequences (continuous batching)
@@ -912,7 +922,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         else
             hipLaunchKernelGGL(k_logits_finish<F16>, fg, dim3(256), 0, st, logits, c.vocab, s->tail_stats, lm_waves, logprobs, next_tokens, (DecState *)nullptr, (int *)nullptr, 0, (const unsigned *)nullptr);
         PIE_LAUNCH_CHECK();
-        return PIE_OK;
+        return batch_top_logprobs_launch(d, B, logprobs, next_tokens, st);
     }
     if ((rc = embed_rows(d, tokens, B, s->x, st))) return rc;
     hipLaunchKernelGGL(k_rope_cs_rows, dim3(B), dim3(64), 0, st, d->glob.rope_freqs, nullptr, ctx_len, D / 2, s->rope_cs);
@@ -1042,6 +1052,8 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     PIE_REQUIRE(d->glob_set, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: set_globals must be called first");
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: a layer has no weights (pie_decoder_set_layer)");
     PIE_REQUIRE(!d->bt_table || S <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch tail's rows_cap");
+    PIE_REQUIRE(!d->btl_n || S <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the top log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
     PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_prefill_batch / _step_mixed: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
@@ -1095,6 +1107,8 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_step_batch: a layer has no weights (pie_decoder_set_layer)");
     PIE_REQUIRE(B >= 1 && B <= 4096 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_step_batch: bad batch shape");
     PIE_REQUIRE(!d->bt_table || B <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch tail's rows_cap");
+    PIE_REQUIRE(!d->btl_n || B <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the top log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_step_batch: logprobs need 4-byte alignment");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_step_batch: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
     const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
@@ -1109,6 +1123,8 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
                                   (uintptr_t)next_tokens, (uintptr_t)n_pages, (uintptr_t)max_blocks, (uintptr_t)B, (uintptr_t)d->kv_i8 /* the page format is baked into the launches too */};
     for (int i = 0; i < d->cfg.n_layers; ++i) key.push_back((uintptr_t)slabs[i]);
     for (uintptr_t v : {(uintptr_t)d->bt_table, (uintptr_t)d->bt_recent, (uintptr_t)d->bt_ws, (uintptr_t)d->bt_rows_cap}) key.push_back(v);  // the tail's launches bake them in
+    for (uintptr_t v : {(uintptr_t)d->btl_n, (uintptr_t)d->btl_rows_cap, (uintptr_t)d->btl_ids, (uintptr_t)d->btl_vals, (uintptr_t)d->btl_count, (uintptr_t)d->btl_ws})
+        key.push_back(v);  // and so do the top log-probabilities'
     if (!d->prefill) d->prefill = new PrefillScratch();
     PrefillScratch *s = d->prefill;
     if (s->batch_graph && s->batch_key == key && s->batch_gen == s->alloc_gen) {

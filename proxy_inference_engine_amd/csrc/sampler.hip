@@ -55,12 +55,6 @@ __device__ __forceinline__ float gumbel(unsigned r) {
     const float u = ((float)(r >> 8) + 0.5f) * 0x1p-24f;  // (0, 1), never 0 or 1
     return -logf(-logf(u));
 }
-// order-preserving key of a float (larger float <-> larger key)
-__device__ __forceinline__ unsigned okey(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float okey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 enum { SMP_CATEGORICAL = 0, SMP_TOP_K = 1, SMP_TOP_P = 2, SMP_MIN_P = 3 };
 

@@ -2,6 +2,13 @@
 #pragma once
 #include "common.hpp"
 
+// order-preserving key of a float (larger float <-> larger key); shared with top_logprobs.hip, whose rank order is this key's
+__device__ __forceinline__ unsigned okey(float v) {
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float okey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
 // Where the decode step's tail wants the drawn id besides `tokens` (rows = 1): the device-side state's fed-back token and the token history
 // at the (already advanced) position *pos.  All null: a plain pie_sample.
 struct SampleFeed {

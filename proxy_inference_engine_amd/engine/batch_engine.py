@@ -7,16 +7,19 @@ wait in a queue, join the batch when a slot and enough pages are free -- their p
 in flight (`Model.step_mixed`: both kinds of sequence in one pass over the weights, as BatchDetails holds both), or run as a
 prompt pass of their own when nothing is decoding -- every step decodes all active sequences with one pass over the weights
 (`Model.step_batch`), finished sequences leave and return their pages.  Greedy by default; `generate(sampling=...)` gives every request
-its own `SamplingParams`, run per row inside the passes; `sampler` maps a [B, V] log-probability block to B token ids."""
+its own `SamplingParams`, run per row inside the passes (DESIGN.md 11); `sampler` maps a [B, V] log-probability block to B token ids;
+`generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes."""
 from __future__ import annotations
 
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, Iterable
 
+import numpy as np
 import torch
 
 from ..cache.kv_cache.paged import TOKEN_CAPACITY_PER_PAGE
+from .inference_engine import host_record_to_map
 
 
 @dataclass
@@ -65,6 +68,7 @@ class _Active:
     cache: list
     token: torch.Tensor           # [1] int32 on the device: the input of the next step
     generated: list = field(default_factory=list)
+    rec: torch.Tensor | None = None   # int32 [2 (n + 1)] on the device: the top-n record of `token` (ids, then the values' bits); None: not asked for
 
 
 class BatchedEngine:
@@ -96,11 +100,25 @@ class BatchedEngine:
     def _pages_for(self, n_tokens: int) -> int:
         return (n_tokens + TOKEN_CAPACITY_PER_PAGE - 1) // TOKEN_CAPACITY_PER_PAGE
 
-    def generate(self, prompts: list, max_new_tokens: int, sampling: SamplingParams | list | None = None) -> list[list[int]]:
+    def generate(self, prompts: list, max_new_tokens: int, sampling: SamplingParams | list | None = None, logprobs: bool = False,
+                 top_logprobs: int | list = 0):
         """Token ids generated for every prompt (in order), at most max_new_tokens each, ending early at a stop token.
         sampling: None (greedy, or the constructor's `sampler`), one SamplingParams for every request, or one per prompt: each request's
         own sampler, seed and repetition penalty, applied to its row inside every pass (Model.set_batch_tail) -- a request's tokens depend
-        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters."""
+        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters.
+        logprobs=True: returns (outputs, maps) -- maps[i][j] is the {token id: log-probability} dict of outputs[i][j], as
+        InferenceEngine.generate yields it: the best top_logprobs pairs by decreasing log-probability (ties: lowest id first), then the
+        token itself when absent.  top_logprobs: one int for every request or one per prompt, each 0..20; ignored with logprobs=False.  The
+        records are selected per row inside the passes (Model.set_batch_top_logprobs) and fetched in the per-pass read-back of the tokens."""
+        tops = None
+        if logprobs:
+            if self.sampler is not None:
+                raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
+            tops = [top_logprobs] * len(prompts) if isinstance(top_logprobs, int) else list(top_logprobs)
+            if len(tops) != len(prompts):
+                raise ValueError("generate: `top_logprobs` is one int or one per prompt")
+            if not all(isinstance(n, int) and not isinstance(n, bool) and 0 <= n <= 20 for n in tops):
+                raise ValueError("generate: every `top_logprobs` is an int in 0..20")
         if sampling is not None:
             if self.sampler is not None:
                 raise ValueError("generate: `sampling` and the constructor's `sampler` callable exclude each other")
@@ -114,17 +132,27 @@ class BatchedEngine:
             if all(sp.plain for sp in params):
                 sampling = None               # nothing to configure: today's passes
         if max_new_tokens < 1:
-            return [[] for _ in prompts]
-        if sampling is None:
+            return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
+        if sampling is None and tops is None:
             return self._generate(prompts, max_new_tokens, None)
-        self.model.set_batch_tail(self.max_batch)
-        self.model.write_batch_tail(list(range(self.max_batch)), [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
         try:
-            return self._generate(prompts, max_new_tokens, (params, seeds))
+            if sampling is not None:
+                self.model.set_batch_tail(self.max_batch)
+                self.model.write_batch_tail(list(range(self.max_batch)), [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
+            if tops is None:
+                return self._generate(prompts, max_new_tokens, (params, seeds))
+            bufs = self.model.set_batch_top_logprobs(self.max_batch, max(max(tops, default=1), 1))
+            bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
+            maps: list = [[] for _ in prompts]
+            out = self._generate(prompts, max_new_tokens, None if sampling is None else (params, seeds), (tops, bufs, maps))
+            return out, maps
         finally:
-            self.model.clear_batch_tail()
+            if sampling is not None:
+                self.model.clear_batch_tail()
+            if tops is not None:
+                self.model.clear_batch_top_logprobs()
 
-    def _generate(self, prompts: list, max_new_tokens: int, tails) -> list[list[int]]:
+    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None) -> list[list[int]]:
         for p in prompts:
             if self._pages_for(len(p) + max_new_tokens) > self.pool.size():
                 raise ValueError("a prompt does not fit the page pool")
@@ -146,7 +174,7 @@ class BatchedEngine:
             P = lcp // TOKEN_CAPACITY_PER_PAGE * TOKEN_CAPACITY_PER_PAGE
             if P and self._pages_for(P) + self._pages_for(max(len(p) for p in prompts) - P + max_new_tokens) <= self.pool.size():
                 root = self.model.make_cache()
-                self.model.step_mixed(None, [], [list(first[:P])], [root])    # one pass over the prefix; its pages are shared from here on
+                self.model.step_mixed(None, [], [list(first[:P])], [root])    # one pass over the prefix; its pages are shared from here on (no top-n record: every count is still -1)
                 reserved = self.shared_pages = P // TOKEN_CAPACITY_PER_PAGE
             else:
                 P = 0
@@ -158,11 +186,23 @@ class BatchedEngine:
             return [type(root[0])(seq, i) for i in range(len(root))]
         filling: list = []            # chunked prefill: [request, prompt, cache, rows done] of admitted prompts not yet fully in their pages
         slots: list = []              # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
+        counts: list = []             # top-n records: the count the device holds for row s (-1: the row reports nothing)
 
         def seat(rows: list) -> None:
             """The coming pass's output rows, in order: a request index (its own record; its ring rows from the ids it has been fed) or
             None (a prompt still filling: greedy, its token is discarded).  Rewrites the rows whose occupant changed -- the moment at which
-            step_batch rewrites the block table; a row a request keeps is left alone (its `calls` advances on the device)."""
+            step_batch rewrites the block table; a row a request keeps is left alone (its `calls` advances on the device).  The rows' top-n
+            counts follow the same rule: a request's own top_logprobs, -1 for a prompt still filling."""
+            if tops is not None:
+                want_c = [-1 if r is None else tops[0][r] for r in rows]
+                counts.extend([-1] * (len(want_c) - len(counts)))
+                changed = [s_ for s_, c_ in enumerate(want_c) if counts[s_] != c_]
+                if changed:
+                    dev = tops[1]["count"].device
+                    tops[1]["count"].index_copy_(0, torch.tensor(changed, dtype=torch.long, device=dev),
+                                                 torch.tensor([want_c[s_] for s_ in changed], dtype=torch.int32, device=dev))
+                    for s_ in changed:
+                        counts[s_] = want_c[s_]
             if tails is None:
                 return
             params, seeds = tails
@@ -189,14 +229,27 @@ class BatchedEngine:
             self.model.write_batch_tail(idx, recs, fed)
 
         def lone_step(idx) -> bool:
-            """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record of its own."""
-            return tails is None or tails[0][idx].plain
+            """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record of its own, or wants
+            log-probabilities: then it is a batch of one."""
+            return tops is None and (tails is None or tails[0][idx].plain)
+
+        def records(n_rows: int):
+            """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'
+            bits): row views of it outlive the next pass.  None when log-probabilities are not asked for."""
+            if tops is None:
+                return [None] * n_rows
+            return torch.cat([tops[1]["ids"][:n_rows], tops[1]["vals"][:n_rows].view(torch.int32)], dim=1)
         while pending or active or filling:
             # every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
             if active:
-                host = torch.cat([a.token for a in active]).tolist()      # one read-back per pass for the stop / length checks
+                # one read-back per pass for the stop / length checks -- and, in the same copy, the tokens' top-n records
+                host = torch.cat([a.token for a in active] + ([a.rec for a in active] if tops is not None else [])).cpu().numpy()
+                if tops is not None:
+                    recs = host[len(active):].reshape(len(active), 2, -1)
+                    for a, r in zip(active, recs):
+                        tops[2][a.request].append(host_record_to_map(r[0], r[1].view(np.float32), tops[0][a.request])[1])
                 keep = []
-                for a, t in zip(active, host):
+                for a, t in zip(active, host[:len(active)].tolist()):
                     a.generated.append(int(t))
                     if int(t) in self.stop_tokens or len(a.generated) >= max_new_tokens:
                         out[a.request] = a.generated
@@ -239,6 +292,7 @@ class BatchedEngine:
                 self.steps += 1
                 self.mixed_passes += bool(active)
                 nb = len(active)
+                recs = records(nb + len(take))
                 if self.sampler is not None:
                     # the sampler sees generation steps only: the decode rows and the rows of prompts whose LAST chunk is in this pass; the row
                     # of a prompt that is still filling is discarded (its greedy id stands in), so a seeded sampler's stream and a stateful
@@ -249,11 +303,11 @@ class BatchedEngine:
                         nxt = nxt.clone()
                         nxt[idx] = self.sampler(logprobs[idx]).reshape(-1).to(torch.int32)
                 for i, a in enumerate(active):
-                    a.token = nxt[i:i + 1]
+                    a.token, a.rec = nxt[i:i + 1], recs[i]
                 for i, (f, n) in enumerate(take):
                     f[3] += n
                     if f[3] == len(f[1]):                                 # its last chunk: the row's token is the request's first
-                        active.append(_Active(f[0], f[2], nxt[nb + i:nb + i + 1]))
+                        active.append(_Active(f[0], f[2], nxt[nb + i:nb + i + 1], rec=recs[nb + i]))
                 filling = [f for f in filling if f[3] < len(f[1])]
                 continue
             # Worth it while the decode rows do not push the prompt rows into another 256-row GEMM tile: 8 sequences + a prompt of
@@ -270,10 +324,11 @@ class BatchedEngine:
                 if self.sampler is not None:
                     nxt = self.sampler(logprobs).reshape(-1).to(torch.int32)
                 nb = len(active)
+                recs = records(nb + len(batch))
                 for i, a in enumerate(active):
-                    a.token = nxt[i:i + 1]
+                    a.token, a.rec = nxt[i:i + 1], recs[i]
                 for i, (idx, _, cache) in enumerate(batch):
-                    active.append(_Active(idx, cache, nxt[nb + i:nb + i + 1]))
+                    active.append(_Active(idx, cache, nxt[nb + i:nb + i + 1], rec=recs[nb + i]))
                 continue
             joined = []
             if self._i8 and batch and (len(batch) == 1 or not self.batch_prefill):
@@ -282,20 +337,21 @@ class BatchedEngine:
                     toks, logprobs, _ = self.model.prefill_batch([prompt], [cache])
                     if self.sampler is not None:
                         toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
-                    joined.append(_Active(idx, cache, toks[:1].clone()))
+                    joined.append(_Active(idx, cache, toks[:1].clone(), rec=records(1)[0]))
             elif P and batch:                                            # suffixes behind the shared prefix: prompts continuing a cached prefix
                 seat([idx for idx, _, _ in batch])
                 toks, logprobs, _ = self.model.step_mixed(None, [], [p for _, p, _ in batch], [c for _, _, c in batch])
                 if self.sampler is not None:
                     toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
+                recs = records(len(batch))
                 for i, (idx, _, cache) in enumerate(batch):
-                    joined.append(_Active(idx, cache, toks[i:i + 1].clone()))
+                    joined.append(_Active(idx, cache, toks[i:i + 1].clone(), rec=recs[i]))
             elif len(batch) == 1 or (batch and not self.batch_prefill):
                 for idx, prompt, cache in batch:
                     if not lone_step(idx):                                # its first token is drawn by its own sampler: a batch of one
                         seat([idx])
                         toks, _, _ = self.model.prefill_batch([prompt], [cache])
-                        joined.append(_Active(idx, cache, toks[:1].clone()))
+                        joined.append(_Active(idx, cache, toks[:1].clone(), rec=records(1)[0]))
                         continue
                     ids = torch.as_tensor(prompt, dtype=torch.int32).reshape(-1)
                     tok, logprobs, _ = self.model.step(ids.to(self.model.device), cache)
@@ -307,16 +363,18 @@ class BatchedEngine:
                 toks, logprobs, _ = self.model.prefill_batch([p for _, p, _ in batch], [c for _, _, c in batch])
                 if self.sampler is not None:
                     toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
+                recs = records(len(batch))
                 for i, (idx, _, cache) in enumerate(batch):
-                    joined.append(_Active(idx, cache, toks[i:i + 1].clone()))
+                    joined.append(_Active(idx, cache, toks[i:i + 1].clone(), rec=recs[i]))
             if active:
                 seat([a.request for a in active])
                 nxt, logprobs, _ = self.model.step_batch(torch.cat([a.token for a in active]), [a.cache for a in active])
                 self.steps += 1
                 if self.sampler is not None:
                     nxt = self.sampler(logprobs).reshape(-1).to(torch.int32)
+                recs = records(len(active))
                 for i, a in enumerate(active):
-                    a.token = nxt[i:i + 1]
+                    a.token, a.rec = nxt[i:i + 1], recs[i]
             active += joined
         if root is not None:
             root[0].page_manager.release()

@@ -154,7 +154,8 @@ class InferenceEngine:
 
     # ------------------------------------------------------------------ the hot loop
     def generate_step(self, prompt_ids, pixel_values=None, mask=None, kv_bits: int | None = None, kv_group_size: int = 64,
-                      quantized_kv_start: int = 0, max_kv_size: int | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
+                      quantized_kv_start: int = 0, max_kv_size: int | None = None,
+                      top_logprobs: int | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
         """Yields (next_token_id[1] int32, logprobs[V] fp32) per step, forever (inference_engine.py:228-297).
         Prefill of the non-cached prompt suffix, then one forward per token; all device work is queued
         asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202).
@@ -163,7 +164,14 @@ class InferenceEngine:
         cache/kv_cache/__init__.py:240-266).
         max_kv_size (mlx_lm's name): the prompt cache becomes RotatingKVCache(max_kv_size, keep=4) per layer -- memory and step cost
         bounded by the window; kv_bits then has no effect (a rotating cache stays 16-bit, as in the reference).  A prompt cache of
-        another kind or size is replaced by fresh rings (and back to the model's own caches when max_kv_size is None)."""
+        another kind or size is replaced by fresh rings (and back to the model's own caches when max_kv_size is None).
+        top_logprobs (None: off, else 0..20): every step also leaves `self.top_record` = (ids int32 [n + 1], vals fp32 [n + 1]) on the
+        device -- hip_ops.top_logprobs of the yielded logprobs with the yielded token in slot 0, valid until the next step:
+        written inside the replayed step where the request takes the fused plan, by the op on the host-orchestrated branches."""
+        if top_logprobs is not None and not 0 <= int(top_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"top_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
+        self.top_record = None
+        host_top: list = []   # [(ids, vals), workspace] of the host-orchestrated branches' top-n record
         if kv_bits is not None:
             check_kv_format(kv_group_size, kv_bits)
         if max_kv_size is not None:
@@ -181,6 +189,20 @@ class InferenceEngine:
         dev = self.model.device
 
         def _inference(ids: torch.Tensor, fed_back: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+            """_forward, then the top-n record of a host-orchestrated branch (the fused plan's is written inside the step)."""
+            self.top_record = None
+            tok, logprobs = _forward(ids, fed_back)
+            if top_logprobs is not None and self.top_record is None:
+                n = max(int(top_logprobs), 1)
+                if not host_top:  # this generation's own record and workspace, made once: the branch allocates nothing per token
+                    host_top.append((torch.full((1, n + 1), -1, dtype=torch.int32, device=logprobs.device),
+                                     torch.full((1, n + 1), float("-inf"), dtype=torch.float32, device=logprobs.device)))
+                    host_top.append(hip_ops.top_logprobs_workspace(logprobs.device, 1, logprobs.numel(), n))
+                rec_ids, rec_vals = hip_ops.top_logprobs(logprobs.reshape(1, -1), n, tokens=tok.reshape(1).to(torch.int32), workspace=host_top[1], out=host_top[0])
+                self.top_record = (rec_ids[0, :int(top_logprobs) + 1], rec_vals[0, :int(top_logprobs) + 1])
+            return tok, logprobs
+
+        def _forward(ids: torch.Tensor, fed_back: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
             """One forward + tail.  fed_back: `ids` is the token the previous call returned (still in the decoder's
             device-side state), so nothing has to be copied or read back."""
             state = "root"
@@ -215,7 +237,8 @@ class InferenceEngine:
                     recorded = True
                     words = packed_token_mask(mask.mask_fn(self.prompt_cache.computed_ids), vocab)
                 set_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
-                         token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values))
+                         token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values),
+                         **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}))
                 if pixel_values is not None and not fed_back:
                     embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
                     tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)
@@ -223,6 +246,8 @@ class InferenceEngine:
                     tok, logprobs, _ = self.model.step(None if fed_back else ids, self.prompt_cache.cache)
                 if not recorded:
                     self.prompt_cache.update(ids)                              # :255 (device ids resolve lazily)
+                if top_logprobs is not None:
+                    self.top_record = self.model.step_top_logprobs
                 return tok, logprobs
             if set_tail is not None:
                 set_tail()  # the host-orchestrated branches below run on Model.step's documented greedy tail
@@ -298,22 +323,27 @@ class InferenceEngine:
         the generator's return value is the stop reason ("stop" | "length" | "tool_calls")."""
         max_completion_tokens = inference_kwargs.get("max_completion_tokens", -1)
         collect_logprobs = inference_kwargs.get("logprobs", False)
-        top_logprobs: int = inference_kwargs.get("top_logprobs", 0)
+        top_logprobs: int = int(inference_kwargs.get("top_logprobs", 0) or 0)
+        if collect_logprobs and not 0 <= top_logprobs <= hip_ops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"top_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")   # the reference request model's bound
         logprobs_map: dict[int, float] = {}
         stop_reason = "stop"
         token_count = 0
         kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start", "max_kv_size") if inference_kwargs.get(k) is not None}
+        if collect_logprobs:
+            kv["top_logprobs"] = top_logprobs
         for new_tokens, new_logprobs in self.generate_step(prompt_ids, **kv):
             token_count += new_tokens.numel()
             if collect_logprobs:
-                logprobs_map = get_top_logprobs(new_logprobs, top_logprobs)
+                # one read per token: the (n + 1)-pair record, whose slot 0 is the token itself
+                token_ids, logprobs_map = record_to_map(*self.top_record, top_logprobs)
+            else:
+                token_ids = new_tokens.tolist()
             stopped = False
-            for token_id in new_tokens.tolist():
+            for token_id in token_ids:
                 if token_id in self.stop_tokens:
                     stopped = True
                     break
-                if collect_logprobs and token_id not in logprobs_map:
-                    logprobs_map[token_id] = float(new_logprobs[token_id].item())
                 yield token_id, logprobs_map
             if stopped:
                 # the reference `break`s only the inner loop and keeps generating (inference_engine.py:204-206);
@@ -326,6 +356,24 @@ class InferenceEngine:
                 stop_reason = "length"
                 break
         return stop_reason
+
+
+def record_to_map(ids: torch.Tensor, vals: torch.Tensor, top_k: int) -> tuple[list[int], dict[int, float]]:
+    """One top-n record (hip_ops.top_logprobs; device or host) -> ([token], {id: logprob}): the best top_k pairs by decreasing
+    log-probability (ties: lowest id first), then the chosen token of slot 0 when absent.  One read-back of 2 (n + 1) words."""
+    import numpy as np
+    words = torch.cat([ids.reshape(-1), vals.reshape(-1).view(torch.int32)]).cpu().numpy()
+    m = ids.numel()
+    return host_record_to_map(words[:m], words[m:].view(np.float32), top_k)
+
+
+def host_record_to_map(ids, vals, top_k: int) -> tuple[list[int], dict[int, float]]:
+    """record_to_map for a record already on the host (numpy int32 [n + 1], float32 [n + 1])."""
+    out = {int(i): float(v) for i, v in zip(ids[1:1 + top_k], vals[1:1 + top_k]) if i >= 0}
+    token = int(ids[0])
+    if token not in out:
+        out[token] = float(vals[0])
+    return [token], out
 
 
 def get_top_logprobs(logprobs: torch.Tensor, top_k: int) -> dict[int, float]:

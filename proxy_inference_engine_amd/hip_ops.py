@@ -864,6 +864,50 @@ def logits_penalty_rows(logits: torch.Tensor, table: torch.Tensor, recent_ids: t
     return logits
 
 
+# ---------------------------------------------------------------- top-n log-probabilities (csrc/top_logprobs.hip)
+TOP_LOGPROBS_MAX = _ffi.PIE_TOP_LOGPROBS_MAX
+
+
+def top_logprobs_workspace(device, rows: int, V: int, n: int) -> torch.Tensor:
+    """pie_top_logprobs' workspace for a [rows, V] block and `n` pairs on `device`: uninitialised, nothing is carried from call to call."""
+    nbytes = int(_ffi.load().pie_top_logprobs_workspace_bytes(int(rows), int(V), int(n)))
+    if nbytes == 0:
+        raise ValueError(f"top_logprobs: rows >= 1, 1 <= V <= 524288 and 1 <= n <= {TOP_LOGPROBS_MAX}, got rows = {rows}, V = {V}, n = {n}")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def top_logprobs(logprobs: torch.Tensor, n: int, tokens: torch.Tensor | None = None, count: torch.Tensor | None = None,
+                 workspace: torch.Tensor | None = None, out: tuple | None = None):
+    """get_top_logprobs (engine/utils.py:4-48) on the device (pie_top_logprobs): logprobs fp32 [rows, V] or [V] -> (ids int32 [rows, n + 1],
+    vals fp32 [rows, n + 1]), no sort and no host sync.  Slot 0 is (tokens[r], its log-probability), or (-1, -inf) without tokens or for an
+    id outside [0, V); slots 1.. are the best min(c, V) ids by (value descending, id ascending) -- ties to the lowest id -- with bit copies
+    of their values, then (-1, -inf); c = count[r] where count (device int32 [rows]) is given, else n: c > n acts as n, c == 0 leaves slot 0
+    only, c < 0 leaves the row's record as it is -- out = (ids, vals) to write into, else fresh tensors of (-1, -inf).  n 1..20."""
+    x = logprobs
+    _dev(x)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("top_logprobs: contiguous fp32 [rows, V] log-probabilities")
+    rows, V = x.shape
+    for t, name in ((tokens, "tokens"), (count, "count")):
+        if t is not None:
+            _dev(t)
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows:
+                raise ValueError(f"top_logprobs: {name} is a contiguous int32 [rows] device tensor")
+    ws = top_logprobs_workspace(x.device, rows, V, n) if workspace is None else workspace
+    if out is None:
+        out = (torch.full((rows, int(n) + 1), -1, dtype=torch.int32, device=x.device),
+               torch.full((rows, int(n) + 1), float("-inf"), dtype=torch.float32, device=x.device))
+    ids, vals = out
+    for t, dt in ((ids, torch.int32), (vals, torch.float32)):
+        _dev(t)
+        if t.dtype != dt or tuple(t.shape) != (rows, int(n) + 1):
+            raise ValueError("top_logprobs: out is (int32 [rows, n + 1], fp32 [rows, n + 1])")
+    _ffi.check(_ffi.load().pie_top_logprobs(_ffi.p(x), rows, V, int(n), _ffi.p(tokens), _ffi.p(count), _ffi.p(ids), _ffi.p(vals), _ffi.p(ws), _ffi.stream()))
+    return ids, vals
+
+
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)
 def kv_ring_order(keys: torch.Tensor, values: torch.Tensor, keep: int, n: int, shift: int, n_dst: int) -> None:
     """In place on RotatingKVCache buffers [1, H, cap, D]: rows keep + j <- rows keep + (j + shift) % n for j < n_dst."""

@@ -113,8 +113,13 @@ class Model:
         return self.language_model.step_embeds(inputs_embeds, cache, ids)
 
     # the step's configurable tail is the text tower's (llama/language.py: set_step_tail)
-    def set_step_tail(self, sampler=None, repetition_penalty: float = 1.0, context_size: int = 60, token_mask=None, logit_bias=None) -> None:
-        self.language_model.set_step_tail(sampler, repetition_penalty, context_size, token_mask, logit_bias)
+    def set_step_tail(self, sampler=None, repetition_penalty: float = 1.0, context_size: int = 60, token_mask=None, logit_bias=None,
+                      top_logprobs: int | None = None) -> None:
+        self.language_model.set_step_tail(sampler, repetition_penalty, context_size, token_mask, logit_bias, top_logprobs)
+
+    @property
+    def step_top_logprobs(self):
+        return self.language_model.step_top_logprobs
 
     @property
     def step_tail(self):

@@ -303,6 +303,8 @@ class Model:
         self._batch_bufs: dict = {}
         self._batch_tails: dict = {}   # rows_cap -> the batch tail's device buffers (set_batch_tail)
         self._batch_tail = None
+        self._top_n, self._top_rec = None, None   # the step's top-n log-probability record (set_step_tail(top_logprobs=))
+        self._batch_tops: dict = {}    # rows_cap -> the passes' top-n records (set_batch_top_logprobs)
         torch.cuda.synchronize(device)
 
     def __del__(self):
@@ -362,7 +364,7 @@ class Model:
 
     # ------------------------------------------------------------------ the step's tail
     def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
-                      token_mask=None, logit_bias=None) -> None:
+                      token_mask=None, logit_bias=None, top_logprobs: int | None = None) -> None:
         """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
         DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
@@ -373,9 +375,13 @@ class Model:
         and one bias table at stable addresses and copies the contents in, in stream order: new words every token are a copy and a
         replay, not a re-capture (a new number of bias entries is one).  A mask tensor, or a pair of bias sequences, already uploaded is not copied
         again: pass new objects for new contents.
+        top_logprobs: None (off) or 0..20 -- the step also leaves the (n + 1)-pair record of hip_ops.top_logprobs over the returned
+        logprobs, slot 0 being the returned token, in `step_top_logprobs`; 0 means slot 0 only.  The model owns the record
+        and the workspace at stable addresses.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
         self._set_tail_edits(token_mask, logit_bias)
+        self._set_tail_top_logprobs(top_logprobs)
         pen = (float(repetition_penalty), int(context_size)) if repetition_penalty != 1.0 and context_size != 0 else None
         seed = counter = None
         if sampler is not None:
@@ -396,6 +402,34 @@ class Model:
             _ffi.check(lib.pie_decoder_set_sampler(self._dec, hip_ops.SAMPLE_MODES[sampler[0]], sampler[1], sampler[2], sampler[3], seed, _ffi.p(counter),
                                                    _ffi.p(ws), ws.numel() * 8))
         self._tail = tail
+
+    def _set_tail_top_logprobs(self, n: int | None) -> None:
+        """The step's top-n record: asked of the library only when n changes.  n == 0 runs the op with one candidate and reports slot 0."""
+        if n is not None and not 0 <= int(n) <= hip_ops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"set_step_tail: top_logprobs is None or 0..{hip_ops.TOP_LOGPROBS_MAX}")
+        n = None if n is None else int(n)
+        if n == self._top_n:
+            return
+        lib = _ffi.load()
+        if n is None:
+            _ffi.check(lib.pie_decoder_set_top_logprobs(self._dec, 0, None, None, None, 0))
+        else:
+            if self._top_rec is None:  # sized for the largest n once: the addresses never change
+                m = hip_ops.TOP_LOGPROBS_MAX
+                self._top_rec = (torch.full((m + 1,), -1, dtype=torch.int32, device=self.device),
+                                 torch.full((m + 1,), float("-inf"), dtype=torch.float32, device=self.device),
+                                 hip_ops.top_logprobs_workspace(self.device, 1, self.logprobs.numel(), m))
+            ids, vals, ws = self._top_rec
+            _ffi.check(lib.pie_decoder_set_top_logprobs(self._dec, max(n, 1), _ffi.p(ids), _ffi.p(vals), _ffi.p(ws), ws.numel() * 8))
+        self._top_n = n
+
+    @property
+    def step_top_logprobs(self):
+        """(ids int32 [n + 1], vals fp32 [n + 1]) of the last step under set_step_tail(top_logprobs=n): slot 0 the returned token and its
+        log-probability, then the n best by (value descending, id ascending).  Device views, valid until the next call."""
+        if self._top_n is None:
+            raise RuntimeError("step_top_logprobs: set_step_tail(top_logprobs=n) first")
+        return self._top_rec[0][:self._top_n + 1], self._top_rec[1][:self._top_n + 1]
 
     def _set_tail_edits(self, token_mask, logit_bias) -> None:
         """The mask words and the bias table into the model's own buffers; the library is asked only when an edit is switched on or
@@ -556,7 +590,7 @@ class Model:
         else:
             ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0):  # (the several-prompts pass ends in the greedy tail only)
+            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None:  # (the several-prompts pass ends in the greedy tail only)
                 # A fresh prompt on int8 pages: the single-sequence prompt pass reads T pages (it would run the prompt as L decode steps,
                 # ~1.2 ms per token), the several-prompts pass quantises into int8 pages -- one prompt is a batch of one.
                 nxt, logprobs, logits = self.prefill_batch([ids.cpu().numpy()], [cache])  # (a prompt arrives once: the host copy is the pass's own row bookkeeping)
@@ -681,6 +715,36 @@ class Model:
         """Back to the greedy tail of the multi-sequence passes; the buffers stay cached for the next set_batch_tail."""
         _ffi.check(_ffi.load().pie_decoder_set_batch_tail(self._dec, None, 0, None, None))
         self._batch_tail = None
+
+    # ------------------------------------------------------------------ the multi-sequence passes' top-n log-probabilities (DESIGN.md 13)
+    def set_batch_top_logprobs(self, rows_cap: int, n: int) -> dict:
+        """From now on step_batch / prefill_batch / step_mixed also leave every output row's record of hip_ops.top_logprobs over its returned
+        logprobs and token (pie_decoder_set_batch_top_logprobs), with or without a batch tail: {"ids": int32 [rows_cap, n + 1], "vals": fp32
+        [rows_cap, n + 1], "count": int32 [rows_cap]}, returned, owned by the model and kept per rows_cap (the 4 most recent, like
+        set_batch_tail's buffers: one allocation sized for n = 20, of which "ids" / "vals" are the [rows_cap, n + 1] views).  Row s reports
+        count[s] pairs (more than n acts as n, 0: slot 0 only, negative: the row's record is left alone); a new count is all -1.  The
+        caller writes count in stream order; a captured step keeps replaying."""
+        rows_cap, n = int(rows_cap), int(n)
+        if rows_cap < 1 or not 1 <= n <= hip_ops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"set_batch_top_logprobs: rows_cap >= 1 and 1 <= n <= {hip_ops.TOP_LOGPROBS_MAX}")
+        own = self._batch_tops.pop(rows_cap, None)
+        if own is None:
+            while len(self._batch_tops) >= 4:
+                self._batch_tops.pop(next(iter(self._batch_tops)))
+            m = hip_ops.TOP_LOGPROBS_MAX
+            own = {"ids": torch.full((rows_cap * (m + 1),), -1, dtype=torch.int32, device=self.device),
+                   "vals": torch.full((rows_cap * (m + 1),), float("-inf"), dtype=torch.float32, device=self.device),
+                   "count": torch.full((rows_cap,), -1, dtype=torch.int32, device=self.device),
+                   "ws": hip_ops.top_logprobs_workspace(self.device, rows_cap, self.args.vocab_size, m)}
+        self._batch_tops[rows_cap] = own  # most recently used last
+        bt = {"ids": own["ids"][:rows_cap * (n + 1)].view(rows_cap, n + 1), "vals": own["vals"][:rows_cap * (n + 1)].view(rows_cap, n + 1),
+              "count": own["count"], "ws": own["ws"]}
+        _ffi.check(_ffi.load().pie_decoder_set_batch_top_logprobs(self._dec, n, rows_cap, _ffi.p(bt["ids"]), _ffi.p(bt["vals"]), _ffi.p(bt["count"]), _ffi.p(bt["ws"])))
+        return bt
+
+    def clear_batch_top_logprobs(self) -> None:
+        """The multi-sequence passes launch what they launched before set_batch_top_logprobs; the buffers stay cached."""
+        _ffi.check(_ffi.load().pie_decoder_set_batch_top_logprobs(self._dec, 0, 0, None, None, None, None))
 
     def batch_graph_launches(self) -> int:
         """Kernel nodes of the step_batch graph captured last (-1 before the first capture)."""
