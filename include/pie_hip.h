@@ -284,6 +284,23 @@ int pie_sample_rows(const float *logprobs, int rows, int V, pie_row_tail *table,
 int pie_logits_penalty_rows(void *logits, int rows, int V, int dtype, const pie_row_tail *table, int32_t *recent_ids, const int32_t *ids,
                             const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream);
 
+/* Per-row forms of the token mask and of logit_bias: what the multi-sequence passes run with pie_decoder_set_batch_logits_edits.
+ * pie_logprobs_argmax_rows_masked: logits [rows, V] T, masks DEVICE uint32 [rows, mask_words >= ceil(V / 32)] in pie_logprobs_argmax_masked's
+ *   bit layout, mask_on DEVICE int32 [rows], read on the device: nonzero = row r is masked in place with its own words and logprobs [rows, V],
+ *   tokens [rows] are written -- bit for bit what pie_logprobs_argmax_masked(logits + r * V, ..., masks + r * mask_words, ...) gives that row
+ *   alone; zero = the row's words are not read, every logit keeps its bits and the row is pie_logprobs_argmax's.  Two launches over a
+ *   (256, rows) and a (64, rows) grid; the partials live in stream-ordered scratch.  An all-zero mask on an armed row is the caller's error.
+ *   rows < 1, a null pointer: PIE_E_ARG; rows > 65535, V < 1, mask_words < ceil(V / 32): PIE_E_SHAPE; masks or mask_on not 4-byte aligned:
+ *   PIE_E_ALIGN -- each before any launch.
+ * pie_logits_bias_rows: logits [rows, V] T in place; ids DEVICE int32 [rows, cap], bias DEVICE float [rows, cap], n DEVICE int32 [rows], cap
+ *   1..1024.  Row r takes its first min(max(n[r], 0), cap) entries under pie_logits_bias's rule (id in [0, V), the first of duplicate ids
+ *   owns the id, one fp32 addition, one rounding to T): bit for bit pie_logits_bias of that row with that table; n[r] == 0 keeps every bit.
+ *   One launch, one workgroup per row.  rows < 1, cap outside 1..1024: PIE_E_ARG; V < 1: PIE_E_SHAPE; ids, bias or n not 4-byte aligned:
+ *   PIE_E_ALIGN -- each before any launch. */
+int pie_logprobs_argmax_rows_masked(void *logits, int rows, int V, int dtype, const uint32_t *masks, int mask_words, const int32_t *mask_on,
+                                    float *logprobs, int32_t *tokens, void *stream);
+int pie_logits_bias_rows(void *logits, int rows, int V, int dtype, const int32_t *ids, const float *bias, const int32_t *n, int cap, void *stream);
+
 /* ---------------------------------------------------------------- top-n log-probabilities
  * get_top_logprobs (engine/utils.py:4-48) on the device, sort-free: for every row of fp32 log-probabilities [rows, V] the n best
  * (id, value) pairs and the chosen token's own, n 1..PIE_TOP_LOGPROBS_MAX.  tokens (nullable) DEVICE int32 [rows]; count (nullable)
@@ -490,7 +507,8 @@ int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int
  *   edit launch runs with its penalty phase off and records nothing in ids_by_pos.
  * Both keep caller-owned device memory that stays alive while set; its CONTENTS may change between steps (the host writes in stream
  * order and a captured graph keeps replaying).  Switching either on or off, a new address or a new n drops the captured graphs.
- * Tensor-parallel decoders refuse (PIE_E_STATE).  pie_decoder_step_batch / _prefill_batch / _step_mixed ignore both. */
+ * Tensor-parallel decoders refuse (PIE_E_STATE).  pie_decoder_step_batch / _prefill_batch / _step_mixed ignore both: they take per-row
+ * masks and biases of their own (pie_decoder_set_batch_logits_edits). */
 int pie_decoder_set_logits_mask(pie_decoder *d, const uint32_t *mask, int mask_words);
 int pie_decoder_set_logit_bias(pie_decoder *d, const int32_t *ids, const float *bias, int n);
 /* The multi-sequence passes' tail: per-row penalties and samplers inside pie_decoder_step_batch (eager or PIE_STEP_GRAPH),
@@ -526,6 +544,29 @@ int pie_decoder_batch_graph_launches(const pie_decoder *d);
  * Both: the op's argument rules; tensor-parallel decoders refuse (PIE_E_STATE). */
 int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float *out_vals, void *workspace, size_t workspace_bytes);
 int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int32_t *out_ids, float *out_vals, const int32_t *count, void *workspace);
+/* Per-row token masks and logit biases inside the multi-sequence passes: pie_decoder_step_batch (eager or PIE_STEP_GRAPH),
+ * pie_decoder_prefill_batch and pie_decoder_step_mixed, output row s in pie_decoder_set_batch_tail's row order.  The processed logits of a row
+ * are the single-sequence tail's (above) with the row's own parameters: (1) mask, (2) the row's repetition penalty from its pie_row_tail
+ * record when a batch tail is set, (3) bias; then the unchanged log-softmax + argmax, pie_sample_rows and the top-n records.  A masked id is
+ * -inf in the processed logits whatever else is configured (the mask is applied physically last, inside the partials pass).  logits then hold
+ * the processed logits and logprobs their log-softmax, each row bit-identical with pie_logits_penalty over the ring's window +
+ * pie_logits_bias + pie_logprobs_argmax_masked + a one-row pie_sample of that row alone.
+ *   masks / mask_on    DEVICE uint32 [rows_cap, mask_words >= ceil(vocab / 32)] and int32 [rows_cap] as pie_logprobs_argmax_rows_masked takes
+ *                      them: mask_on[s] == 0 leaves row s unmasked, bit for bit.  masks == NULL (then mask_on == NULL too): no mask part
+ *   bias_ids / _vals / _n  DEVICE int32 / float [rows_cap, bias_cap] and int32 [rows_cap] as pie_logits_bias_rows takes them, bias_cap 1..1024;
+ *                      bias_n[s] is clamped to [0, bias_cap] on the device, 0: none.  bias_cap == 0: no bias part
+ * All five arrays are caller-owned and alive while set; their CONTENTS may change between calls in stream order while a captured step keeps
+ * replaying; the addresses, rows_cap, mask_words and bias_cap are part of the captured graph's key, so switching a part on or off or changing
+ * any of them leaves the captured batch graph behind.  rows_cap == 0 switches the edits off: the passes then launch exactly what they launch
+ * without.  Independent of pie_decoder_set_batch_tail and of pie_decoder_set_batch_top_logprobs.  Launches: lm_head | pie_logits_penalty_rows,
+ * or k_logits_edit_rows (penalty phase + bias phase in one launch) when a bias part is set | the partials, masked per row when a mask part
+ * is set | finish | [pie_sample_rows] | [top-n]: per pass +0 for masks and +1 for a bias without a batch tail, +0 with one; the fused
+ * few-sequence step, whose lm_head epilogue partials are stale after an edit, +1 / +2 without a batch tail and +0 with one.
+ * rows_cap < 0, bias_cap outside 0..1024, neither part, a part with a NULL array: PIE_E_ARG; mask_words < ceil(vocab / 32): PIE_E_SHAPE; an
+ * array not 4-byte aligned: PIE_E_ALIGN; a pass with more output rows than rows_cap: PIE_E_SHAPE before any launch; tensor-parallel
+ * decoders refuse the setter (PIE_E_STATE). */
+int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint32_t *masks, int mask_words, const int32_t *mask_on,
+                                       const int32_t *bias_ids, const float *bias_vals, const int32_t *bias_n, int bias_cap);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -49,6 +49,7 @@ EXPORTS = [
     "pie_logprobs_argmax_masked", "pie_logits_bias", "pie_decoder_set_logits_mask", "pie_decoder_set_logit_bias",
     "pie_row_tail_bytes", "pie_row_tail_pack", "pie_sample_rows", "pie_logits_penalty_rows", "pie_decoder_set_batch_tail", "pie_decoder_batch_graph_replays", "pie_decoder_batch_graph_launches",
     "pie_top_logprobs_workspace_bytes", "pie_top_logprobs", "pie_decoder_set_top_logprobs", "pie_decoder_set_batch_top_logprobs",
+    "pie_logprobs_argmax_rows_masked", "pie_logits_bias_rows", "pie_decoder_set_batch_logits_edits",
 ]
 
 
@@ -152,6 +153,9 @@ def load() -> C.CDLL:
     lib.pie_top_logprobs.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 6
     lib.pie_decoder_set_top_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.pie_decoder_set_batch_top_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    lib.pie_logprobs_argmax_rows_masked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    lib.pie_logits_bias_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.pie_decoder_set_batch_logits_edits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

@@ -898,6 +898,37 @@ int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap
     return PIE_OK;
 }
 
+int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint32_t *masks, int mask_words, const int32_t *mask_on,
+                                       const int32_t *bias_ids, const float *bias_vals, const int32_t *bias_n, int bias_cap) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_logits_edits: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (rows_cap == 0) {
+        d->be_rows_cap = 0, d->be_masks = nullptr, d->be_mask_words = 0, d->be_mask_on = nullptr;
+        d->be_bias_ids = nullptr, d->be_bias_vals = nullptr, d->be_bias_n = nullptr, d->be_bias_cap = 0;
+        return PIE_OK;
+    }
+    PIE_REQUIRE(rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: rows_cap >= 1 (0: off)");
+    PIE_REQUIRE(bias_cap >= 0 && bias_cap <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: bias_cap must be 1..1024 (0: no bias part)");
+    PIE_REQUIRE(masks || bias_cap, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: neither a mask part nor a bias part");
+    PIE_REQUIRE((masks != nullptr) == (mask_on != nullptr), PIE_E_ARG, "pie_decoder_set_batch_logits_edits: masks and mask_on come together");
+    if (masks) {
+        PIE_REQUIRE(mask_words >= (d->cfg.vocab + 31) / 32, PIE_E_SHAPE, "pie_decoder_set_batch_logits_edits: every row's mask needs ceil(vocab / 32) words");
+        PIE_REQUIRE(pie_aligned(masks, 4) && pie_aligned(mask_on, 4), PIE_E_ALIGN, "pie_decoder_set_batch_logits_edits: masks and mask_on need 4-byte alignment");
+    } else {
+        mask_words = 0;
+    }
+    if (bias_cap) {
+        PIE_REQUIRE(bias_ids && bias_vals && bias_n, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: null pointer");
+        PIE_REQUIRE(pie_aligned(bias_ids, 4) && pie_aligned(bias_vals, 4) && pie_aligned(bias_n, 4), PIE_E_ALIGN,
+                    "pie_decoder_set_batch_logits_edits: bias_ids, bias_vals and bias_n need 4-byte alignment");
+    } else {
+        bias_ids = nullptr, bias_vals = nullptr, bias_n = nullptr;
+    }
+    d->be_rows_cap = rows_cap, d->be_masks = masks, d->be_mask_words = mask_words, d->be_mask_on = mask_on;
+    d->be_bias_ids = bias_ids, d->be_bias_vals = bias_vals, d->be_bias_n = bias_n, d->be_bias_cap = bias_cap;  // (the batch graph's key holds them: no graph to drop)
+    return PIE_OK;
+}
+
 unsigned long long pie_decoder_batch_graph_replays(const pie_decoder *d) { return d ? d->batch_replays : 0; }
 int pie_decoder_batch_graph_launches(const pie_decoder *d) { return d ? d->batch_graph_kernels : -1; }
 

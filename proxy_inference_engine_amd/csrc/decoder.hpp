@@ -109,6 +109,16 @@ struct pie_decoder {
     float *btl_vals = nullptr;
     const int *btl_count = nullptr;
     void *btl_ws = nullptr;
+    // The multi-sequence passes' per-row token masks and logit biases (pie_decoder_set_batch_logits_edits): caller-owned device
+    // memory whose CONTENTS may change between calls; the addresses and the three sizes are in the captured batch graph's key.
+    int be_rows_cap = 0;  // 0: off
+    const unsigned *be_masks = nullptr;  // [rows_cap, be_mask_words], nullptr: no mask part
+    int be_mask_words = 0;
+    const int *be_mask_on = nullptr;
+    const int *be_bias_ids = nullptr;  // [rows_cap, be_bias_cap]
+    const float *be_bias_vals = nullptr;
+    const int *be_bias_n = nullptr;
+    int be_bias_cap = 0;  // 0: no bias part
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
     bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n; }

@@ -387,4 +387,32 @@ int pie_logits_penalty_rows(void *logits, int rows, int V, int dtype, const pie_
     return logits_penalty_rows_launch(dtype, a, rows, (hipStream_t)stream);
 }
 
+int pie_logprobs_argmax_rows_masked(void *logits, int rows, int V, int dtype, const uint32_t *masks, int mask_words, const int32_t *mask_on,
+                                    float *logprobs, int32_t *tokens, void *stream) {
+    PIE_REQUIRE(logits && masks && mask_on && logprobs && tokens, PIE_E_ARG, "pie_logprobs_argmax_rows_masked: null pointer");
+    PIE_REQUIRE(rows >= 1, PIE_E_ARG, "pie_logprobs_argmax_rows_masked: rows >= 1");
+    PIE_REQUIRE(rows <= 65535 && V > 0, PIE_E_SHAPE, "pie_logprobs_argmax_rows_masked: rows <= 65535 and a non-empty vocabulary");
+    PIE_REQUIRE(mask_words >= (V + 31) / 32, PIE_E_SHAPE, "pie_logprobs_argmax_rows_masked: every row's mask needs ceil(V / 32) words");
+    PIE_REQUIRE(pie_aligned(masks, 4) && pie_aligned(mask_on, 4), PIE_E_ALIGN, "pie_logprobs_argmax_rows_masked: masks and mask_on need 4-byte alignment");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_logprobs_argmax_rows_masked: dtype must be PIE_BF16 or PIE_F16");
+    hipStream_t st = (hipStream_t)stream;
+    LogitStat *stats = nullptr;  // stream-ordered scratch, like pie_logprobs_argmax's
+    if (hipMallocAsync((void **)&stats, sizeof(LogitStat) * TAIL_STAT_TILES * (size_t)rows, st) != hipSuccess)
+        return pie::fail(PIE_E_HIP, "pie_logprobs_argmax_rows_masked: hipMallocAsync failed");
+    const int rc = logits_tail_rows_masked_launch(dtype, (u16 *)logits, V, rows, stats, masks, mask_words, mask_on, logprobs, tokens, st);
+    (void)hipFreeAsync(stats, st);
+    return rc;
+}
+
+int pie_logits_bias_rows(void *logits, int rows, int V, int dtype, const int32_t *ids, const float *bias, const int32_t *n, int cap, void *stream) {
+    PIE_REQUIRE(logits && ids && bias && n, PIE_E_ARG, "pie_logits_bias_rows: null pointer");
+    PIE_REQUIRE(rows >= 1 && cap >= 1 && cap <= PEN_MAX_IDS, PIE_E_ARG, "pie_logits_bias_rows: rows >= 1 and 1 <= cap <= 1024 entries per row");
+    PIE_REQUIRE(V >= 1, PIE_E_SHAPE, "pie_logits_bias_rows: empty vocabulary");
+    PIE_REQUIRE(pie_aligned(ids, 4) && pie_aligned(bias, 4) && pie_aligned(n, 4), PIE_E_ALIGN, "pie_logits_bias_rows: ids, bias and n need 4-byte alignment");
+    PenRowsArgs a = {};
+    a.logits = (u16 *)logits, a.V = V;  // no ctx: every row is live, and the penalty phase is off
+    const BiasRowsArgs b = {ids, bias, n, cap, 0};
+    return logits_edit_rows_launch(dtype, a, b, rows, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -836,6 +836,8 @@ static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
 // What follows the lm_head of `rows` output rows.  No table set: the greedy tail, as ever.  A table (pie_decoder_set_batch_tail):
 // every row's own penalty over its own window first (ids / ctx / out_rows: the pass's input ids, context lengths and, where output row s
 // is not source row s, its source rows), then the same log-softmax + argmax, then every row's own sampler over the fp32 log-probabilities.
+// Per-row edits (pie_decoder_set_batch_logits_edits), with or without a table: every row's own bias behind its penalty, in the
+// penalty's launch, and every row's own token mask inside the partials pass of the log-softmax.
 // The rows' top-n log-probability records (pie_decoder_set_batch_top_logprobs), once next_tokens are final.  Off: nothing is launched.
 static int batch_top_logprobs_launch(pie_decoder *d, int rows, const float *logprobs, const int32_t *next_tokens, hipStream_t st) {
     if (!d->btl_n) return PIE_OK;
@@ -847,15 +849,26 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     const pie_decoder_config &c = d->cfg;
     PrefillScratch *s = d->prefill;
     int rc;
-    if (!d->bt_table) {
+    if (!d->bt_table && !d->be_rows_cap) {
         if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
         return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
     }
+    // per-row edits (pie_decoder_set_batch_logits_edits): the rows' biases ride the penalty's launch (k_logits_edit_rows: phase 1
+    // off without a table), the rows' masks the partials pass -- physically last, so a masked id is -inf whatever else is configured
     PenRowsArgs p = {};
     p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = d->bt_table, p.recent = d->bt_recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
-    if ((rc = logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
-    if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
-    if ((rc = sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st))) return rc;
+    if (d->be_bias_cap) {
+        const BiasRowsArgs b = {d->be_bias_ids, d->be_bias_vals, d->be_bias_n, d->be_bias_cap, d->bt_table ? 1 : 0};
+        if ((rc = logits_edit_rows_launch(c.dtype, p, b, rows, st))) return rc;
+    } else if (d->bt_table) {
+        if ((rc = logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
+    }
+    if (d->be_masks)
+        rc = logits_tail_rows_masked_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, d->be_masks, d->be_mask_words, d->be_mask_on, logprobs, next_tokens, st);
+    else
+        rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st);
+    if (rc) return rc;
+    if (d->bt_table && (rc = sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st))) return rc;
     return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
 }
 
@@ -915,7 +928,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         g.w = (const char *)d->glob.lm_head, g.K = H, g.N = c.vocab, g.M = B, g.x = s->x, g.norm_w = (const u16 *)d->glob.final_norm, g.eps = c.rms_eps;
         g.y = logits, g.stats = s->tail_stats;
         if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_RMSNORM, EPI_LOGITS, g, st))) return rc;
-        if (d->bt_table) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty)
+        if (d->bt_table || d->be_rows_cap) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty or an edit)
         const dim3 fg(TAIL_FINISH_BLOCKS, B);
         if (c.dtype == PIE_BF16)
             hipLaunchKernelGGL(k_logits_finish<BF16>, fg, dim3(256), 0, st, logits, c.vocab, s->tail_stats, lm_waves, logprobs, next_tokens, (DecState *)nullptr, (int *)nullptr, 0, (const unsigned *)nullptr);
@@ -1052,6 +1065,7 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     PIE_REQUIRE(d->glob_set, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: set_globals must be called first");
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: a layer has no weights (pie_decoder_set_layer)");
     PIE_REQUIRE(!d->bt_table || S <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch tail's rows_cap");
+    PIE_REQUIRE(!d->be_rows_cap || S <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch logits edits' rows_cap");
     PIE_REQUIRE(!d->btl_n || S <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the top log-probabilities' rows_cap");
     PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
     PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
@@ -1107,6 +1121,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_step_batch: a layer has no weights (pie_decoder_set_layer)");
     PIE_REQUIRE(B >= 1 && B <= 4096 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_step_batch: bad batch shape");
     PIE_REQUIRE(!d->bt_table || B <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch tail's rows_cap");
+    PIE_REQUIRE(!d->be_rows_cap || B <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch logits edits' rows_cap");
     PIE_REQUIRE(!d->btl_n || B <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the top log-probabilities' rows_cap");
     PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_step_batch: logprobs need 4-byte alignment");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
@@ -1125,6 +1140,9 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     for (uintptr_t v : {(uintptr_t)d->bt_table, (uintptr_t)d->bt_recent, (uintptr_t)d->bt_ws, (uintptr_t)d->bt_rows_cap}) key.push_back(v);  // the tail's launches bake them in
     for (uintptr_t v : {(uintptr_t)d->btl_n, (uintptr_t)d->btl_rows_cap, (uintptr_t)d->btl_ids, (uintptr_t)d->btl_vals, (uintptr_t)d->btl_count, (uintptr_t)d->btl_ws})
         key.push_back(v);  // and so do the top log-probabilities'
+    for (uintptr_t v : {(uintptr_t)d->be_rows_cap, (uintptr_t)d->be_masks, (uintptr_t)d->be_mask_words, (uintptr_t)d->be_mask_on, (uintptr_t)d->be_bias_ids,
+                        (uintptr_t)d->be_bias_vals, (uintptr_t)d->be_bias_n, (uintptr_t)d->be_bias_cap})
+        key.push_back(v);  // and the per-row masks' and biases'
     if (!d->prefill) d->prefill = new PrefillScratch();
     PrefillScratch *s = d->prefill;
     if (s->batch_graph && s->batch_key == key && s->batch_gen == s->alloc_gen) {

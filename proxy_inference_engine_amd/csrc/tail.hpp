@@ -67,6 +67,20 @@ __global__ void __launch_bounds__(256) k_logits_stats_masked(u16 *logits, int V,
     logits_stats_tile<T, true>(logits, V, stats, mask);
 }
 
+// The masked partials of a batch of rows, each under its own mask (pie_logprobs_argmax_rows_masked): row blockIdx.y reads the
+// words masks + blockIdx.y * mask_words when mask_on[blockIdx.y] != 0 and runs k_logits_stats' unmasked body otherwise (every logit keeps its
+// bits, whatever the row's words hold).  mask_on is device memory the host rewrites between launches: one thread reads it and the workgroup
+// takes the decision from LDS, so the branch around the tile bodies' barriers is block-uniform by construction.
+template <class T>
+__global__ void __launch_bounds__(256) k_logits_stats_rows_masked(u16 *logits, int V, LogitStat *stats, const unsigned *masks, int mask_words,
+                                                                  const int *mask_on) {
+    __shared__ int s_on;
+    if (threadIdx.x == 0) s_on = mask_on[blockIdx.y];
+    __syncthreads();
+    if (s_on != 0) logits_stats_tile<T, true>(logits, V, stats, masks + (size_t)blockIdx.y * mask_words);
+    else logits_stats_tile<T, false>(logits, V, stats, nullptr);
+}
+
 constexpr int TAIL_MAX_STATS = 4096;  // 256 threads x 16 register-resident partials
 
 template <class T>
@@ -144,6 +158,23 @@ static inline int logits_tail_rows_launch(int dtype, const u16 *logits, int V, i
         hipLaunchKernelGGL(k_logits_finish<BF16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
     } else {
         hipLaunchKernelGGL(k_logits_stats<F16>, g1, dim3(256), 0, st, logits, V, stats_buf);
+        hipLaunchKernelGGL(k_logits_finish<F16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
+    }
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// The same two launches with every row's own token mask riding the partials pass (k_logits_stats_rows_masked): masks [rows, mask_words],
+// mask_words >= ceil(V / 32) (checked by every caller), mask_on [rows].
+static inline int logits_tail_rows_masked_launch(int dtype, u16 *logits, int V, int rows, LogitStat *stats_buf, const unsigned *masks, int mask_words,
+                                                 const int *mask_on, float *logprobs, int *tokens, hipStream_t st) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits tail: dtype must be PIE_BF16 or PIE_F16");
+    const dim3 g1(TAIL_STAT_TILES, rows), g2(TAIL_FINISH_BLOCKS, rows);
+    if (dtype == PIE_BF16) {
+        hipLaunchKernelGGL(k_logits_stats_rows_masked<BF16>, g1, dim3(256), 0, st, logits, V, stats_buf, masks, mask_words, mask_on);
+        hipLaunchKernelGGL(k_logits_finish<BF16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
+    } else {
+        hipLaunchKernelGGL(k_logits_stats_rows_masked<F16>, g1, dim3(256), 0, st, logits, V, stats_buf, masks, mask_words, mask_on);
         hipLaunchKernelGGL(k_logits_finish<F16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
     }
     PIE_LAUNCH_CHECK();
@@ -322,6 +353,77 @@ static inline int logits_penalty_rows_launch(int dtype, const PenRowsArgs &a, in
     if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits penalty: dtype must be PIE_BF16 or PIE_F16");
     if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_penalty_rows<BF16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a);
     else hipLaunchKernelGGL(k_logits_penalty_rows<F16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// The rows' penalties and the rows' logit biases in one launch (pie_logits_bias_rows, and the multi-sequence passes' tail when a bias is
+// configured): one workgroup per output row s.  Phase 1 is k_logits_penalty_rows' body on that row (b.penalise == 0, no batch
+// tail: off, and nothing is recorded in the ring), phase 2 k_logits_edit's bias phase on the row's logits with the row's own table: entries
+// t < n[s] (device memory, untrusted: clamped to [0, cap]) of ids / bias [rows, cap], ownership among duplicate ids through the same LDS array.
+// k_logits_penalty_rows leaves before its barrier for an idle slot, a source row out of range and a penalty of exactly 1.0; a row of the
+// last kind may still carry a bias, so here only the first two leave (such a row gets neither phase) and everything else that skips phase 1
+// is a block-uniform decision (a kernel argument, or a value every thread reads from one address that no thread writes), after which
+// every thread reaches phase 2's barriers.  The ring is written where k_logits_penalty_rows writes it.  a.ctx == nullptr (the op): every row
+// is live.  Phase 2 reads what phase 1 stored to the same id from another wave: the workgroup-scope argument above k_logits_edit.
+struct BiasRowsArgs {
+    const int *ids;     // [rows, cap]
+    const float *bias;  // [rows, cap]
+    const int *n;       // [rows]
+    int cap;            // 1..PEN_MAX_IDS
+    int penalise;       // run phase 1 (the caller's own decision: a batch tail is set)
+};
+
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_edit_rows(const PenRowsArgs a, const BiasRowsArgs b) {
+    __shared__ int s_ids[PEN_MAX_IDS];
+    const int t = threadIdx.x, s = blockIdx.x;
+    int i = s, pos = 0;
+    if (a.ctx) {
+        i = a.out_rows ? a.out_rows[s] : s;
+        if (i < 0 || i >= a.n_src) return;  // block-uniform, and before every barrier
+        pos = a.ctx[i] - 1;
+        if (pos < 0) return;  // likewise
+    }
+    u16 *logits = a.logits + (size_t)s * a.V;
+    const float penalty = b.penalise ? a.table[s].penalty : 1.0f;
+    if (b.penalise && penalty == 1.0f && t == 0) a.recent[(size_t)s * PEN_MAX_IDS + (pos & (PEN_MAX_IDS - 1))] = a.ids[i];
+    if (penalty != 1.0f) {  // block-uniform: phase 1, k_logits_penalty_rows from its window on
+        int *ring = a.recent + (size_t)s * PEN_MAX_IDS;
+        int context = a.table[s].context_size;
+        context = context < 1 ? 1 : (context > PEN_MAX_IDS ? PEN_MAX_IDS : context);
+        const int lo = pos + 1 - context > 0 ? pos + 1 - context : 0, n = pos + 1 - lo;  // 1 <= n <= context
+        int id = -1;
+        if (t < n) {
+            const int p = lo + t;
+            if (p == pos) id = a.ids[i], ring[p & (PEN_MAX_IDS - 1)] = id;
+            else id = ring[p & (PEN_MAX_IDS - 1)];
+        }
+        s_ids[t] = id;
+        __syncthreads();
+        bool own = t < n && id >= 0 && id < a.V;
+        for (int j = 0; own && j < t; ++j) own = s_ids[j] != id;  // an earlier entry owns this id
+        if (own) {
+            const float x = T::to_f32(logits[id]);
+            logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, penalty) : __fdiv_rn(x, penalty));  // k_logits_penalty's arithmetic
+        }
+    }
+    __syncthreads();  // phase 1's stores are visible, and its readers of s_ids are done
+    int bn = b.n[s];
+    bn = bn < 0 ? 0 : (bn > b.cap ? b.cap : bn);
+    const int id = t < bn ? b.ids[(size_t)s * b.cap + t] : -1;
+    s_ids[t] = id;
+    __syncthreads();
+    if (id < 0 || id >= a.V) return;
+    for (int j = 0; j < t; ++j)
+        if (s_ids[j] == id) return;  // an earlier entry owns this id
+    logits[id] = T::from_f32(__fadd_rn(T::to_f32(logits[id]), b.bias[(size_t)s * b.cap + t]));
+}
+
+static inline int logits_edit_rows_launch(int dtype, const PenRowsArgs &a, const BiasRowsArgs &b, int rows, hipStream_t st) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits bias: dtype must be PIE_BF16 or PIE_F16");
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_edit_rows<BF16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a, b);
+    else hipLaunchKernelGGL(k_logits_edit_rows<F16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a, b);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }

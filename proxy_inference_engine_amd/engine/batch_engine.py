@@ -7,7 +7,8 @@ wait in a queue, join the batch when a slot and enough pages are free -- their p
 in flight (`Model.step_mixed`: both kinds of sequence in one pass over the weights, as BatchDetails holds both), or run as a
 prompt pass of their own when nothing is decoding -- every step decodes all active sequences with one pass over the weights
 (`Model.step_batch`), finished sequences leave and return their pages.  Greedy by default; `generate(sampling=...)` gives every request
-its own `SamplingParams`, run per row inside the passes (DESIGN.md 11); `sampler` maps a [B, V] log-probability block to B token ids;
+its own `SamplingParams`, run per row inside the passes (DESIGN.md 11) -- its token mask and logit_bias included (DESIGN.md 14);
+`sampler` maps a [B, V] log-probability block to B token ids;
 `generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes."""
 from __future__ import annotations
 
@@ -27,7 +28,11 @@ class SamplingParams:
     """One request's sampler and repetition penalty: the reference's per-Sequence SamplingParams (temperature, top_p, top_k, min_p, rng_seed;
     include/sequence/sampling_params.hpp) and LogitsParams (repetition_penalty, repetition_context_size; logits_params.hpp).  The branch
     is make_sampler's: temp == 0 greedy, else top_p inside (0, 1), else min_p != 0, else top_k > 0, else plain categorical.
-    seed None: a fresh random seed per request."""
+    seed None: a fresh random seed per request.
+    token_mask: what make_token_mask takes -- packed int32 words, a bool [V] mask, or a callable that receives every id the request has
+    been fed so far (the prompt, then the prompt plus every generated token) and returns packed words, a bool mask or the allowed ids: the
+    hook a grammar engine binds to.  logit_bias: {id: bias} under make_logit_bias's rules (1..1024 entries, finite values).  Both run per
+    row inside the passes, in the single-sequence tail's order: mask, repetition penalty, bias."""
     temp: float = 0.0
     top_p: float = 1.0
     top_k: int = -1
@@ -36,6 +41,8 @@ class SamplingParams:
     seed: int | None = None
     repetition_penalty: float = 1.0
     repetition_context_size: int = 60
+    token_mask: object = None
+    logit_bias: dict | None = None
 
     def hip_spec(self) -> tuple | None:
         """None (greedy) or (mode, temp, p, k) as hip_ops.sample / row_tail_pack take them."""
@@ -50,9 +57,30 @@ class SamplingParams:
         return ("categorical", float(self.temp), 0.0, 0)
 
     @property
-    def plain(self) -> bool:
-        """Greedy without a penalty: today's tail."""
+    def tailless(self) -> bool:
+        """Greedy without a penalty: the request needs no record in the batch tail."""
         return self.temp == 0 and self.repetition_penalty == 1.0
+
+    @property
+    def plain(self) -> bool:
+        """Greedy without a penalty, a mask or a bias: today's tail."""
+        return self.tailless and self.token_mask is None and self.logit_bias is None
+
+    def edits(self, vocab_size: int) -> tuple:
+        """(the token mask's processor or None, (ids, values) of the bias table or None), checked as make_token_mask / make_logit_bias
+        check them and against the vocabulary: ValueError for a bool mask of another length, too few packed words, a mask that allows
+        nothing, a bad bias table."""
+        from ..logits_processors import check_vocab, make_logit_bias, make_token_mask, packed_token_mask
+        proc = bias = None
+        if self.token_mask is not None:
+            proc = make_token_mask(self.token_mask)
+            check_vocab(proc, vocab_size)
+            if proc.mask is not None:
+                packed_token_mask(proc.mask, vocab_size)
+        if self.logit_bias is not None:
+            b = make_logit_bias(self.logit_bias)
+            bias = (b.ids, b.values)
+        return proc, bias
 
     def record(self, calls: int = 0, seed: int | None = None):
         """The request's device record (hip_ops.row_tail_pack) after `calls` drawn tokens; ValueError for arguments the samplers refuse."""
@@ -105,12 +133,14 @@ class BatchedEngine:
         """Token ids generated for every prompt (in order), at most max_new_tokens each, ending early at a stop token.
         sampling: None (greedy, or the constructor's `sampler`), one SamplingParams for every request, or one per prompt: each request's
         own sampler, seed and repetition penalty, applied to its row inside every pass (Model.set_batch_tail) -- a request's tokens depend
-        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters.
+        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters.  A request's token_mask and
+        logit_bias ride the same passes (Model.set_batch_edits); a callable mask is evaluated on the host after the per-pass read-back of
+        the tokens and only the rows whose words changed are uploaded.  With logprobs=True the maps report the processed log-probabilities.
         logprobs=True: returns (outputs, maps) -- maps[i][j] is the {token id: log-probability} dict of outputs[i][j], as
         InferenceEngine.generate yields it: the best top_logprobs pairs by decreasing log-probability (ties: lowest id first), then the
         token itself when absent.  top_logprobs: one int for every request or one per prompt, each 0..20; ignored with logprobs=False.  The
         records are selected per row inside the passes (Model.set_batch_top_logprobs) and fetched in the per-pass read-back of the tokens."""
-        tops = None
+        tops = edits = None
         if logprobs:
             if self.sampler is not None:
                 raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
@@ -129,30 +159,40 @@ class BatchedEngine:
             seeds = [int.from_bytes(os.urandom(8), "little") if sp.seed is None else int(sp.seed) for sp in params]
             for sp, sd in zip(params, seeds):
                 sp.record(0, sd)              # every request's arguments are checked before anything runs
-            if all(sp.plain for sp in params):
-                sampling = None               # nothing to configure: today's passes
+            if any(sp.token_mask is not None or sp.logit_bias is not None for sp in params):
+                edits = [sp.edits(self.model.args.vocab_size) for sp in params]
+            if all(sp.tailless for sp in params):
+                sampling = None               # no record to configure: a request with only a mask or a bias arms no batch tail
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        if sampling is None and tops is None:
+        if sampling is None and tops is None and edits is None:
             return self._generate(prompts, max_new_tokens, None)
         try:
             if sampling is not None:
                 self.model.set_batch_tail(self.max_batch)
                 self.model.write_batch_tail(list(range(self.max_batch)), [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
+            if edits is not None:
+                any_mask, cap = any(m is not None for m, _ in edits), max(len(b[0]) if b else 0 for _, b in edits)
+                self.model.set_batch_edits(self.max_batch, masks=any_mask, bias_cap=cap)
+                self.model.write_batch_edits(list(range(self.max_batch)), [None] * self.max_batch if any_mask else None,
+                                             [None] * self.max_batch if cap else None)   # (cached buffers may hold an earlier call's rows)
+            tails = None if sampling is None else (params, seeds)
             if tops is None:
-                return self._generate(prompts, max_new_tokens, (params, seeds))
+                return self._generate(prompts, max_new_tokens, tails, edits=edits)
             bufs = self.model.set_batch_top_logprobs(self.max_batch, max(max(tops, default=1), 1))
             bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
             maps: list = [[] for _ in prompts]
-            out = self._generate(prompts, max_new_tokens, None if sampling is None else (params, seeds), (tops, bufs, maps))
+            out = self._generate(prompts, max_new_tokens, tails, (tops, bufs, maps), edits=edits)
             return out, maps
         finally:
             if sampling is not None:
                 self.model.clear_batch_tail()
+            if edits is not None:
+                self.model.clear_batch_edits()
             if tops is not None:
                 self.model.clear_batch_top_logprobs()
 
-    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None) -> list[list[int]]:
+    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None, edits=None) -> list[list[int]]:
         for p in prompts:
             if self._pages_for(len(p) + max_new_tokens) > self.pool.size():
                 raise ValueError("a prompt does not fit the page pool")
@@ -187,6 +227,8 @@ class BatchedEngine:
         filling: list = []            # chunked prefill: [request, prompt, cache, rows done] of admitted prompts not yet fully in their pages
         slots: list = []              # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
         counts: list = []             # top-n records: the count the device holds for row s (-1: the row reports nothing)
+        seats: list = []              # per-request edits: the request whose mask and bias table row s holds, None = unarmed
+        words: list = []              # ... and the mask words row s holds when that request's mask is a callable
 
         def seat(rows: list) -> None:
             """The coming pass's output rows, in order: a request index (its own record; its ring rows from the ids it has been fed) or
@@ -203,6 +245,36 @@ class BatchedEngine:
                                                  torch.tensor([want_c[s_] for s_ in changed], dtype=torch.int32, device=dev))
                     for s_ in changed:
                         counts[s_] = want_c[s_]
+            if edits is not None:
+                # a row's mask and bias table are rewritten where its record is: when its occupant changes.  A callable mask is evaluated for
+                # every live row, every pass, on what the request has been fed -- the read-back above already brought the tokens -- and the
+                # rows whose words changed go up in one copy.
+                from ..logits_processors import packed_token_mask
+                V = self.model.args.vocab_size
+                fed_by = {a.request: a.generated for a in active}
+                want_e = [r if r is not None and edits[r] != (None, None) else None for r in rows]
+                seats.extend([None] * (len(want_e) - len(seats)))
+                words.extend([None] * (len(want_e) - len(words)))
+                m_rows, m_new, b_rows, b_new = [], [], [], []
+                for s_, r in enumerate(want_e):
+                    proc, bias = edits[r] if r is not None else (None, None)
+                    moved = seats[s_] != r
+                    if moved:
+                        if any(b is not None for _, b in edits):
+                            b_rows.append(s_), b_new.append(bias)
+                        words[s_] = None
+                    if proc is not None and proc.mask_fn is not None:
+                        w = packed_token_mask(proc.mask_fn(list(prompts[r]) + list(fed_by.get(r, []))), V)
+                        if words[s_] is None or not torch.equal(words[s_], w):
+                            m_rows.append(s_), m_new.append(w)
+                            words[s_] = w
+                    elif moved and any(m is not None for m, _ in edits):
+                        m_rows.append(s_), m_new.append(None if proc is None else proc.mask)
+                    seats[s_] = r
+                if m_rows:
+                    self.model.write_batch_edits(m_rows, masks=m_new)
+                if b_rows:
+                    self.model.write_batch_edits(b_rows, biases=b_new)
             if tails is None:
                 return
             params, seeds = tails
@@ -229,9 +301,9 @@ class BatchedEngine:
             self.model.write_batch_tail(idx, recs, fed)
 
         def lone_step(idx) -> bool:
-            """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record of its own, or wants
-            log-probabilities: then it is a batch of one."""
-            return tops is None and (tails is None or tails[0][idx].plain)
+            """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
+            own, or wants log-probabilities: then it is a batch of one."""
+            return tops is None and (tails is None or tails[0][idx].tailless) and (edits is None or edits[idx] == (None, None))
 
         def records(n_rows: int):
             """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'

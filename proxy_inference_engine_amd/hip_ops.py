@@ -864,6 +864,41 @@ def logits_penalty_rows(logits: torch.Tensor, table: torch.Tensor, recent_ids: t
     return logits
 
 
+# ---------------------------------------------------------------- per-row token masks and logit biases
+def logprobs_argmax_rows_masked(logits: torch.Tensor, masks: torch.Tensor, mask_on: torch.Tensor):
+    """pie_logprobs_argmax_rows_masked: row r of 16-bit logits [rows, V] is masked IN PLACE with masks[r] (pack_token_mask's layout, device
+    int32 [rows, >= ceil(V / 32)]) when mask_on[r] (device int32 [rows]) is nonzero and left bit for bit otherwise; returns (tokens int32
+    [rows], logprobs fp32 [rows, V]) -- every row what logprobs_argmax_masked (armed) or logprobs_argmax (off) gives that row alone."""
+    _dev(logits), _dev(masks), _dev(mask_on)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logprobs_argmax_rows_masked: contiguous [rows, V] logits")
+    rows, V = logits.shape
+    if masks.dtype != torch.int32 or masks.dim() != 2 or not masks.is_contiguous() or masks.shape[0] < rows or \
+            mask_on.dtype != torch.int32 or not mask_on.is_contiguous() or mask_on.numel() < rows:
+        raise ValueError("logprobs_argmax_rows_masked: contiguous int32 masks [>= rows, words] and mask_on [>= rows]")
+    lp = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
+    tok = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    _ffi.check(_ffi.load().pie_logprobs_argmax_rows_masked(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(masks), masks.shape[1],
+                                                           _ffi.p(mask_on), _ffi.p(lp), _ffi.p(tok), _ffi.stream()))
+    return tok, lp
+
+
+def logits_bias_rows(logits: torch.Tensor, ids: torch.Tensor, bias: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
+    """pie_logits_bias_rows on 16-bit logits [rows, V], IN PLACE: row r takes the first n[r] entries (clamped to [0, cap]) of ids[r] / bias[r]
+    (device int32 / float32 [rows, cap], cap 1..1024) under logits_bias's rule; n device int32 [rows], 0: the row keeps every bit.
+    Returns logits."""
+    _dev(logits), _dev(ids), _dev(bias), _dev(n)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logits_bias_rows: contiguous [rows, V] logits")
+    rows, V = logits.shape
+    if ids.dtype != torch.int32 or bias.dtype != torch.float32 or n.dtype != torch.int32 or ids.dim() != 2 or ids.shape != bias.shape or \
+            not (ids.is_contiguous() and bias.is_contiguous() and n.is_contiguous()) or ids.shape[0] < rows or n.numel() < rows:
+        raise ValueError("logits_bias_rows: contiguous int32 ids and float32 bias [>= rows, cap], int32 n [>= rows]")
+    _ffi.check(_ffi.load().pie_logits_bias_rows(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(ids), _ffi.p(bias), _ffi.p(n),
+                                                ids.shape[1], _ffi.stream()))
+    return logits
+
+
 # ---------------------------------------------------------------- top-n log-probabilities (csrc/top_logprobs.hip; DESIGN.md 13)
 TOP_LOGPROBS_MAX = _ffi.PIE_TOP_LOGPROBS_MAX
 

@@ -305,6 +305,8 @@ class Model:
         self._batch_tail = None
         self._top_n, self._top_rec = None, None   # the step's top-n log-probability record (set_step_tail(top_logprobs=))
         self._batch_tops: dict = {}    # rows_cap -> the passes' top-n records (set_batch_top_logprobs)
+        self._batch_edit_bufs: dict = {}   # rows_cap -> the passes' per-row masks and bias tables (set_batch_edits)
+        self._batch_edits = None
         torch.cuda.synchronize(device)
 
     def __del__(self):
@@ -745,6 +747,90 @@ class Model:
     def clear_batch_top_logprobs(self) -> None:
         """The multi-sequence passes launch what they launched before set_batch_top_logprobs; the buffers stay cached."""
         _ffi.check(_ffi.load().pie_decoder_set_batch_top_logprobs(self._dec, 0, 0, None, None, None, None))
+
+    # ------------------------------------------------------------------ the multi-sequence passes' per-row masks and biases (DESIGN.md 14)
+    def set_batch_edits(self, rows_cap: int, masks: bool = True, bias_cap: int = 0) -> dict:
+        """From now on step_batch / prefill_batch / step_mixed apply every output row's own token mask and logit bias
+        (pie_decoder_set_batch_logits_edits), with or without a batch tail: {"masks": int32 [rows_cap, ceil(V / 32)] packed words
+        (hip_ops.pack_token_mask's layout), "mask_on": int32 [rows_cap], "bias_ids": int32 [rows_cap, bias_cap], "bias_vals": fp32 [rows_cap,
+        bias_cap], "bias_n": int32 [rows_cap]}, returned (a part that is not asked for is None), owned by the model and kept per rows_cap
+        at stable addresses (the 4 most recent, like set_batch_tail's buffers; the bias tables are views of one allocation sized for 1024
+        entries).  Fresh buffers start with mask_on and bias_n all zero: the passes' results are the unedited ones until
+        write_batch_edits (or the caller, in stream order) arms a row."""
+        rows_cap, bias_cap = int(rows_cap), int(bias_cap)
+        if rows_cap < 1 or not 0 <= bias_cap <= 1024 or not (masks or bias_cap):
+            raise ValueError("set_batch_edits: rows_cap >= 1, 0 <= bias_cap <= 1024, and a mask part or a bias part")
+        own = self._batch_edit_bufs.pop(rows_cap, None)
+        if own is None:
+            while len(self._batch_edit_bufs) >= 4:
+                self._batch_edit_bufs.pop(next(iter(self._batch_edit_bufs)))
+            own = {}
+        if masks and "masks" not in own:
+            own["masks"] = torch.zeros((rows_cap, (self.args.vocab_size + 31) // 32), dtype=torch.int32, device=self.device)
+            own["mask_on"] = torch.zeros(rows_cap, dtype=torch.int32, device=self.device)
+        if bias_cap and "bias_ids" not in own:
+            own["bias_ids"] = torch.zeros(rows_cap * 1024, dtype=torch.int32, device=self.device)
+            own["bias_vals"] = torch.zeros(rows_cap * 1024, dtype=torch.float32, device=self.device)
+            own["bias_n"] = torch.zeros(rows_cap, dtype=torch.int32, device=self.device)
+        self._batch_edit_bufs[rows_cap] = own  # most recently used last
+        be = {k: None for k in ("masks", "mask_on", "bias_ids", "bias_vals", "bias_n")}
+        if masks:
+            be["masks"], be["mask_on"] = own["masks"], own["mask_on"]
+        if bias_cap:
+            be["bias_ids"] = own["bias_ids"][:rows_cap * bias_cap].view(rows_cap, bias_cap)
+            be["bias_vals"] = own["bias_vals"][:rows_cap * bias_cap].view(rows_cap, bias_cap)
+            be["bias_n"] = own["bias_n"]
+        _ffi.check(_ffi.load().pie_decoder_set_batch_logits_edits(self._dec, rows_cap, _ffi.p(be["masks"]), be["masks"].shape[1] if masks else 0,
+                                                                  _ffi.p(be["mask_on"]), _ffi.p(be["bias_ids"]), _ffi.p(be["bias_vals"]), _ffi.p(be["bias_n"]),
+                                                                  bias_cap))
+        self._batch_edits = be
+        return be
+
+    def write_batch_edits(self, rows: list[int], masks: list | None = None, biases: list | None = None) -> None:
+        """Rewrites the masks and / or the bias tables of `rows` of the armed buffers, in stream order, one copy per array for all of them.
+        masks[i]: the mask of rows[i] in any form packed_token_mask takes (packed int32 words, a bool [V] tensor, allowed ids), or None:
+        the row is unmasked; an all-zero mask is refused here (ValueError), not decoded.  biases[i]: (ids, values) of 1..bias_cap entries, or
+        None: no bias.  masks / biases None as a whole: that part of the rows is left as it is."""
+        import numpy as np
+        be = self._batch_edits
+        if be is None:
+            raise RuntimeError("write_batch_edits: no batch edits are set (set_batch_edits)")
+        if not rows:
+            return
+        if (masks is not None and len(masks) != len(rows)) or (biases is not None and len(biases) != len(rows)):
+            raise ValueError("write_batch_edits: one mask and one bias table per row")
+        idx = torch.tensor(rows, dtype=torch.long, device=self.device)
+        if masks is not None:
+            if be["masks"] is None:
+                raise RuntimeError("write_batch_edits: the batch edits were set without a mask part")
+            from ...logits_processors import packed_token_mask
+            V, W = self.args.vocab_size, be["masks"].shape[1]
+            words = [None if m is None else packed_token_mask(m, V)[:W] for m in masks]     # every mask is checked before any row is written
+            armed = [i for i, w in enumerate(words) if w is not None]
+            if armed:
+                be["masks"].index_copy_(0, idx[armed], torch.stack([words[i] for i in armed]).to(self.device))
+            be["mask_on"].index_copy_(0, idx, torch.tensor([int(w is not None) for w in words], dtype=torch.int32, device=self.device))
+        if biases is not None:
+            if be["bias_ids"] is None:
+                raise RuntimeError("write_batch_edits: the batch edits were set without a bias part")
+            cap = be["bias_ids"].shape[1]
+            ids, vals = np.zeros((len(rows), cap), np.int32), np.zeros((len(rows), cap), np.float32)
+            n = np.zeros(len(rows), np.int32)
+            for i, b in enumerate(biases):
+                if b is None:
+                    continue
+                if not 1 <= len(b[0]) <= cap or len(b[1]) != len(b[0]):
+                    raise ValueError(f"write_batch_edits: a bias table is (ids, values) with 1..{cap} entries each")
+                n[i] = len(b[0])
+                ids[i, :n[i]], vals[i, :n[i]] = np.asarray(b[0], dtype=np.int32), np.asarray(b[1], dtype=np.float32)
+            be["bias_ids"].index_copy_(0, idx, torch.from_numpy(ids).to(self.device))
+            be["bias_vals"].index_copy_(0, idx, torch.from_numpy(vals).to(self.device))
+            be["bias_n"].index_copy_(0, idx, torch.from_numpy(n).to(self.device))
+
+    def clear_batch_edits(self) -> None:
+        """The multi-sequence passes launch what they launched before set_batch_edits; the buffers stay cached."""
+        _ffi.check(_ffi.load().pie_decoder_set_batch_logits_edits(self._dec, 0, None, 0, None, None, None, None, 0))
+        self._batch_edits = None
 
     def batch_graph_launches(self) -> int:
         """Kernel nodes of the step_batch graph captured last (-1 before the first capture)."""
