@@ -301,6 +301,42 @@ int pie_logprobs_argmax_rows_masked(void *logits, int rows, int V, int dtype, co
                                     float *logprobs, int32_t *tokens, void *stream);
 int pie_logits_bias_rows(void *logits, int rows, int V, int dtype, const int32_t *ids, const float *bias, const int32_t *n, int cap, void *stream);
 
+/* ---------------------------------------------------------------- frequency and presence penalties
+ * The two OpenAI-style logits parameters, on counts of a request's GENERATED tokens: with c[v] = how often id v occurs among the tokens
+ * generated so far for the request (prompt tokens do not count, neither does the token about to be chosen),
+ *   c[v] == 0 :  x'[v] = x[v]                                             (the stored T value is not rewritten)
+ *   c[v] >  0 :  x'[v] = T( f32(x[v]) - ( f32(freq) * (float)c[v] + f32(pres) ) )
+ * with one fp32 multiplication, one fp32 addition and one fp32 subtraction in that association (no fma), and one round-to-nearest-even
+ * to T.  -inf stays -inf, +-inf and NaN follow IEEE, an f16 result beyond 65504 is inf.  freq and pres may be negative.
+ * ORDER inside a tail: (1) token mask (physically last: a masked id is -inf whatever else is configured), (2) repetition penalty,
+ * (3) logit_bias, (4) frequency / presence; then the unchanged log-softmax + argmax, the sampler and the top-n record.
+ * State per output row, caller-owned DEVICE memory: counts int32 [rows_cap, V] (exact beyond 65535) and one pie_count_penalty record:
+ *   freq, pres    the two parameters as fp32; both exactly 0: the row is left alone, bit for bit, and nothing is counted
+ *   start         the first position that holds a generated token (= the prompt's length): an input id at a position below it is a
+ *                 prompt token and is not counted
+ *   counted_pos   the last position whose input id has been counted (start - 1 when none has): a position is counted once, however
+ *                 often a pass over it is run
+ * pie_count_penalty_pack fills a record in HOST memory: freq and pres finite, start >= 0, counted_pos >= -1, PIE_E_ARG otherwise; nothing
+ * touches a device.  The kernel does not trust the bytes it reads: every index is checked, freq and pres only enter arithmetic.
+ * pie_logits_count_penalty_rows: logits [rows, V] T in place, one launch over a (ceil((ceil(V / 4) + 1) / 128), rows) grid of 128-thread
+ *   workgroups, four elements per thread (8-byte logits and 16-byte counts accesses where the row's base allows, scalar heads and tails
+ *   where it does not).  Row s reads source row i = out_rows ? out_rows[s] : s of ids / ctx [n_src] (pie_logits_penalty_rows' rule): its
+ *   input id ids[i] sits at position pos = ctx[i] - 1; pos < 0 (an idle slot) or i outside [0, n_src): the row is skipped.  COUNTING: when
+ *   pos >= start, pos > counted_pos and 0 <= ids[i] < V, the one thread that covers element ids[i] increments counts[s][ids[i]], stores
+ *   counted_pos = pos and uses the incremented count; no other thread reads or writes either, so there is no atomic and no ordering
+ *   between workgroups.  Then the formula over the row.  ctx == NULL (ids and out_rows are then ignored): every row is live and nothing
+ *   is counted -- the counts are used as they are.  rows < 1, a null pointer: PIE_E_ARG; rows > 65535, V < 1, n_src < 1, fewer source rows
+ *   than rows without out_rows: PIE_E_SHAPE; records or counts not 4-byte aligned, logits not 2-byte aligned: PIE_E_ALIGN -- each before
+ *   any launch. */
+typedef struct pie_count_penalty {
+    float freq, pres;
+    int32_t start, counted_pos;
+} pie_count_penalty;
+size_t pie_count_penalty_bytes(void); /* sizeof(pie_count_penalty) = 16, for bindings */
+int pie_count_penalty_pack(double freq, double pres, int start, int counted_pos, pie_count_penalty *out);
+int pie_logits_count_penalty_rows(void *logits, int rows, int V, int dtype, pie_count_penalty *records, int32_t *counts, const int32_t *ids,
+                                  const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream);
+
 /* ---------------------------------------------------------------- top-n log-probabilities
  * get_top_logprobs (engine/utils.py:4-48) on the device, sort-free: for every row of fp32 log-probabilities [rows, V] the n best
  * (id, value) pairs and the chosen token's own, n 1..PIE_TOP_LOGPROBS_MAX.  tokens (nullable) DEVICE int32 [rows]; count (nullable)
@@ -567,6 +603,27 @@ int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int3
  * decoders refuse the setter (PIE_E_STATE). */
 int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint32_t *masks, int mask_words, const int32_t *mask_on,
                                        const int32_t *bias_ids, const float *bias_vals, const int32_t *bias_n, int bias_cap);
+/* Frequency and presence penalties inside the passes: pie_logits_count_penalty_rows' kernel as step (4) of a tail -- after
+ * the mask's, the repetition penalty's and the bias' turn in the order above, before the log-softmax (whose partials are recomputed from the
+ * processed logits: k_logits_stats, as after a penalty or a bias; in the fused few-sequence step too).  One more launch per pass, plus
+ * the partials launch where nothing else had made them stale already.
+ * pie_decoder_set_count_penalty: the single-sequence tail, wherever the configured tail applies (pie_decoder_step with PIE_STEP_LOGITS, eager
+ *   or PIE_STEP_GRAPH; the last row of pie_decoder_prefill / _prefill_embeds with logits_all == NULL -- with logits_all != NULL the logits
+ *   stay raw), on every KV binding.  record: DEVICE pie_count_penalty, counts: DEVICE int32 [vocab], caller-owned and alive while set.  A step
+ *   takes its position and input id from the device-side state (the fed-back token, or the explicit one) and counts it under the rule
+ *   above; a prompt pass counts nothing (its rows are prompt tokens) and applies the penalty from the counts as they are.  The record's and
+ *   the counts' CONTENTS may change between steps in stream order while a captured graph keeps replaying; the two addresses are launch
+ *   arguments: setting, clearing or moving them drops the captured graphs.  record == NULL switches it off.  A null counts with a record:
+ *   PIE_E_ARG; misaligned (4 bytes): PIE_E_ALIGN.
+ * pie_decoder_set_batch_count_penalty: pie_decoder_step_batch (eager or PIE_STEP_GRAPH), _prefill_batch and _step_mixed; record s and counts
+ *   row s belong to output row s in pie_decoder_set_batch_tail's row order, with the pass's own ids / context lengths / output rows as the
+ *   op's ids / ctx / out_rows.  records DEVICE pie_count_penalty [rows_cap], counts DEVICE int32 [rows_cap, vocab].  Independent of the batch
+ *   tail, the batch edits and the batch top-n setters; the addresses and rows_cap are part of the captured batch graph's key.
+ *   records == NULL switches it off.  rows_cap < 1, a null counts: PIE_E_ARG; misaligned: PIE_E_ALIGN; a pass with more output rows than
+ *   rows_cap: PIE_E_SHAPE before any launch.
+ * With neither set every pass launches exactly what it launches without.  Tensor-parallel decoders refuse both (PIE_E_STATE). */
+int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int32_t *counts);
+int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *records, int32_t *counts, int rows_cap);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -50,6 +50,7 @@ EXPORTS = [
     "pie_row_tail_bytes", "pie_row_tail_pack", "pie_sample_rows", "pie_logits_penalty_rows", "pie_decoder_set_batch_tail", "pie_decoder_batch_graph_replays", "pie_decoder_batch_graph_launches",
     "pie_top_logprobs_workspace_bytes", "pie_top_logprobs", "pie_decoder_set_top_logprobs", "pie_decoder_set_batch_top_logprobs",
     "pie_logprobs_argmax_rows_masked", "pie_logits_bias_rows", "pie_decoder_set_batch_logits_edits",
+    "pie_count_penalty_bytes", "pie_count_penalty_pack", "pie_logits_count_penalty_rows", "pie_decoder_set_count_penalty", "pie_decoder_set_batch_count_penalty",
 ]
 
 
@@ -77,6 +78,11 @@ class pie_row_tail(C.Structure):
     """One output row's penalty and sampler in device memory (include/pie_hip.h)."""
     _fields_ = [("mode", C.c_int32), ("inv_temp", C.c_float), ("thr", C.c_float), ("k", C.c_int32), ("seed", C.c_uint64), ("calls", C.c_uint64),
                 ("penalty", C.c_float), ("context_size", C.c_int32)]
+
+
+class pie_count_penalty(C.Structure):
+    """One output row's frequency / presence penalties and counting state in device memory (include/pie_hip.h)."""
+    _fields_ = [("freq", C.c_float), ("pres", C.c_float), ("start", C.c_int32), ("counted_pos", C.c_int32)]
 
 
 def set_knob(name: str, value: int | None) -> None:
@@ -156,6 +162,12 @@ def load() -> C.CDLL:
     lib.pie_logprobs_argmax_rows_masked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
     lib.pie_logits_bias_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.pie_decoder_set_batch_logits_edits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+    lib.pie_count_penalty_bytes.restype = C.c_size_t
+    lib.pie_count_penalty_bytes.argtypes = []
+    lib.pie_count_penalty_pack.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(pie_count_penalty)]
+    lib.pie_logits_count_penalty_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    lib.pie_decoder_set_count_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pie_decoder_set_batch_count_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

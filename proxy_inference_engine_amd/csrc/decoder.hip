@@ -156,8 +156,8 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
     return a;
 }
 
-// The configured tail over the bound outputs (include/pie_hip.h): penalty and / or bias (one launch) + fresh partials, which apply the token
-// mask on their way | finish | the sampler's launches | the top-n log-probabilities' two.
+// The configured tail over the bound outputs (include/pie_hip.h): penalty and / or bias (one launch) | frequency / presence penalties (one
+// launch) + fresh partials, which apply the token mask on their way | finish | the sampler's launches | the top-n log-probabilities' two.
 // from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
 static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
@@ -170,7 +170,12 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
         const BiasArgs b = {d->bias_ids, d->bias_vals, d->bias_n, d->pen != 1.0};
         if ((rc = d->bias_n ? logits_edit_launch(c.dtype, a, b, st) : logits_penalty_launch(c.dtype, a, st))) return rc;
     }
-    if (d->pen != 1.0 || d->bias_n || d->tok_mask) {  // the lm_head epilogue's partials are stale
+    if (d->cp_record) {  // frequency / presence: behind the penalty and the bias; a prompt pass counts nothing
+        CountPenArgs k = {};
+        k.logits = d->logits, k.V = c.vocab, k.records = d->cp_record, k.counts = d->cp_counts, k.state = d->state, k.count = from_state;
+        if ((rc = logits_count_penalty_rows_launch(c.dtype, k, 1, st))) return rc;
+    }
+    if (d->pen != 1.0 || d->bias_n || d->tok_mask || d->cp_record) {  // the lm_head epilogue's partials are stale
         if ((rc = d->tok_mask ? logits_stats_masked_launch(c.dtype, d->logits, c.vocab, d->tok_mask, d->tail_stats, st)
                               : logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st)))
             return rc;
@@ -926,6 +931,33 @@ int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint3
     }
     d->be_rows_cap = rows_cap, d->be_masks = masks, d->be_mask_words = mask_words, d->be_mask_on = mask_on;
     d->be_bias_ids = bias_ids, d->be_bias_vals = bias_vals, d->be_bias_n = bias_n, d->be_bias_cap = bias_cap;  // (the batch graph's key holds them: no graph to drop)
+    return PIE_OK;
+}
+
+int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int32_t *counts) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_count_penalty: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_count_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (!record) counts = nullptr;
+    else {
+        PIE_REQUIRE(counts, PIE_E_ARG, "pie_decoder_set_count_penalty: a record needs its counts");
+        PIE_REQUIRE(pie_aligned(record, 4) && pie_aligned(counts, 4), PIE_E_ALIGN, "pie_decoder_set_count_penalty: the record and the counts need 4-byte alignment");
+        if (int rc = tail_stats_alloc(d)) return rc;
+    }
+    if (d->cp_record != record || d->cp_counts != counts) drop_graphs(d);  // both are launch arguments (what they point at is read by every launch)
+    d->cp_record = record, d->cp_counts = counts;
+    return PIE_OK;
+}
+
+int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *records, int32_t *counts, int rows_cap) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_count_penalty: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_count_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (!records) {
+        d->bc_records = nullptr, d->bc_counts = nullptr, d->bc_rows_cap = 0;
+        return PIE_OK;
+    }
+    PIE_REQUIRE(counts && rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_count_penalty: the records need their counts and rows_cap >= 1");
+    PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(counts, 4), PIE_E_ALIGN, "pie_decoder_set_batch_count_penalty: the records and the counts need 4-byte alignment");
+    d->bc_records = records, d->bc_counts = counts, d->bc_rows_cap = rows_cap;  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 

@@ -119,9 +119,16 @@ struct pie_decoder {
     const float *be_bias_vals = nullptr;
     const int *be_bias_n = nullptr;
     int be_bias_cap = 0;  // 0: no bias part
+    // Frequency / presence penalties (pie_decoder_set_count_penalty / _set_batch_count_penalty): caller-owned records and
+    // counts whose CONTENTS change between steps; cp_*: the step's tail (launch arguments), bc_*: the multi-sequence passes' (in the batch graph's key).
+    pie_count_penalty *cp_record = nullptr;  // nullptr: off
+    int *cp_counts = nullptr;                // [vocab]
+    pie_count_penalty *bc_records = nullptr;  // [bc_rows_cap], nullptr: off
+    int *bc_counts = nullptr;                 // [bc_rows_cap, vocab]
+    int bc_rows_cap = 0;
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
-    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n; }
+    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n || cp_record; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)

@@ -415,4 +415,34 @@ int pie_logits_bias_rows(void *logits, int rows, int V, int dtype, const int32_t
     return logits_edit_rows_launch(dtype, a, b, rows, (hipStream_t)stream);
 }
 
+size_t pie_count_penalty_bytes(void) { return sizeof(pie_count_penalty); }
+
+int pie_count_penalty_pack(double freq, double pres, int start, int counted_pos, pie_count_penalty *out) {
+    PIE_REQUIRE(out, PIE_E_ARG, "pie_count_penalty_pack: null pointer");
+    PIE_REQUIRE(std::isfinite(freq) && std::isfinite(pres) && std::isfinite((float)freq) && std::isfinite((float)pres), PIE_E_ARG,
+                "pie_count_penalty_pack: the frequency and presence penalties must be finite");
+    PIE_REQUIRE(start >= 0 && counted_pos >= -1, PIE_E_ARG, "pie_count_penalty_pack: start >= 0 and counted_pos >= -1");
+    pie_count_penalty r = {};
+    r.freq = (float)freq, r.pres = (float)pres, r.start = start, r.counted_pos = counted_pos;
+    *out = r;
+    return PIE_OK;
+}
+
+int pie_logits_count_penalty_rows(void *logits, int rows, int V, int dtype, pie_count_penalty *records, int32_t *counts, const int32_t *ids,
+                                  const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream) {
+    PIE_REQUIRE(logits && records && counts, PIE_E_ARG, "pie_logits_count_penalty_rows: null pointer");
+    PIE_REQUIRE(rows >= 1, PIE_E_ARG, "pie_logits_count_penalty_rows: rows >= 1");
+    PIE_REQUIRE(!ctx || ids, PIE_E_ARG, "pie_logits_count_penalty_rows: context lengths without input ids");
+    PIE_REQUIRE(rows <= 65535 && V >= 1, PIE_E_SHAPE, "pie_logits_count_penalty_rows: rows <= 65535 and a non-empty vocabulary");
+    PIE_REQUIRE(!ctx || (n_src >= 1 && (out_rows || n_src >= rows)), PIE_E_SHAPE,
+                "pie_logits_count_penalty_rows: n_src >= 1, and without out_rows every output row needs its source row");
+    PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(counts, 4) && pie_aligned(logits, 2), PIE_E_ALIGN,
+                "pie_logits_count_penalty_rows: records and counts need 4-byte alignment, logits 2-byte");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_logits_count_penalty_rows: dtype must be PIE_BF16 or PIE_F16");
+    CountPenArgs a = {};
+    a.logits = (u16 *)logits, a.V = V, a.n_src = n_src, a.records = records, a.counts = counts;
+    if (ctx) a.ids = ids, a.ctx = ctx, a.out_rows = out_rows;
+    return logits_count_penalty_rows_launch(dtype, a, rows, (hipStream_t)stream);
+}
+
 }  // extern "C"

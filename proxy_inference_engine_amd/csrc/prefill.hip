@@ -849,7 +849,7 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     const pie_decoder_config &c = d->cfg;
     PrefillScratch *s = d->prefill;
     int rc;
-    if (!d->bt_table && !d->be_rows_cap) {
+    if (!d->bt_table && !d->be_rows_cap && !d->bc_records) {
         if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
         return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
     }
@@ -862,6 +862,11 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
         if ((rc = logits_edit_rows_launch(c.dtype, p, b, rows, st))) return rc;
     } else if (d->bt_table) {
         if ((rc = logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
+    }
+    if (d->bc_records) {  // every row's frequency / presence penalties, behind its penalty and its bias
+        CountPenArgs k = {};
+        k.logits = logits, k.V = c.vocab, k.n_src = n_src, k.records = d->bc_records, k.counts = d->bc_counts, k.ids = ids, k.ctx = ctx, k.out_rows = out_rows;
+        if ((rc = logits_count_penalty_rows_launch(c.dtype, k, rows, st))) return rc;
     }
     if (d->be_masks)
         rc = logits_tail_rows_masked_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, d->be_masks, d->be_mask_words, d->be_mask_on, logprobs, next_tokens, st);
@@ -928,7 +933,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         g.w = (const char *)d->glob.lm_head, g.K = H, g.N = c.vocab, g.M = B, g.x = s->x, g.norm_w = (const u16 *)d->glob.final_norm, g.eps = c.rms_eps;
         g.y = logits, g.stats = s->tail_stats;
         if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_RMSNORM, EPI_LOGITS, g, st))) return rc;
-        if (d->bt_table || d->be_rows_cap) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty or an edit)
+        if (d->bt_table || d->be_rows_cap || d->bc_records) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty or an edit)
         const dim3 fg(TAIL_FINISH_BLOCKS, B);
         if (c.dtype == PIE_BF16)
             hipLaunchKernelGGL(k_logits_finish<BF16>, fg, dim3(256), 0, st, logits, c.vocab, s->tail_stats, lm_waves, logprobs, next_tokens, (DecState *)nullptr, (int *)nullptr, 0, (const unsigned *)nullptr);
@@ -1067,6 +1072,7 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     PIE_REQUIRE(!d->bt_table || S <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch tail's rows_cap");
     PIE_REQUIRE(!d->be_rows_cap || S <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch logits edits' rows_cap");
     PIE_REQUIRE(!d->btl_n || S <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the top log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->bc_records || S <= d->bc_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch count penalty's rows_cap");
     PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
     PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
@@ -1123,6 +1129,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     PIE_REQUIRE(!d->bt_table || B <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch tail's rows_cap");
     PIE_REQUIRE(!d->be_rows_cap || B <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch logits edits' rows_cap");
     PIE_REQUIRE(!d->btl_n || B <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the top log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->bc_records || B <= d->bc_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch count penalty's rows_cap");
     PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_step_batch: logprobs need 4-byte alignment");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_step_batch: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
@@ -1143,6 +1150,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     for (uintptr_t v : {(uintptr_t)d->be_rows_cap, (uintptr_t)d->be_masks, (uintptr_t)d->be_mask_words, (uintptr_t)d->be_mask_on, (uintptr_t)d->be_bias_ids,
                         (uintptr_t)d->be_bias_vals, (uintptr_t)d->be_bias_n, (uintptr_t)d->be_bias_cap})
         key.push_back(v);  // and the per-row masks' and biases'
+    for (uintptr_t v : {(uintptr_t)d->bc_records, (uintptr_t)d->bc_counts, (uintptr_t)d->bc_rows_cap}) key.push_back(v);  // and the frequency / presence penalties'
     if (!d->prefill) d->prefill = new PrefillScratch();
     PrefillScratch *s = d->prefill;
     if (s->batch_graph && s->batch_key == key && s->batch_gen == s->alloc_gen) {

@@ -7,6 +7,7 @@
 #pragma once
 #include "common.hpp"
 #include "w4_gemv.hpp"  // LogitStat, DecState
+#include "count_penalty.hpp"  // frequency / presence penalties: step (4) of a tail
 
 constexpr int TAIL_STAT_TILES = 256;
 constexpr int TAIL_FINISH_BLOCKS = 64;

@@ -7,7 +7,8 @@ wait in a queue, join the batch when a slot and enough pages are free -- their p
 in flight (`Model.step_mixed`: both kinds of sequence in one pass over the weights, as BatchDetails holds both), or run as a
 prompt pass of their own when nothing is decoding -- every step decodes all active sequences with one pass over the weights
 (`Model.step_batch`), finished sequences leave and return their pages.  Greedy by default; `generate(sampling=...)` gives every request
-its own `SamplingParams`, run per row inside the passes (DESIGN.md 11) -- its token mask and logit_bias included (DESIGN.md 14);
+its own `SamplingParams`, run per row inside the passes -- its token mask and logit_bias included, and its
+frequency and presence penalties over the counts of what it has generated (DESIGN.md 15);
 `sampler` maps a [B, V] log-probability block to B token ids;
 `generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes."""
 from __future__ import annotations
@@ -32,7 +33,10 @@ class SamplingParams:
     token_mask: what make_token_mask takes -- packed int32 words, a bool [V] mask, or a callable that receives every id the request has
     been fed so far (the prompt, then the prompt plus every generated token) and returns packed words, a bool mask or the allowed ids: the
     hook a grammar engine binds to.  logit_bias: {id: bias} under make_logit_bias's rules (1..1024 entries, finite values).  Both run per
-    row inside the passes, in the single-sequence tail's order: mask, repetition penalty, bias."""
+    row inside the passes, in the single-sequence tail's order: mask, repetition penalty, bias.
+    frequency_penalty / presence_penalty (each -2.0 .. 2.0; the two remaining fields of LogitsParams): logits[v] -= frequency_penalty *
+    c[v] + presence_penalty wherever c[v] > 0, c = how often the request has GENERATED id v so far (its prompt does not count), per row
+    inside the passes, after the bias: mask, repetition penalty, bias, frequency / presence."""
     temp: float = 0.0
     top_p: float = 1.0
     top_k: int = -1
@@ -43,6 +47,8 @@ class SamplingParams:
     repetition_context_size: int = 60
     token_mask: object = None
     logit_bias: dict | None = None
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
 
     def hip_spec(self) -> tuple | None:
         """None (greedy) or (mode, temp, p, k) as hip_ops.sample / row_tail_pack take them."""
@@ -57,14 +63,29 @@ class SamplingParams:
         return ("categorical", float(self.temp), 0.0, 0)
 
     @property
-    def tailless(self) -> bool:
-        """Greedy without a penalty: the request needs no record in the batch tail."""
+    def recordless(self) -> bool:
+        """Greedy without a repetition penalty: the request needs no record in the batch tail's table."""
         return self.temp == 0 and self.repetition_penalty == 1.0
+
+    @property
+    def counted(self) -> bool:
+        """A frequency or a presence penalty: the request needs a row of the batch count penalty's state."""
+        return self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+
+    @property
+    def tailless(self) -> bool:
+        """Greedy without a penalty of any kind: the request's row needs no per-row state in a pass's tail."""
+        return self.recordless and not self.counted
 
     @property
     def plain(self) -> bool:
         """Greedy without a penalty, a mask or a bias: today's tail."""
         return self.tailless and self.token_mask is None and self.logit_bias is None
+
+    def count_penalties(self) -> tuple[float, float]:
+        """(frequency_penalty, presence_penalty), each within -2.0 .. 2.0: ValueError otherwise."""
+        from .. import hip_ops
+        return hip_ops.check_count_penalties(self.frequency_penalty, self.presence_penalty, "SamplingParams")
 
     def edits(self, vocab_size: int) -> tuple:
         """(the token mask's processor or None, (ids, values) of the bias table or None), checked as make_token_mask / make_logit_bias
@@ -133,14 +154,16 @@ class BatchedEngine:
         """Token ids generated for every prompt (in order), at most max_new_tokens each, ending early at a stop token.
         sampling: None (greedy, or the constructor's `sampler`), one SamplingParams for every request, or one per prompt: each request's
         own sampler, seed and repetition penalty, applied to its row inside every pass (Model.set_batch_tail) -- a request's tokens depend
-        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters.  A request's token_mask and
+        on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters.  A request's frequency_penalty and
+        presence_penalty run on per-row counts of its own generated tokens (Model.set_batch_count_penalty), rebuilt from the ids the
+        host holds whenever the request takes another row.  A request's token_mask and
         logit_bias ride the same passes (Model.set_batch_edits); a callable mask is evaluated on the host after the per-pass read-back of
         the tokens and only the rows whose words changed are uploaded.  With logprobs=True the maps report the processed log-probabilities.
         logprobs=True: returns (outputs, maps) -- maps[i][j] is the {token id: log-probability} dict of outputs[i][j], as
         InferenceEngine.generate yields it: the best top_logprobs pairs by decreasing log-probability (ties: lowest id first), then the
         token itself when absent.  top_logprobs: one int for every request or one per prompt, each 0..20; ignored with logprobs=False.  The
         records are selected per row inside the passes (Model.set_batch_top_logprobs) and fetched in the per-pass read-back of the tokens."""
-        tops = edits = None
+        tops = edits = cnts = None
         if logprobs:
             if self.sampler is not None:
                 raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
@@ -159,13 +182,16 @@ class BatchedEngine:
             seeds = [int.from_bytes(os.urandom(8), "little") if sp.seed is None else int(sp.seed) for sp in params]
             for sp, sd in zip(params, seeds):
                 sp.record(0, sd)              # every request's arguments are checked before anything runs
+                sp.count_penalties()          # (the record knows nothing of these two: their own range check)
             if any(sp.token_mask is not None or sp.logit_bias is not None for sp in params):
                 edits = [sp.edits(self.model.args.vocab_size) for sp in params]
-            if all(sp.tailless for sp in params):
-                sampling = None               # no record to configure: a request with only a mask or a bias arms no batch tail
+            if any(sp.counted for sp in params):   # the per-row counting state is armed only when some request asks for it
+                cnts = [sp.count_penalties() if sp.counted else None for sp in params]
+            if all(sp.recordless for sp in params):
+                sampling = None               # no record to configure: a request with only a mask, a bias or count penalties arms no batch tail
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        if sampling is None and tops is None and edits is None:
+        if sampling is None and tops is None and edits is None and cnts is None:
             return self._generate(prompts, max_new_tokens, None)
         try:
             if sampling is not None:
@@ -176,23 +202,28 @@ class BatchedEngine:
                 self.model.set_batch_edits(self.max_batch, masks=any_mask, bias_cap=cap)
                 self.model.write_batch_edits(list(range(self.max_batch)), [None] * self.max_batch if any_mask else None,
                                              [None] * self.max_batch if cap else None)   # (cached buffers may hold an earlier call's rows)
+            if cnts is not None:
+                self.model.set_batch_count_penalty(self.max_batch)
+                self.model.write_batch_count_penalty(list(range(self.max_batch)), [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
             tails = None if sampling is None else (params, seeds)
             if tops is None:
-                return self._generate(prompts, max_new_tokens, tails, edits=edits)
+                return self._generate(prompts, max_new_tokens, tails, edits=edits, cnts=cnts)
             bufs = self.model.set_batch_top_logprobs(self.max_batch, max(max(tops, default=1), 1))
             bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
             maps: list = [[] for _ in prompts]
-            out = self._generate(prompts, max_new_tokens, tails, (tops, bufs, maps), edits=edits)
+            out = self._generate(prompts, max_new_tokens, tails, (tops, bufs, maps), edits=edits, cnts=cnts)
             return out, maps
         finally:
             if sampling is not None:
                 self.model.clear_batch_tail()
             if edits is not None:
                 self.model.clear_batch_edits()
+            if cnts is not None:
+                self.model.clear_batch_count_penalty()
             if tops is not None:
                 self.model.clear_batch_top_logprobs()
 
-    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None, edits=None) -> list[list[int]]:
+    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None, edits=None, cnts=None) -> list[list[int]]:
         for p in prompts:
             if self._pages_for(len(p) + max_new_tokens) > self.pool.size():
                 raise ValueError("a prompt does not fit the page pool")
@@ -229,6 +260,7 @@ class BatchedEngine:
         counts: list = []             # top-n records: the count the device holds for row s (-1: the row reports nothing)
         seats: list = []              # per-request edits: the request whose mask and bias table row s holds, None = unarmed
         words: list = []              # ... and the mask words row s holds when that request's mask is a callable
+        cseats: list = []             # frequency / presence penalties: what row s of the counting state holds, (request, tokens generated) or None = a zero record
 
         def seat(rows: list) -> None:
             """The coming pass's output rows, in order: a request index (its own record; its ring rows from the ids it has been fed) or
@@ -275,6 +307,25 @@ class BatchedEngine:
                     self.model.write_batch_edits(m_rows, masks=m_new)
                 if b_rows:
                     self.model.write_batch_edits(b_rows, biases=b_new)
+            if cnts is not None:
+                # a row's record and counts are rebuilt where its sampler record is: when its occupant changes, from the ids the request has
+                # generated so far (the host holds them; the last of them is the row's input, counted here and not again by the pass).  A
+                # request one token further on in the row it held is the row's own progress: the pass counts that token itself.  A prompt
+                # that is still filling, and a request without penalties, hold a zero record.
+                gen_by = {a.request: a.generated for a in active}
+                want_c = [None if r is None or cnts[r] is None else (r, len(gen_by.get(r, []))) for r in rows]
+                cseats.extend([None] * (len(want_c) - len(cseats)))
+                c_rows, c_recs, c_gen = [], [], []
+                for s_, w in enumerate(want_c):
+                    have = cseats[s_]
+                    if w == have or (w is not None and have is not None and w[0] == have[0] and w[1] == have[1] + 1):
+                        cseats[s_] = w
+                        continue
+                    c_rows.append(s_)
+                    c_recs.append(None if w is None else (*cnts[w[0]], len(prompts[w[0]])))
+                    c_gen.append(None if w is None else list(gen_by.get(w[0], [])))
+                    cseats[s_] = w
+                self.model.write_batch_count_penalty(c_rows, c_recs, c_gen)
             if tails is None:
                 return
             params, seeds = tails
@@ -302,7 +353,9 @@ class BatchedEngine:
 
         def lone_step(idx) -> bool:
             """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
-            own, or wants log-probabilities: then it is a batch of one."""
+            own, or wants log-probabilities: then it is a batch of one.  Frequency / presence penalties alone do not make it one: a request's
+            first token is chosen against empty counts, which is the unpenalised row, so the greedy prompt pass gives the token the
+            penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`)."""
             return tops is None and (tails is None or tails[0][idx].tailless) and (edits is None or edits[idx] == (None, None))
 
         def records(n_rows: int):

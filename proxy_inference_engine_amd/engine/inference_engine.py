@@ -18,7 +18,7 @@ from .. import hip_ops
 from ..cache import BaseCache, PromptCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from ..cache.kv_cache import PagedKVCache
 from ..cache.kv_cache.quantized import check_format as check_kv_format
-from ..logits_processors import check_vocab, make_logit_bias, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
+from ..logits_processors import check_vocab, count_penalty_logits_processor, make_logit_bias, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
 from ..models import load
 from ..samplers import make_sampler
 
@@ -74,8 +74,9 @@ def fused_tail_spec(processors, sampler, structuring_engine=None, tensor_paralle
 def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_parallel: bool = False):
     """fused_tail_spec with the tail's token mask and logit bias: whether one _inference call can end inside the decode
     step's configured tail, and with what -- a dict(sampler=spec or None, repetition_penalty, context_size, mask=the token-mask processor
-    or None, bias=the logit-bias processor or None), or None for the host-orchestrated branches.  Fused: the processor list is a
-    sub-sequence of (one token mask, one repetition penalty, one logit bias) in that order -- the order the kernels define -- and
+    or None, bias=the logit-bias processor or None) -- plus counts=the frequency / presence processor when the request carries one
+     -- or None for the host-orchestrated branches.  Fused: the processor list is a
+    sub-sequence of (one token mask, one repetition penalty, one logit bias, one frequency / presence penalty) in that order -- the order the kernels define -- and
     fused_tail_spec's other conditions hold: no structuring engine, a repetition context of 1..1024, a greedy or `hip_spec` sampler,
     no tensor parallelism."""
     kinds = []
@@ -86,16 +87,21 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
             kinds.append("penalty")
         elif hasattr(proc, "ids") and hasattr(proc, "values"):
             kinds.append("bias")
+        elif hasattr(proc, "frequency_penalty") and hasattr(proc, "presence_penalty"):
+            kinds.append("counts")
         else:
             return None
-    order = [("mask", "penalty", "bias").index(k) for k in kinds]
+    order = [("mask", "penalty", "bias", "counts").index(k) for k in kinds]
     if any(b <= a for a, b in zip(order, order[1:])):  # out of order, or one kind twice
         return None
     by_kind = dict(zip(kinds, list(processors or [])))
     spec = fused_tail_spec([by_kind["penalty"]] if "penalty" in by_kind else [], sampler, structuring_engine, tensor_parallel)
     if spec is None:
         return None
-    return dict(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2], mask=by_kind.get("mask"), bias=by_kind.get("bias"))
+    plan = dict(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2], mask=by_kind.get("mask"), bias=by_kind.get("bias"))
+    if "counts" in by_kind:  # (a request without the penalties gets the plan it always got)
+        plan["counts"] = by_kind["counts"]
+    return plan
 
 
 class InferenceEngine:
@@ -131,7 +137,9 @@ class InferenceEngine:
     def make_processors(self, **kwargs) -> list[LogitsProcessor]:
         """inference_engine.py:319-335: [PSE process_logits] + optional repetition penalty; around it the two processors DESIGN.md 12
         defines -- [token mask] in front (where the PSE's masking stands), [logit bias] behind (logit_processor_factory.cpp's order).
-        token_mask: packed words, a bool mask or a callable tokens -> mask (make_token_mask); logit_bias: {token id: bias}."""
+        token_mask: packed words, a bool mask or a callable tokens -> mask (make_token_mask); logit_bias: {token id: bias}.
+        frequency_penalty / presence_penalty (each -2.0 .. 2.0): one processor behind the bias, over the counts of the
+        request's generated tokens."""
         procs: list[LogitsProcessor] = []
         if self.structuring_engine is not None:
             procs.append(self.structuring_engine.process_logits)
@@ -142,6 +150,9 @@ class InferenceEngine:
                                                              int(kwargs.get("context_size", 60))))
         if kwargs.get("logit_bias"):
             procs.append(make_logit_bias(kwargs["logit_bias"]))
+        freq, pres = hip_ops.check_count_penalties(kwargs.get("frequency_penalty") or 0.0, kwargs.get("presence_penalty") or 0.0, "make_processors")
+        if freq != 0.0 or pres != 0.0:
+            procs.append(count_penalty_logits_processor(freq, pres))
         return procs
 
     def prepare_engine(self, prompt_ids, **inference_kwargs):
@@ -236,9 +247,13 @@ class InferenceEngine:
                     self.prompt_cache.update(ids)
                     recorded = True
                     words = packed_token_mask(mask.mask_fn(self.prompt_cache.computed_ids), vocab)
+                counts = {}
+                if plan.get("counts") is not None:  # (a request without them passes nothing: set_step_tail's defaults switch them off)
+                    counts = {"frequency_penalty": plan["counts"].frequency_penalty, "presence_penalty": plan["counts"].presence_penalty,
+                              "count_start": None if fed_back else len(prompt_ids)}   # the request's first call: zero counts, from the prompt's end on
                 set_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
                          token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values),
-                         **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}))
+                         **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}), **counts)
                 if pixel_values is not None and not fed_back:
                     embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
                     tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)
@@ -299,6 +314,10 @@ class InferenceEngine:
                 self.prompt_cache.cache = BaseCache.make_kv_cache(self.model, max_kv_size=max_kv_size)
             else:
                 self.prompt_cache.create_kv_cache(self.model)                  # :274-275
+        for procs in self.logits_processors.values():
+            for proc in procs:
+                if hasattr(proc, "frequency_penalty") and hasattr(proc, "reset"):
+                    proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts may not: this request's start
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
         next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))   # :278 (host ids: no read-back)

@@ -899,6 +899,68 @@ def logits_bias_rows(logits: torch.Tensor, ids: torch.Tensor, bias: torch.Tensor
     return logits
 
 
+# ---------------------------------------------------------------- frequency and presence penalties (include/pie_hip.h: pie_count_penalty)
+COUNT_PENALTY_WORDS = C.sizeof(_ffi.pie_count_penalty) // 4   # a record as int32 words: a device table is an int32 [rows, COUNT_PENALTY_WORDS] tensor
+COUNT_PENALTY_RANGE = (-2.0, 2.0)                             # what the Python layers accept for either penalty (the OpenAI range)
+
+
+def check_count_penalties(frequency_penalty, presence_penalty, who: str) -> tuple[float, float]:
+    """(frequency_penalty, presence_penalty) as floats, each within -2.0 .. 2.0: ValueError otherwise (NaN included)."""
+    lo, hi = COUNT_PENALTY_RANGE
+    f, p = float(frequency_penalty), float(presence_penalty)
+    if not (lo <= f <= hi and lo <= p <= hi):
+        raise ValueError(f"{who}: frequency_penalty and presence_penalty must lie in {lo} .. {hi}, got {frequency_penalty!r} and {presence_penalty!r}")
+    return f, p
+
+
+def count_penalty_pack(freq: float = 0.0, pres: float = 0.0, start: int = 0, counted_pos: int | None = None) -> _ffi.pie_count_penalty:
+    """One row's record (pie_count_penalty_pack) in host memory: the two penalties (any finite value: the ABI's rule), `start` = the first
+    position that holds a generated token (the prompt's length), counted_pos = the last position already counted (None: start - 1, nothing
+    counted yet).  ValueError for NaN, inf or a negative start.  Needs no device."""
+    rec = _ffi.pie_count_penalty()
+    _ffi.check(_ffi.load().pie_count_penalty_pack(float(freq), float(pres), int(start), int(start) - 1 if counted_pos is None else int(counted_pos),
+                                                  C.byref(rec)))
+    return rec
+
+
+def count_penalty_records(records, device=None) -> torch.Tensor:
+    """Records (count_penalty_pack) as an int32 [rows, COUNT_PENALTY_WORDS] tensor, on `device` when given."""
+    import numpy as np
+    host = np.frombuffer(b"".join(bytes(r) for r in records), dtype=np.int32).reshape(len(records), COUNT_PENALTY_WORDS).copy()
+    t = torch.from_numpy(host)
+    return t if device is None else t.to(device)
+
+
+def logits_count_penalty_rows(logits: torch.Tensor, records: torch.Tensor, counts: torch.Tensor, ids: torch.Tensor | None = None,
+                              ctx: torch.Tensor | None = None, out_rows: torch.Tensor | None = None) -> torch.Tensor:
+    """pie_logits_count_penalty_rows on 16-bit logits [rows, V], IN PLACE: row s with source row i = out_rows[s] (or s) first counts its
+    input id ids[i] at position ctx[i] - 1 (once per position, from records[s].start on; `counts` and the record's counted_pos are
+    updated), then logits[s, v] -= freq * counts[s, v] + pres wherever counts[s, v] > 0 (fp32, one rounding).  records int32 [>= rows,
+    COUNT_PENALTY_WORDS] (count_penalty_records), counts int32 [>= rows, V]; ids / ctx (/ out_rows) int32 device tensors, or all None: every
+    row is live and nothing is counted.  Returns logits."""
+    _dev(logits), _dev(records), _dev(counts)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logits_count_penalty_rows: contiguous [rows, V] logits")
+    rows, V = logits.shape
+    if records.dtype != torch.int32 or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != COUNT_PENALTY_WORDS or records.shape[0] < rows:
+        raise ValueError(f"logits_count_penalty_rows: the records are a contiguous int32 [>= rows, {COUNT_PENALTY_WORDS}] device tensor (count_penalty_records)")
+    if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.dim() != 2 or counts.shape[1] != V or counts.shape[0] < rows:
+        raise ValueError("logits_count_penalty_rows: the counts are a contiguous int32 [>= rows, V] device tensor")
+    if (ids is None) != (ctx is None) or (ctx is None and out_rows is not None):
+        raise ValueError("logits_count_penalty_rows: ids and ctx come together (out_rows only with them)")
+    for t in (ids, ctx, out_rows):
+        if t is not None:
+            _dev(t)
+            if t.dtype != torch.int32 or not t.is_contiguous():
+                raise ValueError("logits_count_penalty_rows: contiguous int32 index tensors")
+    if ids is not None and (ids.numel() != ctx.numel() or ids.numel() < 1 or (out_rows is None and ids.numel() < rows) or
+                            (out_rows is not None and out_rows.numel() != rows)):
+        raise ValueError("logits_count_penalty_rows: ids and ctx of one length (>= rows without out_rows), out_rows [rows]")
+    _ffi.check(_ffi.load().pie_logits_count_penalty_rows(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(records), _ffi.p(counts), _ffi.p(ids),
+                                                         _ffi.p(ctx), _ffi.p(out_rows), 0 if ids is None else ids.numel(), _ffi.stream()))
+    return logits
+
+
 # ---------------------------------------------------------------- top-n log-probabilities (csrc/top_logprobs.hip; DESIGN.md 13)
 TOP_LOGPROBS_MAX = _ffi.PIE_TOP_LOGPROBS_MAX
 

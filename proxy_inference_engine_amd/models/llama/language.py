@@ -307,6 +307,11 @@ class Model:
         self._batch_tops: dict = {}    # rows_cap -> the passes' top-n records (set_batch_top_logprobs)
         self._batch_edit_bufs: dict = {}   # rows_cap -> the passes' per-row masks and bias tables (set_batch_edits)
         self._batch_edits = None
+        # frequency / presence penalties: the step's record + counts at stable addresses, made when first used; (freq, pres,
+        # start) while switched on.  The passes' per-row records and counts, kept per rows_cap.
+        self._cnt, self._cnt_rec, self._cnt_counts = None, None, None
+        self._batch_count_bufs: dict = {}
+        self._batch_counts = None
         torch.cuda.synchronize(device)
 
     def __del__(self):
@@ -366,7 +371,8 @@ class Model:
 
     # ------------------------------------------------------------------ the step's tail
     def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
-                      token_mask=None, logit_bias=None, top_logprobs: int | None = None) -> None:
+                      token_mask=None, logit_bias=None, top_logprobs: int | None = None, frequency_penalty: float = 0.0,
+                      presence_penalty: float = 0.0, count_start: int | None = None) -> None:
         """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
         DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
@@ -380,10 +386,17 @@ class Model:
         top_logprobs: None (off) or 0..20 -- the step also leaves the (n + 1)-pair record of hip_ops.top_logprobs over the returned
         logprobs, slot 0 being the returned token, in `step_top_logprobs`; 0 means slot 0 only.  The model owns the record
         and the workspace at stable addresses.
+        frequency_penalty / presence_penalty (each -2.0 .. 2.0): logits[v] -= frequency_penalty * c[v] + presence_penalty
+        wherever c[v] > 0, c = how often id v was GENERATED so far (prompt tokens do not count, nor the token about to be chosen), after
+        the mask's, the repetition penalty's and the bias' turn: mask (physically last), repetition penalty, logit_bias, frequency /
+        presence.  The model owns one record and one [V] count buffer at stable addresses; the step counts every token it is fed from
+        position count_start on, inside the replayed graph.  count_start given: the counts start afresh from that position
+        (reset_step_counts); None: the counting state stays and only the two values are rewritten -- a copy and a replay.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
         self._set_tail_edits(token_mask, logit_bias)
         self._set_tail_top_logprobs(top_logprobs)
+        self._set_tail_counts(frequency_penalty, presence_penalty, count_start)
         pen = (float(repetition_penalty), int(context_size)) if repetition_penalty != 1.0 and context_size != 0 else None
         seed = counter = None
         if sampler is not None:
@@ -468,6 +481,54 @@ class Model:
         if n != self._edits[1]:
             _ffi.check(lib.pie_decoder_set_logit_bias(self._dec, _ffi.p(self._bias_table[0]) if n else None, _ffi.p(self._bias_table[1]) if n else None, n))
             self._edits = (self._edits[0], n)
+
+    def _set_tail_counts(self, frequency_penalty, presence_penalty, count_start) -> None:
+        """The two penalties into the model's own record; the library is asked only when the feature is switched on or off."""
+        f, p = hip_ops.check_count_penalties(frequency_penalty, presence_penalty, "set_step_tail")
+        if count_start is not None and int(count_start) < 0:
+            raise ValueError("set_step_tail: count_start >= 0")
+        lib = _ffi.load()
+        if f == 0.0 and p == 0.0:
+            if self._cnt is not None:
+                _ffi.check(lib.pie_decoder_set_count_penalty(self._dec, None, None))
+                self._cnt = None
+            return
+        if self._cnt_rec is None:
+            self._cnt_rec = hip_ops.count_penalty_records([hip_ops.count_penalty_pack()], self.device)
+            self._cnt_counts = torch.zeros(self.logprobs.numel(), dtype=torch.int32, device=self.device)
+        was = self._cnt
+        if was is None:
+            _ffi.check(lib.pie_decoder_set_count_penalty(self._dec, _ffi.p(self._cnt_rec), _ffi.p(self._cnt_counts)))
+        if count_start is not None or was is None:
+            self._cnt = (f, p, int(count_start or 0))
+            self.reset_step_counts(self._cnt[2])
+        elif (f, p) != was[:2]:
+            self._cnt = (f, p, was[2])
+            self._cnt_rec[0, :2].copy_(hip_ops.count_penalty_records([hip_ops.count_penalty_pack(f, p)])[0, :2])  # (counted_pos lives on the device: left alone)
+
+    def reset_step_counts(self, start: int, generated_ids=()) -> None:
+        """The step's frequency / presence counting starts afresh, in stream order: the counts become the multiplicities of
+        `generated_ids` (the tokens generated so far, the first of which sits at position `start`), all of them counted already; positions
+        below `start` hold the prompt and never count.  At a request's start (start = the prompt's length, nothing generated), and after
+        a cache was trimmed."""
+        if self._cnt is None:
+            raise RuntimeError("reset_step_counts: set_step_tail(frequency_penalty=..., presence_penalty=...) first")
+        ids = torch.as_tensor(generated_ids, dtype=torch.int64).reshape(-1)
+        V = self._cnt_counts.numel()
+        self._cnt = (self._cnt[0], self._cnt[1], int(start))
+        self._cnt_counts.zero_()
+        kept = ids[(ids >= 0) & (ids < V)]
+        if kept.numel():
+            kept = kept.to(self.device)
+            self._cnt_counts.index_add_(0, kept, torch.ones(kept.numel(), dtype=torch.int32, device=self.device))
+        rec = hip_ops.count_penalty_pack(self._cnt[0], self._cnt[1], int(start), int(start) + ids.numel() - 1)
+        self._cnt_rec.copy_(hip_ops.count_penalty_records([rec]))
+
+    @property
+    def step_tail_counts(self) -> tuple:
+        """((frequency_penalty, presence_penalty, start) or None, counts): what set_step_tail last configured, and a device view of the
+        int32 [V] counts of the tokens generated so far (None before the feature was first used)."""
+        return self._cnt, self._cnt_counts
 
     @property
     def step_tail(self) -> tuple:
@@ -592,7 +653,7 @@ class Model:
         else:
             ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None:  # (the several-prompts pass ends in the greedy tail only)
+            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None and self._cnt is None:  # (the several-prompts pass ends in the greedy tail only)
                 # A fresh prompt on int8 pages: the single-sequence prompt pass reads T pages (it would run the prompt as L decode steps,
                 # ~1.2 ms per token), the several-prompts pass quantises into int8 pages -- one prompt is a batch of one.
                 nxt, logprobs, logits = self.prefill_batch([ids.cpu().numpy()], [cache])  # (a prompt arrives once: the host copy is the pass's own row bookkeeping)
@@ -831,6 +892,61 @@ class Model:
         """The multi-sequence passes launch what they launched before set_batch_edits; the buffers stay cached."""
         _ffi.check(_ffi.load().pie_decoder_set_batch_logits_edits(self._dec, 0, None, 0, None, None, None, None, 0))
         self._batch_edits = None
+
+    # ------------------------------------------------------------------ the multi-sequence passes' frequency / presence penalties (DESIGN.md 15)
+    def set_batch_count_penalty(self, rows_cap: int) -> dict:
+        """From now on step_batch / prefill_batch / step_mixed apply every output row's own frequency and presence penalties
+        (pie_decoder_set_batch_count_penalty), with or without a batch tail or batch edits: {"records": int32 [rows_cap,
+        COUNT_PENALTY_WORDS], "counts": int32 [rows_cap, V]}, returned, owned by the model and kept per rows_cap at stable addresses (the
+        4 most recent, like set_batch_tail's buffers).  Fresh buffers hold zero records and zero counts: the passes' results are the
+        unpenalised ones until write_batch_count_penalty arms a row."""
+        rows_cap = int(rows_cap)
+        if rows_cap < 1:
+            raise ValueError("set_batch_count_penalty: rows_cap >= 1")
+        bc = self._batch_count_bufs.pop(rows_cap, None)
+        if bc is None:
+            while len(self._batch_count_bufs) >= 4:
+                self._batch_count_bufs.pop(next(iter(self._batch_count_bufs)))
+            bc = {"records": hip_ops.count_penalty_records([hip_ops.count_penalty_pack()] * rows_cap, self.device),
+                  "counts": torch.zeros((rows_cap, self.args.vocab_size), dtype=torch.int32, device=self.device)}
+        self._batch_count_bufs[rows_cap] = bc  # most recently used last
+        _ffi.check(_ffi.load().pie_decoder_set_batch_count_penalty(self._dec, _ffi.p(bc["records"]), _ffi.p(bc["counts"]), rows_cap))
+        self._batch_counts = bc
+        return bc
+
+    def write_batch_count_penalty(self, rows: list[int], records: list, generated: list | None = None) -> None:
+        """Rewrites the records and the counts of `rows` of the armed buffers, in stream order -- when a row's occupant changes.
+        records[i]: (frequency_penalty, presence_penalty, start) of the occupant of rows[i] (start = its prompt's length), or None: a zero
+        record (a row without penalties, a prompt that is still filling; so is a pair of zeros: such a row's counts stay zero).  generated[i]: the ids that request has generated so far, the
+        first of which sits at position start: the row's counts become their multiplicities, all of them counted already."""
+        bc = self._batch_counts
+        if bc is None:
+            raise RuntimeError("write_batch_count_penalty: no batch count penalty is set (set_batch_count_penalty)")
+        if not rows:
+            return
+        if len(records) != len(rows) or (generated is not None and len(generated) != len(rows)):
+            raise ValueError("write_batch_count_penalty: one record and one list of generated ids per row")
+        V = bc["counts"].shape[1]
+        packed, flat = [], []
+        for i, (r, rec) in enumerate(zip(rows, records)):
+            gen = [int(t) for t in (generated[i] if generated is not None and generated[i] is not None else ())]
+            f, p = (0.0, 0.0) if rec is None else hip_ops.check_count_penalties(rec[0], rec[1], "write_batch_count_penalty")
+            if f == 0.0 and p == 0.0:  # a zero record reads no counts and counts nothing: its row stays zero
+                packed.append(hip_ops.count_penalty_pack())
+                continue
+            packed.append(hip_ops.count_penalty_pack(f, p, int(rec[2]), int(rec[2]) + len(gen) - 1))
+            flat.extend(int(r) * V + t for t in gen if 0 <= t < V)
+        idx = torch.tensor(rows, dtype=torch.long, device=self.device)
+        bc["records"].index_copy_(0, idx, hip_ops.count_penalty_records(packed, self.device))
+        bc["counts"].index_fill_(0, idx, 0)
+        if flat:
+            at = torch.tensor(flat, dtype=torch.long, device=self.device)
+            bc["counts"].view(-1).index_add_(0, at, torch.ones(at.numel(), dtype=torch.int32, device=self.device))
+
+    def clear_batch_count_penalty(self) -> None:
+        """The multi-sequence passes launch what they launched before set_batch_count_penalty; the buffers stay cached."""
+        _ffi.check(_ffi.load().pie_decoder_set_batch_count_penalty(self._dec, None, None, 0))
+        self._batch_counts = None
 
     def batch_graph_launches(self) -> int:
         """Kernel nodes of the step_batch graph captured last (-1 before the first capture)."""
