@@ -595,7 +595,7 @@ int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int3
  * replaying; the addresses, rows_cap, mask_words and bias_cap are part of the captured graph's key, so switching a part on or off or changing
  * any of them leaves the captured batch graph behind.  rows_cap == 0 switches the edits off: the passes then launch exactly what they launch
  * without.  Independent of pie_decoder_set_batch_tail and of pie_decoder_set_batch_top_logprobs.  Launches: lm_head | pie_logits_penalty_rows,
- * or k_logits_edit_rows (penalty phase + bias phase in one launch) when a bias part is set | the partials, masked per row when a mask part
+ * or k_logits_edit_rows (the same row lookup, ring window and penalise phase, then the bias phase, in one launch) when a bias part is set | the partials, masked per row when a mask part
  * is set | finish | [pie_sample_rows] | [top-n]: per pass +0 for masks and +1 for a bias without a batch tail, +0 with one; the fused
  * few-sequence step, whose lm_head epilogue partials are stale after an edit, +1 / +2 without a batch tail and +0 with one.
  * rows_cap < 0, bias_cap outside 0..1024, neither part, a part with a NULL array: PIE_E_ARG; mask_words < ceil(vocab / 32): PIE_E_SHAPE; an

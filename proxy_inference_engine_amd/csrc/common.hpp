@@ -127,6 +127,17 @@ template <class T> __device__ __forceinline__ u32 pack2(float lo, float hi) {
 }
 template <class T> __device__ __forceinline__ float round_T(float v) { return T::to_f32(T::from_f32(v)); }
 
+// Host side: runs launch(BF16()) or launch(F16()) -- the kernel launches of one launcher, instantiated for the activation dtype -- and
+// checks them.  Any other dtype fails as "<what> dtype must be PIE_BF16 or PIE_F16"; `what` is the launcher's prefix, colon included.
+template <class F>
+static inline int launch_for_dtype(int dtype, const char *what, F &&launch) {
+    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, std::string(what) + " dtype must be PIE_BF16 or PIE_F16");
+    if (dtype == PIE_BF16) launch(BF16());
+    else launch(F16());
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
 // ---------------------------------------------------------------- wave64 reductions (DPP, no LDS)
 // Sum over each 32-lane half of the wave; the result is valid in lanes 16..31 (low half) and 48..63 (high half).
 __device__ __forceinline__ float half_wave_sum(float v) {

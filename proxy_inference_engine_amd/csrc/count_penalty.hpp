@@ -92,11 +92,7 @@ __global__ void __launch_bounds__(CNT_THREADS) k_logits_count_penalty_rows(const
 }
 
 static inline int logits_count_penalty_rows_launch(int dtype, const CountPenArgs &a, int rows, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits count penalty: dtype must be PIE_BF16 or PIE_F16");
     const int slots = (a.V + CNT_VEC - 1) / CNT_VEC + 1;
     const dim3 grid((slots + CNT_THREADS - 1) / CNT_THREADS, rows);
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_count_penalty_rows<BF16>, grid, dim3(CNT_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(k_logits_count_penalty_rows<F16>, grid, dim3(CNT_THREADS), 0, st, a);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+    return launch_for_dtype(dtype, "logits count penalty:", [&](auto t) { hipLaunchKernelGGL(k_logits_count_penalty_rows<decltype(t)>, grid, dim3(CNT_THREADS), 0, st, a); });
 }

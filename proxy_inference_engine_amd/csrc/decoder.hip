@@ -156,33 +156,33 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
     return a;
 }
 
-// The configured tail over the bound outputs (include/pie_hip.h): penalty and / or bias (one launch) | frequency / presence penalties (one
-// launch) + fresh partials, which apply the token mask on their way | finish | the sampler's launches | the top-n log-probabilities' two.
+// The configured tail over the bound outputs (include/pie_hip.h), in batch_tail_launch's five stages (prefill.hip): edit -- penalty and / or
+// bias, one launch | count penalty -- frequency / presence, one launch | fresh partials, which apply the token mask on their way | finish |
+// the sampler's launches and the top-n log-probabilities' two.
 // from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
 static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     const LogitStat *stats = d->stats;
     int n_stats = d->n_stats, rc;
-    if (d->pen != 1.0 || d->bias_n) {
+    if (d->pen != 1.0 || d->bias_n) {  // edit
         PenArgs a = {};
         a.logits = d->logits, a.V = c.vocab, a.penalty = (float)d->pen, a.ids_by_pos = d->ids_by_pos, a.ids_cap = d->ids_cap, a.context = d->pen_ctx;
         a.state = d->state, a.record = from_state;
         const BiasArgs b = {d->bias_ids, d->bias_vals, d->bias_n, d->pen != 1.0};
         if ((rc = d->bias_n ? logits_edit_launch(c.dtype, a, b, st) : logits_penalty_launch(c.dtype, a, st))) return rc;
     }
-    if (d->cp_record) {  // frequency / presence: behind the penalty and the bias; a prompt pass counts nothing
+    if (d->cp_record) {  // count penalty: behind the penalty and the bias; a prompt pass counts nothing
         CountPenArgs k = {};
         k.logits = d->logits, k.V = c.vocab, k.records = d->cp_record, k.counts = d->cp_counts, k.state = d->state, k.count = from_state;
         if ((rc = logits_count_penalty_rows_launch(c.dtype, k, 1, st))) return rc;
     }
-    if (d->pen != 1.0 || d->bias_n || d->tok_mask || d->cp_record) {  // the lm_head epilogue's partials are stale
-        if ((rc = d->tok_mask ? logits_stats_masked_launch(c.dtype, d->logits, c.vocab, d->tok_mask, d->tail_stats, st)
-                              : logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st)))
-            return rc;
+    if (d->pen != 1.0 || d->bias_n || d->tok_mask || d->cp_record) {  // partials: the lm_head epilogue's are stale
+        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st, d->tok_mask))) return rc;
         stats = d->tail_stats, n_stats = TAIL_STAT_TILES;
     }
+    // finish
     if ((rc = logits_tail_launch(c.dtype, d->logits, c.vocab, stats, n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st))) return rc;
-    if (d->smp_mode != PIE_SAMPLE_GREEDY) {
+    if (d->smp_mode != PIE_SAMPLE_GREEDY) {  // sampler and top-n
         const SampleFeed feed = {&d->state->token, &d->state->pos, d->history, d->hist_cap};
         if ((rc = sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st)))
             return rc;

@@ -359,7 +359,7 @@ int pie_logprobs_argmax_masked(void *logits, int V, int dtype, const uint32_t *m
     hipStream_t st = (hipStream_t)stream;
     LogitStat *stats = nullptr;  // stream-ordered scratch, like pie_logprobs_argmax's
     if (hipMallocAsync((void **)&stats, sizeof(LogitStat) * TAIL_STAT_TILES, st) != hipSuccess) return pie::fail(PIE_E_HIP, "pie_logprobs_argmax_masked: hipMallocAsync failed");
-    int rc = logits_stats_masked_launch(dtype, (u16 *)logits, V, mask, stats, st);
+    int rc = logits_stats_launch(dtype, (u16 *)logits, V, stats, st, mask);
     if (!rc) rc = logits_tail_launch(dtype, (const u16 *)logits, V, stats, TAIL_STAT_TILES, logprobs, token, nullptr, nullptr, 0, st);
     (void)hipFreeAsync(stats, st);
     return rc;
@@ -399,7 +399,7 @@ int pie_logprobs_argmax_rows_masked(void *logits, int rows, int V, int dtype, co
     LogitStat *stats = nullptr;  // stream-ordered scratch, like pie_logprobs_argmax's
     if (hipMallocAsync((void **)&stats, sizeof(LogitStat) * TAIL_STAT_TILES * (size_t)rows, st) != hipSuccess)
         return pie::fail(PIE_E_HIP, "pie_logprobs_argmax_rows_masked: hipMallocAsync failed");
-    const int rc = logits_tail_rows_masked_launch(dtype, (u16 *)logits, V, rows, stats, masks, mask_words, mask_on, logprobs, tokens, st);
+    const int rc = logits_tail_rows_launch(dtype, (u16 *)logits, V, rows, stats, logprobs, tokens, st, masks, mask_words, mask_on);
     (void)hipFreeAsync(stats, st);
     return rc;
 }

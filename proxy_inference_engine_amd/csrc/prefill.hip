@@ -849,30 +849,21 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     const pie_decoder_config &c = d->cfg;
     PrefillScratch *s = d->prefill;
     int rc;
-    if (!d->bt_table && !d->be_rows_cap && !d->bc_records) {
-        if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st))) return rc;
-        return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
-    }
-    // per-row edits (pie_decoder_set_batch_logits_edits): the rows' biases ride the penalty's launch (k_logits_edit_rows: phase 1
-    // off without a table), the rows' masks the partials pass -- physically last, so a masked id is -inf whatever else is configured
-    PenRowsArgs p = {};
-    p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = d->bt_table, p.recent = d->bt_recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
-    if (d->be_bias_cap) {
+    // The five stages of configured_tail (decoder.hip), per row; with nothing configured only the partials and the finish run.
+    if (d->bt_table || d->be_bias_cap) {  // edit: the rows' biases ride the penalty's launch (k_logits_edit_rows: no penalties without a table)
+        PenRowsArgs p = {};
+        p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = d->bt_table, p.recent = d->bt_recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
         const BiasRowsArgs b = {d->be_bias_ids, d->be_bias_vals, d->be_bias_n, d->be_bias_cap, d->bt_table ? 1 : 0};
-        if ((rc = logits_edit_rows_launch(c.dtype, p, b, rows, st))) return rc;
-    } else if (d->bt_table) {
-        if ((rc = logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
+        if ((rc = d->be_bias_cap ? logits_edit_rows_launch(c.dtype, p, b, rows, st) : logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
     }
-    if (d->bc_records) {  // every row's frequency / presence penalties, behind its penalty and its bias
+    if (d->bc_records) {  // count penalty: behind the row's penalty and its bias
         CountPenArgs k = {};
         k.logits = logits, k.V = c.vocab, k.n_src = n_src, k.records = d->bc_records, k.counts = d->bc_counts, k.ids = ids, k.ctx = ctx, k.out_rows = out_rows;
         if ((rc = logits_count_penalty_rows_launch(c.dtype, k, rows, st))) return rc;
     }
-    if (d->be_masks)
-        rc = logits_tail_rows_masked_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, d->be_masks, d->be_mask_words, d->be_mask_on, logprobs, next_tokens, st);
-    else
-        rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st);
-    if (rc) return rc;
+    // partials and finish: the rows' masks ride the partials pass -- physically last, so a masked id is -inf whatever else is configured
+    if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st, d->be_masks, d->be_mask_words, d->be_mask_on))) return rc;
+    // sampler and top-n
     if (d->bt_table && (rc = sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st))) return rc;
     return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
 }
@@ -934,12 +925,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         g.y = logits, g.stats = s->tail_stats;
         if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_RMSNORM, EPI_LOGITS, g, st))) return rc;
         if (d->bt_table || d->be_rows_cap || d->bc_records) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty or an edit)
-        const dim3 fg(TAIL_FINISH_BLOCKS, B);
-        if (c.dtype == PIE_BF16)
-            hipLaunchKernelGGL(k_logits_finish<BF16>, fg, dim3(256), 0, st, logits, c.vocab, s->tail_stats, lm_waves, logprobs, next_tokens, (DecState *)nullptr, (int *)nullptr, 0, (const unsigned *)nullptr);
-        else
-            hipLaunchKernelGGL(k_logits_finish<F16>, fg, dim3(256), 0, st, logits, c.vocab, s->tail_stats, lm_waves, logprobs, next_tokens, (DecState *)nullptr, (int *)nullptr, 0, (const unsigned *)nullptr);
-        PIE_LAUNCH_CHECK();
+        if ((rc = logits_finish_launch(c.dtype, logits, c.vocab, B, s->tail_stats, lm_waves, logprobs, next_tokens, nullptr, nullptr, 0, nullptr, st))) return rc;
         return batch_top_logprobs_launch(d, B, logprobs, next_tokens, st);
     }
     if ((rc = embed_rows(d, tokens, B, s->x, st))) return rc;

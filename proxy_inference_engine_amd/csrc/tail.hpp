@@ -149,74 +149,116 @@ __global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V,
     }
 }
 
-// `rows` logit vectors [rows, V] at once (the multi-sequence decode step): stats_buf = rows * TAIL_STAT_TILES partials of scratch.
-static inline int logits_tail_rows_launch(int dtype, const u16 *logits, int V, int rows, LogitStat *stats_buf, float *logprobs, int *tokens,
-                                          hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits tail: dtype must be PIE_BF16 or PIE_F16");
-    const dim3 g1(TAIL_STAT_TILES, rows), g2(TAIL_FINISH_BLOCKS, rows);
-    if (dtype == PIE_BF16) {
-        hipLaunchKernelGGL(k_logits_stats<BF16>, g1, dim3(256), 0, st, logits, V, stats_buf);
-        hipLaunchKernelGGL(k_logits_finish<BF16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_logits_stats<F16>, g1, dim3(256), 0, st, logits, V, stats_buf);
-        hipLaunchKernelGGL(k_logits_finish<F16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
-    }
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+// ---------------------------------------------------------------- launchers of the two stages
+// The per-tile partials of one logit vector as pie_logprobs_argmax computes them (k_logits_stats over TAIL_STAT_TILES tiles), into caller-owned
+// scratch: the step's tail after an edit, whose lm_head epilogue partials are stale.  mask != nullptr: the token mask is applied on the way
+// (k_logits_stats_masked), and `logits` then hold -inf at every disallowed id; without one the logits are only read.
+static inline int logits_stats_launch(int dtype, u16 *logits, int V, LogitStat *stats, hipStream_t st, const unsigned *mask = nullptr) {
+    return launch_for_dtype(dtype, mask ? "logits mask:" : "logits tail:", [&](auto t) {
+        using T = decltype(t);
+        if (mask) hipLaunchKernelGGL(k_logits_stats_masked<T>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats, mask);
+        else hipLaunchKernelGGL(k_logits_stats<T>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, (const u16 *)logits, V, stats);
+    });
 }
 
-// The same two launches with every row's own token mask riding the partials pass (k_logits_stats_rows_masked): masks [rows, mask_words],
-// mask_words >= ceil(V / 32) (checked by every caller), mask_on [rows].
-static inline int logits_tail_rows_masked_launch(int dtype, u16 *logits, int V, int rows, LogitStat *stats_buf, const unsigned *masks, int mask_words,
-                                                 const int *mask_on, float *logprobs, int *tokens, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits tail: dtype must be PIE_BF16 or PIE_F16");
-    const dim3 g1(TAIL_STAT_TILES, rows), g2(TAIL_FINISH_BLOCKS, rows);
-    if (dtype == PIE_BF16) {
-        hipLaunchKernelGGL(k_logits_stats_rows_masked<BF16>, g1, dim3(256), 0, st, logits, V, stats_buf, masks, mask_words, mask_on);
-        hipLaunchKernelGGL(k_logits_finish<BF16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_logits_stats_rows_masked<F16>, g1, dim3(256), 0, st, logits, V, stats_buf, masks, mask_words, mask_on);
-        hipLaunchKernelGGL(k_logits_finish<F16>, g2, dim3(256), 0, st, logits, V, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, (const unsigned *)nullptr);
-    }
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+// k_logits_finish over `rows` logit vectors [rows, V], each with its own n_stats partials (stats [rows, n_stats]) and its own token.
+// state / history / err_word belong to the single-sequence step (rows == 1) and are nullptr elsewhere.
+static inline int logits_finish_launch(int dtype, const u16 *logits, int V, int rows, const LogitStat *stats, int n_stats, float *logprobs, int *tokens,
+                                       DecState *state, int *history, int hist_cap, const unsigned *err_word, hipStream_t st) {
+    if (n_stats > TAIL_MAX_STATS) return pie::fail(PIE_E_SHAPE, "logits tail: too many partials");
+    return launch_for_dtype(dtype, "logits tail:", [&](auto t) {
+        hipLaunchKernelGGL(k_logits_finish<decltype(t)>, dim3(TAIL_FINISH_BLOCKS, rows), dim3(256), 0, st, logits, V, stats, n_stats, logprobs, tokens, state, history,
+                           hist_cap, err_word);
+    });
 }
 
-// stats == nullptr (op-level API): the per-tile partials are computed from the logits first, into
-// stream-ordered scratch (hipMallocAsync; the decoder path passes its own stats and never allocates).
+// `rows` logit vectors [rows, V] at once (the multi-sequence passes): stats_buf = rows * TAIL_STAT_TILES partials of scratch.  masks != nullptr:
+// every row's own token mask rides the partials pass (k_logits_stats_rows_masked): masks [rows, mask_words], mask_words >= ceil(V / 32)
+// (checked by every caller), mask_on [rows].  Without masks the partials pass is k_logits_stats and the logits are only read.
+static inline int logits_tail_rows_launch(int dtype, u16 *logits, int V, int rows, LogitStat *stats_buf, float *logprobs, int *tokens, hipStream_t st,
+                                          const unsigned *masks = nullptr, int mask_words = 0, const int *mask_on = nullptr) {
+    const int rc = launch_for_dtype(dtype, "logits tail:", [&](auto t) {
+        using T = decltype(t);
+        const dim3 grid(TAIL_STAT_TILES, rows);
+        if (masks) hipLaunchKernelGGL(k_logits_stats_rows_masked<T>, grid, dim3(256), 0, st, logits, V, stats_buf, masks, mask_words, mask_on);
+        else hipLaunchKernelGGL(k_logits_stats<T>, grid, dim3(256), 0, st, (const u16 *)logits, V, stats_buf);
+    });
+    return rc ? rc : logits_finish_launch(dtype, logits, V, rows, stats_buf, TAIL_STAT_TILES, logprobs, tokens, nullptr, nullptr, 0, nullptr, st);
+}
+
+// The single-sequence tail over given partials.  stats == nullptr (op-level API): the per-tile partials are computed from the logits first,
+// into stream-ordered scratch (hipMallocAsync; the decoder path passes its own stats and never allocates).
 static inline int logits_tail_launch(int dtype, const u16 *logits, int V, const LogitStat *stats, int n_stats, float *logprobs,
                                      int *token, DecState *state, int *history, int hist_cap, hipStream_t st, const unsigned *err_word = nullptr) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits tail: dtype must be PIE_BF16 or PIE_F16");
-    if (stats && n_stats > TAIL_MAX_STATS) return pie::fail(PIE_E_SHAPE, "logits tail: too many partials");
+    if (stats) return logits_finish_launch(dtype, logits, V, 1, stats, n_stats, logprobs, token, state, history, hist_cap, err_word, st);
     LogitStat *tmp = nullptr;
-    if (!stats) {
-        if (hipMallocAsync((void **)&tmp, sizeof(LogitStat) * TAIL_STAT_TILES, st) != hipSuccess)
-            return pie::fail(PIE_E_HIP, "logits tail: hipMallocAsync failed");
-        if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_stats<BF16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, tmp);
-        else hipLaunchKernelGGL(k_logits_stats<F16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, tmp);
-        PIE_LAUNCH_CHECK();
-        stats = tmp, n_stats = TAIL_STAT_TILES;
+    if (hipMallocAsync((void **)&tmp, sizeof(LogitStat) * TAIL_STAT_TILES, st) != hipSuccess)
+        return pie::fail(PIE_E_HIP, "logits tail: hipMallocAsync failed");
+    int rc = logits_stats_launch(dtype, const_cast<u16 *>(logits), V, tmp, st);  // unmasked: read only
+    if (!rc) rc = logits_finish_launch(dtype, logits, V, 1, tmp, TAIL_STAT_TILES, logprobs, token, state, history, hist_cap, err_word, st);
+    if (rc) {
+        (void)hipFreeAsync(tmp, st);
+        return rc;
     }
-    if (dtype == PIE_BF16)
-        hipLaunchKernelGGL(k_logits_finish<BF16>, dim3(TAIL_FINISH_BLOCKS), dim3(256), 0, st, logits, V, stats, n_stats, logprobs, token, state, history, hist_cap, err_word);
-    else
-        hipLaunchKernelGGL(k_logits_finish<F16>, dim3(TAIL_FINISH_BLOCKS), dim3(256), 0, st, logits, V, stats, n_stats, logprobs, token, state, history, hist_cap, err_word);
-    PIE_LAUNCH_CHECK();
-    if (tmp) PIE_HIP_TRY(hipFreeAsync(tmp, st));
+    PIE_HIP_TRY(hipFreeAsync(tmp, st));
     return PIE_OK;
 }
 
-// ---------------------------------------------------------------- repetition penalty (logits_processors/repetition.py:11-22)
-// logits[id] = T(x < 0 ? x * penalty : x / penalty), x = f32(logits[id]), once for every distinct id of a window of at most PEN_MAX_IDS token
-// ids: the reference gathers, computes and scatters, so an id that occurs several times is penalised once.  One workgroup, a thread per
-// window entry; an entry owns its id when no earlier entry holds it.  Ids outside [0, V) are skipped, never indexed.
-// The window is either ids[0..n) (the op, pie_logits_penalty) or -- state != nullptr, the decode step's tail -- the positions
-// max(0, pos + 1 - context) .. pos of ids_by_pos, pos = state->pos: the ids the model was fed, the row's own input included
-// (prompt_cache.update(ids) runs before the processors, inference_engine.py:255-266).  record: the step's input token is state->token
-// (fed back by the previous tail, or set by the caller): it is written to ids_by_pos[pos] first, so fed-back tokens never visit the host.
-// Every index into ids_by_pos is checked against ids_cap here.
+// ---------------------------------------------------------------- the logits edits: repetition penalty and logit bias
+// Repetition penalty (logits_processors/repetition.py:11-22): logits[id] = T(x < 0 ? x * penalty : x / penalty), x = f32(logits[id]), once for
+// every distinct id of a window of at most PEN_MAX_IDS token ids: the reference gathers, computes and scatters, so an id that occurs several
+// times is penalised once.  Logit bias (logits_params.hpp: logit_bias; logit_processor_factory.cpp builds it after the repetition penalty):
+// logits[ids[t]] = T(f32(logits[ids[t]]) + bias[t]), one fp32 addition and one rounding, once for every distinct id of at most PEN_MAX_IDS entries.
+//
+// Four kernels -- the penalty alone or the penalty and the bias in one launch, for one logit vector (the op and the decode step) or one
+// workgroup per row of a multi-sequence pass -- composed of the device phases below, each written once.  A workgroup is PEN_MAX_IDS threads,
+// a thread per window entry or bias entry, and one LDS array s_ids[PEN_MAX_IDS] that both phases decide ownership through.
 constexpr int PEN_MAX_IDS = 1024;
 
+// Ownership: entry t owns `id` when the id lies in [0, V) -- anything else is skipped, never indexed -- and no earlier entry holds it.
+// The scan takes two entries per LDS read (s_ids is 8-byte aligned) and compares both without a branch between them: a wave waits for
+// every read before it can leave the loop, so the reads are the loop's cost (EXPERIMENTS.md, "One set of device phases").
+__device__ __forceinline__ bool owns_id(const int *s_ids, int t, int id, int V) {
+    bool own = id >= 0 && id < V;
+    int j = 0;
+    for (; own && j + 1 < t; j += 2) {
+        const int2 e = *reinterpret_cast<const int2 *>(s_ids + j);
+        own = (e.x != id) & (e.y != id);  // an earlier entry owns this id
+    }
+    return own && (j >= t || s_ids[j] != id);
+}
+
+// Penalise phase: this thread's window entry is `id` (-1: none).  One barrier; then the owners do the one read-modify-write.  Returns to the
+// kernel on every path, so that a bias phase can follow.
+template <class T>
+__device__ __forceinline__ void penalise_phase(u16 *logits, int V, float penalty, int id, int *s_ids) {
+    const int t = threadIdx.x;
+    s_ids[t] = id;
+    __syncthreads();
+    if (!owns_id(s_ids, t, id, V)) return;
+    const float x = T::to_f32(logits[id]);
+    logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, penalty) : __fdiv_rn(x, penalty));  // -0.0 is not < 0: divided
+}
+
+// Bias phase: entries base + t, t < n, of ids / bias (read on the device each launch), ownership among duplicate ids as above.  Two barriers.
+// It reads what a penalise phase in front of it stored to the same id from another wave.  The rule this rests on: __syncthreads() is a
+// workgroup-scope release / acquire fence around the barrier, and at workgroup scope that needs no cache maintenance here -- the waves of one
+// workgroup run on one CU (the library is not built with -mtgsplit) and their global accesses go through that CU's one in-order vector L1, so
+// a plain store issued before the barrier is what a plain load issued after it returns.  Nothing here crosses a workgroup.
+template <class T>
+__device__ __forceinline__ void bias_phase(u16 *logits, int V, const int *ids, const float *bias, int n, size_t base, int *s_ids) {
+    __syncthreads();  // the penalise phase's stores are visible, and its readers of s_ids are done
+    const int t = threadIdx.x;
+    const int id = t < n ? ids[base + t] : -1;
+    s_ids[t] = id;
+    __syncthreads();
+    if (owns_id(s_ids, t, id, V)) logits[id] = T::from_f32(__fadd_rn(T::to_f32(logits[id]), bias[base + t]));
+}
+
+// One logit vector.  The window is either ids[0..n) (the op, pie_logits_penalty) or -- state != nullptr, the decode step's tail -- the
+// positions max(0, pos + 1 - context) .. pos of ids_by_pos, pos = state->pos: the ids the model was fed, the row's own input included
+// (prompt_cache.update(ids) runs before the processors, inference_engine.py:255-266).  record: the step's input token is state->token
+// (fed back by the previous tail, or set by the caller): it is written to ids_by_pos[pos] first, so fed-back tokens never visit the host.
 struct PenArgs {
     u16 *logits;
     int V;
@@ -229,86 +271,48 @@ struct PenArgs {
     int record;
 };
 
-template <class T>
-__device__ __forceinline__ void logits_penalty_phase(const PenArgs &a, int *s_ids) {
+// Step window: this thread's entry of the window, -1 beyond it.  Every index into ids_by_pos is checked against ids_cap here.
+__device__ __forceinline__ int step_window_id(const PenArgs &a) {
     const int t = threadIdx.x;
-    int n = a.n, id = -1;
-    if (a.state) {
-        const int pos = a.state->pos, lo = pos + 1 - a.context > 0 ? pos + 1 - a.context : 0;
-        n = pos + 1 - lo;  // <= context <= PEN_MAX_IDS
-        const int p = lo + t;
-        if (t < n && p >= 0 && p < a.ids_cap) {
-            if (a.record && p == pos) id = a.state->token, a.ids_by_pos[p] = id;
-            else id = a.ids_by_pos[p];
-        }
-    } else if (t < n) {
-        id = a.ids[t];
-    }
-    s_ids[t] = id;
-    __syncthreads();
-    if (t >= n || id < 0 || id >= a.V) return;
-    for (int j = 0; j < t; ++j)
-        if (s_ids[j] == id) return;  // an earlier entry owns this id
-    const float x = T::to_f32(a.logits[id]);
-    a.logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, a.penalty) : __fdiv_rn(x, a.penalty));  // -0.0 is not < 0: divided
+    if (!a.state) return t < a.n ? a.ids[t] : -1;
+    const int pos = a.state->pos, lo = pos + 1 - a.context > 0 ? pos + 1 - a.context : 0;
+    const int n = pos + 1 - lo, p = lo + t;  // n <= context <= PEN_MAX_IDS
+    if (t >= n || p < 0 || p >= a.ids_cap) return -1;
+    if (a.record && p == pos) return a.ids_by_pos[p] = a.state->token;
+    return a.ids_by_pos[p];
 }
 
 template <class T>
 __global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty(const PenArgs a) {
-    __shared__ int s_ids[PEN_MAX_IDS];
-    logits_penalty_phase<T>(a, s_ids);
+    __shared__ alignas(8) int s_ids[PEN_MAX_IDS];
+    penalise_phase<T>(a.logits, a.V, a.penalty, step_window_id(a), s_ids);
 }
 
-// The logit bias (logits_params.hpp: logit_bias; logit_processor_factory.cpp builds it after the repetition penalty), in the penalty's launch:
-// phase 1 is logits_penalty_phase (skipped when b.penalise == 0: then nothing is recorded in ids_by_pos either), phase 2 one thread per
-// entry t < n: logits[ids[t]] = T(f32(logits[ids[t]]) + bias[t]), one fp32 addition and one rounding, for every entry whose id is in [0, V) and
-// not held by an earlier entry (k_logits_penalty's rule, decided through the same LDS array).  ids / bias are read on the device each launch.
-// Phase 2 reads what phase 1 stored to the same id from another wave.  The rule this rests on: __syncthreads() is a workgroup-scope release /
-// acquire fence around the barrier, and at workgroup scope that needs no cache maintenance here -- the waves of one workgroup run on one CU
-// (the library is not built with -mtgsplit) and their global accesses go through that CU's one in-order vector L1, so a plain store issued
-// before the barrier is what a plain load issued after it returns.  Nothing here crosses a workgroup.
 struct BiasArgs {
     const int *ids;
     const float *bias;
     int n;  // 1..PEN_MAX_IDS
-    int penalise;  // run phase 1 (the caller's own decision: no float sentinel)
+    int penalise;  // run the penalise phase (the caller's own decision: no float sentinel); off: nothing is recorded in ids_by_pos either
 };
 
 template <class T>
 __global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_edit(const PenArgs a, const BiasArgs b) {
-    __shared__ int s_ids[PEN_MAX_IDS];
-    if (b.penalise) logits_penalty_phase<T>(a, s_ids);  // block-uniform
-    __syncthreads();  // phase 1's stores are visible, and its readers of s_ids are done
-    const int t = threadIdx.x;
-    const int id = t < b.n ? b.ids[t] : -1;
-    s_ids[t] = id;
-    __syncthreads();
-    if (id < 0 || id >= a.V) return;
-    for (int j = 0; j < t; ++j)
-        if (s_ids[j] == id) return;  // an earlier entry owns this id
-    a.logits[id] = T::from_f32(__fadd_rn(T::to_f32(a.logits[id]), b.bias[t]));
-}
-
-static inline int logits_edit_launch(int dtype, const PenArgs &a, const BiasArgs &b, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits bias: dtype must be PIE_BF16 or PIE_F16");
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_edit<BF16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a, b);
-    else hipLaunchKernelGGL(k_logits_edit<F16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a, b);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+    __shared__ alignas(8) int s_ids[PEN_MAX_IDS];
+    if (b.penalise) penalise_phase<T>(a.logits, a.V, a.penalty, step_window_id(a), s_ids);  // block-uniform
+    bias_phase<T>(a.logits, a.V, b.ids, b.bias, b.n, 0, s_ids);
 }
 
 static inline int logits_penalty_launch(int dtype, const PenArgs &a, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits penalty: dtype must be PIE_BF16 or PIE_F16");
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_penalty<BF16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a);
-    else hipLaunchKernelGGL(k_logits_penalty<F16>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+    return launch_for_dtype(dtype, "logits penalty:", [&](auto t) { hipLaunchKernelGGL(k_logits_penalty<decltype(t)>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a); });
 }
 
-// The same penalty for every row of a multi-sequence pass at once (pie_logits_penalty_rows): one workgroup per output row s, the penalty and
-// the window size from the row's record (device memory, untrusted: the context is clamped to [1, PEN_MAX_IDS]), the window from the row's
-// ring recent[s][q & 1023] = the id fed at position q.  Source row i = out_rows ? out_rows[s] : s of the pass's ids / ctx (checked against
-// n_src); pos = ctx[i] - 1 < 0: an idle slot, skipped.  The row's own input id is recorded at pos first; a penalty of exactly 1.0 stops there.
+static inline int logits_edit_launch(int dtype, const PenArgs &a, const BiasArgs &b, hipStream_t st) {
+    return launch_for_dtype(dtype, "logits bias:", [&](auto t) { hipLaunchKernelGGL(k_logits_edit<decltype(t)>, dim3(1), dim3(PEN_MAX_IDS), 0, st, a, b); });
+}
+
+// Every row of a multi-sequence pass at once (pie_logits_penalty_rows, pie_logits_bias_rows and the passes' tail): one
+// workgroup per output row s, the penalty and the window size from the row's record table[s], the window from the row's ring
+// recent[s][q & 1023] = the id fed at position q, the bias from the row's own entries t < n[s] of ids / bias [rows, cap].
 struct PenRowsArgs {
     u16 *logits;
     int V, n_src;
@@ -317,132 +321,71 @@ struct PenRowsArgs {
     const int *ids, *ctx, *out_rows;
 };
 
-template <class T>
-__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty_rows(const PenRowsArgs a) {
-    __shared__ int s_ids[PEN_MAX_IDS];
-    const int t = threadIdx.x, s = blockIdx.x;
-    const int i = a.out_rows ? a.out_rows[s] : s;
-    if (i < 0 || i >= a.n_src) return;  // block-uniform, like every return before the barrier
-    const int pos = a.ctx[i] - 1;
-    if (pos < 0) return;
-    int *ring = a.recent + (size_t)s * PEN_MAX_IDS;
-    const float penalty = a.table[s].penalty;
-    if (penalty == 1.0f) {
-        if (t == 0) ring[pos & (PEN_MAX_IDS - 1)] = a.ids[i];
-        return;
-    }
-    int context = a.table[s].context_size;
-    context = context < 1 ? 1 : (context > PEN_MAX_IDS ? PEN_MAX_IDS : context);
-    const int lo = pos + 1 - context > 0 ? pos + 1 - context : 0, n = pos + 1 - lo;  // 1 <= n <= context
-    int id = -1;
-    if (t < n) {
-        const int p = lo + t;
-        if (p == pos) id = a.ids[i], ring[p & (PEN_MAX_IDS - 1)] = id;
-        else id = ring[p & (PEN_MAX_IDS - 1)];
-    }
-    s_ids[t] = id;
-    __syncthreads();
-    if (t >= n || id < 0 || id >= a.V) return;
-    for (int j = 0; j < t; ++j)
-        if (s_ids[j] == id) return;  // an earlier entry owns this id
-    u16 *logits = a.logits + (size_t)s * a.V;
-    const float x = T::to_f32(logits[id]);
-    logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, penalty) : __fdiv_rn(x, penalty));  // k_logits_penalty's arithmetic
-}
-
-static inline int logits_penalty_rows_launch(int dtype, const PenRowsArgs &a, int rows, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits penalty: dtype must be PIE_BF16 or PIE_F16");
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_penalty_rows<BF16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a);
-    else hipLaunchKernelGGL(k_logits_penalty_rows<F16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-// The rows' penalties and the rows' logit biases in one launch (pie_logits_bias_rows, and the multi-sequence passes' tail when a bias is
-// configured): one workgroup per output row s.  Phase 1 is k_logits_penalty_rows' body on that row (b.penalise == 0, no batch
-// tail: off, and nothing is recorded in the ring), phase 2 k_logits_edit's bias phase on the row's logits with the row's own table: entries
-// t < n[s] (device memory, untrusted: clamped to [0, cap]) of ids / bias [rows, cap], ownership among duplicate ids through the same LDS array.
-// k_logits_penalty_rows leaves before its barrier for an idle slot, a source row out of range and a penalty of exactly 1.0; a row of the
-// last kind may still carry a bias, so here only the first two leave (such a row gets neither phase) and everything else that skips phase 1
-// is a block-uniform decision (a kernel argument, or a value every thread reads from one address that no thread writes), after which
-// every thread reaches phase 2's barriers.  The ring is written where k_logits_penalty_rows writes it.  a.ctx == nullptr (the op): every row
-// is live.  Phase 2 reads what phase 1 stored to the same id from another wave: the workgroup-scope argument above k_logits_edit.
 struct BiasRowsArgs {
     const int *ids;     // [rows, cap]
     const float *bias;  // [rows, cap]
-    const int *n;       // [rows]
+    const int *n;       // [rows]: device memory, untrusted: clamped to [0, cap]
     int cap;            // 1..PEN_MAX_IDS
-    int penalise;       // run phase 1 (the caller's own decision: a batch tail is set)
+    int penalise;       // run the rows' penalties (the caller's own decision: a batch tail is set); off: nothing is recorded in the ring
 };
 
+// Row lookup: output row s is source row i = out_rows ? out_rows[s] : s of the pass's ids / ctx, at position pos = ctx[i] - 1.  False for a
+// source row outside [0, n_src) and for an idle slot (pos < 0): the workgroup then returns before any barrier.
+__device__ __forceinline__ bool row_lookup(const PenRowsArgs &a, int s, int &i, int &pos) {
+    i = a.out_rows ? a.out_rows[s] : s;
+    if (i < 0 || i >= a.n_src) return false;
+    pos = a.ctx[i] - 1;
+    return pos >= 0;
+}
+
+// Ring window: this thread's entry of the positions max(0, pos + 1 - context) .. pos of a row's ring, -1 beyond them.  context is device
+// memory, untrusted: clamped to [1, PEN_MAX_IDS].  The window's last thread holds position pos: the row's own input id, which it records.
+__device__ __forceinline__ int ring_window_id(int *ring, int context, int pos, const int *input_id) {
+    const int t = threadIdx.x;
+    context = context < 1 ? 1 : (context > PEN_MAX_IDS ? PEN_MAX_IDS : context);
+    const int lo = pos + 1 - context > 0 ? pos + 1 - context : 0, n = pos + 1 - lo, p = lo + t;  // 1 <= n <= context
+    if (t >= n) return -1;
+    if (p == pos) return ring[p & (PEN_MAX_IDS - 1)] = *input_id;
+    return ring[p & (PEN_MAX_IDS - 1)];
+}
+
+// A penalty of exactly 1.0 edits nothing, but the row's input id still has to reach the ring: such a row takes a window of that one entry,
+// which thread 0 records.  The two rows kernels differ in what follows.  k_logits_penalty_rows leaves there, before its one barrier.
+// k_logits_edit_rows must not: the row may still carry a bias, so it only skips the penalise phase.  Every exit before a barrier and every
+// skipped phase is a block-uniform decision: a kernel argument, or a value that every thread reads from one address that no thread writes.
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_penalty_rows(const PenRowsArgs a) {
+    __shared__ alignas(8) int s_ids[PEN_MAX_IDS];
+    const int s = blockIdx.x;
+    int i, pos;
+    if (!row_lookup(a, s, i, pos)) return;
+    const float penalty = a.table[s].penalty;
+    const int id = ring_window_id(a.recent + (size_t)s * PEN_MAX_IDS, penalty == 1.0f ? 1 : a.table[s].context_size, pos, a.ids + i);
+    if (penalty == 1.0f) return;
+    penalise_phase<T>(a.logits + (size_t)s * a.V, a.V, penalty, id, s_ids);
+}
+
+// a.ctx == nullptr (the op, pie_logits_bias_rows): every row is live.  A row that the lookup rejects gets neither phase.
 template <class T>
 __global__ void __launch_bounds__(PEN_MAX_IDS) k_logits_edit_rows(const PenRowsArgs a, const BiasRowsArgs b) {
-    __shared__ int s_ids[PEN_MAX_IDS];
-    const int t = threadIdx.x, s = blockIdx.x;
+    __shared__ alignas(8) int s_ids[PEN_MAX_IDS];
+    const int s = blockIdx.x;
     int i = s, pos = 0;
-    if (a.ctx) {
-        i = a.out_rows ? a.out_rows[s] : s;
-        if (i < 0 || i >= a.n_src) return;  // block-uniform, and before every barrier
-        pos = a.ctx[i] - 1;
-        if (pos < 0) return;  // likewise
-    }
+    if (a.ctx && !row_lookup(a, s, i, pos)) return;
     u16 *logits = a.logits + (size_t)s * a.V;
-    const float penalty = b.penalise ? a.table[s].penalty : 1.0f;
-    if (b.penalise && penalty == 1.0f && t == 0) a.recent[(size_t)s * PEN_MAX_IDS + (pos & (PEN_MAX_IDS - 1))] = a.ids[i];
-    if (penalty != 1.0f) {  // block-uniform: phase 1, k_logits_penalty_rows from its window on
-        int *ring = a.recent + (size_t)s * PEN_MAX_IDS;
-        int context = a.table[s].context_size;
-        context = context < 1 ? 1 : (context > PEN_MAX_IDS ? PEN_MAX_IDS : context);
-        const int lo = pos + 1 - context > 0 ? pos + 1 - context : 0, n = pos + 1 - lo;  // 1 <= n <= context
-        int id = -1;
-        if (t < n) {
-            const int p = lo + t;
-            if (p == pos) id = a.ids[i], ring[p & (PEN_MAX_IDS - 1)] = id;
-            else id = ring[p & (PEN_MAX_IDS - 1)];
-        }
-        s_ids[t] = id;
-        __syncthreads();
-        bool own = t < n && id >= 0 && id < a.V;
-        for (int j = 0; own && j < t; ++j) own = s_ids[j] != id;  // an earlier entry owns this id
-        if (own) {
-            const float x = T::to_f32(logits[id]);
-            logits[id] = T::from_f32(x < 0.0f ? __fmul_rn(x, penalty) : __fdiv_rn(x, penalty));  // k_logits_penalty's arithmetic
-        }
+    if (b.penalise) {
+        const float penalty = a.table[s].penalty;
+        const int id = ring_window_id(a.recent + (size_t)s * PEN_MAX_IDS, penalty == 1.0f ? 1 : a.table[s].context_size, pos, a.ids + i);
+        if (penalty != 1.0f) penalise_phase<T>(logits, a.V, penalty, id, s_ids);
     }
-    __syncthreads();  // phase 1's stores are visible, and its readers of s_ids are done
-    int bn = b.n[s];
-    bn = bn < 0 ? 0 : (bn > b.cap ? b.cap : bn);
-    const int id = t < bn ? b.ids[(size_t)s * b.cap + t] : -1;
-    s_ids[t] = id;
-    __syncthreads();
-    if (id < 0 || id >= a.V) return;
-    for (int j = 0; j < t; ++j)
-        if (s_ids[j] == id) return;  // an earlier entry owns this id
-    logits[id] = T::from_f32(__fadd_rn(T::to_f32(logits[id]), b.bias[(size_t)s * b.cap + t]));
+    const int n = b.n[s];
+    bias_phase<T>(logits, a.V, b.ids, b.bias, n < 0 ? 0 : (n > b.cap ? b.cap : n), (size_t)s * b.cap, s_ids);
+}
+
+static inline int logits_penalty_rows_launch(int dtype, const PenRowsArgs &a, int rows, hipStream_t st) {
+    return launch_for_dtype(dtype, "logits penalty:", [&](auto t) { hipLaunchKernelGGL(k_logits_penalty_rows<decltype(t)>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a); });
 }
 
 static inline int logits_edit_rows_launch(int dtype, const PenRowsArgs &a, const BiasRowsArgs &b, int rows, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits bias: dtype must be PIE_BF16 or PIE_F16");
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_edit_rows<BF16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a, b);
-    else hipLaunchKernelGGL(k_logits_edit_rows<F16>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a, b);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-// The per-tile partials of `logits` as pie_logprobs_argmax computes them (k_logits_stats over TAIL_STAT_TILES tiles), into caller-owned
-// scratch: the step's tail after a penalty, whose lm_head epilogue partials are stale.
-static inline int logits_stats_launch(int dtype, const u16 *logits, int V, LogitStat *stats, hipStream_t st) {
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_stats<BF16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats);
-    else hipLaunchKernelGGL(k_logits_stats<F16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
-}
-
-// The same partials with the token mask applied on the way (k_logits_stats_masked): `logits` then hold -inf at every disallowed id.
-static inline int logits_stats_masked_launch(int dtype, u16 *logits, int V, const unsigned *mask, LogitStat *stats, hipStream_t st) {
-    if (dtype != PIE_BF16 && dtype != PIE_F16) return pie::fail(PIE_E_ARG, "logits mask: dtype must be PIE_BF16 or PIE_F16");
-    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_logits_stats_masked<BF16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats, mask);
-    else hipLaunchKernelGGL(k_logits_stats_masked<F16>, dim3(TAIL_STAT_TILES), dim3(256), 0, st, logits, V, stats, mask);
-    PIE_LAUNCH_CHECK();
-    return PIE_OK;
+    return launch_for_dtype(dtype, "logits bias:", [&](auto t) { hipLaunchKernelGGL(k_logits_edit_rows<decltype(t)>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a, b); });
 }

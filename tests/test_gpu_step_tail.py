@@ -326,3 +326,43 @@ def test_tensor_parallel_refuses_and_call_keeps_raw_logits(tiny):
         model.set_step_tail()
     assert np.array_equal(got, raw)
     assert np.array_equal(one, to_bits(model(ids[:, :1], cache=model.make_cache())))
+
+
+# ------------------------------------------------------------------ 7. the ids_cap boundary of the step's window
+def test_step_window_stops_at_ids_cap(tiny):
+    """The step form checks every index into ids_by_pos against ids_cap.  The penalty is configured through the library with a cap of 6,
+    far below the buffer's size; everything from index 6 on holds a sentinel id.  A 4-token prompt and seven un-graphed steps take pos
+    from 3 to 10: the window (5 positions) first lies below the cap, then straddles it, then (the last step) lies wholly beyond it.
+    Positions at or beyond the cap are neither read nor recorded."""
+    from proxy_inference_engine_amd import _ffi, hip_ops
+    g, cfg, model = tiny
+    lib = _ffi.load()
+    prompt, pen, ctx, cap, sentinel, steps = [17, 450, 33, 17], 1.8, 5, 6, 7, 7
+    try:
+        model.set_step_tail()
+        model.fed_ids.zero_()
+        model.fed_ids[cap:] = sentinel
+        _ffi.check(lib.pie_decoder_set_logits_penalty(model._dec, pen, ctx, _ffi.p(model.fed_ids), cap))
+        cache, got, fed = model.make_cache(), [], list(prompt)
+        for i in range(1 + steps):
+            tok, lp, lg = model.step(dev_ids(prompt) if i == 0 else None, cache, graph=False)
+            got.append(to_bits(lg))
+            seen = min(cap, len(fed))
+            assert model.fed_ids[:seen].tolist() == fed[:seen], i                      # fed ids below the cap: recorded
+            assert bool((model.fed_ids[cap:] == sentinel).all()), i                    # at or beyond it: nothing was written
+            fed.append(int(tok.item()))
+        assert sentinel not in fed
+    finally:
+        _ffi.check(lib.pie_decoder_set_logits_penalty(model._dec, 1.0, 0, None, 0))
+        model.set_step_tail()
+    # the raw logits of the same run: the unconfigured step over the same ids, fed explicitly
+    cache = model.make_cache()
+    for i in range(1 + steps):
+        raw = model.step(dev_ids(prompt if i == 0 else fed[len(prompt) + i - 1:len(prompt) + i]), cache, graph=False)[2].clone()
+        pos = len(prompt) + i - 1
+        window = [fed[p] for p in range(max(0, pos + 1 - ctx), pos + 1) if p < cap]
+        assert (len(window) == 0) == (i == steps) and (len(window) == ctx) == (i in (1, 2))
+        want = hip_ops.logits_penalty(raw.clone(), dev_ids(window), pen) if window else raw
+        assert np.array_equal(got[i], to_bits(want)), f"step {i}: window {window}"
+        if window:
+            assert not np.array_equal(got[i], to_bits(raw)), f"step {i}: the penalty changed nothing"
