@@ -357,6 +357,21 @@ size_t pie_top_logprobs_workspace_bytes(int rows, int V, int n);
 int pie_top_logprobs(const float *logprobs, int rows, int V, int n, const int32_t *tokens, const int32_t *count, int32_t *out_ids, float *out_vals,
                      void *workspace, void *stream);
 
+/* ---------------------------------------------------------------- log-probabilities of prompt tokens
+ * `echo` / prompt_logprobs: pie_top_logprobs' record of every row, straight from a block of T logits [rows, V] -- no fp32 row is written.
+ * lp[i] = f32(logits[r][i]) - lse_r in fp32, lse_r the row's log-sum-exp exactly as pie_logprobs_argmax computes it; slot 0 is
+ * (targets[r], lp[targets[r]]) -- (-1, -inf) for NULL targets or an id outside [0, V), never indexed -- and slots 1..n follow pie_top_logprobs'
+ * rank, output and count rules, ranked on lp (two logits may round to one lp: the tie goes to the lower id).  The record equals, bit for bit,
+ * pie_top_logprobs over the logprobs pie_logprobs_argmax writes for the same row.  targets, count (both nullable) DEVICE int32 [rows].
+ * Four launches (the tail's partials, one lse per row, slices of 512 ids, one workgroup per row), deterministic; a row with count <= 0
+ * leaves the slices launch at once.  workspace: pie_prompt_logprobs_workspace_bytes(rows, V, n) bytes of device memory, 8-byte aligned; needs
+ * no initialisation and carries nothing from call to call (0 is returned for sizes the op refuses).  Checked in this order, each before any
+ * launch: n outside 1..20: PIE_E_ARG; rows outside 1..65535 or V outside 1..524288: PIE_E_SHAPE; targets, count or an output not 4-byte
+ * aligned, logits not 2-byte, the workspace not 8-byte aligned: PIE_E_ALIGN; a dtype that is neither PIE_BF16 nor PIE_F16: PIE_E_ARG. */
+size_t pie_prompt_logprobs_workspace_bytes(int rows, int V, int n);
+int pie_prompt_logprobs(const void *logits, int rows, int V, int dtype, int n, const int32_t *targets, const int32_t *count, int32_t *out_ids,
+                        float *out_vals, void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- fused decode step
  * One forward of Model.__call__ (models/llama/language.py:199-210) for inputs[1,1] over per-layer
  * ReusableKVCache buffers (cache/kv_cache/reusable.py:96-142) followed by the tail of _inference
@@ -580,6 +595,23 @@ int pie_decoder_batch_graph_launches(const pie_decoder *d);
  * Both: the op's argument rules; tensor-parallel decoders refuse (PIE_E_STATE). */
 int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float *out_vals, void *workspace, size_t workspace_bytes);
 int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int32_t *out_ids, float *out_vals, const int32_t *count, void *workspace);
+/* Log-probabilities of prompt tokens inside the prompt passes: while set, record i = pie_prompt_logprobs' record of row i of
+ * the call, for pie_decoder_prefill / _prefill_embeds (the batched path per chunk, the iterated path per step: every step then computes its
+ * logits, as with logits_all, and the regime a prompt runs in does not depend on the setting) and for the prompt rows n_decode..N-1 of
+ * pie_decoder_prefill_batch / _step_mixed (decode rows are not scored and their records stay untouched; pie_decoder_step_batch ignores the
+ * setting).  The rows are scored in blocks of at most block_rows (8..1024): the lm_head on the block's final-normed rows, as the logits_all
+ * branch multiplies it, into a T [block_rows, vocab] block at the head of the workspace, then the op's four launches.  The log-probabilities
+ * are of the RAW model distribution, as logits_all is raw: configured masks, biases, penalties and samplers do not apply to prompt rows (on
+ * the iterated path a row before the last ends in the raw greedy tail).  The library never guesses targets: the host writes targets[i] = the
+ * id that follows row i in its prompt, across chunk boundaries too, and count[i] = -1 for a prompt's last row.
+ *   targets, count DEVICE int32 [rows_cap], whose CONTENTS may change between calls; out_ids int32 [rows_cap, n + 1], out_vals fp32
+ *   [rows_cap, n + 1]; workspace of at least pie_decoder_prompt_logprobs_workspace_bytes(d, n, block_rows) bytes (0 for refused sizes),
+ *   16-byte aligned -- all caller-owned DEVICE memory, alive while set.  n == 0 switches it off; a decoder that does not set it launches
+ *   exactly what it launches without.  The op's argument rules; block_rows outside 8..1024: PIE_E_ARG; tensor-parallel decoders refuse
+ *   (PIE_E_STATE); a pass with more rows than rows_cap is PIE_E_SHAPE before any launch. */
+size_t pie_decoder_prompt_logprobs_workspace_bytes(const pie_decoder *d, int n, int block_rows);
+int pie_decoder_set_prompt_logprobs(pie_decoder *d, int n, int rows_cap, int block_rows, const int32_t *targets, const int32_t *count,
+                                    int32_t *out_ids, float *out_vals, void *workspace, size_t workspace_bytes);
 /* Per-row token masks and logit biases inside the multi-sequence passes: pie_decoder_step_batch (eager or PIE_STEP_GRAPH),
  * pie_decoder_prefill_batch and pie_decoder_step_mixed, output row s in pie_decoder_set_batch_tail's row order.  The processed logits of a row
  * are the single-sequence tail's (above) with the row's own parameters: (1) mask, (2) the row's repetition penalty from its pie_row_tail

@@ -48,6 +48,7 @@ EXPORTS = [
     "pie_logits_penalty", "pie_decoder_set_logits_penalty", "pie_decoder_set_sampler",
     "pie_logprobs_argmax_masked", "pie_logits_bias", "pie_decoder_set_logits_mask", "pie_decoder_set_logit_bias",
     "pie_row_tail_bytes", "pie_row_tail_pack", "pie_sample_rows", "pie_logits_penalty_rows", "pie_decoder_set_batch_tail", "pie_decoder_batch_graph_replays", "pie_decoder_batch_graph_launches",
+    "pie_prompt_logprobs_workspace_bytes", "pie_prompt_logprobs", "pie_decoder_prompt_logprobs_workspace_bytes", "pie_decoder_set_prompt_logprobs",
     "pie_top_logprobs_workspace_bytes", "pie_top_logprobs", "pie_decoder_set_top_logprobs", "pie_decoder_set_batch_top_logprobs",
     "pie_logprobs_argmax_rows_masked", "pie_logits_bias_rows", "pie_decoder_set_batch_logits_edits",
     "pie_count_penalty_bytes", "pie_count_penalty_pack", "pie_logits_count_penalty_rows", "pie_decoder_set_count_penalty", "pie_decoder_set_batch_count_penalty",
@@ -157,6 +158,12 @@ def load() -> C.CDLL:
     lib.pie_top_logprobs_workspace_bytes.restype = C.c_size_t
     lib.pie_top_logprobs_workspace_bytes.argtypes = [C.c_int] * 3
     lib.pie_top_logprobs.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 6
+    lib.pie_prompt_logprobs_workspace_bytes.restype = C.c_size_t
+    lib.pie_prompt_logprobs_workspace_bytes.argtypes = [C.c_int] * 3
+    lib.pie_prompt_logprobs.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6
+    lib.pie_decoder_prompt_logprobs_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_prompt_logprobs_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.pie_decoder_set_prompt_logprobs.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_size_t]
     lib.pie_decoder_set_top_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.pie_decoder_set_batch_top_logprobs.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     lib.pie_logprobs_argmax_rows_masked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4

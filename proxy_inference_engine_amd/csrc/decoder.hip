@@ -698,6 +698,17 @@ struct RawTail {  // pie_decoder::tail_raw for the duration of one prompt pass
     RawTail(pie_decoder *dec, bool raw) : d(dec) { d->tail_raw = raw; }
     ~RawTail() { d->tail_raw = false; }
 };
+
+// Row l of a prompt that runs as decode steps.  Scored (pie_decoder_set_prompt_logprobs): every row computes its logits, as with logits on
+// every position, and the op runs on that one row; a row before the last ends in the raw tail, so a configured sampler draws nothing for it.
+int enqueue_scored_step(pie_decoder *d, const int *token_ptr, int l, bool last, bool every_logits, u16 *dst, hipStream_t st) {
+    if (!d->pl_n) return enqueue_step(d, token_ptr, last || every_logits, dst, st);
+    const bool raw = d->tail_raw;
+    d->tail_raw = raw || !last;
+    int rc = enqueue_step(d, token_ptr, true, dst, st);
+    d->tail_raw = raw;
+    return rc ? rc : d->score_rows(dst, l, 1, st);
+}
 }  // namespace
 extern "C" {
 
@@ -706,6 +717,7 @@ int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_
     if (rc) return rc;
     PIE_REQUIRE(ids && L > 0, PIE_E_ARG, "pie_decoder_prefill: need at least one token");
     hipStream_t st = (hipStream_t)stream;
+    PIE_REQUIRE(!d->pl_n || L <= d->pl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill: more rows than the prompt log-probabilities' rows_cap");
     const RawTail raw(d, logits_all != nullptr);  // logits on every position: raw, whatever tail is configured
     // a tensor-parallel shard feeds its prompt through the step kernels (2 all-reduces per layer and token); the many-row GEMM
     // path has no collective yet
@@ -717,7 +729,7 @@ int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_
     for (int l = 0; l < L; ++l) {
         const bool last = l == L - 1;
         u16 *dst = logits_all ? (u16 *)logits_all + (size_t)l * d->cfg.vocab : d->logits;
-        if ((rc = enqueue_step(d, ids + l, last || logits_all != nullptr, dst, st))) return rc;
+        if ((rc = enqueue_scored_step(d, ids + l, l, last, logits_all != nullptr, dst, st))) return rc;
     }
     if (logits_all)  // keep pie_decoder_outputs()'s logits pointer meaningful: last row
         PIE_HIP_TRY(hipMemcpyAsync(d->logits, (u16 *)logits_all + (size_t)(L - 1) * d->cfg.vocab, 2 * (size_t)d->cfg.vocab,
@@ -732,6 +744,7 @@ int pie_decoder_prefill_embeds(pie_decoder *d, const void *embeds, int L, void *
     PIE_REQUIRE(pie_aligned(embeds, 16), PIE_E_ALIGN, "pie_decoder_prefill_embeds: 16-byte alignment required");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_prefill_embeds: not available on a tensor-parallel shard");
     hipStream_t st = (hipStream_t)stream;
+    PIE_REQUIRE(!d->pl_n || L <= d->pl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_embeds: more rows than the prompt log-probabilities' rows_cap");
     const RawTail raw(d, logits_all != nullptr);
     // (one row on a rotating cache is a single-row update: the decode step below, as in rotating.py)
     if (!(d->kv_i8 && d->block_table) && !(d->ring && L == 1)) return prefill_batched(d, nullptr, embeds, L, logits_all, st);
@@ -743,7 +756,7 @@ int pie_decoder_prefill_embeds(pie_decoder *d, const void *embeds, int L, void *
     for (int l = 0; l < L && !rc; ++l) {
         u16 *dst = logits_all ? (u16 *)logits_all + (size_t)l * d->cfg.vocab : d->logits;
         if (hipMemcpyAsync(d->h, (const char *)embeds + (size_t)l * row_bytes, row_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = pie::fail(PIE_E_HIP, "pie_decoder_prefill_embeds: copying a row failed");
-        else rc = enqueue_step(d, &d->state->token, l == L - 1 || logits_all != nullptr, dst, st);
+        else rc = enqueue_scored_step(d, &d->state->token, l, l == L - 1, logits_all != nullptr, dst, st);
     }
     d->row_is_h = false;
     if (rc) return rc;
@@ -795,6 +808,9 @@ int pie_decoder_configure(pie_decoder *d, int option, int value) {
     drop_graphs(d);
     return PIE_OK;
 }
+
+// the T [block_rows, vocab] logits block at the head of the prompt log-probabilities' workspace, padded so that the op's part stays 16-byte aligned
+static size_t prompt_block_bytes(const pie_decoder *d, int block_rows) { return ((size_t)block_rows * d->cfg.vocab * 2 + 15) & ~(size_t)15; }
 
 static int tail_stats_alloc(pie_decoder *d) {
     return d->tail_stats ? PIE_OK : dev_alloc((void **)&d->tail_stats, sizeof(LogitStat) * TAIL_STAT_TILES);
@@ -886,6 +902,33 @@ int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int3
     // (a pass is handed its logprobs per call: their alignment is checked there, with rows <= rows_cap)
     if (int rc = top_logprobs_check("pie_decoder_set_batch_top_logprobs", rows_cap, d->cfg.vocab, n, false, nullptr, nullptr, count, out_ids, out_vals, workspace)) return rc;
     d->btl_n = n, d->btl_rows_cap = rows_cap, d->btl_ids = out_ids, d->btl_vals = out_vals, d->btl_count = count, d->btl_ws = workspace;  // (the batch graph's key holds them: no graph to drop)
+    return PIE_OK;
+}
+
+size_t pie_decoder_prompt_logprobs_workspace_bytes(const pie_decoder *d, int n, int block_rows) {
+    if (!d || block_rows < 8 || block_rows > 1024) return 0;
+    const size_t op = pie_prompt_logprobs_workspace_bytes(block_rows, d->cfg.vocab, n);
+    return op ? prompt_block_bytes(d, block_rows) + op : 0;
+}
+
+int pie_decoder_set_prompt_logprobs(pie_decoder *d, int n, int rows_cap, int block_rows, const int32_t *targets, const int32_t *count, int32_t *out_ids,
+                                    float *out_vals, void *workspace, size_t workspace_bytes) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_prompt_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (n == 0) {
+        d->pl_n = 0, d->pl_rows_cap = 0, d->pl_block = 0, d->pl_targets = nullptr, d->pl_count = nullptr, d->pl_ids = nullptr, d->pl_vals = nullptr;
+        d->pl_ws = nullptr, d->pl_op_ws = nullptr;
+        return PIE_OK;
+    }
+    PIE_REQUIRE(n >= 1 && n <= PIE_TOP_LOGPROBS_MAX, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: n must be 1..20 (0: off)");
+    PIE_REQUIRE(block_rows >= 8 && block_rows <= 1024, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: block_rows must be 8..1024");
+    PIE_REQUIRE(targets && count, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: null pointer");
+    if (int rc = prompt_logprobs_check("pie_decoder_set_prompt_logprobs", rows_cap, d->cfg.vocab, d->cfg.dtype, n, false, nullptr, targets, count, out_ids, out_vals, workspace)) return rc;
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_decoder_set_prompt_logprobs: the workspace needs 16-byte alignment (it starts with the logits block)");
+    PIE_REQUIRE(workspace_bytes >= pie_decoder_prompt_logprobs_workspace_bytes(d, n, block_rows), PIE_E_SHAPE,
+                "pie_decoder_set_prompt_logprobs: the workspace is smaller than pie_decoder_prompt_logprobs_workspace_bytes(n, block_rows)");
+    d->pl_n = n, d->pl_rows_cap = rows_cap, d->pl_block = block_rows, d->pl_targets = targets, d->pl_count = count, d->pl_ids = out_ids, d->pl_vals = out_vals;
+    d->pl_ws = (u16 *)workspace, d->pl_op_ws = (char *)workspace + prompt_block_bytes(d, block_rows);  // (no step graph holds them: only the prompt passes launch them)
     return PIE_OK;
 }
 

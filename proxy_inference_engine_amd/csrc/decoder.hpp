@@ -9,6 +9,7 @@
 #include "sampler.hpp"
 #include "tail.hpp"
 #include "top_logprobs.hpp"
+#include "prompt_logprobs.hpp"
 #include "w4_gemv.hpp"
 
 // The step's attention: its own launch | behind the q|k|v launch's seam, merged by o_proj's prologue | behind the seam and merged there
@@ -126,6 +127,20 @@ struct pie_decoder {
     pie_count_penalty *bc_records = nullptr;  // [bc_rows_cap], nullptr: off
     int *bc_counts = nullptr;                 // [bc_rows_cap, vocab]
     int bc_rows_cap = 0;
+    // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): the prompt passes score their rows in blocks of at
+    // most pl_block rows -- lm_head into the logits block at the head of pl_ws, then pie_prompt_logprobs' launches on the op's workspace behind
+    // it (pl_op_ws).  Caller-owned; record i belongs to row i of the call.  pl_n == 0: off, and nothing else is launched.
+    int pl_n = 0, pl_rows_cap = 0, pl_block = 0;
+    const int *pl_targets = nullptr, *pl_count = nullptr;
+    int *pl_ids = nullptr;
+    float *pl_vals = nullptr;
+    u16 *pl_ws = nullptr;
+    void *pl_op_ws = nullptr;
+    // the op on `rows` rows of logits, whose first row is row `row0` of the call
+    int score_rows(const u16 *logits, int row0, int rows, hipStream_t st) const {
+        return prompt_logprobs_launch(logits, rows, cfg.vocab, cfg.dtype, pl_n, pl_targets + row0, pl_count + row0, pl_ids + (size_t)row0 * (pl_n + 1),
+                                      pl_vals + (size_t)row0 * (pl_n + 1), pl_op_ws, st);
+    }
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
     bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n || cp_record; }

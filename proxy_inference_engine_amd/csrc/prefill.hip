@@ -682,12 +682,34 @@ static int kvq_scratch_reserve(pie_decoder *d) {
     return PIE_OK;
 }
 
+// The lm_head on every position: through the scratch (no 16-bit resident copy)
+static RowsOpts every_row_head_opts() {
+    RowsOpts o;
+    o.keep = false;
+    return o;
+}
+
+// Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): rows [0, M) of xn -- final-normed already -- are
+// rows row0 .. row0 + M - 1 of the call.  Per block of at most pl_block rows: the lm_head as the logits-on-every-position branch multiplies
+// it, into the caller's logits block, then the op's launches on that block.  Off: nothing is launched.
+template <class T>
+static int score_prompt_rows(pie_decoder *d, const u16 *xn, int row0, int M, hipStream_t st) {
+    if (!d->pl_n) return PIE_OK;
+    const pie_decoder_config &c = d->cfg;
+    for (int b0 = 0; b0 < M; b0 += d->pl_block) {
+        const int rows = M - b0 < d->pl_block ? M - b0 : d->pl_block;
+        int rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, c.hidden, xn + (size_t)b0 * c.hidden, rows, d->pl_ws, st, every_row_head_opts());
+        if (rc || (rc = d->score_rows(d->pl_ws, row0 + b0, rows, st))) return rc;
+    }
+    return PIE_OK;
+}
+
 template <class T>
 static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int L, void *logits_all, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
     const int chunk = prefill_chunk_rows() < L ? prefill_chunk_rows() : L;
-    int rc = scratch_reserve(d, chunk, w16_copy_elems(c, logits_all != nullptr), d->splits);
+    int rc = scratch_reserve(d, chunk, w16_copy_elems(c, logits_all != nullptr || d->pl_n), d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     // quantized KV: the pass runs on the T scratch (kv_table below), the layer's codes are expanded into it and the chunk's rows quantized back
@@ -757,15 +779,14 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
                 a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
                 if ((rc = attn_decode_launch(c.dtype, D, a, true, st))) return rc;
             }
-            // the last layer ends in the plain add: the final norm runs below, and only for logits on every position
+            // the last layer ends in the plain add: the final norm runs below, and only for logits on every position or for scored rows
             if ((rc = mlp_rows<T>(d, w, M, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : nullptr, st))) return rc;
         }
+        if ((logits_all || d->pl_n) && (rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
         if (logits_all) {  // lm_head on every position, like the reference (language.py:205-209)
-            if ((rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
-            RowsOpts head_opts;
-            head_opts.keep = false;  // the lm_head on every position: through the scratch
-            if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, head_opts))) return rc;
+            if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, every_row_head_opts()))) return rc;
         }
+        if ((rc = score_prompt_rows<T>(d, s->xn, c0, M, st))) return rc;
         const bool last = c0 + M >= L;
         if (last)  // the last position continues through the decode step's lm_head + tail below
             PIE_HIP_TRY(hipMemcpyAsync(d->h, s->x + (size_t)(M - 1) * H, 2 * (size_t)H, hipMemcpyDeviceToDevice, st));
@@ -1035,7 +1056,9 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
     RowsOpts head_opts;
     head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
     if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->r, S, logits, st, head_opts))) return rc;
-    return batch_tail_launch(d, ids, row_ctx, last_rows, N, S, logits, logprobs, next_tokens, st);
+    if ((rc = batch_tail_launch(d, ids, row_ctx, last_rows, N, S, logits, logprobs, next_tokens, st))) return rc;
+    // the prompt rows' own records (pie_decoder_set_prompt_logprobs): s->xn still holds every row final-normed; the decode rows are not scored
+    return score_prompt_rows<T>(d, s->xn + (size_t)n_decode * H, n_decode, N - n_decode, st);
 }
 
 static size_t active_page_bytes(const pie_decoder *d);
@@ -1059,6 +1082,7 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     PIE_REQUIRE(!d->be_rows_cap || S <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch logits edits' rows_cap");
     PIE_REQUIRE(!d->btl_n || S <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the top log-probabilities' rows_cap");
     PIE_REQUIRE(!d->bc_records || S <= d->bc_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch count penalty's rows_cap");
+    PIE_REQUIRE(!d->pl_n || N <= d->pl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more rows than the prompt log-probabilities' rows_cap");
     PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
     PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,

@@ -84,13 +84,12 @@ __global__ void __launch_bounds__(256) k_logits_stats_rows_masked(u16 *logits, i
 
 constexpr int TAIL_MAX_STATS = 4096;  // 256 threads x 16 register-resident partials
 
-template <class T>
-__global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V, const LogitStat *stats, int n_stats, float *logprobs,
-                                                       int *token, DecState *state, int *history, int hist_cap, const unsigned *err_word) {
+// The merge of one row's partials by a workgroup of 256 threads: the row's log-sum-exp (returned by every thread) and its first argmax.
+// 16 independent 16-byte loads per thread, then two register passes.  k_logits_finish and the prompt scoring (prompt_logprobs.hip) both
+// call it, so a row's lse has the same bits wherever it is computed.  Two barriers; called by every thread of the workgroup.
+__device__ __forceinline__ float logits_merge_partials(const LogitStat *stats, int n_stats, int &tok) {
     __shared__ float s_max[4], s_sum[4];
     __shared__ int s_arg[4];
-    logits += (size_t)blockIdx.y * V, stats += (size_t)blockIdx.y * n_stats, logprobs += (size_t)blockIdx.y * V, token += blockIdx.y;  // batch row
-    // every workgroup merges all partials: 16 independent 16-byte loads per thread, then two register passes
     LogitStat st[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -113,7 +112,7 @@ __global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V,
     if ((threadIdx.x & 63) == 0) s_max[wave] = wmax, s_arg[wave] = cand;
     __syncthreads();
     float M = s_max[0];
-    int tok = s_arg[0];
+    tok = s_arg[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w)
         if (s_max[w] > M || (s_max[w] == M && s_arg[w] < tok)) M = s_max[w], tok = s_arg[w];
@@ -123,7 +122,15 @@ __global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V,
     se = wave_sum(se);
     if ((threadIdx.x & 63) == 0) s_sum[wave] = se;
     __syncthreads();
-    const float lse = M + logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+    return M + logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V, const LogitStat *stats, int n_stats, float *logprobs,
+                                                       int *token, DecState *state, int *history, int hist_cap, const unsigned *err_word) {
+    logits += (size_t)blockIdx.y * V, stats += (size_t)blockIdx.y * n_stats, logprobs += (size_t)blockIdx.y * V, token += blockIdx.y;  // batch row
+    int tok;
+    const float lse = logits_merge_partials(stats, n_stats, tok);  // every workgroup merges all partials
     const int slice = (((V + gridDim.x - 1) / gridDim.x) + 7) & ~7;  // 8 logits per thread and pass
     const int begin = blockIdx.x * slice, end = min(V, begin + slice);
     for (int i = begin + threadIdx.x * 8; i < end; i += 256 * 8) {

@@ -10,7 +10,8 @@ prompt pass of their own when nothing is decoding -- every step decodes all acti
 its own `SamplingParams`, run per row inside the passes -- its token mask and logit_bias included, and its
 frequency and presence penalties over the counts of what it has generated (DESIGN.md 15);
 `sampler` maps a [B, V] log-probability block to B token ids;
-`generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes."""
+`generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes (DESIGN.md 13);
+`generate(prompt_logprobs=...)` also returns the log-probabilities of the prompts' own tokens, scored inside the prompt passes."""
 from __future__ import annotations
 
 from collections import deque
@@ -120,6 +121,68 @@ class _Active:
     rec: torch.Tensor | None = None   # int32 [2 (n + 1)] on the device: the top-n record of `token` (ids, then the values' bits); None: not asked for
 
 
+def pass_targets(prompts: list, wants: list, parts: list) -> tuple[list[int], list[int]]:
+    """What the host writes for the prompt rows of one pass (Model.set_prompt_logprobs), in row order.  parts: (request, start, rows) --
+    the pass holds rows prompts[request][start : start + rows].  The row of token j has target = token j + 1 of its prompt -- in this
+    chunk or in a later pass's -- and count = the request's wants; a prompt's last row, which nothing follows, and every row of a request
+    that is not scored (wants None) have count -1: their records are left alone."""
+    targets, counts = [], []
+    for req, start, rows in parts:
+        p, w = prompts[req], wants[req]
+        for j in range(start, start + rows):
+            scored = w is not None and j + 1 < len(p)
+            targets.append(int(p[j + 1]) if scored else 0)
+            counts.append(int(w) if scored else -1)
+    return targets, counts
+
+
+class _PromptScores:
+    """The prompts' own log-probabilities of one generate() call: arms the rows of every pass that carries prompt rows, keeps the pass's
+    records on the device until the loop's next read-back of the tokens, and builds the maps from them there."""
+
+    def __init__(self, model, prompts: list, wants: list, rows_cap: int):
+        self.model, self.prompts, self.wants = model, prompts, wants
+        self.bufs = model.set_prompt_logprobs(rows_cap, max(max(w for w in wants if w is not None), 1))
+        self.maps: list = [None if w is None else [None] * len(p) for p, w in zip(prompts, wants)]
+        self.pending: list = []      # (request, first row's token index, rows, int32 [rows, 2 (n + 1)] on the device: ids, then the values' bits)
+        self.span = None
+
+    def arm(self, n_decode: int, parts: list) -> None:
+        """Before a pass whose rows n_decode.. are `parts` (pass_targets)."""
+        targets, counts = pass_targets(self.prompts, self.wants, parts)
+        dev = self.bufs["targets"].device
+        self.bufs["targets"][n_decode:n_decode + len(targets)].copy_(torch.tensor(targets, dtype=torch.int32, device=dev))
+        self.bufs["count"][n_decode:n_decode + len(counts)].copy_(torch.tensor(counts, dtype=torch.int32, device=dev))
+        self.span = (n_decode, parts)
+
+    def collect(self) -> None:
+        """After that pass: its scored rows' records as fresh device tensors (the next pass overwrites the buffers)."""
+        r, parts = self.span
+        for req, start, rows in parts:
+            if self.wants[req] is not None:
+                self.pending.append((req, start, rows, torch.cat([self.bufs["ids"][r:r + rows], self.bufs["vals"][r:r + rows].view(torch.int32)], dim=1)))
+            r += rows
+        self.span = None
+
+    def tensors(self) -> list:
+        return [t.reshape(-1) for _, _, _, t in self.pending]
+
+    def absorb(self, words) -> None:
+        """words: the pending records as read back (numpy int32, flat, in `tensors` order)."""
+        at = 0
+        for req, start, rows, t in self.pending:
+            rec = words[at:at + t.numel()].reshape(rows, 2, -1)
+            at += t.numel()
+            for k in range(rows):
+                if start + k + 1 < len(self.prompts[req]):   # row of token j scores token j + 1
+                    self.maps[req][start + k + 1] = host_record_to_map(rec[k, 0], rec[k, 1].view(np.float32), self.wants[req])[1]
+        self.pending = []
+
+    def flush(self) -> None:
+        if self.pending:
+            self.absorb(torch.cat(self.tensors()).cpu().numpy())
+
+
 class BatchedEngine:
     def __init__(self, model, num_pages: int = 1024, max_batch: int = 32, stop_tokens: Iterable[int] = (),
                  sampler: Callable[[torch.Tensor], torch.Tensor] | None = None, batch_prefill: bool = True, max_prefill_rows: int = 4096,
@@ -150,7 +213,7 @@ class BatchedEngine:
         return (n_tokens + TOKEN_CAPACITY_PER_PAGE - 1) // TOKEN_CAPACITY_PER_PAGE
 
     def generate(self, prompts: list, max_new_tokens: int, sampling: SamplingParams | list | None = None, logprobs: bool = False,
-                 top_logprobs: int | list = 0):
+                 top_logprobs: int | list = 0, prompt_logprobs: int | list | None = None):
         """Token ids generated for every prompt (in order), at most max_new_tokens each, ending early at a stop token.
         sampling: None (greedy, or the constructor's `sampler`), one SamplingParams for every request, or one per prompt: each request's
         own sampler, seed and repetition penalty, applied to its row inside every pass (Model.set_batch_tail) -- a request's tokens depend
@@ -162,7 +225,39 @@ class BatchedEngine:
         logprobs=True: returns (outputs, maps) -- maps[i][j] is the {token id: log-probability} dict of outputs[i][j], as
         InferenceEngine.generate yields it: the best top_logprobs pairs by decreasing log-probability (ties: lowest id first), then the
         token itself when absent.  top_logprobs: one int for every request or one per prompt, each 0..20; ignored with logprobs=False.  The
-        records are selected per row inside the passes (Model.set_batch_top_logprobs) and fetched in the per-pass read-back of the tokens."""
+        records are selected per row inside the passes (Model.set_batch_top_logprobs) and fetched in the per-pass read-back of the tokens.
+        prompt_logprobs: None (nothing changes, the return shape included), one int for every request, or one int or None per prompt, each
+        0..20: the prompt maps are appended as the last element of the returned tuple -- prompt_maps[i] is None for a request that asked
+        for none, else a list as long as prompt i: entry 0 None, entry j the {id: log-probability} map of prompt token j given the tokens
+        before it, under the raw model distribution: the best prompt_logprobs pairs, then the token itself when absent
+        (InferenceEngine.score's list).  Scored inside the prompt passes (Model.set_prompt_logprobs), across prefill_chunk
+        boundaries, and fetched in the per-pass read-back of the tokens.  ValueError with share_prefix=True (the shared pages' rows are
+        computed once, for no request in particular, and cannot be scored) and with max_new_tokens < 1 (InferenceEngine.score runs a prompt only)."""
+        if prompt_logprobs is None:
+            return self._run(prompts, max_new_tokens, sampling, logprobs, top_logprobs, None)
+        wants = list(prompt_logprobs) if isinstance(prompt_logprobs, (list, tuple)) else [prompt_logprobs] * len(prompts)
+        if len(wants) != len(prompts):
+            raise ValueError("generate: `prompt_logprobs` is None, one int, or one int or None per prompt")
+        if not all(w is None or (isinstance(w, int) and not isinstance(w, bool) and 0 <= w <= 20) for w in wants):
+            raise ValueError("generate: every `prompt_logprobs` is None or an int in 0..20")
+        if self.share_prefix:
+            raise ValueError("generate: `prompt_logprobs` and share_prefix=True exclude each other (the shared pages' rows are never computed for a request)")
+        if max_new_tokens < 1:
+            raise ValueError("generate: `prompt_logprobs` needs max_new_tokens >= 1 (InferenceEngine.score runs a prompt only)")
+        scores = None
+        try:
+            if any(w is not None for w in wants):
+                rows_cap = min(65535, self.max_batch + max([self.max_prefill_rows, self.prefill_chunk or 0] + [len(p) for p in prompts]))
+                scores = _PromptScores(self.model, prompts, wants, rows_cap)
+            res = self._run(prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores)
+        finally:
+            if scores is not None:
+                self.model.clear_prompt_logprobs()
+        maps = scores.maps if scores is not None else [None] * len(prompts)
+        return (*res, maps) if logprobs else (res, maps)
+
+    def _run(self, prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores):
+        """generate's body; scores: the call's _PromptScores or None."""
         tops = edits = cnts = None
         if logprobs:
             if self.sampler is not None:
@@ -192,7 +287,7 @@ class BatchedEngine:
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
         if sampling is None and tops is None and edits is None and cnts is None:
-            return self._generate(prompts, max_new_tokens, None)
+            return self._generate(prompts, max_new_tokens, None, scores=scores)
         try:
             if sampling is not None:
                 self.model.set_batch_tail(self.max_batch)
@@ -207,11 +302,11 @@ class BatchedEngine:
                 self.model.write_batch_count_penalty(list(range(self.max_batch)), [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
             tails = None if sampling is None else (params, seeds)
             if tops is None:
-                return self._generate(prompts, max_new_tokens, tails, edits=edits, cnts=cnts)
+                return self._generate(prompts, max_new_tokens, tails, edits=edits, cnts=cnts, scores=scores)
             bufs = self.model.set_batch_top_logprobs(self.max_batch, max(max(tops, default=1), 1))
             bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
             maps: list = [[] for _ in prompts]
-            out = self._generate(prompts, max_new_tokens, tails, (tops, bufs, maps), edits=edits, cnts=cnts)
+            out = self._generate(prompts, max_new_tokens, tails, (tops, bufs, maps), edits=edits, cnts=cnts, scores=scores)
             return out, maps
         finally:
             if sampling is not None:
@@ -223,7 +318,7 @@ class BatchedEngine:
             if tops is not None:
                 self.model.clear_batch_top_logprobs()
 
-    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None, edits=None, cnts=None) -> list[list[int]]:
+    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None, edits=None, cnts=None, scores=None) -> list[list[int]]:
         for p in prompts:
             if self._pages_for(len(p) + max_new_tokens) > self.pool.size():
                 raise ValueError("a prompt does not fit the page pool")
@@ -358,6 +453,12 @@ class BatchedEngine:
             penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`)."""
             return tops is None and (tails is None or tails[0][idx].tailless) and (edits is None or edits[idx] == (None, None))
 
+        def scored(n_decode: int | None = None, parts: list | None = None) -> None:
+            """Around a pass that carries prompt rows: with arguments before it (the rows n_decode.. hold `parts`, as pass_targets takes
+            them), without after it.  Nothing without `scores`."""
+            if scores is not None:
+                scores.arm(n_decode, parts) if parts is not None else scores.collect()
+
         def records(n_rows: int):
             """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'
             bits): row views of it outlive the next pass.  None when log-probabilities are not asked for."""
@@ -368,9 +469,12 @@ class BatchedEngine:
             # every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
             if active:
                 # one read-back per pass for the stop / length checks -- and, in the same copy, the tokens' top-n records
-                host = torch.cat([a.token for a in active] + ([a.rec for a in active] if tops is not None else [])).cpu().numpy()
+                n_top = sum(a.rec.numel() for a in active) if tops is not None else 0
+                host = torch.cat([a.token for a in active] + ([a.rec for a in active] if tops is not None else []) + (scores.tensors() if scores else [])).cpu().numpy()
+                if scores:
+                    scores.absorb(host[len(active) + n_top:])
                 if tops is not None:
-                    recs = host[len(active):].reshape(len(active), 2, -1)
+                    recs = host[len(active):len(active) + n_top].reshape(len(active), 2, -1)
                     for a, r in zip(active, recs):
                         tops[2][a.request].append(host_record_to_map(r[0], r[1].view(np.float32), tops[0][a.request])[1])
                 keep = []
@@ -412,8 +516,10 @@ class BatchedEngine:
                         take.append((f, n))
                         budget -= n
                 seat([a.request for a in active] + [f[0] if f[3] + n == len(f[1]) else None for f, n in take])
+                scored(len(active), [(f[0], f[3], n) for f, n in take])
                 nxt, logprobs, _ = self.model.step_mixed(torch.cat([a.token for a in active]) if active else None, [a.cache for a in active],
                                                          [f[1][f[3]:f[3] + n] for f, n in take], [f[2] for f, _ in take])
+                scored()
                 self.steps += 1
                 self.mixed_passes += bool(active)
                 nb = len(active)
@@ -442,8 +548,10 @@ class BatchedEngine:
             if active and batch and self.mixed and (n_mix <= 512 or (n_mix + 255) // 256 == (rows + 255) // 256):
                 # the admitted prompts ride the decode step of the sequences in flight: one pass over the weights for both
                 seat([a.request for a in active] + [idx for idx, _, _ in batch])
+                scored(len(active), [(idx, 0, len(p)) for idx, p, _ in batch])
                 nxt, logprobs, _ = self.model.step_mixed(torch.cat([a.token for a in active]), [a.cache for a in active],
                                                          [p for _, p, _ in batch], [c for _, _, c in batch])
+                scored()
                 self.steps += 1
                 self.mixed_passes += 1
                 if self.sampler is not None:
@@ -459,7 +567,9 @@ class BatchedEngine:
             if self._i8 and batch and (len(batch) == 1 or not self.batch_prefill):
                 for idx, prompt, cache in batch:
                     seat([idx])
+                    scored(0, [(idx, 0, len(prompt))])
                     toks, logprobs, _ = self.model.prefill_batch([prompt], [cache])
+                    scored()
                     if self.sampler is not None:
                         toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
                     joined.append(_Active(idx, cache, toks[:1].clone(), rec=records(1)[0]))
@@ -473,19 +583,24 @@ class BatchedEngine:
                     joined.append(_Active(idx, cache, toks[i:i + 1].clone(), rec=recs[i]))
             elif len(batch) == 1 or (batch and not self.batch_prefill):
                 for idx, prompt, cache in batch:
+                    scored(0, [(idx, 0, len(prompt))])                    # (either pass below: record i belongs to row i of the prompt)
                     if not lone_step(idx):                                # its first token is drawn by its own sampler: a batch of one
                         seat([idx])
                         toks, _, _ = self.model.prefill_batch([prompt], [cache])
+                        scored()
                         joined.append(_Active(idx, cache, toks[:1].clone(), rec=records(1)[0]))
                         continue
                     ids = torch.as_tensor(prompt, dtype=torch.int32).reshape(-1)
                     tok, logprobs, _ = self.model.step(ids.to(self.model.device), cache)
+                    scored()
                     if self.sampler is not None:
                         tok = self.sampler(logprobs[None]).reshape(1).to(torch.int32)
                     joined.append(_Active(idx, cache, tok.reshape(1).clone()))
             elif batch:
                 seat([idx for idx, _, _ in batch])
+                scored(0, [(idx, 0, len(p)) for idx, p, _ in batch])
                 toks, logprobs, _ = self.model.prefill_batch([p for _, p, _ in batch], [c for _, _, c in batch])
+                scored()
                 if self.sampler is not None:
                     toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
                 recs = records(len(batch))
@@ -503,4 +618,6 @@ class BatchedEngine:
             active += joined
         if root is not None:
             root[0].page_manager.release()
+        if scores is not None:
+            scores.flush()   # (the loop's last read-back leaves nothing pending: every pass with prompt rows is followed by one)
         return out

@@ -166,7 +166,7 @@ class InferenceEngine:
     # ------------------------------------------------------------------ the hot loop
     def generate_step(self, prompt_ids, pixel_values=None, mask=None, kv_bits: int | None = None, kv_group_size: int = 64,
                       quantized_kv_start: int = 0, max_kv_size: int | None = None,
-                      top_logprobs: int | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
+                      top_logprobs: int | None = None, prompt_logprobs: int | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
         """Yields (next_token_id[1] int32, logprobs[V] fp32) per step, forever (inference_engine.py:228-297).
         Prefill of the non-cached prompt suffix, then one forward per token; all device work is queued
         asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202).
@@ -178,7 +178,17 @@ class InferenceEngine:
         another kind or size is replaced by fresh rings (and back to the model's own caches when max_kv_size is None).
         top_logprobs (None: off, else 0..20): every step also leaves `self.top_record` = (ids int32 [n + 1], vals fp32 [n + 1]) on the
         device -- hip_ops.top_logprobs of the yielded logprobs with the yielded token in slot 0, valid until the next step:
-        written inside the replayed step where the request takes the fused plan, by the op on the host-orchestrated branches."""
+        written inside the replayed step where the request takes the fused plan, by the op on the host-orchestrated branches.
+        prompt_logprobs (None: off, else 0..20): the prompt's own tokens are scored inside the prompt pass (Model.set_prompt_logprobs;
+        DESIGN.md 16) and `self.prompt_logprobs` holds their maps before the first yield -- entry 0 None, entry j the map of prompt token j
+        under the raw model distribution: the best prompt_logprobs pairs, then the token itself when absent.  Such a request processes its
+        whole prompt: the prompt cache's common prefix is not reused for it."""
+        scored = prompt_logprobs is not None
+        if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"prompt_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
+        if scored and getattr(self.model, "tp", None) is not None:
+            raise ValueError("prompt_logprobs: not available on a tensor-parallel model")
+        self.prompt_logprobs = None
         if top_logprobs is not None and not 0 <= int(top_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
             raise ValueError(f"top_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
         self.top_record = None
@@ -307,8 +317,8 @@ class InferenceEngine:
 
         cur = self.prompt_cache.cache
         ring = bool(cur) and isinstance(cur[0], RotatingKVCache)
-        if cur and (ring != (max_kv_size is not None) or (ring and cur[0].max_size != max_kv_size)):
-            self.prompt_cache.cache, self.prompt_cache.computed_ids = [], []  # another cache kind: nothing of it is reusable
+        if cur and (scored or ring != (max_kv_size is not None) or (ring and cur[0].max_size != max_kv_size)):
+            self.prompt_cache.cache, self.prompt_cache.computed_ids = [], []  # another cache kind: nothing of it is reusable; a scored prompt: every row is computed
         if len(self.prompt_cache.cache) == 0:
             if max_kv_size is not None:
                 self.prompt_cache.cache = BaseCache.make_kv_cache(self.model, max_kv_size=max_kv_size)
@@ -320,13 +330,36 @@ class InferenceEngine:
                     proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts may not: this request's start
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
-        next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))   # :278 (host ids: no read-back)
+        if scored and len(host_ids) > 1:
+            lm = getattr(self.model, "language_model", self.model)
+            bufs = lm.set_prompt_logprobs(len(host_ids), max(int(prompt_logprobs), 1))
+            targets, counts = prompt_targets(host_ids, int(prompt_logprobs))
+            bufs["targets"].copy_(torch.tensor(targets, dtype=torch.int32))
+            bufs["count"].copy_(torch.tensor(counts, dtype=torch.int32))
+            try:
+                next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))
+            finally:
+                lm.clear_prompt_logprobs()
+            self.prompt_logprobs = prompt_maps(bufs["ids"].cpu().numpy(), bufs["vals"].cpu().numpy(), int(prompt_logprobs))
+        else:
+            if scored:
+                self.prompt_logprobs = [None]
+            next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))   # :278 (host ids: no read-back)
         step_count = 0
         while True:
             if step_count > 0:
                 next_token, logprobs = _inference(next_token, fed_back=True)   # :288
             yield next_token, logprobs
             step_count += 1
+
+    def score(self, prompt_ids, top_logprobs: int = 0, **kv) -> list:
+        """The log-probabilities of a prompt's own tokens (`echo`, perplexity, ranking): runs the prompt only and returns a list as long as
+        the prompt -- entry 0 None, entry j the {id: logprob} map of prompt token j given the tokens before it: the best top_logprobs
+        pairs, then the token itself when absent.  kv: generate_step's KV arguments (kv_bits, kv_group_size, quantized_kv_start, max_kv_size)."""
+        step = self.generate_step(prompt_ids, prompt_logprobs=int(top_logprobs), **kv)
+        next(step)
+        step.close()
+        return self.prompt_logprobs
 
     def _maybe_quantize(self, quantized_start: int, group_size: int, bits: int) -> None:
         """BaseCache.maybe_quantize (cache/kv_cache/__init__.py:240-266) on the prompt cache's layers."""
@@ -351,6 +384,8 @@ class InferenceEngine:
         kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start", "max_kv_size") if inference_kwargs.get(k) is not None}
         if collect_logprobs:
             kv["top_logprobs"] = top_logprobs
+        if inference_kwargs.get("prompt_logprobs") is not None:  # the prompt's maps are on `self.prompt_logprobs` before the first yield
+            kv["prompt_logprobs"] = int(inference_kwargs["prompt_logprobs"])
         for new_tokens, new_logprobs in self.generate_step(prompt_ids, **kv):
             token_count += new_tokens.numel()
             if collect_logprobs:
@@ -393,6 +428,19 @@ def host_record_to_map(ids, vals, top_k: int) -> tuple[list[int], dict[int, floa
     if token not in out:
         out[token] = float(vals[0])
     return [token], out
+
+
+def prompt_targets(prompt_ids, top_k: int) -> tuple[list[int], list[int]]:
+    """What the host writes for the rows of one prompt (Model.set_prompt_logprobs): targets[i] = the id that follows row i, counts[i] =
+    top_k -- and for the last row, which nothing follows, (0, -1): its record is left alone."""
+    ids = [int(t) for t in prompt_ids]
+    return ids[1:] + [0], [int(top_k)] * (len(ids) - 1) + [-1]
+
+
+def prompt_maps(ids, vals, top_k: int) -> list:
+    """The records of a prompt's rows on the host (numpy int32 / float32 [L, n + 1]) -> [None, map of token 1, ..., map of token L - 1]:
+    row j - 1 scores token j."""
+    return [None] + [host_record_to_map(ids[r], vals[r], top_k)[1] for r in range(len(ids) - 1)]
 
 
 def get_top_logprobs(logprobs: torch.Tensor, top_k: int) -> dict[int, float]:

@@ -1005,6 +1005,47 @@ def top_logprobs(logprobs: torch.Tensor, n: int, tokens: torch.Tensor | None = N
     return ids, vals
 
 
+# ---------------------------------------------------------------- log-probabilities of prompt tokens (csrc/prompt_logprobs.hip)
+def prompt_logprobs_workspace(device, rows: int, V: int, n: int) -> torch.Tensor:
+    """pie_prompt_logprobs' workspace for a [rows, V] block and `n` pairs on `device`: uninitialised, nothing is carried from call to call."""
+    nbytes = int(_ffi.load().pie_prompt_logprobs_workspace_bytes(int(rows), int(V), int(n)))
+    if nbytes == 0:
+        raise ValueError(f"prompt_logprobs: 1 <= rows <= 65535, 1 <= V <= 524288 and 1 <= n <= {TOP_LOGPROBS_MAX}, got rows = {rows}, V = {V}, n = {n}")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def prompt_logprobs(logits: torch.Tensor, n: int, targets: torch.Tensor | None = None, count: torch.Tensor | None = None,
+                    workspace: torch.Tensor | None = None, out: tuple | None = None):
+    """The records of `top_logprobs` straight from 16-bit logits (pie_prompt_logprobs): logits bf16 / f16 [rows, V] or [V] -> (ids int32
+    [rows, n + 1], vals fp32 [rows, n + 1]), bit for bit top_logprobs(logprobs_argmax(row)) of every row, with no fp32 row in between.
+    Slot 0 is (targets[r], its log-probability), or (-1, -inf) without targets or for an id outside [0, V); the other slots, `count`,
+    `workspace` and `out` are top_logprobs'.  n 1..20."""
+    x = logits
+    _dev(x)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.dtype not in (torch.bfloat16, torch.float16) or not x.is_contiguous():
+        raise ValueError("prompt_logprobs: contiguous bf16 / f16 [rows, V] logits")
+    rows, V = x.shape
+    for t, name in ((targets, "targets"), (count, "count")):
+        if t is not None:
+            _dev(t)
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows:
+                raise ValueError(f"prompt_logprobs: {name} is a contiguous int32 [rows] device tensor")
+    ws = prompt_logprobs_workspace(x.device, rows, V, n) if workspace is None else workspace
+    if out is None:
+        out = (torch.full((rows, int(n) + 1), -1, dtype=torch.int32, device=x.device),
+               torch.full((rows, int(n) + 1), float("-inf"), dtype=torch.float32, device=x.device))
+    ids, vals = out
+    for t, dt in ((ids, torch.int32), (vals, torch.float32)):
+        _dev(t)
+        if t.dtype != dt or tuple(t.shape) != (rows, int(n) + 1):
+            raise ValueError("prompt_logprobs: out is (int32 [rows, n + 1], fp32 [rows, n + 1])")
+    _ffi.check(_ffi.load().pie_prompt_logprobs(_ffi.p(x), rows, V, _ffi.dtype_code(x.dtype), int(n), _ffi.p(targets), _ffi.p(count), _ffi.p(ids), _ffi.p(vals),
+                                               _ffi.p(ws), _ffi.stream()))
+    return ids, vals
+
+
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)
 def kv_ring_order(keys: torch.Tensor, values: torch.Tensor, keep: int, n: int, shift: int, n_dst: int) -> None:
     """In place on RotatingKVCache buffers [1, H, cap, D]: rows keep + j <- rows keep + (j + shift) % n for j < n_dst."""

@@ -305,6 +305,8 @@ class Model:
         self._batch_tail = None
         self._top_n, self._top_rec = None, None   # the step's top-n log-probability record (set_step_tail(top_logprobs=))
         self._batch_tops: dict = {}    # rows_cap -> the passes' top-n records (set_batch_top_logprobs)
+        self._prompt_lps: dict = {}    # rows_cap -> the prompt passes' targets, counts and records (set_prompt_logprobs)
+        self._prompt_lp_ws = None      # (block_rows, its logits block + the op's workspace)
         self._batch_edit_bufs: dict = {}   # rows_cap -> the passes' per-row masks and bias tables (set_batch_edits)
         self._batch_edits = None
         # frequency / presence penalties: the step's record + counts at stable addresses, made when first used; (freq, pres,
@@ -808,6 +810,47 @@ class Model:
     def clear_batch_top_logprobs(self) -> None:
         """The multi-sequence passes launch what they launched before set_batch_top_logprobs; the buffers stay cached."""
         _ffi.check(_ffi.load().pie_decoder_set_batch_top_logprobs(self._dec, 0, 0, None, None, None, None))
+
+    # ------------------------------------------------------------------ log-probabilities of prompt tokens (DESIGN.md 16)
+    def set_prompt_logprobs(self, rows_cap: int, n: int, block_rows: int = 256) -> dict:
+        """From now on every prompt pass -- step / step_embeds / __call__ with more than one row, prefill_batch, step_mixed -- also leaves
+        the record of hip_ops.prompt_logprobs for each of its prompt rows (pie_decoder_set_prompt_logprobs): record i belongs to row i of
+        the call (step_mixed: the decode rows come first and are not scored).  Returns {"targets": int32 [rows_cap], "count": int32
+        [rows_cap], "ids": int32 [rows_cap, n + 1], "vals": fp32 [rows_cap, n + 1]}, owned by the model and kept per rows_cap (the 4 most
+        recent; one allocation sized for n = 20).  The caller writes, in stream order, targets[i] = the id that follows row i in its prompt
+        and count[i] = how many pairs row i reports (0: the target's own only, -1: none -- a prompt's last row); a new count is all -1.  The rows
+        are scored block_rows (8..1024) at a time through a T [block_rows, V] logits block; the log-probabilities are of the raw model
+        distribution, whatever tail is configured."""
+        rows_cap, n, block_rows = int(rows_cap), int(n), int(block_rows)
+        if not 1 <= rows_cap <= 65535 or not 1 <= n <= hip_ops.TOP_LOGPROBS_MAX or not 8 <= block_rows <= 1024:
+            raise ValueError(f"set_prompt_logprobs: 1 <= rows_cap <= 65535, 1 <= n <= {hip_ops.TOP_LOGPROBS_MAX} and 8 <= block_rows <= 1024")
+        if self.tp is not None:
+            raise ValueError("set_prompt_logprobs: not available on a tensor-parallel model")
+        m = hip_ops.TOP_LOGPROBS_MAX
+        own = self._prompt_lps.pop(rows_cap, None)
+        if own is None:
+            while len(self._prompt_lps) >= 4:
+                self._prompt_lps.pop(next(iter(self._prompt_lps)))
+            own = {"targets": torch.zeros(rows_cap, dtype=torch.int32, device=self.device),
+                   "count": torch.full((rows_cap,), -1, dtype=torch.int32, device=self.device),
+                   "ids": torch.full((rows_cap * (m + 1),), -1, dtype=torch.int32, device=self.device),
+                   "vals": torch.full((rows_cap * (m + 1),), float("-inf"), dtype=torch.float32, device=self.device)}
+        self._prompt_lps[rows_cap] = own  # most recently used last
+        lib = _ffi.load()
+        if self._prompt_lp_ws is None or self._prompt_lp_ws[0] != block_rows:  # the logits block + the op's workspace, sized for n = 20
+            self._prompt_lp_ws = None
+            nbytes = int(lib.pie_decoder_prompt_logprobs_workspace_bytes(self._dec, m, block_rows))
+            self._prompt_lp_ws = (block_rows, torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device))
+        ws = self._prompt_lp_ws[1]
+        pl = {"targets": own["targets"], "count": own["count"], "ids": own["ids"][:rows_cap * (n + 1)].view(rows_cap, n + 1),
+              "vals": own["vals"][:rows_cap * (n + 1)].view(rows_cap, n + 1)}
+        _ffi.check(lib.pie_decoder_set_prompt_logprobs(self._dec, n, rows_cap, block_rows, _ffi.p(pl["targets"]), _ffi.p(pl["count"]), _ffi.p(pl["ids"]),
+                                                       _ffi.p(pl["vals"]), _ffi.p(ws), ws.numel() * 8))
+        return pl
+
+    def clear_prompt_logprobs(self) -> None:
+        """The prompt passes launch what they launched before set_prompt_logprobs; the buffers stay cached."""
+        _ffi.check(_ffi.load().pie_decoder_set_prompt_logprobs(self._dec, 0, 0, 0, None, None, None, None, None, 0))
 
     # ------------------------------------------------------------------ the multi-sequence passes' per-row masks and biases (DESIGN.md 14)
     def set_batch_edits(self, rows_cap: int, masks: bool = True, bias_cap: int = 0) -> dict:
