@@ -319,6 +319,19 @@ static int enqueue_step(pie_decoder *d, const int *token_ptr, bool with_logits, 
     return enqueue_kernel(d, PIE_K_TAIL, 0, token_ptr, logits_dst, st);
 }
 
+int graph_kernel_nodes(hipGraph_t g) {
+    size_t n_nodes = 0;
+    if (hipGraphGetNodes(g, nullptr, &n_nodes) != hipSuccess || !n_nodes) return -1;
+    std::vector<hipGraphNode_t> nodes(n_nodes);
+    if (hipGraphGetNodes(g, nodes.data(), &n_nodes) != hipSuccess) return -1;
+    int k = 0;
+    for (size_t i = 0; i < n_nodes; ++i) {
+        hipGraphNodeType t;
+        if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++k;
+    }
+    return k;
+}
+
 int capture_graph(const std::function<int(hipStream_t)> &enqueue, int *enqueue_rc, hipGraph_t *graph, hipError_t *end_err) {
     *enqueue_rc = PIE_OK, *graph = nullptr, *end_err = hipSuccess;
     hipStream_t cs = nullptr;
@@ -662,21 +675,7 @@ int pie_decoder_step(pie_decoder *d, int flags, void *stream) {
         }
         if (e != hipSuccess) return pie::fail(PIE_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
         d->graph_form[gi] = d->attn_form;  // what the capture's q|k|v launches decided, not a second look at the knobs
-        {  // what the graph really holds, for the benchmark's launches_per_step (not a formula)
-            size_t n_nodes = 0;
-            d->graph_kernels[gi] = -1;
-            if (hipGraphGetNodes(g, nullptr, &n_nodes) == hipSuccess) {
-                std::vector<hipGraphNode_t> nodes(n_nodes);
-                int k = 0;
-                if (n_nodes && hipGraphGetNodes(g, nodes.data(), &n_nodes) == hipSuccess) {
-                    for (size_t i = 0; i < n_nodes; ++i) {
-                        hipGraphNodeType t;
-                        if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++k;
-                    }
-                    d->graph_kernels[gi] = k;
-                }
-            }
-        }
+        d->graph_kernels[gi] = graph_kernel_nodes(g);  // what the graph really holds, for the benchmark's launches_per_step (not a formula)
         e = hipGraphInstantiate(&d->graph[gi], g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) return pie::fail(PIE_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
@@ -702,12 +701,12 @@ struct RawTail {  // pie_decoder::tail_raw for the duration of one prompt pass
 // Row l of a prompt that runs as decode steps.  Scored (pie_decoder_set_prompt_logprobs): every row computes its logits, as with logits on
 // every position, and the op runs on that one row; a row before the last ends in the raw tail, so a configured sampler draws nothing for it.
 int enqueue_scored_step(pie_decoder *d, const int *token_ptr, int l, bool last, bool every_logits, u16 *dst, hipStream_t st) {
-    if (!d->pl_n) return enqueue_step(d, token_ptr, last || every_logits, dst, st);
+    if (!d->prompt.n) return enqueue_step(d, token_ptr, last || every_logits, dst, st);
     const bool raw = d->tail_raw;
     d->tail_raw = raw || !last;
     int rc = enqueue_step(d, token_ptr, true, dst, st);
     d->tail_raw = raw;
-    return rc ? rc : d->score_rows(dst, l, 1, st);
+    return rc ? rc : d->prompt.score_rows(d->cfg, dst, l, 1, st);
 }
 }  // namespace
 extern "C" {
@@ -717,7 +716,7 @@ int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_
     if (rc) return rc;
     PIE_REQUIRE(ids && L > 0, PIE_E_ARG, "pie_decoder_prefill: need at least one token");
     hipStream_t st = (hipStream_t)stream;
-    PIE_REQUIRE(!d->pl_n || L <= d->pl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill: more rows than the prompt log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->prompt.n || L <= d->prompt.rows_cap, PIE_E_SHAPE, "pie_decoder_prefill: more rows than the prompt log-probabilities' rows_cap");
     const RawTail raw(d, logits_all != nullptr);  // logits on every position: raw, whatever tail is configured
     // a tensor-parallel shard feeds its prompt through the step kernels (2 all-reduces per layer and token); the many-row GEMM
     // path has no collective yet
@@ -744,7 +743,7 @@ int pie_decoder_prefill_embeds(pie_decoder *d, const void *embeds, int L, void *
     PIE_REQUIRE(pie_aligned(embeds, 16), PIE_E_ALIGN, "pie_decoder_prefill_embeds: 16-byte alignment required");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_prefill_embeds: not available on a tensor-parallel shard");
     hipStream_t st = (hipStream_t)stream;
-    PIE_REQUIRE(!d->pl_n || L <= d->pl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_embeds: more rows than the prompt log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->prompt.n || L <= d->prompt.rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_embeds: more rows than the prompt log-probabilities' rows_cap");
     const RawTail raw(d, logits_all != nullptr);
     // (one row on a rotating cache is a single-row update: the decode step below, as in rotating.py)
     if (!(d->kv_i8 && d->block_table) && !(d->ring && L == 1)) return prefill_batched(d, nullptr, embeds, L, logits_all, st);
@@ -895,13 +894,10 @@ int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float 
 int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int32_t *out_ids, float *out_vals, const int32_t *count, void *workspace) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_top_logprobs: null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_top_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
-    if (n == 0) {
-        d->btl_n = 0, d->btl_rows_cap = 0, d->btl_ids = nullptr, d->btl_vals = nullptr, d->btl_count = nullptr, d->btl_ws = nullptr;
-        return PIE_OK;
-    }
+    if (n == 0) return d->rows.top = {}, PIE_OK;  // off
     // (a pass is handed its logprobs per call: their alignment is checked there, with rows <= rows_cap)
     if (int rc = top_logprobs_check("pie_decoder_set_batch_top_logprobs", rows_cap, d->cfg.vocab, n, false, nullptr, nullptr, count, out_ids, out_vals, workspace)) return rc;
-    d->btl_n = n, d->btl_rows_cap = rows_cap, d->btl_ids = out_ids, d->btl_vals = out_vals, d->btl_count = count, d->btl_ws = workspace;  // (the batch graph's key holds them: no graph to drop)
+    d->rows.top = {n, rows_cap, out_ids, out_vals, count, workspace};  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 
@@ -915,11 +911,7 @@ int pie_decoder_set_prompt_logprobs(pie_decoder *d, int n, int rows_cap, int blo
                                     float *out_vals, void *workspace, size_t workspace_bytes) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_prompt_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
-    if (n == 0) {
-        d->pl_n = 0, d->pl_rows_cap = 0, d->pl_block = 0, d->pl_targets = nullptr, d->pl_count = nullptr, d->pl_ids = nullptr, d->pl_vals = nullptr;
-        d->pl_ws = nullptr, d->pl_op_ws = nullptr;
-        return PIE_OK;
-    }
+    if (n == 0) return d->prompt = {}, PIE_OK;  // off
     PIE_REQUIRE(n >= 1 && n <= PIE_TOP_LOGPROBS_MAX, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: n must be 1..20 (0: off)");
     PIE_REQUIRE(block_rows >= 8 && block_rows <= 1024, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: block_rows must be 8..1024");
     PIE_REQUIRE(targets && count, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: null pointer");
@@ -927,22 +919,18 @@ int pie_decoder_set_prompt_logprobs(pie_decoder *d, int n, int rows_cap, int blo
     PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_decoder_set_prompt_logprobs: the workspace needs 16-byte alignment (it starts with the logits block)");
     PIE_REQUIRE(workspace_bytes >= pie_decoder_prompt_logprobs_workspace_bytes(d, n, block_rows), PIE_E_SHAPE,
                 "pie_decoder_set_prompt_logprobs: the workspace is smaller than pie_decoder_prompt_logprobs_workspace_bytes(n, block_rows)");
-    d->pl_n = n, d->pl_rows_cap = rows_cap, d->pl_block = block_rows, d->pl_targets = targets, d->pl_count = count, d->pl_ids = out_ids, d->pl_vals = out_vals;
-    d->pl_ws = (u16 *)workspace, d->pl_op_ws = (char *)workspace + prompt_block_bytes(d, block_rows);  // (no step graph holds them: only the prompt passes launch them)
+    d->prompt = {n, rows_cap, block_rows, targets, count, out_ids, out_vals, (u16 *)workspace, (char *)workspace + prompt_block_bytes(d, block_rows)};
     return PIE_OK;
 }
 
 int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap, int32_t *recent_ids, void *workspace) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_tail: null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_tail: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
-    if (!table) {
-        d->bt_table = nullptr, d->bt_rows_cap = 0, d->bt_recent = nullptr, d->bt_ws = nullptr;
-        return PIE_OK;
-    }
+    if (!table) return d->rows.sampler = {}, PIE_OK;  // off
     PIE_REQUIRE(recent_ids && workspace, PIE_E_ARG, "pie_decoder_set_batch_tail: null pointer");
     PIE_REQUIRE(pie_aligned(recent_ids, 4), PIE_E_ALIGN, "pie_decoder_set_batch_tail: the ring needs 4-byte alignment");
     if (int rc = sample_rows_check("pie_decoder_set_batch_tail", rows_cap, d->cfg.vocab, table, workspace)) return rc;
-    d->bt_table = table, d->bt_rows_cap = rows_cap, d->bt_recent = recent_ids, d->bt_ws = workspace;  // (the batch graph's key holds them: no graph to drop)
+    d->rows.sampler = {table, rows_cap, recent_ids, workspace};  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 
@@ -950,11 +938,7 @@ int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint3
                                        const int32_t *bias_ids, const float *bias_vals, const int32_t *bias_n, int bias_cap) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_logits_edits: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
-    if (rows_cap == 0) {
-        d->be_rows_cap = 0, d->be_masks = nullptr, d->be_mask_words = 0, d->be_mask_on = nullptr;
-        d->be_bias_ids = nullptr, d->be_bias_vals = nullptr, d->be_bias_n = nullptr, d->be_bias_cap = 0;
-        return PIE_OK;
-    }
+    if (rows_cap == 0) return d->rows.edits = {}, PIE_OK;  // off
     PIE_REQUIRE(rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: rows_cap >= 1 (0: off)");
     PIE_REQUIRE(bias_cap >= 0 && bias_cap <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: bias_cap must be 1..1024 (0: no bias part)");
     PIE_REQUIRE(masks || bias_cap, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: neither a mask part nor a bias part");
@@ -972,8 +956,7 @@ int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint3
     } else {
         bias_ids = nullptr, bias_vals = nullptr, bias_n = nullptr;
     }
-    d->be_rows_cap = rows_cap, d->be_masks = masks, d->be_mask_words = mask_words, d->be_mask_on = mask_on;
-    d->be_bias_ids = bias_ids, d->be_bias_vals = bias_vals, d->be_bias_n = bias_n, d->be_bias_cap = bias_cap;  // (the batch graph's key holds them: no graph to drop)
+    d->rows.edits = {rows_cap, masks, mask_words, mask_on, bias_ids, bias_vals, bias_n, bias_cap};  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 
@@ -994,13 +977,10 @@ int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int
 int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *records, int32_t *counts, int rows_cap) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_count_penalty: null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_count_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
-    if (!records) {
-        d->bc_records = nullptr, d->bc_counts = nullptr, d->bc_rows_cap = 0;
-        return PIE_OK;
-    }
+    if (!records) return d->rows.counts = {}, PIE_OK;  // off
     PIE_REQUIRE(counts && rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_count_penalty: the records need their counts and rows_cap >= 1");
     PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(counts, 4), PIE_E_ALIGN, "pie_decoder_set_batch_count_penalty: the records and the counts need 4-byte alignment");
-    d->bc_records = records, d->bc_counts = counts, d->bc_rows_cap = rows_cap;  // (the batch graph's key holds them: no graph to drop)
+    d->rows.counts = {records, counts, rows_cap};  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 

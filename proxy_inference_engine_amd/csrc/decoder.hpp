@@ -15,6 +15,75 @@
 // The step's attention: its own launch | behind the q|k|v launch's seam, merged by o_proj's prologue | behind the seam and merged there
 enum { ATTN_TWO_LAUNCHES = 0, ATTN_FUSED = 1, ATTN_FUSED_MERGED = 2 };
 
+// The multi-sequence passes' per-row tail state (pie_decoder_step_batch, _prefill_batch, _step_mixed): four parts, each set as a
+// whole by its own entry and off in its value-initialised state.  Caller-owned device memory, read on the device only, whose CONTENTS may
+// change between calls; the addresses and sizes are launch arguments, so a captured batch graph bakes them in.  key(), check_rows() and
+// edits_logits() are the only readers of "what is configured" besides the launches: a field that joins a part joins key() below it.
+struct RowsTail {
+    struct Sampler {  // pie_decoder_set_batch_tail: per-row records, rings of fed ids, the sampler's workspace
+        pie_row_tail *table = nullptr;  // nullptr: off
+        int rows_cap = 0;
+        int *recent = nullptr;
+        void *ws = nullptr;
+    } sampler;
+    struct Top {  // pie_decoder_set_batch_top_logprobs: pie_top_logprobs' launches behind the passes' tail
+        int n = 0, rows_cap = 0;  // n == 0: off
+        int *ids = nullptr;
+        float *vals = nullptr;
+        const int *count = nullptr;
+        void *ws = nullptr;
+    } top;
+    struct Edits {  // pie_decoder_set_batch_logits_edits: per-row token masks and logit biases
+        int rows_cap = 0;                 // 0: off
+        const unsigned *masks = nullptr;  // [rows_cap, mask_words], nullptr: no mask part
+        int mask_words = 0;
+        const int *mask_on = nullptr, *bias_ids = nullptr;  // bias_ids, bias_vals: [rows_cap, bias_cap]
+        const float *bias_vals = nullptr;
+        const int *bias_n = nullptr;
+        int bias_cap = 0;  // 0: no bias part
+    } edits;
+    struct Counts {  // pie_decoder_set_batch_count_penalty: per-row frequency / presence records and counts
+        pie_count_penalty *records = nullptr;  // [rows_cap], nullptr: off
+        int *counts = nullptr;                 // [rows_cap, vocab]
+        int rows_cap = 0;
+    } counts;
+    // everything a captured batch graph bakes in (pie_decoder_step_batch's key): a setter drops no graph, a changed key captures a new one
+    void key(std::vector<uintptr_t> &k) const {
+        for (uintptr_t v : {(uintptr_t)sampler.table, (uintptr_t)sampler.recent, (uintptr_t)sampler.ws, (uintptr_t)sampler.rows_cap,
+                            (uintptr_t)top.n, (uintptr_t)top.rows_cap, (uintptr_t)top.ids, (uintptr_t)top.vals, (uintptr_t)top.count, (uintptr_t)top.ws,
+                            (uintptr_t)edits.rows_cap, (uintptr_t)edits.masks, (uintptr_t)edits.mask_words, (uintptr_t)edits.mask_on, (uintptr_t)edits.bias_ids,
+                            (uintptr_t)edits.bias_vals, (uintptr_t)edits.bias_n, (uintptr_t)edits.bias_cap,
+                            (uintptr_t)counts.records, (uintptr_t)counts.counts, (uintptr_t)counts.rows_cap})
+            k.push_back(v);
+    }
+    // a pass with `out_rows` output rows fits every configured part (checked before any launch)
+    int check_rows(int out_rows, const char *entry) const {
+        const char *over = sampler.table && out_rows > sampler.rows_cap   ? "batch tail"
+                           : edits.rows_cap && out_rows > edits.rows_cap  ? "batch logits edits"
+                           : top.n && out_rows > top.rows_cap             ? "top log-probabilities"
+                           : counts.records && out_rows > counts.rows_cap ? "batch count penalty" : nullptr;
+        return over ? pie::fail(PIE_E_SHAPE, std::string(entry) + ": more output rows than the " + over + "'s rows_cap") : PIE_OK;
+    }
+    // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale
+    bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records; }
+};
+
+// Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): the prompt passes score their rows in blocks of at most
+// `block` rows -- lm_head into the logits block at the head of ws, then pie_prompt_logprobs' launches on the op's workspace behind it (op_ws).
+// Caller-owned; record i belongs to row i of the call (ALL its N rows, not RowsTail's S output rows); n == 0: off.  In no graph's key.
+struct PromptScores {
+    int n = 0, rows_cap = 0, block = 0;
+    const int *targets = nullptr, *count = nullptr;
+    int *ids = nullptr;
+    float *vals = nullptr;
+    u16 *ws = nullptr;
+    void *op_ws = nullptr;
+    // the op on `rows` rows of logits, whose first row is row `row0` of the call
+    int score_rows(const pie_decoder_config &cfg, const u16 *logits, int row0, int rows, hipStream_t st) const {
+        return prompt_logprobs_launch(logits, rows, cfg.vocab, cfg.dtype, n, targets + row0, count + row0, ids + (size_t)row0 * (n + 1), vals + (size_t)row0 * (n + 1), op_ws, st);
+    }
+};
+
 struct pie_decoder {
     pie_decoder_config cfg;
     std::vector<pie_layer_weights> layers;
@@ -93,54 +162,18 @@ struct pie_decoder {
     const int *bias_ids = nullptr;
     const float *bias_vals = nullptr;
     int bias_n = 0;  // 0: off
-    // The multi-sequence passes' tail (pie_decoder_set_batch_tail): per-row records, rings and sampler workspace, caller-owned.
-    // bt_table == nullptr: off.  The passes read the records on the device only; the addresses are in the captured batch graph's key.
-    pie_row_tail *bt_table = nullptr;
-    int bt_rows_cap = 0;
-    int *bt_recent = nullptr;
-    void *bt_ws = nullptr;
-    // Top-n log-probabilities (pie_decoder_set_top_logprobs / _set_batch_top_logprobs): pie_top_logprobs' launches behind the
-    // step's configured tail (tlp_n > 0) and behind the multi-sequence passes' tail (btl_n > 0).  Caller-owned; all launch arguments.
+    // Top-n log-probabilities of the single-sequence step (pie_decoder_set_top_logprobs): pie_top_logprobs' launches behind the
+    // step's configured tail (tlp_n > 0).  Caller-owned; all launch arguments.
     int tlp_n = 0;
     int *tlp_ids = nullptr;
     float *tlp_vals = nullptr;
     void *tlp_ws = nullptr;
-    int btl_n = 0, btl_rows_cap = 0;
-    int *btl_ids = nullptr;
-    float *btl_vals = nullptr;
-    const int *btl_count = nullptr;
-    void *btl_ws = nullptr;
-    // The multi-sequence passes' per-row token masks and logit biases (pie_decoder_set_batch_logits_edits): caller-owned device
-    // memory whose CONTENTS may change between calls; the addresses and the three sizes are in the captured batch graph's key.
-    int be_rows_cap = 0;  // 0: off
-    const unsigned *be_masks = nullptr;  // [rows_cap, be_mask_words], nullptr: no mask part
-    int be_mask_words = 0;
-    const int *be_mask_on = nullptr;
-    const int *be_bias_ids = nullptr;  // [rows_cap, be_bias_cap]
-    const float *be_bias_vals = nullptr;
-    const int *be_bias_n = nullptr;
-    int be_bias_cap = 0;  // 0: no bias part
-    // Frequency / presence penalties (pie_decoder_set_count_penalty / _set_batch_count_penalty): caller-owned records and
-    // counts whose CONTENTS change between steps; cp_*: the step's tail (launch arguments), bc_*: the multi-sequence passes' (in the batch graph's key).
+    // Frequency / presence penalties of the single-sequence step (pie_decoder_set_count_penalty): a caller-owned record and
+    // counts whose CONTENTS change between steps; launch arguments of the step's tail.
     pie_count_penalty *cp_record = nullptr;  // nullptr: off
     int *cp_counts = nullptr;                // [vocab]
-    pie_count_penalty *bc_records = nullptr;  // [bc_rows_cap], nullptr: off
-    int *bc_counts = nullptr;                 // [bc_rows_cap, vocab]
-    int bc_rows_cap = 0;
-    // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): the prompt passes score their rows in blocks of at
-    // most pl_block rows -- lm_head into the logits block at the head of pl_ws, then pie_prompt_logprobs' launches on the op's workspace behind
-    // it (pl_op_ws).  Caller-owned; record i belongs to row i of the call.  pl_n == 0: off, and nothing else is launched.
-    int pl_n = 0, pl_rows_cap = 0, pl_block = 0;
-    const int *pl_targets = nullptr, *pl_count = nullptr;
-    int *pl_ids = nullptr;
-    float *pl_vals = nullptr;
-    u16 *pl_ws = nullptr;
-    void *pl_op_ws = nullptr;
-    // the op on `rows` rows of logits, whose first row is row `row0` of the call
-    int score_rows(const u16 *logits, int row0, int rows, hipStream_t st) const {
-        return prompt_logprobs_launch(logits, rows, cfg.vocab, cfg.dtype, pl_n, pl_targets + row0, pl_count + row0, pl_ids + (size_t)row0 * (pl_n + 1),
-                                      pl_vals + (size_t)row0 * (pl_n + 1), pl_op_ws, st);
-    }
+    RowsTail rows;        // the multi-sequence passes' per-row tail state
+    PromptScores prompt;  // the prompt passes' log-probabilities of prompt tokens
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
     bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n || cp_record; }
@@ -183,6 +216,7 @@ int paged_attn_i8_launch(int dtype, int D, const AttnArgs &a, hipStream_t st);
 // stream, which cannot be captured) in thread-local mode.  Returns the failure to begin the capture (enqueue did not run), else PIE_OK with
 // enqueue's result in *enqueue_rc and the graph (the caller's to destroy) in *graph, or hipStreamEndCapture's error in *end_err.
 int capture_graph(const std::function<int(hipStream_t)> &enqueue, int *enqueue_rc, hipGraph_t *graph, hipError_t *end_err);
+int graph_kernel_nodes(hipGraph_t g);  // the kernel nodes `g` holds, -1 where the runtime does not tell
 
 // prefill.hip: batched prompt processing (L >= prefill_min_rows() tokens): per layer many-row GEMMs on the weights' W4M tiles (int4) or
 // W16M copies (the other formats), with hand-written HIP kernels for RoPE + cache append, causal attention and SwiGLU.

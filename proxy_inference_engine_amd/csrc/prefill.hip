@@ -690,16 +690,17 @@ static RowsOpts every_row_head_opts() {
 }
 
 // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): rows [0, M) of xn -- final-normed already -- are
-// rows row0 .. row0 + M - 1 of the call.  Per block of at most pl_block rows: the lm_head as the logits-on-every-position branch multiplies
+// rows row0 .. row0 + M - 1 of the call.  Per block of at most `block` rows: the lm_head as the logits-on-every-position branch multiplies
 // it, into the caller's logits block, then the op's launches on that block.  Off: nothing is launched.
 template <class T>
 static int score_prompt_rows(pie_decoder *d, const u16 *xn, int row0, int M, hipStream_t st) {
-    if (!d->pl_n) return PIE_OK;
+    const PromptScores &pl = d->prompt;
+    if (!pl.n) return PIE_OK;
     const pie_decoder_config &c = d->cfg;
-    for (int b0 = 0; b0 < M; b0 += d->pl_block) {
-        const int rows = M - b0 < d->pl_block ? M - b0 : d->pl_block;
-        int rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, c.hidden, xn + (size_t)b0 * c.hidden, rows, d->pl_ws, st, every_row_head_opts());
-        if (rc || (rc = d->score_rows(d->pl_ws, row0 + b0, rows, st))) return rc;
+    for (int b0 = 0; b0 < M; b0 += pl.block) {
+        const int rows = M - b0 < pl.block ? M - b0 : pl.block;
+        int rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, c.hidden, xn + (size_t)b0 * c.hidden, rows, pl.ws, st, every_row_head_opts());
+        if (rc || (rc = pl.score_rows(c, pl.ws, row0 + b0, rows, st))) return rc;
     }
     return PIE_OK;
 }
@@ -709,7 +710,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
     const pie_decoder_config &c = d->cfg;
     const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
     const int chunk = prefill_chunk_rows() < L ? prefill_chunk_rows() : L;
-    int rc = scratch_reserve(d, chunk, w16_copy_elems(c, logits_all != nullptr || d->pl_n), d->splits);
+    int rc = scratch_reserve(d, chunk, w16_copy_elems(c, logits_all != nullptr || d->prompt.n), d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     // quantized KV: the pass runs on the T scratch (kv_table below), the layer's codes are expanded into it and the chunk's rows quantized back
@@ -782,7 +783,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             // the last layer ends in the plain add: the final norm runs below, and only for logits on every position or for scored rows
             if ((rc = mlp_rows<T>(d, w, M, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : nullptr, st))) return rc;
         }
-        if ((logits_all || d->pl_n) && (rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
+        if ((logits_all || d->prompt.n) && (rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
         if (logits_all) {  // lm_head on every position, like the reference (language.py:205-209)
             if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, every_row_head_opts()))) return rc;
         }
@@ -861,31 +862,33 @@ static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
 // penalty's launch, and every row's own token mask inside the partials pass of the log-softmax.
 // The rows' top-n log-probability records (pie_decoder_set_batch_top_logprobs), once next_tokens are final.  Off: nothing is launched.
 static int batch_top_logprobs_launch(pie_decoder *d, int rows, const float *logprobs, const int32_t *next_tokens, hipStream_t st) {
-    if (!d->btl_n) return PIE_OK;
-    return top_logprobs_launch(logprobs, rows, d->cfg.vocab, d->btl_n, next_tokens, d->btl_count, d->btl_ids, d->btl_vals, d->btl_ws, st);
+    const RowsTail::Top &t = d->rows.top;
+    if (!t.n) return PIE_OK;
+    return top_logprobs_launch(logprobs, rows, d->cfg.vocab, t.n, next_tokens, t.count, t.ids, t.vals, t.ws, st);
 }
 
 static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *ctx, const int32_t *out_rows, int n_src, int rows, u16 *logits,
                              float *logprobs, int32_t *next_tokens, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     PrefillScratch *s = d->prefill;
+    const RowsTail &r = d->rows;
     int rc;
     // The five stages of configured_tail (decoder.hip), per row; with nothing configured only the partials and the finish run.
-    if (d->bt_table || d->be_bias_cap) {  // edit: the rows' biases ride the penalty's launch (k_logits_edit_rows: no penalties without a table)
+    if (r.sampler.table || r.edits.bias_cap) {  // edit: the rows' biases ride the penalty's launch (k_logits_edit_rows: no penalties without a table)
         PenRowsArgs p = {};
-        p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = d->bt_table, p.recent = d->bt_recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
-        const BiasRowsArgs b = {d->be_bias_ids, d->be_bias_vals, d->be_bias_n, d->be_bias_cap, d->bt_table ? 1 : 0};
-        if ((rc = d->be_bias_cap ? logits_edit_rows_launch(c.dtype, p, b, rows, st) : logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
+        p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = r.sampler.table, p.recent = r.sampler.recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
+        const BiasRowsArgs b = {r.edits.bias_ids, r.edits.bias_vals, r.edits.bias_n, r.edits.bias_cap, r.sampler.table ? 1 : 0};
+        if ((rc = r.edits.bias_cap ? logits_edit_rows_launch(c.dtype, p, b, rows, st) : logits_penalty_rows_launch(c.dtype, p, rows, st))) return rc;
     }
-    if (d->bc_records) {  // count penalty: behind the row's penalty and its bias
+    if (r.counts.records) {  // count penalty: behind the row's penalty and its bias
         CountPenArgs k = {};
-        k.logits = logits, k.V = c.vocab, k.n_src = n_src, k.records = d->bc_records, k.counts = d->bc_counts, k.ids = ids, k.ctx = ctx, k.out_rows = out_rows;
+        k.logits = logits, k.V = c.vocab, k.n_src = n_src, k.records = r.counts.records, k.counts = r.counts.counts, k.ids = ids, k.ctx = ctx, k.out_rows = out_rows;
         if ((rc = logits_count_penalty_rows_launch(c.dtype, k, rows, st))) return rc;
     }
     // partials and finish: the rows' masks ride the partials pass -- physically last, so a masked id is -inf whatever else is configured
-    if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st, d->be_masks, d->be_mask_words, d->be_mask_on))) return rc;
+    if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st, r.edits.masks, r.edits.mask_words, r.edits.mask_on))) return rc;
     // sampler and top-n
-    if (d->bt_table && (rc = sample_rows_launch(logprobs, rows, c.vocab, d->bt_table, d->bt_ws, next_tokens, nullptr, nullptr, st))) return rc;
+    if (r.sampler.table && (rc = sample_rows_launch(logprobs, rows, c.vocab, r.sampler.table, r.sampler.ws, next_tokens, nullptr, nullptr, st))) return rc;
     return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
 }
 
@@ -945,7 +948,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         g.w = (const char *)d->glob.lm_head, g.K = H, g.N = c.vocab, g.M = B, g.x = s->x, g.norm_w = (const u16 *)d->glob.final_norm, g.eps = c.rms_eps;
         g.y = logits, g.stats = s->tail_stats;
         if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_RMSNORM, EPI_LOGITS, g, st))) return rc;
-        if (d->bt_table || d->be_rows_cap || d->bc_records) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty or an edit)
+        if (d->rows.edits_logits()) return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);  // (the epilogue's partials are stale after a penalty or an edit)
         if ((rc = logits_finish_launch(c.dtype, logits, c.vocab, B, s->tail_stats, lm_waves, logprobs, next_tokens, nullptr, nullptr, 0, nullptr, st))) return rc;
         return batch_top_logprobs_launch(d, B, logprobs, next_tokens, st);
     }
@@ -1078,12 +1081,9 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     }
     PIE_REQUIRE(d->glob_set, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: set_globals must be called first");
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: a layer has no weights (pie_decoder_set_layer)");
-    PIE_REQUIRE(!d->bt_table || S <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch tail's rows_cap");
-    PIE_REQUIRE(!d->be_rows_cap || S <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch logits edits' rows_cap");
-    PIE_REQUIRE(!d->btl_n || S <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the top log-probabilities' rows_cap");
-    PIE_REQUIRE(!d->bc_records || S <= d->bc_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more output rows than the batch count penalty's rows_cap");
-    PIE_REQUIRE(!d->pl_n || N <= d->pl_rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more rows than the prompt log-probabilities' rows_cap");
-    PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
+    if (int rc = d->rows.check_rows(S, "pie_decoder_prefill_batch / _step_mixed")) return rc;
+    PIE_REQUIRE(!d->prompt.n || N <= d->prompt.rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more rows than the prompt log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->rows.top.n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
     PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_prefill_batch / _step_mixed: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
@@ -1136,11 +1136,8 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_step_batch: not available on a tensor-parallel shard");
     for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_step_batch: a layer has no weights (pie_decoder_set_layer)");
     PIE_REQUIRE(B >= 1 && B <= 4096 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_step_batch: bad batch shape");
-    PIE_REQUIRE(!d->bt_table || B <= d->bt_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch tail's rows_cap");
-    PIE_REQUIRE(!d->be_rows_cap || B <= d->be_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch logits edits' rows_cap");
-    PIE_REQUIRE(!d->btl_n || B <= d->btl_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the top log-probabilities' rows_cap");
-    PIE_REQUIRE(!d->bc_records || B <= d->bc_rows_cap, PIE_E_SHAPE, "pie_decoder_step_batch: more rows than the batch count penalty's rows_cap");
-    PIE_REQUIRE(!d->btl_n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_step_batch: logprobs need 4-byte alignment");
+    if (int rc = d->rows.check_rows(B, "pie_decoder_step_batch")) return rc;
+    PIE_REQUIRE(!d->rows.top.n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_step_batch: logprobs need 4-byte alignment");
     PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
                 "pie_decoder_step_batch: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
     const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
@@ -1154,13 +1151,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
     std::vector<uintptr_t> key = {(uintptr_t)tokens, (uintptr_t)context_lens, (uintptr_t)block_tables, (uintptr_t)logits, (uintptr_t)logprobs,
                                   (uintptr_t)next_tokens, (uintptr_t)n_pages, (uintptr_t)max_blocks, (uintptr_t)B, (uintptr_t)d->kv_i8 /* the page format is baked into the launches too */};
     for (int i = 0; i < d->cfg.n_layers; ++i) key.push_back((uintptr_t)slabs[i]);
-    for (uintptr_t v : {(uintptr_t)d->bt_table, (uintptr_t)d->bt_recent, (uintptr_t)d->bt_ws, (uintptr_t)d->bt_rows_cap}) key.push_back(v);  // the tail's launches bake them in
-    for (uintptr_t v : {(uintptr_t)d->btl_n, (uintptr_t)d->btl_rows_cap, (uintptr_t)d->btl_ids, (uintptr_t)d->btl_vals, (uintptr_t)d->btl_count, (uintptr_t)d->btl_ws})
-        key.push_back(v);  // and so do the top log-probabilities'
-    for (uintptr_t v : {(uintptr_t)d->be_rows_cap, (uintptr_t)d->be_masks, (uintptr_t)d->be_mask_words, (uintptr_t)d->be_mask_on, (uintptr_t)d->be_bias_ids,
-                        (uintptr_t)d->be_bias_vals, (uintptr_t)d->be_bias_n, (uintptr_t)d->be_bias_cap})
-        key.push_back(v);  // and the per-row masks' and biases'
-    for (uintptr_t v : {(uintptr_t)d->bc_records, (uintptr_t)d->bc_counts, (uintptr_t)d->bc_rows_cap}) key.push_back(v);  // and the frequency / presence penalties'
+    d->rows.key(key);  // the tail's launches bake the per-row state in too
     if (!d->prefill) d->prefill = new PrefillScratch();
     PrefillScratch *s = d->prefill;
     if (s->batch_graph && s->batch_key == key && s->batch_gen == s->alloc_gen) {
@@ -1186,21 +1177,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
         }
         s = d->prefill;
         e = hipGraphInstantiate(&s->batch_graph, g, nullptr, nullptr, 0);
-        {  // the kernel nodes the graph really holds (pie_decoder_batch_graph_launches), not a formula
-            size_t n_nodes = 0;
-            d->batch_graph_kernels = -1;
-            if (hipGraphGetNodes(g, nullptr, &n_nodes) == hipSuccess && n_nodes) {
-                std::vector<hipGraphNode_t> nodes(n_nodes);
-                if (hipGraphGetNodes(g, nodes.data(), &n_nodes) == hipSuccess) {
-                    int k = 0;
-                    for (size_t i = 0; i < n_nodes; ++i) {
-                        hipGraphNodeType t;
-                        if (hipGraphNodeGetType(nodes[i], &t) == hipSuccess && t == hipGraphNodeTypeKernel) ++k;
-                    }
-                    d->batch_graph_kernels = k;
-                }
-            }
-        }
+        d->batch_graph_kernels = graph_kernel_nodes(g);  // what the graph really holds (pie_decoder_batch_graph_launches), not a formula
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) return pie::fail(PIE_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
         s->batch_key = key, s->batch_gen = s->alloc_gen;

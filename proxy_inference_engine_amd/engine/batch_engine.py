@@ -183,6 +183,147 @@ class _PromptScores:
             self.absorb(torch.cat(self.tensors()).cpu().numpy())
 
 
+def same_occupant(have, want) -> bool:
+    """What a row holds and what the coming pass wants there, each (request, tokens it has generated) or None: the same request one token
+    further on is the row's own progress (the pass advances the device's state by that token itself), not a new occupant."""
+    return want == have or (want is not None and have is not None and want[0] == have[0] and want[1] == have[1] + 1)
+
+
+class _RowSeats:
+    """The per-row tail state of one generate() call: which request's sampler record, top-n count, mask, bias table and counts every output
+    row of the device buffers holds, rewritten where a row's occupant changes.  tails: (params, seeds) or None; edits: every request's
+    SamplingParams.edits or None; cnts: every request's (frequency, presence) or None, or None; tops: every request's top_logprobs or None
+    (then `maps` collects their records' maps).  A kind that is None is neither armed nor written.  As a context manager: arms the kinds
+    asked for with every row neutral, and clears them on the way out, whatever happened."""
+
+    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None):
+        self.model, self.max_batch, self.prompts = model, max_batch, prompts
+        self.tails, self.edits, self.cnts, self.tops = tails, edits, cnts, tops
+        self.maps = None if tops is None else [[] for _ in prompts]
+        self.bufs = None              # the armed top-n buffers
+        self.slots: list = []         # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
+        self.counts: list = []        # top-n records: the count the device holds for row s (-1: the row reports nothing)
+        self.seats: list = []         # per-request edits: the request whose mask and bias table row s holds, None = unarmed
+        self.words: list = []         # ... and the mask words row s holds when that request's mask is a callable
+        self.cseats: list = []        # frequency / presence penalties: what row s of the counting state holds, (request, tokens generated) or None = a zero record
+
+    def __enter__(self):
+        m, every = self.model, list(range(self.max_batch))
+        try:
+            if self.tails is not None:
+                m.set_batch_tail(self.max_batch)
+                m.write_batch_tail(every, [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
+            if self.edits is not None:
+                any_mask, cap = any(k is not None for k, _ in self.edits), max(len(b[0]) if b else 0 for _, b in self.edits)
+                m.set_batch_edits(self.max_batch, masks=any_mask, bias_cap=cap)
+                m.write_batch_edits(every, [None] * self.max_batch if any_mask else None, [None] * self.max_batch if cap else None)   # (cached buffers may hold an earlier call's rows)
+            if self.cnts is not None:
+                m.set_batch_count_penalty(self.max_batch)
+                m.write_batch_count_penalty(every, [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
+            if self.tops is not None:
+                self.bufs = m.set_batch_top_logprobs(self.max_batch, max(max(self.tops, default=1), 1))
+                self.bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
+        except BaseException:
+            self.__exit__()
+            raise
+        return self
+
+    def __exit__(self, *exc) -> None:
+        for asked, clear in ((self.tails, "clear_batch_tail"), (self.edits, "clear_batch_edits"), (self.cnts, "clear_batch_count_penalty"),
+                             (self.tops, "clear_batch_top_logprobs")):
+            if asked is not None:
+                getattr(self.model, clear)()
+
+    @staticmethod
+    def _changed(held: list, want: list, same=same_occupant, empty=None) -> list[int]:
+        """The rows of `want` that do not hold the `same` as `held` records (rows it has not seen: `empty`); `held` is brought up to date."""
+        held.extend([empty] * (len(want) - len(held)))
+        rows = [s for s, w in enumerate(want) if not same(held[s], w)]
+        held[:len(want)] = want
+        return rows
+
+    def seat(self, rows: list, active: list) -> None:
+        """The coming pass's output rows, in order: a request index (its own record; its ring rows from the ids it has been fed) or
+        None (a prompt still filling: greedy, its token is discarded).  Rewrites the rows whose occupant changed -- the moment at which
+        step_batch rewrites the block table; a row a request keeps is left alone (its `calls` advances on the device).  The rows' top-n
+        counts follow the same rule: a request's own top_logprobs, -1 for a prompt still filling.  active: the sequences in flight."""
+        prompts, edits, cnts = self.prompts, self.edits, self.cnts
+        gen_by = {a.request: a.generated for a in active}
+        if self.tops is not None:
+            want_c = [-1 if r is None else self.tops[r] for r in rows]
+            changed, count = self._changed(self.counts, want_c, int.__eq__, -1), self.bufs["count"]
+            if changed:
+                count.index_copy_(0, torch.tensor(changed, dtype=torch.long, device=count.device),
+                                  torch.tensor([want_c[s_] for s_ in changed], dtype=torch.int32, device=count.device))
+        if edits is not None:
+            # a row's mask and bias table are rewritten where its record is: when its occupant changes.  A callable mask is evaluated for
+            # every live row, every pass, on what the request has been fed -- the loop's read-back already brought the tokens -- and the
+            # rows whose words changed go up in one copy.
+            from ..logits_processors import packed_token_mask
+            V, seats, words = self.model.args.vocab_size, self.seats, self.words
+            want_e = [r if r is not None and edits[r] != (None, None) else None for r in rows]
+            seats.extend([None] * (len(want_e) - len(seats)))
+            words.extend([None] * (len(want_e) - len(words)))
+            m_rows, m_new, b_rows, b_new = [], [], [], []
+            for s_, r in enumerate(want_e):
+                proc, bias = edits[r] if r is not None else (None, None)
+                moved = seats[s_] != r
+                if moved:
+                    if any(b is not None for _, b in edits):
+                        b_rows.append(s_), b_new.append(bias)
+                    words[s_] = None
+                if proc is not None and proc.mask_fn is not None:
+                    w = packed_token_mask(proc.mask_fn(list(prompts[r]) + list(gen_by.get(r, []))), V)
+                    if words[s_] is None or not torch.equal(words[s_], w):
+                        m_rows.append(s_), m_new.append(w)
+                        words[s_] = w
+                elif moved and any(m is not None for m, _ in edits):
+                    m_rows.append(s_), m_new.append(None if proc is None else proc.mask)
+                seats[s_] = r
+            if m_rows:
+                self.model.write_batch_edits(m_rows, masks=m_new)
+            if b_rows:
+                self.model.write_batch_edits(b_rows, biases=b_new)
+        if cnts is not None:
+            # a row's record and counts are rebuilt where its sampler record is: when its occupant changes, from the ids the request has
+            # generated so far (the host holds them; the last of them is the row's input, counted here and not again by the pass).  A
+            # prompt that is still filling, and a request without penalties, hold a zero record.
+            want = [None if r is None or cnts[r] is None else (r, len(gen_by.get(r, []))) for r in rows]
+            c_rows = self._changed(self.cseats, want)
+            moved = [want[s_] for s_ in c_rows]
+            self.model.write_batch_count_penalty(c_rows, [None if w is None else (*cnts[w[0]], len(prompts[w[0]])) for w in moved],
+                                                 [None if w is None else list(gen_by.get(w[0], [])) for w in moved])
+        if self.tails is None:
+            return
+        params, seeds = self.tails
+        want = [None if r is None else (r, len(gen_by.get(r, []))) for r in rows]
+        idx = self._changed(self.slots, want)
+        recs, fed = [], []
+        for w in (want[s_] for s_ in idx):
+            if w is None:
+                recs.append(SamplingParams().record())
+                fed.append(None)
+            else:
+                sp = params[w[0]]
+                recs.append(sp.record(w[1], seeds[w[0]]))
+                fed.append(None if sp.repetition_penalty == 1.0 else list(prompts[w[0]]) + list(gen_by.get(w[0], [])[:-1]))
+        self.model.write_batch_tail(idx, recs, fed)
+
+    def lone_step(self, idx) -> bool:
+        """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
+        own, or wants log-probabilities: then it is a batch of one.  Frequency / presence penalties alone do not make it one: a request's
+        first token is chosen against empty counts, which is the unpenalised row, so the greedy prompt pass gives the token the
+        penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`)."""
+        return self.tops is None and (self.tails is None or self.tails[0][idx].tailless) and (self.edits is None or self.edits[idx] == (None, None))
+
+    def records(self, n_rows: int):
+        """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'
+        bits): row views of it outlive the next pass.  None when log-probabilities are not asked for."""
+        if self.tops is None:
+            return [None] * n_rows
+        return torch.cat([self.bufs["ids"][:n_rows], self.bufs["vals"][:n_rows].view(torch.int32)], dim=1)
+
+
 class BatchedEngine:
     def __init__(self, model, num_pages: int = 1024, max_batch: int = 32, stop_tokens: Iterable[int] = (),
                  sampler: Callable[[torch.Tensor], torch.Tensor] | None = None, batch_prefill: bool = True, max_prefill_rows: int = 4096,
@@ -286,39 +427,11 @@ class BatchedEngine:
                 sampling = None               # no record to configure: a request with only a mask, a bias or count penalties arms no batch tail
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        if sampling is None and tops is None and edits is None and cnts is None:
-            return self._generate(prompts, max_new_tokens, None, scores=scores)
-        try:
-            if sampling is not None:
-                self.model.set_batch_tail(self.max_batch)
-                self.model.write_batch_tail(list(range(self.max_batch)), [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
-            if edits is not None:
-                any_mask, cap = any(m is not None for m, _ in edits), max(len(b[0]) if b else 0 for _, b in edits)
-                self.model.set_batch_edits(self.max_batch, masks=any_mask, bias_cap=cap)
-                self.model.write_batch_edits(list(range(self.max_batch)), [None] * self.max_batch if any_mask else None,
-                                             [None] * self.max_batch if cap else None)   # (cached buffers may hold an earlier call's rows)
-            if cnts is not None:
-                self.model.set_batch_count_penalty(self.max_batch)
-                self.model.write_batch_count_penalty(list(range(self.max_batch)), [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
-            tails = None if sampling is None else (params, seeds)
-            if tops is None:
-                return self._generate(prompts, max_new_tokens, tails, edits=edits, cnts=cnts, scores=scores)
-            bufs = self.model.set_batch_top_logprobs(self.max_batch, max(max(tops, default=1), 1))
-            bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
-            maps: list = [[] for _ in prompts]
-            out = self._generate(prompts, max_new_tokens, tails, (tops, bufs, maps), edits=edits, cnts=cnts, scores=scores)
-            return out, maps
-        finally:
-            if sampling is not None:
-                self.model.clear_batch_tail()
-            if edits is not None:
-                self.model.clear_batch_edits()
-            if cnts is not None:
-                self.model.clear_batch_count_penalty()
-            if tops is not None:
-                self.model.clear_batch_top_logprobs()
+        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops) as seats:
+            out = self._generate(prompts, max_new_tokens, seats, scores)
+        return out if tops is None else (out, seats.maps)
 
-    def _generate(self, prompts: list, max_new_tokens: int, tails, tops=None, edits=None, cnts=None, scores=None) -> list[list[int]]:
+    def _generate(self, prompts: list, max_new_tokens: int, seats: _RowSeats, scores=None) -> list[list[int]]:
         for p in prompts:
             if self._pages_for(len(p) + max_new_tokens) > self.pool.size():
                 raise ValueError("a prompt does not fit the page pool")
@@ -351,107 +464,9 @@ class BatchedEngine:
             seq = root[0].page_manager.fork()                               # whole pages: add_ref only, nothing is copied
             return [type(root[0])(seq, i) for i in range(len(root))]
         filling: list = []            # chunked prefill: [request, prompt, cache, rows done] of admitted prompts not yet fully in their pages
-        slots: list = []              # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
-        counts: list = []             # top-n records: the count the device holds for row s (-1: the row reports nothing)
-        seats: list = []              # per-request edits: the request whose mask and bias table row s holds, None = unarmed
-        words: list = []              # ... and the mask words row s holds when that request's mask is a callable
-        cseats: list = []             # frequency / presence penalties: what row s of the counting state holds, (request, tokens generated) or None = a zero record
-
-        def seat(rows: list) -> None:
-            """The coming pass's output rows, in order: a request index (its own record; its ring rows from the ids it has been fed) or
-            None (a prompt still filling: greedy, its token is discarded).  Rewrites the rows whose occupant changed -- the moment at which
-            step_batch rewrites the block table; a row a request keeps is left alone (its `calls` advances on the device).  The rows' top-n
-            counts follow the same rule: a request's own top_logprobs, -1 for a prompt still filling."""
-            if tops is not None:
-                want_c = [-1 if r is None else tops[0][r] for r in rows]
-                counts.extend([-1] * (len(want_c) - len(counts)))
-                changed = [s_ for s_, c_ in enumerate(want_c) if counts[s_] != c_]
-                if changed:
-                    dev = tops[1]["count"].device
-                    tops[1]["count"].index_copy_(0, torch.tensor(changed, dtype=torch.long, device=dev),
-                                                 torch.tensor([want_c[s_] for s_ in changed], dtype=torch.int32, device=dev))
-                    for s_ in changed:
-                        counts[s_] = want_c[s_]
-            if edits is not None:
-                # a row's mask and bias table are rewritten where its record is: when its occupant changes.  A callable mask is evaluated for
-                # every live row, every pass, on what the request has been fed -- the read-back above already brought the tokens -- and the
-                # rows whose words changed go up in one copy.
-                from ..logits_processors import packed_token_mask
-                V = self.model.args.vocab_size
-                fed_by = {a.request: a.generated for a in active}
-                want_e = [r if r is not None and edits[r] != (None, None) else None for r in rows]
-                seats.extend([None] * (len(want_e) - len(seats)))
-                words.extend([None] * (len(want_e) - len(words)))
-                m_rows, m_new, b_rows, b_new = [], [], [], []
-                for s_, r in enumerate(want_e):
-                    proc, bias = edits[r] if r is not None else (None, None)
-                    moved = seats[s_] != r
-                    if moved:
-                        if any(b is not None for _, b in edits):
-                            b_rows.append(s_), b_new.append(bias)
-                        words[s_] = None
-                    if proc is not None and proc.mask_fn is not None:
-                        w = packed_token_mask(proc.mask_fn(list(prompts[r]) + list(fed_by.get(r, []))), V)
-                        if words[s_] is None or not torch.equal(words[s_], w):
-                            m_rows.append(s_), m_new.append(w)
-                            words[s_] = w
-                    elif moved and any(m is not None for m, _ in edits):
-                        m_rows.append(s_), m_new.append(None if proc is None else proc.mask)
-                    seats[s_] = r
-                if m_rows:
-                    self.model.write_batch_edits(m_rows, masks=m_new)
-                if b_rows:
-                    self.model.write_batch_edits(b_rows, biases=b_new)
-            if cnts is not None:
-                # a row's record and counts are rebuilt where its sampler record is: when its occupant changes, from the ids the request has
-                # generated so far (the host holds them; the last of them is the row's input, counted here and not again by the pass).  A
-                # request one token further on in the row it held is the row's own progress: the pass counts that token itself.  A prompt
-                # that is still filling, and a request without penalties, hold a zero record.
-                gen_by = {a.request: a.generated for a in active}
-                want_c = [None if r is None or cnts[r] is None else (r, len(gen_by.get(r, []))) for r in rows]
-                cseats.extend([None] * (len(want_c) - len(cseats)))
-                c_rows, c_recs, c_gen = [], [], []
-                for s_, w in enumerate(want_c):
-                    have = cseats[s_]
-                    if w == have or (w is not None and have is not None and w[0] == have[0] and w[1] == have[1] + 1):
-                        cseats[s_] = w
-                        continue
-                    c_rows.append(s_)
-                    c_recs.append(None if w is None else (*cnts[w[0]], len(prompts[w[0]])))
-                    c_gen.append(None if w is None else list(gen_by.get(w[0], [])))
-                    cseats[s_] = w
-                self.model.write_batch_count_penalty(c_rows, c_recs, c_gen)
-            if tails is None:
-                return
-            params, seeds = tails
-            drawn = {a.request: len(a.generated) for a in active}
-            want = [None if r is None else (r, drawn.get(r, 0)) for r in rows]
-            slots.extend([None] * (len(want) - len(slots)))
-            idx, recs, fed = [], [], []
-            for s_, w in enumerate(want):
-                have = slots[s_]
-                # the same request one token further on is the row's own progress, not a new occupant
-                if w == have or (w is not None and have is not None and w[0] == have[0] and w[1] == have[1] + 1):
-                    slots[s_] = w
-                    continue
-                idx.append(s_)
-                if w is None:
-                    recs.append(SamplingParams().record())
-                    fed.append(None)
-                else:
-                    sp = params[w[0]]
-                    recs.append(sp.record(w[1], seeds[w[0]]))
-                    gen = next((a.generated for a in active if a.request == w[0]), [])
-                    fed.append(None if sp.repetition_penalty == 1.0 else list(prompts[w[0]]) + list(gen[:-1]))
-                slots[s_] = w
-            self.model.write_batch_tail(idx, recs, fed)
-
-        def lone_step(idx) -> bool:
-            """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
-            own, or wants log-probabilities: then it is a batch of one.  Frequency / presence penalties alone do not make it one: a request's
-            first token is chosen against empty counts, which is the unpenalised row, so the greedy prompt pass gives the token the
-            penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`)."""
-            return tops is None and (tails is None or tails[0][idx].tailless) and (edits is None or edits[idx] == (None, None))
+        tops = seats.tops
+        seat = lambda rows: seats.seat(rows, active)   # (the loop below rebinds `active`: read when called)
+        lone_step, records = seats.lone_step, seats.records
 
         def scored(n_decode: int | None = None, parts: list | None = None) -> None:
             """Around a pass that carries prompt rows: with arguments before it (the rows n_decode.. hold `parts`, as pass_targets takes
@@ -459,12 +474,6 @@ class BatchedEngine:
             if scores is not None:
                 scores.arm(n_decode, parts) if parts is not None else scores.collect()
 
-        def records(n_rows: int):
-            """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'
-            bits): row views of it outlive the next pass.  None when log-probabilities are not asked for."""
-            if tops is None:
-                return [None] * n_rows
-            return torch.cat([tops[1]["ids"][:n_rows], tops[1]["vals"][:n_rows].view(torch.int32)], dim=1)
         while pending or active or filling:
             # every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
             if active:
@@ -476,7 +485,7 @@ class BatchedEngine:
                 if tops is not None:
                     recs = host[len(active):len(active) + n_top].reshape(len(active), 2, -1)
                     for a, r in zip(active, recs):
-                        tops[2][a.request].append(host_record_to_map(r[0], r[1].view(np.float32), tops[0][a.request])[1])
+                        seats.maps[a.request].append(host_record_to_map(r[0], r[1].view(np.float32), tops[a.request])[1])
                 keep = []
                 for a, t in zip(active, host[:len(active)].tolist()):
                     a.generated.append(int(t))
