@@ -372,6 +372,37 @@ size_t pie_prompt_logprobs_workspace_bytes(int rows, int V, int n);
 int pie_prompt_logprobs(const void *logits, int rows, int V, int dtype, int n, const int32_t *targets, const int32_t *count, int32_t *out_ids,
                         float *out_vals, void *workspace, void *stream);
 
+/* ---------------------------------------------------------------- greedy speculative decoding
+ * No reference counterpart beyond the shape of its loop: generate() consumes several tokens per generate_step yield
+ * (engine/inference_engine.py:200-206).  Two ops: a prompt-lookup drafter (n-gram copy from the sequence's own ids) and the verify of a block
+ * of raw logits against a draft.
+ * pie_ngram_draft: ids DEVICE int32 [>= cap] = the sequence so far, the last id being the token about to be fed; len DEVICE int32 [1], read on
+ *   the device and CLAMPED there to [0, cap] (a device value cannot be refused before the launch: the search never reads beyond the cap ids
+ *   the caller vouches for); out_ids DEVICE int32 [k], out_count DEVICE int32 [1].  RULE: for n = ngram_max down to ngram_min the suffix is
+ *   ids[len - n : len]; a match is a start p with p + n <= len - 1 and ids[p : p + n] == suffix; the LARGEST p of the LARGEST n that has any
+ *   match is taken, and with h' = ids ++ draft, draft[i] = h'[p + n + i] for i < k -- an overlapped (LZ77) copy, so a period-3 tail drafts k
+ *   ids -- and out_count = k.  No match for any n, or len <= ngram_min: out_count = 0 and out_ids keeps its contents.  Deterministic: no
+ *   atomics, nothing depends on arrival order.  Two launches: the search over a grid sized from cap (one workgroup per 2048 ids, at most
+ *   1024, grid-stride beyond; one partial per workgroup in the workspace), then one workgroup that reduces the partials and one thread of
+ *   it that copies the k ids.  workspace: pie_ngram_draft_workspace_bytes() bytes of device memory, 4-byte aligned, no initialisation.
+ *   Checked in this order, each before any launch: ngram_min < 1, ngram_min > ngram_max, ngram_max > 8, k outside 1..31, a null pointer:
+ *   PIE_E_ARG; cap outside 1..2^27: PIE_E_SHAPE; a pointer not 4-byte aligned: PIE_E_ALIGN.
+ * pie_spec_verify: logits [rows, V] T, rows 2..32: row 0 is the fed token's, row i the i-th draft's; draft DEVICE int32 [rows - 1].  a_r = row
+ *   r's greedy token, bit for bit what pie_logprobs_argmax gives that row alone (same 256-tile partition, same merge, same first-argmax
+ *   rule).  n_acc = the largest j with draft[i - 1] == a_{i - 1} for all 1 <= i <= j; a draft id outside [0, V) is never accepted and never
+ *   used as an index.  out_n [1] = n_acc + 1; out_tokens [rows]: a_0 .. a_{n_acc}, then -1.  logprobs (nullable) fp32 [rows, V]: rows
+ *   0 .. n_acc are written, bit-identical with pie_logprobs_argmax's; the rows behind them keep their contents (the predicate is read on
+ *   the device: their workgroups return at once).  Three launches: the partials over (256, rows), one merge workgroup per row, the accept
+ *   and log-probabilities over (64, rows).  workspace: pie_spec_verify_workspace_bytes(rows) bytes (0 for refused sizes), 16-byte aligned,
+ *   no initialisation.  A null pointer: PIE_E_ARG; rows outside 2..32, V < 1: PIE_E_SHAPE; logits not 2-byte, draft or an output not
+ *   4-byte, the workspace not 16-byte aligned: PIE_E_ALIGN; a dtype that is neither PIE_BF16 nor PIE_F16: PIE_E_ARG -- each before any launch. */
+size_t pie_ngram_draft_workspace_bytes(void);
+int pie_ngram_draft(const int32_t *ids, const int32_t *len, int cap, int ngram_max, int ngram_min, int k, int32_t *out_ids, int32_t *out_count,
+                    void *workspace, void *stream);
+size_t pie_spec_verify_workspace_bytes(int rows);
+int pie_spec_verify(const void *logits, int rows, int V, int dtype, const int32_t *draft, int32_t *out_tokens, int32_t *out_n, float *logprobs,
+                    void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- fused decode step
  * One forward of Model.__call__ (models/llama/language.py:199-210) for inputs[1,1] over per-layer
  * ReusableKVCache buffers (cache/kv_cache/reusable.py:96-142) followed by the tail of _inference
@@ -656,6 +687,28 @@ int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint3
  * With neither set every pass launches exactly what it launches without.  Tensor-parallel decoders refuse both (PIE_E_STATE). */
 int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int32_t *counts);
 int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *records, int32_t *counts, int rows_cap);
+/* One speculative pass of the single-sequence decoder: m = n_draft drafted ids (draft_ids DEVICE int32 [m]) are verified in one
+ * pass over the weights.  In order: (1) rows [the device-side token, draft_0 .. draft_{m - 1}] are gathered on the device (a draft id the
+ * embedding could not index is fed as id 0; pie_spec_verify never accepts it) and forwarded from the device-side offset through
+ * pie_decoder_prefill's many-row pass with raw logits on every row into a block of the workspace; (2) pie_spec_verify on the block, into
+ * out_tokens [m + 1], out_n [1] and logprobs_rows (nullable fp32 [m + 1, vocab]); (3) its last launch leaves the decoder as if out_n plain
+ * greedy steps had run: the device-side offset advanced by out_n (not by m + 1), the device-side token and the bound token output = the last
+ * accepted token, history[o + 1 + i] = accepted token i.  The K / V rows of rejected drafts stay behind the offset and are overwritten by
+ * the positions that follow; nothing reads them.  The bound logits and log-probabilities hold row m's, accepted or not.
+ * seq_ids (nullable DEVICE int32 [seq_cap]) = the sequence's ids by position, kept whole for pie_ngram_draft: seq_ids[o] = the fed token and
+ * seq_ids[o + 1 + i] = accepted token i are written, every index checked against seq_cap; seq_len (nullable DEVICE int32 [1]) = o + out_n + 1,
+ * the drafter's len for the next draft, so that a draft can be queued behind the pass before the host has read out_n.
+ * The caller has made room for m + 1 rows at the offset (pie_decoder_set_kv / _set_paged_kv, block table filled).  4 launches (the gather and
+ * pie_spec_verify's three) beyond pie_decoder_prefill's; nothing is captured in a graph, and a decoder
+ * that never calls this entry launches exactly what it launches without it.
+ * Speculation here is greedy and raw.  PIE_E_STATE before any launch: a tensor-parallel decoder; a quantized or rotating KV cache; int8
+ * pages (PIE_OPT_KV_I8); any configured tail (sampler, repetition penalty, mask, bias, top-logprobs, counts) or prompt scoring.
+ * PIE_E_SHAPE before any launch: m + 1 below the many-row pass's first row count (PIE_KNOB_PREFILL_MIN, default 6: the rows would run as
+ * iterated steps -- the host runs a plain step instead) or above 32.  workspace: pie_decoder_spec_workspace_bytes(d, m + 1) bytes (0 for
+ * refused row counts), 16-byte aligned, caller-owned, no initialisation. */
+size_t pie_decoder_spec_workspace_bytes(const pie_decoder *d, int rows);
+int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                          int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -8,6 +8,6 @@ import os
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 from . import pie_core  # noqa: E402
-from .engine import InferenceEngine  # noqa: E402
+from .engine import InferenceEngine, SpeculativeParams  # noqa: E402
 
-__all__ = ["InferenceEngine", "pie_core"]
+__all__ = ["InferenceEngine", "SpeculativeParams", "pie_core"]

@@ -52,6 +52,7 @@ EXPORTS = [
     "pie_top_logprobs_workspace_bytes", "pie_top_logprobs", "pie_decoder_set_top_logprobs", "pie_decoder_set_batch_top_logprobs",
     "pie_logprobs_argmax_rows_masked", "pie_logits_bias_rows", "pie_decoder_set_batch_logits_edits",
     "pie_count_penalty_bytes", "pie_count_penalty_pack", "pie_logits_count_penalty_rows", "pie_decoder_set_count_penalty", "pie_decoder_set_batch_count_penalty",
+    "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
 ]
 
 
@@ -175,6 +176,15 @@ def load() -> C.CDLL:
     lib.pie_logits_count_penalty_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
     lib.pie_decoder_set_count_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_decoder_set_batch_count_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pie_ngram_draft_workspace_bytes.restype = C.c_size_t
+    lib.pie_ngram_draft_workspace_bytes.argtypes = []
+    lib.pie_ngram_draft.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4
+    lib.pie_spec_verify_workspace_bytes.restype = C.c_size_t
+    lib.pie_spec_verify_workspace_bytes.argtypes = [C.c_int]
+    lib.pie_spec_verify.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 6
+    lib.pie_decoder_spec_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_spec_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    lib.pie_decoder_spec_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

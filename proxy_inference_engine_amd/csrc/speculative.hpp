@@ -1,0 +1,30 @@
+// speculative.hpp -- pie_spec_verify's launches for callers inside the library (speculative.hip): pie_decoder_spec_step verifies the block
+// its many-row pass wrote and moves the decoder's device-side state to the accepted position.
+#pragma once
+#include "attention.hpp"  // DecState
+#include "common.hpp"
+
+constexpr int SPEC_MAX_ROWS = 32;   // rows of one verify pass: the fed token and up to 31 drafts
+constexpr int SPEC_MAX_NGRAM = 8;   // the drafter's longest suffix
+constexpr int SPEC_MAX_IDS = 1 << 27;  // the drafter's search key packs (match length, end position) into 32 bits
+
+// What the accept launch does besides the op's outputs when the block came from the decoder's own pass (all device memory; state == nullptr:
+// the op alone).  Before the launch state->pos = o + rows and the pass's tail has run; after it the decoder is where `n` greedy steps from
+// position o would have left it: pos = o + n, token = the last accepted token, history[o + 1 + i] = accepted token i.  seq_ids (nullable,
+// [seq_cap]) = the sequence's ids by position, made whole here: seq_ids[o] = fed[0] (the fed-back token of row 0) and seq_ids[o + 1 + i] =
+// accepted token i; seq_len (nullable) = o + n + 1, the drafter's `len` for the next draft.  token_out (nullable): the bound token output.
+struct SpecState {
+    DecState *state = nullptr;
+    int *history = nullptr;
+    int hist_cap = 0;
+    const int *fed = nullptr;
+    int *seq_ids = nullptr;
+    int seq_cap = 0;
+    int *seq_len = nullptr;
+    int *token_out = nullptr;
+};
+
+size_t spec_verify_workspace_bytes(int rows);
+// the op's three launches (arguments already checked)
+int spec_verify_launch(const u16 *logits, int rows, int V, int dtype, const int *draft, int *out_tokens, int *out_n, float *logprobs, void *workspace,
+                       const SpecState &s, hipStream_t st);

@@ -125,12 +125,10 @@ __device__ __forceinline__ float logits_merge_partials(const LogitStat *stats, i
     return M + logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
 }
 
+// Workgroup blockIdx.x of gridDim.x writes its slice of one row's log-probabilities, logprobs[i] = f32(logits[i]) - lse: the tail's finish and
+// the speculative verify's rows (speculative.hip) store the same bits through it.
 template <class T>
-__global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V, const LogitStat *stats, int n_stats, float *logprobs,
-                                                       int *token, DecState *state, int *history, int hist_cap, const unsigned *err_word) {
-    logits += (size_t)blockIdx.y * V, stats += (size_t)blockIdx.y * n_stats, logprobs += (size_t)blockIdx.y * V, token += blockIdx.y;  // batch row
-    int tok;
-    const float lse = logits_merge_partials(stats, n_stats, tok);  // every workgroup merges all partials
+__device__ __forceinline__ void logits_write_logprobs(const u16 *logits, int V, float lse, float *logprobs) {
     const int slice = (((V + gridDim.x - 1) / gridDim.x) + 7) & ~7;  // 8 logits per thread and pass
     const int begin = blockIdx.x * slice, end = min(V, begin + slice);
     for (int i = begin + threadIdx.x * 8; i < end; i += 256 * 8) {
@@ -144,6 +142,15 @@ __global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V,
             for (int k = i; k < min(i + 8, end); ++k) logprobs[k] = T::to_f32(logits[k]) - lse;
         }
     }
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_logits_finish(const u16 *logits, int V, const LogitStat *stats, int n_stats, float *logprobs,
+                                                       int *token, DecState *state, int *history, int hist_cap, const unsigned *err_word) {
+    logits += (size_t)blockIdx.y * V, stats += (size_t)blockIdx.y * n_stats, logprobs += (size_t)blockIdx.y * V, token += blockIdx.y;  // batch row
+    int tok;
+    const float lse = logits_merge_partials(stats, n_stats, tok);  // every workgroup merges all partials
+    logits_write_logprobs<T>(logits, V, lse, logprobs);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (err_word && *err_word != 0u) tok = -1;  // the persistent launch gave up a bounded wait (sticky): no plausible-looking id from garbage
         *token = tok;

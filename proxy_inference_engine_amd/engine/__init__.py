@@ -1,4 +1,4 @@
 from .batch_engine import BatchedEngine, SamplingParams
-from .inference_engine import InferenceEngine
+from .inference_engine import InferenceEngine, SpeculativeParams
 
-__all__ = ["InferenceEngine", "BatchedEngine", "SamplingParams"]
+__all__ = ["InferenceEngine", "BatchedEngine", "SamplingParams", "SpeculativeParams"]

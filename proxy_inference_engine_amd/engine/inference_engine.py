@@ -11,6 +11,7 @@ Array type: torch.Tensor on the ROCm device instead of mx.array.
 from __future__ import annotations
 
 from collections.abc import Callable, Generator, Iterator
+from dataclasses import dataclass
 
 import torch
 
@@ -104,6 +105,37 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
     return plan
 
 
+@dataclass(frozen=True)
+class SpeculativeParams:
+    """Greedy speculative decoding with prompt-lookup drafts (generate_step(speculative=...)): after every step or pass the
+    drafter looks the sequence's last ngram_max .. ngram_min ids up in the sequence itself and copies the num_draft ids behind the latest
+    occurrence of the longest suffix found; a draft of at least min_draft ids is verified in one many-row pass, anything shorter is one
+    plain replayed step.  The tokens are exactly greedy decoding's."""
+    num_draft: int = 7
+    ngram_max: int = 3
+    ngram_min: int = 1
+    min_draft: int = 5
+
+    def __post_init__(self):
+        if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= hip_ops.SPEC_MAX_NGRAM:
+            raise ValueError(f"SpeculativeParams: 1 <= ngram_min <= ngram_max <= {hip_ops.SPEC_MAX_NGRAM}")
+        if not 1 <= int(self.min_draft) <= int(self.num_draft) <= hip_ops.SPEC_MAX_ROWS - 1:
+            raise ValueError(f"SpeculativeParams: 1 <= min_draft <= num_draft <= {hip_ops.SPEC_MAX_ROWS - 1}")
+
+
+def check_speculative(model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size) -> None:
+    """What generate_step(speculative=...) refuses, each by name: speculation here is greedy and raw, on one sequence's 16-bit cache."""
+    for bad, name in ((not getattr(sampler, "is_greedy", False), "a non-greedy sampler (temp > 0)"), (bool(processors), "logits processors"),
+                      (structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
+                      (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"),
+                      (getattr(model, "tp", None) is not None, "a tensor-parallel model"),
+                      (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")):
+        if bad:
+            raise ValueError(f"speculative decoding is not available with {name}")
+    if not hasattr(model, "spec_step"):
+        raise ValueError("speculative decoding is not available with this model (no spec_step)")
+
+
 class InferenceEngine:
     """One model, one PromptCache, not re-entrant -- like the reference (server/app.py:23,35)."""
 
@@ -166,7 +198,8 @@ class InferenceEngine:
     # ------------------------------------------------------------------ the hot loop
     def generate_step(self, prompt_ids, pixel_values=None, mask=None, kv_bits: int | None = None, kv_group_size: int = 64,
                       quantized_kv_start: int = 0, max_kv_size: int | None = None,
-                      top_logprobs: int | None = None, prompt_logprobs: int | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
+                      top_logprobs: int | None = None, prompt_logprobs: int | None = None,
+                      speculative: SpeculativeParams | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
         """Yields (next_token_id[1] int32, logprobs[V] fp32) per step, forever (inference_engine.py:228-297).
         Prefill of the non-cached prompt suffix, then one forward per token; all device work is queued
         asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202).
@@ -182,8 +215,16 @@ class InferenceEngine:
         prompt_logprobs (None: off, else 0..20): the prompt's own tokens are scored inside the prompt pass (Model.set_prompt_logprobs;
         DESIGN.md 16) and `self.prompt_logprobs` holds their maps before the first yield -- entry 0 None, entry j the map of prompt token j
         under the raw model distribution: the best prompt_logprobs pairs, then the token itself when absent.  Such a request processes its
-        whole prompt: the prompt cache's common prefix is not reused for it."""
+        whole prompt: the prompt cache's common prefix is not reused for it.
+        speculative (None: exactly the path above): greedy speculative decoding -- each yield is then (tokens [m] int32,
+        logprobs [m, V] fp32), the m >= 1 tokens one verify pass accepted (or the one token of a plain step) with their rows'
+        log-probabilities, the same tokens the plain loop yields one by one; `self.spec_stats` counts passes, steps, drafted and accepted
+        ids.  With top_logprobs, `self.top_record` holds one record per yielded token ([m, n + 1]).  Greedy and raw only: a non-greedy
+        sampler, logits processors, a structuring engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs, a tensor-parallel model
+        and int8 KV pages are refused by name."""
         scored = prompt_logprobs is not None
+        if speculative is not None and scored:
+            raise ValueError("speculative decoding is not available with prompt_logprobs")
         if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
             raise ValueError(f"prompt_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
         if scored and getattr(self.model, "tp", None) is not None:
@@ -207,6 +248,9 @@ class InferenceEngine:
             raise TypeError("pixel_values need a VLM ensemble (models/intern/ensemble.py: Model) as the engine's model")
         if "root" not in self.samplers:
             self.prepare_engine(prompt_ids, temp=0)
+        if speculative is not None:
+            check_speculative(self.model, self.samplers["root"], [p for ps in self.logits_processors.values() for p in ps], self.structuring_engine,
+                              pixel_values, kv_bits, max_kv_size)
         dev = self.model.device
 
         def _inference(ids: torch.Tensor, fed_back: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
@@ -330,6 +374,9 @@ class InferenceEngine:
                     proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts may not: this request's start
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
+        if speculative is not None:
+            yield from self._speculative_steps(host_ids, speculative, top_logprobs)
+            return
         if scored and len(host_ids) > 1:
             lm = getattr(self.model, "language_model", self.model)
             bufs = lm.set_prompt_logprobs(len(host_ids), max(int(prompt_logprobs), 1))
@@ -351,6 +398,54 @@ class InferenceEngine:
                 next_token, logprobs = _inference(next_token, fed_back=True)   # :288
             yield next_token, logprobs
             step_count += 1
+
+    def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None):
+        """generate_step's loop under speculative decoding.  The prompt's suffix is one plain step; behind it, and behind every
+        later step or pass, ONE drafter launch is queued, and its count comes back in the read-back the loop pays anyway: the tokens
+        (Model.spec_read).  count >= min_draft (and enough rows for the many-row pass): a verify pass over count + 1 rows, whose accepted
+        tokens are the next yield; otherwise one replayed step.  prompt_cache.update receives the ids whose K / V rows the cache now holds:
+        the fed-back token and the accepted drafts."""
+        model, cache = self.model, self.prompt_cache.cache
+        if hasattr(model, "set_step_tail"):
+            model.set_step_tail()  # the documented greedy tail: the passes refuse anything else
+        drafter = (int(sp.ngram_max), int(sp.ngram_min), int(sp.num_draft))
+        floor = max(int(sp.min_draft), int(getattr(model, "spec_min_rows", 6)) - 1)
+        self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}
+        host_top: list = []
+
+        def record(tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
+            """One hip_ops.top_logprobs call over the yielded rows: record r = token r's."""
+            if top_logprobs is None:
+                return
+            n, m = max(int(top_logprobs), 1), rows.shape[0]
+            if not host_top:
+                host_top.append(hip_ops.top_logprobs_workspace(rows.device, hip_ops.SPEC_MAX_ROWS, rows.shape[1], n))
+            ids, vals = hip_ops.top_logprobs(rows, n, tokens=tokens_dev[:m].contiguous(), workspace=host_top[0])
+            self.top_record = (ids[:, :int(top_logprobs) + 1], vals[:, :int(top_logprobs) + 1])
+
+        ids = torch.tensor(host_ids, dtype=torch.int32)
+        _, logprobs, _ = model.step(ids, cache)
+        self.prompt_cache.update(ids)
+        model.draft(*drafter)
+        rows = logprobs[None]
+        while True:
+            tokens, count = model.spec_read()
+            record(model.spec_tokens, rows)
+            yield torch.tensor(tokens, dtype=torch.int32), rows
+            fed = tokens[-1]
+            if count >= floor:
+                _, n, rows = model.spec_step(model.spec_draft[:count], cache, then_draft=drafter)
+                accepted = model.spec_read()[0]
+                self.prompt_cache.update([fed] + accepted[:-1])
+                self.spec_stats["passes"] += 1
+                self.spec_stats["drafted"] += count
+                self.spec_stats["accepted"] += n - 1
+            else:
+                _, logprobs, _ = model.step(None, cache)
+                self.prompt_cache.update([fed])
+                model.draft(*drafter)
+                rows = logprobs[None]
+                self.spec_stats["steps"] += 1
 
     def score(self, prompt_ids, top_logprobs: int = 0, **kv) -> list:
         """The log-probabilities of a prompt's own tokens (`echo`, perplexity, ranking): runs the prompt only and returns a list as long as
@@ -386,18 +481,27 @@ class InferenceEngine:
             kv["top_logprobs"] = top_logprobs
         if inference_kwargs.get("prompt_logprobs") is not None:  # the prompt's maps are on `self.prompt_logprobs` before the first yield
             kv["prompt_logprobs"] = int(inference_kwargs["prompt_logprobs"])
+        if inference_kwargs.get("speculative") is not None:  # (a request without it passes nothing: exactly the plain loop)
+            kv["speculative"] = inference_kwargs["speculative"]
         for new_tokens, new_logprobs in self.generate_step(prompt_ids, **kv):
+            budget = max_completion_tokens - token_count if max_completion_tokens > 0 else new_tokens.numel()  # a pass may yield more than is left
             token_count += new_tokens.numel()
-            if collect_logprobs:
+            maps = None
+            if collect_logprobs and self.top_record[0].dim() == 2:
+                # a speculative pass: one read of its [m, n + 1] records, one map per accepted token
+                token_ids, maps = records_to_maps(*self.top_record, top_logprobs)
+            elif collect_logprobs:
                 # one read per token: the (n + 1)-pair record, whose slot 0 is the token itself
                 token_ids, logprobs_map = record_to_map(*self.top_record, top_logprobs)
             else:
                 token_ids = new_tokens.tolist()
             stopped = False
-            for token_id in token_ids:
+            for i, token_id in enumerate(token_ids[:budget]):
                 if token_id in self.stop_tokens:
                     stopped = True
                     break
+                if maps is not None:
+                    logprobs_map = maps[i]
                 yield token_id, logprobs_map
             if stopped:
                 # the reference `break`s only the inner loop and keeps generating (inference_engine.py:204-206);
@@ -419,6 +523,16 @@ def record_to_map(ids: torch.Tensor, vals: torch.Tensor, top_k: int) -> tuple[li
     words = torch.cat([ids.reshape(-1), vals.reshape(-1).view(torch.int32)]).cpu().numpy()
     m = ids.numel()
     return host_record_to_map(words[:m], words[m:].view(np.float32), top_k)
+
+
+def records_to_maps(ids: torch.Tensor, vals: torch.Tensor, top_k: int) -> tuple[list[int], list[dict[int, float]]]:
+    """record_to_map for the [m, n + 1] records of a speculative pass: ([token per row], [map per row]), one read-back for all rows."""
+    import numpy as np
+    m = ids.shape[0]
+    words = torch.cat([ids.reshape(-1), vals.reshape(-1).view(torch.int32)]).cpu().numpy()
+    h_ids, h_vals = words[:words.size // 2].reshape(m, -1), words[words.size // 2:].view(np.float32).reshape(m, -1)
+    rows = [host_record_to_map(h_ids[r], h_vals[r], top_k) for r in range(m)]
+    return [t[0][0] for t in rows], [t[1] for t in rows]
 
 
 def host_record_to_map(ids, vals, top_k: int) -> tuple[list[int], dict[int, float]]:

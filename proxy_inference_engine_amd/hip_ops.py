@@ -1046,6 +1046,80 @@ def prompt_logprobs(logits: torch.Tensor, n: int, targets: torch.Tensor | None =
     return ids, vals
 
 
+# ---------------------------------------------------------------- greedy speculative decoding (csrc/speculative.hip)
+SPEC_MAX_ROWS, SPEC_MAX_NGRAM = 32, 8
+
+
+def _int32_dev(t: torch.Tensor, n: int | None, who: str, name: str) -> None:
+    _dev(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{who}: {name} is a contiguous int32 device tensor" + ("" if n is None else f" of {n}"))
+
+
+def ngram_draft_workspace(device) -> torch.Tensor:
+    """pie_ngram_draft's workspace on `device`: uninitialised, nothing is carried from call to call."""
+    return torch.empty(int(_ffi.load().pie_ngram_draft_workspace_bytes()) // 4, dtype=torch.int32, device=device)
+
+
+def ngram_draft(ids: torch.Tensor, length: torch.Tensor, ngram_max: int, ngram_min: int, k: int, workspace: torch.Tensor | None = None,
+                out: tuple | None = None):
+    """The prompt-lookup drafter (pie_ngram_draft): ids int32 [cap] = the sequence so far (the last id the token about to be fed), length
+    device int32 [1], read on the device and clamped to [0, cap] -> (draft int32 [k], count int32 [1]), no host sync.  The suffix
+    ids[len - n : len] of the largest n in ngram_max .. ngram_min that occurs earlier (ending at len - 1 at the latest) is looked up at its
+    LATEST occurrence, and the k ids behind it are copied, the copy running on into its own output (a period-3 tail drafts k ids);
+    count = k, or 0 without a match -- out = (draft, count) to write into (a draft without a match keeps its contents), else fresh
+    tensors of -1 and 0.  1 <= ngram_min <= ngram_max <= 8, 1 <= k <= 31."""
+    who = "ngram_draft"
+    _int32_dev(ids, None, who, "ids"), _int32_dev(length, 1, who, "length")
+    if ids.numel() < 1:
+        raise ValueError("ngram_draft: ids holds at least one id")
+    ws = ngram_draft_workspace(ids.device) if workspace is None else workspace
+    if out is None:
+        out = (torch.full((max(int(k), 1),), -1, dtype=torch.int32, device=ids.device), torch.zeros(1, dtype=torch.int32, device=ids.device))
+    draft, count = out
+    _int32_dev(draft, None, who, "out[0]"), _int32_dev(count, 1, who, "out[1]"), _int32_dev(ws, None, who, "workspace")
+    if draft.numel() < int(k) or ws.numel() * 4 < int(_ffi.load().pie_ngram_draft_workspace_bytes()):
+        raise ValueError("ngram_draft: out[0] holds k ids and the workspace ngram_draft_workspace()'s size")
+    _ffi.check(_ffi.load().pie_ngram_draft(_ffi.p(ids), _ffi.p(length), ids.numel(), int(ngram_max), int(ngram_min), int(k), _ffi.p(draft), _ffi.p(count),
+                                           _ffi.p(ws), _ffi.stream()))
+    return draft, count
+
+
+def spec_verify_workspace(device, rows: int) -> torch.Tensor:
+    """pie_spec_verify's workspace for `rows` rows on `device`: uninitialised, nothing is carried from call to call."""
+    nbytes = int(_ffi.load().pie_spec_verify_workspace_bytes(int(rows)))
+    if nbytes == 0:
+        raise ValueError(f"spec_verify: 2 <= rows <= {SPEC_MAX_ROWS}, got {rows}")
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+
+
+def spec_verify(logits: torch.Tensor, draft: torch.Tensor, logprobs: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                out: tuple | None = None):
+    """The verify of a speculative pass (pie_spec_verify): logits bf16 / f16 [rows, V] (row 0 the fed token's, row i the i-th draft's),
+    draft int32 [rows - 1] -> (tokens int32 [rows], n int32 [1]), no host sync: the drafts are accepted while draft[i] equals row i's
+    greedy token (hip_ops.logprobs_argmax of that row, bit for bit; an id outside [0, V) is never accepted), n = accepted + 1, tokens =
+    the greedy tokens of rows 0 .. n - 1, then -1.  logprobs: fp32 [rows, V] to write rows 0 .. n - 1 into (logprobs_argmax's bits); the
+    rows behind them keep their contents.  out = (tokens, n) to write into.  rows 2..32."""
+    who = "spec_verify"
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError("spec_verify: contiguous bf16 / f16 [rows, V] logits")
+    rows, V = logits.shape
+    _int32_dev(draft, rows - 1, who, "draft")
+    if logprobs is not None:
+        _dev(logprobs)
+        if logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (rows, V) or not logprobs.is_contiguous():
+            raise ValueError("spec_verify: logprobs is a contiguous fp32 [rows, V] device tensor")
+    ws = spec_verify_workspace(logits.device, rows) if workspace is None else workspace
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
+    tokens, n = out
+    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
+    _ffi.check(_ffi.load().pie_spec_verify(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(draft), _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs),
+                                           _ffi.p(ws), _ffi.stream()))
+    return tokens, n
+
+
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)
 def kv_ring_order(keys: torch.Tensor, values: torch.Tensor, keep: int, n: int, shift: int, n_dst: int) -> None:
     """In place on RotatingKVCache buffers [1, H, cap, D]: rows keep + j <- rows keep + (j + shift) % n for j < n_dst."""

@@ -306,7 +306,8 @@ class Model(RowsTailState):
         # frequency / presence penalties: the step's record + counts at stable addresses, made when first used; (freq, pres,
         # start) while switched on.
         self._cnt, self._cnt_rec, self._cnt_counts = None, None, None
-        self._init_rows_state()   # the multi-sequence passes' per-row tail state (rows_state.py)
+        self._spec = None   # speculative decoding's record and workspaces, made when first used
+        self._init_rows_state()  # the multi-sequence passes' per-row tail state (rows_state.py)
         torch.cuda.synchronize(device)
 
     def __del__(self):
@@ -672,6 +673,117 @@ class Model(RowsTailState):
         pos = self._kv.offset  # position the chosen token will occupy
         token = self.history[pos:pos + 1] if pos < self.history.numel() else self.token.clone()
         return token, self.logprobs, self.logits
+
+    # ------------------------------------------------------------------ greedy speculative decoding
+    # One int32 record at a stable address carries everything the host reads per pass, in one copy:
+    #   [0] n | [1:33] the pass's tokens (n of them, then -1) | [33] the next draft's count | [34:65] the next draft | [65] the drafter's len
+    _SPEC_N, _SPEC_TOK, _SPEC_COUNT, _SPEC_DRAFT, _SPEC_LEN, _SPEC_WORDS = 0, 1, 33, 34, 65, 66
+
+    def _spec_state(self) -> dict:
+        """The record, the pass's workspace and log-probability rows, the drafter's workspace: made when first used."""
+        if self._spec is None:
+            nbytes = int(_ffi.load().pie_decoder_spec_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
+            self._spec = {"rec": torch.zeros(self._SPEC_WORDS, dtype=torch.int32, device=self.device),
+                          "ws": torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device),
+                          "logprobs": torch.empty((hip_ops.SPEC_MAX_ROWS, self.vocab_out), dtype=torch.float32, device=self.device),
+                          "draft_ws": hip_ops.ngram_draft_workspace(self.device), "host": None}
+        return self._spec
+
+    @property
+    def spec_min_rows(self) -> int:
+        """The fewest rows (drafts + 1) a speculative pass takes: below it the many-row pass would run as iterated steps."""
+        v = int(_ffi.load().pie_get_knob(_ffi.KNOBS["prefill_min"]))
+        return 6 if v < 0 else max(v, 2)
+
+    @property
+    def spec_draft(self) -> torch.Tensor:
+        """Device int32 [31]: the ids the last drafter launch left (`draft`, or `spec_step(then_draft=...)`); spec_read() tells how many."""
+        return self._spec_state()["rec"][self._SPEC_DRAFT:self._SPEC_LEN]
+
+    @property
+    def spec_tokens(self) -> torch.Tensor:
+        """Device int32 [32]: the tokens of the last pass (or, after `draft`, the one token it drafted behind), then -1."""
+        return self._spec_state()["rec"][self._SPEC_TOK:self._SPEC_COUNT]
+
+    def spec_read(self) -> tuple[list[int], int]:
+        """(the tokens of the last pass or step, the count of the draft made behind them): ONE read-back of the record, kept until the
+        next launch that writes it."""
+        sp = self._spec_state()
+        if sp["host"] is None:
+            sp["host"] = sp["rec"].cpu().numpy()
+        h = sp["host"]
+        n = int(h[self._SPEC_N])
+        return [int(t) for t in h[self._SPEC_TOK:self._SPEC_TOK + n]], int(h[self._SPEC_COUNT])
+
+    def _check_speculative(self, who: str, cache) -> None:
+        if self.tp is not None:
+            raise ValueError(f"{who}: not available on a tensor-parallel model")
+        if on_int8_pages(cache):
+            raise ValueError(f"{who}: not available on int8 KV pages")
+        if not isinstance(cache[0], (ReusableKVCache, PagedKVCache)):
+            raise ValueError(f"{who}: runs on ReusableKVCache or 16-bit PagedKVCache, not on {type(cache[0]).__name__}")
+        if self._tail[:2] != (None, None) or self._edits != (False, 0) or self._top_n is not None or self._cnt is not None:
+            raise ValueError(f"{who}: speculation is greedy and raw -- set_step_tail() with its defaults first "
+                             "(no sampler, repetition penalty, token mask, logit bias, top_logprobs or frequency / presence penalty)")
+
+    def _queue_draft(self, ngram_max: int, ngram_min: int, k: int) -> None:
+        sp = self._spec_state()
+        rec = sp["rec"]
+        sp["host"] = None
+        hip_ops.ngram_draft(self.fed_ids, rec[self._SPEC_LEN:self._SPEC_LEN + 1], ngram_max, ngram_min, k, workspace=sp["draft_ws"],
+                            out=(rec[self._SPEC_DRAFT:self._SPEC_LEN], rec[self._SPEC_COUNT:self._SPEC_COUNT + 1]))
+
+    def draft(self, ngram_max: int = 3, ngram_min: int = 1, k: int = 7):
+        """The prompt-lookup drafter over the sequence of the cache last stepped (hip_ops.ngram_draft): its ids are `fed_ids` up to the
+        position the last chosen token will occupy, which is copied in from `history` on the device -- a fed-back token never visits the
+        host.  Queued behind the step, no host sync; returns (spec_draft, count [1]) as device views, and spec_read() then gives
+        ([the last chosen token], count) in one read-back."""
+        pos = self._kv.offset
+        if pos is None or not 0 < pos < self.fed_ids.numel():
+            raise ValueError("draft: step a prompt first (and stay inside the model's id history)")
+        rec = self._spec_state()["rec"]
+        self.fed_ids[pos:pos + 1].copy_(self.history[pos:pos + 1])
+        rec[self._SPEC_TOK:self._SPEC_TOK + 1].copy_(self.history[pos:pos + 1])
+        rec[self._SPEC_N:self._SPEC_N + 1].fill_(1)
+        rec[self._SPEC_LEN:self._SPEC_LEN + 1].fill_(pos + 1)
+        self._queue_draft(ngram_max, ngram_min, k)
+        return self.spec_draft, rec[self._SPEC_COUNT:self._SPEC_COUNT + 1]
+
+    def spec_step(self, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None = None):
+        """One speculative pass (pie_decoder_spec_step): the previous call's token and the m ids of `draft_ids` (device int32) go through
+        the many-row pass at once, and the drafts are accepted while each equals the greedy token of the row before it.  Returns
+        (tokens int32 [n] device view, n, logprobs fp32 [n, V] device view): the n = accepted + 1 tokens greedy decoding would have
+        produced and their rows' log-probabilities, valid until the next call; the model, the cache (offset + n) and `fed_ids` are
+        then exactly where n calls of step(None) would have left them, so step(None) right after feeds back the last accepted token.
+        then_draft = (ngram_max, ngram_min, k): the next draft is queued behind the pass before the host reads n -- the pass costs ONE
+        read-back (spec_read() returns it without another).  m + 1 rows: spec_min_rows .. 32.  Contiguous and 16-bit paged caches; the
+        greedy raw tail only.  Pages taken for rejected rows stay with the sequence."""
+        who = "spec_step"
+        self._check_speculative(who, cache)
+        draft_ids = draft_ids.reshape(-1)
+        if not draft_ids.is_cuda or draft_ids.dtype != torch.int32 or not draft_ids.is_contiguous():
+            raise ValueError(f"{who}: draft_ids is a contiguous int32 device tensor")
+        m = draft_ids.numel()
+        if not self.spec_min_rows <= m + 1 <= hip_ops.SPEC_MAX_ROWS:
+            raise ValueError(f"{who}: {m} drafts make {m + 1} rows, outside {self.spec_min_rows}..{hip_ops.SPEC_MAX_ROWS} (run a plain step below)")
+        sp = self._spec_state()
+        rec = sp["rec"]
+        self._kv.sync(cache, m + 1)
+        if self._kv.offset + m + 1 > self.fed_ids.numel():
+            raise ValueError(f"{who}: the pass would run past the model's id history")
+        sp["host"] = None
+        _ffi.check(_ffi.load().pie_decoder_spec_step(self._dec, _ffi.p(draft_ids), m, _ffi.p(rec[self._SPEC_TOK:]), _ffi.p(rec[self._SPEC_N:]),
+                                                     _ffi.p(sp["logprobs"]), _ffi.p(sp["ws"]), _ffi.p(self.fed_ids), self.fed_ids.numel(),
+                                                     _ffi.p(rec[self._SPEC_LEN:]), _ffi.stream()))
+        if then_draft is not None:
+            self._queue_draft(*then_draft)
+        n = len(self.spec_read()[0])  # the one read-back
+        self._kv.advance(cache, n)    # the rejected rows stay behind the offset and are overwritten
+        return rec[self._SPEC_TOK:self._SPEC_TOK + n], n, sp["logprobs"][:n]
+
+    def spec_logits(self, rows: int) -> torch.Tensor:
+        """The raw logits block [rows, V] of the last spec_step (a view of its workspace, valid until the next one)."""
+        return self._spec_state()["ws"].view(self.dtype)[:rows * self.vocab_out].view(rows, self.vocab_out)
 
     def step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], graph: bool = True):
         """One decode step for several sequences at once (continuous batching over the page pool; pie_decoder_step_batch):
