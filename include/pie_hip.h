@@ -337,6 +337,53 @@ int pie_count_penalty_pack(double freq, double pres, int start, int counted_pos,
 int pie_logits_count_penalty_rows(void *logits, int rows, int V, int dtype, pie_count_penalty *records, int32_t *counts, const int32_t *ids,
                                   const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream);
 
+/* ---------------------------------------------------------------- DRY penalty
+ * DRY ("don't repeat yourself"), the sequence-repetition penalty of text-generation-webui, llama.cpp, koboldcpp and exllama: only the token
+ * that would extend a verbatim repeat of the sequence's tail is penalised, exponentially in the length of that repeat.
+ * PARAMETERS  multiplier: finite, >= 0; exactly 0 means off and the row keeps every bit.  base: finite, > 0.  allowed_length: 1..64.
+ *   range: 1..1024 window positions.  breakers: up to PIE_DRY_BREAKERS_MAX token ids ("sequence breakers"; the caller passes ids).
+ * WINDOW  c[0..n) are the ids at positions max(0, pos + 1 - range) .. pos, pos = the position of the row's input id, so c[n-1] is the input
+ *   id; the token about to be chosen is not in the window (the repetition penalty's window rule).
+ * No penalty if n < 2 or c[n-1] is a breaker.
+ * CANDIDATES  every i in 0 .. n-2 with c[i] == c[n-1].  Let t = c[i+1].  Position i is skipped if t is a breaker or lies outside [0, V);
+ *   such a t is never used as an index.
+ * MATCH LENGTH  L_i is the largest L with 1 <= L <= min(i + 1, PIE_DRY_MAX_MATCH) such that for every 1 <= m < L: c[i-m] == c[n-1-m], and
+ *   c[n-1-m] is not a breaker.  The two runs may overlap, so a period-3 tail matches to the cap.  A match never reaches before the window's
+ *   first position.
+ * PENALTY  M[t] = max L_i over the positions i with c[i+1] == t.  For every t with M[t] >= allowed_length: p = f32(multiplier), then
+ *   p = p * f32(base) exactly M[t] - allowed_length times, each one fp32 round-to-nearest multiplication (no powf, no fma); then
+ *   x'[t] = T( f32(x[t]) - p ): one fp32 subtraction and one rounding to T.  Every other element keeps its stored bits and is not rewritten.
+ *   -inf stays -inf; infinities, NaN and f16 overflow follow IEEE, as for the count penalties.
+ * ORDER inside a tail: (1) token mask (physically last: a masked id stays -inf), (2) repetition penalty, (3) logit_bias, (4) frequency /
+ *   presence, (5) DRY; then the unchanged log-softmax + argmax, the sampler and the top-n record.
+ * DETERMINISM  M[t] is a maximum: among the candidates of one id the one with the larger L, then the lower i, owns the id (decided through
+ *   LDS) and does the one read-modify-write; nothing depends on arrival order.  One workgroup of 1024 threads per logit vector, one thread
+ *   per window position; breaker membership is computed once per window position.
+ * pie_dry_penalty is one row's record; pie_dry_penalty_pack fills it in HOST memory under the parameter rules above (n_breakers
+ *   0..PIE_DRY_BREAKERS_MAX), PIE_E_ARG otherwise; nothing touches a device.  The kernels do not trust the bytes they read: allowed_length
+ *   is clamped to 1..64, range to 1..1024, n_breakers to 0..64; multiplier and base only enter arithmetic.
+ * pie_logits_dry_penalty: logits [V] T in place, the window is ids[0..n) (DEVICE int32, n 1..1024, ids[n-1] = the input id; the range is
+ *   n), breakers DEVICE int32 [n_breakers] (may be NULL when n_breakers == 0).  One launch.
+ * pie_logits_dry_penalty_rows: logits [rows, V] T in place, one launch, one workgroup per row.  Row s reads source row i = out_rows ?
+ *   out_rows[s] : s of ids / ctx [n_src] (pie_logits_penalty_rows' rule): its input id ids[i] sits at position pos = ctx[i] - 1; pos < 0
+ *   (an idle slot) or i outside [0, n_src): the row is skipped.  Every live row first records its input id in its ring
+ *   recent_ids[s][pos & 1023] -- a zero record too -- then takes its window from the ring.  records DEVICE [rows], breakers DEVICE int32
+ *   [rows, PIE_DRY_BREAKERS_MAX], recent_ids DEVICE int32 [rows, 1024].
+ * A null pointer, an argument outside the parameter rules, n outside 1..1024, a dtype other than PIE_BF16 / PIE_F16: PIE_E_ARG; V < 1, rows
+ *   outside 1..65535, n_src < 1, fewer source rows than rows without out_rows: PIE_E_SHAPE; an int32 array or the records not 4-byte
+ *   aligned, logits not 2-byte aligned: PIE_E_ALIGN -- each before any launch. */
+enum { PIE_DRY_MAX_MATCH = 64, PIE_DRY_BREAKERS_MAX = 64 };
+typedef struct pie_dry_penalty {
+    float multiplier, base;
+    int32_t allowed_length, range, n_breakers, reserved;
+} pie_dry_penalty;
+size_t pie_dry_penalty_bytes(void); /* sizeof(pie_dry_penalty) = 24, for bindings */
+int pie_dry_penalty_pack(double multiplier, double base, int allowed_length, int range, int n_breakers, pie_dry_penalty *out);
+int pie_logits_dry_penalty(void *logits, int V, int dtype, const int32_t *ids, int n, double multiplier, double base, int allowed_length,
+                           const int32_t *breakers, int n_breakers, void *stream);
+int pie_logits_dry_penalty_rows(void *logits, int rows, int V, int dtype, const pie_dry_penalty *records, const int32_t *breakers,
+                                int32_t *recent_ids, const int32_t *ids, const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream);
+
 /* ---------------------------------------------------------------- top-n log-probabilities
  * get_top_logprobs (engine/utils.py:4-48) on the device, sort-free: for every row of fp32 log-probabilities [rows, V] the n best
  * (id, value) pairs and the chosen token's own, n 1..PIE_TOP_LOGPROBS_MAX.  tokens (nullable) DEVICE int32 [rows]; count (nullable)
@@ -687,6 +734,27 @@ int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint3
  * With neither set every pass launches exactly what it launches without.  Tensor-parallel decoders refuse both (PIE_E_STATE). */
 int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int32_t *counts);
 int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *records, int32_t *counts, int rows_cap);
+/* The DRY penalty inside the passes: the op's kernels as step (5) of a tail, behind the count penalties and in front of the
+ * log-softmax, whose partials are recomputed from the processed logits as after every other edit (in the fused few-sequence step too).
+ * One more launch per pass, plus the partials launch where nothing else had made them stale already.
+ * pie_decoder_set_dry_penalty: the single-sequence tail, wherever the configured tail applies (pie_decoder_step with PIE_STEP_LOGITS, eager
+ *   or PIE_STEP_GRAPH; the last row of pie_decoder_prefill / _prefill_embeds with logits_all == NULL -- with logits_all != NULL the logits
+ *   stay raw), on every KV binding.  record: DEVICE pie_dry_penalty; breakers: DEVICE int32 [PIE_DRY_BREAKERS_MAX]; ids_by_pos: DEVICE int32
+ *   [ids_cap], the id fed at every position (pie_decoder_set_logits_penalty's; a step records its input token there first, and every index
+ *   is checked against ids_cap).  All caller-owned and alive while set; their CONTENTS may change between steps in stream order while a
+ *   captured graph keeps replaying; the addresses and ids_cap are launch arguments: setting, clearing or moving them drops the captured
+ *   graphs.  record == NULL switches it off.  A null breakers or ids_by_pos with a record, ids_cap < 1: PIE_E_ARG; misaligned (4 bytes):
+ *   PIE_E_ALIGN.
+ * pie_decoder_set_batch_dry_penalty: pie_decoder_step_batch (eager or PIE_STEP_GRAPH), _prefill_batch and _step_mixed; record s, breakers
+ *   row s and ring s belong to output row s, with the pass's own ids / context lengths / output rows as the op's.  records DEVICE [rows_cap],
+ *   breakers DEVICE int32 [rows_cap, PIE_DRY_BREAKERS_MAX], recent_ids DEVICE int32 [rows_cap, 1024]: a ring of its own, so the setter is
+ *   independent of the batch tail, the batch edits, the batch counts and the batch top-n setters; the addresses and rows_cap are part of the
+ *   captured batch graph's key.  records == NULL switches it off.  rows_cap < 1, a null array: PIE_E_ARG; misaligned: PIE_E_ALIGN; a pass
+ *   with more output rows than rows_cap: PIE_E_SHAPE before any launch.
+ * With neither set every pass launches exactly what it launches without.  Tensor-parallel decoders refuse both (PIE_E_STATE), and
+ * pie_decoder_spec_step refuses a configured DRY penalty like every other tail. */
+int pie_decoder_set_dry_penalty(pie_decoder *d, const pie_dry_penalty *record, const int32_t *breakers, int32_t *ids_by_pos, int ids_cap);
+int pie_decoder_set_batch_dry_penalty(pie_decoder *d, const pie_dry_penalty *records, const int32_t *breakers, int32_t *recent_ids, int rows_cap);
 /* One speculative pass of the single-sequence decoder: m = n_draft drafted ids (draft_ids DEVICE int32 [m]) are verified in one
  * pass over the weights.  In order: (1) rows [the device-side token, draft_0 .. draft_{m - 1}] are gathered on the device (a draft id the
  * embedding could not index is fed as id 0; pie_spec_verify never accepts it) and forwarded from the device-side offset through

@@ -52,6 +52,7 @@ EXPORTS = [
     "pie_top_logprobs_workspace_bytes", "pie_top_logprobs", "pie_decoder_set_top_logprobs", "pie_decoder_set_batch_top_logprobs",
     "pie_logprobs_argmax_rows_masked", "pie_logits_bias_rows", "pie_decoder_set_batch_logits_edits",
     "pie_count_penalty_bytes", "pie_count_penalty_pack", "pie_logits_count_penalty_rows", "pie_decoder_set_count_penalty", "pie_decoder_set_batch_count_penalty",
+    "pie_dry_penalty_bytes", "pie_dry_penalty_pack", "pie_logits_dry_penalty", "pie_logits_dry_penalty_rows", "pie_decoder_set_dry_penalty", "pie_decoder_set_batch_dry_penalty",
     "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
 ]
 
@@ -85,6 +86,12 @@ class pie_row_tail(C.Structure):
 class pie_count_penalty(C.Structure):
     """One output row's frequency / presence penalties and counting state in device memory (include/pie_hip.h)."""
     _fields_ = [("freq", C.c_float), ("pres", C.c_float), ("start", C.c_int32), ("counted_pos", C.c_int32)]
+
+
+class pie_dry_penalty(C.Structure):
+    """One output row's DRY penalty parameters in device memory (include/pie_hip.h)."""
+    _fields_ = [("multiplier", C.c_float), ("base", C.c_float), ("allowed_length", C.c_int32), ("range", C.c_int32), ("n_breakers", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 def set_knob(name: str, value: int | None) -> None:
@@ -176,6 +183,13 @@ def load() -> C.CDLL:
     lib.pie_logits_count_penalty_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
     lib.pie_decoder_set_count_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_decoder_set_batch_count_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pie_dry_penalty_bytes.restype = C.c_size_t
+    lib.pie_dry_penalty_bytes.argtypes = []
+    lib.pie_dry_penalty_pack.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(pie_dry_penalty)]
+    lib.pie_logits_dry_penalty.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.pie_logits_dry_penalty_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+    lib.pie_decoder_set_dry_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pie_decoder_set_batch_dry_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.pie_ngram_draft_workspace_bytes.restype = C.c_size_t
     lib.pie_ngram_draft_workspace_bytes.argtypes = []
     lib.pie_ngram_draft.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4

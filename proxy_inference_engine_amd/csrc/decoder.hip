@@ -156,8 +156,8 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
     return a;
 }
 
-// The configured tail over the bound outputs (include/pie_hip.h), in batch_tail_launch's five stages (prefill.hip): edit -- penalty and / or
-// bias, one launch | count penalty -- frequency / presence, one launch | fresh partials, which apply the token mask on their way | finish |
+// The configured tail over the bound outputs (include/pie_hip.h), in batch_tail_launch's six stages (prefill.hip): edit -- penalty and / or
+// bias, one launch | count penalty -- frequency / presence, one launch | DRY, one launch | fresh partials, which apply the token mask on their way | finish |
 // the sampler's launches and the top-n log-probabilities' two.
 // from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
 static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
@@ -176,7 +176,13 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
         k.logits = d->logits, k.V = c.vocab, k.records = d->cp_record, k.counts = d->cp_counts, k.state = d->state, k.count = from_state;
         if ((rc = logits_count_penalty_rows_launch(c.dtype, k, 1, st))) return rc;
     }
-    if (d->pen != 1.0 || d->bias_n || d->tok_mask || d->cp_record) {  // partials: the lm_head epilogue's are stale
+    if (d->dry_record) {  // DRY: behind the count penalty; a step records its input token before it reads its window
+        DryArgs k = {};
+        k.w.logits = d->logits, k.w.V = c.vocab, k.w.ids_by_pos = d->dry_ids_by_pos, k.w.ids_cap = d->dry_ids_cap, k.w.state = d->state, k.w.record = from_state;
+        k.record = d->dry_record, k.breakers = d->dry_breakers;
+        if ((rc = logits_dry_launch(c.dtype, k, st))) return rc;
+    }
+    if (d->pen != 1.0 || d->bias_n || d->tok_mask || d->cp_record || d->dry_record) {  // partials: the lm_head epilogue's are stale
         if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st, d->tok_mask))) return rc;
         stats = d->tail_stats, n_stats = TAIL_STAT_TILES;
     }
@@ -971,6 +977,32 @@ int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int
     }
     if (d->cp_record != record || d->cp_counts != counts) drop_graphs(d);  // both are launch arguments (what they point at is read by every launch)
     d->cp_record = record, d->cp_counts = counts;
+    return PIE_OK;
+}
+
+int pie_decoder_set_dry_penalty(pie_decoder *d, const pie_dry_penalty *record, const int32_t *breakers, int32_t *ids_by_pos, int ids_cap) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_dry_penalty: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_dry_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (!record) breakers = nullptr, ids_by_pos = nullptr, ids_cap = 0;
+    else {
+        PIE_REQUIRE(breakers && ids_by_pos && ids_cap >= 1, PIE_E_ARG, "pie_decoder_set_dry_penalty: a record needs its breakers and ids_by_pos [ids_cap >= 1]");
+        PIE_REQUIRE(pie_aligned(record, 4) && pie_aligned(breakers, 4) && pie_aligned(ids_by_pos, 4), PIE_E_ALIGN,
+                    "pie_decoder_set_dry_penalty: the record, the breakers and ids_by_pos need 4-byte alignment");
+        if (int rc = tail_stats_alloc(d)) return rc;
+    }
+    if (d->dry_record != record || d->dry_breakers != breakers || d->dry_ids_by_pos != ids_by_pos || d->dry_ids_cap != ids_cap) drop_graphs(d);  // all launch arguments
+    d->dry_record = record, d->dry_breakers = breakers, d->dry_ids_by_pos = ids_by_pos, d->dry_ids_cap = ids_cap;
+    return PIE_OK;
+}
+
+int pie_decoder_set_batch_dry_penalty(pie_decoder *d, const pie_dry_penalty *records, const int32_t *breakers, int32_t *recent_ids, int rows_cap) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_dry_penalty: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_dry_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (!records) return d->rows.dry = {}, PIE_OK;  // off
+    PIE_REQUIRE(breakers && recent_ids && rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_dry_penalty: the records need their breakers, their rings and rows_cap >= 1");
+    PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(breakers, 4) && pie_aligned(recent_ids, 4), PIE_E_ALIGN,
+                "pie_decoder_set_batch_dry_penalty: the records, the breakers and the rings need 4-byte alignment");
+    d->rows.dry = {records, breakers, recent_ids, rows_cap};  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 

@@ -47,13 +47,20 @@ struct RowsTail {
         int *counts = nullptr;                 // [rows_cap, vocab]
         int rows_cap = 0;
     } counts;
+    struct Dry {  // pie_decoder_set_batch_dry_penalty: per-row DRY records, breaker tables and rings of fed ids (its own rings)
+        const pie_dry_penalty *records = nullptr;  // [rows_cap], nullptr: off
+        const int *breakers = nullptr;             // [rows_cap, PIE_DRY_BREAKERS_MAX]
+        int *recent = nullptr;                     // [rows_cap, 1024]
+        int rows_cap = 0;
+    } dry;
     // everything a captured batch graph bakes in (pie_decoder_step_batch's key): a setter drops no graph, a changed key captures a new one
     void key(std::vector<uintptr_t> &k) const {
         for (uintptr_t v : {(uintptr_t)sampler.table, (uintptr_t)sampler.recent, (uintptr_t)sampler.ws, (uintptr_t)sampler.rows_cap,
                             (uintptr_t)top.n, (uintptr_t)top.rows_cap, (uintptr_t)top.ids, (uintptr_t)top.vals, (uintptr_t)top.count, (uintptr_t)top.ws,
                             (uintptr_t)edits.rows_cap, (uintptr_t)edits.masks, (uintptr_t)edits.mask_words, (uintptr_t)edits.mask_on, (uintptr_t)edits.bias_ids,
                             (uintptr_t)edits.bias_vals, (uintptr_t)edits.bias_n, (uintptr_t)edits.bias_cap,
-                            (uintptr_t)counts.records, (uintptr_t)counts.counts, (uintptr_t)counts.rows_cap})
+                            (uintptr_t)counts.records, (uintptr_t)counts.counts, (uintptr_t)counts.rows_cap,
+                            (uintptr_t)dry.records, (uintptr_t)dry.breakers, (uintptr_t)dry.recent, (uintptr_t)dry.rows_cap})
             k.push_back(v);
     }
     // a pass with `out_rows` output rows fits every configured part (checked before any launch)
@@ -61,11 +68,12 @@ struct RowsTail {
         const char *over = sampler.table && out_rows > sampler.rows_cap   ? "batch tail"
                            : edits.rows_cap && out_rows > edits.rows_cap  ? "batch logits edits"
                            : top.n && out_rows > top.rows_cap             ? "top log-probabilities"
-                           : counts.records && out_rows > counts.rows_cap ? "batch count penalty" : nullptr;
+                           : counts.records && out_rows > counts.rows_cap ? "batch count penalty"
+                           : dry.records && out_rows > dry.rows_cap       ? "batch DRY penalty" : nullptr;
         return over ? pie::fail(PIE_E_SHAPE, std::string(entry) + ": more output rows than the " + over + "'s rows_cap") : PIE_OK;
     }
     // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale
-    bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records; }
+    bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records || dry.records; }
 };
 
 // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): the prompt passes score their rows in blocks of at most
@@ -172,11 +180,17 @@ struct pie_decoder {
     // counts whose CONTENTS change between steps; launch arguments of the step's tail.
     pie_count_penalty *cp_record = nullptr;  // nullptr: off
     int *cp_counts = nullptr;                // [vocab]
+    // The DRY penalty of the single-sequence step (pie_decoder_set_dry_penalty): a caller-owned record, breaker table and
+    // ids by position whose CONTENTS change between steps; launch arguments of the step's tail.
+    const pie_dry_penalty *dry_record = nullptr;  // nullptr: off
+    const int *dry_breakers = nullptr;            // [PIE_DRY_BREAKERS_MAX]
+    int *dry_ids_by_pos = nullptr;                // [dry_ids_cap]
+    int dry_ids_cap = 0;
     RowsTail rows;        // the multi-sequence passes' per-row tail state
     PromptScores prompt;  // the prompt passes' log-probabilities of prompt tokens
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
-    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n || cp_record; }
+    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n || cp_record || dry_record; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)

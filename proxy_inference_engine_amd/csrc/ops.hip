@@ -445,4 +445,50 @@ int pie_logits_count_penalty_rows(void *logits, int rows, int V, int dtype, pie_
     return logits_count_penalty_rows_launch(dtype, a, rows, (hipStream_t)stream);
 }
 
+size_t pie_dry_penalty_bytes(void) { return sizeof(pie_dry_penalty); }
+
+int pie_dry_penalty_pack(double multiplier, double base, int allowed_length, int range, int n_breakers, pie_dry_penalty *out) {
+    PIE_REQUIRE(out, PIE_E_ARG, "pie_dry_penalty_pack: null pointer");
+    PIE_REQUIRE(std::isfinite(multiplier) && std::isfinite((float)multiplier) && multiplier >= 0.0, PIE_E_ARG,
+                "pie_dry_penalty_pack: the multiplier must be finite and non-negative");
+    PIE_REQUIRE(std::isfinite(base) && std::isfinite((float)base) && (float)base > 0.0f, PIE_E_ARG, "pie_dry_penalty_pack: the base must be finite and positive");
+    PIE_REQUIRE(allowed_length >= 1 && allowed_length <= PIE_DRY_MAX_MATCH, PIE_E_ARG, "pie_dry_penalty_pack: 1 <= allowed_length <= 64");
+    PIE_REQUIRE(range >= 1 && range <= PEN_MAX_IDS, PIE_E_ARG, "pie_dry_penalty_pack: 1 <= range <= 1024 window positions");
+    PIE_REQUIRE(n_breakers >= 0 && n_breakers <= PIE_DRY_BREAKERS_MAX, PIE_E_ARG, "pie_dry_penalty_pack: 0 <= n_breakers <= 64");
+    pie_dry_penalty r = {};
+    r.multiplier = (float)multiplier, r.base = (float)base, r.allowed_length = allowed_length, r.range = range, r.n_breakers = n_breakers;
+    *out = r;
+    return PIE_OK;
+}
+
+int pie_logits_dry_penalty(void *logits, int V, int dtype, const int32_t *ids, int n, double multiplier, double base, int allowed_length,
+                           const int32_t *breakers, int n_breakers, void *stream) {
+    PIE_REQUIRE(logits && ids && (breakers || n_breakers == 0), PIE_E_ARG, "pie_logits_dry_penalty: null pointer");
+    PIE_REQUIRE(n >= 1 && n <= PEN_MAX_IDS, PIE_E_ARG, "pie_logits_dry_penalty: 1 <= n <= 1024 ids");
+    DryArgs a = {};
+    if (pie_dry_penalty_pack(multiplier, base, allowed_length, n, n_breakers, &a.value)) return PIE_E_ARG;  // (the message names the rule)
+    PIE_REQUIRE(V >= 1, PIE_E_SHAPE, "pie_logits_dry_penalty: empty vocabulary");
+    PIE_REQUIRE(pie_aligned(ids, 4) && pie_aligned(breakers, 4) && pie_aligned(logits, 2), PIE_E_ALIGN,
+                "pie_logits_dry_penalty: ids and breakers need 4-byte alignment, logits 2-byte");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_logits_dry_penalty: dtype must be PIE_BF16 or PIE_F16");
+    a.w.logits = (u16 *)logits, a.w.V = V, a.w.ids = ids, a.w.n = n, a.breakers = breakers;
+    return logits_dry_launch(dtype, a, (hipStream_t)stream);
+}
+
+int pie_logits_dry_penalty_rows(void *logits, int rows, int V, int dtype, const pie_dry_penalty *records, const int32_t *breakers,
+                                int32_t *recent_ids, const int32_t *ids, const int32_t *ctx, const int32_t *out_rows, int n_src, void *stream) {
+    PIE_REQUIRE(logits && records && breakers && recent_ids && ids && ctx, PIE_E_ARG, "pie_logits_dry_penalty_rows: null pointer");
+    PIE_REQUIRE(rows >= 1, PIE_E_ARG, "pie_logits_dry_penalty_rows: rows >= 1");
+    PIE_REQUIRE(rows <= 65535 && n_src >= 1 && V >= 1, PIE_E_SHAPE, "pie_logits_dry_penalty_rows: rows <= 65535, n_src >= 1, V >= 1");
+    PIE_REQUIRE(out_rows || n_src >= rows, PIE_E_SHAPE, "pie_logits_dry_penalty_rows: without out_rows every output row needs its source row");
+    PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(breakers, 4) && pie_aligned(recent_ids, 4) && pie_aligned(ids, 4) && pie_aligned(ctx, 4) &&
+                    pie_aligned(out_rows, 4) && pie_aligned(logits, 2),
+                PIE_E_ALIGN, "pie_logits_dry_penalty_rows: the records and the int32 arrays need 4-byte alignment, logits 2-byte");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_logits_dry_penalty_rows: dtype must be PIE_BF16 or PIE_F16");
+    DryRowsArgs a = {};
+    a.r.logits = (u16 *)logits, a.r.V = V, a.r.n_src = n_src, a.r.recent = recent_ids, a.r.ids = ids, a.r.ctx = ctx, a.r.out_rows = out_rows;
+    a.records = records, a.breakers = breakers;
+    return logits_dry_rows_launch(dtype, a, rows, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -873,7 +873,7 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     PrefillScratch *s = d->prefill;
     const RowsTail &r = d->rows;
     int rc;
-    // The five stages of configured_tail (decoder.hip), per row; with nothing configured only the partials and the finish run.
+    // The six stages of configured_tail (decoder.hip), per row; with nothing configured only the partials and the finish run.
     if (r.sampler.table || r.edits.bias_cap) {  // edit: the rows' biases ride the penalty's launch (k_logits_edit_rows: no penalties without a table)
         PenRowsArgs p = {};
         p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = r.sampler.table, p.recent = r.sampler.recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
@@ -884,6 +884,12 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
         CountPenArgs k = {};
         k.logits = logits, k.V = c.vocab, k.n_src = n_src, k.records = r.counts.records, k.counts = r.counts.counts, k.ids = ids, k.ctx = ctx, k.out_rows = out_rows;
         if ((rc = logits_count_penalty_rows_launch(c.dtype, k, rows, st))) return rc;
+    }
+    if (r.dry.records) {  // DRY: behind the count penalty, over the rows' own rings
+        DryRowsArgs k = {};
+        k.r.logits = logits, k.r.V = c.vocab, k.r.n_src = n_src, k.r.recent = r.dry.recent, k.r.ids = ids, k.r.ctx = ctx, k.r.out_rows = out_rows;
+        k.records = r.dry.records, k.breakers = r.dry.breakers;
+        if ((rc = logits_dry_rows_launch(c.dtype, k, rows, st))) return rc;
     }
     // partials and finish: the rows' masks ride the partials pass -- physically last, so a masked id is -inf whatever else is configured
     if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st, r.edits.masks, r.edits.mask_words, r.edits.mask_on))) return rc;

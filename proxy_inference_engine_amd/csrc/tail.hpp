@@ -403,3 +403,5 @@ static inline int logits_penalty_rows_launch(int dtype, const PenRowsArgs &a, in
 static inline int logits_edit_rows_launch(int dtype, const PenRowsArgs &a, const BiasRowsArgs &b, int rows, hipStream_t st) {
     return launch_for_dtype(dtype, "logits bias:", [&](auto t) { hipLaunchKernelGGL(k_logits_edit_rows<decltype(t)>, dim3(rows), dim3(PEN_MAX_IDS), 0, st, a, b); });
 }
+
+#include "dry_penalty.hpp"  // the DRY penalty: step (5) of a tail; built on the window and row lookups above

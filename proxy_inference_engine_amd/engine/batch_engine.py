@@ -37,7 +37,10 @@ class SamplingParams:
     row inside the passes, in the single-sequence tail's order: mask, repetition penalty, bias.
     frequency_penalty / presence_penalty (each -2.0 .. 2.0; the two remaining fields of LogitsParams): logits[v] -= frequency_penalty *
     c[v] + presence_penalty wherever c[v] > 0, c = how often the request has GENERATED id v so far (its prompt does not count), per row
-    inside the passes, after the bias: mask, repetition penalty, bias, frequency / presence."""
+    inside the passes, after the bias: mask, repetition penalty, bias, frequency / presence.
+    dry_multiplier != 0: the DRY penalty over the last dry_range ids the request has been fed, per row inside the passes,
+    after the frequency / presence penalties: the token that would extend a repeat of the sequence's tail of at least dry_allowed_length
+    ids loses dry_multiplier * dry_base ** (length - dry_allowed_length).  dry_sequence_breakers: up to 64 token ids a repeat does not cross."""
     temp: float = 0.0
     top_p: float = 1.0
     top_k: int = -1
@@ -50,6 +53,11 @@ class SamplingParams:
     logit_bias: dict | None = None
     frequency_penalty: float = 0.0
     presence_penalty: float = 0.0
+    dry_multiplier: float = 0.0
+    dry_base: float = 1.75
+    dry_allowed_length: int = 2
+    dry_range: int = 1024
+    dry_sequence_breakers: tuple = ()
 
     def hip_spec(self) -> tuple | None:
         """None (greedy) or (mode, temp, p, k) as hip_ops.sample / row_tail_pack take them."""
@@ -76,7 +84,17 @@ class SamplingParams:
     @property
     def tailless(self) -> bool:
         """Greedy without a penalty of any kind: the request's row needs no per-row state in a pass's tail."""
-        return self.recordless and not self.counted
+        return self.recordless and not self.counted and not self.dried
+
+    @property
+    def dried(self) -> bool:
+        """A DRY penalty: the request needs a row of the batch DRY penalty's state."""
+        return self.dry_multiplier != 0.0
+
+    def dry(self) -> tuple:
+        """(multiplier, base, allowed_length, range, breaker ids) under hip_ops.check_dry's rules: ValueError otherwise."""
+        from .. import hip_ops
+        return hip_ops.check_dry(self.dry_multiplier, self.dry_base, self.dry_allowed_length, self.dry_range, self.dry_sequence_breakers, "SamplingParams")
 
     @property
     def plain(self) -> bool:
@@ -192,13 +210,14 @@ def same_occupant(have, want) -> bool:
 class _RowSeats:
     """The per-row tail state of one generate() call: which request's sampler record, top-n count, mask, bias table and counts every output
     row of the device buffers holds, rewritten where a row's occupant changes.  tails: (params, seeds) or None; edits: every request's
-    SamplingParams.edits or None; cnts: every request's (frequency, presence) or None, or None; tops: every request's top_logprobs or None
+    SamplingParams.edits or None; cnts: every request's (frequency, presence) or None, or None; drys: every request's SamplingParams.dry or
+    None, or None; tops: every request's top_logprobs or None
     (then `maps` collects their records' maps).  A kind that is None is neither armed nor written.  As a context manager: arms the kinds
     asked for with every row neutral, and clears them on the way out, whatever happened."""
 
-    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None):
+    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None, drys=None):
         self.model, self.max_batch, self.prompts = model, max_batch, prompts
-        self.tails, self.edits, self.cnts, self.tops = tails, edits, cnts, tops
+        self.tails, self.edits, self.cnts, self.tops, self.drys = tails, edits, cnts, tops, drys
         self.maps = None if tops is None else [[] for _ in prompts]
         self.bufs = None              # the armed top-n buffers
         self.slots: list = []         # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
@@ -206,6 +225,7 @@ class _RowSeats:
         self.seats: list = []         # per-request edits: the request whose mask and bias table row s holds, None = unarmed
         self.words: list = []         # ... and the mask words row s holds when that request's mask is a callable
         self.cseats: list = []        # frequency / presence penalties: what row s of the counting state holds, (request, tokens generated) or None = a zero record
+        self.dseats: list = []        # DRY penalty: what row s of the DRY state holds, (request, tokens generated) or None = a zero record
 
     def __enter__(self):
         m, every = self.model, list(range(self.max_batch))
@@ -220,6 +240,9 @@ class _RowSeats:
             if self.cnts is not None:
                 m.set_batch_count_penalty(self.max_batch)
                 m.write_batch_count_penalty(every, [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
+            if self.drys is not None:
+                m.set_batch_dry_penalty(self.max_batch)
+                m.write_batch_dry_penalty(every, [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
             if self.tops is not None:
                 self.bufs = m.set_batch_top_logprobs(self.max_batch, max(max(self.tops, default=1), 1))
                 self.bufs["count"].fill_(-1)       # (cached buffers may hold an earlier call's counts)
@@ -230,6 +253,7 @@ class _RowSeats:
 
     def __exit__(self, *exc) -> None:
         for asked, clear in ((self.tails, "clear_batch_tail"), (self.edits, "clear_batch_edits"), (self.cnts, "clear_batch_count_penalty"),
+                             (self.drys, "clear_batch_dry_penalty"),
                              (self.tops, "clear_batch_top_logprobs")):
             if asked is not None:
                 getattr(self.model, clear)()
@@ -293,6 +317,16 @@ class _RowSeats:
             moved = [want[s_] for s_ in c_rows]
             self.model.write_batch_count_penalty(c_rows, [None if w is None else (*cnts[w[0]], len(prompts[w[0]])) for w in moved],
                                                  [None if w is None else list(gen_by.get(w[0], [])) for w in moved])
+        if self.drys is not None:
+            # a row's record, breaker table and ring are rebuilt where its sampler record is: when its occupant changes, from the ids the
+            # request has been fed so far (the pass records the row's own input id).  A prompt that is still filling, and a request
+            # without DRY, hold a zero record.
+            drys = self.drys
+            want = [None if r is None or drys[r] is None else (r, len(gen_by.get(r, []))) for r in rows]
+            d_rows = self._changed(self.dseats, want)
+            moved = [want[s_] for s_ in d_rows]
+            self.model.write_batch_dry_penalty(d_rows, [None if w is None else drys[w[0]] for w in moved],
+                                               [None if w is None else list(prompts[w[0]]) + list(gen_by.get(w[0], [])[:-1]) for w in moved])
         if self.tails is None:
             return
         params, seeds = self.tails
@@ -313,8 +347,9 @@ class _RowSeats:
         """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
         own, or wants log-probabilities: then it is a batch of one.  Frequency / presence penalties alone do not make it one: a request's
         first token is chosen against empty counts, which is the unpenalised row, so the greedy prompt pass gives the token the
-        penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`)."""
-        return self.tops is None and (self.tails is None or self.tails[0][idx].tailless) and (self.edits is None or self.edits[idx] == (None, None))
+        penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`).  A DRY penalty
+        does make it one: the first token is chosen against the prompt's own window."""
+        return self.tops is None and (self.drys is None or self.drys[idx] is None) and (self.tails is None or self.tails[0][idx].tailless) and (self.edits is None or self.edits[idx] == (None, None))
 
     def records(self, n_rows: int):
         """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'
@@ -360,7 +395,8 @@ class BatchedEngine:
         own sampler, seed and repetition penalty, applied to its row inside every pass (Model.set_batch_tail) -- a request's tokens depend
         on its seed and on what it was fed, not on the row it occupies or on its neighbours' parameters.  A request's frequency_penalty and
         presence_penalty run on per-row counts of its own generated tokens (Model.set_batch_count_penalty), rebuilt from the ids the
-        host holds whenever the request takes another row.  A request's token_mask and
+        host holds whenever the request takes another row; so does its DRY penalty (dry_multiplier != 0), on a ring of the ids it has
+        been fed (Model.set_batch_dry_penalty).  A request's token_mask and
         logit_bias ride the same passes (Model.set_batch_edits); a callable mask is evaluated on the host after the per-pass read-back of
         the tokens and only the rows whose words changed are uploaded.  With logprobs=True the maps report the processed log-probabilities.
         logprobs=True: returns (outputs, maps) -- maps[i][j] is the {token id: log-probability} dict of outputs[i][j], as
@@ -399,7 +435,7 @@ class BatchedEngine:
 
     def _run(self, prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores):
         """generate's body; scores: the call's _PromptScores or None."""
-        tops = edits = cnts = None
+        tops = edits = cnts = drys = None
         if logprobs:
             if self.sampler is not None:
                 raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
@@ -423,11 +459,14 @@ class BatchedEngine:
                 edits = [sp.edits(self.model.args.vocab_size) for sp in params]
             if any(sp.counted for sp in params):   # the per-row counting state is armed only when some request asks for it
                 cnts = [sp.count_penalties() if sp.counted else None for sp in params]
+            dry_all = [sp.dry() for sp in params]   # (checked for every request, armed or not)
+            if any(sp.dried for sp in params):     # the per-row DRY state is armed only when some request asks for it
+                drys = [d if sp.dried else None for sp, d in zip(params, dry_all)]
             if all(sp.recordless for sp in params):
                 sampling = None               # no record to configure: a request with only a mask, a bias or count penalties arms no batch tail
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops) as seats:
+        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops, drys) as seats:
             out = self._generate(prompts, max_new_tokens, seats, scores)
         return out if tops is None else (out, seats.maps)
 

@@ -19,7 +19,7 @@ from .. import hip_ops
 from ..cache import BaseCache, PromptCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from ..cache.kv_cache import PagedKVCache
 from ..cache.kv_cache.quantized import check_format as check_kv_format
-from ..logits_processors import check_vocab, count_penalty_logits_processor, make_logit_bias, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
+from ..logits_processors import check_vocab, count_penalty_logits_processor, dry_logits_processor, make_logit_bias, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
 from ..models import load
 from ..samplers import make_sampler
 
@@ -75,9 +75,10 @@ def fused_tail_spec(processors, sampler, structuring_engine=None, tensor_paralle
 def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_parallel: bool = False):
     """fused_tail_spec with the tail's token mask and logit bias: whether one _inference call can end inside the decode
     step's configured tail, and with what -- a dict(sampler=spec or None, repetition_penalty, context_size, mask=the token-mask processor
-    or None, bias=the logit-bias processor or None) -- plus counts=the frequency / presence processor when the request carries one
-     -- or None for the host-orchestrated branches.  Fused: the processor list is a
-    sub-sequence of (one token mask, one repetition penalty, one logit bias, one frequency / presence penalty) in that order -- the order the kernels define -- and
+    or None, bias=the logit-bias processor or None) -- plus counts=the frequency / presence processor and dry=the DRY
+    processor when the request carries one -- or None for the host-orchestrated branches.  Fused: the processor list is a
+    sub-sequence of (one token mask, one repetition penalty, one logit bias, one frequency / presence penalty, one DRY penalty) in that
+    order -- the order the kernels define -- and
     fused_tail_spec's other conditions hold: no structuring engine, a repetition context of 1..1024, a greedy or `hip_spec` sampler,
     no tensor parallelism."""
     kinds = []
@@ -90,9 +91,11 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
             kinds.append("bias")
         elif hasattr(proc, "frequency_penalty") and hasattr(proc, "presence_penalty"):
             kinds.append("counts")
+        elif hasattr(proc, "dry_multiplier"):
+            kinds.append("dry")
         else:
             return None
-    order = [("mask", "penalty", "bias", "counts").index(k) for k in kinds]
+    order = [("mask", "penalty", "bias", "counts", "dry").index(k) for k in kinds]
     if any(b <= a for a, b in zip(order, order[1:])):  # out of order, or one kind twice
         return None
     by_kind = dict(zip(kinds, list(processors or [])))
@@ -102,6 +105,8 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
     plan = dict(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2], mask=by_kind.get("mask"), bias=by_kind.get("bias"))
     if "counts" in by_kind:  # (a request without the penalties gets the plan it always got)
         plan["counts"] = by_kind["counts"]
+    if "dry" in by_kind:
+        plan["dry"] = by_kind["dry"]
     return plan
 
 
@@ -171,7 +176,9 @@ class InferenceEngine:
         defines -- [token mask] in front (where the PSE's masking stands), [logit bias] behind (logit_processor_factory.cpp's order).
         token_mask: packed words, a bool mask or a callable tokens -> mask (make_token_mask); logit_bias: {token id: bias}.
         frequency_penalty / presence_penalty (each -2.0 .. 2.0): one processor behind the bias, over the counts of the
-        request's generated tokens."""
+        request's generated tokens.
+        dry_multiplier != 0 (with dry_base, dry_allowed_length, dry_range, dry_sequence_breakers = token ids): the DRY
+        processor behind the count penalty."""
         procs: list[LogitsProcessor] = []
         if self.structuring_engine is not None:
             procs.append(self.structuring_engine.process_logits)
@@ -185,6 +192,10 @@ class InferenceEngine:
         freq, pres = hip_ops.check_count_penalties(kwargs.get("frequency_penalty") or 0.0, kwargs.get("presence_penalty") or 0.0, "make_processors")
         if freq != 0.0 or pres != 0.0:
             procs.append(count_penalty_logits_processor(freq, pres))
+        dry = hip_ops.check_dry(kwargs.get("dry_multiplier") or 0.0, kwargs.get("dry_base", 1.75), kwargs.get("dry_allowed_length", 2),
+                                kwargs.get("dry_range", 1024), kwargs.get("dry_sequence_breakers") or (), "make_processors")
+        if dry[0] != 0.0:
+            procs.append(dry_logits_processor(dry[0], dry[1], dry[2], dry[3], dry[4]))
         return procs
 
     def prepare_engine(self, prompt_ids, **inference_kwargs):
@@ -285,9 +296,10 @@ class InferenceEngine:
             if plan is not None and offset + int(ids.numel()) <= self.model.fed_ids.numel():
                 # The whole tail inside the step: mask, penalty, bias, log-softmax and the draw ride the replayed graph; the
                 # drawn token is fed back on the device, so a fed-back step passes nothing, whatever the sampler
-                penalised = plan["repetition_penalty"] != 1.0
-                if penalised and not fed_back and offset > 0:  # a reused prefix: its ids may predate this configuration (fed back unrecorded, loaded from disk)
-                    seen = self.prompt_cache.computed_ids[-min(offset, plan["context_size"]):]
+                dry = plan.get("dry")
+                window = max(plan["context_size"] if plan["repetition_penalty"] != 1.0 else 0, 0 if dry is None else dry.dry_range)  # the fed ids a tail reads
+                if window and not fed_back and offset > 0:  # a reused prefix: its ids may predate this configuration (fed back unrecorded, loaded from disk)
+                    seen = self.prompt_cache.computed_ids[-min(offset, window):]
                     self.model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
                 mask, bias, recorded = plan["mask"], plan["bias"], False
                 vocab = getattr(self.model, "language_model", self.model).logprobs.numel()
@@ -307,7 +319,8 @@ class InferenceEngine:
                               "count_start": None if fed_back else len(prompt_ids)}   # the request's first call: zero counts, from the prompt's end on
                 set_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
                          token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values),
-                         **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}), **counts)
+                         **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}), **counts,
+                         **({} if dry is None else {"dry": (dry.dry_multiplier, dry.dry_base, dry.dry_allowed_length, dry.dry_range, dry.dry_sequence_breakers)}))
                 if pixel_values is not None and not fed_back:
                     embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
                     tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)

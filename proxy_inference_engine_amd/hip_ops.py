@@ -961,6 +961,103 @@ def logits_count_penalty_rows(logits: torch.Tensor, records: torch.Tensor, count
     return logits
 
 
+# ---------------------------------------------------------------- DRY penalty (include/pie_hip.h: pie_dry_penalty)
+DRY_MAX_MATCH = 64        # PIE_DRY_MAX_MATCH
+DRY_BREAKERS_MAX = 64     # PIE_DRY_BREAKERS_MAX
+DRY_PENALTY_WORDS = C.sizeof(_ffi.pie_dry_penalty) // 4   # a record as int32 words: a device table is an int32 [rows, DRY_PENALTY_WORDS] tensor
+
+
+def check_dry(multiplier, base=1.75, allowed_length=2, range=1024, breakers=(), who: str = "dry") -> tuple[float, float, int, int, tuple]:
+    """(multiplier, base, allowed_length, range, breaker ids) under the ABI's rules: multiplier finite and >= 0, base finite and > 0 (both
+    as fp32), allowed_length 1..64, range 1..1024, at most 64 breaker ids, each an int32: ValueError otherwise (NaN included)."""
+    import math
+    m, b = float(multiplier), float(base)
+    big = float(torch.finfo(torch.float32).max)
+    if not (math.isfinite(m) and 0.0 <= m <= big):
+        raise ValueError(f"{who}: the multiplier must be finite and >= 0, got {multiplier!r}")
+    if not (math.isfinite(b) and 0.0 < b <= big and float(torch.tensor(b, dtype=torch.float32)) > 0.0):
+        raise ValueError(f"{who}: the base must be finite and > 0, got {base!r}")
+    for name, v, hi in (("allowed_length", allowed_length, DRY_MAX_MATCH), ("range", range, RECENT_IDS)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= hi:
+            raise ValueError(f"{who}: {name} must be an integer in 1 .. {hi}, got {v!r}")
+    ids = tuple(int(i) for i in breakers)
+    if len(ids) > DRY_BREAKERS_MAX or any(not -2 ** 31 <= i < 2 ** 31 for i in ids):
+        raise ValueError(f"{who}: at most {DRY_BREAKERS_MAX} sequence breakers, each an int32 token id")
+    return m, b, int(allowed_length), int(range), ids
+
+
+def dry_penalty_pack(multiplier: float = 0.0, base: float = 1.75, allowed_length: int = 2, range: int = 1024, n_breakers: int = 0) -> _ffi.pie_dry_penalty:
+    """One row's record (pie_dry_penalty_pack) in host memory; the default is the zero record (multiplier 0: the row keeps every bit).
+    ValueError outside the ABI's rules.  Needs no device."""
+    rec = _ffi.pie_dry_penalty()
+    _ffi.check(_ffi.load().pie_dry_penalty_pack(float(multiplier), float(base), int(allowed_length), int(range), int(n_breakers), C.byref(rec)))
+    return rec
+
+
+def dry_penalty_records(records, device=None) -> torch.Tensor:
+    """Records (dry_penalty_pack) as an int32 [rows, DRY_PENALTY_WORDS] tensor, on `device` when given."""
+    import numpy as np
+    host = np.frombuffer(b"".join(bytes(r) for r in records), dtype=np.int32).reshape(len(records), DRY_PENALTY_WORDS).copy()
+    t = torch.from_numpy(host)
+    return t if device is None else t.to(device)
+
+
+def dry_breaker_table(breakers, device=None) -> torch.Tensor:
+    """One row's breaker ids as an int32 [DRY_BREAKERS_MAX] tensor (unused entries 0: the record's n_breakers bounds the reads)."""
+    row = torch.zeros(DRY_BREAKERS_MAX, dtype=torch.int32)
+    if len(breakers):
+        row[:len(breakers)] = torch.tensor(list(breakers), dtype=torch.int32)
+    return row if device is None else row.to(device)
+
+
+def logits_dry_penalty(logits: torch.Tensor, ids: torch.Tensor, multiplier: float, base: float = 1.75, allowed_length: int = 2,
+                       breakers=()) -> torch.Tensor:
+    """pie_logits_dry_penalty on one 16-bit logit vector [V] (or [1, V]), IN PLACE: the window is ids (int32 device tensor, 1..1024 entries,
+    the last one the input id; the range is its length), breakers a sequence or int32 device tensor of at most 64 ids.  Returns logits."""
+    _dev(logits), _dev(ids)
+    if not logits.is_contiguous() or logits.numel() != logits.shape[-1]:
+        raise ValueError("logits_dry_penalty: one contiguous logit vector")
+    if ids.dtype != torch.int32 or not ids.is_contiguous() or not 1 <= ids.numel() <= RECENT_IDS:
+        raise ValueError("logits_dry_penalty: 1..1024 contiguous int32 ids")
+    if not isinstance(breakers, torch.Tensor):
+        m, b, a, _, br = check_dry(multiplier, base, allowed_length, ids.numel(), breakers, "logits_dry_penalty")
+        breakers = torch.tensor(br, dtype=torch.int32, device=logits.device) if br else None
+    else:
+        _dev(breakers)
+        if breakers.dtype != torch.int32 or not breakers.is_contiguous():
+            raise ValueError("logits_dry_penalty: contiguous int32 breakers")
+        m, b, a = float(multiplier), float(base), int(allowed_length)
+    nb = 0 if breakers is None else breakers.numel()
+    _ffi.check(_ffi.load().pie_logits_dry_penalty(_ffi.p(logits), logits.shape[-1], _ffi.dtype_code(logits.dtype), _ffi.p(ids), ids.numel(), m, b, a,
+                                                  _ffi.p(breakers), nb, _ffi.stream()))
+    return logits
+
+
+def logits_dry_penalty_rows(logits: torch.Tensor, records: torch.Tensor, breakers: torch.Tensor, recent_ids: torch.Tensor, ids: torch.Tensor,
+                            ctx: torch.Tensor, out_rows: torch.Tensor | None = None) -> torch.Tensor:
+    """pie_logits_dry_penalty_rows on 16-bit logits [rows, V], IN PLACE: row s with source row i = out_rows[s] (or s) records ids[i] at
+    recent_ids[s][(ctx[i] - 1) & 1023] and is penalised under records[s] / breakers[s] over its last records[s].range fed ids.  records
+    int32 [>= rows, DRY_PENALTY_WORDS] (dry_penalty_records), breakers int32 [>= rows, 64], recent_ids int32 [>= rows, 1024]; ids / ctx
+    (/ out_rows) int32 device tensors.  Returns logits."""
+    _dev(logits)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logits_dry_penalty_rows: contiguous [rows, V] logits")
+    rows, V = logits.shape
+    for t in (records, breakers, recent_ids, ids, ctx) + ((out_rows,) if out_rows is not None else ()):
+        _dev(t)
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("logits_dry_penalty_rows: contiguous int32 records, breakers, rings and index tensors")
+    if records.dim() != 2 or records.shape[1] != DRY_PENALTY_WORDS or records.shape[0] < rows or breakers.dim() != 2 or \
+            breakers.shape[1] != DRY_BREAKERS_MAX or breakers.shape[0] < rows or recent_ids.dim() != 2 or recent_ids.shape[1] != RECENT_IDS or \
+            recent_ids.shape[0] < rows:
+        raise ValueError(f"logits_dry_penalty_rows: records [>= rows, {DRY_PENALTY_WORDS}], breakers [>= rows, 64], recent_ids [>= rows, 1024]")
+    if ids.numel() != ctx.numel() or ids.numel() < 1 or (out_rows is None and ids.numel() < rows) or (out_rows is not None and out_rows.numel() != rows):
+        raise ValueError("logits_dry_penalty_rows: ids and ctx of one length (>= rows without out_rows), out_rows [rows]")
+    _ffi.check(_ffi.load().pie_logits_dry_penalty_rows(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(records), _ffi.p(breakers),
+                                                       _ffi.p(recent_ids), _ffi.p(ids), _ffi.p(ctx), _ffi.p(out_rows), ids.numel(), _ffi.stream()))
+    return logits
+
+
 # ---------------------------------------------------------------- top-n log-probabilities (csrc/top_logprobs.hip; DESIGN.md 13)
 TOP_LOGPROBS_MAX = _ffi.PIE_TOP_LOGPROBS_MAX
 

@@ -306,6 +306,9 @@ class Model(RowsTailState):
         # frequency / presence penalties: the step's record + counts at stable addresses, made when first used; (freq, pres,
         # start) while switched on.
         self._cnt, self._cnt_rec, self._cnt_counts = None, None, None
+        # the DRY penalty: the step's record + 64-entry breaker table at stable addresses, made when first used;
+        # (multiplier, base, allowed_length, range, breaker ids) while switched on.
+        self._dry, self._dry_rec, self._dry_brk = None, None, None
         self._spec = None   # speculative decoding's record and workspaces, made when first used
         self._init_rows_state()  # the multi-sequence passes' per-row tail state (rows_state.py)
         torch.cuda.synchronize(device)
@@ -368,7 +371,7 @@ class Model(RowsTailState):
     # ------------------------------------------------------------------ the step's tail
     def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
                       token_mask=None, logit_bias=None, top_logprobs: int | None = None, frequency_penalty: float = 0.0,
-                      presence_penalty: float = 0.0, count_start: int | None = None) -> None:
+                      presence_penalty: float = 0.0, count_start: int | None = None, dry: tuple | None = None) -> None:
         """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
         DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
@@ -388,11 +391,15 @@ class Model(RowsTailState):
         presence.  The model owns one record and one [V] count buffer at stable addresses; the step counts every token it is fed from
         position count_start on, inside the replayed graph.  count_start given: the counts start afresh from that position
         (reset_step_counts); None: the counting state stays and only the two values are rewritten -- a copy and a replay.
+        dry: None (off) or (multiplier, base, allowed_length, range, breaker_ids) -- the DRY penalty (hip_ops.check_dry's rules; DESIGN.md
+        18) over the last `range` fed ids (`fed_ids`), behind the frequency / presence penalties.  The model owns one record and one
+        64-entry breaker table at stable addresses: new values are a copy and a replay, not a re-capture.  A multiplier of 0 is off.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
         self._set_tail_edits(token_mask, logit_bias)
         self._set_tail_top_logprobs(top_logprobs)
         self._set_tail_counts(frequency_penalty, presence_penalty, count_start)
+        self._set_tail_dry(dry)
         pen = (float(repetition_penalty), int(context_size)) if repetition_penalty != 1.0 and context_size != 0 else None
         seed = counter = None
         if sampler is not None:
@@ -501,6 +508,36 @@ class Model(RowsTailState):
         elif (f, p) != was[:2]:
             self._cnt = (f, p, was[2])
             self._cnt_rec[0, :2].copy_(hip_ops.count_penalty_records([hip_ops.count_penalty_pack(f, p)])[0, :2])  # (counted_pos lives on the device: left alone)
+
+    def _set_tail_dry(self, dry) -> None:
+        """The DRY parameters into the model's own record and breaker table; the library is asked only when the feature is switched on or off."""
+        if dry is not None:
+            if len(dry) != 5:
+                raise ValueError("set_step_tail: dry is (multiplier, base, allowed_length, range, breaker_ids)")
+            dry = hip_ops.check_dry(*dry, who="set_step_tail")
+            if dry[0] == 0.0:
+                dry = None
+        if dry == self._dry:
+            return
+        lib = _ffi.load()
+        if dry is None:
+            _ffi.check(lib.pie_decoder_set_dry_penalty(self._dec, None, None, None, 0))
+            self._dry = None
+            return
+        if self._dry_rec is None:
+            self._dry_rec = hip_ops.dry_penalty_records([hip_ops.dry_penalty_pack()], self.device)
+            self._dry_brk = torch.zeros(hip_ops.DRY_BREAKERS_MAX, dtype=torch.int32, device=self.device)
+        m, b, a, r, brk = dry
+        self._dry_rec.copy_(hip_ops.dry_penalty_records([hip_ops.dry_penalty_pack(m, b, a, r, len(brk))]))
+        self._dry_brk.copy_(hip_ops.dry_breaker_table(brk))
+        if self._dry is None:
+            _ffi.check(lib.pie_decoder_set_dry_penalty(self._dec, _ffi.p(self._dry_rec), _ffi.p(self._dry_brk), _ffi.p(self.fed_ids), self.fed_ids.numel()))
+        self._dry = dry
+
+    @property
+    def step_tail_dry(self) -> tuple | None:
+        """(multiplier, base, allowed_length, range, breaker ids) as set_step_tail last configured the DRY penalty, None while it is off."""
+        return self._dry
 
     def reset_step_counts(self, start: int, generated_ids=()) -> None:
         """The step's frequency / presence counting starts afresh, in stream order: the counts become the multiplicities of
@@ -649,7 +686,7 @@ class Model(RowsTailState):
         else:
             ids = ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
             L = ids.numel()
-            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None and self._cnt is None:  # (the several-prompts pass ends in the greedy tail only)
+            if L >= 6 and on_int8_pages(cache) and cache[0].offset == 0 and self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None and self._cnt is None and self._dry is None:  # (the several-prompts pass ends in the greedy tail only)
                 # A fresh prompt on int8 pages: the single-sequence prompt pass reads T pages (it would run the prompt as L decode steps,
                 # ~1.2 ms per token), the several-prompts pass quantises into int8 pages -- one prompt is a batch of one.
                 nxt, logprobs, logits = self.prefill_batch([ids.cpu().numpy()], [cache])  # (a prompt arrives once: the host copy is the pass's own row bookkeeping)
@@ -722,7 +759,7 @@ class Model(RowsTailState):
             raise ValueError(f"{who}: not available on int8 KV pages")
         if not isinstance(cache[0], (ReusableKVCache, PagedKVCache)):
             raise ValueError(f"{who}: runs on ReusableKVCache or 16-bit PagedKVCache, not on {type(cache[0]).__name__}")
-        if self._tail[:2] != (None, None) or self._edits != (False, 0) or self._top_n is not None or self._cnt is not None:
+        if self._tail[:2] != (None, None) or self._edits != (False, 0) or self._top_n is not None or self._cnt is not None or self._dry is not None:
             raise ValueError(f"{who}: speculation is greedy and raw -- set_step_tail() with its defaults first "
                              "(no sampler, repetition penalty, token mask, logit bias, top_logprobs or frequency / presence penalty)")
 

@@ -1,5 +1,5 @@
 """The per-row tail state of the multi-sequence passes (step_batch / prefill_batch / step_mixed), as `Model` owns it: sampler records and
-rings, top-n records, token masks and bias tables, frequency / presence counts, and the prompt passes' log-probability records.  Every
+rings, top-n records, token masks and bias tables, frequency / presence counts, DRY records, and the prompt passes' log-probability records.  Every
 kind is a set_* / write_* / clear_* family over device buffers kept per rows_cap by one `RowsCapCache`."""
 from __future__ import annotations
 
@@ -50,7 +50,10 @@ class RowsTailState:
             "masks": i32((r, (V + 31) // 32)), "mask_on": i32(r), "bias_ids": i32(r * 1024), "bias_vals": f32(r * 1024, 0.0), "bias_n": i32(r)})
         self._batch_count_bufs = RowsCapCache(lambda r: {
             "records": hip_ops.count_penalty_records([hip_ops.count_penalty_pack()] * r, dev), "counts": i32((r, V))})
-        self._batch_tail = self._batch_edits = self._batch_counts = None   # the armed buffers
+        self._batch_dry_bufs = RowsCapCache(lambda r: {
+            "records": hip_ops.dry_penalty_records([hip_ops.dry_penalty_pack()] * r, dev), "breakers": i32((r, hip_ops.DRY_BREAKERS_MAX)),
+            "recent": i32((r, hip_ops.RECENT_IDS))})
+        self._batch_tail = self._batch_edits = self._batch_counts = self._batch_dry = None   # the armed buffers
         self._prompt_lp_ws = None      # (block_rows, its logits block + the op's workspace)
 
     # ------------------------------------------------------------------ the multi-sequence passes' tail
@@ -264,3 +267,54 @@ class RowsTailState:
         _ffi.check(_ffi.load().pie_decoder_set_batch_count_penalty(self._dec, None, None, 0))
         self._batch_counts = None
 
+    # ------------------------------------------------------------------ the multi-sequence passes' DRY penalty
+    def set_batch_dry_penalty(self, rows_cap: int) -> dict:
+        """From now on step_batch / prefill_batch / step_mixed apply every output row's own DRY penalty (pie_decoder_set_batch_dry_penalty),
+        with or without a batch tail, batch edits or batch counts: {"records": int32 [rows_cap, DRY_PENALTY_WORDS], "breakers": int32
+        [rows_cap, 64], "recent": int32 [rows_cap, 1024] rings of fed ids (its own, not the batch tail's)}, returned, owned by the model
+        and kept per rows_cap at stable addresses (the 4 most recent, like set_batch_tail's buffers).  Fresh buffers hold zero records:
+        the passes' results are the unpenalised ones until write_batch_dry_penalty arms a row."""
+        rows_cap = int(rows_cap)
+        if rows_cap < 1:
+            raise ValueError("set_batch_dry_penalty: rows_cap >= 1")
+        bd = self._batch_dry_bufs.get(rows_cap)
+        _ffi.check(_ffi.load().pie_decoder_set_batch_dry_penalty(self._dec, _ffi.p(bd["records"]), _ffi.p(bd["breakers"]), _ffi.p(bd["recent"]), rows_cap))
+        self._batch_dry = bd
+        return bd
+
+    def write_batch_dry_penalty(self, rows: list[int], records: list, fed: list | None = None) -> None:
+        """Rewrites the records and breaker tables of `rows` of the armed buffers, in stream order, one copy per array for all of them --
+        when a row's occupant changes.  records[i]: (multiplier, base, allowed_length, range, breaker_ids) of the occupant of rows[i]
+        (hip_ops.check_dry's rules), or None: a zero record (a row without DRY, a prompt that is still filling).  fed[i] (None: leave the
+        ring): the ids the occupant of rows[i] has been fed so far, by position, of which the ring keeps the last 1024."""
+        bd = self._batch_dry
+        if bd is None:
+            raise RuntimeError("write_batch_dry_penalty: no batch DRY penalty is set (set_batch_dry_penalty)")
+        if not rows:
+            return
+        if len(records) != len(rows) or (fed is not None and len(fed) != len(rows)):
+            raise ValueError("write_batch_dry_penalty: one record and one list of fed ids per row")
+        packed, tables = [], []
+        for rec in records:
+            m, b, a, r, brk = hip_ops.check_dry(0.0, who="write_batch_dry_penalty") if rec is None else hip_ops.check_dry(*rec, who="write_batch_dry_penalty")
+            packed.append(hip_ops.dry_penalty_pack(m, b, a, r, len(brk)))
+            tables.append(hip_ops.dry_breaker_table(brk))
+        idx = torch.tensor(rows, dtype=torch.long, device=self.device)
+        bd["records"].index_copy_(0, idx, hip_ops.dry_penalty_records(packed, self.device))
+        bd["breakers"].index_copy_(0, idx, torch.stack(tables).to(self.device))
+        ring_rows, rings = [], []
+        for r, ids in zip(rows, fed or []):
+            if ids is None:
+                continue
+            ids = np.asarray(ids, dtype=np.int32).reshape(-1)
+            q = np.arange(max(0, ids.size - hip_ops.RECENT_IDS), ids.size)
+            ring = np.zeros(hip_ops.RECENT_IDS, np.int32)
+            ring[q & (hip_ops.RECENT_IDS - 1)] = ids[q]
+            ring_rows.append(r), rings.append(ring)
+        if rings:
+            bd["recent"].index_copy_(0, torch.tensor(ring_rows, dtype=torch.long, device=self.device), torch.from_numpy(np.stack(rings)).to(self.device))
+
+    def clear_batch_dry_penalty(self) -> None:
+        """The multi-sequence passes launch what they launched before set_batch_dry_penalty; the buffers stay cached."""
+        _ffi.check(_ffi.load().pie_decoder_set_batch_dry_penalty(self._dec, None, None, None, 0))
+        self._batch_dry = None
