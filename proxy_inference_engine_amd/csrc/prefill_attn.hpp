@@ -247,6 +247,7 @@ static int prefill_attn_launch_d(const PrefillAttnArgs &a, hipStream_t st) {
     const int qt = pie_knob(PIE_KNOB_PREFILL_QT);  // test knob: 1 forces one 32-row query tile per workgroup, 2 forces two wherever they fit
     // 2 tiles need 2*rep <= 8 waves of up to 256 registers, and only pay while the halved grid still fills the 256 CUs
     // (8B model: 4096 tokens 54.9 -> 53.9 ms, 8000 tokens 126.3 -> 125.0 ms; at 1024 tokens it would idle half the chip)
+    // (tests/prefill_attn_reference.py two_tiles() restates this rule to steer its cases into both forms: change the two together)
     const bool two = rep <= 4 && a.M > 32 && (qt > 0 ? qt == 2 : ((a.M + 63) / 64) * a.Hkv >= 256);
     const dim3 grid(((a.M + (two ? 63 : 31)) / (two ? 64 : 32)) * a.Hkv);
 #define PA_LAUNCH(R)                                                                                         \
@@ -275,6 +276,8 @@ static int prefill_attn_launch_d(const PrefillAttnArgs &a, hipStream_t st) {
 template <class T, int D>
 static int segment_attn_launch_d(const PrefillAttnArgs &a, hipStream_t st) {
     if (a.Hq != a.Hkv) return pie::fail(PIE_E_SHAPE, "segment attention: n_heads must equal n_kv_heads");
+    // (no knob here: tests/prefill_attn_reference.py reaches the two-tile form by this rule itself -- SEGMENT_TWO_TILE_RULE, H = 64 and
+    // N = 449 / 512 -- so a new threshold has to move those cases with it)
     const bool two = a.M > 32 && ((a.M + 63) / 64) * a.Hkv >= 512;
     const dim3 grid(((a.M + (two ? 63 : 31)) / (two ? 64 : 32)) * a.Hkv);
     if (two) hipLaunchKernelGGL((k_prefill_attn<T, D, 1, 2, true>), grid, dim3(128), 0, st, a);

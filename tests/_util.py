@@ -63,6 +63,21 @@ def assert_vec_close(got, want, dtype, c_max=4.0, c_rms=4.0, what=""):
     return err / (eps * scale)
 
 
+def window_mask(L, o, W):
+    """create_causal_mask(L, o, window_size=W) as an additive fp32 mask [L, o + L]."""
+    i, j = np.arange(L)[:, None], np.arange(o + L)[None]
+    return np.where((j <= o + i) & (j >= o + i - W), 0.0, -1e9).astype(np.float32)
+
+
+def segment_mask(cu, N, dt):
+    """The block-diagonal additive mask of vision.py:160-167 for cu_seqlens cu: 0 inside a segment, finfo(dt).min elsewhere, fp32 [N, N]."""
+    from oracle import vision_oracle as vo
+    m = np.full((N, N), vo.finfo_min(dt), np.float32)
+    for i in range(1, len(cu)):
+        m[cu[i - 1]:cu[i], cu[i - 1]:cu[i]] = 0.0
+    return m
+
+
 def to_dev(bits: np.ndarray, dtype: str, device="cuda") -> torch.Tensor:
     """numpy storage bits (uint16) -> device tensor of the 16-bit float dtype."""
     t = torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).to(device)

@@ -13,15 +13,9 @@ import pytest
 import torch
 
 from oracle import pie_oracle as po
-from tests._util import assert_vec_close, codes_dev, to_dev
+from tests._util import assert_vec_close, codes_dev, to_dev, window_mask
 
 pytestmark = pytest.mark.gpu
-
-
-def window_mask(L, o, W):
-    """create_causal_mask(L, o, window_size=W) as an additive fp32 mask [L, o + L]."""
-    i, j = np.arange(L)[:, None], np.arange(o + L)[None]
-    return np.where((j <= o + i) & (j >= o + i - W), 0.0, -1e9).astype(np.float32)
 
 
 # ------------------------------------------------------------------ pie_sdpa_prefill_window

@@ -6,7 +6,7 @@ import torch
 
 from oracle import pie_oracle as po
 from oracle import vision_oracle as vo
-from tests._util import EPS, assert_bits_close, assert_dot_close, assert_vec_close, to_bits, to_dev
+from tests._util import EPS, assert_bits_close, assert_dot_close, assert_vec_close, segment_mask, to_bits, to_dev
 
 pytestmark = pytest.mark.gpu
 DT = "bfloat16"
@@ -133,18 +133,12 @@ def test_linear_w16m_refuses_what_it_cannot_do(ops):
         ops.linear_rows(torch.zeros((8, 128), dtype=torch.bfloat16), small)
 
 
-def _mask(cu, N, dt):
-    m = np.full((N, N), vo.finfo_min(dt), np.float32)
-    for i in range(1, len(cu)):
-        m[cu[i - 1]:cu[i], cu[i - 1]:cu[i]] = 0.0
-    return m
-
-
 @pytest.mark.parametrize("dt", ["bfloat16", "float16"])
 @pytest.mark.parametrize("H,D,cu", [
     (2, 64, [0, 64, 128, 192]),                       # windows aligned with the 32-row tiles
     (3, 128, [0, 40, 44, 108, 109, 300]),            # ragged: tiles span several segments, a 1-row and a 4-row segment
-    (16, 128, [0, 1024]),                            # one full-image segment (two query tiles per workgroup)
+    (16, 128, [0, 1024]),                            # one full-image segment (one query tile per workgroup: ceil(N / 64) * H = 256 < 512;
+                                                     # the two-tile form runs in test_gpu_prefill_attn.py)
     (4, 64, [0, 16, 48, 112, 176, 180, 436, 500]),
 ])
 def test_sdpa_segments_vs_oracle(ops, dt, H, D, cu):
@@ -155,7 +149,7 @@ def test_sdpa_segments_vs_oracle(ops, dt, H, D, cu):
     v = po.round_T(rng.standard_normal((H, N, D)), dt)
     lo, hi = ops.segment_bounds(cu, "cuda")
     got = ops.sdpa_segments(dev(q, dt), dev(k, dt), dev(v, dt), lo, hi, D ** -0.5)
-    want = po.sdpa(np.ascontiguousarray(q.transpose(1, 0, 2)), k, v, D ** -0.5, _mask(cu, N, dt), dt, True).transpose(1, 0, 2)
+    want = po.sdpa(np.ascontiguousarray(q.transpose(1, 0, 2)), k, v, D ** -0.5, segment_mask(cu, N, dt), dt, True).transpose(1, 0, 2)
     assert_dot_close(got.float().cpu().numpy(), po.round_T(want, dt), dt, max_frac=0.05, what=f"segments H{H} D{D} {dt}")
 
 
