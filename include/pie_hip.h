@@ -275,6 +275,38 @@ int pie_row_tail_pack(int mode, double temp, double p, int k, unsigned long long
  * pie_sample_workspace_bytes(rows, V) bytes, zeroed once, reusable from call to call whatever the rows' modes become. */
 int pie_sample_rows(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int32_t *tokens, int32_t *kept_count,
                     unsigned char *kept_mask, void *stream);
+/* XTC, "exclude top choices" (mlx-lm's apply_xtc): with a coin's probability, every id more probable than the LEAST
+ * probable one above a threshold is hidden from the draw, so the sampler takes a plausible continuation other than the obvious one.
+ * It runs over the unscaled fp32 log-probabilities lp[0..V) of a row, before the division by the temperature:
+ *   COIN        u = ((r >> 8) + 0.5) * 2^-24, r = word 0 of the Philox-4x32-10 block with key seed and counter {0xFFFFFFFF, row, call}
+ *               (row and call as for the draw: row 0 and the record's `calls` in the table form).  No vocabulary index reaches that block
+ *               (V <= 524288), so the draw's Gumbel stream is untouched.  XTC applies to this call iff u < probability.
+ *   CANDIDATES  A = { i : lp[i] > log_threshold } (fp32 compare; special ids are members like any other).  |A| < 2: nothing is removed.
+ *   CUT         m = min over A of lp[i]; removed R = { i : lp[i] > m, i not special }.  Ids tied at m stay, special ids stay.
+ *   DRAW        exactly as if lp[i] were -inf for i in R, in every mode; top-p's weights and min-p's threshold refer to the survivors' maximum.
+ * The token is bit for bit pie_sample's over a copy of logprobs with R set to -inf on the same seed and counter; kept_mask is 0 on R and
+ * that call's mask elsewhere, kept_count that call's count without the members of R it counts; the call counter advances as ever.  A greedy
+ * row ignores XTC; probability == 0 is off.  logprobs are only read.
+ * pie_xtc is one record in DEVICE memory (4-byte aligned); pie_xtc_pack fills it in HOST memory: probability in [0, 1], threshold in
+ * (0, 0.5] (log_threshold = (float)log(threshold)), n_special 0..PIE_XTC_SPECIAL_MAX ids never removed (end of sequence, newline):
+ * PIE_E_ARG otherwise, nothing touches a device.  The kernels do not trust the bytes they read: n_special is clamped to 0..16, a special id
+ * outside [0, V) matches nothing, probability and log_threshold only enter comparisons (NaN: nothing is removed).
+ * pie_sample_xtc / pie_sample_rows_xtc: pie_sample / pie_sample_rows plus xtc -- ONE record shared by the rows, or DEVICE [rows] in the
+ * table form -- and removed (nullable) DEVICE int32 [rows] = |R| of the call (0 when the coin says no; a greedy row's is not written).
+ * xtc == NULL: exactly the old op.  One launch more than the same call without (a grid-wide integer atomic min finds the cut and leaves
+ * it in a word of the row's workspace header: pie_sample_workspace_bytes is unchanged, and nothing depends on arrival order). */
+enum { PIE_XTC_SPECIAL_MAX = 16 };
+typedef struct pie_xtc {
+    float log_threshold, probability;
+    int32_t n_special, reserved;
+    int32_t special[PIE_XTC_SPECIAL_MAX];
+} pie_xtc;
+size_t pie_xtc_bytes(void); /* sizeof(pie_xtc) = 80, for bindings */
+int pie_xtc_pack(double probability, double threshold, const int32_t *special, int n_special, pie_xtc *out);
+int pie_sample_xtc(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
+                   void *workspace, int32_t *tokens, int32_t *kept_count, unsigned char *kept_mask, const pie_xtc *xtc, int32_t *removed, void *stream);
+int pie_sample_rows_xtc(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int32_t *tokens, int32_t *kept_count,
+                        unsigned char *kept_mask, const pie_xtc *xtc, int32_t *removed, void *stream);
 /* pie_logits_penalty with per-row windows, one launch, one workgroup per row of logits [rows, V] T.  recent_ids: caller-owned DEVICE int32
  * [rows, 1024], a ring per row: the id fed at position q lives at recent_ids[r][q & 1023].  ids / ctx: the pass's input ids and context
  * lengths [n_src]; out_rows (nullable) [rows]: output row s reads source row i = out_rows ? out_rows[s] : s.  With pos = ctx[i] - 1 the
@@ -755,6 +787,19 @@ int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *recor
  * pie_decoder_spec_step refuses a configured DRY penalty like every other tail. */
 int pie_decoder_set_dry_penalty(pie_decoder *d, const pie_dry_penalty *record, const int32_t *breakers, int32_t *ids_by_pos, int ids_cap);
 int pie_decoder_set_batch_dry_penalty(pie_decoder *d, const pie_dry_penalty *records, const int32_t *breakers, int32_t *recent_ids, int rows_cap);
+/* XTC inside the passes: the configured sampler draws with pie_sample_xtc / pie_sample_rows_xtc instead of pie_sample /
+ * pie_sample_rows: one launch more per pass.  The bound logits, logprobs and top-n records stay those of the distribution before XTC.
+ * pie_decoder_set_xtc: the single-sequence tail, wherever pie_decoder_set_sampler's sampler draws.  record: DEVICE pie_xtc, caller-owned
+ *   and alive while set; its CONTENTS may change between steps in stream order while a captured graph keeps replaying; the address is a
+ *   launch argument: setting, clearing or moving it drops the captured graphs.  NULL switches it off.
+ * pie_decoder_set_batch_xtc: pie_decoder_step_batch (eager or PIE_STEP_GRAPH), _prefill_batch and _step_mixed; record s belongs to output
+ *   row s in pie_decoder_set_batch_tail's row order.  records DEVICE [rows_cap]; the address and rows_cap are part of the captured batch
+ *   graph's key.  NULL switches it off.  rows_cap < 1: PIE_E_ARG; a pass with more output rows than rows_cap: PIE_E_SHAPE before any launch.
+ * Without a sampler (or a batch tail) to act on, a set record is a NO-OP: the greedy tail runs exactly what it runs without, and the record
+ * takes effect as soon as a sampler is set.  Misaligned (4 bytes): PIE_E_ALIGN.  Tensor-parallel decoders refuse both (PIE_E_STATE), and
+ * pie_decoder_spec_step refuses a set record like every other tail. */
+int pie_decoder_set_xtc(pie_decoder *d, const pie_xtc *record);
+int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_cap);
 /* One speculative pass of the single-sequence decoder: m = n_draft drafted ids (draft_ids DEVICE int32 [m]) are verified in one
  * pass over the weights.  In order: (1) rows [the device-side token, draft_0 .. draft_{m - 1}] are gathered on the device (a draft id the
  * embedding could not index is fed as id 0; pie_spec_verify never accepts it) and forwarded from the device-side offset through

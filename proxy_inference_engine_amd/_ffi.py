@@ -53,6 +53,7 @@ EXPORTS = [
     "pie_logprobs_argmax_rows_masked", "pie_logits_bias_rows", "pie_decoder_set_batch_logits_edits",
     "pie_count_penalty_bytes", "pie_count_penalty_pack", "pie_logits_count_penalty_rows", "pie_decoder_set_count_penalty", "pie_decoder_set_batch_count_penalty",
     "pie_dry_penalty_bytes", "pie_dry_penalty_pack", "pie_logits_dry_penalty", "pie_logits_dry_penalty_rows", "pie_decoder_set_dry_penalty", "pie_decoder_set_batch_dry_penalty",
+    "pie_xtc_bytes", "pie_xtc_pack", "pie_sample_xtc", "pie_sample_rows_xtc", "pie_decoder_set_xtc", "pie_decoder_set_batch_xtc",
     "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
 ]
 
@@ -92,6 +93,15 @@ class pie_dry_penalty(C.Structure):
     """One output row's DRY penalty parameters in device memory (include/pie_hip.h)."""
     _fields_ = [("multiplier", C.c_float), ("base", C.c_float), ("allowed_length", C.c_int32), ("range", C.c_int32), ("n_breakers", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+PIE_XTC_SPECIAL_MAX = 16
+
+
+class pie_xtc(C.Structure):
+    """One XTC record in device memory (include/pie_hip.h)."""
+    _fields_ = [("log_threshold", C.c_float), ("probability", C.c_float), ("n_special", C.c_int32), ("reserved", C.c_int32),
+                ("special", C.c_int32 * PIE_XTC_SPECIAL_MAX)]
 
 
 def set_knob(name: str, value: int | None) -> None:
@@ -190,6 +200,13 @@ def load() -> C.CDLL:
     lib.pie_logits_dry_penalty_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
     lib.pie_decoder_set_dry_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.pie_decoder_set_batch_dry_penalty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.pie_xtc_bytes.restype = C.c_size_t
+    lib.pie_xtc_bytes.argtypes = []
+    lib.pie_xtc_pack.argtypes = [C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(pie_xtc)]
+    lib.pie_sample_xtc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64] + [C.c_void_p] * 8
+    lib.pie_sample_rows_xtc.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+    lib.pie_decoder_set_xtc.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pie_decoder_set_batch_xtc.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.pie_ngram_draft_workspace_bytes.restype = C.c_size_t
     lib.pie_ngram_draft_workspace_bytes.argtypes = []
     lib.pie_ngram_draft.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4

@@ -190,7 +190,8 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     if ((rc = logits_tail_launch(c.dtype, d->logits, c.vocab, stats, n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st))) return rc;
     if (d->smp_mode != PIE_SAMPLE_GREEDY) {  // sampler and top-n
         const SampleFeed feed = {&d->state->token, &d->state->pos, d->history, d->hist_cap};
-        if ((rc = sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st)))
+        if ((rc = sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st,
+                                SampleXtc{d->xtc_record, nullptr})))
             return rc;
     }
     if (!d->tlp_n) return PIE_OK;
@@ -879,6 +880,25 @@ int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int
     const bool changed = d->smp_mode != mode || d->smp_temp != temp || d->smp_p != p || d->smp_k != k || d->smp_seed != seed || d->smp_counter != counter || d->smp_ws != workspace;
     d->smp_mode = mode, d->smp_temp = temp, d->smp_p = p, d->smp_k = k, d->smp_seed = seed, d->smp_counter = counter, d->smp_ws = workspace;
     if (changed) drop_graphs(d);
+    return PIE_OK;
+}
+
+int pie_decoder_set_xtc(pie_decoder *d, const pie_xtc *record) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_xtc: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_xtc: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    PIE_REQUIRE(pie_aligned(record, 4), PIE_E_ALIGN, "pie_decoder_set_xtc: the record needs 4-byte alignment");
+    if (d->xtc_record != record) drop_graphs(d);  // a launch argument
+    d->xtc_record = record;
+    return PIE_OK;
+}
+
+int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_cap) {
+    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_xtc: null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_xtc: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (!records) return d->rows.xtc = {}, PIE_OK;  // off
+    PIE_REQUIRE(rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_xtc: rows_cap >= 1");
+    PIE_REQUIRE(pie_aligned(records, 4), PIE_E_ALIGN, "pie_decoder_set_batch_xtc: the records need 4-byte alignment");
+    d->rows.xtc = {records, rows_cap};  // (the batch graph's key holds them: no graph to drop)
     return PIE_OK;
 }
 

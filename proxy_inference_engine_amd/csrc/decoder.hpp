@@ -53,6 +53,10 @@ struct RowsTail {
         int *recent = nullptr;                     // [rows_cap, 1024]
         int rows_cap = 0;
     } dry;
+    struct Xtc {  // pie_decoder_set_batch_xtc: per-row XTC records, read by the batch tail's sampler (nothing without one)
+        const pie_xtc *records = nullptr;  // [rows_cap], nullptr: off
+        int rows_cap = 0;
+    } xtc;
     // everything a captured batch graph bakes in (pie_decoder_step_batch's key): a setter drops no graph, a changed key captures a new one
     void key(std::vector<uintptr_t> &k) const {
         for (uintptr_t v : {(uintptr_t)sampler.table, (uintptr_t)sampler.recent, (uintptr_t)sampler.ws, (uintptr_t)sampler.rows_cap,
@@ -60,7 +64,8 @@ struct RowsTail {
                             (uintptr_t)edits.rows_cap, (uintptr_t)edits.masks, (uintptr_t)edits.mask_words, (uintptr_t)edits.mask_on, (uintptr_t)edits.bias_ids,
                             (uintptr_t)edits.bias_vals, (uintptr_t)edits.bias_n, (uintptr_t)edits.bias_cap,
                             (uintptr_t)counts.records, (uintptr_t)counts.counts, (uintptr_t)counts.rows_cap,
-                            (uintptr_t)dry.records, (uintptr_t)dry.breakers, (uintptr_t)dry.recent, (uintptr_t)dry.rows_cap})
+                            (uintptr_t)dry.records, (uintptr_t)dry.breakers, (uintptr_t)dry.recent, (uintptr_t)dry.rows_cap,
+                            (uintptr_t)xtc.records, (uintptr_t)xtc.rows_cap})
             k.push_back(v);
     }
     // a pass with `out_rows` output rows fits every configured part (checked before any launch)
@@ -69,7 +74,8 @@ struct RowsTail {
                            : edits.rows_cap && out_rows > edits.rows_cap  ? "batch logits edits"
                            : top.n && out_rows > top.rows_cap             ? "top log-probabilities"
                            : counts.records && out_rows > counts.rows_cap ? "batch count penalty"
-                           : dry.records && out_rows > dry.rows_cap       ? "batch DRY penalty" : nullptr;
+                           : dry.records && out_rows > dry.rows_cap       ? "batch DRY penalty"
+                           : xtc.records && out_rows > xtc.rows_cap       ? "batch XTC" : nullptr;
         return over ? pie::fail(PIE_E_SHAPE, std::string(entry) + ": more output rows than the " + over + "'s rows_cap") : PIE_OK;
     }
     // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale
@@ -186,6 +192,9 @@ struct pie_decoder {
     const int *dry_breakers = nullptr;            // [PIE_DRY_BREAKERS_MAX]
     int *dry_ids_by_pos = nullptr;                // [dry_ids_cap]
     int dry_ids_cap = 0;
+    // XTC of the single-sequence step's sampler (pie_decoder_set_xtc): a caller-owned record whose CONTENTS change between
+    // steps; a launch argument of the sampler's launches, read only when a sampler is set.
+    const pie_xtc *xtc_record = nullptr;  // nullptr: off
     RowsTail rows;        // the multi-sequence passes' per-row tail state
     PromptScores prompt;  // the prompt passes' log-probabilities of prompt tokens
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph

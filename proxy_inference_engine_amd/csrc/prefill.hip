@@ -894,7 +894,8 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     // partials and finish: the rows' masks ride the partials pass -- physically last, so a masked id is -inf whatever else is configured
     if ((rc = logits_tail_rows_launch(c.dtype, logits, c.vocab, rows, s->tail_stats, logprobs, next_tokens, st, r.edits.masks, r.edits.mask_words, r.edits.mask_on))) return rc;
     // sampler and top-n
-    if (r.sampler.table && (rc = sample_rows_launch(logprobs, rows, c.vocab, r.sampler.table, r.sampler.ws, next_tokens, nullptr, nullptr, st))) return rc;
+    if (r.sampler.table && (rc = sample_rows_launch(logprobs, rows, c.vocab, r.sampler.table, r.sampler.ws, next_tokens, nullptr, nullptr, st,
+                                                     SampleXtc{r.xtc.records, nullptr}))) return rc;
     return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
 }
 

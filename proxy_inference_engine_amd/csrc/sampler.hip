@@ -32,7 +32,9 @@ constexpr int SMP_BINS = 2048;
 // per-row workspace, in 64-bit words: header | hist digit 0 | hist digit 1 | hist digit 2 | per-workgroup digit-2 counts (u32)
 constexpr int SMP_HDR = 8;
 constexpr size_t smp_row_words(int wgs) { return SMP_HDR + 3 * (size_t)SMP_BINS + (size_t)wgs * 1024 / 2; }
-enum { H_MAXKEY = 0, H_BEST = 1, H_ARRIVE = 2 };
+// H_XTC: the row's XTC cut as ~okey(min over the candidates), 0 = nothing is removed in this call; like H_MAXKEY it is an
+// atomic max's target that k_smp_init must not clear, zeroed again by the row's last draw workgroup
+enum { H_MAXKEY = 0, H_BEST = 1, H_ARRIVE = 2, H_XTC = 3 };
 
 __device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
     const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
@@ -75,6 +77,10 @@ struct SmpArgs {
     int *feed_token, *history;
     const int *feed_pos;
     int hist_cap;
+    // XTC (pie_sample_xtc / pie_sample_rows_xtc): device records (untrusted), one shared by every row or, with a table, one
+    // per row; null: off, and nothing below is launched or read.  removed (nullable) [rows]: |R| of the call
+    const pie_xtc *xtc;
+    int *removed;
 };
 
 // The selection runs in ASCENDING key order with an integer target: the answer is the smallest key T with
@@ -95,6 +101,36 @@ __device__ __forceinline__ SmpArgs smp_row_args(const SmpArgs &in, unsigned row)
     }
     return a;
 }
+// XTC, as every launch behind k_smp_xtc sees it: element i of the row reads as -inf iff on && lp[i] > m && i is no special id.
+struct SmpCut {
+    bool on;
+    float m;             // the smallest candidate log-probability
+    const int *special;  // ids never removed; an id outside [0, V) matches no element
+    int ns;
+};
+__device__ __forceinline__ const pie_xtc *smp_xtc_record(const SmpArgs &a, unsigned row) { return a.xtc ? a.xtc + (a.table ? row : 0u) : nullptr; }
+__device__ __forceinline__ SmpCut smp_cut(const SmpArgs &a, unsigned row, const unsigned long long *ws) {
+    SmpCut c = {false, 0.0f, nullptr, 0};
+    const pie_xtc *rec = smp_xtc_record(a, row);
+    if (!rec) return c;
+    const unsigned nk = (unsigned)__hip_atomic_load(ws + H_XTC, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!nk) return c;  // the coin said no, or no candidate
+    c.on = true, c.m = okey_inv(~nk), c.special = rec->special, c.ns = min(max(rec->n_special, 0), (int)PIE_XTC_SPECIAL_MAX);
+    return c;
+}
+// only elements above the cut get here: at most 1 / threshold of a row
+__device__ __forceinline__ bool smp_special(const SmpCut &c, int i) {
+    for (int s = 0; s < c.ns; ++s)
+        if (c.special[s] == i) return true;
+    return false;
+}
+__device__ __forceinline__ bool smp_removed(const SmpCut &c, float lp, int i) { return c.on && lp > c.m && !smp_special(c, i); }
+// what the sampler sees of element i: removed ? -inf : lp / temp
+__device__ __forceinline__ float smp_elem(const SmpArgs &a, const SmpCut &c, const float *x, int i) {
+    const float lp = x[i];
+    return smp_removed(c, lp, i) ? -INFINITY : lp * a.inv_temp;
+}
+
 __device__ __forceinline__ bool smp_has_select(const SmpArgs &a) { return a.mode == SMP_TOP_P || a.mode == SMP_TOP_K || (a.mode == SMP_MIN_P && a.k > 1); }
 
 // Walks one global histogram (n bins) from bin 0 up: first bin b with cum + h[b] > target.  Every thread returns the same (b, cum below b).
@@ -151,6 +187,37 @@ __device__ __forceinline__ unsigned long long smp_weight(const SmpArgs &a, float
 }
 __device__ __forceinline__ unsigned smp_key(const SmpArgs &a, float xs) { return a.mode == SMP_TOP_P ? okey(xs) : ~okey(xs); }
 
+// XTC's one launch, in front of launch 0 (only with a record): the row's coin, then the cut = the smallest log-probability above
+// log_threshold, as an atomic max over ~okey (the header word's zero is its identity and means "nothing removed").  One candidate alone
+// is its own minimum and nothing lies above it, so |A| < 2 needs no count.  Reads the UNSCALED log-probabilities.
+__global__ void __launch_bounds__(SMP_T) k_smp_xtc(const SmpArgs a_in) {
+    __shared__ unsigned s_m[SMP_T / 64];
+    const unsigned row = blockIdx.y, G = gridDim.x;
+    const SmpArgs a = smp_row_args(a_in, row);
+    if (a.mode == PIE_SAMPLE_GREEDY) return;  // a greedy row ignores XTC
+    const pie_xtc *rec = smp_xtc_record(a, row);
+    // the coin: word 0 of the block no vocabulary index reaches (idx4 <= V / 4 < 2^32 - 1); every workgroup of the row draws the same
+    unsigned r4[4];
+    philox(a.seed, a.table ? a.table[row].calls : a.counter[0], a.table ? 0u : row, 0xFFFFFFFFu, r4);
+    const float u = ((float)(r4[0] >> 8) + 0.5f) * 0x1p-24f;
+    if (!(u < rec->probability)) return;  // (a NaN probability: never)
+    const float log_thr = rec->log_threshold;
+    const float *x = a.logprobs + (size_t)row * a.V;
+    unsigned m = 0;
+    for (int i = blockIdx.x * SMP_SLICE + threadIdx.x; i < min(a.V, (int)(blockIdx.x + 1) * SMP_SLICE); i += SMP_T) {
+        const float lp = x[i];
+        if (lp > log_thr) m = max(m, ~okey(lp));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < SMP_T / 64; ++w) m = max(m, s_m[w]);
+        if (m) atomicMax(reinterpret_cast<unsigned *>(a.ws + (size_t)row * smp_row_words(G) + H_XTC), m);
+    }
+}
+
 // launch 0: clears the row's workspace and finds max(x) (needed by top-p's weights and min-p's threshold)
 __global__ void __launch_bounds__(SMP_T) k_smp_init(const SmpArgs a_in) {
     __shared__ unsigned s_m[SMP_T / 64];
@@ -160,10 +227,11 @@ __global__ void __launch_bounds__(SMP_T) k_smp_init(const SmpArgs a_in) {
     unsigned long long *ws = a.ws + (size_t)row * smp_row_words(G);
     const size_t words = SMP_HDR + 3 * (size_t)SMP_BINS;  // the per-workgroup count table is fully rewritten by digit 2's launch
     for (size_t i = (size_t)blockIdx.x * SMP_T + threadIdx.x; i < words; i += (size_t)G * SMP_T)
-        if (i != H_MAXKEY) ws[i] = 0;
+        if (i != H_MAXKEY && i != H_XTC) ws[i] = 0;
+    const SmpCut cut = smp_cut(a, row, ws);
     const float *x = a.logprobs + (size_t)row * a.V;
     unsigned m = 0;
-    for (int i = blockIdx.x * SMP_SLICE + threadIdx.x; i < min(a.V, (int)(blockIdx.x + 1) * SMP_SLICE); i += SMP_T) m = max(m, okey(x[i] * a.inv_temp));
+    for (int i = blockIdx.x * SMP_SLICE + threadIdx.x; i < min(a.V, (int)(blockIdx.x + 1) * SMP_SLICE); i += SMP_T) m = max(m, okey(smp_elem(a, cut, x, i)));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
     if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
@@ -173,7 +241,8 @@ __global__ void __launch_bounds__(SMP_T) k_smp_init(const SmpArgs a_in) {
         atomicMax(reinterpret_cast<unsigned *>(ws + H_MAXKEY), m);
     }
 }
-// H_MAXKEY must be zero before k_smp_init's atomicMax: cleared by the previous call's draw launch (and by the host at allocation)
+// H_MAXKEY must be zero before k_smp_init's atomicMax, and H_XTC before k_smp_xtc's: cleared by the previous call's draw launch (and by the
+// host at allocation); without XTC nothing ever writes H_XTC
 
 // launches 1..3: one radix digit each (DIGIT 0: bits 31..21, 1: bits 20..10, 2: bits 9..0)
 template <int DIGIT>
@@ -186,6 +255,7 @@ __global__ void __launch_bounds__(SMP_T) k_smp_digit(const SmpArgs a_in) {
     unsigned long long *ws = a.ws + (size_t)row * smp_row_words(G);
     unsigned long long *h0 = ws + SMP_HDR, *h1 = h0 + SMP_BINS, *h2 = h1 + SMP_BINS;
     const float xmax = okey_inv((unsigned)__hip_atomic_load(ws + H_MAXKEY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const SmpCut cut = smp_cut(a, row, ws);
     // the digits decided so far (every workgroup repeats the walk: 16 KB of L2-resident bins)
     unsigned prefix = 0;
     if (DIGIT >= 1) {
@@ -207,7 +277,7 @@ __global__ void __launch_bounds__(SMP_T) k_smp_digit(const SmpArgs a_in) {
     __syncthreads();
     const float *x = a.logprobs + (size_t)row * a.V;
     for (int i = blockIdx.x * SMP_SLICE + threadIdx.x; i < min(a.V, (int)(blockIdx.x + 1) * SMP_SLICE); i += SMP_T) {
-        const float xs = x[i] * a.inv_temp;
+        const float xs = smp_elem(a, cut, x, i);
         const unsigned key = smp_key(a, xs);
         bool mine;
         unsigned d;
@@ -231,13 +301,14 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a_in) {
     __shared__ unsigned long long s_scan[SMP_T + 2];
     __shared__ unsigned s_cnt[SMP_T];
     __shared__ unsigned long long s_best[SMP_T / 64];
-    __shared__ unsigned s_kept[SMP_T / 64];
+    __shared__ unsigned s_kept[SMP_T / 64], s_gone[SMP_T / 64];
     const unsigned row = blockIdx.y, G = gridDim.x;
     const SmpArgs a = smp_row_args(a_in, row);
     if (a.mode == PIE_SAMPLE_GREEDY) return;
     unsigned long long *ws = a.ws + (size_t)row * smp_row_words(G);
     unsigned long long *h0 = ws + SMP_HDR, *h1 = h0 + SMP_BINS, *h2 = h1 + SMP_BINS;
     const float xmax = okey_inv((unsigned)__hip_atomic_load(ws + H_MAXKEY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const SmpCut cut = smp_cut(a, row, ws);
 
     // keep(i) <=> okey(x_i) > T, or == T for the first `eq_take` ties in index order (eq_take = ~0: every tie, as the inclusive bound)
     unsigned T = 0, eq_take = 0xFFFFFFFFu;  // T = 0, all ties: everything (keys of floats are > 0)
@@ -283,11 +354,13 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a_in) {
     const int base = blockIdx.x * SMP_SLICE + 2 * threadIdx.x;
     float xs[2];
     unsigned key[2];
-    bool live[2];
+    bool live[2], gone[2];  // gone: removed by XTC -- it ranks as the -inf it reads as, and is neither kept nor counted
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         live[j] = base + j < a.V && base + j < (int)(blockIdx.x + 1) * SMP_SLICE;
-        xs[j] = live[j] ? x[base + j] * a.inv_temp : -INFINITY;
+        const float lp = live[j] ? x[base + j] : -INFINITY;
+        gone[j] = live[j] && smp_removed(cut, lp, base + j);
+        xs[j] = live[j] && !gone[j] ? lp * a.inv_temp : -INFINITY;
         key[j] = okey(xs[j]);
     }
     unsigned tie_rank = 0;
@@ -303,11 +376,12 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a_in) {
     unsigned r4[4];
     philox(a.seed, call, a.table ? 0u : row, (unsigned)base >> 2, r4);  // ids base, base + 1 share one 4-word block (base is even)
     unsigned long long best = 0;  // packed: okey(x + G) << 32 | ~index  (max = larger value, then lower index)
-    unsigned n_kept = 0;
+    unsigned n_kept = 0, n_gone = 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         bool keep = live[j] && !keep_none && (key[j] > T || (key[j] == T && (eq_take == 0xFFFFFFFFu || tie_rank < eq_take)));
         if (live[j] && key[j] == T && eq_take != 0xFFFFFFFFu) ++tie_rank;
+        if (gone[j]) keep = false, ++n_gone;
         if (a.kept_mask && live[j]) a.kept_mask[(size_t)row * a.V + base + j] = keep ? 1 : 0;
         if (keep_none && live[j]) {  // fall back to the plain argmax
             const unsigned long long cand = ((unsigned long long)key[j] << 32) | (unsigned)~(unsigned)(base + j);
@@ -324,16 +398,23 @@ __global__ void __launch_bounds__(SMP_T) k_smp_draw(const SmpArgs a_in) {
         const unsigned long long ob = __shfl_xor(best, o, 64);
         best = ob > best ? ob : best;
         n_kept += (unsigned)__shfl_xor((int)n_kept, o, 64);
+        n_gone += (unsigned)__shfl_xor((int)n_gone, o, 64);
     }
-    if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best, s_kept[threadIdx.x >> 6] = n_kept;
+    if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best, s_kept[threadIdx.x >> 6] = n_kept, s_gone[threadIdx.x >> 6] = n_gone;
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned kept = 0;
-        for (int w = 0; w < SMP_T / 64; ++w) best = s_best[w] > best ? s_best[w] : best, kept += s_kept[w];
+        unsigned kept = 0, gone_n = 0;
+        for (int w = 0; w < SMP_T / 64; ++w) best = s_best[w] > best ? s_best[w] : best, kept += s_kept[w], gone_n += s_gone[w];
         atomicMax(ws + H_BEST, best);
-        // arrival word: low 32 bits = workgroups done, high 32 bits = kept ids so far
-        const unsigned long long arr = atomicAdd(ws + H_ARRIVE, 1ull | ((unsigned long long)kept << 32)) + (1ull | ((unsigned long long)kept << 32));
-        if ((unsigned)arr == G) {  // last workgroup of the row
+        // arrival word: bits 0..11 = workgroups done (<= 1024), bits 12..31 = ids XTC removed so far (<= 2^19; 0 without), high 32 bits =
+        // kept ids so far
+        const unsigned long long mine = 1ull | ((unsigned long long)gone_n << 12) | ((unsigned long long)kept << 32);
+        const unsigned long long arr = atomicAdd(ws + H_ARRIVE, mine) + mine;
+        if (((unsigned)arr & 0xFFFu) == G) {  // last workgroup of the row
+            if (a.xtc) {
+                ws[H_XTC] = 0;  // ready for the row's next k_smp_xtc
+                if (a.removed) a.removed[row] = (int)(((unsigned)arr >> 12) & 0xFFFFFu);
+            }
             const unsigned long long win = __hip_atomic_load(ws + H_BEST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int tok = (int)~(unsigned)win;
             if (a.table) {
@@ -385,15 +466,17 @@ static void sample_derive(int mode, double temp, double p, int k, float *inv_tem
     *k_out = mode == SMP_TOP_K || mode == SMP_MIN_P ? k : 0;
 }
 
-// pie_sample's launches (arguments already checked: sample_check): 2 (categorical, min-p that keeps one) or 5
+// pie_sample's launches (arguments already checked: sample_check): 2 (categorical, min-p that keeps one) or 5, one more with an XTC record
 int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
-                  void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st) {
+                  void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st, const SampleXtc &xtc) {
     SmpArgs a = {};
     a.logprobs = logprobs, a.V = V, a.mode = mode, a.seed = seed, a.counter = counter, a.ws = (unsigned long long *)workspace;
     a.token_out = tokens, a.kept_count = kept_count, a.kept_mask = kept_mask;
     a.feed_token = feed.token, a.feed_pos = feed.pos, a.history = feed.history, a.hist_cap = feed.hist_cap;
+    a.xtc = xtc.records, a.removed = xtc.records ? xtc.removed : nullptr;
     sample_derive(mode, temp, p, k, &a.inv_temp, &a.thr, &a.k);
     const dim3 grid((unsigned)((V + SMP_SLICE - 1) / SMP_SLICE), (unsigned)rows), block(SMP_T);
+    if (a.xtc) hipLaunchKernelGGL(k_smp_xtc, grid, block, 0, st, a);
     hipLaunchKernelGGL(k_smp_init, grid, block, 0, st, a);
     if (mode == SMP_TOP_P || mode == SMP_TOP_K || (mode == SMP_MIN_P && k > 1)) {
         hipLaunchKernelGGL(k_smp_digit<0>, grid, block, 0, st, a);
@@ -405,13 +488,16 @@ int sample_launch(const float *logprobs, int rows, int V, int mode, double temp,
     return PIE_OK;
 }
 
-// pie_sample_rows' launches (arguments already checked): always the five, every workgroup deciding by its row's record
+// pie_sample_rows' launches (arguments already checked): always the five, every workgroup deciding by its row's record; one more with XTC
+// records
 int sample_rows_launch(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask,
-                       hipStream_t st) {
+                       hipStream_t st, const SampleXtc &xtc) {
     SmpArgs a = {};
     a.logprobs = logprobs, a.V = V, a.mode = PIE_SAMPLE_GREEDY, a.table = table, a.ws = (unsigned long long *)workspace;
     a.token_out = tokens, a.kept_count = kept_count, a.kept_mask = kept_mask;
+    a.xtc = xtc.records, a.removed = xtc.records ? xtc.removed : nullptr;
     const dim3 grid((unsigned)((V + SMP_SLICE - 1) / SMP_SLICE), (unsigned)rows), block(SMP_T);
+    if (a.xtc) hipLaunchKernelGGL(k_smp_xtc, grid, block, 0, st, a);
     hipLaunchKernelGGL(k_smp_init, grid, block, 0, st, a);
     hipLaunchKernelGGL(k_smp_digit<0>, grid, block, 0, st, a);
     hipLaunchKernelGGL(k_smp_digit<1>, grid, block, 0, st, a);
@@ -457,6 +543,39 @@ int pie_sample_rows(const float *logprobs, int rows, int V, pie_row_tail *table,
     PIE_REQUIRE(logprobs && table && tokens && workspace, PIE_E_ARG, "pie_sample_rows: null pointer");
     if (int rc = sample_rows_check("pie_sample_rows", rows, V, table, workspace)) return rc;
     return sample_rows_launch(logprobs, rows, V, table, workspace, tokens, kept_count, kept_mask, (hipStream_t)stream);
+}
+
+size_t pie_xtc_bytes(void) { return sizeof(pie_xtc); }
+
+int pie_xtc_pack(double probability, double threshold, const int32_t *special, int n_special, pie_xtc *out) {
+    PIE_REQUIRE(out && (special || n_special == 0), PIE_E_ARG, "pie_xtc_pack: null pointer");
+    PIE_REQUIRE(probability >= 0.0 && probability <= 1.0, PIE_E_ARG, "pie_xtc_pack: `probability` has to be in [0, 1]");
+    PIE_REQUIRE(threshold > 0.0 && threshold <= 0.5, PIE_E_ARG, "pie_xtc_pack: `threshold` has to be in (0, 0.5]");
+    PIE_REQUIRE(n_special >= 0 && n_special <= PIE_XTC_SPECIAL_MAX, PIE_E_ARG, "pie_xtc_pack: 0 <= n_special <= 16");
+    pie_xtc r = {};
+    r.log_threshold = (float)log(threshold), r.probability = (float)probability, r.n_special = n_special;
+    for (int i = 0; i < n_special; ++i) r.special[i] = special[i];
+    *out = r;
+    return PIE_OK;
+}
+
+int pie_sample_rows_xtc(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int32_t *tokens, int32_t *kept_count,
+                        unsigned char *kept_mask, const pie_xtc *xtc, int32_t *removed, void *stream) {
+    PIE_REQUIRE(logprobs && table && tokens && workspace, PIE_E_ARG, "pie_sample_rows_xtc: null pointer");
+    if (int rc = sample_rows_check("pie_sample_rows_xtc", rows, V, table, workspace)) return rc;
+    PIE_REQUIRE(pie_aligned(xtc, 4) && pie_aligned(removed, 4), PIE_E_ALIGN, "pie_sample_rows_xtc: the XTC records and `removed` need 4-byte alignment");
+    return sample_rows_launch(logprobs, rows, V, table, workspace, tokens, kept_count, kept_mask, (hipStream_t)stream, SampleXtc{xtc, removed});
+}
+
+int pie_sample_xtc(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
+                   void *workspace, int32_t *tokens, int32_t *kept_count, unsigned char *kept_mask, const pie_xtc *xtc, int32_t *removed, void *stream) {
+    PIE_REQUIRE(logprobs && counter && tokens && workspace, PIE_E_ARG, "pie_sample_xtc: null pointer");
+    PIE_REQUIRE(rows >= 1 && rows <= 65535, PIE_E_SHAPE, "pie_sample_xtc: 1 <= rows <= 65535 and 1 <= V <= 524288");
+    if (int rc = sample_check("pie_sample_xtc", V, mode, temp, p, k, workspace)) return rc;
+    PIE_REQUIRE(pie_aligned(xtc, 4) && pie_aligned(removed, 4), PIE_E_ALIGN, "pie_sample_xtc: the XTC record and `removed` need 4-byte alignment");
+    SampleFeed none = {};
+    return sample_launch(logprobs, rows, V, mode, temp, p, k, seed, counter, workspace, tokens, kept_count, kept_mask, none, (hipStream_t)stream,
+                         SampleXtc{xtc, removed});
 }
 
 size_t pie_sample_workspace_bytes(int rows, int V) {

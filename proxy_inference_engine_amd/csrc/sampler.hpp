@@ -18,11 +18,19 @@ struct SampleFeed {
     int hist_cap;
 };
 
+// XTC for a launch sequence (pie_sample_xtc's): device records -- one shared by the rows of sample_launch, one per row of
+// sample_rows_launch -- and the nullable [rows] count of removed ids.  records == nullptr: off, the sequence is pie_sample's own.
+struct SampleXtc {
+    const pie_xtc *records;
+    int *removed;
+};
+
 // pie_sample's argument checks, reported under `who`; nothing is launched
 int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace);
 int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
-                  void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st);
+                  void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st,
+                  const SampleXtc &xtc = {});
 // pie_sample_rows' checks and launches (per-row records in device memory): the multi-sequence passes' tail draws with them
 int sample_rows_check(const char *who, int rows, int V, const void *table, const void *workspace);
 int sample_rows_launch(const float *logprobs, int rows, int V, pie_row_tail *table, void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask,
-                       hipStream_t st);
+                       hipStream_t st, const SampleXtc &xtc = {});

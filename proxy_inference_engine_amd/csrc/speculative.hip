@@ -224,6 +224,7 @@ int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft,
     PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, "pie_decoder_spec_step: not available on int8 KV pages");
     PIE_REQUIRE(!d->tail_configured() && !d->prompt.n, PIE_E_STATE,
                 "pie_decoder_spec_step: speculation is greedy and raw: no sampler, penalty, mask, bias, top-logprobs, counts or prompt scoring may be set");
+    PIE_REQUIRE(!d->xtc_record, PIE_E_STATE, "pie_decoder_spec_step: speculation is greedy: no XTC record may be set");
     const int rows = n_draft + 1;
     PIE_REQUIRE(n_draft >= 1 && rows >= prefill_min_rows(), PIE_E_SHAPE, "pie_decoder_spec_step: fewer rows than the many-row pass takes (run a plain step)");
     PIE_REQUIRE(rows <= SPEC_MAX_ROWS, PIE_E_SHAPE, "pie_decoder_spec_step: at most 31 drafts");

@@ -40,7 +40,9 @@ class SamplingParams:
     inside the passes, after the bias: mask, repetition penalty, bias, frequency / presence.
     dry_multiplier != 0: the DRY penalty over the last dry_range ids the request has been fed, per row inside the passes,
     after the frequency / presence penalties: the token that would extend a repeat of the sequence's tail of at least dry_allowed_length
-    ids loses dry_multiplier * dry_base ** (length - dry_allowed_length).  dry_sequence_breakers: up to 64 token ids a repeat does not cross."""
+    ids loses dry_multiplier * dry_base ** (length - dry_allowed_length).  dry_sequence_breakers: up to 64 token ids a repeat does not cross.
+    xtc_probability > 0 with xtc_threshold in (0, 0.5] (DESIGN.md 19): the request's draw runs under XTC, per row inside the passes' sampler;
+    xtc_special_tokens: up to 16 ids XTC never removes, None: the engine's stop tokens.  A greedy request (temp == 0) ignores XTC."""
     temp: float = 0.0
     top_p: float = 1.0
     top_k: int = -1
@@ -58,6 +60,17 @@ class SamplingParams:
     dry_allowed_length: int = 2
     dry_range: int = 1024
     dry_sequence_breakers: tuple = ()
+    xtc_probability: float = 0.0
+    xtc_threshold: float = 0.0
+    xtc_special_tokens: tuple | None = None
+
+    def xtc(self, stop_tokens=()) -> tuple | None:
+        """(probability, threshold, special ids) under samplers.check_xtc's rules (ValueError otherwise), None when the request draws
+        without XTC: probability 0, or a greedy request."""
+        from ..samplers import check_xtc
+        special = sorted(int(t) for t in stop_tokens) if self.xtc_special_tokens is None else self.xtc_special_tokens
+        checked = check_xtc(self.xtc_probability, self.xtc_threshold, special, "SamplingParams")
+        return None if self.temp == 0 else checked
 
     def hip_spec(self) -> tuple | None:
         """None (greedy) or (mode, temp, p, k) as hip_ops.sample / row_tail_pack take them."""
@@ -215,9 +228,10 @@ class _RowSeats:
     (then `maps` collects their records' maps).  A kind that is None is neither armed nor written.  As a context manager: arms the kinds
     asked for with every row neutral, and clears them on the way out, whatever happened."""
 
-    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None, drys=None):
+    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None, drys=None, xtcs=None):
         self.model, self.max_batch, self.prompts = model, max_batch, prompts
         self.tails, self.edits, self.cnts, self.tops, self.drys = tails, edits, cnts, tops, drys
+        self.xtcs = xtcs if tails is not None else None   # every request's SamplingParams.xtc or None, or None: XTC rides the batch tail's sampler
         self.maps = None if tops is None else [[] for _ in prompts]
         self.bufs = None              # the armed top-n buffers
         self.slots: list = []         # per-request tails: what the device table's row s holds, (request, tokens drawn) or None = greedy
@@ -233,6 +247,9 @@ class _RowSeats:
             if self.tails is not None:
                 m.set_batch_tail(self.max_batch)
                 m.write_batch_tail(every, [SamplingParams().record()] * self.max_batch)   # (a cached table may hold an earlier call's records)
+            if self.xtcs is not None:
+                m.set_batch_xtc(self.max_batch)
+                m.write_batch_xtc(every, [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
             if self.edits is not None:
                 any_mask, cap = any(k is not None for k, _ in self.edits), max(len(b[0]) if b else 0 for _, b in self.edits)
                 m.set_batch_edits(self.max_batch, masks=any_mask, bias_cap=cap)
@@ -253,7 +270,7 @@ class _RowSeats:
 
     def __exit__(self, *exc) -> None:
         for asked, clear in ((self.tails, "clear_batch_tail"), (self.edits, "clear_batch_edits"), (self.cnts, "clear_batch_count_penalty"),
-                             (self.drys, "clear_batch_dry_penalty"),
+                             (self.drys, "clear_batch_dry_penalty"), (self.xtcs, "clear_batch_xtc"),
                              (self.tops, "clear_batch_top_logprobs")):
             if asked is not None:
                 getattr(self.model, clear)()
@@ -342,6 +359,8 @@ class _RowSeats:
                 recs.append(sp.record(w[1], seeds[w[0]]))
                 fed.append(None if sp.repetition_penalty == 1.0 else list(prompts[w[0]]) + list(gen_by.get(w[0], [])[:-1]))
         self.model.write_batch_tail(idx, recs, fed)
+        if self.xtcs is not None:  # a row's XTC record moves with its sampler record
+            self.model.write_batch_xtc(idx, [None if want[s_] is None else self.xtcs[want[s_][0]] for s_ in idx])
 
     def lone_step(self, idx) -> bool:
         """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
@@ -435,7 +454,7 @@ class BatchedEngine:
 
     def _run(self, prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores):
         """generate's body; scores: the call's _PromptScores or None."""
-        tops = edits = cnts = drys = None
+        tops = edits = cnts = drys = xtcs = None
         if logprobs:
             if self.sampler is not None:
                 raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
@@ -462,11 +481,14 @@ class BatchedEngine:
             dry_all = [sp.dry() for sp in params]   # (checked for every request, armed or not)
             if any(sp.dried for sp in params):     # the per-row DRY state is armed only when some request asks for it
                 drys = [d if sp.dried else None for sp, d in zip(params, dry_all)]
+            xtc_all = [sp.xtc(self.stop_tokens) for sp in params]   # (checked for every request, armed or not)
+            if any(x is not None for x in xtc_all):   # the per-row XTC records are armed only when some request asks for them
+                xtcs = xtc_all
             if all(sp.recordless for sp in params):
                 sampling = None               # no record to configure: a request with only a mask, a bias or count penalties arms no batch tail
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops, drys) as seats:
+        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops, drys, xtcs) as seats:
             out = self._generate(prompts, max_new_tokens, seats, scores)
         return out if tops is None else (out, seats.maps)
 

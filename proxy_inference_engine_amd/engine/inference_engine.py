@@ -55,7 +55,9 @@ def fused_tail_spec(processors, sampler, structuring_engine=None, tensor_paralle
     returns (sampler spec or None, repetition_penalty, context_size) -- set_step_tail's arguments -- or None for the host-orchestrated
     branches.  Fused: no structuring engine (its hooks are host callables), processors empty or exactly the one repetition-penalty
     processor with 1 <= context_size <= 1024 (context_size 0 means the whole history upstream, tokens[-0:]), a sampler that is greedy or
-    carries a `hip_spec` (make_sampler's own closures), and a model that is not tensor-parallel (vocabulary-parallel tail)."""
+    carries a `hip_spec` (make_sampler's own closures), and a model that is not tensor-parallel (vocabulary-parallel tail).  A sampler
+    under XTC (`hip_xtc` next to `hip_spec`) is fused like the same sampler without: fused_tail_plan passes its
+    parameters on as plan["xtc"]."""
     if structuring_engine is not None or tensor_parallel:
         return None
     procs = list(processors or [])
@@ -103,6 +105,8 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
     if spec is None:
         return None
     plan = dict(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2], mask=by_kind.get("mask"), bias=by_kind.get("bias"))
+    if spec[0] is not None and getattr(sampler, "hip_xtc", None) is not None:  # XTC rides the sampler's launches
+        plan["xtc"] = tuple(sampler.hip_xtc)
     if "counts" in by_kind:  # (a request without the penalties gets the plan it always got)
         plan["counts"] = by_kind["counts"]
     if "dry" in by_kind:
@@ -163,9 +167,14 @@ class InferenceEngine:
 
     # ------------------------------------------------------------------ samplers / processors
     def make_sampler(self, **kwargs) -> Sampler:
-        """inference_engine.py:299-317.  NB the reference's default is temp=1.0 (sampling); greedy needs temp=0."""
+        """inference_engine.py:299-317.  NB the reference's default is temp=1.0 (sampling); greedy needs temp=0.
+        xtc_probability > 0 with xtc_threshold in (0, 0.5]: the draw runs under XTC; xtc_special_tokens (at most 16 ids)
+        defaults to the engine's stop tokens, so XTC never removes the end of a sequence."""
+        special = kwargs.get("xtc_special_tokens")
         sampler = make_sampler(temp=kwargs.get("temp", 1.0), top_p=kwargs.get("top_p", 1.0), top_k=kwargs.get("top_k", -1),
-                               min_p=kwargs.get("min_p", 0.0), min_tokens_to_keep=kwargs.get("min_tokens_to_keep", 1))
+                               min_p=kwargs.get("min_p", 0.0), min_tokens_to_keep=kwargs.get("min_tokens_to_keep", 1),
+                               xtc_probability=kwargs.get("xtc_probability") or 0.0, xtc_threshold=kwargs.get("xtc_threshold") or 0.0,
+                               xtc_special_tokens=sorted(self.stop_tokens) if special is None else special)
         if self.structuring_engine is None:
             return sampler
         wrapped = lambda x: self.structuring_engine.sample(x, sampler)  # noqa: E731
@@ -320,7 +329,8 @@ class InferenceEngine:
                 set_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
                          token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values),
                          **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}), **counts,
-                         **({} if dry is None else {"dry": (dry.dry_multiplier, dry.dry_base, dry.dry_allowed_length, dry.dry_range, dry.dry_sequence_breakers)}))
+                         **({} if dry is None else {"dry": (dry.dry_multiplier, dry.dry_base, dry.dry_allowed_length, dry.dry_range, dry.dry_sequence_breakers)}),
+                         **({} if plan.get("xtc") is None else {"xtc": plan["xtc"]}))
                 if pixel_values is not None and not fed_back:
                     embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
                     tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)

@@ -746,10 +746,48 @@ def repack_w4m(w: PackedWeight) -> torch.Tensor:
 SAMPLE_MODES = {"categorical": 0, "top_k": 1, "top_p": 2, "min_p": 3}
 
 
-def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0, want_mask: bool = False):
+# ---------------------------------------------------------------- XTC (include/pie_hip.h: pie_xtc)
+XTC_SPECIAL_MAX = _ffi.PIE_XTC_SPECIAL_MAX
+XTC_WORDS = C.sizeof(_ffi.pie_xtc) // 4   # a record as int32 words: a device table is an int32 [rows, XTC_WORDS] tensor
+XTC_PROBABILITY_WORD = 1                  # the fp32 `probability` of a record, as a word index (an engine rewrites it between replays)
+
+
+def xtc_pack(probability: float = 0.0, threshold: float = 0.1, special=()) -> _ffi.pie_xtc:
+    """One XTC record (pie_xtc_pack) in host memory: probability in [0, 1] (0: off), threshold in (0, 0.5], at most 16 special token ids
+    that are never removed.  ValueError outside the ABI's rules.  Needs no device."""
+    ids = [int(i) for i in special]
+    if len(ids) > XTC_SPECIAL_MAX or any(not -2 ** 31 <= i < 2 ** 31 for i in ids):
+        raise ValueError(f"xtc_pack: at most {XTC_SPECIAL_MAX} special tokens, each an int32 token id")
+    rec = _ffi.pie_xtc()
+    arr = (C.c_int32 * max(len(ids), 1))(*ids)
+    _ffi.check(_ffi.load().pie_xtc_pack(float(probability), float(threshold), C.cast(arr, C.c_void_p), len(ids), C.byref(rec)))
+    return rec
+
+
+def xtc_records(records, device=None) -> torch.Tensor:
+    """Records (xtc_pack) as an int32 [rows, XTC_WORDS] tensor, on `device` when given."""
+    import numpy as np
+    host = np.frombuffer(b"".join(bytes(r) for r in records), dtype=np.int32).reshape(len(records), XTC_WORDS).copy()
+    t = torch.from_numpy(host)
+    return t if device is None else t.to(device)
+
+
+def _xtc(xtc, rows: int, device, who: str) -> torch.Tensor:
+    """xtc as a device int32 [>= rows, XTC_WORDS] tensor: a host record (xtc_pack) is uploaded, a device tensor is checked."""
+    if isinstance(xtc, _ffi.pie_xtc):
+        return xtc_records([xtc] * rows, device)
+    _dev(xtc)
+    if xtc.dtype != torch.int32 or not xtc.is_contiguous() or xtc.numel() < rows * XTC_WORDS or xtc.numel() % XTC_WORDS:
+        raise ValueError(f"{who}: xtc is a record (xtc_pack) or a contiguous int32 [>= rows, {XTC_WORDS}] device tensor (xtc_records)")
+    return xtc
+
+
+def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0, want_mask: bool = False, xtc=None,
+           want_removed: bool = False):
     """The stochastic branches of make_sampler (samplers/__init__.py:39-46) as ONE HIP kernel (pie_sample): logprobs fp32 [rows, V] or [V]
     on the GPU -> token ids int32 [rows] on the same device, no host sync.  want_mask: also return (kept_count int32 [rows], kept uint8
-    [rows, V]) -- the filter's kept set, for tests."""
+    [rows, V]) -- the filter's kept set, for tests.  xtc: one record shared by the rows (xtc_pack, or its device form) -- the draw is
+    pie_sample_xtc's; want_removed: the int32 [rows] count of ids XTC removed joins the result as its last member."""
     from .samplers import _rng
     x = logprobs
     if not x.is_cuda:
@@ -768,9 +806,17 @@ def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: in
     tokens = torch.empty(rows, dtype=torch.int32, device=x.device)
     kept = torch.empty(rows, dtype=torch.int32, device=x.device) if want_mask else None
     mask = torch.empty((rows, V), dtype=torch.uint8, device=x.device) if want_mask else None
-    _ffi.check(lib.pie_sample(_ffi.p(x), rows, V, SAMPLE_MODES[mode], float(temp), float(p), int(k), seed, _ffi.p(counter), _ffi.p(ws), _ffi.p(tokens),
-                              _ffi.p(kept) if want_mask else None, _ffi.p(mask) if want_mask else None, _ffi.stream()))
-    return (tokens, kept, mask) if want_mask else tokens
+    if xtc is None and not want_removed:
+        _ffi.check(lib.pie_sample(_ffi.p(x), rows, V, SAMPLE_MODES[mode], float(temp), float(p), int(k), seed, _ffi.p(counter), _ffi.p(ws), _ffi.p(tokens),
+                                  _ffi.p(kept) if want_mask else None, _ffi.p(mask) if want_mask else None, _ffi.stream()))
+        return (tokens, kept, mask) if want_mask else tokens
+    rec = None if xtc is None else _xtc(xtc, 1, x.device, "sample")
+    removed = torch.zeros(rows, dtype=torch.int32, device=x.device) if want_removed else None
+    _ffi.check(lib.pie_sample_xtc(_ffi.p(x), rows, V, SAMPLE_MODES[mode], float(temp), float(p), int(k), seed, _ffi.p(counter), _ffi.p(ws), _ffi.p(tokens),
+                                  _ffi.p(kept), _ffi.p(mask), _ffi.p(rec), _ffi.p(removed), _ffi.stream()))
+    out = (tokens, kept, mask) if want_mask else (tokens,)
+    out = out + (removed,) if want_removed else out
+    return out if len(out) > 1 else tokens
 
 
 _sample_ws: dict = {}
@@ -820,10 +866,11 @@ def _table(table: torch.Tensor, rows: int, who: str) -> None:
 
 
 def sample_rows(logprobs: torch.Tensor, table: torch.Tensor, tokens: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
-                want_mask: bool = False):
+                want_mask: bool = False, xtc: torch.Tensor | None = None, want_removed: bool = False):
     """pie_sample_rows: row r of logprobs fp32 [rows, V] drawn with table[r]'s own sampler, seed and call counter (advanced on the device);
     greedy rows keep tokens[r] as given (zeros when tokens is None).  Returns tokens int32 [rows], with want_mask also (kept_count, kept
-    uint8 [rows, V]) -- rows of greedy records are left unwritten."""
+    uint8 [rows, V]) -- rows of greedy records are left unwritten.  xtc: int32 [>= rows, XTC_WORDS] device records (xtc_records), row r's
+    for row r -- the draw is pie_sample_rows_xtc's; want_removed: the int32 [rows] counts of removed ids join the result last."""
     x = logprobs
     _dev(x)
     if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
@@ -838,8 +885,18 @@ def sample_rows(logprobs: torch.Tensor, table: torch.Tensor, tokens: torch.Tenso
         tokens = torch.zeros(rows, dtype=torch.int32, device=x.device)
     kept = torch.zeros(rows, dtype=torch.int32, device=x.device) if want_mask else None
     mask = torch.zeros((rows, V), dtype=torch.uint8, device=x.device) if want_mask else None
-    _ffi.check(lib.pie_sample_rows(_ffi.p(x), rows, V, _ffi.p(table), _ffi.p(ws), _ffi.p(tokens), _ffi.p(kept), _ffi.p(mask), _ffi.stream()))
-    return (tokens, kept, mask) if want_mask else tokens
+    if xtc is None and not want_removed:
+        _ffi.check(lib.pie_sample_rows(_ffi.p(x), rows, V, _ffi.p(table), _ffi.p(ws), _ffi.p(tokens), _ffi.p(kept), _ffi.p(mask), _ffi.stream()))
+        return (tokens, kept, mask) if want_mask else tokens
+    if isinstance(xtc, _ffi.pie_xtc):
+        raise ValueError("sample_rows: xtc is a device table of one record per row (xtc_records)")
+    rec = None if xtc is None else _xtc(xtc, rows, x.device, "sample_rows")
+    removed = torch.zeros(rows, dtype=torch.int32, device=x.device) if want_removed else None
+    _ffi.check(lib.pie_sample_rows_xtc(_ffi.p(x), rows, V, _ffi.p(table), _ffi.p(ws), _ffi.p(tokens), _ffi.p(kept), _ffi.p(mask), _ffi.p(rec),
+                                       _ffi.p(removed), _ffi.stream()))
+    out = (tokens, kept, mask) if want_mask else (tokens,)
+    out = out + (removed,) if want_removed else out
+    return out if len(out) > 1 else tokens
 
 
 def logits_penalty_rows(logits: torch.Tensor, table: torch.Tensor, recent_ids: torch.Tensor, ids: torch.Tensor, ctx: torch.Tensor,

@@ -115,9 +115,9 @@ class Model:
     # the step's configurable tail is the text tower's (llama/language.py: set_step_tail)
     def set_step_tail(self, sampler=None, repetition_penalty: float = 1.0, context_size: int = 60, token_mask=None, logit_bias=None,
                       top_logprobs: int | None = None, frequency_penalty: float = 0.0, presence_penalty: float = 0.0,
-                      count_start: int | None = None, dry: tuple | None = None) -> None:
+                      count_start: int | None = None, dry: tuple | None = None, xtc: tuple | None = None) -> None:
         self.language_model.set_step_tail(sampler, repetition_penalty, context_size, token_mask, logit_bias, top_logprobs, frequency_penalty,
-                                          presence_penalty, count_start, dry)
+                                          presence_penalty, count_start, dry, xtc)
 
     def reset_step_counts(self, start: int, generated_ids=()) -> None:
         self.language_model.reset_step_counts(start, generated_ids)

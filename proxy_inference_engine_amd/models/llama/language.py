@@ -309,6 +309,8 @@ class Model(RowsTailState):
         # the DRY penalty: the step's record + 64-entry breaker table at stable addresses, made when first used;
         # (multiplier, base, allowed_length, range, breaker ids) while switched on.
         self._dry, self._dry_rec, self._dry_brk = None, None, None
+        # XTC: the step's record at a stable address, made when first used; (probability, threshold, special ids) while on.
+        self._xtc, self._xtc_rec = None, None
         self._spec = None   # speculative decoding's record and workspaces, made when first used
         self._init_rows_state()  # the multi-sequence passes' per-row tail state (rows_state.py)
         torch.cuda.synchronize(device)
@@ -371,7 +373,8 @@ class Model(RowsTailState):
     # ------------------------------------------------------------------ the step's tail
     def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
                       token_mask=None, logit_bias=None, top_logprobs: int | None = None, frequency_penalty: float = 0.0,
-                      presence_penalty: float = 0.0, count_start: int | None = None, dry: tuple | None = None) -> None:
+                      presence_penalty: float = 0.0, count_start: int | None = None, dry: tuple | None = None,
+                      xtc: tuple | None = None) -> None:
         """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
         DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
@@ -394,12 +397,17 @@ class Model(RowsTailState):
         dry: None (off) or (multiplier, base, allowed_length, range, breaker_ids) -- the DRY penalty (hip_ops.check_dry's rules; DESIGN.md
         18) over the last `range` fed ids (`fed_ids`), behind the frequency / presence penalties.  The model owns one record and one
         64-entry breaker table at stable addresses: new values are a copy and a replay, not a re-capture.  A multiplier of 0 is off.
+        xtc: None (off) or (probability, threshold, special_ids) -- XTC (hip_ops.xtc_pack's rules): the sampler's draw hides
+        the top choices with the given probability; the returned logits, logprobs and top-n record stay those before XTC.  Ignored without
+        a sampler (a greedy tail), and a probability of 0 is off.  The model owns one record at a stable address (`step_xtc_record`): new
+        values are a copy and a replay, not a re-capture.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
         self._set_tail_edits(token_mask, logit_bias)
         self._set_tail_top_logprobs(top_logprobs)
         self._set_tail_counts(frequency_penalty, presence_penalty, count_start)
         self._set_tail_dry(dry)
+        self._set_tail_xtc(xtc if sampler is not None else None)
         pen = (float(repetition_penalty), int(context_size)) if repetition_penalty != 1.0 and context_size != 0 else None
         seed = counter = None
         if sampler is not None:
@@ -533,6 +541,35 @@ class Model(RowsTailState):
         if self._dry is None:
             _ffi.check(lib.pie_decoder_set_dry_penalty(self._dec, _ffi.p(self._dry_rec), _ffi.p(self._dry_brk), _ffi.p(self.fed_ids), self.fed_ids.numel()))
         self._dry = dry
+
+    def _set_tail_xtc(self, xtc) -> None:
+        """The XTC parameters into the model's own record; the library is asked only when the feature is switched on or off."""
+        if xtc is not None:
+            if len(xtc) != 3:
+                raise ValueError("set_step_tail: xtc is (probability, threshold, special_ids)")
+            xtc = (float(xtc[0]), float(xtc[1]), tuple(int(i) for i in xtc[2]))
+            rec = hip_ops.xtc_pack(*xtc)  # (the ABI's range checks, before anything changes)
+            if xtc[0] == 0.0:
+                xtc = None
+        if xtc == self._xtc:
+            return
+        lib = _ffi.load()
+        if xtc is None:
+            _ffi.check(lib.pie_decoder_set_xtc(self._dec, None))
+            self._xtc = None
+            return
+        if self._xtc_rec is None:
+            self._xtc_rec = torch.zeros((1, hip_ops.XTC_WORDS), dtype=torch.int32, device=self.device)
+        self._xtc_rec.copy_(hip_ops.xtc_records([rec]))
+        if self._xtc is None:
+            _ffi.check(lib.pie_decoder_set_xtc(self._dec, _ffi.p(self._xtc_rec)))
+        self._xtc = xtc
+
+    @property
+    def step_xtc_record(self) -> torch.Tensor | None:
+        """The step's XTC record on the device (int32 [1, hip_ops.XTC_WORDS]) while set_step_tail(xtc=) is on, else None: rewriting its
+        contents in stream order changes the next replay's draw without a new capture."""
+        return self._xtc_rec if self._xtc is not None else None
 
     @property
     def step_tail_dry(self) -> tuple | None:

@@ -53,7 +53,8 @@ class RowsTailState:
         self._batch_dry_bufs = RowsCapCache(lambda r: {
             "records": hip_ops.dry_penalty_records([hip_ops.dry_penalty_pack()] * r, dev), "breakers": i32((r, hip_ops.DRY_BREAKERS_MAX)),
             "recent": i32((r, hip_ops.RECENT_IDS))})
-        self._batch_tail = self._batch_edits = self._batch_counts = self._batch_dry = None   # the armed buffers
+        self._batch_xtc_bufs = RowsCapCache(lambda r: {"records": torch.zeros((r, hip_ops.XTC_WORDS), dtype=torch.int32, device=dev)})
+        self._batch_tail = self._batch_edits = self._batch_counts = self._batch_dry = self._batch_xtc = None   # the armed buffers
         self._prompt_lp_ws = None      # (block_rows, its logits block + the op's workspace)
 
     # ------------------------------------------------------------------ the multi-sequence passes' tail
@@ -318,3 +319,36 @@ class RowsTailState:
         """The multi-sequence passes launch what they launched before set_batch_dry_penalty; the buffers stay cached."""
         _ffi.check(_ffi.load().pie_decoder_set_batch_dry_penalty(self._dec, None, None, None, 0))
         self._batch_dry = None
+
+    # ------------------------------------------------------------------ the multi-sequence passes' XTC (DESIGN.md 19)
+    def set_batch_xtc(self, rows_cap: int) -> dict:
+        """From now on the batch tail's sampler draws every output row under the row's own XTC record (pie_decoder_set_batch_xtc):
+        {"records": int32 [rows_cap, XTC_WORDS]}, returned, owned by the model and kept per rows_cap at a stable address (the 4 most
+        recent, like set_batch_tail's buffers).  Fresh records are zero -- probability 0, off -- until write_batch_xtc arms a row.  Without
+        a batch tail (set_batch_tail) the passes stay greedy and ignore the records."""
+        rows_cap = int(rows_cap)
+        if rows_cap < 1:
+            raise ValueError("set_batch_xtc: rows_cap >= 1")
+        bx = self._batch_xtc_bufs.get(rows_cap)
+        _ffi.check(_ffi.load().pie_decoder_set_batch_xtc(self._dec, _ffi.p(bx["records"]), rows_cap))
+        self._batch_xtc = bx
+        return bx
+
+    def write_batch_xtc(self, rows: list[int], records: list) -> None:
+        """Rewrites the records of `rows` of the armed buffer, in stream order, one copy for all of them -- when a row's occupant changes.
+        records[i]: (probability, threshold, special_ids) of the occupant of rows[i] (hip_ops.xtc_pack's rules), or None: a zero record."""
+        bx = self._batch_xtc
+        if bx is None:
+            raise RuntimeError("write_batch_xtc: no batch XTC is set (set_batch_xtc)")
+        if not rows:
+            return
+        if len(records) != len(rows):
+            raise ValueError("write_batch_xtc: one record per row")
+        packed = [_ffi.pie_xtc() if rec is None else hip_ops.xtc_pack(*rec) for rec in records]
+        idx = torch.tensor(rows, dtype=torch.long, device=self.device)
+        bx["records"].index_copy_(0, idx, hip_ops.xtc_records(packed, self.device))
+
+    def clear_batch_xtc(self) -> None:
+        """The multi-sequence passes launch what they launched before set_batch_xtc; the buffers stay cached."""
+        _ffi.check(_ffi.load().pie_decoder_set_batch_xtc(self._dec, None, 0))
+        self._batch_xtc = None

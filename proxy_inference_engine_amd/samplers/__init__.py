@@ -20,6 +20,7 @@ from .categorical import categorical_sampling
 from .min_p import min_p_sampling
 from .top_k import top_k_sampling
 from .top_p import top_p_sampling
+from .xtc import check_xtc, xtc_sampling
 
 
 def greedy(logprobs: torch.Tensor) -> torch.Tensor:
@@ -41,12 +42,17 @@ def _argmax_f32(x: torch.Tensor) -> torch.Tensor:
 
 
 def make_sampler(temp: float = 0.0, top_p: float = 0.0, min_p: float = 0.0, min_tokens_to_keep: int = 1,
-                 top_k: int = -1) -> Callable[[torch.Tensor], torch.Tensor]:
+                 top_k: int = -1, xtc_probability: float = 0.0, xtc_threshold: float = 0.0,
+                 xtc_special_tokens=()) -> Callable[[torch.Tensor], torch.Tensor]:
     """The stochastic closures carry `hip_spec = (mode, temp, p, k)` -- hip_ops.sample's arguments -- so the engine can run the same
-    draw inside the decode step's tail (Model.set_step_tail) instead of calling the closure."""
+    draw inside the decode step's tail (Model.set_step_tail) instead of calling the closure.
+    xtc_probability > 0 (with xtc_threshold in (0, 0.5] and up to 16 xtc_special_tokens; samplers/xtc.py): the chosen
+    branch draws under XTC, and the closure also carries `hip_xtc = (probability, threshold, special ids)` -- set_step_tail's `xtc`.
+    The greedy branch ignores XTC, as upstream's make_sampler does; with xtc_probability == 0 nothing changes."""
     if temp == 0:
         return greedy
-    elif top_p > 0 and top_p < 1.0:
+    xtc = check_xtc(xtc_probability, xtc_threshold, xtc_special_tokens, "make_sampler")
+    if top_p > 0 and top_p < 1.0:
         sampler, spec = (lambda x: top_p_sampling(x, top_p, temp)), ("top_p", temp, top_p, 0)
     elif min_p != 0.0:
         sampler, spec = (lambda x: min_p_sampling(x, min_p, min_tokens_to_keep, temp)), ("min_p", temp, min_p, min_tokens_to_keep)
@@ -54,6 +60,9 @@ def make_sampler(temp: float = 0.0, top_p: float = 0.0, min_p: float = 0.0, min_
         sampler, spec = (lambda x: top_k_sampling(x, top_k, temp)), ("top_k", temp, 0.0, top_k)
     else:
         sampler, spec = (lambda x: categorical_sampling(x, temp)), ("categorical", temp, 0.0, 0)
+    if xtc is not None:
+        sampler = xtc_sampling(spec, xtc)
+        sampler.hip_xtc = xtc
     sampler.hip_spec = spec
     return sampler
 
