@@ -481,6 +481,28 @@ int pie_ngram_draft(const int32_t *ids, const int32_t *len, int cap, int ngram_m
 size_t pie_spec_verify_workspace_bytes(int rows);
 int pie_spec_verify(const void *logits, int rows, int V, int dtype, const int32_t *draft, int32_t *out_tokens, int32_t *out_n, float *logprobs,
                     void *workspace, void *stream);
+/* pie_spec_verify_sampled: pie_spec_verify under a stochastic sampler.  A prompt-lookup draft is a point mass, so "draw row
+ * r from the model's own distribution with the draw the plain loop would have used for that token, and accept while the draw equals the
+ * draft" is exact and needs no rejection-sampling arithmetic.  Let c = counter[0] at entry, READ ON THE DEVICE (no host round trip):
+ *   - logprobs (required) fp32 [rows, V]: EVERY row r gets pie_logprobs_argmax's bits of row r alone (the draws read them before n_acc is
+ *     known -- unlike pie_spec_verify, which leaves the rows behind the accepted run alone);
+ *   - t_r = the token pie_sample_xtc(logprobs + r * V, rows = 1, V, mode, temp, p, k, seed, counter = {c + r, 0}, ..., xtc) draws (pie_sample's
+ *     when xtc == NULL), bit for bit: row r goes through pie_sample_rows(_xtc)'s launches with a record whose calls = c + r;
+ *   - n_acc = the largest j with draft[i] == t_i for all i < j; a draft id outside [0, V) is never accepted and never used as an index;
+ *   - out_n [1] = n_acc + 1; out_tokens [rows] = t_0 .. t_{n_acc}, then -1;
+ *   - afterwards counter = {c + out_n, 0}: the draws of the rows behind the accepted run are discarded and their stream positions are NOT
+ *     consumed, so token number j of a generation is always draw number j of the seed, whether a step or a pass produced it.
+ * xtc (nullable): ONE DEVICE record shared by the rows.  Launches: the partials and the finish over every row (2), one workgroup that
+ * fills the rows' records from counter[0] (1), pie_sample_rows' 5 (6 with xtc), and one thread that accepts, writes the outputs and stores
+ * the counter: 9 or 10.  No atomics beyond the sampler's own; nothing depends on arrival order.  workspace:
+ * pie_spec_verify_sampled_workspace_bytes(rows, V) bytes (0 for refused sizes), 16-byte aligned, ZEROED ONCE by the caller (as
+ * pie_sample's) and reusable from call to call.  Each before any launch: a null pointer (xtc excepted), mode PIE_SAMPLE_GREEDY (use
+ * pie_spec_verify), a dtype that is neither PIE_BF16 nor PIE_F16, a parameter outside pie_sample's rules: PIE_E_ARG; rows outside 2..32, V
+ * outside 1..524288: PIE_E_SHAPE; logits not 2-byte, draft, xtc or an output not 4-byte, the counter not 8-byte, the workspace not 16-byte
+ * aligned: PIE_E_ALIGN. */
+size_t pie_spec_verify_sampled_workspace_bytes(int rows, int V);
+int pie_spec_verify_sampled(const void *logits, int rows, int V, int dtype, const int32_t *draft, int mode, double temp, double p, int k, unsigned long long seed,
+                            unsigned long long *counter, const pie_xtc *xtc, int32_t *out_tokens, int32_t *out_n, float *logprobs, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------- fused decode step
  * One forward of Model.__call__ (models/llama/language.py:199-210) for inputs[1,1] over per-layer
@@ -814,7 +836,8 @@ int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_c
  * The caller has made room for m + 1 rows at the offset (pie_decoder_set_kv / _set_paged_kv, block table filled).  4 launches (the gather and
  * pie_spec_verify's three) beyond pie_decoder_prefill's; nothing is captured in a graph, and a decoder
  * that never calls this entry launches exactly what it launches without it.
- * Speculation here is greedy and raw.  PIE_E_STATE before any launch: a tensor-parallel decoder; a quantized or rotating KV cache; int8
+ * Speculation here is greedy and raw (the pass under a sampler, a repetition penalty and a logit bias is pie_decoder_spec_step_tail,
+ * below).  PIE_E_STATE before any launch: a tensor-parallel decoder; a quantized or rotating KV cache; int8
  * pages (PIE_OPT_KV_I8); any configured tail (sampler, repetition penalty, mask, bias, top-logprobs, counts) or prompt scoring.
  * PIE_E_SHAPE before any launch: m + 1 below the many-row pass's first row count (PIE_KNOB_PREFILL_MIN, default 6: the rows would run as
  * iterated steps -- the host runs a plain step instead) or above 32.  workspace: pie_decoder_spec_workspace_bytes(d, m + 1) bytes (0 for
@@ -822,6 +845,28 @@ int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_c
 size_t pie_decoder_spec_workspace_bytes(const pie_decoder *d, int rows);
 int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
                           int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
+/* One speculative pass under the decoder's configured single-sequence tail: pie_decoder_spec_step's arguments and row bounds
+ * (m + 1 rows, PIE_KNOB_PREFILL_MIN .. 32), except that logprobs_rows is REQUIRED and every one of its m + 1 rows is written.  With o = the
+ * device-side offset, in order: (1) the gather and pie_decoder_prefill with raw logits on every row, as pie_decoder_spec_step; the pass's
+ * own last-row tail stays raw and greedy, so the sampler's counter does not move there; (2) unless neither a repetition penalty nor a
+ * logit bias is set, ONE edit launch, a workgroup per row r: pie_logits_penalty over the ids of positions max(0, o + r + 1 - context) ..
+ * o + r -- ids_by_pos[q] for q < o, the device-side token for q == o (recorded at ids_by_pos[o], as the step's tail records its input),
+ * draft[q - o - 1] for q > o (not recorded) -- then pie_logits_bias with the decoder's table: row r's processed logits are those of the
+ * step's tail on that row alone; (3) pie_spec_verify_sampled's launches on the processed block with the decoder's mode / temp / p / k / seed
+ * / counter / XTC record -- under the greedy sampler (a penalty and / or a bias only) the rows' tokens are the argmaxes of the processed
+ * rows, nothing is drawn and the counter is untouched; (4) its accept launch leaves what pie_decoder_spec_step's leaves, and
+ * ids_by_pos[o + 1 + i] = token i for i < out_n (with a penalty set), so that the plain step that follows finds its window whole, and the
+ * counter = {c + out_n, 0}.  Afterwards the decoder is where out_n plain steps under the same tail would have left it, and the workspace's
+ * block holds the PROCESSED logits.  3 or 4 launches (greedy sampler), 9 .. 11 otherwise, beyond the gather and pie_decoder_prefill's;
+ * nothing is captured in a graph, and a decoder that never calls this entry launches exactly what it launches without it.
+ * Accepted tail settings, at least one of which must be set (else PIE_E_STATE: that pass is pie_decoder_spec_step's):
+ * pie_decoder_set_sampler (any mode), pie_decoder_set_xtc, pie_decoder_set_logits_penalty, pie_decoder_set_logit_bias.  PIE_E_STATE before
+ * any launch: a token mask, a top-logprobs record, frequency / presence counts, a DRY penalty, prompt scoring, a tensor-parallel decoder, a
+ * quantized or rotating KV cache, int8 pages.  workspace: pie_decoder_spec_tail_workspace_bytes(d, m + 1) bytes (0 for refused row
+ * counts), 16-byte aligned, caller-owned, ZEROED ONCE and reusable from pass to pass. */
+size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows);
+int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                               int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -55,6 +55,7 @@ EXPORTS = [
     "pie_dry_penalty_bytes", "pie_dry_penalty_pack", "pie_logits_dry_penalty", "pie_logits_dry_penalty_rows", "pie_decoder_set_dry_penalty", "pie_decoder_set_batch_dry_penalty",
     "pie_xtc_bytes", "pie_xtc_pack", "pie_sample_xtc", "pie_sample_rows_xtc", "pie_decoder_set_xtc", "pie_decoder_set_batch_xtc",
     "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
+    "pie_spec_verify_sampled_workspace_bytes", "pie_spec_verify_sampled", "pie_decoder_spec_tail_workspace_bytes", "pie_decoder_spec_step_tail",
 ]
 
 
@@ -216,6 +217,12 @@ def load() -> C.CDLL:
     lib.pie_decoder_spec_workspace_bytes.restype = C.c_size_t
     lib.pie_decoder_spec_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.pie_decoder_spec_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_spec_verify_sampled_workspace_bytes.restype = C.c_size_t
+    lib.pie_spec_verify_sampled_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pie_spec_verify_sampled.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64] + [C.c_void_p] * 7
+    lib.pie_decoder_spec_tail_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_spec_tail_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    lib.pie_decoder_spec_step_tail.argtypes = lib.pie_decoder_spec_step.argtypes
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

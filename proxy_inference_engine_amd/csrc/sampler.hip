@@ -34,7 +34,7 @@ constexpr int SMP_HDR = 8;
 constexpr size_t smp_row_words(int wgs) { return SMP_HDR + 3 * (size_t)SMP_BINS + (size_t)wgs * 1024 / 2; }
 // H_XTC: the row's XTC cut as ~okey(min over the candidates), 0 = nothing is removed in this call; like H_MAXKEY it is an
 // atomic max's target that k_smp_init must not clear, zeroed again by the row's last draw workgroup
-enum { H_MAXKEY = 0, H_BEST = 1, H_ARRIVE = 2, H_XTC = 3 };
+enum { H_MAXKEY = SMP_WS_MAXKEY_WORD, H_BEST = 1, H_ARRIVE = 2, H_XTC = SMP_WS_XTC_WORD };
 
 __device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
     const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];

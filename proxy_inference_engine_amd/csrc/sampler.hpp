@@ -9,6 +9,11 @@ __device__ __forceinline__ unsigned okey(float v) {
 }
 __device__ __forceinline__ float okey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
+// A row's workspace starts with a header of 64-bit words.  A call clears every word it reads except these two, which it expects to be zero
+// and leaves zero (the host zeroes the workspace once); a caller that moves rows about inside one allocation re-arms them itself
+// (speculative.hip).  A row's stride is pie_sample_workspace_bytes(1, V).
+constexpr int SMP_WS_MAXKEY_WORD = 0, SMP_WS_XTC_WORD = 3;
+
 // Where the decode step's tail wants the drawn id besides `tokens` (rows = 1): the device-side state's fed-back token and the token history
 // at the (already advanced) position *pos.  All null: a plain pie_sample.
 struct SampleFeed {

@@ -15,6 +15,15 @@
 //   3. k_spec_accept over (TAIL_FINISH_BLOCKS, rows): every workgroup counts the accepted drafts from the rows' tokens (at most 31
 //      comparisons); a row behind them leaves at once, the others write their slice of the log-probabilities as k_logits_finish does;
 //      workgroup (0, 0) writes the tokens, their number and -- for the decoder -- the device-side state.
+// pie_spec_verify_sampled, 3 launches under the greedy sampler, 9 with a sampler (10 with an XTC record):
+//   1. k_logits_stats and k_logits_finish over every row (logits_tail_rows_launch): all log-probabilities and the rows' argmaxes;
+//   2. k_spec_fill_rows, one workgroup: the call's first stream position c = counter[0], read on the device, and one pie_row_tail per row
+//      with calls = c + r (and the shared XTC record once per row), in the workspace;
+//   3. pie_sample_rows(_xtc)'s launches (sample_rows_launch): row r drawn as the one-row pie_sample call number c + r of the seed;
+//   4. k_spec_accept_sampled, ONE thread: the accepted run against the drawn tokens, the outputs, counter = {c + n, 0} and -- for the
+//      decoder -- the device-side state, through the functions k_spec_accept ends in.
+// pie_decoder_spec_step_tail puts k_spec_edit_rows in front: one workgroup per row applies the decoder's repetition penalty over the row's
+// own window (ids_by_pos below the offset, the fed token at it, the drafts behind it) and its logit bias (tail.hpp's phases).
 #include "speculative.hpp"
 
 #include "decoder.hpp"
@@ -110,39 +119,145 @@ struct SpecArgs {
     SpecState s;
 };
 
-template <class T>
-__global__ void __launch_bounds__(256) k_spec_accept(const SpecArgs a) {
-    __shared__ int s_acc;
-    if (threadIdx.x == 0) {  // the accepted drafts: the longest run draft[i] == the token row i chose; an id outside [0, V) ends it
-        int n = 0;
-        while (n < a.rows - 1) {
-            const int d = a.draft[n];
-            if (d < 0 || d >= a.V || d != a.tok[n]) break;
-            ++n;
-        }
-        s_acc = n;
+// The accepted drafts: the longest run draft[i] == the token row i chose; an id outside [0, V) ends it.  At most rows - 1 comparisons.
+__device__ __forceinline__ int spec_count_accepted(const int *draft, const int *tok, int rows, int V) {
+    int n = 0;
+    while (n < rows - 1) {
+        const int d = draft[n];
+        if (d < 0 || d >= V || d != tok[n]) break;
+        ++n;
     }
-    __syncthreads();
-    const int n_acc = s_acc, r = blockIdx.y;
-    if (r > n_acc) return;  // block-uniform: a row behind the accepted run is not written
-    if (a.logprobs) logits_write_logprobs<T>(a.logits + (size_t)r * a.V, a.V, a.lse[r], a.logprobs + (size_t)r * a.V);
-    if (r != 0 || blockIdx.x != 0 || threadIdx.x != 0) return;
-    for (int i = 0; i < a.rows; ++i) a.out_tokens[i] = i <= n_acc ? a.tok[i] : -1;
-    const int n = n_acc + 1, last = a.tok[n_acc];
-    *a.out_n = n;
-    const SpecState &s = a.s;
+    return n;
+}
+
+// What the one writer of a verify leaves: the tokens, their number and -- for the decoder -- the device-side state (speculative.hpp).
+__device__ __forceinline__ void spec_commit(const SpecState &s, const int *tok, int rows, int n_acc, int *out_tokens, int *out_n) {
+    for (int i = 0; i < rows; ++i) out_tokens[i] = i <= n_acc ? tok[i] : -1;
+    const int n = n_acc + 1, last = tok[n_acc];
+    *out_n = n;
     if (!s.state) return;
-    const int o = s.state->pos - a.rows;  // the pass and its tail advanced the position over every row
-    for (int i = 0; i < n; ++i) {         // the token row i chose occupies position o + 1 + i
+    const int o = s.state->pos - rows;  // the pass and its tail advanced the position over every row
+    for (int i = 0; i < n; ++i) {       // the token row i chose occupies position o + 1 + i
         const int p = o + 1 + i;
-        if (s.history && p >= 0 && p < s.hist_cap) s.history[p] = a.tok[i];
-        if (s.seq_ids && p >= 0 && p < s.seq_cap) s.seq_ids[p] = a.tok[i];
+        if (s.history && p >= 0 && p < s.hist_cap) s.history[p] = tok[i];
+        if (s.seq_ids && p >= 0 && p < s.seq_cap) s.seq_ids[p] = tok[i];
+        if (s.ids_by_pos && p >= 0 && p < s.ids_cap) s.ids_by_pos[p] = tok[i];
     }
     if (s.seq_ids && o >= 0 && o < s.seq_cap) s.seq_ids[o] = s.fed[0];
     if (s.seq_len) *s.seq_len = o + n + 1;
     if (s.token_out) *s.token_out = last;
     s.state->token = last;
     s.state->pos = o + n;
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_spec_accept(const SpecArgs a) {
+    __shared__ int s_acc;
+    if (threadIdx.x == 0) s_acc = spec_count_accepted(a.draft, a.tok, a.rows, a.V);
+    __syncthreads();
+    const int n_acc = s_acc, r = blockIdx.y;
+    if (r > n_acc) return;  // block-uniform: a row behind the accepted run is not written
+    if (a.logprobs) logits_write_logprobs<T>(a.logits + (size_t)r * a.V, a.V, a.lse[r], a.logprobs + (size_t)r * a.V);
+    if (r != 0 || blockIdx.x != 0 || threadIdx.x != 0) return;
+    spec_commit(a.s, a.tok, a.rows, n_acc, a.out_tokens, a.out_n);
+}
+
+// ---------------------------------------------------------------- the verify under a sampler
+// pie_spec_verify_sampled's workspace: the tail's partials | the rows' tokens | the call's first stream position | one pie_row_tail and one
+// pie_xtc per row | pie_sample_rows' workspace (the part that has to be zeroed once).
+struct SpecSampledLayout {
+    size_t tok, base, table, xtc, smp, bytes;
+    SpecSampledLayout(int rows, int V) {
+        tok = sizeof(LogitStat) * TAIL_STAT_TILES * (size_t)rows;
+        base = tok + sizeof(int) * SPEC_MAX_ROWS;
+        table = base + 16;
+        xtc = table + sizeof(pie_row_tail) * SPEC_MAX_ROWS;
+        smp = (xtc + sizeof(pie_xtc) * SPEC_MAX_ROWS + 15) & ~(size_t)15;
+        bytes = smp + pie_sample_workspace_bytes(rows, V);
+    }
+};
+
+struct SpecFillArgs {
+    int rows, mode, k;
+    float inv_temp, thr;
+    unsigned long long seed;
+    const unsigned long long *counter;
+    const pie_xtc *xtc;  // nullable: the one record every row shares
+    unsigned long long *base;
+    pie_row_tail *table;
+    pie_xtc *xtc_rows;
+    unsigned long long *smp_ws;  // pie_sample_rows' workspace, row stride smp_row_words 64-bit words
+    size_t smp_row_words;
+};
+
+// Row r draws at stream position counter[0] + r: the position a plain loop's draw number r from here would have.  The position is device
+// memory (a replayed step advances it without the host), so the records are made here and not by the caller.
+__global__ void __launch_bounds__(SPEC_MAX_ROWS) k_spec_fill_rows(const SpecFillArgs a) {
+    const int r = threadIdx.x;
+    if (r >= a.rows) return;
+    const unsigned long long c = a.counter[0];
+    if (r == 0) *a.base = c;
+    pie_row_tail t = {};
+    t.mode = a.mode, t.inv_temp = a.inv_temp, t.thr = a.thr, t.k = a.k, t.seed = a.seed, t.calls = c + (unsigned long long)r;
+    t.penalty = 1.0f, t.context_size = 1;
+    a.table[r] = t;
+    if (a.xtc) a.xtc_rows[r] = *a.xtc;
+    // The workspace's parts lie where the call's row count puts them, so a row's header may hold what a pass of another size left there:
+    // the two words the sampler expects to be zero are zeroed here, in front of its launches.
+    unsigned long long *hdr = a.smp_ws + (size_t)r * a.smp_row_words;
+    hdr[SMP_WS_MAXKEY_WORD] = 0ull, hdr[SMP_WS_XTC_WORD] = 0ull;
+}
+
+struct SpecSampledArgs {
+    int rows, V;
+    const int *draft;  // [rows - 1]
+    const int *tok;    // [rows]: the rows' drawn tokens (their argmaxes under the greedy sampler)
+    int *out_tokens, *out_n;
+    const unsigned long long *base;  // the call's first stream position
+    unsigned long long *counter;     // nullable (the greedy sampler): {base + n, 0} afterwards
+    SpecState s;
+};
+
+// The log-probabilities of every row are already written (the draws read them): one thread does what is left.
+__global__ void k_spec_accept_sampled(const SpecSampledArgs a) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int n_acc = spec_count_accepted(a.draft, a.tok, a.rows, a.V);
+    spec_commit(a.s, a.tok, a.rows, n_acc, a.out_tokens, a.out_n);
+    if (a.counter) a.counter[0] = *a.base + (unsigned long long)(n_acc + 1), a.counter[1] = 0ull;  // the rejected rows' positions are not consumed
+}
+
+// pie_decoder_spec_step_tail's edit: workgroup r is row r of the block, at position o + r, o = state->pos - rows (the pass has run).
+struct SpecEditArgs {
+    u16 *logits;
+    int V, rows;
+    float penalty;
+    int context;  // 1..PEN_MAX_IDS with a penalty
+    int *ids_by_pos;
+    int ids_cap;
+    const DecState *state;
+    const int *fed, *draft;
+    BiasArgs b;
+};
+
+// Row window: this thread's entry of the positions max(0, o + r + 1 - context) .. o + r, -1 beyond them: ids_by_pos below o, the fed token
+// at o -- recorded there, as the step's tail records its input (every row that sees o stores the same value; no row reads it back) -- and
+// draft[q - o - 1] behind it (q <= o + r: an index below rows - 1).  Every position is checked against ids_cap, as step_window_id's are.
+__device__ __forceinline__ int spec_window_id(const SpecEditArgs &a, int r) {
+    const int t = threadIdx.x, o = a.state->pos - a.rows, pos = o + r;
+    const int lo = pos + 1 - a.context > 0 ? pos + 1 - a.context : 0, n = pos + 1 - lo, p = lo + t;
+    if (o < 0 || t >= n || p < 0 || p >= a.ids_cap) return -1;
+    if (p > o) return a.draft[p - o - 1];
+    if (p == o) return a.ids_by_pos[p] = a.fed[0];
+    return a.ids_by_pos[p];
+}
+
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_spec_edit_rows(const SpecEditArgs a) {
+    __shared__ alignas(8) int s_ids[PEN_MAX_IDS];
+    const int r = blockIdx.x;
+    u16 *logits = a.logits + (size_t)r * a.V;
+    if (a.b.penalise) penalise_phase<T>(logits, a.V, a.penalty, spec_window_id(a, r), s_ids);  // block-uniform: launch arguments
+    if (a.b.n) bias_phase<T>(logits, a.V, a.b.ids, a.b.bias, a.b.n, 0, s_ids);
 }
 
 // pie_decoder_spec_step's input rows: fed[0] = the device-side token, fed[1 + i] = draft[i]; an id the embedding could not index is fed as
@@ -173,6 +288,34 @@ int spec_verify_launch(const u16 *logits, int rows, int V, int dtype, const int 
         hipLaunchKernelGGL(k_spec_merge, dim3((unsigned)rows), dim3(256), 0, st, (const LogitStat *)stats, tok, lse);
         hipLaunchKernelGGL(k_spec_accept<T>, dim3(TAIL_FINISH_BLOCKS, (unsigned)rows), dim3(256), 0, st, a);
     });
+}
+
+// pie_spec_verify_sampled's launches behind whatever made the logits (arguments already checked).  mode PIE_SAMPLE_GREEDY (the decoder's
+// penalty- or bias-only tails): the rows' tokens are their argmaxes, nothing is drawn and the counter is not touched.
+static int spec_verify_sampled_launch(u16 *logits, int rows, int V, int dtype, const int *draft, int mode, double temp, double p, int k, unsigned long long seed,
+                                      unsigned long long *counter, const pie_xtc *xtc, int *out_tokens, int *out_n, float *logprobs, void *workspace,
+                                      const SpecState &s, hipStream_t st) {
+    const SpecSampledLayout lay(rows, V);
+    char *ws = (char *)workspace;
+    int *tok = (int *)(ws + lay.tok);
+    unsigned long long *base = (unsigned long long *)(ws + lay.base);
+    if (int rc = logits_tail_rows_launch(dtype, logits, V, rows, (LogitStat *)ws, logprobs, tok, st)) return rc;
+    const bool draws = mode != PIE_SAMPLE_GREEDY;
+    if (draws) {
+        SpecFillArgs f = {};
+        f.rows = rows, f.mode = mode, f.seed = seed, f.counter = counter, f.xtc = xtc, f.base = base;
+        f.table = (pie_row_tail *)(ws + lay.table), f.xtc_rows = (pie_xtc *)(ws + lay.xtc);
+        f.smp_ws = (unsigned long long *)(ws + lay.smp), f.smp_row_words = pie_sample_workspace_bytes(1, V) / sizeof(unsigned long long);
+        f.inv_temp = (float)(1.0 / temp), f.thr = mode == PIE_SAMPLE_TOP_P ? (float)(1.0 - p) : (mode == PIE_SAMPLE_MIN_P ? (float)log(p) : 0.0f);  // pie_sample's derived values
+        f.k = mode == PIE_SAMPLE_TOP_K || mode == PIE_SAMPLE_MIN_P ? k : 0;
+        hipLaunchKernelGGL(k_spec_fill_rows, dim3(1), dim3(SPEC_MAX_ROWS), 0, st, f);
+        PIE_LAUNCH_CHECK();
+        if (int rc = sample_rows_launch(logprobs, rows, V, f.table, ws + lay.smp, tok, nullptr, nullptr, st, SampleXtc{xtc ? f.xtc_rows : nullptr, nullptr})) return rc;
+    }
+    const SpecSampledArgs a = {rows, V, draft, tok, out_tokens, out_n, base, draws ? counter : nullptr, s};
+    hipLaunchKernelGGL(k_spec_accept_sampled, dim3(1), dim3(64), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
 }
 
 extern "C" {
@@ -208,6 +351,26 @@ int pie_spec_verify(const void *logits, int rows, int V, int dtype, const int32_
     PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_spec_verify: workspace needs 16-byte alignment");
     PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_spec_verify: dtype must be PIE_BF16 or PIE_F16");
     return spec_verify_launch((const u16 *)logits, rows, V, dtype, draft, out_tokens, out_n, logprobs, workspace, SpecState(), (hipStream_t)stream);
+}
+
+size_t pie_spec_verify_sampled_workspace_bytes(int rows, int V) {
+    if (rows < 2 || rows > SPEC_MAX_ROWS || pie_sample_workspace_bytes(rows, V) == 0) return 0;
+    return SpecSampledLayout(rows, V).bytes;
+}
+
+int pie_spec_verify_sampled(const void *logits, int rows, int V, int dtype, const int32_t *draft, int mode, double temp, double p, int k, unsigned long long seed,
+                            unsigned long long *counter, const pie_xtc *xtc, int32_t *out_tokens, int32_t *out_n, float *logprobs, void *workspace, void *stream) {
+    PIE_REQUIRE(logits && draft && counter && out_tokens && out_n && logprobs && workspace, PIE_E_ARG, "pie_spec_verify_sampled: null pointer");
+    PIE_REQUIRE(mode != PIE_SAMPLE_GREEDY, PIE_E_ARG, "pie_spec_verify_sampled: the greedy sampler draws nothing (use pie_spec_verify)");
+    PIE_REQUIRE(rows >= 2 && rows <= SPEC_MAX_ROWS && V >= 1, PIE_E_SHAPE, "pie_spec_verify_sampled: need 2 <= rows <= 32 and V >= 1");
+    PIE_REQUIRE(pie_aligned(logits, 2) && pie_aligned(draft, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(logprobs, 4) && pie_aligned(xtc, 4),
+                PIE_E_ALIGN, "pie_spec_verify_sampled: logits need 2-byte, the draft, the XTC record and the outputs 4-byte alignment");
+    PIE_REQUIRE(pie_aligned(counter, 8), PIE_E_ALIGN, "pie_spec_verify_sampled: the counter needs 8-byte alignment");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_spec_verify_sampled: workspace needs 16-byte alignment");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_spec_verify_sampled: dtype must be PIE_BF16 or PIE_F16");
+    if (int rc = sample_check("pie_spec_verify_sampled", V, mode, temp, p, k, workspace)) return rc;
+    return spec_verify_sampled_launch((u16 *)const_cast<void *>(logits), rows, V, dtype, draft, mode, temp, p, k, seed, counter, xtc, out_tokens, out_n, logprobs,
+                                      workspace, SpecState(), (hipStream_t)stream);
 }
 
 // workspace: the logits block [rows, vocab] T | the pass's input ids [32] | pie_spec_verify's workspace
@@ -246,6 +409,62 @@ int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft,
     s.state = d->state, s.history = d->history, s.hist_cap = d->hist_cap, s.fed = fed;
     s.seq_ids = seq_ids, s.seq_cap = seq_cap, s.seq_len = seq_len, s.token_out = d->token_out;
     return spec_verify_launch(block, rows, c.vocab, c.dtype, draft_ids, out_tokens, out_n, logprobs_rows, verify_ws, s, st);
+}
+
+// workspace: the logits block [rows, vocab] T | the pass's input ids [32] | pie_spec_verify_sampled's workspace
+size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows) {
+    if (!d || rows < 2 || rows > SPEC_MAX_ROWS || pie_sample_workspace_bytes(rows, d->cfg.vocab) == 0) return 0;
+    return align16((size_t)rows * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_MAX_ROWS) + SpecSampledLayout(rows, d->cfg.vocab).bytes;
+}
+
+int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                               int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
+    const std::string who = "pie_decoder_spec_step_tail: ";
+    PIE_REQUIRE(d && draft_ids && out_tokens && out_n && logprobs_rows && workspace, PIE_E_ARG, who + "null pointer");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
+    PIE_REQUIRE(!d->kv_quant && !d->ring, PIE_E_STATE, who + "not available on a quantized or rotating KV cache");
+    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
+    PIE_REQUIRE(!d->tok_mask, PIE_E_STATE, who + "not available with a token mask");
+    PIE_REQUIRE(!d->tlp_n, PIE_E_STATE, who + "not available with a top-logprobs record");
+    PIE_REQUIRE(!d->cp_record, PIE_E_STATE, who + "not available with frequency / presence counts");
+    PIE_REQUIRE(!d->dry_record, PIE_E_STATE, who + "not available with a DRY penalty");
+    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
+    const bool penalise = d->pen != 1.0, draws = d->smp_mode != PIE_SAMPLE_GREEDY;
+    PIE_REQUIRE(penalise || draws || d->bias_n || d->xtc_record, PIE_E_STATE,
+                who + "no sampler, XTC record, repetition penalty or logit bias is set (the greedy and raw pass is pie_decoder_spec_step)");
+    const int rows = n_draft + 1;
+    PIE_REQUIRE(n_draft >= 1 && rows >= prefill_min_rows(), PIE_E_SHAPE, who + "fewer rows than the many-row pass takes (run a plain step)");
+    PIE_REQUIRE(rows <= SPEC_MAX_ROWS, PIE_E_SHAPE, who + "at most 31 drafts");
+    PIE_REQUIRE(seq_cap >= 0 && (seq_ids || seq_cap == 0), PIE_E_ARG, who + "bad sequence buffer");
+    PIE_REQUIRE(pie_aligned(draft_ids, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(logprobs_rows, 4) && pie_aligned(seq_ids, 4) &&
+                    pie_aligned(seq_len, 4), PIE_E_ALIGN, who + "4-byte alignment required");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, who + "workspace needs 16-byte alignment");
+    hipStream_t st = (hipStream_t)stream;
+    const pie_decoder_config &c = d->cfg;
+    PIE_REQUIRE(pie_sample_workspace_bytes(rows, c.vocab) != 0, PIE_E_SHAPE, who + "the vocabulary is larger than the sampler takes (524288)");
+    u16 *block = (u16 *)workspace;
+    int *fed = (int *)((char *)workspace + align16((size_t)rows * c.vocab * 2));
+    void *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_MAX_ROWS);
+    PIE_REQUIRE(d->glob_set && d->kv_set && d->out_set, PIE_E_STATE, "pie_decoder: set_globals, set_kv and bind_outputs must be called before stepping");
+    hipLaunchKernelGGL(k_spec_gather, dim3(1), dim3(SPEC_MAX_ROWS), 0, st, (const DecState *)d->state, draft_ids, n_draft, d->embed_vocab(), fed);
+    PIE_LAUNCH_CHECK();
+    // Raw logits on every row: logits_all != nullptr makes the pass's own last-row tail raw and greedy (pie_decoder::tail_raw), so the
+    // configured sampler draws nothing there and its counter stays where it is -- the rows' draws below are the pass's only ones.
+    if (int rc = pie_decoder_prefill(d, fed, rows, block, stream)) return rc;
+    if (penalise || d->bias_n) {  // the rows' edits, in the step tail's order: penalty, then bias
+        SpecEditArgs e = {};
+        e.logits = block, e.V = c.vocab, e.rows = rows, e.penalty = (float)d->pen, e.context = d->pen_ctx, e.ids_by_pos = d->ids_by_pos, e.ids_cap = d->ids_cap;
+        e.state = d->state, e.fed = fed, e.draft = draft_ids;
+        e.b = BiasArgs{d->bias_ids, d->bias_vals, d->bias_n, penalise};
+        if (int rc = launch_for_dtype(c.dtype, "spec edit:", [&](auto t) { hipLaunchKernelGGL(k_spec_edit_rows<decltype(t)>, dim3((unsigned)rows), dim3(PEN_MAX_IDS), 0, st, e); }))
+            return rc;
+    }
+    SpecState s;
+    s.state = d->state, s.history = d->history, s.hist_cap = d->hist_cap, s.fed = fed;
+    s.seq_ids = seq_ids, s.seq_cap = seq_cap, s.seq_len = seq_len, s.token_out = d->token_out;
+    if (penalise) s.ids_by_pos = d->ids_by_pos, s.ids_cap = d->ids_cap;
+    return spec_verify_sampled_launch(block, rows, c.vocab, c.dtype, draft_ids, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter,
+                                      draws ? d->xtc_record : nullptr, out_tokens, out_n, logprobs_rows, verify_ws, s, st);
 }
 
 }  // extern "C"

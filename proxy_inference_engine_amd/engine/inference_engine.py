@@ -119,17 +119,27 @@ class SpeculativeParams:
     """Greedy speculative decoding with prompt-lookup drafts (generate_step(speculative=...)): after every step or pass the
     drafter looks the sequence's last ngram_max .. ngram_min ids up in the sequence itself and copies the num_draft ids behind the latest
     occurrence of the longest suffix found; a draft of at least min_draft ids is verified in one many-row pass, anything shorter is one
-    plain replayed step.  The tokens are exactly greedy decoding's."""
+    plain replayed step.  The tokens are exactly greedy decoding's.
+    configured_tail: False -- speculation is greedy and raw, and anything else is refused.  True -- the request's sampler
+    (any temperature, top-p / top-k / min-p, XTC), repetition penalty and logit bias run inside the passes: row r's token is drawn from the
+    model's own processed distribution at the stream position the plain loop would have used for it, and a draft is accepted while it
+    equals the draw -- exact for prompt-lookup drafts, which are point masses: token j of the generation is draw j of the seed from row
+    j's own distribution.  (A pass's rows come from the many-row GEMMs and a step's from the GEMVs, so their logits may differ in the last
+    bit, as in the greedy case: the plain loop draws the same tokens wherever no draw falls within that rounding of a boundary.)  A greedy
+    request without processors takes the greedy path either way."""
     num_draft: int = 7
     ngram_max: int = 3
     ngram_min: int = 1
     min_draft: int = 5
+    configured_tail: bool = False
 
     def __post_init__(self):
         if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= hip_ops.SPEC_MAX_NGRAM:
             raise ValueError(f"SpeculativeParams: 1 <= ngram_min <= ngram_max <= {hip_ops.SPEC_MAX_NGRAM}")
         if not 1 <= int(self.min_draft) <= int(self.num_draft) <= hip_ops.SPEC_MAX_ROWS - 1:
             raise ValueError(f"SpeculativeParams: 1 <= min_draft <= num_draft <= {hip_ops.SPEC_MAX_ROWS - 1}")
+        if not isinstance(self.configured_tail, bool):
+            raise ValueError("SpeculativeParams: configured_tail is a bool")
 
 
 def check_speculative(model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size) -> None:
@@ -143,6 +153,30 @@ def check_speculative(model, sampler, processors, structuring_engine, pixel_valu
             raise ValueError(f"speculative decoding is not available with {name}")
     if not hasattr(model, "spec_step"):
         raise ValueError("speculative decoding is not available with this model (no spec_step)")
+
+
+def check_speculative_tail(model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs=None) -> dict:
+    """What generate_step(speculative=SpeculativeParams(configured_tail=True)) refuses, each by name, and the fused tail
+    plan of what it accepts: a greedy or `hip_spec` sampler (XTC included), the repetition penalty and the logit bias.  A token mask,
+    frequency / presence penalties and DRY stay out of the passes, like everything check_speculative refuses besides the sampler and the
+    processors."""
+    tp = getattr(model, "tp", None) is not None
+    for bad, name in ((structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
+                      (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"), (prompt_logprobs is not None, "prompt_logprobs"),
+                      (tp, "a tensor-parallel model"),
+                      (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")):
+        if bad:
+            raise ValueError(f"speculative decoding is not available with {name}")
+    plan = fused_tail_plan(processors, sampler, structuring_engine, tp)
+    if plan is None:
+        raise ValueError("speculative decoding under a configured tail is not available with a sampler or logits processors outside the fused tail plan "
+                         "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
+    for key, name in (("mask", "a token mask"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
+        if plan.get(key) is not None:
+            raise ValueError(f"speculative decoding under a configured tail is not available with {name}")
+    if not hasattr(model, "spec_step_tail") or not hasattr(model, "set_step_tail"):
+        raise ValueError("speculative decoding under a configured tail is not available with this model (no spec_step_tail)")
+    return plan
 
 
 class InferenceEngine:
@@ -241,7 +275,10 @@ class InferenceEngine:
         log-probabilities, the same tokens the plain loop yields one by one; `self.spec_stats` counts passes, steps, drafted and accepted
         ids.  With top_logprobs, `self.top_record` holds one record per yielded token ([m, n + 1]).  Greedy and raw only: a non-greedy
         sampler, logits processors, a structuring engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs, a tensor-parallel model
-        and int8 KV pages are refused by name."""
+        and int8 KV pages are refused by name.  SpeculativeParams(configured_tail=True) lifts the first two for what the
+        fused tail plan holds besides a token mask, counts and DRY: the request's sampler, repetition penalty and logit bias run inside
+        the passes, token j is draw j of the samplers' seed from row j's distribution, and the yielded rows are the processed
+        log-probabilities."""
         scored = prompt_logprobs is not None
         if speculative is not None and scored:
             raise ValueError("speculative decoding is not available with prompt_logprobs")
@@ -268,9 +305,14 @@ class InferenceEngine:
             raise TypeError("pixel_values need a VLM ensemble (models/intern/ensemble.py: Model) as the engine's model")
         if "root" not in self.samplers:
             self.prepare_engine(prompt_ids, temp=0)
+        spec_plan = None
         if speculative is not None:
-            check_speculative(self.model, self.samplers["root"], [p for ps in self.logits_processors.values() for p in ps], self.structuring_engine,
-                              pixel_values, kv_bits, max_kv_size)
+            all_procs = [p for ps in self.logits_processors.values() for p in ps]
+            if speculative.configured_tail and not (getattr(self.samplers["root"], "is_greedy", False) and not all_procs):
+                spec_plan = check_speculative_tail(self.model, self.samplers["root"], self.logits_processors.get("root") or [], self.structuring_engine,
+                                                   pixel_values, kv_bits, max_kv_size)
+            else:  # (a greedy request without processors under configured_tail=True: today's greedy path)
+                check_speculative(self.model, self.samplers["root"], all_procs, self.structuring_engine, pixel_values, kv_bits, max_kv_size)
         dev = self.model.device
 
         def _inference(ids: torch.Tensor, fed_back: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
@@ -398,7 +440,7 @@ class InferenceEngine:
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
         if speculative is not None:
-            yield from self._speculative_steps(host_ids, speculative, top_logprobs)
+            yield from self._speculative_steps(host_ids, speculative, top_logprobs, spec_plan)
             return
         if scored and len(host_ids) > 1:
             lm = getattr(self.model, "language_model", self.model)
@@ -422,14 +464,30 @@ class InferenceEngine:
             yield next_token, logprobs
             step_count += 1
 
-    def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None):
+    def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None, plan: dict | None = None):
         """generate_step's loop under speculative decoding.  The prompt's suffix is one plain step; behind it, and behind every
         later step or pass, ONE drafter launch is queued, and its count comes back in the read-back the loop pays anyway: the tokens
         (Model.spec_read).  count >= min_draft (and enough rows for the many-row pass): a verify pass over count + 1 rows, whose accepted
         tokens are the next yield; otherwise one replayed step.  prompt_cache.update receives the ids whose K / V rows the cache now holds:
-        the fed-back token and the accepted drafts."""
+        the fed-back token and the accepted drafts.
+        plan (check_speculative_tail's): the steps are the ordinary configured replayed step and the passes
+        Model.spec_step_tail under the plan's sampler / XTC / repetition penalty / logit bias; both draw from one stream position, so
+        token j of the generation is draw j of the seed whichever produced it."""
         model, cache = self.model, self.prompt_cache.cache
-        if hasattr(model, "set_step_tail"):
+        spec_pass = model.spec_step
+        if plan is not None:
+            offset = int(cache[0].offset) if cache else 0
+            if offset + len(host_ids) > model.fed_ids.numel():
+                raise ValueError("speculative decoding: the prompt runs past the model's id history")
+            if plan["repetition_penalty"] != 1.0 and offset > 0:  # a reused prefix: its ids may predate this configuration (as in _forward)
+                seen = self.prompt_cache.computed_ids[-min(offset, plan["context_size"]):]
+                model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
+            bias = plan["bias"]
+            model.set_step_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
+                                logit_bias=None if bias is None else (bias.ids, bias.values),
+                                **({} if plan.get("xtc") is None else {"xtc": plan["xtc"]}))
+            spec_pass = model.spec_step_tail
+        elif hasattr(model, "set_step_tail"):
             model.set_step_tail()  # the documented greedy tail: the passes refuse anything else
         drafter = (int(sp.ngram_max), int(sp.ngram_min), int(sp.num_draft))
         floor = max(int(sp.min_draft), int(getattr(model, "spec_min_rows", 6)) - 1)
@@ -457,7 +515,7 @@ class InferenceEngine:
             yield torch.tensor(tokens, dtype=torch.int32), rows
             fed = tokens[-1]
             if count >= floor:
-                _, n, rows = model.spec_step(model.spec_draft[:count], cache, then_draft=drafter)
+                _, n, rows = spec_pass(model.spec_draft[:count], cache, then_draft=drafter)
                 accepted = model.spec_read()[0]
                 self.prompt_cache.update([fed] + accepted[:-1])
                 self.spec_stats["passes"] += 1

@@ -1274,6 +1274,50 @@ def spec_verify(logits: torch.Tensor, draft: torch.Tensor, logprobs: torch.Tenso
     return tokens, n
 
 
+def spec_verify_sampled_workspace(device, rows: int, V: int) -> torch.Tensor:
+    """pie_spec_verify_sampled's workspace for a [rows, V] block on `device`: zeroed once, the kernels leave it ready for the next call."""
+    nbytes = int(_ffi.load().pie_spec_verify_sampled_workspace_bytes(int(rows), int(V)))
+    if nbytes == 0:
+        raise ValueError(f"spec_verify_sampled: 2 <= rows <= {SPEC_MAX_ROWS} and 1 <= V <= 524288, got [{rows}, {V}]")
+    return torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+
+
+def spec_verify_sampled(logits: torch.Tensor, draft: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0, xtc=None,
+                        logprobs: torch.Tensor | None = None, workspace: torch.Tensor | None = None, out: tuple | None = None):
+    """The verify of a speculative pass under a stochastic sampler (pie_spec_verify_sampled): logits bf16 / f16 [rows, V],
+    draft int32 [rows - 1], (mode, temp, p, k) as `sample` takes them -> (tokens int32 [rows], n int32 [1], logprobs fp32 [rows, V]), no
+    host sync.  With c = the samplers' stream position (read on the device), row r's token is `sample`'s of that row alone at position
+    c + r; the drafts are accepted while draft[i] equals row i's token (an id outside [0, V) is never accepted), n = accepted + 1, tokens =
+    the tokens of rows 0 .. n - 1, then -1, and the stream position becomes c + n.  Every row of logprobs is written
+    (logprobs_argmax's bits).  xtc: one record shared by the rows (xtc_pack, or its device form).  workspace:
+    spec_verify_sampled_workspace's (zeroed once); out = (tokens, n) to write into.  rows 2..32."""
+    from .samplers import _rng
+    who = "spec_verify_sampled"
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError(f"{who}: contiguous bf16 / f16 [rows, V] logits")
+    if mode not in SAMPLE_MODES:
+        raise ValueError(f"{who}: mode is one of {sorted(SAMPLE_MODES)} (the greedy verify is spec_verify)")
+    rows, V = logits.shape
+    _int32_dev(draft, rows - 1, who, "draft")
+    if logprobs is None:
+        logprobs = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
+    _dev(logprobs)
+    if logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (rows, V) or not logprobs.is_contiguous():
+        raise ValueError(f"{who}: logprobs is a contiguous fp32 [rows, V] device tensor")
+    ws = spec_verify_sampled_workspace(logits.device, rows, V) if workspace is None else workspace
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
+    tokens, n = out
+    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
+    seed, counter = _rng.hip_state(logits.device)
+    rec = None if xtc is None else _xtc(xtc, 1, logits.device, who)
+    _ffi.check(_ffi.load().pie_spec_verify_sampled(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(draft), SAMPLE_MODES[mode], float(temp), float(p),
+                                                   int(k), seed, _ffi.p(counter), _ffi.p(rec), _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs), _ffi.p(ws),
+                                                   _ffi.stream()))
+    return tokens, n, logprobs
+
+
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)
 def kv_ring_order(keys: torch.Tensor, values: torch.Tensor, keep: int, n: int, shift: int, n_dst: int) -> None:
     """In place on RotatingKVCache buffers [1, H, cap, D]: rows keep + j <- rows keep + (j + shift) % n for j < n_dst."""

@@ -790,15 +790,18 @@ class Model(RowsTailState):
         return [int(t) for t in h[self._SPEC_TOK:self._SPEC_TOK + n]], int(h[self._SPEC_COUNT])
 
     def _check_speculative(self, who: str, cache) -> None:
+        self._check_speculative_kv(who, cache)
+        if self._tail[:2] != (None, None) or self._edits != (False, 0) or self._top_n is not None or self._cnt is not None or self._dry is not None:
+            raise ValueError(f"{who}: speculation is greedy and raw -- set_step_tail() with its defaults first "
+                             "(no sampler, repetition penalty, token mask, logit bias, top_logprobs or frequency / presence penalty)")
+
+    def _check_speculative_kv(self, who: str, cache) -> None:
         if self.tp is not None:
             raise ValueError(f"{who}: not available on a tensor-parallel model")
         if on_int8_pages(cache):
             raise ValueError(f"{who}: not available on int8 KV pages")
         if not isinstance(cache[0], (ReusableKVCache, PagedKVCache)):
             raise ValueError(f"{who}: runs on ReusableKVCache or 16-bit PagedKVCache, not on {type(cache[0]).__name__}")
-        if self._tail[:2] != (None, None) or self._edits != (False, 0) or self._top_n is not None or self._cnt is not None or self._dry is not None:
-            raise ValueError(f"{who}: speculation is greedy and raw -- set_step_tail() with its defaults first "
-                             "(no sampler, repetition penalty, token mask, logit bias, top_logprobs or frequency / presence penalty)")
 
     def _queue_draft(self, ngram_max: int, ngram_min: int, k: int) -> None:
         sp = self._spec_state()
@@ -832,8 +835,12 @@ class Model(RowsTailState):
         then_draft = (ngram_max, ngram_min, k): the next draft is queued behind the pass before the host reads n -- the pass costs ONE
         read-back (spec_read() returns it without another).  m + 1 rows: spec_min_rows .. 32.  Contiguous and 16-bit paged caches; the
         greedy raw tail only.  Pages taken for rejected rows stay with the sequence."""
-        who = "spec_step"
-        self._check_speculative(who, cache)
+        self._check_speculative("spec_step", cache)
+        return self._spec_pass("spec_step", "pie_decoder_spec_step", "ws", draft_ids, cache, then_draft)
+
+    def _spec_pass(self, who: str, entry: str, ws: str, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None):
+        """What spec_step and spec_step_tail share: the record, the library entry on workspace `ws`, the drafter hand-off, the one
+        read-back and the cache advance."""
         draft_ids = draft_ids.reshape(-1)
         if not draft_ids.is_cuda or draft_ids.dtype != torch.int32 or not draft_ids.is_contiguous():
             raise ValueError(f"{who}: draft_ids is a contiguous int32 device tensor")
@@ -846,18 +853,44 @@ class Model(RowsTailState):
         if self._kv.offset + m + 1 > self.fed_ids.numel():
             raise ValueError(f"{who}: the pass would run past the model's id history")
         sp["host"] = None
-        _ffi.check(_ffi.load().pie_decoder_spec_step(self._dec, _ffi.p(draft_ids), m, _ffi.p(rec[self._SPEC_TOK:]), _ffi.p(rec[self._SPEC_N:]),
-                                                     _ffi.p(sp["logprobs"]), _ffi.p(sp["ws"]), _ffi.p(self.fed_ids), self.fed_ids.numel(),
-                                                     _ffi.p(rec[self._SPEC_LEN:]), _ffi.stream()))
+        _ffi.check(getattr(_ffi.load(), entry)(self._dec, _ffi.p(draft_ids), m, _ffi.p(rec[self._SPEC_TOK:]), _ffi.p(rec[self._SPEC_N:]),
+                                               _ffi.p(sp["logprobs"]), _ffi.p(sp[ws]), _ffi.p(self.fed_ids), self.fed_ids.numel(),
+                                               _ffi.p(rec[self._SPEC_LEN:]), _ffi.stream()))
+        sp["last_ws"] = ws
         if then_draft is not None:
             self._queue_draft(*then_draft)
         n = len(self.spec_read()[0])  # the one read-back
         self._kv.advance(cache, n)    # the rejected rows stay behind the offset and are overwritten
         return rec[self._SPEC_TOK:self._SPEC_TOK + n], n, sp["logprobs"][:n]
 
+    def spec_step_tail(self, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None = None):
+        """spec_step under the configured tail (pie_decoder_spec_step_tail): after set_step_tail(sampler=..., xtc=...,
+        repetition_penalty=..., logit_bias=...) -- at least one of them -- row r's logits get the repetition penalty over the ids a plain
+        step at that position would see (the drafts before it included) and the logit bias, its token is drawn at stream position c + r
+        (c = the samplers' position before the pass; the argmax under the greedy sampler), and the drafts are accepted while each equals
+        the token of the row before it.  The same returns as spec_step; all m + 1 rows of the log-probabilities are written, and
+        spec_logits() then holds the PROCESSED logits.  Afterwards the model, the cache, `fed_ids` and the samplers' stream are exactly
+        where n calls of step(None) under the same tail would have left them.  A token mask, top_logprobs, frequency / presence
+        penalties and DRY are refused by name, like tensor-parallel models, int8 pages and the other cache kinds."""
+        who = "spec_step_tail"
+        self._check_speculative_kv(who, cache)
+        for bad, name in ((self._edits[0], "a token mask"), (self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"),
+                          (self._dry is not None, "a DRY penalty")):
+            if bad:
+                raise ValueError(f"{who}: not available with {name}")
+        if self._tail[:2] == (None, None) and self._edits[1] == 0:
+            raise ValueError(f"{who}: no sampler, repetition penalty or logit bias is set -- the greedy and raw pass is spec_step")
+        sp = self._spec_state()
+        if "tail_ws" not in sp:  # zeroed once: the sampler's part is carried from pass to pass
+            nbytes = int(_ffi.load().pie_decoder_spec_tail_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
+            sp["tail_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        return self._spec_pass(who, "pie_decoder_spec_step_tail", "tail_ws", draft_ids, cache, then_draft)
+
     def spec_logits(self, rows: int) -> torch.Tensor:
-        """The raw logits block [rows, V] of the last spec_step (a view of its workspace, valid until the next one)."""
-        return self._spec_state()["ws"].view(self.dtype)[:rows * self.vocab_out].view(rows, self.vocab_out)
+        """The logits block [rows, V] of the last pass (a view of its workspace, valid until the next one): raw after spec_step, processed
+        after spec_step_tail."""
+        sp = self._spec_state()
+        return sp[sp.get("last_ws", "ws")].view(self.dtype)[:rows * self.vocab_out].view(rows, self.vocab_out)
 
     def step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], graph: bool = True):
         """One decode step for several sequences at once (continuous batching over the page pool; pie_decoder_step_batch):
