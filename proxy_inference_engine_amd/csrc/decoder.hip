@@ -162,41 +162,42 @@ static AttnArgs attn_args(pie_decoder *d, int li) {
 // from_state: the row's input token is the device-side state's (a step): recorded in ids_by_pos before the penalty reads its window.
 static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
+    const StepTail &t = d->tail;
     const LogitStat *stats = d->stats;
     int n_stats = d->n_stats, rc;
-    if (d->pen != 1.0 || d->bias_n) {  // edit
+    if (t.penalty.on() || t.bias.on()) {  // edit
         PenArgs a = {};
-        a.logits = d->logits, a.V = c.vocab, a.penalty = (float)d->pen, a.ids_by_pos = d->ids_by_pos, a.ids_cap = d->ids_cap, a.context = d->pen_ctx;
+        a.logits = d->logits, a.V = c.vocab, a.penalty = (float)t.penalty.value, a.ids_by_pos = t.penalty.ids_by_pos, a.ids_cap = t.penalty.ids_cap, a.context = t.penalty.context;
         a.state = d->state, a.record = from_state;
-        const BiasArgs b = {d->bias_ids, d->bias_vals, d->bias_n, d->pen != 1.0};
-        if ((rc = d->bias_n ? logits_edit_launch(c.dtype, a, b, st) : logits_penalty_launch(c.dtype, a, st))) return rc;
+        const BiasArgs b = {t.bias.ids, t.bias.vals, t.bias.n, t.penalty.on()};
+        if ((rc = t.bias.on() ? logits_edit_launch(c.dtype, a, b, st) : logits_penalty_launch(c.dtype, a, st))) return rc;
     }
-    if (d->cp_record) {  // count penalty: behind the penalty and the bias; a prompt pass counts nothing
+    if (t.counts.on()) {  // count penalty: behind the penalty and the bias; a prompt pass counts nothing
         CountPenArgs k = {};
-        k.logits = d->logits, k.V = c.vocab, k.records = d->cp_record, k.counts = d->cp_counts, k.state = d->state, k.count = from_state;
+        k.logits = d->logits, k.V = c.vocab, k.records = t.counts.record, k.counts = t.counts.counts, k.state = d->state, k.count = from_state;
         if ((rc = logits_count_penalty_rows_launch(c.dtype, k, 1, st))) return rc;
     }
-    if (d->dry_record) {  // DRY: behind the count penalty; a step records its input token before it reads its window
+    if (t.dry.on()) {  // DRY: behind the count penalty; a step records its input token before it reads its window
         DryArgs k = {};
-        k.w.logits = d->logits, k.w.V = c.vocab, k.w.ids_by_pos = d->dry_ids_by_pos, k.w.ids_cap = d->dry_ids_cap, k.w.state = d->state, k.w.record = from_state;
-        k.record = d->dry_record, k.breakers = d->dry_breakers;
+        k.w.logits = d->logits, k.w.V = c.vocab, k.w.ids_by_pos = t.dry.ids_by_pos, k.w.ids_cap = t.dry.ids_cap, k.w.state = d->state, k.w.record = from_state;
+        k.record = t.dry.record, k.breakers = t.dry.breakers;
         if ((rc = logits_dry_launch(c.dtype, k, st))) return rc;
     }
-    if (d->pen != 1.0 || d->bias_n || d->tok_mask || d->cp_record || d->dry_record) {  // partials: the lm_head epilogue's are stale
-        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, d->tail_stats, st, d->tok_mask))) return rc;
-        stats = d->tail_stats, n_stats = TAIL_STAT_TILES;
+    if (t.edits_logits()) {  // partials: the lm_head epilogue's are stale
+        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, t.tail_stats, st, t.mask.words))) return rc;
+        stats = t.tail_stats, n_stats = TAIL_STAT_TILES;
     }
     // finish
     if ((rc = logits_tail_launch(c.dtype, d->logits, c.vocab, stats, n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st))) return rc;
-    if (d->smp_mode != PIE_SAMPLE_GREEDY) {  // sampler and top-n
+    if (t.sampler.on()) {  // sampler and top-n
+        const StepTail::Sampler &s = t.sampler;
         const SampleFeed feed = {&d->state->token, &d->state->pos, d->history, d->hist_cap};
-        if ((rc = sample_launch(d->logprobs, 1, c.vocab, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter, d->smp_ws, d->token_out, nullptr, nullptr, feed, st,
-                                SampleXtc{d->xtc_record, nullptr})))
+        if ((rc = sample_launch(d->logprobs, 1, c.vocab, s.mode, s.temp, s.p, s.k, s.seed, s.counter, s.ws, d->token_out, nullptr, nullptr, feed, st, SampleXtc{t.xtc.record, nullptr})))
             return rc;
     }
-    if (!d->tlp_n) return PIE_OK;
+    if (!t.top.on()) return PIE_OK;
     // last, after the draw: slot 0 is the token that is fed back
-    return top_logprobs_launch(d->logprobs, 1, c.vocab, d->tlp_n, d->token_out, nullptr, d->tlp_ids, d->tlp_vals, d->tlp_ws, st);
+    return top_logprobs_launch(d->logprobs, 1, c.vocab, t.top.n, d->token_out, nullptr, t.top.ids, t.top.vals, t.top.ws, st);
 }
 
 // One launch of the step's sequence (PIE_K_* of include/pie_hip.h); `li` is the layer for per-layer kernels.
@@ -301,7 +302,7 @@ int enqueue_kernel(pie_decoder *d, int which, int li, const int *token_ptr, u16 
             if (d->tp())  // vocabulary-parallel: (max, sum exp, argmax) of every shard -> global log-sum-exp and token
                 return tp_tail_launch(d->comm, c.dtype, logits_dst, c.vocab, c.tp_rank * c.vocab, d->stats, d->n_stats, d->tp_part + H, d->logprobs, d->token_out,
                                       d->state, d->history, d->hist_cap, st);
-            if (d->tail_configured() && logits_dst == d->logits && !d->tail_raw) return configured_tail(d, token_ptr == &d->state->token && !d->row_is_h, st);
+            if (d->tail.configured() && logits_dst == d->logits && !d->tail_raw) return configured_tail(d, token_ptr == &d->state->token && !d->row_is_h, st);
             return logits_tail_launch(c.dtype, logits_dst, c.vocab, d->stats, d->n_stats, d->logprobs, d->token_out, d->state, d->history, d->hist_cap, st);
         default: return pie::fail(PIE_E_ARG, "pie_decoder: unknown kernel id");
     }
@@ -433,7 +434,7 @@ int pie_decoder_destroy(pie_decoder *d) {
     drop_graphs(d);
     prefill_free(d);
     void *ptrs[] = {d->state, d->kv_table, d->qbuf, d->attn, d->act, d->part_acc, d->part_ml, d->stats, d->rope_cs, d->pf_sink, d->seam, d->tp_part, d->kv_stage, d->kv_table_stage,
-                    d->zero_table, d->kvq_scratch, d->kvq_table, d->ring_rows, d->tail_stats};
+                    d->zero_table, d->kvq_scratch, d->kvq_table, d->ring_rows, d->tail.tail_stats};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete d;
@@ -715,6 +716,25 @@ int enqueue_scored_step(pie_decoder *d, const int *token_ptr, int l, bool last, 
     d->tail_raw = raw;
     return rc ? rc : d->prompt.score_rows(d->cfg, dst, l, 1, st);
 }
+
+// What every setter of a tail begins with -- the eight of the step's and the seven of the multi-sequence passes'
+static int tail_entry(const pie_decoder *d, const char *entry) {
+    PIE_REQUIRE(d, PIE_E_ARG, std::string(entry) + ": null decoder");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, std::string(entry) + ": the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    return PIE_OK;
+}
+
+// One part of the step's tail (decoder.hpp: StepTail), assigned as a whole: every field is a launch argument, so the captured graphs go exactly
+// when the part compares unequal; once some part edits the logits the fresh partials need their scratch (without it the part stays as it was).
+template <class Part>
+static int set_part(pie_decoder *d, Part &slot, const Part &v) {
+    const Part old = slot;
+    slot = v;
+    if (d->tail.edits_logits() && !d->tail.tail_stats)
+        if (int rc = dev_alloc((void **)&d->tail.tail_stats, sizeof(LogitStat) * TAIL_STAT_TILES)) return slot = old, rc;
+    if (!(old == v)) drop_graphs(d);
+    return PIE_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -818,83 +838,53 @@ int pie_decoder_configure(pie_decoder *d, int option, int value) {
 // the T [block_rows, vocab] logits block at the head of the prompt log-probabilities' workspace, padded so that the op's part stays 16-byte aligned
 static size_t prompt_block_bytes(const pie_decoder *d, int block_rows) { return ((size_t)block_rows * d->cfg.vocab * 2 + 15) & ~(size_t)15; }
 
-static int tail_stats_alloc(pie_decoder *d) {
-    return d->tail_stats ? PIE_OK : dev_alloc((void **)&d->tail_stats, sizeof(LogitStat) * TAIL_STAT_TILES);
-}
-
 int pie_decoder_set_logits_penalty(pie_decoder *d, double penalty, int context_size, int32_t *ids_by_pos, int ids_cap) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logits_penalty: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logits_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_logits_penalty")) return rc;
     PIE_REQUIRE(penalty >= 0.0 && std::isfinite(penalty), PIE_E_ARG, "pie_decoder_set_logits_penalty: the penalty must be finite and non-negative");
     PIE_REQUIRE(context_size >= 0 && context_size <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_logits_penalty: context_size must be 1..1024 (0: off)");
     if (penalty == 1.0 || context_size == 0) penalty = 1.0, context_size = 0, ids_by_pos = nullptr, ids_cap = 0;
     else PIE_REQUIRE(ids_by_pos && ids_cap >= 1 && pie_aligned(ids_by_pos, 4), PIE_E_ARG, "pie_decoder_set_logits_penalty: ids_by_pos must hold at least one id");
-    if (penalty != 1.0)
-        if (int rc = tail_stats_alloc(d)) return rc;
-    const bool changed = d->pen != penalty || d->pen_ctx != context_size || d->ids_by_pos != ids_by_pos || d->ids_cap != ids_cap;
-    d->pen = penalty, d->pen_ctx = context_size, d->ids_by_pos = ids_by_pos, d->ids_cap = ids_cap;
-    if (changed) drop_graphs(d);  // every one of them is a launch argument
-    return PIE_OK;
+    return set_part(d, d->tail.penalty, {penalty, context_size, ids_by_pos, ids_cap});
 }
 
 int pie_decoder_set_logits_mask(pie_decoder *d, const uint32_t *mask, int mask_words) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logits_mask: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logits_mask: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_logits_mask")) return rc;
     if (mask) {
         PIE_REQUIRE(mask_words >= (d->cfg.vocab + 31) / 32, PIE_E_SHAPE, "pie_decoder_set_logits_mask: the mask needs ceil(vocab / 32) words");
         PIE_REQUIRE(pie_aligned(mask, 4), PIE_E_ALIGN, "pie_decoder_set_logits_mask: the mask needs 4-byte alignment");
-        if (int rc = tail_stats_alloc(d)) return rc;
     }
-    if (d->tok_mask != mask) drop_graphs(d);  // the address is a launch argument (the words behind it are read by every launch)
-    d->tok_mask = mask;
-    return PIE_OK;
+    return set_part(d, d->tail.mask, {mask});
 }
 
 int pie_decoder_set_logit_bias(pie_decoder *d, const int32_t *ids, const float *bias, int n) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_logit_bias: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_logit_bias: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_logit_bias")) return rc;
     PIE_REQUIRE(n >= 0 && n <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_logit_bias: 1 <= n <= 1024 entries (0: off)");
     if (n == 0) ids = nullptr, bias = nullptr;
     else {
         PIE_REQUIRE(ids && bias, PIE_E_ARG, "pie_decoder_set_logit_bias: null pointer");
         PIE_REQUIRE(pie_aligned(ids, 4) && pie_aligned(bias, 4), PIE_E_ALIGN, "pie_decoder_set_logit_bias: ids and bias need 4-byte alignment");
-        if (int rc = tail_stats_alloc(d)) return rc;
     }
-    if (d->bias_ids != ids || d->bias_vals != bias || d->bias_n != n) drop_graphs(d);  // every one of them is a launch argument
-    d->bias_ids = ids, d->bias_vals = bias, d->bias_n = n;
-    return PIE_OK;
+    return set_part(d, d->tail.bias, {ids, bias, n});
 }
 
 int pie_decoder_set_sampler(pie_decoder *d, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                             void *workspace, size_t workspace_bytes) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_sampler: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_sampler: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
-    if (mode == PIE_SAMPLE_GREEDY) {
-        if (d->smp_mode != PIE_SAMPLE_GREEDY) drop_graphs(d);
-        d->smp_mode = PIE_SAMPLE_GREEDY, d->smp_counter = nullptr, d->smp_ws = nullptr;
-        return PIE_OK;
-    }
+    if (int rc = tail_entry(d, "pie_decoder_set_sampler")) return rc;
+    if (mode == PIE_SAMPLE_GREEDY) return set_part(d, d->tail.sampler, {});  // off, whatever the other arguments say
     PIE_REQUIRE(counter && workspace, PIE_E_ARG, "pie_decoder_set_sampler: null pointer");
     if (int rc = sample_check("pie_decoder_set_sampler", d->cfg.vocab, mode, temp, p, k, workspace)) return rc;
     PIE_REQUIRE(workspace_bytes >= pie_sample_workspace_bytes(1, d->cfg.vocab), PIE_E_SHAPE, "pie_decoder_set_sampler: the workspace is smaller than pie_sample_workspace_bytes(1, vocab)");
-    const bool changed = d->smp_mode != mode || d->smp_temp != temp || d->smp_p != p || d->smp_k != k || d->smp_seed != seed || d->smp_counter != counter || d->smp_ws != workspace;
-    d->smp_mode = mode, d->smp_temp = temp, d->smp_p = p, d->smp_k = k, d->smp_seed = seed, d->smp_counter = counter, d->smp_ws = workspace;
-    if (changed) drop_graphs(d);
-    return PIE_OK;
+    return set_part(d, d->tail.sampler, {mode, k, temp, p, seed, counter, workspace});
 }
 
 int pie_decoder_set_xtc(pie_decoder *d, const pie_xtc *record) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_xtc: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_xtc: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_xtc")) return rc;
     PIE_REQUIRE(pie_aligned(record, 4), PIE_E_ALIGN, "pie_decoder_set_xtc: the record needs 4-byte alignment");
-    if (d->xtc_record != record) drop_graphs(d);  // a launch argument
-    d->xtc_record = record;
-    return PIE_OK;
+    return set_part(d, d->tail.xtc, {record});
 }
 
 int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_cap) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_xtc: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_xtc: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_xtc")) return rc;
     if (!records) return d->rows.xtc = {}, PIE_OK;  // off
     PIE_REQUIRE(rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_xtc: rows_cap >= 1");
     PIE_REQUIRE(pie_aligned(records, 4), PIE_E_ALIGN, "pie_decoder_set_batch_xtc: the records need 4-byte alignment");
@@ -903,8 +893,7 @@ int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_c
 }
 
 int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float *out_vals, void *workspace, size_t workspace_bytes) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_top_logprobs: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_top_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_top_logprobs")) return rc;
     if (n == 0) out_ids = nullptr, out_vals = nullptr, workspace = nullptr;
     else {
         PIE_REQUIRE(d->out_set, PIE_E_STATE, "pie_decoder_set_top_logprobs: bind_outputs must be called first");
@@ -912,14 +901,11 @@ int pie_decoder_set_top_logprobs(pie_decoder *d, int n, int32_t *out_ids, float 
         PIE_REQUIRE(workspace_bytes >= pie_top_logprobs_workspace_bytes(1, d->cfg.vocab, n), PIE_E_SHAPE,
                     "pie_decoder_set_top_logprobs: the workspace is smaller than pie_top_logprobs_workspace_bytes(1, vocab, n)");
     }
-    if (d->tlp_n != n || d->tlp_ids != out_ids || d->tlp_vals != out_vals || d->tlp_ws != workspace) drop_graphs(d);  // every one of them is a launch argument
-    d->tlp_n = n, d->tlp_ids = out_ids, d->tlp_vals = out_vals, d->tlp_ws = workspace;
-    return PIE_OK;
+    return set_part(d, d->tail.top, {n, out_ids, out_vals, workspace});
 }
 
 int pie_decoder_set_batch_top_logprobs(pie_decoder *d, int n, int rows_cap, int32_t *out_ids, float *out_vals, const int32_t *count, void *workspace) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_top_logprobs: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_top_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_top_logprobs")) return rc;
     if (n == 0) return d->rows.top = {}, PIE_OK;  // off
     // (a pass is handed its logprobs per call: their alignment is checked there, with rows <= rows_cap)
     if (int rc = top_logprobs_check("pie_decoder_set_batch_top_logprobs", rows_cap, d->cfg.vocab, n, false, nullptr, nullptr, count, out_ids, out_vals, workspace)) return rc;
@@ -935,8 +921,7 @@ size_t pie_decoder_prompt_logprobs_workspace_bytes(const pie_decoder *d, int n, 
 
 int pie_decoder_set_prompt_logprobs(pie_decoder *d, int n, int rows_cap, int block_rows, const int32_t *targets, const int32_t *count, int32_t *out_ids,
                                     float *out_vals, void *workspace, size_t workspace_bytes) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_prompt_logprobs: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_prompt_logprobs")) return rc;
     if (n == 0) return d->prompt = {}, PIE_OK;  // off
     PIE_REQUIRE(n >= 1 && n <= PIE_TOP_LOGPROBS_MAX, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: n must be 1..20 (0: off)");
     PIE_REQUIRE(block_rows >= 8 && block_rows <= 1024, PIE_E_ARG, "pie_decoder_set_prompt_logprobs: block_rows must be 8..1024");
@@ -950,8 +935,7 @@ int pie_decoder_set_prompt_logprobs(pie_decoder *d, int n, int rows_cap, int blo
 }
 
 int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap, int32_t *recent_ids, void *workspace) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_tail: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_tail: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_tail")) return rc;
     if (!table) return d->rows.sampler = {}, PIE_OK;  // off
     PIE_REQUIRE(recent_ids && workspace, PIE_E_ARG, "pie_decoder_set_batch_tail: null pointer");
     PIE_REQUIRE(pie_aligned(recent_ids, 4), PIE_E_ALIGN, "pie_decoder_set_batch_tail: the ring needs 4-byte alignment");
@@ -962,8 +946,7 @@ int pie_decoder_set_batch_tail(pie_decoder *d, pie_row_tail *table, int rows_cap
 
 int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint32_t *masks, int mask_words, const int32_t *mask_on,
                                        const int32_t *bias_ids, const float *bias_vals, const int32_t *bias_n, int bias_cap) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_logits_edits: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_logits_edits")) return rc;
     if (rows_cap == 0) return d->rows.edits = {}, PIE_OK;  // off
     PIE_REQUIRE(rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: rows_cap >= 1 (0: off)");
     PIE_REQUIRE(bias_cap >= 0 && bias_cap <= PEN_MAX_IDS, PIE_E_ARG, "pie_decoder_set_batch_logits_edits: bias_cap must be 1..1024 (0: no bias part)");
@@ -987,37 +970,28 @@ int pie_decoder_set_batch_logits_edits(pie_decoder *d, int rows_cap, const uint3
 }
 
 int pie_decoder_set_count_penalty(pie_decoder *d, pie_count_penalty *record, int32_t *counts) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_count_penalty: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_count_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_count_penalty")) return rc;
     if (!record) counts = nullptr;
     else {
         PIE_REQUIRE(counts, PIE_E_ARG, "pie_decoder_set_count_penalty: a record needs its counts");
         PIE_REQUIRE(pie_aligned(record, 4) && pie_aligned(counts, 4), PIE_E_ALIGN, "pie_decoder_set_count_penalty: the record and the counts need 4-byte alignment");
-        if (int rc = tail_stats_alloc(d)) return rc;
     }
-    if (d->cp_record != record || d->cp_counts != counts) drop_graphs(d);  // both are launch arguments (what they point at is read by every launch)
-    d->cp_record = record, d->cp_counts = counts;
-    return PIE_OK;
+    return set_part(d, d->tail.counts, {record, counts});
 }
 
 int pie_decoder_set_dry_penalty(pie_decoder *d, const pie_dry_penalty *record, const int32_t *breakers, int32_t *ids_by_pos, int ids_cap) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_dry_penalty: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_dry_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_dry_penalty")) return rc;
     if (!record) breakers = nullptr, ids_by_pos = nullptr, ids_cap = 0;
     else {
         PIE_REQUIRE(breakers && ids_by_pos && ids_cap >= 1, PIE_E_ARG, "pie_decoder_set_dry_penalty: a record needs its breakers and ids_by_pos [ids_cap >= 1]");
         PIE_REQUIRE(pie_aligned(record, 4) && pie_aligned(breakers, 4) && pie_aligned(ids_by_pos, 4), PIE_E_ALIGN,
                     "pie_decoder_set_dry_penalty: the record, the breakers and ids_by_pos need 4-byte alignment");
-        if (int rc = tail_stats_alloc(d)) return rc;
     }
-    if (d->dry_record != record || d->dry_breakers != breakers || d->dry_ids_by_pos != ids_by_pos || d->dry_ids_cap != ids_cap) drop_graphs(d);  // all launch arguments
-    d->dry_record = record, d->dry_breakers = breakers, d->dry_ids_by_pos = ids_by_pos, d->dry_ids_cap = ids_cap;
-    return PIE_OK;
+    return set_part(d, d->tail.dry, {record, breakers, ids_by_pos, ids_cap});
 }
 
 int pie_decoder_set_batch_dry_penalty(pie_decoder *d, const pie_dry_penalty *records, const int32_t *breakers, int32_t *recent_ids, int rows_cap) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_dry_penalty: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_dry_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_dry_penalty")) return rc;
     if (!records) return d->rows.dry = {}, PIE_OK;  // off
     PIE_REQUIRE(breakers && recent_ids && rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_dry_penalty: the records need their breakers, their rings and rows_cap >= 1");
     PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(breakers, 4) && pie_aligned(recent_ids, 4), PIE_E_ALIGN,
@@ -1027,8 +1001,7 @@ int pie_decoder_set_batch_dry_penalty(pie_decoder *d, const pie_dry_penalty *rec
 }
 
 int pie_decoder_set_batch_count_penalty(pie_decoder *d, pie_count_penalty *records, int32_t *counts, int rows_cap) {
-    PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_set_batch_count_penalty: null decoder");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_set_batch_count_penalty: the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_count_penalty")) return rc;
     if (!records) return d->rows.counts = {}, PIE_OK;  // off
     PIE_REQUIRE(counts && rows_cap >= 1, PIE_E_ARG, "pie_decoder_set_batch_count_penalty: the records need their counts and rows_cap >= 1");
     PIE_REQUIRE(pie_aligned(records, 4) && pie_aligned(counts, 4), PIE_E_ALIGN, "pie_decoder_set_batch_count_penalty: the records and the counts need 4-byte alignment");

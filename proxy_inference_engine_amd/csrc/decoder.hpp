@@ -82,6 +82,76 @@ struct RowsTail {
     bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records || dry.records; }
 };
 
+// The single-sequence step's configured tail, applied where the tail writes the bound outputs and pie_decoder::tail_raw is
+// false: eight parts, each set as a whole by its own entry and off in its value-initialised state.  Caller-owned device memory whose CONTENTS
+// may change between steps; every field is a launch argument that a captured step graph bakes in, so a setter drops the graphs exactly when
+// its part compares unequal (decoder.hip: set_part): a field that joins a part joins the operator== beside it.
+struct StepTail {
+    struct Penalty {  // pie_decoder_set_logits_penalty: the repetition penalty over the last `context` of ids_by_pos [ids_cap]
+        double value = 1.0;  // 1.0: off
+        int context = 0, *ids_by_pos = nullptr, ids_cap = 0;
+        bool on() const { return value != 1.0; }
+        bool operator==(const Penalty &o) const { return value == o.value && context == o.context && ids_by_pos == o.ids_by_pos && ids_cap == o.ids_cap; }
+    } penalty;
+    struct Sampler {  // pie_decoder_set_sampler: pie_sample's launches behind the finish
+        int mode = PIE_SAMPLE_GREEDY, k = 0;  // PIE_SAMPLE_GREEDY: off
+        double temp = 1.0, p = 0.0;
+        unsigned long long seed = 0, *counter = nullptr;
+        void *ws = nullptr;
+        bool on() const { return mode != PIE_SAMPLE_GREEDY; }
+        bool operator==(const Sampler &o) const { return mode == o.mode && k == o.k && temp == o.temp && p == o.p && seed == o.seed && counter == o.counter && ws == o.ws; }
+    } sampler;
+    struct Mask {  // pie_decoder_set_logits_mask: the token mask, applied by the fresh partials on their way
+        const unsigned *words = nullptr;  // [>= ceil(vocab / 32)], nullptr: off
+        bool on() const { return words != nullptr; }
+        bool operator==(const Mask &o) const { return words == o.words; }
+    } mask;
+    struct Bias {  // pie_decoder_set_logit_bias
+        const int *ids = nullptr;
+        const float *vals = nullptr;
+        int n = 0;  // 0: off
+        bool on() const { return n != 0; }
+        bool operator==(const Bias &o) const { return ids == o.ids && vals == o.vals && n == o.n; }
+    } bias;
+    struct Top {  // pie_decoder_set_top_logprobs: pie_top_logprobs' launches, last
+        int n = 0, *ids = nullptr;  // n == 0: off
+        float *vals = nullptr;
+        void *ws = nullptr;
+        bool on() const { return n != 0; }
+        bool operator==(const Top &o) const { return n == o.n && ids == o.ids && vals == o.vals && ws == o.ws; }
+    } top;
+    struct Counts {  // pie_decoder_set_count_penalty: the frequency / presence record and its counts [vocab]
+        pie_count_penalty *record = nullptr;  // nullptr: off
+        int *counts = nullptr;
+        bool on() const { return record != nullptr; }
+        bool operator==(const Counts &o) const { return record == o.record && counts == o.counts; }
+    } counts;
+    struct Dry {  // pie_decoder_set_dry_penalty: the DRY record, breaker table [PIE_DRY_BREAKERS_MAX] and ids_by_pos [ids_cap]
+        const pie_dry_penalty *record = nullptr;  // nullptr: off
+        const int *breakers = nullptr;
+        int *ids_by_pos = nullptr, ids_cap = 0;
+        bool on() const { return record != nullptr; }
+        bool operator==(const Dry &o) const { return record == o.record && breakers == o.breakers && ids_by_pos == o.ids_by_pos && ids_cap == o.ids_cap; }
+    } dry;
+    struct Xtc {  // pie_decoder_set_xtc: a launch argument of the sampler's launches, read only when a sampler is set
+        const pie_xtc *record = nullptr;  // nullptr: off
+        bool on() const { return record != nullptr; }
+        bool operator==(const Xtc &o) const { return record == o.record; }
+    } xtc;
+    LogitStat *tail_stats = nullptr;  // owned scratch, not configuration: [TAIL_STAT_TILES] partials of the edited logits (decoder.hip: set_part)
+    // The only readers of "what is configured" besides the launches:
+    // some part wants more than the greedy tail over the lm_head's own partials.  XTC is missing on purpose: it only changes a sampler's
+    // draw, so alone it configures nothing (and with a sampler, the sampler answers).
+    bool configured() const { return penalty.on() || sampler.on() || mask.on() || bias.on() || top.on() || counts.on() || dry.on(); }
+    // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale.  The sampler, XTC and top-n are
+    // missing on purpose: they read the finished log-probabilities and change no logit.
+    bool edits_logits() const { return penalty.on() || mask.on() || bias.on() || counts.on() || dry.on(); }
+    // Speculation under a tail (speculative.hip: spec_prologue) admits the penalty, the bias, the sampler and XTC -- what its per-row edit
+    // and its sampled verify apply -- and refuses every other part by name.  (The greedy and raw pass asks !configured() and !xtc.on().)
+    const char *spec_tail_refused() const { return mask.on() ? "a token mask" : top.on() ? "a top-logprobs record" : counts.on() ? "frequency / presence counts" : dry.on() ? "a DRY penalty" : nullptr; }
+    bool spec_tail_admitted() const { return penalty.on() || sampler.on() || bias.on() || xtc.on(); }
+};
+
 // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): the prompt passes score their rows in blocks of at most
 // `block` rows -- lm_head into the logits block at the head of ws, then pie_prompt_logprobs' launches on the op's workspace behind it (op_ws).
 // Caller-owned; record i belongs to row i of the call (ALL its N rows, not RowsTail's S output rows); n == 0: off.  In no graph's key.
@@ -159,47 +229,12 @@ struct pie_decoder {
     bool ring = false;
     int ring_w = 0, ring_row0 = 0;  // window; buffer row of the next prompt pass's first row (host copy of ring_rows->pos at bind time)
     DecState *ring_rows = nullptr;
-    // The configured tail (pie_decoder_set_logits_penalty / _set_sampler): applied where the tail writes the bound outputs and
-    // tail_raw is false (a prompt pass asked for logits on every position keeps raw logits and the greedy tail).  All launch arguments.
-    double pen = 1.0;  // 1.0: off
-    int pen_ctx = 0, ids_cap = 0;
-    int *ids_by_pos = nullptr;        // caller-owned
-    LogitStat *tail_stats = nullptr;  // [TAIL_STAT_TILES] partials of the processed logits (owned, allocated when a penalty, a mask or a bias is first set)
-    int smp_mode = PIE_SAMPLE_GREEDY, smp_k = 0;
-    double smp_temp = 1.0, smp_p = 0.0;
-    unsigned long long smp_seed = 0, *smp_counter = nullptr;
-    void *smp_ws = nullptr;
-    bool tail_raw = false;
-    // The tail's token mask and logit bias (pie_decoder_set_logits_mask / _set_logit_bias): caller-owned device memory whose
-    // CONTENTS may change between steps; the addresses and bias_n are launch arguments.
-    const unsigned *tok_mask = nullptr;  // [>= ceil(vocab / 32)] words, nullptr: off
-    const int *bias_ids = nullptr;
-    const float *bias_vals = nullptr;
-    int bias_n = 0;  // 0: off
-    // Top-n log-probabilities of the single-sequence step (pie_decoder_set_top_logprobs): pie_top_logprobs' launches behind the
-    // step's configured tail (tlp_n > 0).  Caller-owned; all launch arguments.
-    int tlp_n = 0;
-    int *tlp_ids = nullptr;
-    float *tlp_vals = nullptr;
-    void *tlp_ws = nullptr;
-    // Frequency / presence penalties of the single-sequence step (pie_decoder_set_count_penalty): a caller-owned record and
-    // counts whose CONTENTS change between steps; launch arguments of the step's tail.
-    pie_count_penalty *cp_record = nullptr;  // nullptr: off
-    int *cp_counts = nullptr;                // [vocab]
-    // The DRY penalty of the single-sequence step (pie_decoder_set_dry_penalty): a caller-owned record, breaker table and
-    // ids by position whose CONTENTS change between steps; launch arguments of the step's tail.
-    const pie_dry_penalty *dry_record = nullptr;  // nullptr: off
-    const int *dry_breakers = nullptr;            // [PIE_DRY_BREAKERS_MAX]
-    int *dry_ids_by_pos = nullptr;                // [dry_ids_cap]
-    int dry_ids_cap = 0;
-    // XTC of the single-sequence step's sampler (pie_decoder_set_xtc): a caller-owned record whose CONTENTS change between
-    // steps; a launch argument of the sampler's launches, read only when a sampler is set.
-    const pie_xtc *xtc_record = nullptr;  // nullptr: off
+    StepTail tail;          // the single-sequence step's configured tail
+    bool tail_raw = false;  // per pass, not configuration: a prompt pass asked for logits on every position keeps raw logits and the greedy tail
     RowsTail rows;        // the multi-sequence passes' per-row tail state
     PromptScores prompt;  // the prompt passes' log-probabilities of prompt tokens
     unsigned long long batch_replays = 0;  // pie_decoder_step_batch calls served by the captured graph
     int batch_graph_kernels = -1;          // kernel nodes of the batch graph captured last
-    bool tail_configured() const { return pen != 1.0 || smp_mode != PIE_SAMPLE_GREEDY || tok_mask || bias_n || tlp_n || cp_record || dry_record; }
     hipGraphExec_t graph[2] = {nullptr, nullptr};  // [with_logits]
     int graph_kernels[2] = {-1, -1};                // kernel nodes of each captured graph (hipGraphGetNodes)
     int graph_form[2] = {ATTN_TWO_LAUNCHES, ATTN_TWO_LAUNCHES};  // the attn_form each graph was captured with (re-captured when that form is withdrawn)

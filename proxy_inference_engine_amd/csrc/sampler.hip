@@ -460,7 +460,7 @@ int sample_check(const char *who, int V, int mode, double temp, double p, int k,
 }
 
 // Python scalars enter the reference's fp32 arithmetic as the fp32 value of the double expression: 1 / temperature, 1 - top_p, log(min_p)
-static void sample_derive(int mode, double temp, double p, int k, float *inv_temp, float *thr, int *k_out) {
+void sample_derive(int mode, double temp, double p, int k, float *inv_temp, float *thr, int *k_out) {
     *inv_temp = (float)(1.0 / temp);
     *thr = mode == SMP_TOP_P ? (float)(1.0 - p) : (mode == SMP_MIN_P ? (float)log(p) : 0.0f);
     *k_out = mode == SMP_TOP_K || mode == SMP_MIN_P ? k : 0;

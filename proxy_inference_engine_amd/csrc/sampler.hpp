@@ -32,6 +32,8 @@ struct SampleXtc {
 
 // pie_sample's argument checks, reported under `who`; nothing is launched
 int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace);
+// what the launches compute with, from pie_sample's parameters: the ONE place (pie_row_tail_pack's and the speculative verify's records draw as sample_launch does)
+void sample_derive(int mode, double temp, double p, int k, float *inv_temp, float *thr, int *k_out);
 int sample_launch(const float *logprobs, int rows, int V, int mode, double temp, double p, int k, unsigned long long seed, unsigned long long *counter,
                   void *workspace, int *tokens, int *kept_count, unsigned char *kept_mask, const SampleFeed &feed, hipStream_t st,
                   const SampleXtc &xtc = {});

@@ -306,8 +306,7 @@ static int spec_verify_sampled_launch(u16 *logits, int rows, int V, int dtype, c
         f.rows = rows, f.mode = mode, f.seed = seed, f.counter = counter, f.xtc = xtc, f.base = base;
         f.table = (pie_row_tail *)(ws + lay.table), f.xtc_rows = (pie_xtc *)(ws + lay.xtc);
         f.smp_ws = (unsigned long long *)(ws + lay.smp), f.smp_row_words = pie_sample_workspace_bytes(1, V) / sizeof(unsigned long long);
-        f.inv_temp = (float)(1.0 / temp), f.thr = mode == PIE_SAMPLE_TOP_P ? (float)(1.0 - p) : (mode == PIE_SAMPLE_MIN_P ? (float)log(p) : 0.0f);  // pie_sample's derived values
-        f.k = mode == PIE_SAMPLE_TOP_K || mode == PIE_SAMPLE_MIN_P ? k : 0;
+        sample_derive(mode, temp, p, k, &f.inv_temp, &f.thr, &f.k);
         hipLaunchKernelGGL(k_spec_fill_rows, dim3(1), dim3(SPEC_MAX_ROWS), 0, st, f);
         PIE_LAUNCH_CHECK();
         if (int rc = sample_rows_launch(logprobs, rows, V, f.table, ws + lay.smp, tok, nullptr, nullptr, st, SampleXtc{xtc ? f.xtc_rows : nullptr, nullptr})) return rc;
@@ -379,92 +378,91 @@ size_t pie_decoder_spec_workspace_bytes(const pie_decoder *d, int rows) {
     return align16((size_t)rows * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_MAX_ROWS) + spec_verify_workspace_bytes(rows);
 }
 
-int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
-                          int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
-    PIE_REQUIRE(d && draft_ids && out_tokens && out_n && workspace, PIE_E_ARG, "pie_decoder_spec_step: null pointer");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_spec_step: not available on a tensor-parallel shard");
-    PIE_REQUIRE(!d->kv_quant && !d->ring, PIE_E_STATE, "pie_decoder_spec_step: not available on a quantized or rotating KV cache");
-    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, "pie_decoder_spec_step: not available on int8 KV pages");
-    PIE_REQUIRE(!d->tail_configured() && !d->prompt.n, PIE_E_STATE,
-                "pie_decoder_spec_step: speculation is greedy and raw: no sampler, penalty, mask, bias, top-logprobs, counts or prompt scoring may be set");
-    PIE_REQUIRE(!d->xtc_record, PIE_E_STATE, "pie_decoder_spec_step: speculation is greedy: no XTC record may be set");
-    const int rows = n_draft + 1;
-    PIE_REQUIRE(n_draft >= 1 && rows >= prefill_min_rows(), PIE_E_SHAPE, "pie_decoder_spec_step: fewer rows than the many-row pass takes (run a plain step)");
-    PIE_REQUIRE(rows <= SPEC_MAX_ROWS, PIE_E_SHAPE, "pie_decoder_spec_step: at most 31 drafts");
-    PIE_REQUIRE(seq_cap >= 0 && (seq_ids || seq_cap == 0), PIE_E_ARG, "pie_decoder_spec_step: bad sequence buffer");
-    PIE_REQUIRE(pie_aligned(draft_ids, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(logprobs_rows, 4) && pie_aligned(seq_ids, 4) &&
-                    pie_aligned(seq_len, 4), PIE_E_ALIGN, "pie_decoder_spec_step: 4-byte alignment required");
-    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_decoder_spec_step: workspace needs 16-byte alignment");
-    hipStream_t st = (hipStream_t)stream;
-    const pie_decoder_config &c = d->cfg;
-    u16 *block = (u16 *)workspace;
-    int *fed = (int *)((char *)workspace + align16((size_t)rows * c.vocab * 2));
-    void *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_MAX_ROWS);
-    PIE_REQUIRE(d->glob_set && d->kv_set && d->out_set, PIE_E_STATE, "pie_decoder: set_globals, set_kv and bind_outputs must be called before stepping");
-    hipLaunchKernelGGL(k_spec_gather, dim3(1), dim3(SPEC_MAX_ROWS), 0, st, (const DecState *)d->state, draft_ids, n_draft, d->embed_vocab(), fed);
-    PIE_LAUNCH_CHECK();
-    // raw logits on every row; the pass ends in the greedy tail of its last row, which leaves pos = o + rows
-    if (int rc = pie_decoder_prefill(d, fed, rows, block, stream)) return rc;
-    SpecState s;
-    s.state = d->state, s.history = d->history, s.hist_cap = d->hist_cap, s.fed = fed;
-    s.seq_ids = seq_ids, s.seq_cap = seq_cap, s.seq_len = seq_len, s.token_out = d->token_out;
-    return spec_verify_launch(block, rows, c.vocab, c.dtype, draft_ids, out_tokens, out_n, logprobs_rows, verify_ws, s, st);
-}
-
 // workspace: the logits block [rows, vocab] T | the pass's input ids [32] | pie_spec_verify_sampled's workspace
 size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows) {
     if (!d || rows < 2 || rows > SPEC_MAX_ROWS || pie_sample_workspace_bytes(rows, d->cfg.vocab) == 0) return 0;
     return align16((size_t)rows * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_MAX_ROWS) + SpecSampledLayout(rows, d->cfg.vocab).bytes;
 }
 
-int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
-                               int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
-    const std::string who = "pie_decoder_spec_step_tail: ";
-    PIE_REQUIRE(d && draft_ids && out_tokens && out_n && logprobs_rows && workspace, PIE_E_ARG, who + "null pointer");
+}  // extern "C"
+
+namespace {
+
+// What the two pie_decoder_spec_step* entries share: the entry's refusals -- with_tail: which parts of the step's tail the pass admits is
+// StepTail's answer (decoder.hpp) --, the shape and alignment checks, the workspace's carve-up (the logits block at its head, then s->fed,
+// then *verify_ws), the gather of the input rows, the SpecState fill and the many-row pass itself, raw logits on every row.
+int spec_prologue(const char *entry, bool with_tail, pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows,
+                  void *workspace, int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream, SpecState *s, void **verify_ws) {
+    const std::string who = std::string(entry) + ": ";
+    PIE_REQUIRE(d && draft_ids && out_tokens && out_n && (logprobs_rows || !with_tail) && workspace, PIE_E_ARG, who + "null pointer");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
     PIE_REQUIRE(!d->kv_quant && !d->ring, PIE_E_STATE, who + "not available on a quantized or rotating KV cache");
     PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
-    PIE_REQUIRE(!d->tok_mask, PIE_E_STATE, who + "not available with a token mask");
-    PIE_REQUIRE(!d->tlp_n, PIE_E_STATE, who + "not available with a top-logprobs record");
-    PIE_REQUIRE(!d->cp_record, PIE_E_STATE, who + "not available with frequency / presence counts");
-    PIE_REQUIRE(!d->dry_record, PIE_E_STATE, who + "not available with a DRY penalty");
-    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
-    const bool penalise = d->pen != 1.0, draws = d->smp_mode != PIE_SAMPLE_GREEDY;
-    PIE_REQUIRE(penalise || draws || d->bias_n || d->xtc_record, PIE_E_STATE,
-                who + "no sampler, XTC record, repetition penalty or logit bias is set (the greedy and raw pass is pie_decoder_spec_step)");
-    const int rows = n_draft + 1;
+    const StepTail &t = d->tail;
+    if (!with_tail) {
+        PIE_REQUIRE(!t.configured() && !d->prompt.n, PIE_E_STATE,
+                    who + "speculation is greedy and raw: no sampler, penalty, mask, bias, top-logprobs, counts or prompt scoring may be set");
+        PIE_REQUIRE(!t.xtc.on(), PIE_E_STATE, who + "speculation is greedy: no XTC record may be set");
+    } else {
+        const char *part = t.spec_tail_refused();
+        PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
+        PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
+        PIE_REQUIRE(t.spec_tail_admitted(), PIE_E_STATE,
+                    who + "no sampler, XTC record, repetition penalty or logit bias is set (the greedy and raw pass is pie_decoder_spec_step)");
+    }
+    const int rows = n_draft + 1, V = d->cfg.vocab;
     PIE_REQUIRE(n_draft >= 1 && rows >= prefill_min_rows(), PIE_E_SHAPE, who + "fewer rows than the many-row pass takes (run a plain step)");
     PIE_REQUIRE(rows <= SPEC_MAX_ROWS, PIE_E_SHAPE, who + "at most 31 drafts");
     PIE_REQUIRE(seq_cap >= 0 && (seq_ids || seq_cap == 0), PIE_E_ARG, who + "bad sequence buffer");
     PIE_REQUIRE(pie_aligned(draft_ids, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(logprobs_rows, 4) && pie_aligned(seq_ids, 4) &&
                     pie_aligned(seq_len, 4), PIE_E_ALIGN, who + "4-byte alignment required");
     PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, who + "workspace needs 16-byte alignment");
+    PIE_REQUIRE(!with_tail || pie_sample_workspace_bytes(rows, V) != 0, PIE_E_SHAPE, who + "the vocabulary is larger than the sampler takes (524288)");
+    int *fed = (int *)((char *)workspace + align16((size_t)rows * V * 2));
+    *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_MAX_ROWS);
+    PIE_REQUIRE(d->glob_set && d->kv_set && d->out_set, PIE_E_STATE, "pie_decoder: set_globals, set_kv and bind_outputs must be called before stepping");
+    hipLaunchKernelGGL(k_spec_gather, dim3(1), dim3(SPEC_MAX_ROWS), 0, (hipStream_t)stream, (const DecState *)d->state, draft_ids, n_draft, d->embed_vocab(), fed);
+    PIE_LAUNCH_CHECK();
+    s->state = d->state, s->history = d->history, s->hist_cap = d->hist_cap, s->fed = fed;
+    s->seq_ids = seq_ids, s->seq_cap = seq_cap, s->seq_len = seq_len, s->token_out = d->token_out;
+    // Raw logits on every row: logits_all != nullptr makes the pass's own last-row tail raw and greedy (pie_decoder::tail_raw), which leaves
+    // pos = o + rows; a configured sampler draws nothing there and its counter stays where it is.
+    return pie_decoder_prefill(d, fed, rows, workspace, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                          int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
+    SpecState s;
+    void *verify_ws;
+    if (int rc = spec_prologue("pie_decoder_spec_step", false, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
+    return spec_verify_launch((const u16 *)workspace, n_draft + 1, d->cfg.vocab, d->cfg.dtype, draft_ids, out_tokens, out_n, logprobs_rows, verify_ws, s, (hipStream_t)stream);
+}
+
+int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                               int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
+    SpecState s;
+    void *verify_ws;
+    if (int rc = spec_prologue("pie_decoder_spec_step_tail", true, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const pie_decoder_config &c = d->cfg;
-    PIE_REQUIRE(pie_sample_workspace_bytes(rows, c.vocab) != 0, PIE_E_SHAPE, who + "the vocabulary is larger than the sampler takes (524288)");
-    u16 *block = (u16 *)workspace;
-    int *fed = (int *)((char *)workspace + align16((size_t)rows * c.vocab * 2));
-    void *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_MAX_ROWS);
-    PIE_REQUIRE(d->glob_set && d->kv_set && d->out_set, PIE_E_STATE, "pie_decoder: set_globals, set_kv and bind_outputs must be called before stepping");
-    hipLaunchKernelGGL(k_spec_gather, dim3(1), dim3(SPEC_MAX_ROWS), 0, st, (const DecState *)d->state, draft_ids, n_draft, d->embed_vocab(), fed);
-    PIE_LAUNCH_CHECK();
-    // Raw logits on every row: logits_all != nullptr makes the pass's own last-row tail raw and greedy (pie_decoder::tail_raw), so the
-    // configured sampler draws nothing there and its counter stays where it is -- the rows' draws below are the pass's only ones.
-    if (int rc = pie_decoder_prefill(d, fed, rows, block, stream)) return rc;
-    if (penalise || d->bias_n) {  // the rows' edits, in the step tail's order: penalty, then bias
+    const StepTail &t = d->tail;
+    const int rows = n_draft + 1;
+    if (t.penalty.on() || t.bias.on()) {  // the rows' edits, in the step tail's order: penalty, then bias
         SpecEditArgs e = {};
-        e.logits = block, e.V = c.vocab, e.rows = rows, e.penalty = (float)d->pen, e.context = d->pen_ctx, e.ids_by_pos = d->ids_by_pos, e.ids_cap = d->ids_cap;
-        e.state = d->state, e.fed = fed, e.draft = draft_ids;
-        e.b = BiasArgs{d->bias_ids, d->bias_vals, d->bias_n, penalise};
-        if (int rc = launch_for_dtype(c.dtype, "spec edit:", [&](auto t) { hipLaunchKernelGGL(k_spec_edit_rows<decltype(t)>, dim3((unsigned)rows), dim3(PEN_MAX_IDS), 0, st, e); }))
+        e.logits = (u16 *)workspace, e.V = c.vocab, e.rows = rows, e.penalty = (float)t.penalty.value, e.context = t.penalty.context, e.ids_by_pos = t.penalty.ids_by_pos, e.ids_cap = t.penalty.ids_cap;
+        e.state = d->state, e.fed = s.fed, e.draft = draft_ids;
+        e.b = BiasArgs{t.bias.ids, t.bias.vals, t.bias.n, t.penalty.on()};
+        if (int rc = launch_for_dtype(c.dtype, "spec edit:", [&](auto ty) { hipLaunchKernelGGL(k_spec_edit_rows<decltype(ty)>, dim3((unsigned)rows), dim3(PEN_MAX_IDS), 0, st, e); }))
             return rc;
     }
-    SpecState s;
-    s.state = d->state, s.history = d->history, s.hist_cap = d->hist_cap, s.fed = fed;
-    s.seq_ids = seq_ids, s.seq_cap = seq_cap, s.seq_len = seq_len, s.token_out = d->token_out;
-    if (penalise) s.ids_by_pos = d->ids_by_pos, s.ids_cap = d->ids_cap;
-    return spec_verify_sampled_launch(block, rows, c.vocab, c.dtype, draft_ids, d->smp_mode, d->smp_temp, d->smp_p, d->smp_k, d->smp_seed, d->smp_counter,
-                                      draws ? d->xtc_record : nullptr, out_tokens, out_n, logprobs_rows, verify_ws, s, st);
+    if (t.penalty.on()) s.ids_by_pos = t.penalty.ids_by_pos, s.ids_cap = t.penalty.ids_cap;
+    const StepTail::Sampler &m = t.sampler;
+    return spec_verify_sampled_launch((u16 *)workspace, rows, c.vocab, c.dtype, draft_ids, m.mode, m.temp, m.p, m.k, m.seed, m.counter, m.on() ? t.xtc.record : nullptr, out_tokens, out_n,
+                                      logprobs_rows, verify_ws, s, st);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ from typing import Callable
 import torch
 
 from ..llama.language import Model as LanguageModel
+from ..llama.step_state import STEP_TAIL_SURFACE
 
 
 @dataclass
@@ -112,31 +113,11 @@ class Model:
     def step_embeds(self, inputs_embeds, cache, ids=None):
         return self.language_model.step_embeds(inputs_embeds, cache, ids)
 
-    # the step's configurable tail is the text tower's (llama/language.py: set_step_tail)
-    def set_step_tail(self, sampler=None, repetition_penalty: float = 1.0, context_size: int = 60, token_mask=None, logit_bias=None,
-                      top_logprobs: int | None = None, frequency_penalty: float = 0.0, presence_penalty: float = 0.0,
-                      count_start: int | None = None, dry: tuple | None = None, xtc: tuple | None = None) -> None:
-        self.language_model.set_step_tail(sampler, repetition_penalty, context_size, token_mask, logit_bias, top_logprobs, frequency_penalty,
-                                          presence_penalty, count_start, dry, xtc)
-
-    def reset_step_counts(self, start: int, generated_ids=()) -> None:
-        self.language_model.reset_step_counts(start, generated_ids)
-
-    @property
-    def step_tail_counts(self):
-        return self.language_model.step_tail_counts
-
-    @property
-    def step_top_logprobs(self):
-        return self.language_model.step_top_logprobs
-
-    @property
-    def step_tail(self):
-        return self.language_model.step_tail
-
-    @property
-    def step_tail_edits(self):
-        return self.language_model.step_tail_edits
+    def __getattr__(self, name):
+        """The step's configurable tail is the text tower's: exactly step_state.STEP_TAIL_SURFACE (names this class lacks arrive here)."""
+        if name in STEP_TAIL_SURFACE:
+            return getattr(self.language_model, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     @property
     def fed_ids(self):

@@ -3,7 +3,7 @@ generation knobs, each through the fused step tail and through th
 
     python scripts/bench_step_tail.py [--steps 64] [--warmup 8] [--reps 3] [--prompt 128]
 
-Configurations: greedy | temp=1, top_k=40 | repetition_penalty=1.1 | both.  "host" runs the same request with the sampler closure and
+Configurations: greedy | temp=1, top_k=40 | repetition_penalty=1.1 | both | both and a three-entry logit_bias.  "host" runs the same request with the sampler closure and
 the processor wrapped in plain callables (no `hip_spec`, no `.penalty`), which is exactly what an engine without the fused tail runs:
 model.step + the sampler closure for a sampler alone, Model.__call__ + the torch processor + logprobs_argmax with a penalty.  (Greedy has
 no other branch: its "host" column is the same path, the run-to-run spread.)  The two paths alternate, rep by rep, on one model; every rep
@@ -22,7 +22,8 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 CONFIGS = {"greedy": dict(temp=0), "top_k": dict(temp=1.0, top_k=40), "penalty": dict(temp=0, repetition_penalty=1.1),
-           "top_k+penalty": dict(temp=1.0, top_k=40, repetition_penalty=1.1)}
+           "top_k+penalty": dict(temp=1.0, top_k=40, repetition_penalty=1.1),
+           "top_k+penalty+bias": dict(temp=1.0, top_k=40, repetition_penalty=1.1, logit_bias={11: -2.0, 257: 1.5, 4000: 0.75})}
 
 
 def plain(fn):
