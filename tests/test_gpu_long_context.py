@@ -48,12 +48,13 @@ def m8b():
     return w, po.OracleLlama(CFG, w, DT), build(CFG, w)
 
 
-def history(rng, T, cap, plans, more=()):
+def history(rng, T, cap, plans, more=(), cfg=CFG, dt=DT, **kw):
     """One (K, V) history [Hkv, cap, D] per layer (fp32, representable in T); `more`: marker rows besides marker_rows', with
-    the K norm of rows 0 and T - 1."""
+    the K norm of rows 0 and T - 1.  cfg / dt: another geometry than this file's; kw: kv_history's scales."""
     more = [r for r in more if 0 <= r < T]
     rows = sorted(set(marker_rows(T, plans)) | set(more))
-    return [kv_history(rng, HKV, T, D, DT, rows, cap=cap, strong=more) for _ in range(NL)]
+    return [kv_history(rng, cfg["num_key_value_heads"], T, cfg["head_dim"] if "head_dim" in cfg else D, dt, rows, cap=cap, strong=more, **kw)
+            for _ in range(cfg["num_hidden_layers"])]
 
 
 def dev_rows(x):
@@ -81,13 +82,16 @@ def oracle_cache(layers, T):
     return out
 
 
-def ref_step16(w, freqs, token, pos, kv, extra=None):
+def ref_step16(w, freqs, token, pos, kv, extra=None, cfg=CFG, dt=DT, regime="qmv", new_row=None):
     """One 16-bit decode step composed from oracle primitives over explicit rows: kv[li] = (K, V) [Hkv, pos, D] cached, the new row at
-    `pos`, then extra[li] (rows a kernel that reads past the end would see).  Returns the logits."""
-    e, H, Hq = "model.embed_tokens", CFG["hidden_size"], CFG["num_attention_heads"]
+    `pos`, then extra[li] (rows a kernel that reads past the end would see).  Returns the logits.  cfg / dt: another geometry than this
+    file's; regime: the oracle's Linear regime for the pass's row count; new_row(li, k, v) -> (k, v): what the cache holds of the new row
+    (an int8 page: its dequantised codes) and, as a side effect, a record of it."""
+    e, Hq, HKV, NL = "model.embed_tokens", cfg["num_attention_heads"], cfg["num_key_value_heads"], cfg["num_hidden_layers"]
+    D, DT = cfg["head_dim"] if "head_dim" in cfg else cfg["hidden_size"] // Hq, dt
 
     def lin(x, name):
-        return po.quantized_matmul(x, w[name + ".weight"], w[name + ".scales"], w[name + ".biases"], group_size=64, bits=4, dtype=DT)
+        return po.quantized_matmul(x, w[name + ".weight"], w[name + ".scales"], w[name + ".biases"], group_size=64, bits=4, dtype=DT, regime=regime)
 
     h = po.dequantize(w[e + ".weight"][[token]], w[e + ".scales"][[token]], w[e + ".biases"][[token]], 64, 4, DT)
     for li in range(NL):
@@ -96,6 +100,8 @@ def ref_step16(w, freqs, token, pos, kv, extra=None):
         q = po.rope(lin(xn, p + ".self_attn.q_proj").reshape(Hq, 1, D), freqs, pos, DT)
         k = po.rope(lin(xn, p + ".self_attn.k_proj").reshape(HKV, 1, D), freqs, pos, DT)
         v = lin(xn, p + ".self_attn.v_proj").reshape(HKV, 1, D)
+        if new_row is not None:
+            k, v = new_row(li, k, v)
         ks, vs = [kv[li][0], k], [kv[li][1], v]
         if extra is not None:
             ks.append(extra[li][0]), vs.append(extra[li][1])
