@@ -503,6 +503,40 @@ int pie_spec_verify(const void *logits, int rows, int V, int dtype, const int32_
 size_t pie_spec_verify_sampled_workspace_bytes(int rows, int V);
 int pie_spec_verify_sampled(const void *logits, int rows, int V, int dtype, const int32_t *draft, int mode, double temp, double p, int k, unsigned long long seed,
                             unsigned long long *counter, const pie_xtc *xtc, int32_t *out_tokens, int32_t *out_n, float *logprobs, void *workspace, void *stream);
+/* pie_spec_verify_draft: the verify of a block drafted by a MODEL -- speculative sampling (Leviathan et al. 2023, Chen et
+ * al. 2023).  logits [rows, V] T as above; q_logprobs DEVICE fp32 [rows - 1, V]: the drafter's log-probabilities at the step that drew
+ * draft[i]; one sampler setting (mode, temp, p, k) for both sides; (seed, counter) the TARGET's stream, c = counter[0] read on the device.
+ *   dist: for a row of fp32 log-probabilities lp with the sampler's kept set K -- exactly the kept_mask pie_sample yields on that row (the
+ *     op runs the sampler's own filter launches with a mask output) -- dist(x) = exp((lp[x] - max_K lp) * inv_temp) / sum_{y in K}
+ *     exp((lp[y] - max_K lp) * inv_temp) for x in K and 0 elsewhere, inv_temp = fp32(1 / temp); a filter that kept nothing (top_p below
+ *     2^-25) gives dist = 0 everywhere.  P_r = dist of pie_logprobs_argmax's bits of logits row r (written to logprobs, required, fp32
+ *     [rows, V], every row); Q_i = dist of q_logprobs row i.  The arithmetic is fp64, rounded to fp32 where a value is stored or tested.
+ *   u_i = ((w >> 8) + 0.5) * 2^-24 in fp32, w = word 0 of the Philox-4x32-10 block with key seed and counter {0xFFFFFFFE, 0, call lo, call
+ *     hi}, call = c + i: XTC's coin construction on an index word that neither the coin (0xFFFFFFFF) nor a vocabulary index (<= V / 4) uses.
+ *   Draft i is accepted iff 0 <= draft[i] < V and Q_i(draft[i]) > 0 and u_i * Q_i(draft[i]) < P_i(draft[i]) (fp32 values, one fp32 multiply,
+ *     one fp32 compare); n_acc = the length of the accepted prefix; an id outside [0, V) is never used as an index.
+ *   n_acc < rows - 1, j = n_acc: the last token is what pie_sample(PIE_SAMPLE_CATEGORICAL, temp = 1) draws at counter {c + j, 0} over the
+ *     residual row R_j[x] = log(max(0, P_j(x) - Q_j(x))), -inf where the difference is <= 0 -- bit for bit, through pie_sample's launches.
+ *     FALLBACK: if every entry of R_j is -inf (Q_j covers P_j: the refusal came from an id outside the vocabulary), the last token is
+ *     pie_sample's ordinary draw from row j at {c + j, 0}.
+ *   n_acc == rows - 1: the last token is pie_sample's ordinary draw from row rows - 1 at {c + rows - 1, 0}, the bonus token.
+ *   out_tokens [rows] = the accepted drafts, the last token, then -1; out_n [1] = n_acc + 1; afterwards counter = {c + out_n, 0}.
+ *   accept_rec (nullable) fp32 [rows - 1, 3] = (P_i(d_i), Q_i(d_i), u_i) of EVERY draft (0, 0 for an id outside the vocabulary); residual
+ *     (nullable) fp32 [rows, V]: rows 0 .. rows - 2 = R_i, row j holding the bits drawn from; row rows - 1 is not written.  Diagnostics.
+ * 19 launches: the partials and the finish over every row (2), one workgroup that fills both filters' records (1), pie_sample_rows' 5
+ * over the target's rows -- whose draws are the rows' ordinary tokens -- and 5 over the drafter's, one over (ceil(V / 512), 2 rows - 1) for
+ * the tiles' shares of the normalisers and one workgroup per row that merges them in a fixed order (2), one over ceil(V / 512) tiles --
+ * times rows - 1 with the residual diagnostic -- that decides the drafts in every workgroup and writes R_j (1), pie_sample's 2, and one
+ * workgroup that composes the tokens and stores the counter (1).  n_acc never visits the host.  No floating-point atomics, nothing
+ * depends on arrival order: results are bit-identical from run to run.  workspace: pie_spec_verify_draft_workspace_bytes(rows, V) bytes
+ * (0 for refused sizes), 16-byte aligned, ZEROED ONCE by the caller (as pie_sample's) and reusable from call to call.  Each before any
+ * launch: a null pointer (the diagnostics excepted), mode PIE_SAMPLE_GREEDY (a greedy draft is a point mass: pie_spec_verify), a dtype that
+ * is neither PIE_BF16 nor PIE_F16, a parameter outside pie_sample's rules: PIE_E_ARG; rows outside 2..32, V outside 1..524288: PIE_E_SHAPE;
+ * logits not 2-byte, draft, q_logprobs or an output not 4-byte, the counter not 8-byte, the workspace not 16-byte aligned: PIE_E_ALIGN. */
+size_t pie_spec_verify_draft_workspace_bytes(int rows, int V);
+int pie_spec_verify_draft(const void *logits, int rows, int V, int dtype, const int32_t *draft, const float *q_logprobs, int mode, double temp, double p, int k,
+                          unsigned long long seed, unsigned long long *counter, int32_t *out_tokens, int32_t *out_n, float *logprobs, float *accept_rec, float *residual,
+                          void *workspace, void *stream);
 
 /* ---------------------------------------------------------------- fused decode step
  * One forward of Model.__call__ (models/llama/language.py:199-210) for inputs[1,1] over per-layer
@@ -867,6 +901,20 @@ int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft,
 size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows);
 int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
                                int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
+/* One speculative pass over a draft MODEL's block: pie_decoder_spec_step_tail's arguments, row bounds and order, plus
+ * q_logprobs DEVICE fp32 [m, vocab] (the drafter's log-probabilities at the step that drew draft i), with pie_spec_verify_draft's launches
+ * in place of pie_spec_verify_sampled's: (1) the gather and pie_decoder_prefill, raw logits on every row; (2) the edit launch when a
+ * repetition penalty or a logit bias is set; (3) pie_spec_verify_draft on the processed block with the decoder's mode / temp / p / k / seed /
+ * counter; (4) its last launch leaves pos = o + out_n, the device-side token and the bound token = the last token, and history, seq_ids,
+ * seq_len and ids_by_pos as pie_decoder_spec_step_tail leaves them; counter = {c + out_n, 0}.  19 or 20 launches beyond the gather and
+ * pie_decoder_prefill's; nothing is captured in a graph, and a decoder that never calls this entry launches exactly what it launches
+ * without it.  REQUIRED: a stochastic sampler (pie_decoder_set_sampler).  PIE_E_STATE before any launch, each by name: no stochastic
+ * sampler; an XTC record (its coin changes P from call to call: out of scope); a token mask; a top-logprobs record; frequency / presence
+ * counts; a DRY penalty; prompt scoring; a tensor-parallel decoder; a quantized or rotating KV cache; int8 pages.  workspace:
+ * pie_decoder_spec_draft_workspace_bytes(d, m + 1) bytes (0 for refused row counts), 16-byte aligned, caller-owned, ZEROED ONCE. */
+size_t pie_decoder_spec_draft_workspace_bytes(const pie_decoder *d, int rows);
+int pie_decoder_spec_step_draft(pie_decoder *d, const int32_t *draft_ids, int n_draft, const float *q_logprobs, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows,
+                                void *workspace, int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
 /* The step's launches by name.  pie_decoder_launch_kernel() enqueues ONE of them with exactly the arguments
  * the step uses (for per-kernel timing with events / rocprof; it does not advance the decode state, and
  * PIE_K_TAIL, which does, is refused).  pie_decoder_kernel_bytes() is that launch's algorithmic HBM traffic

@@ -56,6 +56,7 @@ EXPORTS = [
     "pie_xtc_bytes", "pie_xtc_pack", "pie_sample_xtc", "pie_sample_rows_xtc", "pie_decoder_set_xtc", "pie_decoder_set_batch_xtc",
     "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
     "pie_spec_verify_sampled_workspace_bytes", "pie_spec_verify_sampled", "pie_decoder_spec_tail_workspace_bytes", "pie_decoder_spec_step_tail",
+    "pie_spec_verify_draft_workspace_bytes", "pie_spec_verify_draft", "pie_decoder_spec_draft_workspace_bytes", "pie_decoder_spec_step_draft",
 ]
 
 
@@ -223,6 +224,12 @@ def load() -> C.CDLL:
     lib.pie_decoder_spec_tail_workspace_bytes.restype = C.c_size_t
     lib.pie_decoder_spec_tail_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.pie_decoder_spec_step_tail.argtypes = lib.pie_decoder_spec_step.argtypes
+    lib.pie_spec_verify_draft_workspace_bytes.restype = C.c_size_t
+    lib.pie_spec_verify_draft_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pie_spec_verify_draft.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64] + [C.c_void_p] * 8
+    lib.pie_decoder_spec_draft_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_spec_draft_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    lib.pie_decoder_spec_step_draft.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

@@ -22,7 +22,22 @@
 //   3. pie_sample_rows(_xtc)'s launches (sample_rows_launch): row r drawn as the one-row pie_sample call number c + r of the seed;
 //   4. k_spec_accept_sampled, ONE thread: the accepted run against the drawn tokens, the outputs, counter = {c + n, 0} and -- for the
 //      decoder -- the device-side state, through the functions k_spec_accept ends in.
-// pie_decoder_spec_step_tail puts k_spec_edit_rows in front: one workgroup per row applies the decoder's repetition penalty over the row's
+// pie_spec_verify_draft, 19 launches: speculative sampling over a block a draft MODEL proposed
+//   1. k_logits_stats and k_logits_finish over every row, as above (2);
+//   2. k_spec_draft_fill, one workgroup: c = counter[0] and the records of BOTH filters -- target row r at calls = c + r, the drafter's rows
+//      at any position (their draws are discarded) -- and the sampler workspaces' re-armed headers (1);
+//   3. sample_rows_launch over the target's log-probabilities with a mask output: the kept sets K of P, and the rows' ordinary draws --
+//      the bonus token and the fallback come from them (5); the same over q_logprobs: the kept sets of Q (5);
+//   4. k_spec_dist_stats over (ceil(V / 512), 2 rows - 1): a tile's largest kept log-probability and sum of exp((lp - m) * inv_temp), fp64;
+//      k_spec_dist_merge, one workgroup per row: the tiles' shares in a fixed order (2);
+//   5. k_spec_draft_residual over ceil(V / 512) tiles (x rows - 1 with the residual diagnostic): every workgroup decides the drafts --
+//      thread i draft i: P_i(d), Q_i(d), u_i from the Philox block {0xFFFFFFFE, 0, c + i} -- takes n_acc as the first refusal and
+//      writes its tile of R_j = log(max(0, P_j - Q_j)), j = n_acc, with a per-tile "has a finite entry" flag (1);
+//   6. sample_launch(CATEGORICAL, temp 1) on R_j at {c + j, 0}: pie_sample itself (2);
+//   7. k_spec_draft_commit, one workgroup: the accepted drafts, then the residual's token (the row's ordinary draw when no tile had a
+//      finite entry, or behind a fully accepted block), through spec_commit; counter = {c + n, 0} (1).
+//   No floating-point atomics; every reduction has a fixed order; n_acc stays on the device.
+// pie_decoder_spec_step_tail (and _spec_step_draft) puts k_spec_edit_rows in front: one workgroup per row applies the decoder's repetition penalty over the row's
 // own window (ids_by_pos below the offset, the fed token at it, the drafts behind it) and its logit bias (tail.hpp's phases).
 #include "speculative.hpp"
 
@@ -317,6 +332,261 @@ static int spec_verify_sampled_launch(u16 *logits, int rows, int V, int dtype, c
     return PIE_OK;
 }
 
+// ---------------------------------------------------------------- the verify of a draft MODEL's block
+namespace {
+
+constexpr int DIST_T = 256, DIST_SLICE = 512;  // the sampler's partition of a row: 512 ids per workgroup, two adjacent ids per thread
+constexpr unsigned SPEC_U_IDX4 = 0xFFFFFFFEu;  // the accept test's index word: the coin's is 0xFFFFFFFF, a vocabulary index's <= V / 4
+
+struct DistPart {  // a tile's, then a row's, share of dist's normaliser: the largest kept log-probability and sum exp((lp - m) * inv_temp) over the kept ids
+    double m, s;   // no kept id: m = -inf, s = 0
+};
+
+struct SpecDraftMeta {
+    unsigned long long base;        // c = counter[0] at entry
+    unsigned long long rcounter[2];  // the residual draw's stream position {c + n_acc, 0}: pie_sample's counter
+    int n_acc, res_tok;
+};
+
+// pie_spec_verify_draft's workspace.  P rows are 0 .. rows - 1, Q rows rows .. 2 rows - 2 wherever both share an array.
+struct SpecDraftLayout {
+    int tiles;
+    size_t tok, qtok, comp, meta, table, norms, parts, flags, resrow, mask, smp_res, smp, bytes;
+    SpecDraftLayout(int rows, int V) {
+        tiles = (V + DIST_SLICE - 1) / DIST_SLICE;
+        const size_t dist_rows = 2 * (size_t)rows - 1;
+        tok = sizeof(LogitStat) * TAIL_STAT_TILES * (size_t)rows;
+        qtok = tok + sizeof(int) * SPEC_MAX_ROWS;
+        comp = qtok + sizeof(int) * SPEC_MAX_ROWS;
+        meta = comp + sizeof(int) * SPEC_MAX_ROWS;
+        table = (meta + sizeof(SpecDraftMeta) + 15) & ~(size_t)15;
+        norms = table + sizeof(pie_row_tail) * 2 * SPEC_MAX_ROWS;
+        parts = norms + sizeof(DistPart) * 2 * SPEC_MAX_ROWS;
+        flags = parts + sizeof(DistPart) * dist_rows * tiles;
+        resrow = (flags + sizeof(int) * tiles + 15) & ~(size_t)15;
+        mask = (resrow + sizeof(float) * (size_t)V + 15) & ~(size_t)15;
+        smp_res = (mask + dist_rows * (size_t)V + 15) & ~(size_t)15;
+        smp = smp_res + pie_sample_workspace_bytes(1, V);
+        bytes = smp + pie_sample_workspace_bytes((int)dist_rows, V);
+    }
+};
+
+struct SpecDraftArgs {
+    int rows, V, mode, k;
+    float inv_temp, thr;
+    unsigned long long seed;
+    unsigned long long *counter;
+    const int *draft;            // [rows - 1]
+    const float *logprobs;       // [rows, V]: the target's
+    const float *q_logprobs;     // [rows - 1, V]: the drafter's
+    const unsigned char *mask;   // [2 rows - 1, V]: the sampler's kept sets
+    pie_row_tail *table;         // [2 rows - 1]
+    unsigned long long *smp_ws;  // the filters' sampler workspaces, [2 rows - 1] rows, then ...
+    unsigned long long *smp_res;  // ... the residual draw's one row (laid out in front of them)
+    size_t smp_row_words;
+    DistPart *parts, *norms;
+    int tiles;
+    int *flags;                  // [tiles]: the drawn residual row has a finite entry in the tile
+    float *resrow;               // [V]: the residual row the last token is drawn from
+    float *accept_rec, *residual;  // nullable diagnostics
+    SpecDraftMeta *meta;
+    const int *tok;              // [rows]: the rows' ordinary draws
+    int *comp;                   // [rows]: the accepted drafts, then the last token
+    int *out_tokens, *out_n;
+    SpecState s;
+};
+
+__device__ __forceinline__ const float *dist_row_lp(const SpecDraftArgs &a, int r) {
+    return r < a.rows ? a.logprobs + (size_t)r * a.V : a.q_logprobs + (size_t)(r - a.rows) * a.V;
+}
+
+// Both filters' records and the workspaces' re-armed headers, as k_spec_fill_rows: P row r draws at c + r -- its token is the row's
+// ordinary draw --, a Q row is only filtered (its draw is discarded: any stream position does).
+__global__ void __launch_bounds__(2 * SPEC_MAX_ROWS) k_spec_draft_fill(const SpecDraftArgs a) {
+    const int r = threadIdx.x;
+    const unsigned long long c = a.counter[0];
+    if (r == 0) {
+        a.meta->base = c;
+        a.smp_res[SMP_WS_MAXKEY_WORD] = 0ull, a.smp_res[SMP_WS_XTC_WORD] = 0ull;
+    }
+    if (r >= 2 * a.rows - 1) return;
+    pie_row_tail t = {};
+    t.mode = a.mode, t.inv_temp = a.inv_temp, t.thr = a.thr, t.k = a.k, t.seed = a.seed, t.calls = c + (unsigned long long)(r < a.rows ? r : 0);
+    t.penalty = 1.0f, t.context_size = 1;
+    a.table[r] = t;
+    unsigned long long *hdr = a.smp_ws + (size_t)r * a.smp_row_words;
+    hdr[SMP_WS_MAXKEY_WORD] = 0ull, hdr[SMP_WS_XTC_WORD] = 0ull;
+}
+
+// A block's sum and maximum in a fixed order: the butterfly inside a wave, then the four waves in turn.  Every thread gets the result.
+__device__ __forceinline__ double dist_block_sum(double v, double *s_w) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+__device__ __forceinline__ double dist_block_max(double v, double *s_w) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(s_w[0], s_w[1]), fmax(s_w[2], s_w[3]));
+}
+
+// Launch 1 of dist, over (tiles, 2 rows - 1): a tile's share of its row's normaliser.  The arithmetic is fp64 -- 2 x 63 x V exponentials
+// are nothing beside the pass -- so that the residual's difference of two normalised rows keeps its digits where P and Q are close.
+__global__ void __launch_bounds__(DIST_T) k_spec_dist_stats(const SpecDraftArgs a) {
+    __shared__ double s_w[DIST_T / 64];
+    const int r = blockIdx.y, base = blockIdx.x * DIST_SLICE + 2 * threadIdx.x;
+    const float *lp = dist_row_lp(a, r);
+    const unsigned char *mask = a.mask + (size_t)r * a.V;
+    double x[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) x[j] = base + j < a.V && mask[base + j] ? (double)lp[base + j] : -INFINITY;
+    const double m = dist_block_max(fmax(x[0], x[1]), s_w);
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (x[j] != -INFINITY) s += exp((x[j] - m) * (double)a.inv_temp);
+    s = dist_block_sum(s, s_w);
+    if (threadIdx.x == 0) a.parts[(size_t)r * a.tiles + blockIdx.x] = DistPart{m, s};
+}
+
+// Launch 2 of dist, one workgroup per row: the tiles' shares in a fixed order (thread t takes tiles t, t + 256, ...; then the block's tree).
+__global__ void __launch_bounds__(DIST_T) k_spec_dist_merge(const SpecDraftArgs a) {
+    __shared__ double s_w[DIST_T / 64];
+    const DistPart *p = a.parts + (size_t)blockIdx.x * a.tiles;
+    double m = -INFINITY;
+    for (int t = threadIdx.x; t < a.tiles; t += DIST_T) m = fmax(m, p[t].m);
+    m = dist_block_max(m, s_w);
+    double s = 0.0;
+    for (int t = threadIdx.x; t < a.tiles; t += DIST_T)
+        if (p[t].s > 0.0) s += p[t].s * exp((p[t].m - m) * (double)a.inv_temp);
+    s = dist_block_sum(s, s_w);
+    if (threadIdx.x == 0) a.norms[blockIdx.x] = DistPart{m, s};
+}
+
+// dist(x) of row r (0 <= x < V): 0 outside the kept set, and everywhere when the filter kept nothing
+__device__ __forceinline__ double dist_at(const SpecDraftArgs &a, int r, int x) {
+    const DistPart n = a.norms[r];
+    if (!(n.s > 0.0) || !a.mask[(size_t)r * a.V + x]) return 0.0;
+    return exp(((double)dist_row_lp(a, r)[x] - n.m) * (double)a.inv_temp) / n.s;
+}
+
+// u_i: XTC's coin construction (sampler.hip: k_smp_xtc) on the index word no coin and no vocabulary index uses.  The Philox block is
+// restated here because sampler.hip keeps its own file-local.
+__device__ __forceinline__ float spec_accept_u(unsigned long long seed, unsigned long long call) {
+    unsigned c[4] = {SPEC_U_IDX4, 0u, (unsigned)call, (unsigned)(call >> 32)};
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
+        c[0] = n0, c[1] = n1, c[2] = n2, c[3] = n3;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return ((float)(c[0] >> 8) + 0.5f) * 0x1p-24f;
+}
+
+// Launch 3, over (tiles, 1) -- (tiles, rows - 1) with the residual diagnostic: every workgroup decides the drafts (thread i draft i, at
+// most 31 in parallel: two dist values and one Philox block each), takes n_acc as the first refusal, and writes its tile of the residual
+// row R_j, j = n_acc (and of every R_i into the diagnostic).  All drafts accepted: nothing is drawn from, nothing is written.
+__global__ void __launch_bounds__(DIST_T) k_spec_draft_residual(const SpecDraftArgs a) {
+    __shared__ int s_ok[SPEC_MAX_ROWS];
+    __shared__ int s_acc;
+    const int t = threadIdx.x, m = a.rows - 1;
+    const unsigned long long c = a.meta->base;
+    if (t < m) {
+        const int d = a.draft[t];
+        const bool in = d >= 0 && d < a.V;  // an id outside the vocabulary indexes nothing
+        const float p = in ? (float)dist_at(a, t, d) : 0.0f, q = in ? (float)dist_at(a, a.rows + t, d) : 0.0f;
+        const float u = spec_accept_u(a.seed, c + (unsigned long long)t);
+        s_ok[t] = in && q > 0.0f && __fmul_rn(u, q) < p;
+        if (a.accept_rec && blockIdx.x == 0 && blockIdx.y == 0) a.accept_rec[3 * t] = p, a.accept_rec[3 * t + 1] = q, a.accept_rec[3 * t + 2] = u;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int n = 0;
+        while (n < m && s_ok[n]) ++n;
+        s_acc = n;
+        if (blockIdx.x == 0 && blockIdx.y == 0) a.meta->n_acc = n, a.meta->rcounter[0] = c + (unsigned long long)n, a.meta->rcounter[1] = 0ull;
+    }
+    __syncthreads();
+    const int j = s_acc, r = a.residual ? (int)blockIdx.y : j;
+    if (r >= m) return;  // block-uniform
+    const int base = blockIdx.x * DIST_SLICE + 2 * t;
+    bool finite = false;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int x = base + e;
+        if (x >= a.V) continue;
+        const double diff = dist_at(a, r, x) - dist_at(a, a.rows + r, x);
+        const float v = diff > 0.0 ? (float)log(diff) : -INFINITY;
+        finite = finite || diff > 0.0;
+        if (a.residual) a.residual[(size_t)r * a.V + x] = v;
+        if (r == j) a.resrow[x] = v;
+    }
+    const int any = __syncthreads_or(finite ? 1 : 0);
+    if (r == j && t == 0) a.flags[blockIdx.x] = any;
+}
+
+// The last launch, one workgroup: whether the drawn residual row had a finite entry (an OR over the tiles' flags), then one thread composes
+// the tokens and commits through the function both other verifies end in.
+__global__ void __launch_bounds__(DIST_T) k_spec_draft_commit(const SpecDraftArgs a) {
+    int any = 0;
+    for (int t = threadIdx.x; t < a.tiles; t += DIST_T) any |= a.flags[t];
+    any = __syncthreads_or(any);
+    if (threadIdx.x != 0) return;
+    const int n_acc = a.meta->n_acc;
+    for (int i = 0; i < n_acc; ++i) a.comp[i] = a.draft[i];
+    // the bonus token behind a fully accepted block, the residual's draw behind a refusal, the row's ordinary draw when the residual is empty
+    a.comp[n_acc] = n_acc < a.rows - 1 && any ? a.meta->res_tok : a.tok[n_acc];
+    spec_commit(a.s, a.comp, a.rows, n_acc, a.out_tokens, a.out_n);
+    a.counter[0] = a.meta->base + (unsigned long long)(n_acc + 1), a.counter[1] = 0ull;
+}
+
+}  // namespace
+
+// pie_spec_verify_draft's launches behind whatever made the logits (arguments already checked)
+static int spec_verify_draft_launch(u16 *logits, int rows, int V, int dtype, const int *draft, const float *q_logprobs, int mode, double temp, double p, int k,
+                                    unsigned long long seed, unsigned long long *counter, int *out_tokens, int *out_n, float *logprobs, float *accept_rec,
+                                    float *residual, void *workspace, const SpecState &s, hipStream_t st) {
+    const SpecDraftLayout lay(rows, V);
+    char *ws = (char *)workspace;
+    const int dist_rows = 2 * rows - 1;
+    SpecDraftArgs a = {};
+    a.rows = rows, a.V = V, a.mode = mode, a.seed = seed, a.counter = counter, a.draft = draft, a.logprobs = logprobs, a.q_logprobs = q_logprobs;
+    sample_derive(mode, temp, p, k, &a.inv_temp, &a.thr, &a.k);
+    unsigned char *mask = (unsigned char *)(ws + lay.mask);
+    int *tok = (int *)(ws + lay.tok), *qtok = (int *)(ws + lay.qtok);
+    a.mask = mask, a.table = (pie_row_tail *)(ws + lay.table), a.smp_ws = (unsigned long long *)(ws + lay.smp), a.smp_res = (unsigned long long *)(ws + lay.smp_res);
+    a.smp_row_words = pie_sample_workspace_bytes(1, V) / sizeof(unsigned long long);
+    a.parts = (DistPart *)(ws + lay.parts), a.norms = (DistPart *)(ws + lay.norms), a.tiles = lay.tiles, a.flags = (int *)(ws + lay.flags);
+    a.resrow = (float *)(ws + lay.resrow), a.accept_rec = accept_rec, a.residual = residual, a.meta = (SpecDraftMeta *)(ws + lay.meta);
+    a.tok = tok, a.comp = (int *)(ws + lay.comp), a.out_tokens = out_tokens, a.out_n = out_n, a.s = s;
+    if (int rc = logits_tail_rows_launch(dtype, logits, V, rows, (LogitStat *)ws, logprobs, tok, st)) return rc;
+    hipLaunchKernelGGL(k_spec_draft_fill, dim3(1), dim3(2 * SPEC_MAX_ROWS), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    // the kept sets are the sampler's own: its filter launches with a mask output, over the target's rows (whose draws are the rows' ordinary
+    // tokens) and over the drafter's (whose draws are discarded)
+    if (int rc = sample_rows_launch(logprobs, rows, V, a.table, a.smp_ws, tok, nullptr, mask, st)) return rc;
+    if (int rc = sample_rows_launch(q_logprobs, rows - 1, V, a.table + rows, a.smp_ws + (size_t)rows * a.smp_row_words, qtok, nullptr, mask + (size_t)rows * V, st)) return rc;
+    hipLaunchKernelGGL(k_spec_dist_stats, dim3((unsigned)lay.tiles, (unsigned)dist_rows), dim3(DIST_T), 0, st, a);
+    hipLaunchKernelGGL(k_spec_dist_merge, dim3((unsigned)dist_rows), dim3(DIST_T), 0, st, a);
+    hipLaunchKernelGGL(k_spec_draft_residual, dim3((unsigned)lay.tiles, residual ? (unsigned)(rows - 1) : 1u), dim3(DIST_T), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    // the residual's draw IS pie_sample(CATEGORICAL, temp = 1) on that row at {c + n_acc, 0}; behind a fully accepted block it draws from
+    // whatever the row holds and nobody reads the token
+    SampleFeed none = {};
+    if (int rc = sample_launch(a.resrow, 1, V, PIE_SAMPLE_CATEGORICAL, 1.0, 0.0, 0, seed, a.meta->rcounter, a.smp_res, &a.meta->res_tok, nullptr, nullptr, none, st)) return rc;
+    hipLaunchKernelGGL(k_spec_draft_commit, dim3(1), dim3(DIST_T), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
 extern "C" {
 
 size_t pie_ngram_draft_workspace_bytes(void) { return sizeof(unsigned) * NGRAM_MAX_WGS; }
@@ -372,6 +642,28 @@ int pie_spec_verify_sampled(const void *logits, int rows, int V, int dtype, cons
                                       workspace, SpecState(), (hipStream_t)stream);
 }
 
+size_t pie_spec_verify_draft_workspace_bytes(int rows, int V) {
+    if (rows < 2 || rows > SPEC_MAX_ROWS || pie_sample_workspace_bytes(rows, V) == 0) return 0;
+    return SpecDraftLayout(rows, V).bytes;
+}
+
+int pie_spec_verify_draft(const void *logits, int rows, int V, int dtype, const int32_t *draft, const float *q_logprobs, int mode, double temp, double p, int k,
+                          unsigned long long seed, unsigned long long *counter, int32_t *out_tokens, int32_t *out_n, float *logprobs, float *accept_rec, float *residual,
+                          void *workspace, void *stream) {
+    PIE_REQUIRE(logits && draft && q_logprobs && counter && out_tokens && out_n && logprobs && workspace, PIE_E_ARG, "pie_spec_verify_draft: null pointer");
+    PIE_REQUIRE(mode != PIE_SAMPLE_GREEDY, PIE_E_ARG, "pie_spec_verify_draft: a greedy draft is a point mass (use pie_spec_verify)");
+    PIE_REQUIRE(rows >= 2 && rows <= SPEC_MAX_ROWS && V >= 1, PIE_E_SHAPE, "pie_spec_verify_draft: need 2 <= rows <= 32 and V >= 1");
+    PIE_REQUIRE(pie_aligned(logits, 2) && pie_aligned(draft, 4) && pie_aligned(q_logprobs, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(logprobs, 4) &&
+                    pie_aligned(accept_rec, 4) && pie_aligned(residual, 4),
+                PIE_E_ALIGN, "pie_spec_verify_draft: logits need 2-byte, the draft, its log-probabilities and the outputs 4-byte alignment");
+    PIE_REQUIRE(pie_aligned(counter, 8), PIE_E_ALIGN, "pie_spec_verify_draft: the counter needs 8-byte alignment");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_spec_verify_draft: workspace needs 16-byte alignment");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_spec_verify_draft: dtype must be PIE_BF16 or PIE_F16");
+    if (int rc = sample_check("pie_spec_verify_draft", V, mode, temp, p, k, workspace)) return rc;
+    return spec_verify_draft_launch((u16 *)const_cast<void *>(logits), rows, V, dtype, draft, q_logprobs, mode, temp, p, k, seed, counter, out_tokens, out_n, logprobs,
+                                    accept_rec, residual, workspace, SpecState(), (hipStream_t)stream);
+}
+
 // workspace: the logits block [rows, vocab] T | the pass's input ids [32] | pie_spec_verify's workspace
 size_t pie_decoder_spec_workspace_bytes(const pie_decoder *d, int rows) {
     if (!d || rows < 2 || rows > SPEC_MAX_ROWS) return 0;
@@ -384,16 +676,25 @@ size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows) {
     return align16((size_t)rows * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_MAX_ROWS) + SpecSampledLayout(rows, d->cfg.vocab).bytes;
 }
 
+// workspace: the logits block [rows, vocab] T | the pass's input ids [32] | pie_spec_verify_draft's workspace
+size_t pie_decoder_spec_draft_workspace_bytes(const pie_decoder *d, int rows) {
+    if (!d || rows < 2 || rows > SPEC_MAX_ROWS || pie_sample_workspace_bytes(rows, d->cfg.vocab) == 0) return 0;
+    return align16((size_t)rows * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_MAX_ROWS) + SpecDraftLayout(rows, d->cfg.vocab).bytes;
+}
+
 }  // extern "C"
 
 namespace {
 
-// What the two pie_decoder_spec_step* entries share: the entry's refusals -- with_tail: which parts of the step's tail the pass admits is
+enum SpecKind { SPEC_RAW = 0, SPEC_TAIL = 1, SPEC_DRAFT = 2 };  // pie_decoder_spec_step, _spec_step_tail, _spec_step_draft
+
+// What the three pie_decoder_spec_step* entries share: the entry's refusals -- with_tail: which parts of the step's tail the pass admits is
 // StepTail's answer (decoder.hpp) --, the shape and alignment checks, the workspace's carve-up (the logits block at its head, then s->fed,
 // then *verify_ws), the gather of the input rows, the SpecState fill and the many-row pass itself, raw logits on every row.
-int spec_prologue(const char *entry, bool with_tail, pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows,
+int spec_prologue(const char *entry, SpecKind kind, pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows,
                   void *workspace, int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream, SpecState *s, void **verify_ws) {
     const std::string who = std::string(entry) + ": ";
+    const bool with_tail = kind != SPEC_RAW;
     PIE_REQUIRE(d && draft_ids && out_tokens && out_n && (logprobs_rows || !with_tail) && workspace, PIE_E_ARG, who + "null pointer");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
     PIE_REQUIRE(!d->kv_quant && !d->ring, PIE_E_STATE, who + "not available on a quantized or rotating KV cache");
@@ -407,6 +708,10 @@ int spec_prologue(const char *entry, bool with_tail, pie_decoder *d, const int32
         const char *part = t.spec_tail_refused();
         PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
         PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
+        // XTC's coin changes the target's distribution from call to call: the acceptance test would need the coin of every row's own call
+        PIE_REQUIRE(kind != SPEC_DRAFT || !t.xtc.on(), PIE_E_STATE, who + "not available with an XTC record");
+        PIE_REQUIRE(kind != SPEC_DRAFT || t.sampler.on(), PIE_E_STATE,
+                    who + "no stochastic sampler is set (a greedy draft is a point mass: pie_decoder_spec_step or pie_decoder_spec_step_tail)");
         PIE_REQUIRE(t.spec_tail_admitted(), PIE_E_STATE,
                     who + "no sampler, XTC record, repetition penalty or logit bias is set (the greedy and raw pass is pie_decoder_spec_step)");
     }
@@ -430,6 +735,20 @@ int spec_prologue(const char *entry, bool with_tail, pie_decoder *d, const int32
     return pie_decoder_prefill(d, fed, rows, workspace, stream);
 }
 
+// The rows' edits behind the pass, in the step tail's order: penalty, then bias (one launch, none when neither is set); with a penalty the
+// accept launch keeps ids_by_pos whole.
+int spec_edit_launch(pie_decoder *d, const int32_t *draft_ids, int rows, void *workspace, SpecState *s, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    const StepTail &t = d->tail;
+    if (t.penalty.on()) s->ids_by_pos = t.penalty.ids_by_pos, s->ids_cap = t.penalty.ids_cap;
+    if (!t.penalty.on() && !t.bias.on()) return PIE_OK;
+    SpecEditArgs e = {};
+    e.logits = (u16 *)workspace, e.V = c.vocab, e.rows = rows, e.penalty = (float)t.penalty.value, e.context = t.penalty.context, e.ids_by_pos = t.penalty.ids_by_pos, e.ids_cap = t.penalty.ids_cap;
+    e.state = d->state, e.fed = s->fed, e.draft = draft_ids;
+    e.b = BiasArgs{t.bias.ids, t.bias.vals, t.bias.n, t.penalty.on()};
+    return launch_for_dtype(c.dtype, "spec edit:", [&](auto ty) { hipLaunchKernelGGL(k_spec_edit_rows<decltype(ty)>, dim3((unsigned)rows), dim3(PEN_MAX_IDS), 0, st, e); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -438,7 +757,7 @@ int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft,
                           int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
     SpecState s;
     void *verify_ws;
-    if (int rc = spec_prologue("pie_decoder_spec_step", false, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
+    if (int rc = spec_prologue("pie_decoder_spec_step", SPEC_RAW, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
     return spec_verify_launch((const u16 *)workspace, n_draft + 1, d->cfg.vocab, d->cfg.dtype, draft_ids, out_tokens, out_n, logprobs_rows, verify_ws, s, (hipStream_t)stream);
 }
 
@@ -446,23 +765,24 @@ int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_d
                                int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
     SpecState s;
     void *verify_ws;
-    if (int rc = spec_prologue("pie_decoder_spec_step_tail", true, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const pie_decoder_config &c = d->cfg;
-    const StepTail &t = d->tail;
-    const int rows = n_draft + 1;
-    if (t.penalty.on() || t.bias.on()) {  // the rows' edits, in the step tail's order: penalty, then bias
-        SpecEditArgs e = {};
-        e.logits = (u16 *)workspace, e.V = c.vocab, e.rows = rows, e.penalty = (float)t.penalty.value, e.context = t.penalty.context, e.ids_by_pos = t.penalty.ids_by_pos, e.ids_cap = t.penalty.ids_cap;
-        e.state = d->state, e.fed = s.fed, e.draft = draft_ids;
-        e.b = BiasArgs{t.bias.ids, t.bias.vals, t.bias.n, t.penalty.on()};
-        if (int rc = launch_for_dtype(c.dtype, "spec edit:", [&](auto ty) { hipLaunchKernelGGL(k_spec_edit_rows<decltype(ty)>, dim3((unsigned)rows), dim3(PEN_MAX_IDS), 0, st, e); }))
-            return rc;
-    }
-    if (t.penalty.on()) s.ids_by_pos = t.penalty.ids_by_pos, s.ids_cap = t.penalty.ids_cap;
-    const StepTail::Sampler &m = t.sampler;
-    return spec_verify_sampled_launch((u16 *)workspace, rows, c.vocab, c.dtype, draft_ids, m.mode, m.temp, m.p, m.k, m.seed, m.counter, m.on() ? t.xtc.record : nullptr, out_tokens, out_n,
-                                      logprobs_rows, verify_ws, s, st);
+    if (int rc = spec_prologue("pie_decoder_spec_step_tail", SPEC_TAIL, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
+    if (int rc = spec_edit_launch(d, draft_ids, n_draft + 1, workspace, &s, (hipStream_t)stream)) return rc;
+    const StepTail::Sampler &m = d->tail.sampler;
+    return spec_verify_sampled_launch((u16 *)workspace, n_draft + 1, d->cfg.vocab, d->cfg.dtype, draft_ids, m.mode, m.temp, m.p, m.k, m.seed, m.counter,
+                                      m.on() ? d->tail.xtc.record : nullptr, out_tokens, out_n, logprobs_rows, verify_ws, s, (hipStream_t)stream);
+}
+
+int pie_decoder_spec_step_draft(pie_decoder *d, const int32_t *draft_ids, int n_draft, const float *q_logprobs, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows,
+                                void *workspace, int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
+    PIE_REQUIRE(q_logprobs, PIE_E_ARG, "pie_decoder_spec_step_draft: null pointer");
+    PIE_REQUIRE(pie_aligned(q_logprobs, 4), PIE_E_ALIGN, "pie_decoder_spec_step_draft: 4-byte alignment required");
+    SpecState s;
+    void *verify_ws;
+    if (int rc = spec_prologue("pie_decoder_spec_step_draft", SPEC_DRAFT, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
+    if (int rc = spec_edit_launch(d, draft_ids, n_draft + 1, workspace, &s, (hipStream_t)stream)) return rc;
+    const StepTail::Sampler &m = d->tail.sampler;
+    return spec_verify_draft_launch((u16 *)workspace, n_draft + 1, d->cfg.vocab, d->cfg.dtype, draft_ids, q_logprobs, m.mode, m.temp, m.p, m.k, m.seed, m.counter, out_tokens, out_n,
+                                    logprobs_rows, nullptr, nullptr, verify_ws, s, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ constexpr int SPEC_MAX_IDS = 1 << 27;  // the drafter's search key packs (match 
 // position o would have left it: pos = o + n, token = the last accepted token, history[o + 1 + i] = accepted token i.  seq_ids (nullable,
 // [seq_cap]) = the sequence's ids by position, made whole here: seq_ids[o] = fed[0] (the fed-back token of row 0) and seq_ids[o + 1 + i] =
 // accepted token i; seq_len (nullable) = o + n + 1, the drafter's `len` for the next draft.  token_out (nullable): the bound token output.
-// ids_by_pos (nullable, [ids_cap]; pie_decoder_spec_step_tail): the repetition penalty's ids by position, ids_by_pos[o + 1 + i] = accepted
+// ids_by_pos (nullable, [ids_cap]; pie_decoder_spec_step_tail and pie_decoder_spec_step_draft): the repetition penalty's ids by position, ids_by_pos[o + 1 + i] = accepted
 // token i, so that the plain step that follows finds its window whole.
 struct SpecState {
     DecState *state = nullptr;

@@ -126,17 +126,33 @@ class SpeculativeParams:
     equals the draw -- exact for prompt-lookup drafts, which are point masses: token j of the generation is draw j of the seed from row
     j's own distribution.  (A pass's rows come from the many-row GEMMs and a step's from the GEMVs, so their logits may differ in the last
     bit, as in the greedy case: the plain loop draws the same tokens wherever no draw falls within that rounding of a boundary.)  A greedy
-    request without processors takes the greedy path either way."""
+    request without processors takes the greedy path either way.
+    draft_model: None -- prompt-lookup drafts, as above.  A built `Model` of the target's vocabulary, or a checkpoint
+    path (loaded once and kept on the engine) -- every round the draft model runs num_draft of its own replayed steps (num_draft =
+    the target's spec_min_rows - 1 .. 31, so that the pass keeps its many-row form) and the target verifies them in one pass.  A greedy
+    request accepts while the draft equals the target's greedy token: the tokens are the plain greedy loop's.  A sampled request (any
+    temperature, top-p / top-k / min-p; repetition penalty and logit bias on the target) runs speculative sampling: the drafter draws
+    under the request's (mode, temp, p, k) and a seed of its own, draft i is accepted with probability min(1, P_i / Q_i), and the token
+    behind the accepted prefix comes from the residual max(0, P - Q) -- every token is distributed as the plain loop's, though it is no
+    longer draw j of the seed.  min_draft, ngram_max, ngram_min and configured_tail are ignored with a draft model: every round drafts
+    num_draft ids, and the request's sampler decides the path."""
     num_draft: int = 7
     ngram_max: int = 3
     ngram_min: int = 1
     min_draft: int = 5
     configured_tail: bool = False
+    draft_model: object = None
 
     def __post_init__(self):
         if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= hip_ops.SPEC_MAX_NGRAM:
             raise ValueError(f"SpeculativeParams: 1 <= ngram_min <= ngram_max <= {hip_ops.SPEC_MAX_NGRAM}")
-        if not 1 <= int(self.min_draft) <= int(self.num_draft) <= hip_ops.SPEC_MAX_ROWS - 1:
+        if self.draft_model is not None:
+            import os
+            if not isinstance(self.draft_model, (str, os.PathLike)) and not all(hasattr(self.draft_model, a) for a in ("step", "set_step_tail", "history", "logprobs")):
+                raise ValueError("SpeculativeParams: draft_model is None, a built Model or a checkpoint path")
+            if not 1 <= int(self.num_draft) <= hip_ops.SPEC_MAX_ROWS - 1:
+                raise ValueError(f"SpeculativeParams: 1 <= num_draft <= {hip_ops.SPEC_MAX_ROWS - 1} with a draft model")
+        elif not 1 <= int(self.min_draft) <= int(self.num_draft) <= hip_ops.SPEC_MAX_ROWS - 1:
             raise ValueError(f"SpeculativeParams: 1 <= min_draft <= num_draft <= {hip_ops.SPEC_MAX_ROWS - 1}")
         if not isinstance(self.configured_tail, bool):
             raise ValueError("SpeculativeParams: configured_tail is a bool")
@@ -179,6 +195,39 @@ def check_speculative_tail(model, sampler, processors, structuring_engine, pixel
     return plan
 
 
+def check_speculative_draft(model, draft_model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs=None):
+    """What generate_step(speculative=SpeculativeParams(draft_model=...)) refuses, each by name, and the fused tail plan of
+    what it accepts -- None for a greedy request without processors, whose passes are Model.spec_step's.  Besides what
+    check_speculative_tail refuses: XTC (its coin changes the target's distribution from call to call), a draft model of another
+    vocabulary, a tensor-parallel draft model."""
+    tp = getattr(model, "tp", None) is not None
+    for bad, name in ((structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
+                      (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"), (prompt_logprobs is not None, "prompt_logprobs"),
+                      (tp, "a tensor-parallel model"), (getattr(draft_model, "tp", None) is not None, "a tensor-parallel draft model"),
+                      (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")):
+        if bad:
+            raise ValueError(f"speculative decoding with a draft model is not available with {name}")
+    if not hasattr(model, "spec_step_draft") or not hasattr(model, "set_step_tail"):
+        raise ValueError("speculative decoding with a draft model is not available with this model (no spec_step_draft)")
+    if not all(hasattr(draft_model, a) for a in ("step", "set_step_tail", "history", "logprobs")):
+        raise ValueError("speculative decoding with a draft model is not available with this draft model (no step / set_step_tail)")
+    if draft_model is model:
+        raise ValueError("speculative decoding with a draft model: the draft model is the target itself (build a second Model; the two keep separate caches and streams)")
+    v_t, v_d = int(model.logprobs.numel()), int(draft_model.logprobs.numel())
+    if v_t != v_d:
+        raise ValueError(f"speculative decoding with a draft model: a vocabulary mismatch (the target has {v_t} ids, the draft model {v_d})")
+    if getattr(sampler, "is_greedy", False) and not processors:
+        return None
+    plan = fused_tail_plan(processors, sampler, structuring_engine, tp)
+    if plan is None:
+        raise ValueError("speculative decoding with a draft model is not available with a sampler or logits processors outside the fused tail plan "
+                         "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
+    for key, name in (("xtc", "XTC"), ("mask", "a token mask"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
+        if plan.get(key) is not None:
+            raise ValueError(f"speculative decoding with a draft model is not available with {name}")
+    return plan
+
+
 class InferenceEngine:
     """One model, one PromptCache, not re-entrant -- like the reference (server/app.py:23,35)."""
 
@@ -198,6 +247,18 @@ class InferenceEngine:
         self.structuring_engine = structuring_engine  # optional PSE-like object (inference_engine.py:37-41)
         self.samplers: dict[str, Sampler] = {}
         self.logits_processors: dict[str, list[LogitsProcessor]] = {}
+        self._draft_models: dict = {}   # SpeculativeParams(draft_model=path): the checkpoints loaded so far, by path
+        self._draft_cache = None        # the draft model's KV caches of the running request
+
+    def _draft_model(self, sp):
+        """SpeculativeParams.draft_model as a built Model: a checkpoint path is loaded once and kept."""
+        dm = sp.draft_model
+        if hasattr(dm, "step"):
+            return dm
+        key = str(dm)
+        if key not in self._draft_models:
+            self._draft_models[key] = load(key).model
+        return self._draft_models[key]
 
     # ------------------------------------------------------------------ samplers / processors
     def make_sampler(self, **kwargs) -> Sampler:
@@ -306,7 +367,10 @@ class InferenceEngine:
         if "root" not in self.samplers:
             self.prepare_engine(prompt_ids, temp=0)
         spec_plan = None
-        if speculative is not None:
+        if speculative is not None and speculative.draft_model is not None:
+            spec_plan = check_speculative_draft(self.model, self._draft_model(speculative), self.samplers["root"], self.logits_processors.get("root") or [],
+                                                self.structuring_engine, pixel_values, kv_bits, max_kv_size)
+        elif speculative is not None:
             all_procs = [p for ps in self.logits_processors.values() for p in ps]
             if speculative.configured_tail and not (getattr(self.samplers["root"], "is_greedy", False) and not all_procs):
                 spec_plan = check_speculative_tail(self.model, self.samplers["root"], self.logits_processors.get("root") or [], self.structuring_engine,
@@ -439,6 +503,9 @@ class InferenceEngine:
                     proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts may not: this request's start
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
+        if speculative is not None and speculative.draft_model is not None:
+            yield from self._speculative_draft_steps([int(t) for t in prompt_ids], host_ids, speculative, top_logprobs, spec_plan)
+            return
         if speculative is not None:
             yield from self._speculative_steps(host_ids, speculative, top_logprobs, spec_plan)
             return
@@ -463,6 +530,17 @@ class InferenceEngine:
                 next_token, logprobs = _inference(next_token, fed_back=True)   # :288
             yield next_token, logprobs
             step_count += 1
+
+    def _record_top(self, host_top: list, top_logprobs: int | None, tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
+        """The top-n records of a speculative yield: one hip_ops.top_logprobs call over the yielded rows, record r = token r's.  host_top
+        keeps the generation's workspace."""
+        if top_logprobs is None:
+            return
+        n, m = max(int(top_logprobs), 1), rows.shape[0]
+        if not host_top:
+            host_top.append(hip_ops.top_logprobs_workspace(rows.device, hip_ops.SPEC_MAX_ROWS, rows.shape[1], n))
+        ids, vals = hip_ops.top_logprobs(rows, n, tokens=tokens_dev[:m].contiguous(), workspace=host_top[0])
+        self.top_record = (ids[:, :int(top_logprobs) + 1], vals[:, :int(top_logprobs) + 1])
 
     def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None, plan: dict | None = None):
         """generate_step's loop under speculative decoding.  The prompt's suffix is one plain step; behind it, and behind every
@@ -495,14 +573,7 @@ class InferenceEngine:
         host_top: list = []
 
         def record(tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
-            """One hip_ops.top_logprobs call over the yielded rows: record r = token r's."""
-            if top_logprobs is None:
-                return
-            n, m = max(int(top_logprobs), 1), rows.shape[0]
-            if not host_top:
-                host_top.append(hip_ops.top_logprobs_workspace(rows.device, hip_ops.SPEC_MAX_ROWS, rows.shape[1], n))
-            ids, vals = hip_ops.top_logprobs(rows, n, tokens=tokens_dev[:m].contiguous(), workspace=host_top[0])
-            self.top_record = (ids[:, :int(top_logprobs) + 1], vals[:, :int(top_logprobs) + 1])
+            self._record_top(host_top, top_logprobs, tokens_dev, rows)
 
         ids = torch.tensor(host_ids, dtype=torch.int32)
         _, logprobs, _ = model.step(ids, cache)
@@ -527,6 +598,87 @@ class InferenceEngine:
                 model.draft(*drafter)
                 rows = logprobs[None]
                 self.spec_stats["steps"] += 1
+
+    def _speculative_draft_steps(self, prompt_ids: list[int], host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None, plan: dict | None):
+        """generate_step's loop with a draft model.  The draft model gets ReusableKVCaches of its own and the WHOLE prompt (no
+        prefix reuse for it); the target's prompt suffix is one plain step.  A round: the drafter is fed the current token and replays
+        num_draft of its configured steps back to back, no host synchronisation in between -- its drafts are its own device-side history,
+        and behind every step its bound log-probabilities are copied, device to device in stream order, into a row of one [31, V] block;
+        one target pass (Model.spec_step_draft under a stochastic sampler, spec_step / spec_step_tail for a greedy request); the one
+        record read-back; the drafter's caches trimmed to the accepted offset -- the rows behind it are overwritten before anything
+        attends to them -- or, when every draft was accepted, the drafter fed the last draft, whose K / V rows it never produced.
+        The drafter draws under the request's (mode, temp, p, k) and samplers._rng.draft_state's seed, never under the target's."""
+        from ..samplers import _rng
+        model, cache, d = self.model, self.prompt_cache.cache, self._draft_model(sp)
+        k, min_rows = int(sp.num_draft), int(model.spec_min_rows)
+        if not min_rows - 1 <= k <= hip_ops.SPEC_MAX_ROWS - 1:
+            raise ValueError(f"speculative decoding with a draft model: num_draft is {min_rows - 1}..{hip_ops.SPEC_MAX_ROWS - 1} (the pass keeps at least {min_rows} rows), got {k}")
+        limit = min(model.fed_ids.numel(), d.fed_ids.numel(), d.history.numel())
+        if len(prompt_ids) > limit:
+            raise ValueError("speculative decoding: the prompt runs past the model's id history")
+        sampler = None if plan is None else plan["sampler"]
+        if plan is not None:
+            offset = int(cache[0].offset) if cache else 0
+            if plan["repetition_penalty"] != 1.0 and offset > 0:  # a reused prefix: its ids may predate this configuration (as in _forward)
+                seen = self.prompt_cache.computed_ids[-min(offset, plan["context_size"]):]
+                model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
+            bias = plan["bias"]
+            model.set_step_tail(sampler=sampler, repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
+                                logit_bias=None if bias is None else (bias.ids, bias.values))
+        else:
+            model.set_step_tail()
+        draft_seed = None
+        if sampler is not None:  # one sampler setting for both sides, two streams
+            draft_seed, draft_counter = _rng.draft_state(d.device)
+            d.set_step_tail(sampler=sampler, rng=(draft_seed, draft_counter))
+            q_rows = torch.empty((hip_ops.SPEC_MAX_ROWS - 1, d.logprobs.numel()), dtype=torch.float32, device=d.device)
+        else:
+            d.set_step_tail()
+        self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}
+        host_top: list = []
+
+        def record(tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
+            self._record_top(host_top, top_logprobs, tokens_dev, rows)
+
+        self._draft_cache = dcache = [ReusableKVCache() for _ in d.layers]
+        d.step(torch.tensor(prompt_ids, dtype=torch.int32), dcache)  # (its own choice behind the prompt is not used: the target's is fed)
+        ids = torch.tensor(host_ids, dtype=torch.int32)
+        tok, logprobs, _ = model.step(ids, cache)
+        self.prompt_cache.update(ids)
+        rows = logprobs[None]
+        record(tok, rows)
+        tokens = [int(tok)]
+        while True:
+            yield torch.tensor(tokens, dtype=torch.int32), rows
+            fed, o = tokens[-1], int(cache[0].offset)
+            if o != int(dcache[0].offset):
+                raise RuntimeError("speculative decoding: the draft model's cache left the target's offset")
+            if o + k + 1 > limit:
+                raise ValueError("speculative decoding: the round would run past the model's id history")
+            d.step(torch.tensor([fed], dtype=torch.int32), dcache)
+            for i in range(k):
+                if i:
+                    d.step(None, dcache)
+                if sampler is not None:
+                    q_rows[i].copy_(d.logprobs)
+            draft = d.history[o + 1:o + 1 + k]
+            if sampler is not None:
+                _, n, rows = model.spec_step_draft(draft, q_rows, cache, draft_seed=draft_seed)
+            elif plan is not None:
+                _, n, rows = model.spec_step_tail(draft, cache)
+            else:
+                _, n, rows = model.spec_step(draft, cache)
+            tokens = model.spec_read()[0]
+            self.prompt_cache.update([fed] + tokens[:-1])
+            self.spec_stats["passes"] += 1
+            self.spec_stats["drafted"] += k
+            self.spec_stats["accepted"] += n - 1
+            if n == k + 1:
+                d.step(torch.tensor(tokens[-2:-1], dtype=torch.int32), dcache)  # the last draft: accepted, and not yet in the drafter's cache
+            else:
+                for c in dcache:
+                    c.trim(k - n)  # offset o + k -> o + n
+            record(model.spec_tokens, rows)
 
     def score(self, prompt_ids, top_logprobs: int = 0, **kv) -> list:
         """The log-probabilities of a prompt's own tokens (`echo`, perplexity, ranking): runs the prompt only and returns a list as long as

@@ -783,11 +783,12 @@ def _xtc(xtc, rows: int, device, who: str) -> torch.Tensor:
 
 
 def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0, want_mask: bool = False, xtc=None,
-           want_removed: bool = False):
+           want_removed: bool = False, rng: tuple | None = None):
     """The stochastic branches of make_sampler (samplers/__init__.py:39-46) as ONE HIP kernel (pie_sample): logprobs fp32 [rows, V] or [V]
     on the GPU -> token ids int32 [rows] on the same device, no host sync.  want_mask: also return (kept_count int32 [rows], kept uint8
     [rows, V]) -- the filter's kept set, for tests.  xtc: one record shared by the rows (xtc_pack, or its device form) -- the draw is
-    pie_sample_xtc's; want_removed: the int32 [rows] count of ids XTC removed joins the result as its last member."""
+    pie_sample_xtc's; want_removed: the int32 [rows] count of ids XTC removed joins the result as its last member.  rng = (seed,
+    counter int64 [2] device): another stream than the samplers' own (samplers._rng), e.g. a draft model's."""
     from .samplers import _rng
     x = logprobs
     if not x.is_cuda:
@@ -801,7 +802,7 @@ def sample(logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: in
     lib = _ffi.load()
     if int(lib.pie_sample_workspace_bytes(rows, V)) == 0:  # V > 524288 (1024 workgroups of 512 ids) or an empty block: refused, nothing launched
         raise ValueError(f"sample: a [rows, V] block with rows >= 1 and 1 <= V <= 524288, got [{rows}, {V}]")
-    seed, counter = _rng.hip_state(x.device)
+    seed, counter = _rng.hip_state(x.device) if rng is None else rng
     ws = sample_workspace(x.device, rows, V)
     tokens = torch.empty(rows, dtype=torch.int32, device=x.device)
     kept = torch.empty(rows, dtype=torch.int32, device=x.device) if want_mask else None
@@ -1316,6 +1317,59 @@ def spec_verify_sampled(logits: torch.Tensor, draft: torch.Tensor, mode: str, te
                                                    int(k), seed, _ffi.p(counter), _ffi.p(rec), _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs), _ffi.p(ws),
                                                    _ffi.stream()))
     return tokens, n, logprobs
+
+
+def spec_verify_draft_workspace(device, rows: int, V: int) -> torch.Tensor:
+    """pie_spec_verify_draft's workspace for a [rows, V] block on `device`: zeroed once, the kernels leave it ready for the next call."""
+    nbytes = int(_ffi.load().pie_spec_verify_draft_workspace_bytes(int(rows), int(V)))
+    if nbytes == 0:
+        raise ValueError(f"spec_verify_draft: 2 <= rows <= {SPEC_MAX_ROWS} and 1 <= V <= 524288, got [{rows}, {V}]")
+    return torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+
+
+def spec_verify_draft(logits: torch.Tensor, draft: torch.Tensor, q_logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0,
+                      logprobs: torch.Tensor | None = None, workspace: torch.Tensor | None = None, out: tuple | None = None,
+                      want_record: bool = False, rng: tuple | None = None):
+    """The verify of a block a draft MODEL proposed (pie_spec_verify_draft) -- speculative sampling: logits bf16 / f16
+    [rows, V] (row 0 the fed token's, row i the i-th draft's), draft int32 [rows - 1], q_logprobs fp32 [rows - 1, V] = the drafter's
+    log-probabilities at the step that drew draft[i], (mode, temp, p, k) as `sample` takes them, shared by both sides -> (tokens int32
+    [rows], n int32 [1], logprobs fp32 [rows, V]), no host sync.  With P_r / Q_i the rows' distributions under the sampler's own kept
+    sets and c the target stream's position (read on the device), draft i is accepted iff it lies in [0, V), Q_i(d) > 0 and
+    u_i * Q_i(d) < P_i(d); behind the accepted prefix comes one token more -- `sample("categorical", 1.0)` over the residual
+    log(max(0, P_j - Q_j)) at position c + j after a refusal (the row's ordinary draw when the residual is empty), the ordinary draw of
+    the last row at c + rows - 1 when every draft was accepted -- then -1, n = accepted + 1, and the stream position becomes c + n.
+    want_record: (accept_rec fp32 [rows - 1, 3] = (P_i(d_i), Q_i(d_i), u_i), residual fp32 [rows, V], rows 0 .. rows - 2 written) join
+    the result, for tests.  rng = (seed, counter int64 [2] device): the target's stream, the samplers' own by default -- the drafter must
+    have drawn under ANOTHER seed.  workspace: spec_verify_draft_workspace's (zeroed once); out = (tokens, n) to write into.  rows 2..32."""
+    from .samplers import _rng
+    who = "spec_verify_draft"
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError(f"{who}: contiguous bf16 / f16 [rows, V] logits")
+    if mode not in SAMPLE_MODES:
+        raise ValueError(f"{who}: mode is one of {sorted(SAMPLE_MODES)} (a greedy draft is verified by spec_verify)")
+    rows, V = logits.shape
+    _int32_dev(draft, rows - 1, who, "draft")
+    _dev(q_logprobs)
+    if q_logprobs.dtype != torch.float32 or tuple(q_logprobs.shape) != (rows - 1, V) or not q_logprobs.is_contiguous():
+        raise ValueError(f"{who}: q_logprobs is a contiguous fp32 [rows - 1, V] device tensor")
+    if logprobs is None:
+        logprobs = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
+    _dev(logprobs)
+    if logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (rows, V) or not logprobs.is_contiguous():
+        raise ValueError(f"{who}: logprobs is a contiguous fp32 [rows, V] device tensor")
+    ws = spec_verify_draft_workspace(logits.device, rows, V) if workspace is None else workspace
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
+    tokens, n = out
+    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
+    seed, counter = _rng.hip_state(logits.device) if rng is None else rng
+    rec = torch.zeros((rows - 1, 3), dtype=torch.float32, device=logits.device) if want_record else None
+    res = torch.zeros((rows, V), dtype=torch.float32, device=logits.device) if want_record else None
+    _ffi.check(_ffi.load().pie_spec_verify_draft(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(draft), _ffi.p(q_logprobs), SAMPLE_MODES[mode],
+                                                 float(temp), float(p), int(k), int(seed), _ffi.p(counter), _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs), _ffi.p(rec),
+                                                 _ffi.p(res), _ffi.p(ws), _ffi.stream()))
+    return (tokens, n, logprobs, rec, res) if want_record else (tokens, n, logprobs)
 
 
 # ---------------------------------------------------------------- rotating KV cache (csrc/rotating.hip, prefill.hip)

@@ -583,9 +583,9 @@ class Model(RowsTailState, StepTailState):
         self._check_speculative("spec_step", cache)
         return self._spec_pass("spec_step", "pie_decoder_spec_step", "ws", draft_ids, cache, then_draft)
 
-    def _spec_pass(self, who: str, entry: str, ws: str, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None):
-        """What spec_step and spec_step_tail share: the record, the library entry on workspace `ws`, the drafter hand-off, the one
-        read-back and the cache advance."""
+    def _spec_pass(self, who: str, entry: str, ws: str, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None, extra: tuple = ()):
+        """What spec_step, spec_step_tail and spec_step_draft share: the record, the library entry on workspace `ws`, the drafter hand-off,
+        the one read-back and the cache advance.  extra: the entry's arguments between the draft and the outputs."""
         draft_ids = draft_ids.reshape(-1)
         if not draft_ids.is_cuda or draft_ids.dtype != torch.int32 or not draft_ids.is_contiguous():
             raise ValueError(f"{who}: draft_ids is a contiguous int32 device tensor")
@@ -598,7 +598,7 @@ class Model(RowsTailState, StepTailState):
         if self._kv.offset + m + 1 > self.fed_ids.numel():
             raise ValueError(f"{who}: the pass would run past the model's id history")
         sp["host"] = None
-        _ffi.check(getattr(_ffi.load(), entry)(self._dec, _ffi.p(draft_ids), m, _ffi.p(rec[self._SPEC_TOK:]), _ffi.p(rec[self._SPEC_N:]),
+        _ffi.check(getattr(_ffi.load(), entry)(self._dec, _ffi.p(draft_ids), m, *extra, _ffi.p(rec[self._SPEC_TOK:]), _ffi.p(rec[self._SPEC_N:]),
                                                _ffi.p(sp["logprobs"]), _ffi.p(sp[ws]), _ffi.p(self.fed_ids), self.fed_ids.numel(),
                                                _ffi.p(rec[self._SPEC_LEN:]), _ffi.stream()))
         sp["last_ws"] = ws
@@ -630,6 +630,38 @@ class Model(RowsTailState, StepTailState):
             nbytes = int(_ffi.load().pie_decoder_spec_tail_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
             sp["tail_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
         return self._spec_pass(who, "pie_decoder_spec_step_tail", "tail_ws", draft_ids, cache, then_draft)
+
+    def spec_step_draft(self, draft_ids: torch.Tensor, q_logprobs: torch.Tensor, cache: list[BaseCache], *, draft_seed: int):
+        """One speculative pass over a block a draft MODEL proposed (pie_decoder_spec_step_draft): spec_step_tail's pass and
+        per-row edits, with speculative sampling's acceptance in place of "the draw equals the draft".  q_logprobs fp32 [m, V] (device):
+        row i = the drafter's log-probabilities at the step that drew draft_ids[i], under the same (mode, temp, p, k) as this model's
+        sampler and ANOTHER seed, draft_seed (samplers._rng.draft_state's): under the target's seed the drafter's Gumbels would be those
+        of the target's residual draw at the same call index, and the result would no longer be distributed as the target's -- refused.
+        Draft i is accepted with probability min(1, P_i(d) / Q_i(d)); the token behind the accepted prefix is
+        drawn from the residual max(0, P - Q) (or, behind a fully accepted block, from the last row), so every returned token is
+        distributed as a plain step's.  The same returns as spec_step; all m + 1 rows of the log-probabilities are written and the
+        samplers' stream moves by n.  A stochastic sampler is required (set_step_tail(sampler=...)); a repetition penalty and a logit
+        bias are applied; XTC, a token mask, top_logprobs, frequency / presence penalties and DRY are refused by name, like
+        tensor-parallel models, int8 pages and the other cache kinds."""
+        who = "spec_step_draft"
+        self._check_speculative_kv(who, cache)
+        for bad, name in ((self._xtc is not None, "XTC"), (self._edits[0], "a token mask"), (self._top_n is not None, "top_logprobs"),
+                          (self._cnt is not None, "frequency / presence penalties"), (self._dry is not None, "a DRY penalty")):
+            if bad:
+                raise ValueError(f"{who}: not available with {name}")
+        if self._tail[0] is None:
+            raise ValueError(f"{who}: no stochastic sampler is set -- a greedy draft is a point mass, verified by spec_step or spec_step_tail")
+        if int(draft_seed) & (2 ** 64 - 1) == int(self._tail[2]) & (2 ** 64 - 1):
+            raise ValueError(f"{who}: not available with a drafter under the target's seed (samplers._rng.draft_state gives the drafter's)")
+        m = draft_ids.numel()
+        if not q_logprobs.is_cuda or q_logprobs.dtype != torch.float32 or q_logprobs.dim() != 2 or q_logprobs.shape[0] < m or \
+                q_logprobs.shape[1] != self.vocab_out or not q_logprobs.is_contiguous():
+            raise ValueError(f"{who}: q_logprobs is a contiguous fp32 [>= {m}, {self.vocab_out}] device tensor (a vocabulary mismatch is refused)")
+        sp = self._spec_state()
+        if "draft_model_ws" not in sp:  # zeroed once: the samplers' parts are carried from pass to pass
+            nbytes = int(_ffi.load().pie_decoder_spec_draft_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
+            sp["draft_model_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        return self._spec_pass(who, "pie_decoder_spec_step_draft", "draft_model_ws", draft_ids, cache, None, extra=(_ffi.p(q_logprobs),))
 
     def spec_logits(self, rows: int) -> torch.Tensor:
         """The logits block [rows, V] of the last pass (a view of its workspace, valid until the next one): raw after spec_step, processed

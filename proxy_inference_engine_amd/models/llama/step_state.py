@@ -35,7 +35,7 @@ class StepTailState:
     def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
                       token_mask=None, logit_bias=None, top_logprobs: int | None = None, frequency_penalty: float = 0.0,
                       presence_penalty: float = 0.0, count_start: int | None = None, dry: tuple | None = None,
-                      xtc: tuple | None = None) -> None:
+                      xtc: tuple | None = None, rng: tuple | None = None) -> None:
         """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
         DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
@@ -62,6 +62,8 @@ class StepTailState:
         the top choices with the given probability; the returned logits, logprobs and top-n record stay those before XTC.  Ignored without
         a sampler (a greedy tail), and a probability of 0 is off.  The model owns one record at a stable address (`step_xtc_record`): new
         values are a copy and a replay, not a re-capture.
+        rng: None = samplers' random stream, or (seed, counter int64 [2] device) -- a stream of the caller's own: a draft model draws
+        under samplers._rng.draft_state, never under the target's seed.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
         self._set_tail_edits(token_mask, logit_bias)
@@ -73,7 +75,7 @@ class StepTailState:
         seed = counter = None
         if sampler is not None:
             from ...samplers import _rng
-            seed, counter = _rng.hip_state(self.device)
+            seed, counter = _rng.hip_state(self.device) if rng is None else (int(rng[0]), rng[1])
             sampler = (str(sampler[0]), float(sampler[1]), float(sampler[2]), int(sampler[3]))
         tail = (sampler, pen, seed)
         if tail == self._tail:
