@@ -856,6 +856,50 @@ int pie_decoder_set_batch_dry_penalty(pie_decoder *d, const pie_dry_penalty *rec
  * pie_decoder_spec_step refuses a set record like every other tail. */
 int pie_decoder_set_xtc(pie_decoder *d, const pie_xtc *record);
 int pie_decoder_set_batch_xtc(pie_decoder *d, const pie_xtc *records, int rows_cap);
+/* Token automaton: a grammar as a token-level DFA compressed by token classes, whose state lives on the device.  An automaton
+ * over a vocabulary of V ids with S states and C classes is V + S * C consecutive int32 words inside a caller-owned DEVICE arena
+ * `tables` [tables_len]: cls [V] (token id -> class in [0, C)), then trans [S, C] (the next state in [0, S), or -1: not allowed).  Token t
+ * is allowed in state s iff trans[s, cls[t]] >= 0.  A row is a record pie_row_dfa (word offsets into the arena) and a state (int32), both
+ * DEVICE memory whose CONTENTS the host may rewrite in stream order, and neither is trusted.  A row is ARMED iff n_states > 0 and
+ * n_classes > 0, both offsets >= 0, cls_off + V <= tables_len and trans_off + n_states * n_classes <= tables_len (in 64 bits); an id
+ * whose class lies outside [0, n_classes) is disallowed.  An all-zero record is unarmed.
+ * pie_token_dfa_mask: records [rows], states [rows]; masks DEVICE uint32 [rows, mask_words >= ceil(V / 32)] in pie_logprobs_argmax_masked's
+ *   bit layout; mask_on nullable DEVICE int32 [rows] (pie_logprobs_argmax_rows_masked's).  Armed row, state in [0, S): words 0 ..
+ *   ceil(V / 32) - 1 of the row are written (bits at or beyond V as 0; later words are never touched) and mask_on[row] = 1.  Armed row,
+ *   state outside [0, S) -- the automaton has been left, or is finished: mask_on[row] = 0 and the words are left alone; without mask_on
+ *   the words are written all-allowed below V.  Unarmed row: nothing of the row is written -- a mask the host wrote survives.
+ * pie_token_dfa_advance: tokens DEVICE int32 [rows].  Armed row with a state in [0, S): states[row] = trans[s, cls[token]] for a token
+ *   in [0, V) whose class is in range, -1 for any other token.  A state outside [0, S) stays what it is; an unarmed row is untouched.
+ * Both: one launch.  A NULL pointer (but mask_on): PIE_E_ARG; rows outside 1..65535, V < 1, tables_len < 1, mask_words < ceil(V / 32):
+ * PIE_E_SHAPE; a pointer not 4-byte aligned: PIE_E_ALIGN -- all before any launch.
+ * pie_decoder_set_token_dfa: the single-sequence step derives its token mask from the state and advances the state by the token it feeds
+ *   back, inside the replayed graph.  record: one pie_row_dfa, state: one int32, tables [tables_len], mask [mask_words >= ceil(vocab /
+ *   32)] (the buffer the part writes and the masked partials read) -- all caller-owned DEVICE memory, alive while set.  Wherever the
+ *   configured tail applies: pie_token_dfa_mask first | the edits | the partials, masked with `mask` | finish, sampler, top-n |
+ *   pie_token_dfa_advance on the bound token, after the draw.  With logits_all != NULL nothing of it runs and the state does not move.
+ *   Launches beyond the unconfigured step's: alone 3 (pie_decoder_set_logits_mask's 1, plus 2); with a bias and / or a penalty 4.  The
+ *   CONTENTS of record, state and tables may change between steps in stream order while a captured graph keeps replaying; a new address or
+ *   size drops the captured graphs.  record == NULL switches it off.  Mutually exclusive with pie_decoder_set_logits_mask: whichever is
+ *   set second is refused (PIE_E_STATE).  pie_decoder_spec_step_tail refuses a set automaton by name; tensor-parallel decoders refuse the
+ *   setter (PIE_E_STATE).  The op's argument rules.
+ * pie_decoder_set_batch_token_dfa: pie_decoder_step_batch (eager or PIE_STEP_GRAPH, the fused few-sequence form included),
+ *   _prefill_batch and _step_mixed; record s and state s belong to output row s in pie_decoder_set_batch_tail's row order.  records DEVICE
+ *   pie_row_dfa [rows_cap], states DEVICE int32 [rows_cap], tables [tables_len].  Needs pie_decoder_set_batch_logits_edits with a mask
+ *   part set first (else PIE_E_STATE; a pass that finds the mask part gone is PIE_E_STATE before any launch): pie_token_dfa_mask over
+ *   the pass's output rows writes the armed rows' words and mask_on entries into that part's arrays in front of the tail, so an unarmed
+ *   row keeps the mask the host wrote, or none; pie_token_dfa_advance on next_tokens follows the rows' samplers.  +2 launches on every
+ *   path, relative to masks alone.  The addresses, tables_len and rows_cap are part of the captured batch graph's key.  rows_cap == 0
+ *   switches it off.  A pass with more output rows than rows_cap is PIE_E_SHAPE before any launch; tensor-parallel decoders refuse. */
+typedef struct pie_row_dfa {
+    int32_t cls_off, trans_off, n_states, n_classes;
+} pie_row_dfa;
+int pie_token_dfa_mask(const pie_row_dfa *records, const int32_t *states, const int32_t *tables, int tables_len, int rows, int V, uint32_t *masks,
+                       int mask_words, int32_t *mask_on, void *stream);
+int pie_token_dfa_advance(const pie_row_dfa *records, int32_t *states, const int32_t *tables, int tables_len, int rows, int V, const int32_t *tokens,
+                          void *stream);
+int pie_decoder_set_token_dfa(pie_decoder *d, const pie_row_dfa *record, int32_t *state, const int32_t *tables, int tables_len, uint32_t *mask,
+                              int mask_words);
+int pie_decoder_set_batch_token_dfa(pie_decoder *d, int rows_cap, const pie_row_dfa *records, int32_t *states, const int32_t *tables, int tables_len);
 /* One speculative pass of the single-sequence decoder: m = n_draft drafted ids (draft_ids DEVICE int32 [m]) are verified in one
  * pass over the weights.  In order: (1) rows [the device-side token, draft_0 .. draft_{m - 1}] are gathered on the device (a draft id the
  * embedding could not index is fed as id 0; pie_spec_verify never accepts it) and forwarded from the device-side offset through

@@ -54,6 +54,7 @@ EXPORTS = [
     "pie_count_penalty_bytes", "pie_count_penalty_pack", "pie_logits_count_penalty_rows", "pie_decoder_set_count_penalty", "pie_decoder_set_batch_count_penalty",
     "pie_dry_penalty_bytes", "pie_dry_penalty_pack", "pie_logits_dry_penalty", "pie_logits_dry_penalty_rows", "pie_decoder_set_dry_penalty", "pie_decoder_set_batch_dry_penalty",
     "pie_xtc_bytes", "pie_xtc_pack", "pie_sample_xtc", "pie_sample_rows_xtc", "pie_decoder_set_xtc", "pie_decoder_set_batch_xtc",
+    "pie_token_dfa_mask", "pie_token_dfa_advance", "pie_decoder_set_token_dfa", "pie_decoder_set_batch_token_dfa",
     "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
     "pie_spec_verify_sampled_workspace_bytes", "pie_spec_verify_sampled", "pie_decoder_spec_tail_workspace_bytes", "pie_decoder_spec_step_tail",
     "pie_spec_verify_draft_workspace_bytes", "pie_spec_verify_draft", "pie_decoder_spec_draft_workspace_bytes", "pie_decoder_spec_step_draft",
@@ -104,6 +105,11 @@ class pie_xtc(C.Structure):
     """One XTC record in device memory (include/pie_hip.h)."""
     _fields_ = [("log_threshold", C.c_float), ("probability", C.c_float), ("n_special", C.c_int32), ("reserved", C.c_int32),
                 ("special", C.c_int32 * PIE_XTC_SPECIAL_MAX)]
+
+
+class pie_row_dfa(C.Structure):
+    """One row's token-automaton record in device memory: word offsets into the arena and the table's shape (include/pie_hip.h)."""
+    _fields_ = [("cls_off", C.c_int32), ("trans_off", C.c_int32), ("n_states", C.c_int32), ("n_classes", C.c_int32)]
 
 
 def set_knob(name: str, value: int | None) -> None:
@@ -209,6 +215,10 @@ def load() -> C.CDLL:
     lib.pie_sample_rows_xtc.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
     lib.pie_decoder_set_xtc.argtypes = [C.c_void_p, C.c_void_p]
     lib.pie_decoder_set_batch_xtc.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.pie_token_dfa_mask.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_token_dfa_advance.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]
+    lib.pie_decoder_set_token_dfa.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int]
+    lib.pie_decoder_set_batch_token_dfa.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
     lib.pie_ngram_draft_workspace_bytes.restype = C.c_size_t
     lib.pie_ngram_draft_workspace_bytes.argtypes = []
     lib.pie_ngram_draft.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4

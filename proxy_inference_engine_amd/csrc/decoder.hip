@@ -165,6 +165,8 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
     const StepTail &t = d->tail;
     const LogitStat *stats = d->stats;
     int n_stats = d->n_stats, rc;
+    // token automaton: its mask words come first, from the state as the previous step's advance left it
+    if (t.dfa.on() && (rc = token_dfa_mask_launch(t.dfa.record, t.dfa.state, t.dfa.tables, t.dfa.tables_len, 1, c.vocab, t.dfa.mask, t.dfa.mask_words, nullptr, st))) return rc;
     if (t.penalty.on() || t.bias.on()) {  // edit
         PenArgs a = {};
         a.logits = d->logits, a.V = c.vocab, a.penalty = (float)t.penalty.value, a.ids_by_pos = t.penalty.ids_by_pos, a.ids_cap = t.penalty.ids_cap, a.context = t.penalty.context;
@@ -184,7 +186,7 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
         if ((rc = logits_dry_launch(c.dtype, k, st))) return rc;
     }
     if (t.edits_logits()) {  // partials: the lm_head epilogue's are stale
-        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, t.tail_stats, st, t.mask.words))) return rc;
+        if ((rc = logits_stats_launch(c.dtype, d->logits, c.vocab, t.tail_stats, st, t.dfa.on() ? t.dfa.mask : t.mask.words))) return rc;
         stats = t.tail_stats, n_stats = TAIL_STAT_TILES;
     }
     // finish
@@ -195,9 +197,11 @@ static int configured_tail(pie_decoder *d, bool from_state, hipStream_t st) {
         if ((rc = sample_launch(d->logprobs, 1, c.vocab, s.mode, s.temp, s.p, s.k, s.seed, s.counter, s.ws, d->token_out, nullptr, nullptr, feed, st, SampleXtc{t.xtc.record, nullptr})))
             return rc;
     }
-    if (!t.top.on()) return PIE_OK;
-    // last, after the draw: slot 0 is the token that is fed back
-    return top_logprobs_launch(d->logprobs, 1, c.vocab, t.top.n, d->token_out, nullptr, t.top.ids, t.top.vals, t.top.ws, st);
+    // after the draw: slot 0 is the token that is fed back
+    if (t.top.on() && (rc = top_logprobs_launch(d->logprobs, 1, c.vocab, t.top.n, d->token_out, nullptr, t.top.ids, t.top.vals, t.top.ws, st))) return rc;
+    if (!t.dfa.on()) return PIE_OK;
+    // last: the automaton's state moves by the token that is fed back
+    return token_dfa_advance_launch(t.dfa.record, t.dfa.state, t.dfa.tables, t.dfa.tables_len, 1, c.vocab, d->token_out, st);
 }
 
 // One launch of the step's sequence (PIE_K_* of include/pie_hip.h); `li` is the layer for per-layer kernels.
@@ -717,7 +721,7 @@ int enqueue_scored_step(pie_decoder *d, const int *token_ptr, int l, bool last, 
     return rc ? rc : d->prompt.score_rows(d->cfg, dst, l, 1, st);
 }
 
-// What every setter of a tail begins with -- the eight of the step's and the seven of the multi-sequence passes'
+// What every setter of a tail begins with -- the nine of the step's and the eight of the multi-sequence passes'
 static int tail_entry(const pie_decoder *d, const char *entry) {
     PIE_REQUIRE(d, PIE_E_ARG, std::string(entry) + ": null decoder");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, std::string(entry) + ": the tail of a tensor-parallel decoder is vocabulary-parallel and not configurable");
@@ -852,8 +856,29 @@ int pie_decoder_set_logits_mask(pie_decoder *d, const uint32_t *mask, int mask_w
     if (mask) {
         PIE_REQUIRE(mask_words >= (d->cfg.vocab + 31) / 32, PIE_E_SHAPE, "pie_decoder_set_logits_mask: the mask needs ceil(vocab / 32) words");
         PIE_REQUIRE(pie_aligned(mask, 4), PIE_E_ALIGN, "pie_decoder_set_logits_mask: the mask needs 4-byte alignment");
+        PIE_REQUIRE(!d->tail.dfa.on(), PIE_E_STATE, "pie_decoder_set_logits_mask: a token automaton is set (pie_decoder_set_token_dfa), and it writes the step's mask");
     }
     return set_part(d, d->tail.mask, {mask});
+}
+
+int pie_decoder_set_token_dfa(pie_decoder *d, const pie_row_dfa *record, int32_t *state, const int32_t *tables, int tables_len, uint32_t *mask, int mask_words) {
+    if (int rc = tail_entry(d, "pie_decoder_set_token_dfa")) return rc;
+    if (!record) return set_part(d, d->tail.dfa, {});  // off, whatever the other arguments say
+    PIE_REQUIRE(mask, PIE_E_ARG, "pie_decoder_set_token_dfa: null pointer");
+    if (int rc = token_dfa_check("pie_decoder_set_token_dfa", record, state, tables, tables_len, 1, d->cfg.vocab)) return rc;
+    PIE_REQUIRE(mask_words >= (d->cfg.vocab + 31) / 32, PIE_E_SHAPE, "pie_decoder_set_token_dfa: the mask needs ceil(vocab / 32) words");
+    PIE_REQUIRE(pie_aligned(mask, 4), PIE_E_ALIGN, "pie_decoder_set_token_dfa: the mask needs 4-byte alignment");
+    PIE_REQUIRE(!d->tail.mask.on(), PIE_E_STATE, "pie_decoder_set_token_dfa: a token mask is set (pie_decoder_set_logits_mask), and the automaton writes a mask of its own");
+    return set_part(d, d->tail.dfa, {record, state, tables, tables_len, mask, mask_words});
+}
+
+int pie_decoder_set_batch_token_dfa(pie_decoder *d, int rows_cap, const pie_row_dfa *records, int32_t *states, const int32_t *tables, int tables_len) {
+    if (int rc = tail_entry(d, "pie_decoder_set_batch_token_dfa")) return rc;
+    if (rows_cap == 0) return d->rows.dfa = {}, PIE_OK;  // off
+    if (int rc = token_dfa_check("pie_decoder_set_batch_token_dfa", records, states, tables, tables_len, rows_cap, d->cfg.vocab)) return rc;
+    PIE_REQUIRE(d->rows.edits.masks, PIE_E_STATE, "pie_decoder_set_batch_token_dfa: set the batch logits edits with a mask part first (pie_decoder_set_batch_logits_edits): the automata write its masks");
+    d->rows.dfa = {records, states, tables, tables_len, rows_cap};  // (the batch graph's key holds them: no graph to drop)
+    return PIE_OK;
 }
 
 int pie_decoder_set_logit_bias(pie_decoder *d, const int32_t *ids, const float *bias, int n) {

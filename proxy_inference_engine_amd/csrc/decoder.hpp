@@ -8,6 +8,7 @@
 #include "kv_quant.hpp"
 #include "sampler.hpp"
 #include "tail.hpp"
+#include "token_dfa.hpp"
 #include "top_logprobs.hpp"
 #include "prompt_logprobs.hpp"
 #include "w4_gemv.hpp"
@@ -57,6 +58,12 @@ struct RowsTail {
         const pie_xtc *records = nullptr;  // [rows_cap], nullptr: off
         int rows_cap = 0;
     } xtc;
+    struct Dfa {  // pie_decoder_set_batch_token_dfa: per-row automaton records and states over one arena; writes the edits' masks
+        const pie_row_dfa *records = nullptr;  // [rows_cap], nullptr: off
+        int *states = nullptr;                 // [rows_cap]
+        const int *tables = nullptr;           // [tables_len]
+        int tables_len = 0, rows_cap = 0;
+    } dfa;
     // everything a captured batch graph bakes in (pie_decoder_step_batch's key): a setter drops no graph, a changed key captures a new one
     void key(std::vector<uintptr_t> &k) const {
         for (uintptr_t v : {(uintptr_t)sampler.table, (uintptr_t)sampler.recent, (uintptr_t)sampler.ws, (uintptr_t)sampler.rows_cap,
@@ -65,25 +72,28 @@ struct RowsTail {
                             (uintptr_t)edits.bias_vals, (uintptr_t)edits.bias_n, (uintptr_t)edits.bias_cap,
                             (uintptr_t)counts.records, (uintptr_t)counts.counts, (uintptr_t)counts.rows_cap,
                             (uintptr_t)dry.records, (uintptr_t)dry.breakers, (uintptr_t)dry.recent, (uintptr_t)dry.rows_cap,
-                            (uintptr_t)xtc.records, (uintptr_t)xtc.rows_cap})
+                            (uintptr_t)xtc.records, (uintptr_t)xtc.rows_cap,
+                            (uintptr_t)dfa.records, (uintptr_t)dfa.states, (uintptr_t)dfa.tables, (uintptr_t)dfa.tables_len, (uintptr_t)dfa.rows_cap})
             k.push_back(v);
     }
     // a pass with `out_rows` output rows fits every configured part (checked before any launch)
     int check_rows(int out_rows, const char *entry) const {
+        if (dfa.records && !edits.masks) return pie::fail(PIE_E_STATE, std::string(entry) + ": the batch token automata need the batch logits edits' mask part");
         const char *over = sampler.table && out_rows > sampler.rows_cap   ? "batch tail"
                            : edits.rows_cap && out_rows > edits.rows_cap  ? "batch logits edits"
                            : top.n && out_rows > top.rows_cap             ? "top log-probabilities"
                            : counts.records && out_rows > counts.rows_cap ? "batch count penalty"
                            : dry.records && out_rows > dry.rows_cap       ? "batch DRY penalty"
-                           : xtc.records && out_rows > xtc.rows_cap       ? "batch XTC" : nullptr;
+                           : xtc.records && out_rows > xtc.rows_cap       ? "batch XTC"
+                           : dfa.records && out_rows > dfa.rows_cap       ? "batch token automata" : nullptr;
         return over ? pie::fail(PIE_E_SHAPE, std::string(entry) + ": more output rows than the " + over + "'s rows_cap") : PIE_OK;
     }
     // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale
-    bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records || dry.records; }
+    bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records || dry.records || dfa.records; }
 };
 
 // The single-sequence step's configured tail, applied where the tail writes the bound outputs and pie_decoder::tail_raw is
-// false: eight parts, each set as a whole by its own entry and off in its value-initialised state.  Caller-owned device memory whose CONTENTS
+// false: nine parts, each set as a whole by its own entry and off in its value-initialised state.  Caller-owned device memory whose CONTENTS
 // may change between steps; every field is a launch argument that a captured step graph bakes in, so a setter drops the graphs exactly when
 // its part compares unequal (decoder.hip: set_part): a field that joins a part joins the operator== beside it.
 struct StepTail {
@@ -138,17 +148,27 @@ struct StepTail {
         bool on() const { return record != nullptr; }
         bool operator==(const Xtc &o) const { return record == o.record; }
     } xtc;
+    struct Dfa {  // pie_decoder_set_token_dfa: the automaton's record, state and arena, and the mask words the part writes
+        const pie_row_dfa *record = nullptr;  // nullptr: off
+        int *state = nullptr;
+        const int *tables = nullptr;
+        int tables_len = 0;
+        unsigned *mask = nullptr;  // [mask_words >= ceil(vocab / 32)]: written by the mask op, read by the masked partials
+        int mask_words = 0;
+        bool on() const { return record != nullptr; }
+        bool operator==(const Dfa &o) const { return record == o.record && state == o.state && tables == o.tables && tables_len == o.tables_len && mask == o.mask && mask_words == o.mask_words; }
+    } dfa;
     LogitStat *tail_stats = nullptr;  // owned scratch, not configuration: [TAIL_STAT_TILES] partials of the edited logits (decoder.hip: set_part)
     // The only readers of "what is configured" besides the launches:
     // some part wants more than the greedy tail over the lm_head's own partials.  XTC is missing on purpose: it only changes a sampler's
     // draw, so alone it configures nothing (and with a sampler, the sampler answers).
-    bool configured() const { return penalty.on() || sampler.on() || mask.on() || bias.on() || top.on() || counts.on() || dry.on(); }
+    bool configured() const { return penalty.on() || sampler.on() || mask.on() || bias.on() || top.on() || counts.on() || dry.on() || dfa.on(); }
     // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale.  The sampler, XTC and top-n are
     // missing on purpose: they read the finished log-probabilities and change no logit.
-    bool edits_logits() const { return penalty.on() || mask.on() || bias.on() || counts.on() || dry.on(); }
+    bool edits_logits() const { return penalty.on() || mask.on() || bias.on() || counts.on() || dry.on() || dfa.on(); }
     // Speculation under a tail (speculative.hip: spec_prologue) admits the penalty, the bias, the sampler and XTC -- what its per-row edit
     // and its sampled verify apply -- and refuses every other part by name.  (The greedy and raw pass asks !configured() and !xtc.on().)
-    const char *spec_tail_refused() const { return mask.on() ? "a token mask" : top.on() ? "a top-logprobs record" : counts.on() ? "frequency / presence counts" : dry.on() ? "a DRY penalty" : nullptr; }
+    const char *spec_tail_refused() const { return mask.on() ? "a token mask" : dfa.on() ? "a token automaton" : top.on() ? "a top-logprobs record" : counts.on() ? "frequency / presence counts" : dry.on() ? "a DRY penalty" : nullptr; }
     bool spec_tail_admitted() const { return penalty.on() || sampler.on() || bias.on() || xtc.on(); }
 };
 

@@ -5,6 +5,7 @@
 
 #include "attention.hpp"
 #include "tail.hpp"
+#include "token_dfa.hpp"
 
 // ---------------------------------------------------------------- attention launch
 template <class T, int D, bool PAGED, bool NT, bool SHORT = false, bool RING = false>
@@ -413,6 +414,23 @@ int pie_logits_bias_rows(void *logits, int rows, int V, int dtype, const int32_t
     a.logits = (u16 *)logits, a.V = V;  // no ctx: every row is live, and the penalty phase is off
     const BiasRowsArgs b = {ids, bias, n, cap, 0};
     return logits_edit_rows_launch(dtype, a, b, rows, (hipStream_t)stream);
+}
+
+int pie_token_dfa_mask(const pie_row_dfa *records, const int32_t *states, const int32_t *tables, int tables_len, int rows, int V, uint32_t *masks,
+                       int mask_words, int32_t *mask_on, void *stream) {
+    PIE_REQUIRE(masks, PIE_E_ARG, "pie_token_dfa_mask: null pointer");
+    if (int rc = token_dfa_check("pie_token_dfa_mask", records, states, tables, tables_len, rows, V)) return rc;
+    PIE_REQUIRE(mask_words >= (V + 31) / 32, PIE_E_SHAPE, "pie_token_dfa_mask: every row's mask needs ceil(V / 32) words");
+    PIE_REQUIRE(pie_aligned(masks, 4) && pie_aligned(mask_on, 4), PIE_E_ALIGN, "pie_token_dfa_mask: masks and mask_on need 4-byte alignment");
+    return token_dfa_mask_launch(records, states, tables, tables_len, rows, V, masks, mask_words, mask_on, (hipStream_t)stream);
+}
+
+int pie_token_dfa_advance(const pie_row_dfa *records, int32_t *states, const int32_t *tables, int tables_len, int rows, int V, const int32_t *tokens,
+                          void *stream) {
+    PIE_REQUIRE(tokens, PIE_E_ARG, "pie_token_dfa_advance: null pointer");
+    if (int rc = token_dfa_check("pie_token_dfa_advance", records, states, tables, tables_len, rows, V)) return rc;
+    PIE_REQUIRE(pie_aligned(tokens, 4), PIE_E_ALIGN, "pie_token_dfa_advance: tokens need 4-byte alignment");
+    return token_dfa_advance_launch(records, states, tables, tables_len, rows, V, tokens, (hipStream_t)stream);
 }
 
 size_t pie_count_penalty_bytes(void) { return sizeof(pie_count_penalty); }

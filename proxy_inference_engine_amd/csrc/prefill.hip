@@ -874,6 +874,9 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     const RowsTail &r = d->rows;
     int rc;
     // The six stages of configured_tail (decoder.hip), per row; with nothing configured only the partials and the finish run.
+    // token automata: the armed rows' masks and mask_on entries come first, written into the edits' mask part (check_rows: set)
+    if (r.dfa.records && (rc = token_dfa_mask_launch(r.dfa.records, r.dfa.states, r.dfa.tables, r.dfa.tables_len, rows, c.vocab, const_cast<unsigned *>(r.edits.masks),
+                                                     r.edits.mask_words, const_cast<int *>(r.edits.mask_on), st))) return rc;
     if (r.sampler.table || r.edits.bias_cap) {  // edit: the rows' biases ride the penalty's launch (k_logits_edit_rows: no penalties without a table)
         PenRowsArgs p = {};
         p.logits = logits, p.V = c.vocab, p.n_src = n_src, p.table = r.sampler.table, p.recent = r.sampler.recent, p.ids = ids, p.ctx = ctx, p.out_rows = out_rows;
@@ -896,7 +899,10 @@ static int batch_tail_launch(pie_decoder *d, const int32_t *ids, const int32_t *
     // sampler and top-n
     if (r.sampler.table && (rc = sample_rows_launch(logprobs, rows, c.vocab, r.sampler.table, r.sampler.ws, next_tokens, nullptr, nullptr, st,
                                                      SampleXtc{r.xtc.records, nullptr}))) return rc;
-    return batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st);
+    if ((rc = batch_top_logprobs_launch(d, rows, logprobs, next_tokens, st))) return rc;
+    if (!r.dfa.records) return PIE_OK;
+    // last: every armed row's state moves by the token it drew
+    return token_dfa_advance_launch(r.dfa.records, r.dfa.states, r.dfa.tables, r.dfa.tables_len, rows, c.vocab, next_tokens, st);
 }
 
 // ---------------------------------------------------------------- one decode step for B sequences (continuous batching)

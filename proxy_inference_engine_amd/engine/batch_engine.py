@@ -42,7 +42,10 @@ class SamplingParams:
     after the frequency / presence penalties: the token that would extend a repeat of the sequence's tail of at least dry_allowed_length
     ids loses dry_multiplier * dry_base ** (length - dry_allowed_length).  dry_sequence_breakers: up to 64 token ids a repeat does not cross.
     xtc_probability > 0 with xtc_threshold in (0, 0.5] (DESIGN.md 19): the request's draw runs under XTC, per row inside the passes' sampler;
-    xtc_special_tokens: up to 16 ids XTC never removes, None: the engine's stop tokens.  A greedy request (temp == 0) ignores XTC."""
+    xtc_special_tokens: up to 16 ids XTC never removes, None: the engine's stop tokens.  A greedy request (temp == 0) ignores XTC.
+    token_automaton: a logits_processors.TokenAutomaton -- a grammar compiled ahead of time, where token_mask stands and
+    exclusive with it: the request's row derives its mask from the automaton's state inside the passes and advances the state by the token
+    it drew (Model.set_batch_automata), so no callable runs for it on the host."""
     temp: float = 0.0
     top_p: float = 1.0
     top_k: int = -1
@@ -63,6 +66,7 @@ class SamplingParams:
     xtc_probability: float = 0.0
     xtc_threshold: float = 0.0
     xtc_special_tokens: tuple | None = None
+    token_automaton: object = None
 
     def xtc(self, stop_tokens=()) -> tuple | None:
         """(probability, threshold, special ids) under samplers.check_xtc's rules (ValueError otherwise), None when the request draws
@@ -112,7 +116,21 @@ class SamplingParams:
     @property
     def plain(self) -> bool:
         """Greedy without a penalty, a mask or a bias: today's tail."""
-        return self.tailless and self.token_mask is None and self.logit_bias is None
+        return self.tailless and self.token_mask is None and self.logit_bias is None and self.token_automaton is None
+
+    def automaton(self, vocab_size: int):
+        """The request's TokenAutomaton or None, checked against the vocabulary: ValueError for another type, another vocabulary, and
+        together with a token_mask."""
+        from ..logits_processors import TokenAutomaton
+        a = self.token_automaton
+        if a is None:
+            return None
+        if self.token_mask is not None:
+            raise ValueError("SamplingParams: token_mask and token_automaton are exclusive")
+        if not isinstance(a, TokenAutomaton):
+            raise ValueError("SamplingParams: token_automaton is a logits_processors.TokenAutomaton")
+        a.check_vocab(vocab_size)
+        return a
 
     def count_penalties(self) -> tuple[float, float]:
         """(frequency_penalty, presence_penalty), each within -2.0 .. 2.0: ValueError otherwise."""
@@ -228,8 +246,10 @@ class _RowSeats:
     (then `maps` collects their records' maps).  A kind that is None is neither armed nor written.  As a context manager: arms the kinds
     asked for with every row neutral, and clears them on the way out, whatever happened."""
 
-    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None, drys=None, xtcs=None):
+    def __init__(self, model, max_batch: int, prompts: list, tails=None, edits=None, cnts=None, tops=None, drys=None, xtcs=None, autos=None):
         self.model, self.max_batch, self.prompts = model, max_batch, prompts
+        self.autos = autos            # every request's TokenAutomaton or None, or None
+        self.aseats: list = []        # token automata: what row s of the records holds, (request, tokens generated) or None = unarmed
         self.tails, self.edits, self.cnts, self.tops, self.drys = tails, edits, cnts, tops, drys
         self.xtcs = xtcs if tails is not None else None   # every request's SamplingParams.xtc or None, or None: XTC rides the batch tail's sampler
         self.maps = None if tops is None else [[] for _ in prompts]
@@ -254,6 +274,9 @@ class _RowSeats:
                 any_mask, cap = any(k is not None for k, _ in self.edits), max(len(b[0]) if b else 0 for _, b in self.edits)
                 m.set_batch_edits(self.max_batch, masks=any_mask, bias_cap=cap)
                 m.write_batch_edits(every, [None] * self.max_batch if any_mask else None, [None] * self.max_batch if cap else None)   # (cached buffers may hold an earlier call's rows)
+            if self.autos is not None:   # behind the edits: the automata write the edits' masks, and arm a mask part where none is set
+                distinct = {id(a): a for a in self.autos if a is not None}
+                m.set_batch_automata(self.max_batch, sum(a.words().size for a in distinct.values()))
             if self.cnts is not None:
                 m.set_batch_count_penalty(self.max_batch)
                 m.write_batch_count_penalty(every, [None] * self.max_batch)   # (cached buffers may hold an earlier call's rows)
@@ -269,7 +292,7 @@ class _RowSeats:
         return self
 
     def __exit__(self, *exc) -> None:
-        for asked, clear in ((self.tails, "clear_batch_tail"), (self.edits, "clear_batch_edits"), (self.cnts, "clear_batch_count_penalty"),
+        for asked, clear in ((self.autos, "clear_batch_automata"), (self.tails, "clear_batch_tail"), (self.edits, "clear_batch_edits"), (self.cnts, "clear_batch_count_penalty"),
                              (self.drys, "clear_batch_dry_penalty"), (self.xtcs, "clear_batch_xtc"),
                              (self.tops, "clear_batch_top_logprobs")):
             if asked is not None:
@@ -296,6 +319,17 @@ class _RowSeats:
             if changed:
                 count.index_copy_(0, torch.tensor(changed, dtype=torch.long, device=count.device),
                                   torch.tensor([want_c[s_] for s_ in changed], dtype=torch.int32, device=count.device))
+        if self.autos is not None:
+            # a row's automaton record and state are rewritten where its sampler record is: when its occupant changes, the state being the
+            # automaton's walk over the ids the request has generated so far (the last of them is the row's input).  A row a request keeps
+            # is left alone: the pass advanced its state on the device.  A prompt that is still filling, and a request without an
+            # automaton, hold a zero record.  In front of the edits: a row that loses its automaton loses the mask it wrote.
+            autos = self.autos
+            want = [None if r is None or autos[r] is None else (r, len(gen_by.get(r, []))) for r in rows]
+            a_rows = self._changed(self.aseats, want)
+            moved = [want[s_] for s_ in a_rows]
+            self.model.write_batch_automata(a_rows, [None if w is None else autos[w[0]] for w in moved],
+                                            [None if w is None else autos[w[0]].walk(gen_by.get(w[0], [])) for w in moved])
         if edits is not None:
             # a row's mask and bias table are rewritten where its record is: when its occupant changes.  A callable mask is evaluated for
             # every live row, every pass, on what the request has been fed -- the loop's read-back already brought the tokens -- and the
@@ -367,8 +401,9 @@ class _RowSeats:
         own, or wants log-probabilities: then it is a batch of one.  Frequency / presence penalties alone do not make it one: a request's
         first token is chosen against empty counts, which is the unpenalised row, so the greedy prompt pass gives the token the
         penalised one would; the request's row of the counting state is written when it first sits in a pass (`seat`).  A DRY penalty
-        does make it one: the first token is chosen against the prompt's own window."""
-        return self.tops is None and (self.drys is None or self.drys[idx] is None) and (self.tails is None or self.tails[0][idx].tailless) and (self.edits is None or self.edits[idx] == (None, None))
+        does make it one: the first token is chosen against the prompt's own window.  So does a token automaton: the first token is chosen
+        under the start state's mask."""
+        return self.tops is None and (self.autos is None or self.autos[idx] is None) and (self.drys is None or self.drys[idx] is None) and (self.tails is None or self.tails[0][idx].tailless) and (self.edits is None or self.edits[idx] == (None, None))
 
     def records(self, n_rows: int):
         """The last pass's top-n records of output rows [0, n_rows) as one fresh int32 [n_rows, 2 (n + 1)] tensor (ids, then the values'
@@ -454,7 +489,7 @@ class BatchedEngine:
 
     def _run(self, prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores):
         """generate's body; scores: the call's _PromptScores or None."""
-        tops = edits = cnts = drys = xtcs = None
+        tops = edits = cnts = drys = xtcs = autos = None
         if logprobs:
             if self.sampler is not None:
                 raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
@@ -474,6 +509,8 @@ class BatchedEngine:
             for sp, sd in zip(params, seeds):
                 sp.record(0, sd)              # every request's arguments are checked before anything runs
                 sp.count_penalties()          # (the record knows nothing of these two: their own range check)
+            if any(sp.token_automaton is not None for sp in params):   # the per-row automaton records are armed only when some request asks for them
+                autos = [sp.automaton(self.model.args.vocab_size) for sp in params]
             if any(sp.token_mask is not None or sp.logit_bias is not None for sp in params):
                 edits = [sp.edits(self.model.args.vocab_size) for sp in params]
             if any(sp.counted for sp in params):   # the per-row counting state is armed only when some request asks for it
@@ -488,7 +525,7 @@ class BatchedEngine:
                 sampling = None               # no record to configure: a request with only a mask, a bias or count penalties arms no batch tail
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops, drys, xtcs) as seats:
+        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops, drys, xtcs, autos) as seats:
             out = self._generate(prompts, max_new_tokens, seats, scores)
         return out if tops is None else (out, seats.maps)
 

@@ -19,7 +19,7 @@ from .. import hip_ops
 from ..cache import BaseCache, PromptCache, QuantizedKVCache, ReusableKVCache, RotatingKVCache
 from ..cache.kv_cache import PagedKVCache
 from ..cache.kv_cache.quantized import check_format as check_kv_format
-from ..logits_processors import check_vocab, count_penalty_logits_processor, dry_logits_processor, make_logit_bias, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
+from ..logits_processors import check_vocab, count_penalty_logits_processor, dry_logits_processor, make_logit_bias, make_token_automaton, make_token_mask, packed_token_mask, repetition_penalty_logits_processor
 from ..models import load
 from ..samplers import make_sampler
 
@@ -82,11 +82,15 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
     sub-sequence of (one token mask, one repetition penalty, one logit bias, one frequency / presence penalty, one DRY penalty) in that
     order -- the order the kernels define -- and
     fused_tail_spec's other conditions hold: no structuring engine, a repetition context of 1..1024, a greedy or `hip_spec` sampler,
-    no tensor parallelism."""
+    no tensor parallelism.  A token automaton's processor (make_token_automaton) is a kind of its own, in the mask's
+    position: plan["automaton"] carries it, and a list that holds it together with a token mask is a ValueError -- the automaton writes
+    the step's mask."""
     kinds = []
     for proc in list(processors or []):
         if hasattr(proc, "mask_fn") and hasattr(proc, "mask"):
             kinds.append("mask")
+        elif hasattr(proc, "automaton"):
+            kinds.append("automaton")
         elif hasattr(proc, "penalty") and hasattr(proc, "context_size"):
             kinds.append("penalty")
         elif hasattr(proc, "ids") and hasattr(proc, "values"):
@@ -97,7 +101,9 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
             kinds.append("dry")
         else:
             return None
-    order = [("mask", "penalty", "bias", "counts", "dry").index(k) for k in kinds]
+    if "mask" in kinds and "automaton" in kinds:
+        raise ValueError("a token mask and a token automaton are exclusive: the automaton derives the mask itself")
+    order = [("mask", "penalty", "bias", "counts", "dry").index("mask" if k == "automaton" else k) for k in kinds]
     if any(b <= a for a, b in zip(order, order[1:])):  # out of order, or one kind twice
         return None
     by_kind = dict(zip(kinds, list(processors or [])))
@@ -111,6 +117,8 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
         plan["counts"] = by_kind["counts"]
     if "dry" in by_kind:
         plan["dry"] = by_kind["dry"]
+    if "automaton" in by_kind:
+        plan["automaton"] = by_kind["automaton"]
     return plan
 
 
@@ -160,7 +168,8 @@ class SpeculativeParams:
 
 def check_speculative(model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size) -> None:
     """What generate_step(speculative=...) refuses, each by name: speculation here is greedy and raw, on one sequence's 16-bit cache."""
-    for bad, name in ((not getattr(sampler, "is_greedy", False), "a non-greedy sampler (temp > 0)"), (bool(processors), "logits processors"),
+    for bad, name in ((not getattr(sampler, "is_greedy", False), "a non-greedy sampler (temp > 0)"),
+                      (any(hasattr(p, "automaton") for p in processors or []), "a token automaton"), (bool(processors), "logits processors"),
                       (structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
                       (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"),
                       (getattr(model, "tp", None) is not None, "a tensor-parallel model"),
@@ -187,7 +196,7 @@ def check_speculative_tail(model, sampler, processors, structuring_engine, pixel
     if plan is None:
         raise ValueError("speculative decoding under a configured tail is not available with a sampler or logits processors outside the fused tail plan "
                          "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
-    for key, name in (("mask", "a token mask"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
+    for key, name in (("mask", "a token mask"), ("automaton", "a token automaton"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
         if plan.get(key) is not None:
             raise ValueError(f"speculative decoding under a configured tail is not available with {name}")
     if not hasattr(model, "spec_step_tail") or not hasattr(model, "set_step_tail"):
@@ -222,7 +231,7 @@ def check_speculative_draft(model, draft_model, sampler, processors, structuring
     if plan is None:
         raise ValueError("speculative decoding with a draft model is not available with a sampler or logits processors outside the fused tail plan "
                          "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
-    for key, name in (("xtc", "XTC"), ("mask", "a token mask"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
+    for key, name in (("xtc", "XTC"), ("mask", "a token mask"), ("automaton", "a token automaton"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
         if plan.get(key) is not None:
             raise ValueError(f"speculative decoding with a draft model is not available with {name}")
     return plan
@@ -279,6 +288,8 @@ class InferenceEngine:
         """inference_engine.py:319-335: [PSE process_logits] + optional repetition penalty; around it the two processors DESIGN.md 12
         defines -- [token mask] in front (where the PSE's masking stands), [logit bias] behind (logit_processor_factory.cpp's order).
         token_mask: packed words, a bool mask or a callable tokens -> mask (make_token_mask); logit_bias: {token id: bias}.
+        token_automaton: a TokenAutomaton, where the token mask stands and exclusive with it -- a grammar whose state
+        lives on the device wherever the request takes the fused plan.
         frequency_penalty / presence_penalty (each -2.0 .. 2.0): one processor behind the bias, over the counts of the
         request's generated tokens.
         dry_multiplier != 0 (with dry_base, dry_allowed_length, dry_range, dry_sequence_breakers = token ids): the DRY
@@ -286,8 +297,12 @@ class InferenceEngine:
         procs: list[LogitsProcessor] = []
         if self.structuring_engine is not None:
             procs.append(self.structuring_engine.process_logits)
+        if kwargs.get("token_mask") is not None and kwargs.get("token_automaton") is not None:
+            raise ValueError("make_processors: token_mask and token_automaton are exclusive")
         if kwargs.get("token_mask") is not None:
             procs.append(make_token_mask(kwargs["token_mask"]))
+        if kwargs.get("token_automaton") is not None:
+            procs.append(make_token_automaton(kwargs["token_automaton"]))
         if kwargs.get("repetition_penalty", 1.0) != 1.0:
             procs.append(repetition_penalty_logits_processor(float(kwargs.get("repetition_penalty", 1.0)),
                                                              int(kwargs.get("context_size", 60))))
@@ -436,7 +451,12 @@ class InferenceEngine:
                          token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values),
                          **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}), **counts,
                          **({} if dry is None else {"dry": (dry.dry_multiplier, dry.dry_base, dry.dry_allowed_length, dry.dry_range, dry.dry_sequence_breakers)}),
-                         **({} if plan.get("xtc") is None else {"xtc": plan["xtc"]}))
+                         **({} if plan.get("xtc") is None else {"xtc": plan["xtc"]}),
+                         **({} if plan.get("automaton") is None else {"token_automaton": plan["automaton"].automaton}))
+                if plan.get("automaton") is not None and not fed_back:
+                    # the request's first call: the start state, in stream order.  From here on the state moves on the device by the
+                    # token each step feeds back: nothing is read back and no mask is uploaded
+                    self.model.reset_step_automaton()
                 if pixel_values is not None and not fed_back:
                     embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
                     tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)
@@ -499,8 +519,8 @@ class InferenceEngine:
                 self.prompt_cache.create_kv_cache(self.model)                  # :274-275
         for procs in self.logits_processors.values():
             for proc in procs:
-                if hasattr(proc, "frequency_penalty") and hasattr(proc, "reset"):
-                    proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts may not: this request's start
+                if (hasattr(proc, "frequency_penalty") or hasattr(proc, "automaton")) and hasattr(proc, "reset"):
+                    proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts and an automaton's walk may not: this request's start
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
         if speculative is not None and speculative.draft_model is not None:

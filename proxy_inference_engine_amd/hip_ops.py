@@ -532,6 +532,61 @@ def logits_bias(logits: torch.Tensor, ids: torch.Tensor, bias: torch.Tensor) -> 
     return logits
 
 
+# ---------------------------------------------------------------- token automaton (include/pie_hip.h: pie_row_dfa)
+DFA_WORDS = C.sizeof(_ffi.pie_row_dfa) // 4  # a record as int32 words: a device table is an int32 [rows, DFA_WORDS] tensor
+
+
+def token_dfa_records(records, device=None) -> torch.Tensor:
+    """Per-row automaton records as an int32 [rows, DFA_WORDS] tensor, on `device` when given.  An entry is (cls_off, trans_off, n_states,
+    n_classes) -- word offsets into the arena and the table's shape -- or None: the all-zero record of an unarmed row."""
+    rows = [(0, 0, 0, 0) if r is None else tuple(int(v) for v in r) for r in records]
+    if not rows or any(len(r) != DFA_WORDS or any(not -2 ** 31 <= v < 2 ** 31 for v in r) for r in rows):
+        raise ValueError("token_dfa_records: at least one entry, each None or (cls_off, trans_off, n_states, n_classes) of int32 values")
+    t = torch.tensor(rows, dtype=torch.int32)
+    return t if device is None else t.to(device)
+
+
+def _dfa_rows(who: str, records: torch.Tensor, states: torch.Tensor, tables: torch.Tensor) -> int:
+    for t in (records, states, tables):
+        _dev(t)
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f"{who}: records, states and tables are contiguous int32 device tensors")
+    rows = states.numel()
+    if records.numel() != rows * DFA_WORDS:
+        raise ValueError(f"{who}: records is int32 [rows, {DFA_WORDS}] (token_dfa_records) for states [rows]")
+    return rows
+
+
+def token_dfa_mask(records: torch.Tensor, states: torch.Tensor, tables: torch.Tensor, vocab_size: int, masks: torch.Tensor,
+                   mask_on: torch.Tensor | None = None) -> torch.Tensor:
+    """pie_token_dfa_mask: every armed row's token mask, derived from its state, into masks int32 [rows, words >= ceil(V / 32)] IN PLACE
+    (pack_token_mask's layout); mask_on int32 [rows] gets 1 for a row that was written and 0 for an armed row whose state has left the
+    automaton -- without mask_on such a row is written all-allowed.  An unarmed row is not touched.  Returns masks."""
+    rows = _dfa_rows("token_dfa_mask", records, states, tables)
+    _dev(masks)
+    if masks.dtype != torch.int32 or not masks.is_contiguous() or masks.dim() != 2 or masks.shape[0] != rows:
+        raise ValueError("token_dfa_mask: masks is a contiguous int32 [rows, words] device tensor")
+    if mask_on is not None:
+        _dev(mask_on)
+        if mask_on.dtype != torch.int32 or not mask_on.is_contiguous() or mask_on.numel() != rows:
+            raise ValueError("token_dfa_mask: mask_on is a contiguous int32 [rows] device tensor")
+    _ffi.check(_ffi.load().pie_token_dfa_mask(_ffi.p(records), _ffi.p(states), _ffi.p(tables), tables.numel(), rows, int(vocab_size), _ffi.p(masks),
+                                              masks.shape[1], _ffi.p(mask_on), _ffi.stream()))
+    return masks
+
+
+def token_dfa_advance(records: torch.Tensor, states: torch.Tensor, tables: torch.Tensor, vocab_size: int, tokens: torch.Tensor) -> torch.Tensor:
+    """pie_token_dfa_advance: every armed row's state moves by tokens[row] (device int32 [rows]) IN PLACE: the table's next state, -1 for
+    a token that is not allowed or not an id; a state outside the automaton stays what it is.  Returns states."""
+    rows = _dfa_rows("token_dfa_advance", records, states, tables)
+    _dev(tokens)
+    if tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.numel() != rows:
+        raise ValueError("token_dfa_advance: tokens is a contiguous int32 [rows] device tensor")
+    _ffi.check(_ffi.load().pie_token_dfa_advance(_ffi.p(records), _ffi.p(states), _ffi.p(tables), tables.numel(), rows, int(vocab_size), _ffi.p(tokens),
+                                                 _ffi.stream()))
+    return states
+
+
 def qkv_row_map(n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
     n = (n_heads + 2 * n_kv_heads) * head_dim
     arr = (C.c_int32 * n)()

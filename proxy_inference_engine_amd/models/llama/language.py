@@ -615,11 +615,11 @@ class Model(RowsTailState, StepTailState):
         (c = the samplers' position before the pass; the argmax under the greedy sampler), and the drafts are accepted while each equals
         the token of the row before it.  The same returns as spec_step; all m + 1 rows of the log-probabilities are written, and
         spec_logits() then holds the PROCESSED logits.  Afterwards the model, the cache, `fed_ids` and the samplers' stream are exactly
-        where n calls of step(None) under the same tail would have left them.  A token mask, top_logprobs, frequency / presence
+        where n calls of step(None) under the same tail would have left them.  A token mask, a token automaton, top_logprobs, frequency / presence
         penalties and DRY are refused by name, like tensor-parallel models, int8 pages and the other cache kinds."""
         who = "spec_step_tail"
         self._check_speculative_kv(who, cache)
-        for bad, name in ((self._edits[0], "a token mask"), (self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"),
+        for bad, name in ((self._edits[0], "a token mask"), (self._dfa is not None, "a token automaton"), (self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"),
                           (self._dry is not None, "a DRY penalty")):
             if bad:
                 raise ValueError(f"{who}: not available with {name}")

@@ -1,5 +1,5 @@
 """The per-row tail state of the multi-sequence passes (step_batch / prefill_batch / step_mixed), as `Model` owns it: sampler records and
-rings, top-n records, token masks and bias tables, frequency / presence counts, DRY records, and the prompt passes' log-probability records.  Every
+rings, top-n records, token masks and bias tables, frequency / presence counts, DRY records, token automata, and the prompt passes' log-probability records.  Every
 kind is a set_* / write_* / clear_* family over device buffers kept per rows_cap by one `RowsCapCache`."""
 from __future__ import annotations
 
@@ -54,7 +54,8 @@ class RowsTailState:
             "records": hip_ops.dry_penalty_records([hip_ops.dry_penalty_pack()] * r, dev), "breakers": i32((r, hip_ops.DRY_BREAKERS_MAX)),
             "recent": i32((r, hip_ops.RECENT_IDS))})
         self._batch_xtc_bufs = RowsCapCache(lambda r: {"records": torch.zeros((r, hip_ops.XTC_WORDS), dtype=torch.int32, device=dev)})
-        self._batch_tail = self._batch_edits = self._batch_counts = self._batch_dry = self._batch_xtc = None   # the armed buffers
+        self._batch_dfa_bufs = RowsCapCache(lambda r: {"records": i32((r, hip_ops.DFA_WORDS)), "states": i32(r), "tables": i32(1)})
+        self._batch_tail = self._batch_edits = self._batch_counts = self._batch_dry = self._batch_xtc = self._batch_dfa = None   # the armed buffers
         self._prompt_lp_ws = None      # (block_rows, its logits block + the op's workspace)
 
     # ------------------------------------------------------------------ the multi-sequence passes' tail
@@ -352,3 +353,91 @@ class RowsTailState:
         """The multi-sequence passes launch what they launched before set_batch_xtc; the buffers stay cached."""
         _ffi.check(_ffi.load().pie_decoder_set_batch_xtc(self._dec, None, 0))
         self._batch_xtc = None
+
+    # ------------------------------------------------------------------ the multi-sequence passes' token automata (DESIGN.md 22)
+    def set_batch_automata(self, rows_cap: int, tables_words: int) -> dict:
+        """From now on step_batch / prefill_batch / step_mixed derive the token mask of every armed output row from its automaton's state
+        and advance the state by the token the row drew (pie_decoder_set_batch_token_dfa): {"records": int32 [rows_cap, DFA_WORDS],
+        "states": int32 [rows_cap], "tables": the arena, int32 [>= tables_words]}, returned, owned by the model and kept per rows_cap (the
+        4 most recent; the arena grows to the largest size asked for and starts empty at every call).  The masks are the batch edits':
+        without a mask part set (set_batch_edits) this call sets one, and clear_batch_automata then clears it again.  Fresh records are
+        zero -- unarmed: such a row keeps the mask write_batch_edits gave it, or none -- until write_batch_automata arms a row."""
+        rows_cap, tables_words = int(rows_cap), int(tables_words)
+        if rows_cap < 1 or tables_words < 1:
+            raise ValueError("set_batch_automata: rows_cap >= 1 and tables_words >= 1")
+        own = self._batch_dfa_bufs.get(rows_cap)
+        if own["tables"].numel() < tables_words:
+            own["tables"] = torch.zeros(tables_words, dtype=torch.int32, device=self.device)
+        own["records"].zero_()
+        own["states"].zero_()
+        own.update(used=0, uploaded={}, armed=set(), own_edits=False)
+        be = self._batch_edits
+        if be is None or be["masks"] is None:
+            self.set_batch_edits(rows_cap if be is None else be["bias_n"].numel(), True, 0 if be is None else be["bias_ids"].shape[1])
+            own["own_edits"] = be is None
+            self._batch_edits["mask_on"].zero_()   # (cached buffers may hold an earlier call's rows)
+        _ffi.check(_ffi.load().pie_decoder_set_batch_token_dfa(self._dec, rows_cap, _ffi.p(own["records"]), _ffi.p(own["states"]), _ffi.p(own["tables"]),
+                                                               own["tables"].numel()))
+        self._batch_dfa = own
+        return own
+
+    def upload_automaton(self, automaton) -> tuple[int, int]:
+        """(cls_off, trans_off) of `automaton` (a logits_processors.TokenAutomaton) inside the armed arena, in words; every distinct
+        object is uploaded once, in stream order.  ValueError for another vocabulary and for an arena that cannot hold it."""
+        bd = self._batch_dfa
+        if bd is None:
+            raise RuntimeError("upload_automaton: no batch automata are set (set_batch_automata)")
+        hit = bd["uploaded"].get(id(automaton))
+        if hit is not None:
+            return hit[1], hit[2]
+        automaton.check_vocab(self.args.vocab_size)
+        words = torch.from_numpy(automaton.words())
+        at, n = bd["used"], words.numel()
+        if at + n > bd["tables"].numel():
+            raise ValueError(f"upload_automaton: the arena holds {bd['tables'].numel()} words, {at} of them used, and the automaton needs {n} (set_batch_automata's tables_words)")
+        bd["tables"][at:at + n].copy_(words)
+        bd["used"] = at + n
+        bd["uploaded"][id(automaton)] = (automaton, at, at + automaton.vocab_size)  # (the object is kept: its id stays its own)
+        return at, at + automaton.vocab_size
+
+    def write_batch_automata(self, rows: list[int], automata: list, states: list | None = None) -> None:
+        """Rewrites the records and the states of `rows` of the armed buffers, in stream order, one copy per array for all of them -- when
+        a row's occupant changes.  automata[i]: the TokenAutomaton of the occupant of rows[i] (uploaded when the arena does not hold it
+        yet), or None: a zero record -- a row without one, a prompt that is still filling.  states[i]: the state the row's next pass
+        masks with (automaton.walk(the ids the request has generated so far)); None: the start state.  A row that held an automaton and
+        loses it also gets mask_on = 0 -- the words its last pass wrote are stale: write_batch_edits for such a row comes after this call."""
+        bd = self._batch_dfa
+        if bd is None:
+            raise RuntimeError("write_batch_automata: no batch automata are set (set_batch_automata)")
+        if not rows:
+            return
+        if len(automata) != len(rows) or (states is not None and len(states) != len(rows)):
+            raise ValueError("write_batch_automata: one automaton and one state per row")
+        recs, sts = [], []
+        for i, a in enumerate(automata):
+            if a is None:
+                recs.append(None), sts.append(0)
+                continue
+            cls_off, trans_off = self.upload_automaton(a)
+            recs.append((cls_off, trans_off, a.n_states, a.n_classes))
+            sts.append(a.start if states is None or states[i] is None else int(states[i]))
+        idx = torch.tensor(rows, dtype=torch.long, device=self.device)
+        bd["records"].index_copy_(0, idx, hip_ops.token_dfa_records(recs, self.device))
+        bd["states"].index_copy_(0, idx, torch.tensor(sts, dtype=torch.int32, device=self.device))
+        lost = [r for r, a in zip(rows, automata) if a is None and r in bd["armed"]]
+        if lost and self._batch_edits is not None and self._batch_edits["mask_on"] is not None:
+            self._batch_edits["mask_on"].index_fill_(0, torch.tensor(lost, dtype=torch.long, device=self.device), 0)
+        bd["armed"].difference_update(lost)
+        bd["armed"].update(r for r, a in zip(rows, automata) if a is not None)
+
+    def clear_batch_automata(self) -> None:
+        """The multi-sequence passes launch what they launched before set_batch_automata; the buffers stay cached, the arena empty."""
+        bd = self._batch_dfa
+        _ffi.check(_ffi.load().pie_decoder_set_batch_token_dfa(self._dec, 0, None, None, None, 0))
+        self._batch_dfa = None
+        if bd is not None:
+            if bd["armed"] and self._batch_edits is not None and self._batch_edits["mask_on"] is not None:
+                self._batch_edits["mask_on"].index_fill_(0, torch.tensor(sorted(bd["armed"]), dtype=torch.long, device=self.device), 0)
+            bd.update(used=0, uploaded={}, armed=set())
+            if bd["own_edits"]:
+                self.clear_batch_edits()

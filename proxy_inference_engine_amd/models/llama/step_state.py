@@ -1,5 +1,5 @@
 """The tail state of the single-sequence step (step / step_embeds), as `Model` owns it: the sampler and the repetition penalty, the token
-mask and the bias table, the top-n record, frequency / presence counts, the DRY record and the XTC record.  Every part
+mask and the bias table, the top-n record, frequency / presence counts, the DRY record, the XTC record and the token automaton.  Every part
 lives in device buffers at stable addresses, made when first used: the library (csrc/decoder.hpp: StepTail) is asked only when a part is
 switched on or off or one of its launch arguments changes, and new contents are a copy in stream order -- a replay, not a re-capture."""
 from __future__ import annotations
@@ -10,7 +10,7 @@ from ... import _ffi, hip_ops
 
 # The step-tail surface: what a wrapper around a text tower forwards to it (models/intern/ensemble.py) -- all of these, and nothing else.
 STEP_TAIL_SURFACE = ("set_step_tail", "reset_step_counts", "step_tail", "step_tail_edits", "step_tail_counts", "step_tail_dry",
-                     "step_top_logprobs", "step_xtc_record")
+                     "step_top_logprobs", "step_xtc_record", "reset_step_automaton", "step_tail_automaton")
 
 
 class StepTailState:
@@ -26,16 +26,18 @@ class StepTailState:
         self._cnt, self._cnt_rec, self._cnt_counts = None, None, None
         self._dry, self._dry_rec, self._dry_brk = None, None, None
         self._xtc, self._xtc_rec = None, None
+        # the token automaton while the part is on, then its buffers: the arena (cls, then trans), the record, the state, the mask words it writes
+        self._dfa, self._dfa_arena, self._dfa_rec, self._dfa_state, self._dfa_mask = None, None, None, None, None
 
     @property
     def _step_tail_plain(self) -> bool:
         """Nothing but XTC is set: the step ends in the greedy tail over raw logits (XTC alone configures nothing, as in the library)."""
-        return self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None and self._cnt is None and self._dry is None
+        return self._tail[:2] == (None, None) and self._edits == (False, 0) and self._top_n is None and self._cnt is None and self._dry is None and self._dfa is None
 
     def set_step_tail(self, sampler: tuple | None = None, repetition_penalty: float = 1.0, context_size: int = 60,
                       token_mask=None, logit_bias=None, top_logprobs: int | None = None, frequency_penalty: float = 0.0,
                       presence_penalty: float = 0.0, count_start: int | None = None, dry: tuple | None = None,
-                      xtc: tuple | None = None, rng: tuple | None = None) -> None:
+                      xtc: tuple | None = None, rng: tuple | None = None, token_automaton=None) -> None:
         """What `step` / `step_embeds` end in (pie_decoder_set_logits_penalty / _set_sampler / _set_logits_mask / _set_logit_bias;
         DESIGN.md 10, 12), inside the replayed graph:
         sampler None = the greedy argmax, or (mode, temp, p, k) as hip_ops.sample takes them (make_sampler's `hip_spec`), drawn from
@@ -62,11 +64,21 @@ class StepTailState:
         the top choices with the given probability; the returned logits, logprobs and top-n record stay those before XTC.  Ignored without
         a sampler (a greedy tail), and a probability of 0 is off.  The model owns one record at a stable address (`step_xtc_record`): new
         values are a copy and a replay, not a re-capture.
+        token_automaton: None (off) or a logits_processors.TokenAutomaton -- the step derives its token mask from the
+        automaton's state on the device and advances the state by the token it feeds back, inside the replayed graph: no mask is uploaded
+        and no token is read back.  Exclusive with token_mask.  The model owns the arena, the record, the state and the mask words at
+        stable addresses: a new automaton that fits the arena is a copy and a state reset -- a replay, not a re-capture; the same object
+        again changes nothing, the state included (reset_step_automaton rewrites it).
         rng: None = samplers' random stream, or (seed, counter int64 [2] device) -- a stream of the caller's own: a draft model draws
         under samplers._rng.draft_state, never under the target's seed.
         The defaults restore the documented greedy contract.  A no-op when nothing changed (a new seed is a change).  `__call__` keeps
         returning raw logits."""
+        if token_mask is not None and token_automaton is not None:
+            raise ValueError("set_step_tail: token_mask and token_automaton are exclusive -- the automaton writes the step's mask")
+        if token_automaton is None:  # off before a mask goes on, on after a mask went off: the library refuses the two together
+            self._set_tail_automaton(None)
         self._set_tail_edits(token_mask, logit_bias)
+        self._set_tail_automaton(token_automaton)
         self._set_tail_top_logprobs(top_logprobs)
         self._set_tail_counts(frequency_penalty, presence_penalty, count_start)
         self._set_tail_dry(dry)
@@ -210,6 +222,50 @@ class StepTailState:
         if (xtc is None) != (self._xtc is None):  # switched on or off
             _ffi.check(_ffi.load().pie_decoder_set_xtc(self._dec, _ffi.p(self._xtc_rec) if xtc is not None else None))
         self._xtc = xtc
+
+    def _set_tail_automaton(self, automaton) -> None:
+        """The automaton's words into the model's arena; the library is asked only when the part is switched on or off or the arena has to
+        grow (the record's, the state's and the mask words' addresses never change)."""
+        if automaton is self._dfa:
+            return
+        lib = _ffi.load()
+        if automaton is None:
+            _ffi.check(lib.pie_decoder_set_token_dfa(self._dec, None, None, None, 0, None, 0))
+            self._dfa = None
+            return
+        from ...logits_processors.token_automaton import TokenAutomaton
+        if not isinstance(automaton, TokenAutomaton):
+            raise ValueError("set_step_tail: token_automaton is a logits_processors.TokenAutomaton")
+        V = self.logprobs.numel()
+        automaton.check_vocab(V)
+        words = torch.from_numpy(automaton.words())
+        if self._dfa_rec is None:
+            self._dfa_rec = torch.zeros((1, hip_ops.DFA_WORDS), dtype=torch.int32, device=self.device)
+            self._dfa_state = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._dfa_mask = torch.zeros((V + 31) // 32, dtype=torch.int32, device=self.device)
+        grown = self._dfa_arena is None or words.numel() > self._dfa_arena.numel()
+        if grown:
+            self._dfa_arena = torch.zeros(words.numel(), dtype=torch.int32, device=self.device)
+        self._dfa_arena[:words.numel()].copy_(words)
+        self._dfa_rec.copy_(hip_ops.token_dfa_records([(0, V, automaton.n_states, automaton.n_classes)]))
+        if grown or self._dfa is None:
+            _ffi.check(lib.pie_decoder_set_token_dfa(self._dec, _ffi.p(self._dfa_rec), _ffi.p(self._dfa_state), _ffi.p(self._dfa_arena), self._dfa_arena.numel(),
+                                                     _ffi.p(self._dfa_mask), self._dfa_mask.numel()))
+        self._dfa = automaton
+        self.reset_step_automaton()
+
+    def reset_step_automaton(self, state: int | None = None) -> None:
+        """The automaton's state is rewritten in stream order: `state`, or the start state -- at a request's start, and after a cache was
+        trimmed (state = automaton.walk(the ids generated so far))."""
+        if self._dfa is None:
+            raise RuntimeError("reset_step_automaton: set_step_tail(token_automaton=...) first")
+        self._dfa_state.fill_(self._dfa.start if state is None else int(state))
+
+    @property
+    def step_tail_automaton(self) -> tuple:
+        """(the automaton or None, the state): the state is a device view (int32 [1]) of what the next step will mask with (None before the
+        feature was first used)."""
+        return self._dfa, self._dfa_state
 
     def reset_step_counts(self, start: int, generated_ids=()) -> None:
         """The step's frequency / presence counting starts afresh, in stream order: the counts become the multiplicities of
