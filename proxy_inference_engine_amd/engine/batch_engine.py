@@ -78,15 +78,9 @@ class SamplingParams:
 
     def hip_spec(self) -> tuple | None:
         """None (greedy) or (mode, temp, p, k) as hip_ops.sample / row_tail_pack take them."""
-        if self.temp == 0:
-            return None
-        if 0 < self.top_p < 1.0:
-            return ("top_p", float(self.temp), float(self.top_p), 0)
-        if self.min_p != 0.0:
-            return ("min_p", float(self.temp), float(self.min_p), int(self.min_tokens_to_keep))
-        if self.top_k > 0:
-            return ("top_k", float(self.temp), 0.0, int(self.top_k))
-        return ("categorical", float(self.temp), 0.0, 0)
+        from ..samplers import sampler_spec
+        spec = sampler_spec(self.temp, self.top_p, self.min_p, self.min_tokens_to_keep, self.top_k)
+        return None if spec is None else (spec[0], float(spec[1]), float(spec[2]), int(spec[3]))
 
     @property
     def recordless(self) -> bool:

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from collections.abc import Callable, Generator, Iterator
 from dataclasses import dataclass
+from functools import partial
 
 import torch
 
@@ -113,12 +114,9 @@ def fused_tail_plan(processors, sampler, structuring_engine=None, tensor_paralle
     plan = dict(sampler=spec[0], repetition_penalty=spec[1], context_size=spec[2], mask=by_kind.get("mask"), bias=by_kind.get("bias"))
     if spec[0] is not None and getattr(sampler, "hip_xtc", None) is not None:  # XTC rides the sampler's launches
         plan["xtc"] = tuple(sampler.hip_xtc)
-    if "counts" in by_kind:  # (a request without the penalties gets the plan it always got)
-        plan["counts"] = by_kind["counts"]
-    if "dry" in by_kind:
-        plan["dry"] = by_kind["dry"]
-    if "automaton" in by_kind:
-        plan["automaton"] = by_kind["automaton"]
+    for kind in ("counts", "dry", "automaton"):  # (a request without them gets the plan it always got)
+        if kind in by_kind:
+            plan[kind] = by_kind[kind]
     return plan
 
 
@@ -166,16 +164,40 @@ class SpeculativeParams:
             raise ValueError("SpeculativeParams: configured_tail is a bool")
 
 
+def _speculative_environment(model, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs=None) -> list:
+    """The (refused, name) rows every kind of speculation shares: it runs on one sequence's 16-bit cache, without host hooks."""
+    return [(structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
+            (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"), (prompt_logprobs is not None, "prompt_logprobs"),
+            (getattr(model, "tp", None) is not None, "a tensor-parallel model"),
+            (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")]
+
+
+def _refuse(what: str, rows) -> None:
+    """ValueError for the first refused row: '`what` is not available with `name`'."""
+    for bad, name in rows:
+        if bad:
+            raise ValueError(f"{what} is not available with {name}")
+
+
+def _speculative_plan(what: str, model, sampler, processors, structuring_engine, refused_parts) -> dict:
+    """The request's fused tail plan for a kind of speculation whose passes run a configured tail: ValueError when there is none, or
+    when it holds one of refused_parts ((plan key, name) rows)."""
+    plan = fused_tail_plan(processors, sampler, structuring_engine, getattr(model, "tp", None) is not None)
+    if plan is None:
+        raise ValueError(f"{what} is not available with a sampler or logits processors outside the fused tail plan "
+                         "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
+    _refuse(what, ((plan.get(key) is not None, name) for key, name in refused_parts))
+    return plan
+
+
+_PASS_REFUSED_PARTS = (("mask", "a token mask"), ("automaton", "a token automaton"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty"))
+
+
 def check_speculative(model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size) -> None:
     """What generate_step(speculative=...) refuses, each by name: speculation here is greedy and raw, on one sequence's 16-bit cache."""
-    for bad, name in ((not getattr(sampler, "is_greedy", False), "a non-greedy sampler (temp > 0)"),
-                      (any(hasattr(p, "automaton") for p in processors or []), "a token automaton"), (bool(processors), "logits processors"),
-                      (structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
-                      (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"),
-                      (getattr(model, "tp", None) is not None, "a tensor-parallel model"),
-                      (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")):
-        if bad:
-            raise ValueError(f"speculative decoding is not available with {name}")
+    _refuse("speculative decoding", [(not getattr(sampler, "is_greedy", False), "a non-greedy sampler (temp > 0)"),
+                                     (any(hasattr(p, "automaton") for p in processors or []), "a token automaton"), (bool(processors), "logits processors")]
+            + _speculative_environment(model, structuring_engine, pixel_values, kv_bits, max_kv_size))
     if not hasattr(model, "spec_step"):
         raise ValueError("speculative decoding is not available with this model (no spec_step)")
 
@@ -185,20 +207,8 @@ def check_speculative_tail(model, sampler, processors, structuring_engine, pixel
     plan of what it accepts: a greedy or `hip_spec` sampler (XTC included), the repetition penalty and the logit bias.  A token mask,
     frequency / presence penalties and DRY stay out of the passes, like everything check_speculative refuses besides the sampler and the
     processors."""
-    tp = getattr(model, "tp", None) is not None
-    for bad, name in ((structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
-                      (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"), (prompt_logprobs is not None, "prompt_logprobs"),
-                      (tp, "a tensor-parallel model"),
-                      (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")):
-        if bad:
-            raise ValueError(f"speculative decoding is not available with {name}")
-    plan = fused_tail_plan(processors, sampler, structuring_engine, tp)
-    if plan is None:
-        raise ValueError("speculative decoding under a configured tail is not available with a sampler or logits processors outside the fused tail plan "
-                         "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
-    for key, name in (("mask", "a token mask"), ("automaton", "a token automaton"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
-        if plan.get(key) is not None:
-            raise ValueError(f"speculative decoding under a configured tail is not available with {name}")
+    _refuse("speculative decoding", _speculative_environment(model, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs))
+    plan = _speculative_plan("speculative decoding under a configured tail", model, sampler, processors, structuring_engine, _PASS_REFUSED_PARTS)
     if not hasattr(model, "spec_step_tail") or not hasattr(model, "set_step_tail"):
         raise ValueError("speculative decoding under a configured tail is not available with this model (no spec_step_tail)")
     return plan
@@ -209,13 +219,10 @@ def check_speculative_draft(model, draft_model, sampler, processors, structuring
     what it accepts -- None for a greedy request without processors, whose passes are Model.spec_step's.  Besides what
     check_speculative_tail refuses: XTC (its coin changes the target's distribution from call to call), a draft model of another
     vocabulary, a tensor-parallel draft model."""
-    tp = getattr(model, "tp", None) is not None
-    for bad, name in ((structuring_engine is not None, "a structuring engine"), (pixel_values is not None, "pixel_values"),
-                      (kv_bits is not None, "kv_bits"), (max_kv_size is not None, "max_kv_size"), (prompt_logprobs is not None, "prompt_logprobs"),
-                      (tp, "a tensor-parallel model"), (getattr(draft_model, "tp", None) is not None, "a tensor-parallel draft model"),
-                      (getattr(getattr(model, "_page_pool", None), "dtype", None) == torch.int8, "int8 KV pages")):
-        if bad:
-            raise ValueError(f"speculative decoding with a draft model is not available with {name}")
+    what = "speculative decoding with a draft model"
+    rows = _speculative_environment(model, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs)
+    rows.insert(-1, (getattr(draft_model, "tp", None) is not None, "a tensor-parallel draft model"))  # (the KV pages' row stays the last)
+    _refuse(what, rows)
     if not hasattr(model, "spec_step_draft") or not hasattr(model, "set_step_tail"):
         raise ValueError("speculative decoding with a draft model is not available with this model (no spec_step_draft)")
     if not all(hasattr(draft_model, a) for a in ("step", "set_step_tail", "history", "logprobs")):
@@ -227,14 +234,47 @@ def check_speculative_draft(model, draft_model, sampler, processors, structuring
         raise ValueError(f"speculative decoding with a draft model: a vocabulary mismatch (the target has {v_t} ids, the draft model {v_d})")
     if getattr(sampler, "is_greedy", False) and not processors:
         return None
-    plan = fused_tail_plan(processors, sampler, structuring_engine, tp)
-    if plan is None:
-        raise ValueError("speculative decoding with a draft model is not available with a sampler or logits processors outside the fused tail plan "
-                         "(make_sampler's samplers; one repetition penalty with a context of 1..1024, one logit bias)")
-    for key, name in (("xtc", "XTC"), ("mask", "a token mask"), ("automaton", "a token automaton"), ("counts", "frequency / presence penalties"), ("dry", "a DRY penalty")):
-        if plan.get(key) is not None:
-            raise ValueError(f"speculative decoding with a draft model is not available with {name}")
-    return plan
+    return _speculative_plan(what, model, sampler, processors, structuring_engine, (("xtc", "XTC"),) + _PASS_REFUSED_PARTS)
+
+
+def _speculative_request_plan(model, draft_model, sp: SpeculativeParams, samplers: dict, logits_processors: dict, structuring_engine,
+                              pixel_values, kv_bits, max_kv_size):
+    """Which of the three checks a generate_step(speculative=sp) request goes through, and the plan its passes run under (None: greedy
+    and raw).  draft_model: sp.draft_model as a built Model, or None."""
+    sampler, root = samplers["root"], logits_processors.get("root") or []
+    if draft_model is not None:
+        return check_speculative_draft(model, draft_model, sampler, root, structuring_engine, pixel_values, kv_bits, max_kv_size)
+    all_procs = [p for ps in logits_processors.values() for p in ps]
+    if sp.configured_tail and not (getattr(sampler, "is_greedy", False) and not all_procs):
+        return check_speculative_tail(model, sampler, root, structuring_engine, pixel_values, kv_bits, max_kv_size)
+    # (a greedy request without processors under configured_tail=True: the greedy path)
+    check_speculative(model, sampler, all_procs, structuring_engine, pixel_values, kv_bits, max_kv_size)
+    return None
+
+
+def _check_generate_args(model, pixel_values, mask, kv_bits, kv_group_size, max_kv_size, top_logprobs, prompt_logprobs, speculative) -> None:
+    """What generate_step refuses in its arguments, before it touches the prompt cache or the model."""
+    scored = prompt_logprobs is not None
+    if speculative is not None and scored:
+        raise ValueError("speculative decoding is not available with prompt_logprobs")
+    if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
+        raise ValueError(f"prompt_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
+    if scored and getattr(model, "tp", None) is not None:
+        raise ValueError("prompt_logprobs: not available on a tensor-parallel model")
+    if top_logprobs is not None and not 0 <= int(top_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
+    if kv_bits is not None:
+        check_kv_format(kv_group_size, kv_bits)
+    if max_kv_size is not None:
+        RotatingKVCache(max_kv_size, keep=4)  # ValueError for a window that cannot hold the 4 sink rows plus one
+        if getattr(model, "_page_pool", None) is not None:
+            raise ValueError("max_kv_size: a rotating KV cache runs on contiguous buffers, not on the model's KV pages")
+        if getattr(model, "tp", None) is not None:
+            raise ValueError("max_kv_size: a rotating KV cache is not available on a tensor-parallel model")
+    if mask is not None and not (isinstance(mask, str) and mask == "causal"):
+        check_generate_mask(mask, getattr(getattr(model, "args", None), "num_attention_heads", None))
+    if pixel_values is not None and not hasattr(model, "get_input_embeddings"):
+        raise TypeError("pixel_values need a VLM ensemble (models/intern/ensemble.py: Model) as the engine's model")
 
 
 class InferenceEngine:
@@ -355,159 +395,49 @@ class InferenceEngine:
         fused tail plan holds besides a token mask, counts and DRY: the request's sampler, repetition penalty and logit bias run inside
         the passes, token j is draw j of the samplers' seed from row j's distribution, and the yielded rows are the processed
         log-probabilities."""
+        _check_generate_args(self.model, pixel_values, mask, kv_bits, kv_group_size, max_kv_size, top_logprobs, prompt_logprobs, speculative)
         scored = prompt_logprobs is not None
-        if speculative is not None and scored:
-            raise ValueError("speculative decoding is not available with prompt_logprobs")
-        if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
-            raise ValueError(f"prompt_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
-        if scored and getattr(self.model, "tp", None) is not None:
-            raise ValueError("prompt_logprobs: not available on a tensor-parallel model")
-        self.prompt_logprobs = None
-        if top_logprobs is not None and not 0 <= int(top_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:
-            raise ValueError(f"top_logprobs must be 0..{hip_ops.TOP_LOGPROBS_MAX}")
-        self.top_record = None
-        host_top: list = []   # [(ids, vals), workspace] of the host-orchestrated branches' top-n record
-        if kv_bits is not None:
-            check_kv_format(kv_group_size, kv_bits)
-        if max_kv_size is not None:
-            RotatingKVCache(max_kv_size, keep=4)  # ValueError for a window that cannot hold the 4 sink rows plus one
-            if getattr(self.model, "_page_pool", None) is not None:
-                raise ValueError("max_kv_size: a rotating KV cache runs on contiguous buffers, not on the model's KV pages")
-            if getattr(self.model, "tp", None) is not None:
-                raise ValueError("max_kv_size: a rotating KV cache is not available on a tensor-parallel model")
-        if mask is not None and not (isinstance(mask, str) and mask == "causal"):
-            check_generate_mask(mask, getattr(getattr(self.model, "args", None), "num_attention_heads", None))
-        if pixel_values is not None and not hasattr(self.model, "get_input_embeddings"):
-            raise TypeError("pixel_values need a VLM ensemble (models/intern/ensemble.py: Model) as the engine's model")
+        self.prompt_logprobs = self.top_record = None
         if "root" not in self.samplers:
             self.prepare_engine(prompt_ids, temp=0)
         spec_plan = None
+        if speculative is not None:
+            spec_plan = _speculative_request_plan(self.model, None if speculative.draft_model is None else self._draft_model(speculative), speculative,
+                                                  self.samplers, self.logits_processors, self.structuring_engine, pixel_values, kv_bits, max_kv_size)
+        self._select_prompt_cache(prompt_ids, max_kv_size, scored)
+        todo = self.prompt_cache(prompt_ids)                                   # :277
+        host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
         if speculative is not None and speculative.draft_model is not None:
-            spec_plan = check_speculative_draft(self.model, self._draft_model(speculative), self.samplers["root"], self.logits_processors.get("root") or [],
-                                                self.structuring_engine, pixel_values, kv_bits, max_kv_size)
-        elif speculative is not None:
-            all_procs = [p for ps in self.logits_processors.values() for p in ps]
-            if speculative.configured_tail and not (getattr(self.samplers["root"], "is_greedy", False) and not all_procs):
-                spec_plan = check_speculative_tail(self.model, self.samplers["root"], self.logits_processors.get("root") or [], self.structuring_engine,
-                                                   pixel_values, kv_bits, max_kv_size)
-            else:  # (a greedy request without processors under configured_tail=True: today's greedy path)
-                check_speculative(self.model, self.samplers["root"], all_procs, self.structuring_engine, pixel_values, kv_bits, max_kv_size)
-        dev = self.model.device
+            yield from self._speculative_draft_steps([int(t) for t in prompt_ids], host_ids, speculative, top_logprobs, spec_plan)
+            return
+        if speculative is not None:
+            yield from self._speculative_steps(host_ids, speculative, top_logprobs, spec_plan)
+            return
+        # what every step of this request is called with; host_top: [(ids, vals), workspace] of the host-orchestrated branches' top-n record
+        request = dict(pixel_values=pixel_values, kv_quant=None if kv_bits is None else (quantized_kv_start, kv_group_size, kv_bits),
+                       top_logprobs=top_logprobs, count_start=len(prompt_ids), host_top=[])
+        if scored and len(host_ids) > 1:
+            lm = getattr(self.model, "language_model", self.model)
+            bufs = lm.set_prompt_logprobs(len(host_ids), max(int(prompt_logprobs), 1))
+            targets, counts = prompt_targets(host_ids, int(prompt_logprobs))
+            bufs["targets"].copy_(torch.tensor(targets, dtype=torch.int32))
+            bufs["count"].copy_(torch.tensor(counts, dtype=torch.int32))
+            try:
+                next_token, logprobs = self._inference(torch.tensor(host_ids, dtype=torch.int32), False, **request)
+            finally:
+                lm.clear_prompt_logprobs()
+            self.prompt_logprobs = prompt_maps(bufs["ids"].cpu().numpy(), bufs["vals"].cpu().numpy(), int(prompt_logprobs))
+        else:
+            if scored:
+                self.prompt_logprobs = [None]
+            next_token, logprobs = self._inference(torch.tensor(host_ids, dtype=torch.int32), False, **request)   # :278 (host ids: no read-back)
+        while True:
+            yield next_token, logprobs
+            next_token, logprobs = self._inference(next_token, True, **request)   # :288
 
-        def _inference(ids: torch.Tensor, fed_back: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
-            """_forward, then the top-n record of a host-orchestrated branch (the fused plan's is written inside the step)."""
-            self.top_record = None
-            tok, logprobs = _forward(ids, fed_back)
-            if top_logprobs is not None and self.top_record is None:
-                n = max(int(top_logprobs), 1)
-                if not host_top:  # this generation's own record and workspace, made once: the branch allocates nothing per token
-                    host_top.append((torch.full((1, n + 1), -1, dtype=torch.int32, device=logprobs.device),
-                                     torch.full((1, n + 1), float("-inf"), dtype=torch.float32, device=logprobs.device)))
-                    host_top.append(hip_ops.top_logprobs_workspace(logprobs.device, 1, logprobs.numel(), n))
-                rec_ids, rec_vals = hip_ops.top_logprobs(logprobs.reshape(1, -1), n, tokens=tok.reshape(1).to(torch.int32), workspace=host_top[1], out=host_top[0])
-                self.top_record = (rec_ids[0, :int(top_logprobs) + 1], rec_vals[0, :int(top_logprobs) + 1])
-            return tok, logprobs
-
-        def _forward(ids: torch.Tensor, fed_back: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
-            """One forward + tail.  fed_back: `ids` is the token the previous call returned (still in the decoder's
-            device-side state), so nothing has to be copied or read back."""
-            state = "root"
-            if self.structuring_engine is not None:
-                state = self.structuring_engine.get_current_state() or "root"
-                if state not in self.logits_processors:
-                    state = "root"
-            sampler = self.samplers[state]
-            procs = self.logits_processors.get(state) or []
-            if kv_bits is not None:
-                self._maybe_quantize(quantized_kv_start, kv_group_size, kv_bits)
-            set_tail = getattr(self.model, "set_step_tail", None)
-            plan = fused_tail_plan(procs, sampler, self.structuring_engine, getattr(self.model, "tp", None) is not None) if set_tail is not None else None
-            offset = int(self.prompt_cache.cache[0].offset) if self.prompt_cache.cache else 0
-            if plan is not None and offset + int(ids.numel()) <= self.model.fed_ids.numel():
-                # The whole tail inside the step (DESIGN.md 10, 12): mask, penalty, bias, log-softmax and the draw ride the replayed graph; the
-                # drawn token is fed back on the device, so a fed-back step passes nothing, whatever the sampler
-                dry = plan.get("dry")
-                window = max(plan["context_size"] if plan["repetition_penalty"] != 1.0 else 0, 0 if dry is None else dry.dry_range)  # the fed ids a tail reads
-                if window and not fed_back and offset > 0:  # a reused prefix: its ids may predate this configuration (fed back unrecorded, loaded from disk)
-                    seen = self.prompt_cache.computed_ids[-min(offset, window):]
-                    self.model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
-                mask, bias, recorded = plan["mask"], plan["bias"], False
-                vocab = getattr(self.model, "language_model", self.model).logprobs.numel()
-                words = None
-                if mask is not None:
-                    check_vocab(mask, vocab)
-                    words = mask.mask  # (static host words: set_step_tail refuses a mask that allows no token when it uploads them)
-                if mask is not None and mask.mask_fn is not None:
-                    # a grammar's mask depends on the tokens so far, this row's input included (the processors run after :255): the one
-                    # read-back of the fed-back token such a request pays per step, then a 16 KB upload into the replayed graph's buffer
-                    self.prompt_cache.update(ids)
-                    recorded = True
-                    words = packed_token_mask(mask.mask_fn(self.prompt_cache.computed_ids), vocab)
-                counts = {}
-                if plan.get("counts") is not None:  # (a request without them passes nothing: set_step_tail's defaults switch them off)
-                    counts = {"frequency_penalty": plan["counts"].frequency_penalty, "presence_penalty": plan["counts"].presence_penalty,
-                              "count_start": None if fed_back else len(prompt_ids)}   # the request's first call: zero counts, from the prompt's end on
-                set_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
-                         token_mask=words, logit_bias=None if bias is None else (bias.ids, bias.values),
-                         **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}), **counts,
-                         **({} if dry is None else {"dry": (dry.dry_multiplier, dry.dry_base, dry.dry_allowed_length, dry.dry_range, dry.dry_sequence_breakers)}),
-                         **({} if plan.get("xtc") is None else {"xtc": plan["xtc"]}),
-                         **({} if plan.get("automaton") is None else {"token_automaton": plan["automaton"].automaton}))
-                if plan.get("automaton") is not None and not fed_back:
-                    # the request's first call: the start state, in stream order.  From here on the state moves on the device by the
-                    # token each step feeds back: nothing is read back and no mask is uploaded (DESIGN.md 22)
-                    self.model.reset_step_automaton()
-                if pixel_values is not None and not fed_back:
-                    embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
-                    tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache, ids)
-                else:
-                    tok, logprobs, _ = self.model.step(None if fed_back else ids, self.prompt_cache.cache)
-                if not recorded:
-                    self.prompt_cache.update(ids)                              # :255 (device ids resolve lazily)
-                if top_logprobs is not None:
-                    self.top_record = self.model.step_top_logprobs
-                return tok, logprobs
-            if set_tail is not None:
-                set_tail()  # the host-orchestrated branches below run on Model.step's documented greedy tail
-            if pixel_values is not None and not fed_back:
-                # the prompt of a VLM request (:246-252): text embeddings with the image features scattered in, through the
-                # text tower.  The reference passes pixel_values on every later step too, where a single new token holds
-                # no image token and the vision tower's output is discarded (ensemble.py:62-91); those steps skip it here.
-                embeds = self.model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
-                if not procs:
-                    tok, logprobs, _ = self.model.step_embeds(embeds, self.prompt_cache.cache)
-                    self.prompt_cache.update(ids)
-                    if getattr(sampler, "is_greedy", False):
-                        return tok, logprobs
-                    return sampler(logprobs[None]).reshape(1).to(torch.int32), logprobs
-                logits = self.model.language_model(None, cache=self.prompt_cache.cache, inputs_embeds=embeds)
-                last = logits[:, -1, :]
-                self.prompt_cache.update(ids)
-                for proc in procs:
-                    last = proc(self.prompt_cache.computed_ids, last)
-                tok, logprobs = hip_ops.logprobs_argmax(last)
-                if getattr(sampler, "is_greedy", False):
-                    return tok, logprobs
-                return sampler(logprobs[None]), logprobs
-            if not procs:
-                # fused step: hipGraph replay for L == 1, log-softmax (+ greedy argmax) in the HIP tail, no host sync
-                greedy_fused = getattr(sampler, "is_greedy", False)
-                tok, logprobs, _ = self.model.step(None if (fed_back and greedy_fused) else ids, self.prompt_cache.cache)
-                self.prompt_cache.update(ids)                                  # :255 (device ids resolve lazily)
-                if greedy_fused:
-                    return tok, logprobs
-                # stochastic sampler (:271): drawn on the device; the token tensor feeds the next step without a read-back
-                return sampler(logprobs[None]).reshape(1).to(torch.int32), logprobs
-            logits = self.model(ids[None], cache=self.prompt_cache.cache)      # :252
-            last = logits[:, -1, :]                                            # :254
-            self.prompt_cache.update(ids)                                      # :255
-            for proc in procs:                                                 # :257-266
-                last = proc(self.prompt_cache.computed_ids, last)
-            tok, logprobs = hip_ops.logprobs_argmax(last)                      # :268-269 + greedy argmax, HIP tail
-            if getattr(sampler, "is_greedy", False):
-                return tok, logprobs
-            return sampler(logprobs[None]), logprobs                           # :271
-
+    def _select_prompt_cache(self, prompt_ids, max_kv_size: int | None, scored: bool) -> None:
+        """The prompt cache a request runs on -- the one it finds, or fresh caches of the kind it asks for -- and the request's start for
+        the processors that keep state of their own."""
         cur = self.prompt_cache.cache
         ring = bool(cur) and isinstance(cur[0], RotatingKVCache)
         if cur and (scored or ring != (max_kv_size is not None) or (ring and cur[0].max_size != max_kv_size)):
@@ -521,46 +451,163 @@ class InferenceEngine:
             for proc in procs:
                 if (hasattr(proc, "frequency_penalty") or hasattr(proc, "automaton")) and hasattr(proc, "reset"):
                     proc.reset(len(prompt_ids))  # the prompt cache may be reused across requests, the counts and an automaton's walk may not: this request's start
-        todo = self.prompt_cache(prompt_ids)                                   # :277
-        host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
-        if speculative is not None and speculative.draft_model is not None:
-            yield from self._speculative_draft_steps([int(t) for t in prompt_ids], host_ids, speculative, top_logprobs, spec_plan)
-            return
-        if speculative is not None:
-            yield from self._speculative_steps(host_ids, speculative, top_logprobs, spec_plan)
-            return
-        if scored and len(host_ids) > 1:
-            lm = getattr(self.model, "language_model", self.model)
-            bufs = lm.set_prompt_logprobs(len(host_ids), max(int(prompt_logprobs), 1))
-            targets, counts = prompt_targets(host_ids, int(prompt_logprobs))
-            bufs["targets"].copy_(torch.tensor(targets, dtype=torch.int32))
-            bufs["count"].copy_(torch.tensor(counts, dtype=torch.int32))
-            try:
-                next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))
-            finally:
-                lm.clear_prompt_logprobs()
-            self.prompt_logprobs = prompt_maps(bufs["ids"].cpu().numpy(), bufs["vals"].cpu().numpy(), int(prompt_logprobs))
-        else:
-            if scored:
-                self.prompt_logprobs = [None]
-            next_token, logprobs = _inference(torch.tensor(host_ids, dtype=torch.int32))   # :278 (host ids: no read-back)
-        step_count = 0
-        while True:
-            if step_count > 0:
-                next_token, logprobs = _inference(next_token, fed_back=True)   # :288
-            yield next_token, logprobs
-            step_count += 1
 
-    def _record_top(self, host_top: list, top_logprobs: int | None, tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
-        """The top-n records of a speculative yield: one hip_ops.top_logprobs call over the yielded rows, record r = token r's.  host_top
-        keeps the generation's workspace."""
+    def _inference(self, ids: torch.Tensor, fed_back: bool, *, pixel_values, kv_quant, top_logprobs, count_start, host_top: list) -> tuple[torch.Tensor, torch.Tensor]:
+        """One forward + tail.  fed_back: `ids` is the token the previous call returned (still in the decoder's
+        device-side state), so nothing has to be copied or read back.  The state, its sampler and processors and the plan are resolved
+        here, per call: a structuring engine changes state per token, and prepare_engine may run between two steps."""
+        self.top_record = None
+        state = "root"
+        if self.structuring_engine is not None:
+            state = self.structuring_engine.get_current_state() or "root"
+            if state not in self.logits_processors:
+                state = "root"
+        sampler = self.samplers[state]
+        procs = self.logits_processors.get(state) or []
+        if kv_quant is not None:
+            self._maybe_quantize(*kv_quant)
+        model = self.model
+        plan = fused_tail_plan(procs, sampler, self.structuring_engine, getattr(model, "tp", None) is not None) if hasattr(model, "set_step_tail") else None
+        offset = int(self.prompt_cache.cache[0].offset) if self.prompt_cache.cache else 0
+        if plan is None or offset + int(ids.numel()) > model.fed_ids.numel():
+            self._apply_tail_plan(None)  # the host-orchestrated branches run on Model.step's documented greedy tail
+            tok, logprobs = self._host_tail(ids, fed_back, pixel_values, sampler, procs)
+            if top_logprobs is not None:  # their top-n record comes from the op (the fused plan's is written inside the step)
+                self._record_top(host_top, top_logprobs, tok.reshape(1).to(torch.int32), logprobs.reshape(1, -1), 1)
+                self.top_record = (self.top_record[0][0], self.top_record[1][0])
+            return tok, logprobs
+        # The whole tail inside the step (DESIGN.md 10, 12): mask, penalty, bias, log-softmax and the draw ride the replayed graph; the
+        # drawn token is fed back on the device, so a fed-back step passes nothing, whatever the sampler
+        mask = plan["mask"]
+        vocab = getattr(model, "language_model", model).logprobs.numel()
+        words = None
+        if mask is not None:
+            check_vocab(mask, vocab)
+            words = mask.mask  # (static host words: set_step_tail refuses a mask that allows no token when it uploads them)
+        recorded = mask is not None and mask.mask_fn is not None
+        if recorded:
+            # a grammar's mask depends on the tokens so far, this row's input included (the processors run after :255): the one
+            # read-back of the fed-back token such a request pays per step, then a 16 KB upload into the replayed graph's buffer
+            self.prompt_cache.update(ids)
+            words = packed_token_mask(mask.mask_fn(self.prompt_cache.computed_ids), vocab)
+        # count_start: the request's first call starts zero counts, from the prompt's end on
+        self._apply_tail_plan(plan, offset, first=not fed_back, count_start=None if fed_back else count_start, token_mask=words,
+                              **({} if top_logprobs is None else {"top_logprobs": int(top_logprobs)}))
+        if plan.get("automaton") is not None and not fed_back:
+            # the request's first call: the start state, in stream order.  From here on the state moves on the device by the
+            # token each step feeds back: nothing is read back and no mask is uploaded (DESIGN.md 22)
+            model.reset_step_automaton()
+        if pixel_values is not None and not fed_back:
+            embeds = model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
+            tok, logprobs, _ = model.step_embeds(embeds, self.prompt_cache.cache, ids)
+        else:
+            tok, logprobs, _ = model.step(None if fed_back else ids, self.prompt_cache.cache)
+        if not recorded:
+            self.prompt_cache.update(ids)                              # :255 (device ids resolve lazily)
+        if top_logprobs is not None:
+            self.top_record = model.step_top_logprobs
+        return tok, logprobs
+
+    def _apply_tail_plan(self, plan: dict | None, offset: int = 0, first: bool = True, count_start: int | None = None, **step_parts) -> None:
+        """Configures the model's step tail (Model.set_step_tail) with a fused tail plan's parts -- a part the plan lacks is not passed,
+        so the setter's default switches it off -- and the caller's step_parts; plan None: the documented greedy tail, where the model
+        has a configurable one.  first, over a reused prefix of `offset` cached positions: the prefix's ids may predate this
+        configuration (fed back unrecorded, loaded from disk), so the fed ids a tail reads are written again from the prompt cache's,
+        which may already hold this call's own ids behind them."""
+        model = self.model
+        if plan is None:
+            if hasattr(model, "set_step_tail"):
+                model.set_step_tail()
+            return
+        bias, counts, dry = plan["bias"], plan.get("counts"), plan.get("dry")
+        window = max(plan["context_size"] if plan["repetition_penalty"] != 1.0 else 0, 0 if dry is None else dry.dry_range)  # the fed ids a tail reads
+        if window and first and offset > 0:
+            seen = self.prompt_cache.computed_ids[offset - min(offset, window):offset]
+            model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
+        parts = dict(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
+                     logit_bias=None if bias is None else (bias.ids, bias.values))
+        if counts is not None:  # (a request without them passes nothing: set_step_tail's defaults switch them off)
+            parts.update(frequency_penalty=counts.frequency_penalty, presence_penalty=counts.presence_penalty, count_start=count_start)
+        if dry is not None:
+            parts["dry"] = (dry.dry_multiplier, dry.dry_base, dry.dry_allowed_length, dry.dry_range, dry.dry_sequence_breakers)
+        if plan.get("xtc") is not None:
+            parts["xtc"] = plan["xtc"]
+        if plan.get("automaton") is not None:
+            parts["token_automaton"] = plan["automaton"].automaton
+        model.set_step_tail(**parts, **step_parts)
+
+    def _invoke(self, ids: torch.Tensor, fed_back: bool, pixel_values, procs, greedy: bool):
+        """The model call of a host-orchestrated step: (token, logprobs) from the fused step where no processor wants the logits,
+        else the raw logits of the last row [1, V]."""
+        model, cache = self.model, self.prompt_cache.cache
+        if pixel_values is not None and not fed_back:
+            # the prompt of a VLM request (:246-252): text embeddings with the image features scattered in, through the
+            # text tower.  The reference passes pixel_values on every later step too, where a single new token holds
+            # no image token and the vision tower's output is discarded (ensemble.py:62-91); those steps skip it here.
+            embeds = model.get_input_embeddings(ids.reshape(1, -1), pixel_values)
+            if not procs:
+                return model.step_embeds(embeds, cache)[:2]
+            return model.language_model(None, cache=cache, inputs_embeds=embeds)[:, -1, :]
+        if not procs:
+            # fused step: hipGraph replay for L == 1, log-softmax (+ greedy argmax) in the HIP tail, no host sync; only a greedy
+            # step finds the token it is fed on the device
+            return model.step(None if (fed_back and greedy) else ids, cache)[:2]
+        return model(ids[None], cache=cache)[:, -1, :]                         # :252, :254
+
+    def _host_tail(self, ids: torch.Tensor, fed_back: bool, pixel_values, sampler, procs) -> tuple[torch.Tensor, torch.Tensor]:
+        """A step outside the fused plan: the model call, then the processors, the log-softmax and the sampler from the host."""
+        greedy_sampler = getattr(sampler, "is_greedy", False)
+        out = self._invoke(ids, fed_back, pixel_values, procs, greedy_sampler)
+        self.prompt_cache.update(ids)                                          # :255 (device ids resolve lazily)
+        if procs:
+            last = out
+            for proc in procs:                                                 # :257-266
+                last = proc(self.prompt_cache.computed_ids, last)
+            tok, logprobs = hip_ops.logprobs_argmax(last)                      # :268-269 + greedy argmax, HIP tail
+        else:
+            tok, logprobs = out
+        if greedy_sampler:
+            return tok, logprobs
+        drawn = sampler(logprobs[None])                                        # :271
+        # stochastic sampler without processors: drawn on the device; the token tensor feeds the next step without a read-back
+        return (drawn if procs else drawn.reshape(1).to(torch.int32)), logprobs
+
+    def _record_top(self, host_top: list, top_logprobs: int | None, tokens_dev: torch.Tensor, rows: torch.Tensor, max_rows: int) -> None:
+        """The top-n records of a yield, from the host: one hip_ops.top_logprobs call over the yielded rows [m <= max_rows, V], record r =
+        token r's, left on `self.top_record` as [m, n + 1].  host_top keeps this generation's own record and workspace, made once: a
+        yield allocates nothing."""
         if top_logprobs is None:
             return
         n, m = max(int(top_logprobs), 1), rows.shape[0]
         if not host_top:
-            host_top.append(hip_ops.top_logprobs_workspace(rows.device, hip_ops.SPEC_MAX_ROWS, rows.shape[1], n))
-        ids, vals = hip_ops.top_logprobs(rows, n, tokens=tokens_dev[:m].contiguous(), workspace=host_top[0])
+            host_top.append((torch.full((max_rows, n + 1), -1, dtype=torch.int32, device=rows.device),
+                             torch.full((max_rows, n + 1), float("-inf"), dtype=torch.float32, device=rows.device)))
+            host_top.append(hip_ops.top_logprobs_workspace(rows.device, max_rows, rows.shape[1], n))
+        ids, vals = hip_ops.top_logprobs(rows, n, tokens=tokens_dev[:m].contiguous(), workspace=host_top[1], out=(host_top[0][0][:m], host_top[0][1][:m]))
         self.top_record = (ids[:, :int(top_logprobs) + 1], vals[:, :int(top_logprobs) + 1])
+
+    def _speculative_prologue(self, host_ids: list[int], plan: dict | None, top_logprobs: int | None):
+        """What both speculative loops begin with: the plan's tail on the target (its passes and its plain steps run under it), fresh
+        `spec_stats`, the generation's top-n recorder, and the prompt's suffix as one plain step.  Returns (token, rows [1, V], record)."""
+        model, cache = self.model, self.prompt_cache.cache
+        offset = int(cache[0].offset) if cache else 0
+        if plan is not None and offset + len(host_ids) > model.fed_ids.numel():
+            raise ValueError("speculative decoding: the prompt runs past the model's id history")
+        self._apply_tail_plan(plan, offset)  # (plan None: the documented greedy tail: the passes refuse anything else)
+        self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}
+        record = partial(self._record_top, [], top_logprobs, max_rows=hip_ops.SPEC_MAX_ROWS)  # record(tokens on the device, rows)
+        ids = torch.tensor(host_ids, dtype=torch.int32)
+        tok, logprobs, _ = model.step(ids, cache)
+        self.prompt_cache.update(ids)
+        return tok, logprobs[None], record
+
+    def _speculative_pass_done(self, fed: int, tokens: list[int], drafted: int, n: int) -> None:
+        """A verify pass's accounting.  The prompt cache receives the ids whose K / V rows the cache now holds: the fed-back token and the
+        accepted drafts, not the token behind them."""
+        self.prompt_cache.update([fed] + tokens[:-1])
+        self.spec_stats["passes"] += 1
+        self.spec_stats["drafted"] += drafted
+        self.spec_stats["accepted"] += n - 1
 
     def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None, plan: dict | None = None):
         """generate_step's loop under speculative decoding.  The prompt's suffix is one plain step; behind it, and behind every
@@ -572,34 +619,11 @@ class InferenceEngine:
         Model.spec_step_tail under the plan's sampler / XTC / repetition penalty / logit bias; both draw from one stream position, so
         token j of the generation is draw j of the seed whichever produced it."""
         model, cache = self.model, self.prompt_cache.cache
-        spec_pass = model.spec_step
-        if plan is not None:
-            offset = int(cache[0].offset) if cache else 0
-            if offset + len(host_ids) > model.fed_ids.numel():
-                raise ValueError("speculative decoding: the prompt runs past the model's id history")
-            if plan["repetition_penalty"] != 1.0 and offset > 0:  # a reused prefix: its ids may predate this configuration (as in _forward)
-                seen = self.prompt_cache.computed_ids[-min(offset, plan["context_size"]):]
-                model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
-            bias = plan["bias"]
-            model.set_step_tail(sampler=plan["sampler"], repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
-                                logit_bias=None if bias is None else (bias.ids, bias.values),
-                                **({} if plan.get("xtc") is None else {"xtc": plan["xtc"]}))
-            spec_pass = model.spec_step_tail
-        elif hasattr(model, "set_step_tail"):
-            model.set_step_tail()  # the documented greedy tail: the passes refuse anything else
+        spec_pass = model.spec_step if plan is None else model.spec_step_tail
         drafter = (int(sp.ngram_max), int(sp.ngram_min), int(sp.num_draft))
         floor = max(int(sp.min_draft), int(getattr(model, "spec_min_rows", 6)) - 1)
-        self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}
-        host_top: list = []
-
-        def record(tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
-            self._record_top(host_top, top_logprobs, tokens_dev, rows)
-
-        ids = torch.tensor(host_ids, dtype=torch.int32)
-        _, logprobs, _ = model.step(ids, cache)
-        self.prompt_cache.update(ids)
+        _, rows, record = self._speculative_prologue(host_ids, plan, top_logprobs)
         model.draft(*drafter)
-        rows = logprobs[None]
         while True:
             tokens, count = model.spec_read()
             record(model.spec_tokens, rows)
@@ -607,11 +631,7 @@ class InferenceEngine:
             fed = tokens[-1]
             if count >= floor:
                 _, n, rows = spec_pass(model.spec_draft[:count], cache, then_draft=drafter)
-                accepted = model.spec_read()[0]
-                self.prompt_cache.update([fed] + accepted[:-1])
-                self.spec_stats["passes"] += 1
-                self.spec_stats["drafted"] += count
-                self.spec_stats["accepted"] += n - 1
+                self._speculative_pass_done(fed, model.spec_read()[0], count, n)
             else:
                 _, logprobs, _ = model.step(None, cache)
                 self.prompt_cache.update([fed])
@@ -637,16 +657,6 @@ class InferenceEngine:
         if len(prompt_ids) > limit:
             raise ValueError("speculative decoding: the prompt runs past the model's id history")
         sampler = None if plan is None else plan["sampler"]
-        if plan is not None:
-            offset = int(cache[0].offset) if cache else 0
-            if plan["repetition_penalty"] != 1.0 and offset > 0:  # a reused prefix: its ids may predate this configuration (as in _forward)
-                seen = self.prompt_cache.computed_ids[-min(offset, plan["context_size"]):]
-                model.fed_ids[offset - len(seen):offset].copy_(torch.tensor(seen, dtype=torch.int32))
-            bias = plan["bias"]
-            model.set_step_tail(sampler=sampler, repetition_penalty=plan["repetition_penalty"], context_size=plan["context_size"],
-                                logit_bias=None if bias is None else (bias.ids, bias.values))
-        else:
-            model.set_step_tail()
         draft_seed = None
         if sampler is not None:  # one sampler setting for both sides, two streams
             draft_seed, draft_counter = _rng.draft_state(d.device)
@@ -654,18 +664,9 @@ class InferenceEngine:
             q_rows = torch.empty((hip_ops.SPEC_MAX_ROWS - 1, d.logprobs.numel()), dtype=torch.float32, device=d.device)
         else:
             d.set_step_tail()
-        self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}
-        host_top: list = []
-
-        def record(tokens_dev: torch.Tensor, rows: torch.Tensor) -> None:
-            self._record_top(host_top, top_logprobs, tokens_dev, rows)
-
         self._draft_cache = dcache = [ReusableKVCache() for _ in d.layers]
         d.step(torch.tensor(prompt_ids, dtype=torch.int32), dcache)  # (its own choice behind the prompt is not used: the target's is fed)
-        ids = torch.tensor(host_ids, dtype=torch.int32)
-        tok, logprobs, _ = model.step(ids, cache)
-        self.prompt_cache.update(ids)
-        rows = logprobs[None]
+        tok, rows, record = self._speculative_prologue(host_ids, plan, top_logprobs)
         record(tok, rows)
         tokens = [int(tok)]
         while True:
@@ -689,10 +690,7 @@ class InferenceEngine:
             else:
                 _, n, rows = model.spec_step(draft, cache)
             tokens = model.spec_read()[0]
-            self.prompt_cache.update([fed] + tokens[:-1])
-            self.spec_stats["passes"] += 1
-            self.spec_stats["drafted"] += k
-            self.spec_stats["accepted"] += n - 1
+            self._speculative_pass_done(fed, tokens, k, n)
             if n == k + 1:
                 d.step(torch.tensor(tokens[-2:-1], dtype=torch.int32), dcache)  # the last draft: accepted, and not yet in the drafter's cache
             else:
@@ -772,10 +770,8 @@ class InferenceEngine:
 def record_to_map(ids: torch.Tensor, vals: torch.Tensor, top_k: int) -> tuple[list[int], dict[int, float]]:
     """One top-n record (hip_ops.top_logprobs; device or host) -> ([token], {id: logprob}): the best top_k pairs by decreasing
     log-probability (ties: lowest id first), then the chosen token of slot 0 when absent.  One read-back of 2 (n + 1) words."""
-    import numpy as np
-    words = torch.cat([ids.reshape(-1), vals.reshape(-1).view(torch.int32)]).cpu().numpy()
-    m = ids.numel()
-    return host_record_to_map(words[:m], words[m:].view(np.float32), top_k)
+    tokens, maps = records_to_maps(ids.reshape(1, -1), vals.reshape(1, -1), top_k)
+    return tokens, maps[0]
 
 
 def records_to_maps(ids: torch.Tensor, vals: torch.Tensor, top_k: int) -> tuple[list[int], list[dict[int, float]]]:

@@ -41,6 +41,20 @@ def _argmax_f32(x: torch.Tensor) -> torch.Tensor:
     return idx.to(torch.int32).reshape(1)
 
 
+def sampler_spec(temp: float = 0.0, top_p: float = 0.0, min_p: float = 0.0, min_tokens_to_keep: int = 1, top_k: int = -1) -> tuple | None:
+    """Which branch a request's sampler settings select (samplers/__init__.py:37-46 of the reference): None for greedy (temp == 0), else
+    (mode, temp, p, k) as hip_ops.sample takes them -- top-p for 0 < top_p < 1, else min-p, else top-k, else categorical."""
+    if temp == 0:
+        return None
+    if top_p > 0 and top_p < 1.0:
+        return ("top_p", temp, top_p, 0)
+    if min_p != 0.0:
+        return ("min_p", temp, min_p, min_tokens_to_keep)
+    if top_k > 0:
+        return ("top_k", temp, 0.0, top_k)
+    return ("categorical", temp, 0.0, 0)
+
+
 def make_sampler(temp: float = 0.0, top_p: float = 0.0, min_p: float = 0.0, min_tokens_to_keep: int = 1,
                  top_k: int = -1, xtc_probability: float = 0.0, xtc_threshold: float = 0.0,
                  xtc_special_tokens=()) -> Callable[[torch.Tensor], torch.Tensor]:
@@ -49,17 +63,14 @@ def make_sampler(temp: float = 0.0, top_p: float = 0.0, min_p: float = 0.0, min_
     xtc_probability > 0 (with xtc_threshold in (0, 0.5] and up to 16 xtc_special_tokens; samplers/xtc.py): the chosen
     branch draws under XTC, and the closure also carries `hip_xtc = (probability, threshold, special ids)` -- set_step_tail's `xtc`.
     The greedy branch ignores XTC, as upstream's make_sampler does; with xtc_probability == 0 nothing changes."""
-    if temp == 0:
+    spec = sampler_spec(temp, top_p, min_p, min_tokens_to_keep, top_k)
+    if spec is None:
         return greedy
     xtc = check_xtc(xtc_probability, xtc_threshold, xtc_special_tokens, "make_sampler")
-    if top_p > 0 and top_p < 1.0:
-        sampler, spec = (lambda x: top_p_sampling(x, top_p, temp)), ("top_p", temp, top_p, 0)
-    elif min_p != 0.0:
-        sampler, spec = (lambda x: min_p_sampling(x, min_p, min_tokens_to_keep, temp)), ("min_p", temp, min_p, min_tokens_to_keep)
-    elif top_k > 0:
-        sampler, spec = (lambda x: top_k_sampling(x, top_k, temp)), ("top_k", temp, 0.0, top_k)
-    else:
-        sampler, spec = (lambda x: categorical_sampling(x, temp)), ("categorical", temp, 0.0, 0)
+    sampler = {"top_p": lambda x: top_p_sampling(x, top_p, temp),
+               "min_p": lambda x: min_p_sampling(x, min_p, min_tokens_to_keep, temp),
+               "top_k": lambda x: top_k_sampling(x, top_k, temp),
+               "categorical": lambda x: categorical_sampling(x, temp)}[spec[0]]
     if xtc is not None:
         sampler = xtc_sampling(spec, xtc)
         sampler.hip_xtc = xtc
