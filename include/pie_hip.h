@@ -945,6 +945,50 @@ int pie_decoder_spec_step(pie_decoder *d, const int32_t *draft_ids, int n_draft,
 size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows);
 int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
                                int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
+/* The automaton along a draft.  record, state, tables: ONE row of pie_token_dfa_mask's, untrusted like there: every index a
+ * kernel forms is checked against tables_len, V, S and C, and a record that is not armed constrains nothing.  Both ops: one launch of one wave.
+ * pie_token_dfa_walk: tokens DEVICE int32 [n], 1 <= n <= 31 -> out_states DEVICE int32 [n + 1]: out_states[0] = *state, out_states[i + 1] =
+ *   pie_token_dfa_advance's result for out_states[i] and tokens[i] -- a state outside [0, S) stays what it is; an unarmed record copies
+ *   *state to every slot.  Neither *state nor anything else is modified.
+ * pie_token_dfa_draft: the grammar-aware drafter.  forced DEVICE int32 [forced_states, 2], 8-byte aligned: row s = (t, next) when exactly one
+ *   id t is allowed in state s and leads to next, else (-1, -1) (TokenAutomaton.forced()) -- a HINT: an entry is used only where the tables
+ *   re-derive it.  cand DEVICE int32 [>= min(*cand_count, 31)]: a candidate draft (pie_ngram_draft's), cand_count DEVICE int32 [1], clamped
+ *   on the device to [0, 31]; 1 <= k <= 31; out_ids DEVICE int32 [k] (may be cand), out_count DEVICE int32 [1] (may be cand_count).
+ *     unarmed record, or s0 = *state outside [0, S): out_ids = cand[: min(cand_count, k)], out_count likewise
+ *     s = s0; j = 0; live = true; n = 0
+ *     while n < k:
+ *         (f, fn) = forced[s] when s < forced_states, else (-1, -1)
+ *         if 0 <= f < V and fn >= 0 and trans[s, cls[f]] == fn:  t, next = f, fn;  if live and j < cand_count and cand[j] == t: j += 1, else: live = false
+ *         else if live and j < cand_count and cand[j] is allowed in s:  t, next = cand[j], trans[s, cls[cand[j]]];  j += 1
+ *         else: stop
+ *         out_ids[n] = t; n += 1; s = next;  stop when s is outside [0, S)
+ *     out_count = n;  out_ids[n ..] keep their contents
+ *   So a looked-up draft is cut at the first id the grammar forbids, a forced id replaces whatever was looked up (which ends the
+ *   look-up's part), and without a look-up the grammar drafts its forced run.  Every id written is allowed in the state the ids before it
+ *   lead to, whatever `forced` holds.  *state is not modified.
+ * Both: a NULL pointer: PIE_E_ARG; n or k outside 1..31, V < 1, tables_len < 1, forced_states < 1: PIE_E_SHAPE; a pointer not aligned:
+ * PIE_E_ALIGN -- all before any launch. */
+int pie_token_dfa_walk(const pie_row_dfa *record, const int32_t *state, const int32_t *tables, int tables_len, int V, const int32_t *tokens, int n,
+                       int32_t *out_states, void *stream);
+int pie_token_dfa_draft(const pie_row_dfa *record, const int32_t *state, const int32_t *tables, int tables_len, const int32_t *forced, int forced_states, int V,
+                        const int32_t *cand, const int32_t *cand_count, int k, int32_t *out_ids, int32_t *out_count, void *stream);
+/* One speculative pass under a token automaton: pie_decoder_spec_step_tail's arguments, row bounds and settings PLUS
+ * pie_decoder_set_token_dfa, which is REQUIRED (without one: PIE_E_STATE, the pass is pie_decoder_spec_step_tail's) and alone is enough.
+ * With o the device-side offset and s0 the automaton's state, in order: (1) the gather and pie_decoder_prefill with raw logits on every row;
+ * (2) pie_token_dfa_walk over draft_ids into states [m + 1] of the workspace (the same launch replicates the record per row and zeroes
+ * mask_on); (3) pie_token_dfa_mask over the m + 1 rows into masks / mask_on of the workspace: a row whose state has left [0, S) is an
+ * unmasked row; (4) pie_decoder_spec_step_tail's edit launch when a penalty or a bias is set; (5) pie_spec_verify_sampled's launches, the
+ * partials masked per row (pie_logprobs_argmax_rows_masked's); (6) the accept launch also stores the automaton's state: states[out_n - 1]
+ * advanced by token out_n - 1 under pie_token_dfa_advance's rule.  Row r's log-probabilities and token are those of the step's tail on that
+ * row alone in state states[r] at stream position c + r; afterwards the decoder -- pos, tokens, history, ids_by_pos, seq_ids / seq_len, the
+ * counter {c + out_n, 0} and the automaton's state -- is where out_n configured steps would have left it.  2 launches beyond
+ * pie_decoder_spec_step_tail's; nothing is captured in a graph, and a decoder that never calls this entry launches exactly what it
+ * launches without it.  PIE_E_STATE before any launch, each by name: no automaton; a token mask; a top-logprobs record; frequency /
+ * presence counts; a DRY penalty; prompt scoring; a tensor-parallel decoder; a quantized or rotating KV cache; int8 pages.  workspace:
+ * pie_decoder_spec_dfa_workspace_bytes(d, m + 1) bytes (0 for refused row counts), 16-byte aligned, caller-owned, ZEROED ONCE. */
+size_t pie_decoder_spec_dfa_workspace_bytes(const pie_decoder *d, int rows);
+int pie_decoder_spec_step_dfa(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                              int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream);
 /* One speculative pass over a draft MODEL's block: pie_decoder_spec_step_tail's arguments, row bounds and order, plus
  * q_logprobs DEVICE fp32 [m, vocab] (the drafter's log-probabilities at the step that drew draft i), with pie_spec_verify_draft's launches
  * in place of pie_spec_verify_sampled's: (1) the gather and pie_decoder_prefill, raw logits on every row; (2) the edit launch when a

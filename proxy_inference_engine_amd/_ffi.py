@@ -58,6 +58,7 @@ EXPORTS = [
     "pie_ngram_draft_workspace_bytes", "pie_ngram_draft", "pie_spec_verify_workspace_bytes", "pie_spec_verify", "pie_decoder_spec_workspace_bytes", "pie_decoder_spec_step",
     "pie_spec_verify_sampled_workspace_bytes", "pie_spec_verify_sampled", "pie_decoder_spec_tail_workspace_bytes", "pie_decoder_spec_step_tail",
     "pie_spec_verify_draft_workspace_bytes", "pie_spec_verify_draft", "pie_decoder_spec_draft_workspace_bytes", "pie_decoder_spec_step_draft",
+    "pie_token_dfa_walk", "pie_token_dfa_draft", "pie_decoder_spec_dfa_workspace_bytes", "pie_decoder_spec_step_dfa",
 ]
 
 
@@ -234,6 +235,11 @@ def load() -> C.CDLL:
     lib.pie_decoder_spec_tail_workspace_bytes.restype = C.c_size_t
     lib.pie_decoder_spec_tail_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.pie_decoder_spec_step_tail.argtypes = lib.pie_decoder_spec_step.argtypes
+    lib.pie_token_dfa_walk.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_token_dfa_draft.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.pie_decoder_spec_dfa_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_spec_dfa_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
+    lib.pie_decoder_spec_step_dfa.argtypes = lib.pie_decoder_spec_step.argtypes
     lib.pie_spec_verify_draft_workspace_bytes.restype = C.c_size_t
     lib.pie_spec_verify_draft_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.pie_spec_verify_draft.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint64] + [C.c_void_p] * 8

@@ -170,6 +170,9 @@ struct StepTail {
     // and its sampled verify apply -- and refuses every other part by name.  (The greedy and raw pass asks !configured() and !xtc.on().)
     const char *spec_tail_refused() const { return mask.on() ? "a token mask" : dfa.on() ? "a token automaton" : top.on() ? "a top-logprobs record" : counts.on() ? "frequency / presence counts" : dry.on() ? "a DRY penalty" : nullptr; }
     bool spec_tail_admitted() const { return penalty.on() || sampler.on() || bias.on() || xtc.on(); }
+    // Speculation under a token automaton (pie_decoder_spec_step_dfa) admits what the tail's pass admits plus the automaton,
+    // which alone is enough; every other part is refused under the name spec_tail_refused gives it.
+    const char *spec_dfa_refused() const { return mask.on() ? "a token mask" : top.on() ? "a top-logprobs record" : counts.on() ? "frequency / presence counts" : dry.on() ? "a DRY penalty" : nullptr; }
 };
 
 // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): the prompt passes score their rows in blocks of at most

@@ -433,6 +433,25 @@ int pie_token_dfa_advance(const pie_row_dfa *records, int32_t *states, const int
     return token_dfa_advance_launch(records, states, tables, tables_len, rows, V, tokens, (hipStream_t)stream);
 }
 
+int pie_token_dfa_walk(const pie_row_dfa *record, const int32_t *state, const int32_t *tables, int tables_len, int V, const int32_t *tokens, int n,
+                       int32_t *out_states, void *stream) {
+    PIE_REQUIRE(tokens && out_states, PIE_E_ARG, "pie_token_dfa_walk: null pointer");
+    if (int rc = token_dfa_check("pie_token_dfa_walk", record, state, tables, tables_len, 1, V)) return rc;
+    PIE_REQUIRE(n >= 1 && n <= DFA_MAX_DRAFT, PIE_E_SHAPE, "pie_token_dfa_walk: n must be 1..31");
+    PIE_REQUIRE(pie_aligned(tokens, 4) && pie_aligned(out_states, 4), PIE_E_ALIGN, "pie_token_dfa_walk: tokens and out_states need 4-byte alignment");
+    return token_dfa_walk_launch(record, state, tables, tables_len, V, tokens, n, out_states, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int pie_token_dfa_draft(const pie_row_dfa *record, const int32_t *state, const int32_t *tables, int tables_len, const int32_t *forced, int forced_states, int V,
+                        const int32_t *cand, const int32_t *cand_count, int k, int32_t *out_ids, int32_t *out_count, void *stream) {
+    PIE_REQUIRE(forced && cand && cand_count && out_ids && out_count, PIE_E_ARG, "pie_token_dfa_draft: null pointer");
+    if (int rc = token_dfa_check("pie_token_dfa_draft", record, state, tables, tables_len, 1, V)) return rc;
+    PIE_REQUIRE(k >= 1 && k <= DFA_MAX_DRAFT && forced_states >= 1, PIE_E_SHAPE, "pie_token_dfa_draft: k must be 1..31 and the forced table hold at least one state");
+    PIE_REQUIRE(pie_aligned(forced, 8) && pie_aligned(cand, 4) && pie_aligned(cand_count, 4) && pie_aligned(out_ids, 4) && pie_aligned(out_count, 4), PIE_E_ALIGN,
+                "pie_token_dfa_draft: the forced table needs 8-byte, the candidate and the outputs 4-byte alignment");
+    return token_dfa_draft_launch(record, state, tables, tables_len, forced, forced_states, V, cand, cand_count, k, out_ids, out_count, (hipStream_t)stream);
+}
+
 size_t pie_count_penalty_bytes(void) { return sizeof(pie_count_penalty); }
 
 int pie_count_penalty_pack(double freq, double pres, int start, int counted_pos, pie_count_penalty *out) {

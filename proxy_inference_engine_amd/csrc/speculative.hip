@@ -234,11 +234,42 @@ struct SpecSampledArgs {
 };
 
 // The log-probabilities of every row are already written (the draws read them): one thread does what is left.
-__global__ void k_spec_accept_sampled(const SpecSampledArgs a) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+__device__ __forceinline__ int spec_accept_sampled(const SpecSampledArgs &a) {
     const int n_acc = spec_count_accepted(a.draft, a.tok, a.rows, a.V);
     spec_commit(a.s, a.tok, a.rows, n_acc, a.out_tokens, a.out_n);
     if (a.counter) a.counter[0] = *a.base + (unsigned long long)(n_acc + 1), a.counter[1] = 0ull;  // the rejected rows' positions are not consumed
+    return n_acc;
+}
+
+__global__ void k_spec_accept_sampled(const SpecSampledArgs a) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    spec_accept_sampled(a);
+}
+
+// pie_decoder_spec_step_dfa's part of the verify, all of it in the workspace but the decoder's own record, state and arena:
+// states [rows] = the automaton's state in front of every row (the walk along the draft), records [rows] = the record once per row,
+// masks [rows, mask_words] and mask_on [rows] = what the mask op derives from them and the masked partials read.
+struct SpecDfa {
+    const pie_row_dfa *record;
+    int *state;
+    const int *tables;
+    int tables_len;
+    int *states, *mask_on;
+    pie_row_dfa *records;
+    unsigned *masks;
+    int mask_words;
+};
+
+// The accept launch under an automaton: what k_spec_accept_sampled leaves, and the decoder's automaton state where out_n configured steps
+// would have left it -- the state in front of row n_acc (every draft before it was accepted: the plain loop's state) advanced by that
+// row's token, by pie_token_dfa_advance's rule.
+__global__ void k_spec_accept_dfa(const SpecSampledArgs a, const SpecDfa f) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int n_acc = spec_accept_sampled(a);
+    const pie_row_dfa r = *f.record;
+    if (!dfa_armed(r, a.V, f.tables_len)) return;
+    const int s = f.states[n_acc];
+    *f.state = s >= 0 && s < r.n_states ? dfa_next(r, f.tables, a.V, s, a.tok[n_acc]) : s;
 }
 
 // pie_decoder_spec_step_tail's edit: workgroup r is row r of the block, at position o + r, o = state->pos - rows (the pass has run).
@@ -286,6 +317,19 @@ __global__ void k_spec_gather(const DecState *state, const int *draft, int m, in
 
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
+struct SpecDfaLayout {  // pie_decoder_spec_step_dfa's part of the workspace, behind the `head` bytes of pie_decoder_spec_step_tail's
+    size_t states, mask_on, records, masks, bytes;
+    int mask_words;
+    SpecDfaLayout(size_t head, int V) {
+        mask_words = (V + 31) / 32;
+        states = align16(head);
+        mask_on = states + sizeof(int) * SPEC_MAX_ROWS;
+        records = mask_on + sizeof(int) * SPEC_MAX_ROWS;
+        masks = records + sizeof(pie_row_dfa) * SPEC_MAX_ROWS;
+        bytes = align16(masks + sizeof(unsigned) * SPEC_MAX_ROWS * (size_t)mask_words);
+    }
+};
+
 }  // namespace
 
 size_t spec_verify_workspace_bytes(int rows) { return rows < 2 || rows > SPEC_MAX_ROWS ? 0 : SpecLayout(rows).bytes; }
@@ -309,12 +353,15 @@ int spec_verify_launch(const u16 *logits, int rows, int V, int dtype, const int 
 // penalty- or bias-only tails): the rows' tokens are their argmaxes, nothing is drawn and the counter is not touched.
 static int spec_verify_sampled_launch(u16 *logits, int rows, int V, int dtype, const int *draft, int mode, double temp, double p, int k, unsigned long long seed,
                                       unsigned long long *counter, const pie_xtc *xtc, int *out_tokens, int *out_n, float *logprobs, void *workspace,
-                                      const SpecState &s, hipStream_t st) {
+                                      const SpecState &s, hipStream_t st, const SpecDfa *dfa = nullptr) {
     const SpecSampledLayout lay(rows, V);
     char *ws = (char *)workspace;
     int *tok = (int *)(ws + lay.tok);
     unsigned long long *base = (unsigned long long *)(ws + lay.base);
-    if (int rc = logits_tail_rows_launch(dtype, logits, V, rows, (LogitStat *)ws, logprobs, tok, st)) return rc;
+    // dfa (pie_decoder_spec_step_dfa): every row's partials are masked with the row's own words, and the accept launch moves the automaton
+    if (int rc = logits_tail_rows_launch(dtype, logits, V, rows, (LogitStat *)ws, logprobs, tok, st, dfa ? dfa->masks : nullptr, dfa ? dfa->mask_words : 0,
+                                         dfa ? dfa->mask_on : nullptr))
+        return rc;
     const bool draws = mode != PIE_SAMPLE_GREEDY;
     if (draws) {
         SpecFillArgs f = {};
@@ -327,7 +374,8 @@ static int spec_verify_sampled_launch(u16 *logits, int rows, int V, int dtype, c
         if (int rc = sample_rows_launch(logprobs, rows, V, f.table, ws + lay.smp, tok, nullptr, nullptr, st, SampleXtc{xtc ? f.xtc_rows : nullptr, nullptr})) return rc;
     }
     const SpecSampledArgs a = {rows, V, draft, tok, out_tokens, out_n, base, draws ? counter : nullptr, s};
-    hipLaunchKernelGGL(k_spec_accept_sampled, dim3(1), dim3(64), 0, st, a);
+    if (dfa) hipLaunchKernelGGL(k_spec_accept_dfa, dim3(1), dim3(64), 0, st, a, *dfa);
+    else hipLaunchKernelGGL(k_spec_accept_sampled, dim3(1), dim3(64), 0, st, a);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
@@ -676,6 +724,12 @@ size_t pie_decoder_spec_tail_workspace_bytes(const pie_decoder *d, int rows) {
     return align16((size_t)rows * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_MAX_ROWS) + SpecSampledLayout(rows, d->cfg.vocab).bytes;
 }
 
+// workspace: pie_decoder_spec_step_tail's | the states in front of the rows [32] | mask_on [32] | the record per row [32] | the rows' mask words
+size_t pie_decoder_spec_dfa_workspace_bytes(const pie_decoder *d, int rows) {
+    const size_t head = pie_decoder_spec_tail_workspace_bytes(d, rows);
+    return head ? SpecDfaLayout(head, d->cfg.vocab).bytes : 0;
+}
+
 // workspace: the logits block [rows, vocab] T | the pass's input ids [32] | pie_spec_verify_draft's workspace
 size_t pie_decoder_spec_draft_workspace_bytes(const pie_decoder *d, int rows) {
     if (!d || rows < 2 || rows > SPEC_MAX_ROWS || pie_sample_workspace_bytes(rows, d->cfg.vocab) == 0) return 0;
@@ -686,7 +740,7 @@ size_t pie_decoder_spec_draft_workspace_bytes(const pie_decoder *d, int rows) {
 
 namespace {
 
-enum SpecKind { SPEC_RAW = 0, SPEC_TAIL = 1, SPEC_DRAFT = 2 };  // pie_decoder_spec_step, _spec_step_tail, _spec_step_draft
+enum SpecKind { SPEC_RAW = 0, SPEC_TAIL = 1, SPEC_DRAFT = 2, SPEC_DFA = 3 };  // pie_decoder_spec_step, _spec_step_tail, _spec_step_draft, _spec_step_dfa
 
 // What the three pie_decoder_spec_step* entries share: the entry's refusals -- with_tail: which parts of the step's tail the pass admits is
 // StepTail's answer (decoder.hpp) --, the shape and alignment checks, the workspace's carve-up (the logits block at its head, then s->fed,
@@ -704,6 +758,11 @@ int spec_prologue(const char *entry, SpecKind kind, pie_decoder *d, const int32_
         PIE_REQUIRE(!t.configured() && !d->prompt.n, PIE_E_STATE,
                     who + "speculation is greedy and raw: no sampler, penalty, mask, bias, top-logprobs, counts or prompt scoring may be set");
         PIE_REQUIRE(!t.xtc.on(), PIE_E_STATE, who + "speculation is greedy: no XTC record may be set");
+    } else if (kind == SPEC_DFA) {  // the tail's pass plus the automaton, which alone is enough
+        const char *part = t.spec_dfa_refused();
+        PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
+        PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
+        PIE_REQUIRE(t.dfa.on(), PIE_E_STATE, who + "no token automaton is set (the pass without one is pie_decoder_spec_step_tail)");
     } else {
         const char *part = t.spec_tail_refused();
         PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
@@ -770,6 +829,28 @@ int pie_decoder_spec_step_tail(pie_decoder *d, const int32_t *draft_ids, int n_d
     const StepTail::Sampler &m = d->tail.sampler;
     return spec_verify_sampled_launch((u16 *)workspace, n_draft + 1, d->cfg.vocab, d->cfg.dtype, draft_ids, m.mode, m.temp, m.p, m.k, m.seed, m.counter,
                                       m.on() ? d->tail.xtc.record : nullptr, out_tokens, out_n, logprobs_rows, verify_ws, s, (hipStream_t)stream);
+}
+
+int pie_decoder_spec_step_dfa(pie_decoder *d, const int32_t *draft_ids, int n_draft, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows, void *workspace,
+                              int32_t *seq_ids, int seq_cap, int32_t *seq_len, void *stream) {
+    SpecState s;
+    void *verify_ws;
+    if (int rc = spec_prologue("pie_decoder_spec_step_dfa", SPEC_DFA, d, draft_ids, n_draft, out_tokens, out_n, logprobs_rows, workspace, seq_ids, seq_cap, seq_len, stream, &s, &verify_ws)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = n_draft + 1, V = d->cfg.vocab;
+    const StepTail::Dfa &a = d->tail.dfa;
+    const SpecDfaLayout lay(pie_decoder_spec_tail_workspace_bytes(d, rows), V);
+    char *ws = (char *)workspace;
+    const SpecDfa f = {a.record, a.state, a.tables, a.tables_len, (int *)(ws + lay.states), (int *)(ws + lay.mask_on), (pie_row_dfa *)(ws + lay.records),
+                       (unsigned *)(ws + lay.masks), lay.mask_words};
+    // the state in front of every row, from the caller's draft (an id the grammar forbids leaves the automaton: the rows behind it are
+    // unmasked, and never accepted -- the forbidden id's own row is masked in the state before it), then the rows' masks
+    if (int rc = token_dfa_walk_launch(a.record, a.state, a.tables, a.tables_len, V, draft_ids, n_draft, f.states, f.records, f.mask_on, st)) return rc;
+    if (int rc = token_dfa_mask_launch(f.records, f.states, a.tables, a.tables_len, rows, V, f.masks, f.mask_words, f.mask_on, st)) return rc;
+    if (int rc = spec_edit_launch(d, draft_ids, rows, workspace, &s, st)) return rc;
+    const StepTail::Sampler &m = d->tail.sampler;
+    return spec_verify_sampled_launch((u16 *)workspace, rows, V, d->cfg.dtype, draft_ids, m.mode, m.temp, m.p, m.k, m.seed, m.counter,
+                                      m.on() ? d->tail.xtc.record : nullptr, out_tokens, out_n, logprobs_rows, verify_ws, s, st, &f);
 }
 
 int pie_decoder_spec_step_draft(pie_decoder *d, const int32_t *draft_ids, int n_draft, const float *q_logprobs, int32_t *out_tokens, int32_t *out_n, float *logprobs_rows,

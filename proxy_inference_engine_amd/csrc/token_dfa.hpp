@@ -68,6 +68,104 @@ static __global__ void __launch_bounds__(64) k_token_dfa_advance(const pie_row_d
     states[row] = next;
 }
 
+// ---------------------------------------------------------------- the automaton along a draft
+constexpr int DFA_MAX_DRAFT = 31;  // a speculative pass's drafts (speculative.hpp: SPEC_MAX_ROWS - 1)
+
+// pie_token_dfa_advance's rule for one armed record: the state after `t`, from state s in [0, S)
+__device__ __forceinline__ int dfa_next(const pie_row_dfa &r, const int *tables, int V, int s, int t) {
+    if (t < 0 || t >= V) return -1;
+    const int c = tables[r.cls_off + t];
+    return c >= 0 && c < r.n_classes ? tables[r.trans_off + s * r.n_classes + c] : -1;
+}
+
+// The class of id t under an armed record, -1 for an id outside [0, V) or a class outside [0, C)
+__device__ __forceinline__ int dfa_class(const pie_row_dfa &r, const int *tables, int V, int t) {
+    if (t < 0 || t >= V) return -1;
+    const int c = tables[r.cls_off + t];
+    return c >= 0 && c < r.n_classes ? c : -1;
+}
+
+// One wave.  Lane i loads the class of tokens[i] -- n independent loads -- and lane 0 then walks: one dependent trans load per position.
+// out_states[0] = *state, out_states[i + 1] = the advance op's result for out_states[i] and tokens[i]; a state outside [0, S) stays what
+// it is and an unarmed record copies *state to every slot.  rep / mask_on (nullable, the speculative pass's): the record once per state
+// for the mask op's per-row form, and mask_on zeroed in front of it -- the mask op writes only an armed row's entry.
+static __global__ void __launch_bounds__(64) k_token_dfa_walk(const pie_row_dfa *record, const int *state, const int *tables, int tables_len, int V,
+                                                       const int *tokens, int n, int *out_states, pie_row_dfa *rep, int *mask_on) {
+    __shared__ int s_cls[DFA_MAX_DRAFT];
+    const int lane = threadIdx.x;
+    const pie_row_dfa r = *record;
+    const bool armed = dfa_armed(r, V, tables_len);
+    if (lane < n) s_cls[lane] = armed ? dfa_class(r, tables, V, tokens[lane]) : -1;
+    if (lane <= n) {
+        if (rep) rep[lane] = r;
+        if (mask_on) mask_on[lane] = 0;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    int s = *state;
+    out_states[0] = s;
+    for (int i = 0; i < n; ++i) {
+        if (armed && s >= 0 && s < r.n_states) s = s_cls[i] >= 0 ? tables[r.trans_off + s * r.n_classes + s_cls[i]] : -1;
+        out_states[i + 1] = s;
+    }
+}
+
+// The grammar-aware drafter (include/pie_hip.h: pie_token_dfa_draft has the rule).  One wave: lane i holds candidate i and its class --
+// loaded before anything is stored, so out_ids may be cand and out_count cand_count -- and lane 0 then walks.  `forced` is a hint: an
+// entry is used only when the tables re-derive it (0 <= f < V, trans[s, cls[f]] == next >= 0), so whatever it holds, every id written is
+// allowed in the state the ids before it lead to.  forced[next] is requested before the re-derivation of forced[s] is waited for: a forced
+// step's dependent chain is cls[f] -> trans[s, .], not forced[s] -> cls[f] -> trans[s, .].
+static __global__ void __launch_bounds__(64) k_token_dfa_draft(const pie_row_dfa *record, const int *state, const int *tables, int tables_len, const int *forced,
+                                                        int forced_states, int V, const int *cand, const int *cand_count, int k, int *out_ids, int *out_count) {
+    __shared__ int s_cand[DFA_MAX_DRAFT], s_ccls[DFA_MAX_DRAFT];
+    const int lane = threadIdx.x;
+    const pie_row_dfa r = *record;
+    const bool armed = dfa_armed(r, V, tables_len);
+    int cc = *cand_count;
+    cc = cc < 0 ? 0 : (cc > DFA_MAX_DRAFT ? DFA_MAX_DRAFT : cc);
+    if (lane < DFA_MAX_DRAFT) {
+        const int id = lane < cc ? cand[lane] : -1;
+        s_cand[lane] = id, s_ccls[lane] = armed ? dfa_class(r, tables, V, id) : -1;
+    }
+    __syncthreads();  // every candidate is in LDS before the first store below
+    if (lane != 0) return;
+    const int s0 = *state, S = r.n_states, C = r.n_classes;
+    if (!armed || s0 < 0 || s0 >= S) {  // an unconstrained request drafts as before
+        const int n = cc < k ? cc : k;
+        for (int i = 0; i < n; ++i) out_ids[i] = s_cand[i];
+        *out_count = n;
+        return;
+    }
+    const int2 *hint = reinterpret_cast<const int2 *>(forced);
+    const int2 none = make_int2(-1, -1);
+    int s = s0, j = 0, n = 0;
+    bool live = true;
+    int2 f = s < forced_states ? hint[s] : none;
+    while (n < k) {
+        const int row = r.trans_off + s * C;  // s in [0, S): below trans_off + S * C <= tables_len
+        const bool hinted = f.x >= 0 && f.x < V && f.y >= 0;
+        const int fc = hinted ? tables[r.cls_off + f.x] : -1;
+        const int2 ahead = hinted && f.y < S && f.y < forced_states ? hint[f.y] : none;  // in flight while the hint is re-derived
+        const bool has = live && j < cc && s_ccls[j] >= 0;
+        const int cnext = has ? tables[row + s_ccls[j]] : -1;
+        const bool ok = hinted && fc >= 0 && fc < C && tables[row + fc] == f.y;
+        int t, nxt;
+        if (ok) {
+            t = f.x, nxt = f.y;
+            if (live && j < cc && s_cand[j] == t) ++j;
+            else live = false;
+        } else if (cnext >= 0) {
+            t = s_cand[j], nxt = cnext, ++j;
+        } else {
+            break;
+        }
+        out_ids[n++] = t, s = nxt;
+        if (s < 0 || s >= S) break;
+        f = ok ? ahead : (s < forced_states ? hint[s] : none);
+    }
+    *out_count = n;
+}
+
 // ---------------------------------------------------------------- checks and launchers (the ops of ops.hip and the passes' tails)
 static inline int token_dfa_check(const char *who, const void *records, const void *states, const void *tables, int tables_len, int rows, int V) {
     const std::string w(who);
@@ -80,6 +178,21 @@ static inline int token_dfa_check(const char *who, const void *records, const vo
 static inline int token_dfa_mask_launch(const pie_row_dfa *records, const int *states, const int *tables, int tables_len, int rows, int V, unsigned *masks,
                                         int mask_words, int *mask_on, hipStream_t st) {
     hipLaunchKernelGGL(k_token_dfa_mask, dim3((V + 255) / 256, rows), dim3(256), 0, st, records, states, tables, tables_len, V, masks, mask_words, mask_on);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+static inline int token_dfa_walk_launch(const pie_row_dfa *record, const int *state, const int *tables, int tables_len, int V, const int *tokens, int n,
+                                        int *out_states, pie_row_dfa *rep, int *mask_on, hipStream_t st) {
+    hipLaunchKernelGGL(k_token_dfa_walk, dim3(1), dim3(64), 0, st, record, state, tables, tables_len, V, tokens, n, out_states, rep, mask_on);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+static inline int token_dfa_draft_launch(const pie_row_dfa *record, const int *state, const int *tables, int tables_len, const int *forced, int forced_states,
+                                         int V, const int *cand, const int *cand_count, int k, int *out_ids, int *out_count, hipStream_t st) {
+    hipLaunchKernelGGL(k_token_dfa_draft, dim3(1), dim3(64), 0, st, record, state, tables, tables_len, forced, forced_states, V, cand, cand_count, k, out_ids,
+                       out_count);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }

@@ -141,13 +141,20 @@ class SpeculativeParams:
     under the request's (mode, temp, p, k) and a seed of its own, draft i is accepted with probability min(1, P_i / Q_i), and the token
     behind the accepted prefix comes from the residual max(0, P - Q) -- every token is distributed as the plain loop's, though it is no
     longer draw j of the seed.  min_draft, ngram_max, ngram_min and configured_tail are ignored with a draft model: every round drafts
-    num_draft ids, and the request's sampler decides the path."""
+    num_draft ids, and the request's sampler decides the path.
+    grammar: True -- a request whose root processors hold a token automaton (make_token_automaton) is speculated too: the
+    drafter knows the grammar -- a looked-up draft is cut at the first id the automaton forbids, and in a state that allows exactly one
+    id that id is drafted, with no look-up and no second model -- and the pass masks every row in the state the drafts before it lead
+    to (Model.spec_step_grammar).  A forced id is a point mass under any sampler, so it is always accepted; `spec_stats["forced"]` counts
+    the drafted ids that came from the forced table.  What configured_tail=True admits is admitted beside the automaton; a request
+    without an automaton behaves as under configured_tail=True.  Not available with a draft model."""
     num_draft: int = 7
     ngram_max: int = 3
     ngram_min: int = 1
     min_draft: int = 5
     configured_tail: bool = False
     draft_model: object = None
+    grammar: bool = False
 
     def __post_init__(self):
         if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= hip_ops.SPEC_MAX_NGRAM:
@@ -162,6 +169,10 @@ class SpeculativeParams:
             raise ValueError(f"SpeculativeParams: 1 <= min_draft <= num_draft <= {hip_ops.SPEC_MAX_ROWS - 1}")
         if not isinstance(self.configured_tail, bool):
             raise ValueError("SpeculativeParams: configured_tail is a bool")
+        if not isinstance(self.grammar, bool):
+            raise ValueError("SpeculativeParams: grammar is a bool")
+        if self.grammar and self.draft_model is not None:
+            raise ValueError("SpeculativeParams: grammar is not available with a draft model")
 
 
 def _speculative_environment(model, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs=None) -> list:
@@ -214,6 +225,22 @@ def check_speculative_tail(model, sampler, processors, structuring_engine, pixel
     return plan
 
 
+_GRAMMAR_REFUSED_PARTS = tuple(row for row in _PASS_REFUSED_PARTS if row[0] != "automaton")
+
+
+def check_speculative_grammar(model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs=None) -> dict:
+    """What generate_step(speculative=SpeculativeParams(grammar=True)) refuses for a request that carries a token automaton, each by name
+    (DESIGN.md 23), and the fused tail plan of what it accepts: what check_speculative_tail accepts, plus the automaton.  A token mask,
+    frequency / presence penalties and DRY stay out of the passes, like everything _speculative_environment refuses."""
+    _refuse("speculative decoding", _speculative_environment(model, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs))
+    plan = _speculative_plan("speculative decoding under a token automaton", model, sampler, processors, structuring_engine, _GRAMMAR_REFUSED_PARTS)
+    if plan.get("automaton") is None:
+        raise ValueError("speculative decoding under a token automaton: the request carries no token automaton (check_speculative_tail's path)")
+    if not hasattr(model, "spec_step_grammar") or not hasattr(model, "set_step_tail"):
+        raise ValueError("speculative decoding under a token automaton is not available with this model (no spec_step_grammar)")
+    return plan
+
+
 def check_speculative_draft(model, draft_model, sampler, processors, structuring_engine, pixel_values, kv_bits, max_kv_size, prompt_logprobs=None):
     """What generate_step(speculative=SpeculativeParams(draft_model=...)) refuses, each by name, and the fused tail plan of
     what it accepts -- None for a greedy request without processors, whose passes are Model.spec_step's.  Besides what
@@ -245,11 +272,24 @@ def _speculative_request_plan(model, draft_model, sp: SpeculativeParams, sampler
     if draft_model is not None:
         return check_speculative_draft(model, draft_model, sampler, root, structuring_engine, pixel_values, kv_bits, max_kv_size)
     all_procs = [p for ps in logits_processors.values() for p in ps]
-    if sp.configured_tail and not (getattr(sampler, "is_greedy", False) and not all_procs):
+    if sp.grammar and any(hasattr(p, "automaton") for p in root):
+        return check_speculative_grammar(model, sampler, root, structuring_engine, pixel_values, kv_bits, max_kv_size)
+    if (sp.configured_tail or sp.grammar) and not (getattr(sampler, "is_greedy", False) and not all_procs):
         return check_speculative_tail(model, sampler, root, structuring_engine, pixel_values, kv_bits, max_kv_size)
     # (a greedy request without processors under configured_tail=True: the greedy path)
     check_speculative(model, sampler, all_procs, structuring_engine, pixel_values, kv_bits, max_kv_size)
     return None
+
+
+def _forced_ids(automaton, state: int, draft: list[int]) -> int:
+    """How many ids of `draft`, walked from `state`, are the forced id of the state they were drafted in (TokenAutomaton.forced())."""
+    forced, n = automaton.forced(), 0
+    for t in draft:
+        if not 0 <= state < automaton.n_states:
+            break
+        n += int(forced[state, 0] == t)
+        state = automaton.step(state, t)
+    return n
 
 
 def _check_generate_args(model, pixel_values, mask, kv_bits, kv_group_size, max_kv_size, top_logprobs, prompt_logprobs, speculative) -> None:
@@ -595,6 +635,9 @@ class InferenceEngine:
             raise ValueError("speculative decoding: the prompt runs past the model's id history")
         self._apply_tail_plan(plan, offset)  # (plan None: the documented greedy tail: the passes refuse anything else)
         self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}
+        if plan is not None and plan.get("automaton") is not None:  # (only check_speculative_grammar's plans hold one)
+            model.reset_step_automaton()  # the request's start state, in stream order, as _inference's first call
+            self.spec_stats["forced"] = 0
         record = partial(self._record_top, [], top_logprobs, max_rows=hip_ops.SPEC_MAX_ROWS)  # record(tokens on the device, rows)
         ids = torch.tensor(host_ids, dtype=torch.int32)
         tok, logprobs, _ = model.step(ids, cache)
@@ -617,19 +660,28 @@ class InferenceEngine:
         the fed-back token and the accepted drafts.
         plan (check_speculative_tail's): the steps are the ordinary configured replayed step and the passes
         Model.spec_step_tail under the plan's sampler / XTC / repetition penalty / logit bias; both draw from one stream position, so
-        token j of the generation is draw j of the seed whichever produced it."""
+        token j of the generation is draw j of the seed whichever produced it.
+        A plan that holds an automaton (check_speculative_grammar's): the drafter's launch is followed by the grammar's, the
+        passes are Model.spec_step_grammar and the steps the ordinary step under the automaton.  The automaton's state is followed on the
+        host from the tokens the loop reads anyway, only to count the forced ids of a draft: nothing more is read back."""
         model, cache = self.model, self.prompt_cache.cache
-        spec_pass = model.spec_step if plan is None else model.spec_step_tail
-        drafter = (int(sp.ngram_max), int(sp.ngram_min), int(sp.num_draft))
+        automaton = None if plan is None or plan.get("automaton") is None else plan["automaton"].automaton
+        spec_pass = model.spec_step if plan is None else model.spec_step_tail if automaton is None else model.spec_step_grammar
+        drafter = (int(sp.ngram_max), int(sp.ngram_min), int(sp.num_draft)) + (() if automaton is None else (True,))
         floor = max(int(sp.min_draft), int(getattr(model, "spec_min_rows", 6)) - 1)
         _, rows, record = self._speculative_prologue(host_ids, plan, top_logprobs)
         model.draft(*drafter)
+        state = None if automaton is None else automaton.start
         while True:
             tokens, count = model.spec_read()
             record(model.spec_tokens, rows)
             yield torch.tensor(tokens, dtype=torch.int32), rows
             fed = tokens[-1]
+            if automaton is not None:
+                state = automaton.walk(tokens, state)  # the device-side state the draft started from
             if count >= floor:
+                if automaton is not None:
+                    self.spec_stats["forced"] += _forced_ids(automaton, state, model.spec_read_draft())
                 _, n, rows = spec_pass(model.spec_draft[:count], cache, then_draft=drafter)
                 self._speculative_pass_done(fed, model.spec_read()[0], count, n)
             else:

@@ -587,6 +587,69 @@ def token_dfa_advance(records: torch.Tensor, states: torch.Tensor, tables: torch
     return states
 
 
+DFA_MAX_DRAFT = 31  # the ids a speculative pass verifies at most (SPEC_MAX_ROWS - 1)
+
+
+def token_dfa_forced(automaton, device=None) -> torch.Tensor:
+    """TokenAutomaton.forced() as the int32 [S, 2] tensor token_dfa_draft takes, on `device` when given."""
+    t = torch.from_numpy(automaton.forced().copy())  # (the cached table is read-only)
+    return t if device is None else t.to(device)
+
+
+def _dfa_one(who: str, record: torch.Tensor, state: torch.Tensor, tables: torch.Tensor) -> None:
+    if _dfa_rows(who, record, state, tables) != 1:
+        raise ValueError(f"{who}: one record (int32 [1, {DFA_WORDS}]) and one state (int32 [1])")
+
+
+def token_dfa_walk(record: torch.Tensor, state: torch.Tensor, tables: torch.Tensor, vocab_size: int, tokens: torch.Tensor,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """pie_token_dfa_walk: the automaton's states along tokens (device int32 [n], 1 <= n <= 31) from `state` (int32 [1], not modified) ->
+    int32 [n + 1]: out[0] = the state, out[i + 1] = token_dfa_advance's result for out[i] and tokens[i].  A state outside the automaton
+    stays what it is; an unarmed record copies the state to every slot.  out: at least n + 1 words to write into."""
+    who = "token_dfa_walk"
+    _dfa_one(who, record, state, tables)
+    _dev(tokens)
+    n = tokens.numel()
+    if tokens.dtype != torch.int32 or not tokens.is_contiguous() or not 1 <= n <= DFA_MAX_DRAFT:
+        raise ValueError(f"{who}: tokens is a contiguous int32 device tensor of 1..{DFA_MAX_DRAFT} ids")
+    if out is None:
+        out = torch.empty(n + 1, dtype=torch.int32, device=tokens.device)
+    _dev(out)
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < n + 1:
+        raise ValueError(f"{who}: out is a contiguous int32 device tensor of at least n + 1 words")
+    _ffi.check(_ffi.load().pie_token_dfa_walk(_ffi.p(record), _ffi.p(state), _ffi.p(tables), tables.numel(), int(vocab_size), _ffi.p(tokens), n, _ffi.p(out),
+                                              _ffi.stream()))
+    return out[:n + 1]
+
+
+def token_dfa_draft(record: torch.Tensor, state: torch.Tensor, tables: torch.Tensor, forced: torch.Tensor, vocab_size: int, cand: torch.Tensor,
+                    cand_count: torch.Tensor, k: int, out: tuple | None = None):
+    """pie_token_dfa_draft, the grammar-aware drafter: forced int32 [S', 2] (token_dfa_forced; a hint, re-derived from the
+    tables), cand int32 [>= 31] a candidate draft and cand_count int32 [1] its length (clamped to 0..31 on the device), k in 1..31 ->
+    (draft int32 [k], count int32 [1]), no host sync: the candidate cut at the first id the grammar forbids, with every forced id put in
+    (a forced id that differs from the candidate ends the candidate's part); an unarmed record or a state outside the automaton passes
+    the candidate through.  out = (draft, count) to write into -- they may be (cand, cand_count) -- else fresh tensors of -1 and 0."""
+    who = "token_dfa_draft"
+    _dfa_one(who, record, state, tables)
+    _dev(forced)
+    if forced.dtype != torch.int32 or not forced.is_contiguous() or forced.dim() != 2 or forced.shape[1] != 2 or forced.shape[0] < 1:
+        raise ValueError(f"{who}: forced is a contiguous int32 [states, 2] device tensor (token_dfa_forced)")
+    if not 1 <= int(k) <= DFA_MAX_DRAFT:
+        raise ValueError(f"{who}: 1 <= k <= {DFA_MAX_DRAFT}")
+    _dev(cand), _dev(cand_count)
+    if cand.dtype != torch.int32 or not cand.is_contiguous() or cand.numel() < DFA_MAX_DRAFT or cand_count.dtype != torch.int32 or cand_count.numel() != 1:
+        raise ValueError(f"{who}: cand is a contiguous int32 device tensor of at least {DFA_MAX_DRAFT} ids and cand_count int32 [1]")
+    if out is None:
+        out = (torch.full((int(k),), -1, dtype=torch.int32, device=cand.device), torch.zeros(1, dtype=torch.int32, device=cand.device))
+    draft, count = out
+    _dev(draft), _dev(count)
+    if draft.dtype != torch.int32 or not draft.is_contiguous() or draft.numel() < int(k) or count.dtype != torch.int32 or count.numel() != 1:
+        raise ValueError(f"{who}: out is (int32 [>= k], int32 [1]) on the device")
+    _ffi.check(_ffi.load().pie_token_dfa_draft(_ffi.p(record), _ffi.p(state), _ffi.p(tables), tables.numel(), _ffi.p(forced), forced.shape[0], int(vocab_size),
+                                               _ffi.p(cand), _ffi.p(cand_count), int(k), _ffi.p(draft), _ffi.p(count), _ffi.stream()))
+    return draft, count
+
+
 def qkv_row_map(n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
     n = (n_heads + 2 * n_kv_heads) * head_dim
     arr = (C.c_int32 * n)()

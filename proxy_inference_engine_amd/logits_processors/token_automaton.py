@@ -49,6 +49,7 @@ class TokenAutomaton:
         if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= int(start) < S:
             raise ValueError(f"TokenAutomaton: start must be a state in [0, {S}), got {start!r}")
         self.cls, self.trans, self.start = cls, trans, int(start)
+        self._forced = None
         self.cls.setflags(write=False)
         self.trans.setflags(write=False)
         # every state reachable from start allows some token: the device never sees an all-zero mask (a class no id maps to allows nothing)
@@ -89,6 +90,25 @@ class TokenAutomaton:
     def words(self) -> np.ndarray:
         """int32 [V + S * C]: cls, then trans row by row -- the device layout."""
         return np.concatenate([self.cls, self.trans.reshape(-1)])
+
+    def forced(self) -> np.ndarray:
+        """int32 [S, 2]: row s = (t, trans[s, cls[t]]) when exactly one id t in [0, V) is allowed in state s -- the masked distribution is
+        a point mass there, and a grammar-aware drafter drafts t without a model -- else (-1, -1).  From the ids per class
+        and the allowed classes per state; computed once."""
+        if self._forced is None:
+            S, C = self.trans.shape
+            per = np.bincount(self.cls, minlength=C).astype(np.int64)        # ids per class
+            live = (self.trans >= 0) & (per[None, :] > 0)                    # the allowed classes that hold an id
+            one = (live * per[None, :]).sum(axis=1) == 1                     # exactly one allowed id: one live class, of one id
+            c = np.argmax(live, axis=1)
+            first = np.full(C, -1, dtype=np.int64)
+            first[self.cls[::-1]] = np.arange(self.vocab_size - 1, -1, -1)   # a class's lowest id (the last write wins)
+            out = np.full((S, 2), -1, dtype=np.int32)
+            out[one, 0] = first[c[one]]
+            out[one, 1] = self.trans[one, c[one]]
+            out.setflags(write=False)
+            self._forced = out
+        return self._forced
 
     # ---------------------------------------------------------------- the host definition of the two device ops
     def allowed(self, state: int) -> np.ndarray:

@@ -548,18 +548,30 @@ class Model(RowsTailState, StepTailState):
         if not isinstance(cache[0], (ReusableKVCache, PagedKVCache)):
             raise ValueError(f"{who}: runs on ReusableKVCache or 16-bit PagedKVCache, not on {type(cache[0]).__name__}")
 
-    def _queue_draft(self, ngram_max: int, ngram_min: int, k: int) -> None:
+    def _queue_draft(self, ngram_max: int, ngram_min: int, k: int, grammar: bool = False) -> None:
         sp = self._spec_state()
         rec = sp["rec"]
         sp["host"] = None
-        hip_ops.ngram_draft(self.fed_ids, rec[self._SPEC_LEN:self._SPEC_LEN + 1], ngram_max, ngram_min, k, workspace=sp["draft_ws"],
-                            out=(rec[self._SPEC_DRAFT:self._SPEC_LEN], rec[self._SPEC_COUNT:self._SPEC_COUNT + 1]))
+        out = (rec[self._SPEC_DRAFT:self._SPEC_LEN], rec[self._SPEC_COUNT:self._SPEC_COUNT + 1])
+        hip_ops.ngram_draft(self.fed_ids, rec[self._SPEC_LEN:self._SPEC_LEN + 1], ngram_max, ngram_min, k, workspace=sp["draft_ws"], out=out)
+        if grammar:
+            # one more launch, in place on the record's draft and count words, from the automaton's device-side state
+            if self._dfa is None:
+                raise ValueError("draft(grammar=True): set_step_tail(token_automaton=...) first")
+            hip_ops.token_dfa_draft(self._dfa_rec, self._dfa_state, self._dfa_arena, self._step_automaton_forced, self.vocab_out, out[0], out[1], k, out=out)
 
-    def draft(self, ngram_max: int = 3, ngram_min: int = 1, k: int = 7):
+    def spec_read_draft(self) -> list[int]:
+        """The ids of the draft spec_read() counted, from the same read-back."""
+        count = self.spec_read()[1]
+        return [int(t) for t in self._spec_state()["host"][self._SPEC_DRAFT:self._SPEC_DRAFT + count]]
+
+    def draft(self, ngram_max: int = 3, ngram_min: int = 1, k: int = 7, grammar: bool = False):
         """The prompt-lookup drafter over the sequence of the cache last stepped (hip_ops.ngram_draft): its ids are `fed_ids` up to the
         position the last chosen token will occupy, which is copied in from `history` on the device -- a fed-back token never visits the
         host.  Queued behind the step, no host sync; returns (spec_draft, count [1]) as device views, and spec_read() then gives
-        ([the last chosen token], count) in one read-back."""
+        ([the last chosen token], count) in one read-back.  grammar=True (needs set_step_tail(token_automaton=...)): one
+        hip_ops.token_dfa_draft launch follows, in place, from the automaton's device-side state -- the looked-up ids are cut at the
+        first one the grammar forbids and every forced id is put in, so a forced run is drafted even when nothing was looked up."""
         pos = self._kv.offset
         if pos is None or not 0 < pos < self.fed_ids.numel():
             raise ValueError("draft: step a prompt first (and stay inside the model's id history)")
@@ -568,7 +580,7 @@ class Model(RowsTailState, StepTailState):
         rec[self._SPEC_TOK:self._SPEC_TOK + 1].copy_(self.history[pos:pos + 1])
         rec[self._SPEC_N:self._SPEC_N + 1].fill_(1)
         rec[self._SPEC_LEN:self._SPEC_LEN + 1].fill_(pos + 1)
-        self._queue_draft(ngram_max, ngram_min, k)
+        self._queue_draft(ngram_max, ngram_min, k, grammar)
         return self.spec_draft, rec[self._SPEC_COUNT:self._SPEC_COUNT + 1]
 
     def spec_step(self, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None = None):
@@ -630,6 +642,28 @@ class Model(RowsTailState, StepTailState):
             nbytes = int(_ffi.load().pie_decoder_spec_tail_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
             sp["tail_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
         return self._spec_pass(who, "pie_decoder_spec_step_tail", "tail_ws", draft_ids, cache, then_draft)
+
+    def spec_step_grammar(self, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None = None):
+        """spec_step_tail under a token automaton (pie_decoder_spec_step_dfa): after set_step_tail(token_automaton=..., and
+        any of sampler / xtc / repetition_penalty / logit_bias) row r is masked in the state the drafts before it lead to -- the automaton
+        is walked along draft_ids on the device --, edited and drawn as spec_step_tail's rows are, and the drafts are accepted while each
+        equals the token of the row before it.  The same returns; afterwards the model, the cache, `fed_ids`, the samplers' stream and
+        the automaton's state are where n calls of step(None) under the same tail would have left them.  then_draft may carry a fourth
+        entry, grammar (Model.draft's).  Without an automaton the pass is spec_step_tail's; a token mask, top_logprobs, frequency /
+        presence penalties and DRY are refused by name, like tensor-parallel models, int8 pages and the other cache kinds."""
+        who = "spec_step_grammar"
+        self._check_speculative_kv(who, cache)
+        for bad, name in ((self._edits[0], "a token mask"), (self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"),
+                          (self._dry is not None, "a DRY penalty")):
+            if bad:
+                raise ValueError(f"{who}: not available with {name}")
+        if self._dfa is None:
+            raise ValueError(f"{who}: no token automaton is set -- the pass without one is spec_step_tail")
+        sp = self._spec_state()
+        if "grammar_ws" not in sp:  # zeroed once, a workspace of its own: the sampler's part is carried from pass to pass
+            nbytes = int(_ffi.load().pie_decoder_spec_dfa_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
+            sp["grammar_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        return self._spec_pass(who, "pie_decoder_spec_step_dfa", "grammar_ws", draft_ids, cache, then_draft)
 
     def spec_step_draft(self, draft_ids: torch.Tensor, q_logprobs: torch.Tensor, cache: list[BaseCache], *, draft_seed: int):
         """One speculative pass over a block a draft MODEL proposed (pie_decoder_spec_step_draft): spec_step_tail's pass and

@@ -28,6 +28,8 @@ class StepTailState:
         self._xtc, self._xtc_rec = None, None
         # the token automaton while the part is on, then its buffers: the arena (cls, then trans), the record, the state, the mask words it writes
         self._dfa, self._dfa_arena, self._dfa_rec, self._dfa_state, self._dfa_mask = None, None, None, None, None
+        # the automaton's forced table (TokenAutomaton.forced()), next to the arena: int32 [capacity, 2], and the states it holds
+        self._dfa_forced, self._dfa_forced_states = None, 0
 
     @property
     def _step_tail_plain(self) -> bool:
@@ -248,6 +250,11 @@ class StepTailState:
             self._dfa_arena = torch.zeros(words.numel(), dtype=torch.int32, device=self.device)
         self._dfa_arena[:words.numel()].copy_(words)
         self._dfa_rec.copy_(hip_ops.token_dfa_records([(0, V, automaton.n_states, automaton.n_classes)]))
+        forced = hip_ops.token_dfa_forced(automaton)  # the grammar-aware drafter's hint: a launch argument of no graph, grown like the arena
+        if self._dfa_forced is None or forced.shape[0] > self._dfa_forced.shape[0]:
+            self._dfa_forced = torch.full((forced.shape[0], 2), -1, dtype=torch.int32, device=self.device)
+        self._dfa_forced[:forced.shape[0]].copy_(forced)
+        self._dfa_forced_states = forced.shape[0]
         if grown or self._dfa is None:
             _ffi.check(lib.pie_decoder_set_token_dfa(self._dec, _ffi.p(self._dfa_rec), _ffi.p(self._dfa_state), _ffi.p(self._dfa_arena), self._dfa_arena.numel(),
                                                      _ffi.p(self._dfa_mask), self._dfa_mask.numel()))
@@ -266,6 +273,11 @@ class StepTailState:
         """(the automaton or None, the state): the state is a device view (int32 [1]) of what the next step will mask with (None before the
         feature was first used)."""
         return self._dfa, self._dfa_state
+
+    @property
+    def _step_automaton_forced(self) -> torch.Tensor | None:
+        """The set automaton's forced table on the device (int32 [S, 2]; hip_ops.token_dfa_draft's hint), None while no automaton is set."""
+        return None if self._dfa is None else self._dfa_forced[:self._dfa_forced_states]
 
     def reset_step_counts(self, start: int, generated_ids=()) -> None:
         """The step's frequency / presence counting starts afresh, in stream order: the counts become the multiplicities of
