@@ -6,7 +6,7 @@ empty, the Python engine serves one sequence).  This is the smallest complete lo
 wait in a queue, join the batch when a slot and enough pages are free -- their prompt rows ride the decode step of the sequences
 in flight (`Model.step_mixed`: both kinds of sequence in one pass over the weights, as BatchDetails holds both), or run as a
 prompt pass of their own when nothing is decoding -- every step decodes all active sequences with one pass over the weights
-(`Model.step_batch`), finished sequences leave and return their pages.  Greedy by default; `generate(sampling=...)` gives every request
+(`Model.step_batch`), finished sequences leave and return their pages.  Every such pass is formed and run by `BatchedEngine._pass`.  Greedy by default; `generate(sampling=...)` gives every request
 its own `SamplingParams`, run per row inside the passes -- its token mask and logit_bias included, and its
 frequency and presence penalties over the counts of what it has generated (DESIGN.md 15);
 `sampler` maps a [B, V] log-probability block to B token ids;
@@ -15,6 +15,7 @@ frequency and presence penalties over the counts of what it has generated (DESIG
 from __future__ import annotations
 
 from collections import deque
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Callable, Iterable
 
@@ -164,6 +165,61 @@ class _Active:
     rec: torch.Tensor | None = None   # int32 [2 (n + 1)] on the device: the top-n record of `token` (ids, then the values' bits); None: not asked for
 
 
+@dataclass
+class _Admitted:
+    """A prompt that holds its slot and its pages and is not yet fully in them: fed whole in one pass, or prefill_chunk rows at a time."""
+    request: int
+    rows: list                    # what is fed: the prompt behind the shared prefix
+    cache: list
+    done: int = 0                 # rows fed so far
+
+
+def per_prompt_counts(value, n_prompts: int, name: str, optional: bool = False) -> list:
+    """generate's `top_logprobs` / `prompt_logprobs`: one value for every prompt or one per prompt, each an int in 0..20 -- or None where
+    `optional`.  ValueError otherwise."""
+    wants = list(value) if isinstance(value, Iterable) else [value] * n_prompts
+    if len(wants) != n_prompts:
+        raise ValueError(f"generate: `{name}` is " + ("None, one int, or one int or None per prompt" if optional else "one int or one per prompt"))
+    if not all((optional and w is None) or (isinstance(w, int) and not isinstance(w, bool) and 0 <= w <= 20) for w in wants):
+        raise ValueError(f"generate: every `{name}` is " + ("None or an int in 0..20" if optional else "an int in 0..20"))
+    return wants
+
+
+def request_kinds(model, n_prompts: int, sampling, top_logprobs, stop_tokens, host_sampler: bool) -> dict:
+    """What one generate() call asks of the passes' per-row state, as _RowSeats' keyword arguments: every request's arguments are checked
+    here, before anything runs (ValueError), and a kind is None -- neither armed nor written -- unless some request asks for it.
+    sampling: generate's; top_logprobs: generate's, None without logprobs=True."""
+    kinds = dict.fromkeys(("tails", "edits", "cnts", "tops", "drys", "xtcs", "autos"))
+    if top_logprobs is not None:
+        if host_sampler:
+            raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
+        kinds["tops"] = per_prompt_counts(top_logprobs, n_prompts, "top_logprobs")
+    if sampling is None:
+        return kinds
+    if host_sampler:
+        raise ValueError("generate: `sampling` and the constructor's `sampler` callable exclude each other")
+    params = [sampling] * n_prompts if isinstance(sampling, SamplingParams) else list(sampling)
+    if len(params) != n_prompts or not all(isinstance(sp, SamplingParams) for sp in params):
+        raise ValueError("generate: `sampling` is one SamplingParams or one per prompt")
+    import os
+    seeds = [int.from_bytes(os.urandom(8), "little") if sp.seed is None else int(sp.seed) for sp in params]
+    for sp, sd in zip(params, seeds):
+        sp.record(0, sd)
+        sp.count_penalties()          # (the record knows nothing of these two: their own range check)
+    asked = lambda each: each if any(e is not None for e in each) else None
+    if any(sp.token_automaton is not None for sp in params):            # (these two need the model's vocabulary)
+        kinds["autos"] = [sp.automaton(model.args.vocab_size) for sp in params]
+    if any(sp.token_mask is not None or sp.logit_bias is not None for sp in params):
+        kinds["edits"] = [sp.edits(model.args.vocab_size) for sp in params]
+    kinds["cnts"] = asked([sp.count_penalties() if sp.counted else None for sp in params])
+    drys = [sp.dry() for sp in params]                    # (checked for every request, armed or not: as XTC is below)
+    kinds["drys"] = asked([d if sp.dried else None for sp, d in zip(params, drys)])
+    kinds["xtcs"] = asked([sp.xtc(stop_tokens) for sp in params])
+    if not all(sp.recordless for sp in params):           # a request with only a mask, a bias or count penalties arms no batch tail
+        kinds["tails"] = (params, seeds)
+    return kinds
+
+
 def pass_targets(prompts: list, wants: list, parts: list) -> tuple[list[int], list[int]]:
     """What the host writes for the prompt rows of one pass (Model.set_prompt_logprobs), in row order.  parts: (request, start, rows) --
     the pass holds rows prompts[request][start : start + rows].  The row of token j has target = token j + 1 of its prompt -- in this
@@ -224,6 +280,18 @@ class _PromptScores:
     def flush(self) -> None:
         if self.pending:
             self.absorb(torch.cat(self.tensors()).cpu().numpy())
+
+
+@contextmanager
+def scored(scores: _PromptScores | None, n_decode: int, parts: list):
+    """Around a pass whose rows n_decode.. are `parts` (pass_targets): armed before it, collected after it.  Nothing without `scores` or
+    without prompt rows, and nothing is collected from a pass that raised."""
+    on = scores is not None and bool(parts)
+    if on:
+        scores.arm(n_decode, parts)
+    yield
+    if on:
+        scores.collect()
 
 
 def same_occupant(have, want) -> bool:
@@ -460,11 +528,7 @@ class BatchedEngine:
         computed once, for no request in particular, and cannot be scored) and with max_new_tokens < 1 (InferenceEngine.score runs a prompt only)."""
         if prompt_logprobs is None:
             return self._run(prompts, max_new_tokens, sampling, logprobs, top_logprobs, None)
-        wants = list(prompt_logprobs) if isinstance(prompt_logprobs, (list, tuple)) else [prompt_logprobs] * len(prompts)
-        if len(wants) != len(prompts):
-            raise ValueError("generate: `prompt_logprobs` is None, one int, or one int or None per prompt")
-        if not all(w is None or (isinstance(w, int) and not isinstance(w, bool) and 0 <= w <= 20) for w in wants):
-            raise ValueError("generate: every `prompt_logprobs` is None or an int in 0..20")
+        wants = per_prompt_counts(prompt_logprobs, len(prompts), "prompt_logprobs", optional=True)
         if self.share_prefix:
             raise ValueError("generate: `prompt_logprobs` and share_prefix=True exclude each other (the shared pages' rows are never computed for a request)")
         if max_new_tokens < 1:
@@ -483,45 +547,65 @@ class BatchedEngine:
 
     def _run(self, prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores):
         """generate's body; scores: the call's _PromptScores or None."""
-        tops = edits = cnts = drys = xtcs = autos = None
-        if logprobs:
-            if self.sampler is not None:
-                raise ValueError("generate: `logprobs` and the constructor's `sampler` callable exclude each other (a host sampler picks the token after the pass)")
-            tops = [top_logprobs] * len(prompts) if isinstance(top_logprobs, int) else list(top_logprobs)
-            if len(tops) != len(prompts):
-                raise ValueError("generate: `top_logprobs` is one int or one per prompt")
-            if not all(isinstance(n, int) and not isinstance(n, bool) and 0 <= n <= 20 for n in tops):
-                raise ValueError("generate: every `top_logprobs` is an int in 0..20")
-        if sampling is not None:
-            if self.sampler is not None:
-                raise ValueError("generate: `sampling` and the constructor's `sampler` callable exclude each other")
-            params = [sampling] * len(prompts) if isinstance(sampling, SamplingParams) else list(sampling)
-            if len(params) != len(prompts) or not all(isinstance(sp, SamplingParams) for sp in params):
-                raise ValueError("generate: `sampling` is one SamplingParams or one per prompt")
-            import os
-            seeds = [int.from_bytes(os.urandom(8), "little") if sp.seed is None else int(sp.seed) for sp in params]
-            for sp, sd in zip(params, seeds):
-                sp.record(0, sd)              # every request's arguments are checked before anything runs
-                sp.count_penalties()          # (the record knows nothing of these two: their own range check)
-            if any(sp.token_automaton is not None for sp in params):   # the per-row automaton records are armed only when some request asks for them
-                autos = [sp.automaton(self.model.args.vocab_size) for sp in params]
-            if any(sp.token_mask is not None or sp.logit_bias is not None for sp in params):
-                edits = [sp.edits(self.model.args.vocab_size) for sp in params]
-            if any(sp.counted for sp in params):   # the per-row counting state is armed only when some request asks for it
-                cnts = [sp.count_penalties() if sp.counted else None for sp in params]
-            dry_all = [sp.dry() for sp in params]   # (checked for every request, armed or not)
-            if any(sp.dried for sp in params):     # the per-row DRY state is armed only when some request asks for it
-                drys = [d if sp.dried else None for sp, d in zip(params, dry_all)]
-            xtc_all = [sp.xtc(self.stop_tokens) for sp in params]   # (checked for every request, armed or not)
-            if any(x is not None for x in xtc_all):   # the per-row XTC records are armed only when some request asks for them
-                xtcs = xtc_all
-            if all(sp.recordless for sp in params):
-                sampling = None               # no record to configure: a request with only a mask, a bias or count penalties arms no batch tail
+        kinds = request_kinds(self.model, len(prompts), sampling, top_logprobs if logprobs else None, self.stop_tokens, self.sampler is not None)
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
-        with _RowSeats(self.model, self.max_batch, prompts, None if sampling is None else (params, seeds), edits, cnts, tops, drys, xtcs, autos) as seats:
+        with _RowSeats(self.model, self.max_batch, prompts, **kinds) as seats:
             out = self._generate(prompts, max_new_tokens, seats, scores)
-        return out if tops is None else (out, seats.maps)
+        return out if seats.tops is None else (out, seats.maps)
+
+    def _pass(self, seats: _RowSeats, scores, P: int, active: list, parts: list) -> list:
+        """One pass over the weights: a decode step of `active` (_Active, in row order) and, behind them, parts = (_Admitted, rows) -- the next
+        `rows` rows of each admitted prompt.  Seats the output rows, arms and collects the prompt scores, picks the Model entry, counts the
+        pass, lets the host sampler redraw, and hands every row its token and top-n record: the decode rows in place; the prompts that this
+        pass finished are returned as new _Active.  P: the shared prefix in force (such prompts continue cached pages).
+        A token is a row view of the pass's result: the varlen passes return fresh tensors, and step_batch's buffer, which the model owns per
+        batch size, is next written by the next iteration's decode step -- after that iteration's read-back."""
+        nb = len(active)
+        ends = [p.done + n == len(p.rows) for p, n in parts]                # a part that does not finish its prompt produces no token: seated None
+        seats.seat([a.request for a in active] + [p.request if end else None for (p, _), end in zip(parts, ends)], active)
+        tokens, caches = torch.cat([a.token for a in active]) if active else None, [a.cache for a in active]
+        rows, into = [p.rows[p.done:p.done + n] for p, n in parts], [p.cache for p, _ in parts]
+        with scored(scores, nb, [(p.request, p.done, n) for p, n in parts]):
+            if not parts:
+                nxt, logprobs, _ = self.model.step_batch(tokens, caches)
+            elif not active and not self.prefill_chunk and P == 0:          # fresh whole prompts alone (int8 pages take prompts through this entry only)
+                nxt, logprobs, _ = self.model.prefill_batch(rows, into)
+            else:
+                nxt, logprobs, _ = self.model.step_mixed(tokens, caches, rows, into)
+        self.steps += bool(active or self.prefill_chunk)                     # a decode step, or the chunked pass (which stands for one)
+        self.mixed_passes += bool(active and parts)
+        if self.sampler is not None:
+            # the sampler sees generation steps only: the decode rows and the rows of prompts whose LAST chunk is in this pass; the row
+            # of a prompt that is still filling is discarded (its greedy id stands in), so a seeded sampler's stream and a stateful
+            # sampler's history do not depend on the chunk size
+            live = list(range(nb)) + [nb + i for i, end in enumerate(ends) if end]
+            if live:
+                some = len(live) < nb + len(parts)
+                idx = torch.tensor(live, dtype=torch.long, device=logprobs.device) if some else slice(None)   # (every row: the block itself)
+                drawn = self.sampler(logprobs[idx]).reshape(-1).to(torch.int32)
+                if some:
+                    nxt[idx] = drawn                                         # (only a pass with prompt rows has such rows: its result is a fresh tensor)
+                else:
+                    nxt = drawn
+        recs = seats.records(nb + len(parts))
+        for i, a in enumerate(active):
+            a.token, a.rec = nxt[i:i + 1], recs[i]
+        joined = []
+        for i, ((p, n), end) in enumerate(zip(parts, ends), nb):
+            p.done += n
+            if end:                                                          # the row's token is the request's first
+                joined.append(_Active(p.request, p.cache, nxt[i:i + 1], rec=recs[i]))
+        return joined
+
+    def _lone_prompt(self, scores, p: _Admitted) -> _Active:
+        """The one prompt pass that is not a batch pass: a lone prompt whose request needs no per-row state (_RowSeats.lone_step) through the
+        single-sequence Model.step -- nothing to seat, no top-n record."""
+        with scored(scores, 0, [(p.request, 0, len(p.rows))]):              # (record i belongs to row i of the prompt)
+            tok, logprobs, _ = self.model.step(torch.as_tensor(p.rows, dtype=torch.int32).reshape(-1).to(self.model.device), p.cache)
+        if self.sampler is not None:
+            tok = self.sampler(logprobs[None]).reshape(1).to(torch.int32)
+        return _Active(p.request, p.cache, tok.reshape(1).clone())
 
     def _generate(self, prompts: list, max_new_tokens: int, seats: _RowSeats, scores=None) -> list[list[int]]:
         for p in prompts:
@@ -555,19 +639,13 @@ class BatchedEngine:
                 return self.model.make_cache()
             seq = root[0].page_manager.fork()                               # whole pages: add_ref only, nothing is copied
             return [type(root[0])(seq, i) for i in range(len(root))]
-        filling: list = []            # chunked prefill: [request, prompt, cache, rows done] of admitted prompts not yet fully in their pages
+        filling: list[_Admitted] = []   # chunked prefill: the admitted prompts not yet fully in their pages, oldest first
         tops = seats.tops
-        seat = lambda rows: seats.seat(rows, active)   # (the loop below rebinds `active`: read when called)
-        lone_step, records = seats.lone_step, seats.records
-
-        def scored(n_decode: int | None = None, parts: list | None = None) -> None:
-            """Around a pass that carries prompt rows: with arguments before it (the rows n_decode.. hold `parts`, as pass_targets takes
-            them), without after it.  Nothing without `scores`."""
-            if scores is not None:
-                scores.arm(n_decode, parts) if parts is not None else scores.collect()
+        run = lambda rows, parts: self._pass(seats, scores, P, rows, parts)
+        whole = lambda admitted: [(p, len(p.rows)) for p in admitted]
 
         while pending or active or filling:
-            # every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
+            # 1. every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
             if active:
                 # one read-back per pass for the stop / length checks -- and, in the same copy, the tokens' top-n records
                 n_top = sum(a.rec.numel() for a in active) if tops is not None else 0
@@ -588,8 +666,8 @@ class BatchedEngine:
                     else:
                         keep.append(a)
                 active = keep
-            # admit while there is a slot and the pool can hold the request to its end; the admitted prompts run as ONE pass
-            batch = []
+            # 2. admit while there is a slot and the pool can hold the request to its end; the admitted prompts run as ONE pass
+            batch: list[_Admitted] = []
             rows = 0
             while pending and len(active) + len(batch) + len(filling) < self.max_batch:
                 idx, prompt = pending[0]
@@ -600,122 +678,43 @@ class BatchedEngine:
                 need[idx] = n_pages
                 reserved += n_pages
                 rows += len(prompt) - P
-                batch.append((idx, prompt[P:] if P else prompt, new_cache()))
+                batch.append(_Admitted(idx, prompt[P:] if P else prompt, new_cache()))
             if self.prefill_chunk:
-                filling += [[idx, prompt, cache, 0] for idx, prompt, cache in batch]
-                batch = []
+                filling, batch = filling + batch, []
             if not active and not batch and not filling:
                 if pending:
                     raise RuntimeError("no request fits the page pool")  # unreachable after the check above
                 break
-            if filling:
-                # one pass: every decoding sequence's step + the next rows of the filling prompts, oldest first, prefill_chunk rows in all (decode rows included)
-                take, budget = [], max(1, self.prefill_chunk - len(active))   # the pass's rows INCLUDING the decode rows: a chunk of 256 + 8 decode rows would cost the GEMMs a second 256-row tile
-                for f in filling:
-                    n = min(len(f[1]) - f[3], budget)
-                    if n > 0:
-                        take.append((f, n))
-                        budget -= n
-                seat([a.request for a in active] + [f[0] if f[3] + n == len(f[1]) else None for f, n in take])
-                scored(len(active), [(f[0], f[3], n) for f, n in take])
-                nxt, logprobs, _ = self.model.step_mixed(torch.cat([a.token for a in active]) if active else None, [a.cache for a in active],
-                                                         [f[1][f[3]:f[3] + n] for f, n in take], [f[2] for f, _ in take])
-                scored()
-                self.steps += 1
-                self.mixed_passes += bool(active)
-                nb = len(active)
-                recs = records(nb + len(take))
-                if self.sampler is not None:
-                    # the sampler sees generation steps only: the decode rows and the rows of prompts whose LAST chunk is in this pass; the row
-                    # of a prompt that is still filling is discarded (its greedy id stands in), so a seeded sampler's stream and a stateful
-                    # sampler's history do not depend on the chunk size
-                    live = list(range(nb)) + [nb + i for i, (f, n) in enumerate(take) if f[3] + n == len(f[1])]
-                    if live:
-                        idx = torch.tensor(live, dtype=torch.long, device=logprobs.device)
-                        nxt = nxt.clone()
-                        nxt[idx] = self.sampler(logprobs[idx]).reshape(-1).to(torch.int32)
-                for i, a in enumerate(active):
-                    a.token, a.rec = nxt[i:i + 1], recs[i]
-                for i, (f, n) in enumerate(take):
-                    f[3] += n
-                    if f[3] == len(f[1]):                                 # its last chunk: the row's token is the request's first
-                        active.append(_Active(f[0], f[2], nxt[nb + i:nb + i + 1], rec=recs[nb + i]))
-                filling = [f for f in filling if f[3] < len(f[1])]
-                continue
-            # Worth it while the decode rows do not push the prompt rows into another 256-row GEMM tile: 8 sequences + a prompt of
+            # 3. the passes of this iteration.  Admitted prompts ride the decode step of the sequences in flight (one pass over the weights for both)
+            # while the decode rows do not push the prompt rows into another 256-row GEMM tile: 8 sequences + a prompt of
             # 8 / 64 / 192 / 256 / 384 rows on the 8B model take 0.61 / 0.76 / 0.75 / 0.97 / 0.84 of a prompt pass + a step, but
             # 508 / 2048 rows take 1.08 / 1.06 (516 rows are three 256-row tiles' worth of work for the GEMMs, 508 are two).
             n_mix = len(active) + rows
-            if active and batch and self.mixed and (n_mix <= 512 or (n_mix + 255) // 256 == (rows + 255) // 256):
-                # the admitted prompts ride the decode step of the sequences in flight: one pass over the weights for both
-                seat([a.request for a in active] + [idx for idx, _, _ in batch])
-                scored(len(active), [(idx, 0, len(p)) for idx, p, _ in batch])
-                nxt, logprobs, _ = self.model.step_mixed(torch.cat([a.token for a in active]), [a.cache for a in active],
-                                                         [p for _, p, _ in batch], [c for _, _, c in batch])
-                scored()
-                self.steps += 1
-                self.mixed_passes += 1
-                if self.sampler is not None:
-                    nxt = self.sampler(logprobs).reshape(-1).to(torch.int32)
-                nb = len(active)
-                recs = records(nb + len(batch))
-                for i, a in enumerate(active):
-                    a.token, a.rec = nxt[i:i + 1], recs[i]
-                for i, (idx, _, cache) in enumerate(batch):
-                    active.append(_Active(idx, cache, nxt[nb + i:nb + i + 1], rec=recs[nb + i]))
-                continue
-            joined = []
-            if self._i8 and batch and (len(batch) == 1 or not self.batch_prefill):
-                for idx, prompt, cache in batch:
-                    seat([idx])
-                    scored(0, [(idx, 0, len(prompt))])
-                    toks, logprobs, _ = self.model.prefill_batch([prompt], [cache])
-                    scored()
-                    if self.sampler is not None:
-                        toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
-                    joined.append(_Active(idx, cache, toks[:1].clone(), rec=records(1)[0]))
-            elif P and batch:                                            # suffixes behind the shared prefix: prompts continuing a cached prefix
-                seat([idx for idx, _, _ in batch])
-                toks, logprobs, _ = self.model.step_mixed(None, [], [p for _, p, _ in batch], [c for _, _, c in batch])
-                if self.sampler is not None:
-                    toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
-                recs = records(len(batch))
-                for i, (idx, _, cache) in enumerate(batch):
-                    joined.append(_Active(idx, cache, toks[i:i + 1].clone(), rec=recs[i]))
-            elif len(batch) == 1 or (batch and not self.batch_prefill):
-                for idx, prompt, cache in batch:
-                    scored(0, [(idx, 0, len(prompt))])                    # (either pass below: record i belongs to row i of the prompt)
-                    if not lone_step(idx):                                # its first token is drawn by its own sampler: a batch of one
-                        seat([idx])
-                        toks, _, _ = self.model.prefill_batch([prompt], [cache])
-                        scored()
-                        joined.append(_Active(idx, cache, toks[:1].clone(), rec=records(1)[0]))
-                        continue
-                    ids = torch.as_tensor(prompt, dtype=torch.int32).reshape(-1)
-                    tok, logprobs, _ = self.model.step(ids.to(self.model.device), cache)
-                    scored()
-                    if self.sampler is not None:
-                        tok = self.sampler(logprobs[None]).reshape(1).to(torch.int32)
-                    joined.append(_Active(idx, cache, tok.reshape(1).clone()))
-            elif batch:
-                seat([idx for idx, _, _ in batch])
-                scored(0, [(idx, 0, len(p)) for idx, p, _ in batch])
-                toks, logprobs, _ = self.model.prefill_batch([p for _, p, _ in batch], [c for _, _, c in batch])
-                scored()
-                if self.sampler is not None:
-                    toks = self.sampler(logprobs).reshape(-1).to(torch.int32)
-                recs = records(len(batch))
-                for i, (idx, _, cache) in enumerate(batch):
-                    joined.append(_Active(idx, cache, toks[i:i + 1].clone(), rec=recs[i]))
-            if active:
-                seat([a.request for a in active])
-                nxt, logprobs, _ = self.model.step_batch(torch.cat([a.token for a in active]), [a.cache for a in active])
-                self.steps += 1
-                if self.sampler is not None:
-                    nxt = self.sampler(logprobs).reshape(-1).to(torch.int32)
-                recs = records(len(active))
-                for i, a in enumerate(active):
-                    a.token, a.rec = nxt[i:i + 1], recs[i]
+            mix = active and batch and self.mixed and (n_mix <= 512 or (n_mix + 255) // 256 == (rows + 255) // 256)
+            if filling:
+                # one pass: every decoding sequence's step + the next rows of the filling prompts, oldest first, prefill_chunk rows in all (decode rows included)
+                take, budget = [], max(1, self.prefill_chunk - len(active))   # the pass's rows INCLUDING the decode rows: a chunk of 256 + 8 decode rows would cost the GEMMs a second 256-row tile
+                for p in filling:
+                    n = min(len(p.rows) - p.done, budget)
+                    if n > 0:
+                        take.append((p, n))
+                        budget -= n
+                joined = run(active, take)
+                filling = [p for p in filling if p.done < len(p.rows)]
+            elif mix:
+                joined = run(active, whole(batch))
+            else:
+                # the prompts in passes of their own -- one each for a single prompt and without batch_prefill, unless they continue the
+                # shared prefix; else jointly --, then the decode step
+                if batch and not P and (len(batch) == 1 or not self.batch_prefill):
+                    joined = []
+                    for p in batch:                                       # (int8 pages are written by the batch passes only)
+                        joined += [self._lone_prompt(scores, p)] if not self._i8 and seats.lone_step(p.request) else run([], whole([p]))
+                else:
+                    joined = run([], whole(batch)) if batch else []
+                if active:
+                    run(active, [])
+            # 4. the prompts that finished decode from the next pass on
             active += joined
         if root is not None:
             root[0].page_manager.release()
