@@ -1129,6 +1129,63 @@ int pie_paged_attn_decode_i8(const void *q, const void *slab, size_t n_pages, co
                              const int32_t *context_lens, int B, int n_heads, int n_kv_heads, int head_dim, float scale, int dtype,
                              void *out, void *workspace, void *stream);
 
+/* ---------------------------------------------------------------- batched speculation
+ * One verify pass for B decode-state sequences on T pages: sequence s presents 1 + m_s rows (0 <= m_s <= 7), its fed token and its
+ * drafts.  Throughout, seg_first DEVICE int32 [B + 1] cuts the pass's N rows into segments: sequence s owns rows seg_first[s] ..
+ * seg_first[s + 1] - 1, 1..8 consecutive rows, none for an idle slot; every kernel clamps what it reads of it into [0, N] and to 8 rows.
+ *
+ * pie_paged_attn_verify: q, out T [N, n_heads, head_dim]; slab, block_tables [B, max_blocks] as pie_paged_attn_decode takes them;
+ *   row_seq DEVICE int32 [N] = the block-table row of row r's sequence (read at a segment's first row, clamped to [0, B)),
+ *   row_context_lens DEVICE int32 [N] = the positions row r attends INCLUDING its own (clamped to [0, 64 max_blocks]; 0: the row's output
+ *   is zeros).  Row r attends positions 0 .. row_context_lens[r] - 1 of its sequence's pages -- the caller has appended the pass's own rows
+ *   already -- so inside a segment, whose context lengths rise by one per row, no row sees its successors.  One launch for all segments
+ *   over (n_kv_heads, splits, B) workgroups: the positions of a segment's longest row are cut into `splits` parts the way
+ *   pie_paged_attn_decode cuts a sequence's, a part's K / V rows are read ONCE for all rows of the segment and all heads of the kv-group,
+ *   positions at or behind the longest context are never used; fp32 online softmax, one rounding at the end.  splits > 1: one merge
+ *   launch follows.  splits: 1..32, or 0 = pie_paged_attn_verify_splits(B, n_kv_heads, max_blocks), enough workgroups for two per CU
+ *   and never more than max_blocks.  A row that belongs to no segment keeps an unspecified output.
+ *   workspace: pie_paged_attn_verify_workspace_bytes(N, n_heads, head_dim, splits) bytes with the splits the call will use (0 for
+ *   refused sizes), 16-byte aligned, no initialisation.  head_dim 64 / 128, n_heads / n_kv_heads 1..8, N and B 1..65535.  Before any
+ *   launch: a NULL pointer, a dtype that is neither PIE_BF16 nor PIE_F16, splits outside 0..32: PIE_E_ARG; a bad shape: PIE_E_SHAPE;
+ *   q, slab, out or workspace not 16-byte aligned, an index array not 4-byte aligned: PIE_E_ALIGN.
+ * pie_ngram_draft_rows: pie_ngram_draft's rule on B sequences in one call, two launches, no atomics: ids DEVICE int32 [B, cap], len
+ *   DEVICE int32 [B] (each clamped on the device to [0, cap]) -> out_ids DEVICE int32 [B, k], out_count DEVICE int32 [B]; row s is bit
+ *   for bit what pie_ngram_draft returns for (ids[s], len[s]) alone.  workspace: pie_ngram_draft_rows_workspace_bytes(B) bytes, 4-byte
+ *   aligned.  B 1..4096; the other bounds and codes are pie_ngram_draft's.
+ * pie_spec_verify_rows: logits T [n_rows, V]; draft_ids DEVICE int32 [B, draft_stride >= 1]: sequence s's m_s drafts (m_s = its rows
+ *   - 1: the segments carry the counts; a row behind the draft_stride ids the array holds has no draft and ends the run).  Row r's greedy token a_r is pie_logprobs_argmax's of that row alone (the same partials and
+ *   merge: no second softmax).  Per sequence, by pie_spec_verify's rule: n_acc = the longest run draft[i] == a_i (an id outside [0, V)
+ *   is never accepted and never used as an index), out_n [B] = n_acc + 1 (0 for an idle slot), out_tokens [B, 8] = a_0 .. a_n_acc, then
+ *   -1.  ids / len (nullable, together): DEVICE int32 [B, cap] / [B], the drafter's input, whose ids[s, len[s] - 1] is the token the pass
+ *   was fed: the accept launch writes the out_n tokens behind it and len[s] += out_n[s] (both clamped to cap), so the next
+ *   pie_ngram_draft_rows can be queued behind the pass before the host reads anything.  Three launches.  workspace:
+ *   pie_spec_verify_rows_workspace_bytes(n_rows) bytes, 16-byte aligned, no initialisation.  n_rows 1..65535, B 1..4096.
+ * pie_decoder_spec_step_batch: one pass over the weights.  tokens DEVICE int32 [B] = every sequence's fed token; row_context_lens,
+ *   row_seq [N], slabs / n_pages / slab_bytes / block_tables / max_blocks as pie_decoder_step_mixed takes them (the pages must reach
+ *   every row's position).  In order: the input ids gathered on the device (an id the embedding could not index is fed as 0); the
+ *   several-prompts pass's body on the N rows with RoPE + append into each sequence's pages; pie_paged_attn_verify's launches once per
+ *   layer; the lm_head over all N rows into the workspace; pie_spec_verify_rows with seq_ids / seq_len / seq_cap as its ids / len / cap.
+ *   N <= 256 (one tile of the streaming GEMM) and N <= 8 B.  PIE_E_STATE before any launch, each by name: int8 pages, a
+ *   tensor-parallel decoder, any configured batch tail, edits, counts, DRY, XTC, automaton or top-logprobs state, prompt scoring.
+ *   Nothing is captured in a graph, and a decoder that never calls this entry launches exactly what it launches without it.
+ *   workspace: pie_decoder_spec_batch_workspace_bytes(d) bytes, 16-byte aligned, no initialisation. */
+int pie_paged_attn_verify_splits(int B, int n_kv_heads, int max_blocks);
+size_t pie_paged_attn_verify_workspace_bytes(int N, int n_heads, int head_dim, int splits);
+int pie_paged_attn_verify(const void *q, const void *slab, size_t n_pages, const int32_t *block_tables, int max_blocks, const int32_t *row_seq,
+                          const int32_t *row_context_lens, const int32_t *seg_first, int N, int B, int n_heads, int n_kv_heads, int head_dim, float scale,
+                          int dtype, int splits, void *out, void *workspace, void *stream);
+size_t pie_ngram_draft_rows_workspace_bytes(int B);
+int pie_ngram_draft_rows(const int32_t *ids, const int32_t *len, int B, int cap, int ngram_max, int ngram_min, int k, int32_t *out_ids, int32_t *out_count,
+                         void *workspace, void *stream);
+size_t pie_spec_verify_rows_workspace_bytes(int n_rows);
+int pie_spec_verify_rows(const void *logits, int n_rows, int V, int dtype, const int32_t *seg_first, int B, const int32_t *draft_ids, int draft_stride,
+                         int32_t *out_tokens, int32_t *out_n, int32_t *ids, int32_t *len, int cap, void *workspace, void *stream);
+size_t pie_decoder_spec_batch_workspace_bytes(const pie_decoder *d);
+int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride, const int32_t *row_context_lens,
+                                const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages, size_t slab_bytes,
+                                const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, int32_t *seq_ids, int32_t *seq_len, int seq_cap,
+                                void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- quantized KV cache (QuantizedKVCache, cache/kv_cache/quantized.py)
  * The reference's format: every cached row stored as mx.quantize output -- codes uint32 [n_kv_heads, capacity, head_dim*bits/32],
  * scales / biases T [n_kv_heads, capacity, head_dim/group_size] (B = 1).  bits 4 / 8, group_size 32 / 64 / 128 dividing head_dim,

@@ -59,6 +59,8 @@ EXPORTS = [
     "pie_spec_verify_sampled_workspace_bytes", "pie_spec_verify_sampled", "pie_decoder_spec_tail_workspace_bytes", "pie_decoder_spec_step_tail",
     "pie_spec_verify_draft_workspace_bytes", "pie_spec_verify_draft", "pie_decoder_spec_draft_workspace_bytes", "pie_decoder_spec_step_draft",
     "pie_token_dfa_walk", "pie_token_dfa_draft", "pie_decoder_spec_dfa_workspace_bytes", "pie_decoder_spec_step_dfa",
+    "pie_paged_attn_verify_splits", "pie_paged_attn_verify_workspace_bytes", "pie_paged_attn_verify", "pie_ngram_draft_rows_workspace_bytes", "pie_ngram_draft_rows",
+    "pie_spec_verify_rows_workspace_bytes", "pie_spec_verify_rows", "pie_decoder_spec_batch_workspace_bytes", "pie_decoder_spec_step_batch",
 ]
 
 
@@ -246,6 +248,20 @@ def load() -> C.CDLL:
     lib.pie_decoder_spec_draft_workspace_bytes.restype = C.c_size_t
     lib.pie_decoder_spec_draft_workspace_bytes.argtypes = [C.c_void_p, C.c_int]
     lib.pie_decoder_spec_step_draft.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_paged_attn_verify_splits.argtypes = [C.c_int] * 3
+    lib.pie_paged_attn_verify_workspace_bytes.restype = C.c_size_t
+    lib.pie_paged_attn_verify_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.pie_paged_attn_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.pie_ngram_draft_rows_workspace_bytes.restype = C.c_size_t
+    lib.pie_ngram_draft_rows_workspace_bytes.argtypes = [C.c_int]
+    lib.pie_ngram_draft_rows.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4
+    lib.pie_spec_verify_rows_workspace_bytes.restype = C.c_size_t
+    lib.pie_spec_verify_rows_workspace_bytes.argtypes = [C.c_int]
+    lib.pie_spec_verify_rows.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_decoder_spec_batch_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_spec_batch_workspace_bytes.argtypes = [C.c_void_p]
+    lib.pie_decoder_spec_step_batch.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [
+        C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

@@ -90,6 +90,11 @@ struct RowsTail {
     }
     // some part rewrites or masks the logits behind the lm_head: partials its epilogue left are stale
     bool edits_logits() const { return sampler.table || edits.rows_cap || counts.records || dry.records || dfa.records; }
+    // The batched speculative pass (pie_decoder_spec_step_batch) is greedy and raw: every configured part is refused by name.
+    const char *spec_refused() const {
+        return sampler.table ? "a batch tail" : dfa.records ? "batch token automata" : edits.rows_cap ? "batch logits edits" : counts.records ? "a batch count penalty"
+               : dry.records ? "a batch DRY penalty" : xtc.records ? "batch XTC records" : top.n ? "batch top log-probabilities" : nullptr;
+    }
 };
 
 // The single-sequence step's configured tail, applied where the tail writes the bound outputs and pie_decoder::tail_raw is

@@ -19,6 +19,8 @@
 
 #include "decoder.hpp"
 #include "gemm_rows.hpp"  // the many-row GEMM family of w4m_gemm.hip: W4mRope, W4lSlabs, the int4 entry (prefill_attn.hpp comes with it)
+#include "paged_attn_verify.hpp"
+#include "speculative.hpp"
 
 // ---------------------------------------------------------------- kernels
 // W4S -> T row-major [N, K]; one thread per code word (8 weights, 16 B out).  Same arithmetic as k_dequantize_w4g64.
@@ -1126,6 +1128,100 @@ extern "C" int pie_decoder_step_mixed(pie_decoder *d, const int32_t *ids, const 
     PIE_REQUIRE(n_decode >= 0 && n_decode <= S, PIE_E_SHAPE, "pie_decoder_step_mixed: n_decode must be between 0 and the number of output rows");
     return varlen_batch(d, ids, row_context_lens, row_seq, seg_lo, seg_hi, out_rows, N, S, n_decode, slabs, n_pages, slab_bytes, block_tables,
                         max_blocks, logits, logprobs, next_tokens, stream, n_chunks, chunks_host);
+}
+
+// ---------------------------------------------------------------- one speculative pass for B decode-state sequences
+// Sequence s presents 1 + m_s consecutive rows (segment s of seg_first): its fed token, then its drafts.  The pass is the several-prompts
+// pass's body on those N rows -- embed, linear_rows / mlp_rows, RoPE + append into each sequence's own pages -- with ONE attention launch
+// per layer for all segments (paged_attn_verify.hip) where that pass runs a segment kernel and a launch per chunk, the lm_head on ALL N
+// rows (s->xn holds them final-normed, in row order: nothing to gather) and the segmented verify behind it.
+static size_t align16z(size_t n) { return (n + 15) & ~(size_t)15; }
+
+template <class T>
+static int spec_batch_t(pie_decoder *d, const int32_t *fed, const int32_t *row_ctx, const int32_t *row_seq, const int32_t *seg_first, int N, int B,
+                        const void *const *slabs, int n_pages, const int32_t *block_tables, int max_blocks, u16 *logits, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
+    const int splits = paged_attn_verify_splits(B, c.n_kv_heads, max_blocks);
+    int rc = scratch_reserve(d, N, w16_copy_elems(c, true), splits > d->splits ? splits : d->splits);
+    if (rc) return rc;
+    PrefillScratch *s = d->prefill;
+    if ((rc = embed_rows(d, fed, N, s->x, st))) return rc;
+    hipLaunchKernelGGL(k_rope_cs_rows, dim3(N), dim3(64), 0, st, d->glob.rope_freqs, nullptr, row_ctx, D / 2, s->rope_cs);
+    PIE_LAUNCH_CHECK();
+    for (int li = 0; li < c.n_layers; ++li) {
+        const pie_layer_weights &w = d->layers[li];
+        if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, N, H, c.dtype, s->xn, st))) return rc;
+        RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
+        qkv_opts.bias = w.bqkv, qkv_opts.slabs = !w.bqkv;
+        RowsDone qkv_done;
+        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, N, s->qkv, st, qkv_opts, &qkv_done))) return rc;
+        const W4lSlabs &sq = qkv_done.slabs;
+        const auto rope_k = rope_append_kernel<T>(sq.S > 1, false);
+        hipLaunchKernelGGL(rope_k, dim3(N, sq.S > 1 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers, c.n_heads,
+                           c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, row_ctx, max_blocks, (u16 *)slabs[li], row_seq,
+                           (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, (size_t)0);
+        PIE_LAUNCH_CHECK();
+        VerifyAttnArgs a = {};  // every row attends its sequence's pages, which now hold the pass's own rows
+        a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.row_seq = row_seq, a.row_ctx = row_ctx, a.seg_first = seg_first;
+        a.N = N, a.B = B, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.bt_stride = max_blocks, a.n_pages = n_pages, a.splits = splits;
+        a.scale = 1.0f / sqrtf((float)D), a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
+        if ((rc = paged_attn_verify_launch(c.dtype, D, a, st))) return rc;
+        if ((rc = mlp_rows<T>(d, w, N, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
+    }
+    RowsOpts head_opts;
+    head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
+    return linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, N, logits, st, head_opts);
+}
+
+// workspace: the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows' workspace for 256 rows
+extern "C" size_t pie_decoder_spec_batch_workspace_bytes(const pie_decoder *d) {
+    if (!d) return 0;
+    return align16z((size_t)SPEC_BATCH_ROWS * d->cfg.vocab * 2) + align16z(sizeof(int) * SPEC_BATCH_ROWS) + spec_verify_rows_workspace_bytes(SPEC_BATCH_ROWS);
+}
+
+extern "C" int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride, const int32_t *row_context_lens,
+                                           const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages,
+                                           size_t slab_bytes, const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, int32_t *seq_ids,
+                                           int32_t *seq_len, int seq_cap, void *workspace, void *stream) {
+    const char *who = "pie_decoder_spec_step_batch: ";
+    PIE_REQUIRE(d && tokens && draft_ids && row_context_lens && row_seq && seg_first && slabs && block_tables && out_tokens && out_n && workspace, PIE_E_ARG,
+                std::string(who) + "null pointer");
+    PIE_REQUIRE((seq_ids == nullptr) == (seq_len == nullptr) && (seq_ids ? seq_cap >= 1 : seq_cap == 0), PIE_E_ARG,
+                std::string(who) + "seq_ids [B, seq_cap >= 1] and seq_len come together or not at all");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, std::string(who) + "not available on a tensor-parallel shard");
+    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, std::string(who) + "not available on int8 KV pages");
+    const char *part = d->rows.spec_refused();
+    PIE_REQUIRE(!part, PIE_E_STATE, std::string(who) + "not available with " + part);
+    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, std::string(who) + "not available with prompt scoring");
+    PIE_REQUIRE(d->glob_set, PIE_E_STATE, std::string(who) + "set_globals must be called first");
+    for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, std::string(who) + "a layer has no weights (pie_decoder_set_layer)");
+    PIE_REQUIRE(B >= 1 && N >= B && N <= SPEC_BATCH_ROWS && N <= SPEC_SEG_ROWS * B && draft_stride >= 1 && max_blocks > 0 && n_pages > 0 &&
+                    n_pages < 0x7FFFFFFFu, PIE_E_SHAPE,
+                std::string(who) + "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool");
+    PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE, std::string(who) + "the slabs are smaller than n_pages T pages");
+    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, std::string(who) + "hidden must be a multiple of 8, at most 8192");
+    PIE_REQUIRE(d->cfg.head_dim == 64 || d->cfg.head_dim == 128, PIE_E_SHAPE, std::string(who) + "head_dim must be 64 or 128");
+    const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
+    PIE_REQUIRE(rep >= 1 && rep <= 8 && rep * d->cfg.n_kv_heads == d->cfg.n_heads, PIE_E_SHAPE, std::string(who) + "n_heads / n_kv_heads must be between 1 and 8");
+    PIE_REQUIRE(pie_aligned(tokens, 4) && pie_aligned(draft_ids, 4) && pie_aligned(row_context_lens, 4) && pie_aligned(row_seq, 4) && pie_aligned(seg_first, 4) &&
+                    pie_aligned(block_tables, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(seq_ids, 4) && pie_aligned(seq_len, 4),
+                PIE_E_ALIGN, std::string(who) + "4-byte alignment required");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, std::string(who) + "workspace needs 16-byte alignment");
+    for (int i = 0; i < d->cfg.n_layers; ++i) PIE_REQUIRE(slabs[i] && pie_aligned(slabs[i], 16), PIE_E_ALIGN, std::string(who) + "null or misaligned slab");
+    hipStream_t st = (hipStream_t)stream;
+    const int V = d->cfg.vocab;
+    u16 *logits = (u16 *)workspace;
+    int *fed = (int *)((char *)workspace + align16z((size_t)SPEC_BATCH_ROWS * V * 2));
+    void *verify_ws = (char *)fed + align16z(sizeof(int) * SPEC_BATCH_ROWS);
+    // a row no segment covers is fed id 0 (seg_first is device memory: nothing here can check it)
+    PIE_HIP_TRY(hipMemsetAsync(fed, 0, sizeof(int) * (size_t)N, st));
+    if (int rc = spec_gather_rows_launch(tokens, draft_ids, draft_stride, seg_first, B, N, d->embed_vocab(), fed, st)) return rc;
+    const int rc = d->cfg.dtype == PIE_BF16
+                       ? spec_batch_t<BF16>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st)
+                       : spec_batch_t<F16>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st);
+    if (rc) return rc;
+    return spec_verify_rows_launch(logits, N, V, d->cfg.dtype, seg_first, B, draft_ids, draft_stride, out_tokens, out_n, seq_ids, seq_len, seq_cap, verify_ws, st);
 }
 
 static int decode_batch(pie_decoder *d, const int32_t *tokens, const int32_t *ctx_len, const void *const *slabs, int n_pages, const int32_t *block_tables,

@@ -65,8 +65,10 @@ __device__ __forceinline__ int match_len(const int *ids, const int *suffix, int 
     return n;
 }
 
+// blockIdx.y (pie_ngram_draft_rows; 0 for the one-sequence op): the sequence -- its row of ids [B, cap], its len, its row of the partials
 __global__ void __launch_bounds__(NGRAM_T) k_ngram_search(const int *ids, const int *len, int cap, int nmax, int nmin, unsigned *partials) {
     __shared__ unsigned s_best[NGRAM_T / 64];
+    ids += (size_t)blockIdx.y * cap, len += blockIdx.y, partials += (size_t)blockIdx.y * gridDim.x;
     const int L = clamp_len(len, cap);
     int suffix[SPEC_MAX_NGRAM];
 #pragma unroll
@@ -87,6 +89,8 @@ __global__ void __launch_bounds__(NGRAM_T) k_ngram_pick(const int *ids, const in
                                                         int *out_ids, int *out_count) {
     __shared__ unsigned s_best[NGRAM_T / 64];
     __shared__ int s_draft[SPEC_MAX_ROWS];
+    // blockIdx.x: the sequence (pie_ngram_draft_rows; one workgroup for the one-sequence op)
+    ids += (size_t)blockIdx.x * cap, len += blockIdx.x, partials += (size_t)blockIdx.x * n_partials, out_ids += (size_t)blockIdx.x * k, out_count += blockIdx.x;
     unsigned best = 0u;
     for (int i = threadIdx.x; i < n_partials; i += NGRAM_T) best = max(best, partials[i]);
 #pragma unroll
@@ -175,6 +179,58 @@ __global__ void __launch_bounds__(256) k_spec_accept(const SpecArgs a) {
     if (a.logprobs) logits_write_logprobs<T>(a.logits + (size_t)r * a.V, a.V, a.lse[r], a.logprobs + (size_t)r * a.V);
     if (r != 0 || blockIdx.x != 0 || threadIdx.x != 0) return;
     spec_commit(a.s, a.tok, a.rows, n_acc, a.out_tokens, a.out_n);
+}
+
+// ---------------------------------------------------------------- the segmented verify of a batched pass
+// pie_spec_verify_rows' workspace: the partials of every row, then the rows' tokens and log-sum-exps
+struct SpecRowsLayout {
+    size_t tok, lse, bytes;
+    explicit SpecRowsLayout(int n_rows) {
+        tok = sizeof(LogitStat) * TAIL_STAT_TILES * (size_t)n_rows;
+        lse = tok + sizeof(int) * (size_t)n_rows;
+        bytes = (lse + sizeof(float) * (size_t)n_rows + 15) & ~(size_t)15;
+    }
+};
+
+struct SpecRowsArgs {
+    int N, B, V;
+    const int *seg_first;  // [B + 1]
+    const int *draft;      // [B, draft_stride]: sequence s's drafts, as many as it has rows behind its first
+    int draft_stride;
+    const int *tok;        // [N]: the rows' greedy tokens
+    int *out_tokens;       // [B, SPEC_SEG_ROWS]
+    int *out_n;            // [B]
+    int *ids;              // nullable, [B, cap]: the sequences' ids, the drafter's input
+    int *len;              // [B]
+    int cap;
+};
+
+// Thread s is sequence s: pie_spec_verify's rule on its own rows (spec_count_accepted, at most 7 comparisons), then its tokens behind its
+// ids.  An idle slot (no rows): out_n = 0.  seg_first is device memory: the rows are clamped into [0, N] and to 8 before anything is read.
+__global__ void __launch_bounds__(64) k_spec_accept_rows(const SpecRowsArgs a) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.B) return;
+    int r0 = a.seg_first[s], r1 = a.seg_first[s + 1];
+    r0 = r0 < 0 ? 0 : (r0 > a.N ? a.N : r0);
+    r1 = r1 < r0 ? r0 : (r1 > a.N ? a.N : r1);
+    const int rows = r1 - r0 > SPEC_SEG_ROWS ? SPEC_SEG_ROWS : r1 - r0;
+    int *out = a.out_tokens + (size_t)s * SPEC_SEG_ROWS;
+    if (rows == 0) {
+        for (int i = 0; i < SPEC_SEG_ROWS; ++i) out[i] = -1;
+        a.out_n[s] = 0;
+        return;
+    }
+    const int *tok = a.tok + r0;
+    // (a row behind the drafts the stride holds has no draft: it ends the run like a refused one)
+    const int n_acc = spec_count_accepted(a.draft + (size_t)s * a.draft_stride, tok, rows > a.draft_stride + 1 ? a.draft_stride + 1 : rows, a.V);
+    for (int i = 0; i < SPEC_SEG_ROWS; ++i) out[i] = i <= n_acc ? tok[i] : -1;
+    a.out_n[s] = n_acc + 1;
+    if (!a.ids) return;
+    // ids[s, len - 1] is the token this pass was fed; the chosen tokens follow it, the last of them being the next pass's input
+    int L = a.len[s];
+    L = L < 0 ? 0 : (L > a.cap ? a.cap : L);
+    for (int i = 0; i <= n_acc && L + i < a.cap; ++i) a.ids[(size_t)s * a.cap + L + i] = tok[i];
+    a.len[s] = L + n_acc + 1 > a.cap ? a.cap : L + n_acc + 1;
 }
 
 // ---------------------------------------------------------------- the verify under a sampler
@@ -376,6 +432,50 @@ static int spec_verify_sampled_launch(u16 *logits, int rows, int V, int dtype, c
     const SpecSampledArgs a = {rows, V, draft, tok, out_tokens, out_n, base, draws ? counter : nullptr, s};
     if (dfa) hipLaunchKernelGGL(k_spec_accept_dfa, dim3(1), dim3(64), 0, st, a, *dfa);
     else hipLaunchKernelGGL(k_spec_accept_sampled, dim3(1), dim3(64), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+size_t spec_verify_rows_workspace_bytes(int n_rows) { return n_rows < 1 || n_rows > 65535 ? 0 : SpecRowsLayout(n_rows).bytes; }
+
+// pie_spec_verify_rows' three launches (arguments already checked): pie_spec_verify's partials and merge over every row, then one thread per sequence
+int spec_verify_rows_launch(const u16 *logits, int N, int V, int dtype, const int *seg_first, int B, const int *draft, int draft_stride, int *out_tokens,
+                            int *out_n, int *ids, int *len, int cap, void *workspace, hipStream_t st) {
+    const SpecRowsLayout lay(N);
+    LogitStat *stats = (LogitStat *)workspace;
+    int *tok = (int *)((char *)workspace + lay.tok);
+    float *lse = (float *)((char *)workspace + lay.lse);
+    const SpecRowsArgs a = {N, B, V, seg_first, draft, draft_stride, tok, out_tokens, out_n, ids, len, cap};
+    return launch_for_dtype(dtype, "spec verify rows:", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_logits_stats<T>, dim3(TAIL_STAT_TILES, (unsigned)N), dim3(256), 0, st, logits, V, stats);
+        hipLaunchKernelGGL(k_spec_merge, dim3((unsigned)N), dim3(256), 0, st, (const LogitStat *)stats, tok, lse);
+        hipLaunchKernelGGL(k_spec_accept_rows, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, a);
+    });
+}
+
+namespace {
+
+// pie_decoder_spec_step_batch's input rows: sequence s's first row is its fed token, the rows behind it its drafts; an id the embedding
+// could not index is fed as id 0 (the verify reads the caller's draft, where such an id ends the accepted run)
+__global__ void __launch_bounds__(64) k_spec_gather_rows(const int *tokens, const int *draft, int draft_stride, const int *seg_first, int B, int N, int vocab,
+                                                         int *fed) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= B) return;
+    int r0 = seg_first[s], r1 = seg_first[s + 1];
+    r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
+    r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
+    const int rows = r1 - r0 > SPEC_SEG_ROWS ? SPEC_SEG_ROWS : r1 - r0;
+    for (int i = 0; i < rows; ++i) {
+        const int id = i == 0 ? tokens[s] : (i - 1 < draft_stride ? draft[(size_t)s * draft_stride + i - 1] : 0);
+        fed[r0 + i] = id >= 0 && id < vocab ? id : 0;
+    }
+}
+
+}  // namespace
+
+int spec_gather_rows_launch(const int *tokens, const int *draft, int draft_stride, const int *seg_first, int B, int N, int vocab, int *fed, hipStream_t st) {
+    hipLaunchKernelGGL(k_spec_gather_rows, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, tokens, draft, draft_stride, seg_first, B, N, vocab, fed);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
@@ -668,6 +768,43 @@ int pie_spec_verify(const void *logits, int rows, int V, int dtype, const int32_
     PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_spec_verify: workspace needs 16-byte alignment");
     PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_spec_verify: dtype must be PIE_BF16 or PIE_F16");
     return spec_verify_launch((const u16 *)logits, rows, V, dtype, draft, out_tokens, out_n, logprobs, workspace, SpecState(), (hipStream_t)stream);
+}
+
+size_t pie_ngram_draft_rows_workspace_bytes(int B) { return B < 1 || B > SPEC_MAX_SEQS ? 0 : sizeof(unsigned) * NGRAM_MAX_WGS * (size_t)B; }
+
+int pie_ngram_draft_rows(const int32_t *ids, const int32_t *len, int B, int cap, int ngram_max, int ngram_min, int k, int32_t *out_ids, int32_t *out_count,
+                         void *workspace, void *stream) {
+    PIE_REQUIRE(ngram_min >= 1 && ngram_min <= ngram_max && ngram_max <= SPEC_MAX_NGRAM, PIE_E_ARG, "pie_ngram_draft_rows: need 1 <= ngram_min <= ngram_max <= 8");
+    PIE_REQUIRE(k >= 1 && k <= SPEC_MAX_ROWS - 1, PIE_E_ARG, "pie_ngram_draft_rows: k must be 1..31");
+    PIE_REQUIRE(ids && len && out_ids && out_count && workspace, PIE_E_ARG, "pie_ngram_draft_rows: null pointer");
+    PIE_REQUIRE(B >= 1 && B <= SPEC_MAX_SEQS, PIE_E_SHAPE, "pie_ngram_draft_rows: B must be 1..4096");
+    PIE_REQUIRE(cap >= 1 && cap <= SPEC_MAX_IDS, PIE_E_SHAPE, "pie_ngram_draft_rows: cap must be 1..2^27");
+    PIE_REQUIRE(pie_aligned(ids, 4) && pie_aligned(len, 4) && pie_aligned(out_ids, 4) && pie_aligned(out_count, 4) && pie_aligned(workspace, 4), PIE_E_ALIGN,
+                "pie_ngram_draft_rows: 4-byte alignment required");
+    hipStream_t st = (hipStream_t)stream;
+    const int wgs = (cap + NGRAM_IDS_PER_WG - 1) / NGRAM_IDS_PER_WG;  // pie_ngram_draft's grid per sequence: the same partials, the same maximum
+    const int G = wgs < 1 ? 1 : (wgs > NGRAM_MAX_WGS ? NGRAM_MAX_WGS : wgs);
+    hipLaunchKernelGGL(k_ngram_search, dim3((unsigned)G, (unsigned)B), dim3(NGRAM_T), 0, st, ids, len, cap, ngram_max, ngram_min, (unsigned *)workspace);
+    PIE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ngram_pick, dim3((unsigned)B), dim3(NGRAM_T), 0, st, ids, len, cap, (const unsigned *)workspace, G, k, out_ids, out_count);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+size_t pie_spec_verify_rows_workspace_bytes(int n_rows) { return spec_verify_rows_workspace_bytes(n_rows); }
+
+int pie_spec_verify_rows(const void *logits, int n_rows, int V, int dtype, const int32_t *seg_first, int B, const int32_t *draft_ids, int draft_stride,
+                         int32_t *out_tokens, int32_t *out_n, int32_t *ids, int32_t *len, int cap, void *workspace, void *stream) {
+    PIE_REQUIRE(logits && seg_first && draft_ids && out_tokens && out_n && workspace, PIE_E_ARG, "pie_spec_verify_rows: null pointer");
+    PIE_REQUIRE((ids == nullptr) == (len == nullptr) && (ids || cap == 0) && (!ids || cap >= 1), PIE_E_ARG, "pie_spec_verify_rows: ids [B, cap >= 1] and len come together or not at all");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, "pie_spec_verify_rows: dtype must be PIE_BF16 or PIE_F16");
+    PIE_REQUIRE(n_rows >= 1 && n_rows <= 65535 && V >= 1 && B >= 1 && B <= SPEC_MAX_SEQS && draft_stride >= 1, PIE_E_SHAPE,
+                "pie_spec_verify_rows: need 1 <= n_rows <= 65535, V >= 1, 1 <= B <= 4096 and draft_stride >= 1");
+    PIE_REQUIRE(pie_aligned(logits, 2) && pie_aligned(seg_first, 4) && pie_aligned(draft_ids, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) &&
+                    pie_aligned(ids, 4) && pie_aligned(len, 4), PIE_E_ALIGN, "pie_spec_verify_rows: logits need 2-byte, the index arrays and the outputs 4-byte alignment");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_spec_verify_rows: workspace needs 16-byte alignment");
+    return spec_verify_rows_launch((const u16 *)logits, n_rows, V, dtype, seg_first, B, draft_ids, draft_stride, out_tokens, out_n, ids, len, cap, workspace,
+                                   (hipStream_t)stream);
 }
 
 size_t pie_spec_verify_sampled_workspace_bytes(int rows, int V) {

@@ -7,6 +7,9 @@
 constexpr int SPEC_MAX_ROWS = 32;   // rows of one verify pass: the fed token and up to 31 drafts
 constexpr int SPEC_MAX_NGRAM = 8;   // the drafter's longest suffix
 constexpr int SPEC_MAX_IDS = 1 << 27;  // the drafter's search key packs (match length, end position) into 32 bits
+constexpr int SPEC_SEG_ROWS = 8;    // rows of one sequence in a batched pass: the fed token and up to 7 drafts
+constexpr int SPEC_MAX_SEQS = 4096;  // sequences of one pie_ngram_draft_rows / pie_spec_verify_rows call
+constexpr int SPEC_BATCH_ROWS = 256;  // rows of one batched pass: one tile of the streaming GEMM
 
 // What the accept launch does besides the op's outputs when the block came from the decoder's own pass (all device memory; state == nullptr:
 // the op alone).  Before the launch state->pos = o + rows and the pass's tail has run; after it the decoder is where `n` greedy steps from
@@ -32,3 +35,11 @@ size_t spec_verify_workspace_bytes(int rows);
 // the op's three launches (arguments already checked)
 int spec_verify_launch(const u16 *logits, int rows, int V, int dtype, const int *draft, int *out_tokens, int *out_n, float *logprobs, void *workspace,
                        const SpecState &s, hipStream_t st);
+
+// The batched pass (pie_decoder_spec_step_batch in prefill.hip).  pie_spec_verify_rows' three launches (arguments already
+// checked): segment s = rows seg_first[s] .. seg_first[s + 1] - 1 of logits [N, V] against draft [B, draft_stride]; ids / len nullable.
+size_t spec_verify_rows_workspace_bytes(int n_rows);
+int spec_verify_rows_launch(const u16 *logits, int N, int V, int dtype, const int *seg_first, int B, const int *draft, int draft_stride, int *out_tokens,
+                            int *out_n, int *ids, int *len, int cap, void *workspace, hipStream_t st);
+// fed [N] = the pass's input ids: every segment's fed token (tokens [B]), then its drafts
+int spec_gather_rows_launch(const int *tokens, const int *draft, int draft_stride, const int *seg_first, int B, int N, int vocab, int *fed, hipStream_t st);

@@ -163,6 +163,90 @@ class _Active:
     token: torch.Tensor           # [1] int32 on the device: the input of the next step
     generated: list = field(default_factory=list)
     rec: torch.Tensor | None = None   # int32 [2 (n + 1)] on the device: the top-n record of `token` (ids, then the values' bits); None: not asked for
+    fresh: list | None = None     # batched speculation: the tokens the last pass chose, already on the host (the last of them is `token`); None: read `token` back
+
+
+SPEC_SEG_DRAFTS, SPEC_PASS_ROWS = 7, 256   # drafts of one sequence in a batched speculative pass; rows of the pass (hip_ops.SPEC_SEG_ROWS - 1, SPEC_BATCH_ROWS)
+
+
+def spec_plan(counts: list, room: list, min_draft: int) -> list:
+    """The drafts m_s every decode row presents in one batched speculative pass.  counts[s]: the ids the drafter found for
+    row s (0: none, or none that is still valid); room[s]: the tokens the request may still generate.  m_s = count_s where count_s >=
+    min_draft, else 0; then the three clamps: m_s <= 7; m_s <= room_s (the pass writes positions up to the fed token's + m_s, and the
+    request's pages are reserved only as far as len(prompt) + max_new_tokens); sum(1 + m_s) <= 256, the largest drafts shortened first
+    (the lowest row among equals)."""
+    m = [min(c if c >= min_draft else 0, SPEC_SEG_DRAFTS, max(r, 0)) for c, r in zip(counts, room)]
+    while len(m) + sum(m) > SPEC_PASS_ROWS and any(m):
+        m[m.index(max(m))] -= 1
+    return m
+
+
+def cut_run(generated: list, tokens: list, stop_tokens, max_new_tokens: int) -> bool:
+    """Appends the tokens one pass chose for a request to `generated`, in order, up to and including the first stop token or the
+    max_new_tokens-th token: what lies behind that cut is dropped.  True: the request retires."""
+    for t in tokens:
+        generated.append(int(t))
+        if int(t) in stop_tokens or len(generated) >= max_new_tokens:
+            return True
+    return False
+
+
+class _SpecSeats:
+    """Batched speculation's per-seat state of one generate() call.  Seat s is row s of the decode passes.  ids [max_batch,
+    cap] / len [max_batch] on the device hold the ids of the request in the seat -- its prompt and what it has generated, the last id being
+    the input of its next pass; a row is uploaded when its occupant changes (a request takes the seat, or moves to it when another retires)
+    and is moved on by the passes themselves otherwise: the speculative pass's accept launch appends what it chose, a plain step's tokens
+    are appended by one scatter.  Behind every decode pass ONE drafter launch over the seats is queued (Model.draft_rows); its counts come
+    to the host with the pass's own read-back, and a draft counts only for the (request, tokens generated) it was made for."""
+
+    def __init__(self, model, params, max_batch: int, prompts: list, max_new_tokens: int):
+        self.model, self.p, self.prompts, self.max_new = model, params, prompts, max_new_tokens
+        dev = model.device
+        self.cap = max(len(p) for p in prompts) + max_new_tokens + SPEC_SEG_DRAFTS + 1   # a run may pass max_new_tokens before the host cuts it
+        self.ids = torch.zeros((max_batch, self.cap), dtype=torch.int32, device=dev)
+        self.len = torch.zeros(max_batch, dtype=torch.int32, device=dev)
+        self.drafts = torch.full((max_batch, int(params.num_draft)), -1, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(max_batch, dtype=torch.int32, device=dev)
+        self.held: list = [None] * max_batch      # (request, tokens generated) whose ids seat s holds
+        self.drafted: list = [None] * max_batch   # (request, tokens generated) the draft in seat s was made for
+        self.host_counts: list = [0] * max_batch  # that draft's count, once read
+        self.pending = 0                          # seats whose counts are still on the device (a plain step's drafter launch)
+
+    def sync(self, active: list) -> None:
+        """Before a pass of decode rows only: every seat holds its occupant's ids."""
+        for s, a in enumerate(active):
+            want = (a.request, len(a.generated))
+            if self.held[s] != want:
+                seq = torch.tensor(list(self.prompts[a.request]) + a.generated, dtype=torch.int32)
+                self.ids[s, :seq.numel()].copy_(seq)
+                self.len[s:s + 1].fill_(seq.numel())
+                self.held[s] = want
+        for s in range(len(active), len(self.held)):
+            self.held[s] = self.drafted[s] = None
+
+    def plan(self, active: list) -> list:
+        counts = [self.host_counts[s] if self.drafted[s] == (a.request, len(a.generated)) else 0 for s, a in enumerate(active)]
+        return spec_plan(counts, [self.max_new - len(a.generated) for a in active], self.p.min_draft)
+
+    def moved(self, active: list, n: list) -> None:
+        """After a decode pass that chose n[s] tokens for seat s and queued the drafter behind them."""
+        for s, a in enumerate(active):
+            self.held[s] = self.drafted[s] = (a.request, len(a.generated) + n[s])
+
+    def stale(self) -> None:
+        """After a pass that moved the requests without moving the seats (it carried prompt rows): every seat is uploaded again."""
+        self.held = [None] * len(self.held)
+        self.drafted = [None] * len(self.held)
+        self.pending = 0
+
+    def after_step(self, active: list, nxt: torch.Tensor) -> None:
+        """Behind a plain step of the seats: its tokens go behind the seats' ids on the device, and the drafter is queued."""
+        B = len(active)
+        self.ids[:B].scatter_(1, self.len[:B].long().clamp_(max=self.cap - 1)[:, None], nxt[:B, None])
+        self.len[:B] += 1
+        self.model.draft_rows(self.ids[:B], self.len[:B], self.p.ngram_max, self.p.ngram_min, self.p.num_draft, out=(self.drafts[:B], self.counts[:B]))
+        self.moved(active, [1] * B)
+        self.pending = B
 
 
 @dataclass
@@ -478,9 +562,28 @@ class _RowSeats:
 class BatchedEngine:
     def __init__(self, model, num_pages: int = 1024, max_batch: int = 32, stop_tokens: Iterable[int] = (),
                  sampler: Callable[[torch.Tensor], torch.Tensor] | None = None, batch_prefill: bool = True, max_prefill_rows: int = 4096,
-                 kv_dtype: torch.dtype | None = None, kv_scales=None, mixed: bool = True, prefill_chunk: int | None = None, share_prefix: bool = False):
+                 kv_dtype: torch.dtype | None = None, kv_scales=None, mixed: bool = True, prefill_chunk: int | None = None, share_prefix: bool = False,
+                 speculative=None):
         """kv_dtype=torch.int8 (+ kv_scales = (k, v) float16 [n_layers, n_kv_heads]): the pool holds the reference KVPage's int8 pages with
-        per-head scales (page.hpp:25-32) -- half the cache bytes per token, so twice the sequences / context per pool."""
+        per-head scales (page.hpp:25-32) -- half the cache bytes per token, so twice the sequences / context per pool.
+        speculative=SpeculativeParams(num_draft=, ngram_max=, ngram_min=, min_draft=): greedy prompt-lookup speculation for
+        every request at once.  Behind every decode pass one drafter launch looks every sequence's last ids up in the sequence itself; an
+        iteration of decode rows only then gives sequence s 1 + m_s rows of ONE pass over the weights (Model.spec_step_batch) -- m_s = its
+        draft where that has at least min_draft ids, at most 7, else 0 -- and accepts each draft while it equals the greedy token of the
+        row before it; an iteration in which no sequence has a draft is the replayed step as ever, and an iteration that carries prompt
+        rows runs without drafts.  The tokens are greedy decoding's; `spec_stats` counts the passes.  None: today's engine exactly.
+        ValueError, by name: a `sampler`, kv_dtype=torch.int8, a tensor-parallel model, num_draft > 7, draft_model, grammar and
+        configured_tail; generate() then refuses any request whose SamplingParams is not plain, logprobs, top_logprobs and prompt_logprobs."""
+        if speculative is not None:
+            who = "BatchedEngine(speculative=...): "
+            for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8, "kv_dtype=torch.int8 (int8 KV pages)"),
+                              (getattr(model, "tp", None) is not None, "a tensor-parallel model"), (int(speculative.num_draft) > SPEC_SEG_DRAFTS, "num_draft > 7"),
+                              (speculative.draft_model is not None, "draft_model"), (bool(speculative.grammar), "grammar"),
+                              (bool(speculative.configured_tail), "configured_tail")):
+                if bad:
+                    raise ValueError(who + "not available with " + name)
+        self.speculative = speculative
+        self.spec_stats = {"passes": 0, "steps": 0, "drafted": 0, "accepted": 0}   # of the last generate(): speculative passes, plain decode passes, ids drafted / accepted
         self.model = model
         self.pool = model.enable_paged_kv(num_pages=num_pages, kv_dtype=kv_dtype, kv_scales=kv_scales)
         self._i8 = self.pool.dtype == torch.int8   # int8 pages are written by the batch paths only: lone prompts go through prefill_batch too
@@ -526,6 +629,17 @@ class BatchedEngine:
         (InferenceEngine.score's list).  Scored inside the prompt passes (Model.set_prompt_logprobs), across prefill_chunk
         boundaries, and fetched in the per-pass read-back of the tokens.  ValueError with share_prefix=True (the shared pages' rows are
         computed once, for no request in particular, and cannot be scored) and with max_new_tokens < 1 (InferenceEngine.score runs a prompt only)."""
+        if self.speculative is not None:
+            who = "generate: batched speculation is greedy and raw -- not available with "
+            params = [] if sampling is None else [sampling] if isinstance(sampling, SamplingParams) else list(sampling)
+            if any(not (isinstance(sp, SamplingParams) and sp.plain) for sp in params):
+                raise ValueError(who + "a request whose `sampling` is not plain (a sampler, penalty, mask, bias or automaton)")
+            if logprobs:
+                raise ValueError(who + "`logprobs`")
+            if not (isinstance(top_logprobs, int) and top_logprobs == 0):
+                raise ValueError(who + "`top_logprobs`")
+            if prompt_logprobs is not None:
+                raise ValueError(who + "`prompt_logprobs`")
         if prompt_logprobs is None:
             return self._run(prompts, max_new_tokens, sampling, logprobs, top_logprobs, None)
         wants = per_prompt_counts(prompt_logprobs, len(prompts), "prompt_logprobs", optional=True)
@@ -598,6 +712,31 @@ class BatchedEngine:
                 joined.append(_Active(p.request, p.cache, nxt[i:i + 1], rec=recs[i]))
         return joined
 
+    def _spec_decode(self, spec: _SpecSeats, seats: _RowSeats, scores, P: int, active: list) -> None:
+        """An iteration of decode rows only under batched speculation: the seats' ids are brought up to date, every row
+        gets its drafts (spec_plan), and the iteration is ONE speculative pass -- or, where no row has a draft, the replayed step untouched,
+        its tokens appended to the seats' ids on the device.  Either way the next drafter launch is queued behind it."""
+        spec.sync(active)
+        m = spec.plan(active)
+        if not any(m):
+            self._pass(seats, scores, P, active, [])
+            spec.after_step(active, torch.cat([a.token for a in active]))
+            self.spec_stats["steps"] += 1
+            return
+        seats.seat([a.request for a in active], active)
+        sp = self.speculative
+        n, toks, nxt = self.model.spec_step_batch(torch.cat([a.token for a in active]), [a.cache for a in active], spec.drafts, m, spec.ids, spec.len,
+                                                  then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts))
+        spec.moved(active, n)
+        spec.host_counts[:len(active)] = nxt
+        last = torch.tensor([t[-1] for t in toks], dtype=torch.int32, device=self.model.device)   # (the record is on the host already: one small upload)
+        for s, (a, t) in enumerate(zip(active, toks)):
+            a.fresh, a.token = t, last[s:s + 1]
+        self.steps += 1
+        self.spec_stats["passes"] += 1
+        self.spec_stats["drafted"] += sum(m)
+        self.spec_stats["accepted"] += sum(n) - len(n)
+
     def _lone_prompt(self, scores, p: _Admitted) -> _Active:
         """The one prompt pass that is not a batch pass: a lone prompt whose request needs no per-row state (_RowSeats.lone_step) through the
         single-sequence Model.step -- nothing to seat, no top-n record."""
@@ -641,25 +780,34 @@ class BatchedEngine:
             return [type(root[0])(seq, i) for i in range(len(root))]
         filling: list[_Admitted] = []   # chunked prefill: the admitted prompts not yet fully in their pages, oldest first
         tops = seats.tops
+        spec = _SpecSeats(self.model, self.speculative, self.max_batch, prompts, max_new_tokens) if self.speculative is not None and prompts else None
+        self.spec_stats = dict.fromkeys(self.spec_stats, 0)
         run = lambda rows, parts: self._pass(seats, scores, P, rows, parts)
         whole = lambda admitted: [(p, len(p.rows)) for p in admitted]
 
         while pending or active or filling:
             # 1. every active sequence holds one token not yet recorded (from its prompt or from the last pass): record, retire
-            if active:
+            if active and spec is not None and all(a.fresh is not None for a in active):
+                chosen = [a.fresh for a in active]   # a speculative pass read its own record back: nothing is left on the device
+            elif active:
                 # one read-back per pass for the stop / length checks -- and, in the same copy, the tokens' top-n records
                 n_top = sum(a.rec.numel() for a in active) if tops is not None else 0
-                host = torch.cat([a.token for a in active] + ([a.rec for a in active] if tops is not None else []) + (scores.tensors() if scores else [])).cpu().numpy()
+                counts = [spec.counts[:spec.pending]] if spec is not None and spec.pending else []   # (the counts of the draft queued behind a plain step)
+                host = torch.cat([a.token for a in active] + ([a.rec for a in active] if tops is not None else []) + (scores.tensors() if scores else []) + counts).cpu().numpy()
+                if counts:
+                    spec.host_counts[:spec.pending], host, spec.pending = host[-spec.pending:].tolist(), host[:-spec.pending], 0
                 if scores:
                     scores.absorb(host[len(active) + n_top:])
                 if tops is not None:
                     recs = host[len(active):len(active) + n_top].reshape(len(active), 2, -1)
                     for a, r in zip(active, recs):
                         seats.maps[a.request].append(host_record_to_map(r[0], r[1].view(np.float32), tops[a.request])[1])
+                chosen = [[t] if a.fresh is None else a.fresh for a, t in zip(active, host[:len(active)].tolist())]   # (fresh: a speculative pass's run beside newly joined prompts)
+            if active:
                 keep = []
-                for a, t in zip(active, host[:len(active)].tolist()):
-                    a.generated.append(int(t))
-                    if int(t) in self.stop_tokens or len(a.generated) >= max_new_tokens:
+                for a, run_tokens in zip(active, chosen):
+                    a.fresh = None
+                    if cut_run(a.generated, run_tokens, self.stop_tokens, max_new_tokens):   # (a plain pass's one token; a speculative pass's run, cut)
                         out[a.request] = a.generated
                         a.cache[0].page_manager.release()
                         reserved -= need.pop(a.request)
@@ -690,6 +838,7 @@ class BatchedEngine:
             # 8 / 64 / 192 / 256 / 384 rows on the 8B model take 0.61 / 0.76 / 0.75 / 0.97 / 0.84 of a prompt pass + a step, but
             # 508 / 2048 rows take 1.08 / 1.06 (516 rows are three 256-row tiles' worth of work for the GEMMs, 508 are two).
             n_mix = len(active) + rows
+            carried = False               # this iteration's decode rows rode a pass that carried prompt rows
             mix = active and batch and self.mixed and (n_mix <= 512 or (n_mix + 255) // 256 == (rows + 255) // 256)
             if filling:
                 # one pass: every decoding sequence's step + the next rows of the filling prompts, oldest first, prefill_chunk rows in all (decode rows included)
@@ -701,8 +850,10 @@ class BatchedEngine:
                         budget -= n
                 joined = run(active, take)
                 filling = [p for p in filling if p.done < len(p.rows)]
+                carried = bool(active)
             elif mix:
                 joined = run(active, whole(batch))
+                carried = True
             else:
                 # the prompts in passes of their own -- one each for a single prompt and without batch_prefill, unless they continue the
                 # shared prefix; else jointly --, then the decode step
@@ -712,8 +863,13 @@ class BatchedEngine:
                         joined += [self._lone_prompt(scores, p)] if not self._i8 and seats.lone_step(p.request) else run([], whole([p]))
                 else:
                     joined = run([], whole(batch)) if batch else []
-                if active:
+                if active and spec is not None:
+                    self._spec_decode(spec, seats, scores, P, active)
+                elif active:
                     run(active, [])
+            if spec is not None and carried:                            # decode rows rode a pass with prompt rows: plain rows, and they moved on without their seats
+                spec.stale()
+                self.spec_stats["steps"] += 1
             # 4. the prompts that finished decode from the next pass on
             active += joined
         if root is not None:

@@ -1533,3 +1533,112 @@ def sdpa_decode_ring(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_new: t
     _ffi.check(lib.pie_sdpa_decode_ring(_ffi.p(q.contiguous()), _ffi.p(k), _ffi.p(v), _ffi.p(stage), Hq, Hkv, cap, D, pos, window, keep, rot0,
                                         float(scale), _ffi.dtype_code(q.dtype), _ffi.p(out), _ffi.p(ws), _ffi.stream()))
     return out
+
+
+# ---------------------------------------------------------------- batched speculation
+SPEC_SEG_ROWS, SPEC_BATCH_ROWS = 8, 256   # rows of one sequence in a batched pass (the fed token and up to 7 drafts); rows of the pass
+
+
+def paged_attn_verify_splits(B: int, n_kv_heads: int, max_blocks: int) -> int:
+    """The splits paged_attn_verify(splits=0) cuts a segment's positions into (pie_paged_attn_verify_splits)."""
+    return int(_ffi.load().pie_paged_attn_verify_splits(int(B), int(n_kv_heads), int(max_blocks)))
+
+
+def paged_attn_verify(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_tables: torch.Tensor, row_seq: torch.Tensor, row_context_lens: torch.Tensor,
+                      seg_first: torch.Tensor, n_kv_heads: int, scale: float, splits: int = 0) -> torch.Tensor:
+    """The attention of a batched speculative pass (pie_paged_attn_verify): q [N, Hq, D]; block_tables int32 [B, max_blocks]; seg_first
+    int32 [B + 1] cuts the N rows into the sequences' segments of 1..8 consecutive rows (none: an idle slot); row_seq int32 [N] = the row's
+    block-table row; row_context_lens int32 [N] = the positions the row attends including its own, in the pages of its sequence -> [N, Hq,
+    D].  One launch for all segments (one more to merge the splits); a segment's K / V are read once for all its rows and heads.
+    splits: 0 = paged_attn_verify_splits(B, n_kv_heads, max_blocks), else 1..32."""
+    for t in (q, slab, block_tables, row_seq, row_context_lens, seg_first):
+        _dev(t)
+    if any(t.dtype != torch.int32 for t in (block_tables, row_seq, row_context_lens, seg_first)):
+        raise TypeError("paged_attn_verify: block_tables, row_seq, row_context_lens and seg_first must be int32")
+    if q.dim() != 3 or block_tables.dim() != 2:
+        raise ValueError("paged_attn_verify: q [N, Hq, D]; block_tables [B, max_blocks]")
+    N, Hq, D = q.shape
+    B = block_tables.shape[0]
+    if row_seq.numel() != N or row_context_lens.numel() != N or seg_first.numel() != B + 1:
+        raise ValueError("paged_attn_verify: row_seq [N]; row_context_lens [N]; seg_first [B + 1]")
+    if slab.numel() * slab.element_size() < n_pages * 2 * 64 * n_kv_heads * D * 2:
+        raise ValueError("paged_attn_verify: slab smaller than n_pages pages")
+    if not 0 <= int(splits) <= 32:
+        raise ValueError("paged_attn_verify: splits is 0 (chosen by the library) or 1..32")
+    lib = _ffi.load()
+    used = int(splits) or paged_attn_verify_splits(B, n_kv_heads, block_tables.shape[1])
+    ws = torch.empty(max(int(lib.pie_paged_attn_verify_workspace_bytes(N, Hq, D, used)), 16), dtype=torch.uint8, device=q.device)
+    out = torch.empty_like(q)
+    _ffi.check(lib.pie_paged_attn_verify(_ffi.p(q), _ffi.p(slab), n_pages, _ffi.p(block_tables), block_tables.shape[1], _ffi.p(row_seq), _ffi.p(row_context_lens),
+                                         _ffi.p(seg_first), N, B, Hq, int(n_kv_heads), D, float(scale), _ffi.dtype_code(q.dtype), int(splits), _ffi.p(out),
+                                         _ffi.p(ws), _ffi.stream()))
+    return out
+
+
+def ngram_draft_rows_workspace(device, B: int) -> torch.Tensor:
+    """pie_ngram_draft_rows' workspace for B sequences on `device`: uninitialised, nothing is carried from call to call."""
+    nbytes = int(_ffi.load().pie_ngram_draft_rows_workspace_bytes(int(B)))
+    if nbytes == 0:
+        raise ValueError(f"ngram_draft_rows: 1 <= B <= 4096, got {B}")
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def ngram_draft_rows(ids: torch.Tensor, lengths: torch.Tensor, ngram_max: int, ngram_min: int, k: int, workspace: torch.Tensor | None = None,
+                     out: tuple | None = None):
+    """ngram_draft on B sequences in one call (pie_ngram_draft_rows): ids int32 [B, cap], lengths device int32 [B], each clamped on the
+    device to [0, cap] -> (drafts int32 [B, k], counts int32 [B]), no host sync; row s is bit for bit ngram_draft(ids[s], lengths[s]).
+    out = (drafts, counts) to write into (a row without a match keeps its draft's contents), else fresh tensors of -1 and 0."""
+    who = "ngram_draft_rows"
+    _int32_dev(ids, None, who, "ids")
+    if ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1:
+        raise ValueError("ngram_draft_rows: ids is [B, cap] with at least one id per row")
+    B, cap = ids.shape
+    _int32_dev(lengths, B, who, "lengths")
+    ws = ngram_draft_rows_workspace(ids.device, B) if workspace is None else workspace
+    if out is None:
+        out = (torch.full((B, max(int(k), 1)), -1, dtype=torch.int32, device=ids.device), torch.zeros(B, dtype=torch.int32, device=ids.device))
+    drafts, counts = out
+    _int32_dev(drafts, None, who, "out[0]"), _int32_dev(counts, B, who, "out[1]"), _int32_dev(ws, None, who, "workspace")
+    if tuple(drafts.shape) != (B, int(k)) or ws.numel() * 4 < int(_ffi.load().pie_ngram_draft_rows_workspace_bytes(B)):
+        raise ValueError("ngram_draft_rows: out[0] is [B, k] and the workspace ngram_draft_rows_workspace()'s size")
+    _ffi.check(_ffi.load().pie_ngram_draft_rows(_ffi.p(ids), _ffi.p(lengths), B, cap, int(ngram_max), int(ngram_min), int(k), _ffi.p(drafts), _ffi.p(counts),
+                                                _ffi.p(ws), _ffi.stream()))
+    return drafts, counts
+
+
+def spec_verify_rows(logits: torch.Tensor, seg_first: torch.Tensor, drafts: torch.Tensor, ids: torch.Tensor | None = None, lengths: torch.Tensor | None = None,
+                     workspace: torch.Tensor | None = None, out: tuple | None = None):
+    """The segmented verify of a batched speculative pass (pie_spec_verify_rows): logits bf16 / f16 [N, V]; seg_first int32 [B + 1] cuts
+    the rows into the sequences' segments of 1..8 rows (none: an idle slot); drafts int32 [B, width >= 1]: sequence s's drafts, one per row
+    behind its first (a row beyond the width has no draft and ends the run) -> (tokens int32 [B, 8], n int32 [B]), no host sync.  Per sequence spec_verify's rule on its own rows: the drafts are
+    accepted while draft[i] equals row i's greedy token (logprobs_argmax of that row, bit for bit; an id outside [0, V) is never accepted),
+    n = accepted + 1, tokens = those greedy tokens, then -1; a one-row segment gives its greedy token and n = 1, an idle slot n = 0.
+    ids int32 [B, cap] / lengths int32 [B] (together, optional): the drafter's input, ids[s, lengths[s] - 1] being the token the pass was
+    fed -- the n tokens are written behind it and lengths[s] += n, on the device."""
+    who = "spec_verify_rows"
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError("spec_verify_rows: contiguous bf16 / f16 [N, V] logits")
+    N, V = logits.shape
+    _int32_dev(seg_first, None, who, "seg_first"), _int32_dev(drafts, None, who, "drafts")
+    B = seg_first.numel() - 1
+    if B < 1 or drafts.dim() != 2 or drafts.shape[0] != B or drafts.shape[1] < 1:
+        raise ValueError("spec_verify_rows: seg_first [B + 1] and drafts [B, >= 1]")
+    if (ids is None) != (lengths is None):
+        raise ValueError("spec_verify_rows: ids and lengths come together")
+    cap = 0
+    if ids is not None:
+        _int32_dev(ids, None, who, "ids"), _int32_dev(lengths, B, who, "lengths")
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
+            raise ValueError("spec_verify_rows: ids is [B, cap]")
+        cap = ids.shape[1]
+    lib = _ffi.load()
+    if workspace is None:
+        workspace = torch.empty((int(lib.pie_spec_verify_rows_workspace_bytes(N)) + 15) // 16 * 2, dtype=torch.int64, device=logits.device)
+    if out is None:
+        out = (torch.empty((B, SPEC_SEG_ROWS), dtype=torch.int32, device=logits.device), torch.empty(B, dtype=torch.int32, device=logits.device))
+    tokens, n = out
+    _int32_dev(tokens, B * SPEC_SEG_ROWS, who, "out[0]"), _int32_dev(n, B, who, "out[1]")
+    _ffi.check(lib.pie_spec_verify_rows(_ffi.p(logits), N, V, _ffi.dtype_code(logits.dtype), _ffi.p(seg_first), B, _ffi.p(drafts), drafts.shape[1], _ffi.p(tokens),
+                                        _ffi.p(n), _ffi.p(ids), _ffi.p(lengths), cap, _ffi.p(workspace), _ffi.stream()))
+    return tokens, n

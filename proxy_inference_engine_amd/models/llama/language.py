@@ -298,6 +298,8 @@ class Model(RowsTailState, StepTailState):
         self._page_pool, self._page_blocks = None, 16
         self._batch_bufs: dict = {}
         self._spec = None   # speculative decoding's record and workspaces, made when first used
+        self._spec_batch_ws = None   # the batched speculative pass's workspace, made when first used
+        self.spec_batch_last = None  # ... and its last record on the device
         self._init_rows_state()  # the multi-sequence passes' per-row tail state (rows_state.py)
         self._init_step_state()  # the single-sequence step's tail state (step_state.py)
         torch.cuda.synchronize(device)
@@ -702,6 +704,92 @@ class Model(RowsTailState, StepTailState):
         after spec_step_tail."""
         sp = self._spec_state()
         return sp[sp.get("last_ws", "ws")].view(self.dtype)[:rows * self.vocab_out].view(rows, self.vocab_out)
+
+    def draft_rows(self, seq_ids: torch.Tensor, seq_len: torch.Tensor, ngram_max: int, ngram_min: int, k: int, out: tuple):
+        """The prompt-lookup drafter over several sequences' ids at once (hip_ops.ngram_draft_rows): seq_ids int32 [B, cap], seq_len int32
+        [B], out = (drafts int32 [B, k], counts int32 [B]) on the device; queued, no host sync."""
+        return hip_ops.ngram_draft_rows(seq_ids, seq_len, ngram_max, ngram_min, k, out=out)
+
+    def spec_step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], drafts: torch.Tensor, counts, seq_ids: torch.Tensor | None = None,
+                        seq_len: torch.Tensor | None = None, then_draft: tuple | None = None):
+        """One speculative pass for several decode-state sequences (pie_decoder_spec_step_batch): tokens [B] = every sequence's
+        input token, caches as step_batch takes them (16-bit pages), drafts device int32 [>= B, >= the largest count] = row s's drafted ids, counts = the
+        host's m_s for every sequence, 0..7 (the first m_s ids of its row are verified; their sum + B is at most 256).  Sequence s presents
+        1 + m_s rows; its drafts are accepted while each equals the greedy token of the row before it.  Returns (n, tokens, next_counts):
+        n[s] = accepted + 1, tokens[s] = the n[s] tokens greedy decoding would have produced (host lists), next_counts = None; every cache
+        advances by n[s] -- the pages taken for rejected rows stay with the sequence, their K / V lie behind the offset and are overwritten
+        before anything attends to them -- and `spec_batch_last` holds the record on the device: "tokens" int32 [B, 8], "n" int32 [B].
+        seq_ids int32 [>= B, cap] / seq_len int32 [>= B] (together): the sequences' ids, row s = sequence s, the last id being its input
+        token -- the pass writes the chosen tokens behind it and moves seq_len on the device.  then_draft = (ngram_max, ngram_min, k,
+        drafts_out): hip_ops.ngram_draft_rows over those rows is queued behind the pass, before the host reads anything, into drafts_out
+        [B, k], and next_counts are its counts, read back with the pass's one record.  Greedy and raw: int8 pages, tensor-parallel models
+        and any armed per-row state of the multi-sequence passes are refused by name."""
+        import numpy as np
+        who = "spec_step_batch"
+        seqs = self._kv.sequences(who, caches)
+        B = len(seqs)
+        a = seqs[0].allocator
+        if self.tp is not None:
+            raise ValueError(f"{who}: not available on a tensor-parallel model")
+        if a.dtype == torch.int8:
+            raise ValueError(f"{who}: not available on int8 KV pages")
+        for armed, name in ((self._batch_tail, "a batch tail"), (self._batch_edits, "batch logits edits"), (self._batch_counts, "a batch count penalty"),
+                            (self._batch_dry, "a batch DRY penalty"), (self._batch_xtc, "batch XTC records"), (self._batch_dfa, "batch token automata")):
+            if armed is not None:
+                raise ValueError(f"{who}: not available with {name}")
+        tokens = torch.as_tensor(tokens).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        m = [int(c) for c in counts]
+        if tokens.numel() != B or len(m) != B:
+            raise ValueError(f"{who}: one token and one count per sequence")
+        if any(not 0 <= c <= hip_ops.SPEC_SEG_ROWS - 1 for c in m) or B + sum(m) > hip_ops.SPEC_BATCH_ROWS:
+            raise ValueError(f"{who}: every count is 0..{hip_ops.SPEC_SEG_ROWS - 1} and the pass holds at most {hip_ops.SPEC_BATCH_ROWS} rows")
+        if any(s.offset < 1 for s in seqs):
+            raise ValueError(f"{who}: a decoding sequence holds its prompt already")
+        if not drafts.is_cuda or drafts.dtype != torch.int32 or drafts.dim() != 2 or not drafts.is_contiguous() or drafts.shape[0] < B or \
+                drafts.shape[1] < max(max(m), 1):
+            raise ValueError(f"{who}: drafts is a contiguous int32 device tensor [>= B, >= the largest count]")
+        if (seq_ids is None) != (seq_len is None):
+            raise ValueError(f"{who}: seq_ids and seq_len come together")
+        if seq_ids is not None and (seq_ids.dtype != torch.int32 or seq_len.dtype != torch.int32 or seq_ids.dim() != 2 or not seq_ids.is_contiguous() or
+                                    not seq_len.is_contiguous() or seq_ids.shape[0] < B or seq_len.numel() < B or not seq_ids.is_cuda or not seq_len.is_cuda):
+            raise ValueError(f"{who}: seq_ids int32 [>= B, cap] and seq_len int32 [>= B] are contiguous device tensors")
+        for s, c in zip(seqs, m):
+            s.reserve(1 + c)
+        # the index arrays, as step_mixed forms them: row r of sequence s at position offset_s + (r - first_s)
+        rows = np.asarray([1 + c for c in m], dtype=np.int32)
+        N = int(rows.sum())
+        seg_first = np.concatenate([[0], np.cumsum(rows)]).astype(np.int32)
+        row_seq = np.repeat(np.arange(B, dtype=np.int32), rows)
+        row_ctx = (np.repeat(np.asarray([s.offset for s in seqs], dtype=np.int32), rows) + np.arange(N, dtype=np.int32) - np.repeat(seg_first[:-1], rows) + 1).astype(np.int32)
+        mb = max(len(s.pages) for s in seqs)
+        table = np.zeros((B, mb), np.int32)
+        for i, s in enumerate(seqs):
+            table[i, :len(s.pages)] = s.pages
+        index = torch.from_numpy(np.concatenate([seg_first, row_seq, row_ctx, table.reshape(-1)])).to(self.device)   # one upload
+        t_first, t_seq, t_ctx, t_table = index[:B + 1], index[B + 1:B + 1 + N], index[B + 1 + N:B + 1 + 2 * N], index[B + 1 + 2 * N:]
+        lib = _ffi.load()
+        if self._spec_batch_ws is None:
+            self._spec_batch_ws = torch.empty((int(lib.pie_decoder_spec_batch_workspace_bytes(self._dec)) + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        rec = torch.empty(B * (hip_ops.SPEC_SEG_ROWS + 2), dtype=torch.int32, device=self.device)   # tokens [B, 8] | n [B] | the next draft's counts [B]
+        out_tok, out_n, nxt_cnt = rec[:B * hip_ops.SPEC_SEG_ROWS], rec[B * hip_ops.SPEC_SEG_ROWS:B * (hip_ops.SPEC_SEG_ROWS + 1)], rec[B * (hip_ops.SPEC_SEG_ROWS + 1):]
+        rc = lib.pie_decoder_spec_step_batch(self._dec, _ffi.p(tokens), _ffi.p(drafts), drafts.shape[1], _ffi.p(t_ctx), _ffi.p(t_seq), _ffi.p(t_first), N, B,
+                                             *self._kv.pool_args(a), _ffi.p(t_table), mb, _ffi.p(out_tok), _ffi.p(out_n), _ffi.p(seq_ids), _ffi.p(seq_len),
+                                             0 if seq_ids is None else seq_ids.shape[1], _ffi.p(self._spec_batch_ws), _ffi.stream())
+        if rc == -5:   # PIE_E_STATE: some per-row state of the multi-sequence passes is armed (top_logprobs, prompt scoring): the caller's fault, by name
+            raise ValueError(f"{who}: " + lib.pie_last_error().decode("utf-8", "replace"))
+        _ffi.check(rc)
+        if then_draft is not None:
+            if seq_ids is None:
+                raise ValueError(f"{who}: then_draft needs seq_ids and seq_len")
+            ngram_max, ngram_min, k, drafts_out = then_draft
+            self.draft_rows(seq_ids[:B], seq_len[:B], ngram_max, ngram_min, k, out=(drafts_out[:B], nxt_cnt))
+        host = rec.cpu().numpy()   # the one read-back
+        n = host[B * hip_ops.SPEC_SEG_ROWS:B * (hip_ops.SPEC_SEG_ROWS + 1)].tolist()
+        toks = [host[s * hip_ops.SPEC_SEG_ROWS:s * hip_ops.SPEC_SEG_ROWS + n[s]].tolist() for s in range(B)]
+        for s, k_ in zip(seqs, n):
+            s.advance(k_)
+        self.spec_batch_last = {"tokens": out_tok.view(B, hip_ops.SPEC_SEG_ROWS), "n": out_n}
+        return n, toks, (host[B * (hip_ops.SPEC_SEG_ROWS + 1):].tolist() if then_draft is not None else None)
 
     def step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], graph: bool = True):
         """One decode step for several sequences at once (continuous batching over the page pool; pie_decoder_step_batch):
