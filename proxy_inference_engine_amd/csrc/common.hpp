@@ -35,6 +35,7 @@ int fail(int code, const std::string &msg);
 int pie_knob(int knob);  // current value; PIE_KNOB_DEFAULT (-1) = the built-in default
 
 static inline bool pie_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+static inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }  // workspace parts start on 16-byte boundaries
 
 // ---------------------------------------------------------------- device side: 16-bit float traits
 // T-typed values travel as raw u16 bits; math is fp32.  codes2() turns two 4-bit codes (one per 16-bit

@@ -13,6 +13,7 @@
 //   * hand-written HIP for everything around it: RMSNorm rows, RoPE + cache append from the packed q|k|v rows, causal
 //     attention (MFMA flash kernel), the split merge, SwiGLU on the interleaved gate/up rows, residual adds.
 // The chunk is bounded (PIE_KNOB_PREFILL_CHUNK, default 4096 rows: ~0.6 GB of activation scratch on the 8B model).
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -332,17 +333,12 @@ __global__ void __launch_bounds__(256) k_add_rms_norm_rows(u16 *x, const u16 *r,
 template <class T>
 static int add_rms_norm_rows(u16 *x, const u16 *r, const void *w, float eps, int M, int H, int dtype, u16 *xn, hipStream_t st,
                              const void *bias = nullptr, const W4lSlabs *sl = nullptr) {
-    if (sl && sl->S > 1) {  // (mlp_rows only offers to take slabs for H <= 8192)
-        hipLaunchKernelGGL(k_add_rms_norm_rows<T>, dim3(M), dim3(256), 0, st, x, r, (const u16 *)w, eps, H, xn, (const u16 *)bias, sl->part, sl->S,
-                           sl->MN);
-        PIE_LAUNCH_CHECK();
-        return PIE_OK;
-    }
-    if (H > 8192) {  // wider than the register-resident row: the two separate kernels
+    const W4lSlabs none, &p = sl && sl->S > 1 ? *sl : none;  // (mlp_rows only offers to take slabs for H <= 8192)
+    if (p.S <= 1 && H > 8192) {  // wider than the register-resident row: the two separate kernels
         const int rc = pie_add(x, r, (size_t)M * H, dtype, x, st);
         return rc ? rc : pie_rms_norm(x, w, eps, M, H, dtype, xn, st);
     }
-    hipLaunchKernelGGL(k_add_rms_norm_rows<T>, dim3(M), dim3(256), 0, st, x, r, (const u16 *)w, eps, H, xn, (const u16 *)bias);
+    hipLaunchKernelGGL(k_add_rms_norm_rows<T>, dim3(M), dim3(256), 0, st, x, r, (const u16 *)w, eps, H, xn, (const u16 *)bias, p.part, p.S, p.MN);
     PIE_LAUNCH_CHECK();
     return PIE_OK;
 }
@@ -378,35 +374,32 @@ struct PrefillScratch {
     size_t resident_left = 0; // bytes still available for resident copies
 };
 
+// A buffer that only grows: re-allocated, its contents dropped, when `need` units exceed its capacity (captured launches are stale then)
+static int scratch_grow(PrefillScratch *s, void **buf, size_t *cap, size_t need, size_t unit_bytes = 1) {
+    if (*cap >= need) return PIE_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr, *cap = 0;
+    PIE_HIP_TRY(hipMalloc(buf, need * unit_bytes));
+    *cap = need, ++s->alloc_gen;
+    return PIE_OK;
+}
+
 // The tail partials are sized in entries, not rows: a prompt pass needs 256 per row, the fused few-sequence step one per lm_head GEMV
 // wave (2048 at V = 128256) -- a buffer sized by the first and reused by the second was overrun 8 x.
 static int tail_stats_reserve(PrefillScratch *s, size_t entries) {
-    if (s->tail_entries >= entries) return PIE_OK;
-    if (s->tail_stats) (void)hipFree(s->tail_stats);
-    s->tail_stats = nullptr, s->tail_entries = 0;
-    PIE_HIP_TRY(hipMalloc((void **)&s->tail_stats, sizeof(LogitStat) * entries));
-    s->tail_entries = entries, ++s->alloc_gen;
-    return PIE_OK;
+    return scratch_grow(s, (void **)&s->tail_stats, &s->tail_entries, entries, sizeof(LogitStat));
 }
 
 static void scratch_release(PrefillScratch *s) {  // the chunk buffers; resident weight copies survive a re-size
     void *ptrs[] = {s->wT, s->wM, s->x, s->xn, s->qkv, s->q, s->attn, s->gu, s->act, s->r, s->part_acc, s->part_ml, s->rope_cs, s->kc, s->vc};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    auto keep = std::move(s->resident);
-    auto keep_m = std::move(s->resident_w4m);
-    LogitStat *keep_ts = s->tail_stats;
-    const size_t keep_tr = s->tail_entries;
-    const unsigned gen = s->alloc_gen + 1;  // the chunk buffers move: captured launches are stale
     if (s->batch_graph) (void)hipGraphExecDestroy(s->batch_graph);
-    const int mode = s->resident_mode;
-    const size_t left = s->resident_left;
-    void *keep_ws = s->w4l_ws;
-    const size_t keep_wsb = s->w4l_ws_bytes;
-    *s = PrefillScratch();
-    s->w4l_ws = keep_ws, s->w4l_ws_bytes = keep_wsb;
-    s->resident = std::move(keep), s->resident_w4m = std::move(keep_m), s->resident_mode = mode, s->resident_left = left;
-    s->tail_stats = keep_ts, s->tail_entries = keep_tr, s->alloc_gen = gen;
+    PrefillScratch fresh;  // everything back to its default, except what survives:
+    fresh.resident = std::move(s->resident), fresh.resident_w4m = std::move(s->resident_w4m), fresh.resident_mode = s->resident_mode, fresh.resident_left = s->resident_left;
+    fresh.tail_stats = s->tail_stats, fresh.tail_entries = s->tail_entries, fresh.w4l_ws = s->w4l_ws, fresh.w4l_ws_bytes = s->w4l_ws_bytes;
+    fresh.alloc_gen = s->alloc_gen + 1;  // the chunk buffers move: captured launches are stale
+    *s = std::move(fresh);
 }
 
 void prefill_free(pie_decoder *d) {
@@ -416,7 +409,6 @@ void prefill_free(pie_decoder *d) {
     for (auto &kv : d->prefill->resident_w4m) (void)hipFree(kv.second);
     if (d->prefill->tail_stats) (void)hipFree(d->prefill->tail_stats);
     if (d->prefill->w4l_ws) (void)hipFree(d->prefill->w4l_ws);
-    if (d->prefill->batch_graph) (void)hipGraphExecDestroy(d->prefill->batch_graph);
     delete d->prefill;
     d->prefill = nullptr;
 }
@@ -552,15 +544,7 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
     // streaming GEMV with the rows' images side by side -- one pass over the weights, each row with the batch-1 arithmetic.
     if (is_int4 && M <= GEMV_ROWS_MAX && K % 64 == 0 && N % 2 == 0 && gemv_rows_lds_bytes(K, 1) <= 160u * 1024u)
         return w4s_gemv_rows_launch(d->cfg.dtype, packed, N, K, x, M, y, (const u16 *)bias, st);
-    auto w4l_reserve = [&](size_t wb) -> int {  // fp32 slabs of a K-split product
-        if (wb > s->w4l_ws_bytes) {
-            if (s->w4l_ws) (void)hipFree(s->w4l_ws);
-            s->w4l_ws = nullptr, s->w4l_ws_bytes = 0;
-            PIE_HIP_TRY(hipMalloc(&s->w4l_ws, wb));
-            s->w4l_ws_bytes = wb, ++s->alloc_gen;
-        }
-        return PIE_OK;
-    };
+    auto w4l_reserve = [&](size_t wb) { return scratch_grow(s, &s->w4l_ws, &s->w4l_ws_bytes, wb); };  // fp32 slabs of a K-split product
     int rc = PIE_OK;
     if (is_int4 && N % 32 == 0 && K % 64 == 0) {  // every shape the W4M tiles take: get tiles, reserve, enter, add the bias if it is still ours
         // resident W4M tile copy (0.5625 B per weight, built on first use within the residency budget); none: no room, the W16M path below
@@ -612,11 +596,8 @@ static int linear_rows(pie_decoder *d, const void *packed, int N, int K, const u
 // Elements of the 16-bit weight scratch: the largest W16M copy a pass may build (with_lm_head: the lm_head goes through linear_rows too)
 static size_t w16_copy_elems(const pie_decoder_config &c, bool with_lm_head) {
     const int H = c.hidden, NQKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, I = c.inter;
-    size_t w_elems = w16m_size(2 * I, H) / 2;  // the 16-bit copies are W16M tiles (rows padded to 32, columns to 64)
-    if (w16m_size(NQKV, H) / 2 > w_elems) w_elems = w16m_size(NQKV, H) / 2;
-    if (w16m_size(H, I) / 2 > w_elems) w_elems = w16m_size(H, I) / 2;
-    if (with_lm_head && w16m_size(c.vocab, H) / 2 > w_elems) w_elems = w16m_size(c.vocab, H) / 2;
-    return w_elems;
+    // the 16-bit copies are W16M tiles (rows padded to 32, columns to 64)
+    return std::max({w16m_size(2 * I, H), w16m_size(NQKV, H), w16m_size(H, I), with_lm_head ? w16m_size(c.vocab, H) : (size_t)0}) / 2;
 }
 
 // h = embed_tokens(ids) (language.py:176) for M rows into x
@@ -632,6 +613,46 @@ template <class T>
 static decltype(&k_rope_append_rows<T>) rope_append_kernel(bool slabs, bool i8) {
     if (slabs) return i8 ? &k_rope_append_rows<T, true, true> : &k_rope_append_rows<T, true, false>;
     return i8 ? &k_rope_append_rows<T, false, true> : &k_rope_append_rows<T, false, false>;
+}
+
+// Where the M rows of a many-row pass sit and where their K / V go: everything the passes' layer head (qkv_rope_rows) differs in, as data.
+struct RowsKv {
+    const DecState *state = nullptr;              // positions: row m continues the decoder's one sequence at state->pos + m (cache capacity state->cap) ...
+    const int *row_ctx = nullptr;                 // ... or row m sits at row_ctx[m] - 1 of its own sequence (< 0: idle slot)
+    const unsigned long long *kv_table = nullptr; // cache: the per-layer K / V buffer (or slab) bases ...
+    const void *const *slabs = nullptr;           // ... or every layer's slab directly
+    const int *block_tables = nullptr;            // paged KV (nullable): a sequence's table row is bt_stride entries long (0: every row reads the one table)
+    int bt_stride = 0, n_pages = 0;
+    const int *row_seq = nullptr;                 // row m belongs to sequence row_seq[m] (its block-table row); nullptr: to sequence m
+    u16 *kc = nullptr, *vc = nullptr;             // contiguous [n_kv_heads, M, HD] copies of the rotated K and the V rows, where the pass's own attention reads them
+    bool i8 = false;                              // the pages are int8 with per-head fp16 scales (paged_i8.hip): K / V are quantised on the way in
+    bool gemm_rope = false;                       // the GEMM's own RoPE epilogue (W4mRope) may be offered: it knows neither row_seq nor kc / vc
+    bool split_any_rows = false;                  // four workgroups per row of slabs at any row count, not only below 512 (see qkv_rope_rows)
+};
+
+// The head of a decoder layer on M rows of s->xn (Attention.__call__ up to the cache update, language.py:75-95): the packed q|k|v Linear, RoPE on
+// q / k into s->q and K / V appended where `kv` says -- by the GEMM's own epilogue where it is offered and taken, else by k_rope_append_rows.
+template <class T>
+static int qkv_rope_rows(pie_decoder *d, const pie_layer_weights &w, int li, int M, const RowsKv &kv, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    const int D = c.head_dim, NQKV = (c.n_heads + 2 * c.n_kv_heads) * D;
+    PrefillScratch *s = d->prefill;
+    W4mRope re = {s->rope_cs, kv.state, kv.row_ctx, kv.kv_table, kv.slabs ? (u16 *)kv.slabs[li] : nullptr, kv.block_tables, kv.bt_stride, kv.n_pages, li,
+                  c.n_layers, c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, nullptr, kv.i8 ? pie_page_i8_bytes(c.n_kv_heads, D) : (size_t)0};
+    RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
+    qkv_opts.bias = w.bqkv, qkv_opts.rope = kv.gemm_rope ? &re : nullptr, qkv_opts.slabs = !w.bqkv;
+    RowsDone qkv_done;
+    if (int rc = linear_rows<T>(d, w.wqkv, NQKV, c.hidden, s->xn, M, s->qkv, st, qkv_opts, &qkv_done)) return rc;
+    if (qkv_done.roped) return PIE_OK;
+    const W4lSlabs &sq = qkv_done.slabs;
+    // few rows of slabs: four workgroups per row (256 tokens: 6.03 vs 6.20 ms; from 512 rows no difference).  The multi-sequence step
+    // (split_any_rows) has launched the four at every row count, up to its 4096 sequences: kept as it is, not re-measured from 512.
+    const unsigned row_wgs = sq.S > 1 && (M < 512 || kv.split_any_rows) ? 4u : 1u;
+    hipLaunchKernelGGL(rope_append_kernel<T>(sq.S > 1, kv.i8), dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, re.state, re.kv_table,
+                       li, c.n_layers, c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, re.block_table, re.n_pages, s->rope_cs, re.ctx_len, re.bt_stride,
+                       re.slab, kv.row_seq, kv.kc, kv.vc, sq.part, sq.S, sq.MN, re.i8_page_bytes);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
 }
 
 // The rest of a decoder layer after its attention, on M rows: o_proj of s->attn, the residual adds on s->x, the MLP in between, and
@@ -666,6 +687,39 @@ static int mlp_rows(pie_decoder *d, const pie_layer_weights &w, int M, const voi
     return add_rms_norm_rows<T>(s->x, s->r, next_norm, c.rms_eps, M, H, c.dtype, s->xn, st, down_done.slabs.S > 1 ? w.bdown : nullptr, &down_done.slabs);
 }
 
+// What opens a pass whose M rows are each at their own position: h = embed_tokens(ids) into s->x and the rows' rotary (cos, sin)
+static int embed_rope_cs_rows(pie_decoder *d, const int32_t *ids, int M, const int32_t *row_ctx, hipStream_t st) {
+    PrefillScratch *s = d->prefill;
+    if (int rc = embed_rows(d, ids, M, s->x, st)) return rc;
+    hipLaunchKernelGGL(k_rope_cs_rows, dim3(M), dim3(64), 0, st, d->glob.rope_freqs, nullptr, row_ctx, d->cfg.head_dim / 2, s->rope_cs);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+// The layers of a pass over M rows on pages (kv.row_ctx: every row at its own position): that opening, then per layer the head, the pass's
+// own attention -- attn(li) reads s->q and the cache and writes s->attn -- and the tail.  s->xn ends up holding every row final-normed.
+template <class T, class Attn>
+static int paged_rows_layers(pie_decoder *d, const int32_t *ids, int M, const RowsKv &kv, hipStream_t st, Attn &&attn) {
+    const pie_decoder_config &c = d->cfg;
+    PrefillScratch *s = d->prefill;
+    int rc = embed_rope_cs_rows(d, ids, M, kv.row_ctx, st);
+    if (rc) return rc;
+    for (int li = 0; li < c.n_layers; ++li) {
+        const pie_layer_weights &w = d->layers[li];
+        // input_layernorm: layer 0 here; for the later layers it was fused with the previous block's residual add
+        if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, M, c.hidden, c.dtype, s->xn, st))) return rc;
+        if ((rc = qkv_rope_rows<T>(d, w, li, M, kv, st)) || (rc = attn(li))) return rc;
+        if ((rc = mlp_rows<T>(d, w, M, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
+    }
+    return PIE_OK;
+}
+
+// f(BF16()) or f(F16()) by a decoder's activation dtype (one of the two: pie_decoder_create refuses anything else)
+template <class F>
+static int for_dtype(int dtype, F &&f) {
+    return dtype == PIE_BF16 ? f(BF16()) : f(F16());
+}
+
 // Quantized KV (pie_decoder_set_kv_quant): the T scratch of one layer's K and V at the cache's capacity and the table that points every layer at it.
 static int kvq_scratch_reserve(pie_decoder *d) {
     const pie_decoder_config &c = d->cfg;
@@ -684,11 +738,13 @@ static int kvq_scratch_reserve(pie_decoder *d) {
     return PIE_OK;
 }
 
-// The lm_head on every position: through the scratch (no 16-bit resident copy)
-static RowsOpts every_row_head_opts() {
+// The lm_head on `rows` final-normed rows: through the scratch (no 16-bit resident copy of it); keep_w4m: its int4 tiles stay (the multi-sequence
+// passes), where a logits-on-every-position call keeps nothing
+template <class T>
+static int lm_head_rows(pie_decoder *d, const u16 *x, int rows, void *logits, hipStream_t st, bool keep_w4m = true) {
     RowsOpts o;
-    o.keep = false;
-    return o;
+    o.keep = false, o.keep_w4m = keep_w4m;
+    return linear_rows<T>(d, d->glob.lm_head, d->cfg.vocab, d->cfg.hidden, x, rows, (u16 *)logits, st, o);
 }
 
 // Log-probabilities of prompt tokens (pie_decoder_set_prompt_logprobs): rows [0, M) of xn -- final-normed already -- are
@@ -701,7 +757,7 @@ static int score_prompt_rows(pie_decoder *d, const u16 *xn, int row0, int M, hip
     const pie_decoder_config &c = d->cfg;
     for (int b0 = 0; b0 < M; b0 += pl.block) {
         const int rows = M - b0 < pl.block ? M - b0 : pl.block;
-        int rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, c.hidden, xn + (size_t)b0 * c.hidden, rows, pl.ws, st, every_row_head_opts());
+        int rc = lm_head_rows<T>(d, xn + (size_t)b0 * c.hidden, rows, pl.ws, st, false);
         if (rc || (rc = pl.score_rows(c, pl.ws, row0 + b0, rows, st))) return rc;
     }
     return PIE_OK;
@@ -710,21 +766,20 @@ static int score_prompt_rows(pie_decoder *d, const u16 *xn, int row0, int M, hip
 template <class T>
 static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int L, void *logits_all, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
-    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
+    const int H = c.hidden, D = c.head_dim;
     const int chunk = prefill_chunk_rows() < L ? prefill_chunk_rows() : L;
     int rc = scratch_reserve(d, chunk, w16_copy_elems(c, logits_all != nullptr || d->prompt.n), d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     // quantized KV: the pass runs on the T scratch (kv_table below), the layer's codes are expanded into it and the chunk's rows quantized back
-    unsigned long long *kv_table = d->kv_table;
-    if (d->kv_quant) {
-        if ((rc = kvq_scratch_reserve(d))) return rc;
-        kv_table = d->kvq_table;
-    }
+    if (d->kv_quant && (rc = kvq_scratch_reserve(d))) return rc;
+    unsigned long long *const kv_table = d->kv_quant ? d->kvq_table : d->kv_table;
     u16 *const sk = d->kvq_scratch, *const sv = d->kvq_scratch ? d->kvq_scratch + (size_t)c.n_kv_heads * d->kvq_scratch_cap * D : nullptr;
-    auto kvq_layer = [d](int li) {
+    auto kvq_rows = [&](bool expand, int li, int M) {  // the layer's codes into the scratch / the chunk's M rows quantized back; nothing without quantized KV
+        if (!d->kv_quant) return (int)PIE_OK;
         const void *const *p = &d->kvq_host[(size_t)6 * li];
-        return QKvLayer{(const u32 *)p[0], (const u16 *)p[1], (const u16 *)p[2], (const u32 *)p[3], (const u16 *)p[4], (const u16 *)p[5]};
+        const QKvLayer q = {(const u32 *)p[0], (const u16 *)p[1], (const u16 *)p[2], (const u32 *)p[3], (const u16 *)p[4], (const u16 *)p[5]};
+        return kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, expand, q, d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st);
     };
     // RotatingKVCache: the chunk's K / V rows go to rows ring_rows->pos + m of the buffers (the retained window in temporal order, then the
     // update: cache/kv_cache/rotating.py), RoPE stays at the absolute position state->pos + m; the attention is windowed
@@ -735,6 +790,8 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
         PIE_LAUNCH_CHECK();
     }
     const bool mfma_attn = d->ring || pie_knob(PIE_KNOB_PREFILL_ATTN_VALU) != 1;  // 1 forces the row-per-launch-slice VALU kernel (tests compare the two)
+    RowsKv kv;  // one sequence: rows at kvs->pos + m of the table's buffers, or of the pages of the decoder's one block table
+    kv.state = kvs, kv.kv_table = kv_table, kv.block_tables = d->block_table, kv.n_pages = d->n_pages, kv.gemm_rope = true;
     for (int c0 = 0; c0 < L; c0 += chunk) {
         const int M = L - c0 < chunk ? L - c0 : chunk;
         // h = embed_tokens(inputs)  (language.py:176)
@@ -749,25 +806,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             // Attention.__call__ (language.py:75-108) on input_layernorm(x)
             // input_layernorm: layer 0 here; for the later layers it was fused with the previous block's residual add
             if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
-            if (d->kv_quant && (rc = kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, true, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st)))
-                return rc;
-            W4mRope re = {s->rope_cs, kvs, nullptr, kv_table, nullptr, d->block_table, 0, d->n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads, D,
-                          c.rope_traditional, s->q, nullptr, 0};
-            RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
-            qkv_opts.bias = w.bqkv, qkv_opts.rope = &re, qkv_opts.slabs = !w.bqkv;
-            RowsDone qkv_done;
-            if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, M, s->qkv, st, qkv_opts, &qkv_done))) return rc;
-            const W4lSlabs &sq = qkv_done.slabs;
-            if (!qkv_done.roped) {
-                const unsigned row_wgs = sq.S > 1 ? (M < 512 ? 4u : 1u) : 1u;  // few rows of slabs: four workgroups per row (256 tokens: 6.03 vs 6.20 ms; from 512 rows no difference)
-                const auto rope_k = rope_append_kernel<T>(sq.S > 1, false);
-                hipLaunchKernelGGL(rope_k, dim3(M, row_wgs), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, kvs, kv_table, li,
-                                   c.n_layers, c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, d->block_table, d->n_pages, s->rope_cs, (const int *)nullptr, 0,
-                                   (u16 *)nullptr, (const int *)nullptr, (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, (size_t)0);
-                PIE_LAUNCH_CHECK();
-            }
-            if (d->kv_quant && (rc = kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, false, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st)))
-                return rc;
+            if ((rc = kvq_rows(true, li, M)) || (rc = qkv_rope_rows<T>(d, w, li, M, kv, st)) || (rc = kvq_rows(false, li, M))) return rc;
             if (mfma_attn) {  // causal flash attention on the MFMA units (prefill_attn.hpp)
                 PrefillAttnArgs pa = {};
                 pa.q = s->q, pa.kv_table = kv_table, pa.layer = li, pa.n_layers = c.n_layers, pa.state = kvs, pa.window = d->ring ? d->ring_w : 0;
@@ -786,9 +825,8 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             if ((rc = mlp_rows<T>(d, w, M, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : nullptr, st))) return rc;
         }
         if ((logits_all || d->prompt.n) && (rc = pie_rms_norm(s->x, d->glob.final_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
-        if (logits_all) {  // lm_head on every position, like the reference (language.py:205-209)
-            if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, every_row_head_opts()))) return rc;
-        }
+        // lm_head on every position, like the reference (language.py:205-209)
+        if (logits_all && (rc = lm_head_rows<T>(d, s->xn, M, (u16 *)logits_all + (size_t)c0 * c.vocab, st, false))) return rc;
         if ((rc = score_prompt_rows<T>(d, s->xn, c0, M, st))) return rc;
         const bool last = c0 + M >= L;
         if (last)  // the last position continues through the decode step's lm_head + tail below
@@ -808,36 +846,31 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
 // mx.fast.scaled_dot_product_attention(q, k, v, scale, mask=causal) for L > 1 (models/base.py:37-53,111-113), op level.
 // The windowed form (RotatingKVCache prompts): query row r sees keys offset + r - window .. offset + r -- create_causal_mask(L, offset,
 // window_size=window) in index space (models/base.py:18-34).  Key blocks wholly below a tile's first row's bound are skipped.
-extern "C" int pie_sdpa_prefill_window(const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D, int window,
-                                       float scale, int dtype, void *out, void *stream) {
-    PIE_REQUIRE(q && k && v && out, PIE_E_ARG, "pie_sdpa_prefill_window: null pointer");
-    PIE_REQUIRE(L >= 1 && offset >= 0 && offset + L <= cap && window >= 1, PIE_E_SHAPE, "pie_sdpa_prefill_window: need offset + L <= cap, window >= 1");
-    PIE_REQUIRE(D == 64 || D == 128, PIE_E_SHAPE, "pie_sdpa_prefill_window: head_dim must be 64 or 128");
-    PIE_REQUIRE(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, PIE_E_SHAPE, "pie_sdpa_prefill_window: n_heads / n_kv_heads must be between 1 and 8");
-    PIE_REQUIRE(pie_aligned(q, 16) && pie_aligned(k, 16) && pie_aligned(v, 16) && pie_aligned(out, 8), PIE_E_ALIGN, "pie_sdpa_prefill_window: misaligned pointer");
+// Both entries' body; window 0: the plain causal mask, which `windowed` (the entry that takes a window) refuses.
+static int sdpa_prefill(const std::string &who, bool windowed, const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D,
+                        int window, float scale, int dtype, void *out, void *stream) {
+    PIE_REQUIRE(q && k && v && out, PIE_E_ARG, who + "null pointer");
+    PIE_REQUIRE(L >= 1 && offset >= 0 && offset + L <= cap && (!windowed || window >= 1), PIE_E_SHAPE,
+                who + (windowed ? "need offset + L <= cap, window >= 1" : "need offset + L <= cap"));
+    PIE_REQUIRE(D == 64 || D == 128, PIE_E_SHAPE, who + "head_dim must be 64 or 128");
+    PIE_REQUIRE(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, PIE_E_SHAPE, who + "n_heads / n_kv_heads must be between 1 and 8");
+    PIE_REQUIRE(pie_aligned(q, 16) && pie_aligned(k, 16) && pie_aligned(v, 16) && pie_aligned(out, 8), PIE_E_ALIGN, who + "misaligned pointer");
     PrefillAttnArgs a = {};
     a.q = (const u16 *)q, a.k = (const u16 *)k, a.v = (const u16 *)v, a.offset = offset, a.cap = cap, a.window = window;
     a.M = L, a.Hq = Hq, a.Hkv = Hkv, a.scale = scale, a.out = (u16 *)out;
-    if (dtype == PIE_BF16) return prefill_attn_launch_t<BF16>(a, D, (hipStream_t)stream);
-    if (dtype == PIE_F16) return prefill_attn_launch_t<F16>(a, D, (hipStream_t)stream);
-    return pie::fail(PIE_E_ARG, "pie_sdpa_prefill_window: dtype must be PIE_BF16 or PIE_F16");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, who + "dtype must be PIE_BF16 or PIE_F16");
+    return for_dtype(dtype, [&](auto t) { return prefill_attn_launch_t<decltype(t)>(a, D, (hipStream_t)stream); });
+}
+
+extern "C" int pie_sdpa_prefill_window(const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D, int window,
+                                       float scale, int dtype, void *out, void *stream) {
+    return sdpa_prefill("pie_sdpa_prefill_window: ", true, q, k, v, Hq, Hkv, L, offset, cap, D, window, scale, dtype, out, stream);
 }
 
 extern "C" int pie_sdpa_prefill(const void *q, const void *k, const void *v, int Hq, int Hkv, int L, int offset, int cap, int D, float scale,
                                 int dtype, void *out, void *stream) {
-    PIE_REQUIRE(q && k && v && out, PIE_E_ARG, "pie_sdpa_prefill: null pointer");
-    PIE_REQUIRE(L >= 1 && offset >= 0 && offset + L <= cap, PIE_E_SHAPE, "pie_sdpa_prefill: need offset + L <= cap");
-    PIE_REQUIRE(D == 64 || D == 128, PIE_E_SHAPE, "pie_sdpa_prefill: head_dim must be 64 or 128");
-    PIE_REQUIRE(Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= 8, PIE_E_SHAPE, "pie_sdpa_prefill: n_heads / n_kv_heads must be between 1 and 8");
-    PIE_REQUIRE(pie_aligned(q, 16) && pie_aligned(k, 16) && pie_aligned(v, 16) && pie_aligned(out, 8), PIE_E_ALIGN, "pie_sdpa_prefill: misaligned pointer");
-    PrefillAttnArgs a = {};
-    a.q = (const u16 *)q, a.k = (const u16 *)k, a.v = (const u16 *)v, a.offset = offset, a.cap = cap;
-    a.M = L, a.Hq = Hq, a.Hkv = Hkv, a.scale = scale, a.out = (u16 *)out;
-    if (dtype == PIE_BF16) return prefill_attn_launch_t<BF16>(a, D, (hipStream_t)stream);
-    if (dtype == PIE_F16) return prefill_attn_launch_t<F16>(a, D, (hipStream_t)stream);
-    return pie::fail(PIE_E_ARG, "pie_sdpa_prefill: dtype must be PIE_BF16 or PIE_F16");
+    return sdpa_prefill("pie_sdpa_prefill: ", false, q, k, v, Hq, Hkv, L, offset, cap, D, 0, scale, dtype, out, stream);
 }
-
 
 // attention splits of a batch of B decode rows over block tables of max_blocks pages
 static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
@@ -854,6 +887,19 @@ static int batch_attn_splits(const pie_decoder *d, int B, int max_blocks) {
     // batch-1 step's attention, and a few hundred positions are a handful of row blocks per wave
     if (B <= GEMV_ROWS_MAX && max_blocks <= 4 && !d->kv_i8) splits = 1;
     return splits;
+}
+
+// The attention of decode-state rows: rows [0, rows) of s->q, each its own sequence (kv.row_ctx[r] positions, block-table row r) over its
+// pages of layer li -- which hold the row just appended -- into s->attn
+static int paged_decode_attn(pie_decoder *d, int li, int rows, int splits, const RowsKv &kv, hipStream_t st) {
+    const pie_decoder_config &c = d->cfg;
+    PrefillScratch *s = d->prefill;
+    AttnArgs a = {};
+    a.q = s->q, a.slab = (const u16 *)kv.slabs[li], a.block_table = kv.block_tables, a.ctx_len = kv.row_ctx, a.bt_stride = kv.bt_stride, a.n_pages = kv.n_pages;
+    a.rows = rows, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.splits = splits, a.scale = 1.0f / sqrtf((float)c.head_dim);
+    a.nt_kv = (size_t)rows * kv.bt_stride * 64 >= 2048;
+    a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
+    return kv.i8 ? paged_attn_i8_launch(c.dtype, c.head_dim, a, st) : attn_decode_launch(c.dtype, c.head_dim, a, true, st);
 }
 
 // ---------------------------------------------------------------- the multi-sequence passes' tail
@@ -925,6 +971,9 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
     const int lm_waves = w4s_gemv_waves(c.vocab, H);  // the fused few-sequence form: one log-softmax partial per GEMV wave and row
     const size_t stats_per_row = (size_t)(lm_waves > TAIL_STAT_TILES ? lm_waves : TAIL_STAT_TILES);
     if ((rc = tail_stats_reserve(s, stats_per_row * (size_t)B))) return rc;
+    RowsKv kv;  // every row its own sequence: its own position, page (T or int8: the append quantises) and block-table row
+    kv.row_ctx = ctx_len, kv.slabs = slabs, kv.block_tables = block_tables, kv.bt_stride = max_blocks, kv.n_pages = n_pages, kv.i8 = d->kv_i8;
+    kv.gemm_rope = true, kv.split_any_rows = true;
     // Up to 5 sequences on an int4 checkpoint: the batch-1 launch sequence, once, with every GEMV multiplying all rows per weight
     // unit (k_w4s_gemv_rows: RMSNorm prologues; RoPE + page append, residual, SwiGLU and logits epilogues, per row) -- 6 launches per
     // layer instead of 9-10, each row in MLX's row-by-row fp32 regime.  Biases, int8 pages and hidden sizes beyond 8192 take the
@@ -933,9 +982,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
     for (const pie_layer_weights &w : d->layers)
         if (w.bqkv || w.bo || w.bgateup || w.bdown) fused_rows = false;
     if (fused_rows) {
-        if ((rc = embed_rows(d, tokens, B, s->x, st))) return rc;
-        hipLaunchKernelGGL(k_rope_cs_rows, dim3(B), dim3(64), 0, st, d->glob.rope_freqs, nullptr, ctx_len, D / 2, s->rope_cs);
-        PIE_LAUNCH_CHECK();
+        if ((rc = embed_rope_cs_rows(d, tokens, B, ctx_len, st))) return rc;
         for (int li = 0; li < c.n_layers; ++li) {
             const pie_layer_weights &w = d->layers[li];
             GemvRowsArgs g = {};
@@ -943,12 +990,7 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
             g.rope_cs = s->rope_cs, g.ctx_len = ctx_len, g.block_table = block_tables, g.slab = (u16 *)slabs[li], g.q_out = s->q;
             g.bt_stride = max_blocks, g.n_pages = n_pages, g.n_heads = c.n_heads, g.n_kv_heads = c.n_kv_heads, g.head_dim = D, g.rope_traditional = c.rope_traditional;
             if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_RMSNORM, EPI_ROPE_KV, g, st))) return rc;
-            AttnArgs a = {};
-            a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.ctx_len = ctx_len, a.bt_stride = max_blocks, a.n_pages = n_pages;
-            a.rows = B, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.splits = splits, a.scale = 1.0f / sqrtf((float)D);
-            a.nt_kv = (size_t)B * max_blocks * 64 >= 2048;
-            a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
-            if ((rc = attn_decode_launch(c.dtype, D, a, true, st))) return rc;
+            if ((rc = paged_decode_attn(d, li, B, splits, kv, st))) return rc;
             g = GemvRowsArgs();
             g.w = (const char *)w.wo, g.K = QD, g.N = H, g.M = B, g.x = s->attn, g.resid = s->x;
             if ((rc = w4s_gemv_rows_fused_launch(c.dtype, PRO_NONE, EPI_RESIDUAL, g, st))) return rc;
@@ -967,41 +1009,10 @@ static int decode_batch_t(pie_decoder *d, const int32_t *tokens, const int32_t *
         if ((rc = logits_finish_launch(c.dtype, logits, c.vocab, B, s->tail_stats, lm_waves, logprobs, next_tokens, nullptr, nullptr, 0, nullptr, st))) return rc;
         return batch_top_logprobs_launch(d, B, logprobs, next_tokens, st);
     }
-    if ((rc = embed_rows(d, tokens, B, s->x, st))) return rc;
-    hipLaunchKernelGGL(k_rope_cs_rows, dim3(B), dim3(64), 0, st, d->glob.rope_freqs, nullptr, ctx_len, D / 2, s->rope_cs);
-    PIE_LAUNCH_CHECK();
-    for (int li = 0; li < c.n_layers; ++li) {
-        const pie_layer_weights &w = d->layers[li];
-        if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, B, H, c.dtype, s->xn, st))) return rc;
-        const size_t i8pb = d->kv_i8 ? pie_page_i8_bytes(c.n_kv_heads, D) : 0;  // int8 pages: the append (epilogue or row kernel) quantises
-        W4mRope re = {s->rope_cs, nullptr, ctx_len, nullptr, (u16 *)slabs[li], block_tables, max_blocks, n_pages, li, c.n_layers, c.n_heads, c.n_kv_heads,
-                      D, c.rope_traditional, s->q, nullptr, i8pb};
-        RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
-        qkv_opts.bias = w.bqkv, qkv_opts.rope = &re, qkv_opts.slabs = !w.bqkv;
-        RowsDone qkv_done;
-        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, B, s->qkv, st, qkv_opts, &qkv_done))) return rc;
-        const W4lSlabs &sq = qkv_done.slabs;
-        if (!qkv_done.roped) {
-            const auto rope_k = rope_append_kernel<T>(sq.S > 1, d->kv_i8);
-            hipLaunchKernelGGL(rope_k, dim3(B, sq.S > 1 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers,
-                               c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, ctx_len, max_blocks, (u16 *)slabs[li],
-                               (const int *)nullptr, (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, i8pb);
-            PIE_LAUNCH_CHECK();
-        }
-        AttnArgs a = {};
-        a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.ctx_len = ctx_len, a.bt_stride = max_blocks, a.n_pages = n_pages;
-        a.rows = B, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.splits = splits, a.scale = 1.0f / sqrtf((float)D);
-        a.nt_kv = (size_t)B * max_blocks * 64 >= 2048;
-        a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
-        if ((rc = d->kv_i8 ? paged_attn_i8_launch(c.dtype, D, a, st) : attn_decode_launch(c.dtype, D, a, true, st))) return rc;
-        if ((rc = mlp_rows<T>(d, w, B, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
-    }
-    RowsOpts head_opts;
-    head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
-    if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, B, logits, st, head_opts))) return rc;
+    if ((rc = paged_rows_layers<T>(d, tokens, B, kv, st, [&](int li) { return paged_decode_attn(d, li, B, splits, kv, st); }))) return rc;
+    if ((rc = lm_head_rows<T>(d, s->xn, B, logits, st))) return rc;
     return batch_tail_launch(d, tokens, ctx_len, nullptr, B, B, logits, logprobs, next_tokens, st);
 }
-
 
 // ---------------------------------------------------------------- several fresh prompts in one pass
 __global__ void k_gather_rows(const uint4 *x, const int *rows, int H8, uint4 *y) {  // y[s] = x[rows[s]], H8 = hidden / 8
@@ -1022,64 +1033,83 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
                             const int32_t *block_tables, int max_blocks, u16 *logits, float *logprobs, int32_t *next_tokens, hipStream_t st,
                             int n_chunks = 0, const int32_t *chunks = nullptr) {
     const pie_decoder_config &c = d->cfg;
-    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
+    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D;
     const int dsplits = n_decode > 0 ? batch_attn_splits(d, n_decode, max_blocks) : 1;
     int rc = scratch_reserve(d, N > S ? N : S, w16_copy_elems(c, true), dsplits > d->splits ? dsplits : d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     if ((rc = tail_stats_reserve(s, (size_t)TAIL_STAT_TILES * (size_t)S))) return rc;
-    if ((rc = embed_rows(d, ids, N, s->x, st))) return rc;
-    hipLaunchKernelGGL(k_rope_cs_rows, dim3(N), dim3(64), 0, st, d->glob.rope_freqs, nullptr, row_ctx, D / 2, s->rope_cs);
-    PIE_LAUNCH_CHECK();
-    for (int li = 0; li < c.n_layers; ++li) {
-        const pie_layer_weights &w = d->layers[li];
-        if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, N, H, c.dtype, s->xn, st))) return rc;
-        RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
-        qkv_opts.bias = w.bqkv, qkv_opts.slabs = !w.bqkv;
-        RowsDone qkv_done;
-        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, N, s->qkv, st, qkv_opts, &qkv_done))) return rc;
-        const W4lSlabs &sq = qkv_done.slabs;
-        const auto rope_k = rope_append_kernel<T>(sq.S > 1, d->kv_i8);
-        hipLaunchKernelGGL(rope_k, dim3(N, sq.S > 1 && N < 512 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers,
-                           c.n_heads, c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, row_ctx, max_blocks, (u16 *)slabs[li],
-                           row_seq, s->kc, s->vc, sq.part, sq.S, sq.MN,
-                           d->kv_i8 ? pie_page_i8_bytes(c.n_kv_heads, D) : (size_t)0);  // int8 pages: quantised on the way in; this pass's own attention reads the T copies
-        PIE_LAUNCH_CHECK();
+    RowsKv kv;  // rows of a sequence share its block-table row; K / V also go to the contiguous copies this pass's own attention reads
+    kv.row_ctx = row_ctx, kv.slabs = slabs, kv.block_tables = block_tables, kv.bt_stride = max_blocks, kv.n_pages = n_pages, kv.i8 = d->kv_i8;
+    kv.row_seq = row_seq, kv.kc = s->kc, kv.vc = s->vc;
+    rc = paged_rows_layers<T>(d, ids, N, kv, st, [&](int li) {
         PrefillAttnArgs pa = {};
         pa.q = s->q, pa.k = s->kc, pa.v = s->vc, pa.offset = 0, pa.cap = N, pa.seg_lo = seg_lo, pa.seg_hi = seg_hi;
         pa.M = N, pa.Hq = c.n_heads, pa.Hkv = c.n_kv_heads, pa.scale = 1.0f / sqrtf((float)D), pa.out = s->attn;
-        if ((rc = segment_attn_gqa_launch_t<T>(pa, D, st))) return rc;
-        if (n_decode > 0) {  // the decode-state rows attend to their pages (which hold the row just appended)
-            AttnArgs a = {};
-            a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.ctx_len = row_ctx, a.bt_stride = max_blocks, a.n_pages = n_pages;
-            a.rows = n_decode, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.splits = dsplits, a.scale = pa.scale;
-            a.nt_kv = (size_t)n_decode * max_blocks * 64 >= 2048;
-            a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
-            if ((rc = d->kv_i8 ? paged_attn_i8_launch(c.dtype, D, a, st) : attn_decode_launch(c.dtype, D, a, true, st))) return rc;
-        }
-        for (int ci = 0; ci < n_chunks; ++ci) {  // prompts continuing a cached prefix: causal attention over their pages from the cached length
+        int rc = segment_attn_gqa_launch_t<T>(pa, D, st);
+        // the decode-state rows attend to their pages (which hold the row just appended)
+        if (!rc && n_decode > 0) rc = paged_decode_attn(d, li, n_decode, dsplits, kv, st);
+        for (int ci = 0; ci < n_chunks && !rc; ++ci) {  // prompts continuing a cached prefix: causal attention over their pages from the cached length
             const int32_t *ch = chunks + 4 * ci;
             PrefillAttnArgs ca = {};
             ca.q = s->q + (size_t)ch[0] * QD, ca.out = s->attn + (size_t)ch[0] * QD;
             ca.k = (const u16 *)slabs[li], ca.v = (const u16 *)slabs[li] + (size_t)c.n_kv_heads * PIE_PAGE_TOKENS * D;
             ca.offset = ch[2], ca.cap = PIE_PAGE_TOKENS, ca.block_table = block_tables + (size_t)ch[3] * max_blocks, ca.n_pages = n_pages;
             ca.M = ch[1], ca.Hq = c.n_heads, ca.Hkv = c.n_kv_heads, ca.scale = pa.scale;
-            if ((rc = prefill_attn_launch_t<T>(ca, D, st))) return rc;
+            rc = prefill_attn_launch_t<T>(ca, D, st);
         }
-        if ((rc = mlp_rows<T>(d, w, N, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
-    }
+        return rc;
+    });
+    if (rc) return rc;
     // the normalised last row of every prompt -> lm_head -> tail
     hipLaunchKernelGGL(k_gather_rows, dim3(S), dim3(256), 0, st, (const uint4 *)s->xn, last_rows, H / 8, (uint4 *)s->r);
     PIE_LAUNCH_CHECK();
-    RowsOpts head_opts;
-    head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
-    if ((rc = linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->r, S, logits, st, head_opts))) return rc;
+    if ((rc = lm_head_rows<T>(d, s->r, S, logits, st))) return rc;
     if ((rc = batch_tail_launch(d, ids, row_ctx, last_rows, N, S, logits, logprobs, next_tokens, st))) return rc;
     // the prompt rows' own records (pie_decoder_set_prompt_logprobs): s->xn still holds every row final-normed; the decode rows are not scored
     return score_prompt_rows<T>(d, s->xn + (size_t)n_decode * H, n_decode, N - n_decode, st);
 }
 
-static size_t active_page_bytes(const pie_decoder *d);
+// ---------------------------------------------------------------- what the page-pool entries refuse alike
+// bytes one page of the active format takes in a layer's slab: K block + V block of T rows, or the int8 page with its scales
+static size_t active_page_bytes(const pie_decoder *d) {
+    const pie_decoder_config &c = d->cfg;
+    return d->kv_i8 ? pie_page_i8_bytes(c.n_kv_heads, c.head_dim) : (size_t)2 * PIE_PAGE_TOKENS * c.n_kv_heads * c.head_dim * 2;
+}
+
+static const char *const SLABS_BELOW_ACTIVE_FORMAT =
+    "the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)";
+
+// The six refusals that pie_decoder_step_batch, pie_decoder_prefill_batch / _step_mixed and pie_decoder_spec_step_batch share, each written once.  An entry
+// fills the record and runs them as check(first, last) in the order it always made them, its own checks between them where they always stood: a call
+// that breaks two rules still reports the same one.
+enum PoolCheck { POOL_GLOBALS, POOL_LAYERS, POOL_SHAPE, POOL_SLAB_BYTES, POOL_HEAD_RATIO, POOL_SLABS };
+struct PoolRefusals {
+    const pie_decoder *d;
+    std::string who;                   // the entry's prefix ("...: ")
+    const void *const *slabs;          // the caller's pool: one slab of slab_bytes per layer holding n_pages pages, block tables of max_blocks entries
+    size_t n_pages, slab_bytes;
+    int max_blocks;
+    bool rows_ok;                      // the entry's row limits: refused together with the pool's size, as shape_msg
+    const char *shape_msg, *slab_msg;  // ... and the entry's wording of the slab_bytes refusal
+    int check(int first, int last) const {
+        for (int k = first; k <= last; ++k) {
+            if (k == POOL_GLOBALS) PIE_REQUIRE(d->glob_set, PIE_E_STATE, who + "set_globals must be called first");
+            if (k == POOL_LAYERS)
+                for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, who + "a layer has no weights (pie_decoder_set_layer)");
+            if (k == POOL_SHAPE) PIE_REQUIRE(rows_ok && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, who + shape_msg);
+            if (k == POOL_SLAB_BYTES) PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE, who + slab_msg);
+            if (k == POOL_HEAD_RATIO) {
+                const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
+                PIE_REQUIRE(rep >= 1 && rep <= 8, PIE_E_SHAPE, who + "n_heads / n_kv_heads must be between 1 and 8");
+            }
+            if (k == POOL_SLABS)
+                for (int i = 0; i < d->cfg.n_layers; ++i) PIE_REQUIRE(slabs[i] && pie_aligned(slabs[i], 16), PIE_E_ALIGN, who + "null or misaligned slab");
+        }
+        return PIE_OK;
+    }
+};
+
 static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_context_lens, const int32_t *row_seq, const int32_t *seg_lo,
                         const int32_t *seg_hi, const int32_t *last_rows, int N, int S, int n_decode, const void *const *slabs, size_t n_pages, size_t slab_bytes,
                         const int32_t *block_tables, int max_blocks, void *logits, float *logprobs, int32_t *next_tokens, void *stream, int n_chunks = 0,
@@ -1094,23 +1124,19 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
                         (ch[2] + ch[1] + PIE_PAGE_TOKENS - 1) / PIE_PAGE_TOKENS <= max_blocks,
                     PIE_E_SHAPE, "pie_decoder_step_mixed: a chunk is {first row >= n_decode, rows >= 1, cached positions >= 1, sequence < S} inside the batch and its block table");
     }
-    PIE_REQUIRE(d->glob_set, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: set_globals must be called first");
-    for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_prefill_batch / _step_mixed: a layer has no weights (pie_decoder_set_layer)");
+    const PoolRefusals shared = {d, "pie_decoder_prefill_batch / _step_mixed: ", slabs, n_pages, slab_bytes, max_blocks, S >= 1 && N >= S && N <= 65535,
+                                 "bad batch shape", SLABS_BELOW_ACTIVE_FORMAT};
+    if (int rc = shared.check(POOL_GLOBALS, POOL_LAYERS)) return rc;
     if (int rc = d->rows.check_rows(S, "pie_decoder_prefill_batch / _step_mixed")) return rc;
-    PIE_REQUIRE(!d->prompt.n || N <= d->prompt.rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: more rows than the prompt log-probabilities' rows_cap");
-    PIE_REQUIRE(!d->rows.top.n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: logprobs need 4-byte alignment");
-    PIE_REQUIRE(S >= 1 && N >= S && N <= 65535 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: bad batch shape");
-    PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
-                "pie_decoder_prefill_batch / _step_mixed: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
-    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: hidden must be a multiple of 8, at most 8192");
-    const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
-    PIE_REQUIRE(rep >= 1 && rep <= 8, PIE_E_SHAPE, "pie_decoder_prefill_batch / _step_mixed: n_heads / n_kv_heads must be between 1 and 8");
-    for (int i = 0; i < d->cfg.n_layers; ++i) PIE_REQUIRE(slabs[i] && pie_aligned(slabs[i], 16), PIE_E_ALIGN, "pie_decoder_prefill_batch / _step_mixed: null or misaligned slab");
-    hipStream_t st = (hipStream_t)stream;
-    return d->cfg.dtype == PIE_BF16 ? prefill_varlen_t<BF16>(d, ids, row_context_lens, row_seq, seg_lo, seg_hi, last_rows, N, S, n_decode, slabs, (int)n_pages,
-                                                             block_tables, max_blocks, (u16 *)logits, logprobs, next_tokens, st, n_chunks, chunks)
-                                    : prefill_varlen_t<F16>(d, ids, row_context_lens, row_seq, seg_lo, seg_hi, last_rows, N, S, n_decode, slabs, (int)n_pages,
-                                                            block_tables, max_blocks, (u16 *)logits, logprobs, next_tokens, st, n_chunks, chunks);
+    PIE_REQUIRE(!d->prompt.n || N <= d->prompt.rows_cap, PIE_E_SHAPE, shared.who + "more rows than the prompt log-probabilities' rows_cap");
+    PIE_REQUIRE(!d->rows.top.n || pie_aligned(logprobs, 4), PIE_E_ALIGN, shared.who + "logprobs need 4-byte alignment");
+    if (int rc = shared.check(POOL_SHAPE, POOL_SLAB_BYTES)) return rc;
+    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, shared.who + "hidden must be a multiple of 8, at most 8192");
+    if (int rc = shared.check(POOL_HEAD_RATIO, POOL_SLABS)) return rc;
+    return for_dtype(d->cfg.dtype, [&](auto t) {
+        return prefill_varlen_t<decltype(t)>(d, ids, row_context_lens, row_seq, seg_lo, seg_hi, last_rows, N, S, n_decode, slabs, (int)n_pages, block_tables,
+                                             max_blocks, (u16 *)logits, logprobs, next_tokens, (hipStream_t)stream, n_chunks, chunks);
+    });
 }
 
 extern "C" int pie_decoder_prefill_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_context_lens, const int32_t *row_seq,
@@ -1135,125 +1161,95 @@ extern "C" int pie_decoder_step_mixed(pie_decoder *d, const int32_t *ids, const 
 // pass's body on those N rows -- embed, linear_rows / mlp_rows, RoPE + append into each sequence's own pages -- with ONE attention launch
 // per layer for all segments (paged_attn_verify.hip) where that pass runs a segment kernel and a launch per chunk, the lm_head on ALL N
 // rows (s->xn holds them final-normed, in row order: nothing to gather) and the segmented verify behind it.
-static size_t align16z(size_t n) { return (n + 15) & ~(size_t)15; }
-
 template <class T>
 static int spec_batch_t(pie_decoder *d, const int32_t *fed, const int32_t *row_ctx, const int32_t *row_seq, const int32_t *seg_first, int N, int B,
                         const void *const *slabs, int n_pages, const int32_t *block_tables, int max_blocks, u16 *logits, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
-    const int H = c.hidden, D = c.head_dim, QD = c.n_heads * D, KVD = c.n_kv_heads * D, NQKV = QD + 2 * KVD;
+    const int D = c.head_dim;
     const int splits = paged_attn_verify_splits(B, c.n_kv_heads, max_blocks);
     int rc = scratch_reserve(d, N, w16_copy_elems(c, true), splits > d->splits ? splits : d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
-    if ((rc = embed_rows(d, fed, N, s->x, st))) return rc;
-    hipLaunchKernelGGL(k_rope_cs_rows, dim3(N), dim3(64), 0, st, d->glob.rope_freqs, nullptr, row_ctx, D / 2, s->rope_cs);
-    PIE_LAUNCH_CHECK();
-    for (int li = 0; li < c.n_layers; ++li) {
-        const pie_layer_weights &w = d->layers[li];
-        if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, N, H, c.dtype, s->xn, st))) return rc;
-        RowsOpts qkv_opts;  // q|k|v as the fp32 slabs of a K-split product only without a Linear bias: RoPE takes T(x W^T + b)
-        qkv_opts.bias = w.bqkv, qkv_opts.slabs = !w.bqkv;
-        RowsDone qkv_done;
-        if ((rc = linear_rows<T>(d, w.wqkv, NQKV, H, s->xn, N, s->qkv, st, qkv_opts, &qkv_done))) return rc;
-        const W4lSlabs &sq = qkv_done.slabs;
-        const auto rope_k = rope_append_kernel<T>(sq.S > 1, false);
-        hipLaunchKernelGGL(rope_k, dim3(N, sq.S > 1 ? 4u : 1u), dim3(256), 0, st, s->qkv, NQKV, d->glob.rope_freqs, nullptr, nullptr, li, c.n_layers, c.n_heads,
-                           c.n_kv_heads, D, c.rope_traditional, s->q, block_tables, n_pages, s->rope_cs, row_ctx, max_blocks, (u16 *)slabs[li], row_seq,
-                           (u16 *)nullptr, (u16 *)nullptr, sq.part, sq.S, sq.MN, (size_t)0);
-        PIE_LAUNCH_CHECK();
+    RowsKv kv;  // rows of a sequence share its block-table row; T pages only (the entry refuses int8 pages)
+    kv.row_ctx = row_ctx, kv.slabs = slabs, kv.block_tables = block_tables, kv.bt_stride = max_blocks, kv.n_pages = n_pages, kv.row_seq = row_seq;
+    rc = paged_rows_layers<T>(d, fed, N, kv, st, [&](int li) {
         VerifyAttnArgs a = {};  // every row attends its sequence's pages, which now hold the pass's own rows
         a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.row_seq = row_seq, a.row_ctx = row_ctx, a.seg_first = seg_first;
         a.N = N, a.B = B, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.bt_stride = max_blocks, a.n_pages = n_pages, a.splits = splits;
         a.scale = 1.0f / sqrtf((float)D), a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
-        if ((rc = paged_attn_verify_launch(c.dtype, D, a, st))) return rc;
-        if ((rc = mlp_rows<T>(d, w, N, li + 1 < c.n_layers ? d->layers[li + 1].attn_norm : d->glob.final_norm, st))) return rc;
-    }
-    RowsOpts head_opts;
-    head_opts.keep = false, head_opts.keep_w4m = true;  // no 16-bit resident copy of the lm_head, but its int4 tiles stay
-    return linear_rows<T>(d, d->glob.lm_head, c.vocab, H, s->xn, N, logits, st, head_opts);
+        return paged_attn_verify_launch(c.dtype, D, a, st);
+    });
+    if (rc) return rc;
+    return lm_head_rows<T>(d, s->xn, N, logits, st);
 }
 
 // workspace: the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows' workspace for 256 rows
 extern "C" size_t pie_decoder_spec_batch_workspace_bytes(const pie_decoder *d) {
     if (!d) return 0;
-    return align16z((size_t)SPEC_BATCH_ROWS * d->cfg.vocab * 2) + align16z(sizeof(int) * SPEC_BATCH_ROWS) + spec_verify_rows_workspace_bytes(SPEC_BATCH_ROWS);
+    return align16((size_t)SPEC_BATCH_ROWS * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_BATCH_ROWS) + spec_verify_rows_workspace_bytes(SPEC_BATCH_ROWS);
 }
 
 extern "C" int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride, const int32_t *row_context_lens,
                                            const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages,
                                            size_t slab_bytes, const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, int32_t *seq_ids,
                                            int32_t *seq_len, int seq_cap, void *workspace, void *stream) {
-    const char *who = "pie_decoder_spec_step_batch: ";
+    const std::string who = "pie_decoder_spec_step_batch: ";
     PIE_REQUIRE(d && tokens && draft_ids && row_context_lens && row_seq && seg_first && slabs && block_tables && out_tokens && out_n && workspace, PIE_E_ARG,
-                std::string(who) + "null pointer");
+                who + "null pointer");
     PIE_REQUIRE((seq_ids == nullptr) == (seq_len == nullptr) && (seq_ids ? seq_cap >= 1 : seq_cap == 0), PIE_E_ARG,
-                std::string(who) + "seq_ids [B, seq_cap >= 1] and seq_len come together or not at all");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, std::string(who) + "not available on a tensor-parallel shard");
-    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, std::string(who) + "not available on int8 KV pages");
+                who + "seq_ids [B, seq_cap >= 1] and seq_len come together or not at all");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
+    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
     const char *part = d->rows.spec_refused();
-    PIE_REQUIRE(!part, PIE_E_STATE, std::string(who) + "not available with " + part);
-    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, std::string(who) + "not available with prompt scoring");
-    PIE_REQUIRE(d->glob_set, PIE_E_STATE, std::string(who) + "set_globals must be called first");
-    for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, std::string(who) + "a layer has no weights (pie_decoder_set_layer)");
-    PIE_REQUIRE(B >= 1 && N >= B && N <= SPEC_BATCH_ROWS && N <= SPEC_SEG_ROWS * B && draft_stride >= 1 && max_blocks > 0 && n_pages > 0 &&
-                    n_pages < 0x7FFFFFFFu, PIE_E_SHAPE,
-                std::string(who) + "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool");
-    PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE, std::string(who) + "the slabs are smaller than n_pages T pages");
-    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, std::string(who) + "hidden must be a multiple of 8, at most 8192");
-    PIE_REQUIRE(d->cfg.head_dim == 64 || d->cfg.head_dim == 128, PIE_E_SHAPE, std::string(who) + "head_dim must be 64 or 128");
-    const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
-    PIE_REQUIRE(rep >= 1 && rep <= 8 && rep * d->cfg.n_kv_heads == d->cfg.n_heads, PIE_E_SHAPE, std::string(who) + "n_heads / n_kv_heads must be between 1 and 8");
+    PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
+    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
+    const PoolRefusals shared = {d, who, slabs, n_pages, slab_bytes, max_blocks, B >= 1 && N >= B && N <= SPEC_BATCH_ROWS && N <= SPEC_SEG_ROWS * B && draft_stride >= 1,
+                                 "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool", "the slabs are smaller than n_pages T pages"};
+    if (int rc = shared.check(POOL_GLOBALS, POOL_SLAB_BYTES)) return rc;
+    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, who + "hidden must be a multiple of 8, at most 8192");
+    PIE_REQUIRE(d->cfg.head_dim == 64 || d->cfg.head_dim == 128, PIE_E_SHAPE, who + "head_dim must be 64 or 128");
+    // this entry's ratio must also be whole: refused in the words of the shared check right behind it
+    PIE_REQUIRE(d->cfg.n_heads % d->cfg.n_kv_heads == 0, PIE_E_SHAPE, who + "n_heads / n_kv_heads must be between 1 and 8");
+    if (int rc = shared.check(POOL_HEAD_RATIO, POOL_HEAD_RATIO)) return rc;
     PIE_REQUIRE(pie_aligned(tokens, 4) && pie_aligned(draft_ids, 4) && pie_aligned(row_context_lens, 4) && pie_aligned(row_seq, 4) && pie_aligned(seg_first, 4) &&
                     pie_aligned(block_tables, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(seq_ids, 4) && pie_aligned(seq_len, 4),
-                PIE_E_ALIGN, std::string(who) + "4-byte alignment required");
-    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, std::string(who) + "workspace needs 16-byte alignment");
-    for (int i = 0; i < d->cfg.n_layers; ++i) PIE_REQUIRE(slabs[i] && pie_aligned(slabs[i], 16), PIE_E_ALIGN, std::string(who) + "null or misaligned slab");
+                PIE_E_ALIGN, who + "4-byte alignment required");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, who + "workspace needs 16-byte alignment");
+    if (int rc = shared.check(POOL_SLABS, POOL_SLABS)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int V = d->cfg.vocab;
     u16 *logits = (u16 *)workspace;
-    int *fed = (int *)((char *)workspace + align16z((size_t)SPEC_BATCH_ROWS * V * 2));
-    void *verify_ws = (char *)fed + align16z(sizeof(int) * SPEC_BATCH_ROWS);
+    int *fed = (int *)((char *)workspace + align16((size_t)SPEC_BATCH_ROWS * V * 2));
+    void *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_BATCH_ROWS);
     // a row no segment covers is fed id 0 (seg_first is device memory: nothing here can check it)
     PIE_HIP_TRY(hipMemsetAsync(fed, 0, sizeof(int) * (size_t)N, st));
     if (int rc = spec_gather_rows_launch(tokens, draft_ids, draft_stride, seg_first, B, N, d->embed_vocab(), fed, st)) return rc;
-    const int rc = d->cfg.dtype == PIE_BF16
-                       ? spec_batch_t<BF16>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st)
-                       : spec_batch_t<F16>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st);
+    const int rc = for_dtype(d->cfg.dtype, [&](auto t) {
+        return spec_batch_t<decltype(t)>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st);
+    });
     if (rc) return rc;
     return spec_verify_rows_launch(logits, N, V, d->cfg.dtype, seg_first, B, draft_ids, draft_stride, out_tokens, out_n, seq_ids, seq_len, seq_cap, verify_ws, st);
-}
-
-static int decode_batch(pie_decoder *d, const int32_t *tokens, const int32_t *ctx_len, const void *const *slabs, int n_pages, const int32_t *block_tables,
-                        int max_blocks, int B, void *logits, float *logprobs, int32_t *next_tokens, hipStream_t st) {
-    return d->cfg.dtype == PIE_BF16
-               ? decode_batch_t<BF16>(d, tokens, ctx_len, slabs, n_pages, block_tables, max_blocks, B, (u16 *)logits, logprobs, next_tokens, st)
-               : decode_batch_t<F16>(d, tokens, ctx_len, slabs, n_pages, block_tables, max_blocks, B, (u16 *)logits, logprobs, next_tokens, st);
-}
-
-// bytes one page of the active format takes in a layer's slab: K block + V block of T rows, or the int8 page with its scales
-static size_t active_page_bytes(const pie_decoder *d) {
-    const pie_decoder_config &c = d->cfg;
-    return d->kv_i8 ? pie_page_i8_bytes(c.n_kv_heads, c.head_dim) : (size_t)2 * PIE_PAGE_TOKENS * c.n_kv_heads * c.head_dim * 2;
 }
 
 extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, const int32_t *context_lens, const void *const *slabs, size_t n_pages, size_t slab_bytes,
                                       const int32_t *block_tables, int max_blocks, int B, void *logits, float *logprobs, int32_t *next_tokens,
                                       int flags, void *stream) {
-    PIE_REQUIRE(d && tokens && context_lens && slabs && block_tables && logits && logprobs && next_tokens, PIE_E_ARG, "pie_decoder_step_batch: null pointer");
-    PIE_REQUIRE(d->glob_set, PIE_E_STATE, "pie_decoder_step_batch: set_globals must be called first");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, "pie_decoder_step_batch: not available on a tensor-parallel shard");
-    for (char s : d->layer_set) PIE_REQUIRE(s, PIE_E_STATE, "pie_decoder_step_batch: a layer has no weights (pie_decoder_set_layer)");
-    PIE_REQUIRE(B >= 1 && B <= 4096 && max_blocks > 0 && n_pages > 0 && n_pages < 0x7FFFFFFFu, PIE_E_SHAPE, "pie_decoder_step_batch: bad batch shape");
+    const std::string who = "pie_decoder_step_batch: ";
+    PIE_REQUIRE(d && tokens && context_lens && slabs && block_tables && logits && logprobs && next_tokens, PIE_E_ARG, who + "null pointer");
+    const PoolRefusals shared = {d, who, slabs, n_pages, slab_bytes, max_blocks, B >= 1 && B <= 4096, "bad batch shape", SLABS_BELOW_ACTIVE_FORMAT};
+    if (int rc = shared.check(POOL_GLOBALS, POOL_GLOBALS)) return rc;
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
+    if (int rc = shared.check(POOL_LAYERS, POOL_SHAPE)) return rc;
     if (int rc = d->rows.check_rows(B, "pie_decoder_step_batch")) return rc;
-    PIE_REQUIRE(!d->rows.top.n || pie_aligned(logprobs, 4), PIE_E_ALIGN, "pie_decoder_step_batch: logprobs need 4-byte alignment");
-    PIE_REQUIRE(slab_bytes >= n_pages * active_page_bytes(d), PIE_E_SHAPE,
-                "pie_decoder_step_batch: the slabs are smaller than n_pages pages of the active page format (an int8 pool needs PIE_OPT_KV_I8, a T pool must not have it)");
-    const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
-    PIE_REQUIRE(rep >= 1 && rep <= 8, PIE_E_SHAPE, "pie_decoder_step_batch: n_heads / n_kv_heads must be between 1 and 8");
-    for (int i = 0; i < d->cfg.n_layers; ++i) PIE_REQUIRE(slabs[i] && pie_aligned(slabs[i], 16), PIE_E_ALIGN, "pie_decoder_step_batch: null or misaligned slab");
+    PIE_REQUIRE(!d->rows.top.n || pie_aligned(logprobs, 4), PIE_E_ALIGN, who + "logprobs need 4-byte alignment");
+    if (int rc = shared.check(POOL_SLAB_BYTES, POOL_SLABS)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (!(flags & PIE_STEP_GRAPH)) return decode_batch(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, logits, logprobs, next_tokens, st);
+    const auto decode_batch = [&](hipStream_t on) {  // the step's launches on a stream: the caller's, or the capturing one
+        return for_dtype(d->cfg.dtype, [&](auto t) {
+            return decode_batch_t<decltype(t)>(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, (u16 *)logits, logprobs, next_tokens, on);
+        });
+    };
+    if (!(flags & PIE_STEP_GRAPH)) return decode_batch(st);
     // Graph replay.  The launches bake in the caller's buffers and this library's scratch / resident weight copies, so a graph is
     // captured only for a call that repeats the previous call's buffers after that call allocated nothing, and is dropped when
     // either changes.  (First call with new buffers: eager, it may allocate; second: capture; from the third: replay.)
@@ -1274,15 +1270,13 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
         hipGraph_t g = nullptr;
         hipError_t e = hipSuccess;
         int rc = PIE_OK;
-        const int crc = capture_graph(
-            [&](hipStream_t cs) { return decode_batch(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, logits, logprobs, next_tokens, cs); },
-            &rc, &g, &e);
+        const int crc = capture_graph(decode_batch, &rc, &g, &e);
         if (crc) return crc;
         if (rc || e != hipSuccess || d->prefill->alloc_gen != gen) {  // something allocated or failed under capture: run this call eagerly instead
             if (g) (void)hipGraphDestroy(g);
             (void)hipGetLastError();
             d->prefill->warm_key.clear();
-            return decode_batch(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, logits, logprobs, next_tokens, st);
+            return decode_batch(st);
         }
         s = d->prefill;
         e = hipGraphInstantiate(&s->batch_graph, g, nullptr, nullptr, 0);
@@ -1293,7 +1287,7 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
         PIE_HIP_TRY(hipGraphLaunch(s->batch_graph, st));
         return PIE_OK;
     }
-    const int rc = decode_batch(d, tokens, context_lens, slabs, (int)n_pages, block_tables, max_blocks, B, logits, logprobs, next_tokens, st);
+    const int rc = decode_batch(st);
     d->prefill->warm_key = key, d->prefill->warm_gen = d->prefill->alloc_gen;
     return rc;
 }
@@ -1301,5 +1295,5 @@ extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, con
 int prefill_batched(pie_decoder *d, const int32_t *ids, const void *embeds, int L, void *logits_all, hipStream_t st) {
     const int rep = d->cfg.n_heads / d->cfg.n_kv_heads;
     PIE_REQUIRE(rep >= 1 && rep <= 8, PIE_E_SHAPE, "prefill: n_heads / n_kv_heads must be between 1 and 8");
-    return d->cfg.dtype == PIE_BF16 ? prefill_t<BF16>(d, ids, embeds, L, logits_all, st) : prefill_t<F16>(d, ids, embeds, L, logits_all, st);
+    return for_dtype(d->cfg.dtype, [&](auto t) { return prefill_t<decltype(t)>(d, ids, embeds, L, logits_all, st); });
 }

@@ -371,8 +371,6 @@ __global__ void k_spec_gather(const DecState *state, const int *draft, int m, in
     fed[i] = id >= 0 && id < vocab ? id : 0;
 }
 
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 struct SpecDfaLayout {  // pie_decoder_spec_step_dfa's part of the workspace, behind the `head` bytes of pie_decoder_spec_step_tail's
     size_t states, mask_on, records, masks, bytes;
     int mask_words;
