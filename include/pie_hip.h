@@ -1185,6 +1185,54 @@ int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens, const int
                                 const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages, size_t slab_bytes,
                                 const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, int32_t *seq_ids, int32_t *seq_len, int seq_cap,
                                 void *workspace, void *stream);
+/* The batched pass under per-seat tails: pie_spec_verify_sampled's rule -- a prompt-lookup draft is a point mass, so row j
+ * is drawn with the draw the plain loop would use for that position and a draft is accepted while it equals the draw -- on every segment
+ * of a batched pass, each under its own seat's state.  Record, ring, bias entries and XTC record s belong to segment s.
+ * pie_spec_verify_rows_sampled: logits T [n_rows, V], EDITED IN PLACE; seg_first [B + 1] and draft_ids [B, draft_stride] as
+ *   pie_spec_verify_rows takes them; fed DEVICE int32 [n_rows] = the rows' input ids (a segment's fed token, then its drafts, an id the
+ *   embedding could not index replaced by 0: what pie_decoder_spec_step_batch gathers); pos0 DEVICE int32 [B] = the position of every
+ *   segment's first row (negative: the segment's rows are not edited and its seat does not move); table DEVICE pie_row_tail [B], 8-byte
+ *   aligned; recent_ids DEVICE int32 [B, 1024], the rings of pie_logits_penalty_rows; bias_ids / bias_vals [B, bias_cap] and bias_n [B]
+ *   (nullable, together; 1 <= bias_cap <= 1024) as pie_logits_bias_rows takes them; xtc (nullable) DEVICE pie_xtc [B].
+ *   For row r = seg_first[s] + j of segment s, at position p = pos0[s] + j, with calls_s = table[s].calls at entry:
+ *   - the repetition penalty of table[s] over the ids at positions max(0, p + 1 - context_size) .. p: recent_ids[s][q & 1023] for q <
+ *     pos0[s], fed[seg_first[s] + i] for q = pos0[s] + i, 0 <= i <= j (never read from the ring); then seat s's bias entries: the
+ *     arithmetic and the ownership rule among duplicate ids of pie_logits_penalty / pie_logits_bias; a penalty of exactly 1.0 edits nothing;
+ *   - logprobs (required) fp32 [n_rows, V]: every row gets pie_logprobs_argmax's bits of the processed row alone;
+ *   - t_r = the token a one-row pie_sample (pie_sample_xtc with xtc) draws from that row with table[s]'s mode, temperature, p, k and
+ *     seed and a counter of {calls_s + j, 0}; the row's argmax for a greedy or unknown mode;
+ *   - n_acc_s = the largest j <= m_s with draft[s][i] == t_{first + i} for all i < j; a draft id outside [0, V) is never accepted and
+ *     never used as an index; out_n [B] = n_acc_s + 1 (0 for an idle slot), out_tokens [B, 8] = those tokens, then -1.  The contract
+ *     covers every row whose preceding drafts all lie inside the vocabulary; the rows behind an invalid draft are written but unspecified.
+ *   Afterwards, by ONE launch behind every draw (one thread per sequence, nothing depends on arrival order): table[s].calls = calls_s +
+ *   out_n[s] for a drawing mode (a greedy seat's record is not written); recent_ids[s][(pos0[s] + i) & 1023] = fed[seg_first[s] + i]
+ *   for i < out_n[s] and no other slot -- no row writes the ring before that launch, so a plain pass that follows finds the ring and the
+ *   stream where out_n[s] plain steps would have left them; ids / len (nullable) move as in pie_spec_verify_rows.
+ *   Launches: the edit over (8, B) workgroups (1), the partials and the finish over every row (2), a fill of the rows' records with the
+ *   greedy mode and one launch that expands the seats' records over their rows (2), pie_sample_rows' 5 (6 with xtc), the commit (1).
+ *   The only atomics are the sampler's own.  workspace: pie_spec_verify_rows_sampled_workspace_bytes(n_rows, V) bytes (0 for refused
+ *   sizes), 16-byte aligned, ZEROED ONCE by the caller (as pie_sample's) and reusable from call to call.  Each before any launch: a null
+ *   pointer (the bias part, xtc, ids / len excepted), a partial bias part, a dtype that is neither PIE_BF16 nor PIE_F16: PIE_E_ARG;
+ *   n_rows outside 1..65535, V outside 1..524288, B outside 1..4096, draft_stride < 1: PIE_E_SHAPE; logits not 2-byte, an index array,
+ *   a part of the seats' state or an output not 4-byte, the table not 8-byte, the workspace not 16-byte aligned: PIE_E_ALIGN.
+ * pie_decoder_spec_step_batch_tail: pie_decoder_spec_step_batch's arguments plus logprobs fp32 [>= N, V], and its pass up to the lm_head;
+ *   behind it pie_spec_verify_rows_sampled with the batch tail's table and rings (pie_decoder_set_batch_tail: required, else PIE_E_STATE),
+ *   the bias part of pie_decoder_set_batch_logits_edits and pie_decoder_set_batch_xtc's records where set, seat s = sequence s, pos0[s] =
+ *   row_context_lens[seg_first[s]] - 1.  The workspace's head then holds the processed logits [N, V].  PIE_E_STATE before any launch,
+ *   each by name: int8 pages, a tensor-parallel decoder, batch token automata, a mask part of the batch logits edits, a batch count
+ *   penalty, a batch DRY penalty, batch top log-probabilities, prompt scoring; PIE_E_SHAPE for more sequences than a configured part's
+ *   rows_cap.  pie_decoder_spec_step_batch itself still refuses every configured part.  workspace:
+ *   pie_decoder_spec_batch_tail_workspace_bytes(d) bytes, 16-byte aligned, zeroed once. */
+size_t pie_spec_verify_rows_sampled_workspace_bytes(int n_rows, int V);
+int pie_spec_verify_rows_sampled(void *logits, int n_rows, int V, int dtype, const int32_t *seg_first, int B, const int32_t *fed, const int32_t *draft_ids,
+                                 int draft_stride, const int32_t *pos0, pie_row_tail *table, int32_t *recent_ids, const int32_t *bias_ids, const float *bias_vals,
+                                 const int32_t *bias_n, int bias_cap, const pie_xtc *xtc, int32_t *out_tokens, int32_t *out_n, float *logprobs, int32_t *ids,
+                                 int32_t *len, int cap, void *workspace, void *stream);
+size_t pie_decoder_spec_batch_tail_workspace_bytes(const pie_decoder *d);
+int pie_decoder_spec_step_batch_tail(pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride, const int32_t *row_context_lens,
+                                     const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages, size_t slab_bytes,
+                                     const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, float *logprobs, int32_t *seq_ids,
+                                     int32_t *seq_len, int seq_cap, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------- quantized KV cache (QuantizedKVCache, cache/kv_cache/quantized.py)
  * The reference's format: every cached row stored as mx.quantize output -- codes uint32 [n_kv_heads, capacity, head_dim*bits/32],

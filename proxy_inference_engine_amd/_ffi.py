@@ -61,6 +61,7 @@ EXPORTS = [
     "pie_token_dfa_walk", "pie_token_dfa_draft", "pie_decoder_spec_dfa_workspace_bytes", "pie_decoder_spec_step_dfa",
     "pie_paged_attn_verify_splits", "pie_paged_attn_verify_workspace_bytes", "pie_paged_attn_verify", "pie_ngram_draft_rows_workspace_bytes", "pie_ngram_draft_rows",
     "pie_spec_verify_rows_workspace_bytes", "pie_spec_verify_rows", "pie_decoder_spec_batch_workspace_bytes", "pie_decoder_spec_step_batch",
+    "pie_spec_verify_rows_sampled_workspace_bytes", "pie_spec_verify_rows_sampled", "pie_decoder_spec_batch_tail_workspace_bytes", "pie_decoder_spec_step_batch_tail",
 ]
 
 
@@ -262,6 +263,14 @@ def load() -> C.CDLL:
     lib.pie_decoder_spec_batch_workspace_bytes.argtypes = [C.c_void_p]
     lib.pie_decoder_spec_step_batch.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [
         C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_spec_verify_rows_sampled_workspace_bytes.restype = C.c_size_t
+    lib.pie_spec_verify_rows_sampled_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pie_spec_verify_rows_sampled.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [
+        C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.pie_decoder_spec_batch_tail_workspace_bytes.restype = C.c_size_t
+    lib.pie_decoder_spec_batch_tail_workspace_bytes.argtypes = [C.c_void_p]
+    lib.pie_decoder_spec_step_batch_tail.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [
+        C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_comm_create.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.pie_comm_rccl_unique_id.argtypes = [C.c_void_p]
     lib.pie_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]

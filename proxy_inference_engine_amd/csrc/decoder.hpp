@@ -95,6 +95,12 @@ struct RowsTail {
         return sampler.table ? "a batch tail" : dfa.records ? "batch token automata" : edits.rows_cap ? "batch logits edits" : counts.records ? "a batch count penalty"
                : dry.records ? "a batch DRY penalty" : xtc.records ? "batch XTC records" : top.n ? "batch top log-probabilities" : nullptr;
     }
+    // The pass under the seats' tails (pie_decoder_spec_step_batch_tail) admits the batch tail, the edits' bias part and the
+    // XTC records; every other configured part is refused by name.
+    const char *spec_tail_refused() const {
+        return dfa.records ? "batch token automata" : edits.masks ? "a mask part of the batch logits edits" : counts.records ? "a batch count penalty"
+               : dry.records ? "a batch DRY penalty" : top.n ? "batch top log-probabilities" : nullptr;
+    }
 };
 
 // The single-sequence step's configured tail, applied where the tail writes the bound outputs and pie_decoder::tail_raw is

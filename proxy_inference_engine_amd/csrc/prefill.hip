@@ -1183,6 +1183,52 @@ static int spec_batch_t(pie_decoder *d, const int32_t *fed, const int32_t *row_c
     return lm_head_rows<T>(d, s->xn, N, logits, st);
 }
 
+// What pie_decoder_spec_step_batch and pie_decoder_spec_step_batch_tail share: the entry's refusals -- with_tail: which parts of the batch
+// tail the pass admits is RowsTail's answer (decoder.hpp) --, the pool's, shape and alignment checks, the workspace's carve-up (the logits
+// block at its head, then *fed, then *verify_ws), the gather of the input rows and the pass itself, raw logits on every row.
+static int spec_batch_body(const std::string &who, bool with_tail, pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride,
+                           const int32_t *row_context_lens, const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages,
+                           size_t slab_bytes, const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, float *logprobs, int32_t *seq_ids,
+                           int32_t *seq_len, int seq_cap, void *workspace, hipStream_t st, int **fed_out, void **verify_ws) {
+    PIE_REQUIRE(d && tokens && draft_ids && row_context_lens && row_seq && seg_first && slabs && block_tables && out_tokens && out_n && (logprobs || !with_tail) && workspace,
+                PIE_E_ARG, who + "null pointer");
+    PIE_REQUIRE((seq_ids == nullptr) == (seq_len == nullptr) && (seq_ids ? seq_cap >= 1 : seq_cap == 0), PIE_E_ARG,
+                who + "seq_ids [B, seq_cap >= 1] and seq_len come together or not at all");
+    PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
+    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
+    const char *part = with_tail ? d->rows.spec_tail_refused() : d->rows.spec_refused();
+    PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
+    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
+    PIE_REQUIRE(!with_tail || d->rows.sampler.table, PIE_E_STATE, who + "no batch tail is set (the greedy and raw pass is pie_decoder_spec_step_batch)");
+    const PoolRefusals shared = {d, who, slabs, n_pages, slab_bytes, max_blocks, B >= 1 && N >= B && N <= SPEC_BATCH_ROWS && N <= SPEC_SEG_ROWS * B && draft_stride >= 1,
+                                 "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool", "the slabs are smaller than n_pages T pages"};
+    if (int rc = shared.check(POOL_GLOBALS, POOL_SLAB_BYTES)) return rc;
+    if (with_tail)  // record, ring, bias entries and XTC record s belong to sequence s: every configured part holds B of them
+        if (int rc = d->rows.check_rows(B, "pie_decoder_spec_step_batch_tail")) return rc;
+    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, who + "hidden must be a multiple of 8, at most 8192");
+    PIE_REQUIRE(d->cfg.head_dim == 64 || d->cfg.head_dim == 128, PIE_E_SHAPE, who + "head_dim must be 64 or 128");
+    // this entry's ratio must also be whole: refused in the words of the shared check right behind it
+    PIE_REQUIRE(d->cfg.n_heads % d->cfg.n_kv_heads == 0, PIE_E_SHAPE, who + "n_heads / n_kv_heads must be between 1 and 8");
+    if (int rc = shared.check(POOL_HEAD_RATIO, POOL_HEAD_RATIO)) return rc;
+    PIE_REQUIRE(pie_aligned(tokens, 4) && pie_aligned(draft_ids, 4) && pie_aligned(row_context_lens, 4) && pie_aligned(row_seq, 4) && pie_aligned(seg_first, 4) &&
+                    pie_aligned(block_tables, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(logprobs, 4) && pie_aligned(seq_ids, 4) &&
+                    pie_aligned(seq_len, 4),
+                PIE_E_ALIGN, who + "4-byte alignment required");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, who + "workspace needs 16-byte alignment");
+    PIE_REQUIRE(!with_tail || pie_sample_workspace_bytes(SPEC_BATCH_ROWS, d->cfg.vocab) != 0, PIE_E_SHAPE, who + "the vocabulary is larger than the sampler takes (524288)");
+    if (int rc = shared.check(POOL_SLABS, POOL_SLABS)) return rc;
+    const int V = d->cfg.vocab;
+    u16 *logits = (u16 *)workspace;
+    int *fed = (int *)((char *)workspace + align16((size_t)SPEC_BATCH_ROWS * V * 2));
+    *fed_out = fed, *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_BATCH_ROWS);
+    // a row no segment covers is fed id 0 (seg_first is device memory: nothing here can check it)
+    PIE_HIP_TRY(hipMemsetAsync(fed, 0, sizeof(int) * (size_t)N, st));
+    if (int rc = spec_gather_rows_launch(tokens, draft_ids, draft_stride, seg_first, B, N, d->embed_vocab(), fed, st)) return rc;
+    return for_dtype(d->cfg.dtype, [&](auto t) {
+        return spec_batch_t<decltype(t)>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st);
+    });
+}
+
 // workspace: the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows' workspace for 256 rows
 extern "C" size_t pie_decoder_spec_batch_workspace_bytes(const pie_decoder *d) {
     if (!d) return 0;
@@ -1193,42 +1239,41 @@ extern "C" int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens
                                            const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages,
                                            size_t slab_bytes, const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, int32_t *seq_ids,
                                            int32_t *seq_len, int seq_cap, void *workspace, void *stream) {
-    const std::string who = "pie_decoder_spec_step_batch: ";
-    PIE_REQUIRE(d && tokens && draft_ids && row_context_lens && row_seq && seg_first && slabs && block_tables && out_tokens && out_n && workspace, PIE_E_ARG,
-                who + "null pointer");
-    PIE_REQUIRE((seq_ids == nullptr) == (seq_len == nullptr) && (seq_ids ? seq_cap >= 1 : seq_cap == 0), PIE_E_ARG,
-                who + "seq_ids [B, seq_cap >= 1] and seq_len come together or not at all");
-    PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
-    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
-    const char *part = d->rows.spec_refused();
-    PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
-    PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
-    const PoolRefusals shared = {d, who, slabs, n_pages, slab_bytes, max_blocks, B >= 1 && N >= B && N <= SPEC_BATCH_ROWS && N <= SPEC_SEG_ROWS * B && draft_stride >= 1,
-                                 "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool", "the slabs are smaller than n_pages T pages"};
-    if (int rc = shared.check(POOL_GLOBALS, POOL_SLAB_BYTES)) return rc;
-    PIE_REQUIRE(d->cfg.hidden % 8 == 0 && d->cfg.hidden <= 8192, PIE_E_SHAPE, who + "hidden must be a multiple of 8, at most 8192");
-    PIE_REQUIRE(d->cfg.head_dim == 64 || d->cfg.head_dim == 128, PIE_E_SHAPE, who + "head_dim must be 64 or 128");
-    // this entry's ratio must also be whole: refused in the words of the shared check right behind it
-    PIE_REQUIRE(d->cfg.n_heads % d->cfg.n_kv_heads == 0, PIE_E_SHAPE, who + "n_heads / n_kv_heads must be between 1 and 8");
-    if (int rc = shared.check(POOL_HEAD_RATIO, POOL_HEAD_RATIO)) return rc;
-    PIE_REQUIRE(pie_aligned(tokens, 4) && pie_aligned(draft_ids, 4) && pie_aligned(row_context_lens, 4) && pie_aligned(row_seq, 4) && pie_aligned(seg_first, 4) &&
-                    pie_aligned(block_tables, 4) && pie_aligned(out_tokens, 4) && pie_aligned(out_n, 4) && pie_aligned(seq_ids, 4) && pie_aligned(seq_len, 4),
-                PIE_E_ALIGN, who + "4-byte alignment required");
-    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, who + "workspace needs 16-byte alignment");
-    if (int rc = shared.check(POOL_SLABS, POOL_SLABS)) return rc;
+    int *fed;
+    void *verify_ws;
     hipStream_t st = (hipStream_t)stream;
-    const int V = d->cfg.vocab;
-    u16 *logits = (u16 *)workspace;
-    int *fed = (int *)((char *)workspace + align16((size_t)SPEC_BATCH_ROWS * V * 2));
-    void *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_BATCH_ROWS);
-    // a row no segment covers is fed id 0 (seg_first is device memory: nothing here can check it)
-    PIE_HIP_TRY(hipMemsetAsync(fed, 0, sizeof(int) * (size_t)N, st));
-    if (int rc = spec_gather_rows_launch(tokens, draft_ids, draft_stride, seg_first, B, N, d->embed_vocab(), fed, st)) return rc;
-    const int rc = for_dtype(d->cfg.dtype, [&](auto t) {
-        return spec_batch_t<decltype(t)>(d, fed, row_context_lens, row_seq, seg_first, N, B, slabs, (int)n_pages, block_tables, max_blocks, logits, st);
-    });
-    if (rc) return rc;
-    return spec_verify_rows_launch(logits, N, V, d->cfg.dtype, seg_first, B, draft_ids, draft_stride, out_tokens, out_n, seq_ids, seq_len, seq_cap, verify_ws, st);
+    if (int rc = spec_batch_body("pie_decoder_spec_step_batch: ", false, d, tokens, draft_ids, draft_stride, row_context_lens, row_seq, seg_first, N, B, slabs, n_pages,
+                                 slab_bytes, block_tables, max_blocks, out_tokens, out_n, nullptr, seq_ids, seq_len, seq_cap, workspace, st, &fed, &verify_ws))
+        return rc;
+    return spec_verify_rows_launch((const u16 *)workspace, N, d->cfg.vocab, d->cfg.dtype, seg_first, B, draft_ids, draft_stride, out_tokens, out_n, seq_ids, seq_len, seq_cap,
+                                   verify_ws, st);
+}
+
+// workspace: the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows_sampled's workspace for 256 rows (zeroed once)
+extern "C" size_t pie_decoder_spec_batch_tail_workspace_bytes(const pie_decoder *d) {
+    if (!d || spec_verify_rows_sampled_workspace_bytes(SPEC_BATCH_ROWS, d->cfg.vocab) == 0) return 0;
+    return align16((size_t)SPEC_BATCH_ROWS * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_BATCH_ROWS) +
+           spec_verify_rows_sampled_workspace_bytes(SPEC_BATCH_ROWS, d->cfg.vocab);
+}
+
+// The pass under the seats' own tails: the same body, then the batch tail's records and rings, the batch edits' bias part
+// and the batch XTC records applied to every segment's rows, and moved by what the pass accepted (speculative.hip).
+extern "C" int pie_decoder_spec_step_batch_tail(pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride, const int32_t *row_context_lens,
+                                                const int32_t *row_seq, const int32_t *seg_first, int N, int B, const void *const *slabs, size_t n_pages,
+                                                size_t slab_bytes, const int32_t *block_tables, int max_blocks, int32_t *out_tokens, int32_t *out_n, float *logprobs,
+                                                int32_t *seq_ids, int32_t *seq_len, int seq_cap, void *workspace, void *stream) {
+    int *fed;
+    void *verify_ws;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = spec_batch_body("pie_decoder_spec_step_batch_tail: ", true, d, tokens, draft_ids, draft_stride, row_context_lens, row_seq, seg_first, N, B, slabs, n_pages,
+                                 slab_bytes, block_tables, max_blocks, out_tokens, out_n, logprobs, seq_ids, seq_len, seq_cap, workspace, st, &fed, &verify_ws))
+        return rc;
+    const RowsTail &t = d->rows;
+    SpecSeats q;
+    q.table = t.sampler.table, q.recent = t.sampler.recent, q.row_ctx = row_context_lens, q.xtc = t.xtc.records;
+    if (t.edits.rows_cap && t.edits.bias_cap) q.bias_ids = t.edits.bias_ids, q.bias_vals = t.edits.bias_vals, q.bias_n = t.edits.bias_n, q.bias_cap = t.edits.bias_cap;
+    return spec_verify_rows_sampled_launch(q, (u16 *)workspace, N, d->cfg.vocab, d->cfg.dtype, seg_first, B, fed, draft_ids, draft_stride, out_tokens, out_n, logprobs,
+                                           seq_ids, seq_len, seq_cap, verify_ws, st);
 }
 
 extern "C" int pie_decoder_step_batch(pie_decoder *d, const int32_t *tokens, const int32_t *context_lens, const void *const *slabs, size_t n_pages, size_t slab_bytes,

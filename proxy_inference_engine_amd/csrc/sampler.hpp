@@ -30,6 +30,9 @@ struct SampleXtc {
     int *removed;
 };
 
+// a pie_row_tail's mode draws: one of sampler.hip's four modes; anything else acts as PIE_SAMPLE_GREEDY and leaves the record alone
+__host__ __device__ inline bool sample_mode_draws(int mode) { return mode >= 0 && mode <= 3; }
+
 // pie_sample's argument checks, reported under `who`; nothing is launched
 int sample_check(const char *who, int V, int mode, double temp, double p, int k, const void *workspace);
 // what the launches compute with, from pie_sample's parameters: the ONE place (pie_row_tail_pack's and the speculative verify's records draw as sample_launch does)

@@ -37,6 +37,14 @@
 //   7. k_spec_draft_commit, one workgroup: the accepted drafts, then the residual's token (the row's ordinary draw when no tile had a
 //      finite entry, or behind a fully accepted block), through spec_commit; counter = {c + n, 0} (1).
 //   No floating-point atomics; every reduction has a fixed order; n_acc stays on the device.
+// pie_spec_verify_rows_sampled, 10 launches and a fill (11 with XTC records): pie_spec_verify_sampled's rule per segment of a batched pass
+//   1. k_spec_edit_seg_rows over (8, B): workgroup (j, s) applies seat s's repetition penalty -- the window from the seat's ring below
+//      the segment's first position and from the pass's own inputs from it on -- and the seat's bias entries to row j of segment s (1);
+//   2. k_logits_stats and k_logits_finish over every row (2);
+//   3. the rows' records filled with the greedy mode, then k_spec_fill_seg_rows, one workgroup per segment: row j's record = the seat's
+//      with calls + j (and the seat's XTC record), in the workspace (1 + the fill);
+//   4. pie_sample_rows(_xtc)'s launches over the N rows (5 or 6);
+//   5. k_spec_commit_rows, one thread per sequence: k_spec_accept_rows' part over the drawn tokens, then the seat's calls and ring (1).
 // pie_decoder_spec_step_tail (and _spec_step_draft) puts k_spec_edit_rows in front: one workgroup per row applies the decoder's repetition penalty over the row's
 // own window (ids_by_pos below the offset, the fed token at it, the drafts behind it) and its logit bias (tail.hpp's phases).
 #include "speculative.hpp"
@@ -207,30 +215,141 @@ struct SpecRowsArgs {
 
 // Thread s is sequence s: pie_spec_verify's rule on its own rows (spec_count_accepted, at most 7 comparisons), then its tokens behind its
 // ids.  An idle slot (no rows): out_n = 0.  seg_first is device memory: the rows are clamped into [0, N] and to 8 before anything is read.
-__global__ void __launch_bounds__(64) k_spec_accept_rows(const SpecRowsArgs a) {
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= a.B) return;
-    int r0 = a.seg_first[s], r1 = a.seg_first[s + 1];
-    r0 = r0 < 0 ? 0 : (r0 > a.N ? a.N : r0);
-    r1 = r1 < r0 ? r0 : (r1 > a.N ? a.N : r1);
-    const int rows = r1 - r0 > SPEC_SEG_ROWS ? SPEC_SEG_ROWS : r1 - r0;
+// Segment s of seg_first [B + 1] as every kernel of a batched pass reads it: its first row, and how many rows it has (0: an idle slot)
+__device__ __forceinline__ int spec_segment(const int *seg_first, int s, int N, int &r0) {
+    int r1 = seg_first[s + 1];
+    r0 = seg_first[s];
+    r0 = r0 < 0 ? 0 : (r0 > N ? N : r0);
+    r1 = r1 < r0 ? r0 : (r1 > N ? N : r1);
+    return r1 - r0 > SPEC_SEG_ROWS ? SPEC_SEG_ROWS : r1 - r0;
+}
+
+// What k_spec_accept_rows does for sequence s, for the kernels that end in it: returns out_n[s] and the segment's first row.
+__device__ __forceinline__ int spec_accept_seq(const SpecRowsArgs &a, int s, int &r0) {
+    const int rows = spec_segment(a.seg_first, s, a.N, r0);
     int *out = a.out_tokens + (size_t)s * SPEC_SEG_ROWS;
     if (rows == 0) {
         for (int i = 0; i < SPEC_SEG_ROWS; ++i) out[i] = -1;
         a.out_n[s] = 0;
-        return;
+        return 0;
     }
     const int *tok = a.tok + r0;
     // (a row behind the drafts the stride holds has no draft: it ends the run like a refused one)
     const int n_acc = spec_count_accepted(a.draft + (size_t)s * a.draft_stride, tok, rows > a.draft_stride + 1 ? a.draft_stride + 1 : rows, a.V);
     for (int i = 0; i < SPEC_SEG_ROWS; ++i) out[i] = i <= n_acc ? tok[i] : -1;
     a.out_n[s] = n_acc + 1;
-    if (!a.ids) return;
+    if (!a.ids) return n_acc + 1;
     // ids[s, len - 1] is the token this pass was fed; the chosen tokens follow it, the last of them being the next pass's input
     int L = a.len[s];
     L = L < 0 ? 0 : (L > a.cap ? a.cap : L);
     for (int i = 0; i <= n_acc && L + i < a.cap; ++i) a.ids[(size_t)s * a.cap + L + i] = tok[i];
     a.len[s] = L + n_acc + 1 > a.cap ? a.cap : L + n_acc + 1;
+    return n_acc + 1;
+}
+
+__global__ void __launch_bounds__(64) k_spec_accept_rows(const SpecRowsArgs a) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.B) return;
+    int r0;
+    spec_accept_seq(a, s, r0);
+}
+
+// ---------------------------------------------------------------- the segmented verify under per-seat tails
+// pie_spec_verify_rows_sampled's workspace: the tail's partials of every row | the rows' tokens | one pie_row_tail and one pie_xtc per ROW
+// (the seats' records expanded over their segments) | pie_sample_rows' workspace (the part that has to be zeroed once).
+struct SpecRowsSampledLayout {
+    size_t tok, table, xtc, smp, bytes;
+    SpecRowsSampledLayout(int n_rows, int V) {
+        tok = sizeof(LogitStat) * TAIL_STAT_TILES * (size_t)n_rows;
+        table = align16(tok + sizeof(int) * (size_t)n_rows);
+        xtc = table + sizeof(pie_row_tail) * (size_t)n_rows;
+        smp = align16(xtc + sizeof(pie_xtc) * (size_t)n_rows);
+        bytes = smp + pie_sample_workspace_bytes(n_rows, V);
+    }
+};
+
+struct SpecSeatsArgs {  // what the seats own (all device memory): record, ring, bias entries and XTC record s belong to segment s
+    u16 *logits;
+    int N, B, V;
+    const int *seg_first, *fed;
+    const int *pos0;     // [B]: the position of segment s's first row, or nullptr: ...
+    const int *row_ctx;  // ... [N], the decoder's row_context_lens: pos0[s] = row_ctx[first row of s] - 1
+    pie_row_tail *table;
+    int *recent;
+    const int *bias_ids;  // nullptr: no bias part
+    const float *bias_vals;
+    const int *bias_n;
+    int bias_cap;
+    const pie_xtc *xtc;  // nullptr: off
+    pie_row_tail *table_rows;  // [N], the workspace's
+    pie_xtc *xtc_rows;
+    unsigned long long *smp_ws;
+    size_t smp_row_words;
+};
+
+__device__ __forceinline__ int spec_seat_pos0(const SpecSeatsArgs &a, int s, int r0) { return a.pos0 ? a.pos0[s] : a.row_ctx[r0] - 1; }
+
+// Segment window: this thread's entry of the positions max(0, pos + 1 - context) .. pos of row j of a segment that starts at pos0, pos =
+// pos0 + j, -1 beyond them: the seat's ring below pos0, the pass's own inputs fed[0 .. j] from pos0 on.  NOTHING is recorded here, unlike
+// ring_window_id: slot (pos0 + j) & 1023 still holds position pos0 + j - 1024, which lies inside row 0's window whenever context_size >=
+// 1025 - j, so a row that stored its own input would race with its segment's earlier rows, which run in other workgroups.  The commit
+// launch, behind every draw, is the ring's one writer.
+__device__ __forceinline__ int seg_window_id(const int *ring, const int *fed, int context, int pos0, int j) {
+    const int t = threadIdx.x, pos = pos0 + j;
+    context = context < 1 ? 1 : (context > PEN_MAX_IDS ? PEN_MAX_IDS : context);
+    const int lo = pos + 1 - context > 0 ? pos + 1 - context : 0, n = pos + 1 - lo, p = lo + t;  // 1 <= n <= context
+    if (t >= n) return -1;
+    return p < pos0 ? ring[p & (PEN_MAX_IDS - 1)] : fed[p - pos0];  // p - pos0 <= j
+}
+
+// Workgroup (j, s) is row j of segment s: the seat's repetition penalty over the row's own window, then the seat's bias entries
+// (tail.hpp's phases).  Every exit and every skipped phase is block-uniform: a launch argument, or a value every thread reads from one
+// address that no launch of this sequence has written yet.
+template <class T>
+__global__ void __launch_bounds__(PEN_MAX_IDS) k_spec_edit_seg_rows(const SpecSeatsArgs a) {
+    __shared__ alignas(8) int s_ids[PEN_MAX_IDS];
+    const int j = blockIdx.x, s = blockIdx.y;
+    int r0;
+    if (j >= spec_segment(a.seg_first, s, a.N, r0)) return;
+    const int pos0 = spec_seat_pos0(a, s, r0);
+    if (pos0 < 0) return;
+    u16 *logits = a.logits + (size_t)(r0 + j) * a.V;
+    const float penalty = a.table[s].penalty;
+    if (penalty != 1.0f)
+        penalise_phase<T>(logits, a.V, penalty, seg_window_id(a.recent + (size_t)s * PEN_MAX_IDS, a.fed + r0, a.table[s].context_size, pos0, j), s_ids);
+    if (!a.bias_ids) return;
+    const int n = a.bias_n[s];
+    bias_phase<T>(logits, a.V, a.bias_ids, a.bias_vals, n < 0 ? 0 : (n > a.bias_cap ? a.bias_cap : n), (size_t)s * a.bias_cap, s_ids);
+}
+
+// Thread j of workgroup s: row j of segment s draws as the seat's one-row call number calls_s + j -- the position a plain loop's draw
+// number j from here would have -- with no penalty of its own (the edit launch applied the seat's).  The sampler advances the ROW's calls,
+// in the workspace; the seat's record is read only until the commit launch.  The workspace header's two words: as k_spec_fill_rows.
+__global__ void __launch_bounds__(64) k_spec_fill_seg_rows(const SpecSeatsArgs a) {
+    const int j = threadIdx.x, s = blockIdx.x;
+    int r0;
+    if (j >= spec_segment(a.seg_first, s, a.N, r0)) return;
+    pie_row_tail t = a.table[s];
+    t.calls += (unsigned long long)j, t.penalty = 1.0f, t.context_size = 1;
+    a.table_rows[r0 + j] = t;
+    if (a.xtc) a.xtc_rows[r0 + j] = a.xtc[s];
+    unsigned long long *hdr = a.smp_ws + (size_t)(r0 + j) * a.smp_row_words;
+    hdr[SMP_WS_MAXKEY_WORD] = 0ull, hdr[SMP_WS_XTC_WORD] = 0ull;
+}
+
+// Thread s is sequence s, behind every draw: k_spec_accept_rows' part over the drawn tokens, then the seat's state moves by the n tokens
+// the pass chose -- calls for a seat that draws (a greedy seat's record is not written), and the ring's slots of the n positions the pass
+// has fed for good: its fed token and the n - 1 accepted drafts.  No other slot is written.
+__global__ void __launch_bounds__(64) k_spec_commit_rows(const SpecRowsArgs a, const SpecSeatsArgs q) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.B) return;
+    int r0;
+    const int n = spec_accept_seq(a, s, r0);
+    if (n == 0) return;
+    const int pos0 = spec_seat_pos0(q, s, r0);
+    if (pos0 < 0) return;
+    if (sample_mode_draws(q.table[s].mode)) q.table[s].calls += (unsigned long long)n;
+    for (int i = 0; i < n; ++i) q.recent[(size_t)s * PEN_MAX_IDS + ((pos0 + i) & (PEN_MAX_IDS - 1))] = q.fed[r0 + i];
 }
 
 // ---------------------------------------------------------------- the verify under a sampler
@@ -450,6 +569,37 @@ int spec_verify_rows_launch(const u16 *logits, int N, int V, int dtype, const in
         hipLaunchKernelGGL(k_spec_merge, dim3((unsigned)N), dim3(256), 0, st, (const LogitStat *)stats, tok, lse);
         hipLaunchKernelGGL(k_spec_accept_rows, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, a);
     });
+}
+
+size_t spec_verify_rows_sampled_workspace_bytes(int n_rows, int V) {
+    return n_rows < 1 || n_rows > 65535 || pie_sample_workspace_bytes(n_rows, V) == 0 ? 0 : SpecRowsSampledLayout(n_rows, V).bytes;
+}
+
+// pie_spec_verify_rows_sampled's launches (arguments already checked): the edit over (8, B), the tail's two over every row, the records
+// (a fill of the rows' table with the greedy mode first: a row no segment covers draws nothing), pie_sample_rows' and the commit.
+int spec_verify_rows_sampled_launch(const SpecSeats &q, u16 *logits, int N, int V, int dtype, const int *seg_first, int B, const int *fed, const int *draft,
+                                    int draft_stride, int *out_tokens, int *out_n, float *logprobs, int *ids, int *len, int cap, void *workspace, hipStream_t st) {
+    const SpecRowsSampledLayout lay(N, V);
+    char *ws = (char *)workspace;
+    int *tok = (int *)(ws + lay.tok);
+    SpecSeatsArgs a = {};
+    a.logits = logits, a.N = N, a.B = B, a.V = V, a.seg_first = seg_first, a.fed = fed, a.pos0 = q.pos0, a.row_ctx = q.row_ctx;
+    a.table = q.table, a.recent = q.recent, a.bias_ids = q.bias_ids, a.bias_vals = q.bias_vals, a.bias_n = q.bias_n, a.bias_cap = q.bias_cap, a.xtc = q.xtc;
+    a.table_rows = (pie_row_tail *)(ws + lay.table), a.xtc_rows = (pie_xtc *)(ws + lay.xtc);
+    a.smp_ws = (unsigned long long *)(ws + lay.smp), a.smp_row_words = pie_sample_workspace_bytes(1, V) / sizeof(unsigned long long);
+    if (int rc = launch_for_dtype(dtype, "spec verify rows sampled:", [&](auto t) {
+            hipLaunchKernelGGL(k_spec_edit_seg_rows<decltype(t)>, dim3(SPEC_SEG_ROWS, (unsigned)B), dim3(PEN_MAX_IDS), 0, st, a);
+        }))
+        return rc;
+    if (int rc = logits_tail_rows_launch(dtype, logits, V, N, (LogitStat *)ws, logprobs, tok, st)) return rc;
+    PIE_HIP_TRY(hipMemsetAsync(a.table_rows, 0xFF, sizeof(pie_row_tail) * (size_t)N, st));  // mode = PIE_SAMPLE_GREEDY in every record
+    hipLaunchKernelGGL(k_spec_fill_seg_rows, dim3((unsigned)B), dim3(64), 0, st, a);
+    PIE_LAUNCH_CHECK();
+    if (int rc = sample_rows_launch(logprobs, N, V, a.table_rows, ws + lay.smp, tok, nullptr, nullptr, st, SampleXtc{q.xtc ? a.xtc_rows : nullptr, nullptr})) return rc;
+    const SpecRowsArgs r = {N, B, V, seg_first, draft, draft_stride, tok, out_tokens, out_n, ids, len, cap};
+    hipLaunchKernelGGL(k_spec_commit_rows, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, r, a);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
 }
 
 namespace {
@@ -803,6 +953,32 @@ int pie_spec_verify_rows(const void *logits, int n_rows, int V, int dtype, const
     PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, "pie_spec_verify_rows: workspace needs 16-byte alignment");
     return spec_verify_rows_launch((const u16 *)logits, n_rows, V, dtype, seg_first, B, draft_ids, draft_stride, out_tokens, out_n, ids, len, cap, workspace,
                                    (hipStream_t)stream);
+}
+
+size_t pie_spec_verify_rows_sampled_workspace_bytes(int n_rows, int V) { return spec_verify_rows_sampled_workspace_bytes(n_rows, V); }
+
+int pie_spec_verify_rows_sampled(void *logits, int n_rows, int V, int dtype, const int32_t *seg_first, int B, const int32_t *fed, const int32_t *draft_ids,
+                                 int draft_stride, const int32_t *pos0, pie_row_tail *table, int32_t *recent_ids, const int32_t *bias_ids, const float *bias_vals,
+                                 const int32_t *bias_n, int bias_cap, const pie_xtc *xtc, int32_t *out_tokens, int32_t *out_n, float *logprobs, int32_t *ids,
+                                 int32_t *len, int cap, void *workspace, void *stream) {
+    const std::string who = "pie_spec_verify_rows_sampled: ";
+    PIE_REQUIRE(logits && seg_first && fed && draft_ids && pos0 && table && recent_ids && out_tokens && out_n && logprobs && workspace, PIE_E_ARG, who + "null pointer");
+    PIE_REQUIRE((ids == nullptr) == (len == nullptr) && (ids || cap == 0) && (!ids || cap >= 1), PIE_E_ARG, who + "ids [B, cap >= 1] and len come together or not at all");
+    PIE_REQUIRE(bias_ids ? (bias_vals && bias_n && bias_cap >= 1 && bias_cap <= PEN_MAX_IDS) : (!bias_vals && !bias_n && bias_cap == 0), PIE_E_ARG,
+                who + "bias_ids, bias_vals [B, 1 <= bias_cap <= 1024] and bias_n come together or not at all");
+    PIE_REQUIRE(dtype == PIE_BF16 || dtype == PIE_F16, PIE_E_ARG, who + "dtype must be PIE_BF16 or PIE_F16");
+    PIE_REQUIRE(n_rows >= 1 && n_rows <= 65535 && B >= 1 && B <= SPEC_MAX_SEQS && draft_stride >= 1 && pie_sample_workspace_bytes(n_rows, V) != 0, PIE_E_SHAPE,
+                who + "need 1 <= n_rows <= 65535, 1 <= V <= 524288, 1 <= B <= 4096 and draft_stride >= 1");
+    PIE_REQUIRE(pie_aligned(logits, 2) && pie_aligned(seg_first, 4) && pie_aligned(fed, 4) && pie_aligned(draft_ids, 4) && pie_aligned(pos0, 4) && pie_aligned(recent_ids, 4) &&
+                    pie_aligned(bias_ids, 4) && pie_aligned(bias_vals, 4) && pie_aligned(bias_n, 4) && pie_aligned(xtc, 4) && pie_aligned(out_tokens, 4) &&
+                    pie_aligned(out_n, 4) && pie_aligned(logprobs, 4) && pie_aligned(ids, 4) && pie_aligned(len, 4),
+                PIE_E_ALIGN, who + "logits need 2-byte, the index arrays, the seats' state and the outputs 4-byte alignment");
+    PIE_REQUIRE(pie_aligned(table, 8), PIE_E_ALIGN, who + "the table needs 8-byte alignment");
+    PIE_REQUIRE(pie_aligned(workspace, 16), PIE_E_ALIGN, who + "workspace needs 16-byte alignment");
+    SpecSeats q;
+    q.table = table, q.recent = recent_ids, q.pos0 = pos0, q.bias_ids = bias_ids, q.bias_vals = bias_vals, q.bias_n = bias_n, q.bias_cap = bias_cap, q.xtc = xtc;
+    return spec_verify_rows_sampled_launch(q, (u16 *)logits, n_rows, V, dtype, seg_first, B, fed, draft_ids, draft_stride, out_tokens, out_n, logprobs, ids, len, cap,
+                                           workspace, (hipStream_t)stream);
 }
 
 size_t pie_spec_verify_sampled_workspace_bytes(int rows, int V) {

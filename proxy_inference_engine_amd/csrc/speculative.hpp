@@ -41,5 +41,22 @@ int spec_verify_launch(const u16 *logits, int rows, int V, int dtype, const int 
 size_t spec_verify_rows_workspace_bytes(int n_rows);
 int spec_verify_rows_launch(const u16 *logits, int N, int V, int dtype, const int *seg_first, int B, const int *draft, int draft_stride, int *out_tokens,
                             int *out_n, int *ids, int *len, int cap, void *workspace, hipStream_t st);
+// The batched pass under per-seat tails (pie_decoder_spec_step_batch_tail in prefill.hip).  What the seats own, all device
+// memory: record, ring, bias entries and XTC record s belong to segment s.  Exactly one of pos0 [B] (the op) and row_ctx [N] (the decoder's
+// row_context_lens: segment s starts at position row_ctx[its first row] - 1) is given; the bias part and xtc are nullable.
+struct SpecSeats {
+    pie_row_tail *table = nullptr;
+    int *recent = nullptr;
+    const int *pos0 = nullptr, *row_ctx = nullptr;
+    const int *bias_ids = nullptr;
+    const float *bias_vals = nullptr;
+    const int *bias_n = nullptr;
+    int bias_cap = 0;
+    const pie_xtc *xtc = nullptr;
+};
+size_t spec_verify_rows_sampled_workspace_bytes(int n_rows, int V);
+// pie_spec_verify_rows_sampled's launches (arguments already checked); logits are edited in place, logprobs [N, V] are required
+int spec_verify_rows_sampled_launch(const SpecSeats &q, u16 *logits, int N, int V, int dtype, const int *seg_first, int B, const int *fed, const int *draft,
+                                    int draft_stride, int *out_tokens, int *out_n, float *logprobs, int *ids, int *len, int cap, void *workspace, hipStream_t st);
 // fed [N] = the pass's input ids: every segment's fed token (tokens [B]), then its drafts
 int spec_gather_rows_launch(const int *tokens, const int *draft, int draft_stride, const int *seg_first, int B, int N, int vocab, int *fed, hipStream_t st);

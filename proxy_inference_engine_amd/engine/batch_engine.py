@@ -46,7 +46,11 @@ class SamplingParams:
     xtc_special_tokens: up to 16 ids XTC never removes, None: the engine's stop tokens.  A greedy request (temp == 0) ignores XTC.
     token_automaton: a logits_processors.TokenAutomaton -- a grammar compiled ahead of time, where token_mask stands and
     exclusive with it: the request's row derives its mask from the automaton's state inside the passes and advances the state by the token
-    it drew (Model.set_batch_automata), so no callable runs for it on the host."""
+    it drew (Model.set_batch_automata), so no callable runs for it on the host.
+    Under BatchedEngine(speculative=...) a request's parameters must be plain, unless the engine was built with
+    SpeculativeParams(batch_tail=True): then temp, top_p, top_k, min_p, min_tokens_to_keep, seed, XTC, repetition_penalty
+    and logit_bias also run inside the speculative passes, per seat; token_mask, token_automaton, frequency_penalty / presence_penalty
+    and DRY stay refused there."""
     temp: float = 0.0
     top_p: float = 1.0
     top_k: int = -1
@@ -269,10 +273,11 @@ def per_prompt_counts(value, n_prompts: int, name: str, optional: bool = False) 
     return wants
 
 
-def request_kinds(model, n_prompts: int, sampling, top_logprobs, stop_tokens, host_sampler: bool) -> dict:
+def request_kinds(model, n_prompts: int, sampling, top_logprobs, stop_tokens, host_sampler: bool, always_tails: bool = False) -> dict:
     """What one generate() call asks of the passes' per-row state, as _RowSeats' keyword arguments: every request's arguments are checked
     here, before anything runs (ValueError), and a kind is None -- neither armed nor written -- unless some request asks for it.
-    sampling: generate's; top_logprobs: generate's, None without logprobs=True."""
+    sampling: generate's; top_logprobs: generate's, None without logprobs=True.  always_tails (batched speculation under batch_tail): a
+    given `sampling` arms the batch tail whatever it holds -- the speculative pass applies a bias or draws under XTC through the tail."""
     kinds = dict.fromkeys(("tails", "edits", "cnts", "tops", "drys", "xtcs", "autos"))
     if top_logprobs is not None:
         if host_sampler:
@@ -299,7 +304,7 @@ def request_kinds(model, n_prompts: int, sampling, top_logprobs, stop_tokens, ho
     drys = [sp.dry() for sp in params]                    # (checked for every request, armed or not: as XTC is below)
     kinds["drys"] = asked([d if sp.dried else None for sp, d in zip(params, drys)])
     kinds["xtcs"] = asked([sp.xtc(stop_tokens) for sp in params])
-    if not all(sp.recordless for sp in params):           # a request with only a mask, a bias or count penalties arms no batch tail
+    if always_tails or not all(sp.recordless for sp in params):   # a request with only a mask, a bias or count penalties arms no batch tail
         kinds["tails"] = (params, seeds)
     return kinds
 
@@ -542,6 +547,14 @@ class _RowSeats:
         if self.xtcs is not None:  # a row's XTC record moves with its sampler record
             self.model.write_batch_xtc(idx, [None if want[s_] is None else self.xtcs[want[s_][0]] for s_ in idx])
 
+    def moved(self, n: list) -> None:
+        """Behind a speculative pass under the seats' tails that chose n[s] tokens for seat s: the device moved the seat's
+        `calls` and ring by n[s] itself, so what the table's row holds moves with it -- the same request n[s] tokens further on, which the
+        next `seat` finds in place and does not rewrite.  A seat whose occupant then changes is rewritten from the host's state, as ever."""
+        for s, k in enumerate(n):
+            if self.slots[s] is not None:
+                self.slots[s] = (self.slots[s][0], self.slots[s][1] + k)
+
     def lone_step(self, idx) -> bool:
         """A lone prompt takes the single-sequence prompt pass (greedy tail) unless its request has a record, a mask or a bias of its
         own, or wants log-probabilities: then it is a batch of one.  Frequency / presence penalties alone do not make it one: a request's
@@ -573,7 +586,12 @@ class BatchedEngine:
         row before it; an iteration in which no sequence has a draft is the replayed step as ever, and an iteration that carries prompt
         rows runs without drafts.  The tokens are greedy decoding's; `spec_stats` counts the passes.  None: today's engine exactly.
         ValueError, by name: a `sampler`, kv_dtype=torch.int8, a tensor-parallel model, num_draft > 7, draft_model, grammar and
-        configured_tail; generate() then refuses any request whose SamplingParams is not plain, logprobs, top_logprobs and prompt_logprobs."""
+        configured_tail; generate() then refuses any request whose SamplingParams is not plain, logprobs, top_logprobs and prompt_logprobs.
+        SpeculativeParams(batch_tail=True): generate() also admits requests whose SamplingParams set temp, top_p, top_k,
+        min_p, min_tokens_to_keep, seed, XTC, repetition_penalty and logit_bias -- with `sampling` given the pass is
+        Model.spec_step_batch_tail, which applies every seat's own record, ring, bias table and XTC record to the rows of its segment and
+        accepts a draft while it equals the row's draw: the tokens are those the plain passes draw.  Still refused by name: a token mask,
+        a token automaton, frequency / presence penalties, DRY, logprobs, top_logprobs and prompt_logprobs."""
         if speculative is not None:
             who = "BatchedEngine(speculative=...): "
             for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8, "kv_dtype=torch.int8 (int8 KV pages)"),
@@ -627,12 +645,23 @@ class BatchedEngine:
         for none, else a list as long as prompt i: entry 0 None, entry j the {id: log-probability} map of prompt token j given the tokens
         before it, under the raw model distribution: the best prompt_logprobs pairs, then the token itself when absent
         (InferenceEngine.score's list).  Scored inside the prompt passes (Model.set_prompt_logprobs), across prefill_chunk
-        boundaries, and fetched in the per-pass read-back of the tokens.  ValueError with share_prefix=True (the shared pages' rows are
+        boundaries, and fetched in the per-pass read-back of the tokens.
+        With speculative= set on the engine: `sampling` must be plain and logprobs, top_logprobs and prompt_logprobs are refused; under
+        SpeculativeParams(batch_tail=True) `sampling` may set a sampler, XTC, a repetition penalty and a logit_bias -- the
+        tokens are then the ones the plain passes draw, token j of a request being draw j of its seed from its own row -- and a token
+        mask, a token automaton, frequency / presence penalties and DRY are refused by name.  ValueError with share_prefix=True (the shared pages' rows are
         computed once, for no request in particular, and cannot be scored) and with max_new_tokens < 1 (InferenceEngine.score runs a prompt only)."""
         if self.speculative is not None:
             who = "generate: batched speculation is greedy and raw -- not available with "
             params = [] if sampling is None else [sampling] if isinstance(sampling, SamplingParams) else list(sampling)
-            if any(not (isinstance(sp, SamplingParams) and sp.plain) for sp in params):
+            if self.speculative.batch_tail:
+                who = "generate: batched speculation under batch_tail -- not available with "
+                for sp in (sp for sp in params if isinstance(sp, SamplingParams)):
+                    for bad, name in ((sp.token_mask is not None, "a token mask"), (sp.token_automaton is not None, "a token automaton"),
+                                      (sp.counted, "frequency / presence penalties"), (sp.dried, "a DRY penalty")):
+                        if bad:
+                            raise ValueError(who + name)
+            elif any(not (isinstance(sp, SamplingParams) and sp.plain) for sp in params):
                 raise ValueError(who + "a request whose `sampling` is not plain (a sampler, penalty, mask, bias or automaton)")
             if logprobs:
                 raise ValueError(who + "`logprobs`")
@@ -661,7 +690,8 @@ class BatchedEngine:
 
     def _run(self, prompts, max_new_tokens, sampling, logprobs, top_logprobs, scores):
         """generate's body; scores: the call's _PromptScores or None."""
-        kinds = request_kinds(self.model, len(prompts), sampling, top_logprobs if logprobs else None, self.stop_tokens, self.sampler is not None)
+        kinds = request_kinds(self.model, len(prompts), sampling, top_logprobs if logprobs else None, self.stop_tokens, self.sampler is not None,
+                              always_tails=self.speculative is not None and self.speculative.batch_tail)
         if max_new_tokens < 1:
             return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs else [[] for _ in prompts]
         with _RowSeats(self.model, self.max_batch, prompts, **kinds) as seats:
@@ -715,7 +745,9 @@ class BatchedEngine:
     def _spec_decode(self, spec: _SpecSeats, seats: _RowSeats, scores, P: int, active: list) -> None:
         """An iteration of decode rows only under batched speculation: the seats' ids are brought up to date, every row
         gets its drafts (spec_plan), and the iteration is ONE speculative pass -- or, where no row has a draft, the replayed step untouched,
-        its tokens appended to the seats' ids on the device.  Either way the next drafter launch is queued behind it."""
+        its tokens appended to the seats' ids on the device.  Either way the next drafter launch is queued behind it.  The pass is the
+        greedy and raw one, or -- where the seats hold a batch tail -- the one under the seats' tails, behind which the
+        seats' bookkeeping moves by what the device moved."""
         spec.sync(active)
         m = spec.plan(active)
         if not any(m):
@@ -725,8 +757,11 @@ class BatchedEngine:
             return
         seats.seat([a.request for a in active], active)
         sp = self.speculative
-        n, toks, nxt = self.model.spec_step_batch(torch.cat([a.token for a in active]), [a.cache for a in active], spec.drafts, m, spec.ids, spec.len,
-                                                  then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts))
+        entry = self.model.spec_step_batch if seats.tails is None else self.model.spec_step_batch_tail   # (a tail: `sampling` was given under batch_tail)
+        n, toks, nxt = entry(torch.cat([a.token for a in active]), [a.cache for a in active], spec.drafts, m, spec.ids, spec.len,
+                             then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts))
+        if seats.tails is not None:
+            seats.moved(n)
         spec.moved(active, n)
         spec.host_counts[:len(active)] = nxt
         last = torch.tensor([t[-1] for t in toks], dtype=torch.int32, device=self.model.device)   # (the record is on the host already: one small upload)

@@ -11,7 +11,7 @@ Array type: torch.Tensor on the ROCm device instead of mx.array.
 from __future__ import annotations
 
 from collections.abc import Callable, Generator, Iterator
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from functools import partial
 
 import torch
@@ -133,6 +133,11 @@ class SpeculativeParams:
     j's own distribution.  (A pass's rows come from the many-row GEMMs and a step's from the GEMVs, so their logits may differ in the last
     bit, as in the greedy case: the plain loop draws the same tokens wherever no draw falls within that rounding of a boundary.)  A greedy
     request without processors takes the greedy path either way.
+    batch_tail: configured_tail's analogue for BatchedEngine(speculative=...), which refuses configured_tail itself.  True --
+    generate() admits requests whose SamplingParams set a sampler (temp, top_p, top_k, min_p, min_tokens_to_keep, seed, XTC), a
+    repetition penalty and a logit_bias: every seat's record, ring, bias table and XTC record are applied to the 1 + m_s rows of its
+    segment inside the one pass (Model.spec_step_batch_tail), by the same point-mass rule.  A token mask, a token automaton, frequency /
+    presence penalties, DRY and log-probabilities stay refused there.  InferenceEngine refuses batch_tail=True by name.
     draft_model: None -- prompt-lookup drafts, as above.  A built `Model` of the target's vocabulary, or a checkpoint
     path (loaded once and kept on the engine) -- every round the draft model runs num_draft of its own replayed steps (num_draft =
     the target's spec_min_rows - 1 .. 31, so that the pass keeps its many-row form) and the target verifies them in one pass.  A greedy
@@ -153,6 +158,7 @@ class SpeculativeParams:
     ngram_min: int = 1
     min_draft: int = 5
     configured_tail: bool = False
+    batch_tail: bool = field(default=False, kw_only=True)   # (keyword-only: the positional order of the fields around it stays as it was)
     draft_model: object = None
     grammar: bool = False
 
@@ -171,6 +177,8 @@ class SpeculativeParams:
             raise ValueError("SpeculativeParams: configured_tail is a bool")
         if not isinstance(self.grammar, bool):
             raise ValueError("SpeculativeParams: grammar is a bool")
+        if not isinstance(self.batch_tail, bool):
+            raise ValueError("SpeculativeParams: batch_tail is a bool")
         if self.grammar and self.draft_model is not None:
             raise ValueError("SpeculativeParams: grammar is not available with a draft model")
 
@@ -295,6 +303,8 @@ def _forced_ids(automaton, state: int, draft: list[int]) -> int:
 def _check_generate_args(model, pixel_values, mask, kv_bits, kv_group_size, max_kv_size, top_logprobs, prompt_logprobs, speculative) -> None:
     """What generate_step refuses in its arguments, before it touches the prompt cache or the model."""
     scored = prompt_logprobs is not None
+    if speculative is not None and getattr(speculative, "batch_tail", False):
+        raise ValueError("speculative decoding is not available with batch_tail (BatchedEngine's passes; the single sequence's is configured_tail)")
     if speculative is not None and scored:
         raise ValueError("speculative decoding is not available with prompt_logprobs")
     if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:

@@ -1642,3 +1642,78 @@ def spec_verify_rows(logits: torch.Tensor, seg_first: torch.Tensor, drafts: torc
     _ffi.check(lib.pie_spec_verify_rows(_ffi.p(logits), N, V, _ffi.dtype_code(logits.dtype), _ffi.p(seg_first), B, _ffi.p(drafts), drafts.shape[1], _ffi.p(tokens),
                                         _ffi.p(n), _ffi.p(ids), _ffi.p(lengths), cap, _ffi.p(workspace), _ffi.stream()))
     return tokens, n
+
+
+def spec_verify_rows_sampled_workspace(device, n_rows: int, V: int) -> torch.Tensor:
+    """pie_spec_verify_rows_sampled's workspace for a [n_rows, V] block on `device`: zeroed once, reusable from call to call."""
+    nbytes = int(_ffi.load().pie_spec_verify_rows_sampled_workspace_bytes(int(n_rows), int(V)))
+    if nbytes == 0:
+        raise ValueError(f"spec_verify_rows_sampled: a [n_rows, V] block with 1 <= n_rows <= 65535 and 1 <= V <= 524288, got [{n_rows}, {V}]")
+    return torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+
+
+def spec_verify_rows_sampled(logits: torch.Tensor, seg_first: torch.Tensor, fed: torch.Tensor, drafts: torch.Tensor, pos0: torch.Tensor, table: torch.Tensor,
+                             recent_ids: torch.Tensor, bias: tuple | None = None, xtc: torch.Tensor | None = None, ids: torch.Tensor | None = None,
+                             lengths: torch.Tensor | None = None, workspace: torch.Tensor | None = None, out: tuple | None = None):
+    """The segmented verify of a batched speculative pass under per-seat tails (pie_spec_verify_rows_sampled): logits bf16 /
+    f16 [N, V], EDITED IN PLACE; seg_first int32 [B + 1] and drafts int32 [B, width >= 1] as spec_verify_rows takes them; fed int32 [N] =
+    the rows' input ids (a segment's fed token, then its drafts); pos0 int32 [B] = the position of every segment's first row; table (row_tail_table)
+    [>= B] and recent_ids int32 [>= B, 1024] = the seats' records and rings, seat s = segment s; bias = (ids int32 [>= B, cap], values fp32
+    [>= B, cap], n int32 [>= B]) as logits_bias_rows takes them, or None; xtc = int32 [>= B, XTC_WORDS] device records or None.
+    Row j of segment s, at position pos0[s] + j: the seat's repetition penalty over the row's own window (the ring below pos0[s], fed
+    from it on), the seat's bias, log-softmax and argmax, and the draw a one-row sample makes with the seat's sampler at stream position
+    calls_s + j; the drafts are accepted while each equals the draw of the row before it.  Returns (tokens int32 [B, 8], n int32 [B],
+    logprobs fp32 [N, V]), no host sync; afterwards a drawing seat's calls has advanced by n[s] and its ring holds the n[s] ids the pass fed
+    for good, on the device.  ids / lengths as in spec_verify_rows.  workspace: spec_verify_rows_sampled_workspace's (zeroed once)."""
+    who = "spec_verify_rows_sampled"
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError(f"{who}: contiguous bf16 / f16 [N, V] logits")
+    N, V = logits.shape
+    _int32_dev(seg_first, None, who, "seg_first"), _int32_dev(drafts, None, who, "drafts"), _int32_dev(fed, N, who, "fed")
+    B = seg_first.numel() - 1
+    if B < 1 or drafts.dim() != 2 or drafts.shape[0] != B or drafts.shape[1] < 1:
+        raise ValueError(f"{who}: seg_first [B + 1] and drafts [B, >= 1]")
+    _int32_dev(pos0, B, who, "pos0"), _int32_dev(recent_ids, None, who, "recent_ids")
+    _table(table, B, who)
+    if recent_ids.dim() != 2 or recent_ids.shape[1] != RECENT_IDS or recent_ids.shape[0] < B:
+        raise ValueError(f"{who}: recent_ids is [>= B, {RECENT_IDS}]")
+    b_ids = b_vals = b_n = None
+    b_cap = 0
+    if bias is not None:
+        b_ids, b_vals, b_n = bias
+        _dev(b_ids), _dev(b_vals), _dev(b_n)
+        if b_ids.dtype != torch.int32 or b_vals.dtype != torch.float32 or b_n.dtype != torch.int32 or b_ids.dim() != 2 or b_ids.shape != b_vals.shape or \
+                not (b_ids.is_contiguous() and b_vals.is_contiguous() and b_n.is_contiguous()) or b_ids.shape[0] < B or b_n.numel() < B or not 1 <= b_ids.shape[1] <= 1024:
+            raise ValueError(f"{who}: bias is (int32 ids, float32 values [>= B, 1 <= cap <= 1024], int32 n [>= B]), contiguous")
+        b_cap = b_ids.shape[1]
+    rec = None if xtc is None else _xtc(xtc, B, logits.device, who)
+    if (ids is None) != (lengths is None):
+        raise ValueError(f"{who}: ids and lengths come together")
+    cap = 0
+    if ids is not None:
+        _int32_dev(ids, None, who, "ids"), _int32_dev(lengths, B, who, "lengths")
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
+            raise ValueError(f"{who}: ids is [B, cap]")
+        cap = ids.shape[1]
+    lib = _ffi.load()
+    need = int(lib.pie_spec_verify_rows_sampled_workspace_bytes(N, V))
+    if need == 0:
+        raise ValueError(f"{who}: a [N, V] block with 1 <= N <= 65535 and 1 <= V <= 524288, got [{N}, {V}]")
+    if workspace is None:
+        workspace = spec_verify_rows_sampled_workspace(logits.device, N, V)
+    _dev(workspace)
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"{who}: the workspace is spec_verify_rows_sampled_workspace()'s size")
+    if out is None:
+        out = (torch.empty((B, SPEC_SEG_ROWS), dtype=torch.int32, device=logits.device), torch.empty(B, dtype=torch.int32, device=logits.device),
+               torch.empty((N, V), dtype=torch.float32, device=logits.device))
+    tokens, n, logprobs = out
+    _int32_dev(tokens, B * SPEC_SEG_ROWS, who, "out[0]"), _int32_dev(n, B, who, "out[1]")
+    _dev(logprobs)
+    if logprobs.dtype != torch.float32 or not logprobs.is_contiguous() or logprobs.numel() < N * V:
+        raise ValueError(f"{who}: out[2] is a contiguous fp32 [N, V] device tensor")
+    _ffi.check(lib.pie_spec_verify_rows_sampled(_ffi.p(logits), N, V, _ffi.dtype_code(logits.dtype), _ffi.p(seg_first), B, _ffi.p(fed), _ffi.p(drafts), drafts.shape[1],
+                                                _ffi.p(pos0), _ffi.p(table), _ffi.p(recent_ids), _ffi.p(b_ids), _ffi.p(b_vals), _ffi.p(b_n), b_cap, _ffi.p(rec),
+                                                _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs), _ffi.p(ids), _ffi.p(lengths), cap, _ffi.p(workspace), _ffi.stream()))
+    return tokens, n, logprobs

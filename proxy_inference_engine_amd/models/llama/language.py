@@ -299,6 +299,7 @@ class Model(RowsTailState, StepTailState):
         self._batch_bufs: dict = {}
         self._spec = None   # speculative decoding's record and workspaces, made when first used
         self._spec_batch_ws = None   # the batched speculative pass's workspace, made when first used
+        self._spec_batch_tail_ws = None   # ... and the one of the pass under the seats' tails, zeroed when made
         self.spec_batch_last = None  # ... and its last record on the device
         self._init_rows_state()  # the multi-sequence passes' per-row tail state (rows_state.py)
         self._init_step_state()  # the single-sequence step's tail state (step_state.py)
@@ -724,8 +725,25 @@ class Model(RowsTailState, StepTailState):
         drafts_out): hip_ops.ngram_draft_rows over those rows is queued behind the pass, before the host reads anything, into drafts_out
         [B, k], and next_counts are its counts, read back with the pass's one record.  Greedy and raw: int8 pages, tensor-parallel models
         and any armed per-row state of the multi-sequence passes are refused by name."""
+        return self._spec_batch_pass("spec_step_batch", False, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft)
+
+    def spec_step_batch_tail(self, tokens: torch.Tensor, caches: list[list[BaseCache]], drafts: torch.Tensor, counts, seq_ids: torch.Tensor | None = None,
+                             seq_len: torch.Tensor | None = None, then_draft: tuple | None = None):
+        """spec_step_batch under the sequences' own samplers, repetition penalties and logit biases (pie_decoder_spec_step_batch_tail;
+        DESIGN.md 25): the same arguments and returns.  Needs set_batch_tail armed; record, ring, bias table (set_batch_edits' bias part)
+        and XTC record (set_batch_xtc) s belong to sequence s, as in step_batch.  Row j of sequence s is edited with its seat's penalty over
+        its own window and its seat's bias and drawn with the draw a plain step would make at the seat's stream position calls + j; a draft
+        is accepted while it equals the draw, so tokens[s] are the n[s] tokens that many step_batch calls would have produced.  Afterwards
+        the seat's `calls` and ring stand where those steps would have left them, on the device.  `spec_batch_last` additionally holds
+        "logprobs" fp32 [N, V] (every row's processed log-probabilities), "logits" [N, V] (the processed block, a view of the workspace,
+        valid until the next pass) and "seg_first" int32 [B + 1].  Refused by name, before anything moves: int8 pages, tensor-parallel
+        models, a mask part of the batch edits, batch token automata, a batch count penalty, a batch DRY penalty, batch top log-probabilities
+        and prompt scoring."""
+        return self._spec_batch_pass("spec_step_batch_tail", True, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft)
+
+    def _spec_batch_pass(self, who: str, tail: bool, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft):
+        """spec_step_batch's and spec_step_batch_tail's body: the refusals, the index arrays, the entry's call and the one read-back."""
         import numpy as np
-        who = "spec_step_batch"
         seqs = self._kv.sequences(who, caches)
         B = len(seqs)
         a = seqs[0].allocator
@@ -733,8 +751,15 @@ class Model(RowsTailState, StepTailState):
             raise ValueError(f"{who}: not available on a tensor-parallel model")
         if a.dtype == torch.int8:
             raise ValueError(f"{who}: not available on int8 KV pages")
-        for armed, name in ((self._batch_tail, "a batch tail"), (self._batch_edits, "batch logits edits"), (self._batch_counts, "a batch count penalty"),
-                            (self._batch_dry, "a batch DRY penalty"), (self._batch_xtc, "batch XTC records"), (self._batch_dfa, "batch token automata")):
+        if tail:
+            if self._batch_tail is None:
+                raise ValueError(f"{who}: no batch tail is set (set_batch_tail; the greedy and raw pass is spec_step_batch)")
+            refused = ((self._batch_dfa, "batch token automata"), (None if self._batch_edits is None else self._batch_edits["masks"], "a mask part of the batch logits edits"),
+                       (self._batch_counts, "a batch count penalty"), (self._batch_dry, "a batch DRY penalty"))
+        else:
+            refused = ((self._batch_tail, "a batch tail"), (self._batch_edits, "batch logits edits"), (self._batch_counts, "a batch count penalty"),
+                       (self._batch_dry, "a batch DRY penalty"), (self._batch_xtc, "batch XTC records"), (self._batch_dfa, "batch token automata"))
+        for armed, name in refused:
             if armed is not None:
                 raise ValueError(f"{who}: not available with {name}")
         tokens = torch.as_tensor(tokens).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
@@ -753,6 +778,8 @@ class Model(RowsTailState, StepTailState):
         if seq_ids is not None and (seq_ids.dtype != torch.int32 or seq_len.dtype != torch.int32 or seq_ids.dim() != 2 or not seq_ids.is_contiguous() or
                                     not seq_len.is_contiguous() or seq_ids.shape[0] < B or seq_len.numel() < B or not seq_ids.is_cuda or not seq_len.is_cuda):
             raise ValueError(f"{who}: seq_ids int32 [>= B, cap] and seq_len int32 [>= B] are contiguous device tensors")
+        if then_draft is not None and seq_ids is None:
+            raise ValueError(f"{who}: then_draft needs seq_ids and seq_len")
         for s, c in zip(seqs, m):
             s.reserve(1 + c)
         # the index arrays, as step_mixed forms them: row r of sequence s at position offset_s + (r - first_s)
@@ -768,19 +795,25 @@ class Model(RowsTailState, StepTailState):
         index = torch.from_numpy(np.concatenate([seg_first, row_seq, row_ctx, table.reshape(-1)])).to(self.device)   # one upload
         t_first, t_seq, t_ctx, t_table = index[:B + 1], index[B + 1:B + 1 + N], index[B + 1 + N:B + 1 + 2 * N], index[B + 1 + 2 * N:]
         lib = _ffi.load()
-        if self._spec_batch_ws is None:
-            self._spec_batch_ws = torch.empty((int(lib.pie_decoder_spec_batch_workspace_bytes(self._dec)) + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        V = self.vocab_out
+        if tail:
+            if self._spec_batch_tail_ws is None:   # zeroed once: the sampler's part carries over
+                self._spec_batch_tail_ws = torch.zeros((int(lib.pie_decoder_spec_batch_tail_workspace_bytes(self._dec)) + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+            ws, logprobs = self._spec_batch_tail_ws, torch.empty((N, V), dtype=torch.float32, device=self.device)
+        else:
+            if self._spec_batch_ws is None:
+                self._spec_batch_ws = torch.empty((int(lib.pie_decoder_spec_batch_workspace_bytes(self._dec)) + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+            ws, logprobs = self._spec_batch_ws, None
         rec = torch.empty(B * (hip_ops.SPEC_SEG_ROWS + 2), dtype=torch.int32, device=self.device)   # tokens [B, 8] | n [B] | the next draft's counts [B]
         out_tok, out_n, nxt_cnt = rec[:B * hip_ops.SPEC_SEG_ROWS], rec[B * hip_ops.SPEC_SEG_ROWS:B * (hip_ops.SPEC_SEG_ROWS + 1)], rec[B * (hip_ops.SPEC_SEG_ROWS + 1):]
-        rc = lib.pie_decoder_spec_step_batch(self._dec, _ffi.p(tokens), _ffi.p(drafts), drafts.shape[1], _ffi.p(t_ctx), _ffi.p(t_seq), _ffi.p(t_first), N, B,
-                                             *self._kv.pool_args(a), _ffi.p(t_table), mb, _ffi.p(out_tok), _ffi.p(out_n), _ffi.p(seq_ids), _ffi.p(seq_len),
-                                             0 if seq_ids is None else seq_ids.shape[1], _ffi.p(self._spec_batch_ws), _ffi.stream())
+        head = (self._dec, _ffi.p(tokens), _ffi.p(drafts), drafts.shape[1], _ffi.p(t_ctx), _ffi.p(t_seq), _ffi.p(t_first), N, B, *self._kv.pool_args(a), _ffi.p(t_table), mb,
+                _ffi.p(out_tok), _ffi.p(out_n))
+        back = (_ffi.p(seq_ids), _ffi.p(seq_len), 0 if seq_ids is None else seq_ids.shape[1], _ffi.p(ws), _ffi.stream())
+        rc = lib.pie_decoder_spec_step_batch_tail(*head, _ffi.p(logprobs), *back) if tail else lib.pie_decoder_spec_step_batch(*head, *back)
         if rc == -5:   # PIE_E_STATE: some per-row state of the multi-sequence passes is armed (top_logprobs, prompt scoring): the caller's fault, by name
             raise ValueError(f"{who}: " + lib.pie_last_error().decode("utf-8", "replace"))
         _ffi.check(rc)
         if then_draft is not None:
-            if seq_ids is None:
-                raise ValueError(f"{who}: then_draft needs seq_ids and seq_len")
             ngram_max, ngram_min, k, drafts_out = then_draft
             self.draft_rows(seq_ids[:B], seq_len[:B], ngram_max, ngram_min, k, out=(drafts_out[:B], nxt_cnt))
         host = rec.cpu().numpy()   # the one read-back
@@ -789,6 +822,8 @@ class Model(RowsTailState, StepTailState):
         for s, k_ in zip(seqs, n):
             s.advance(k_)
         self.spec_batch_last = {"tokens": out_tok.view(B, hip_ops.SPEC_SEG_ROWS), "n": out_n}
+        if tail:
+            self.spec_batch_last.update(logprobs=logprobs, logits=ws.view(self.dtype)[:N * V].view(N, V), seg_first=t_first)
         return n, toks, (host[B * (hip_ops.SPEC_SEG_ROWS + 1):].tolist() if then_draft is not None else None)
 
     def step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], graph: bool = True):
