@@ -57,7 +57,8 @@ enum {
     PIE_KNOB_W4R = 9,                /* 0: int4 Linears of 6..256 rows on the round-2 kernels (k_w4m_gemm, k_w4l2_gemm) instead of the weight-streaming k_w4r_gemm (the tests' cross-check) */
     PIE_KNOB_FUSE_ATTN = 10,         /* 0: the step's attention as its own launch instead of behind the q|k|v launch's XCD-local seam (32 / 8 / 128 heads; bit-identical; read per step enqueue / graph capture) */
     PIE_KNOB_ATTN_MERGE_IN_LAUNCH = 11, /* 0: the fused launch leaves the split-KV partials to o_proj's merging prologue instead of finishing every query head itself (bit-identical; read where the q|k|v launch is enqueued / captured) */
-    PIE_KNOB_COUNT = 12
+    PIE_KNOB_PREFILL_RESIDENT_KB = 12, /* the PIE_KNOB_PREFILL_RESIDENT budget in KiB; set (>= 0) it takes precedence.  It exists so that tests can admit some matrices of a small model and refuse others */
+    PIE_KNOB_COUNT = 13
 };
 #define PIE_KNOB_DEFAULT (-1)
 int pie_set_knob(int knob, int value);

@@ -19,7 +19,8 @@ PIE_SAMPLE_GREEDY = -1  # pie_decoder_set_sampler: the greedy tail
 PIE_TOP_LOGPROBS_MAX = 20  # pie_top_logprobs: the largest n
 # test / tuning switches (include/pie_hip.h: pie_set_knob); -1 restores a default
 KNOBS = {"prefill_min": 0, "prefill_chunk": 1, "prefill_resident": 2, "small_m": 3, "w4l_slabs": 4, "prefill_attn_valu": 5,
-         "prefill_qt": 6, "attn_merge_max_cap": 7, "attn_warm_max_mb": 8, "w4r": 9, "fuse_attn": 10, "attn_merge_in_launch": 11}
+         "prefill_qt": 6, "attn_merge_max_cap": 7, "attn_warm_max_mb": 8, "w4r": 9, "fuse_attn": 10, "attn_merge_in_launch": 11,
+         "prefill_resident_kb": 12}
 PIE_I8 = 3  # KV page storage: int8 rows + per-head fp16 scales
 # weight formats (pie_decoder_config.weight_format; pie_layer_weights / pie_global_weights fmt_* take PIE_W_* + 1, 0 = the decoder's)
 PIE_W_INT4_G64, PIE_W_DENSE, PIE_W_INT8_G64, PIE_W_INT4_G32, PIE_W_INT8_G32, PIE_W_INT2_G64, PIE_W_INT6_G64 = range(7)

@@ -467,14 +467,15 @@ static int scratch_reserve(pie_decoder *d, int rows, size_t w_elems, int splits)
 // ---------------------------------------------------------------- the batched forward
 
 // Byte budget for resident T copies of layer matrices, fixed at the first batched prefill: half of the free device memory
-// (PIE_KNOB_PREFILL_RESIDENT: 0 disables, <GiB> sets it).  Matrices are admitted in first-use order while the budget lasts
+// (PIE_KNOB_PREFILL_RESIDENT: 0 disables, <GiB> sets it; PIE_KNOB_PREFILL_RESIDENT_KB: the same in KiB, first).  Matrices are admitted in first-use order while the budget lasts
 // (8B model: all 15 GB; 70B: ~7/8 of its 140 GB); the rest keep going through the scratch every chunk.
 static size_t resident_budget(pie_decoder *d) {
     PrefillScratch *s = d->prefill;
     if (s->resident_mode < 0) {
         size_t free_b = 0, total_b = 0;
-        const int k = pie_knob(PIE_KNOB_PREFILL_RESIDENT);
-        if (k >= 0) s->resident_left = (size_t)k << 30;
+        const int k = pie_knob(PIE_KNOB_PREFILL_RESIDENT), kb = pie_knob(PIE_KNOB_PREFILL_RESIDENT_KB);
+        if (kb >= 0) s->resident_left = (size_t)kb << 10;
+        else if (k >= 0) s->resident_left = (size_t)k << 30;
         else s->resident_left = hipMemGetInfo(&free_b, &total_b) == hipSuccess ? free_b / 2 : 0;
         s->resident_mode = 1;
     }
