@@ -1220,8 +1220,9 @@ static int spec_batch_body(const std::string &who, bool with_tail, pie_decoder *
     if (int rc = shared.check(POOL_SLABS, POOL_SLABS)) return rc;
     const int V = d->cfg.vocab;
     u16 *logits = (u16 *)workspace;
-    int *fed = (int *)((char *)workspace + align16((size_t)SPEC_BATCH_ROWS * V * 2));
-    *fed_out = fed, *verify_ws = (char *)fed + align16(sizeof(int) * SPEC_BATCH_ROWS);
+    const SpecPassLayout lay(SPEC_BATCH_ROWS, SPEC_BATCH_ROWS, V);
+    int *fed = (int *)((char *)workspace + lay.fed);
+    *fed_out = fed, *verify_ws = (char *)workspace + lay.verify;
     // a row no segment covers is fed id 0 (seg_first is device memory: nothing here can check it)
     PIE_HIP_TRY(hipMemsetAsync(fed, 0, sizeof(int) * (size_t)N, st));
     if (int rc = spec_gather_rows_launch(tokens, draft_ids, draft_stride, seg_first, B, N, d->embed_vocab(), fed, st)) return rc;
@@ -1230,10 +1231,9 @@ static int spec_batch_body(const std::string &who, bool with_tail, pie_decoder *
     });
 }
 
-// workspace: the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows' workspace for 256 rows
+// workspace (SpecPassLayout): the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows' workspace for 256 rows
 extern "C" size_t pie_decoder_spec_batch_workspace_bytes(const pie_decoder *d) {
-    if (!d) return 0;
-    return align16((size_t)SPEC_BATCH_ROWS * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_BATCH_ROWS) + spec_verify_rows_workspace_bytes(SPEC_BATCH_ROWS);
+    return d ? SpecPassLayout(SPEC_BATCH_ROWS, SPEC_BATCH_ROWS, d->cfg.vocab).bytes(pie_spec_verify_rows_workspace_bytes(SPEC_BATCH_ROWS)) : 0;
 }
 
 extern "C" int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens, const int32_t *draft_ids, int draft_stride, const int32_t *row_context_lens,
@@ -1250,11 +1250,9 @@ extern "C" int pie_decoder_spec_step_batch(pie_decoder *d, const int32_t *tokens
                                    verify_ws, st);
 }
 
-// workspace: the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows_sampled's workspace for 256 rows (zeroed once)
+// workspace (SpecPassLayout): the logits block [256, vocab] T | the pass's input ids [256] | pie_spec_verify_rows_sampled's workspace for 256 rows (zeroed once)
 extern "C" size_t pie_decoder_spec_batch_tail_workspace_bytes(const pie_decoder *d) {
-    if (!d || spec_verify_rows_sampled_workspace_bytes(SPEC_BATCH_ROWS, d->cfg.vocab) == 0) return 0;
-    return align16((size_t)SPEC_BATCH_ROWS * d->cfg.vocab * 2) + align16(sizeof(int) * SPEC_BATCH_ROWS) +
-           spec_verify_rows_sampled_workspace_bytes(SPEC_BATCH_ROWS, d->cfg.vocab);
+    return d ? SpecPassLayout(SPEC_BATCH_ROWS, SPEC_BATCH_ROWS, d->cfg.vocab).bytes(pie_spec_verify_rows_sampled_workspace_bytes(SPEC_BATCH_ROWS, d->cfg.vocab)) : 0;
 }
 
 // The pass under the seats' own tails: the same body, then the batch tail's records and rings, the batch edits' bias part

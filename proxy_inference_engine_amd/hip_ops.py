@@ -1329,6 +1329,40 @@ def _int32_dev(t: torch.Tensor, n: int | None, who: str, name: str) -> None:
         raise ValueError(f"{who}: {name} is a contiguous int32 device tensor" + ("" if n is None else f" of {n}"))
 
 
+def _workspace(size_fn: str, zeroed: bool, who: str, hint: str, device, *dims) -> torch.Tensor:
+    """A 16-byte aligned workspace of the library's size function `size_fn` over `dims`, zeroed or uninitialised; a size of 0 (the
+    library refuses the dims) is `who`'s ValueError with `hint`."""
+    nbytes = int(getattr(_ffi.load(), size_fn)(*(int(d) for d in dims)))
+    if nbytes == 0:
+        raise ValueError(f"{who}: {hint}")
+    return (torch.zeros if zeroed else torch.empty)((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+
+
+def _fp32_block(t: torch.Tensor, shape: tuple, who: str, name: str, dims: str) -> None:
+    _dev(t)
+    if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} is a contiguous fp32 [{dims}] device tensor")
+
+
+def _spec_block(who: str, logits: torch.Tensor, draft: torch.Tensor, logprobs: torch.Tensor | None, out: tuple | None, need_logprobs: bool):
+    """A one-sequence verify's block, validated: logits bf16 / f16 [rows, V], draft int32 [rows - 1], logprobs fp32 [rows, V] (made here
+    when the verify needs them and none are given), out = (tokens int32 [rows], n int32 [1]) or fresh ones -> (rows, V, tokens, n, logprobs)."""
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError(f"{who}: contiguous bf16 / f16 [rows, V] logits")
+    rows, V = logits.shape
+    _int32_dev(draft, rows - 1, who, "draft")
+    if logprobs is None and need_logprobs:
+        logprobs = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
+    if logprobs is not None:
+        _fp32_block(logprobs, (rows, V), who, "logprobs", "rows, V")
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
+    tokens, n = out
+    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
+    return rows, V, tokens, n, logprobs
+
+
 def ngram_draft_workspace(device) -> torch.Tensor:
     """pie_ngram_draft's workspace on `device`: uninitialised, nothing is carried from call to call."""
     return torch.empty(int(_ffi.load().pie_ngram_draft_workspace_bytes()) // 4, dtype=torch.int32, device=device)
@@ -1360,10 +1394,7 @@ def ngram_draft(ids: torch.Tensor, length: torch.Tensor, ngram_max: int, ngram_m
 
 def spec_verify_workspace(device, rows: int) -> torch.Tensor:
     """pie_spec_verify's workspace for `rows` rows on `device`: uninitialised, nothing is carried from call to call."""
-    nbytes = int(_ffi.load().pie_spec_verify_workspace_bytes(int(rows)))
-    if nbytes == 0:
-        raise ValueError(f"spec_verify: 2 <= rows <= {SPEC_MAX_ROWS}, got {rows}")
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+    return _workspace("pie_spec_verify_workspace_bytes", False, "spec_verify", f"2 <= rows <= {SPEC_MAX_ROWS}, got {rows}", device, rows)
 
 
 def spec_verify(logits: torch.Tensor, draft: torch.Tensor, logprobs: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
@@ -1373,21 +1404,8 @@ def spec_verify(logits: torch.Tensor, draft: torch.Tensor, logprobs: torch.Tenso
     greedy token (hip_ops.logprobs_argmax of that row, bit for bit; an id outside [0, V) is never accepted), n = accepted + 1, tokens =
     the greedy tokens of rows 0 .. n - 1, then -1.  logprobs: fp32 [rows, V] to write rows 0 .. n - 1 into (logprobs_argmax's bits); the
     rows behind them keep their contents.  out = (tokens, n) to write into.  rows 2..32."""
-    who = "spec_verify"
-    _dev(logits)
-    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
-        raise ValueError("spec_verify: contiguous bf16 / f16 [rows, V] logits")
-    rows, V = logits.shape
-    _int32_dev(draft, rows - 1, who, "draft")
-    if logprobs is not None:
-        _dev(logprobs)
-        if logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (rows, V) or not logprobs.is_contiguous():
-            raise ValueError("spec_verify: logprobs is a contiguous fp32 [rows, V] device tensor")
+    rows, V, tokens, n, logprobs = _spec_block("spec_verify", logits, draft, logprobs, out, False)
     ws = spec_verify_workspace(logits.device, rows) if workspace is None else workspace
-    if out is None:
-        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
-    tokens, n = out
-    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
     _ffi.check(_ffi.load().pie_spec_verify(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(draft), _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs),
                                            _ffi.p(ws), _ffi.stream()))
     return tokens, n
@@ -1395,10 +1413,8 @@ def spec_verify(logits: torch.Tensor, draft: torch.Tensor, logprobs: torch.Tenso
 
 def spec_verify_sampled_workspace(device, rows: int, V: int) -> torch.Tensor:
     """pie_spec_verify_sampled's workspace for a [rows, V] block on `device`: zeroed once, the kernels leave it ready for the next call."""
-    nbytes = int(_ffi.load().pie_spec_verify_sampled_workspace_bytes(int(rows), int(V)))
-    if nbytes == 0:
-        raise ValueError(f"spec_verify_sampled: 2 <= rows <= {SPEC_MAX_ROWS} and 1 <= V <= 524288, got [{rows}, {V}]")
-    return torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+    return _workspace("pie_spec_verify_sampled_workspace_bytes", True, "spec_verify_sampled", f"2 <= rows <= {SPEC_MAX_ROWS} and 1 <= V <= 524288, got [{rows}, {V}]",
+                      device, rows, V)
 
 
 def spec_verify_sampled(logits: torch.Tensor, draft: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0, xtc=None,
@@ -1412,23 +1428,10 @@ def spec_verify_sampled(logits: torch.Tensor, draft: torch.Tensor, mode: str, te
     spec_verify_sampled_workspace's (zeroed once); out = (tokens, n) to write into.  rows 2..32."""
     from .samplers import _rng
     who = "spec_verify_sampled"
-    _dev(logits)
-    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
-        raise ValueError(f"{who}: contiguous bf16 / f16 [rows, V] logits")
     if mode not in SAMPLE_MODES:
         raise ValueError(f"{who}: mode is one of {sorted(SAMPLE_MODES)} (the greedy verify is spec_verify)")
-    rows, V = logits.shape
-    _int32_dev(draft, rows - 1, who, "draft")
-    if logprobs is None:
-        logprobs = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
-    _dev(logprobs)
-    if logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (rows, V) or not logprobs.is_contiguous():
-        raise ValueError(f"{who}: logprobs is a contiguous fp32 [rows, V] device tensor")
+    rows, V, tokens, n, logprobs = _spec_block(who, logits, draft, logprobs, out, True)
     ws = spec_verify_sampled_workspace(logits.device, rows, V) if workspace is None else workspace
-    if out is None:
-        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
-    tokens, n = out
-    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
     seed, counter = _rng.hip_state(logits.device)
     rec = None if xtc is None else _xtc(xtc, 1, logits.device, who)
     _ffi.check(_ffi.load().pie_spec_verify_sampled(_ffi.p(logits), rows, V, _ffi.dtype_code(logits.dtype), _ffi.p(draft), SAMPLE_MODES[mode], float(temp), float(p),
@@ -1439,10 +1442,8 @@ def spec_verify_sampled(logits: torch.Tensor, draft: torch.Tensor, mode: str, te
 
 def spec_verify_draft_workspace(device, rows: int, V: int) -> torch.Tensor:
     """pie_spec_verify_draft's workspace for a [rows, V] block on `device`: zeroed once, the kernels leave it ready for the next call."""
-    nbytes = int(_ffi.load().pie_spec_verify_draft_workspace_bytes(int(rows), int(V)))
-    if nbytes == 0:
-        raise ValueError(f"spec_verify_draft: 2 <= rows <= {SPEC_MAX_ROWS} and 1 <= V <= 524288, got [{rows}, {V}]")
-    return torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+    return _workspace("pie_spec_verify_draft_workspace_bytes", True, "spec_verify_draft", f"2 <= rows <= {SPEC_MAX_ROWS} and 1 <= V <= 524288, got [{rows}, {V}]",
+                      device, rows, V)
 
 
 def spec_verify_draft(logits: torch.Tensor, draft: torch.Tensor, q_logprobs: torch.Tensor, mode: str, temp: float, p: float = 0.0, k: int = 0,
@@ -1461,26 +1462,11 @@ def spec_verify_draft(logits: torch.Tensor, draft: torch.Tensor, q_logprobs: tor
     have drawn under ANOTHER seed.  workspace: spec_verify_draft_workspace's (zeroed once); out = (tokens, n) to write into.  rows 2..32."""
     from .samplers import _rng
     who = "spec_verify_draft"
-    _dev(logits)
-    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
-        raise ValueError(f"{who}: contiguous bf16 / f16 [rows, V] logits")
     if mode not in SAMPLE_MODES:
         raise ValueError(f"{who}: mode is one of {sorted(SAMPLE_MODES)} (a greedy draft is verified by spec_verify)")
-    rows, V = logits.shape
-    _int32_dev(draft, rows - 1, who, "draft")
-    _dev(q_logprobs)
-    if q_logprobs.dtype != torch.float32 or tuple(q_logprobs.shape) != (rows - 1, V) or not q_logprobs.is_contiguous():
-        raise ValueError(f"{who}: q_logprobs is a contiguous fp32 [rows - 1, V] device tensor")
-    if logprobs is None:
-        logprobs = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
-    _dev(logprobs)
-    if logprobs.dtype != torch.float32 or tuple(logprobs.shape) != (rows, V) or not logprobs.is_contiguous():
-        raise ValueError(f"{who}: logprobs is a contiguous fp32 [rows, V] device tensor")
+    rows, V, tokens, n, logprobs = _spec_block(who, logits, draft, logprobs, out, True)
+    _fp32_block(q_logprobs, (rows - 1, V), who, "q_logprobs", "rows - 1, V")
     ws = spec_verify_draft_workspace(logits.device, rows, V) if workspace is None else workspace
-    if out is None:
-        out = (torch.empty(rows, dtype=torch.int32, device=logits.device), torch.empty(1, dtype=torch.int32, device=logits.device))
-    tokens, n = out
-    _int32_dev(tokens, rows, who, "out[0]"), _int32_dev(n, 1, who, "out[1]")
     seed, counter = _rng.hip_state(logits.device) if rng is None else rng
     rec = torch.zeros((rows - 1, 3), dtype=torch.float32, device=logits.device) if want_record else None
     res = torch.zeros((rows, V), dtype=torch.float32, device=logits.device) if want_record else None
@@ -1577,10 +1563,7 @@ def paged_attn_verify(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_t
 
 def ngram_draft_rows_workspace(device, B: int) -> torch.Tensor:
     """pie_ngram_draft_rows' workspace for B sequences on `device`: uninitialised, nothing is carried from call to call."""
-    nbytes = int(_ffi.load().pie_ngram_draft_rows_workspace_bytes(int(B)))
-    if nbytes == 0:
-        raise ValueError(f"ngram_draft_rows: 1 <= B <= 4096, got {B}")
-    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+    return _workspace("pie_ngram_draft_rows_workspace_bytes", False, "ngram_draft_rows", f"1 <= B <= 4096, got {B}", device, B).view(torch.int32)
 
 
 def ngram_draft_rows(ids: torch.Tensor, lengths: torch.Tensor, ngram_max: int, ngram_min: int, k: int, workspace: torch.Tensor | None = None,
@@ -1606,6 +1589,39 @@ def ngram_draft_rows(ids: torch.Tensor, lengths: torch.Tensor, ngram_max: int, n
     return drafts, counts
 
 
+def _spec_segments(who: str, logits: torch.Tensor, seg_first: torch.Tensor, drafts: torch.Tensor, ids: torch.Tensor | None, lengths: torch.Tensor | None,
+                   out: tuple | None, with_logprobs: bool):
+    """A segmented verify's block, validated: logits bf16 / f16 [N, V], seg_first int32 [B + 1], drafts int32 [B, >= 1], ids int32 [B, cap]
+    with lengths int32 [B] or neither, out = (tokens int32 [B, 8], n int32 [B]) -- with_logprobs: and logprobs fp32 [N, V] -- or fresh
+    ones -> (N, V, B, cap, out)."""
+    _dev(logits)
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
+        raise ValueError(f"{who}: contiguous bf16 / f16 [N, V] logits")
+    N, V = logits.shape
+    _int32_dev(seg_first, None, who, "seg_first"), _int32_dev(drafts, None, who, "drafts")
+    B = seg_first.numel() - 1
+    if B < 1 or drafts.dim() != 2 or drafts.shape[0] != B or drafts.shape[1] < 1:
+        raise ValueError(f"{who}: seg_first [B + 1] and drafts [B, >= 1]")
+    if (ids is None) != (lengths is None):
+        raise ValueError(f"{who}: ids and lengths come together")
+    cap = 0
+    if ids is not None:
+        _int32_dev(ids, None, who, "ids"), _int32_dev(lengths, B, who, "lengths")
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
+            raise ValueError(f"{who}: ids is [B, cap]")
+        cap = ids.shape[1]
+    if out is None:
+        out = (torch.empty((B, SPEC_SEG_ROWS), dtype=torch.int32, device=logits.device), torch.empty(B, dtype=torch.int32, device=logits.device))
+        if with_logprobs:
+            out += (torch.empty((N, V), dtype=torch.float32, device=logits.device),)
+    _int32_dev(out[0], B * SPEC_SEG_ROWS, who, "out[0]"), _int32_dev(out[1], B, who, "out[1]")
+    if with_logprobs:
+        _dev(out[2])
+        if out[2].dtype != torch.float32 or not out[2].is_contiguous() or out[2].numel() < N * V:
+            raise ValueError(f"{who}: out[2] is a contiguous fp32 [N, V] device tensor")
+    return N, V, B, cap, out
+
+
 def spec_verify_rows(logits: torch.Tensor, seg_first: torch.Tensor, drafts: torch.Tensor, ids: torch.Tensor | None = None, lengths: torch.Tensor | None = None,
                      workspace: torch.Tensor | None = None, out: tuple | None = None):
     """The segmented verify of a batched speculative pass (pie_spec_verify_rows): logits bf16 / f16 [N, V]; seg_first int32 [B + 1] cuts
@@ -1615,30 +1631,10 @@ def spec_verify_rows(logits: torch.Tensor, seg_first: torch.Tensor, drafts: torc
     n = accepted + 1, tokens = those greedy tokens, then -1; a one-row segment gives its greedy token and n = 1, an idle slot n = 0.
     ids int32 [B, cap] / lengths int32 [B] (together, optional): the drafter's input, ids[s, lengths[s] - 1] being the token the pass was
     fed -- the n tokens are written behind it and lengths[s] += n, on the device."""
-    who = "spec_verify_rows"
-    _dev(logits)
-    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
-        raise ValueError("spec_verify_rows: contiguous bf16 / f16 [N, V] logits")
-    N, V = logits.shape
-    _int32_dev(seg_first, None, who, "seg_first"), _int32_dev(drafts, None, who, "drafts")
-    B = seg_first.numel() - 1
-    if B < 1 or drafts.dim() != 2 or drafts.shape[0] != B or drafts.shape[1] < 1:
-        raise ValueError("spec_verify_rows: seg_first [B + 1] and drafts [B, >= 1]")
-    if (ids is None) != (lengths is None):
-        raise ValueError("spec_verify_rows: ids and lengths come together")
-    cap = 0
-    if ids is not None:
-        _int32_dev(ids, None, who, "ids"), _int32_dev(lengths, B, who, "lengths")
-        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
-            raise ValueError("spec_verify_rows: ids is [B, cap]")
-        cap = ids.shape[1]
+    N, V, B, cap, (tokens, n) = _spec_segments("spec_verify_rows", logits, seg_first, drafts, ids, lengths, out, False)
     lib = _ffi.load()
     if workspace is None:
         workspace = torch.empty((int(lib.pie_spec_verify_rows_workspace_bytes(N)) + 15) // 16 * 2, dtype=torch.int64, device=logits.device)
-    if out is None:
-        out = (torch.empty((B, SPEC_SEG_ROWS), dtype=torch.int32, device=logits.device), torch.empty(B, dtype=torch.int32, device=logits.device))
-    tokens, n = out
-    _int32_dev(tokens, B * SPEC_SEG_ROWS, who, "out[0]"), _int32_dev(n, B, who, "out[1]")
     _ffi.check(lib.pie_spec_verify_rows(_ffi.p(logits), N, V, _ffi.dtype_code(logits.dtype), _ffi.p(seg_first), B, _ffi.p(drafts), drafts.shape[1], _ffi.p(tokens),
                                         _ffi.p(n), _ffi.p(ids), _ffi.p(lengths), cap, _ffi.p(workspace), _ffi.stream()))
     return tokens, n
@@ -1646,10 +1642,8 @@ def spec_verify_rows(logits: torch.Tensor, seg_first: torch.Tensor, drafts: torc
 
 def spec_verify_rows_sampled_workspace(device, n_rows: int, V: int) -> torch.Tensor:
     """pie_spec_verify_rows_sampled's workspace for a [n_rows, V] block on `device`: zeroed once, reusable from call to call."""
-    nbytes = int(_ffi.load().pie_spec_verify_rows_sampled_workspace_bytes(int(n_rows), int(V)))
-    if nbytes == 0:
-        raise ValueError(f"spec_verify_rows_sampled: a [n_rows, V] block with 1 <= n_rows <= 65535 and 1 <= V <= 524288, got [{n_rows}, {V}]")
-    return torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=device)
+    return _workspace("pie_spec_verify_rows_sampled_workspace_bytes", True, "spec_verify_rows_sampled",
+                      f"a [n_rows, V] block with 1 <= n_rows <= 65535 and 1 <= V <= 524288, got [{n_rows}, {V}]", device, n_rows, V)
 
 
 def spec_verify_rows_sampled(logits: torch.Tensor, seg_first: torch.Tensor, fed: torch.Tensor, drafts: torch.Tensor, pos0: torch.Tensor, table: torch.Tensor,
@@ -1666,15 +1660,8 @@ def spec_verify_rows_sampled(logits: torch.Tensor, seg_first: torch.Tensor, fed:
     logprobs fp32 [N, V]), no host sync; afterwards a drawing seat's calls has advanced by n[s] and its ring holds the n[s] ids the pass fed
     for good, on the device.  ids / lengths as in spec_verify_rows.  workspace: spec_verify_rows_sampled_workspace's (zeroed once)."""
     who = "spec_verify_rows_sampled"
-    _dev(logits)
-    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float16) or not logits.is_contiguous():
-        raise ValueError(f"{who}: contiguous bf16 / f16 [N, V] logits")
-    N, V = logits.shape
-    _int32_dev(seg_first, None, who, "seg_first"), _int32_dev(drafts, None, who, "drafts"), _int32_dev(fed, N, who, "fed")
-    B = seg_first.numel() - 1
-    if B < 1 or drafts.dim() != 2 or drafts.shape[0] != B or drafts.shape[1] < 1:
-        raise ValueError(f"{who}: seg_first [B + 1] and drafts [B, >= 1]")
-    _int32_dev(pos0, B, who, "pos0"), _int32_dev(recent_ids, None, who, "recent_ids")
+    N, V, B, cap, (tokens, n, logprobs) = _spec_segments(who, logits, seg_first, drafts, ids, lengths, out, True)
+    _int32_dev(fed, N, who, "fed"), _int32_dev(pos0, B, who, "pos0"), _int32_dev(recent_ids, None, who, "recent_ids")
     _table(table, B, who)
     if recent_ids.dim() != 2 or recent_ids.shape[1] != RECENT_IDS or recent_ids.shape[0] < B:
         raise ValueError(f"{who}: recent_ids is [>= B, {RECENT_IDS}]")
@@ -1688,14 +1675,6 @@ def spec_verify_rows_sampled(logits: torch.Tensor, seg_first: torch.Tensor, fed:
             raise ValueError(f"{who}: bias is (int32 ids, float32 values [>= B, 1 <= cap <= 1024], int32 n [>= B]), contiguous")
         b_cap = b_ids.shape[1]
     rec = None if xtc is None else _xtc(xtc, B, logits.device, who)
-    if (ids is None) != (lengths is None):
-        raise ValueError(f"{who}: ids and lengths come together")
-    cap = 0
-    if ids is not None:
-        _int32_dev(ids, None, who, "ids"), _int32_dev(lengths, B, who, "lengths")
-        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
-            raise ValueError(f"{who}: ids is [B, cap]")
-        cap = ids.shape[1]
     lib = _ffi.load()
     need = int(lib.pie_spec_verify_rows_sampled_workspace_bytes(N, V))
     if need == 0:
@@ -1705,14 +1684,6 @@ def spec_verify_rows_sampled(logits: torch.Tensor, seg_first: torch.Tensor, fed:
     _dev(workspace)
     if workspace.numel() * workspace.element_size() < need:
         raise ValueError(f"{who}: the workspace is spec_verify_rows_sampled_workspace()'s size")
-    if out is None:
-        out = (torch.empty((B, SPEC_SEG_ROWS), dtype=torch.int32, device=logits.device), torch.empty(B, dtype=torch.int32, device=logits.device),
-               torch.empty((N, V), dtype=torch.float32, device=logits.device))
-    tokens, n, logprobs = out
-    _int32_dev(tokens, B * SPEC_SEG_ROWS, who, "out[0]"), _int32_dev(n, B, who, "out[1]")
-    _dev(logprobs)
-    if logprobs.dtype != torch.float32 or not logprobs.is_contiguous() or logprobs.numel() < N * V:
-        raise ValueError(f"{who}: out[2] is a contiguous fp32 [N, V] device tensor")
     _ffi.check(lib.pie_spec_verify_rows_sampled(_ffi.p(logits), N, V, _ffi.dtype_code(logits.dtype), _ffi.p(seg_first), B, _ffi.p(fed), _ffi.p(drafts), drafts.shape[1],
                                                 _ffi.p(pos0), _ffi.p(table), _ffi.p(recent_ids), _ffi.p(b_ids), _ffi.p(b_vals), _ffi.p(b_n), b_cap, _ffi.p(rec),
                                                 _ffi.p(tokens), _ffi.p(n), _ffi.p(logprobs), _ffi.p(ids), _ffi.p(lengths), cap, _ffi.p(workspace), _ffi.stream()))

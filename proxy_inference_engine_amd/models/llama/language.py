@@ -504,12 +504,29 @@ class Model(RowsTailState, StepTailState):
     def _spec_state(self) -> dict:
         """The record, the pass's workspace and log-probability rows, the drafter's workspace: made when first used."""
         if self._spec is None:
-            nbytes = int(_ffi.load().pie_decoder_spec_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
             self._spec = {"rec": torch.zeros(self._SPEC_WORDS, dtype=torch.int32, device=self.device),
-                          "ws": torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device),
                           "logprobs": torch.empty((hip_ops.SPEC_MAX_ROWS, self.vocab_out), dtype=torch.float32, device=self.device),
                           "draft_ws": hip_ops.ngram_draft_workspace(self.device), "host": None}
+            self._spec_ws(self._spec, "ws", "pie_decoder_spec_workspace_bytes", False, hip_ops.SPEC_MAX_ROWS)
         return self._spec
+
+    def _spec_ws(self, store: dict, key: str, size_fn: str, zeroed: bool, *dims) -> torch.Tensor:
+        """store[key] = the workspace of one kind of speculative pass, made when first used: `size_fn`(decoder, *dims) bytes, zeroed once
+        where the sampler's part is carried from pass to pass."""
+        if store.get(key) is None:
+            nbytes = int(getattr(_ffi.load(), size_fn)(self._dec, *dims))
+            store[key] = (torch.zeros if zeroed else torch.empty)((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        return store[key]
+
+    def _refuse(self, who: str, rows) -> None:
+        """The speculative passes' refusals by name: rows = ((set or not, the part's name), ...)."""
+        for bad, name in rows:
+            if bad:
+                raise ValueError(f"{who}: not available with {name}")
+
+    def _spec_refused_rows(self) -> tuple:
+        """The parts of the step's tail that no speculative pass under a tail takes."""
+        return ((self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"), (self._dry is not None, "a DRY penalty"))
 
     @property
     def spec_min_rows(self) -> int:
@@ -634,16 +651,10 @@ class Model(RowsTailState, StepTailState):
         penalties and DRY are refused by name, like tensor-parallel models, int8 pages and the other cache kinds."""
         who = "spec_step_tail"
         self._check_speculative_kv(who, cache)
-        for bad, name in ((self._edits[0], "a token mask"), (self._dfa is not None, "a token automaton"), (self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"),
-                          (self._dry is not None, "a DRY penalty")):
-            if bad:
-                raise ValueError(f"{who}: not available with {name}")
+        self._refuse(who, ((self._edits[0], "a token mask"), (self._dfa is not None, "a token automaton"), *self._spec_refused_rows()))
         if self._tail[:2] == (None, None) and self._edits[1] == 0:
             raise ValueError(f"{who}: no sampler, repetition penalty or logit bias is set -- the greedy and raw pass is spec_step")
-        sp = self._spec_state()
-        if "tail_ws" not in sp:  # zeroed once: the sampler's part is carried from pass to pass
-            nbytes = int(_ffi.load().pie_decoder_spec_tail_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
-            sp["tail_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        self._spec_ws(self._spec_state(), "tail_ws", "pie_decoder_spec_tail_workspace_bytes", True, hip_ops.SPEC_MAX_ROWS)
         return self._spec_pass(who, "pie_decoder_spec_step_tail", "tail_ws", draft_ids, cache, then_draft)
 
     def spec_step_grammar(self, draft_ids: torch.Tensor, cache: list[BaseCache], then_draft: tuple | None = None):
@@ -656,16 +667,10 @@ class Model(RowsTailState, StepTailState):
         presence penalties and DRY are refused by name, like tensor-parallel models, int8 pages and the other cache kinds."""
         who = "spec_step_grammar"
         self._check_speculative_kv(who, cache)
-        for bad, name in ((self._edits[0], "a token mask"), (self._top_n is not None, "top_logprobs"), (self._cnt is not None, "frequency / presence penalties"),
-                          (self._dry is not None, "a DRY penalty")):
-            if bad:
-                raise ValueError(f"{who}: not available with {name}")
+        self._refuse(who, ((self._edits[0], "a token mask"), *self._spec_refused_rows()))
         if self._dfa is None:
             raise ValueError(f"{who}: no token automaton is set -- the pass without one is spec_step_tail")
-        sp = self._spec_state()
-        if "grammar_ws" not in sp:  # zeroed once, a workspace of its own: the sampler's part is carried from pass to pass
-            nbytes = int(_ffi.load().pie_decoder_spec_dfa_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
-            sp["grammar_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        self._spec_ws(self._spec_state(), "grammar_ws", "pie_decoder_spec_dfa_workspace_bytes", True, hip_ops.SPEC_MAX_ROWS)  # a workspace of its own
         return self._spec_pass(who, "pie_decoder_spec_step_dfa", "grammar_ws", draft_ids, cache, then_draft)
 
     def spec_step_draft(self, draft_ids: torch.Tensor, q_logprobs: torch.Tensor, cache: list[BaseCache], *, draft_seed: int):
@@ -682,10 +687,7 @@ class Model(RowsTailState, StepTailState):
         tensor-parallel models, int8 pages and the other cache kinds."""
         who = "spec_step_draft"
         self._check_speculative_kv(who, cache)
-        for bad, name in ((self._xtc is not None, "XTC"), (self._edits[0], "a token mask"), (self._top_n is not None, "top_logprobs"),
-                          (self._cnt is not None, "frequency / presence penalties"), (self._dry is not None, "a DRY penalty")):
-            if bad:
-                raise ValueError(f"{who}: not available with {name}")
+        self._refuse(who, ((self._xtc is not None, "XTC"), (self._edits[0], "a token mask"), *self._spec_refused_rows()))
         if self._tail[0] is None:
             raise ValueError(f"{who}: no stochastic sampler is set -- a greedy draft is a point mass, verified by spec_step or spec_step_tail")
         if int(draft_seed) & (2 ** 64 - 1) == int(self._tail[2]) & (2 ** 64 - 1):
@@ -694,10 +696,7 @@ class Model(RowsTailState, StepTailState):
         if not q_logprobs.is_cuda or q_logprobs.dtype != torch.float32 or q_logprobs.dim() != 2 or q_logprobs.shape[0] < m or \
                 q_logprobs.shape[1] != self.vocab_out or not q_logprobs.is_contiguous():
             raise ValueError(f"{who}: q_logprobs is a contiguous fp32 [>= {m}, {self.vocab_out}] device tensor (a vocabulary mismatch is refused)")
-        sp = self._spec_state()
-        if "draft_model_ws" not in sp:  # zeroed once: the samplers' parts are carried from pass to pass
-            nbytes = int(_ffi.load().pie_decoder_spec_draft_workspace_bytes(self._dec, hip_ops.SPEC_MAX_ROWS))
-            sp["draft_model_ws"] = torch.zeros((nbytes + 15) // 16 * 2, dtype=torch.int64, device=self.device)
+        self._spec_ws(self._spec_state(), "draft_model_ws", "pie_decoder_spec_draft_workspace_bytes", True, hip_ops.SPEC_MAX_ROWS)
         return self._spec_pass(who, "pie_decoder_spec_step_draft", "draft_model_ws", draft_ids, cache, None, extra=(_ffi.p(q_logprobs),))
 
     def spec_logits(self, rows: int) -> torch.Tensor:
@@ -759,9 +758,7 @@ class Model(RowsTailState, StepTailState):
         else:
             refused = ((self._batch_tail, "a batch tail"), (self._batch_edits, "batch logits edits"), (self._batch_counts, "a batch count penalty"),
                        (self._batch_dry, "a batch DRY penalty"), (self._batch_xtc, "batch XTC records"), (self._batch_dfa, "batch token automata"))
-        for armed, name in refused:
-            if armed is not None:
-                raise ValueError(f"{who}: not available with {name}")
+        self._refuse(who, ((armed is not None, name) for armed, name in refused))
         tokens = torch.as_tensor(tokens).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
         m = [int(c) for c in counts]
         if tokens.numel() != B or len(m) != B:
@@ -797,13 +794,10 @@ class Model(RowsTailState, StepTailState):
         lib = _ffi.load()
         V = self.vocab_out
         if tail:
-            if self._spec_batch_tail_ws is None:   # zeroed once: the sampler's part carries over
-                self._spec_batch_tail_ws = torch.zeros((int(lib.pie_decoder_spec_batch_tail_workspace_bytes(self._dec)) + 15) // 16 * 2, dtype=torch.int64, device=self.device)
-            ws, logprobs = self._spec_batch_tail_ws, torch.empty((N, V), dtype=torch.float32, device=self.device)
+            ws = self._spec_ws(vars(self), "_spec_batch_tail_ws", "pie_decoder_spec_batch_tail_workspace_bytes", True)
+            logprobs = torch.empty((N, V), dtype=torch.float32, device=self.device)
         else:
-            if self._spec_batch_ws is None:
-                self._spec_batch_ws = torch.empty((int(lib.pie_decoder_spec_batch_workspace_bytes(self._dec)) + 15) // 16 * 2, dtype=torch.int64, device=self.device)
-            ws, logprobs = self._spec_batch_ws, None
+            ws, logprobs = self._spec_ws(vars(self), "_spec_batch_ws", "pie_decoder_spec_batch_workspace_bytes", False), None
         rec = torch.empty(B * (hip_ops.SPEC_SEG_ROWS + 2), dtype=torch.int32, device=self.device)   # tokens [B, 8] | n [B] | the next draft's counts [B]
         out_tok, out_n, nxt_cnt = rec[:B * hip_ops.SPEC_SEG_ROWS], rec[B * hip_ops.SPEC_SEG_ROWS:B * (hip_ops.SPEC_SEG_ROWS + 1)], rec[B * (hip_ops.SPEC_SEG_ROWS + 1):]
         head = (self._dec, _ffi.p(tokens), _ffi.p(drafts), drafts.shape[1], _ffi.p(t_ctx), _ffi.p(t_seq), _ffi.p(t_first), N, B, *self._kv.pool_args(a), _ffi.p(t_table), mb,

@@ -133,7 +133,7 @@ def check_segment(g: dict, got: dict, V: int, cap: int, what):
 # ------------------------------------------------------------------ 1. the op against the rows alone, bit for bit
 SEG_ROWS = [1, 2, 8, 1, 0]                                               # and an idle slot
 KINDS = ["greedy", "greedy_pen", "top_p_pen_bias", "top_k_xtc"]
-POS_CASES = [(0, 60), (37, 60), (1020, 1024)]                            # pos0 0; below context_size; the segment's slots wrap onto positions row 0 still reads
+POS_CASES = [(0, 60), (37, 60), (1020, 1024), (37, 1)]                   # pos0 0; below context_size; the segment's slots wrap onto positions row 0 still reads; a window of the row's own input alone
 VARIANTS = ["all", "rej0", "mid", "oov"]
 
 

@@ -227,14 +227,37 @@ def oracle_after_prompt(golden_dir, name, prompt):
 @pytest.mark.parametrize("o", [60, 252])
 @pytest.mark.parametrize("name", list(MODELS))
 def test_spec_step_tail_equals_the_rows_alone_and_leaves_plain_steps_whole(golden_dir, name, o, kind, tail_name):
-    """o + m + 1 = 68 / 260 crosses a 64-row page boundary (and 256, the contiguous cache's growth step).  The agreeing continuation is
-    built row by row (row r's token depends on the drafts before it only): m + 1 twin passes; then one twin pass per corrupted draft."""
+    """o + m + 1 = 68 / 260 crosses a 64-row page boundary (and 256, the contiguous cache's growth step)."""
+    tail_pass_case(golden_dir, name, o, kind, tail_name, TAILS[tail_name], M_DRAFT)
+
+
+# The edges of a row's penalty window (row r at position o + r covers max(0, o + r + 1 - context) .. o + r), which the cases above do not
+# reach: a window of the row's own input alone, in the fewest rows a pass can have; one that begins at position 0 in every row of the
+# largest pass; and the largest window, full, in front of positions >= 1024.
+WINDOW_EDGES = {
+    "context=1, 2 rows": (60, 1, dict(sampler=("top_p", 0.8, 0.9, 0), repetition_penalty=1.3, context_size=1)),
+    "position + 1 < context, 32 rows": (60, 31, dict(repetition_penalty=1.3, context_size=100)),
+    "context=1024 at positions >= 1024": (1030, M_DRAFT, dict(repetition_penalty=1.3, context_size=1024)),
+}
+
+
+@pytest.mark.parametrize("edge", list(WINDOW_EDGES))
+def test_spec_step_tail_window_edges(golden_dir, knobs, edge):
+    o, m, tail = WINDOW_EDGES[edge]
+    if m + 1 < 6:
+        knobs("prefill_min", m + 1)                                          # the many-row pass from 2 rows on
+    tail_pass_case(golden_dir, "tiny_llama_w4_bf16", o, "contiguous", edge, tail, m)
+
+
+def tail_pass_case(golden_dir, name, o, kind, tail_name, tail, m):
+    """The agreeing continuation is built row by row (row r's token depends on the drafts before it only): m + 1 twin passes; then one
+    twin pass per corrupted draft."""
     from proxy_inference_engine_amd import hip_ops
     cfg, dt, orc, model = load_tiny(golden_dir, name)
-    V, m, tail = cfg["vocab_size"], M_DRAFT, TAILS[tail_name]
+    V = cfg["vocab_size"]
     draws = tail.get("sampler") is not None
     xtc = None if tail.get("xtc") is None else hip_ops.xtc_pack(*tail["xtc"])
-    prompt = [int(t) for t in np.random.default_rng(1000 * o + PASS_SEEDS[o]).integers(0, V, o)]
+    prompt = [int(t) for t in np.random.default_rng(1000 * o + PASS_SEEDS.get(o, 3)).integers(0, V, o)]
     ctx = tail.get("context_size", 60)
     try:
         # the prompt's own step: the last prompt row under the tail, drawn at C0
@@ -248,7 +271,7 @@ def test_spec_step_tail_equals_the_rows_alone_and_leaves_plain_steps_whole(golde
             if r < m:
                 good[r] = toks[r]
         assert toks[:m] == good                                             # the continuation agrees with itself
-        for corrupt in (0, 2, m - 1, None):
+        for corrupt in (*sorted({0, min(2, m - 1), m - 1}), None):
             what = f"{name} o={o} {kind} {tail_name} corrupt={corrupt}"
             draft = list(good)
             if corrupt is not None:
