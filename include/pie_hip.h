@@ -1166,7 +1166,8 @@ int pie_paged_attn_decode_i8(const void *q, const void *slab, size_t n_pages, co
  *   every row's position).  In order: the input ids gathered on the device (an id the embedding could not index is fed as 0); the
  *   several-prompts pass's body on the N rows with RoPE + append into each sequence's pages; pie_paged_attn_verify's launches once per
  *   layer; the lm_head over all N rows into the workspace; pie_spec_verify_rows with seq_ids / seq_len / seq_cap as its ids / len / cap.
- *   N <= 256 (one tile of the streaming GEMM) and N <= 8 B.  PIE_E_STATE before any launch, each by name: int8 pages, a
+ *   N <= 256 (one tile of the streaming GEMM) and N <= 8 B.  A decoder built with PIE_OPT_KV_I8 runs the pass on int8 pages: the append
+ *   quantises the pass's rows and the attention is pie_paged_attn_verify_i8's.  PIE_E_STATE before any launch, each by name: a
  *   tensor-parallel decoder, any configured batch tail, edits, counts, DRY, XTC, automaton or top-logprobs state, prompt scoring.
  *   Nothing is captured in a graph, and a decoder that never calls this entry launches exactly what it launches without it.
  *   workspace: pie_decoder_spec_batch_workspace_bytes(d) bytes, 16-byte aligned, no initialisation. */
@@ -1175,6 +1176,19 @@ size_t pie_paged_attn_verify_workspace_bytes(int N, int n_heads, int head_dim, i
 int pie_paged_attn_verify(const void *q, const void *slab, size_t n_pages, const int32_t *block_tables, int max_blocks, const int32_t *row_seq,
                           const int32_t *row_context_lens, const int32_t *seg_first, int N, int B, int n_heads, int n_kv_heads, int head_dim, float scale,
                           int dtype, int splits, void *out, void *workspace, void *stream);
+/* pie_paged_attn_verify on int8 pages: the same rows, index arrays, clamps, splits rule and error codes; slab = a layer's
+ * slab of PIE_I8 pages (pie_page_i8_bytes(n_kv_heads, head_dim) each: int8 K block, int8 V block, the fp16 per-head scales), slab_bytes
+ * its size -- fewer than n_pages such pages: PIE_E_SHAPE.  A code reads as fp32(code) * fp32(the page's scale of its head), fp32
+ * afterwards, one rounding to T at the end (pie_paged_attn_decode_i8's arithmetic).  One MFMA launch over (n_kv_heads, splits, B)
+ * workgroups -- a page's codes of a kv-head are read once for all rows and heads of the segment, converted to T once and multiplied on
+ * the matrix units with the scales folded into the fp32 scores and probabilities -- and pie_paged_attn_verify's merge launch when
+ * splits > 1.  A page behind every context of its segment is never addressed; codes at or behind the longest context are never used.
+ * splits 0 = pie_paged_attn_verify_i8_splits (a workgroup per CU); workspace: pie_paged_attn_verify_i8_workspace_bytes. */
+int pie_paged_attn_verify_i8_splits(int B, int n_kv_heads, int max_blocks);
+size_t pie_paged_attn_verify_i8_workspace_bytes(int N, int n_heads, int head_dim, int splits);
+int pie_paged_attn_verify_i8(const void *q, const void *slab, size_t n_pages, size_t slab_bytes, const int32_t *block_tables, int max_blocks,
+                             const int32_t *row_seq, const int32_t *row_context_lens, const int32_t *seg_first, int N, int B, int n_heads, int n_kv_heads,
+                             int head_dim, float scale, int dtype, int splits, void *out, void *workspace, void *stream);
 size_t pie_ngram_draft_rows_workspace_bytes(int B);
 int pie_ngram_draft_rows(const int32_t *ids, const int32_t *len, int B, int cap, int ngram_max, int ngram_min, int k, int32_t *out_ids, int32_t *out_count,
                          void *workspace, void *stream);

@@ -17,9 +17,11 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB_DIR = PKG / "lib"
 LIB = LIB_DIR / "libpie_hip.so"
-SOURCES = ["w4_gemv.hip", "ops.hip", "decoder.hip", "prefill.hip", "vision.hip", "w4m_gemm.hip", "tp_comm.hip", "sampler.hip", "top_logprobs.hip", "prompt_logprobs.hip", "speculative.hip", "paged_attn_verify.hip", "paged_i8.hip", "kv_quant.hip", "rotating.hip", "page_pool.cpp"]
+SOURCES = ["w4_gemv.hip", "ops.hip", "decoder.hip", "prefill.hip", "vision.hip", "w4m_gemm.hip", "tp_comm.hip", "sampler.hip", "top_logprobs.hip", "prompt_logprobs.hip", "speculative.hip", "paged_attn_verify.hip", "paged_attn_verify_i8.hip", "paged_i8.hip", "kv_quant.hip", "rotating.hip", "page_pool.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__"]
+# per source: paged_attn_verify_i8.hip's fp32 softmax is compiled without the packed fp32 VALU forms (v_pk_*_f32)
+SOURCE_FLAGS = {"paged_attn_verify_i8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -59,7 +61,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     def compile_one(src: str) -> Path:
         obj = obj_dir / (src + ".o")
         extra = [f'-DPIE_BUILD_HASH="{source_hash()}"'] if src == "decoder.hip" else []
-        cmd = [hipcc, *FLAGS, *extra, "-c", str(CSRC / src), "-o", str(obj)]
+        cmd = [hipcc, *FLAGS, *SOURCE_FLAGS.get(src, []), *extra, "-c", str(CSRC / src), "-o", str(obj)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr[-6000:]}")

@@ -277,6 +277,14 @@ int paged_attn_verify_splits(int B, int Hkv, int max_blocks) {
     return splits < 1 ? 1 : splits;
 }
 
+int verify_attn_merge_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st) {
+    const dim3 grid((unsigned)a.Hq, (unsigned)a.N);
+    if (dtype == PIE_BF16) hipLaunchKernelGGL(k_verify_attn_merge<BF16>, grid, dim3(64), 0, st, a, D);
+    else hipLaunchKernelGGL(k_verify_attn_merge<F16>, grid, dim3(64), 0, st, a, D);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
 int paged_attn_verify_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st) {
     if (dtype == PIE_BF16 && D == 128) return verify_attn_launch_rep<BF16, 128>(a, st);
     if (dtype == PIE_BF16 && D == 64) return verify_attn_launch_rep<BF16, 64>(a, st);

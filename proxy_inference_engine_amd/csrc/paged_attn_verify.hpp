@@ -25,3 +25,10 @@ struct VerifyAttnArgs {
 int paged_attn_verify_splits(int B, int Hkv, int max_blocks);
 // arguments already checked; D 64 / 128, Hq / Hkv 1..8
 int paged_attn_verify_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st);
+// k_verify_attn_merge's launch alone: out[row, head] from the a.splits partials of every (row, head), in split order
+int verify_attn_merge_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st);
+
+// The same pass on int8 pages (paged_attn_verify_i8.hip): a.slab is the layer's int8 slab (pie_page_i8_bytes per page), the
+// rest as above; the partials are merged by verify_attn_merge_launch.
+int paged_attn_verify_i8_splits(int B, int Hkv, int max_blocks);
+int paged_attn_verify_i8_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st);

@@ -1160,25 +1160,26 @@ extern "C" int pie_decoder_step_mixed(pie_decoder *d, const int32_t *ids, const 
 // ---------------------------------------------------------------- one speculative pass for B decode-state sequences
 // Sequence s presents 1 + m_s consecutive rows (segment s of seg_first): its fed token, then its drafts.  The pass is the several-prompts
 // pass's body on those N rows -- embed, linear_rows / mlp_rows, RoPE + append into each sequence's own pages -- with ONE attention launch
-// per layer for all segments (paged_attn_verify.hip) where that pass runs a segment kernel and a launch per chunk, the lm_head on ALL N
+// per layer for all segments (paged_attn_verify.hip; on int8 pages paged_attn_verify_i8.hip) where that pass runs a segment kernel and a launch per chunk, the lm_head on ALL N
 // rows (s->xn holds them final-normed, in row order: nothing to gather) and the segmented verify behind it.
 template <class T>
 static int spec_batch_t(pie_decoder *d, const int32_t *fed, const int32_t *row_ctx, const int32_t *row_seq, const int32_t *seg_first, int N, int B,
                         const void *const *slabs, int n_pages, const int32_t *block_tables, int max_blocks, u16 *logits, hipStream_t st) {
     const pie_decoder_config &c = d->cfg;
     const int D = c.head_dim;
-    const int splits = paged_attn_verify_splits(B, c.n_kv_heads, max_blocks);
+    // the page format picks the attention kernel, and with it the split count the scratch is sized for
+    const int splits = d->kv_i8 ? paged_attn_verify_i8_splits(B, c.n_kv_heads, max_blocks) : paged_attn_verify_splits(B, c.n_kv_heads, max_blocks);
     int rc = scratch_reserve(d, N, w16_copy_elems(c, true), splits > d->splits ? splits : d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
-    RowsKv kv;  // rows of a sequence share its block-table row; T pages only (the entry refuses int8 pages)
-    kv.row_ctx = row_ctx, kv.slabs = slabs, kv.block_tables = block_tables, kv.bt_stride = max_blocks, kv.n_pages = n_pages, kv.row_seq = row_seq;
+    RowsKv kv;  // rows of a sequence share its block-table row; its pages are T or int8 (the append then quantises the pass's rows)
+    kv.row_ctx = row_ctx, kv.slabs = slabs, kv.block_tables = block_tables, kv.bt_stride = max_blocks, kv.n_pages = n_pages, kv.row_seq = row_seq, kv.i8 = d->kv_i8;
     rc = paged_rows_layers<T>(d, fed, N, kv, st, [&](int li) {
         VerifyAttnArgs a = {};  // every row attends its sequence's pages, which now hold the pass's own rows
         a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.row_seq = row_seq, a.row_ctx = row_ctx, a.seg_first = seg_first;
         a.N = N, a.B = B, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.bt_stride = max_blocks, a.n_pages = n_pages, a.splits = splits;
         a.scale = 1.0f / sqrtf((float)D), a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
-        return paged_attn_verify_launch(c.dtype, D, a, st);
+        return d->kv_i8 ? paged_attn_verify_i8_launch(c.dtype, D, a, st) : paged_attn_verify_launch(c.dtype, D, a, st);
     });
     if (rc) return rc;
     return lm_head_rows<T>(d, s->xn, N, logits, st);
@@ -1196,13 +1197,12 @@ static int spec_batch_body(const std::string &who, bool with_tail, pie_decoder *
     PIE_REQUIRE((seq_ids == nullptr) == (seq_len == nullptr) && (seq_ids ? seq_cap >= 1 : seq_cap == 0), PIE_E_ARG,
                 who + "seq_ids [B, seq_cap >= 1] and seq_len come together or not at all");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
-    PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
     const char *part = with_tail ? d->rows.spec_tail_refused() : d->rows.spec_refused();
     PIE_REQUIRE(!part, PIE_E_STATE, who + "not available with " + part);
     PIE_REQUIRE(!d->prompt.n, PIE_E_STATE, who + "not available with prompt scoring");
     PIE_REQUIRE(!with_tail || d->rows.sampler.table, PIE_E_STATE, who + "no batch tail is set (the greedy and raw pass is pie_decoder_spec_step_batch)");
     const PoolRefusals shared = {d, who, slabs, n_pages, slab_bytes, max_blocks, B >= 1 && N >= B && N <= SPEC_BATCH_ROWS && N <= SPEC_SEG_ROWS * B && draft_stride >= 1,
-                                 "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool", "the slabs are smaller than n_pages T pages"};
+                                 "need 1 <= B <= N <= min(256, 8 B) rows, draft_stride >= 1 and a page pool", SLABS_BELOW_ACTIVE_FORMAT};
     if (int rc = shared.check(POOL_GLOBALS, POOL_SLAB_BYTES)) return rc;
     if (with_tail)  // record, ring, bias entries and XTC record s belong to sequence s: every configured part holds B of them
         if (int rc = d->rows.check_rows(B, "pie_decoder_spec_step_batch_tail")) return rc;

@@ -591,10 +591,12 @@ class BatchedEngine:
         min_p, min_tokens_to_keep, seed, XTC, repetition_penalty and logit_bias -- with `sampling` given the pass is
         Model.spec_step_batch_tail, which applies every seat's own record, ring, bias table and XTC record to the rows of its segment and
         accepts a draft while it equals the row's draw: the tokens are those the plain passes draw.  Still refused by name: a token mask,
-        a token automaton, frequency / presence penalties, DRY, logprobs, top_logprobs and prompt_logprobs."""
+        a token automaton, frequency / presence penalties, DRY, logprobs, top_logprobs and prompt_logprobs.
+        SpeculativeParams(int8_pages=True) admits kv_dtype=torch.int8: the passes then run on the int8 pages
+        (Model.spec_step_batch(..., int8_pages=True)); schedule, clamps, `spec_stats` and seats are the 16-bit pool's."""
         if speculative is not None:
             who = "BatchedEngine(speculative=...): "
-            for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8, "kv_dtype=torch.int8 (int8 KV pages)"),
+            for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8 and not getattr(speculative, "int8_pages", False), "kv_dtype=torch.int8 (int8 KV pages)"),
                               (getattr(model, "tp", None) is not None, "a tensor-parallel model"), (int(speculative.num_draft) > SPEC_SEG_DRAFTS, "num_draft > 7"),
                               (speculative.draft_model is not None, "draft_model"), (bool(speculative.grammar), "grammar"),
                               (bool(speculative.configured_tail), "configured_tail")):
@@ -759,7 +761,7 @@ class BatchedEngine:
         sp = self.speculative
         entry = self.model.spec_step_batch if seats.tails is None else self.model.spec_step_batch_tail   # (a tail: `sampling` was given under batch_tail)
         n, toks, nxt = entry(torch.cat([a.token for a in active]), [a.cache for a in active], spec.drafts, m, spec.ids, spec.len,
-                             then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts))
+                             then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts), **({"int8_pages": True} if self._i8 else {}))
         if seats.tails is not None:
             seats.moved(n)
         spec.moved(active, n)

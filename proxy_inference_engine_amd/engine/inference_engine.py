@@ -138,6 +138,10 @@ class SpeculativeParams:
     repetition penalty and a logit_bias: every seat's record, ring, bias table and XTC record are applied to the 1 + m_s rows of its
     segment inside the one pass (Model.spec_step_batch_tail), by the same point-mass rule.  A token mask, a token automaton, frequency /
     presence penalties, DRY and log-probabilities stay refused there.  InferenceEngine refuses batch_tail=True by name.
+    int8_pages: True -- BatchedEngine(kv_dtype=torch.int8, speculative=...) is admitted: the passes quantise their rows into
+    the int8 pages and attend them through the int8-page MFMA kernel (Model.spec_step_batch(..., int8_pages=True)); the tokens are those
+    of the same engine without `speculative`.  False -- an int8 pool is refused, as ever.  On a 16-bit pool the flag does nothing.
+    InferenceEngine, whose passes read 16-bit caches, refuses int8_pages=True by name.
     draft_model: None -- prompt-lookup drafts, as above.  A built `Model` of the target's vocabulary, or a checkpoint
     path (loaded once and kept on the engine) -- every round the draft model runs num_draft of its own replayed steps (num_draft =
     the target's spec_min_rows - 1 .. 31, so that the pass keeps its many-row form) and the target verifies them in one pass.  A greedy
@@ -159,6 +163,7 @@ class SpeculativeParams:
     min_draft: int = 5
     configured_tail: bool = False
     batch_tail: bool = field(default=False, kw_only=True)   # (keyword-only: the positional order of the fields around it stays as it was)
+    int8_pages: bool = field(default=False, kw_only=True)
     draft_model: object = None
     grammar: bool = False
 
@@ -179,6 +184,8 @@ class SpeculativeParams:
             raise ValueError("SpeculativeParams: grammar is a bool")
         if not isinstance(self.batch_tail, bool):
             raise ValueError("SpeculativeParams: batch_tail is a bool")
+        if not isinstance(self.int8_pages, bool):
+            raise ValueError("SpeculativeParams: int8_pages is a bool")
         if self.grammar and self.draft_model is not None:
             raise ValueError("SpeculativeParams: grammar is not available with a draft model")
 
@@ -305,6 +312,8 @@ def _check_generate_args(model, pixel_values, mask, kv_bits, kv_group_size, max_
     scored = prompt_logprobs is not None
     if speculative is not None and getattr(speculative, "batch_tail", False):
         raise ValueError("speculative decoding is not available with batch_tail (BatchedEngine's passes; the single sequence's is configured_tail)")
+    if speculative is not None and getattr(speculative, "int8_pages", False):
+        raise ValueError("speculative decoding is not available with int8_pages (BatchedEngine's passes; the single sequence's read 16-bit caches)")
     if speculative is not None and scored:
         raise ValueError("speculative decoding is not available with prompt_logprobs")
     if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:

@@ -711,9 +711,10 @@ class Model(RowsTailState, StepTailState):
         return hip_ops.ngram_draft_rows(seq_ids, seq_len, ngram_max, ngram_min, k, out=out)
 
     def spec_step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], drafts: torch.Tensor, counts, seq_ids: torch.Tensor | None = None,
-                        seq_len: torch.Tensor | None = None, then_draft: tuple | None = None):
+                        seq_len: torch.Tensor | None = None, then_draft: tuple | None = None, *, int8_pages: bool = False):
         """One speculative pass for several decode-state sequences (pie_decoder_spec_step_batch): tokens [B] = every sequence's
-        input token, caches as step_batch takes them (16-bit pages), drafts device int32 [>= B, >= the largest count] = row s's drafted ids, counts = the
+        input token, caches as step_batch takes them (16-bit pages; int8 pages with int8_pages=True, DESIGN.md 26: the pass's rows are
+        quantised with their pages' scales and attended through the int8-page MFMA kernel), drafts device int32 [>= B, >= the largest count] = row s's drafted ids, counts = the
         host's m_s for every sequence, 0..7 (the first m_s ids of its row are verified; their sum + B is at most 256).  Sequence s presents
         1 + m_s rows; its drafts are accepted while each equals the greedy token of the row before it.  Returns (n, tokens, next_counts):
         n[s] = accepted + 1, tokens[s] = the n[s] tokens greedy decoding would have produced (host lists), next_counts = None; every cache
@@ -722,12 +723,12 @@ class Model(RowsTailState, StepTailState):
         seq_ids int32 [>= B, cap] / seq_len int32 [>= B] (together): the sequences' ids, row s = sequence s, the last id being its input
         token -- the pass writes the chosen tokens behind it and moves seq_len on the device.  then_draft = (ngram_max, ngram_min, k,
         drafts_out): hip_ops.ngram_draft_rows over those rows is queued behind the pass, before the host reads anything, into drafts_out
-        [B, k], and next_counts are its counts, read back with the pass's one record.  Greedy and raw: int8 pages, tensor-parallel models
-        and any armed per-row state of the multi-sequence passes are refused by name."""
-        return self._spec_batch_pass("spec_step_batch", False, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft)
+        [B, k], and next_counts are its counts, read back with the pass's one record.  Greedy and raw: int8 pages without int8_pages=True,
+        tensor-parallel models and any armed per-row state of the multi-sequence passes are refused by name."""
+        return self._spec_batch_pass("spec_step_batch", False, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages)
 
     def spec_step_batch_tail(self, tokens: torch.Tensor, caches: list[list[BaseCache]], drafts: torch.Tensor, counts, seq_ids: torch.Tensor | None = None,
-                             seq_len: torch.Tensor | None = None, then_draft: tuple | None = None):
+                             seq_len: torch.Tensor | None = None, then_draft: tuple | None = None, *, int8_pages: bool = False):
         """spec_step_batch under the sequences' own samplers, repetition penalties and logit biases (pie_decoder_spec_step_batch_tail;
         DESIGN.md 25): the same arguments and returns.  Needs set_batch_tail armed; record, ring, bias table (set_batch_edits' bias part)
         and XTC record (set_batch_xtc) s belong to sequence s, as in step_batch.  Row j of sequence s is edited with its seat's penalty over
@@ -735,12 +736,12 @@ class Model(RowsTailState, StepTailState):
         is accepted while it equals the draw, so tokens[s] are the n[s] tokens that many step_batch calls would have produced.  Afterwards
         the seat's `calls` and ring stand where those steps would have left them, on the device.  `spec_batch_last` additionally holds
         "logprobs" fp32 [N, V] (every row's processed log-probabilities), "logits" [N, V] (the processed block, a view of the workspace,
-        valid until the next pass) and "seg_first" int32 [B + 1].  Refused by name, before anything moves: int8 pages, tensor-parallel
+        valid until the next pass) and "seg_first" int32 [B + 1].  Refused by name, before anything moves: int8 pages without int8_pages=True, tensor-parallel
         models, a mask part of the batch edits, batch token automata, a batch count penalty, a batch DRY penalty, batch top log-probabilities
         and prompt scoring."""
-        return self._spec_batch_pass("spec_step_batch_tail", True, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft)
+        return self._spec_batch_pass("spec_step_batch_tail", True, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages)
 
-    def _spec_batch_pass(self, who: str, tail: bool, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft):
+    def _spec_batch_pass(self, who: str, tail: bool, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages=False):
         """spec_step_batch's and spec_step_batch_tail's body: the refusals, the index arrays, the entry's call and the one read-back."""
         import numpy as np
         seqs = self._kv.sequences(who, caches)
@@ -748,7 +749,7 @@ class Model(RowsTailState, StepTailState):
         a = seqs[0].allocator
         if self.tp is not None:
             raise ValueError(f"{who}: not available on a tensor-parallel model")
-        if a.dtype == torch.int8:
+        if a.dtype == torch.int8 and not int8_pages:   # (opt-in: DESIGN.md 26)
             raise ValueError(f"{who}: not available on int8 KV pages")
         if tail:
             if self._batch_tail is None:

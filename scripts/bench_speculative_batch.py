@@ -19,6 +19,11 @@ break_even = pass_ms / step_sync_ms: the tokens per sequence a pass must yield t
 
     python scripts/bench_speculative_batch.py --context 512 [--batches 2,8,32] [--drafts 3,7] [--accepts 0,2] [--reps 5] [--window 16] [--out FILE]
     python scripts/bench_speculative_batch.py --all [--contexts 512,8192] [--limit 900] --out FILE    # one fresh process per context, each under its own time limit
+--int8: the pool holds int8 pages (random codes, every scale 1/32), the pass is Model.spec_step_batch(int8_pages=True) and the
+steps are the int8 step_batch; attn_us is hip_ops.paged_attn_verify_i8, and "attn_T" the T-page hip_ops.paged_attn_verify on the same shapes
+over a 16-bit slab of its own.  Both attention rows carry kv_bytes (the K / V bytes the shapes need: B x kv-heads x context x head_dim x 2 x
+the element size) over the measured time as kv_gb_per_s and its share of HBM_GB_PER_S.  No mixed rows: a prompt continuing a cached prefix
+reads T pages.
 """
 import argparse
 import json
@@ -31,16 +36,17 @@ from pathlib import Path
 import torch
 
 ROOT = Path(__file__).resolve().parents[1]
+HBM_GB_PER_S = 8000.0   # the MI355X data sheet's peak HBM3E bandwidth, the denominator of hbm_share
 sys.path.insert(0, str(ROOT))
 
 
 def run_all(args):
     """One fresh child per context under its own time limit; the first one that fails or runs out of time ends the run."""
-    merged = {"model": "llama3-8b int4 g64 bf16 (synthetic weights, synthetic cache)", "reps": args.reps, "window": args.window, "contexts": {}}
+    merged = {"model": "llama3-8b int4 g64 bf16 (synthetic weights, synthetic cache)" + (", int8 KV pages" if args.int8 else ""), "reps": args.reps, "window": args.window, "contexts": {}}
     for ctx in [int(x) for x in args.contexts.split(",") if x]:
         part = Path(args.out).with_suffix(f".ctx{ctx}.json")
         cmd = [sys.executable, __file__, "--context", str(ctx), "--batches", args.batches, "--drafts", args.drafts, "--accepts", args.accepts, "--reps", str(args.reps),
-               "--window", str(args.window), "--out", str(part)]
+               "--window", str(args.window), "--out", str(part)] + (["--int8"] if args.int8 else []) + (["--layers", str(args.layers)] if args.layers else [])
         rc = subprocess.run(cmd, timeout=args.limit).returncode
         if rc != 0:
             print(json.dumps({"context": ctx, "failed": rc}), flush=True)
@@ -64,6 +70,7 @@ def main():
     ap.add_argument("--window", type=int, default=16)
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--int8", action="store_true")
     args = ap.parse_args()
     if args.all:
         sys.exit(run_all(args))
@@ -80,8 +87,18 @@ def main():
     batches = [int(x) for x in args.batches.split(",") if x]
     drafts = [int(x) for x in args.drafts.split(",") if x]
     blocks = (o + 64 + 63) // 64 + 1
-    pool = model.enable_paged_kv(num_pages=max(batches) * blocks + 8, max_blocks=blocks)
-    pool.slab.view(torch.bfloat16).normal_(0.0, 0.5)                   # the synthetic cache (the slab is raw bytes)
+    Hq, Hkv, D = cfg["num_attention_heads"], cfg["num_key_value_heads"], cfg["hidden_size"] // cfg["num_attention_heads"]
+    spec_kw = {"int8_pages": True} if args.int8 else {}
+    if args.int8:
+        ones = torch.full((cfg["num_hidden_layers"], Hkv), 1 / 32, dtype=torch.float16)
+        pool = model.enable_paged_kv(num_pages=max(batches) * blocks + 8, max_blocks=blocks, kv_dtype=torch.int8, kv_scales=(ones, ones))
+        pages = pool.slab.view(torch.int8).view(-1, pool.page_bytes)   # the synthetic cache: random codes, the scales behind them untouched
+        for layer in pages.view(cfg["num_hidden_layers"], -1, pool.page_bytes):   # (a layer at a time: the generator's scratch stays small)
+            layer[:, :2 * Hkv * 64 * D] = torch.randint(-48, 49, (layer.shape[0], 2 * Hkv * 64 * D), dtype=torch.int8, device=layer.device)
+        t_slab = torch.empty((pool.size(), 2, Hkv, 64, D), dtype=torch.bfloat16, device="cuda").normal_(0.0, 0.5)   # for the T-page kernel alone
+    else:
+        pool = model.enable_paged_kv(num_pages=max(batches) * blocks + 8, max_blocks=blocks)
+        pool.slab.view(torch.bfloat16).normal_(0.0, 0.5)               # the synthetic cache (the slab is raw bytes)
     g = torch.Generator().manual_seed(1)
     results = []
     for B in batches:
@@ -110,7 +127,7 @@ def main():
             if m not in full:
                 d = torch.tensor([c[1:m + 1] for c in cont], dtype=torch.int32, device="cuda")
                 for _ in range(m + 1):
-                    n, toks, _ = model.spec_step_batch(first, caches, d, [m] * B)
+                    n, toks, _ = model.spec_step_batch(first, caches, d, [m] * B, **spec_kw)
                     rewind()
                     if all(k == m + 1 for k in n):
                         break
@@ -138,7 +155,7 @@ def main():
                 for _ in range(args.window):
                     rewind()
                     seq_len.fill_(o + 1)
-                    n = model.spec_step_batch(first, caches, d, [m] * B, seq_ids, seq_len, then_draft=(3, 1, max(drafts), nxt_drafts))[0]
+                    n = model.spec_step_batch(first, caches, d, [m] * B, seq_ids, seq_len, then_draft=(3, 1, max(drafts), nxt_drafts), **spec_kw)[0]
                     seen[name].update(n)
                 rewind()
             return run
@@ -164,8 +181,7 @@ def main():
                 rewind()
             return run
 
-        def attn_window(m):
-            Hq, Hkv, D = cfg["num_attention_heads"], cfg["num_key_value_heads"], cfg["hidden_size"] // cfg["num_attention_heads"]
+        def attn_window(m, t_pages=False):
             for s in seqs:
                 s.reserve(m + 1)
             table = torch.zeros((B, blocks), dtype=torch.int32)
@@ -179,13 +195,19 @@ def main():
 
             def run():
                 for _ in range(args.window):
-                    hip_ops.paged_attn_verify(q, pool.slab[0], pool.size(), *idx, Hkv, D ** -0.5)
+                    if args.int8 and not t_pages:
+                        hip_ops.paged_attn_verify_i8(q, pool.slab[0], pool.size(), *idx, Hkv, D ** -0.5)
+                    else:
+                        hip_ops.paged_attn_verify(q, t_slab if args.int8 else pool.slab[0], pool.size(), *idx, Hkv, D ** -0.5)
             return run
 
         windows = {"step": step_window(False), "step_sync": step_window(True)}
         for m in drafts:
-            windows[f"mixed m={m}"] = mixed_window(m)
+            if not args.int8:
+                windows[f"mixed m={m}"] = mixed_window(m)
             windows[f"attn m={m}"] = attn_window(m)
+            if args.int8:
+                windows[f"attn_T m={m}"] = attn_window(m, True)
             for a in sorted({int(x) for x in args.accepts.split(",") if x and int(x) < m} | {m}):
                 windows[f"pass m={m} a={a}"] = pass_window(m, a)
         ms = {k: [] for k in windows}
@@ -207,6 +229,9 @@ def main():
                            aggregate_tokens_per_s=round(B * (a + 1) / med[name] * 1e3, 1))
             elif name.startswith("step"):
                 row["aggregate_tokens_per_s"] = round(B / med[name] * 1e3, 1)
+            elif name.startswith("attn"):
+                kv_bytes = B * Hkv * o * D * 2 * (1 if args.int8 and not name.startswith("attn_T") else 2)
+                row.update(kv_bytes=kv_bytes, kv_gb_per_s=round(kv_bytes / med[name] / 1e6, 1), hbm_share=round(kv_bytes / med[name] / 1e6 / HBM_GB_PER_S, 4))
             results.append(row)
             print(json.dumps(row), flush=True)
         for s in seqs:
