@@ -1189,6 +1189,18 @@ size_t pie_paged_attn_verify_i8_workspace_bytes(int N, int n_heads, int head_dim
 int pie_paged_attn_verify_i8(const void *q, const void *slab, size_t n_pages, size_t slab_bytes, const int32_t *block_tables, int max_blocks,
                              const int32_t *row_seq, const int32_t *row_context_lens, const int32_t *seg_first, int N, int B, int n_heads, int n_kv_heads,
                              int head_dim, float scale, int dtype, int splits, void *out, void *workspace, void *stream);
+/* Causal attention of prompt chunks that continue a cached prefix, on int8 pages: what pie_decoder_step_mixed launches per
+ * layer for its chunks when the decoder has PIE_OPT_KV_I8.  q / out DEVICE [N, n_heads, head_dim]; slab / n_pages / slab_bytes as
+ * pie_paged_attn_verify_i8 takes them; block_tables DEVICE int32 [n_seqs, max_blocks]; chunks_host HOST int32 [n_chunks][4] =
+ * {first row, rows M, cached positions P >= 1, block-table row}: row r of a chunk sits at position P + r and attends keys 0 .. P + r of
+ * its sequence's pages, which hold the chunk's own rows already (as codes).  pie_paged_attn_decode_i8's arithmetic; only the chunks' rows
+ * of `out` are written.  One MFMA launch per 32 chunks: the descriptors ride in the kernel arguments, nothing is copied to the device and
+ * the host does not wait.  A table entry is clamped to n_pages - 1; a page behind every row of a query tile is never addressed.
+ * PIE_E_SHAPE by name: a slab below n_pages int8 pages, head_dim other than 64 / 128, n_heads not 1..8 times n_kv_heads, and a chunk
+ * outside [0, N), outside its block table or with sequence >= n_seqs (pie_decoder_step_mixed's chunk checks). */
+int pie_prefill_attn_i8(const void *q, const void *slab, size_t n_pages, size_t slab_bytes, const int32_t *block_tables, int n_seqs, int max_blocks,
+                        const int32_t *chunks_host, int n_chunks, int N, int n_heads, int n_kv_heads, int head_dim, int dtype, float scale, void *out,
+                        void *stream);
 size_t pie_ngram_draft_rows_workspace_bytes(int B);
 int pie_ngram_draft_rows(const int32_t *ids, const int32_t *len, int B, int cap, int ngram_max, int ngram_min, int k, int32_t *out_ids, int32_t *out_count,
                          void *workspace, void *stream);

@@ -64,6 +64,7 @@ EXPORTS = [
     "pie_paged_attn_verify_i8_workspace_bytes", "pie_paged_attn_verify_i8", "pie_ngram_draft_rows_workspace_bytes", "pie_ngram_draft_rows",
     "pie_spec_verify_rows_workspace_bytes", "pie_spec_verify_rows", "pie_decoder_spec_batch_workspace_bytes", "pie_decoder_spec_step_batch",
     "pie_spec_verify_rows_sampled_workspace_bytes", "pie_spec_verify_rows_sampled", "pie_decoder_spec_batch_tail_workspace_bytes", "pie_decoder_spec_step_batch_tail",
+    "pie_prefill_attn_i8",
 ]
 
 
@@ -258,7 +259,8 @@ def load() -> C.CDLL:
     lib.pie_paged_attn_verify_i8_splits.argtypes = [C.c_int] * 3
     lib.pie_paged_attn_verify_i8_workspace_bytes.restype = C.c_size_t
     lib.pie_paged_attn_verify_i8_workspace_bytes.argtypes = [C.c_int] * 4
-    lib.pie_paged_attn_verify_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.pie_prefill_attn_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
+    lib.pie_paged_attn_verify_i8.argtypes =[C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.pie_ngram_draft_rows_workspace_bytes.restype = C.c_size_t
     lib.pie_ngram_draft_rows_workspace_bytes.argtypes = [C.c_int]
     lib.pie_ngram_draft_rows.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4

@@ -21,6 +21,7 @@
 #include "decoder.hpp"
 #include "gemm_rows.hpp"  // the many-row GEMM family of w4m_gemm.hip: W4mRope, W4lSlabs, the int4 entry (prefill_attn.hpp comes with it)
 #include "paged_attn_verify.hpp"
+#include "prefill_attn_i8.hpp"
 #include "speculative.hpp"
 
 // ---------------------------------------------------------------- kernels
@@ -1050,6 +1051,12 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
         int rc = segment_attn_gqa_launch_t<T>(pa, D, st);
         // the decode-state rows attend to their pages (which hold the row just appended)
         if (!rc && n_decode > 0) rc = paged_decode_attn(d, li, n_decode, dsplits, kv, st);
+        if (!rc && n_chunks > 0 && d->kv_i8) {  // ... on int8 pages: ONE launch per 32 chunks (prefill_attn_i8.hip)
+            PrefillI8Args ia = {};
+            ia.q = s->q, ia.slab = slabs[li], ia.block_tables = block_tables, ia.out = s->attn;
+            ia.Hq = c.n_heads, ia.Hkv = c.n_kv_heads, ia.bt_stride = max_blocks, ia.n_pages = n_pages, ia.scale = pa.scale;
+            return prefill_attn_i8_launch(c.dtype, D, ia, chunks, n_chunks, st);
+        }
         for (int ci = 0; ci < n_chunks && !rc; ++ci) {  // prompts continuing a cached prefix: causal attention over their pages from the cached length
             const int32_t *ch = chunks + 4 * ci;
             PrefillAttnArgs ca = {};
@@ -1118,7 +1125,6 @@ static int varlen_batch(pie_decoder *d, const int32_t *ids, const int32_t *row_c
     PIE_REQUIRE(d && ids && row_context_lens && row_seq && seg_lo && seg_hi && last_rows && slabs && block_tables && logits && logprobs && next_tokens,
                 PIE_E_ARG, "pie_decoder_prefill_batch / _step_mixed: null pointer");
     PIE_REQUIRE(n_chunks >= 0 && (n_chunks == 0 || chunks), PIE_E_ARG, "pie_decoder_step_mixed: chunks without their descriptor array");
-    PIE_REQUIRE(n_chunks == 0 || !d->kv_i8, PIE_E_STATE, "pie_decoder_step_mixed: a prompt continuing a cached prefix reads T pages (int8 pages: fresh prompts and decode rows only)");
     for (int ci = 0; ci < n_chunks; ++ci) {
         const int32_t *ch = chunks + 4 * ci;
         PIE_REQUIRE(ch[0] >= n_decode && ch[1] >= 1 && ch[0] + ch[1] <= N && ch[2] >= 1 && ch[3] >= 0 && ch[3] < S &&

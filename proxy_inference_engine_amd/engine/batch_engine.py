@@ -11,7 +11,8 @@ its own `SamplingParams`, run per row inside the passes -- its to
 frequency and presence penalties over the counts of what it has generated (DESIGN.md 15);
 `sampler` maps a [B, V] log-probability block to B token ids;
 `generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes (DESIGN.md 13);
-`generate(prompt_logprobs=...)` also returns the log-probabilities of the prompts' own tokens, scored inside the prompt passes."""
+`generate(prompt_logprobs=...)` also returns the log-probabilities of the prompts' own tokens, scored inside the prompt passes (DESIGN.md 16);
+`BatchedEngine(kv_dtype=torch.int8, int8_chunks=True)` keeps chunked prefill and shared prefixes on an int8 pool."""
 from __future__ import annotations
 
 from collections import deque
@@ -576,7 +577,7 @@ class BatchedEngine:
     def __init__(self, model, num_pages: int = 1024, max_batch: int = 32, stop_tokens: Iterable[int] = (),
                  sampler: Callable[[torch.Tensor], torch.Tensor] | None = None, batch_prefill: bool = True, max_prefill_rows: int = 4096,
                  kv_dtype: torch.dtype | None = None, kv_scales=None, mixed: bool = True, prefill_chunk: int | None = None, share_prefix: bool = False,
-                 speculative=None):
+                 speculative=None, *, int8_chunks: bool = False):
         """kv_dtype=torch.int8 (+ kv_scales = (k, v) float16 [n_layers, n_kv_heads]): the pool holds the reference KVPage's int8 pages with
         per-head scales (page.hpp:25-32) -- half the cache bytes per token, so twice the sequences / context per pool.
         speculative=SpeculativeParams(num_draft=, ngram_max=, ngram_min=, min_draft=): greedy prompt-lookup speculation for
@@ -593,7 +594,12 @@ class BatchedEngine:
         accepts a draft while it equals the row's draw: the tokens are those the plain passes draw.  Still refused by name: a token mask,
         a token automaton, frequency / presence penalties, DRY, logprobs, top_logprobs and prompt_logprobs.
         SpeculativeParams(int8_pages=True) admits kv_dtype=torch.int8: the passes then run on the int8 pages
-        (Model.spec_step_batch(..., int8_pages=True)); schedule, clamps, `spec_stats` and seats are the 16-bit pool's."""
+        (Model.spec_step_batch(..., int8_pages=True)); schedule, clamps, `spec_stats` and seats are the 16-bit pool's.
+        int8_chunks=True keeps prefill_chunk and share_prefix as given on a kv_dtype=torch.int8 pool, where they are
+        otherwise switched off: the passes that carry prompt rows are then Model.step_mixed(..., int8_pages=True).  A prompt's first chunk
+        (and the shared prefix) attends its own rows unquantised, as a whole prompt on int8 pages does; every later chunk and every suffix
+        attends its own rows as codes, as a decode step does -- so the tokens agree with the unchunked int8 engine's within the int8-page
+        bound, not bit for bit.  On a 16-bit pool the flag does nothing; tensor-parallel models stay refused as they are."""
         if speculative is not None:
             who = "BatchedEngine(speculative=...): "
             for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8 and not getattr(speculative, "int8_pages", False), "kv_dtype=torch.int8 (int8 KV pages)"),
@@ -607,6 +613,7 @@ class BatchedEngine:
         self.model = model
         self.pool = model.enable_paged_kv(num_pages=num_pages, kv_dtype=kv_dtype, kv_scales=kv_scales)
         self._i8 = self.pool.dtype == torch.int8   # int8 pages are written by the batch paths only: lone prompts go through prefill_batch too
+        self._i8_chunks = self._i8 and bool(int8_chunks)   # continuing prompts on int8 pages: step_mixed is told so, and only then
         self.max_batch = max_batch
         self.stop_tokens = set(int(t) for t in stop_tokens)
         self.sampler = sampler
@@ -614,12 +621,12 @@ class BatchedEngine:
         self.max_prefill_rows = max_prefill_rows    # prompt tokens per such pass
         self.mixed = mixed            # prompts admitted while sequences are decoding join THAT pass (Model.step_mixed) instead of a pass of their own
         # chunked prefill: an admitted prompt is fed at most this many rows per pass (all filling prompts together), every pass also decoding the
-        # sequences in flight -- a long prompt no longer stalls them for its whole length.  T pages only (a continuing prompt reads T pages).
-        self.prefill_chunk = None if (prefill_chunk is None or self._i8) else max(1, int(prefill_chunk))
+        # sequences in flight -- a long prompt no longer stalls them for its whole length.  T pages, or int8 pages with int8_chunks=True.
+        self.prefill_chunk = None if (prefill_chunk is None or (self._i8 and not self._i8_chunks)) else max(1, int(prefill_chunk))
         # shared prompt prefix (a system prompt): the whole pages of the requests' longest common prefix are computed ONCE and shared by
         # reference count (KVPage::add_ref, page.hpp:55-68 -- PagedSequence.fork); every request then feeds only its own suffix, as a prompt
-        # continuing a cached prefix.  T pages only.
-        self.share_prefix = bool(share_prefix) and not self._i8
+        # continuing a cached prefix.  T pages, or int8 pages with int8_chunks=True.
+        self.share_prefix = bool(share_prefix) and (not self._i8 or self._i8_chunks)
         self.shared_pages = 0         # pages of the last generate()'s shared prefix
         self.steps = 0                # batched decode steps taken (for throughput accounting)
         self.mixed_passes = 0         # ... of which carried prompt rows as well
@@ -718,7 +725,7 @@ class BatchedEngine:
             elif not active and not self.prefill_chunk and P == 0:          # fresh whole prompts alone (int8 pages take prompts through this entry only)
                 nxt, logprobs, _ = self.model.prefill_batch(rows, into)
             else:
-                nxt, logprobs, _ = self.model.step_mixed(tokens, caches, rows, into)
+                nxt, logprobs, _ = self.model.step_mixed(tokens, caches, rows, into, **({"int8_pages": True} if self._i8_chunks else {}))
         self.steps += bool(active or self.prefill_chunk)                     # a decode step, or the chunked pass (which stands for one)
         self.mixed_passes += bool(active and parts)
         if self.sampler is not None:

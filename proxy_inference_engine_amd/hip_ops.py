@@ -1593,6 +1593,27 @@ def paged_attn_verify_i8(q: torch.Tensor, slab: torch.Tensor, n_pages: int, bloc
     return out
 
 
+def prefill_attn_i8(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_tables: torch.Tensor, chunks, n_kv_heads: int, scale: float) -> torch.Tensor:
+    """Causal attention of prompt chunks that continue a cached prefix, on int8 pages (pie_prefill_attn_i8): q [N, Hq, D],
+    slab = a layer's slab of int8 pages with their per-head fp16 scales, block_tables int32 [n_seqs, max_blocks], chunks = HOST rows of
+    {first row, rows M, cached positions P >= 1, block-table row}.  Row r of a chunk attends keys 0 .. P + r of its sequence's pages,
+    which hold the chunk's own rows already, as codes.  One MFMA launch per 32 chunks.  Returns [N, Hq, D]: rows outside every chunk are zero."""
+    import numpy as np
+    for t in (q, slab, block_tables):
+        _dev(t)
+    if block_tables.dtype != torch.int32:
+        raise TypeError("prefill_attn_i8: block_tables must be int32")
+    if q.dim() != 3 or block_tables.dim() != 2:
+        raise ValueError("prefill_attn_i8: q [N, Hq, D]; block_tables [n_seqs, max_blocks]")
+    ch = np.ascontiguousarray(np.asarray(chunks, dtype=np.int32).reshape(-1, 4))
+    N, Hq, D = q.shape
+    out = torch.zeros_like(q)
+    _ffi.check(_ffi.load().pie_prefill_attn_i8(_ffi.p(q), _ffi.p(slab), n_pages, slab.numel() * slab.element_size(), _ffi.p(block_tables), block_tables.shape[0],
+                                               block_tables.shape[1], ch.ctypes.data, len(ch), N, Hq, int(n_kv_heads), D, _ffi.dtype_code(q.dtype), float(scale),
+                                               _ffi.p(out), _ffi.stream()))
+    return out
+
+
 def ngram_draft_rows_workspace(device, B: int) -> torch.Tensor:
     """pie_ngram_draft_rows' workspace for B sequences on `device`: uninitialised, nothing is carried from call to call."""
     return _workspace("pie_ngram_draft_rows_workspace_bytes", False, "ngram_draft_rows", f"1 <= B <= 4096, got {B}", device, B).view(torch.int32)

@@ -886,16 +886,22 @@ class Model(RowsTailState, StepTailState):
         prompts' last positions; every cache then holds its prompt."""
         return self._varlen_pass("prefill_batch", None, [], prompts, caches)
 
-    def step_mixed(self, tokens: torch.Tensor | None, decode_caches: list[list[BaseCache]], prompts: list, prompt_caches: list[list[BaseCache]]):
+    def step_mixed(self, tokens: torch.Tensor | None, decode_caches: list[list[BaseCache]], prompts: list, prompt_caches: list[list[BaseCache]], *,
+                   int8_pages: bool = False):
         """Decode-state sequences AND fresh prompts in one pass over the weights (pie_decoder_step_mixed; the reference's BatchDetails holds
         both kinds, batch_details.hpp:10-88): tokens [B] = the input token of each decoding sequence (caches as in step_batch), prompts /
         prompt_caches as in prefill_batch -- or caches that already hold a PREFIX (offset > 0: the next chunk of a long prompt, or a suffix
         behind shared prefix pages of a forked sequence): such rows attend to the sequence's pages from that offset.  Returns (next_tokens [B + S], logprobs [B + S, V], logits [B + S, V]): the decoding sequences
         first, then every prompt's last position; the decode caches advance by one position, the prompt caches hold their prompts.
-        Every row rides the many-row regime of the Linears (as the rows of a prompt do), also when B alone would take the few-row one."""
-        return self._varlen_pass("step_mixed", tokens, decode_caches, prompts, prompt_caches)
+        Every row rides the many-row regime of the Linears (as the rows of a prompt do), also when B alone would take the few-row one.
+        int8_pages=True admits a prompt cache with offset > 0 on an int8 pool: its rows are quantised into their pages and
+        attend the sequence's pages -- their own rows included -- as codes, the way a decode step does (one MFMA launch per layer for all
+        such prompts), where a FRESH whole prompt on an int8 pool attends its own rows unquantised.  So a chunked or prefix-shared prompt
+        agrees with the whole prompt within the int8-page bound, not bit for bit.  Without the flag such a cache is refused on an int8
+        pool, as ever; on a 16-bit pool the flag does nothing."""
+        return self._varlen_pass("step_mixed", tokens, decode_caches, prompts, prompt_caches, int8_pages)
 
-    def _varlen_pass(self, who: str, tokens, decode_caches, prompts, caches):
+    def _varlen_pass(self, who: str, tokens, decode_caches, prompts, caches, int8_pages: bool = False):
         import numpy as np
         every = self._kv.sequences(who, list(decode_caches) + list(caches))
         B = len(decode_caches)
@@ -915,7 +921,7 @@ class Model(RowsTailState, StepTailState):
         if (lens and min(lens) < 1) or B + sum(lens) > 65535:
             raise ValueError(f"{who}: prompts must be non-empty and the pass holds at most 65535 rows")
         cached = [int(s.offset) for s in seqs]      # > 0: the prompt continues a cached prefix (a chunk of a long prompt, a suffix behind shared pages)
-        if any(cached) and a.dtype == torch.int8:
+        if any(cached) and a.dtype == torch.int8 and not int8_pages:   # (opt-in: DESIGN.md 27)
             raise ValueError(f"{who}: a prompt that continues a cached prefix reads T pages (int8 pools: fresh prompts and decoding rows)")
         for s in dseqs:
             s.reserve(1)
