@@ -1017,12 +1017,14 @@ size_t pie_decoder_kernel_bytes(const pie_decoder *d, int which, int T);
 size_t pie_decoder_step_bytes(const pie_decoder *d, int T, int with_logits);
 /* Decoder options.  PIE_OPT_KV_I8 = 1: the slabs handed to pie_decoder_step_batch / pie_decoder_prefill_batch hold int8 pages (PIE_I8 pools,
  * pie_paged_*_i8 below): new rows are quantised with their page's scales, the step's attention reads them back.  Changing an option drops the
- * captured graphs.  pie_decoder_status: synchronises the device and reports a give-up of a bounded wait of the tensor-parallel collectives in
+ * captured graphs.  PIE_OPT_VERIFY_MFMA = 3 (default 0): while set, and the decoder is on T pages, pie_decoder_spec_step_batch and
+ * pie_decoder_spec_step_batch_tail take their split count from pie_paged_attn_verify_mfma_splits and attend through pie_paged_attn_verify_mfma's
+ * kernel; with PIE_OPT_KV_I8 it does nothing, nothing else reads it, and no graph is dropped.  pie_decoder_status: synchronises the device and reports a give-up of a bounded wait of the tensor-parallel collectives in
  * *error (0 = none; sticky; that step's token is -1); bit 31: the fused q|k|v + attention launch (32 / 8 / 128 head geometry, PIE_KNOB_FUSE_ATTN) gave up
  * waiting for its kv-group (the producers of a group must get dispatched while its <= 128 attention workgroups spin: guaranteed for up to five such
  * launches in flight on a full device; the library fuses only while a process holds at most four decoders; a process that masks CUs sets
  * PIE_KNOB_FUSE_ATTN = 0).  Results after a give-up are not valid. */
-enum { PIE_OPT_KV_I8 = 2 };
+enum { PIE_OPT_KV_I8 = 2, PIE_OPT_VERIFY_MFMA = 3 };
 int pie_decoder_configure(pie_decoder *d, int option, int value);
 int pie_decoder_status(pie_decoder *d, unsigned *error);
 
@@ -1201,6 +1203,15 @@ int pie_paged_attn_verify_i8(const void *q, const void *slab, size_t n_pages, si
 int pie_prefill_attn_i8(const void *q, const void *slab, size_t n_pages, size_t slab_bytes, const int32_t *block_tables, int n_seqs, int max_blocks,
                         const int32_t *chunks_host, int n_chunks, int N, int n_heads, int n_kv_heads, int head_dim, int dtype, float scale, void *out,
                         void *stream);
+/* pie_paged_attn_verify on the MFMA units: the same T pages, arguments, index arrays, clamps, checks and error codes, and
+ * pie_paged_attn_verify_workspace_bytes for the workspace.  One launch over (n_kv_heads, splits, B) workgroups -- the segment's (row, head)
+ * pairs are one or two 32-column operands of v_mfma_f32_32x32x16, a page's K and V rows of a kv-head are read once for all of them -- and
+ * pie_paged_attn_verify's merge launch when splits > 1.  A page behind every context of its segment is never addressed; positions at or
+ * behind the longest context are never used.  splits 0 = pie_paged_attn_verify_mfma_splits (two workgroups per CU). */
+int pie_paged_attn_verify_mfma_splits(int B, int n_kv_heads, int max_blocks);
+int pie_paged_attn_verify_mfma(const void *q, const void *slab, size_t n_pages, const int32_t *block_tables, int max_blocks, const int32_t *row_seq,
+                               const int32_t *row_context_lens, const int32_t *seg_first, int N, int B, int n_heads, int n_kv_heads, int head_dim, float scale,
+                               int dtype, int splits, void *out, void *workspace, void *stream);
 size_t pie_ngram_draft_rows_workspace_bytes(int B);
 int pie_ngram_draft_rows(const int32_t *ids, const int32_t *len, int B, int cap, int ngram_max, int ngram_min, int k, int32_t *out_ids, int32_t *out_count,
                          void *workspace, void *stream);

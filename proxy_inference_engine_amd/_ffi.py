@@ -15,6 +15,7 @@ _PKG = Path(__file__).resolve().parent
 PIE_BF16, PIE_F16 = 1, 2
 PIE_STEP_LOGITS, PIE_STEP_GRAPH = 1, 2
 PIE_OPT_KV_I8 = 2
+PIE_OPT_VERIFY_MFMA = 3
 PIE_SAMPLE_GREEDY = -1  # pie_decoder_set_sampler: the greedy tail
 PIE_TOP_LOGPROBS_MAX = 20  # pie_top_logprobs: the largest n
 # test / tuning switches (include/pie_hip.h: pie_set_knob); -1 restores a default
@@ -61,7 +62,8 @@ EXPORTS = [
     "pie_spec_verify_draft_workspace_bytes", "pie_spec_verify_draft", "pie_decoder_spec_draft_workspace_bytes", "pie_decoder_spec_step_draft",
     "pie_token_dfa_walk", "pie_token_dfa_draft", "pie_decoder_spec_dfa_workspace_bytes", "pie_decoder_spec_step_dfa",
     "pie_paged_attn_verify_splits", "pie_paged_attn_verify_workspace_bytes", "pie_paged_attn_verify", "pie_paged_attn_verify_i8_splits",
-    "pie_paged_attn_verify_i8_workspace_bytes", "pie_paged_attn_verify_i8", "pie_ngram_draft_rows_workspace_bytes", "pie_ngram_draft_rows",
+    "pie_paged_attn_verify_i8_workspace_bytes", "pie_paged_attn_verify_i8", "pie_paged_attn_verify_mfma_splits", "pie_paged_attn_verify_mfma",
+    "pie_ngram_draft_rows_workspace_bytes", "pie_ngram_draft_rows",
     "pie_spec_verify_rows_workspace_bytes", "pie_spec_verify_rows", "pie_decoder_spec_batch_workspace_bytes", "pie_decoder_spec_step_batch",
     "pie_spec_verify_rows_sampled_workspace_bytes", "pie_spec_verify_rows_sampled", "pie_decoder_spec_batch_tail_workspace_bytes", "pie_decoder_spec_step_batch_tail",
     "pie_prefill_attn_i8",
@@ -261,6 +263,8 @@ def load() -> C.CDLL:
     lib.pie_paged_attn_verify_i8_workspace_bytes.argtypes = [C.c_int] * 4
     lib.pie_prefill_attn_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
     lib.pie_paged_attn_verify_i8.argtypes =[C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
+    lib.pie_paged_attn_verify_mfma_splits.argtypes = [C.c_int] * 3
+    lib.pie_paged_attn_verify_mfma.argtypes = lib.pie_paged_attn_verify.argtypes
     lib.pie_ngram_draft_rows_workspace_bytes.restype = C.c_size_t
     lib.pie_ngram_draft_rows_workspace_bytes.argtypes = [C.c_int]
     lib.pie_ngram_draft_rows.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4

@@ -832,7 +832,11 @@ void *pie_debug_buffer(pie_decoder *d, int which) {
 
 int pie_decoder_configure(pie_decoder *d, int option, int value) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_configure: null decoder");
-    PIE_REQUIRE(option == PIE_OPT_KV_I8, PIE_E_ARG, "pie_decoder_configure: unknown option");
+    PIE_REQUIRE(option == PIE_OPT_KV_I8 || option == PIE_OPT_VERIFY_MFMA, PIE_E_ARG, "pie_decoder_configure: unknown option");
+    if (option == PIE_OPT_VERIFY_MFMA) {  // read by the batched speculative pass alone, which no graph holds: nothing to plan or drop
+        d->verify_mfma = value != 0;
+        return PIE_OK;
+    }
     d->kv_i8 = value != 0;
     plan_attention(d);
     drop_graphs(d);

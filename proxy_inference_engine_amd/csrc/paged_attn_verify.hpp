@@ -32,3 +32,8 @@ int verify_attn_merge_launch(int dtype, int D, const VerifyAttnArgs &a, hipStrea
 // rest as above; the partials are merged by verify_attn_merge_launch.
 int paged_attn_verify_i8_splits(int B, int Hkv, int max_blocks);
 int paged_attn_verify_i8_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st);
+
+// paged_attn_verify_launch's contract on the MFMA units (paged_attn_verify_mfma.hip): T pages, the same arguments and
+// partials; opt-in (PIE_OPT_VERIFY_MFMA), with a split rule of its own.
+int paged_attn_verify_mfma_splits(int B, int Hkv, int max_blocks);
+int paged_attn_verify_mfma_launch(int dtype, int D, const VerifyAttnArgs &a, hipStream_t st);

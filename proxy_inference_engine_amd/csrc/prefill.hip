@@ -1174,7 +1174,10 @@ static int spec_batch_t(pie_decoder *d, const int32_t *fed, const int32_t *row_c
     const pie_decoder_config &c = d->cfg;
     const int D = c.head_dim;
     // the page format picks the attention kernel, and with it the split count the scratch is sized for
-    const int splits = d->kv_i8 ? paged_attn_verify_i8_splits(B, c.n_kv_heads, max_blocks) : paged_attn_verify_splits(B, c.n_kv_heads, max_blocks);
+    const bool mfma = d->verify_mfma && !d->kv_i8;  // PIE_OPT_VERIFY_MFMA: T pages on the matrix units; int8 pages are there already
+    const int splits = d->kv_i8 ? paged_attn_verify_i8_splits(B, c.n_kv_heads, max_blocks)
+                       : mfma   ? paged_attn_verify_mfma_splits(B, c.n_kv_heads, max_blocks)
+                                : paged_attn_verify_splits(B, c.n_kv_heads, max_blocks);
     int rc = scratch_reserve(d, N, w16_copy_elems(c, true), splits > d->splits ? splits : d->splits);
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
@@ -1185,7 +1188,8 @@ static int spec_batch_t(pie_decoder *d, const int32_t *fed, const int32_t *row_c
         a.q = s->q, a.slab = (const u16 *)slabs[li], a.block_table = block_tables, a.row_seq = row_seq, a.row_ctx = row_ctx, a.seg_first = seg_first;
         a.N = N, a.B = B, a.Hq = c.n_heads, a.Hkv = c.n_kv_heads, a.bt_stride = max_blocks, a.n_pages = n_pages, a.splits = splits;
         a.scale = 1.0f / sqrtf((float)D), a.part_acc = s->part_acc, a.part_ml = s->part_ml, a.out = s->attn;
-        return d->kv_i8 ? paged_attn_verify_i8_launch(c.dtype, D, a, st) : paged_attn_verify_launch(c.dtype, D, a, st);
+        if (d->kv_i8) return paged_attn_verify_i8_launch(c.dtype, D, a, st);
+        return mfma ? paged_attn_verify_mfma_launch(c.dtype, D, a, st) : paged_attn_verify_launch(c.dtype, D, a, st);
     });
     if (rc) return rc;
     return lm_head_rows<T>(d, s->xn, N, logits, st);

@@ -595,6 +595,7 @@ class BatchedEngine:
         a token automaton, frequency / presence penalties, DRY, logprobs, top_logprobs and prompt_logprobs.
         SpeculativeParams(int8_pages=True) admits kv_dtype=torch.int8: the passes then run on the int8 pages
         (Model.spec_step_batch(..., int8_pages=True)); schedule, clamps, `spec_stats` and seats are the 16-bit pool's.
+        SpeculativeParams(mfma_verify=True): the passes get mfma_verify=True, the MFMA verify attention on 16-bit pages.
         int8_chunks=True keeps prefill_chunk and share_prefix as given on a kv_dtype=torch.int8 pool, where they are
         otherwise switched off: the passes that carry prompt rows are then Model.step_mixed(..., int8_pages=True).  A prompt's first chunk
         (and the shared prefix) attends its own rows unquantised, as a whole prompt on int8 pages does; every later chunk and every suffix
@@ -768,7 +769,8 @@ class BatchedEngine:
         sp = self.speculative
         entry = self.model.spec_step_batch if seats.tails is None else self.model.spec_step_batch_tail   # (a tail: `sampling` was given under batch_tail)
         n, toks, nxt = entry(torch.cat([a.token for a in active]), [a.cache for a in active], spec.drafts, m, spec.ids, spec.len,
-                             then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts), **({"int8_pages": True} if self._i8 else {}))
+                             then_draft=(sp.ngram_max, sp.ngram_min, sp.num_draft, spec.drafts), **({"int8_pages": True} if self._i8 else {}),
+                             **({"mfma_verify": True} if getattr(sp, "mfma_verify", False) else {}))
         if seats.tails is not None:
             seats.moved(n)
         spec.moved(active, n)

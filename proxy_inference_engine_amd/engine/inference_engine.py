@@ -142,6 +142,9 @@ class SpeculativeParams:
     the int8 pages and attend them through the int8-page MFMA kernel (Model.spec_step_batch(..., int8_pages=True)); the tokens are those
     of the same engine without `speculative`.  False -- an int8 pool is refused, as ever.  On a 16-bit pool the flag does nothing.
     InferenceEngine, whose passes read 16-bit caches, refuses int8_pages=True by name.
+    mfma_verify: True -- BatchedEngine's passes on a 16-bit pool attend through the MFMA verify kernel
+    (Model.spec_step_batch(..., mfma_verify=True)); the tokens are the same.  False -- the VALU kernel, as ever.  On an int8 pool the flag
+    does nothing.  InferenceEngine, whose passes do not use this kernel, refuses mfma_verify=True by name.
     draft_model: None -- prompt-lookup drafts, as above.  A built `Model` of the target's vocabulary, or a checkpoint
     path (loaded once and kept on the engine) -- every round the draft model runs num_draft of its own replayed steps (num_draft =
     the target's spec_min_rows - 1 .. 31, so that the pass keeps its many-row form) and the target verifies them in one pass.  A greedy
@@ -164,6 +167,7 @@ class SpeculativeParams:
     configured_tail: bool = False
     batch_tail: bool = field(default=False, kw_only=True)   # (keyword-only: the positional order of the fields around it stays as it was)
     int8_pages: bool = field(default=False, kw_only=True)
+    mfma_verify: bool = field(default=False, kw_only=True)
     draft_model: object = None
     grammar: bool = False
 
@@ -186,6 +190,8 @@ class SpeculativeParams:
             raise ValueError("SpeculativeParams: batch_tail is a bool")
         if not isinstance(self.int8_pages, bool):
             raise ValueError("SpeculativeParams: int8_pages is a bool")
+        if not isinstance(self.mfma_verify, bool):
+            raise ValueError("SpeculativeParams: mfma_verify is a bool")
         if self.grammar and self.draft_model is not None:
             raise ValueError("SpeculativeParams: grammar is not available with a draft model")
 
@@ -314,6 +320,8 @@ def _check_generate_args(model, pixel_values, mask, kv_bits, kv_group_size, max_
         raise ValueError("speculative decoding is not available with batch_tail (BatchedEngine's passes; the single sequence's is configured_tail)")
     if speculative is not None and getattr(speculative, "int8_pages", False):
         raise ValueError("speculative decoding is not available with int8_pages (BatchedEngine's passes; the single sequence's read 16-bit caches)")
+    if speculative is not None and getattr(speculative, "mfma_verify", False):
+        raise ValueError("speculative decoding is not available with mfma_verify (BatchedEngine's passes; the single sequence's do not use that kernel)")
     if speculative is not None and scored:
         raise ValueError("speculative decoding is not available with prompt_logprobs")
     if scored and not 0 <= int(prompt_logprobs) <= hip_ops.TOP_LOGPROBS_MAX:

@@ -1614,6 +1614,38 @@ def prefill_attn_i8(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_tab
     return out
 
 
+def paged_attn_verify_mfma_splits(B: int, n_kv_heads: int, max_blocks: int) -> int:
+    """The splits paged_attn_verify_mfma(splits=0) cuts a segment's positions into (pie_paged_attn_verify_mfma_splits)."""
+    return int(_ffi.load().pie_paged_attn_verify_mfma_splits(int(B), int(n_kv_heads), int(max_blocks)))
+
+
+def paged_attn_verify_mfma(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_tables: torch.Tensor, row_seq: torch.Tensor, row_context_lens: torch.Tensor,
+                           seg_first: torch.Tensor, n_kv_heads: int, scale: float, splits: int = 0) -> torch.Tensor:
+    """paged_attn_verify on the MFMA units (pie_paged_attn_verify_mfma): the same arguments and 16-bit pages.  One launch for
+    all segments (one more to merge the splits): a segment's (row, head) pairs are the columns of the matrix products, so a page's rows
+    are read once per kv-head for all of them.  splits: 0 = paged_attn_verify_mfma_splits(...), else 1..32."""
+    for t in (q, slab, block_tables, row_seq, row_context_lens, seg_first):
+        _dev(t)
+    if any(t.dtype != torch.int32 for t in (block_tables, row_seq, row_context_lens, seg_first)):
+        raise TypeError("paged_attn_verify_mfma: block_tables, row_seq, row_context_lens and seg_first must be int32")
+    if q.dim() != 3 or block_tables.dim() != 2:
+        raise ValueError("paged_attn_verify_mfma: q [N, Hq, D]; block_tables [B, max_blocks]")
+    N, Hq, D = q.shape
+    B = block_tables.shape[0]
+    if row_seq.numel() != N or row_context_lens.numel() != N or seg_first.numel() != B + 1:
+        raise ValueError("paged_attn_verify_mfma: row_seq [N]; row_context_lens [N]; seg_first [B + 1]")
+    if not 0 <= int(splits) <= 32:
+        raise ValueError("paged_attn_verify_mfma: splits is 0 (chosen by the library) or 1..32")
+    lib = _ffi.load()
+    used = int(splits) or paged_attn_verify_mfma_splits(B, n_kv_heads, block_tables.shape[1])
+    ws = torch.empty(max(int(lib.pie_paged_attn_verify_workspace_bytes(N, Hq, D, used)), 16), dtype=torch.uint8, device=q.device)
+    out = torch.empty_like(q)
+    _ffi.check(lib.pie_paged_attn_verify_mfma(_ffi.p(q), _ffi.p(slab), n_pages, _ffi.p(block_tables), block_tables.shape[1], _ffi.p(row_seq), _ffi.p(row_context_lens),
+                                              _ffi.p(seg_first), N, B, Hq, int(n_kv_heads), D, float(scale), _ffi.dtype_code(q.dtype), int(splits), _ffi.p(out),
+                                              _ffi.p(ws), _ffi.stream()))
+    return out
+
+
 def ngram_draft_rows_workspace(device, B: int) -> torch.Tensor:
     """pie_ngram_draft_rows' workspace for B sequences on `device`: uninitialised, nothing is carried from call to call."""
     return _workspace("pie_ngram_draft_rows_workspace_bytes", False, "ngram_draft_rows", f"1 <= B <= 4096, got {B}", device, B).view(torch.int32)

@@ -122,6 +122,7 @@ class KVBinding:
         self._hold = None
         self.offset = None   # device-side cache offset the decoder believes in: after advance(), the position the chosen token will occupy
         self._i8 = None      # the decoder's page format (PIE_OPT_KV_I8); None until a pool was seen
+        self._verify_mfma = False   # the decoder's PIE_OPT_VERIFY_MFMA as last set here (its default: off)
 
     def sync(self, cache, n_new: int) -> None:
         """Room for `n_new` more rows in every layer, then the decoder bound to them; all layers are checked before the first allocation."""
@@ -157,6 +158,12 @@ class KVBinding:
         if always or self._i8 != (allocator.dtype == torch.int8):
             self._i8 = allocator.dtype == torch.int8
             _ffi.check(self.lib.pie_decoder_configure(self.dec, _ffi.PIE_OPT_KV_I8, int(self._i8)))
+
+    def match_verify_kernel(self, mfma: bool) -> None:
+        """The verify attention of the batched speculative passes on T pages (PIE_OPT_VERIFY_MFMA): configured only when it changes."""
+        if self._verify_mfma != bool(mfma):
+            _ffi.check(self.lib.pie_decoder_configure(self.dec, _ffi.PIE_OPT_VERIFY_MFMA, int(bool(mfma))))
+            self._verify_mfma = bool(mfma)
 
     def pool_args(self, allocator):
         """(per-layer slab planes, pages, bytes of one plane) as the paged entry points take them, the decoder set to the pool's format."""

@@ -711,7 +711,7 @@ class Model(RowsTailState, StepTailState):
         return hip_ops.ngram_draft_rows(seq_ids, seq_len, ngram_max, ngram_min, k, out=out)
 
     def spec_step_batch(self, tokens: torch.Tensor, caches: list[list[BaseCache]], drafts: torch.Tensor, counts, seq_ids: torch.Tensor | None = None,
-                        seq_len: torch.Tensor | None = None, then_draft: tuple | None = None, *, int8_pages: bool = False):
+                        seq_len: torch.Tensor | None = None, then_draft: tuple | None = None, *, int8_pages: bool = False, mfma_verify: bool = False):
         """One speculative pass for several decode-state sequences (pie_decoder_spec_step_batch): tokens [B] = every sequence's
         input token, caches as step_batch takes them (16-bit pages; int8 pages with int8_pages=True, DESIGN.md 26: the pass's rows are
         quantised with their pages' scales and attended through the int8-page MFMA kernel), drafts device int32 [>= B, >= the largest count] = row s's drafted ids, counts = the
@@ -724,11 +724,13 @@ class Model(RowsTailState, StepTailState):
         token -- the pass writes the chosen tokens behind it and moves seq_len on the device.  then_draft = (ngram_max, ngram_min, k,
         drafts_out): hip_ops.ngram_draft_rows over those rows is queued behind the pass, before the host reads anything, into drafts_out
         [B, k], and next_counts are its counts, read back with the pass's one record.  Greedy and raw: int8 pages without int8_pages=True,
-        tensor-parallel models and any armed per-row state of the multi-sequence passes are refused by name."""
-        return self._spec_batch_pass("spec_step_batch", False, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages)
+        tensor-parallel models and any armed per-row state of the multi-sequence passes are refused by name.
+        mfma_verify=True: on 16-bit pages the pass attends through the MFMA verify kernel (pie_paged_attn_verify_mfma,
+        PIE_OPT_VERIFY_MFMA) with that kernel's split rule; the same rows, tokens and caches.  On int8 pages it does nothing."""
+        return self._spec_batch_pass("spec_step_batch", False, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages, mfma_verify)
 
     def spec_step_batch_tail(self, tokens: torch.Tensor, caches: list[list[BaseCache]], drafts: torch.Tensor, counts, seq_ids: torch.Tensor | None = None,
-                             seq_len: torch.Tensor | None = None, then_draft: tuple | None = None, *, int8_pages: bool = False):
+                             seq_len: torch.Tensor | None = None, then_draft: tuple | None = None, *, int8_pages: bool = False, mfma_verify: bool = False):
         """spec_step_batch under the sequences' own samplers, repetition penalties and logit biases (pie_decoder_spec_step_batch_tail;
         DESIGN.md 25): the same arguments and returns.  Needs set_batch_tail armed; record, ring, bias table (set_batch_edits' bias part)
         and XTC record (set_batch_xtc) s belong to sequence s, as in step_batch.  Row j of sequence s is edited with its seat's penalty over
@@ -738,10 +740,10 @@ class Model(RowsTailState, StepTailState):
         "logprobs" fp32 [N, V] (every row's processed log-probabilities), "logits" [N, V] (the processed block, a view of the workspace,
         valid until the next pass) and "seg_first" int32 [B + 1].  Refused by name, before anything moves: int8 pages without int8_pages=True, tensor-parallel
         models, a mask part of the batch edits, batch token automata, a batch count penalty, a batch DRY penalty, batch top log-probabilities
-        and prompt scoring."""
-        return self._spec_batch_pass("spec_step_batch_tail", True, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages)
+        and prompt scoring.  mfma_verify: as in spec_step_batch."""
+        return self._spec_batch_pass("spec_step_batch_tail", True, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages, mfma_verify)
 
-    def _spec_batch_pass(self, who: str, tail: bool, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages=False):
+    def _spec_batch_pass(self, who: str, tail: bool, tokens, caches, drafts, counts, seq_ids, seq_len, then_draft, int8_pages=False, mfma_verify=False):
         """spec_step_batch's and spec_step_batch_tail's body: the refusals, the index arrays, the entry's call and the one read-back."""
         import numpy as np
         seqs = self._kv.sequences(who, caches)
@@ -793,6 +795,7 @@ class Model(RowsTailState, StepTailState):
         index = torch.from_numpy(np.concatenate([seg_first, row_seq, row_ctx, table.reshape(-1)])).to(self.device)   # one upload
         t_first, t_seq, t_ctx, t_table = index[:B + 1], index[B + 1:B + 1 + N], index[B + 1 + N:B + 1 + 2 * N], index[B + 1 + 2 * N:]
         lib = _ffi.load()
+        self._kv.match_verify_kernel(mfma_verify)
         V = self.vocab_out
         if tail:
             ws = self._spec_ws(vars(self), "_spec_batch_tail_ws", "pie_decoder_spec_batch_tail_workspace_bytes", True)

@@ -24,6 +24,10 @@ steps are the int8 step_batch; attn_us is hip_ops.paged_attn_verify_i8, and "att
 over a 16-bit slab of its own.  Both attention rows carry kv_bytes (the K / V bytes the shapes need: B x kv-heads x context x head_dim x 2 x
 the element size) over the measured time as kv_gb_per_s and its share of HBM_GB_PER_S.  No mixed rows: a prompt continuing a cached prefix
 reads T pages.
+--mfma: a 16-bit pool as without it; beside every "attn" row (hip_ops.paged_attn_verify, the VALU kernel) there are "attn_mfma"
+(hip_ops.paged_attn_verify_mfma with its own split rule, 512 workgroups) and "attn_mfma256" (the same kernel with the split count of a
+256-workgroup target, handed over explicitly), all with kv_bytes and hbm_share; beside every "pass" row a "pass_mfma" row, the same
+Model.spec_step_batch with mfma_verify=True.  No mixed rows.
 """
 import argparse
 import json
@@ -42,11 +46,11 @@ sys.path.insert(0, str(ROOT))
 
 def run_all(args):
     """One fresh child per context under its own time limit; the first one that fails or runs out of time ends the run."""
-    merged = {"model": "llama3-8b int4 g64 bf16 (synthetic weights, synthetic cache)" + (", int8 KV pages" if args.int8 else ""), "reps": args.reps, "window": args.window, "contexts": {}}
+    merged = {"model": "llama3-8b int4 g64 bf16 (synthetic weights, synthetic cache)" + (", int8 KV pages" if args.int8 else "") + (", MFMA verify attention beside the VALU kernel" if args.mfma else ""), "reps": args.reps, "window": args.window, "contexts": {}}
     for ctx in [int(x) for x in args.contexts.split(",") if x]:
         part = Path(args.out).with_suffix(f".ctx{ctx}.json")
         cmd = [sys.executable, __file__, "--context", str(ctx), "--batches", args.batches, "--drafts", args.drafts, "--accepts", args.accepts, "--reps", str(args.reps),
-               "--window", str(args.window), "--out", str(part)] + (["--int8"] if args.int8 else []) + (["--layers", str(args.layers)] if args.layers else [])
+               "--window", str(args.window), "--out", str(part)] + (["--int8"] if args.int8 else []) + (["--mfma"] if args.mfma else []) + (["--layers", str(args.layers)] if args.layers else [])
         rc = subprocess.run(cmd, timeout=args.limit).returncode
         if rc != 0:
             print(json.dumps({"context": ctx, "failed": rc}), flush=True)
@@ -71,7 +75,10 @@ def main():
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--int8", action="store_true")
+    ap.add_argument("--mfma", action="store_true")
     args = ap.parse_args()
+    if args.int8 and args.mfma:
+        ap.error("--mfma measures the 16-bit pool's kernels; --int8 has the MFMA kernel already")
     if args.all:
         sys.exit(run_all(args))
 
@@ -122,12 +129,12 @@ def main():
         rewind()
         full: dict = {}
 
-        def full_draft(m):
+        def full_draft(m, kw):
             """Drafts [B, m] the pass accepts whole: the plain continuations, with the pass's own token wherever it differs."""
-            if m not in full:
+            if (m, *kw) not in full:
                 d = torch.tensor([c[1:m + 1] for c in cont], dtype=torch.int32, device="cuda")
                 for _ in range(m + 1):
-                    n, toks, _ = model.spec_step_batch(first, caches, d, [m] * B, **spec_kw)
+                    n, toks, _ = model.spec_step_batch(first, caches, d, [m] * B, **kw)
                     rewind()
                     if all(k == m + 1 for k in n):
                         break
@@ -135,8 +142,8 @@ def main():
                         if k < m + 1:
                             d[s, k - 1] = t[-1]
                 assert all(k == m + 1 for k in n), f"no fully accepted drafts of {m} ids found"
-                full[m] = d
-            return full[m]
+                full[(m, *kw)] = d
+            return full[(m, *kw)]
 
         seen: dict = {}
         seq_ids = torch.zeros((B, o + 64), dtype=torch.int32, device="cuda")
@@ -144,10 +151,11 @@ def main():
         seq_len = torch.zeros(B, dtype=torch.int32, device="cuda")
         nxt_drafts = torch.zeros((B, max(drafts)), dtype=torch.int32, device="cuda")
 
-        def pass_window(m, a):
-            name = f"pass m={m} a={a}"
+        def pass_window(m, a, mfma=False):
+            name = f"pass{'_mfma' if mfma else ''} m={m} a={a}"
+            kw = dict(spec_kw, mfma_verify=True) if mfma else spec_kw
             seen[name] = set()
-            d = full_draft(m).clone()
+            d = full_draft(m, kw).clone()
             if a < m:
                 d[:, a] = (d[:, a] + 1) % V
 
@@ -155,7 +163,7 @@ def main():
                 for _ in range(args.window):
                     rewind()
                     seq_len.fill_(o + 1)
-                    n = model.spec_step_batch(first, caches, d, [m] * B, seq_ids, seq_len, then_draft=(3, 1, max(drafts), nxt_drafts), **spec_kw)[0]
+                    n = model.spec_step_batch(first, caches, d, [m] * B, seq_ids, seq_len, then_draft=(3, 1, max(drafts), nxt_drafts), **kw)[0]
                     seen[name].update(n)
                 rewind()
             return run
@@ -181,7 +189,7 @@ def main():
                 rewind()
             return run
 
-        def attn_window(m, t_pages=False):
+        def attn_window(m, t_pages=False, mfma_target=0):
             for s in seqs:
                 s.reserve(m + 1)
             table = torch.zeros((B, blocks), dtype=torch.int32)
@@ -193,9 +201,13 @@ def main():
             q = torch.randn((N, Hq, D), device="cuda").to(torch.bfloat16)
             idx = (table.cuda(), dev([r // (m + 1) for r in range(N)]), dev([o + 1 + r % (m + 1) for r in range(N)]), dev([s * (m + 1) for s in range(B + 1)]))
 
+            splits256 = max(1, min(-(-256 // (B * Hkv)), 32, blocks))    # the int8 kernel's rule, for the T-page MFMA kernel
+
             def run():
                 for _ in range(args.window):
-                    if args.int8 and not t_pages:
+                    if mfma_target:
+                        hip_ops.paged_attn_verify_mfma(q, pool.slab[0], pool.size(), *idx, Hkv, D ** -0.5, splits=splits256 if mfma_target == 256 else 0)
+                    elif args.int8 and not t_pages:
                         hip_ops.paged_attn_verify_i8(q, pool.slab[0], pool.size(), *idx, Hkv, D ** -0.5)
                     else:
                         hip_ops.paged_attn_verify(q, t_slab if args.int8 else pool.slab[0], pool.size(), *idx, Hkv, D ** -0.5)
@@ -203,13 +215,18 @@ def main():
 
         windows = {"step": step_window(False), "step_sync": step_window(True)}
         for m in drafts:
-            if not args.int8:
+            if not args.int8 and not args.mfma:
                 windows[f"mixed m={m}"] = mixed_window(m)
             windows[f"attn m={m}"] = attn_window(m)
+            if args.mfma:
+                windows[f"attn_mfma m={m}"] = attn_window(m, mfma_target=512)
+                windows[f"attn_mfma256 m={m}"] = attn_window(m, mfma_target=256)
             if args.int8:
                 windows[f"attn_T m={m}"] = attn_window(m, True)
             for a in sorted({int(x) for x in args.accepts.split(",") if x and int(x) < m} | {m}):
                 windows[f"pass m={m} a={a}"] = pass_window(m, a)
+                if args.mfma:
+                    windows[f"pass_mfma m={m} a={a}"] = pass_window(m, a, True)
         ms = {k: [] for k in windows}
         for rnd in range(args.reps + 1):                               # round 0 warms every shape; then the forms alternate
             for name, fn in windows.items():
