@@ -112,6 +112,22 @@ def marker_rows(T: int, plans=()) -> list:
     return sorted(r for r in rows if 0 <= r < T)
 
 
+def page_run_markers(T: int, splits: int) -> list:
+    """Rows on both sides of the 64-position page edges around every boundary attn_split cuts T attended positions into (the page a split
+    begins or ends inside), and the middle row of the middle page of the middle split's page run."""
+    chunk = max(-(-T // splits), 32)
+    rows = {e + d for b in range(chunk, T, chunk) for e in (b // 64 * 64, b // 64 * 64 + 64) for d in (-1, 0) if 0 < e < T}
+    rows.add(middle_page(T, splits) * 64 + 32)
+    return sorted(r for r in rows if 0 <= r < T)
+
+
+def middle_page(T: int, splits: int) -> int:
+    """The page in the middle of the page run of the middle split of attn_split(T, splits)."""
+    chunk = max(-(-T // splits), 32)
+    lo = (-(-T // chunk) // 2) * chunk
+    return ((lo >> 6) + ((min(T, lo + chunk) - 1) >> 6)) // 2
+
+
 def kv_history(rng, Hkv: int, T: int, D: int, dtype: str, markers, cap: int | None = None, k_scale=0.5, k_marker=4.0, v_marker=30.0,
                strong=()):
     """A synthetic K / V history [Hkv, cap, D] (fp32, representable in T): V = a per-dim mean + noise (outputs O(1)); at the marker

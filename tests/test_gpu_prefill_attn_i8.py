@@ -4,8 +4,8 @@ import pytest
 import torch
 
 from oracle import pie_oracle as po
-from tests._util import EPS, assert_dot_close, assert_vec_close, sdpa_f64, to_bits, to_dev
-from tests.test_gpu_spec_batch_i8 import amax_scales
+from tests._util import EPS, assert_dot_close, assert_vec_close, marker_rows, page_run_markers, sdpa_f64, to_bits, to_dev
+from tests.test_gpu_spec_batch_i8 import amax_scales, i8_markers, lift_k_scales
 from tests.test_gpu_speculative import MODELS, dev_ids, e2e_prompt, load_tiny
 
 pytestmark = pytest.mark.gpu
@@ -15,17 +15,18 @@ PAIRS = [(1, 64), (31, 1), (33, 63), (70, 100), (64, 200)]   # (rows, cached): t
 MAX_FRAC = 0.03                                               # the int8 decode-attention test's share (measured: DESIGN.md 27)
 
 
-def chunk_case(rng, D, rep, dt, pairs):
+def chunk_case(rng, D, rep, dt, pairs, *, hkv=HKV, long=False, details=None, page_bytes=None):
     """(q, slab, tables, chunks, want), built as i8_case of test_gpu_spec_batch_i8 builds its data (a row that sees its successor fails).
-    Row 0 of the batch belongs to no chunk."""
+    Row 0 of the batch belongs to no chunk.  long (tests/page_attn_long_cases.py): i8_case's long markers among the cached positions, as
+    for 32 splits of them; details: a list that receives every chunk's (k, v, P, M, markers, (K codes, V codes, K scales, V scales))."""
     from proxy_inference_engine_amd import _ffi
-    Hq, pb = HKV * rep, int(_ffi.load().pie_page_i8_bytes(HKV, D))
+    Hq, pb = hkv * rep, page_bytes or int(_ffi.load().pie_page_i8_bytes(hkv, D))
     blocks = [(m + p + 63) // 64 for m, p in pairs]
     n_pages, mb, N = sum(blocks) + 3, max(blocks), 1 + sum(m for m, _ in pairs)
     q = po.round_T(rng.standard_normal((N, Hq, D), dtype=np.float32), dt)
-    ksc, vsc = ((unit * (16 + rng.integers(0, 240, (n_pages, HKV)))).astype(np.float16) for unit in (2.0 ** -12, 2.0 ** -11))   # 1/256 .. 1/16, 1/128 .. 1/8
-    codes = np.full((n_pages, 2, HKV, 64, D), -128, np.int8)
-    scales = np.full((n_pages, 2, HKV), np.nan, np.float16)
+    ksc, vsc = ((unit * (16 + rng.integers(0, 240, (n_pages, hkv)))).astype(np.float16) for unit in (2.0 ** -12, 2.0 ** -11))   # 1/256 .. 1/16, 1/128 .. 1/8
+    codes = np.full((n_pages, 2, hkv, 64, D), -128, np.int8)
+    scales = np.full((n_pages, 2, hkv), np.nan, np.float16)
     pages, at, first = rng.permutation(n_pages), 0, 1
     tables = np.full((len(pairs), mb), pages[-1], np.int32)            # behind a sequence's pages: an unreferenced one
     want, chunks = np.zeros((N, Hq, D), np.float64), []
@@ -33,27 +34,32 @@ def chunk_case(rng, D, rep, dt, pairs):
         T = P + M
         mine, at = pages[at:at + nb], at + nb
         tables[s, :nb] = mine
+        marks = sorted(set(marker_rows(P + 1, [(P + 1, 32)]) + page_run_markers(P + 1, 32))) if long else []
+        lift_k_scales(ksc, mine[sorted({m // 64 for m in marks + list(range(P + 1, T))})] if long else [])
         scales[mine, 0], scales[mine, 1] = ksc[mine], vsc[mine]
-        sd = np.sign(rng.standard_normal((HKV, 1, D)))                 # V: one sign per dim
-        k8 = np.clip(np.rint(rng.standard_normal((HKV, nb * 64, D)) * 40), -127, 127)
-        v8 = np.clip(np.rint(sd * (50 + 25 * rng.standard_normal((HKV, nb * 64, D)))), -127, 127)
+        sd = np.sign(rng.standard_normal((hkv, 1, D)))                 # V: one sign per dim
+        k8 = np.clip(np.rint(rng.standard_normal((hkv, nb * 64, D)) * 40), -127, 127)
+        v8 = np.clip(np.rint(sd * (50 + 25 * rng.standard_normal((hkv, nb * 64, D)))), -127, 127)
         for i, p in enumerate(range(P + 1, T)):                        # position P + 1 + i is the first one row i must not see
-            for g in range(HKV):
+            for g in range(hkv):
                 qh = q[first + i, g * rep + i % rep].astype(np.float64)
                 k8[g, p] = np.clip(np.rint((np.log(T) + 6) * np.sqrt(D) / (qh @ qh) * qh / np.float64(ksc[mine[p // 64], g])), -127, 127)
                 v8[g, p] = -127 * sd[g, 0]
+        i8_markers(k8, v8, q[first:first + M], marks, P + 1, T, rep, ksc[mine], sd)
         k8[:, T:], v8[:, T:] = -128, -128
-        codes[mine, 0] = k8.reshape(HKV, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
-        codes[mine, 1] = v8.reshape(HKV, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
+        codes[mine, 0] = k8.reshape(hkv, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
+        codes[mine, 1] = v8.reshape(hkv, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
         per_pos = np.repeat(mine, 64)[:T]
         k = po.kv_i8_dequantize(k8[:, :T].transpose(1, 0, 2), ksc[per_pos]).transpose(1, 0, 2)   # the codes actually in the pages
         v = po.kv_i8_dequantize(v8[:, :T].transpose(1, 0, 2), vsc[per_pos]).transpose(1, 0, 2)
         for i in range(M):
             want[first + i] = sdpa_f64(q[first + i][:, None], k, v, 1.0 / np.sqrt(D), P + i + 1)[:, 0]
+        if details is not None:
+            details.append((k, v, P, M, marks, (k8[:, :T], v8[:, :T], ksc[mine], vsc[mine])))
         chunks, first = chunks + [[first, M, P, s]], first + M
     slab = np.zeros((n_pages, pb), np.uint8)
-    slab[:, :2 * HKV * 64 * D] = codes.reshape(n_pages, -1).view(np.uint8)
-    slab[:, 2 * HKV * 64 * D:2 * HKV * 64 * D + 4 * HKV] = scales.reshape(n_pages, -1).view(np.uint8)
+    slab[:, :2 * hkv * 64 * D] = codes.reshape(n_pages, -1).view(np.uint8)
+    slab[:, 2 * hkv * 64 * D:2 * hkv * 64 * D + 4 * hkv] = scales.reshape(n_pages, -1).view(np.uint8)
     return q, slab, tables, chunks, want
 
 

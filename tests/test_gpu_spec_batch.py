@@ -12,7 +12,7 @@ import torch
 from oracle import pie_oracle as po
 from tests import spec_batch_reference as sb
 from tests import speculative_reference as ref
-from tests._util import POISON, TORCH_DT, assert_dot_close, assert_vec_close, kv_history, marker_rows, plant_needles, sdpa_f64, to_bits, to_dev
+from tests._util import POISON, TORCH_DT, assert_dot_close, assert_vec_close, kv_history, marker_rows, page_run_markers, plant_needles, sdpa_f64, to_bits, to_dev
 from tests.test_gpu_speculative import E2E_SEEDS, MODELS, SENT, STEP_SEEDS, dev_ids, e2e_prompt, load_tiny, oracle_run, rows_alone, verify_rows
 
 pytestmark = pytest.mark.gpu
@@ -68,40 +68,67 @@ SEG_ROWS = (1, 2, 8)                     # three sequences, and an idle slot beh
 FIRST_CTX = [(65, 64, 1), (200, 1, 63), (1, 63, 64), (64, 200, 65), (63, 65, 200), (1, 64, 300)]   # first-row contexts of the three segments
 
 
-def attn_case(rng, D, rep, dt, first, splits):
+def attn_case(rng, D, rep, dt, first, splits, *, seg_rows=SEG_ROWS, hkv=HKV, max_blocks=MAX_BLOCKS, n_pages=N_PAGES, long=False, details=None):
     """(q, slab, tables, row_seq, row_ctx, seg_first, references): every sequence on shuffled pages of a pool that is NaN wherever nothing
     is referenced and behind every context; markers on both sides of every split edge of the segment's longest row; the K of every later
-    draft row aligned with the query of the row before it and its V loud, so a row that sees its successor fails."""
-    Hq = HKV * rep
-    seg_first, row_seq, row_ctx = sb.form_rows([c - 1 for c in first], [r - 1 for r in SEG_ROWS])
+    draft row aligned with the query of the row before it and its V loud, so a row that sees its successor fails.
+    long (tests/page_attn_long_cases.py): markers also at the page edges around every split edge and in the middle of a split's page run
+    (page_run_markers); every marker's K is aligned with one (row, head) query of its segment, scored ~ln T, and its V is four times as loud
+    in a dim of its own, so that each marker alone moves a row.  details: a list that receives every segment's (k, v, c0, rows, markers)."""
+    Hq = hkv * rep
+    seg_first, row_seq, row_ctx = sb.form_rows([c - 1 for c in first], [r - 1 for r in seg_rows])
     seg_first, N = seg_first + [seg_first[-1]], seg_first[-1]          # the idle slot
     q = po.round_T(rng.standard_normal((N, Hq, D), dtype=np.float32), dt)
-    pool = np.full((N_PAGES, 2, HKV, 64, D), np.nan, np.float32)
-    pages = rng.permutation(N_PAGES)
-    tables = np.zeros((len(SEG_ROWS) + 1, MAX_BLOCKS), np.int32)
+    pool = np.full((n_pages, 2, hkv, 64, D), np.nan, np.float32)
+    pages = rng.permutation(n_pages)
+    tables = np.zeros((len(seg_rows) + 1, max_blocks), np.int32)
     want = np.zeros((N, Hq, D), np.float64)
     at = 0
-    for s, (c0, rows) in enumerate(zip(first, SEG_ROWS)):
+    for s, (c0, rows) in enumerate(zip(first, seg_rows)):
         T = c0 + rows - 1
         own = list(range(c0, T))                                       # the positions of the rows behind the first: successors of some row
-        k, v = kv_history(rng, HKV, T, D, dt, sorted(set(marker_rows(T, [(T, splits)]) + own)), strong=own)
-        for i, p in enumerate(own):                                    # position c0 + i is the first one row i must not see
-            plant_needles(k, q[seg_first[s] + i], [p], T, rep, dt, rng)
+        marks = sorted(set(marker_rows(T, [(T, splits)]) + (page_run_markers(T, splits) + [c0 - 1] if long else []) + own))
+        k, v = kv_history(rng, hkv, T, D, dt, marks, strong=own)
+        if long:
+            needle_markers(k, v, q[seg_first[s]:seg_first[s] + rows], marks, c0, T, rep, dt)
+        else:
+            for i, p in enumerate(own):                                # position c0 + i is the first one row i must not see
+                plant_needles(k, q[seg_first[s] + i], [p], T, rep, dt, rng)
         n_blocks = (T + 63) // 64
         mine = pages[at:at + n_blocks]
         at += n_blocks
         tables[s, :n_blocks] = mine
         tables[s, n_blocks:] = pages[-1]                               # an unreferenced page: NaN throughout
-        pad = np.full((HKV, n_blocks * 64, D), np.nan, np.float32)
+        pad = np.full((hkv, n_blocks * 64, D), np.nan, np.float32)
         pad[:, :T] = k
-        pool[mine, 0] = pad.reshape(HKV, n_blocks, 64, D).transpose(1, 0, 2, 3)
+        pool[mine, 0] = pad.reshape(hkv, n_blocks, 64, D).transpose(1, 0, 2, 3)
         pad[:, :T] = v
-        pool[mine, 1] = pad.reshape(HKV, n_blocks, 64, D).transpose(1, 0, 2, 3)
+        pool[mine, 1] = pad.reshape(hkv, n_blocks, 64, D).transpose(1, 0, 2, 3)
         for i in range(rows):
             r = seg_first[s] + i
             want[r] = sdpa_f64(q[r][:, None], k, v, 1.0 / np.sqrt(D), c0 + i)[:, 0]
-    assert at < N_PAGES
+        if details is not None:
+            details.append((k, v, c0, rows, marks))
+    assert at < n_pages
     return q, pool, tables, row_seq, row_ctx, seg_first, want
+
+
+def needle_markers(k, v, q, marks, c0, T, rep, dt, bump=0.0, own_bump=1.0):
+    """The long cases' markers: marker i's K row (every kv-group) aligned with the query of row (i // rep) % rows, head i % rep, scored
+    ln T + bump; position c0 + j, the first one row j must not see and row j + 1's own, with row j's query (ln T + own_bump) and with
+    row j + 1's (ln T + bump) at once; every marker's V four times as loud in dim 7 i % D."""
+    hkv, _, D = k.shape
+
+    def aligned(row, g, i, b):
+        qh = q[row, g * rep + i % rep].astype(np.float64)
+        return (np.log(T) + b) * np.sqrt(D) / (qh @ qh) * qh
+
+    for i, p in enumerate(marks):
+        for g in range(hkv):
+            kp = aligned((i // rep) % q.shape[0], g, i, bump) if p < c0 else aligned(p - c0, g, i, own_bump) + aligned(p - c0 + 1, g, i + 1, bump)
+            k[g, p] = po.round_T(kp.astype(np.float32), dt)
+        v[:, p, 7 * i % D] *= 4.0
+    return k, v
 
 
 @pytest.mark.parametrize("dt", ["bfloat16", "float16"])

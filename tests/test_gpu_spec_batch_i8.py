@@ -7,7 +7,7 @@ import torch
 
 from oracle import pie_oracle as po
 from tests import spec_batch_reference as sb
-from tests._util import assert_dot_close, assert_vec_close, sdpa_f64, to_bits, to_dev
+from tests._util import assert_dot_close, assert_vec_close, marker_rows, page_run_markers, sdpa_f64, to_bits, to_dev
 from tests.test_gpu_spec_batch import BATCH_SEEDS, COUNTS, FURTHER, OFFSET5_SEEDS, OFFSETS, PLAIN_SEEDS, SP_KW
 from tests.test_gpu_speculative import MODELS, SENT, STEP_SEEDS, dev_ids, e2e_prompt, load_tiny
 
@@ -20,48 +20,83 @@ FIRST_CTX = [(300, 31, 1), (32, 200, 33), (63, 64, 65)]                # first-r
 MAX_FRAC = 0.03                                                        # the int8 decode-attention test's share (measured: DESIGN.md 26)
 
 
-def i8_case(rng, D, rep, dt, first):
+def i8_case(rng, D, rep, dt, first, *, seg_rows=SEG_ROWS, hkv=HKV, max_blocks=MAX_BLOCKS, n_pages=N_PAGES, splits=None, details=None, page_bytes=None):
     """(q, slab bytes, tables, row_seq, row_ctx, seg_first, want): shuffled pages, a distinct fp16 K and V scale per (page, head) over four
-    octaves; unreferenced pages hold code -128 under NaN scales, positions behind a context -128; the K codes of every later draft row
-    align with the query of the row before it under a loud V, so a row that sees its successor fails."""
+    octaves (drawn with repeats once the pool has more than 240 of them); unreferenced pages hold code -128 under NaN scales, positions
+    behind a context -128; the K codes of every later draft row align with the query of the row before it under a loud V, so a row that
+    sees its successor fails.
+    splits (the long cases, tests/page_attn_long_cases.py): attn_case's long markers in codes (i8_markers), on pages whose K scale is lifted
+    to 1/64 and more, where the aligned codes do not clip.  details: a list that receives every segment's (k, v, c0, rows, markers, pages)."""
     from proxy_inference_engine_amd import _ffi
-    Hq, pb = HKV * rep, int(_ffi.load().pie_page_i8_bytes(HKV, D))
-    seg_first, row_seq, row_ctx = sb.form_rows([c - 1 for c in first], [r - 1 for r in SEG_ROWS])
+    Hq, pb = hkv * rep, page_bytes or int(_ffi.load().pie_page_i8_bytes(hkv, D))
+    seg_first, row_seq, row_ctx = sb.form_rows([c - 1 for c in first], [r - 1 for r in seg_rows])
     seg_first, N = seg_first + [seg_first[-1]], seg_first[-1]
     q = po.round_T(rng.standard_normal((N, Hq, D), dtype=np.float32), dt)
-    ksc, vsc = ((unit * (16 + rng.permutation(240)[:N_PAGES * HKV].reshape(N_PAGES, HKV))).astype(np.float16) for unit in (2.0 ** -12, 2.0 ** -11))   # 1/256 .. 1/16, 1/128 .. 1/8
-    codes = np.full((N_PAGES, 2, HKV, 64, D), -128, np.int8)
-    scales = np.full((N_PAGES, 2, HKV), np.nan, np.float16)
-    pages, at = rng.permutation(N_PAGES), 0
-    tables = np.full((len(SEG_ROWS) + 1, MAX_BLOCKS), pages[-1], np.int32)   # behind a sequence's pages: an unreferenced one
+    draw = (lambda: rng.permutation(240)[:n_pages * hkv].reshape(n_pages, hkv)) if n_pages * hkv <= 240 else (lambda: rng.integers(0, 240, (n_pages, hkv)))
+    ksc, vsc = ((unit * (16 + draw())).astype(np.float16) for unit in (2.0 ** -12, 2.0 ** -11))   # 1/256 .. 1/16, 1/128 .. 1/8
+    codes = np.full((n_pages, 2, hkv, 64, D), -128, np.int8)
+    scales = np.full((n_pages, 2, hkv), np.nan, np.float16)
+    pages, at = rng.permutation(n_pages), 0
+    tables = np.full((len(seg_rows) + 1, max_blocks), pages[-1], np.int32)   # behind a sequence's pages: an unreferenced one
     want = np.zeros((N, Hq, D), np.float64)
-    for s, (c0, rows) in enumerate(zip(first, SEG_ROWS)):
+    for s, (c0, rows) in enumerate(zip(first, seg_rows)):
         T = c0 + rows - 1
         nb = (T + 63) // 64
         mine = pages[at:at + nb]
         at += nb
         tables[s, :nb] = mine
+        marks = [m for m in sorted(set(marker_rows(T, [(T, splits)]) + page_run_markers(T, splits) + [c0 - 1])) if m < c0] if splits else []
+        lift_k_scales(ksc, mine[sorted({m // 64 for m in marks + list(range(c0, T))})] if splits else [])
         scales[mine, 0], scales[mine, 1] = ksc[mine], vsc[mine]
-        sd = np.sign(rng.standard_normal((HKV, 1, D)))                 # V: one sign per dim, so no mixture of rows cancels
-        k8 = np.clip(np.rint(rng.standard_normal((HKV, nb * 64, D)) * 40), -127, 127)
-        v8 = np.clip(np.rint(sd * (50 + 25 * rng.standard_normal((HKV, nb * 64, D)))), -127, 127)
+        sd = np.sign(rng.standard_normal((hkv, 1, D)))                 # V: one sign per dim, so no mixture of rows cancels
+        k8 = np.clip(np.rint(rng.standard_normal((hkv, nb * 64, D)) * 40), -127, 127)
+        v8 = np.clip(np.rint(sd * (50 + 25 * rng.standard_normal((hkv, nb * 64, D)))), -127, 127)
         for i, p in enumerate(range(c0, T)):                           # position c0 + i is the first one row i must not see
-            for g in range(HKV):
+            for g in range(hkv):
                 qh = q[seg_first[s] + i, g * rep + i % rep].astype(np.float64)
                 k8[g, p] = np.clip(np.rint((np.log(T) + 6) * np.sqrt(D) / (qh @ qh) * qh / np.float64(ksc[mine[p // 64], g])), -127, 127)
                 v8[g, p] = -127 * sd[g, 0]
+        i8_markers(k8, v8, q[seg_first[s]:seg_first[s] + rows], marks, c0, T, rep, ksc[mine], sd)
         k8[:, T:], v8[:, T:] = -128, -128
-        codes[mine, 0] = k8.reshape(HKV, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
-        codes[mine, 1] = v8.reshape(HKV, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
+        codes[mine, 0] = k8.reshape(hkv, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
+        codes[mine, 1] = v8.reshape(hkv, nb, 64, D).transpose(1, 0, 2, 3).astype(np.int8)
         per_pos = np.repeat(mine, 64)[:T]
         k = po.kv_i8_dequantize(k8[:, :T].transpose(1, 0, 2), ksc[per_pos]).transpose(1, 0, 2)   # the codes actually in the pages
         v = po.kv_i8_dequantize(v8[:, :T].transpose(1, 0, 2), vsc[per_pos]).transpose(1, 0, 2)
         for i in range(rows):
             want[seg_first[s] + i] = sdpa_f64(q[seg_first[s] + i][:, None], k, v, 1.0 / np.sqrt(D), c0 + i)[:, 0]
-    slab = np.zeros((N_PAGES, pb), np.uint8)
-    slab[:, :2 * HKV * 64 * D] = codes.reshape(N_PAGES, -1).view(np.uint8)
-    slab[:, 2 * HKV * 64 * D:2 * HKV * 64 * D + 4 * HKV] = scales.reshape(N_PAGES, -1).view(np.uint8)
+        if details is not None:
+            details.append((k, v, c0, rows, marks, (k8[:, :T], v8[:, :T], ksc[mine], vsc[mine])))
+    slab = np.zeros((n_pages, pb), np.uint8)
+    slab[:, :2 * hkv * 64 * D] = codes.reshape(n_pages, -1).view(np.uint8)
+    slab[:, 2 * hkv * 64 * D:2 * hkv * 64 * D + 4 * hkv] = scales.reshape(n_pages, -1).view(np.uint8)
     return q, slab, tables, row_seq, row_ctx, seg_first, want
+
+
+def lift_k_scales(ksc, page_ids):
+    """The K scales of the pages that hold a long case's markers: 1/32 + a quarter of the drawn one (exact in fp16, still distinct), so
+    that codes aligned with a query reach a score of ln T without clipping at 127."""
+    if len(page_ids):
+        ksc[page_ids] = (np.float32(2.0 ** -5) + ksc[page_ids].astype(np.float32) / 4).astype(np.float16)
+
+
+def i8_markers(k8, v8, q, marks, c0, T, rep, ksc, sd, bump=1.0, own_bump=2.0):
+    """needle_markers of tests/test_gpu_spec_batch.py in codes, under each page's scale: marker i's K codes aligned with the query of row
+    (i // rep) % rows, head i % rep, scored ~ln T + bump, its V codes 60 .. 117 of the dims' signs, -127 (against the sign) in dim 7 i % D; once there are
+    markers, position c0 + j (its V stays -127) is aligned with row j's query (ln T + own_bump) and with row j + 1's, whose own it is."""
+    hkv, _, D = k8.shape
+
+    def aligned(row, g, i, b):
+        qh = q[row, g * rep + i % rep].astype(np.float64)
+        return (np.log(T) + b) * np.sqrt(D) / (qh @ qh) * qh
+
+    for i, p in enumerate(marks + (list(range(c0, T)) if marks else [])):
+        for g in range(hkv):
+            kp = aligned((i // rep) % q.shape[0], g, i, bump) if p < c0 else aligned(p - c0, g, i, own_bump) + aligned(p - c0 + 1, g, i + 1, bump)
+            k8[g, p] = np.clip(np.rint(kp / np.float64(ksc[p // 64, g])), -127, 127)
+            if p < c0:
+                v8[g, p] = (60 + 3 * (i % 20)) * sd[g, 0]
+                v8[g, p, 7 * i % D] = -127 * sd[g, 0, 7 * i % D]
 
 
 @pytest.mark.parametrize("dt", ["bfloat16", "float16"])
