@@ -58,7 +58,8 @@ enum {
     PIE_KNOB_FUSE_ATTN = 10,         /* 0: the step's attention as its own launch instead of behind the q|k|v launch's XCD-local seam (32 / 8 / 128 heads; bit-identical; read per step enqueue / graph capture) */
     PIE_KNOB_ATTN_MERGE_IN_LAUNCH = 11, /* 0: the fused launch leaves the split-KV partials to o_proj's merging prologue instead of finishing every query head itself (bit-identical; read where the q|k|v launch is enqueued / captured) */
     PIE_KNOB_PREFILL_RESIDENT_KB = 12, /* the PIE_KNOB_PREFILL_RESIDENT budget in KiB; set (>= 0) it takes precedence.  It exists so that tests can admit some matrices of a small model and refuse others */
-    PIE_KNOB_COUNT = 13
+    PIE_KNOB_CHUNK_SPLITS = 13,      /* n >= 1: pie_decoder_step_mixed with PIE_OPT_CHUNK_BATCHED cuts its chunks' keys into n splits (clamped as pie_prefill_attn_paged_splits clamps) instead of that rule's count; 0 / default: the rule */
+    PIE_KNOB_COUNT = 14
 };
 #define PIE_KNOB_DEFAULT (-1)
 int pie_set_knob(int knob, int value);
@@ -1019,12 +1020,16 @@ size_t pie_decoder_step_bytes(const pie_decoder *d, int T, int with_logits);
  * pie_paged_*_i8 below): new rows are quantised with their page's scales, the step's attention reads them back.  Changing an option drops the
  * captured graphs.  PIE_OPT_VERIFY_MFMA = 3 (default 0): while set, and the decoder is on T pages, pie_decoder_spec_step_batch and
  * pie_decoder_spec_step_batch_tail take their split count from pie_paged_attn_verify_mfma_splits and attend through pie_paged_attn_verify_mfma's
- * kernel; with PIE_OPT_KV_I8 it does nothing, nothing else reads it, and no graph is dropped.  pie_decoder_status: synchronises the device and reports a give-up of a bounded wait of the tensor-parallel collectives in
+ * kernel; with PIE_OPT_KV_I8 it does nothing, nothing else reads it, and no graph is dropped.  PIE_OPT_CHUNK_BATCHED = 4 (default 0):
+ * while set, and the decoder is on T pages, pie_decoder_step_mixed attends all chunks of the pass through pie_prefill_attn_paged's kernel -- one
+ * launch per layer and 32 chunks, split over keys by pie_prefill_attn_paged_splits (PIE_KNOB_CHUNK_SPLITS overrides), its partials in a workspace
+ * the decoder owns and grows before the pass launches anything -- instead of one prompt-attention launch per chunk; with PIE_OPT_KV_I8 it does
+ * nothing, nothing else reads it, and no graph is dropped (no graph holds that pass).  pie_decoder_status: synchronises the device and reports a give-up of a bounded wait of the tensor-parallel collectives in
  * *error (0 = none; sticky; that step's token is -1); bit 31: the fused q|k|v + attention launch (32 / 8 / 128 head geometry, PIE_KNOB_FUSE_ATTN) gave up
  * waiting for its kv-group (the producers of a group must get dispatched while its <= 128 attention workgroups spin: guaranteed for up to five such
  * launches in flight on a full device; the library fuses only while a process holds at most four decoders; a process that masks CUs sets
  * PIE_KNOB_FUSE_ATTN = 0).  Results after a give-up are not valid. */
-enum { PIE_OPT_KV_I8 = 2, PIE_OPT_VERIFY_MFMA = 3 };
+enum { PIE_OPT_KV_I8 = 2, PIE_OPT_VERIFY_MFMA = 3, PIE_OPT_CHUNK_BATCHED = 4 };
 int pie_decoder_configure(pie_decoder *d, int option, int value);
 int pie_decoder_status(pie_decoder *d, unsigned *error);
 
@@ -1203,6 +1208,19 @@ int pie_paged_attn_verify_i8(const void *q, const void *slab, size_t n_pages, si
 int pie_prefill_attn_i8(const void *q, const void *slab, size_t n_pages, size_t slab_bytes, const int32_t *block_tables, int n_seqs, int max_blocks,
                         const int32_t *chunks_host, int n_chunks, int N, int n_heads, int n_kv_heads, int head_dim, int dtype, float scale, void *out,
                         void *stream);
+/* pie_prefill_attn_i8's contract on T pages: the same q / out, block tables, chunk descriptors, clamps, checks and error codes;
+ * slab = a layer's slab of T pages (K block then V block, each [n_kv_heads, 64, head_dim]), slab_bytes its size -- fewer than n_pages such
+ * pages: PIE_E_SHAPE.  One MFMA launch per 32 chunks over (n_kv_heads x splits x query tiles, chunks) workgroups; a split is a run of whole
+ * pages of the keys a query tile sees.  splits 1: the rows are stored directly, bit for bit what pie_sdpa_prefill stores for each chunk
+ * launched alone.  splits > 1: fp32 partials per (chunk row, head, split) in `workspace` (pie_prefill_attn_paged_workspace_bytes; 0 for one
+ * split) and a second launch that merges them in split order and writes the chunks' rows, no other; a null workspace is then PIE_E_ARG.
+ * splits 0 = pie_prefill_attn_paged_splits: 1 while the launch's query tiles x n_kv_heads reach 256 workgroups, else enough to reach them,
+ * at most 32, at most half the pages of the longest chunk (a split keeps two pages), and at most what 64 MiB of partials hold at head_dim 128. */
+int pie_prefill_attn_paged_splits(const int32_t *chunks_host, int n_chunks, int n_heads, int n_kv_heads);
+size_t pie_prefill_attn_paged_workspace_bytes(const int32_t *chunks_host, int n_chunks, int n_heads, int head_dim, int splits);
+int pie_prefill_attn_paged(const void *q, const void *slab, size_t n_pages, size_t slab_bytes, const int32_t *block_tables, int n_seqs, int max_blocks,
+                           const int32_t *chunks_host, int n_chunks, int N, int n_heads, int n_kv_heads, int head_dim, int dtype, float scale, int splits,
+                           void *out, void *workspace, void *stream);
 /* pie_paged_attn_verify on the MFMA units: the same T pages, arguments, index arrays, clamps, checks and error codes, and
  * pie_paged_attn_verify_workspace_bytes for the workspace.  One launch over (n_kv_heads, splits, B) workgroups -- the segment's (row, head)
  * pairs are one or two 32-column operands of v_mfma_f32_32x32x16, a page's K and V rows of a kv-head are read once for all of them -- and

@@ -16,12 +16,13 @@ PIE_BF16, PIE_F16 = 1, 2
 PIE_STEP_LOGITS, PIE_STEP_GRAPH = 1, 2
 PIE_OPT_KV_I8 = 2
 PIE_OPT_VERIFY_MFMA = 3
+PIE_OPT_CHUNK_BATCHED = 4
 PIE_SAMPLE_GREEDY = -1  # pie_decoder_set_sampler: the greedy tail
 PIE_TOP_LOGPROBS_MAX = 20  # pie_top_logprobs: the largest n
 # test / tuning switches (include/pie_hip.h: pie_set_knob); -1 restores a default
 KNOBS = {"prefill_min": 0, "prefill_chunk": 1, "prefill_resident": 2, "small_m": 3, "w4l_slabs": 4, "prefill_attn_valu": 5,
          "prefill_qt": 6, "attn_merge_max_cap": 7, "attn_warm_max_mb": 8, "w4r": 9, "fuse_attn": 10, "attn_merge_in_launch": 11,
-         "prefill_resident_kb": 12}
+         "prefill_resident_kb": 12, "chunk_splits": 13}
 PIE_I8 = 3  # KV page storage: int8 rows + per-head fp16 scales
 # weight formats (pie_decoder_config.weight_format; pie_layer_weights / pie_global_weights fmt_* take PIE_W_* + 1, 0 = the decoder's)
 PIE_W_INT4_G64, PIE_W_DENSE, PIE_W_INT8_G64, PIE_W_INT4_G32, PIE_W_INT8_G32, PIE_W_INT2_G64, PIE_W_INT6_G64 = range(7)
@@ -66,7 +67,7 @@ EXPORTS = [
     "pie_ngram_draft_rows_workspace_bytes", "pie_ngram_draft_rows",
     "pie_spec_verify_rows_workspace_bytes", "pie_spec_verify_rows", "pie_decoder_spec_batch_workspace_bytes", "pie_decoder_spec_step_batch",
     "pie_spec_verify_rows_sampled_workspace_bytes", "pie_spec_verify_rows_sampled", "pie_decoder_spec_batch_tail_workspace_bytes", "pie_decoder_spec_step_batch_tail",
-    "pie_prefill_attn_i8",
+    "pie_prefill_attn_i8", "pie_prefill_attn_paged_splits", "pie_prefill_attn_paged_workspace_bytes", "pie_prefill_attn_paged",
 ]
 
 
@@ -264,6 +265,11 @@ def load() -> C.CDLL:
     lib.pie_prefill_attn_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_void_p]
     lib.pie_paged_attn_verify_i8.argtypes =[C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3
     lib.pie_paged_attn_verify_mfma_splits.argtypes = [C.c_int] * 3
+    lib.pie_prefill_attn_paged_splits.argtypes = [C.c_void_p] + [C.c_int] * 3
+    lib.pie_prefill_attn_paged_workspace_bytes.restype = C.c_size_t
+    lib.pie_prefill_attn_paged_workspace_bytes.argtypes = [C.c_void_p] + [C.c_int] * 4
+    lib.pie_prefill_attn_paged.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 +
+                                           [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     lib.pie_paged_attn_verify_mfma.argtypes = lib.pie_paged_attn_verify.argtypes
     lib.pie_ngram_draft_rows_workspace_bytes.restype = C.c_size_t
     lib.pie_ngram_draft_rows_workspace_bytes.argtypes = [C.c_int]

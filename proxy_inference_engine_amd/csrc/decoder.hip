@@ -27,8 +27,8 @@ constexpr int PROF_QKV = 16, PROF_O = 20, PROF_GU = 24, PROF_DOWN = 28;
 #endif
 }
 namespace {
-int g_knobs[PIE_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-static_assert(PIE_KNOB_COUNT == 13, "one PIE_KNOB_DEFAULT per knob");
+int g_knobs[PIE_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(PIE_KNOB_COUNT == 14, "one PIE_KNOB_DEFAULT per knob");
 }
 int pie_knob(int knob) { return knob >= 0 && knob < PIE_KNOB_COUNT ? g_knobs[knob] : PIE_KNOB_DEFAULT; }
 namespace pie {
@@ -832,9 +832,13 @@ void *pie_debug_buffer(pie_decoder *d, int which) {
 
 int pie_decoder_configure(pie_decoder *d, int option, int value) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_configure: null decoder");
-    PIE_REQUIRE(option == PIE_OPT_KV_I8 || option == PIE_OPT_VERIFY_MFMA, PIE_E_ARG, "pie_decoder_configure: unknown option");
+    PIE_REQUIRE(option == PIE_OPT_KV_I8 || option == PIE_OPT_VERIFY_MFMA || option == PIE_OPT_CHUNK_BATCHED, PIE_E_ARG, "pie_decoder_configure: unknown option");
     if (option == PIE_OPT_VERIFY_MFMA) {  // read by the batched speculative pass alone, which no graph holds: nothing to plan or drop
         d->verify_mfma = value != 0;
+        return PIE_OK;
+    }
+    if (option == PIE_OPT_CHUNK_BATCHED) {  // read by the mixed pass alone (prefill_varlen_t), which no graph holds either
+        d->chunk_batched = value != 0;
         return PIE_OK;
     }
     d->kv_i8 = value != 0;

@@ -22,6 +22,7 @@
 #include "gemm_rows.hpp"  // the many-row GEMM family of w4m_gemm.hip: W4mRope, W4lSlabs, the int4 entry (prefill_attn.hpp comes with it)
 #include "paged_attn_verify.hpp"
 #include "prefill_attn_i8.hpp"
+#include "prefill_attn_paged.hpp"
 #include "speculative.hpp"
 
 // ---------------------------------------------------------------- kernels
@@ -371,6 +372,8 @@ struct PrefillScratch {
     unsigned batch_gen = 0, warm_gen = 0;
     void *w4l_ws = nullptr;   // fp32 partial tiles of the K-split prompt GEMM (w4m_gemm.hip)
     size_t w4l_ws_bytes = 0;
+    void *chunk_ws = nullptr;  // fp32 split-KV partials of the chunks of a mixed pass (prefill_attn_paged.hip; PIE_OPT_CHUNK_BATCHED): the largest pass seen
+    size_t chunk_ws_bytes = 0;
     int resident_mode = -1;   // -1: budget not fixed yet
     size_t resident_left = 0; // bytes still available for resident copies
 };
@@ -399,6 +402,7 @@ static void scratch_release(PrefillScratch *s) {  // the chunk buffers; resident
     PrefillScratch fresh;  // everything back to its default, except what survives:
     fresh.resident = std::move(s->resident), fresh.resident_w4m = std::move(s->resident_w4m), fresh.resident_mode = s->resident_mode, fresh.resident_left = s->resident_left;
     fresh.tail_stats = s->tail_stats, fresh.tail_entries = s->tail_entries, fresh.w4l_ws = s->w4l_ws, fresh.w4l_ws_bytes = s->w4l_ws_bytes;
+    fresh.chunk_ws = s->chunk_ws, fresh.chunk_ws_bytes = s->chunk_ws_bytes;
     fresh.alloc_gen = s->alloc_gen + 1;  // the chunk buffers move: captured launches are stale
     *s = std::move(fresh);
 }
@@ -410,6 +414,7 @@ void prefill_free(pie_decoder *d) {
     for (auto &kv : d->prefill->resident_w4m) (void)hipFree(kv.second);
     if (d->prefill->tail_stats) (void)hipFree(d->prefill->tail_stats);
     if (d->prefill->w4l_ws) (void)hipFree(d->prefill->w4l_ws);
+    if (d->prefill->chunk_ws) (void)hipFree(d->prefill->chunk_ws);
     delete d->prefill;
     d->prefill = nullptr;
 }
@@ -1044,6 +1049,21 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
     RowsKv kv;  // rows of a sequence share its block-table row; K / V also go to the contiguous copies this pass's own attention reads
     kv.row_ctx = row_ctx, kv.slabs = slabs, kv.block_tables = block_tables, kv.bt_stride = max_blocks, kv.n_pages = n_pages, kv.i8 = d->kv_i8;
     kv.row_seq = row_seq, kv.kc = s->kc, kv.vc = s->vc;
+    // PIE_OPT_CHUNK_BATCHED on T pages: every chunk of the pass in one launch per layer, its split count and the partials'
+    // workspace settled here, before the pass launches anything (no graph holds this pass: the buffer may move)
+    const bool chunks_batched = n_chunks > 0 && d->chunk_batched && !d->kv_i8;
+    int csplits = 1;
+    if (chunks_batched) {
+        const int forced = pie_knob(PIE_KNOB_CHUNK_SPLITS);
+        csplits = prefill_attn_paged_splits(chunks, n_chunks, c.n_kv_heads, c.n_heads / c.n_kv_heads, forced > 0 ? forced : 0);
+        const size_t need = prefill_attn_paged_workspace_bytes(chunks, n_chunks, c.n_heads, D, csplits);
+        if (need > s->chunk_ws_bytes) {
+            if (s->chunk_ws) (void)hipFree(s->chunk_ws);
+            s->chunk_ws = nullptr, s->chunk_ws_bytes = 0;
+            PIE_HIP_TRY(hipMalloc(&s->chunk_ws, need));
+            s->chunk_ws_bytes = need;
+        }
+    }
     rc = paged_rows_layers<T>(d, ids, N, kv, st, [&](int li) {
         PrefillAttnArgs pa = {};
         pa.q = s->q, pa.k = s->kc, pa.v = s->vc, pa.offset = 0, pa.cap = N, pa.seg_lo = seg_lo, pa.seg_hi = seg_hi;
@@ -1056,6 +1076,17 @@ static int prefill_varlen_t(pie_decoder *d, const int32_t *ids, const int32_t *r
             ia.q = s->q, ia.slab = slabs[li], ia.block_tables = block_tables, ia.out = s->attn;
             ia.Hq = c.n_heads, ia.Hkv = c.n_kv_heads, ia.bt_stride = max_blocks, ia.n_pages = n_pages, ia.scale = pa.scale;
             return prefill_attn_i8_launch(c.dtype, D, ia, chunks, n_chunks, st);
+        }
+        if (!rc && chunks_batched) {  // ... on T pages with the option: one split-KV launch per 32 chunks, and their rows' merge
+            PrefillPagedArgs ta = {};
+            ta.q = s->q, ta.slab = (const u16 *)slabs[li], ta.block_tables = block_tables, ta.out = s->attn;
+            ta.Hq = c.n_heads, ta.Hkv = c.n_kv_heads, ta.bt_stride = max_blocks, ta.n_pages = n_pages, ta.scale = pa.scale, ta.splits = csplits;
+            if (csplits > 1) {
+                size_t rows = 0;
+                for (int ci = 0; ci < n_chunks; ++ci) rows += (size_t)chunks[4 * ci + 1];
+                ta.part_acc = (float *)s->chunk_ws, ta.part_ml = ta.part_acc + rows * c.n_heads * csplits * D;
+            }
+            return prefill_attn_paged_launch(c.dtype, D, ta, chunks, n_chunks, st);
         }
         for (int ci = 0; ci < n_chunks && !rc; ++ci) {  // prompts continuing a cached prefix: causal attention over their pages from the cached length
             const int32_t *ch = chunks + 4 * ci;

@@ -12,7 +12,8 @@ frequency and presence penalties over the counts of what it has generated (DESIG
 `sampler` maps a [B, V] log-probability block to B token ids;
 `generate(logprobs=True, top_logprobs=...)` also returns every token's top-n log-probabilities, selected per row inside the passes (DESIGN.md 13);
 `generate(prompt_logprobs=...)` also returns the log-probabilities of the prompts' own tokens, scored inside the prompt passes (DESIGN.md 16);
-`BatchedEngine(kv_dtype=torch.int8, int8_chunks=True)` keeps chunked prefill and shared prefixes on an int8 pool."""
+`BatchedEngine(kv_dtype=torch.int8, int8_chunks=True)` keeps chunked prefill and shared prefixes on an int8 pool (DESIGN.md 27);
+`BatchedEngine(batched_chunks=True)` attends every continuing prompt of a pass on a 16-bit pool in one split-KV launch per layer."""
 from __future__ import annotations
 
 from collections import deque
@@ -577,7 +578,7 @@ class BatchedEngine:
     def __init__(self, model, num_pages: int = 1024, max_batch: int = 32, stop_tokens: Iterable[int] = (),
                  sampler: Callable[[torch.Tensor], torch.Tensor] | None = None, batch_prefill: bool = True, max_prefill_rows: int = 4096,
                  kv_dtype: torch.dtype | None = None, kv_scales=None, mixed: bool = True, prefill_chunk: int | None = None, share_prefix: bool = False,
-                 speculative=None, *, int8_chunks: bool = False):
+                 speculative=None, *, int8_chunks: bool = False, batched_chunks: bool = False):
         """kv_dtype=torch.int8 (+ kv_scales = (k, v) float16 [n_layers, n_kv_heads]): the pool holds the reference KVPage's int8 pages with
         per-head scales (page.hpp:25-32) -- half the cache bytes per token, so twice the sequences / context per pool.
         speculative=SpeculativeParams(num_draft=, ngram_max=, ngram_min=, min_draft=): greedy prompt-lookup speculation for
@@ -600,7 +601,11 @@ class BatchedEngine:
         otherwise switched off: the passes that carry prompt rows are then Model.step_mixed(..., int8_pages=True).  A prompt's first chunk
         (and the shared prefix) attends its own rows unquantised, as a whole prompt on int8 pages does; every later chunk and every suffix
         attends its own rows as codes, as a decode step does -- so the tokens agree with the unchunked int8 engine's within the int8-page
-        bound, not bit for bit.  On a 16-bit pool the flag does nothing; tensor-parallel models stay refused as they are."""
+        bound, not bit for bit.  On a 16-bit pool the flag does nothing; tensor-parallel models stay refused as they are.
+        batched_chunks=True: on a 16-bit pool the passes that carry prompt rows are Model.step_mixed(..., batched_chunks=True)
+        -- the chunks of long prompts and the suffixes behind a shared prefix attend their pages in one split-KV MFMA launch per layer
+        instead of one launch each; the same schedule and pages, the same tokens while the kernel's rule takes one split.  On an int8
+        pool the flag does nothing (int8_chunks=True is that pool's one-launch form)."""
         if speculative is not None:
             who = "BatchedEngine(speculative=...): "
             for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8 and not getattr(speculative, "int8_pages", False), "kv_dtype=torch.int8 (int8 KV pages)"),
@@ -615,6 +620,7 @@ class BatchedEngine:
         self.pool = model.enable_paged_kv(num_pages=num_pages, kv_dtype=kv_dtype, kv_scales=kv_scales)
         self._i8 = self.pool.dtype == torch.int8   # int8 pages are written by the batch paths only: lone prompts go through prefill_batch too
         self._i8_chunks = self._i8 and bool(int8_chunks)   # continuing prompts on int8 pages: step_mixed is told so, and only then
+        self._batched_chunks = not self._i8 and bool(batched_chunks)   # continuing prompts on 16-bit pages in one launch: told only then
         self.max_batch = max_batch
         self.stop_tokens = set(int(t) for t in stop_tokens)
         self.sampler = sampler
@@ -726,7 +732,8 @@ class BatchedEngine:
             elif not active and not self.prefill_chunk and P == 0:          # fresh whole prompts alone (int8 pages take prompts through this entry only)
                 nxt, logprobs, _ = self.model.prefill_batch(rows, into)
             else:
-                nxt, logprobs, _ = self.model.step_mixed(tokens, caches, rows, into, **({"int8_pages": True} if self._i8_chunks else {}))
+                nxt, logprobs, _ = self.model.step_mixed(tokens, caches, rows, into, **({"int8_pages": True} if self._i8_chunks else {}),
+                                                         **({"batched_chunks": True} if self._batched_chunks else {}))
         self.steps += bool(active or self.prefill_chunk)                     # a decode step, or the chunked pass (which stands for one)
         self.mixed_passes += bool(active and parts)
         if self.sampler is not None:

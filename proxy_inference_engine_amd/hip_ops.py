@@ -1614,6 +1614,34 @@ def prefill_attn_i8(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_tab
     return out
 
 
+def prefill_attn_paged(q: torch.Tensor, slab: torch.Tensor, n_pages: int, block_tables: torch.Tensor, chunks, n_kv_heads: int, scale: float,
+                       splits: int = 0) -> torch.Tensor:
+    """prefill_attn_i8's contract on 16-bit pages (pie_prefill_attn_paged): q [N, Hq, D], slab = a layer's slab of T pages
+    (K block then V block, each [n_kv_heads, 64, D]), block_tables int32 [n_seqs, max_blocks], chunks = HOST rows of {first row, rows M,
+    cached positions P >= 1, block-table row}.  One split-KV MFMA launch per 32 chunks (one more to merge the splits' partials).
+    splits: 0 = pie_prefill_attn_paged_splits, else 1..32; with 1 the rows are bit for bit sdpa_prefill's of each chunk launched alone.
+    Returns [N, Hq, D]: rows outside every chunk are zero."""
+    import numpy as np
+    for t in (q, slab, block_tables):
+        _dev(t)
+    if block_tables.dtype != torch.int32:
+        raise TypeError("prefill_attn_paged: block_tables must be int32")
+    if q.dim() != 3 or block_tables.dim() != 2:
+        raise ValueError("prefill_attn_paged: q [N, Hq, D]; block_tables [n_seqs, max_blocks]")
+    if not 0 <= int(splits) <= 32:
+        raise ValueError("prefill_attn_paged: splits is 0 (chosen by the library) or 1..32")
+    ch = np.ascontiguousarray(np.asarray(chunks, dtype=np.int32).reshape(-1, 4))
+    N, Hq, D = q.shape
+    lib = _ffi.load()
+    used = int(splits) or int(lib.pie_prefill_attn_paged_splits(ch.ctypes.data, len(ch), Hq, int(n_kv_heads)))
+    ws = torch.empty(max(int(lib.pie_prefill_attn_paged_workspace_bytes(ch.ctypes.data, len(ch), Hq, D, used)), 16), dtype=torch.uint8, device=q.device)
+    out = torch.zeros_like(q)
+    _ffi.check(lib.pie_prefill_attn_paged(_ffi.p(q), _ffi.p(slab), n_pages, slab.numel() * slab.element_size(), _ffi.p(block_tables), block_tables.shape[0],
+                                          block_tables.shape[1], ch.ctypes.data, len(ch), N, Hq, int(n_kv_heads), D, _ffi.dtype_code(q.dtype), float(scale),
+                                          int(splits), _ffi.p(out), _ffi.p(ws), _ffi.stream()))
+    return out
+
+
 def paged_attn_verify_mfma_splits(B: int, n_kv_heads: int, max_blocks: int) -> int:
     """The splits paged_attn_verify_mfma(splits=0) cuts a segment's positions into (pie_paged_attn_verify_mfma_splits)."""
     return int(_ffi.load().pie_paged_attn_verify_mfma_splits(int(B), int(n_kv_heads), int(max_blocks)))

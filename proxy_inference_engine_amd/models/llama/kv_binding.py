@@ -123,6 +123,7 @@ class KVBinding:
         self.offset = None   # device-side cache offset the decoder believes in: after advance(), the position the chosen token will occupy
         self._i8 = None      # the decoder's page format (PIE_OPT_KV_I8); None until a pool was seen
         self._verify_mfma = False   # the decoder's PIE_OPT_VERIFY_MFMA as last set here (its default: off)
+        self._chunk_batched = False  # ... and its PIE_OPT_CHUNK_BATCHED
 
     def sync(self, cache, n_new: int) -> None:
         """Room for `n_new` more rows in every layer, then the decoder bound to them; all layers are checked before the first allocation."""
@@ -164,6 +165,12 @@ class KVBinding:
         if self._verify_mfma != bool(mfma):
             _ffi.check(self.lib.pie_decoder_configure(self.dec, _ffi.PIE_OPT_VERIFY_MFMA, int(bool(mfma))))
             self._verify_mfma = bool(mfma)
+
+    def match_chunk_kernel(self, batched: bool) -> None:
+        """The attention of a mixed pass's continuing prompts on T pages (PIE_OPT_CHUNK_BATCHED): configured only when it changes."""
+        if self._chunk_batched != bool(batched):
+            _ffi.check(self.lib.pie_decoder_configure(self.dec, _ffi.PIE_OPT_CHUNK_BATCHED, int(bool(batched))))
+            self._chunk_batched = bool(batched)
 
     def pool_args(self, allocator):
         """(per-layer slab planes, pages, bytes of one plane) as the paged entry points take them, the decoder set to the pool's format."""

@@ -890,7 +890,7 @@ class Model(RowsTailState, StepTailState):
         return self._varlen_pass("prefill_batch", None, [], prompts, caches)
 
     def step_mixed(self, tokens: torch.Tensor | None, decode_caches: list[list[BaseCache]], prompts: list, prompt_caches: list[list[BaseCache]], *,
-                   int8_pages: bool = False):
+                   int8_pages: bool = False, batched_chunks: bool = False):
         """Decode-state sequences AND fresh prompts in one pass over the weights (pie_decoder_step_mixed; the reference's BatchDetails holds
         both kinds, batch_details.hpp:10-88): tokens [B] = the input token of each decoding sequence (caches as in step_batch), prompts /
         prompt_caches as in prefill_batch -- or caches that already hold a PREFIX (offset > 0: the next chunk of a long prompt, or a suffix
@@ -901,10 +901,13 @@ class Model(RowsTailState, StepTailState):
         attend the sequence's pages -- their own rows included -- as codes, the way a decode step does (one MFMA launch per layer for all
         such prompts), where a FRESH whole prompt on an int8 pool attends its own rows unquantised.  So a chunked or prefix-shared prompt
         agrees with the whole prompt within the int8-page bound, not bit for bit.  Without the flag such a cache is refused on an int8
-        pool, as ever; on a 16-bit pool the flag does nothing."""
-        return self._varlen_pass("step_mixed", tokens, decode_caches, prompts, prompt_caches, int8_pages)
+        pool, as ever; on a 16-bit pool the flag does nothing.
+        batched_chunks=True: on a 16-bit pool the prompts that continue a cached prefix attend their pages in ONE split-KV
+        MFMA launch per layer (pie_prefill_attn_paged, PIE_OPT_CHUNK_BATCHED) instead of one launch per prompt: the same rows and caches,
+        bit for bit while that kernel's rule takes one split, within the summation order beyond.  On an int8 pool it does nothing."""
+        return self._varlen_pass("step_mixed", tokens, decode_caches, prompts, prompt_caches, int8_pages, batched_chunks)
 
-    def _varlen_pass(self, who: str, tokens, decode_caches, prompts, caches, int8_pages: bool = False):
+    def _varlen_pass(self, who: str, tokens, decode_caches, prompts, caches, int8_pages: bool = False, batched_chunks: bool = False):
         import numpy as np
         every = self._kv.sequences(who, list(decode_caches) + list(caches))
         B = len(decode_caches)
@@ -958,6 +961,7 @@ class Model(RowsTailState, StepTailState):
         lib = _ffi.load()
         head = (self._dec, _ffi.p(t_ids), _ffi.p(t_ctx), _ffi.p(t_seq), _ffi.p(t_lo), _ffi.p(t_hi), _ffi.p(t_last), B + N, B + S)
         tail = (*self._kv.pool_args(a), _ffi.p(t_table), mb, _ffi.p(logits), _ffi.p(logprobs), _ffi.p(nxt))
+        self._kv.match_chunk_kernel(batched_chunks)
         if B or len(chunks):
             _ffi.check(lib.pie_decoder_step_mixed(*head, B, *tail, len(chunks), chunks.ctypes.data if len(chunks) else None, _ffi.stream()))
         else:
