@@ -1024,12 +1024,18 @@ size_t pie_decoder_step_bytes(const pie_decoder *d, int T, int with_logits);
  * while set, and the decoder is on T pages, pie_decoder_step_mixed attends all chunks of the pass through pie_prefill_attn_paged's kernel -- one
  * launch per layer and 32 chunks, split over keys by pie_prefill_attn_paged_splits (PIE_KNOB_CHUNK_SPLITS overrides), its partials in a workspace
  * the decoder owns and grows before the pass launches anything -- instead of one prompt-attention launch per chunk; with PIE_OPT_KV_I8 it does
- * nothing, nothing else reads it, and no graph is dropped (no graph holds that pass).  pie_decoder_status: synchronises the device and reports a give-up of a bounded wait of the tensor-parallel collectives in
+ * nothing, nothing else reads it, and no graph is dropped (no graph holds that pass).  PIE_OPT_KVQ_DIRECT = 5 (default 0): while
+ * set, and the decoder is bound by pie_decoder_set_kv_quant, the many-row prompt pass (pie_decoder_prefill / _prefill_embeds of 6+ rows) expands
+ * no prefix: q|k|v + RoPE append the chunk's T rows to a chunk-sized scratch, the rows are quantized into the codes, and the chunk attends the
+ * codes through pie_prefill_attn_quant's kernel, split over keys by pie_prefill_attn_quant_splits at the offset the host last set plus the rows
+ * passed since (an upper bound behind a speculative pass; never beyond the capacity), its partials in a
+ * workspace the decoder owns and grows before the pass launches anything; pie_decoder_spec_step and pie_decoder_spec_step_tail then admit the
+ * quantized cache.  Nothing else reads it and no graph is dropped (no graph holds that pass).  pie_decoder_status: synchronises the device and reports a give-up of a bounded wait of the tensor-parallel collectives in
  * *error (0 = none; sticky; that step's token is -1); bit 31: the fused q|k|v + attention launch (32 / 8 / 128 head geometry, PIE_KNOB_FUSE_ATTN) gave up
  * waiting for its kv-group (the producers of a group must get dispatched while its <= 128 attention workgroups spin: guaranteed for up to five such
  * launches in flight on a full device; the library fuses only while a process holds at most four decoders; a process that masks CUs sets
  * PIE_KNOB_FUSE_ATTN = 0).  Results after a give-up are not valid. */
-enum { PIE_OPT_KV_I8 = 2, PIE_OPT_VERIFY_MFMA = 3, PIE_OPT_CHUNK_BATCHED = 4 };
+enum { PIE_OPT_KV_I8 = 2, PIE_OPT_VERIFY_MFMA = 3, PIE_OPT_CHUNK_BATCHED = 4, PIE_OPT_KVQ_DIRECT = 5 };
 int pie_decoder_configure(pie_decoder *d, int option, int value);
 int pie_decoder_status(pie_decoder *d, unsigned *error);
 
@@ -1303,7 +1309,21 @@ int pie_decoder_spec_step_batch_tail(pie_decoder *d, const int32_t *tokens, cons
  *   Steps append the new K / V rows quantized (the attention launch quantizes the row its q|k|v launch staged) and attend the cache
  *   as pie_attn_decode_quant does.  Prompts (pie_decoder_prefill / _prefill_embeds) take the batched pass over a T scratch of one layer's
  *   K / V, dequantized from the codes, with the chunk's rows quantized into the cache before its attention.  Refused (PIE_E_STATE) on
- *   tensor-parallel decoders. */
+ *   tensor-parallel decoders.
+ * pie_prefill_attn_quant: causal attention of M query rows at positions offset .. offset + M - 1 straight from the cache, which
+ *   already holds those rows' own K / V as codes: q, out T [M, n_heads, head_dim]; row r attends rows 0 .. offset + r of every kv-head.  A
+ *   32-key block is fetched as codes, converted once into LDS as T(s q + b) (mx.dequantize) and scored on the MFMA units in
+ *   pie_sdpa_prefill's order and arithmetic: with one split the output is bit for bit pie_sdpa_prefill over the dequantized rows.  splits > 1
+ *   cut a query tile's keys into runs of whole 32-key blocks, fp32 partials in `workspace` (pie_prefill_attn_quant_workspace_bytes; 0 for one
+ *   split), merged in split order by a second launch.  splits 0 = pie_prefill_attn_quant_splits: 1 while query tiles x n_kv_heads reach 256
+ *   workgroups, else enough to reach them, at most 32, a split keeping at least four blocks, and at most what 64 MiB of partials hold.
+ *   Refused before a launch: a null pointer or a null workspace with more than one split (PIE_E_ARG), the formats above, M < 1, offset < 0 or
+ *   offset + M > cap, n_heads / n_kv_heads other than 1, 2, 4, 8 (PIE_E_SHAPE), q / out off 16 bytes or codes off 8 (PIE_E_ALIGN). */
+int pie_prefill_attn_quant_splits(int M, int offset, int n_heads, int n_kv_heads);
+size_t pie_prefill_attn_quant_workspace_bytes(int M, int n_heads, int head_dim, int splits);
+int pie_prefill_attn_quant(const void *q, const void *k_codes, const void *k_scales, const void *k_biases, const void *v_codes,
+                           const void *v_scales, const void *v_biases, int n_heads, int n_kv_heads, int M, int offset, int cap, int head_dim,
+                           int group_size, int bits, float scale, int dtype, int splits, void *out, void *workspace, void *stream);
 int pie_kv_quantize(const void *x, int H, int n, int src_cap, int head_dim, int group_size, int bits, int dtype, void *codes, void *scales,
                     void *biases, int dst_cap, void *stream);
 int pie_attn_decode_quant(const void *q, const void *k_codes, const void *k_scales, const void *k_biases, const void *v_codes,

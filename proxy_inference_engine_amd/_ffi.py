@@ -17,6 +17,7 @@ PIE_STEP_LOGITS, PIE_STEP_GRAPH = 1, 2
 PIE_OPT_KV_I8 = 2
 PIE_OPT_VERIFY_MFMA = 3
 PIE_OPT_CHUNK_BATCHED = 4
+PIE_OPT_KVQ_DIRECT = 5
 PIE_SAMPLE_GREEDY = -1  # pie_decoder_set_sampler: the greedy tail
 PIE_TOP_LOGPROBS_MAX = 20  # pie_top_logprobs: the largest n
 # test / tuning switches (include/pie_hip.h: pie_set_knob); -1 restores a default
@@ -68,6 +69,7 @@ EXPORTS = [
     "pie_spec_verify_rows_workspace_bytes", "pie_spec_verify_rows", "pie_decoder_spec_batch_workspace_bytes", "pie_decoder_spec_step_batch",
     "pie_spec_verify_rows_sampled_workspace_bytes", "pie_spec_verify_rows_sampled", "pie_decoder_spec_batch_tail_workspace_bytes", "pie_decoder_spec_step_batch_tail",
     "pie_prefill_attn_i8", "pie_prefill_attn_paged_splits", "pie_prefill_attn_paged_workspace_bytes", "pie_prefill_attn_paged",
+    "pie_prefill_attn_quant_splits", "pie_prefill_attn_quant_workspace_bytes", "pie_prefill_attn_quant",
 ]
 
 
@@ -156,6 +158,10 @@ def load() -> C.CDLL:
     lib.pie_sdpa_decode.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_kv_quantize.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
     lib.pie_attn_decode_quant.argtypes = [C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pie_prefill_attn_quant_splits.argtypes = [C.c_int] * 4
+    lib.pie_prefill_attn_quant_workspace_bytes.restype = C.c_size_t
+    lib.pie_prefill_attn_quant_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.pie_prefill_attn_quant.argtypes = [C.c_void_p] * 7 + [C.c_int] * 8 + [C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pie_decoder_set_kv_quant.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6 + [C.c_int] * 3 + [C.c_void_p]
     lib.pie_sdpa_prefill.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
     lib.pie_sdpa_prefill_window.argtypes = [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]

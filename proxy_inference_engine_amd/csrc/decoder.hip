@@ -438,7 +438,7 @@ int pie_decoder_destroy(pie_decoder *d) {
     drop_graphs(d);
     prefill_free(d);
     void *ptrs[] = {d->state, d->kv_table, d->qbuf, d->attn, d->act, d->part_acc, d->part_ml, d->stats, d->rope_cs, d->pf_sink, d->seam, d->tp_part, d->kv_stage, d->kv_table_stage,
-                    d->zero_table, d->kvq_scratch, d->kvq_table, d->ring_rows, d->tail.tail_stats};
+                    d->zero_table, d->kvq_scratch, d->kvq_table, d->kvq_rows, d->ring_rows, d->tail.tail_stats};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete d;
@@ -655,6 +655,7 @@ int pie_decoder_set_state(pie_decoder *d, int offset, int token, void *stream) {
     PIE_REQUIRE(token < d->embed_vocab(), PIE_E_ARG, "pie_decoder_set_state: token id out of range");
     hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, (hipStream_t)stream, d->state, offset, token, -1);
     PIE_LAUNCH_CHECK();
+    d->pos_hint = offset;
     return PIE_OK;
 }
 
@@ -671,6 +672,7 @@ int pie_decoder_step(pie_decoder *d, int flags, void *stream) {
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool with_logits = (flags & PIE_STEP_LOGITS) != 0;
+    if (d->pos_hint >= 0) ++d->pos_hint;
     if (!(flags & PIE_STEP_GRAPH)) return enqueue_step(d, &d->state->token, with_logits, d->logits, st);
     const int gi = with_logits ? 1 : 0;
     if (d->graph[gi] && d->graph_form[gi] > attn_form(d)) drop_graphs(d);  // the captured form was withdrawn (a knob, more than four live decoders): capture what is allowed now
@@ -742,6 +744,12 @@ static int set_part(pie_decoder *d, Part &slot, const Part &v) {
 }  // namespace
 extern "C" {
 
+// pos_hint behind a pass of L rows (decoder.hpp); rc: the pass's result, handed through
+static int rows_done(pie_decoder *d, int L, int rc) {
+    if (d->pos_hint >= 0) d->pos_hint += L;
+    return rc;
+}
+
 int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_all, void *stream) {
     int rc = ready(d);
     if (rc) return rc;
@@ -755,7 +763,8 @@ int pie_decoder_prefill(pie_decoder *d, const int32_t *ids, int L, void *logits_
     // through pie_decoder_prefill_batch, which the Python host does)
     // a rotating cache takes every multi-row update through the windowed pass: a chunk is not a run of single-row updates there
     // (rotating.py: the chunk sees the retained window plus itself, a step only the newest rows)
-    if ((L >= prefill_min_rows() || (d->ring && L >= 2)) && !d->tp() && !(d->kv_i8 && d->block_table)) return prefill_batched(d, ids, nullptr, L, logits_all, st);  // MLX's qmm regime
+    if ((L >= prefill_min_rows() || (d->ring && L >= 2)) && !d->tp() && !(d->kv_i8 && d->block_table)) return rows_done(d, L, prefill_batched(d, ids, nullptr, L, logits_all, st));  // MLX's qmm regime
+    rows_done(d, L, PIE_OK);
     for (int l = 0; l < L; ++l) {
         const bool last = l == L - 1;
         u16 *dst = logits_all ? (u16 *)logits_all + (size_t)l * d->cfg.vocab : d->logits;
@@ -777,7 +786,8 @@ int pie_decoder_prefill_embeds(pie_decoder *d, const void *embeds, int L, void *
     PIE_REQUIRE(!d->prompt.n || L <= d->prompt.rows_cap, PIE_E_SHAPE, "pie_decoder_prefill_embeds: more rows than the prompt log-probabilities' rows_cap");
     const RawTail raw(d, logits_all != nullptr);
     // (one row on a rotating cache is a single-row update: the decode step below, as in rotating.py)
-    if (!(d->kv_i8 && d->block_table) && !(d->ring && L == 1)) return prefill_batched(d, nullptr, embeds, L, logits_all, st);
+    if (!(d->kv_i8 && d->block_table) && !(d->ring && L == 1)) return rows_done(d, L, prefill_batched(d, nullptr, embeds, L, logits_all, st));
+    rows_done(d, L, PIE_OK);
     // int8 pages: the batched prompt path of one sequence reads and writes T pages, so -- like a prompt of tokens (pie_decoder_prefill) -- the rows
     // run as decode steps, each with its row copied into the residual stream instead of an embedding launch (no RoPE table either: the
     // q|k|v epilogue computes its own angles).  The greedy token the tail leaves in the device-side state is that of the last row.
@@ -832,7 +842,12 @@ void *pie_debug_buffer(pie_decoder *d, int which) {
 
 int pie_decoder_configure(pie_decoder *d, int option, int value) {
     PIE_REQUIRE(d, PIE_E_ARG, "pie_decoder_configure: null decoder");
-    PIE_REQUIRE(option == PIE_OPT_KV_I8 || option == PIE_OPT_VERIFY_MFMA || option == PIE_OPT_CHUNK_BATCHED, PIE_E_ARG, "pie_decoder_configure: unknown option");
+    PIE_REQUIRE(option == PIE_OPT_KV_I8 || option == PIE_OPT_VERIFY_MFMA || option == PIE_OPT_CHUNK_BATCHED || option == PIE_OPT_KVQ_DIRECT, PIE_E_ARG,
+                "pie_decoder_configure: unknown option");
+    if (option == PIE_OPT_KVQ_DIRECT) {  // read by the many-row prompt pass on a quantized cache (prefill_t) and by spec_step's admission: no graph holds either
+        d->kvq_direct = value != 0;
+        return PIE_OK;
+    }
     if (option == PIE_OPT_VERIFY_MFMA) {  // read by the batched speculative pass alone, which no graph holds: nothing to plan or drop
         d->verify_mfma = value != 0;
         return PIE_OK;

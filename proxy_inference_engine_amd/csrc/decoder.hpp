@@ -258,6 +258,15 @@ struct pie_decoder {
     u16 *kvq_scratch = nullptr;
     unsigned long long *kvq_table = nullptr;
     int kvq_scratch_cap = 0;
+    // PIE_OPT_KVQ_DIRECT: the prompt pass expands no prefix -- the scratch holds the chunk's rows only ([n_kv, kvq_scratch_cap >= chunk, D]),
+    // kvq_rows is a second DecState whose pos is 0 and whose cap is the scratch's (ring_rows' trick: the append kernels stay as they are), the
+    // rows are quantized into the codes and the chunk attends them through prefill_attn_quant.hip.  Read by prefill_t and spec_step alone.
+    bool kvq_direct = false;
+    DecState *kvq_rows = nullptr;
+    // The host's view of state->pos, which itself lives on the device: what pie_decoder_set_state wrote, plus one per pie_decoder_step and L per
+    // many-row pass since -- exact under steps and prompts, an UPPER bound after a speculative pass (which leaves pos at the accepted row) until
+    // the next pie_decoder_set_state; -1: never set.  Only a planning hint (the direct pass's split count): no launch's correctness reads it.
+    long long pos_hint = -1;
     // RotatingKVCache (pie_decoder_set_kv_ring) over the contiguous buffers of pie_decoder_set_kv: the window / sink rows live in the
     // device-side state (the step finds its row and length from pos); the q|k|v epilogue stages the new rows as for quantized KV and the
     // attention launch (RING) moves them into their ring slot.  ring_rows: a second DecState whose pos is the buffer row of the prompt

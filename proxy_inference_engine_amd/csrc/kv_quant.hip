@@ -409,8 +409,38 @@ __global__ void __launch_bounds__(256) k_kv_requant_chunk(QKvLayer lay, const De
     *reinterpret_cast<uint4 *>(src) = make_uint4(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]), pack2<T>(o[4], o[5]), pack2<T>(o[6], o[7]));
 }
 
+// PIE_OPT_KVQ_DIRECT: rows [0, M) of the chunk-sized T scratch ck / cv [Hkv, src_cap, D] -> the codes of rows [pos, pos + M) of the cache; the
+// scratch is left as it is (the chunk attends the codes: prefill_attn_quant.hip)
 template <class T, int D, int BITS>
-int prefill_quant_t(bool dequant, const QKvLayer &lay, const DecState *state, int Hkv, int cap, int M, int gs, u16 *sk, u16 *sv, hipStream_t st) {
+__global__ void __launch_bounds__(256) k_kv_quant_chunk(QKvLayer lay, const DecState *state, int Hkv, int cap, int M, int gs, const u16 *ck, const u16 *cv, int src_cap) {
+    constexpr int LPT = D / 8, CW = D * BITS / 32;
+    const long long r = (long long)blockIdx.x * (256 / LPT) + threadIdx.x / LPT;
+    const long long total = (long long)Hkv * M;
+    const long long rc = r < total ? r : total - 1;  // whole rows idle together (quant_piece's shuffles stay inside a row)
+    const int dc = threadIdx.x % LPT, hd = (int)(rc / M), m = (int)(rc % M);
+    const bool v = blockIdx.y == 1;
+    float x[8];
+    load_piece<T>((v ? cv : ck) + ((size_t)hd * src_cap + m) * D + dc * 8, x);
+    const QPiece<BITS> p = quant_piece<T, BITS>(x, gs / 8);
+    const long long pos = (long long)state->pos + m;
+    if (r >= total || pos >= cap) return;  // (a row past the capacity is never written: the host made room for the pass)
+    const size_t row = (size_t)hd * cap + (size_t)pos;
+    const int G = D / gs;
+    store_piece<T, BITS>(p, dc, gs, const_cast<u32 *>(v ? lay.vc : lay.kc) + row * CW, const_cast<u16 *>(v ? lay.vs : lay.ks) + row * G,
+                         const_cast<u16 *>(v ? lay.vb : lay.kb) + row * G);
+}
+
+template <class T, int D, int BITS>
+int quant_chunk_t(const QKvLayer &lay, const DecState *state, int Hkv, int cap, int M, int gs, const u16 *ck, const u16 *cv, int src_cap, hipStream_t st) {
+    const int per_block = 256 / (D / 8);
+    const dim3 grid((unsigned)(((long long)Hkv * M + per_block - 1) / per_block), 2), block(256);
+    hipLaunchKernelGGL((k_kv_quant_chunk<T, D, BITS>), grid, block, 0, st, lay, state, Hkv, cap, M, gs, ck, cv, src_cap);
+    PIE_LAUNCH_CHECK();
+    return PIE_OK;
+}
+
+template <class T, int D, int BITS>
+int prefill_quant_t(bool dequant,const QKvLayer &lay, const DecState *state, int Hkv, int cap, int M, int gs, u16 *sk, u16 *sv, hipStream_t st) {
     const long long rows = dequant ? (long long)Hkv * cap : (long long)Hkv * M;
     const int per_block = 256 / (D / 8);
     const dim3 grid((unsigned)((rows + per_block - 1) / per_block), 2), block(256);
@@ -429,6 +459,16 @@ int kv_quant_prefill_launch(int dtype, int D, int bits, bool dequant, const QKvL
     }
     if (D == 128) return bits == 4 ? prefill_quant_t<F16, 128, 4>(dequant, lay, state, Hkv, cap, M, gs, sk, sv, st) : prefill_quant_t<F16, 128, 8>(dequant, lay, state, Hkv, cap, M, gs, sk, sv, st);
     return bits == 4 ? prefill_quant_t<F16, 64, 4>(dequant, lay, state, Hkv, cap, M, gs, sk, sv, st) : prefill_quant_t<F16, 64, 8>(dequant, lay, state, Hkv, cap, M, gs, sk, sv, st);
+}
+
+int kv_quant_chunk_launch(int dtype, int D, int bits, const QKvLayer &lay, const DecState *state, int Hkv, int cap, int M, int gs, const u16 *ck, const u16 *cv,
+                          int src_cap, hipStream_t st) {
+    if (dtype == PIE_BF16) {
+        if (D == 128) return bits == 4 ? quant_chunk_t<BF16, 128, 4>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st) : quant_chunk_t<BF16, 128, 8>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st);
+        return bits == 4 ? quant_chunk_t<BF16, 64, 4>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st) : quant_chunk_t<BF16, 64, 8>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st);
+    }
+    if (D == 128) return bits == 4 ? quant_chunk_t<F16, 128, 4>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st) : quant_chunk_t<F16, 128, 8>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st);
+    return bits == 4 ? quant_chunk_t<F16, 64, 4>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st) : quant_chunk_t<F16, 64, 8>(lay, state, Hkv, cap, M, gs, ck, cv, src_cap, st);
 }
 
 // ---------------------------------------------------------------- C ABI (op level)

@@ -33,3 +33,6 @@ struct QKvLayer {
 // sk / sv [Hkv, cap, D]; otherwise rows [pos, pos + M) of the scratch -> codes, and their dequantized values back into the scratch.
 int kv_quant_prefill_launch(int dtype, int D, int bits, bool dequant, const QKvLayer &lay, const DecState *state, int Hkv, int cap, int M, int gs,
                             u16 *sk, u16 *sv, hipStream_t st);
+// PIE_OPT_KVQ_DIRECT: rows [0, M) of the chunk-sized T scratch ck / cv [Hkv, src_cap, D] -> the codes of rows [state->pos, state->pos + M) of the layer.
+int kv_quant_chunk_launch(int dtype, int D, int bits, const QKvLayer &lay, const DecState *state, int Hkv, int cap, int M, int gs, const u16 *ck, const u16 *cv,
+                          int src_cap, hipStream_t st);

@@ -23,6 +23,7 @@
 #include "paged_attn_verify.hpp"
 #include "prefill_attn_i8.hpp"
 #include "prefill_attn_paged.hpp"
+#include "prefill_attn_quant.hpp"
 #include "speculative.hpp"
 
 // ---------------------------------------------------------------- kernels
@@ -372,7 +373,7 @@ struct PrefillScratch {
     unsigned batch_gen = 0, warm_gen = 0;
     void *w4l_ws = nullptr;   // fp32 partial tiles of the K-split prompt GEMM (w4m_gemm.hip)
     size_t w4l_ws_bytes = 0;
-    void *chunk_ws = nullptr;  // fp32 split-KV partials of the chunks of a mixed pass (prefill_attn_paged.hip; PIE_OPT_CHUNK_BATCHED): the largest pass seen
+    void *chunk_ws = nullptr;  // fp32 split-KV partials of the chunks of a mixed pass (prefill_attn_paged.hip; PIE_OPT_CHUNK_BATCHED) or of a prompt chunk on the quantized cache (prefill_attn_quant.hip; PIE_OPT_KVQ_DIRECT): the largest pass seen
     size_t chunk_ws_bytes = 0;
     int resident_mode = -1;   // -1: budget not fixed yet
     size_t resident_left = 0; // bytes still available for resident copies
@@ -728,20 +729,36 @@ static int for_dtype(int dtype, F &&f) {
 }
 
 // Quantized KV (pie_decoder_set_kv_quant): the T scratch of one layer's K and V at the cache's capacity and the table that points every layer at it.
-static int kvq_scratch_reserve(pie_decoder *d) {
+// chunk_rows > 0 (PIE_OPT_KVQ_DIRECT): the scratch holds the chunk's own rows only -- any capacity of at least chunk_rows serves, with kvq_rows
+// (pos 0, that capacity) as the append's state -- instead of the prefix and the chunk at the cache's capacity.
+static int kvq_scratch_reserve(pie_decoder *d, int chunk_rows = 0) {
     const pie_decoder_config &c = d->cfg;
     if (!d->kvq_table) {
         PIE_HIP_TRY(hipMalloc((void **)&d->kvq_table, sizeof(unsigned long long) * 2 * c.n_layers));
     }
-    if (d->kvq_scratch_cap == d->kv_cap && d->kvq_scratch) return PIE_OK;  // (rows are kv_cap apart: the layout follows the cache's capacity)
-    if (d->kvq_scratch) (void)hipFree(d->kvq_scratch);
-    d->kvq_scratch = nullptr, d->kvq_scratch_cap = 0;
-    const size_t half = (size_t)c.n_kv_heads * d->kv_cap * c.head_dim;
-    PIE_HIP_TRY(hipMalloc((void **)&d->kvq_scratch, 2 * half * 2));
-    d->kvq_scratch_cap = d->kv_cap;
-    std::vector<unsigned long long> tab(2 * (size_t)c.n_layers);
-    for (int i = 0; i < c.n_layers; ++i) tab[i] = (unsigned long long)(uintptr_t)d->kvq_scratch, tab[c.n_layers + i] = tab[i] + half * 2;
-    PIE_HIP_TRY(hipMemcpy(d->kvq_table, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    bool rows_stale = false;  // kvq_rows is written only when it is new or the scratch behind it moved (hipFree has synchronised the device then)
+    if (chunk_rows > 0 && !d->kvq_rows) {
+        PIE_HIP_TRY(hipMalloc((void **)&d->kvq_rows, sizeof(DecState)));
+        rows_stale = true;
+    }
+    const bool fits = chunk_rows > 0 ? d->kvq_scratch_cap >= chunk_rows : d->kvq_scratch_cap == d->kv_cap;  // (rows are kv_cap apart there: the layout follows the cache's capacity)
+    if (!fits || !d->kvq_scratch) {
+        if (d->kvq_scratch) (void)hipFree(d->kvq_scratch);
+        d->kvq_scratch = nullptr, d->kvq_scratch_cap = 0;
+        const int cap = chunk_rows > 0 ? chunk_rows : d->kv_cap;
+        const size_t half = (size_t)c.n_kv_heads * cap * c.head_dim;
+        PIE_HIP_TRY(hipMalloc((void **)&d->kvq_scratch, 2 * half * 2));
+        d->kvq_scratch_cap = cap;
+        std::vector<unsigned long long> tab(2 * (size_t)c.n_layers);
+        for (int i = 0; i < c.n_layers; ++i) tab[i] = (unsigned long long)(uintptr_t)d->kvq_scratch, tab[c.n_layers + i] = tab[i] + half * 2;
+        PIE_HIP_TRY(hipMemcpy(d->kvq_table, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        rows_stale = true;
+    }
+    if (d->kvq_rows && rows_stale) {
+        DecState rows = {};
+        rows.cap = d->kvq_scratch_cap;
+        PIE_HIP_TRY(hipMemcpy(d->kvq_rows, &rows, sizeof(rows), hipMemcpyHostToDevice));
+    }
     return PIE_OK;
 }
 
@@ -779,14 +796,42 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
     if (rc) return rc;
     PrefillScratch *s = d->prefill;
     // quantized KV: the pass runs on the T scratch (kv_table below), the layer's codes are expanded into it and the chunk's rows quantized back
-    if (d->kv_quant && (rc = kvq_scratch_reserve(d))) return rc;
+    // PIE_OPT_KVQ_DIRECT: no prefix is expanded -- the scratch holds the chunk's rows alone, they are quantized into the codes and
+    // the chunk attends the codes (prefill_attn_quant.hip).  Its split count comes from the cache's capacity (the position is the device's), and
+    // the partials' workspace is grown here, before the pass launches anything.
+    const bool direct = d->kv_quant && d->kvq_direct;
+    if (d->kv_quant && (rc = kvq_scratch_reserve(d, direct ? chunk : 0))) return rc;
+    // the rule at the chunk's offset as the host knows it (pos_hint + the rows before the chunk: exact behind steps and prompts, an upper bound
+    // behind a speculative pass), never beyond what the capacity leaves; unknown: the capacity.  The kernel is right for any count: a split
+    // behind a tile's keys exits, and the merge counts the same active ones from the device's position.
+    auto direct_splits = [&](int c0, int M) {
+        const long long room = d->kv_cap > M ? d->kv_cap - M : 0, at = d->pos_hint >= 0 ? d->pos_hint + c0 : room;
+        return prefill_attn_quant_splits(M, (int)(at < room ? at : room), c.n_heads, c.n_kv_heads);
+    };
+    if (direct) {
+        PIE_REQUIRE(L <= d->kv_cap, PIE_E_SHAPE, "pie_decoder_prefill: the quantized cache's buffers do not hold the rows");
+        size_t need = 0;
+        for (int c0 = 0; c0 < L; c0 += chunk) {
+            const int M = L - c0 < chunk ? L - c0 : chunk;
+            need = std::max(need, prefill_attn_quant_workspace_bytes(M, c.n_heads, D, direct_splits(c0, M)));
+        }
+        if (need > s->chunk_ws_bytes) {
+            if (s->chunk_ws) (void)hipFree(s->chunk_ws);
+            s->chunk_ws = nullptr, s->chunk_ws_bytes = 0;
+            PIE_HIP_TRY(hipMalloc(&s->chunk_ws, need));
+            s->chunk_ws_bytes = need;
+        }
+    }
     unsigned long long *const kv_table = d->kv_quant ? d->kvq_table : d->kv_table;
     u16 *const sk = d->kvq_scratch, *const sv = d->kvq_scratch ? d->kvq_scratch + (size_t)c.n_kv_heads * d->kvq_scratch_cap * D : nullptr;
-    auto kvq_rows = [&](bool expand, int li, int M) {  // the layer's codes into the scratch / the chunk's M rows quantized back; nothing without quantized KV
-        if (!d->kv_quant) return (int)PIE_OK;
+    auto kvq_layer = [&](int li) {
         const void *const *p = &d->kvq_host[(size_t)6 * li];
-        const QKvLayer q = {(const u32 *)p[0], (const u16 *)p[1], (const u16 *)p[2], (const u32 *)p[3], (const u16 *)p[4], (const u16 *)p[5]};
-        return kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, expand, q, d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st);
+        return QKvLayer{(const u32 *)p[0], (const u16 *)p[1], (const u16 *)p[2], (const u32 *)p[3], (const u16 *)p[4], (const u16 *)p[5]};
+    };
+    auto kvq_rows = [&](bool expand, int li, int M) {  // the layer's codes into the scratch / the chunk's M rows quantized back; nothing without quantized KV
+        if (!d->kv_quant || (direct && expand)) return (int)PIE_OK;
+        if (direct) return kv_quant_chunk_launch(c.dtype, D, d->kvq_bits, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, d->kvq_scratch_cap, st);
+        return kv_quant_prefill_launch(c.dtype, D, d->kvq_bits, expand, kvq_layer(li), d->state, c.n_kv_heads, d->kv_cap, M, d->kvq_gs, sk, sv, st);
     };
     // RotatingKVCache: the chunk's K / V rows go to rows ring_rows->pos + m of the buffers (the retained window in temporal order, then the
     // update: cache/kv_cache/rotating.py), RoPE stays at the absolute position state->pos + m; the attention is windowed
@@ -798,7 +843,7 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
     }
     const bool mfma_attn = d->ring || pie_knob(PIE_KNOB_PREFILL_ATTN_VALU) != 1;  // 1 forces the row-per-launch-slice VALU kernel (tests compare the two)
     RowsKv kv;  // one sequence: rows at kvs->pos + m of the table's buffers, or of the pages of the decoder's one block table
-    kv.state = kvs, kv.kv_table = kv_table, kv.block_tables = d->block_table, kv.n_pages = d->n_pages, kv.gemm_rope = true;
+    kv.state = direct ? d->kvq_rows : kvs, kv.kv_table = kv_table, kv.block_tables = d->block_table, kv.n_pages = d->n_pages, kv.gemm_rope = true;
     for (int c0 = 0; c0 < L; c0 += chunk) {
         const int M = L - c0 < chunk ? L - c0 : chunk;
         // h = embed_tokens(inputs)  (language.py:176)
@@ -814,7 +859,14 @@ static int prefill_t(pie_decoder *d, const int32_t *ids, const void *embeds, int
             // input_layernorm: layer 0 here; for the later layers it was fused with the previous block's residual add
             if (li == 0 && (rc = pie_rms_norm(s->x, w.attn_norm, c.rms_eps, M, H, c.dtype, s->xn, st))) return rc;
             if ((rc = kvq_rows(true, li, M)) || (rc = qkv_rope_rows<T>(d, w, li, M, kv, st)) || (rc = kvq_rows(false, li, M))) return rc;
-            if (mfma_attn) {  // causal flash attention on the MFMA units (prefill_attn.hpp)
+            if (direct) {  // the chunk attends the codes, its own rows' included (prefill_attn_quant.hip)
+                PrefillQuantArgs qa = {};
+                qa.q = s->q, qa.kv = kvq_layer(li), qa.state = d->state, qa.cap = d->kv_cap, qa.gs = d->kvq_gs;
+                qa.M = M, qa.Hq = c.n_heads, qa.Hkv = c.n_kv_heads, qa.scale = 1.0f / sqrtf((float)D), qa.out = s->attn;
+                qa.splits = direct_splits(c0, M);
+                qa.part_acc = (float *)s->chunk_ws, qa.part_ml = qa.part_acc + (size_t)M * c.n_heads * qa.splits * D;
+                if ((rc = prefill_attn_quant_launch(c.dtype, D, d->kvq_bits, qa, st))) return rc;
+            } else if (mfma_attn) {  // causal flash attention on the MFMA units (prefill_attn.hpp)
                 PrefillAttnArgs pa = {};
                 pa.q = s->q, pa.kv_table = kv_table, pa.layer = li, pa.n_layers = c.n_layers, pa.state = kvs, pa.window = d->ring ? d->ring_w : 0;
                 pa.block_table = d->block_table, pa.n_pages = d->n_pages;

@@ -1083,7 +1083,10 @@ static int spec_step(const char *entry, SpecKind kind, pie_decoder *d, const int
     const bool with_tail = kind != SPEC_RAW;
     PIE_REQUIRE(d && draft_ids && out_tokens && out_n && (logprobs_rows || !with_tail) && workspace, PIE_E_ARG, who + "null pointer");
     PIE_REQUIRE(!d->tp(), PIE_E_STATE, who + "not available on a tensor-parallel shard");
-    PIE_REQUIRE(!d->kv_quant && !d->ring, PIE_E_STATE, who + "not available on a quantized or rotating KV cache");
+    // PIE_OPT_KVQ_DIRECT: the greedy and the configured-tail pass verify on the quantized cache's codes; rejected rows stay as
+    // codes behind the offset and are overwritten, as T rows are
+    const bool kvq_admitted = d->kvq_direct && (kind == SPEC_RAW || kind == SPEC_TAIL);
+    PIE_REQUIRE((!d->kv_quant || kvq_admitted) && !d->ring, PIE_E_STATE, who + "not available on a quantized or rotating KV cache");
     PIE_REQUIRE(!d->kv_i8, PIE_E_STATE, who + "not available on int8 KV pages");
     const StepTail &t = d->tail;
     if (!with_tail) {

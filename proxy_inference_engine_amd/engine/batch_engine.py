@@ -611,7 +611,8 @@ class BatchedEngine:
             for bad, name in ((sampler is not None, "a `sampler` callable"), (kv_dtype == torch.int8 and not getattr(speculative, "int8_pages", False), "kv_dtype=torch.int8 (int8 KV pages)"),
                               (getattr(model, "tp", None) is not None, "a tensor-parallel model"), (int(speculative.num_draft) > SPEC_SEG_DRAFTS, "num_draft > 7"),
                               (speculative.draft_model is not None, "draft_model"), (bool(speculative.grammar), "grammar"),
-                              (bool(speculative.configured_tail), "configured_tail")):
+                              (bool(speculative.configured_tail), "configured_tail"),
+                              (bool(getattr(speculative, "quantized_kv", False)), "quantized_kv (the single sequence's quantized cache; the batch runs on KV pages)")):
                 if bad:
                     raise ValueError(who + "not available with " + name)
         self.speculative = speculative

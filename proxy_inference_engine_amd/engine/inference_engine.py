@@ -145,6 +145,10 @@ class SpeculativeParams:
     mfma_verify: True -- BatchedEngine's passes on a 16-bit pool attend through the MFMA verify kernel
     (Model.spec_step_batch(..., mfma_verify=True)); the tokens are the same.  False -- the VALU kernel, as ever.  On an int8 pool the flag
     does nothing.  InferenceEngine, whose passes do not use this kernel, refuses mfma_verify=True by name.
+    quantized_kv: True -- generate_step(kv_bits=..., speculative=...) is admitted on the greedy and the configured_tail
+    path: the request's many-row passes attend the quantized cache's codes directly (generate_step's kv_direct_attn), which is what
+    lets a verify pass run there at all; the tokens are those of the same call without `speculative`.  False -- kv_bits is refused,
+    as ever.  BatchedEngine (KV pages), draft_model and grammar=True refuse the flag by name.
     draft_model: None -- prompt-lookup drafts, as above.  A built `Model` of the target's vocabulary, or a checkpoint
     path (loaded once and kept on the engine) -- every round the draft model runs num_draft of its own replayed steps (num_draft =
     the target's spec_min_rows - 1 .. 31, so that the pass keeps its many-row form) and the target verifies them in one pass.  A greedy
@@ -168,6 +172,7 @@ class SpeculativeParams:
     batch_tail: bool = field(default=False, kw_only=True)   # (keyword-only: the positional order of the fields around it stays as it was)
     int8_pages: bool = field(default=False, kw_only=True)
     mfma_verify: bool = field(default=False, kw_only=True)
+    quantized_kv: bool = field(default=False, kw_only=True)
     draft_model: object = None
     grammar: bool = False
 
@@ -192,6 +197,12 @@ class SpeculativeParams:
             raise ValueError("SpeculativeParams: int8_pages is a bool")
         if not isinstance(self.mfma_verify, bool):
             raise ValueError("SpeculativeParams: mfma_verify is a bool")
+        if not isinstance(self.quantized_kv, bool):
+            raise ValueError("SpeculativeParams: quantized_kv is a bool")
+        if self.quantized_kv and self.draft_model is not None:
+            raise ValueError("SpeculativeParams: quantized_kv is not available with a draft model")
+        if self.quantized_kv and self.grammar:
+            raise ValueError("SpeculativeParams: quantized_kv is not available with grammar")
         if self.grammar and self.draft_model is not None:
             raise ValueError("SpeculativeParams: grammar is not available with a draft model")
 
@@ -436,13 +447,15 @@ class InferenceEngine:
     def generate_step(self, prompt_ids, pixel_values=None, mask=None, kv_bits: int | None = None, kv_group_size: int = 64,
                       quantized_kv_start: int = 0, max_kv_size: int | None = None,
                       top_logprobs: int | None = None, prompt_logprobs: int | None = None,
-                      speculative: SpeculativeParams | None = None) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
+                      speculative: SpeculativeParams | None = None, kv_direct_attn: bool = False) -> Iterator[tuple[torch.Tensor, torch.Tensor]]:
         """Yields (next_token_id[1] int32, logprobs[V] fp32) per step, forever (inference_engine.py:228-297).
         Prefill of the non-cached prompt suffix, then one forward per token; all device work is queued
         asynchronously, the consumer synchronises when it reads a token (generate() does, like `.tolist()` :202).
         kv_bits (4 / 8; None = 16-bit KV), kv_group_size, quantized_kv_start: mlx_lm's KV quantization -- before a model call the
         prompt cache's layers become QuantizedKVCache once they hold more than quantized_kv_start positions (BaseCache.maybe_quantize,
-        cache/kv_cache/__init__.py:240-266).
+        cache/kv_cache/__init__.py:240-266).  kv_direct_attn (default False: the dequantize-to-T scratch): the request's
+        many-row passes on the quantized cache attend its codes directly (Model.set_kv_direct_attn); it travels with the other three
+        to where the cache is converted and bound.  SpeculativeParams(quantized_kv=True) sets it and admits kv_bits under `speculative`.
         max_kv_size (mlx_lm's name): the prompt cache becomes RotatingKVCache(max_kv_size, keep=4) per layer -- memory and step cost
         bounded by the window; kv_bits then has no effect (a rotating cache stays 16-bit, as in the reference).  A prompt cache of
         another kind or size is replaced by fresh rings (and back to the model's own caches when max_kv_size is None).
@@ -468,9 +481,12 @@ class InferenceEngine:
         if "root" not in self.samplers:
             self.prepare_engine(prompt_ids, temp=0)
         spec_plan = None
+        spec_quant = speculative is not None and getattr(speculative, "quantized_kv", False)  # (its checks see no kv_bits: the passes run on the codes)
+        kv_quant = None if kv_bits is None else (quantized_kv_start, kv_group_size, kv_bits, bool(kv_direct_attn) or spec_quant)
         if speculative is not None:
             spec_plan = _speculative_request_plan(self.model, None if speculative.draft_model is None else self._draft_model(speculative), speculative,
-                                                  self.samplers, self.logits_processors, self.structuring_engine, pixel_values, kv_bits, max_kv_size)
+                                                  self.samplers, self.logits_processors, self.structuring_engine, pixel_values,
+                                                  None if spec_quant else kv_bits, max_kv_size)
         self._select_prompt_cache(prompt_ids, max_kv_size, scored)
         todo = self.prompt_cache(prompt_ids)                                   # :277
         host_ids = [int(t) for t in (todo.tolist() if isinstance(todo, torch.Tensor) else todo)]
@@ -478,10 +494,10 @@ class InferenceEngine:
             yield from self._speculative_draft_steps([int(t) for t in prompt_ids], host_ids, speculative, top_logprobs, spec_plan)
             return
         if speculative is not None:
-            yield from self._speculative_steps(host_ids, speculative, top_logprobs, spec_plan)
+            yield from self._speculative_steps(host_ids, speculative, top_logprobs, spec_plan, kv_quant if spec_quant else None)
             return
         # what every step of this request is called with; host_top: [(ids, vals), workspace] of the host-orchestrated branches' top-n record
-        request = dict(pixel_values=pixel_values, kv_quant=None if kv_bits is None else (quantized_kv_start, kv_group_size, kv_bits),
+        request = dict(pixel_values=pixel_values, kv_quant=kv_quant,
                        top_logprobs=top_logprobs, count_start=len(prompt_ids), host_top=[])
         if scored and len(host_ids) > 1:
             lm = getattr(self.model, "language_model", self.model)
@@ -679,7 +695,7 @@ class InferenceEngine:
         self.spec_stats["drafted"] += drafted
         self.spec_stats["accepted"] += n - 1
 
-    def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None, plan: dict | None = None):
+    def _speculative_steps(self, host_ids: list[int], sp: SpeculativeParams, top_logprobs: int | None, plan: dict | None = None, kv_quant: tuple | None = None):
         """generate_step's loop under speculative decoding.  The prompt's suffix is one plain step; behind it, and behind every
         later step or pass, ONE drafter launch is queued, and its count comes back in the read-back the loop pays anyway: the tokens
         (Model.spec_read).  count >= min_draft (and enough rows for the many-row pass): a verify pass over count + 1 rows, whose accepted
@@ -690,8 +706,12 @@ class InferenceEngine:
         token j of the generation is draw j of the seed whichever produced it.
         A plan that holds an automaton (check_speculative_grammar's): the drafter's launch is followed by the grammar's, the
         passes are Model.spec_step_grammar and the steps the ordinary step under the automaton.  The automaton's state is followed on the
-        host from the tokens the loop reads anyway, only to count the forced ids of a draft: nothing more is read back."""
+        host from the tokens the loop reads anyway, only to count the forced ids of a draft: nothing more is read back.
+        kv_quant (SpeculativeParams(quantized_kv=True)): the request's (quantized_kv_start, kv_group_size, kv_bits, True) --
+        before every model call the prompt cache's layers are converted as in _inference, and the passes then verify on the codes."""
         model, cache = self.model, self.prompt_cache.cache
+        quantize = (lambda: None) if kv_quant is None else partial(self._maybe_quantize, *kv_quant)
+        quantize()
         automaton = None if plan is None or plan.get("automaton") is None else plan["automaton"].automaton
         spec_pass = model.spec_step if plan is None else model.spec_step_tail if automaton is None else model.spec_step_grammar
         drafter = (int(sp.ngram_max), int(sp.ngram_min), int(sp.num_draft)) + (() if automaton is None else (True,))
@@ -706,6 +726,7 @@ class InferenceEngine:
             fed = tokens[-1]
             if automaton is not None:
                 state = automaton.walk(tokens, state)  # the device-side state the draft started from
+            quantize()
             if count >= floor:
                 if automaton is not None:
                     self.spec_stats["forced"] += _forced_ids(automaton, state, model.spec_read_draft())
@@ -786,9 +807,15 @@ class InferenceEngine:
         step.close()
         return self.prompt_logprobs
 
-    def _maybe_quantize(self, quantized_start: int, group_size: int, bits: int) -> None:
-        """BaseCache.maybe_quantize (cache/kv_cache/__init__.py:240-266) on the prompt cache's layers."""
+    def _maybe_quantize(self, quantized_start: int, group_size: int, bits: int, direct_attn: bool = False) -> None:
+        """BaseCache.maybe_quantize (cache/kv_cache/__init__.py:240-266) on the prompt cache's layers; direct_attn: the request's
+        kv_direct_attn, handed to the model the cache is about to be bound to (Model.set_kv_direct_attn)."""
         cache = self.prompt_cache.cache
+        lm = getattr(self.model, "language_model", self.model)
+        if hasattr(lm, "set_kv_direct_attn"):
+            lm.set_kv_direct_attn(direct_attn)
+        elif direct_attn:
+            raise ValueError("kv_direct_attn is not available with this model (no set_kv_direct_attn)")
         if cache and isinstance(cache[0], PagedKVCache):
             raise ValueError("kv_bits: the quantized KV cache runs on contiguous caches, not on KV pages")
         if cache and isinstance(cache[0], ReusableKVCache) and cache[0].offset > quantized_start:
@@ -806,7 +833,7 @@ class InferenceEngine:
         logprobs_map: dict[int, float] = {}
         stop_reason = "stop"
         token_count = 0
-        kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start", "max_kv_size") if inference_kwargs.get(k) is not None}
+        kv = {k: inference_kwargs[k] for k in ("kv_bits", "kv_group_size", "quantized_kv_start", "max_kv_size", "kv_direct_attn") if inference_kwargs.get(k) is not None}
         if collect_logprobs:
             kv["top_logprobs"] = top_logprobs
         if inference_kwargs.get("prompt_logprobs") is not None:  # the prompt's maps are on `self.prompt_logprobs` before the first yield

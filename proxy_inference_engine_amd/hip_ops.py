@@ -340,6 +340,39 @@ def attn_decode_quant(q: torch.Tensor, k: tuple, v: tuple, scale: float, group_s
     return out.reshape(shape)
 
 
+def prefill_attn_quant(q: torch.Tensor, k: tuple, v: tuple, scale: float, offset: int, group_size: int = 64, bits: int = 8, splits: int = 0) -> torch.Tensor:
+    """Causal attention of M query rows at positions offset .. offset + M - 1 straight from a quantized KV cache (pie_prefill_attn_quant;
+    DESIGN.md 31): q [M, Hq, D] T, k / v the (codes, scales, biases) triples attn_decode_quant takes, which already hold the rows' own K / V;
+    row r attends rows 0 .. offset + r.  splits: 0 = pie_prefill_attn_quant_splits, else 1..32; with 1 the rows are bit for bit
+    sdpa_prefill's over the dequantized cache.  Returns [M, Hq, D]."""
+    kk = [t.reshape(-1, t.shape[-2], t.shape[-1]) for t in k]
+    vv = [t.reshape(-1, t.shape[-2], t.shape[-1]) for t in v]
+    for t in (q, *kk, *vv):
+        _dev(t)
+    if q.dim() != 3:
+        raise ValueError("prefill_attn_quant: q [M, Hq, D]")
+    M, Hq, D = q.shape
+    Hkv, cap = kk[0].shape[0], kk[0].shape[1]
+    if bits not in (4, 8) or group_size not in (32, 64, 128) or D % group_size:
+        raise ValueError(f"prefill_attn_quant: bits 4 / 8 and group_size 32 / 64 / 128 dividing head_dim ({D}) only; got bits={bits}, group_size={group_size}")
+    for trip, what in ((kk, "k"), (vv, "v")):
+        c, sc, bi = trip
+        if c.shape != (Hkv, cap, D * bits // 32) or sc.shape != (Hkv, cap, D // group_size) or bi.shape != sc.shape:
+            raise ValueError(f"prefill_attn_quant: {what} triple {[tuple(t.shape) for t in trip]} does not match {Hkv} kv-heads x {cap} positions, "
+                             f"head_dim {D}, bits {bits}, group_size {group_size}")
+        if c.element_size() != 4 or sc.dtype != q.dtype or bi.dtype != q.dtype:
+            raise ValueError(f"prefill_attn_quant: {what} codes must be 32-bit words, scales / biases of q's dtype")
+    if not 0 <= int(splits) <= 32:
+        raise ValueError("prefill_attn_quant: splits is 0 (chosen by the library) or 1..32")
+    lib = _ffi.load()
+    used = int(splits) or int(lib.pie_prefill_attn_quant_splits(M, int(offset), Hq, Hkv))
+    ws = torch.empty(max(int(lib.pie_prefill_attn_quant_workspace_bytes(M, Hq, D, used)), 16), dtype=torch.uint8, device=q.device)
+    out = torch.empty_like(q)
+    _ffi.check(lib.pie_prefill_attn_quant(_ffi.p(q), *(_ffi.p(t) for t in kk), *(_ffi.p(t) for t in vv), Hq, Hkv, M, int(offset), cap, D, group_size, bits,
+                                          float(scale), _ffi.dtype_code(q.dtype), used, _ffi.p(out), _ffi.p(ws), _ffi.stream()))
+    return out
+
+
 def paged_kv_append(k: torch.Tensor, v: torch.Tensor, slab: torch.Tensor, n_pages: int, block_table: torch.Tensor,
                     positions: torch.Tensor) -> None:
     """Stores the new K / V rows [B, Hkv, D] of B sequences in their pages (sequence s at positions[s]; < 0 = idle).

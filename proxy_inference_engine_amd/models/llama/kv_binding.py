@@ -124,6 +124,7 @@ class KVBinding:
         self._i8 = None      # the decoder's page format (PIE_OPT_KV_I8); None until a pool was seen
         self._verify_mfma = False   # the decoder's PIE_OPT_VERIFY_MFMA as last set here (its default: off)
         self._chunk_batched = False  # ... and its PIE_OPT_CHUNK_BATCHED
+        self._kvq_direct = False     # ... and its PIE_OPT_KVQ_DIRECT
 
     def sync(self, cache, n_new: int) -> None:
         """Room for `n_new` more rows in every layer, then the decoder bound to them; all layers are checked before the first allocation."""
@@ -171,6 +172,13 @@ class KVBinding:
         if self._chunk_batched != bool(batched):
             _ffi.check(self.lib.pie_decoder_configure(self.dec, _ffi.PIE_OPT_CHUNK_BATCHED, int(bool(batched))))
             self._chunk_batched = bool(batched)
+
+    def match_quant_attention(self, direct: bool) -> None:
+        """The many-row pass on a quantized cache (PIE_OPT_KVQ_DIRECT): attends the codes directly instead of a dequantized
+        scratch, which also admits the speculative passes; configured only when it changes."""
+        if self._kvq_direct != bool(direct):
+            _ffi.check(self.lib.pie_decoder_configure(self.dec, _ffi.PIE_OPT_KVQ_DIRECT, int(bool(direct))))
+            self._kvq_direct = bool(direct)
 
     def pool_args(self, allocator):
         """(per-layer slab planes, pages, bytes of one plane) as the paged entry points take them, the decoder set to the pool's format."""

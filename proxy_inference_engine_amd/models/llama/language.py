@@ -22,7 +22,7 @@ import torch
 
 from .. import base
 from ... import _ffi, hip_ops
-from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, ReusableKVCache
+from ...cache.kv_cache import BaseCache, PageAllocator, PagedKVCache, PagedSequence, QuantizedKVCache, ReusableKVCache
 from .kv_binding import KVBinding, on_int8_pages
 from .rows_state import RowsTailState
 from .step_state import StepTailState
@@ -554,17 +554,25 @@ class Model(RowsTailState, StepTailState):
         n = int(h[self._SPEC_N])
         return [int(t) for t in h[self._SPEC_TOK:self._SPEC_TOK + n]], int(h[self._SPEC_COUNT])
 
+    def set_kv_direct_attn(self, on: bool) -> None:
+        """PIE_OPT_KVQ_DIRECT: while on, a many-row pass on a QuantizedKVCache attends the codes directly
+        (pie_prefill_attn_quant's kernel) instead of a dequantized scratch, and spec_step / spec_step_tail admit such a cache.  Off: the
+        scratch path, as ever.  Nothing else changes."""
+        self._kv.match_quant_attention(on)
+
     def _check_speculative(self, who: str, cache) -> None:
-        self._check_speculative_kv(who, cache)
+        self._check_speculative_kv(who, cache, quant_ok=True)
         if not self._step_tail_plain:
             raise ValueError(f"{who}: speculation is greedy and raw -- set_step_tail() with its defaults first "
                              "(no sampler, repetition penalty, token mask, logit bias, top_logprobs or frequency / presence penalty)")
 
-    def _check_speculative_kv(self, who: str, cache) -> None:
+    def _check_speculative_kv(self, who: str, cache, quant_ok: bool = False) -> None:
         if self.tp is not None:
             raise ValueError(f"{who}: not available on a tensor-parallel model")
         if on_int8_pages(cache):
             raise ValueError(f"{who}: not available on int8 KV pages")
+        if quant_ok and self._kv._kvq_direct and isinstance(cache[0], QuantizedKVCache):
+            return  # (set_kv_direct_attn(True): the greedy and the configured-tail pass verify on the codes)
         if not isinstance(cache[0], (ReusableKVCache, PagedKVCache)):
             raise ValueError(f"{who}: runs on ReusableKVCache or 16-bit PagedKVCache, not on {type(cache[0]).__name__}")
 
@@ -650,7 +658,7 @@ class Model(RowsTailState, StepTailState):
         where n calls of step(None) under the same tail would have left them.  A token mask, a token automaton, top_logprobs, frequency / presence
         penalties and DRY are refused by name, like tensor-parallel models, int8 pages and the other cache kinds."""
         who = "spec_step_tail"
-        self._check_speculative_kv(who, cache)
+        self._check_speculative_kv(who, cache, quant_ok=True)
         self._refuse(who, ((self._edits[0], "a token mask"), (self._dfa is not None, "a token automaton"), *self._spec_refused_rows()))
         if self._tail[:2] == (None, None) and self._edits[1] == 0:
             raise ValueError(f"{who}: no sampler, repetition penalty or logit bias is set -- the greedy and raw pass is spec_step")
